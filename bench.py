@@ -2,22 +2,30 @@
 """bench.py -- G-VOM hot path (process_pointcloud -> combine_maps) on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config m256|c1|c2|c3|m256b8|c4|c5]
+                    [--dump-outputs DIR] [--full]
 
 A "step" is one pass of the hot path over one synthetic lidar scan: process_pointcloud
 (transform / hit / DDA trace, encode) followed by combine_maps (temporal fusion + column
 reductions + 2-D maps + the four returned maps landing in host memory).  Metric: M points/s
 (whole job), with end-to-end map Hz beside it.
 
-`value` is measured with the cloud already resident in HBM (the driver's contract).  The same
-steps through the reference's own calling conventions are reported beside it, never as `value`:
-`value_host_f32` (host numpy in, gvom.py:110) and `value_ros_f64_tf` (what an unchanged
+`value` is measured with the cloud already resident in HBM (the driver's contract).  With --full
+the same steps through the reference's own calling conventions are reported beside it, never as
+`value`: `value_host_f32` (host numpy in, gvom.py:110) and `value_ros_f64_tf` (what an unchanged
 gvom_ros.py:106-109 hands over: a float64 host array + a 4x4 transform).
 
 N = 1 runs the headline configuration of BASELINE.json's metric: the 256^3 voxel grid at 0.2 m
 with the OS1-64-shaped 131,072-point scan (BASELINE.md row "M"), cycling 8 sensor poses that
-move 0.2 m per scan (the window shifts).  Whatever --steps says, timed blocks of K steps are
-repeated until >= 0.5 s has been timed; `ms_per_step` is the MEDIAN block.  Short runs of the
-other single-GPU BASELINE configs ride along under `configs`.
+move 0.2 m per scan (the window shifts).  W warm-up steps, then exactly K timed steps in one
+block; `ms_per_step` = that block / K.  The inputs are seeded: the same arguments give the same
+steps.  --dump-outputs DIR writes what the last timed step returned (combine_maps' origin and
+four maps) as DIR/<name>.npy in float64.
+
+A plain run does only that.  --full adds everything else the line used to carry: the other
+calling conventions, per-kernel HIP-event times and the roofline, the spread of repeated
+blocks, the statistics path, short runs of the other single-GPU BASELINE configs under
+`configs`, the paced c5 stream and the CPU baseline (--no-cpu / --no-extra / --no-big trim it).
+--offered-hz H adds its paced stream in either mode.
 
 N > 1 runs one map sharded over N GPUs (g-vom_amd/gvom_sharded.py): one rank per GPU, every
 rank its own sensor (weak scaling: per-GPU point count fixed), RCCL over xGMI called from
@@ -25,9 +33,12 @@ libgvom_hip.so.  Started without a launcher (`python bench.py --gpus N`) this pr
 spawns the N ranks -- it never touches the GPU itself -- and relays rank 0's JSON line; under
 torchrun (RANK / WORLD_SIZE / MASTER_* in the environment) it is one of the ranks.
 
-Rank 0 prints ONE JSON line with `roofline` (dominant kernel, HIP-event timed on the library's
-own stream) and `cpu_baseline` (the CPU oracle, a "port" of the reference's algorithm: one thread
-and all host cores, on a bounded sample of the same workload).
+The N > 1 leg also times exactly K steps; it always carries its own verification against an
+unsharded mapper, with or without --full, and has no --dump-outputs.
+
+Rank 0 prints ONE JSON line; with --full it holds `roofline` (dominant kernel, HIP-event timed on
+the library's own stream) and `cpu_baseline` (the CPU oracle, a "port" of the reference's
+algorithm: one thread and all host cores, on a bounded sample of the same workload).
 """
 import argparse
 import ctypes
@@ -300,6 +311,41 @@ def timed_blocks(step, k0, steps, min_s=MIN_TIMED_S, max_blocks=400):
     return blocks, k
 
 
+def timed_steps(step, k0, steps):
+    """Exactly `steps` steps in one timed block; returns (seconds, what the last step returned, next k).  Only the last step's
+    result is kept: an earlier one held across the next call would make combine_maps allocate a second output buffer."""
+    import gc
+    gc.collect(); gc.disable()
+    try:
+        t0 = time.perf_counter()
+        for k in range(k0, k0 + steps - 1):
+            step(k)
+        last = step(k0 + steps - 1)
+        dt = time.perf_counter() - t0
+    finally:
+        gc.enable()
+    return dt, last, k0 + steps
+
+
+MAP_NAMES = ("origin", "positive", "negative", "roughness", "visibility")
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(directory, maps):
+    """--dump-outputs: combine_maps()'s return of the last timed step (origin f64[3]; positive, negative, visibility int32[x, y];
+    roughness f64[x, y]) as DIR/<name>.npy, all float64 (exact for the int32 maps), in the [x, y] indexing the caller gets."""
+    import numpy as np
+    if maps is None:
+        raise RuntimeError("--dump-outputs: the last timed step returned no maps")
+    arrays = {name: np.ascontiguousarray(a, dtype=np.float64) for name, a in zip(MAP_NAMES, maps)}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError("--dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
+
+
 def stage_samples(g, step, k0, n=40):
     """HIP-event times of the kernels (events on the library's own stream) of n steps, outside the
     timed blocks: a sampled step is ~80 us longer (event records + a stream sync)."""
@@ -317,9 +363,10 @@ def stage_samples(g, step, k0, n=40):
             for s, v in acc.items()}
 
 
-def run_config(hip, name, steps, warmup, poses, full):
-    """One BASELINE configuration on one GPU.  full: headline treatment (all calling conventions, the
-    occupancy API, roofline accounting); otherwise a short device-resident run."""
+def run_config(hip, name, steps, warmup, poses, full, headline=False, dump_dir=None):
+    """One BASELINE configuration on one GPU.  headline: exactly `steps` timed steps in one block (dump_dir: their last
+    maps go there); otherwise blocks of `steps` steps for >= 0.1 s (the short ride-along runs of --full).  full: the
+    headline's --full treatment (all calling conventions, the occupancy API, roofline accounting) after its timed steps."""
     import numpy as np
     import gvom
     import synth
@@ -338,13 +385,27 @@ def run_config(hip, name, steps, warmup, poses, full):
 
     for k in range(warmup):
         step(k)
-    blocks, k = timed_blocks(step, warmup, steps, MIN_TIMED_S if full else 0.1)
-    med = _median(blocks)
     out = {"workload": synth.CONFIGS[name][2], "points_per_scan": n_pts, "points_per_scan_range": [min(lengths), max(lengths)],
-           "grid": [params[2], params[2], params[3]],
-           "buffer_size": params[4], "poses": len(scans), "steps": steps, "blocks": len(blocks),
-           "ms_per_step": med / steps * 1e3, "ms_per_step_min": min(blocks) / steps * 1e3,
-           "ms_per_step_max": max(blocks) / steps * 1e3, "value": n_pts * steps / med / 1e6, "map_hz": steps / med}
+           "grid": [params[2], params[2], params[3]], "buffer_size": params[4], "poses": len(scans), "steps": steps}
+    if headline:
+        dt, last, k = timed_steps(step, warmup, steps)
+        if dump_dir:
+            dump_outputs(dump_dir, last)
+        del last
+        out.update(ms_per_step=dt / steps * 1e3, value=n_pts * steps / dt / 1e6, map_hz=steps / dt)
+        if not full:
+            out["fast_path"] = {"eager_adopted": g.get_tuning("eager_adopted"), "dirsort": g.get_tuning("dirsort"), "interleave": g.get_tuning("interleave")}
+            del g
+            return out, None
+        # (the spread of repeated blocks of the same size, after the headline's own steps)
+        blocks, k = timed_blocks(step, k, steps, MIN_TIMED_S)
+        out.update(blocks=len(blocks), ms_per_step_block_median=_median(blocks) / steps * 1e3,
+                   ms_per_step_min=min(blocks) / steps * 1e3, ms_per_step_max=max(blocks) / steps * 1e3)
+    else:
+        blocks, k = timed_blocks(step, warmup, steps, 0.1)
+        med = _median(blocks)
+        out.update(blocks=len(blocks), ms_per_step=med / steps * 1e3, ms_per_step_min=min(blocks) / steps * 1e3,
+                   ms_per_step_max=max(blocks) / steps * 1e3, value=n_pts * steps / med / 1e6, map_hz=steps / med)
     stages = stage_samples(g, step, k, 40 if full else 20)
     out["stage_ms"] = {s: v["median"] for s, v in stages.items()}
     if not full:
@@ -352,6 +413,8 @@ def run_config(hip, name, steps, warmup, poses, full):
         del g
         return out, None
     out["stage_ms_spread"] = stages
+    # (c4 / c5 steps take milliseconds: the legs below time blocks of at most 40 of them)
+    steps = min(steps, 40) if name in ("c4", "c5") else steps
 
     # the same steps through the reference's calling conventions (never `value`)
     def step_host(k):
@@ -730,11 +793,8 @@ def run_single(args):
     hip.set_device(0)
     name = args.config
     big = name in ("c4", "c5")
-    poses = 1 if name == "c1" else (min(args.poses, 4) if big else args.poses)
-    steps = min(args.steps, 40) if big else args.steps            # a c5 step is ~3 ms; 4 M-point clouds take a while to generate
-    res, extra = run_config(hip, name, steps, min(args.warmup, 10) if big else args.warmup, poses, True)
-    args.steps = steps
-    alg, stages, params, scans = extra
+    poses = 1 if name == "c1" else (min(args.poses, 4) if big else args.poses)   # 4 M-point clouds take a while to generate
+    res, extra = run_config(hip, name, args.steps, args.warmup, poses, args.full, headline=True, dump_dir=args.dump_outputs)
     out = {
         "metric": metric_for(name, res["grid"]), "value": res["value"], "unit": "M points/s",
         "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": res["ms_per_step"],
@@ -743,10 +803,19 @@ def run_single(args):
                    "grid": res["grid"], "buffer_size": res["buffer_size"], "poses": res["poses"],
                    "pose_motion": "0.2 m per scan in +x (the window shifts every scan)",
                    "input": "device-resident f32 xyz", "step": "1 scan + 1 combine incl. the 4 maps in host memory",
-                   "timing": "median of %d blocks of %d steps (>= %.1f s timed)" % (res["blocks"], args.steps, MIN_TIMED_S),
+                   "timing": "%d steps timed as one block after %d warm-up steps" % (args.steps, args.warmup),
                    "host_affinity": affinity},
-        "map_hz": res["map_hz"],
+        "map_hz": res["map_hz"], "fast_path": res["fast_path"],
+    }
+    if args.offered_hz > 0:
+        out["stream"] = dict(stream_single(name, args.offered_hz, args.ticks, poses), config=name)
+    if not args.full:
+        return out
+    alg, stages, params, scans = extra
+    steps = min(args.steps, 40) if big else args.steps            # (the block size of the --full legs: a c5 step is ~3 ms)
+    out.update({
         "ms_per_step_min": res["ms_per_step_min"], "ms_per_step_max": res["ms_per_step_max"], "blocks": res["blocks"],
+        "ms_per_step_block_median": res["ms_per_step_block_median"],
         "value_host_f32": res["value_host_f32"], "value_ros_f64_tf": res["value_ros_f64_tf"],
         "value_occupancy_api": res["value_occupancy_api"],
         "value_async_combine": res["value_async_combine"], "ms_per_step_async_combine": res["ms_per_step_async_combine"],
@@ -760,7 +829,7 @@ def run_single(args):
         "stage_ms": res["stage_ms"], "fast_path": res["fast_path"],
         "sum_hit": res["sum_hit"], "sum_total": res["sum_total"], "cells": res["cells"],
         "roofline": roofline_of(alg, stages, profiled=name, xy=params[2], lib_sha=loaded_library_sha()),
-    }
+    })
     if "host_us" in res:
         out["host_us"] = res["host_us"]
     out["roofline"]["step"] = step_roofline(alg, res, name)
@@ -786,9 +855,7 @@ def run_single(args):
                 continue
             r, _ = run_config(hip, other, nsteps, nwarm, poses, False)
             out["configs"][other] = r
-    if args.offered_hz > 0:
-        out["stream"] = dict(stream_single(name, args.offered_hz, args.ticks, poses), config=name)
-    elif not args.no_extra and name == "m256" and not getattr(args, "no_big", False):
+    if args.offered_hz <= 0 and not args.no_extra and name == "m256" and not getattr(args, "no_big", False):
         # BASELINE.json config 5 as it is quoted -- "4 M-pt multi-sensor stream at 20 Hz, sustained throughput" -- on this ONE GPU:
         # 200 ticks (10 s) of host-resident 4,194,304-point clouds handed over at 20 Hz, upload inside
         out["stream"] = dict(stream_single("c5", 20.0, 200, 1), config="c5",
@@ -845,9 +912,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=100)
     ap.add_argument("--config", default="m256", choices=["c1", "c2", "c3", "m256", "m256b8", "c4", "c5", "m256_d10", "m256_d25", "m256_d40"])
     ap.add_argument("--poses", type=int, default=8, help="distinct sensor poses cycled through (0.2 m apart)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
-    ap.add_argument("--no-big", action="store_true", help="skip the c4 / c5 ride-along runs of the default line")
-    ap.add_argument("--no-extra", action="store_true", help="skip the short runs of the other configs")
+    ap.add_argument("--full", action="store_true",
+                    help="N = 1: after the timed steps, also measure everything else the line can carry (other calling conventions, "
+                         "roofline, statistics path, other configs, c5 stream, CPU baseline); a plain run times the steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="N = 1: write the last timed step's origin and four maps as DIR/<name>.npy (float64)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baseline leg")
+    ap.add_argument("--no-big", action="store_true", help="--full: skip the c4 / c5 ride-along runs and the c5 stream")
+    ap.add_argument("--no-extra", action="store_true", help="--full: skip the statistics leg and the short runs of the other configs")
     ap.add_argument("--cpu-budget", type=float, default=20.0)
     ap.add_argument("--offered-hz", type=float, default=0.0,
                     help="adds a paced-stream phase (BASELINE config 5: \"stream at 20 Hz\"): host-resident clouds handed over at "
@@ -860,10 +932,15 @@ def main():
                     help="N > 1 REHEARSAL on a box with fewer GPUs: every rank uses device 0 (peer copies; RCCL refuses it). "
                          "The line says so; it is not a scaling measurement")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     world = int(os.environ.get("WORLD_SIZE", "0"))
+    sharded = args.gpus > 1 or world > 1 or os.environ.get("GVOM_BENCH_FORCE_SHARDED")   # (the last: one rank through the sharded path)
+    if sharded and args.dump_outputs:
+        ap.error("--dump-outputs is available on the N = 1 leg only")
     if args.gpus > 1 and world == 0:
         return spawn_ranks(args)
-    if args.gpus > 1 or world > 1 or os.environ.get("GVOM_BENCH_FORCE_SHARDED"):    # (the last: one rank through the sharded path)
+    if sharded:
         import bench_sharded
         # RCCL prints its version banner on stdout: keep stdout for the ONE JSON line (fd-level, the
         # banner comes from native code)

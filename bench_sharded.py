@@ -200,8 +200,7 @@ def run(args):
     comm = ExchangeTimer(rccl, hip)
     sh = gvom_sharded.ShardedGvom(*params, comm=comm, device=local_rank)
     big = name in ("c4", "c5")
-    steps = min(args.steps, 40) if big else args.steps
-    warmup = min(args.warmup, 12) if big else args.warmup
+    steps, warmup = args.steps, args.warmup
 
     def step(k):
         share, ego = scans[k % poses]
@@ -215,21 +214,18 @@ def run(args):
         step(k)
     import gc
     gc.collect(); gc.disable()
-    blocks, total, k = [], 0.0, warmup
-    # blocks of exactly `steps` steps until >= 0.5 s has been timed on rank 0's clock (the ranks agree on the count)
-    while True:
-        fence()
-        t0 = time.perf_counter()
-        for _ in range(steps):
-            step(k); k += 1
-        fence()
-        dt = time.perf_counter() - t0
-        dt = max(r[0] for r in comm.exchange_host([int(dt * 1e9)])) * 1e-9      # MAX over ranks
-        blocks.append(dt); total += dt
-        if (total >= bench.MIN_TIMED_S and len(blocks) >= 3) or len(blocks) >= 200:
-            break
+    k = warmup
+    # one block of exactly `steps` steps (every rank takes part in every step)
+    fence()
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        step(k); k += 1
+    fence()
+    dt = time.perf_counter() - t0
+    dt = max(r[0] for r in comm.exchange_host([int(dt * 1e9)])) * 1e-9      # MAX over ranks
     gc.enable()
-    med = sorted(blocks)[len(blocks) // 2]
+    blocks = [dt]
+    med = dt
     # this rank's kernels (HIP events on the library's stream) and its exchanges, outside the timed blocks
     comm.on = True
     wire = {"sent": [], "received": []}
@@ -297,7 +293,7 @@ def run(args):
                        "name": name, "points_per_step": n_total, "points_per_gpu": n_local,
                        "grid": [params[2], params[2], params[3]], "buffer_size": params[4], "poses": poses,
                        "input": "device-resident f32 xyz", "host_affinity_rank0": affinity,
-                       "timing": "median of %d blocks of %d steps, max over ranks" % (len(blocks), steps),
+                       "timing": "%d steps timed as one block after %d warm-up steps, max over ranks" % (steps, warmup),
                        "exchange": "per scan: sparse all-to-all of dirty accumulator quads (1 KiB + id) and endpoints (8 B); "
                                    "per combine: in-place all-gather of height|inferred|density rows (24 B/cell); counts "
                                    "through shared memory; transport: see \"transport\""},

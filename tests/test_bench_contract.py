@@ -107,9 +107,9 @@ def test_sharded_workload_table():
 
 @pytest.mark.gpu
 def test_bench_prints_one_json_line_with_the_contract_keys():
-    """`python bench.py` (short run): ONE JSON line on stdout with the keys the driver reads, the roofline of the
+    """`python bench.py --full` (short run): ONE JSON line on stdout with the keys the driver reads, the roofline of the
     dominant kernel measured live, and the CPU baseline of the same workload."""
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "40", "--warmup", "10", "--no-extra",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "40", "--warmup", "10", "--no-extra",
                         "--cpu-budget", "2"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert p.returncode == 0, p.stderr.decode()[-2000:]
     lines = [ln for ln in p.stdout.decode().splitlines() if ln.strip()]
@@ -142,6 +142,72 @@ def test_bench_prints_one_json_line_with_the_contract_keys():
     # otherwise a report, not a bound (no assert on an absolute time or rate under -m gpu)
     print("bench: %.1f M points/s, %.4f ms/step, k_trace frac %.3f, cpu %.3f M points/s"
           % (d["value"], d["ms_per_step"], r["frac"], c["value"]))
+
+
+@pytest.mark.gpu
+def test_plain_bench_run_is_lean_and_dumps_the_last_maps(tmp_path):
+    """`python bench.py --steps K --warmup W --dump-outputs DIR` (no --full): the line holds the headline only -- no roofline, CPU
+    baseline or other configs -- and DIR holds the origin and four maps of the last timed step, identical from run to run."""
+    import numpy as np
+    sys.path.insert(0, os.path.join(ROOT, "g-vom_amd"))
+    import bench
+    import gvom
+    import synth
+    runs = []
+    for r in range(2):
+        out = tmp_path / ("run%d" % r)
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "13", "--warmup", "5",
+                            "--dump-outputs", str(out)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+        assert p.returncode == 0, p.stderr.decode()[-2000:]
+        lines = [ln for ln in p.stdout.decode().splitlines() if ln.strip()]
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert key in d, key
+        assert d["metric"] == bench.METRIC and d["unit"] == "M points/s" and d["higher_is_better"] is True and d["dtype"] == bench.DTYPE
+        assert d["steps"] == 13 and d["warmup"] == 5 and d["ms_per_step"] > 0
+        assert abs(d["value"] - d["config"]["points_per_scan"] / (d["ms_per_step"] * 1e-3) / 1e6) < 1e-6 * d["value"]
+        assert not set(d) & {"roofline", "cpu_baseline", "configs", "stream", "statistics", "value_host_f32"}, sorted(d)
+        runs.append({n: np.load(str(out / (n + ".npy"))) for n in bench.MAP_NAMES})
+    xy = synth.CONFIGS["m256"][0][2]
+    assert runs[0]["origin"].shape == (3,)
+    for n in bench.MAP_NAMES:
+        assert runs[0][n].dtype == np.float64 and np.array_equal(runs[0][n], runs[1][n]), n
+        if n != "origin":
+            assert runs[0][n].shape == (xy, xy), n
+    # the dump is what a caller of the timed path receives at that step: the same 18 steps through gvom.Gvom from host memory
+    params, scans = synth.config_inputs("m256", n_scans=8)
+    g = gvom.Gvom(*params, device=0)
+    for k in range(18):
+        pc, ego, tf = scans[k % len(scans)]
+        g.process_pointcloud(pc, ego, tf)
+        maps = g.combine_maps()
+    for n, a in zip(bench.MAP_NAMES, maps):
+        assert np.array_equal(runs[0][n], np.asarray(a, np.float64)), n
+
+
+def test_timed_steps_runs_exactly_the_steps_asked_for():
+    import bench
+    seen = []
+    dt, last, k = bench.timed_steps(lambda k: seen.append(k) or ("maps", k), 7, 5)
+    assert seen == [7, 8, 9, 10, 11] and last == ("maps", 11) and k == 12 and dt >= 0
+    dt, last, k = bench.timed_steps(lambda k: k * 10, 0, 1)
+    assert last == 0 and k == 1
+
+
+def test_dump_outputs_writes_every_map_as_float64(tmp_path):
+    import numpy as np
+    import bench
+    xy = 8
+    rng = np.random.default_rng(3)
+    pos, neg, vis = (np.asfortranarray(rng.integers(-5, 1000, (xy, xy)).astype(np.int32)) for _ in range(3))
+    maps = (np.array([1.5, -2.0, 0.25]), pos, neg, rng.normal(size=(xy, xy)), vis)
+    bench.dump_outputs(str(tmp_path / "d"), maps)
+    for name, a in zip(bench.MAP_NAMES, maps):
+        got = np.load(str(tmp_path / "d" / (name + ".npy")))
+        assert got.dtype == np.float64 and got.shape == a.shape and np.array_equal(got, a), name
+    with pytest.raises(RuntimeError):
+        bench.dump_outputs(str(tmp_path / "e"), None)
 
 
 def test_usable_cores_honours_the_cgroup_cpu_quota(tmp_path):

@@ -1,5 +1,5 @@
 #!/bin/bash
-# Round profile set on the GPU box: for each config the rocprofv3 kernel-trace stats of `bench.py --no-cpu --no-extra` + the
+# Round profile set on the GPU box: for each config the rocprofv3 kernel-trace stats of `bench.py --full --no-cpu --no-extra` + the
 # PMC traffic passes + calibration (tools/profile_gpu.sh), summarised into profiles/<round>[_<config>]_traffic.json and
 # profiles/<round>_<config>_kernel_stats.csv.  Usage: tools/profile_round.sh <round tag> [configs...]
 R=${1:-r3}; shift

@@ -167,6 +167,7 @@ struct gvom_handle {
     int tune_eager = -1;                                // gvom_set_tuning "eager": 0 off, 1 always, -1 automatic (off after 3 wasted in a row)
     int eager_waste = 0;                                // speculations dropped in a row (saturates at 4)
     int eager_stat[2] = {0, 0};                         // adopted / dropped since creation (gvom_get_tuning "eager_adopted" / "eager_dropped")
+    int last_fuse = 0;                                  // the last fusion's kernel, GVOM_ROUTE_* (gvom_get_tuning "fuse_kernel"; 0: none yet)
     bool last_scan_spec = false;                        // the last accepted scan went through k_encfuse
     bool solo_encoded = false;                          // a sharded handle of ONE rank: gvom_shard_scan_local has already encoded the scan (nothing to wait for)
     bool fresh_scan = false;                            // a scan has been committed and no combine has looked at it yet
@@ -1247,6 +1248,7 @@ int fuse_impl(gvom_handle *h, hipStream_t on = nullptr)
         h->spec_valid = false;
         h->eager_waste = 0;
         ++h->eager_stat[0];
+        h->last_fuse = GVOM_ROUTE_ENCFUSE;
         h->last_scan_spec = false; h->fresh_scan = false;
         h->stage_ms[3] = 0.0f;                             // (the fusion's time is inside the scan's second kernel)
         if (h->stats_release && !h->scan_inflight) release_statistics_buffers(h);
@@ -1327,9 +1329,10 @@ int fuse_impl(gvom_handle *h, hipStream_t on = nullptr)
         descs_mem = h->descs_dev;
     }
     if (h->profiling) HIPCHK(h, hipEventRecord(h->ev[4], fs));
+    h->last_fuse = 0;
     HIPCHK(h, gvom_launch_fuse(fs, P, KD, descs_mem, F.state, (uint4 *)F.rows.p,
                                F.tags, h->blockcounts,
-                               h->height, h->inferred));
+                               h->height, h->inferred, &h->last_fuse));
     if (h->profiling) { HIPCHK(h, hipEventRecord(h->ev[5], fs)); h->ev_fuse = true; }
     if (fstats) {                                        // beside k_map2d, behind this fusion and the scans' statistics
         HIPCHK(h, hipEventRecord(h->ev_fz_s, fs));
@@ -2395,6 +2398,7 @@ VIS int gvom_get_tuning(gvom_t *h, const char *name, int *value)
     if (!strcmp(name, "dirsort")) { *value = h->last_dirsort; return GVOM_OK; }
     if (!strcmp(name, "eager_adopted")) { *value = h->eager_stat[0]; return GVOM_OK; }
     if (!strcmp(name, "eager_dropped")) { *value = h->eager_stat[1]; return GVOM_OK; }
+    if (!strcmp(name, "fuse_kernel")) { *value = h->last_fuse; return GVOM_OK; }                  // read-only, GVOM_ROUTE_*
     if (!strcmp(name, "fastdiv")) { *value = h->tune_fastdiv == 0 ? 0 : h->fastdiv_ok; return GVOM_OK; }   // bit 0 / 1: xy / z resolution divided by reciprocal
     return GVOM_ERR_INVALID;
 }

@@ -1247,7 +1247,7 @@ hipError_t gvom_launch_retag(hipStream_t s, uint32_t *tags, size_t n, uint32_t o
 hipError_t gvom_launch_fuse(hipStream_t s, const FuseParams &P, const FuseDescs &KD,
                             const MapDesc *descs_dev, int32_t *fstate, uint4 *frows,
                             uint32_t *ftags, uint32_t *blockcounts,
-                            double *height, double *inferred)
+                            double *height, double *inferred, int *route)
 {
     const dim3 grid((P.xy + 63) / 64, P.sy_hi - P.sy_lo);
     if (grid.y == 0) return hipSuccess;
@@ -1256,16 +1256,20 @@ hipError_t gvom_launch_fuse(hipStream_t s, const FuseParams &P, const FuseDescs 
     const bool mem = descs_dev != nullptr;
     if (P.one_slot) {                                    // (the host has checked: one slot, 16-level chunks, xy % 4 == 0, descriptors by argument)
         hipLaunchKernelGGL(k_fuse1, grid, dim3(64 * P.nz), 0, s, P, KD, fstate, frows, ftags, blockcounts, height, inferred);
+        *route = GVOM_ROUTE_FUSE1;
         return hipGetLastError();
     }
     if (P.zc == 16 && (P.xy & 3) == 0 && !GVOM_DBG(P, 8)) {
-        if (P.nslots <= 2) { if (mem) FUSE_LAUNCH(k_fuse4<2, true>); else FUSE_LAUNCH(k_fuse4<2, false>); }
-        else { if (mem) FUSE_LAUNCH(k_fuse4<4, true>); else FUSE_LAUNCH(k_fuse4<4, false>); }
+        if (P.nslots <= 2) { if (mem) FUSE_LAUNCH(k_fuse4<2, true>); else FUSE_LAUNCH(k_fuse4<2, false>); *route = GVOM_ROUTE_FUSE4_2; }
+        else { if (mem) FUSE_LAUNCH(k_fuse4<4, true>); else FUSE_LAUNCH(k_fuse4<4, false>); *route = GVOM_ROUTE_FUSE4_4; }
     } else if (P.zc <= 16) {
         if (mem) FUSE_LAUNCH(k_fuse<true, true>); else FUSE_LAUNCH(k_fuse<true, false>);
+        *route = GVOM_ROUTE_FUSE_SHORT;
     } else {
         if (mem) FUSE_LAUNCH(k_fuse<false, true>); else FUSE_LAUNCH(k_fuse<false, false>);
+        *route = GVOM_ROUTE_FUSE_TALL;
     }
+    if (mem) *route |= GVOM_ROUTE_DESCS_MEM;
 #undef FUSE_LAUNCH
     return hipGetLastError();
 }

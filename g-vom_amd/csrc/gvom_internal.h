@@ -204,9 +204,12 @@ hipError_t gvom_launch_publish_seq(hipStream_t s, unsigned long long *host_flag,
 #define GVOM_DIRBINS 8192      // mode 1: 6 cube faces x 16 x 16 (1536 used); mode 2: 256 sin(elevation) rows x 32 azimuth sectors
 hipError_t gvom_launch_dirbin(hipStream_t s, const ScanParams &P, int mode, int dtype, const void *pts, int64_t stride_elems, int64_t n,
                               uint16_t *keys, uint32_t *hist, uint32_t *hist_next, uint32_t *cursor, uint32_t *perm);
+// *route: the kernel launched (gvom_get_tuning "fuse_kernel"); GVOM_ROUTE_ENCFUSE is an adopted eager fusion
+enum { GVOM_ROUTE_FUSE1 = 1, GVOM_ROUTE_FUSE4_2 = 2, GVOM_ROUTE_FUSE4_4 = 3, GVOM_ROUTE_FUSE_SHORT = 4, GVOM_ROUTE_FUSE_TALL = 5,
+       GVOM_ROUTE_ENCFUSE = 6, GVOM_ROUTE_DESCS_MEM = 16 };
 hipError_t gvom_launch_fuse(hipStream_t s, const FuseParams &P, const FuseDescs &KD,
                             const MapDesc *descs_dev, int32_t *fstate, uint4 *frows,
-                            uint32_t *ftags, uint32_t *blockcounts, double *height, double *inferred);
+                            uint32_t *ftags, uint32_t *blockcounts, double *height, double *inferred, int *route);
 void gvom_encfuse_shape(int xy, int zs, int nw_override, int *nw, int *nblocks, size_t *row_cap);
 // flink (or nullptr): per fused row, the voxel's row in the previous map -- what the statistics merge of this speculative fusion needs
 hipError_t gvom_launch_encfuse(hipStream_t s, const ScanParams &P, const FuseParams &F, const MapDesc &prev, int32_t *flink, uint32_t *hit,

@@ -428,7 +428,10 @@ int gvom_host_timing(gvom_t *h, double us[8]);
  * fusions through the general kernel), "flag_kernel" (1: round 3's completion-flag kernel).
  * (Test hooks are not part of this library: include/gvom_hip_test.h, lib/libgvom_hip_test.so.) */
 int gvom_set_tuning(gvom_t *h, const char *name, int value);
-/* The value the LAST scan ran with ("segs", "period", "ep_row", "prio", "interleave": what automatic resolved to). */
+/* The value the LAST scan ran with ("segs", "period", "ep_row", "prio", "interleave": what automatic resolved to).
+ * "fuse_kernel" (read-only): the kernel of the last fusion -- 1 k_fuse1, 2 k_fuse4<2>, 3 k_fuse4<4>, 4 k_fuse (chunks of up to
+ * 16 levels), 5 k_fuse (taller chunks), 6 an adopted eager k_encfuse; + 16 where the fusion descriptors were read from memory
+ * (more sources than fit the kernel arguments); 0 before the first fusion. */
 int gvom_get_tuning(gvom_t *h, const char *name, int *value);
 /* Raw HIP stream the library launches on (hipStream_t as void*), for external event timing. */
 void *gvom_stream(gvom_t *h);

@@ -13,7 +13,7 @@ import pytest
 
 import scenarios
 import synth
-from parity import compare_records
+from parity import compare_cloud, compare_records, compare_statistics
 from oracle import oracle
 
 pytestmark = pytest.mark.gpu
@@ -56,7 +56,7 @@ def test_hip_reproduces_reference_golden(gvom_mod, name):
     # library's raw moments + shift algebra -- agree to 2.3e-16 absolute, tools/stats_deviation.py; held to 1e-6 relative / 1e-9)
     assert compare_records(got, want, float_tol=1e-5, stats_rtol=1e-6, stats_atol=1e-9) > 5
     plain = scenarios.run_and_record(gvom_mod.Gvom, sc, record_debug=(name != "f7"))        # no statistics at any step
-    assert compare_records(plain, want, float_tol=1e-5) > 5 and not any(k.endswith("debug_voxel_map") for k in plain)
+    assert compare_records(plain, want, float_tol=1e-5, skip=("debug_voxel_map",)) > 5 and not any(k.endswith("debug_voxel_map") for k in plain)
     # the DEFAULT constructor, no environment variable, the node's call pattern (gvom_ros.py:109, 115, 171-189: scan, combine,
     # the three debug reads): the per-voxel statistics run for as long as make_debug_voxel_map is called, so the unchanged
     # node gets the reference's debug voxel cloud from its first tick on
@@ -1596,3 +1596,360 @@ def test_fuzz_small_configurations_match_oracle(gvom_mod, seed):
     params, steps = _fuzz_case(1000 + seed)
     got, want = _run_both(gvom_mod, params, steps)
     assert compare_records(got, want, float_tol=1e-5) > 3
+
+
+# ---- per-voxel statistics against the oracle on every fusion route ------------------------------------------------------------
+# gvom_get_tuning("fuse_kernel"): the kernel of the last fusion, as the library launched it (include/gvom_hip.h)
+FUSE1, FUSE4_2, FUSE4_4, FUSE_SHORT, FUSE_TALL, ENCFUSE, DESCS_MEM = 1, 2, 3, 4, 5, 6, 16
+
+
+def _stats_hip(gvom_mod, **kw):
+    return lambda *p: gvom_mod.Gvom(*p, voxel_statistics=True, **kw)
+
+
+def _stats_oracle(**kw):
+    return lambda *p: oracle.OracleGvom(*p, voxel_statistics=True, **kw)
+
+
+def _same_maps(a, b, what):
+    assert (a is None) == (b is None), what
+    if a is None:
+        return
+    for i in (0, 1, 2, 4):
+        assert np.array_equal(a[i], b[i]), "%s: map %d differs" % (what, i)
+    assert np.allclose(a[3], b[3], rtol=0, atol=1e-5), what + ": roughness"
+
+
+def _stats_steps(gvom_mod, params, steps, route=None, make_hip=None, make_oracle=None, what=""):
+    """Drives a HIP mapper and the oracle, both with voxel_statistics, through `steps` (("scan", cloud, ego, tf) / ("combine",)):
+    after every combine the returned maps (ints exact, roughness 1e-5), the fused cell count and ALL the statistics
+    (parity.compare_statistics).  route(k, filled, has_prev) -> the "fuse_kernel" the combine of step k must report (None:
+    not asserted).  Returns (hip mapper, oracle mapper, number of combines checked)."""
+    g = (make_hip or _stats_hip(gvom_mod))(*params)
+    w = (make_oracle or _stats_oracle())(*params)
+    checked, has_prev = 0, False
+    for k, step in enumerate(steps):
+        tag = "%s step %d" % (what, k)
+        if step[0] == "scan":
+            _, pc, ego, tf = step
+            g.process_pointcloud(pc, ego, tf)
+            w.process_pointcloud(np.array(pc, copy=True), ego, tf)
+            continue
+        a, b = g.combine_maps(), w.combine_maps()
+        _same_maps(a, b, tag)
+        if b is None:
+            continue
+        assert g.combined_cell_count_cpu == w.combined_cell_count_cpu, tag
+        if route is not None:
+            filled = sum(o is not None for o in w.origin_buffer)
+            want_route = route(k, filled, has_prev)
+            if want_route is not None:
+                assert g.get_tuning("fuse_kernel") == want_route, (tag, filled, g.get_tuning("fuse_kernel"), want_route)
+        compare_statistics(g, w, what=tag + ": ")
+        checked += 1
+        has_prev = True
+    return g, w, checked
+
+
+def _surface_steps(seed, xy, zs, xy_res, z_res, n_scans, n_pts=4000, dtype=np.float32, with_tf=False, move=(0.45, -0.3, 0.04)):
+    """scan + combine per pose of a moving sensor over a rolling surface with posts on it (voxels with many returns, with few,
+    with one; flat, thin and round neighbourhoods)"""
+    rng = np.random.default_rng(seed)
+    half = 0.5 * xy * xy_res * 0.9
+    steps = []
+    for k in range(n_scans):
+        ego = (move[0] * k, move[1] * k, move[2] * k)
+        x = rng.uniform(-half, half, n_pts) + ego[0]
+        y = rng.uniform(-half, half, n_pts) + ego[1]
+        z = 0.3 * np.sin(0.8 * x) + 0.2 * np.cos(0.5 * y) - 0.8 + rng.normal(0, 0.03, n_pts)
+        posts = rng.uniform(-half, half, (6, 2)) + np.array(ego[:2])
+        m = n_pts // 8
+        j = rng.integers(0, 6, m)
+        x[:m], y[:m] = posts[j, 0] + rng.normal(0, 0.02, m), posts[j, 1] + rng.normal(0, 0.02, m)
+        z[:m] = rng.uniform(-0.8, min(1.2, 0.45 * zs * z_res), m)
+        pc = np.stack([x, y, z], axis=1).astype(dtype)
+        tf = scenarios.rot_z(0.03 * (k + 1), (0.02 * k, -0.01, 0.003)) if with_tf else None
+        steps += [("scan", pc, ego, tf), ("combine",)]
+    return steps
+
+
+def _route_by_slots(filled, has_prev, mem_above=17):
+    r = FUSE1 if filled == 1 else (FUSE4_2 if filled == 2 else FUSE4_4)
+    return r | (DESCS_MEM if filled + has_prev > mem_above else 0)
+
+
+_ROUTES = {
+    # name: (xy, zs, buffer, z_res, n_scans, route(k, filled, has_prev))
+    "encfuse_64x32": (64, 32, 1, 0.2, 7, lambda k, f, p: ENCFUSE),
+    "encfuse_48x20": (48, 20, 1, 0.2, 7, lambda k, f, p: ENCFUSE),          # z_size % 4 != 0
+    "fuse1_36x32": (36, 32, 1, 0.2, 7, lambda k, f, p: FUSE1),              # xy_size % 16 != 0: no eager fusion
+    "fuse4x2_64x32": (64, 32, 2, 0.2, 7, lambda k, f, p: _route_by_slots(f, p)),
+    "fuse4x4_64x32_b3": (64, 32, 3, 0.2, 7, lambda k, f, p: _route_by_slots(f, p)),
+    "fuse4x4_64x32_b4": (64, 32, 4, 0.2, 8, lambda k, f, p: _route_by_slots(f, p)),
+    "fuse_short_50x13": (50, 13, 3, 0.2, 7, lambda k, f, p: FUSE_SHORT),     # xy_size % 4 != 0, 13-level chunks
+    "fuse_tall_16x300": (16, 300, 2, 0.05, 7, lambda k, f, p: FUSE_TALL),    # 19-level chunks
+    "descs_mem_32x16": (32, 16, 20, 0.2, 26, lambda k, f, p: _route_by_slots(f, p)),
+    "descs_mem_30x12": (30, 12, 18, 0.2, 26, lambda k, f, p: FUSE_SHORT | (DESCS_MEM if f + p > 17 else 0)),
+}
+
+
+@pytest.mark.parametrize("name", sorted(_ROUTES))
+def test_voxel_statistics_match_oracle_on_every_fusion_route(gvom_mod, name):
+    """The per-voxel statistics (k_stats, k_stats_gather, k_fuse_stats, k_voxel_cloud) against the oracle after EVERY combine of
+    a moving window, on each fusion kernel the library has -- the adopted eager k_encfuse (its merge reads the previous map
+    through the link table), k_fuse1, k_fuse4<2>, k_fuse4<4>, k_fuse with short and with tall chunks, and the descriptors read
+    from memory (more than 17 sources) -- as the library reports it launched them.  The rings fill, wrap and evict."""
+    xy, zs, buf, z_res, n_scans, route = _ROUTES[name]
+    params = (0.4, z_res, xy, zs, buf, 0.5, 0.5, 0.5, 0.3, 2.0, 2.0, 1.0, 1, 1)
+    n_pts = 1500 if n_scans > 20 else 4000
+    steps = _surface_steps(xy * 100 + zs + buf, xy, zs, 0.4, z_res, n_scans, n_pts, move=(0.25, -0.15, 0.02) if n_scans > 20 else (0.45, -0.3, 0.04))
+    g, _, checked = _stats_steps(gvom_mod, params, steps, route=route, what=name)
+    assert checked == n_scans
+    if name.startswith("encfuse"):
+        assert g.get_tuning("eager_adopted") == n_scans
+
+
+@pytest.mark.parametrize("site", ["combine", "scan"])
+def test_voxel_statistics_across_the_tile_epoch_renumbering(gvom_mod, site):
+    """test_tile_epoch_renumbering_before_the_counter_wraps with the statistics on: the statistics' sources are found by their
+    tile epochs too (k_stats' direct form, k_stats_gather's neighbours, k_fuse_stats' slots and previous map)."""
+    params = (0.4, 0.2, 32, 16, 3, 0.5, 0.5, 0.5, 0.3, 2.0, 4.0, 1.0, 1, 1)
+    steps = _surface_steps(4, 32, 16, 0.4, 0.2, 12, 3000)
+    seen = []
+
+    def hip(*p):
+        g = gvom_mod.Gvom(*p, voxel_statistics=True, _library=TEST_LIB)
+        seen.append(g)
+        return g
+
+    def route(k, f, p):
+        if k == 7:                  # (behind the combine of scan 3: 8 epochs used so far; the threshold is crossed by the next combine / scan)
+            seen[0].set_tuning("epoch_bias", 0xFFFFFF00 - 2 * 4 - (3 if site == "combine" else 2))
+        return _route_by_slots(f, p)
+    _, _, checked = _stats_steps(gvom_mod, params, steps, route=route, make_hip=hip, what="epoch " + site)
+    assert checked == 12
+
+
+def test_voxel_statistics_with_numba_cuda_typing(gvom_mod):
+    """numba_cuda_typing=True (float32 ray lengths) with the statistics on, both sides."""
+    params = (0.2, 0.2, 64, 32, 2, 0.5, 0.5, 0.5, 0.3, 2.0, 4.0, 1.0, 1, 1)
+    steps = _surface_steps(31, 64, 32, 0.2, 0.2, 6)
+    _, _, checked = _stats_steps(gvom_mod, params, steps, route=lambda k, f, p: _route_by_slots(f, p),
+                                 make_hip=_stats_hip(gvom_mod, numba_cuda_typing=True),
+                                 make_oracle=_stats_oracle(numba_cuda_typing=True), what="numba typing")
+    assert checked == 6
+
+
+def test_voxel_statistics_of_float64_transformed_and_strided_clouds(gvom_mod):
+    """float64 clouds with a 4x4 transform, then float32 (N, 4) rows with an extra column, a Fortran-ordered cloud and a
+    strided view, one per scan (k_stats<double> / k_stats<float> and the cloud strides of the statistics' pass)."""
+    params = (0.4, 0.2, 64, 32, 2, 0.5, 0.5, 0.5, 0.3, 2.0, 2.0, 1.0, 1, 1)
+    steps = _surface_steps(5, 64, 32, 0.4, 0.2, 8, dtype=np.float64, with_tf=True)
+    rng = np.random.default_rng(6)
+    for k in range(4, 8):
+        _, pc, ego, _ = steps[2 * k]
+        pc32 = pc.astype(np.float32)
+        xyzi = np.concatenate([pc32, rng.uniform(0, 1, (pc32.shape[0], 1)).astype(np.float32)], axis=1)
+        pc_k = (xyzi, np.asfortranarray(pc32), xyzi[:, :3], pc32[::-1])[k - 4]
+        steps[2 * k] = ("scan", pc_k, ego, None)
+    _, _, checked = _stats_steps(gvom_mod, params, steps, route=lambda k, f, p: _route_by_slots(f, p), what="dtype/stride")
+    assert checked == 8
+
+
+def test_voxel_statistics_at_the_grid_border_inside_min_distance_and_of_empty_scans(gvom_mod):
+    """Returns OUTSIDE the grid whose neighbourhood reaches border voxels (the direct form of k_stats), returns inside
+    min_distance (no statistics), an empty scan and a scan the map rejects (no return near the grid) between the others."""
+    xy, zs, xy_res, z_res = 48, 16, 0.4, 0.2
+    params = (xy_res, z_res, xy, zs, 3, 1.0, 0.5, 0.5, 0.3, 2.0, 2.0, 1.0, 1, 1)
+    rng = np.random.default_rng(8)
+    steps = []
+    for k in range(8):
+        ego = (0.37 * k, -0.21 * k, 0.03 * k)
+        lo = (np.floor(np.array(ego) / np.array([xy_res, xy_res, z_res]) - np.array([xy, xy, zs]) / 2) * np.array([xy_res, xy_res, z_res]))
+        hi = lo + np.array([xy * xy_res, xy * xy_res, zs * z_res])
+        n = 3000
+        pc = np.stack([rng.uniform(lo[0], hi[0], n), rng.uniform(lo[1], hi[1], n), rng.normal(-0.6, 0.3, n) + ego[2]], 1)
+        band = []
+        for ax in range(3):                                       # just outside each face, within one voxel of it
+            for side in (lo, hi):
+                b = np.stack([rng.uniform(lo[0], hi[0], 300), rng.uniform(lo[1], hi[1], 300), rng.uniform(lo[2], hi[2], 300)], 1)
+                res = (xy_res, xy_res, z_res)[ax]
+                b[:, ax] = side[ax] + (rng.uniform(0.02, 0.98, 300) * res if side is hi else -rng.uniform(0.02, 0.98, 300) * res)
+                band.append(b)
+        corner = hi + rng.uniform(0.01, 0.3, (50, 3)) * np.array([xy_res, xy_res, z_res])
+        near = np.array(ego) + rng.normal(0, 0.3, (200, 3))       # mostly inside min_distance (1.0 m)
+        pc = np.concatenate([pc] + band + [corner, near], 0).astype(np.float32 if k % 2 else np.float64)
+        if k == 3:
+            pc = pc[:0]                                            # empty scan
+        if k == 5:
+            pc = pc + 900.0                                        # no return reaches the grid: rejected
+        steps += [("scan", pc, ego, None), ("combine",)]
+    _, _, checked = _stats_steps(gvom_mod, params, steps, route=lambda k, f, p: _route_by_slots(f, p), what="border")
+    assert checked == 8
+
+
+@pytest.mark.parametrize("dist", [(0, 0), (1, 0), (0, 2), (2, 1), (3, 2)])
+def test_voxel_statistics_neighbourhood_sizes(gvom_mod, dist):
+    """(xy_eigen_dist, z_eigen_dist) other than (1, 1): the neighbourhood arithmetic of k_stats' direct form and of k_stats_gather
+    (wx = 2 xy_e + 1, nb = wx^2 (2 z_e + 1), the offset decode, the shifted moments) over a moving window, ring of 2."""
+    params = (0.4, 0.2, 64, 32, 2, 0.5, 0.5, 0.5, 0.3, 2.0, 2.0, 1.0) + dist
+    steps = _surface_steps(40 + 7 * dist[0] + dist[1], 64, 32, 0.4, 0.2, 6)
+    _, _, checked = _stats_steps(gvom_mod, params, steps, route=lambda k, f, p: _route_by_slots(f, p), what="dist %r" % (dist,))
+    assert checked == 6
+
+
+def test_voxel_statistics_of_degenerate_voxels(gvom_mod):
+    """(0, 0) neighbourhoods (each voxel's own returns only) built to hold exactly one return (all covariances zero: the
+    eigen-solver's p1 == 0 branch), two returns, three collinear returns (along an axis: p1 == 0 again; and oblique), four
+    coplanar returns (horizontal and vertical planes), exact duplicates, and returns on voxel faces / corners (in-voxel
+    position exactly 0) -- scanned three times from poses a whole voxel apart and merged over a ring of 2."""
+    xy_res, z_res, xy, zs = 0.5, 0.25, 32, 16
+    params = (xy_res, z_res, xy, zs, 2, 0.5, 0.5, 0.5, 0.3, 2.0, 2.0, 1.0, 0, 0)
+    res = np.array([xy_res, xy_res, z_res])
+    voxels = {
+        (20, 20, 8): [(0.5, 0.5, 0.5)],
+        (22, 20, 8): [(0.2, 0.3, 0.4), (0.7, 0.1, 0.9)],
+        (24, 20, 8): [(0.1, 0.5, 0.5), (0.5, 0.5, 0.5), (0.9, 0.5, 0.5)],
+        (26, 20, 8): [(0.1, 0.1, 0.1), (0.2, 0.3, 0.4), (0.3, 0.5, 0.7)],
+        (28, 20, 8): [(0.1, 0.1, 0.5), (0.9, 0.1, 0.5), (0.1, 0.9, 0.5), (0.9, 0.9, 0.5)],
+        (20, 23, 9): [(0.25, 0.1, 0.1), (0.25, 0.9, 0.1), (0.25, 0.1, 0.9), (0.25, 0.9, 0.9)],
+        (22, 23, 9): [(0.3, 0.6, 0.2)] * 5,
+        (24, 23, 9): [(0.0, 0.0, 0.0)],
+        (26, 23, 9): [(0.0, 0.5, 0.5), (0.0, 0.25, 0.75), (0.5, 0.0, 0.0)],
+        (28, 23, 7): [(0.0, 0.0, 0.0)] * 3 + [(0.5, 0.5, 0.5)],
+        (8, 9, 8): [(0.5, 0.5, 0.5), (0.5, 0.5, 0.5), (0.25, 0.75, 0.5)],
+    }
+    steps = []
+    for k, ego in enumerate([(0.0, 0.0, 0.0), (0.5, 0.0, 0.0), (0.5, 0.5, 0.25)]):
+        pts = [(np.array(v) - np.array([16, 16, 8]) + np.array(f)) * res for v, fs in voxels.items() for f in fs]
+        pc = np.array(pts, np.float64)
+        steps += [("scan", pc if k != 1 else pc.astype(np.float32), ego, None), ("combine",)]
+    g, w, checked = _stats_steps(gvom_mod, params, steps, what="degenerate")
+    assert checked == 3
+    counts = np.asarray(w.metrics_buffer[w.last_buffer_index])[:, 9]
+    assert sorted(np.unique(counts).tolist()) == [1.0, 2.0, 3.0, 4.0, 5.0]
+
+
+def _device_clouds(scans):
+    """the clouds in HBM (hipMalloc'd; bench.py's feed): [(pointer, n, dtype, ego, tf)], and a function that frees them"""
+    import ctypes
+    rt = ctypes.CDLL("libamdhip64.so")
+    rt.hipMalloc.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t]
+    rt.hipMemcpy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
+    rt.hipFree.argtypes = [ctypes.c_void_p]
+    out = []
+    for pc, ego, tf in scans:
+        pc = np.ascontiguousarray(pc)
+        p = ctypes.c_void_p()
+        assert rt.hipMalloc(ctypes.byref(p), pc.nbytes) == 0
+        out.append((p, pc.shape[0], pc.dtype, ego, tf))
+        assert rt.hipMemcpy(p, pc.ctypes.data_as(ctypes.c_void_p), pc.nbytes, 1) == 0
+    assert rt.hipDeviceSynchronize() == 0
+    return out, lambda: [rt.hipFree(d[0]) for d in out]
+
+
+@pytest.mark.parametrize("stats", [True, False])
+def test_bench_sequence_m256_matches_oracle_every_step(gvom_mod, stats):
+    """The exact sequence bench.py times: the m256 grid (256^3 @0.2 m, buffer 1), its 8 moving poses of the 131,072-return
+    scan, each fed from HBM through process_pointcloud_device and combined, every step against the all-core oracle.
+    stats=True: the default constructor read by the node's debug call after every combine (statistics on demand) against the
+    oracle's statistics, every combine an adopted eager fusion.  stats=False: the north-star path, returned maps every step
+    plus the newest ring slot and the fused map densely at steps 1 and 7."""
+    params, scans = synth.config_inputs("m256", n_scans=8)
+    assert params[2:5] == (256, 256, 1) and len(scans) == 8
+    dev, free = _device_clouds(scans)
+    oracle.use_all_cores(True, threads=16)
+    try:
+        g = gvom_mod.DefaultGvom(*params) if stats else gvom_mod.Gvom(*params)
+        w = oracle.OracleGvom(*params, voxel_statistics=stats)
+        for k, ((d, n, dt, ego, tf), (pc, _, _)) in enumerate(zip(dev, scans)):
+            g.process_pointcloud_device(d.value, n, dt, ego, tf)
+            w.process_pointcloud(pc, ego, tf)
+            a, b = g.combine_maps(), w.combine_maps()
+            _same_maps(a, b, "m256 step %d" % k)
+            assert g.combined_cell_count_cpu == w.combined_cell_count_cpu
+            assert (g.buffer_index, g.last_buffer_index) == (w.buffer_index, w.last_buffer_index)
+            assert g.get_tuning("fuse_kernel") == ENCFUSE, k
+            if stats:
+                compare_statistics(g, w, what="m256 step %d: " % k)
+            elif k in (1, 7):
+                slot = w.last_buffer_index
+                ws = scenarios.dense_from_compact(w.index_buffer[slot], w.hit_count_buffer[slot], w.total_count_buffer[slot], w.min_height_buffer[slot])
+                wf = scenarios.dense_from_compact(w.combined_index_map, w.combined_hit_count, w.combined_total_count, w.combined_min_height)
+                for got_d, want_d, what in ((g.read_dense(slot), ws, "slot"), (g.read_dense(gvom_mod.GVOM_WHICH_FUSED), wf, "fused")):
+                    for j, nm in enumerate(("state", "hit", "total", "minh")):
+                        assert np.array_equal(np.asarray(want_d[j]), got_d[j]), "step %d %s %s" % (k, what, nm)
+        assert g.get_tuning("eager_adopted") == 8
+        del g
+    finally:
+        oracle.use_all_cores(False)
+        free()
+
+
+@pytest.mark.parametrize("cfg", ["c3", "c4", "c5"])
+def test_voxel_statistics_match_oracle_at_full_size(gvom_mod, cfg):
+    """Statistics on both sides at BASELINE sizes: c3 (OS1-128 scans, buffer 8) over 12 scans -- the ring fills, wraps and evicts
+    four slots; c4 at its BASELINE settings (512 x 512 x 128, buffer 4, 1,048,576 returns) over 3 scans; one c5 tick (1024 x
+    1024 x 128, 4,194,304 returns: k_fuse_stats at its 8,192-workgroup cap, k_voxel_cloud in many grid-stride passes)."""
+    n_scans = {"c3": 12, "c4": 3, "c5": 1}[cfg]
+    if cfg == "c5" and _free_ram_gb() < 24.0:
+        pytest.skip("needs 24 GB of free host memory at 134 M voxels")
+    params, scans = synth.config_inputs(cfg, n_scans=n_scans)
+    steps = []
+    for pc, ego, tf in scans:
+        steps += [("scan", pc, ego, tf), ("combine",)]
+    oracle.use_all_cores(True, threads=16)
+    try:
+        _, _, checked = _stats_steps(gvom_mod, params, steps, what=cfg)
+    finally:
+        oracle.use_all_cores(False)
+    assert checked == n_scans
+
+
+@pytest.mark.parametrize("world", [2, 4])
+def test_sharded_voxel_statistics_match_oracle(world):
+    """The slab-sharded statistics (thread ranks on one GPU; only the direct form of k_stats: a neighbour's moments may live on
+    another rank) against the ORACLE, not only against the unsharded handle: the ranks' debug voxel clouds together are the
+    oracle's cloud (positions, hit counts exact, solid factors 1e-6, eigenvalue columns to parity.STATS_TOL["cloud"])."""
+    import contextlib
+    import io
+    from shard_threads import run_ranks
+    params = (0.2, 0.2, 64, 32, 2, 1.0, 0.5, 0.5, 0.3, 2.0, 4.0, 1.0, 1, 1)
+    scene = synth.make_scene(2, extent=5.5)
+    steps = []
+    for k in range(5):
+        ego = (0.5 * k, -0.35 * k, 0.04 * k)
+        shares = [synth.lidar_scan(scene, beams=16, azimuths=512, sensor=ego, yaw=0.002 * r, noise_seed=10 * k + r, dtype=np.float32)[:8192 - 701 * r]
+                  for r in range(world)]
+        steps.append((shares, ego))
+    w = oracle.OracleGvom(*params, voxel_statistics=True)
+    want = []
+    for shares, ego in steps:
+        w.process_pointcloud(np.concatenate(shares, 0), ego)
+        want.append((w.combine_maps(), w.make_debug_voxel_map()))
+
+    def body(r, sh):
+        parts = []
+        for (shares, ego), (wmaps, _) in zip(steps, want):
+            sh.process_pointcloud(shares[r], ego)
+            got = sh.combine_maps()
+            _same_maps(got, wmaps, "rank %d" % r)
+            parts.append(np.array(sh.make_debug_voxel_map(), copy=True))
+        return parts
+
+    with contextlib.redirect_stdout(io.StringIO()):
+        parts = run_ranks(world, params, body, voxel_statistics=True)
+    for k, (_, wcloud) in enumerate(want):
+        compare_cloud(np.concatenate([parts[r][k] for r in range(world)], 0), wcloud, what="%d ranks step %d: " % (world, k))
+
+
+@pytest.mark.parametrize("seed", range(24))
+def test_fuzz_voxel_statistics_match_oracle(gvom_mod, seed):
+    """The edge-case fuzz (_fuzz_case, fresh seeds) with the statistics on both sides, (xy_eigen_dist, z_eigen_dist) drawn from
+    {0, 1, 2}^2, and every third seed snapped to the shapes the eager fusion takes (buffer 1, xy_size % 16 == 0, z_size >= 4)."""
+    params, steps = _fuzz_case(3000 + seed)
+    rng = np.random.default_rng(5000 + seed)
+    params = params[:12] + (int(rng.integers(0, 3)), int(rng.integers(0, 3)))
+    if seed % 3 == 0:
+        params = params[:2] + (16 * max(1, min(4, round(params[2] / 16))), max(4, params[3]), 1) + params[5:]
+    _stats_steps(gvom_mod, params, steps, what="seed %d" % seed)

@@ -39,7 +39,8 @@ def test_oracle_reproduces_reference(name, capsys, oracle_build):
     stats = name != "f7" and oracle_build == "one_thread"
     got = scenarios.run_and_record(lambda *p: oracle.OracleGvom(*p, voxel_statistics=stats), sc,
                                    record_debug=(name != "f7"))
-    n = compare_records(got, want, float_tol=1e-9, stats_rtol=2e-6, stats_atol=1e-7)
+    n = compare_records(got, want, float_tol=1e-9, stats_rtol=2e-6, stats_atol=1e-7,
+                        skip=() if stats or name == "f7" else ("debug_voxel_map",))      # (this build runs without them)
     assert n > 5
     if stats:
         assert any(k.endswith("debug_voxel_map") for k in got)

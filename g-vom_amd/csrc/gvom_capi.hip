@@ -63,6 +63,36 @@ struct Fused {
     bool has_metrics = false;                  // k_fuse_stats merged the statistics of this map (every source had its own)
 };
 
+// DEVICE MAP SETS (gvom_combine_maps_device): one device allocation per set holding the nine maps of one combine, [y][x] order,
+// each map at a 256-byte aligned offset: the six f64 maps (3 roughness, 4 height, 5 inferred height, 6 / 7 x / y slope,
+// 8 guessed delta) at k * S doubles, then the three i32 maps (0 positive, 1 negative, 2 visibility) behind them at k * S
+// ints, S = dev_map_stride(xy): 60 bytes per cell.  A set is handed out by EXPORTS (the consumer stream waits on `ready`) and
+// taken back by RELEASES (an event recorded on the consumer stream); the combine that reuses the set first makes the handle's
+// stream wait on every release event.  A set with live exports outlives the handle (orphan) and is freed at its last release.
+struct DevSet {
+    char *mem = nullptr;
+    size_t bytes = 0;
+    int device = 0, xy = 0;
+    hipEvent_t ready = nullptr;                // recorded on the handle's stream behind the set's k_map2d
+    int64_t id = -1;                           // sequence number of the combine that wrote it; -1: free
+    int exports = 0;                           // live exports
+    std::vector<hipStream_t> rel_streams;      // release events since the set was written, one per consumer stream
+    std::vector<hipEvent_t> rel, rel_spare;
+    bool orphan = false;                       // the handle is gone
+};
+#define GVOM_MAX_DEVICE_SETS 8
+// DevSet::exports / rel* / orphan: a DLPack deleter runs on whatever thread frees the consumer's tensor, without the handle
+std::mutex g_set_mu;
+
+// DLPack v0.8 (legacy) and v1.0 (versioned) layouts (as the DLPack specification defines them; no header of another project is included)
+struct DLDevice { int32_t device_type; int32_t device_id; };
+struct DLDataType { uint8_t code; uint8_t bits; uint16_t lanes; };
+struct DLTensor { void *data; DLDevice device; int32_t ndim; DLDataType dtype; int64_t *shape; int64_t *strides; uint64_t byte_offset; };
+struct DLManagedTensor { DLTensor dl_tensor; void *manager_ctx; void (*deleter)(DLManagedTensor *); };
+struct DLPackVersion { uint32_t major; uint32_t minor; };
+struct DLManagedTensorVersioned { DLPackVersion version; void *manager_ctx; void (*deleter)(DLManagedTensorVersioned *); uint64_t flags; DLTensor dl_tensor; };
+enum { kDLInt = 0, kDLFloat = 2, kDLROCM = 10 };
+
 }  // namespace
 
 struct gvom_handle {
@@ -241,6 +271,11 @@ struct gvom_handle {
     bool profiling = false;
     hipEvent_t ev[8] = {nullptr};
     float stage_ms[GVOM_N_STAGES] = {0, 0, 0, 0, 0};
+    // device map sets (gvom_combine_maps_device)
+    std::vector<DevSet *> dsets;
+    int64_t dset_seq = 0;
+    bool count_pending = false;                         // the last combine was a device combine: its fused cell count is read
+    hipEvent_t ev_dcount = nullptr;                     //   from the host-mapped counter once this event (behind its k_map2d) has completed
 };
 
 namespace {
@@ -1356,7 +1391,7 @@ int fuse_impl(gvom_handle *h, hipStream_t on = nullptr)
 // gathered: sharded run -- every row of the interleaved height buffer (heights + owner-computed
 // positive densities) has been all-gathered and this rank computes ALL rows of the outputs.
 int map2d_impl(gvom_handle *h, bool gathered, bool publish, char *out_dev, bool yx, const double *occ = nullptr,
-               hipStream_t on = nullptr, uint32_t done_seq = 0)
+               hipStream_t on = nullptr, uint32_t done_seq = 0, bool dev_set = false)
 {
     const hipStream_t ms = on ? on : h->stream;
     const gvom_params &p = h->prm;
@@ -1387,6 +1422,12 @@ int map2d_impl(gvom_handle *h, bool gathered, bool publish, char *out_dev, bool 
     const size_t n2 = h->cells2d;
     int32_t *o_pos = (int32_t *)out_dev, *o_neg = o_pos + n2, *o_vis = o_neg + n2;
     double *o_rgh = (double *)(o_vis + n2);
+    if (dev_set) {                                // a device map set (DevSet): f64 maps 3-8, then i32 maps 0-2
+        const size_t S = dev_map_stride(p.xy_size);
+        P.out_dev = 1;
+        o_rgh = (double *)out_dev;
+        o_pos = (int32_t *)(o_rgh + 6 * S); o_neg = o_pos + S; o_vis = o_neg + S;
+    }
     if (h->profiling) HIPCHK(h, hipEventRecord(h->ev[6], ms));
     HIPCHK(h, gvom_launch_map2d(ms, P, F.state, F.tags, (const uint4 *)F.rows.p,
                                 h->height, h->inferred, h->slope_x,
@@ -1459,6 +1500,7 @@ int finish_combine(gvom_handle *h, std::unique_lock<std::mutex> &lk, uint32_t se
     memcpy(&c, h->counters_host + 2, 8);
     F.count = (int64_t)c;
     h->combined_cell_count = F.count;
+    h->count_pending = false;
     collect_stage_ms(h);
     return GVOM_OK;
 }
@@ -1472,8 +1514,38 @@ int finish_combine(gvom_handle *h)
     memcpy(&c, h->counters_host + 2, 8);
     F.count = (int64_t)c;
     h->combined_cell_count = F.count;
+    h->count_pending = false;
     collect_stage_ms(h);
     return GVOM_OK;
+}
+
+// the fused cell count of a device combine: read from the host-mapped counter once its k_map2d has completed (handle mutex held)
+int settle_count(gvom_handle *h)
+{
+    if (!h->count_pending) return GVOM_OK;
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipEventSynchronize(h->ev_dcount));
+    h->count_pending = false;
+    Fused &F = h->fused[h->cur];
+    unsigned long long c;
+    memcpy(&c, h->counters_host + 2, 8);
+    F.count = (int64_t)c;
+    h->combined_cell_count = F.count;
+    return GVOM_OK;
+}
+
+void set_free(DevSet *s)                                   // (no export left and unreachable: not under g_set_mu)
+{
+    int dev = 0;
+    hipGetDevice(&dev);
+    hipSetDevice(s->device);
+    for (hipEvent_t e : s->rel) { hipEventSynchronize(e); hipEventDestroy(e); }   // consumers' reads are done before the memory goes
+    for (hipEvent_t e : s->rel_spare) hipEventDestroy(e);
+    if (s->ready) { hipEventSynchronize(s->ready); hipEventDestroy(s->ready); }
+    if (s->mem) hipFree(s->mem);
+    hipSetDevice(dev);
+    (void)hipGetLastError();
+    delete s;
 }
 
 }  // namespace
@@ -1526,6 +1598,16 @@ VIS void gvom_destroy(gvom_t *h)
     hipFree(h->hmaps); hipFree(h->slope_x); hipFree(h->slope_y);
     hipFree(h->rough); hipFree(h->guessed);
     if (h->out_host) hipHostFree(h->out_host);
+    {   // device map sets: exported ones outlive the handle and go at their last release
+        std::vector<DevSet *> idle;
+        {
+            std::lock_guard<std::mutex> g(g_set_mu);
+            for (DevSet *s : h->dsets) { if (s->exports > 0) s->orphan = true; else idle.push_back(s); }
+        }
+        for (DevSet *s : idle) set_free(s);
+        h->dsets.clear();
+        if (h->ev_dcount) hipEventDestroy(h->ev_dcount);
+    }
     for (auto &e : h->ev) if (e) hipEventDestroy(e);
     if (h->ev_fused) hipEventDestroy(h->ev_fused);
     if (h->ev_mapped) hipEventDestroy(h->ev_mapped);
@@ -1893,6 +1975,7 @@ VIS int gvom_combine_begin(gvom_t *h, void *pinned_out, const double *occ)
     if (h->pending_combine) { h->err = "a combine begun with gvom_combine_begin has not been ended"; return GVOM_ERR_INVALID; }
     HIPCHK(h, hipSetDevice(h->device));
     { const int rc0 = check_out_buffer(h, pinned_out); if (rc0) return rc0; }
+    { const int rc0 = settle_count(h); if (rc0) return rc0; }   // (a device combine's count, before the fusion moves on)
     double t0 = now_ns();
     // k_map2d goes to the second stream, and with a ring of three or more filled slots the fusion too (behind
     // the scan's k_encode on the main stream): the next scan's k_trace / k_encode overlap them -- they touch the
@@ -1946,12 +2029,225 @@ VIS int gvom_combine_end(gvom_t *h, double origin_world[3])
     memcpy(&c, h->counters_host + 2, 8);
     F.count = (int64_t)c;
     h->combined_cell_count = F.count;
+    h->count_pending = false;
     HT(h, 3, t0);
     if (origin_world) {
         origin_world[0] = (double)F.origin[0] * h->prm.xy_resolution;
         origin_world[1] = (double)F.origin[1] * h->prm.xy_resolution;
         origin_world[2] = (double)F.origin[2] * h->prm.z_resolution;
     }
+    return GVOM_OK;
+}
+
+// ---- device-resident maps (gvom_combine_maps_device) -----------------------------------------
+// The fusion advances exactly as in gvom_combine_maps; k_map2d's DEV form writes the nine maps into a DevSet in device memory
+// and the call returns once the work is enqueued.  Consumers take a set through exports (their stream waits on the set's
+// ready event) and give it back through releases (an event on their stream): no host wait on either side.
+
+// one release: an event on the consumer's stream (none for GVOM_STREAM_NOSYNC), the export count goes down; an orphaned set
+// goes with its last release.  Needs neither the handle nor the Python GIL.
+static hipError_t set_release(DevSet *s, void *consumer_stream)
+{
+    hipError_t e = hipSuccess;
+    bool free_it = false;
+    {
+        std::lock_guard<std::mutex> g(g_set_mu);
+        if (consumer_stream != GVOM_STREAM_NOSYNC) {
+            int dev = 0;
+            hipGetDevice(&dev);
+            if (dev != s->device) hipSetDevice(s->device);
+            const hipStream_t st = (hipStream_t)consumer_stream;
+            size_t k = 0;
+            while (k < s->rel_streams.size() && s->rel_streams[k] != st) ++k;
+            if (k == s->rel_streams.size()) {                // (a stream seen before: its newer event covers the older reads too)
+                hipEvent_t ev = nullptr;
+                if (!s->rel_spare.empty()) { ev = s->rel_spare.back(); s->rel_spare.pop_back(); }
+                else e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+                if (e == hipSuccess) { s->rel_streams.push_back(st); s->rel.push_back(ev); }
+            }
+            if (e == hipSuccess) e = hipEventRecord(s->rel[k], st);
+            if (dev != s->device) hipSetDevice(dev);
+        }
+        if (s->exports > 0) --s->exports;
+        free_it = s->orphan && s->exports == 0;
+    }
+    if (free_it) set_free(s);
+    return e;
+}
+
+static DevSet *find_set(gvom_handle *h, int64_t set_id)
+{
+    if (set_id < 0) return nullptr;
+    for (DevSet *s : h->dsets) if (s->id == set_id) return s;
+    return nullptr;
+}
+
+static int set_export(gvom_handle *h, int64_t set_id, int which, void *consumer_stream, DevSet **out_set, void **ptr)
+{
+    if (which < 0 || which > 8) { h->err = "map index outside 0..8"; return GVOM_ERR_INVALID; }
+    DevSet *s = find_set(h, set_id);
+    if (!s) { h->err = "unknown or stale device map set id"; return GVOM_ERR_INVALID; }
+    HIPCHK(h, hipSetDevice(h->device));
+    if (consumer_stream != GVOM_STREAM_NOSYNC) HIPCHK(h, hipStreamWaitEvent((hipStream_t)consumer_stream, s->ready, 0));
+    {
+        std::lock_guard<std::mutex> g(g_set_mu);
+        ++s->exports;
+    }
+    const size_t S = dev_map_stride(s->xy);
+    *ptr = which >= 3 ? (void *)((double *)s->mem + (size_t)(which - 3) * S) : (void *)((int32_t *)((double *)s->mem + 6 * S) + (size_t)which * S);
+    *out_set = s;
+    return GVOM_OK;
+}
+
+VIS int gvom_combine_maps_device(gvom_t *h, double origin_world[3], int64_t *set_id)
+{
+    if (!h || !set_id) return GVOM_ERR_INVALID;
+    if (h->sharded) { h->err = "gvom_combine_maps_device: sharded handles are not supported"; return GVOM_ERR_INVALID; }
+    std::lock_guard<std::mutex> ck(h->combine_mu);
+    std::unique_lock<std::mutex> lk(h->mu);
+    if (h->pending_combine) { h->err = "a combine begun with gvom_combine_begin has not been ended"; return GVOM_ERR_INVALID; }
+    HIPCHK(h, hipSetDevice(h->device));
+    double t0 = now_ns();
+    *set_id = -1;
+    // unused sets go back to the pool; then a free one, or a new one (at most GVOM_MAX_DEVICE_SETS)
+    DevSet *set = nullptr;
+    {
+        std::lock_guard<std::mutex> g(g_set_mu);
+        for (DevSet *s : h->dsets) if (s->exports == 0) { s->id = -1; if (!set) set = s; }
+    }
+    if (!set && !h->slots[h->ring[h->last_buffer_index]].filled) return GVOM_EMPTY_BUFFER;
+    if (!set) {
+        if ((int)h->dsets.size() >= GVOM_MAX_DEVICE_SETS) {
+            h->err = "gvom_combine_maps_device: all 8 device map sets are exported; release some (gvom_device_map_release, or drop the tensors)";
+            return GVOM_ERR_CAPACITY;
+        }
+        DevSet *s = new DevSet;
+        s->device = h->device; s->xy = h->prm.xy_size;
+        s->bytes = dev_map_stride(s->xy) * 60;
+        hipError_t e = hipMalloc((void **)&s->mem, s->bytes);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&s->ready, hipEventDisableTiming);
+        if (e != hipSuccess) { set_free(s); HIPCHK(h, e); }
+        h->dsets.push_back(s);
+        set = s;
+    }
+    if (!h->ev_dcount) HIPCHK(h, hipEventCreateWithFlags(&h->ev_dcount, hipEventDisableTiming));
+    int rc = fuse_impl(h);
+    if (rc) return rc;
+    {   // a reused set: its consumers' reads come first
+        std::lock_guard<std::mutex> g(g_set_mu);
+        for (hipEvent_t e : set->rel) HIPCHK(h, hipStreamWaitEvent(h->stream, e, 0));
+        set->rel_spare.insert(set->rel_spare.end(), set->rel.begin(), set->rel.end());
+        set->rel.clear(); set->rel_streams.clear();
+    }
+    if ((rc = map2d_impl(h, false, true, set->mem, true, nullptr, nullptr, 0, true))) return rc;
+    HIPCHK(h, hipEventRecord(set->ready, h->stream));
+    HIPCHK(h, hipEventRecord(h->ev_dcount, h->stream));
+    h->count_pending = true;
+    set->id = ++h->dset_seq;
+    *set_id = set->id;
+    HT(h, 2, t0);
+    if (origin_world) {
+        const Fused &F = h->fused[h->cur];
+        origin_world[0] = (double)F.origin[0] * h->prm.xy_resolution;
+        origin_world[1] = (double)F.origin[1] * h->prm.xy_resolution;
+        origin_world[2] = (double)F.origin[2] * h->prm.z_resolution;
+    }
+    return GVOM_OK;
+}
+
+VIS int gvom_device_map_export(gvom_t *h, int64_t set_id, int which, void *consumer_stream, void **ptr, int64_t strides[2])
+{
+    if (!h || !ptr || !strides) return GVOM_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(h->mu);
+    DevSet *s = nullptr;
+    const int rc = set_export(h, set_id, which, consumer_stream, &s, ptr);
+    if (rc) return rc;
+    strides[0] = 1; strides[1] = h->prm.xy_size;
+    return GVOM_OK;
+}
+
+VIS int gvom_device_map_release(gvom_t *h, int64_t set_id, void *consumer_stream)
+{
+    if (!h) return GVOM_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(h->mu);
+    DevSet *s = find_set(h, set_id);
+    if (!s) { h->err = "unknown or stale device map set id"; return GVOM_ERR_INVALID; }
+    {
+        std::lock_guard<std::mutex> g(g_set_mu);
+        if (s->exports == 0) { h->err = "gvom_device_map_release: the set has no live export"; return GVOM_ERR_INVALID; }
+    }
+    HIPCHK(h, set_release(s, consumer_stream));
+    return GVOM_OK;
+}
+
+// the manager context of one DLPack export: the set, the consumer stream its release is recorded on, shape and strides
+struct DlpackCtx {
+    DevSet *set;
+    void *stream;
+    int64_t shape[2], strides[2];
+    DLManagedTensor legacy;
+    DLManagedTensorVersioned versioned;
+};
+static void dlpack_delete_legacy(DLManagedTensor *m)
+{
+    DlpackCtx *c = (DlpackCtx *)m->manager_ctx;
+    set_release(c->set, c->stream);
+    delete c;
+}
+static void dlpack_delete_versioned(DLManagedTensorVersioned *m)
+{
+    DlpackCtx *c = (DlpackCtx *)m->manager_ctx;
+    set_release(c->set, c->stream);
+    delete c;
+}
+
+VIS int gvom_device_map_dlpack(gvom_t *h, int64_t set_id, int which, void *consumer_stream, int versioned, void **managed)
+{
+    if (!h || !managed) return GVOM_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(h->mu);
+    DevSet *s = nullptr;
+    void *ptr = nullptr;
+    const int rc = set_export(h, set_id, which, consumer_stream, &s, &ptr);
+    if (rc) return rc;
+    DlpackCtx *c = new DlpackCtx();
+    c->set = s; c->stream = consumer_stream;
+    c->shape[0] = c->shape[1] = h->prm.xy_size;
+    c->strides[0] = 1; c->strides[1] = h->prm.xy_size;
+    DLTensor t;
+    t.data = ptr;
+    t.device.device_type = kDLROCM; t.device.device_id = h->device;
+    t.ndim = 2;
+    t.dtype.code = which >= 3 ? kDLFloat : kDLInt; t.dtype.bits = which >= 3 ? 64 : 32; t.dtype.lanes = 1;
+    t.shape = c->shape; t.strides = c->strides;
+    t.byte_offset = 0;
+    if (versioned) {
+        c->versioned.version.major = 1; c->versioned.version.minor = 0;
+        c->versioned.manager_ctx = c;
+        c->versioned.deleter = dlpack_delete_versioned;
+        c->versioned.flags = 0;
+        c->versioned.dl_tensor = t;
+        *managed = &c->versioned;
+    } else {
+        c->legacy.dl_tensor = t;
+        c->legacy.manager_ctx = c;
+        c->legacy.deleter = dlpack_delete_legacy;
+        *managed = &c->legacy;
+    }
+    return GVOM_OK;
+}
+
+VIS int gvom_device_map_copy(gvom_t *h, int64_t set_id, int which, void *host_out)
+{
+    if (!h || !host_out) return GVOM_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(h->mu);
+    DevSet *s = nullptr;
+    void *ptr = nullptr;
+    int rc = set_export(h, set_id, which, GVOM_STREAM_NOSYNC, &s, &ptr);
+    if (rc) return rc;
+    hipError_t e = hipEventSynchronize(s->ready);
+    if (e == hipSuccess) e = hipMemcpy(host_out, ptr, h->cells2d * (which >= 3 ? 8 : 4), hipMemcpyDeviceToHost);
+    set_release(s, GVOM_STREAM_NOSYNC);
+    HIPCHK(h, e);
     return GVOM_OK;
 }
 
@@ -2063,6 +2359,7 @@ VIS int gvom_get_state(gvom_t *h, gvom_state *out)
 {
     if (!h || !out) return GVOM_ERR_INVALID;
     std::lock_guard<std::mutex> lk(h->mu);
+    { const int rc0 = settle_count(h); if (rc0) return rc0; }
     memset(out, 0, sizeof *out);
     out->buffer_index = h->buffer_index;
     out->last_buffer_index = h->last_buffer_index;
@@ -2088,6 +2385,7 @@ VIS int gvom_read_dense(gvom_t *h, int which, int32_t *state, int32_t *hit, int3
     std::lock_guard<std::mutex> lk(h->mu);
     HIPCHK(h, hipSetDevice(h->device));
     const int32_t *st; const uint4 *cr; const uint32_t *tg; uint32_t ep; const int64_t *org; int64_t cnt;
+    { const int rc0 = settle_count(h); if (rc0) return rc0; }
     if (which == GVOM_WHICH_FUSED) {
         if (!h->has_combined) return GVOM_NO_DATA;
         const Fused &F = h->fused[h->cur];
@@ -2398,7 +2696,8 @@ VIS int gvom_get_tuning(gvom_t *h, const char *name, int *value)
     if (!strcmp(name, "dirsort")) { *value = h->last_dirsort; return GVOM_OK; }
     if (!strcmp(name, "eager_adopted")) { *value = h->eager_stat[0]; return GVOM_OK; }
     if (!strcmp(name, "eager_dropped")) { *value = h->eager_stat[1]; return GVOM_OK; }
-    if (!strcmp(name, "fuse_kernel")) { *value = h->last_fuse; return GVOM_OK; }                  // read-only, GVOM_ROUTE_*
+    if (!strcmp(name, "fuse_kernel")) { *value = h->last_fuse; return GVOM_OK; }
+    if (!strcmp(name, "device_map_sets")) { *value = (int)h->dsets.size(); return GVOM_OK; }             // read-only: allocated device map sets                  // read-only, GVOM_ROUTE_*
     if (!strcmp(name, "fastdiv")) { *value = h->tune_fastdiv == 0 ? 0 : h->fastdiv_ok; return GVOM_OK; }   // bit 0 / 1: xy / z resolution divided by reciprocal
     return GVOM_ERR_INVALID;
 }

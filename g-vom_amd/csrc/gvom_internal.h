@@ -178,7 +178,12 @@ struct Map2dParams {
     unsigned long long *done_flag;   // nullptr: no flag
     uint32_t *done_count;
     uint32_t done_seq;
+    int out_dev;            // 1: the output is a device MAP SET (k_map2d's DEV form, gvom_combine_maps_device): nine [y][x] maps,
+                            //    out_rough = map 3 and the start of the f64 block (maps 4-8 follow at dev_map_stride(xy) elements)
+                            //    (last member: it sits in what was the struct's tail padding, the other forms' kernel arguments keep their offsets)
 };
+// elements between two maps of a device map set: xy*xy rounded up to 32 (every map starts 256-byte aligned)
+__host__ __device__ __forceinline__ size_t dev_map_stride(int xy) { return ((size_t)xy * xy + 31) & ~(size_t)31; }
 
 // ---- launchers (gvom_trace / _fuse / _map2d / _stats .hip) --------------------------------------------------------
 hipError_t gvom_launch_trace(hipStream_t s, const ScanParams &P, const ShardExchange &X, int dtype, bool big_origin, const void *pts,

@@ -1,7 +1,8 @@
 // gvom_map2d.hip -- the 2-D STAGE of libgvom_hip.so (gfx950, wave64) and the dense read-back / debug kernels, reference gvom.py:
 //
 //   k_map2d   gvom.py:665-734 (slope/roughness), :558-661 (guess height), :489-521 (positive),
-//             :479-485 (negative), :414-422 (visibility); the four returned maps straight into pinned host memory
+//             :479-485 (negative), :414-422 (visibility); the four returned maps straight into pinned host memory,
+//             or (DEV) all nine maps into a map set in device memory
 //   k_posdens sharded maps: the positive-obstacle densities of a rank's own cells (gvom.py:489-521)
 //   k_read_dense, k_unwrap, k_debug_height   test hooks and the debug accessors (gvom.py:356-410)
 //
@@ -46,6 +47,13 @@ __device__ __forceinline__ void st_sys(V *p, V v)
     asm volatile("" ::: "memory");                       // keep the compiler from sinking it to the kernel's end
 }
 
+// a returned map's store: system scope into host memory, or (DEV) a plain store into a device map set
+template <bool DEV, typename V>
+__device__ __forceinline__ void st_out(V *p, V v)
+{
+    if (DEV) *p = v; else st_sys(p, v);
+}
+
 // ------------------------------------------------------------------------------------------
 // k_map2d: every 2-D output of combine_maps from height/inferred height, one lane per cell.
 //
@@ -75,7 +83,13 @@ __device__ __forceinline__ void st_sys(V *p, V v)
 // Waves 0-3 therefore compute ONLY slope / roughness -- LDS data, no global load -- and store the
 // f64 roughness map (40 % of the bytes) while waves 4-7 are still waiting for their density loads;
 // those then store visibility / positive / negative.  The slope-obstacle flag crosses through LDS.
-template <bool GATHERED_POS, bool YX>
+//
+// DEV (with YX, unsharded): the output is a MAP SET in device memory (gvom_combine_maps_device) -- nine xy*xy maps in the
+// same [y][x] order, plain stores, no completion flag.  out_pos / out_neg / out_vis are maps 0-2, out_rough is map 3 and
+// the start of the set's f64 block: maps 4-8 (height, inferred height, x / y slope, guessed delta) follow it at
+// dev_map_stride(xy) elements each.  The storage-order internal maps are written as on every other path.
+
+template <bool GATHERED_POS, bool YX, bool DEV = false>
 __global__ __launch_bounds__(512) void k_map2d(const Map2dParams P, const int32_t *__restrict__ fstate,
                                                const uint32_t *__restrict__ ftags,
                                                const uint4 *__restrict__ frows,
@@ -161,7 +175,8 @@ __global__ __launch_bounds__(512) void k_map2d(const Map2dParams P, const int32_
     // OCC: instead of the four maps, the five int8 nav_msgs/OccupancyGrid.data arrays the ROS node
     // derives from them (gvom_ros.py:141-165), planes [hard | soft | certainty | negative | roughness]
     visv = h00 > -1000 ? 1 : 0;
-    if (YX && wr) { if (P.occ) st_sys(&occ[2 * n2 + c_out], (int8_t)(visv * 100)); else st_sys(&out_vis[c_out], visv); }
+    if (YX && wr) { if (P.occ && !DEV) st_sys(&occ[2 * n2 + c_out], (int8_t)(visv * 100)); else st_out<DEV>(&out_vis[c_out], visv); }
+    if (DEV && wr) out_rough[dev_map_stride(xy) + c_out] = h00;                 // map 4: height
     if (!YX) o_vis[tx][ty] = visv;
     // ---- role A: slope / roughness: 3x3 least-squares plane (gvom.py:665-734) ---------------------
     // cells outside the window hold -1000 in the tile, i.e. are skipped exactly like the
@@ -232,14 +247,15 @@ __global__ __launch_bounds__(512) void k_map2d(const Map2dParams P, const int32_
     }
     slope_x[c_yx] = sxv; slope_y[c_yx] = syv; rough[c_yx] = rv;
     if (YX && wr) {
-        if (P.occ) {
+        if (P.occ && !DEV) {
             // ((clip(r, min, max) + min) / (max - min)) * 100 in f64 as written (it ADDS min), then numpy's
             // float64 -> int8 cast: truncate to a 32-bit integer, keep the low byte (gvom_ros.py:162-163)
             const double rr = ((py_maxd(py_mind(rv, P.occ_max_rough), P.occ_min_rough) + P.occ_min_rough) / (P.occ_max_rough - P.occ_min_rough)) * 100.0;
             const int32_t ri = (fabs(rr) < 2147483648.0) ? (int32_t)rr : INT_MIN;       // x86 cvttsd2si: out of range / NaN -> INT_MIN
             st_sys(&occ[4 * n2 + c_out], (int8_t)(uint8_t)(uint32_t)ri);
-        } else st_sys(&out_rough[c_out], rv);
+        } else st_out<DEV>(&out_rough[c_out], rv);
     }
+    if (DEV && wr) { out_rough[3 * dev_map_stride(xy) + c_out] = sxv; out_rough[4 * dev_map_stride(xy) + c_out] = syv; }   // maps 6, 7
     s_steep[cell] = (sqrt(sxv * sxv + syv * syv) >= P.slope_thr) ? 1 : 0;   // gvom.py:489-521, used by role B
     if (!YX) o_rgh[tx][ty] = rv;
     }   // mine
@@ -296,8 +312,8 @@ __global__ __launch_bounds__(512) void k_map2d(const Map2dParams P, const int32_
     visv = h00 > -1000 ? 1 : 0;                    // gvom.py:414-422 (stored by role A)
     pos = s_steep[cell] ? 100 : dens_pos;                    // gvom.py:489-521 (slope test done by role A)
     if (YX && wr) {
-        if (P.occ) st_sys(&occ[1 * n2 + c_out], (int8_t)(((double)pos <= P.occ_density_thr && pos > 0) ? 100 : 0));   // soft, :146
-        else st_sys(&out_pos[c_out], pos);
+        if (P.occ && !DEV) st_sys(&occ[1 * n2 + c_out], (int8_t)(((double)pos <= P.occ_density_thr && pos > 0) ? 100 : 0));   // soft, :146
+        else st_out<DEV>(&out_pos[c_out], pos);
     }
 
     // ---- guess height (gvom.py:558-661), typos at :581 and :655 reproduced ---------------
@@ -354,11 +370,12 @@ __global__ __launch_bounds__(512) void k_map2d(const Map2dParams P, const int32_
     guessed[c_yx] = dh_out;
     negv = dh_out > P.neg_thr ? 100 : 0;           // gvom.py:479-485
     if (YX && wr) {
-        if (P.occ) {
+        if (P.occ && !DEV) {
             st_sys(&occ[3 * n2 + c_out], (int8_t)negv);                                                    // negative, :157
             st_sys(&occ[0 * n2 + c_out], (int8_t)max((double)pos > P.occ_density_thr ? 100 : 0, negv));   // hard, :141
-        } else st_sys(&out_neg[c_out], negv);
+        } else st_out<DEV>(&out_neg[c_out], negv);
     }
+    if (DEV && wr) { out_rough[2 * dev_map_stride(xy) + c_out] = inf00; out_rough[5 * dev_map_stride(xy) + c_out] = dh_out; }   // maps 5, 8
 
     if (!YX) { o_pos[tx][ty] = pos; o_neg[tx][ty] = negv; }
     }   // role B, mine
@@ -372,7 +389,7 @@ __global__ __launch_bounds__(512) void k_map2d(const Map2dParams P, const int32_
             out_vis[c_xy] = o_vis[ox][oy]; out_rough[c_xy] = o_rgh[ox][oy];
         }
     }
-    if (P.done_flag) {
+    if (!DEV && P.done_flag) {
         // The maps lie in host memory once every wave's stores have been acknowledged (s_waitcnt vmcnt(0): system-scope
         // stores are written through, and what still sat in this XCD's L2 leaves with the workgroup's one release); the flag
         // store of the last workgroup travels the same ordered path behind them.
@@ -522,12 +539,15 @@ hipError_t gvom_launch_map2d(hipStream_t s, const Map2dParams &P, const int32_t 
     if (P.y_hi <= P.y_lo) return hipSuccess;
     const int tx = P.out_yx ? 32 : 8, ty = P.out_yx ? 8 : 32;
     const dim3 grid((P.xy + tx - 1) / tx, (P.xy + ty - 1) / ty);
-#define MAP2D_LAUNCH(G, Y)                                                                              \
-    hipLaunchKernelGGL((k_map2d<G, Y>), grid, dim3(512), 0, s, P, fstate, ftags, frows, height, \
+#define MAP2D_LAUNCH(G, Y, D)                                                                            \
+    hipLaunchKernelGGL((k_map2d<G, Y, D>), grid, dim3(512), 0, s, P, fstate, ftags, frows, height, \
                        inferred, slope_x, slope_y, rough, guessed, out_pos, out_neg, out_rough, out_vis, \
                        blockcounts, nblocks, host_counter)
-    if (P.gathered_pos) { if (P.out_yx) MAP2D_LAUNCH(true, true); else MAP2D_LAUNCH(true, false); }
-    else { if (P.out_yx) MAP2D_LAUNCH(false, true); else MAP2D_LAUNCH(false, false); }
+    if (P.out_dev) {                                      // a device map set: [y][x] order, unsharded, no occupancy grids, no flag
+        if (P.gathered_pos || !P.out_yx || P.occ || P.done_flag) return hipErrorInvalidValue;
+        MAP2D_LAUNCH(false, true, true);
+    } else if (P.gathered_pos) { if (P.out_yx) MAP2D_LAUNCH(true, true, false); else MAP2D_LAUNCH(true, false, false); }
+    else { if (P.out_yx) MAP2D_LAUNCH(false, true, false); else MAP2D_LAUNCH(false, false, false); }
 #undef MAP2D_LAUNCH
     return hipGetLastError();
 }

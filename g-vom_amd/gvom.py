@@ -24,7 +24,7 @@ import threading
 
 import numpy as np
 
-__all__ = ["Gvom", "GvomBackendError", "load_library", "library_path"]
+__all__ = ["Gvom", "GvomBackendError", "DeviceMaps", "DeviceMap", "load_library", "library_path"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -140,6 +140,11 @@ ABI = [
     ("gvom_last_stage_ms", _I, [_P, ctypes.POINTER(ctypes.c_float * N_STAGES)]),
     ("gvom_combine_begin", _I, [_P, _P, _P]),
     ("gvom_combine_end", _I, [_P, _P]),
+    ("gvom_combine_maps_device", _I, [_P, _P, ctypes.POINTER(_I64)]),
+    ("gvom_device_map_export", _I, [_P, _I64, _I, _P, ctypes.POINTER(_P), ctypes.POINTER(_I64)]),
+    ("gvom_device_map_release", _I, [_P, _I64, _P]),
+    ("gvom_device_map_dlpack", _I, [_P, _I64, _I, _P, _I, ctypes.POINTER(_P)]),
+    ("gvom_device_map_copy", _I, [_P, _I64, _I, _P]),
     ("gvom_set_profiling", _I, [_P, _I]),
     ("gvom_host_timing", _I, [_P, ctypes.POINTER(ctypes.c_double * 8)]),
     ("gvom_set_tuning", _I, [_P, ctypes.c_char_p, _I]),
@@ -153,7 +158,7 @@ ABI = [
 ]
 
 
-ABI_VERSION = 8          # include/gvom_hip.h GVOM_ABI_VERSION this binding was written against
+ABI_VERSION = 9          # include/gvom_hip.h GVOM_ABI_VERSION this binding was written against
 
 
 def load_library(path=None):
@@ -203,6 +208,152 @@ class _DeviceArrayView(object):
     def __array__(self, dtype=None):
         a = self._fetch()
         return a if dtype is None else a.astype(dtype)
+
+
+# ---- device-resident maps (Gvom.combine_maps_device) ------------------------------------------
+DEVICE_MAP_NAMES = ("positive", "negative", "visibility", "roughness", "height_map", "inferred_height_map",
+                    "x_slope_map", "y_slope_map", "guessed_height_delta")     # map index 0..8 of a set (include/gvom_hip.h)
+_STREAM_NOSYNC = (1 << 64) - 1            # GVOM_STREAM_NOSYNC
+_KDL_ROCM = 10
+_DLTENSOR, _DLTENSOR_VERSIONED = b"dltensor", b"dltensor_versioned"    # (module constants: a capsule keeps a pointer to its name)
+_DELETER_T = ctypes.CFUNCTYPE(None, ctypes.c_void_p)
+_capi = None
+
+
+def _capsule_api():
+    global _capi
+    if _capi is None:
+        api = ctypes.pythonapi
+        api.PyCapsule_New.restype = ctypes.py_object
+        api.PyCapsule_New.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_void_p]
+        api.PyCapsule_IsValid.restype = ctypes.c_int
+        api.PyCapsule_IsValid.argtypes = [ctypes.c_void_p, ctypes.c_char_p]
+        api.PyCapsule_GetPointer.restype = ctypes.c_void_p
+        api.PyCapsule_GetPointer.argtypes = [ctypes.c_void_p, ctypes.c_char_p]
+        _capi = api
+    return _capi
+
+
+def _capsule_destructor(name, deleter_offset):
+    """PyCapsule destructor: a capsule nobody consumed (a consumer renames it "used_...") still holds an export -- its managed
+    tensor's deleter (C code of the library) releases it."""
+    def dtor(cap):
+        api = _capsule_api()
+        if api.PyCapsule_IsValid(cap, name):
+            managed = api.PyCapsule_GetPointer(cap, name)
+            fn = ctypes.c_void_p.from_address(managed + deleter_offset).value
+            if fn:
+                _DELETER_T(fn)(managed)
+    return _DELETER_T(dtor)
+
+
+# deleter offsets: DLManagedTensor {DLTensor (48 B), manager_ctx, deleter}; DLManagedTensorVersioned {version, manager_ctx, deleter, ...}
+_DTOR_LEGACY = _capsule_destructor(_DLTENSOR, 56)
+_DTOR_VERSIONED = _capsule_destructor(_DLTENSOR_VERSIONED, 16)
+
+
+def _stream_arg(stream):
+    """DLPack stream value -> the library's consumer stream: None = the null stream, an integer = a hipStream_t (torch on ROCm
+    passes 0 for its default stream), -1 = no synchronisation."""
+    if stream is None:
+        return None
+    s = int(stream)
+    if s == -1:
+        return ctypes.c_void_p(_STREAM_NOSYNC)
+    if s < 0:
+        raise ValueError("stream must be None, -1 or a hipStream_t, got %r" % (stream,))
+    return ctypes.c_void_p(s) if s else None
+
+
+class DeviceMap(object):
+    """One map of a device map set: [x, y]-indexed, column-major in device memory (strides (1, xy) in elements).
+    `__dlpack__` hands it to a GPU consumer without a copy (torch.from_dlpack); `copy_to_host()` returns numpy."""
+
+    def __init__(self, maps, which):
+        self._maps = maps
+        self._which = which
+        xy = maps._owner.xy_size
+        self.shape = (xy, xy)
+        self.dtype = np.dtype(np.int32) if which < 3 else np.dtype(np.float64)
+
+    def __dlpack_device__(self):
+        return (_KDL_ROCM, self._maps._owner._device)
+
+    def __dlpack__(self, stream=None, max_version=None, dl_device=None, copy=None):
+        if copy:
+            raise BufferError("copy=True is not supported: the map is shared in place")
+        if dl_device is not None and tuple(int(v) for v in dl_device) != self.__dlpack_device__():
+            raise BufferError("the map lives on %r; no cross-device export" % (self.__dlpack_device__(),))
+        versioned = max_version is not None and int(max_version[0]) >= 1
+        g = self._maps._owner
+        managed = ctypes.c_void_p()
+        g._check(g._lib.gvom_device_map_dlpack(g._h, self._maps.set_id, self._which, _stream_arg(stream), 1 if versioned else 0,
+                                               ctypes.byref(managed)))
+        api = _capsule_api()
+        if versioned:
+            return api.PyCapsule_New(managed.value, _DLTENSOR_VERSIONED, ctypes.cast(_DTOR_VERSIONED, ctypes.c_void_p))
+        return api.PyCapsule_New(managed.value, _DLTENSOR, ctypes.cast(_DTOR_LEGACY, ctypes.c_void_p))
+
+    @property
+    def ptr(self):
+        """Device address of the map."""
+        g = self._maps._owner
+        p, st = ctypes.c_void_p(), (_I64 * 2)()
+        nosync = ctypes.c_void_p(_STREAM_NOSYNC)
+        g._check(g._lib.gvom_device_map_export(g._h, self._maps.set_id, self._which, nosync, ctypes.byref(p), st))
+        g._check(g._lib.gvom_device_map_release(g._h, self._maps.set_id, nosync))
+        return int(p.value)
+
+    def copy_to_host(self):
+        """numpy [x, y] (Fortran order), equal to what combine_maps returns / the attribute of the same name reads."""
+        g = self._maps._owner
+        out = np.empty(self.shape, self.dtype, order="F")
+        g._check(g._lib.gvom_device_map_copy(g._h, self._maps.set_id, self._which, ctypes.c_void_p(out.ctypes.data)))
+        return out
+
+    def __array__(self, dtype=None):
+        a = self.copy_to_host()
+        return a if dtype is None else a.astype(dtype)
+
+
+class DeviceMaps(object):
+    """The result of Gvom.combine_maps_device(): the nine maps of one combine in device memory (one map set), as DeviceMap
+    attributes named after the reference's (DEVICE_MAP_NAMES), `.origin` (f64[3], world) and `.set_id`.  It holds one export
+    of the set -- the set is not reused while it lives -- given back by release(), by leaving a `with` block, or when it is
+    collected.  Tensors taken through DLPack hold exports of their own and stay valid after release() (and after the mapper)."""
+
+    def __init__(self, owner, set_id, origin):
+        self._owner = owner
+        self.set_id = set_id
+        self.origin = origin
+        p, st = ctypes.c_void_p(), (_I64 * 2)()
+        owner._check(owner._lib.gvom_device_map_export(owner._h, set_id, 0, ctypes.c_void_p(_STREAM_NOSYNC), ctypes.byref(p), st))
+        self._held = True
+
+    def __getattr__(self, name):
+        if name in DEVICE_MAP_NAMES:
+            return DeviceMap(self, DEVICE_MAP_NAMES.index(name))
+        raise AttributeError(name)
+
+    def release(self):
+        if self.__dict__.get("_held"):
+            self._held = False
+            g = self._owner
+            if g._h:
+                g._check(g._lib.gvom_device_map_release(g._h, self.set_id, ctypes.c_void_p(_STREAM_NOSYNC)))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.release()
+        return False
+
+    def __del__(self):
+        try:
+            self.release()
+        except Exception:
+            pass
 
 
 class _OutputPool(object):
@@ -356,6 +507,7 @@ class Gvom(object):
         self.ego_semaphore = threading.Semaphore()
         self.metrics = _DeviceArrayView(lambda: np.array([[3, 2]]))
         self._c_order = bool(c_order)
+        self._device = int(device)
         if cuda_f32_sqrt is not None:
             numba_cuda_typing = bool(cuda_f32_sqrt)
 
@@ -512,6 +664,18 @@ class Gvom(object):
             print("[WARNING] The map buffer is empty, nothing will happen!")
             return None
         return out
+
+    def combine_maps_device(self):
+        """combine_maps() with the maps left in device memory (an extension, for consumers on the GPU): advances the fusion
+        exactly like combine_maps() and returns None (empty ring, with the same warning) or a DeviceMaps -- nine maps, each
+        shareable with torch.from_dlpack() without a copy.  Returns once the work is enqueued: no host wait."""
+        origin = np.zeros(3, np.float64)
+        sid = ctypes.c_int64(-1)
+        rc = self._check(self._lib.gvom_combine_maps_device(self._h, _ptr(origin), ctypes.byref(sid)))
+        if rc == GVOM_EMPTY_BUFFER:
+            print("[WARNING] The map buffer is empty, nothing will happen!")
+            return None
+        return DeviceMaps(self, int(sid.value), origin)
 
     def combine_maps_async(self):
         """combine_maps() split in two (an extension; the reference's call is synchronous): enqueues the

@@ -26,7 +26,8 @@
 extern "C" {
 #endif
 
-#define GVOM_ABI_VERSION 8   /* 8: RCCL loopback transport (GVOM_TRANSPORT_LOOPBACK), gvom_comm_wire_stats, gvom_comm_abort;
+#define GVOM_ABI_VERSION 9   /* 9: device-resident maps (gvom_combine_maps_device, map-set exports, DLPack), "device_map_sets";
+                              * 8: RCCL loopback transport (GVOM_TRANSPORT_LOOPBACK), gvom_comm_wire_stats, gvom_comm_abort;
                               * 7: eager fusion of one-slot rings ("eager" knob, gvom_get_tuning "eager_adopted" / "eager_dropped"); a sharded scan /
                               *    combine as ONE native call (gvom_comm_process_pointcloud, gvom_comm_combine_maps_into);
                               * 6: sub-cloud interleave of the trace ("interleave" knob, automatic by a layout probe), gvom_get_tuning;
@@ -46,7 +47,7 @@ extern "C" {
 #define GVOM_ERR_INVALID      -1   /* bad argument */
 #define GVOM_ERR_HIP          -2   /* a HIP runtime call failed; see gvom_last_error() */
 #define GVOM_ERR_NO_DEVICE    -3   /* no usable gfx950 device / library built without GPU */
-#define GVOM_ERR_CAPACITY     -4   /* grid too large for 32-bit voxel indices, or > 64 ring slots */
+#define GVOM_ERR_CAPACITY     -4   /* grid too large for 32-bit voxel indices, or > 64 ring slots, or every device map set exported */
 
 #define GVOM_DTYPE_F32 0
 #define GVOM_DTYPE_F64 1
@@ -195,6 +196,39 @@ int gvom_combine_occupancy_into(gvom_t *h, double origin_world[3], void *pinned_
  * synchronous combines of several threads simply queue up).  Results are those of the synchronous calls. */
 int gvom_combine_begin(gvom_t *h, void *pinned_out, const double *occ);
 int gvom_combine_end(gvom_t *h, double origin_world[3]);
+
+/* --- device-resident maps (an extension: for consumers that run on the GPU too, e.g. a sampling planner) -----------------
+ * gvom_combine_maps_device advances the fusion exactly like gvom_combine_maps (eager adoption, statistics on demand, ring) but
+ * k_map2d writes a MAP SET in device memory instead of host memory, and the call returns once the work is ENQUEUED (no host
+ * wait).  A set holds nine xy*xy maps of the combine, each COLUMN-MAJOR like gvom_combine_maps_into's (cell (x, y) at
+ * [y*xy_size + x]; element strides {1, xy_size} for [x, y] indexing), bit-identical to what the host routes return:
+ *   0 positive i32   1 negative i32   2 visibility i32   3 roughness f64          (the four returned maps)
+ *   4 height f64     5 inferred height f64   6 x slope f64   7 y slope f64   8 guessed height delta f64
+ *                                                              (the attributes gvom_read_map2d reads, unwrapped)
+ * *set_id names the set (a sequence number); GVOM_EMPTY_BUFFER as gvom_combine_maps.  GVOM_ERR_INVALID on a sharded handle
+ * or while a gvom_combine_begin is pending.  60 bytes per cell and set, at most 8 sets per handle ("device_map_sets" of
+ * gvom_get_tuning: how many are allocated); a combine that needs a ninth returns GVOM_ERR_CAPACITY.  A set nobody holds an
+ * export of goes back to the pool when the next device combine begins (its id is stale from then on).  The fused cell
+ * count (gvom_get_state) is read once the combine's kernels have completed: the first call that needs it waits for them. */
+int gvom_combine_maps_device(gvom_t *h, double origin_world[3], int64_t *set_id);
+/* Consumer streams: a hipStream_t as void* (NULL: the null stream), or GVOM_STREAM_NOSYNC -- no ordering at all (the caller
+ * synchronises on its own; its release records nothing). */
+#define GVOM_STREAM_NOSYNC ((void *)(intptr_t)-1)
+/* EXPORT map `which` (0..8) of a set to `consumer_stream`: the stream waits on the set's completion (hipStreamWaitEvent, no host
+ * wait) and the set's export count goes up.  *ptr = the map's device address, strides = {1, xy_size} elements. */
+int gvom_device_map_export(gvom_t *h, int64_t set_id, int which, void *consumer_stream, void **ptr, int64_t strides[2]);
+/* End one export: an event is recorded on `consumer_stream` behind whatever reads it has queued, and the count goes down.  A set
+ * is reused only when its count is 0, and the combine that reuses it first makes the handle's stream wait on every release
+ * event of the set -- a consumer may queue reads and release at once.  Exports OUTLIVE the handle: a set with live exports
+ * stays valid after gvom_destroy and is freed at its last release (through a DLPack deleter then). */
+int gvom_device_map_release(gvom_t *h, int64_t set_id, void *consumer_stream);
+/* DLPack: an export of map `which` to `consumer_stream` wrapped as a DLManagedTensorVersioned (versioned = 1, DLPack 1.0) or a
+ * legacy DLManagedTensor (0): kDLROCM, this handle's device, shape {xy, xy}, strides {1, xy}, int32 or float64.  Its deleter
+ * (C code of this library, no Python and no GIL needed, callable from any thread and after gvom_destroy) performs the release
+ * on that stream.  Unused managed tensors must be deleted through their deleter as well. */
+int gvom_device_map_dlpack(gvom_t *h, int64_t set_id, int which, void *consumer_stream, int versioned, void **managed);
+/* Blocking copy of map `which` of a set into host memory (xy*xy elements, [y*xy_size + x]). */
+int gvom_device_map_copy(gvom_t *h, int64_t set_id, int which, void *host_out);
 
 /* --- one map sharded over the GPUs of a node (one rank = one process = one GPU) -------------------
  * No counterpart in the reference (it has no multi-GPU path); semantics = SURVEY 8(e):

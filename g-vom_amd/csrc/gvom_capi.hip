@@ -69,10 +69,19 @@ struct Fused {
 // ints, S = dev_map_stride(xy): 60 bytes per cell.  A set is handed out by EXPORTS (the consumer stream waits on `ready`) and
 // taken back by RELEASES (an event recorded on the consumer stream); the combine that reuses the set first makes the handle's
 // stream wait on every release event.  A set with live exports outlives the handle (orphan) and is freed at its last release.
+// PRODUCT SETS (gvom_device_product) are the same thing with another KIND of contents: one allocation with a kind and a shape
+// (set_part() below is the only place that knows the layouts), the same ready event, export count, release events and
+// orphaning.  kind 0 = the nine maps; GVOM_PRODUCT_* otherwise:
+//   occupancy        V bytes, out[x][y][z]
+//   voxel cloud      256-byte header (the uint64 row counter k_voxel_cloud adds to), then cap x 8 and cap x 3 floats, each part
+//                    256-byte aligned
+//   height clouds    xy*xy x 7 / x 3 floats
 struct DevSet {
     char *mem = nullptr;
     size_t bytes = 0;
     int device = 0, xy = 0;
+    int kind = 0, zs = 0;                      // GVOM_PRODUCT_* (0: a map set); z_size (occupancy)
+    int64_t cap = 0;                           // voxel cloud: rows the allocation holds
     hipEvent_t ready = nullptr;                // recorded on the handle's stream behind the set's k_map2d
     int64_t id = -1;                           // sequence number of the combine that wrote it; -1: free
     int exports = 0;                           // live exports
@@ -81,6 +90,7 @@ struct DevSet {
     bool orphan = false;                       // the handle is gone
 };
 #define GVOM_MAX_DEVICE_SETS 8
+#define GVOM_N_PRODUCT_KINDS 4
 // DevSet::exports / rel* / orphan: a DLPack deleter runs on whatever thread frees the consumer's tensor, without the handle
 std::mutex g_set_mu;
 
@@ -91,7 +101,7 @@ struct DLTensor { void *data; DLDevice device; int32_t ndim; DLDataType dtype; i
 struct DLManagedTensor { DLTensor dl_tensor; void *manager_ctx; void (*deleter)(DLManagedTensor *); };
 struct DLPackVersion { uint32_t major; uint32_t minor; };
 struct DLManagedTensorVersioned { DLPackVersion version; void *manager_ctx; void (*deleter)(DLManagedTensorVersioned *); uint64_t flags; DLTensor dl_tensor; };
-enum { kDLInt = 0, kDLFloat = 2, kDLROCM = 10 };
+enum { kDLInt = 0, kDLUInt = 1, kDLFloat = 2, kDLROCM = 10 };
 
 }  // namespace
 
@@ -274,6 +284,9 @@ struct gvom_handle {
     // device map sets (gvom_combine_maps_device)
     std::vector<DevSet *> dsets;
     int64_t dset_seq = 0;
+    std::vector<DevSet *> psets;                        // product sets (gvom_device_product), every kind; ids from pset_seq
+    int64_t pset_seq = 0;
+    int tune_occ_clear = 0;                             // gvom_set_tuning "occupancy_clear": 1 = clear the grid, write live tile columns only (A/B)
     bool count_pending = false;                         // the last combine was a device combine: its fused cell count is read
     hipEvent_t ev_dcount = nullptr;                     //   from the host-mapped counter once this event (behind its k_map2d) has completed
 };
@@ -1602,10 +1615,11 @@ VIS void gvom_destroy(gvom_t *h)
         std::vector<DevSet *> idle;
         {
             std::lock_guard<std::mutex> g(g_set_mu);
-            for (DevSet *s : h->dsets) { if (s->exports > 0) s->orphan = true; else idle.push_back(s); }
+            for (std::vector<DevSet *> *v : {&h->dsets, &h->psets})
+                for (DevSet *s : *v) { if (s->exports > 0) s->orphan = true; else idle.push_back(s); }
         }
         for (DevSet *s : idle) set_free(s);
-        h->dsets.clear();
+        h->dsets.clear(); h->psets.clear();
         if (h->ev_dcount) hipEventDestroy(h->ev_dcount);
     }
     for (auto &e : h->ev) if (e) hipEventDestroy(e);
@@ -2075,27 +2089,201 @@ static hipError_t set_release(DevSet *s, void *consumer_stream)
     return e;
 }
 
-static DevSet *find_set(gvom_handle *h, int64_t set_id)
+static DevSet *find_set(const std::vector<DevSet *> &sets, int64_t set_id)
 {
     if (set_id < 0) return nullptr;
-    for (DevSet *s : h->dsets) if (s->id == set_id) return s;
+    for (DevSet *s : sets) if (s->id == set_id) return s;
     return nullptr;
 }
 
-static int set_export(gvom_handle *h, int64_t set_id, int which, void *consumer_stream, DevSet **out_set, void **ptr)
+// ---- what a set holds: the only place that knows the layouts --------------------------------------------------------------
+struct SetPart { void *ptr; int ndim; int64_t shape[3], strides[3]; uint8_t code, bits; size_t bytes; };
+static inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+static size_t set_bytes(int kind, int xy, int zs, int64_t cap)
 {
-    if (which < 0 || which > 8) { h->err = "map index outside 0..8"; return GVOM_ERR_INVALID; }
-    DevSet *s = find_set(h, set_id);
-    if (!s) { h->err = "unknown or stale device map set id"; return GVOM_ERR_INVALID; }
+    const size_t n2 = (size_t)xy * xy;
+    switch (kind) {
+    case 0: return dev_map_stride(xy) * 60;
+    case GVOM_PRODUCT_OCCUPANCY: return n2 * zs;
+    case GVOM_PRODUCT_VOXEL_CLOUD: return 256 + align256((size_t)cap * 32) + align256((size_t)cap * 12);
+    case GVOM_PRODUCT_HEIGHT_CLOUD: return n2 * 28;
+    case GVOM_PRODUCT_INFERRED_HEIGHT_CLOUD: return n2 * 12;
+    }
+    return 0;
+}
+static bool set_part(const DevSet *s, int part, SetPart *d)
+{
+    const int64_t xy = s->xy, n2 = xy * xy;
+    memset(d, 0, sizeof *d);
+    d->ndim = 2; d->code = kDLFloat; d->bits = 32;
+    d->shape[2] = d->strides[2] = 1;
+    auto rows = [&](void *ptr, int64_t n, int64_t cols) { d->ptr = ptr; d->shape[0] = n; d->shape[1] = cols; d->strides[0] = cols; d->strides[1] = 1; };
+    switch (s->kind) {
+    case 0: {                                              // map `part` of a map set: [x, y] indexing, column-major
+        if (part < 0 || part > 8) return false;
+        const size_t S = dev_map_stride(s->xy);
+        d->ptr = part >= 3 ? (void *)((double *)s->mem + (size_t)(part - 3) * S) : (void *)((int32_t *)((double *)s->mem + 6 * S) + (size_t)part * S);
+        d->shape[0] = d->shape[1] = xy; d->strides[0] = 1; d->strides[1] = xy;
+        d->code = part >= 3 ? kDLFloat : kDLInt; d->bits = part >= 3 ? 64 : 32;
+        break;
+    }
+    case GVOM_PRODUCT_OCCUPANCY:
+        if (part != 0) return false;
+        d->ptr = s->mem; d->ndim = 3; d->code = kDLUInt; d->bits = 8;
+        d->shape[0] = d->shape[1] = xy; d->shape[2] = s->zs;
+        d->strides[0] = xy * s->zs; d->strides[1] = s->zs; d->strides[2] = 1;
+        break;
+    case GVOM_PRODUCT_VOXEL_CLOUD:
+        if (part == 0) rows(s->mem + 256, s->cap, 8);
+        else if (part == 1) rows(s->mem + 256 + align256((size_t)s->cap * 32), s->cap, 3);
+        else if (part == 2) { d->ptr = s->mem; d->ndim = 1; d->shape[0] = 1; d->strides[0] = 1; d->shape[1] = d->strides[1] = 1; d->code = kDLInt; d->bits = 64; }
+        else return false;
+        break;
+    case GVOM_PRODUCT_HEIGHT_CLOUD: if (part != 0) return false; rows(s->mem, n2, 7); break;
+    case GVOM_PRODUCT_INFERRED_HEIGHT_CLOUD: if (part != 0) return false; rows(s->mem, n2, 3); break;
+    default: return false;
+    }
+    d->bytes = (size_t)(d->shape[0] * d->shape[1] * d->shape[2]) * (d->bits / 8);
+    return true;
+}
+
+// ---- pool: a free set of the kind (and size), or a new one ------------------------------------------------------------------
+// sets of `kind` nobody holds an export of go back to the pool (their ids are stale from here on); returns one that holds
+// `bytes`, or nullptr.  Free sets of the kind that are too small are given up.
+static DevSet *set_recycle(std::vector<DevSet *> &sets, int kind, size_t bytes)
+{
+    DevSet *set = nullptr;
+    std::vector<DevSet *> small;
+    {
+        std::lock_guard<std::mutex> g(g_set_mu);
+        for (size_t k = 0; k < sets.size();) {
+            DevSet *s = sets[k];
+            if (s->kind == kind && s->exports == 0) {
+                s->id = -1;
+                if (s->bytes < bytes) { small.push_back(s); sets.erase(sets.begin() + (long)k); continue; }
+                if (!set) set = s;
+            }
+            ++k;
+        }
+    }
+    for (DevSet *s : small) set_free(s);
+    return set;
+}
+static int set_new(gvom_handle *h, std::vector<DevSet *> &sets, int kind, size_t bytes, DevSet **out)
+{
+    DevSet *s = new DevSet;
+    s->device = h->device; s->xy = h->prm.xy_size; s->zs = h->prm.z_size; s->kind = kind;
+    s->bytes = bytes;
+    hipError_t e = hipMalloc((void **)&s->mem, s->bytes);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&s->ready, hipEventDisableTiming);
+    if (e != hipSuccess) { set_free(s); HIPCHK(h, e); }
+    sets.push_back(s);
+    *out = s;
+    return GVOM_OK;
+}
+// a reused set: its consumers' reads come first (the handle's stream waits on every release event)
+static int set_wait_releases(gvom_handle *h, DevSet *set)
+{
+    std::lock_guard<std::mutex> g(g_set_mu);
+    for (hipEvent_t e : set->rel) HIPCHK(h, hipStreamWaitEvent(h->stream, e, 0));
+    set->rel_spare.insert(set->rel_spare.end(), set->rel.begin(), set->rel.end());
+    set->rel.clear(); set->rel_streams.clear();
+    return GVOM_OK;
+}
+
+// ---- exports, releases, DLPack, host copies: the same for every kind (`maps`: which of the handle's two id spaces) -------------
+static int set_export(gvom_handle *h, bool maps, int64_t set_id, int part, void *consumer_stream, DevSet **out_set, SetPart *d)
+{
+    DevSet *s = find_set(maps ? h->dsets : h->psets, set_id);
+    if (maps && (part < 0 || part > 8)) { h->err = "map index outside 0..8"; return GVOM_ERR_INVALID; }
+    if (!s) { h->err = maps ? "unknown or stale device map set id" : "unknown or stale device product id"; return GVOM_ERR_INVALID; }
+    if (!set_part(s, part, d)) { h->err = "part index outside the parts of this device product"; return GVOM_ERR_INVALID; }
     HIPCHK(h, hipSetDevice(h->device));
     if (consumer_stream != GVOM_STREAM_NOSYNC) HIPCHK(h, hipStreamWaitEvent((hipStream_t)consumer_stream, s->ready, 0));
     {
         std::lock_guard<std::mutex> g(g_set_mu);
         ++s->exports;
     }
-    const size_t S = dev_map_stride(s->xy);
-    *ptr = which >= 3 ? (void *)((double *)s->mem + (size_t)(which - 3) * S) : (void *)((int32_t *)((double *)s->mem + 6 * S) + (size_t)which * S);
     *out_set = s;
+    return GVOM_OK;
+}
+
+static int set_release_id(gvom_handle *h, bool maps, int64_t set_id, void *consumer_stream)
+{
+    DevSet *s = find_set(maps ? h->dsets : h->psets, set_id);
+    if (!s) { h->err = maps ? "unknown or stale device map set id" : "unknown or stale device product id"; return GVOM_ERR_INVALID; }
+    {
+        std::lock_guard<std::mutex> g(g_set_mu);
+        if (s->exports == 0) { h->err = maps ? "gvom_device_map_release: the set has no live export" : "gvom_device_product_release: the product has no live export"; return GVOM_ERR_INVALID; }
+    }
+    HIPCHK(h, set_release(s, consumer_stream));
+    return GVOM_OK;
+}
+
+// the manager context of one DLPack export: the set, the consumer stream its release is recorded on, shape and strides
+struct DlpackCtx {
+    DevSet *set;
+    void *stream;
+    int64_t shape[3], strides[3];
+    DLManagedTensor legacy;
+    DLManagedTensorVersioned versioned;
+};
+static void dlpack_delete_legacy(DLManagedTensor *m)
+{
+    DlpackCtx *c = (DlpackCtx *)m->manager_ctx;
+    set_release(c->set, c->stream);
+    delete c;
+}
+static void dlpack_delete_versioned(DLManagedTensorVersioned *m)
+{
+    DlpackCtx *c = (DlpackCtx *)m->manager_ctx;
+    set_release(c->set, c->stream);
+    delete c;
+}
+
+static int set_dlpack(gvom_handle *h, bool maps, int64_t set_id, int part, void *consumer_stream, int versioned, void **managed)
+{
+    DevSet *s = nullptr;
+    SetPart d;
+    const int rc = set_export(h, maps, set_id, part, consumer_stream, &s, &d);
+    if (rc) return rc;
+    DlpackCtx *c = new DlpackCtx();
+    c->set = s; c->stream = consumer_stream;
+    for (int k = 0; k < 3; ++k) { c->shape[k] = d.shape[k]; c->strides[k] = d.strides[k]; }
+    DLTensor t;
+    t.data = d.ptr;
+    t.device.device_type = kDLROCM; t.device.device_id = h->device;
+    t.ndim = d.ndim;
+    t.dtype.code = d.code; t.dtype.bits = d.bits; t.dtype.lanes = 1;
+    t.shape = c->shape; t.strides = c->strides;
+    t.byte_offset = 0;
+    if (versioned) {
+        c->versioned.version.major = 1; c->versioned.version.minor = 0;
+        c->versioned.manager_ctx = c;
+        c->versioned.deleter = dlpack_delete_versioned;
+        c->versioned.flags = 0;
+        c->versioned.dl_tensor = t;
+        *managed = &c->versioned;
+    } else {
+        c->legacy.dl_tensor = t;
+        c->legacy.manager_ctx = c;
+        c->legacy.deleter = dlpack_delete_legacy;
+        *managed = &c->legacy;
+    }
+    return GVOM_OK;
+}
+
+static int set_copy(gvom_handle *h, bool maps, int64_t set_id, int part, void *host_out)
+{
+    DevSet *s = nullptr;
+    SetPart d;
+    int rc = set_export(h, maps, set_id, part, GVOM_STREAM_NOSYNC, &s, &d);
+    if (rc) return rc;
+    hipError_t e = hipEventSynchronize(s->ready);
+    const size_t bytes = maps ? h->cells2d * (d.bits / 8) : d.bytes;      // (a map: xy*xy elements, without the set's padding)
+    if (e == hipSuccess && bytes) e = hipMemcpy(host_out, d.ptr, bytes, hipMemcpyDeviceToHost);
+    set_release(s, GVOM_STREAM_NOSYNC);
+    HIPCHK(h, e);
     return GVOM_OK;
 }
 
@@ -2110,35 +2298,20 @@ VIS int gvom_combine_maps_device(gvom_t *h, double origin_world[3], int64_t *set
     double t0 = now_ns();
     *set_id = -1;
     // unused sets go back to the pool; then a free one, or a new one (at most GVOM_MAX_DEVICE_SETS)
-    DevSet *set = nullptr;
-    {
-        std::lock_guard<std::mutex> g(g_set_mu);
-        for (DevSet *s : h->dsets) if (s->exports == 0) { s->id = -1; if (!set) set = s; }
-    }
+    DevSet *set = set_recycle(h->dsets, 0, 0);
     if (!set && !h->slots[h->ring[h->last_buffer_index]].filled) return GVOM_EMPTY_BUFFER;
     if (!set) {
         if ((int)h->dsets.size() >= GVOM_MAX_DEVICE_SETS) {
             h->err = "gvom_combine_maps_device: all 8 device map sets are exported; release some (gvom_device_map_release, or drop the tensors)";
             return GVOM_ERR_CAPACITY;
         }
-        DevSet *s = new DevSet;
-        s->device = h->device; s->xy = h->prm.xy_size;
-        s->bytes = dev_map_stride(s->xy) * 60;
-        hipError_t e = hipMalloc((void **)&s->mem, s->bytes);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&s->ready, hipEventDisableTiming);
-        if (e != hipSuccess) { set_free(s); HIPCHK(h, e); }
-        h->dsets.push_back(s);
-        set = s;
+        const int rc0 = set_new(h, h->dsets, 0, set_bytes(0, h->prm.xy_size, 0, 0), &set);
+        if (rc0) return rc0;
     }
     if (!h->ev_dcount) HIPCHK(h, hipEventCreateWithFlags(&h->ev_dcount, hipEventDisableTiming));
     int rc = fuse_impl(h);
     if (rc) return rc;
-    {   // a reused set: its consumers' reads come first
-        std::lock_guard<std::mutex> g(g_set_mu);
-        for (hipEvent_t e : set->rel) HIPCHK(h, hipStreamWaitEvent(h->stream, e, 0));
-        set->rel_spare.insert(set->rel_spare.end(), set->rel.begin(), set->rel.end());
-        set->rel.clear(); set->rel_streams.clear();
-    }
+    if ((rc = set_wait_releases(h, set))) return rc;
     if ((rc = map2d_impl(h, false, true, set->mem, true, nullptr, nullptr, 0, true))) return rc;
     HIPCHK(h, hipEventRecord(set->ready, h->stream));
     HIPCHK(h, hipEventRecord(h->ev_dcount, h->stream));
@@ -2160,9 +2333,11 @@ VIS int gvom_device_map_export(gvom_t *h, int64_t set_id, int which, void *consu
     if (!h || !ptr || !strides) return GVOM_ERR_INVALID;
     std::lock_guard<std::mutex> lk(h->mu);
     DevSet *s = nullptr;
-    const int rc = set_export(h, set_id, which, consumer_stream, &s, ptr);
+    SetPart d;
+    const int rc = set_export(h, true, set_id, which, consumer_stream, &s, &d);
     if (rc) return rc;
-    strides[0] = 1; strides[1] = h->prm.xy_size;
+    *ptr = d.ptr;
+    strides[0] = d.strides[0]; strides[1] = d.strides[1];
     return GVOM_OK;
 }
 
@@ -2170,85 +2345,160 @@ VIS int gvom_device_map_release(gvom_t *h, int64_t set_id, void *consumer_stream
 {
     if (!h) return GVOM_ERR_INVALID;
     std::lock_guard<std::mutex> lk(h->mu);
-    DevSet *s = find_set(h, set_id);
-    if (!s) { h->err = "unknown or stale device map set id"; return GVOM_ERR_INVALID; }
-    {
-        std::lock_guard<std::mutex> g(g_set_mu);
-        if (s->exports == 0) { h->err = "gvom_device_map_release: the set has no live export"; return GVOM_ERR_INVALID; }
-    }
-    HIPCHK(h, set_release(s, consumer_stream));
-    return GVOM_OK;
-}
-
-// the manager context of one DLPack export: the set, the consumer stream its release is recorded on, shape and strides
-struct DlpackCtx {
-    DevSet *set;
-    void *stream;
-    int64_t shape[2], strides[2];
-    DLManagedTensor legacy;
-    DLManagedTensorVersioned versioned;
-};
-static void dlpack_delete_legacy(DLManagedTensor *m)
-{
-    DlpackCtx *c = (DlpackCtx *)m->manager_ctx;
-    set_release(c->set, c->stream);
-    delete c;
-}
-static void dlpack_delete_versioned(DLManagedTensorVersioned *m)
-{
-    DlpackCtx *c = (DlpackCtx *)m->manager_ctx;
-    set_release(c->set, c->stream);
-    delete c;
+    return set_release_id(h, true, set_id, consumer_stream);
 }
 
 VIS int gvom_device_map_dlpack(gvom_t *h, int64_t set_id, int which, void *consumer_stream, int versioned, void **managed)
 {
     if (!h || !managed) return GVOM_ERR_INVALID;
     std::lock_guard<std::mutex> lk(h->mu);
-    DevSet *s = nullptr;
-    void *ptr = nullptr;
-    const int rc = set_export(h, set_id, which, consumer_stream, &s, &ptr);
-    if (rc) return rc;
-    DlpackCtx *c = new DlpackCtx();
-    c->set = s; c->stream = consumer_stream;
-    c->shape[0] = c->shape[1] = h->prm.xy_size;
-    c->strides[0] = 1; c->strides[1] = h->prm.xy_size;
-    DLTensor t;
-    t.data = ptr;
-    t.device.device_type = kDLROCM; t.device.device_id = h->device;
-    t.ndim = 2;
-    t.dtype.code = which >= 3 ? kDLFloat : kDLInt; t.dtype.bits = which >= 3 ? 64 : 32; t.dtype.lanes = 1;
-    t.shape = c->shape; t.strides = c->strides;
-    t.byte_offset = 0;
-    if (versioned) {
-        c->versioned.version.major = 1; c->versioned.version.minor = 0;
-        c->versioned.manager_ctx = c;
-        c->versioned.deleter = dlpack_delete_versioned;
-        c->versioned.flags = 0;
-        c->versioned.dl_tensor = t;
-        *managed = &c->versioned;
-    } else {
-        c->legacy.dl_tensor = t;
-        c->legacy.manager_ctx = c;
-        c->legacy.deleter = dlpack_delete_legacy;
-        *managed = &c->legacy;
-    }
-    return GVOM_OK;
+    return set_dlpack(h, true, set_id, which, consumer_stream, versioned, managed);
 }
 
 VIS int gvom_device_map_copy(gvom_t *h, int64_t set_id, int which, void *host_out)
 {
     if (!h || !host_out) return GVOM_ERR_INVALID;
     std::lock_guard<std::mutex> lk(h->mu);
-    DevSet *s = nullptr;
-    void *ptr = nullptr;
-    int rc = set_export(h, set_id, which, GVOM_STREAM_NOSYNC, &s, &ptr);
+    return set_copy(h, true, set_id, which, host_out);
+}
+
+// ---- device-resident 3-D products (gvom_device_product) ----------------------------------------------------------------------
+// A snapshot of the current fused map (occupancy grid, voxel cloud) or of the last combine's 2-D maps (the two height clouds),
+// written into a product set on the handle's stream behind whatever produced its inputs; the call enqueues and returns.  Later
+// scans and combines never touch a product: it is a copy, reused only once nobody holds an export of it and behind its
+// consumers' release events.
+static void occ_params(const gvom_handle *h, const Fused &F, OccParams &P)
+{
+    memset(&P, 0, sizeof P);
+    P.xy = h->prm.xy_size; P.zs = h->prm.z_size;
+    P.om[0] = (int)floor_mod(F.origin[0], h->prm.xy_size);
+    P.om[1] = (int)floor_mod(F.origin[1], h->prm.xy_size);
+    P.om[2] = (int)floor_mod(F.origin[2], h->prm.z_size);
+    P.y_lo = h->sy_lo; P.y_hi = h->sy_hi;
+    P.nseg = h->nseg; P.epoch = F.epoch;
+}
+
+static void cloud_params(const gvom_handle *h, const Fused &F, Map2dParams &P)
+{
+    const gvom_params &p = h->prm;
+    memset(&P, 0, sizeof P);
+    P.xy = p.xy_size; P.zs = p.z_size;
+    P.om[0] = (int)floor_mod(F.origin[0], p.xy_size);
+    P.om[1] = (int)floor_mod(F.origin[1], p.xy_size);
+    P.om[2] = (int)floor_mod(F.origin[2], p.z_size);
+    P.y_lo = h->sy_lo; P.y_hi = h->sy_hi;
+    P.xy_res = p.xy_resolution; P.z_res = p.z_resolution;
+    P.nseg = h->nseg; P.epoch = F.epoch;
+}
+
+static hipError_t launch_height_cloud(gvom_handle *h, const Fused &F, float *out7, float *out3)
+{
+    const double org[3] = {(double)F.origin[0], (double)F.origin[1], (double)F.origin[2]};
+    return gvom_launch_debug_height(h->stream, h->prm.xy_size, (int)floor_mod(F.origin[0], h->prm.xy_size),
+                                    (int)floor_mod(F.origin[1], h->prm.xy_size), org, h->prm.xy_resolution, h->prm.z_resolution,
+                                    h->height, h->hs, h->rough, h->slope_x, h->slope_y, out7, h->guessed, out3);
+}
+
+VIS int gvom_device_product(gvom_t *h, int kind, int64_t max_rows, int64_t *product_id)
+{
+    if (!h || !product_id) return GVOM_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(h->mu);
+    *product_id = -1;
+    if (kind < 1 || kind > GVOM_N_PRODUCT_KINDS) { h->err = "gvom_device_product: unknown product kind"; return GVOM_ERR_INVALID; }
+    if (h->sharded) { h->err = "gvom_device_product: sharded handles are not supported"; return GVOM_ERR_INVALID; }
+    if (kind == GVOM_PRODUCT_VOXEL_CLOUD) stats_demand(h);                  // a read of the statistics, like gvom_debug_voxel_map
+    if (!h->has_combined) return GVOM_NO_DATA;
+    if ((kind == GVOM_PRODUCT_HEIGHT_CLOUD || kind == GVOM_PRODUCT_INFERRED_HEIGHT_CLOUD) && !h->maps_valid) return GVOM_NO_DATA;
+    if (kind == GVOM_PRODUCT_VOXEL_CLOUD && !h->fused[h->cur].has_metrics) return GVOM_NO_DATA;
+    HIPCHK(h, hipSetDevice(h->device));
+    int64_t cap = 0;
+    if (kind == GVOM_PRODUCT_VOXEL_CLOUD) {
+        cap = max_rows;
+        if (cap <= 0) {                                                      // the fused cell count (settles a device combine's pending count)
+            const int rc0 = settle_count(h);
+            if (rc0) return rc0;
+            cap = h->combined_cell_count;
+        }
+        if (cap < 1) cap = 1;
+    }
+    const int xy = h->prm.xy_size, zs = h->prm.z_size;
+    DevSet *set = set_recycle(h->psets, kind, set_bytes(kind, xy, zs, cap));
+    if (!set) {
+        int n = 0;
+        for (DevSet *s : h->psets) n += s->kind == kind;
+        if (n >= GVOM_MAX_PRODUCT_SETS) {
+            h->err = "gvom_device_product: all 4 device product sets of this kind are exported; release some (gvom_device_product_release, or drop the tensors)";
+            return GVOM_ERR_CAPACITY;
+        }
+        const int rc0 = set_new(h, h->psets, kind, set_bytes(kind, xy, zs, cap + cap / 2), &set);   // (a cloud grows with the map: headroom)
+        if (rc0) return rc0;
+    }
+    set->cap = cap;
+    const Fused &F = h->fused[h->cur];
+    HIPCHK(h, join_second_stream(h));
+    int rc = set_wait_releases(h, set);
     if (rc) return rc;
-    hipError_t e = hipEventSynchronize(s->ready);
-    if (e == hipSuccess) e = hipMemcpy(host_out, ptr, h->cells2d * (which >= 3 ? 8 : 4), hipMemcpyDeviceToHost);
-    set_release(s, GVOM_STREAM_NOSYNC);
-    HIPCHK(h, e);
+    SetPart d;
+    switch (kind) {
+    case GVOM_PRODUCT_OCCUPANCY: {
+        OccParams P;
+        occ_params(h, F, P);
+        HIPCHK(h, gvom_launch_occupancy(h->stream, P, F.state, F.tags, (uint8_t *)set->mem, h->tune_occ_clear != 0));
+        break;
+    }
+    case GVOM_PRODUCT_VOXEL_CLOUD: {
+        Map2dParams P;
+        cloud_params(h, F, P);
+        SetPart e;
+        set_part(set, 0, &d); set_part(set, 1, &e);
+        HIPCHK(h, hipMemsetAsync(set->mem, 0, 8, h->stream));
+        HIPCHK(h, gvom_launch_voxel_cloud(h->stream, P, (double)F.origin[0], (double)F.origin[1], (double)F.origin[2], F.state, F.tags,
+                                          (const uint4 *)F.rows.p, (const float *)F.metrics.p, (float *)d.ptr, (float *)e.ptr, cap,
+                                          (unsigned long long *)set->mem));
+        break;
+    }
+    case GVOM_PRODUCT_HEIGHT_CLOUD: HIPCHK(h, launch_height_cloud(h, F, (float *)set->mem, nullptr)); break;
+    default: HIPCHK(h, launch_height_cloud(h, F, nullptr, (float *)set->mem)); break;
+    }
+    HIPCHK(h, hipEventRecord(set->ready, h->stream));
+    set->id = ++h->pset_seq;
+    *product_id = set->id;
     return GVOM_OK;
+}
+
+VIS int gvom_device_product_export(gvom_t *h, int64_t product_id, int part, void *consumer_stream, void **ptr, int32_t *ndim,
+                                   int64_t shape[3], int64_t strides[3])
+{
+    if (!h || !ptr || !ndim || !shape || !strides) return GVOM_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(h->mu);
+    DevSet *s = nullptr;
+    SetPart d;
+    const int rc = set_export(h, false, product_id, part, consumer_stream, &s, &d);
+    if (rc) return rc;
+    *ptr = d.ptr; *ndim = d.ndim;
+    for (int k = 0; k < 3; ++k) { shape[k] = d.shape[k]; strides[k] = d.strides[k]; }
+    return GVOM_OK;
+}
+
+VIS int gvom_device_product_release(gvom_t *h, int64_t product_id, void *consumer_stream)
+{
+    if (!h) return GVOM_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(h->mu);
+    return set_release_id(h, false, product_id, consumer_stream);
+}
+
+VIS int gvom_device_product_dlpack(gvom_t *h, int64_t product_id, int part, void *consumer_stream, int versioned, void **managed)
+{
+    if (!h || !managed) return GVOM_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(h->mu);
+    return set_dlpack(h, false, product_id, part, consumer_stream, versioned, managed);
+}
+
+VIS int gvom_device_product_copy(gvom_t *h, int64_t product_id, int part, void *host_out)
+{
+    if (!h || !host_out) return GVOM_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(h->mu);
+    return set_copy(h, false, product_id, part, host_out);
 }
 
 // ---- split combine for the sharded layer (g-vom_amd/gvom_sharded.py) ---------------------
@@ -2510,23 +2760,24 @@ VIS int gvom_read_map2d(gvom_t *h, int which2d, double *out)
     return GVOM_OK;
 }
 
+// reference: lookup.reshape((xy, xy, z), order='F') >= 0  -> out[x][y][z] (gvom.py:356-361): k_occupancy, then one copy of V bytes
 VIS int gvom_get_occupancy(gvom_t *h, uint8_t *out_xyz)
 {
     if (!h || !out_xyz) return GVOM_ERR_INVALID;
-    std::vector<int32_t> st;
-    {
-        std::lock_guard<std::mutex> lk(h->mu);
-        if (!h->has_combined) return GVOM_NO_DATA;
-        st.resize(h->V);
-    }
-    int rc = gvom_read_dense(h, GVOM_WHICH_FUSED, st.data(), nullptr, nullptr, nullptr, nullptr, nullptr);
-    if (rc) return rc;
-    const int xy = h->prm.xy_size, zs = h->prm.z_size;
-    // reference: lookup.reshape((xy, xy, z), order='F') >= 0  -> out[x][y][z]
-    for (int x = 0; x < xy; ++x)
-        for (int y = 0; y < xy; ++y)
-            for (int z = 0; z < zs; ++z)
-                out_xyz[((size_t)x * xy + y) * zs + z] = st[(size_t)x + (size_t)y * xy + (size_t)z * xy * xy] >= 0;
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (!h->has_combined) return GVOM_NO_DATA;
+    HIPCHK(h, hipSetDevice(h->device));
+    const Fused &F = h->fused[h->cur];
+    OccParams P;
+    occ_params(h, F, P);
+    uint8_t *tmp = nullptr;
+    HIPCHK(h, hipMalloc((void **)&tmp, h->V));
+    hipError_t e = join_second_stream(h);
+    if (e == hipSuccess) e = gvom_launch_occupancy(h->stream, P, F.state, F.tags, tmp, h->tune_occ_clear != 0);
+    if (e == hipSuccess) e = sync_streams(h);
+    if (e == hipSuccess) e = hipMemcpy(out_xyz, tmp, h->V, hipMemcpyDeviceToHost);
+    hipFree(tmp);
+    HIPCHK(h, e);
     return GVOM_OK;
 }
 
@@ -2676,6 +2927,7 @@ VIS int gvom_set_tuning(gvom_t *h, const char *name, int value)
     else if (!strcmp(name, "dirsort")) h->tune_dirsort = value;
     else if (!strcmp(name, "fastdiv")) h->tune_fastdiv = value;
     else if (!strcmp(name, "eager")) { h->tune_eager = value; h->eager_waste = 0; }
+    else if (!strcmp(name, "occupancy_clear")) h->tune_occ_clear = value;   // k_occupancy: 1 = clear the grid first, write live tile columns only
     else if (!strcmp(name, "exported")) h->exported = value != 0;       // (set by the peer transport, gvom_comm.hip)
 #ifdef GVOM_HOOKS
     // test hooks (include/gvom_hip_test.h; lib/libgvom_hip_test.so only)
@@ -2698,6 +2950,8 @@ VIS int gvom_get_tuning(gvom_t *h, const char *name, int *value)
     if (!strcmp(name, "eager_dropped")) { *value = h->eager_stat[1]; return GVOM_OK; }
     if (!strcmp(name, "fuse_kernel")) { *value = h->last_fuse; return GVOM_OK; }
     if (!strcmp(name, "device_map_sets")) { *value = (int)h->dsets.size(); return GVOM_OK; }             // read-only: allocated device map sets                  // read-only, GVOM_ROUTE_*
+    if (!strcmp(name, "device_product_sets")) { *value = (int)h->psets.size(); return GVOM_OK; }        // read-only: allocated device product sets (every kind)
+    if (!strcmp(name, "occupancy_clear")) { *value = h->tune_occ_clear; return GVOM_OK; }
     if (!strcmp(name, "fastdiv")) { *value = h->tune_fastdiv == 0 ? 0 : h->fastdiv_ok; return GVOM_OK; }   // bit 0 / 1: xy / z resolution divided by reciprocal
     return GVOM_ERR_INVALID;
 }

@@ -185,7 +185,17 @@ struct Map2dParams {
 // elements between two maps of a device map set: xy*xy rounded up to 32 (every map starts 256-byte aligned)
 __host__ __device__ __forceinline__ size_t dev_map_stride(int xy) { return ((size_t)xy * xy + 31) & ~(size_t)31; }
 
-// ---- launchers (gvom_trace / _fuse / _map2d / _stats .hip) --------------------------------------------------------
+// k_occupancy (gvom_products.hip): the fused map as the dense uint8 grid out[x][y][z] of gvom.py:356-361
+#define GVOM_OCC_ZC 128         // window z levels per workgroup (a 128-byte run of every output row)
+struct OccParams {
+    int xy, zs;
+    int om[3];              // fused origin mod size
+    int y_lo, y_hi;         // STORAGE rows this handle holds (the others read as empty)
+    int nseg;
+    uint32_t epoch;         // epoch of the fused map (tile liveness)
+};
+
+// ---- launchers (gvom_trace / _fuse / _map2d / _stats / _products .hip) ---------------------------------------------
 hipError_t gvom_launch_trace(hipStream_t s, const ScanParams &P, const ShardExchange &X, int dtype, bool big_origin, const void *pts,
                              int64_t stride_elems, int64_t n, void *world, uint32_t *hit,
                              uint32_t *total, uint32_t *mh, int32_t *state, uint32_t *tags,
@@ -246,6 +256,10 @@ hipError_t gvom_launch_read_dense(hipStream_t s, int xy, int zs, const int om[3]
                                   const uint32_t *tags, uint32_t epoch, const int32_t *state, const uint4 *crows,
                                   int32_t *o_state,
                                   int32_t *o_hit, int32_t *o_total, float *o_minh, int32_t *o_row);
+// out[x][y][z] (window order, C-contiguous, V bytes) = 1 where the fused voxel is occupied.  clear_first: the grid is cleared
+// with hipMemsetAsync and only tile columns with a live tile are written (otherwise the kernel writes every byte itself)
+hipError_t gvom_launch_occupancy(hipStream_t s, const OccParams &P, const int32_t *fstate, const uint32_t *ftags, uint8_t *out,
+                                 bool clear_first);
 // storage order [sy][sx] -> reference order [x][y] (window coordinates)
 hipError_t gvom_launch_unwrap_f64(hipStream_t s, int xy, int om0, int om1, const double *in, int in_stride, double *out_xy);
 hipError_t gvom_launch_posdens(hipStream_t s, const Map2dParams &P, const int32_t *fstate,

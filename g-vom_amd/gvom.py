@@ -24,7 +24,7 @@ import threading
 
 import numpy as np
 
-__all__ = ["Gvom", "GvomBackendError", "DeviceMaps", "DeviceMap", "load_library", "library_path"]
+__all__ = ["Gvom", "GvomBackendError", "DeviceMaps", "DeviceMap", "DeviceArray", "DeviceVoxelCloud", "load_library", "library_path"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -145,6 +145,12 @@ ABI = [
     ("gvom_device_map_release", _I, [_P, _I64, _P]),
     ("gvom_device_map_dlpack", _I, [_P, _I64, _I, _P, _I, ctypes.POINTER(_P)]),
     ("gvom_device_map_copy", _I, [_P, _I64, _I, _P]),
+    ("gvom_device_product", _I, [_P, _I, _I64, ctypes.POINTER(_I64)]),
+    ("gvom_device_product_export", _I, [_P, _I64, _I, _P, ctypes.POINTER(_P), ctypes.POINTER(ctypes.c_int32),
+                                        ctypes.POINTER(_I64), ctypes.POINTER(_I64)]),
+    ("gvom_device_product_release", _I, [_P, _I64, _P]),
+    ("gvom_device_product_dlpack", _I, [_P, _I64, _I, _P, _I, ctypes.POINTER(_P)]),
+    ("gvom_device_product_copy", _I, [_P, _I64, _I, _P]),
     ("gvom_set_profiling", _I, [_P, _I]),
     ("gvom_host_timing", _I, [_P, ctypes.POINTER(ctypes.c_double * 8)]),
     ("gvom_set_tuning", _I, [_P, ctypes.c_char_p, _I]),
@@ -158,7 +164,7 @@ ABI = [
 ]
 
 
-ABI_VERSION = 9          # include/gvom_hip.h GVOM_ABI_VERSION this binding was written against
+ABI_VERSION = 10         # include/gvom_hip.h GVOM_ABI_VERSION this binding was written against
 
 
 def load_library(path=None):
@@ -354,6 +360,137 @@ class DeviceMaps(object):
             self.release()
         except Exception:
             pass
+
+
+# ---- device-resident 3-D products (Gvom.occupancy_grid_device and friends) ----------------------------------------
+PRODUCT_OCCUPANCY, PRODUCT_VOXEL_CLOUD, PRODUCT_HEIGHT_CLOUD, PRODUCT_INFERRED_HEIGHT_CLOUD = 1, 2, 3, 4    # include/gvom_hip.h
+_PRODUCT_DTYPES = {(PRODUCT_OCCUPANCY, 0): np.uint8, (PRODUCT_VOXEL_CLOUD, 0): np.float32, (PRODUCT_VOXEL_CLOUD, 1): np.float32,
+                   (PRODUCT_VOXEL_CLOUD, 2): np.int64, (PRODUCT_HEIGHT_CLOUD, 0): np.float32,
+                   (PRODUCT_INFERRED_HEIGHT_CLOUD, 0): np.float32}
+
+
+class _ProductHold(object):
+    """One export of a device product, held for as long as the Python object that shows it lives: the product's set is not
+    reused meanwhile.  Given back by release() or on collection."""
+
+    def __init__(self, owner, kind, product_id):
+        self.owner, self.kind, self.product_id = owner, kind, product_id
+        self.describe(0, hold=True)
+        self.held = True
+
+    def describe(self, part, hold=False):
+        """(device address, shape, strides in elements) of a part; hold=True keeps the export it takes."""
+        g = self.owner
+        p, nd, sh, st = ctypes.c_void_p(), ctypes.c_int32(0), (_I64 * 3)(), (_I64 * 3)()
+        nosync = ctypes.c_void_p(_STREAM_NOSYNC)
+        g._check(g._lib.gvom_device_product_export(g._h, self.product_id, part, nosync, ctypes.byref(p), ctypes.byref(nd), sh, st))
+        if not hold:
+            g._check(g._lib.gvom_device_product_release(g._h, self.product_id, nosync))
+        n = int(nd.value)
+        return int(p.value), tuple(int(v) for v in sh[:n]), tuple(int(v) for v in st[:n])
+
+    def release(self):
+        if self.__dict__.get("held"):
+            self.held = False
+            g = self.owner
+            if g._h:
+                g._check(g._lib.gvom_device_product_release(g._h, self.product_id, ctypes.c_void_p(_STREAM_NOSYNC)))
+
+    def __del__(self):
+        try:
+            self.release()
+        except Exception:
+            pass
+
+
+class DeviceArray(object):
+    """One array of a device product in device memory, C-contiguous: the uint8 [x, y, z] occupancy grid, a float32 cloud, the
+    int64 row count of a voxel cloud.  `__dlpack__` hands it to a GPU consumer without a copy (torch.from_dlpack), ordered
+    behind the kernel that writes it on the consumer's stream; `copy_to_host()` returns numpy.  The product is a snapshot:
+    later scans and combines do not change it.  The object holds one export of the product -- its memory is not reused while
+    it lives -- given back by release(), by leaving a `with` block, or when it is collected (the parts of a DeviceVoxelCloud
+    share the cloud's).  Tensors taken through DLPack hold exports of their own and stay valid after release() (and after the
+    mapper)."""
+
+    def __init__(self, hold, part=0):
+        self._hold = hold
+        self._part = part
+        _, self.shape, self.strides = hold.describe(part)
+        self.dtype = np.dtype(_PRODUCT_DTYPES[(hold.kind, part)])
+        self.product_id = hold.product_id
+
+    def __dlpack_device__(self):
+        return (_KDL_ROCM, self._hold.owner._device)
+
+    def __dlpack__(self, stream=None, max_version=None, dl_device=None, copy=None):
+        if copy:
+            raise BufferError("copy=True is not supported: the array is shared in place")
+        if dl_device is not None and tuple(int(v) for v in dl_device) != self.__dlpack_device__():
+            raise BufferError("the array lives on %r; no cross-device export" % (self.__dlpack_device__(),))
+        versioned = max_version is not None and int(max_version[0]) >= 1
+        g = self._hold.owner
+        managed = ctypes.c_void_p()
+        g._check(g._lib.gvom_device_product_dlpack(g._h, self.product_id, self._part, _stream_arg(stream), 1 if versioned else 0,
+                                                   ctypes.byref(managed)))
+        api = _capsule_api()
+        if versioned:
+            return api.PyCapsule_New(managed.value, _DLTENSOR_VERSIONED, ctypes.cast(_DTOR_VERSIONED, ctypes.c_void_p))
+        return api.PyCapsule_New(managed.value, _DLTENSOR, ctypes.cast(_DTOR_LEGACY, ctypes.c_void_p))
+
+    @property
+    def ptr(self):
+        """Device address of the array."""
+        return self._hold.describe(self._part)[0]
+
+    def copy_to_host(self):
+        """numpy array of `shape` and `dtype` (waits for the kernel that writes the product)."""
+        g = self._hold.owner
+        out = np.empty(self.shape, self.dtype)
+        g._check(g._lib.gvom_device_product_copy(g._h, self.product_id, self._part, ctypes.c_void_p(out.ctypes.data)))
+        return out
+
+    def __array__(self, dtype=None):
+        a = self.copy_to_host()
+        return a if dtype is None else a.astype(dtype)
+
+    def release(self):
+        self._hold.release()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.release()
+        return False
+
+
+class DeviceVoxelCloud(object):
+    """The result of Gvom.voxel_cloud_device(): `.rows` float32 [cap, 8] (the rows of make_debug_voxel_map, in unspecified
+    order), `.eigenvalues` float32 [cap, 3] (row for row) and `.count` int64 [1] (rows the map has; those beyond cap are dropped),
+    three DeviceArrays of one product.  copy_to_host() returns rows[:min(count, cap)] as numpy."""
+
+    def __init__(self, hold):
+        self._hold = hold
+        self.product_id = hold.product_id
+        self.rows, self.eigenvalues, self.count = (DeviceArray(hold, k) for k in range(3))
+
+    def copy_to_host(self):
+        n = min(int(self.count.copy_to_host()[0]), self.rows.shape[0])
+        return self.rows.copy_to_host()[:n]
+
+    def eigenvalues_to_host(self):
+        n = min(int(self.count.copy_to_host()[0]), self.rows.shape[0])
+        return self.eigenvalues.copy_to_host()[:n]
+
+    def release(self):
+        self._hold.release()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.release()
+        return False
 
 
 class _OutputPool(object):
@@ -780,6 +917,46 @@ class Gvom(object):
         if rc == GVOM_NO_DATA:
             raise AttributeError("'NoneType' object has no attribute 'copy_to_host'")  # as the reference
         return out.astype(bool)
+
+    # ---- the same four, left in device memory (extensions; include/gvom_hip.h "device-resident 3-D products") ----
+    def _device_product(self, kind, max_rows=0):
+        pid = ctypes.c_int64(-1)
+        rc = self._check(self._lib.gvom_device_product(self._h, kind, int(max_rows), ctypes.byref(pid)))
+        return None if rc == GVOM_NO_DATA else _ProductHold(self, kind, int(pid.value))
+
+    def occupancy_grid_device(self):
+        """get_map_as_occupancy_grid() left in device memory: a DeviceArray uint8 [xy, xy, z] (1 = occupied), a snapshot of the
+        current fused map shareable with torch.from_dlpack() without a copy; None before the first combine.  Returns once the
+        work is enqueued: no host wait."""
+        hold = self._device_product(PRODUCT_OCCUPANCY)
+        return None if hold is None else DeviceArray(hold)
+
+    def voxel_cloud_device(self, max_rows=None):
+        """make_debug_voxel_map() left in device memory: a DeviceVoxelCloud (rows, eigenvalues, row count) of at most max_rows
+        rows (default: the fused cell count); None ("No data" before the first combine) under make_debug_voxel_map's conditions.
+        Counts as a read of the per-voxel statistics: statistics on demand stay on while this is called."""
+        hold = self._device_product(PRODUCT_VOXEL_CLOUD, 0 if max_rows is None else max(int(max_rows), 1))
+        if hold is None:
+            if not self._state().has_combined:
+                print("No data")
+            return None
+        return DeviceVoxelCloud(hold)
+
+    def height_cloud_device(self):
+        """make_debug_height_map() left in device memory: a DeviceArray float32 [xy*xy, 7]; None (and "No data") without 2-D maps."""
+        hold = self._device_product(PRODUCT_HEIGHT_CLOUD)
+        if hold is None:
+            print("No data")
+            return None
+        return DeviceArray(hold)
+
+    def inferred_height_cloud_device(self):
+        """make_debug_inferred_height_map() left in device memory: a DeviceArray float32 [xy*xy, 3]; None (and "No data") without 2-D maps."""
+        hold = self._device_product(PRODUCT_INFERRED_HEIGHT_CLOUD)
+        if hold is None:
+            print("No data")
+            return None
+        return DeviceArray(hold)
 
     def make_debug_voxel_map(self):
         """float32[Cc, 8] rows {x, y, z, hit/total, hit, l0-l1, l1-l2, l2} (reference gvom.py:363-378) while the mapper

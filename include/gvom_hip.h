@@ -26,7 +26,9 @@
 extern "C" {
 #endif
 
-#define GVOM_ABI_VERSION 9   /* 9: device-resident maps (gvom_combine_maps_device, map-set exports, DLPack), "device_map_sets";
+#define GVOM_ABI_VERSION 10  /* 10: device-resident 3-D products (gvom_device_product and its export / release / DLPack / copy calls: occupancy
+                              *    grid, voxel cloud, height clouds), "device_product_sets"; gvom_get_occupancy runs k_occupancy;
+                              * 9: device-resident maps (gvom_combine_maps_device, map-set exports, DLPack), "device_map_sets";
                               * 8: RCCL loopback transport (GVOM_TRANSPORT_LOOPBACK), gvom_comm_wire_stats, gvom_comm_abort;
                               * 7: eager fusion of one-slot rings ("eager" knob, gvom_get_tuning "eager_adopted" / "eager_dropped"); a sharded scan /
                               *    combine as ONE native call (gvom_comm_process_pointcloud, gvom_comm_combine_maps_into);
@@ -47,7 +49,7 @@ extern "C" {
 #define GVOM_ERR_INVALID      -1   /* bad argument */
 #define GVOM_ERR_HIP          -2   /* a HIP runtime call failed; see gvom_last_error() */
 #define GVOM_ERR_NO_DEVICE    -3   /* no usable gfx950 device / library built without GPU */
-#define GVOM_ERR_CAPACITY     -4   /* grid too large for 32-bit voxel indices, or > 64 ring slots, or every device map set exported */
+#define GVOM_ERR_CAPACITY     -4   /* grid too large for 32-bit voxel indices, or > 64 ring slots, or every device map / product set (of a kind) exported */
 
 #define GVOM_DTYPE_F32 0
 #define GVOM_DTYPE_F64 1
@@ -229,6 +231,41 @@ int gvom_device_map_release(gvom_t *h, int64_t set_id, void *consumer_stream);
 int gvom_device_map_dlpack(gvom_t *h, int64_t set_id, int which, void *consumer_stream, int versioned, void **managed);
 /* Blocking copy of map `which` of a set into host memory (xy*xy elements, [y*xy_size + x]). */
 int gvom_device_map_copy(gvom_t *h, int64_t set_id, int which, void *host_out);
+
+/* --- device-resident 3-D products (an extension: the occupancy grid and the debug clouds for consumers on the GPU) ----------
+ * gvom_device_product writes one PRODUCT into device memory on the handle's stream and returns once the work is ENQUEUED (no
+ * host wait, no copy).  A product is a SNAPSHOT -- of the current fused map (occupancy, voxel cloud) or of the 2-D maps of the
+ * last combine (the height clouds) -- that later scans and combines do not change.  Kinds, parts and layouts (all C-contiguous):
+ *   GVOM_PRODUCT_OCCUPANCY              part 0  uint8 [xy, xy, z]   1 = occupied: what gvom_get_occupancy returns (k_occupancy)
+ *   GVOM_PRODUCT_VOXEL_CLOUD            part 0  float32 [cap, 8]    the rows of gvom_debug_voxel_map, in unspecified order
+ *                                       part 1  float32 [cap, 3]    their eigenvalues (gvom_debug_voxel_eigen), row for row
+ *                                       part 2  int64 [1]           rows the map HAS (rows beyond cap are dropped, still counted)
+ *   GVOM_PRODUCT_HEIGHT_CLOUD           part 0  float32 [xy*xy, 7]  gvom_debug_height_map
+ *   GVOM_PRODUCT_INFERRED_HEIGHT_CLOUD  part 0  float32 [xy*xy, 3]  gvom_debug_inferred_height_map
+ * max_rows: the voxel cloud's cap; <= 0 = the fused cell count (which waits for a device combine's pending count once).
+ * GVOM_NO_DATA under the conditions of the host forms: nothing combined yet; no 2-D maps since the last fusion (height clouds);
+ * no fused statistics (voxel cloud -- which counts as a read of the statistics, so statistics on demand stay on).
+ * GVOM_ERR_INVALID on a sharded handle.  *product_id names the product (a sequence number of its own, not a map set id).
+ * Products live in PRODUCT SETS that behave exactly like map sets (exports, releases, reuse behind the consumers' release
+ * events, exports outliving the handle); a set is allocated when a kind is first asked for or no set of the kind is free, and
+ * a product nobody holds an export of goes back to the pool when the next product of ITS KIND is asked for (its id is stale from
+ * then on).  At most GVOM_MAX_PRODUCT_SETS sets PER KIND and handle (an occupancy set is xy*xy*z bytes); the call that needs
+ * one more returns GVOM_ERR_CAPACITY.  gvom_get_tuning "device_product_sets": how many are allocated, all kinds together; they
+ * do not count as "device_map_sets". */
+#define GVOM_PRODUCT_OCCUPANCY             1
+#define GVOM_PRODUCT_VOXEL_CLOUD           2
+#define GVOM_PRODUCT_HEIGHT_CLOUD          3
+#define GVOM_PRODUCT_INFERRED_HEIGHT_CLOUD 4
+#define GVOM_MAX_PRODUCT_SETS              4
+int gvom_device_product(gvom_t *h, int kind, int64_t max_rows, int64_t *product_id);
+/* As gvom_device_map_export / _release / _dlpack / _copy, for part `part` of a product.  Export: *ptr, *ndim (1..3), shape and
+ * strides in elements (entries beyond ndim are 1).  DLPack: kDLROCM, uint8 (unsigned-integer type code) / float32 / int64,
+ * ndim up to 3.  Copy: the whole part (cap rows of a voxel cloud) into host memory, blocking. */
+int gvom_device_product_export(gvom_t *h, int64_t product_id, int part, void *consumer_stream, void **ptr, int32_t *ndim,
+                               int64_t shape[3], int64_t strides[3]);
+int gvom_device_product_release(gvom_t *h, int64_t product_id, void *consumer_stream);
+int gvom_device_product_dlpack(gvom_t *h, int64_t product_id, int part, void *consumer_stream, int versioned, void **managed);
+int gvom_device_product_copy(gvom_t *h, int64_t product_id, int part, void *host_out);
 
 /* --- one map sharded over the GPUs of a node (one rank = one process = one GPU) -------------------
  * No counterpart in the reference (it has no multi-GPU path); semantics = SURVEY 8(e):
@@ -460,6 +497,8 @@ int gvom_host_timing(gvom_t *h, double us[8]);
  * verified; 0: always divide.  gvom_get_tuning("fastdiv"): bit 0 / 1 = in use for xy_resolution / z_resolution.
  * "encfuse" (A/B of that kernel's shape: low 4 bits waves per column block, bit 4 no XCD pairing), "fuse1" (1: one-slot
  * fusions through the general kernel), "flag_kernel" (1: round 3's completion-flag kernel).
+ * "occupancy_clear" (A/B of k_occupancy's dead tile columns: 0, default, the kernel writes every byte of the grid; 1 the grid is
+ * cleared with hipMemsetAsync and only tile columns with a live tile are written.  Same grid either way).
  * (Test hooks are not part of this library: include/gvom_hip_test.h, lib/libgvom_hip_test.so.) */
 int gvom_set_tuning(gvom_t *h, const char *name, int value);
 /* The value the LAST scan ran with ("segs", "period", "ep_row", "prio", "interleave": what automatic resolved to).

@@ -15,7 +15,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "g-vom_amd")
-SOURCES = ["csrc/gvom_trace.hip", "csrc/gvom_fuse.hip", "csrc/gvom_map2d.hip", "csrc/gvom_stats.hip", "csrc/gvom_capi.hip", "csrc/gvom_comm.hip",
+SOURCES = ["csrc/gvom_trace.hip", "csrc/gvom_fuse.hip", "csrc/gvom_map2d.hip", "csrc/gvom_stats.hip", "csrc/gvom_products.hip", "csrc/gvom_capi.hip", "csrc/gvom_comm.hip",
            "csrc/gvom_device.h", "csrc/gvom_internal.h", "../include/gvom_hip.h", "../include/gvom_hip_test.h", "Makefile"]
 
 

@@ -10,6 +10,7 @@
 //   * ring slots are swapped with a spare staging slot on commit, so a rejected scan
 //     (gvom.py:148-150) leaves the ring untouched.
 #include "gvom_internal.h"
+#include "gvom_ingest.h"
 #include "../../include/gvom_hip.h"
 
 #include <math.h>
@@ -289,6 +290,17 @@ struct gvom_handle {
     int tune_occ_clear = 0;                             // gvom_set_tuning "occupancy_clear": 1 = clear the grid, write live tile columns only (A/B)
     bool count_pending = false;                         // the last combine was a device combine: its fused cell count is read
     hipEvent_t ev_dcount = nullptr;                     //   from the host-mapped counter once this event (behind its k_map2d) has completed
+    // RANGE IMAGES (gvom_sensor_model_set / gvom_process_range_image): the sensor model in device memory -- [n][3] directions, then
+    // [n][3] offsets, n = ri_H * ri_W -- and the staging buffers of host images and column poses.  k_unproject (gvom_ingest.hip)
+    // turns an image into the cloud in in_pts, which the scan then reads like an uploaded host cloud
+    Buf ri_model, ri_raw, ri_poses;
+    // column poses go through a pinned staging copy: a second PAGEABLE upload per scan is a second staged, blocking copy of the
+    // runtime (m256, 196 KB of poses: +27 us per step); copied here by the calling thread and sent from pinned memory, the
+    // transfer is in flight while the image's own upload runs.  Free again once the scan's k_trace has completed, as in_pts is
+    void *ri_poses_pin = nullptr;
+    size_t ri_poses_pin_bytes = 0;
+    int32_t ri_H = 0, ri_W = 0;                         // 0: no model set
+    double ri_scale = 0.0, ri_min = 0.0, ri_max = 0.0;
 };
 
 namespace {
@@ -1183,6 +1195,64 @@ int renumber_epochs(gvom_handle *h)
     return GVOM_OK;
 }
 
+// ---- the three parts of a scan call, shared by the cloud routes (process_impl) and the range-image route (range_image_impl);
+// all of them under scan_mu and mu ----
+// 1. what the call does to the handle before any data moves.  != 0: the call returns that (GVOM_EMPTY_CLOUD included)
+int scan_begin(gvom_handle *h, const double ego[3], const int64_t *off_bytes, size_t esz, bool widen_f32, bool defer, int64_t n)
+{
+    HIPCHK(h, hipSetDevice(h->device));
+    for (int k = 0; k < 3; ++k) h->in_off[k] = off_bytes ? (int)(off_bytes[k] / (int64_t)esz) : k;
+    h->in_f32 = widen_f32;
+    h->ego[0] = ego[0]; h->ego[1] = ego[1]; h->ego[2] = ego[2];       // gvom.py:102-104
+    // a sharded scan whose second half never came (the exchange failed between gvom_shard_scan_local and
+    // gvom_shard_scan_merge): k_trace's additions to this rank's rows were never encoded or zeroed
+    if (h->pending && h->sharded) scan_abort(h);
+    h->pending = false;
+    if (h->spec_valid) {                                   // a scan behind a scan: the speculative fusion of the first is dropped
+        h->spec_valid = false;
+        if (h->eager_waste < 4) ++h->eager_waste;
+        ++h->eager_stat[1];
+    }
+    if (h->sharded && !defer) { h->err = "a sharded handle scans through gvom_shard_scan_local / gvom_shard_scan_merge"; return GVOM_ERR_INVALID; }
+    if (n == 0 && !defer) return GVOM_EMPTY_CLOUD;                     // gvom.py:107-109 (a rank's share of a sharded scan may be empty)
+    return GVOM_OK;
+}
+
+// 2. host data into the handle's staging buffers (which are free: their readers sit in front of the previous scan's k_trace, and
+// that had completed when its call returned)
+struct Upload { void *dst; const void *src; size_t bytes; };
+int scan_upload(gvom_handle *h, std::unique_lock<std::mutex> &lk, const Upload *up, int count)
+{
+    if (hipStreamQuery(h->stream) == hipErrorNotReady) {
+        // the main stream still has work queued (a combine from another thread, the previous k_encode): upload beside it
+        lk.unlock();                                  // a pageable source is staged by the calling thread: not under the handle mutex
+        hipError_t ue = hipSuccess;
+        for (int k = 0; k < count && ue == hipSuccess; ++k)
+            ue = hipMemcpyAsync(up[k].dst, up[k].src, up[k].bytes, hipMemcpyHostToDevice, h->stream_up);
+        lk.lock();
+        HIPCHK(h, ue);
+        HIPCHK(h, hipEventRecord(h->ev_up, h->stream_up));
+        HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_up, 0));
+    } else {
+        (void)hipGetLastError();
+        for (int k = 0; k < count; ++k)
+            HIPCHK(h, hipMemcpyAsync(up[k].dst, up[k].src, up[k].bytes, hipMemcpyHostToDevice, h->stream));
+    }
+    return GVOM_OK;
+}
+
+// 3. the cloud is now at `dev` (or will be, in stream order): scan it, commit it
+int scan_finish(gvom_handle *h, std::unique_lock<std::mutex> &lk, const void *dev, int64_t n, int64_t stride_elems, int dtype,
+                const double *tf, bool defer)
+{
+    int rc = scan_launch(h, lk, dev, n, stride_elems, dtype, tf, defer);
+    if (rc) return rc;
+    if (defer) return GVOM_OK;
+    const bool accept = h->pending_any;                   // == (global occupied-voxel count > 0), gvom.py:147-150
+    scan_commit(h, accept);
+    return accept ? GVOM_OK : GVOM_NO_OVERLAP;
+}
+
 int process_impl(gvom_handle *h, const void *xyz, bool on_device, int64_t n, int64_t row_stride_bytes,
                  int dtype, const double ego[3], const double *tf, bool defer, const int64_t *off_bytes = nullptr,
                  bool widen_f32 = false)
@@ -1206,47 +1276,65 @@ int process_impl(gvom_handle *h, const void *xyz, bool on_device, int64_t n, int
     }
     std::lock_guard<std::mutex> scan_lk(h->scan_mu);      // scans of one handle are serialised (one staging slot, one set of accumulators)
     std::unique_lock<std::mutex> lk(h->mu);
-    HIPCHK(h, hipSetDevice(h->device));
-    for (int k = 0; k < 3; ++k) h->in_off[k] = off_bytes ? (int)(off_bytes[k] / (int64_t)esz) : k;
-    h->in_f32 = widen_f32;
-    h->ego[0] = ego[0]; h->ego[1] = ego[1]; h->ego[2] = ego[2];       // gvom.py:102-104
-    // a sharded scan whose second half never came (the exchange failed between gvom_shard_scan_local and
-    // gvom_shard_scan_merge): k_trace's additions to this rank's rows were never encoded or zeroed
-    if (h->pending && h->sharded) scan_abort(h);
-    h->pending = false;
-    if (h->spec_valid) {                                   // a scan behind a scan: the speculative fusion of the first is dropped
-        h->spec_valid = false;
-        if (h->eager_waste < 4) ++h->eager_waste;
-        ++h->eager_stat[1];
-    }
-    if (h->sharded && !defer) { h->err = "a sharded handle scans through gvom_shard_scan_local / gvom_shard_scan_merge"; return GVOM_ERR_INVALID; }
-    if (n == 0 && !defer) return GVOM_EMPTY_CLOUD;                     // gvom.py:107-109 (a rank's share of a sharded scan may be empty)
+    int rc = scan_begin(h, ego, off_bytes, esz, widen_f32, defer, n);
+    if (rc) return rc;
     const void *dev = xyz;
     if (!on_device && n > 0) {
-        int rc = ensure(h, h->in_pts, (size_t)n * row_stride_bytes);
-        if (rc) return rc;
-        const size_t up_bytes = (size_t)(n - 1) * row_stride_bytes + (size_t)last_field + esz;
-        // in_pts is free: the previous scan's k_trace (its only reader) had completed when that call returned
-        if (hipStreamQuery(h->stream) == hipErrorNotReady) {
-            // the main stream still has work queued (a combine from another thread, the previous k_encode): upload beside it
-            lk.unlock();                                  // a pageable source is staged by the calling thread: not under the handle mutex
-            const hipError_t ue = hipMemcpyAsync(h->in_pts.p, xyz, up_bytes, hipMemcpyHostToDevice, h->stream_up);
-            lk.lock();
-            HIPCHK(h, ue);
-            HIPCHK(h, hipEventRecord(h->ev_up, h->stream_up));
-            HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_up, 0));
-        } else {
-            (void)hipGetLastError();
-            HIPCHK(h, hipMemcpyAsync(h->in_pts.p, xyz, up_bytes, hipMemcpyHostToDevice, h->stream));
-        }
+        if ((rc = ensure(h, h->in_pts, (size_t)n * row_stride_bytes))) return rc;
+        const Upload up = {h->in_pts.p, xyz, (size_t)(n - 1) * row_stride_bytes + (size_t)last_field + esz};
+        if ((rc = scan_upload(h, lk, &up, 1))) return rc;
         dev = h->in_pts.p;
     }
-    int rc = scan_launch(h, lk, dev, n, row_stride_bytes / (int64_t)esz, dtype, tf, defer);
+    return scan_finish(h, lk, dev, n, row_stride_bytes / (int64_t)esz, dtype, tf, defer);
+}
+
+// A range image (gvom_process_range_image): raw -> (host images: staging buffer ->) k_unproject -> in_pts, then the scan of in_pts
+// as process_impl runs it on an uploaded host cloud of H * W returns
+int range_image_impl(gvom_handle *h, const void *raw, bool on_device, int range_dtype, int64_t row_stride_bytes,
+                     const double *col_poses, int cloud_dtype, const double ego[3], const double *tf)
+{
+    if (!h || !ego || !raw || (cloud_dtype != GVOM_DTYPE_F32 && cloud_dtype != GVOM_DTYPE_F64)) return GVOM_ERR_INVALID;
+    if (range_dtype != GVOM_RANGE_U16 && range_dtype != GVOM_RANGE_U32 && range_dtype != GVOM_RANGE_F32) return GVOM_ERR_INVALID;
+    const int64_t rsz = range_dtype == GVOM_RANGE_U16 ? 2 : 4;
+    std::lock_guard<std::mutex> scan_lk(h->scan_mu);
+    std::unique_lock<std::mutex> lk(h->mu);
+    if (h->sharded) { h->err = "range images are not supported on a sharded handle"; return GVOM_ERR_INVALID; }
+    if (h->ri_H <= 0) { h->err = "gvom_process_range_image: no sensor model (gvom_sensor_model_set)"; return GVOM_ERR_INVALID; }
+    const int64_t H = h->ri_H, W = h->ri_W, n = H * W;
+    if (row_stride_bytes < W * rsz || row_stride_bytes % rsz != 0) { h->err = "gvom_process_range_image: bad row stride"; return GVOM_ERR_INVALID; }
+    int rc = scan_begin(h, ego, nullptr, 0, false, false, n);
     if (rc) return rc;
-    if (defer) return GVOM_OK;
-    const bool accept = h->pending_any;                   // == (global occupied-voxel count > 0), gvom.py:147-150
-    scan_commit(h, accept);
-    return accept ? GVOM_OK : GVOM_NO_OVERLAP;
+    const size_t tsz = cloud_dtype == GVOM_DTYPE_F32 ? 4 : 8;
+    if ((rc = ensure(h, h->in_pts, (size_t)n * 3 * tsz))) return rc;
+    Upload up[2];
+    int ups = 0;
+    if (col_poses) {                                       // (first: see ri_poses_pin)
+        const size_t bytes = (size_t)W * 96;
+        if ((rc = ensure(h, h->ri_poses, bytes))) return rc;
+        if (h->ri_poses_pin_bytes < bytes) {
+            if (h->ri_poses_pin) HIPCHK(h, hipHostFree(h->ri_poses_pin));
+            h->ri_poses_pin = nullptr; h->ri_poses_pin_bytes = 0;
+            HIPCHK(h, hipHostMalloc(&h->ri_poses_pin, bytes + bytes / 2, hipHostMallocDefault));
+            h->ri_poses_pin_bytes = bytes + bytes / 2;
+        }
+        memcpy(h->ri_poses_pin, col_poses, bytes);
+        up[ups++] = {h->ri_poses.p, h->ri_poses_pin, bytes};
+    }
+    if (!on_device) {
+        const size_t bytes = (size_t)(H - 1) * row_stride_bytes + (size_t)(W * rsz);
+        if ((rc = ensure(h, h->ri_raw, bytes))) return rc;
+        up[ups++] = {h->ri_raw.p, raw, bytes};
+    }
+    if (ups && (rc = scan_upload(h, lk, up, ups))) return rc;
+    UnprojectParams U;
+    U.raw = on_device ? raw : h->ri_raw.p; U.row_stride = row_stride_bytes;
+    U.dir = (const double *)h->ri_model.p; U.off = U.dir + (size_t)n * 3;
+    U.poses = col_poses ? (const double *)h->ri_poses.p : nullptr;
+    U.out = h->in_pts.p;
+    U.scale = h->ri_scale; U.min_range = h->ri_min; U.max_range = h->ri_max;
+    U.W = (uint32_t)W; U.n = (uint32_t)n;
+    HIPCHK(h, gvom_launch_unproject(h->stream, U, range_dtype, cloud_dtype));
+    return scan_finish(h, lk, h->in_pts.p, n, 3, cloud_dtype, tf, false);
 }
 
 // z decomposition of k_fuse: chunks of zc levels (16 whenever z_size <= 256), cpw chunks per wave,
@@ -1604,7 +1692,7 @@ VIS void gvom_destroy(gvom_t *h)
     if (h->x_host) hipHostFree(h->x_host);
     for (auto &s : h->slots) { hipFree(s.state); hipFree(s.code16); hipFree(s.tags); fb(s.crows); fb(s.metrics); fb(s.base); fb(s.rowvox); }
     for (auto &f : h->fused) { hipFree(f.state); hipFree(f.tags); fb(f.rows); fb(f.metrics); }
-    fb(h->in_pts); fb(h->world_pts[0]); fb(h->world_pts[1]); fb(h->flink[0]); fb(h->flink[1]); fb(h->tl); fb(h->dir_keys); fb(h->dir_perm); hipFree(h->dir_hist);
+    fb(h->in_pts); fb(h->ri_model); fb(h->ri_raw); fb(h->ri_poses); if (h->ri_poses_pin) hipHostFree(h->ri_poses_pin); fb(h->world_pts[0]); fb(h->world_pts[1]); fb(h->flink[0]); fb(h->flink[1]); fb(h->tl); fb(h->dir_keys); fb(h->dir_perm); hipFree(h->dir_hist);
     hipFree(h->counters); if (h->counters_host) hipHostFree(h->counters_host);
     hipFree(h->descs_dev); if (h->descs_host) hipHostFree(h->descs_host);
     hipFree(h->blockcounts); hipFree(h->blockcounts2); hipFree(h->hmaps2);
@@ -1663,6 +1751,39 @@ VIS int gvom_process_pointcloud2(gvom_t *h, const void *data, int64_t n_points, 
     // the reference computes a FLOAT32 cloud in f64 as well: widen on load, run the f64 kernels
     return process_impl(h, data, false, n_points, point_step, GVOM_DTYPE_F64, ego, transform_4x4, false, off,
                         dtype == GVOM_DTYPE_F32);
+}
+
+// ---- range images (include/gvom_hip.h "range images") -------------------------------------------
+// The model lives in device memory; a scan holds scan_mu until its k_trace -- which sits behind its k_unproject on the stream --
+// has completed, so whoever gets scan_mu here finds no reader of the old model in flight (the stream is drained all the same:
+// a scan that failed half-way may have left one).  The second wait makes the caller's arrays free on return.
+VIS int gvom_sensor_model_set(gvom_t *h, int32_t H, int32_t W, const double *dir, const double *off,
+                              double range_scale, double min_range, double max_range)
+{
+    if (!h || H < 1 || W < 1 || (int64_t)H * W >= (1ll << 31) || !dir) return GVOM_ERR_INVALID;
+    if (!(range_scale > 0.0) || !std::isfinite(range_scale) || std::isnan(min_range) || std::isnan(max_range)) return GVOM_ERR_INVALID;
+    std::lock_guard<std::mutex> scan_lk(h->scan_mu);
+    std::unique_lock<std::mutex> lk(h->mu);
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    const size_t half = (size_t)H * W * 24;
+    h->ri_H = h->ri_W = 0;
+    int rc = ensure(h, h->ri_model, 2 * half);
+    if (rc) return rc;
+    char *m = (char *)h->ri_model.p;
+    HIPCHK(h, hipMemcpyAsync(m, dir, half, hipMemcpyHostToDevice, h->stream));
+    if (off) HIPCHK(h, hipMemcpyAsync(m + half, off, half, hipMemcpyHostToDevice, h->stream));
+    else HIPCHK(h, hipMemsetAsync(m + half, 0, half, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->ri_H = H; h->ri_W = W;
+    h->ri_scale = range_scale; h->ri_min = min_range; h->ri_max = max_range;
+    return GVOM_OK;
+}
+
+VIS int gvom_process_range_image(gvom_t *h, const void *raw, int on_device, int range_dtype, int64_t row_stride_bytes,
+                                 const double *col_poses, int cloud_dtype, const double ego[3], const double *transform_4x4)
+{
+    return range_image_impl(h, raw, on_device != 0, range_dtype, row_stride_bytes, col_poses, cloud_dtype, ego, transform_4x4);
 }
 
 // ---- scan of a sharded map (one rank per GPU; DESIGN.md "Multi-GPU") ---------------------------
@@ -2952,6 +3073,7 @@ VIS int gvom_get_tuning(gvom_t *h, const char *name, int *value)
     if (!strcmp(name, "device_map_sets")) { *value = (int)h->dsets.size(); return GVOM_OK; }             // read-only: allocated device map sets                  // read-only, GVOM_ROUTE_*
     if (!strcmp(name, "device_product_sets")) { *value = (int)h->psets.size(); return GVOM_OK; }        // read-only: allocated device product sets (every kind)
     if (!strcmp(name, "occupancy_clear")) { *value = h->tune_occ_clear; return GVOM_OK; }
+    if (!strcmp(name, "range_image")) { *value = h->ri_H > 0 ? 1 : 0; return GVOM_OK; }                 // read-only: a sensor model is set
     if (!strcmp(name, "fastdiv")) { *value = h->tune_fastdiv == 0 ? 0 : h->fastdiv_ok; return GVOM_OK; }   // bit 0 / 1: xy / z resolution divided by reciprocal
     return GVOM_ERR_INVALID;
 }

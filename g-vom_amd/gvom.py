@@ -24,7 +24,8 @@ import threading
 
 import numpy as np
 
-__all__ = ["Gvom", "GvomBackendError", "DeviceMaps", "DeviceMap", "DeviceArray", "DeviceVoxelCloud", "load_library", "library_path"]
+__all__ = ["Gvom", "GvomBackendError", "DeviceMaps", "DeviceMap", "DeviceArray", "DeviceVoxelCloud", "load_library", "library_path",
+           "unproject_range_image"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -84,6 +85,8 @@ ABI = [
     ("gvom_process_pointcloud2", _I, [_P, _P, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                                        ctypes.c_int64, ctypes.c_int, _P, _P]),
     ("gvom_process_pointcloud_device", _I, [_P, _P, _I64, _I64, _I, _DP, _P]),
+    ("gvom_sensor_model_set", _I, [_P, ctypes.c_int32, ctypes.c_int32, _P, _P, ctypes.c_double, ctypes.c_double, ctypes.c_double]),
+    ("gvom_process_range_image", _I, [_P, _P, _I, _I, _I64, _P, _I, _DP, _P]),
     ("gvom_combine_maps", _I, [_P, _P, _P, _P, _P, _P]),
     ("gvom_output_buffer_alloc", _I, [_P, ctypes.POINTER(_P)]),
     ("gvom_output_buffer_free", _I, [_P, _P]),
@@ -200,6 +203,78 @@ def load_library(path=None):
 
 def _ptr(a):
     return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+
+
+RANGE_U16, RANGE_U32, RANGE_F32 = 0, 1, 2                   # GVOM_RANGE_*
+_RANGE_CODES = {np.dtype(np.uint16): RANGE_U16, np.dtype(np.uint32): RANGE_U32, np.dtype(np.float32): RANGE_F32}
+
+
+def _range_code(dtype):
+    try:
+        return _RANGE_CODES[np.dtype(dtype)]
+    except (KeyError, TypeError):
+        raise ValueError("a range image is uint16, uint32 or float32, got %r" % (dtype,))
+
+
+def _cloud_code(dtype):
+    dt = np.dtype(dtype)
+    if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
+        raise ValueError("cloud_dtype must be float32 or float64, got %r" % (dtype,))
+    return 0 if dt == np.dtype(np.float32) else 1
+
+
+def _column_poses(column_transforms, W):
+    """[W, 4, 4] or [W, 3, 4] -> C-contiguous float64 [W, 12] (rows 0..2 of every matrix), or None"""
+    if column_transforms is None:
+        return None
+    c = np.asarray(column_transforms, dtype=np.float64)
+    if c.ndim != 3 or c.shape[0] != W or c.shape[1] not in (3, 4) or c.shape[2] != 4:
+        raise ValueError("column_transforms must have shape (%d, 4, 4) or (%d, 3, 4), got %r" % (W, W, c.shape))
+    return np.ascontiguousarray(c[:, :3, :]).reshape(W, 12)
+
+
+def unproject_range_image(ranges, directions, offsets=None, range_scale=0.001, min_range=0.0, max_range=float("inf"),
+                          column_transforms=None, cloud_dtype=np.float32, drop_invalid=False):
+    """What Gvom.process_range_image scans, computed with numpy on the CPU: the [H*W, 3] cloud of `cloud_dtype` of a range
+    image -- include/gvom_hip.h "range images", operation for operation, every one a float64 operation rounded once:
+
+        r      = float64(raw) * range_scale
+        valid  = raw != 0 and r finite and min_range <= r <= max_range
+        p[k]   = r * dir[k] + off[k]                                              (multiply, then add)
+        q[k]   = ((p[0]*C[w][k][0] + p[1]*C[w][k][1]) + p[2]*C[w][k][2]) + C[w][k][3]       (with column_transforms)
+        xyz    = cloud_dtype(q)  where valid, else (NaN, NaN, NaN)                (ONE rounding, at the end)
+
+    ranges [H, W] uint16 / uint32 / float32; directions [H, W, 3]; offsets [H, W, 3] or None (zeros); column_transforms
+    [W, 4, 4] or [W, 3, 4] or None.  drop_invalid: the invalid pixels' rows removed, the order of the others kept (the cloud a
+    node that filters its returns hands to process_pointcloud).  The library computes the same bits on the GPU."""
+    raw = np.asarray(ranges)
+    _range_code(raw.dtype)
+    if raw.ndim != 2:
+        raise ValueError("ranges must have shape (H, W), got %r" % (raw.shape,))
+    H, W = raw.shape
+    d = np.asarray(directions, dtype=np.float64)
+    if d.shape != (H, W, 3):
+        raise ValueError("directions must have shape (%d, %d, 3), got %r" % (H, W, d.shape))
+    o = np.zeros((H, W, 3)) if offsets is None else np.asarray(offsets, dtype=np.float64)
+    if o.shape != (H, W, 3):
+        raise ValueError("offsets must have shape (%d, %d, 3), got %r" % (H, W, o.shape))
+    _cloud_code(cloud_dtype)
+    scale = np.float64(range_scale)
+    with np.errstate(invalid="ignore", over="ignore"):
+        r = raw.astype(np.float64) * scale
+        valid = (raw != 0) & np.isfinite(r) & (np.float64(min_range) <= r) & (r <= np.float64(max_range))
+        p = [r * d[:, :, k] + o[:, :, k] for k in range(3)]
+        q = p
+        if column_transforms is not None:
+            C = _column_poses(column_transforms, W).reshape(W, 3, 4)
+            q = [((p[0] * C[None, :, k, 0] + p[1] * C[None, :, k, 1]) + p[2] * C[None, :, k, 2]) + C[None, :, k, 3]
+                 for k in range(3)]
+        xyz = np.stack(q, axis=-1)
+        xyz[~valid] = np.nan
+        xyz = xyz.reshape(H * W, 3).astype(cloud_dtype)
+    if drop_invalid:
+        xyz = xyz[valid.reshape(-1)]
+    return np.ascontiguousarray(xyz)
 
 
 class _DeviceArrayView(object):
@@ -782,6 +857,71 @@ class Gvom(object):
         return self.process_pointcloud2(msg.data, msg.width * msg.height, msg.point_step,
                                         (f["x"].offset, f["y"].offset, f["z"].offset), ego_position,
                                         transform, np.float32 if kinds == {7} else np.float64)
+
+    # ---- range images: the scan as a spinning multi-beam lidar emits it (include/gvom_hip.h "range images") ----------
+    def set_sensor_model(self, directions, offsets=None, range_scale=0.001, min_range=0.0, max_range=float("inf")):
+        """The sensor's per-pixel lookup table, once (or whenever it changes): directions [H, W, 3] (unit vectors), offsets
+        [H, W, 3] metres or None, range_scale metres per raw unit, the inclusive range gate.  The arrays are copied to the GPU."""
+        d = np.ascontiguousarray(np.asarray(directions, dtype=np.float64))
+        if d.ndim != 3 or d.shape[2] != 3 or d.shape[0] < 1 or d.shape[1] < 1:
+            raise ValueError("directions must have shape (H, W, 3), got %r" % (d.shape,))
+        o = None
+        if offsets is not None:
+            o = np.ascontiguousarray(np.asarray(offsets, dtype=np.float64))
+            if o.shape != d.shape:
+                raise ValueError("offsets must have the shape of directions %r, got %r" % (d.shape, o.shape))
+        if not (float(range_scale) > 0.0 and math.isfinite(float(range_scale))):
+            raise ValueError("range_scale must be finite and > 0")
+        self._check(self._lib.gvom_sensor_model_set(self._h, d.shape[0], d.shape[1], _ptr(d), _ptr(o), float(range_scale),
+                                                    float(min_range), float(max_range)))
+        self._sensor_shape = (d.shape[0], d.shape[1])
+
+    def _range_image_call(self, raw_ptr, on_device, rcode, stride, ego_position, transform, column_transforms, cloud_dtype):
+        shape = getattr(self, "_sensor_shape", None)
+        poses = _column_poses(column_transforms, shape[1]) if (column_transforms is not None and shape) else None
+        self.ego_position = ego_position
+        ego = (ctypes.c_double * 3)(float(ego_position[0]), float(ego_position[1]), float(ego_position[2]))
+        tf = None
+        if transform is not None:
+            tf = np.ascontiguousarray(np.asarray(transform, dtype=np.float64))
+            if tf.shape != (4, 4):
+                raise ValueError("transform must be 4x4")
+        rc = self._check(self._lib.gvom_process_range_image(self._h, raw_ptr, int(on_device), rcode, int(stride), _ptr(poses),
+                                                            _cloud_code(cloud_dtype), ego, _ptr(tf)))
+        if rc == GVOM_EMPTY_CLOUD:
+            print("[WARNING] Processing an empty pointcloud, nothing will happen!")
+        elif rc == GVOM_NO_OVERLAP:
+            print("[WARNING] The pointcloud points don't overlap with any voxels, nothing will happen!")
+        return None
+
+    def process_range_image(self, ranges, ego_position, transform=None, column_transforms=None, cloud_dtype=np.float32):
+        """process_pointcloud for a range image: `ranges` [H, W] uint16 / uint32 / float32 raw ranges of the sensor whose model
+        set_sensor_model has handed over (0 = no return), any row stride; column_transforms [W, 4, 4] or [W, 3, 4]: one pose
+        per column (the sweep's de-skew), applied before `transform`.  Equivalent to
+            self.process_pointcloud(unproject_range_image(ranges, <the model>, column_transforms, cloud_dtype), ego_position, transform)
+        with the unprojection done on the GPU and 2 or 4 bytes per pixel uploaded.  Returns None."""
+        raw = ranges if isinstance(ranges, np.ndarray) else np.asarray(ranges)
+        rcode = _range_code(raw.dtype)
+        if raw.ndim != 2 or raw.shape[0] < 1 or raw.shape[1] < 1:
+            raise ValueError("ranges must have shape (H, W), got %r" % (raw.shape,))
+        shape = getattr(self, "_sensor_shape", None)
+        if shape is not None and tuple(raw.shape) != shape:
+            raise ValueError("ranges have shape %r, the sensor model %r" % (tuple(raw.shape), shape))
+        if raw.strides[1] != raw.itemsize or raw.strides[0] < raw.shape[1] * raw.itemsize or raw.strides[0] % raw.itemsize:
+            raise ValueError("ranges must be C-contiguous in the last axis with rows a whole number of elements apart")
+        if shape is None and column_transforms is not None:
+            _column_poses(column_transforms, raw.shape[1])
+        return self._range_image_call(_ptr(raw), 0, rcode, raw.strides[0], ego_position, transform, column_transforms, cloud_dtype)
+
+    def process_range_image_device(self, dev_ptr, range_dtype, ego_position, transform=None, column_transforms=None,
+                                   cloud_dtype=np.float32, row_stride_bytes=None):
+        """process_range_image for an image already resident in HBM (raw device pointer, the model's H x W pixels of
+        `range_dtype`, rows row_stride_bytes apart; default: packed).  The data must be ready when the call is made."""
+        rcode = _range_code(range_dtype)
+        shape = getattr(self, "_sensor_shape", None)
+        stride = row_stride_bytes or ((shape[1] if shape else 0) * np.dtype(range_dtype).itemsize)
+        return self._range_image_call(ctypes.c_void_p(int(dev_ptr)), 1, rcode, stride, ego_position, transform, column_transforms,
+                                      cloud_dtype)
 
     def combine_maps(self):
         """Combines all maps in the buffer and processes the resultant map into 2D maps

@@ -130,6 +130,48 @@ def lidar_scan(scene, beams=64, azimuths=2048, sensor=(0.0, 0.0, 0.0), yaw=0.0, 
     return np.ascontiguousarray(pts.astype(dtype))
 
 
+def range_image_scan(scene, beams=64, azimuths=2048, sensor=(0.0, 0.0, 0.0), yaw=0.0, noise_seed=0, range_dtype=np.uint32,
+                     dropout=0.0, range_scale=None, elevations_deg=None, azimuth_offsets=None, clamp_misses=False):
+    """The same sweep as lidar_scan(frame="sensor") of an os1_like sensor (non-uniform elevations, staggered beam columns unless
+    given), as such a sensor's driver emits it: (raw, directions, offsets) --
+      raw         [beams, azimuths] of range_dtype: the return's distance in units of range_scale (default: millimetres for
+                  uint16 / uint32, metres for float32), rounded to the raw type; 0 where the ray had no return within
+                  MAX_RANGE (clamp_misses=True: MAX_RANGE, as lidar_scan's clouds carry them) and for `dropout` of the pixels
+                  (drop_returns' bursts and singles, seeded by noise_seed)
+      directions  [beams, azimuths, 3] float64 unit vectors in the sensor frame (they include `yaw`, as lidar_scan's do)
+      offsets     [beams, azimuths, 3] float64: a few centimetres, as the distance between a real sensor's beam origin and
+                  its frame origin -- 1.5 cm along the column's azimuth, 3.6 cm up, +-2 mm per beam
+    so that point = raw * range_scale * direction + offset.  A raw value stands for a point of its own: the image is not an
+    encoding of lidar_scan's cloud to the last bit (quantisation, offsets)."""
+    rdt = np.dtype(range_dtype)
+    if range_scale is None:
+        range_scale = 1.0 if rdt == np.dtype(np.float32) else 0.001
+    el_deg = os1_like_elevations(beams) if elevations_deg is None else np.asarray(elevations_deg, np.float64)
+    azo = os1_like_azimuth_offsets(beams) if azimuth_offsets is None else np.asarray(azimuth_offsets, np.float64)
+    pts = lidar_scan(scene, beams=beams, azimuths=azimuths, sensor=sensor, yaw=yaw, noise_seed=noise_seed, dtype=np.float64,
+                     frame="sensor", elevations_deg=el_deg, azimuth_offsets=azo)
+    dist = np.sqrt((pts * pts).sum(axis=1))
+    el = np.deg2rad(el_deg)
+    az = 2.0 * np.pi * np.arange(azimuths) / azimuths + yaw
+    az2 = az[None, :] + azo[:, None]
+    ce, se = np.cos(el)[:, None], np.sin(el)[:, None]
+    directions = np.stack([ce * np.cos(az2), ce * np.sin(az2), se * np.ones_like(az2)], axis=-1)
+    wobble = np.random.default_rng(77).uniform(-0.002, 0.002, beams)[:, None]
+    offsets = np.stack([0.015 * np.cos(az2), 0.015 * np.sin(az2), 0.036 + wobble * np.ones_like(az2)], axis=-1)
+    units = dist / range_scale
+    if rdt.kind == "u":
+        units = np.minimum(np.rint(units), np.iinfo(rdt).max)
+    raw = units.astype(rdt)
+    if not clamp_misses:
+        raw[dist >= MAX_RANGE - 1e-6] = 0
+    if dropout > 0.0:
+        alive = drop_returns(np.arange(raw.size)[:, None], dropout, noise_seed)[:, 0]
+        keep = np.zeros(raw.size, bool)
+        keep[alive] = True
+        raw[~keep] = 0
+    return np.ascontiguousarray(raw.reshape(beams, azimuths)), np.ascontiguousarray(directions), np.ascontiguousarray(offsets)
+
+
 def sensor_transform(sensor, yaw=0.0):
     c, s = np.cos(yaw), np.sin(yaw)
     T = np.eye(4)

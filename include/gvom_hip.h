@@ -148,6 +148,43 @@ int gvom_process_pointcloud2(gvom_t *h, const void *data, int64_t n_points, int6
                              int64_t off_x, int64_t off_y, int64_t off_z, int dtype,
                              const double ego[3], const double *transform_4x4);
 
+/* --- range images (an extension: the scan as a spinning multi-beam lidar emits it) -------------------------------------------
+ * An Ouster-class sensor delivers H beams x W columns of raw ranges (0 = no return) and a fixed per-pixel lookup table -- a unit
+ * direction and a small offset -- that turns a range into a point.  gvom_sensor_model_set hands the table over once;
+ * gvom_process_range_image then takes the raw image (2 or 4 bytes per pixel instead of 12 or 24 per return, the same length
+ * every scan, beam-major by construction) and unprojects it on the GPU (k_unproject, one launch in front of the scan).
+ *
+ * SENSOR MODEL, per handle, replaceable at any time between scans: H, W >= 1 with H*W < 2^31; dir and off: float64 [H*W][3],
+ * pixel i = h*W + w (off may be NULL: zeros); range_scale: metres per raw unit (finite, > 0); min_range <= r <= max_range
+ * (metres, inclusive; 0 and +infinity accept everything).  The arrays are copied to device memory inside the call (the caller
+ * may free them on return); a model that replaces another is ordered behind every scan that read the old one.
+ * gvom_get_tuning "range_image" (read-only): 1 when a model is set, else 0 -- which is also how a caller probes a library of
+ * this ABI version for the two entry points.
+ *
+ * SCAN: raw[H][W], row-major, rows row_stride_bytes apart (>= a row, a multiple of the element size), of GVOM_RANGE_U16 /
+ * _U32 / _F32, in host memory (on_device == 0; uploaded like a host cloud) or device memory (a device pointer, nothing is
+ * copied; as for gvom_process_pointcloud_device the data must be ready when the call is made).  col_poses: NULL, or float64
+ * [W][12] in HOST memory, one row-major 3x4 per column (the de-skew of a sweep: column w was measured at pose C[w]).  cloud_dtype:
+ * GVOM_DTYPE_F32 / _F64, the type T of the cloud the scan runs on.  For pixel i = h*W + w, in float64, every operation rounded
+ * once, in exactly this order (no fused multiply-add):
+ *     r      = (double)raw[i] * range_scale
+ *     valid  = raw[i] != 0  and  r is finite  and  min_range <= r <= max_range
+ *     p[k]   = r * dir[i][k] + off[i][k]                                   k = 0, 1, 2   (multiply, then add)
+ *     q[k]   = ((p[0]*C[w][4k] + p[1]*C[w][4k+1]) + p[2]*C[w][4k+2]) + C[w][4k+3]        (with col_poses; else q = p)
+ *     xyz[i] = (T) q   for valid pixels,   (NaN, NaN, NaN)   for the others
+ * and the call IS gvom_process_pointcloud_device(xyz, H*W, 3*sizeof(T), T, ego, transform_4x4): its return codes (an image
+ * without a valid pixel is GVOM_NO_OVERLAP, as an all-NaN cloud is), ring behaviour, gvom_get_scan_stats (points = H*W),
+ * eager fusion, statistics and layout probe.  GVOM_ERR_INVALID: no model set, a bad range_dtype / cloud_dtype / row stride,
+ * and on a SHARDED handle (range images are not split over ranks). */
+int gvom_sensor_model_set(gvom_t *h, int32_t H, int32_t W, const double *dir, const double *off /* may be NULL */,
+                          double range_scale, double min_range, double max_range);
+#define GVOM_RANGE_U16 0
+#define GVOM_RANGE_U32 1
+#define GVOM_RANGE_F32 2
+int gvom_process_range_image(gvom_t *h, const void *raw, int on_device, int range_dtype, int64_t row_stride_bytes,
+                             const double *col_poses /* host, W*12, may be NULL */, int cloud_dtype,
+                             const double ego[3], const double *transform_4x4);
+
 /* --- Gvom.combine_maps (gvom.py:177-354) --------------------------------------------------
  * Caller-allocated xy_size*xy_size outputs (any of them may be NULL to skip its copy).
  * Returns GVOM_OK or GVOM_EMPTY_BUFFER. */
@@ -499,6 +536,7 @@ int gvom_host_timing(gvom_t *h, double us[8]);
  * fusions through the general kernel), "flag_kernel" (1: round 3's completion-flag kernel).
  * "occupancy_clear" (A/B of k_occupancy's dead tile columns: 0, default, the kernel writes every byte of the grid; 1 the grid is
  * cleared with hipMemsetAsync and only tile columns with a live tile are written.  Same grid either way).
+ * "range_image" (read-only, gvom_get_tuning): 1 when a sensor model is set (gvom_sensor_model_set), else 0.
  * (Test hooks are not part of this library: include/gvom_hip_test.h, lib/libgvom_hip_test.so.) */
 int gvom_set_tuning(gvom_t *h, const char *name, int value);
 /* The value the LAST scan ran with ("segs", "period", "ep_row", "prio", "interleave": what automatic resolved to).

@@ -300,6 +300,13 @@ struct gvom_handle {
     void *ri_poses_pin = nullptr;
     size_t ri_poses_pin_bytes = 0;
     int32_t ri_H = 0, ri_W = 0;                         // 0: no model set
+    // MULTI-ORIGIN scans (gvom_process_pointcloud_origins / gvom_process_range_image_origins): the K x 3 float32 table of ray
+    // origins in voxels, followed (host index) by the uint16 index of every return: ONE region in device memory, one pinned
+    // staging copy the calling thread fills (as ri_poses_pin), one upload per scan, re-used across scans
+    Buf mo_dev;
+    void *mo_pin = nullptr;
+    size_t mo_pin_bytes = 0;
+    int last_multi_origin = 0;                          // the last scan ran the per-lane-origin trace (gvom_get_tuning "multi_origin_ran")
     double ri_scale = 0.0, ri_min = 0.0, ri_max = 0.0;
 };
 
@@ -420,7 +427,7 @@ inline int clamp_delta(int64_t d, int size)
     return (int)d;
 }
 
-void fill_scan_params(const gvom_handle *h, const int64_t origin[3], const double *tf, ScanParams &P, int64_t n_points = 0)
+void fill_scan_params(const gvom_handle *h, const int64_t origin[3], const double *tf, ScanParams &P, int64_t n_points = 0, int mo_maxsteps = 0)
 {
     const gvom_params &p = h->prm;
     P.xy_res = p.xy_resolution; P.z_res = p.z_resolution;
@@ -463,7 +470,8 @@ void fill_scan_params(const gvom_handle *h, const int64_t origin[3], const doubl
     // workgroups are dispatched last and only the longest rays reach them.  (Measured, 256^3 / 131 k
     // points: 5 segments 43.6 us, 6: 44.1, 7: 43.8, 4: 46.4; flush period 16: -0.4 us against 12.)
     {
-        const int maxsteps = (p.xy_size > p.z_size ? p.xy_size : p.z_size) / 2 + 2;
+        // (multi-origin scans: the ray origins are wherever the caller says -- mo_maxsteps, from the origins at hand, see mo_table)
+        const int maxsteps = mo_maxsteps > 0 ? mo_maxsteps : (p.xy_size > p.z_size ? p.xy_size : p.z_size) / 2 + 2;
         // "plenty of returns": more 64-ray bundles than three quarters of the device's resident wave slots
         // (MI355X: 256 CUs x 32 waves -> 393,216 returns)
         const bool many = n_points / 64 > 3 * (int64_t)h->resident_blocks;
@@ -489,8 +497,10 @@ void fill_scan_params(const gvom_handle *h, const int64_t origin[3], const doubl
         {
             // automatic: what the layout probe found in the previous cloud of as many returns, at most 4 sub-clouds side by
             // side (c5, 16 sensors: interleave 4 / 8 / 16 -> k_trace 1450 / 1653 / 1745 us: a wave should keep >= 16 azimuths)
-            int K = h->tune_ilv > 1 ? h->tune_ilv : 1;
-            if (h->tune_ilv == 0 && h->counters_host) {
+            // (multi-origin scans: no interleave, no directional order, no layout probe -- all three judge directions seen from
+            // ONE sensor position; a forced knob is ignored there)
+            int K = h->tune_ilv > 1 && mo_maxsteps <= 0 ? h->tune_ilv : 1;
+            if (h->tune_ilv == 0 && h->counters_host && mo_maxsteps <= 0) {
                 // the layout probe's last answer {n << 8 | log2 K} (host-mapped; written by a kernel of an EARLIER scan)
                 const unsigned long long w = *(volatile unsigned long long *)(h->counters_host + 8);
                 if ((int64_t)(w >> 8) == n_points) K = 1 << (int)(w & 7ull);
@@ -926,7 +936,7 @@ int eager_launch(gvom_handle *h, const ScanParams &P, Slot &st, const int64_t or
 }
 
 int scan_launch(gvom_handle *h, std::unique_lock<std::mutex> &lk, const void *dev_pts, int64_t n, int64_t stride_elems,
-                int dtype, const double *tf, bool shard_local = false)
+                int dtype, const double *tf, bool shard_local = false, const RayOrigins *mo = nullptr, int mo_maxsteps = 0)
 {
     const gvom_params &p = h->prm;
     int64_t origin[3];
@@ -936,7 +946,8 @@ int scan_launch(gvom_handle *h, std::unique_lock<std::mutex> &lk, const void *de
     int rc;
     if (h->epoch >= 0xFFFFFF00u && (rc = renumber_epochs(h))) return rc;
     ScanParams P;
-    fill_scan_params(h, origin, tf, P, n);
+    fill_scan_params(h, origin, tf, P, n, mo ? mo_maxsteps : 0);
+    h->last_multi_origin = mo ? 1 : 0;
     // (a combine in flight -- combine_maps_async, or a second thread inside combine_maps -- has k_map2d's PCIe stores running
     // beside this trace: raised trace waves would take its issue slots (pipelined m256 91.7 us per step against 89.6, c3 122.0 / 115.5))
     if (h->pending_combine && h->tune_prio < 0) P.prio_div = 0;
@@ -1015,7 +1026,7 @@ int scan_launch(gvom_handle *h, std::unique_lock<std::mutex> &lk, const void *de
     // (their process_pointcloud returned behind k_trace), so which scan starts to sort is deterministic (read behind
     // the launch, scan k or k + 1 saw the new verdict depending on how fast the probe ran)
     const unsigned long long probe_word = h->counters_host ? *(volatile unsigned long long *)(h->counters_host + 8) : 0ull;
-    if (h->tune_ilv == 0 && n >= 8192) {
+    if (h->tune_ilv == 0 && n >= 8192 && !mo) {
         // layout probe: only for clouds whose length is STABLE (the same as the previous scan's: a node that drops invalid
         // returns hands over a different length every scan -- its sub-clouds do not start at multiples of n / K, nothing to find,
         // nothing to pay), on the second cloud of a length and every 32nd scan after it; in front of k_trace (the caller may
@@ -1035,7 +1046,8 @@ int scan_launch(gvom_handle *h, std::unique_lock<std::mutex> &lk, const void *de
     P.perm = nullptr;
     {   // directional order: forced, or the probe's verdict on the previous cloud of this length ("scattered", bit 3 of its answer)
         int sort = h->tune_dirsort == 1 || h->tune_dirsort == 2 ? h->tune_dirsort : 0;   // 1: cube cells, 2: elevation rows
-        if (h->tune_dirsort == 0 && h->tune_ilv == 0 && h->counters_host) {
+        if (mo) sort = 0;                                  // (bins are directions seen from ONE sensor position)
+        if (h->tune_dirsort == 0 && !mo && h->tune_ilv == 0 && h->counters_host) {
             const unsigned long long w = probe_word;
             const int64_t np_ = (int64_t)(w >> 8);
             // (the verdict on a cloud of about this length -- within a quarter -- holds for this one)
@@ -1059,7 +1071,7 @@ int scan_launch(gvom_handle *h, std::unique_lock<std::mutex> &lk, const void *de
                                       h->stats ? wpts.p : nullptr, h->hit, h->total, h->mh, st.state,
                                       st.tags, h->counters, h->stats ? (double *)st.metrics.p : nullptr,
                                       h->stats ? (double *)st.base.p : nullptr,
-                                      h->stats ? (uint32_t *)st.rowvox.p : nullptr);
+                                      h->stats ? (uint32_t *)st.rowvox.p : nullptr, mo);
     if (le != hipSuccess) { scan_abort(h); HIPCHK(h, le); }
     if (h->profiling) HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
     // (a sharded map of ONE rank has no other ranks' rows: nothing to pack, no counts to publish and to wait for -- the scan
@@ -1243,9 +1255,9 @@ int scan_upload(gvom_handle *h, std::unique_lock<std::mutex> &lk, const Upload *
 
 // 3. the cloud is now at `dev` (or will be, in stream order): scan it, commit it
 int scan_finish(gvom_handle *h, std::unique_lock<std::mutex> &lk, const void *dev, int64_t n, int64_t stride_elems, int dtype,
-                const double *tf, bool defer)
+                const double *tf, bool defer, const RayOrigins *mo = nullptr, int mo_maxsteps = 0)
 {
-    int rc = scan_launch(h, lk, dev, n, stride_elems, dtype, tf, defer);
+    int rc = scan_launch(h, lk, dev, n, stride_elems, dtype, tf, defer, mo, mo_maxsteps);
     if (rc) return rc;
     if (defer) return GVOM_OK;
     const bool accept = h->pending_any;                   // == (global occupied-voxel count > 0), gvom.py:147-150
@@ -1253,9 +1265,58 @@ int scan_finish(gvom_handle *h, std::unique_lock<std::mutex> &lk, const void *de
     return accept ? GVOM_OK : GVOM_NO_OVERLAP;
 }
 
+// ---- multi-origin scans: the host half ----
+struct OriginArgs { const double *origins; int32_t K; const uint16_t *index; };   // (index: in the memory the cloud is in, or nullptr)
+inline size_t mo_index_offset(int32_t K) { return ((size_t)K * 12 + 255) & ~(size_t)255; }
+bool mo_origins_valid(const double *origins, int32_t K)
+{
+    if (!origins || K < 1 || K > 65536) return false;
+    for (int64_t k = 0; k < (int64_t)K * 3; ++k)
+        if (!std::isfinite(origins[k])) return false;
+    return true;
+}
+// Room for the table (and `idx_n` index entries) in the pinned staging copy and in device memory; the table itself, as the host
+// computes ScanParams::pt0 from the ego (fill_scan_params): one float64 division, one rounding to float32.  Returns through
+// *maxsteps the step bound the segment table is sized with: a dominant-axis DDA moves one voxel per step along its dominant axis,
+// so a ray that starts `e` voxels from the farthest face of the window has left it after e + 2 steps; an origin more than a voxel
+// outside the window takes no step at all (its first one lies outside) and does not count.
+int mo_table(gvom_handle *h, const double *origins, int32_t K, int64_t idx_n, int *maxsteps)
+{
+    const gvom_params &p = h->prm;
+    const size_t bytes = mo_index_offset(K) + (size_t)idx_n * 2;
+    int rc = ensure(h, h->mo_dev, bytes);
+    if (rc) return rc;
+    if (h->mo_pin_bytes < bytes) {
+        if (h->mo_pin) HIPCHK(h, hipHostFree(h->mo_pin));
+        h->mo_pin = nullptr; h->mo_pin_bytes = 0;
+        HIPCHK(h, hipHostMalloc(&h->mo_pin, bytes + bytes / 2, hipHostMallocDefault));
+        h->mo_pin_bytes = bytes + bytes / 2;
+    }
+    double lo[3], size[3];
+    lo[0] = floor((h->ego[0] / p.xy_resolution) - p.xy_size / 2.0);     // the window, as scan_launch places it
+    lo[1] = floor((h->ego[1] / p.xy_resolution) - p.xy_size / 2.0);
+    lo[2] = floor((h->ego[2] / p.z_resolution) - p.z_size / 2.0);
+    size[0] = size[1] = p.xy_size; size[2] = p.z_size;
+    const double longest = (double)(p.xy_size > p.z_size ? p.xy_size : p.z_size);
+    float *tab = (float *)h->mo_pin;
+    double far_ = 0.0;
+    for (int32_t k = 0; k < K; ++k) {
+        double e = 0.0;
+        for (int a = 0; a < 3; ++a) {
+            const float v = (float)(origins[3 * k + a] / (a < 2 ? p.xy_resolution : p.z_resolution));
+            tab[3 * k + a] = v;
+            const double d0 = (double)v - lo[a], d1 = lo[a] + size[a] - (double)v;
+            e = std::max(e, std::max(d0, d1));
+        }
+        if (e <= longest + 1.0) far_ = std::max(far_, e);
+    }
+    *maxsteps = far_ > 0.0 ? (int)far_ + 3 : (int)longest / 2 + 2;
+    return GVOM_OK;
+}
+
 int process_impl(gvom_handle *h, const void *xyz, bool on_device, int64_t n, int64_t row_stride_bytes,
                  int dtype, const double ego[3], const double *tf, bool defer, const int64_t *off_bytes = nullptr,
-                 bool widen_f32 = false)
+                 bool widen_f32 = false, const OriginArgs *mo = nullptr)
 {
     if (!h || !ego || n < 0 || (dtype != GVOM_DTYPE_F32 && dtype != GVOM_DTYPE_F64))
         return GVOM_ERR_INVALID;
@@ -1265,6 +1326,12 @@ int process_impl(gvom_handle *h, const void *xyz, bool on_device, int64_t n, int
     if (n > 0 && (!xyz || row_stride_bytes < (int64_t)(3 * esz) || row_stride_bytes % esz != 0))
         return GVOM_ERR_INVALID;
     if (n >= 2147483647LL) return GVOM_ERR_CAPACITY;
+    if (mo) {                                             // (before anything is enqueued or the handle changes)
+        if (!mo_origins_valid(mo->origins, mo->K)) return GVOM_ERR_INVALID;
+        if (mo->index && !on_device)
+            for (int64_t i = 0; i < n; ++i)
+                if ((int32_t)mo->index[i] >= mo->K) return GVOM_ERR_INVALID;
+    }
     int64_t last_field = 2 * (int64_t)esz;                               // byte offset of the last field read
     if (off_bytes) {
         last_field = 0;
@@ -1276,23 +1343,38 @@ int process_impl(gvom_handle *h, const void *xyz, bool on_device, int64_t n, int
     }
     std::lock_guard<std::mutex> scan_lk(h->scan_mu);      // scans of one handle are serialised (one staging slot, one set of accumulators)
     std::unique_lock<std::mutex> lk(h->mu);
+    if (mo && h->sharded) { h->err = "multi-origin scans are not supported on a sharded handle"; return GVOM_ERR_INVALID; }
     int rc = scan_begin(h, ego, off_bytes, esz, widen_f32, defer, n);
     if (rc) return rc;
     const void *dev = xyz;
+    Upload up[2];
+    int ups = 0;
+    RayOrigins RO = {nullptr, nullptr, 0u};
+    int mo_maxsteps = 0;
+    if (mo && n > 0) {                                     // (first: from pinned memory, in flight while the cloud's own upload runs)
+        const bool host_idx = mo->index && !on_device;
+        if ((rc = mo_table(h, mo->origins, mo->K, host_idx ? n : 0, &mo_maxsteps))) return rc;
+        const size_t ioff = mo_index_offset(mo->K);
+        if (host_idx) memcpy((char *)h->mo_pin + ioff, mo->index, (size_t)n * 2);
+        up[ups++] = {h->mo_dev.p, h->mo_pin, host_idx ? ioff + (size_t)n * 2 : (size_t)mo->K * 12};
+        RO.tab = (const float *)h->mo_dev.p; RO.K = (uint32_t)mo->K;
+        RO.idx = host_idx ? (const uint16_t *)((const char *)h->mo_dev.p + ioff) : mo->index;
+    }
     if (!on_device && n > 0) {
         if ((rc = ensure(h, h->in_pts, (size_t)n * row_stride_bytes))) return rc;
-        const Upload up = {h->in_pts.p, xyz, (size_t)(n - 1) * row_stride_bytes + (size_t)last_field + esz};
-        if ((rc = scan_upload(h, lk, &up, 1))) return rc;
+        up[ups++] = {h->in_pts.p, xyz, (size_t)(n - 1) * row_stride_bytes + (size_t)last_field + esz};
         dev = h->in_pts.p;
     }
-    return scan_finish(h, lk, dev, n, row_stride_bytes / (int64_t)esz, dtype, tf, defer);
+    if (ups && (rc = scan_upload(h, lk, up, ups))) return rc;
+    return scan_finish(h, lk, dev, n, row_stride_bytes / (int64_t)esz, dtype, tf, defer, RO.tab ? &RO : nullptr, mo_maxsteps);
 }
 
 // A range image (gvom_process_range_image): raw -> (host images: staging buffer ->) k_unproject -> in_pts, then the scan of in_pts
 // as process_impl runs it on an uploaded host cloud of H * W returns
 int range_image_impl(gvom_handle *h, const void *raw, bool on_device, int range_dtype, int64_t row_stride_bytes,
-                     const double *col_poses, int cloud_dtype, const double ego[3], const double *tf)
+                     const double *col_poses, int cloud_dtype, const double ego[3], const double *tf, bool from_columns = false)
 {
+    if (from_columns && !col_poses) return GVOM_ERR_INVALID;
     if (!h || !ego || !raw || (cloud_dtype != GVOM_DTYPE_F32 && cloud_dtype != GVOM_DTYPE_F64)) return GVOM_ERR_INVALID;
     if (range_dtype != GVOM_RANGE_U16 && range_dtype != GVOM_RANGE_U32 && range_dtype != GVOM_RANGE_F32) return GVOM_ERR_INVALID;
     const int64_t rsz = range_dtype == GVOM_RANGE_U16 ? 2 : 4;
@@ -1302,12 +1384,32 @@ int range_image_impl(gvom_handle *h, const void *raw, bool on_device, int range_
     if (h->ri_H <= 0) { h->err = "gvom_process_range_image: no sensor model (gvom_sensor_model_set)"; return GVOM_ERR_INVALID; }
     const int64_t H = h->ri_H, W = h->ri_W, n = H * W;
     if (row_stride_bytes < W * rsz || row_stride_bytes % rsz != 0) { h->err = "gvom_process_range_image: bad row stride"; return GVOM_ERR_INVALID; }
+    // every pixel traced from its column's sensor position: O[w] = the translation of C[w] through the cloud's transform, in the
+    // transform's own order of operations (load_return)
+    std::vector<double> col_org;
+    if (from_columns) {
+        if (W > 65536) { h->err = "gvom_process_range_image_origins: more than 65536 columns"; return GVOM_ERR_INVALID; }
+        col_org.resize((size_t)W * 3);
+        for (int64_t w = 0; w < W; ++w) {
+            const double t0 = col_poses[w * 12 + 3], t1 = col_poses[w * 12 + 7], t2 = col_poses[w * 12 + 11];
+            for (int k = 0; k < 3; ++k)
+                col_org[w * 3 + k] = tf ? ((t0 * tf[4 * k] + t1 * tf[4 * k + 1]) + t2 * tf[4 * k + 2]) + tf[4 * k + 3] : (k == 0 ? t0 : (k == 1 ? t1 : t2));
+        }
+        if (!mo_origins_valid(col_org.data(), (int32_t)W)) { h->err = "gvom_process_range_image_origins: non-finite column position"; return GVOM_ERR_INVALID; }
+    }
     int rc = scan_begin(h, ego, nullptr, 0, false, false, n);
     if (rc) return rc;
     const size_t tsz = cloud_dtype == GVOM_DTYPE_F32 ? 4 : 8;
     if ((rc = ensure(h, h->in_pts, (size_t)n * 3 * tsz))) return rc;
-    Upload up[2];
+    Upload up[3];
     int ups = 0;
+    RayOrigins RO = {nullptr, nullptr, 0u};
+    int mo_maxsteps = 0;
+    if (from_columns) {
+        if ((rc = mo_table(h, col_org.data(), (int32_t)W, 0, &mo_maxsteps))) return rc;
+        up[ups++] = {h->mo_dev.p, h->mo_pin, (size_t)W * 12};
+        RO.tab = (const float *)h->mo_dev.p; RO.K = (uint32_t)W;      // index[i] = i % W: the pixel's column
+    }
     if (col_poses) {                                       // (first: see ri_poses_pin)
         const size_t bytes = (size_t)W * 96;
         if ((rc = ensure(h, h->ri_poses, bytes))) return rc;
@@ -1334,7 +1436,7 @@ int range_image_impl(gvom_handle *h, const void *raw, bool on_device, int range_
     U.scale = h->ri_scale; U.min_range = h->ri_min; U.max_range = h->ri_max;
     U.W = (uint32_t)W; U.n = (uint32_t)n;
     HIPCHK(h, gvom_launch_unproject(h->stream, U, range_dtype, cloud_dtype));
-    return scan_finish(h, lk, h->in_pts.p, n, 3, cloud_dtype, tf, false);
+    return scan_finish(h, lk, h->in_pts.p, n, 3, cloud_dtype, tf, false, from_columns ? &RO : nullptr, mo_maxsteps);
 }
 
 // z decomposition of k_fuse: chunks of zc levels (16 whenever z_size <= 256), cpw chunks per wave,
@@ -1692,7 +1794,7 @@ VIS void gvom_destroy(gvom_t *h)
     if (h->x_host) hipHostFree(h->x_host);
     for (auto &s : h->slots) { hipFree(s.state); hipFree(s.code16); hipFree(s.tags); fb(s.crows); fb(s.metrics); fb(s.base); fb(s.rowvox); }
     for (auto &f : h->fused) { hipFree(f.state); hipFree(f.tags); fb(f.rows); fb(f.metrics); }
-    fb(h->in_pts); fb(h->ri_model); fb(h->ri_raw); fb(h->ri_poses); if (h->ri_poses_pin) hipHostFree(h->ri_poses_pin); fb(h->world_pts[0]); fb(h->world_pts[1]); fb(h->flink[0]); fb(h->flink[1]); fb(h->tl); fb(h->dir_keys); fb(h->dir_perm); hipFree(h->dir_hist);
+    fb(h->in_pts); fb(h->ri_model); fb(h->ri_raw); fb(h->ri_poses); if (h->ri_poses_pin) hipHostFree(h->ri_poses_pin); fb(h->mo_dev); if (h->mo_pin) hipHostFree(h->mo_pin); fb(h->world_pts[0]); fb(h->world_pts[1]); fb(h->flink[0]); fb(h->flink[1]); fb(h->tl); fb(h->dir_keys); fb(h->dir_perm); hipFree(h->dir_hist);
     hipFree(h->counters); if (h->counters_host) hipHostFree(h->counters_host);
     hipFree(h->descs_dev); if (h->descs_host) hipHostFree(h->descs_host);
     hipFree(h->blockcounts); hipFree(h->blockcounts2); hipFree(h->hmaps2);
@@ -1784,6 +1886,21 @@ VIS int gvom_process_range_image(gvom_t *h, const void *raw, int on_device, int 
                                  const double *col_poses, int cloud_dtype, const double ego[3], const double *transform_4x4)
 {
     return range_image_impl(h, raw, on_device != 0, range_dtype, row_stride_bytes, col_poses, cloud_dtype, ego, transform_4x4);
+}
+
+// ---- multi-origin scans (include/gvom_hip.h "multi-origin scans") ---------------------------------
+VIS int gvom_process_pointcloud_origins(gvom_t *h, const void *xyz, int on_device, int64_t n, int64_t row_stride_bytes, int dtype,
+                                        const double *origins, int32_t K, const uint16_t *index, const double ego[3],
+                                        const double *transform_4x4)
+{
+    const OriginArgs mo = {origins, K, index};
+    return process_impl(h, xyz, on_device != 0, n, row_stride_bytes, dtype, ego, transform_4x4, false, nullptr, false, &mo);
+}
+
+VIS int gvom_process_range_image_origins(gvom_t *h, const void *raw, int on_device, int range_dtype, int64_t row_stride_bytes,
+                                         const double *col_poses, int cloud_dtype, const double ego[3], const double *transform_4x4)
+{
+    return range_image_impl(h, raw, on_device != 0, range_dtype, row_stride_bytes, col_poses, cloud_dtype, ego, transform_4x4, true);
 }
 
 // ---- scan of a sharded map (one rank per GPU; DESIGN.md "Multi-GPU") ---------------------------
@@ -3073,6 +3190,8 @@ VIS int gvom_get_tuning(gvom_t *h, const char *name, int *value)
     if (!strcmp(name, "device_map_sets")) { *value = (int)h->dsets.size(); return GVOM_OK; }             // read-only: allocated device map sets                  // read-only, GVOM_ROUTE_*
     if (!strcmp(name, "device_product_sets")) { *value = (int)h->psets.size(); return GVOM_OK; }        // read-only: allocated device product sets (every kind)
     if (!strcmp(name, "occupancy_clear")) { *value = h->tune_occ_clear; return GVOM_OK; }
+    if (!strcmp(name, "multi_origin")) { *value = 1; return GVOM_OK; }                                  // read-only: the library has the multi-origin entry points
+    if (!strcmp(name, "multi_origin_ran")) { *value = h->last_multi_origin; return GVOM_OK; }           // read-only: the last scan ran the per-lane-origin trace
     if (!strcmp(name, "range_image")) { *value = h->ri_H > 0 ? 1 : 0; return GVOM_OK; }                 // read-only: a sensor model is set
     if (!strcmp(name, "fastdiv")) { *value = h->tune_fastdiv == 0 ? 0 : h->fastdiv_ok; return GVOM_OK; }   // bit 0 / 1: xy / z resolution divided by reciprocal
     return GVOM_ERR_INVALID;

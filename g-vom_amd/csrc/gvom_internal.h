@@ -113,6 +113,13 @@ struct ShardExchange {
     uint32_t *sp_cnt;     // [world * 16]
 };
 
+// multi-origin scans (gvom_process_pointcloud_origins): return i is traced from row index[i] of a table of K ray origins
+struct RayOrigins {
+    const float    *tab;  // device, [K][3]: (float)(origin / resolution), the per-return ScanParams::pt0 (gvom.py:1097-1099)
+    const uint16_t *idx;  // device, [n], or nullptr: index[i] = i % K
+    uint32_t        K;
+};
+
 #define GVOM_PACK_CHUNK 64     // quads per k_pack workgroup
 #define GVOM_BASE_PITCH 16     // doubles per row of a scan's own-voxel moments (10 used): one 128-byte block per row
 // rank exchange, owner side: received quads of all source ranks are unpacked by one launch
@@ -200,7 +207,7 @@ hipError_t gvom_launch_trace(hipStream_t s, const ScanParams &P, const ShardExch
                              int64_t stride_elems, int64_t n, void *world, uint32_t *hit,
                              uint32_t *total, uint32_t *mh, int32_t *state, uint32_t *tags,
                              uint32_t *counters, double *stat_sums, double *stat_base,
-                             uint32_t *stat_rowvox);
+                             uint32_t *stat_rowvox, const RayOrigins *origins = nullptr);
 hipError_t gvom_launch_pack(hipStream_t s, const ScanParams &P, uint32_t *total, const uint32_t *tags, uint32_t *send_ids,
                             void *send_pay, uint32_t *qcnt, uint32_t *ecnt, uint32_t *spcnt, uint32_t *counters,
                             unsigned long long *host_out, uint32_t seq);

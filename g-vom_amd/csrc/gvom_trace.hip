@@ -214,13 +214,14 @@ __device__ __forceinline__ void endpoint_commit(const ScanParams &P, int lane, l
 // Ray set-up of one return (gvom.py:1093-1118): per-step increments in natural (x, y, z) order, the
 // f64 step length and the length limit of the reference's loop test.
 struct RaySetup { float incx, incy, incz; double step_len, inv_step, lim; bool finite; };
-template <typename T>
-__device__ __forceinline__ RaySetup ray_setup(const ScanParams &P, T x, T y, T z)
+// (MO: the ray starts at the lane's own (o0, o1, o2) -- its row of the origin table, trace_item -- instead of at ScanParams::pt0)
+template <typename T, bool MO>
+__device__ __forceinline__ RaySetup ray_setup(const ScanParams &P, T x, T y, T z, float o0, float o1, float o2)
 {
     const float e0 = (float)div_by_res<T>(x, P.xy_res, P.drcp[0], P.fastdiv & 1);
     const float e1 = (float)div_by_res<T>(y, P.xy_res, P.drcp[0], P.fastdiv & 1);
     const float e2 = (float)div_by_res<T>(z, P.z_res, P.drcp[1], P.fastdiv & 2);
-    float s0 = e0 - P.pt0[0], s1 = e1 - P.pt0[1], s2 = e2 - P.pt0[2];
+    float s0 = e0 - (MO ? o0 : P.pt0[0]), s1 = e1 - (MO ? o1 : P.pt0[1]), s2 = e2 - (MO ? o2 : P.pt0[2]);
     const float ss = (s0 * s0 + s1 * s1) + s2 * s2;
     // math.sqrt -> f64; GVOM_FLAG_CUDA_F32_SQRT: sqrt of the f32 sum in f32, as real
     // Numba-CUDA types it (gvom.py:1109-1114)
@@ -476,12 +477,17 @@ __device__ __forceinline__ void walk_item(const ScanParams &P, int lane, uint32_
 // ------------------------------------------------------------------------------------------
 // One (dispatch row, 64-ray bundle) item of the trace: the endpoint work of the bundle (row == P.ep_row) or one step
 // segment of its rays.  lck / lcc: the wave's line cache, clean on entry and on exit.
-template <typename T, bool BIG>
+// MO (multi-origin scans, gvom_process_pointcloud_origins): return i starts at row index[i] of the origin table O instead of
+// at P.pt0 -- three VGPRs per lane where the single-origin form reads three SGPRs -- in the ray set-up, the early-exit
+// estimate, the start position and the replay.  Behind the set-up a ray is positions and increments: walk_item / walk_steps
+// are the same code in both forms.  A return whose index is not below O.K has no effect at all (no endpoint, no ray) and reads
+// no table row.
+template <typename T, bool BIG, bool MO>
 __device__ __forceinline__ void trace_item(const ScanParams &P, const ShardExchange &X, const T *__restrict__ in, long stride, long n,
                                            T *__restrict__ world, uint32_t *hit, uint32_t *total, uint32_t *mh, int32_t *state,
                                            uint32_t *tags, uint32_t *counters, double *stat_sums, double *stat_base,
                                            uint32_t *stat_rowvox, int row, long bundle, int lane, uint32_t *lck, uint32_t *lcc,
-                                           size_t widx, const WalkConsts &C)
+                                           size_t widx, const WalkConsts &C, const RayOrigins &O)
 {
     const long pos = bundle * 64 + lane;
     const bool live = pos < n;
@@ -490,8 +496,18 @@ __device__ __forceinline__ void trace_item(const ScanParams &P, const ShardExcha
     const long i = P.perm ? (live ? (long)P.perm[pos] : pos) : (P.ilv_lg ? (pos & ((1L << P.ilv_lg) - 1)) * P.ilv_len + (pos >> P.ilv_lg) : pos);
     T x = 0, y = 0, z = 0;
     if (live) load_return(P, in, stride, i, x, y, z);
+    float ox = 0.0f, oy = 0.0f, oz = 0.0f;               // (MO only: the single-origin form reads P.pt0 where it always has)
+    bool valid = live;
+    if (MO) {
+        // one gather per item from a table of K x 12 bytes that every wave of the scan reads (it stays in the L2, mostly in
+        // the CU's vector cache); a wave's rows are usually one or two (sensor groups) or 64 consecutive ones (columns of a sweep)
+        const uint32_t k = !live ? O.K : (O.idx ? (uint32_t)O.idx[i] : (uint32_t)i % O.K);      // (n < 2^31)
+        valid = k < O.K;
+        if (valid) { ox = O.tab[3 * k + 0]; oy = O.tab[3 * k + 1]; oz = O.tab[3 * k + 2]; }
+        else if (live) { x = y = z = (T)NAN; }               // (k_stats drops a NaN return as well)
+    }
     const T d2 = (x * x + y * y) + z * z;
-    const bool pass = live && !((double)d2 < P.min_d2);
+    const bool pass = (MO ? valid : live) && !((double)d2 < P.min_d2);
     // endpoint work: in the items of row P.ep_row, or (P.ep_row < 0) in the waves of segment 0
     const bool ep_here = P.ep_row >= 0 ? row == P.ep_row : row == 0;
     if (ep_here) {
@@ -572,14 +588,14 @@ __device__ __forceinline__ void trace_item(const ScanParams &P, const ShardExcha
     // margin far above the rounding of this estimate; NaN/inf compare false and take the full path.
     if (seg > 0) {
         const float ax = (float)x * P.rinv[0], ay = (float)y * P.rinv[0], az = (float)z * P.rinv[1];
-        const float ux = ax - P.pt0[0], uy = ay - P.pt0[1], uz = az - P.pt0[2];
+        const float ux = ax - (MO ? ox : P.pt0[0]), uy = ay - (MO ? oy : P.pt0[1]), uz = az - (MO ? oz : P.pt0[2]);
         const float r = sqrtf((ux * ux + uy * uy) + uz * uz);
         const float mag = ((fabsf(ax) + fabsf(ay)) + fabsf(az)) + ((fabsf(ux) + fabsf(uy)) + fabsf(uz));
         const bool dead = !pass || (r + (r * 1e-5f + mag * 4e-6f) <= (float)j0 + 0.9f);
         if (lanes(!dead) == 0ull) { TL_MARK(P, widx, 2); return; }       // wave-uniform
     }
-    const RaySetup R = ray_setup<T>(P, x, y, z);
-    float px = P.pt0[0], py = P.pt0[1], pz = P.pt0[2];
+    const RaySetup R = ray_setup<T, MO>(P, x, y, z, ox, oy, oz);
+    float px = MO ? ox : P.pt0[0], py = MO ? oy : P.pt0[1], pz = MO ? oz : P.pt0[2];
     bool run = pass && R.finite;
     if (run) {                                           // step 1 outside the grid: no step at all
         uint32_t wx, wy, wz;
@@ -614,11 +630,13 @@ __device__ __forceinline__ void trace_item(const ScanParams &P, const ShardExcha
 // from being reused: +11 %, c4 +28 %), and a dispatch order planned from the previous scan so that every CU gets 3 or 4
 // walking workgroups instead of 1 to 5 (no gain: all walking waves are resident from t = 0 either way and the kernel
 // runs at the VALU issue rate).)
-template <typename T, bool BIG, int WPB>
-__global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_trace(
-    const ScanParams P, const ShardExchange X, const T *__restrict__ in, long stride, long n, T *__restrict__ world,
+// (the body of k_trace and of k_trace_origins, its multi-origin form: two kernels, so that the single-origin one keeps its
+// arguments and its code)
+template <typename T, bool BIG, int WPB, bool MO>
+__device__ __forceinline__ void trace_block(
+    const ScanParams &P, const ShardExchange &X, const T *__restrict__ in, long stride, long n, T *__restrict__ world,
     uint32_t *hit, uint32_t *total, uint32_t *mh, int32_t *state, uint32_t *tags, uint32_t *counters, double *stat_sums,
-    double *stat_base, uint32_t *stat_rowvox)
+    double *stat_base, uint32_t *stat_rowvox, const RayOrigins &O)
 {
     const int lane = threadIdx.x & (WAVE - 1);
     const int row = (int)blockIdx.y;
@@ -640,8 +658,26 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(8, 8))
     WC.prof = (P.tl && P.prof_on && (widx & 63) == 0 && row != P.ep_row) ? P.tl + P.tl_words + 8 + (widx >> 6) * 128 : nullptr;
     WC.prof_n = 0;
 #endif
-    trace_item<T, BIG>(P, X, in, stride, n, world, hit, total, mh, state, tags, counters, stat_sums, stat_base, stat_rowvox,
-                       row, bundle, lane, lck, lcc, widx, WC);
+    trace_item<T, BIG, MO>(P, X, in, stride, n, world, hit, total, mh, state, tags, counters, stat_sums, stat_base, stat_rowvox,
+                           row, bundle, lane, lck, lcc, widx, WC, O);
+}
+template <typename T, bool BIG, int WPB>
+__global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_trace(
+    const ScanParams P, const ShardExchange X, const T *__restrict__ in, long stride, long n, T *__restrict__ world,
+    uint32_t *hit, uint32_t *total, uint32_t *mh, int32_t *state, uint32_t *tags, uint32_t *counters, double *stat_sums,
+    double *stat_base, uint32_t *stat_rowvox)
+{
+    const RayOrigins none = {nullptr, nullptr, 0u};
+    trace_block<T, BIG, WPB, false>(P, X, in, stride, n, world, hit, total, mh, state, tags, counters, stat_sums, stat_base, stat_rowvox, none);
+}
+// k_trace with every lane's ray starting at its own row of the origin table O (trace_item's MO form)
+template <typename T, bool BIG, int WPB>
+__global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_trace_origins(
+    const ScanParams P, const ShardExchange X, const T *__restrict__ in, long stride, long n, T *__restrict__ world,
+    uint32_t *hit, uint32_t *total, uint32_t *mh, int32_t *state, uint32_t *tags, uint32_t *counters, double *stat_sums,
+    double *stat_base, uint32_t *stat_rowvox, const RayOrigins O)
+{
+    trace_block<T, BIG, WPB, true>(P, X, in, stride, n, world, hit, total, mh, state, tags, counters, stat_sums, stat_base, stat_rowvox, O);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -785,17 +821,28 @@ hipError_t gvom_launch_trace(hipStream_t s, const ScanParams &P, const ShardExch
                              int64_t stride_elems, int64_t n, void *world, uint32_t *hit,
                              uint32_t *total, uint32_t *mh, int32_t *state, uint32_t *tags,
                              uint32_t *counters, double *stat_sums, double *stat_base,
-                             uint32_t *stat_rowvox)
+                             uint32_t *stat_rowvox, const RayOrigins *origins)
 {
     if (n <= 0) return hipSuccess;
+#define TRACE_GRID(WW) dim3((unsigned)((n + 64 * WW - 1) / (64 * WW)), (unsigned)P.nsegs + (P.ep_row >= 0 ? 1u : 0u) + ((unsigned)GVOM_DBG(P, 0xF00) >> 8))
 #define TRACE_LAUNCH(TT, BB, WW)                                                                             \
-    hipLaunchKernelGGL((k_trace<TT, BB, WW>), dim3((unsigned)((n + 64 * WW - 1) / (64 * WW)), (unsigned)P.nsegs + (P.ep_row >= 0 ? 1u : 0u) + ((unsigned)GVOM_DBG(P, 0xF00) >> 8)), dim3(64 * WW), 0, s, P, X, (const TT *)pts, \
+    hipLaunchKernelGGL((k_trace<TT, BB, WW>), TRACE_GRID(WW), dim3(64 * WW), 0, s, P, X, (const TT *)pts, \
                        (long)stride_elems, (long)n, (TT *)world, hit, total, mh, state, tags, counters,     \
                        stat_sums, stat_base, stat_rowvox)
+#define TRACE_LAUNCH_MO(TT, BB, WW)                                                                          \
+    hipLaunchKernelGGL((k_trace_origins<TT, BB, WW>), TRACE_GRID(WW), dim3(64 * WW), 0, s, P, X, (const TT *)pts, \
+                       (long)stride_elems, (long)n, (TT *)world, hit, total, mh, state, tags, counters,     \
+                       stat_sums, stat_base, stat_rowvox, *origins)
     // 8 waves per workgroup (measured on m256: 1 / 2 / 4 / 8 / 16 waves -> 47.4 / 44.6 / 41.7 / 40.5 / 42.8 us)
-    if (dtype == 0) { if (big_origin) TRACE_LAUNCH(float, true, 8); else TRACE_LAUNCH(float, false, 8); }
+    if (origins) {                                        // the per-lane-origin instantiations (trace_item's MO)
+        if (dtype == 0) { if (big_origin) TRACE_LAUNCH_MO(float, true, 8); else TRACE_LAUNCH_MO(float, false, 8); }
+        else { if (big_origin) TRACE_LAUNCH_MO(double, true, 8); else TRACE_LAUNCH_MO(double, false, 8); }
+    }
+    else if (dtype == 0) { if (big_origin) TRACE_LAUNCH(float, true, 8); else TRACE_LAUNCH(float, false, 8); }
     else { if (big_origin) TRACE_LAUNCH(double, true, 8); else TRACE_LAUNCH(double, false, 8); }
 #undef TRACE_LAUNCH
+#undef TRACE_LAUNCH_MO
+#undef TRACE_GRID
     return hipGetLastError();
 }
 

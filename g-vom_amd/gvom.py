@@ -87,6 +87,8 @@ ABI = [
     ("gvom_process_pointcloud_device", _I, [_P, _P, _I64, _I64, _I, _DP, _P]),
     ("gvom_sensor_model_set", _I, [_P, ctypes.c_int32, ctypes.c_int32, _P, _P, ctypes.c_double, ctypes.c_double, ctypes.c_double]),
     ("gvom_process_range_image", _I, [_P, _P, _I, _I, _I64, _P, _I, _DP, _P]),
+    ("gvom_process_pointcloud_origins", _I, [_P, _P, _I, _I64, _I64, _I, _P, ctypes.c_int32, _P, _DP, _P]),
+    ("gvom_process_range_image_origins", _I, [_P, _P, _I, _I, _I64, _P, _I, _DP, _P]),
     ("gvom_combine_maps", _I, [_P, _P, _P, _P, _P, _P]),
     ("gvom_output_buffer_alloc", _I, [_P, ctypes.POINTER(_P)]),
     ("gvom_output_buffer_free", _I, [_P, _P]),
@@ -275,6 +277,38 @@ def unproject_range_image(ranges, directions, offsets=None, range_scale=0.001, m
     if drop_invalid:
         xyz = xyz[valid.reshape(-1)]
     return np.ascontiguousarray(xyz)
+
+
+def column_origins(column_transforms, transform=None):
+    """The ray origins of Gvom.process_range_image_origins: [W, 3] float64, row w = the translation of column
+    w's pose taken through `transform` in the cloud transform's order of operations (include/gvom_hip.h "multi-origin scans"):
+
+        t = C[w][:, 3];   O[w][k] = ((t[0]*tf[k][0] + t[1]*tf[k][1]) + t[2]*tf[k][2]) + tf[k][3]      (O[w] = t without a transform)
+
+    so that process_range_image_origins(r, ego, tf, cols) is
+    process_pointcloud_origins(unproject_range_image(r, <model>, column_transforms=cols), column_origins(cols, tf), ego, tf)."""
+    c = np.asarray(column_transforms, dtype=np.float64)
+    if c.ndim != 3 or c.shape[1] not in (3, 4) or c.shape[2] != 4:
+        raise ValueError("column_transforms must have shape (W, 4, 4) or (W, 3, 4), got %r" % (c.shape,))
+    t = np.ascontiguousarray(c[:, :3, 3])
+    if transform is None:
+        return t
+    tf = np.asarray(transform, dtype=np.float64)
+    if tf.shape != (4, 4):
+        raise ValueError("transform must be 4x4")
+    return np.stack([((t[:, 0] * tf[k, 0] + t[:, 1] * tf[k, 1]) + t[:, 2] * tf[k, 2]) + tf[k, 3] for k in range(3)], axis=-1)
+
+
+def _origin_table(origins):
+    """[K, 3] finite float64, 1 <= K <= 65536 (C-contiguous)"""
+    o = np.ascontiguousarray(np.asarray(origins, dtype=np.float64))
+    if o.ndim != 2 or o.shape[1] != 3:
+        raise ValueError("origins must have shape (K, 3), got %r" % (o.shape,))
+    if not 1 <= o.shape[0] <= 65536:
+        raise ValueError("origins: 1 <= K <= 65536, got K = %d" % o.shape[0])
+    if not np.isfinite(o).all():
+        raise ValueError("origins must be finite")
+    return o
 
 
 class _DeviceArrayView(object):
@@ -817,6 +851,61 @@ class Gvom(object):
         return self._check(self._lib.gvom_process_pointcloud_device(
             self._h, ctypes.c_void_p(int(dev_ptr)), int(n), int(stride), code, ego, _ptr(tf)))
 
+    # ---- multi-origin scans: every return traced from its own sensor position (include/gvom_hip.h "multi-origin scans") ----
+    def _warn_scan(self, rc):
+        if rc == GVOM_EMPTY_CLOUD:
+            print("[WARNING] Processing an empty pointcloud, nothing will happen!")
+        elif rc == GVOM_NO_OVERLAP:
+            print("[WARNING] The pointcloud points don't overlap with any voxels, nothing will happen!")
+
+    def process_pointcloud_origins(self, pointcloud, origins, ego_position, transform=None, origin_index=None):
+        """process_pointcloud with return i traced from origins[origin_index[i]] instead of from ego_position, which keeps
+        every other role (it places the window).  origins [K, 3] world-frame sensor positions (`transform` is not applied to
+        them), 1 <= K <= 65536; origin_index [N] integers below K, or None: return i belongs to origin i % K.  Returns None."""
+        pc, n, stride, code = self._prepare_cloud(pointcloud)
+        o = _origin_table(origins)
+        idx = None
+        if origin_index is not None:
+            raw = np.asarray(origin_index)
+            if raw.shape != (n,):
+                raise ValueError("origin_index must have shape (%d,), got %r" % (n, raw.shape))
+            if n and (raw.min() < 0 or raw.max() >= o.shape[0]):
+                raise ValueError("origin_index entries must lie in [0, %d)" % o.shape[0])
+            idx = np.ascontiguousarray(raw.astype(np.uint16))
+        tf = None
+        if transform is not None:
+            tf = np.ascontiguousarray(np.asarray(transform, dtype=np.float64))
+            if tf.shape != (4, 4):
+                raise ValueError("transform must be 4x4")
+        self.ego_position = ego_position
+        ego = (ctypes.c_double * 3)(float(ego_position[0]), float(ego_position[1]), float(ego_position[2]))
+        self._warn_scan(self._check_args(self._lib.gvom_process_pointcloud_origins(
+            self._h, _ptr(pc) if n else None, 0, n, stride, code, _ptr(o), o.shape[0], _ptr(idx), ego, _ptr(tf))))
+        return None
+
+    def process_pointcloud_origins_device(self, dev_ptr, n, dtype, origins, ego_position, transform=None,
+                                          origin_index_ptr=None, row_stride_bytes=None):
+        """process_pointcloud_origins for a cloud already resident in HBM.  origins: a HOST [K, 3] array; origin_index_ptr: a raw
+        device pointer to n uint16, or None (i % K).  The device index cannot be checked by the host: a return whose index is
+        not below K has no effect at all."""
+        code = 0 if (dtype is np.float32 or np.dtype(dtype) == np.float32) else 1
+        stride = row_stride_bytes or (12 if code == 0 else 24)
+        o = _origin_table(origins)
+        tf = None
+        if transform is not None:
+            tf = np.ascontiguousarray(np.asarray(transform, dtype=np.float64))
+        self.ego_position = ego_position
+        ego = (ctypes.c_double * 3)(float(ego_position[0]), float(ego_position[1]), float(ego_position[2]))
+        return self._check_args(self._lib.gvom_process_pointcloud_origins(
+            self._h, ctypes.c_void_p(int(dev_ptr)), 1, int(n), int(stride), code, _ptr(o), o.shape[0],
+            None if origin_index_ptr is None else ctypes.c_void_p(int(origin_index_ptr)), ego, _ptr(tf)))
+
+    def _check_args(self, rc):
+        """_check, with GVOM_ERR_INVALID (-1) as the ValueError the binding's own argument checks raise"""
+        if rc == GVOM_ERR_INVALID:
+            raise ValueError("libgvom_hip: invalid argument: %s" % self._lib.gvom_last_error(self._h).decode())
+        return self._check(rc)
+
     # ---- ingest side of the ROS node (reference gvom_ros.py:93-109; SURVEY 8f rank 4) ----------
     def process_pointcloud2(self, data, n_points, point_step, offsets, ego_position, transform=None,
                             field_dtype=np.float32):
@@ -876,7 +965,10 @@ class Gvom(object):
                                                     float(min_range), float(max_range)))
         self._sensor_shape = (d.shape[0], d.shape[1])
 
-    def _range_image_call(self, raw_ptr, on_device, rcode, stride, ego_position, transform, column_transforms, cloud_dtype):
+    def _range_image_call(self, raw_ptr, on_device, rcode, stride, ego_position, transform, column_transforms, cloud_dtype,
+                          trace_from_columns=False):
+        if trace_from_columns and column_transforms is None:
+            raise ValueError("process_range_image_origins needs column_transforms (the sensor's pose per column)")
         shape = getattr(self, "_sensor_shape", None)
         poses = _column_poses(column_transforms, shape[1]) if (column_transforms is not None and shape) else None
         self.ego_position = ego_position
@@ -886,8 +978,12 @@ class Gvom(object):
             tf = np.ascontiguousarray(np.asarray(transform, dtype=np.float64))
             if tf.shape != (4, 4):
                 raise ValueError("transform must be 4x4")
-        rc = self._check(self._lib.gvom_process_range_image(self._h, raw_ptr, int(on_device), rcode, int(stride), _ptr(poses),
-                                                            _cloud_code(cloud_dtype), ego, _ptr(tf)))
+        if trace_from_columns:
+            rc = self._check_args(self._lib.gvom_process_range_image_origins(self._h, raw_ptr, int(on_device), rcode, int(stride),
+                                                                             _ptr(poses), _cloud_code(cloud_dtype), ego, _ptr(tf)))
+        else:
+            rc = self._check(self._lib.gvom_process_range_image(self._h, raw_ptr, int(on_device), rcode, int(stride), _ptr(poses),
+                                                                _cloud_code(cloud_dtype), ego, _ptr(tf)))
         if rc == GVOM_EMPTY_CLOUD:
             print("[WARNING] Processing an empty pointcloud, nothing will happen!")
         elif rc == GVOM_NO_OVERLAP:
@@ -900,6 +996,15 @@ class Gvom(object):
         per column (the sweep's de-skew), applied before `transform`.  Equivalent to
             self.process_pointcloud(unproject_range_image(ranges, <the model>, column_transforms, cloud_dtype), ego_position, transform)
         with the unprojection done on the GPU and 2 or 4 bytes per pixel uploaded.  Returns None."""
+        return self._range_image_host(ranges, ego_position, transform, column_transforms, cloud_dtype, False)
+
+    def process_range_image_origins(self, ranges, ego_position, transform=None, column_transforms=None, cloud_dtype=np.float32):
+        """process_range_image with every pixel's ray starting at its column's sensor position -- column_origins(
+        column_transforms, transform) -- instead of at ego_position, as process_pointcloud_origins traces it.
+        column_transforms is required.  Returns None."""
+        return self._range_image_host(ranges, ego_position, transform, column_transforms, cloud_dtype, True)
+
+    def _range_image_host(self, ranges, ego_position, transform, column_transforms, cloud_dtype, trace_from_columns):
         raw = ranges if isinstance(ranges, np.ndarray) else np.asarray(ranges)
         rcode = _range_code(raw.dtype)
         if raw.ndim != 2 or raw.shape[0] < 1 or raw.shape[1] < 1:
@@ -911,7 +1016,8 @@ class Gvom(object):
             raise ValueError("ranges must be C-contiguous in the last axis with rows a whole number of elements apart")
         if shape is None and column_transforms is not None:
             _column_poses(column_transforms, raw.shape[1])
-        return self._range_image_call(_ptr(raw), 0, rcode, raw.strides[0], ego_position, transform, column_transforms, cloud_dtype)
+        return self._range_image_call(_ptr(raw), 0, rcode, raw.strides[0], ego_position, transform, column_transforms, cloud_dtype,
+                                      trace_from_columns)
 
     def process_range_image_device(self, dev_ptr, range_dtype, ego_position, transform=None, column_transforms=None,
                                    cloud_dtype=np.float32, row_stride_bytes=None):
@@ -922,6 +1028,15 @@ class Gvom(object):
         stride = row_stride_bytes or ((shape[1] if shape else 0) * np.dtype(range_dtype).itemsize)
         return self._range_image_call(ctypes.c_void_p(int(dev_ptr)), 1, rcode, stride, ego_position, transform, column_transforms,
                                       cloud_dtype)
+
+    def process_range_image_origins_device(self, dev_ptr, range_dtype, ego_position, transform=None, column_transforms=None,
+                                           cloud_dtype=np.float32, row_stride_bytes=None):
+        """process_range_image_origins for an image already resident in HBM (see process_range_image_device)."""
+        rcode = _range_code(range_dtype)
+        shape = getattr(self, "_sensor_shape", None)
+        stride = row_stride_bytes or ((shape[1] if shape else 0) * np.dtype(range_dtype).itemsize)
+        return self._range_image_call(ctypes.c_void_p(int(dev_ptr)), 1, rcode, stride, ego_position, transform, column_transforms,
+                                      cloud_dtype, True)
 
     def combine_maps(self):
         """Combines all maps in the buffer and processes the resultant map into 2D maps

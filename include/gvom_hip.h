@@ -185,6 +185,42 @@ int gvom_process_range_image(gvom_t *h, const void *raw, int on_device, int rang
                              const double *col_poses /* host, W*12, may be NULL */, int cloud_dtype,
                              const double ego[3], const double *transform_4x4);
 
+/* --- multi-origin scans (an extension: every return traced from its own sensor position) -------------------------------------
+ * The scan calls above trace every ray from `ego`, which also places the window.  A de-skewed sweep (the sensor moved while it
+ * turned) and a vehicle with several lidars have returns that were measured from DIFFERENT places: here return i is traced from
+ * origins[index[i]].  `ego` keeps every other role: window origin, gvom_state.ego_position, the robot-radius fill of the fusion,
+ * the return codes.
+ *
+ * gvom_process_pointcloud_origins is gvom_process_pointcloud (on_device == 0) / gvom_process_pointcloud_device (else) with
+ * gvom.py:1097-1099 replaced, for return i, by
+ *     k = index[i];  pt[0] = (float)(O[k][0] / xy_resolution);  pt[1] = (float)(O[k][1] / xy_resolution);  pt[2] = (float)(O[k][2] / z_resolution)
+ * (float64 division, one rounding to float32: what the host does for `ego`).  Endpoint, min-height, the min-distance test (from
+ * the WORLD origin), the transform of the cloud, ring commit, GVOM_EMPTY_CLOUD / GVOM_NO_OVERLAP, statistics and eager fusion are
+ * unchanged, with the window computed from `ego`.  origins: HOST float64 [K][3], 1 <= K <= 65536, finite, world frame (the
+ * frame of `ego`: transform_4x4 is NOT applied to them).  index: uint16 [n] in the memory the cloud is in (host when
+ * on_device == 0, else device), or NULL: index[i] = i % K.  The reference's own behaviour for an unusual ray start follows: an
+ * origin outside the window contributes endpoints only (its first step is outside), an origin equal to its return takes no step.
+ * GVOM_ERR_INVALID: K out of range, a non-finite origin, a HOST index entry >= K (checked before anything is enqueued: the ring
+ * is untouched), and on a SHARDED handle (multi-origin scans are not split over ranks).  A DEVICE index cannot be checked by the
+ * host: a return with index[i] >= K has no effect at all -- no endpoint, no ray, no table row read.
+ * The step segments of k_trace are sized from the origins at hand; the layout probe, "dirsort" and "interleave" -- which order
+ * returns by direction seen from ONE sensor position -- do not run on this route, forced or not (gvom_get_tuning reports
+ * interleave 1, dirsort 0 after such a scan).  gvom_get_tuning "multi_origin" (read-only): 1 -- how a caller probes a library of
+ * this ABI version for the two entry points; "multi_origin_ran": 1 when the LAST scan ran the per-lane-origin trace.
+ *
+ * gvom_process_range_image_origins is gvom_process_range_image with every pixel traced from its COLUMN's sensor position.
+ * col_poses is required (GVOM_ERR_INVALID without; also for W > 65536).  O[w] is the translation of C[w] taken through
+ * transform_4x4 in the cloud transform's order, in float64, on the host:
+ *     t = (C[w][3], C[w][7], C[w][11]);   O[w][k] = ((t0*tf[4k] + t1*tf[4k+1]) + t2*tf[4k+2]) + tf[4k+3]   (O[w] = t without a transform)
+ * and the call IS gvom_process_pointcloud_origins on the unprojected cloud with origins = O, K = W, index = NULL (pixel
+ * i = h*W + w: i % W = w).  The per-pixel offsets off[i] of the sensor model are not part of a ray's start. */
+int gvom_process_pointcloud_origins(gvom_t *h, const void *xyz, int on_device, int64_t n, int64_t row_stride_bytes, int dtype,
+                                    const double *origins /* host, K*3 */, int32_t K, const uint16_t *index /* may be NULL */,
+                                    const double ego[3], const double *transform_4x4);
+int gvom_process_range_image_origins(gvom_t *h, const void *raw, int on_device, int range_dtype, int64_t row_stride_bytes,
+                                     const double *col_poses /* host, W*12, required */, int cloud_dtype,
+                                     const double ego[3], const double *transform_4x4);
+
 /* --- Gvom.combine_maps (gvom.py:177-354) --------------------------------------------------
  * Caller-allocated xy_size*xy_size outputs (any of them may be NULL to skip its copy).
  * Returns GVOM_OK or GVOM_EMPTY_BUFFER. */
@@ -537,6 +573,7 @@ int gvom_host_timing(gvom_t *h, double us[8]);
  * "occupancy_clear" (A/B of k_occupancy's dead tile columns: 0, default, the kernel writes every byte of the grid; 1 the grid is
  * cleared with hipMemsetAsync and only tile columns with a live tile are written.  Same grid either way).
  * "range_image" (read-only, gvom_get_tuning): 1 when a sensor model is set (gvom_sensor_model_set), else 0.
+ * "multi_origin" / "multi_origin_ran" (read-only, gvom_get_tuning): see "multi-origin scans" above.
  * (Test hooks are not part of this library: include/gvom_hip_test.h, lib/libgvom_hip_test.so.) */
 int gvom_set_tuning(gvom_t *h, const char *name, int value);
 /* The value the LAST scan ran with ("segs", "period", "ep_row", "prio", "interleave": what automatic resolved to).

@@ -77,6 +77,7 @@ struct Fused {
 //   voxel cloud      256-byte header (the uint64 row counter k_voxel_cloud adds to), then cap x 8 and cap x 3 floats, each part
 //                    256-byte aligned
 //   height clouds    xy*xy x 7 / x 3 floats
+//   clearance        xy*xy floats (metres), then xy*xy int32 (squared cells) at the next 256-byte boundary, both [y][x]
 struct DevSet {
     char *mem = nullptr;
     size_t bytes = 0;
@@ -308,6 +309,11 @@ struct gvom_handle {
     size_t mo_pin_bytes = 0;
     int last_multi_origin = 0;                          // the last scan ran the per-lane-origin trace (gvom_get_tuning "multi_origin_ran")
     double ri_scale = 0.0, ri_min = 0.0, ri_max = 0.0;
+    // CLEARANCE (gvom_clearance): the row pass's uint16 distances and the staging copy of a caller's host maps, each allocated
+    // by the first call that needs it; cl_allocs counts every device allocation the entry point has made on this handle
+    // (these two and its product sets: gvom_get_tuning "clearance_allocations")
+    Buf cl_g, cl_stage;
+    int cl_allocs = 0;
 };
 
 namespace {
@@ -1794,7 +1800,7 @@ VIS void gvom_destroy(gvom_t *h)
     if (h->x_host) hipHostFree(h->x_host);
     for (auto &s : h->slots) { hipFree(s.state); hipFree(s.code16); hipFree(s.tags); fb(s.crows); fb(s.metrics); fb(s.base); fb(s.rowvox); }
     for (auto &f : h->fused) { hipFree(f.state); hipFree(f.tags); fb(f.rows); fb(f.metrics); }
-    fb(h->in_pts); fb(h->ri_model); fb(h->ri_raw); fb(h->ri_poses); if (h->ri_poses_pin) hipHostFree(h->ri_poses_pin); fb(h->mo_dev); if (h->mo_pin) hipHostFree(h->mo_pin); fb(h->world_pts[0]); fb(h->world_pts[1]); fb(h->flink[0]); fb(h->flink[1]); fb(h->tl); fb(h->dir_keys); fb(h->dir_perm); hipFree(h->dir_hist);
+    fb(h->in_pts); fb(h->cl_g); fb(h->cl_stage); fb(h->ri_model); fb(h->ri_raw); fb(h->ri_poses); if (h->ri_poses_pin) hipHostFree(h->ri_poses_pin); fb(h->mo_dev); if (h->mo_pin) hipHostFree(h->mo_pin); fb(h->world_pts[0]); fb(h->world_pts[1]); fb(h->flink[0]); fb(h->flink[1]); fb(h->tl); fb(h->dir_keys); fb(h->dir_perm); hipFree(h->dir_hist);
     hipFree(h->counters); if (h->counters_host) hipHostFree(h->counters_host);
     hipFree(h->descs_dev); if (h->descs_host) hipHostFree(h->descs_host);
     hipFree(h->blockcounts); hipFree(h->blockcounts2); hipFree(h->hmaps2);
@@ -2346,6 +2352,7 @@ static size_t set_bytes(int kind, int xy, int zs, int64_t cap)
     case GVOM_PRODUCT_VOXEL_CLOUD: return 256 + align256((size_t)cap * 32) + align256((size_t)cap * 12);
     case GVOM_PRODUCT_HEIGHT_CLOUD: return n2 * 28;
     case GVOM_PRODUCT_INFERRED_HEIGHT_CLOUD: return n2 * 12;
+    case GVOM_PRODUCT_CLEARANCE: return align256(n2 * 4) + n2 * 4;
     }
     return 0;
 }
@@ -2379,6 +2386,12 @@ static bool set_part(const DevSet *s, int part, SetPart *d)
         break;
     case GVOM_PRODUCT_HEIGHT_CLOUD: if (part != 0) return false; rows(s->mem, n2, 7); break;
     case GVOM_PRODUCT_INFERRED_HEIGHT_CLOUD: if (part != 0) return false; rows(s->mem, n2, 3); break;
+    case GVOM_PRODUCT_CLEARANCE:                           // [x, y] indexing, column-major, like a device map
+        if (part < 0 || part > 1) return false;
+        d->ptr = s->mem + (part ? align256((size_t)n2 * 4) : 0);
+        d->shape[0] = d->shape[1] = xy; d->strides[0] = 1; d->strides[1] = xy;
+        if (part) d->code = kDLInt;
+        break;
     default: return false;
     }
     d->bytes = (size_t)(d->shape[0] * d->shape[1] * d->shape[2]) * (d->bits / 8);
@@ -2642,6 +2655,7 @@ VIS int gvom_device_product(gvom_t *h, int kind, int64_t max_rows, int64_t *prod
     if (!h || !product_id) return GVOM_ERR_INVALID;
     std::lock_guard<std::mutex> lk(h->mu);
     *product_id = -1;
+    if (kind == GVOM_PRODUCT_CLEARANCE) { h->err = "gvom_device_product: a clearance product is made by gvom_clearance"; return GVOM_ERR_INVALID; }
     if (kind < 1 || kind > GVOM_N_PRODUCT_KINDS) { h->err = "gvom_device_product: unknown product kind"; return GVOM_ERR_INVALID; }
     if (h->sharded) { h->err = "gvom_device_product: sharded handles are not supported"; return GVOM_ERR_INVALID; }
     if (kind == GVOM_PRODUCT_VOXEL_CLOUD) stats_demand(h);                  // a read of the statistics, like gvom_debug_voxel_map
@@ -2737,6 +2751,75 @@ VIS int gvom_device_product_copy(gvom_t *h, int64_t product_id, int part, void *
     if (!h || !host_out) return GVOM_ERR_INVALID;
     std::lock_guard<std::mutex> lk(h->mu);
     return set_copy(h, false, product_id, part, host_out);
+}
+
+// ---- obstacle clearance (gvom_clearance) ---------------------------------------------------------------------------------------
+// The distance from every cell to the nearest hard obstacle of a positive / negative map pair, as a product of kind
+// GVOM_PRODUCT_CLEARANCE: two kernels (gvom_clearance.hip) on the handle's stream, behind the k_map2d that wrote the map set
+// they read -- and in front of whatever recycles that set later, which runs on the same stream.  Enqueues and returns.
+VIS int gvom_clearance(gvom_t *h, int64_t map_set_id, const int32_t *positive, const int32_t *negative, int on_device,
+                       double density_threshold, int32_t max_cells2, int flags, int64_t *product_id)
+{
+    if (!h || !product_id) return GVOM_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(h->mu);
+    *product_id = -1;
+    if (h->sharded) { h->err = "gvom_clearance: sharded handles are not supported"; return GVOM_ERR_INVALID; }
+    if (flags & ~GVOM_CLEARANCE_NO_NEGATIVE) { h->err = "gvom_clearance: unknown flag bits"; return GVOM_ERR_INVALID; }
+    if (density_threshold != density_threshold) { h->err = "gvom_clearance: the density threshold is not a number"; return GVOM_ERR_INVALID; }
+    if (map_set_id >= 0 && (positive || negative)) { h->err = "gvom_clearance: give a map set id or map pointers, not both"; return GVOM_ERR_INVALID; }
+    if (map_set_id < 0 && !positive) { h->err = "gvom_clearance: give a map set id or a positive map"; return GVOM_ERR_INVALID; }
+    const int xy = h->prm.xy_size;
+    if (xy > GVOM_CLEARANCE_MAX_XY) { h->err = "gvom_clearance: maps of more than 4096 cells a side are not supported"; return GVOM_ERR_CAPACITY; }
+    const size_t n2 = (size_t)xy * xy;
+    const int32_t *pos = positive, *neg = negative;
+    if (map_set_id >= 0) {
+        DevSet *m = find_set(h->dsets, map_set_id);
+        if (!m) { h->err = "unknown or stale device map set id"; return GVOM_ERR_INVALID; }
+        SetPart d;
+        set_part(m, 0, &d); pos = (const int32_t *)d.ptr;
+        set_part(m, 1, &d); neg = (const int32_t *)d.ptr;
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    const int kind = GVOM_PRODUCT_CLEARANCE;
+    DevSet *set = set_recycle(h->psets, kind, set_bytes(kind, xy, 0, 0));
+    if (!set) {
+        int n = 0;
+        for (DevSet *s : h->psets) n += s->kind == kind;
+        if (n >= GVOM_MAX_PRODUCT_SETS) {
+            h->err = "gvom_clearance: all 4 device product sets of this kind are exported; release some (gvom_device_product_release, or drop the tensors)";
+            return GVOM_ERR_CAPACITY;
+        }
+        const int rc0 = set_new(h, h->psets, kind, set_bytes(kind, xy, 0, 0), &set);
+        if (rc0) return rc0;
+        ++h->cl_allocs;
+    }
+    int rc;
+    if (!h->cl_g.p) {
+        if ((rc = ensure(h, h->cl_g, gvom_clearance_scratch_bytes(xy)))) return rc;
+        ++h->cl_allocs;
+    }
+    HIPCHK(h, join_second_stream(h));
+    if (map_set_id < 0 && !on_device) {                                     // host maps: staged, and up before the call returns
+        if (!h->cl_stage.p) {
+            if ((rc = ensure(h, h->cl_stage, 2 * n2 * 4))) return rc;
+            ++h->cl_allocs;
+        }
+        int32_t *st = (int32_t *)h->cl_stage.p;
+        HIPCHK(h, hipMemcpyAsync(st, positive, n2 * 4, hipMemcpyHostToDevice, h->stream));
+        if (negative) HIPCHK(h, hipMemcpyAsync(st + n2, negative, n2 * 4, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        pos = st; neg = negative ? st + n2 : nullptr;
+    }
+    if (flags & GVOM_CLEARANCE_NO_NEGATIVE) neg = nullptr;
+    if ((rc = set_wait_releases(h, set))) return rc;
+    SetPart d0, d1;
+    set_part(set, 0, &d0); set_part(set, 1, &d1);
+    HIPCHK(h, gvom_launch_clearance(h->stream, xy, h->prm.xy_resolution, pos, neg, density_threshold, max_cells2,
+                                    (uint16_t *)h->cl_g.p, (float *)d0.ptr, (int32_t *)d1.ptr));
+    HIPCHK(h, hipEventRecord(set->ready, h->stream));
+    set->id = ++h->pset_seq;
+    *product_id = set->id;
+    return GVOM_OK;
 }
 
 // ---- split combine for the sharded layer (g-vom_amd/gvom_sharded.py) ---------------------
@@ -3188,6 +3271,7 @@ VIS int gvom_get_tuning(gvom_t *h, const char *name, int *value)
     if (!strcmp(name, "eager_dropped")) { *value = h->eager_stat[1]; return GVOM_OK; }
     if (!strcmp(name, "fuse_kernel")) { *value = h->last_fuse; return GVOM_OK; }
     if (!strcmp(name, "device_map_sets")) { *value = (int)h->dsets.size(); return GVOM_OK; }             // read-only: allocated device map sets                  // read-only, GVOM_ROUTE_*
+    if (!strcmp(name, "clearance_allocations")) { *value = h->cl_allocs; return GVOM_OK; }              // read-only: device allocations gvom_clearance has made
     if (!strcmp(name, "device_product_sets")) { *value = (int)h->psets.size(); return GVOM_OK; }        // read-only: allocated device product sets (every kind)
     if (!strcmp(name, "occupancy_clear")) { *value = h->tune_occ_clear; return GVOM_OK; }
     if (!strcmp(name, "multi_origin")) { *value = 1; return GVOM_OK; }                                  // read-only: the library has the multi-origin entry points

@@ -267,6 +267,14 @@ hipError_t gvom_launch_read_dense(hipStream_t s, int xy, int zs, const int om[3]
 // with hipMemsetAsync and only tile columns with a live tile are written (otherwise the kernel writes every byte itself)
 hipError_t gvom_launch_occupancy(hipStream_t s, const OccParams &P, const int32_t *fstate, const uint32_t *ftags, uint8_t *out,
                                  bool clear_first);
+// obstacle clearance (gvom_clearance.hip): pos / neg (neg may be nullptr) are [y][x] int32 maps of xy x xy cells; a cell is an
+// obstacle iff (double)pos > thr or neg > 0.  out_d2[y][x] = exact squared distance in cells to the nearest obstacle (INT32_MAX
+// where there is none, or beyond max_cells2 when that is > 0), out_dist[y][x] = (float)(sqrt((double)d2) * res), +inf there.
+// g: gvom_clearance_scratch_bytes(xy) of scratch (the row pass's uint16 distances).  xy <= GVOM_CLEARANCE_MAX_XY.
+#define GVOM_CLEARANCE_MAX_XY 4096
+size_t gvom_clearance_scratch_bytes(int xy);
+hipError_t gvom_launch_clearance(hipStream_t s, int xy, double res, const int32_t *pos, const int32_t *neg, double thr,
+                                 int32_t max_cells2, uint16_t *g, float *out_dist, int32_t *out_d2);
 // storage order [sy][sx] -> reference order [x][y] (window coordinates)
 hipError_t gvom_launch_unwrap_f64(hipStream_t s, int xy, int om0, int om1, const double *in, int in_stride, double *out_xy);
 hipError_t gvom_launch_posdens(hipStream_t s, const Map2dParams &P, const int32_t *fstate,

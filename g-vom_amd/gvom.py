@@ -156,6 +156,7 @@ ABI = [
     ("gvom_device_product_release", _I, [_P, _I64, _P]),
     ("gvom_device_product_dlpack", _I, [_P, _I64, _I, _P, _I, ctypes.POINTER(_P)]),
     ("gvom_device_product_copy", _I, [_P, _I64, _I, _P]),
+    ("gvom_clearance", _I, [_P, _I64, _P, _P, _I, ctypes.c_double, ctypes.c_int32, _I, ctypes.POINTER(_I64)]),
     ("gvom_set_profiling", _I, [_P, _I]),
     ("gvom_host_timing", _I, [_P, ctypes.POINTER(ctypes.c_double * 8)]),
     ("gvom_set_tuning", _I, [_P, ctypes.c_char_p, _I]),
@@ -450,6 +451,14 @@ class DeviceMaps(object):
             return DeviceMap(self, DEVICE_MAP_NAMES.index(name))
         raise AttributeError(name)
 
+    def clearance(self, density_threshold=50, include_negative=True, max_distance=None):
+        """Distance of every cell to the nearest hard obstacle of this set's positive / negative maps -- a cell is one iff
+        positive > density_threshold or (include_negative and) negative > 0, the non-zero cells of the node's hard-obstacle grid
+        -- as a DeviceClearance, computed on the GPU behind the combine that wrote the set; no host wait.  max_distance (metres):
+        cells further than that from every obstacle read +inf / CLEARANCE_FAR, and the transform looks no further."""
+        g = self._owner
+        return g._clearance(self.set_id, None, None, 0, density_threshold, include_negative, max_distance)
+
     def release(self):
         if self.__dict__.get("_held"):
             self._held = False
@@ -476,6 +485,34 @@ PRODUCT_OCCUPANCY, PRODUCT_VOXEL_CLOUD, PRODUCT_HEIGHT_CLOUD, PRODUCT_INFERRED_H
 _PRODUCT_DTYPES = {(PRODUCT_OCCUPANCY, 0): np.uint8, (PRODUCT_VOXEL_CLOUD, 0): np.float32, (PRODUCT_VOXEL_CLOUD, 1): np.float32,
                    (PRODUCT_VOXEL_CLOUD, 2): np.int64, (PRODUCT_HEIGHT_CLOUD, 0): np.float32,
                    (PRODUCT_INFERRED_HEIGHT_CLOUD, 0): np.float32}
+PRODUCT_CLEARANCE = 5                     # GVOM_PRODUCT_CLEARANCE: made by gvom_clearance, not by gvom_device_product
+CLEARANCE_FAR = 2147483647                # GVOM_CLEARANCE_FAR: squared_cells where no obstacle is in reach
+_CLEARANCE_NO_NEGATIVE = 1                # GVOM_CLEARANCE_NO_NEGATIVE
+_PRODUCT_DTYPES[(PRODUCT_CLEARANCE, 0)] = np.float32
+_PRODUCT_DTYPES[(PRODUCT_CLEARANCE, 1)] = np.int32
+
+
+def _clearance_cap(max_distance, xy_resolution):
+    """max_distance in metres -> max_cells2 of gvom_clearance: floor((max_distance / xy_resolution)^2); 0 (unbounded) for None,
+    +inf and whatever does not fit int32.  ValueError for NaN, negative values and less than one cell."""
+    if max_distance is None:
+        return 0
+    d = float(max_distance)
+    if d != d or d < 0:
+        raise ValueError("max_distance must be None or a distance >= 0 in metres, got %r" % (max_distance,))
+    if d == float("inf"):
+        return 0
+    c = math.floor((d / float(xy_resolution)) ** 2)
+    if c < 1:                                   # (the C ABI reads max_cells2 <= 0 as unbounded)
+        raise ValueError("max_distance must be at least one cell (%r m), got %r" % (xy_resolution, max_distance))
+    return 0 if c >= CLEARANCE_FAR else int(c)
+
+
+def _clearance_threshold(density_threshold):
+    t = float(density_threshold)
+    if t != t:
+        raise ValueError("density_threshold must be a number, got %r" % (density_threshold,))
+    return t
 
 
 class _ProductHold(object):
@@ -554,7 +591,8 @@ class DeviceArray(object):
     def copy_to_host(self):
         """numpy array of `shape` and `dtype` (waits for the kernel that writes the product)."""
         g = self._hold.owner
-        out = np.empty(self.shape, self.dtype)
+        fortran = len(self.shape) == 2 and self.strides == (1, self.shape[0]) and self.shape[0] > 1     # (a clearance map: [x, y], x fastest)
+        out = np.empty(self.shape, self.dtype, order="F" if fortran else "C")
         g._check(g._lib.gvom_device_product_copy(g._h, self.product_id, self._part, ctypes.c_void_p(out.ctypes.data)))
         return out
 
@@ -590,6 +628,31 @@ class DeviceVoxelCloud(object):
     def eigenvalues_to_host(self):
         n = min(int(self.count.copy_to_host()[0]), self.rows.shape[0])
         return self.eigenvalues.copy_to_host()[:n]
+
+    def release(self):
+        self._hold.release()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.release()
+        return False
+
+
+class DeviceClearance(object):
+    """The result of DeviceMaps.clearance() / Gvom.clearance_of() / clearance_of_device(): `.distance` float32 [xy, xy], metres to
+    the nearest hard obstacle (+inf where none is in reach), and `.squared_cells` int32 [xy, xy], the exact squared distance in
+    cells (CLEARANCE_FAR there) -- two DeviceArrays of one product, [x, y]-indexed with strides (1, xy) like a DeviceMap.
+    copy_to_host() returns (distance, squared_cells) as Fortran-ordered numpy [x, y]."""
+
+    def __init__(self, hold):
+        self._hold = hold
+        self.product_id = hold.product_id
+        self.distance, self.squared_cells = DeviceArray(hold, 0), DeviceArray(hold, 1)
+
+    def copy_to_host(self):
+        return self.distance.copy_to_host(), self.squared_cells.copy_to_host()
 
     def release(self):
         self._hold.release()
@@ -1212,6 +1275,39 @@ class Gvom(object):
             print("No data")
             return None
         return DeviceArray(hold)
+
+    # ---- obstacle clearance (an extension; include/gvom_hip.h "obstacle clearance") ----
+    def _clearance(self, set_id, pos_ptr, neg_ptr, on_device, density_threshold, include_negative, max_distance):
+        thr = _clearance_threshold(density_threshold)
+        cap = _clearance_cap(max_distance, self.xy_resolution)
+        pid = ctypes.c_int64(-1)
+        self._check(self._lib.gvom_clearance(self._h, int(set_id), pos_ptr, neg_ptr, int(on_device), thr, cap,
+                                             0 if include_negative else _CLEARANCE_NO_NEGATIVE, ctypes.byref(pid)))
+        return DeviceClearance(_ProductHold(self, PRODUCT_CLEARANCE, int(pid.value)))
+
+    def clearance_of(self, positive, negative=None, density_threshold=50, include_negative=True, max_distance=None):
+        """DeviceMaps.clearance() of maps of the caller's: numpy [x, y] arrays of shape (xy_size, xy_size) in any memory order
+        (negative may be None).  Needs no scan and no combine.  A convenience route: the maps are copied to the device."""
+        maps = []
+        for name, m in (("positive", positive), ("negative", negative)):
+            if m is None:
+                if name == "positive":
+                    raise ValueError("positive must be an array")
+                maps.append(None)
+                continue
+            a = np.asarray(m)
+            if a.shape != (self.xy_size, self.xy_size):
+                raise ValueError("%s must have shape (%d, %d), got %r" % (name, self.xy_size, self.xy_size, a.shape))
+            maps.append(np.asfortranarray(a, dtype=np.int32))           # x fastest
+        return self._clearance(-1, _ptr(maps[0]), _ptr(maps[1]), 0, density_threshold, include_negative, max_distance)
+
+    def clearance_of_device(self, positive_ptr, negative_ptr=None, density_threshold=50, include_negative=True, max_distance=None):
+        """The same for maps in device memory (raw device addresses of xy_size*xy_size int32, cell (x, y) at [y*xy_size + x]; the
+        data must be ready when the call is made).  negative_ptr may be None."""
+        if not positive_ptr:
+            raise ValueError("positive_ptr must be a device address")
+        return self._clearance(-1, ctypes.c_void_p(int(positive_ptr)), ctypes.c_void_p(int(negative_ptr)) if negative_ptr else None, 1,
+                               density_threshold, include_negative, max_distance)
 
     def make_debug_voxel_map(self):
         """float32[Cc, 8] rows {x, y, z, hit/total, hit, l0-l1, l1-l2, l2} (reference gvom.py:363-378) while the mapper

@@ -340,6 +340,44 @@ int gvom_device_product_release(gvom_t *h, int64_t product_id, void *consumer_st
 int gvom_device_product_dlpack(gvom_t *h, int64_t product_id, int part, void *consumer_stream, int versioned, void **managed);
 int gvom_device_product_copy(gvom_t *h, int64_t product_id, int part, void *host_out);
 
+/* --- obstacle clearance (an extension: what a planner asks the hard-obstacle map first -- how far is each cell from an obstacle) --
+ * gvom_clearance computes, on the GPU, the exact Euclidean distance transform of the node's hard-obstacle grid (gvom_ros.py:141-142)
+ * and leaves it in device memory as a product (kind GVOM_PRODUCT_CLEARANCE) that gvom_device_product_export / _release / _dlpack /
+ * _copy handle like the others.  Costmap inflation is `distance < robot_radius` on the result.
+ *
+ * DEFINITION.  positive, negative: int32 maps of xy_size * xy_size cells.  A cell is an OBSTACLE iff (double)positive >
+ * density_threshold, or negative > 0 (not with GVOM_CLEARANCE_NO_NEGATIVE in flags; not when there is no negative map): the
+ * non-zero cells of the hard-obstacle grid.  Cells outside the window are not obstacles.
+ *     d2[x, y]       = min over obstacle cells (ox, oy) of (x - ox)^2 + (y - oy)^2                  int32, exact
+ *                      GVOM_CLEARANCE_FAR where there is no obstacle, or (max_cells2 > 0) where the minimum exceeds max_cells2
+ *     distance[x, y] = (float)(sqrt((double)d2) * xy_resolution)     one float64 square root, one float64 multiply, one rounding
+ *                      +infinity where d2 is GVOM_CLEARANCE_FAR
+ * part 0 = distance, float32 metres; part 1 = d2, int32 squared cells; both [x, y]-indexed with element strides {1, xy_size}
+ * (cell (x, y) at [y*xy_size + x]), like a device map.
+ *
+ * INPUT.  map_set_id >= 0: maps 0 and 1 of that live device map set (gvom_combine_maps_device); positive and negative must be
+ * NULL.  The kernels run on the handle's stream behind the combine that wrote the set, and a later combine that recycles the set
+ * runs behind them: the caller needs no export of the set for the duration of the call.  map_set_id < 0: the caller's arrays,
+ * xy_size*xy_size int32 each with x fastest (cell (x, y) at [y*xy_size + x]); negative may be NULL.  on_device != 0: device
+ * addresses, read in place (the data must be ready when the call is made); on_device == 0: host memory, copied through a staging
+ * buffer of the handle before the call returns (a convenience and test route).  No scan or combine is needed on this route.
+ * The call ENQUEUES and returns (no host wait on the device routes); after the first call on a handle it allocates nothing unless
+ * every clearance set is exported (gvom_get_tuning "clearance_allocations": device allocations the entry point has made so far).
+ * Products of this kind live in the product-set pool ("device_product_sets"): at most GVOM_MAX_PRODUCT_SETS, GVOM_ERR_CAPACITY
+ * beyond; an unexported one goes back to the pool with the next gvom_clearance call.  gvom_device_product(GVOM_PRODUCT_CLEARANCE)
+ * is GVOM_ERR_INVALID (this call makes them).
+ * GVOM_ERR_INVALID: a sharded handle; a set id AND pointers, or neither; a stale or unknown set id; a NaN threshold; unknown flag
+ * bits.  GVOM_ERR_CAPACITY: xy_size > 4096 (2 * (xy_size - 1)^2, the largest d2, fits int32 far beyond that; the kernels' row
+ * masks and LDS strips are sized for 4096).
+ * NOT PROVIDED: the nearest obstacle's indices or a gradient; unknown cells as obstacles; sharded handles; output into pinned
+ * host memory.  k_map2d is unchanged. */
+#define GVOM_PRODUCT_CLEARANCE 5      /* part 0 float32 [xy, xy] metres, part 1 int32 [xy, xy] squared cells;
+                                         both [x, y]-indexed with strides (1, xy), like a device map */
+#define GVOM_CLEARANCE_FAR 2147483647
+#define GVOM_CLEARANCE_NO_NEGATIVE 1  /* flags */
+int gvom_clearance(gvom_t *h, int64_t map_set_id, const int32_t *positive, const int32_t *negative, int on_device,
+                   double density_threshold, int32_t max_cells2, int flags, int64_t *product_id);
+
 /* --- one map sharded over the GPUs of a node (one rank = one process = one GPU) -------------------
  * No counterpart in the reference (it has no multi-GPU path); semantics = SURVEY 8(e):
  * the rays are data-parallel, the per-voxel accumulators (hit / total: int32 sum, min-height: f32 min)
@@ -574,6 +612,7 @@ int gvom_host_timing(gvom_t *h, double us[8]);
  * cleared with hipMemsetAsync and only tile columns with a live tile are written.  Same grid either way).
  * "range_image" (read-only, gvom_get_tuning): 1 when a sensor model is set (gvom_sensor_model_set), else 0.
  * "multi_origin" / "multi_origin_ran" (read-only, gvom_get_tuning): see "multi-origin scans" above.
+ * "clearance_allocations" (read-only, gvom_get_tuning): see "obstacle clearance" above.
  * (Test hooks are not part of this library: include/gvom_hip_test.h, lib/libgvom_hip_test.so.) */
 int gvom_set_tuning(gvom_t *h, const char *name, int value);
 /* The value the LAST scan ran with ("segs", "period", "ep_row", "prio", "interleave": what automatic resolved to).

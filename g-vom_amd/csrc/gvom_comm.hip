@@ -13,7 +13,7 @@
 //     Three rules keep the HSA runtime's inter-process memory honest (each found as a silently different map or a refused
 //     call under tests/shard_procs.py's churn hook): an allocation is exported ONCE and a mapping
 //     opened ONCE (both kept until the communicator goes), exported regions are whole multiples of 2 MiB, and a region a
-//     peer may have mapped is never given back to the allocator while the process lives (gvom_capi.hip);
+//     peer may have mapped is never given back to the allocator while the process lives (gvom_handle.hip);
 //   * device data, third transport (GVOM_TRANSPORT_LOOPBACK): RCCL LOOPBACK -- the ranks are THREADS of one process that share
 //     one GPU (RCCL refuses two ranks of ONE communicator on one device), each with a 1-rank communicator of its own; what
 //     the RCCL transport moves with ncclSend on the sender and ncclRecv on the receiver, the RECEIVER moves with
@@ -59,7 +59,7 @@
 #define GVOM_COMM_MAX_RANKS 64
 #define GVOM_COMM_MAX_VALUES 208          // int64 values per rank and exchange (statistics handles exchange 3 * ranks + 3)
 static_assert(GVOM_COMM_MAX_VALUES >= 3 * GVOM_COMM_MAX_RANKS + 4, "a communicator of GVOM_COMM_MAX_RANKS ranks must be able to exchange its counts");
-extern "C" int gvom_shard_renew_region(gvom_t *h, int which);    // (gvom_capi.hip; same library)
+extern "C" int gvom_shard_renew_region(gvom_t *h, int which);    // (gvom_handle.hip; same library)
 
 namespace {
 
@@ -468,7 +468,7 @@ int peer_publish(gvom_comm *c, gvom_t *h, int kind, const int64_t *counts, bool 
             for (PeerOwn &k : g_own) if (k.base == base && k.size == size && k.generation == gen) { own = k; have = true; break; }
         }
         if (!have) {
-            (void)gvom_set_tuning(h, "exported", 1);                // (its regions go to the pool instead of back to the allocator: gvom_capi.hip)
+            (void)gvom_set_tuning(h, "exported", 1);                // (its regions go to the pool instead of back to the allocator: gvom_handle.hip)
             hipError_t ge = hipSuccess;
             const bool injected = g_fault.export_n > 0 && (g_fault.rank < 0 || g_fault.rank == c->rank) && ++g_fault.exports == g_fault.export_n;
             for (int attempt = 0; attempt < 5; ++attempt) {            // (a refusal is asked again a few times before it counts)

@@ -1231,7 +1231,7 @@ hipError_t gvom_launch_publish_seq(hipStream_t s, unsigned long long *host_flag,
     return hipGetLastError();
 }
 
-// epoch renumbering (gvom_capi.hip renumber_epochs): live tiles get the map's new epoch, all others 0
+// epoch renumbering (gvom_handle.hip renumber_epochs): live tiles get the map's new epoch, all others 0
 __global__ void k_retag(uint32_t *tags, size_t n, uint32_t old_epoch, uint32_t new_epoch)
 {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)

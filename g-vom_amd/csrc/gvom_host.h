@@ -1,0 +1,374 @@
+// gvom_host.h -- private to the host units of libgvom_hip.so (gvom_handle / gvom_capi (scans) / gvom_combine / gvom_export / gvom_debug .hip):
+// the handle and what it is made of, and the functions that cross those units' boundaries (namespace gvom_host; -fvisibility=hidden
+// keeps them out of the dynamic symbol table).  Not part of the public interface (include/gvom_hip.h is); no kernel unit includes it.
+#pragma once
+#include "gvom_internal.h"
+#include "gvom_ingest.h"
+#include "../../include/gvom_hip.h"
+
+#include <math.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include <time.h>
+#include <unistd.h>
+#include <immintrin.h>
+#include <algorithm>
+#include <atomic>
+#include <mutex>
+#include <string>
+#include <vector>
+
+#define VIS __attribute__((visibility("default")))
+
+namespace gvom_host {
+struct Buf {                                   // grow-only device buffer
+    void *p = nullptr;
+    size_t bytes = 0;
+    uint64_t gen = 0;                          // changes with every (re-)allocation (process-wide unique: gvom_region_generation)
+};
+
+struct Slot {                                  // one scan in sparse form
+    int32_t *state = nullptr;                  // [V] storage order
+    uint16_t *code16 = nullptr;                // [V] 16-bit codes of the same voxels (xy % 4 == 0 grids), read by k_fuse4
+    uint32_t *tags = nullptr;                  // [ntiles] tile epochs (live iff == epoch)
+    uint32_t epoch = 0;
+    Buf crows;                                 // compact rows, uint4 each: {hit, total, min-height bits, 0}
+    Buf metrics, base, rowvox;                 // optional statistics: double[rows][10] x2 (metrics; own-voxel moments), row -> voxel
+    int64_t origin[3] = {0, 0, 0};
+    int64_t count = 0;
+    bool filled = false;
+    bool has_code16 = false;                   // the last encode wrote the 16-bit codes (k_fuse4 may read this slot)
+    bool has_metrics = false;                  // the scan computed its per-voxel statistics (metrics / base / rowvox are this scan's)
+    bool stats_valid = false;
+    gvom_scan_stats stats = {0, 0, 0, 0};
+};
+
+struct Fused {
+    int32_t *state = nullptr;
+    uint32_t *tags = nullptr;
+    uint32_t epoch = 0;
+    Buf rows;                                  // compact rows, uint4 each (as a slot's)
+    Buf metrics;                               // optional statistics: float[rows][10]
+    int64_t origin[3] = {0, 0, 0};
+    int64_t count = 0;                         // rows on THIS rank
+    bool valid = false;
+    bool has_metrics = false;                  // k_fuse_stats merged the statistics of this map (every source had its own)
+};
+
+// DEVICE MAP SETS (gvom_combine_maps_device): one device allocation per set holding the nine maps of one combine, [y][x] order,
+// each map at a 256-byte aligned offset: the six f64 maps (3 roughness, 4 height, 5 inferred height, 6 / 7 x / y slope,
+// 8 guessed delta) at k * S doubles, then the three i32 maps (0 positive, 1 negative, 2 visibility) behind them at k * S
+// ints, S = dev_map_stride(xy): 60 bytes per cell.  A set is handed out by EXPORTS (the consumer stream waits on `ready`) and
+// taken back by RELEASES (an event recorded on the consumer stream); the combine that reuses the set first makes the handle's
+// stream wait on every release event.  A set with live exports outlives the handle (orphan) and is freed at its last release.
+// PRODUCT SETS (gvom_device_product) are the same thing with another KIND of contents: one allocation with a kind and a shape
+// (set_part() below is the only place that knows the layouts), the same ready event, export count, release events and
+// orphaning.  kind 0 = the nine maps; GVOM_PRODUCT_* otherwise:
+//   occupancy        V bytes, out[x][y][z]
+//   voxel cloud      256-byte header (the uint64 row counter k_voxel_cloud adds to), then cap x 8 and cap x 3 floats, each part
+//                    256-byte aligned
+//   height clouds    xy*xy x 7 / x 3 floats
+//   clearance        xy*xy floats (metres), then xy*xy int32 (squared cells) at the next 256-byte boundary, both [y][x]
+struct DevSet {
+    char *mem = nullptr;
+    size_t bytes = 0;
+    int device = 0, xy = 0;
+    int kind = 0, zs = 0;                      // GVOM_PRODUCT_* (0: a map set); z_size (occupancy)
+    int64_t cap = 0;                           // voxel cloud: rows the allocation holds
+    hipEvent_t ready = nullptr;                // recorded on the handle's stream behind the set's k_map2d
+    int64_t id = -1;                           // sequence number of the combine that wrote it; -1: free
+    int exports = 0;                           // live exports
+    std::vector<hipStream_t> rel_streams;      // release events since the set was written, one per consumer stream
+    std::vector<hipEvent_t> rel, rel_spare;
+    bool orphan = false;                       // the handle is gone
+};
+#define GVOM_MAX_DEVICE_SETS 8
+#define GVOM_N_PRODUCT_KINDS 4
+// DevSet::exports / rel* / orphan: a DLPack deleter runs on whatever thread frees the consumer's tensor, without the handle
+extern std::mutex g_set_mu;                               // (gvom_export.hip)
+}  // namespace gvom_host
+
+using namespace gvom_host;
+
+struct gvom_handle {
+    gvom_params prm;
+    int device = 0;
+    int rank = 0, world = 1;
+    bool sharded = false;                               // created by gvom_create_sharded: scans / combines go through the split entry points
+    int sy_lo = 0, sy_hi = 0;
+    size_t V = 0, slabV = 0, cells2d = 0, ntiles = 0;
+    int nseg = 1;
+    uint32_t epoch = 0;                                 // last tile epoch handed out
+    hipStream_t stream = nullptr;
+    std::mutex mu;                                      // handle state
+    std::mutex scan_mu;                                 // one scan at a time (held across the wait for k_trace, during which `mu` is free)
+    std::string err;
+
+    uint32_t *hit = nullptr, *total = nullptr, *mh = nullptr;   // dense accumulators (hit, ray passes, min-height), zero between scans
+    size_t acc_elems = 0;
+    int tune_segs = 0, tune_ep_row = -2, tune_period = 0; // gvom_set_tuning (0 / -2: automatic)
+    int tune_prio = -1;                                 // gvom_set_tuning "prio" (-1: automatic)
+    int tune_ilv = 0;                                   // gvom_set_tuning "interleave": sub-clouds per cloud (0: automatic, 1: off)
+    int last_knobs[5] = {0, 0, 0, 0, 1};                // gvom_get_tuning: segs, period, ep_row, prio, interleave of the last scan
+    int64_t last_n = -1;                                // returns of the previous scan
+    uint32_t probe_var_age = 0;                         // scans of changing length since the probe last ran
+    int64_t probe_n = -1; uint32_t probe_age = 0;       // layout probe (k_layout_probe): the length it last looked at, scans since
+    int tune_fuse1 = 0;                                 // gvom_set_tuning "fuse1": 1 = the one-slot fusion through k_fuse4 as well (A/B)
+    int tune_flag_kernel = 0;                           // gvom_set_tuning "flag_kernel": 1 = the combine's completion flag from a kernel of its own (round 3's form)
+    int tune_churn = 0;                                 // test hook: re-allocate the endpoint send region every scan
+    uint64_t alloc_gen = 0;                             // changes whenever a send region of this handle is re-allocated
+    uint64_t handle_gen = 0;                            // this handle's own number (its fixed allocations)
+    bool exported = false;                              // a transport has exported this handle's send regions to other processes
+    bool holds_pooled = false;                          // some region of this handle came out of the process-wide pool (a peer may still have it mapped)
+    std::vector<Buf> retired;                           // outgrown / replaced exported regions (possibly still mapped by peers), with their sizes
+    uint64_t fixed_gen[3] = {0, 0, 0};                  // generations of the fixed exported allocations: send ids, send quads, height-map rows
+    // rank exchange of a sharded map (world > 1): send / receive regions, indexed by peer rank
+    uint32_t *x_send_ids = nullptr, *x_recv_ids = nullptr;     // quad ids: [Q] by owner / [world][myQ] by source
+    void *x_send_pay = nullptr, *x_recv_pay = nullptr;         // 1 KiB per quad, same indexing
+    Buf x_send_eps, x_recv_eps;                                 // endpoints {L, min-height}: [world][ep_cap] / concatenated by source
+    int64_t x_ep_cap = 0;
+    std::vector<int64_t> x_recv_ep_off;                         // receive offsets (endpoints) by source, [world + 1]
+    uint32_t *x_qcnt = nullptr, *x_ecnt = nullptr, *x_spcnt = nullptr;   // device counters, [world * 16] each
+    unsigned long long *x_host = nullptr, *x_host_dev = nullptr;   // pinned, mapped: [3*world + 2]
+    Buf x_send_sp, x_recv_sp;                                   // sharded statistics: returns (3 values each) for / from other ranks
+    std::vector<int64_t> x_recv_sp_off;                         // receive offsets (returns) by source, [world + 1]
+    int pending_dtype = 0;                                      // cloud type of the scan between scan_local and scan_merge
+    size_t x_Q = 0, x_myQ = 0;
+    ScanParams pending_P;                                       // scan parameters between scan_local and scan_merge
+    unsigned resident_blocks = 2048;                    // 256-thread workgroups resident on the device (queried)
+    bool f32_sqrt = false;                              // GVOM_FLAG_CUDA_F32_SQRT
+    std::vector<Slot> slots;                            // buffer_size + 1 (one is staging)
+    std::vector<int> ring;                              // ring position -> slots index
+    int staging = 0;
+    int buffer_index = 0, last_buffer_index = 0;
+    Buf in_pts, world_pts[2];                           // world_pts: the returns as k_trace stored them for k_stats, alternating per scan
+    uint32_t *counters = nullptr;                       // device: [0] scan rows, [2..3] fuse rows (u64)
+    uint32_t *counters_host = nullptr;                  // pinned, device-mapped: kernels publish counts here
+    uint32_t *counters_host_dev = nullptr;              // device view of counters_host
+
+    // pending (uncommitted) scan
+    bool pending = false;
+    bool pending_any = false;
+    int64_t pending_origin[3] = {0, 0, 0};
+    int64_t pending_n = 0;
+
+    Fused fused[2];
+    int cur = 0;                                        // fused[cur] is the latest if valid
+    bool has_combined = false;
+    int64_t combined_cell_count = 0;                    // global count if set by the sharded layer
+    MapDesc *descs_dev = nullptr, *descs_host = nullptr;
+    uint32_t *blockcounts = nullptr;                    // per-workgroup occupied counts of k_fuse
+    int fuse_blocks = 0;
+    int cnt_blocks = 0;                                 // entries of blockcounts the last fusion wrote (k_map2d sums them)
+    // EAGER FUSION (one-slot rings: buffer_size 1, unsharded, no statistics, xy % 16 == 0).  The scan launches k_encfuse
+    // behind k_trace instead of k_encode: the slot is encoded AND fused with the previous map in one pass over the
+    // accumulators, into the spare fused buffer, a spare height buffer and a spare count array -- speculating that the
+    // next call is combine_maps (the reference node's pattern: one combine per scan).  fuse_impl adopts the result (swaps
+    // the spares in) iff nothing has changed since; otherwise it is dropped and the combine runs k_fuse1 over the encoded
+    // slot as before.  Same results either way (tests: eager on / off / mixed call orders).
+    double *hmaps2 = nullptr;                           // spare [sy][3][sx] buffer (k_encfuse's column tails)
+    uint32_t *blockcounts2 = nullptr;
+    bool spec_valid = false;                            // a speculative fusion is waiting to be adopted
+    int spec_nxt = 0, spec_slot = 0, spec_blocks = 0;
+    uint32_t spec_epoch = 0;
+    int64_t spec_origin[3] = {0, 0, 0};
+    // ... with per-voxel statistics: the speculative fusion's statistics half (k_fuse_stats on the statistics stream, behind the
+    // scan's own k_stats / k_stats_gather) is enqueued with the scan too; what it needs of eager_launch's frame is kept here
+    bool spec_has_metrics = false;                      // the speculative fused map will carry merged statistics
+    Buf flink[2];                                       // per fused buffer: link[fused row] = row in the previous map (k_encfuse -> k_fuse_stats)
+    bool fs_reads[2] = {false, false};                  // the pending k_fuse_stats reads fused[i]'s states / tile tags
+    FuseParams spec_FP;
+    FuseDescs spec_KD;
+    // DIRECTIONAL ORDER of unordered clouds (k_dirbin_*, ScanParams::perm): "dirsort" 1 always, -1 never, 0 automatic -- when the
+    // layout probe found no spatial order in the previous cloud of this length (BASELINE c1's 50,000 random points: k_trace 65 -> 16 us)
+    int tune_dirsort = 0;
+    Buf dir_keys, dir_perm;                             // uint16 key / uint32 position -> return, per return
+    uint32_t *dir_hist = nullptr;                       // [3][GVOM_DIRBINS]: two histograms (alternating, zero between uses) + the bins' cursors
+    uint32_t dir_flip = 0;
+    int last_dirsort = 0;                               // gvom_get_tuning "dirsort": the last scan ran in directional order
+    int tune_encfuse = 0;                               // gvom_set_tuning "encfuse": A/B of k_encfuse's shape (low 4 bits: waves per block, bit 4: no XCD pairing)
+    int tune_fastdiv = -1;                              // gvom_set_tuning "fastdiv": 0 = IEEE divides by the resolutions in k_trace, else the verified reciprocal form
+    int fastdiv_ok = 0;                                 // bit 0 / 1: div_by_res() verified for xy_resolution / z_resolution (verify_fastdiv)
+    int tune_eager = -1;                                // gvom_set_tuning "eager": 0 off, 1 always, -1 automatic (off after 3 wasted in a row)
+    int eager_waste = 0;                                // speculations dropped in a row (saturates at 4)
+    int eager_stat[2] = {0, 0};                         // adopted / dropped since creation (gvom_get_tuning "eager_adopted" / "eager_dropped")
+    int last_fuse = 0;                                  // the last fusion's kernel, GVOM_ROUTE_* (gvom_get_tuning "fuse_kernel"; 0: none yet)
+    bool last_scan_spec = false;                        // the last accepted scan went through k_encfuse
+    bool solo_encoded = false;                          // a sharded handle of ONE rank: gvom_shard_scan_local has already encoded the scan (nothing to wait for)
+    bool fresh_scan = false;                            // a scan has been committed and no combine has looked at it yet
+
+    double *hmaps = nullptr;                            // [sy][3][sx]: height | inferred height | positive density
+    double *height = nullptr, *inferred = nullptr;      // = hmaps, hmaps + xy  (row stride hs = 3*xy)
+    int hs = 0;
+    double *slope_x = nullptr, *slope_y = nullptr, *rough = nullptr, *guessed = nullptr;   // [sy][sx]
+    hipStream_t own_stream = nullptr;                   // created by the library
+    // asynchronous combine (gvom_combine_begin / _end): k_map2d runs on a second stream, so the next
+    // scan's k_trace / k_encode (instruction-bound) overlap its PCIe-bound stores
+    hipStream_t stream_b = nullptr;
+    // host clouds go up on a stream of their own when the main stream is busy (the ROS node's two threads: the cloud
+    // callback hands scan k + 1 over while the timer thread's combine k is still running): the copy engine moves the
+    // cloud while k_fuse / k_map2d run, and k_trace waits for it on the device
+    hipStream_t stream_up = nullptr;
+    hipEvent_t ev_up = nullptr;
+    // per-voxel statistics (opt-in) run on a stream of their own: k_stats / k_stats_gather beside the combine's fusion,
+    // k_fuse_stats beside k_map2d's PCIe-bound stores.  ev_enc_s / ev_fz_s: main (or fusion) stream -> statistics
+    // stream; ev_sdone: everything enqueued on the statistics stream so far (the next k_trace rewrites what it reads);
+    // ev_fsdone: the last k_fuse_stats (the next fusion rewrites the fused buffer it reads as "previous")
+    hipStream_t stream_s = nullptr;
+    hipEvent_t ev_enc_s = nullptr, ev_fz_s = nullptr, ev_sdone = nullptr, ev_fsdone = nullptr;
+    // ev_before[k & 1]: the statistics stream's work enqueued BEFORE scan k's own -- all that can still read what scan
+    // k + 1 rewrites (the slot it stages into left the ring at commit k; its buffer of stored returns was scan k - 1's):
+    // scan k + 1 waits for that, not for scan k's statistics, which run beside it
+    hipEvent_t ev_before[2] = {nullptr, nullptr};
+    bool before_valid[2] = {false, false};
+    uint32_t stats_scan = 0;                             // scans with statistics so far (parity selects the buffers above)
+    bool stats_prev_committed = true;                    // a rejected scan leaves its slot as the staging slot: the next scan rewrites it
+    bool s_pending = false, fs_pending = false;          // recorded and not known to have completed
+    hipEvent_t ev_fused = nullptr, ev_mapped = nullptr, ev_done = nullptr;
+    std::mutex combine_mu;                              // one combine call at a time (taken before `mu`)
+    bool pending_combine = false;                       // begun, not ended
+    uint32_t combine_seq = 0;                           // completion flag of the synchronous combine (counters_host + 4)
+    double last_wait_ns[2] = {0.0, 0.0};                // how long the scan / the combine waited last time (wait_published)
+    bool mapped_unjoined = false;                       // ev_mapped recorded; the main stream has not waited on it
+    // a fusion enqueued on the second stream (asynchronous combine, rings of >= 3 filled slots) READS the ring slots
+    // it was given; the main stream must not overwrite one of them (the second scan after the begin does: the
+    // oldest slot becomes the staging slot) nor read the fused map it writes before it has finished
+    hipEvent_t ev_fuse_b = nullptr;
+    bool fuse_b_unjoined = false;                       // ev_fuse_b recorded; the main stream has not waited on it
+    uint64_t fuse_b_slots = 0;                          // bit k: slots[k] is a source of that fusion
+    bool scan_inflight = false;                         // a scan's kernels are enqueued and it is not committed yet (scan_mu held)
+    std::vector<void *> out_bufs;                        // buffers handed out by gvom_output_buffer_alloc (coherent by construction)
+    void *last_checked_out = nullptr;                    // a caller's own output buffer whose flags have been checked
+    void *out_host = nullptr;                           // pinned, device-mapped staging for the 4 outputs
+    char *out_host_dev = nullptr;                       // device view of out_host (zero-copy target)
+    uint32_t scan_seq = 0;                              // sequence number of the {seq,count} flag
+    bool ev_scan = false, ev_fuse = false, ev_map = false;   // which profiling events are recorded
+    bool maps_valid = false;
+
+    double ego[3] = {0, 0, 0};
+    int in_off[3] = {0, 1, 2};                          // element offsets of x, y, z in the cloud being scanned
+    bool in_f32 = false;                                // float32 records widened to a float64 computation (PointCloud2 ingest)
+
+    Buf tl;                                             // diagnostic build: k_trace's timeline of the last scan (GVOM_TRACE_TIMELINE)
+    int tl_grid[2] = {0, 0};
+    double host_ns[8] = {0, 0, 0, 0, 0, 0, 0, 0};       // host-side phase timing (GVOM_HOST_TIMING)
+    long host_calls = 0;
+    bool host_timing = false;
+    bool stats = false;                                 // per-voxel statistics computed by the NEXT scan / merged by the next fusion
+    // ON DEMAND (GVOM_FLAG_STATISTICS_ON_DEMAND): the statistics start ON -- the reference computes them in every scan and
+    // combine (gvom.py:159, 276-284) and its node reads them every tick (gvom_ros.py:171) -- and go OFF when three combines
+    // in a row went by without anybody reading them (gvom_debug_voxel_map*, gvom_read_rows, gvom_gather_metrics); a later read
+    // finds no data and switches them ON again for the scans that follow
+    bool stats_auto = false;
+    int stats_idle = 0;                                 // combines since the statistics were last read
+    bool stats_release = false;                         // they have just been switched off: their buffers go at the end of this combine
+    int acc_pad = 7, sxq = 0;                           // accumulator row pitch (lines) = ceil(xy/4) + acc_pad
+    bool profiling = false;
+    hipEvent_t ev[8] = {nullptr};
+    float stage_ms[GVOM_N_STAGES] = {0, 0, 0, 0, 0};
+    // device map sets (gvom_combine_maps_device)
+    std::vector<DevSet *> dsets;
+    int64_t dset_seq = 0;
+    std::vector<DevSet *> psets;                        // product sets (gvom_device_product), every kind; ids from pset_seq
+    int64_t pset_seq = 0;
+    int tune_occ_clear = 0;                             // gvom_set_tuning "occupancy_clear": 1 = clear the grid, write live tile columns only (A/B)
+    bool count_pending = false;                         // the last combine was a device combine: its fused cell count is read
+    hipEvent_t ev_dcount = nullptr;                     //   from the host-mapped counter once this event (behind its k_map2d) has completed
+    // RANGE IMAGES (gvom_sensor_model_set / gvom_process_range_image): the sensor model in device memory -- [n][3] directions, then
+    // [n][3] offsets, n = ri_H * ri_W -- and the staging buffers of host images and column poses.  k_unproject (gvom_ingest.hip)
+    // turns an image into the cloud in in_pts, which the scan then reads like an uploaded host cloud
+    Buf ri_model, ri_raw, ri_poses;
+    // column poses go through a pinned staging copy: a second PAGEABLE upload per scan is a second staged, blocking copy of the
+    // runtime (m256, 196 KB of poses: +27 us per step); copied here by the calling thread and sent from pinned memory, the
+    // transfer is in flight while the image's own upload runs.  Free again once the scan's k_trace has completed, as in_pts is
+    void *ri_poses_pin = nullptr;
+    size_t ri_poses_pin_bytes = 0;
+    int32_t ri_H = 0, ri_W = 0;                         // 0: no model set
+    // MULTI-ORIGIN scans (gvom_process_pointcloud_origins / gvom_process_range_image_origins): the K x 3 float32 table of ray
+    // origins in voxels, followed (host index) by the uint16 index of every return: ONE region in device memory, one pinned
+    // staging copy the calling thread fills (as ri_poses_pin), one upload per scan, re-used across scans
+    Buf mo_dev;
+    void *mo_pin = nullptr;
+    size_t mo_pin_bytes = 0;
+    int last_multi_origin = 0;                          // the last scan ran the per-lane-origin trace (gvom_get_tuning "multi_origin_ran")
+    double ri_scale = 0.0, ri_min = 0.0, ri_max = 0.0;
+    // CLEARANCE (gvom_clearance): the row pass's uint16 distances and the staging copy of a caller's host maps, each allocated
+    // by the first call that needs it; cl_allocs counts every device allocation the entry point has made on this handle
+    // (these two and its product sets: gvom_get_tuning "clearance_allocations")
+    Buf cl_g, cl_stage;
+    int cl_allocs = 0;
+};
+
+namespace gvom_host {
+inline double now_ns() { timespec t; clock_gettime(CLOCK_MONOTONIC, &t); return t.tv_sec * 1e9 + t.tv_nsec; }
+#define HT(h, slot, t0) do { if ((h)->host_timing) { double n_ = now_ns(); (h)->host_ns[slot] += n_ - (t0); (t0) = n_; } } while (0)
+
+#define HIPCHK(h, call)                                                                         \
+    do {                                                                                        \
+        hipError_t e_ = (call);                                                                 \
+        if (e_ != hipSuccess) {                                                                 \
+            char b_[512];                                                                       \
+            snprintf(b_, sizeof b_, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_),      \
+                     __FILE__, __LINE__);                                                       \
+            (h)->err = b_;                                                                      \
+            return GVOM_ERR_HIP;                                                                \
+        }                                                                                       \
+    } while (0)
+
+// Allocations another process may map (the peer transport exports the send regions and the height-map rows) are whole
+// multiples of 2 MiB: the HSA runtime carves smaller ones out of shared 2 MiB blocks, and a block cannot be exported
+// twice -- a second small region landing in an exported block is what hipIpcGetMemHandle refused ("invalid argument").
+inline size_t exportable_size(size_t bytes) { const size_t g = (size_t)2 << 20; return ((bytes ? bytes : 1) + g - 1) / g * g; }
+
+inline int64_t floor_mod(int64_t a, int64_t n) { int64_t r = a % n; return r < 0 ? r + n : r; }
+
+inline int clamp_delta(int64_t d, int size)
+{   // any |d| >= size puts the whole source window outside; keep ints small
+    if (d > size) return size;
+    if (d < -size) return -size;
+    return (int)d;
+}
+
+inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+// the ring-window phase of a map whose window starts at world voxel `origin`: om = origin mod size (gvom_internal.h "STORAGE LAYOUT")
+inline void window_phase(const gvom_handle *h, const int64_t origin[3], int om[3])
+{
+    for (int k = 0; k < 3; ++k) om[k] = (int)floor_mod(origin[k], k < 2 ? h->prm.xy_size : h->prm.z_size);
+}
+
+// the world position of a fused map's window corner, for the combine calls (gvom.py:185-188); `out` may be null
+inline void world_origin(const gvom_handle *h, const Fused &F, double out[3])
+{
+    for (int k = 0; out && k < 3; ++k) out[k] = (double)F.origin[k] * (k < 2 ? h->prm.xy_resolution : h->prm.z_resolution);
+}
+
+// ---- functions that cross unit boundaries, by the unit that defines them ----
+// gvom_handle.hip
+int ensure(gvom_handle *h, Buf &b, size_t bytes);
+int ensure_keep(gvom_handle *h, Buf &b, size_t bytes);
+void stats_demand(gvom_handle *h);
+void release_statistics_buffers(gvom_handle *h);
+int renumber_epochs(gvom_handle *h);
+hipError_t sync_streams(gvom_handle *h);
+hipError_t join_fuse_stream(gvom_handle *h);
+hipError_t join_map_stream(gvom_handle *h);
+hipError_t join_second_stream(gvom_handle *h);
+bool wait_published(gvom_handle *h, std::unique_lock<std::mutex> &lk, volatile unsigned long long *flag, uint32_t seq,
+                    bool high_half, double *last_ns);
+void collect_stage_ms(gvom_handle *h);
+// gvom_capi.hip (scans)
+bool verify_fastdiv(double d);
+// gvom_combine.hip
+void fill_fuse_frame(const gvom_handle *h, const int64_t origin[3], FuseParams &P);
+int fuse_impl(gvom_handle *h, hipStream_t on = nullptr);
+int map2d_impl(gvom_handle *h, bool gathered, bool publish, char *out_dev, bool yx, const double *occ = nullptr,
+               hipStream_t on = nullptr, uint32_t done_seq = 0, bool dev_set = false);
+int settle_count(gvom_handle *h);
+// gvom_export.hip
+void set_free(DevSet *s);
+void occ_params(const gvom_handle *h, const Fused &F, OccParams &P);
+void cloud_params(const gvom_handle *h, const Fused &F, Map2dParams &P);
+hipError_t launch_height_cloud(gvom_handle *h, const Fused &F, float *out7, float *out3);
+}  // namespace gvom_host

@@ -1,5 +1,5 @@
 // gvom_internal.h -- shared between the kernels (gvom_trace / gvom_fuse / gvom_map2d / gvom_stats .hip) and the C-ABI host
-// layer (gvom_capi.hip).  Not part of the public interface (include/gvom_hip.h is).
+// layer (the host units around gvom_host.h).  Not part of the public interface (include/gvom_hip.h is).
 //
 // STORAGE LAYOUT (DESIGN.md "Data layout in HBM")
 //   Voxels are stored WORLD-ANCHORED (toroidal): the voxel with world index (xw, yw, zw)

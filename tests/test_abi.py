@@ -93,6 +93,26 @@ def test_test_hooks_live_in_the_test_library_only():
         assert word in hooks
 
 
+def test_identity_hashes_every_source_of_the_library():
+    """tools/lib_identity.py takes its list from the Makefile (UNITS, HDR): every unit and header under csrc/ is in it -- a file
+    left out would not change the source_sha256 stamped into the profile sidecars -- every listed file exists, and `make sources`
+    prints the same list."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("lib_identity", os.path.join(ROOT, "tools", "lib_identity.py"))
+    lib_identity = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(lib_identity)
+    pkg = os.path.join(ROOT, "g-vom_amd")
+    listed = lib_identity.sources()
+    assert len(listed) == len(set(listed))
+    for rel in listed:
+        assert os.path.isfile(os.path.join(pkg, rel)), rel
+    on_disk = {"csrc/" + f for f in os.listdir(os.path.join(pkg, "csrc")) if f.endswith((".hip", ".h"))}
+    assert on_disk and on_disk <= set(listed), sorted(on_disk - set(listed))
+    assert {"../include/gvom_hip.h", "../include/gvom_hip_test.h", "Makefile"} <= set(listed)
+    printed = subprocess.run(["make", "-s", "-C", pkg, "sources"], capture_output=True, text=True, check=True).stdout.split()
+    assert printed == listed
+
+
 def test_no_silent_cpu_fallback():
     """Without a GPU the product must refuse to run, not quietly compute on the CPU."""
     import gvom

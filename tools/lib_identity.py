@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Identity of the library a measurement was taken on: sha256 of g-vom_amd/lib/libgvom_hip.so, sha256 of the sources it is
-built from (SOURCES below, in that order, so that anyone can recompute it from a
+built from (the Makefile's own list -- UNITS, HDR, then the Makefile -- in that order, so that anyone can recompute it from a
 commit), and the git commit.  hipcc's output is reproducible: the same sources give the same library bytes.
 The GPU box has no .git: `make -C g-vom_amd stamp` (run here, before gpurun) leaves the commit in g-vom_amd/lib/GIT_HEAD.
 
@@ -10,13 +10,26 @@ The GPU box has no .git: `make -C g-vom_amd stamp` (run here, before gpurun) lea
 import hashlib
 import json
 import os
+import re
 import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "g-vom_amd")
-SOURCES = ["csrc/gvom_trace.hip", "csrc/gvom_fuse.hip", "csrc/gvom_map2d.hip", "csrc/gvom_stats.hip", "csrc/gvom_products.hip", "csrc/gvom_capi.hip", "csrc/gvom_comm.hip",
-           "csrc/gvom_device.h", "csrc/gvom_internal.h", "../include/gvom_hip.h", "../include/gvom_hip_test.h", "Makefile"]
+
+
+def sources():
+    """The files the library is built from, relative to g-vom_amd/: what `make sources` prints ($(SRC) $(HDR) Makefile), read
+    from the Makefile's UNITS and HDR lines without running make."""
+    with open(os.path.join(PKG, "Makefile")) as f:
+        text = f.read().replace("\\\n", " ")
+    var = {}
+    for name in ("UNITS", "HDR"):
+        found = re.findall(r"^%s\s*:=(.*)$" % name, text, re.M)
+        if len(found) != 1:
+            raise RuntimeError("g-vom_amd/Makefile: expected exactly one `%s := ...` line, found %d" % (name, len(found)))
+        var[name] = found[0].split()
+    return ["csrc/%s.hip" % u for u in var["UNITS"]] + var["HDR"] + ["Makefile"]
 
 
 def sha256_file(path):
@@ -29,7 +42,7 @@ def sha256_file(path):
 
 def source_sha256():
     h = hashlib.sha256()
-    for rel in SOURCES:
+    for rel in sources():
         with open(os.path.join(PKG, rel), "rb") as f:
             h.update(f.read())
     return h.hexdigest()

@@ -172,8 +172,12 @@ int fuse_impl(gvom_handle *h, hipStream_t on)
 // 2-D maps (k_map2d) from height/inferred of the whole window (all rows must be present).
 // gathered: sharded run -- every row of the interleaved height buffer (heights + owner-computed
 // positive densities) has been all-gathered and this rank computes ALL rows of the outputs.
+// host_out: the host address of a caller's output buffer (out_dev is its device view).  The four maps in [y][x] order into a
+// buffer from gvom_output_buffer_alloc go through the buffer's content record (k_map2d's DELTA form: runs that are default now and
+// were default the last time are not stored); every other write into a caller's buffer DROPS its record -- the occupancy grids,
+// the sharded form, "delta_out" 0 -- so that a record never describes bytes somebody else has written since.
 int map2d_impl(gvom_handle *h, bool gathered, bool publish, char *out_dev, bool yx, const double *occ, hipStream_t on,
-               uint32_t done_seq, bool dev_set)
+               uint32_t done_seq, bool dev_set, void *host_out)
 {
     const hipStream_t ms = on ? on : h->stream;
     const gvom_params &p = h->prm;
@@ -208,12 +212,34 @@ int map2d_impl(gvom_handle *h, bool gathered, bool publish, char *out_dev, bool 
         o_rgh = (double *)out_dev;
         o_pos = (int32_t *)(o_rgh + 6 * S); o_neg = o_pos + S; o_vis = o_neg + S;
     }
+    uint8_t *bits = nullptr;
+    if (host_out && !dev_set) {
+        const bool recorded = h->tune_delta_out != 0 && yx && !occ && !gathered && !h->sharded && !(P.dbg & 1) &&
+                              std::find(h->out_bufs.begin(), h->out_bufs.end(), host_out) != h->out_bufs.end();
+        if (!recorded) h->out_rec.forget(host_out);
+        else {
+            const size_t slot_bytes = align256(gvom_outrec_bytes(p.xy_size));
+            if (!h->out_rec_bits) HIPCHK(h, hipMalloc((void **)&h->out_rec_bits, slot_bytes * GVOM_OUTREC_MAX));
+            bool fresh = false;
+            const int slot = h->out_rec.use(host_out, p.xy_size, &fresh);
+            bits = h->out_rec_bits + (size_t)slot * slot_bytes;
+            // (on the kernel's stream: every k_map2d of this handle is ordered behind the one before it, whichever stream it ran on)
+            if (fresh) {
+                const hipError_t e = hipMemsetAsync(bits, 0xFF, slot_bytes, ms);
+                if (e != hipSuccess) { h->out_rec.forget(host_out); HIPCHK(h, e); }
+            }
+        }
+    }
     if (h->profiling) HIPCHK(h, hipEventRecord(h->ev[6], ms));
-    HIPCHK(h, gvom_launch_map2d(ms, P, F.state, F.tags, (const uint4 *)F.rows.p,
-                                h->height, h->inferred, h->slope_x,
-                                h->slope_y, h->rough, h->guessed, o_pos, o_neg, o_rgh, o_vis,
-                                h->blockcounts, h->cnt_blocks,
-                                publish ? (unsigned long long *)(h->counters_host_dev + 2) : nullptr));
+    {
+        const hipError_t e = gvom_launch_map2d(ms, P, F.state, F.tags, (const uint4 *)F.rows.p,
+                                               h->height, h->inferred, h->slope_x,
+                                               h->slope_y, h->rough, h->guessed, o_pos, o_neg, o_rgh, o_vis,
+                                               h->blockcounts, h->cnt_blocks,
+                                               publish ? (unsigned long long *)(h->counters_host_dev + 2) : nullptr, bits);
+        if (e != hipSuccess && bits) h->out_rec.forget(host_out);      // (a launch that failed: what the buffer holds is anybody's guess)
+        HIPCHK(h, e);
+    }
     if (h->profiling) { HIPCHK(h, hipEventRecord(h->ev[7], ms)); h->ev_map = true; }
     h->maps_valid = true;
     return GVOM_OK;
@@ -319,9 +345,9 @@ static int combine_sync(gvom_handle *h, double origin_world[3], void *pinned_out
     char *dev = h->out_host_dev;
     if (pinned_out) HIPCHK(h, hipHostGetDevicePointer((void **)&dev, pinned_out, 0));
     const uint32_t done_seq = ++h->combine_seq;
-    if ((rc = map2d_impl(h, false, true, dev, pinned_out != nullptr, occ, nullptr, done_seq))) return rc;
+    if ((rc = map2d_impl(h, false, true, dev, pinned_out != nullptr, occ, nullptr, done_seq, false, pinned_out))) return rc;
     HT(h, 2, t0);                                        // combine: launches
-    if ((rc = finish_combine(h, lk, done_seq))) return rc;
+    if ((rc = finish_combine(h, lk, done_seq))) { if (pinned_out) h->out_rec.forget(pinned_out); return rc; }
     HT(h, 3, t0);                                        // combine: wait
     if (copy_to) {
         const size_t n2 = h->cells2d;
@@ -372,7 +398,36 @@ VIS int gvom_output_buffer_free(gvom_t *h, void *host_ptr)
     for (size_t k = 0; k < h->out_bufs.size(); ++k)
         if (h->out_bufs[k] == host_ptr) { h->out_bufs[k] = h->out_bufs.back(); h->out_bufs.pop_back(); break; }
     if (h->last_checked_out == host_ptr) h->last_checked_out = nullptr;
+    h->out_rec.forget(host_ptr);                         // (the allocator may hand the address out again)
     HIPCHK(h, hipHostFree(host_ptr));
+    return GVOM_OK;
+}
+
+// The CONTENT RECORD of an output buffer (k_map2d stores only the runs that changed: include/gvom_hip.h) is dropped: the next
+// combine into `host_ptr` stores every run again.  For a caller that has written into the buffer itself.  Unknown pointers are fine.
+VIS int gvom_output_forget(gvom_t *h, void *host_ptr)
+{
+    if (!h || !host_ptr) return GVOM_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(h->mu);
+    h->out_rec.forget(host_ptr);
+    return GVOM_OK;
+}
+
+// Read-back of a buffer's record (measurements, tests): waits for the handle's streams and copies the record's bytes -- one per
+// (32 x 8 tile, wave), gvom_outrec.h -- to `bits` (`cap` bytes available); *n: bytes the record has.  GVOM_NO_DATA: no record.
+VIS int gvom_output_record(gvom_t *h, void *host_ptr, uint8_t *bits, size_t cap, size_t *n, uint64_t *generation)
+{
+    if (!h || !host_ptr || !n) return GVOM_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(h->mu);
+    const int slot = h->out_rec.find(host_ptr);
+    if (slot < 0 || !h->out_rec_bits) return GVOM_NO_DATA;
+    *n = gvom_outrec_bytes(h->prm.xy_size);
+    if (generation) *generation = h->out_rec.e[slot].gen;
+    if (!bits) return GVOM_OK;
+    if (cap < *n) return GVOM_ERR_CAPACITY;
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, sync_streams(h));
+    HIPCHK(h, hipMemcpy(bits, h->out_rec_bits + (size_t)slot * align256(*n), *n, hipMemcpyDeviceToHost));
     return GVOM_OK;
 }
 
@@ -435,7 +490,7 @@ VIS int gvom_combine_begin(gvom_t *h, void *pinned_out, const double *occ)
     }
     char *dev = nullptr;
     HIPCHK(h, hipHostGetDevicePointer((void **)&dev, pinned_out, 0));
-    if ((rc = map2d_impl(h, false, true, dev, true, occ, h->stream_b))) return rc;
+    if ((rc = map2d_impl(h, false, true, dev, true, occ, h->stream_b, 0, false, pinned_out))) return rc;
     HIPCHK(h, hipEventRecord(h->ev_mapped, h->stream_b));
     h->mapped_unjoined = true;
     h->pending_combine = true;
@@ -457,6 +512,7 @@ VIS int gvom_combine_end(gvom_t *h, double origin_world[3])
     lk.lock();
     h->pending_combine = false;                            // (also on failure: the handle must not stay blocked)
     h->fuse_b_unjoined = false;                            // k_map2d has completed, and the fusion in front of it
+    if (e != hipSuccess) h->out_rec.clear();               // (what the buffer holds is anybody's guess)
     HIPCHK(h, e);
     adopt_fused_count(h);
     HT(h, 3, t0);
@@ -516,7 +572,7 @@ VIS int gvom_combine_map2d_into(gvom_t *h, double origin_world[3], void *pinned_
     // synchronisation notices the end of the stream several microseconds later); the count was published by k_posdens
     const uint32_t done_seq = ++h->combine_seq;
     const bool solo = h->sharded && h->world == 1;       // (every row is this rank's: no gathered densities, see gvom_combine_fuse)
-    int rc = map2d_impl(h, !solo, solo, dev, true, nullptr, nullptr, done_seq);
+    int rc = map2d_impl(h, !solo, solo, dev, true, nullptr, nullptr, done_seq, false, pinned_out);
     if (rc == GVOM_OK) rc = finish_combine(h, lk, done_seq);
     if (rc) return rc;
     world_origin(h, h->fused[h->cur], origin_world);

@@ -976,13 +976,14 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(7, 8))) voi
     int32_t *state, uint4 *crows, const uint32_t *__restrict__ stags, int32_t *fstate, uint4 *frows, uint32_t *ftags,
     uint32_t *blockcounts, double *height, double *inferred, uint32_t *counters, unsigned long long *host_flag, uint32_t seq)
 {
-    __shared__ unsigned long long s_zh[8][WAVE];            // per wave and column: min of (window z << 32 | min-height bits) over occupied voxels
-    __shared__ uint32_t s_zf[8][WAVE];                      // per wave and column: lowest observed-free window z
-    __shared__ uint32_t s_cnt[8];
+    // (per-wave arrays of FOUR: gvom_encfuse_shape never launches more than four waves)
+    __shared__ unsigned long long s_zh[4][WAVE];            // per wave and column: min of (window z << 32 | min-height bits) over occupied voxels
+    __shared__ uint32_t s_zf[4][WAVE];                      // per wave and column: lowest observed-free window z
+    __shared__ uint32_t s_cnt[4];
     // per wave: the occupied voxels of the levels in hand, one entry each -- storage voxel, accumulator index, the scan's hit and
     // total there, the previous map's state, {window z | column << 10 | occupied in the scan << 16}
-    __shared__ uint32_t s_eL[8][ENCFUSE_LIST], s_eA[8][ENCFUSE_LIST], s_eh[8][ENCFUSE_LIST], s_et[8][ENCFUSE_LIST], s_em[8][ENCFUSE_LIST];
-    __shared__ int32_t s_ep[8][ENCFUSE_LIST];
+    __shared__ uint32_t s_eL[4][ENCFUSE_LIST], s_eA[4][ENCFUSE_LIST], s_eh[4][ENCFUSE_LIST], s_et[4][ENCFUSE_LIST], s_em[4][ENCFUSE_LIST];
+    __shared__ int32_t s_ep[4][ENCFUSE_LIST];
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         // k_trace has completed: {seq, any-in-grid} to the spinning host, as k_encode's first thread does
         const uint32_t any = counters[GVOM_CNT_INGRID] ? 0x80000000u : 0u;

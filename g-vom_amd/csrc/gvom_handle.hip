@@ -455,6 +455,7 @@ VIS void gvom_destroy(gvom_t *h)
     hipFree(h->hmaps); hipFree(h->slope_x); hipFree(h->slope_y);
     hipFree(h->rough); hipFree(h->guessed);
     if (h->out_host) hipHostFree(h->out_host);
+    h->out_rec.clear(); hipFree(h->out_rec_bits);
     {   // device map sets: exported ones outlive the handle and go at their last release
         std::vector<DevSet *> idle;
         {
@@ -534,6 +535,7 @@ VIS int gvom_set_tuning(gvom_t *h, const char *name, int value)
     else if (!strcmp(name, "dirsort")) h->tune_dirsort = value;
     else if (!strcmp(name, "fastdiv")) h->tune_fastdiv = value;
     else if (!strcmp(name, "eager")) { h->tune_eager = value; h->eager_waste = 0; }
+    else if (!strcmp(name, "delta_out")) { if (value >= 0) h->tune_delta_out = value != 0; if (value <= 0) h->out_rec.clear(); }   // (-1: drop every record, keep the setting)   // 0: every run of the returned maps is stored, no record kept
     else if (!strcmp(name, "occupancy_clear")) h->tune_occ_clear = value;   // k_occupancy: 1 = clear the grid first, write live tile columns only
     else if (!strcmp(name, "exported")) h->exported = value != 0;       // (set by the peer transport, gvom_comm.hip)
 #ifdef GVOM_HOOKS
@@ -560,6 +562,8 @@ VIS int gvom_get_tuning(gvom_t *h, const char *name, int *value)
     if (!strcmp(name, "clearance_allocations")) { *value = h->cl_allocs; return GVOM_OK; }              // read-only: device allocations gvom_clearance has made
     if (!strcmp(name, "device_product_sets")) { *value = (int)h->psets.size(); return GVOM_OK; }        // read-only: allocated device product sets (every kind)
     if (!strcmp(name, "occupancy_clear")) { *value = h->tune_occ_clear; return GVOM_OK; }
+    if (!strcmp(name, "delta_out")) { *value = h->tune_delta_out; return GVOM_OK; }
+    if (!strcmp(name, "output_records")) { *value = h->out_rec.size(); return GVOM_OK; }                // read-only: output buffers with a content record
     if (!strcmp(name, "multi_origin")) { *value = 1; return GVOM_OK; }                                  // read-only: the library has the multi-origin entry points
     if (!strcmp(name, "multi_origin_ran")) { *value = h->last_multi_origin; return GVOM_OK; }           // read-only: the last scan ran the per-lane-origin trace
     if (!strcmp(name, "range_image")) { *value = h->ri_H > 0 ? 1 : 0; return GVOM_OK; }                 // read-only: a sensor model is set

@@ -4,6 +4,7 @@
 #pragma once
 #include "gvom_internal.h"
 #include "gvom_ingest.h"
+#include "gvom_outrec.h"
 #include "../../include/gvom_hip.h"
 
 #include <math.h>
@@ -240,6 +241,12 @@ struct gvom_handle {
     bool scan_inflight = false;                         // a scan's kernels are enqueued and it is not committed yet (scan_mu held)
     std::vector<void *> out_bufs;                        // buffers handed out by gvom_output_buffer_alloc (coherent by construction)
     void *last_checked_out = nullptr;                    // a caller's own output buffer whose flags have been checked
+    // CONTENT RECORD of the output buffers (gvom_outrec.h; k_map2d's DELTA form): which of out_bufs has which slot of out_rec_bits
+    // (GVOM_OUTREC_MAX slots of gvom_outrec_bytes(xy) bytes, rounded up to 256; allocated by the first combine that needs it).
+    // Only buffers from gvom_output_buffer_alloc are recorded: their lifetime is the library's to see.
+    OutRecTable out_rec;
+    uint8_t *out_rec_bits = nullptr;
+    int tune_delta_out = 1;                             // gvom_set_tuning "delta_out": 0 = every combine stores every run (and keeps no record)
     void *out_host = nullptr;                           // pinned, device-mapped staging for the 4 outputs
     char *out_host_dev = nullptr;                       // device view of out_host (zero-copy target)
     uint32_t scan_seq = 0;                              // sequence number of the {seq,count} flag
@@ -364,7 +371,7 @@ bool verify_fastdiv(double d);
 void fill_fuse_frame(const gvom_handle *h, const int64_t origin[3], FuseParams &P);
 int fuse_impl(gvom_handle *h, hipStream_t on = nullptr);
 int map2d_impl(gvom_handle *h, bool gathered, bool publish, char *out_dev, bool yx, const double *occ = nullptr,
-               hipStream_t on = nullptr, uint32_t done_seq = 0, bool dev_set = false);
+               hipStream_t on = nullptr, uint32_t done_seq = 0, bool dev_set = false, void *host_out = nullptr);
 int settle_count(gvom_handle *h);
 // gvom_export.hip
 void set_free(DevSet *s);

@@ -243,7 +243,7 @@ hipError_t gvom_launch_map2d(hipStream_t s, const Map2dParams &P, const int32_t 
                              const double *inferred, double *slope_x, double *slope_y,
                              double *rough, double *guessed, int32_t *out_pos, int32_t *out_neg,
                              double *out_rough, int32_t *out_vis, const uint32_t *blockcounts,
-                             int nblocks, unsigned long long *host_counter);
+                             int nblocks, unsigned long long *host_counter, uint8_t *out_bits = nullptr);
 // ---- optional per-voxel statistics (gvom.py:1172-1299, 858-909, 1333-1378, 454-473)
 // nrows: candidate compact rows (the scan's returns, + received endpoints on a sharded map); extra / n_extra: returns
 // received from other ranks (sharded statistics), accumulated like the rank's own

@@ -88,8 +88,18 @@ __device__ __forceinline__ void st_out(V *p, V v)
 // same [y][x] order, plain stores, no completion flag.  out_pos / out_neg / out_vis are maps 0-2, out_rough is map 3 and
 // the start of the set's f64 block: maps 4-8 (height, inferred height, x / y slope, guessed delta) follow it at
 // dev_map_stride(xy) elements each.  The storage-order internal maps are written as on every other path.
+//
+// DELTA (with YX, into host memory, unsharded, the four maps): ONLY WHAT CHANGED CROSSES THE LINK.  A store run -- a half-wave's
+// 32 cells in x of one map, 128 / 256 B -- that holds nothing but the default (visibility 0, positive 0, negative 0, roughness
+// -1.0: a cell without height, without three valid cells in its 3x3, without a negative-obstacle verdict) and held nothing but the
+// default the last time the library wrote THIS buffer is not stored again: the caller's buffer comes back step after step and most
+// of the window is empty.  out_bits is the buffer's record (gvom_outrec.h): byte (tile * 8 + wave), bit 2 m + half-wave for the
+// role's map m -- set: the run holds non-default values.  "Default now" is one half of a __ballot per map; a half-wave stores its
+// run iff it is non-default now or the bit was set.  A wave is the one writer of its byte (a plain device store by lane 0 at the
+// end) and loads it with the staging loads, in front of every host store.  The internal maps, the completion count and the flag
+// are written as in the plain form; a workgroup that stores nothing to the host still arrives at done_count.
 
-template <bool GATHERED_POS, bool YX, bool DEV = false>
+template <bool GATHERED_POS, bool YX, bool DEV = false, bool DELTA = false>
 __global__ __launch_bounds__(512) void k_map2d(const Map2dParams P, const int32_t *__restrict__ fstate,
                                                const uint32_t *__restrict__ ftags,
                                                const uint4 *__restrict__ frows,
@@ -99,8 +109,9 @@ __global__ __launch_bounds__(512) void k_map2d(const Map2dParams P, const int32_
                                                double *guessed, int32_t *out_pos, int32_t *out_neg,
                                                double *out_rough, int32_t *out_vis,
                                                const uint32_t *blockcounts, int nblocks,
-                                               unsigned long long *host_counter)
+                                               unsigned long long *host_counter, uint8_t *out_bits)
 {
+    static_assert(!DELTA || (YX && !DEV && !GATHERED_POS), "DELTA: the host-output [y][x] form only");
     constexpr int M2_TX = YX ? 32 : 8, M2_TY = YX ? 8 : 32;
     constexpr int M2_W = M2_TX + 2 * M2_HALO, M2_H = M2_TY + 2 * M2_HALO;      // 62 x 38 (YX) or 38 x 62
     __shared__ double ht[M2_H][M2_W];
@@ -117,6 +128,18 @@ __global__ __launch_bounds__(512) void k_map2d(const Map2dParams P, const int32_
     const int tx = cell & (M2_TX - 1), ty = cell / M2_TX;
     const int lane = tid & 63, wv = tid >> 6;
     const int X0 = blockIdx.x * M2_TX, Y0 = blockIdx.y * M2_TY;
+    // DELTA: this wave's byte of the buffer's record, as the last combine into the buffer left it, and as this one leaves it
+    const size_t rec_idx = DELTA ? ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 8 + (size_t)wv : (size_t)0;
+    const int rec_half = lane >> 5;
+    uint32_t rec_old = 0, rec_new = 0;
+    // a map's run of this half-wave: stored iff some cell of it is non-default (`nd`, over the lanes that get here) or the
+    // record says the buffer holds non-default values there (m: the role's first / second map)
+    auto run_store = [&](int m, bool nd) -> bool {
+        const unsigned long long b = __ballot(nd);
+        const bool now = (rec_half ? (uint32_t)(b >> 32) : (uint32_t)b) != 0u;
+        rec_new |= (now ? 1u : 0u) << (2 * m + rec_half);
+        return now || ((rec_old >> (2 * m + rec_half)) & 1u);
+    };
     if (host_counter && blockIdx.x == 0 && blockIdx.y == 0 && !GVOM_DBG(P, 16)) {
         // k_fuse is complete: publish the fused occupied-voxel count (host-mapped memory)
         __shared__ unsigned long long s_red[512];
@@ -130,6 +153,7 @@ __global__ __launch_bounds__(512) void k_map2d(const Map2dParams P, const int32_
         double v[NR];
         bool inw[NR];
         const int gx = X0 - M2_HALO + lane;
+        if (DELTA) rec_old = out_bits[rec_idx];
         const int sxh = wrap_add((gx >= 0 && gx < xy) ? gx : 0, P.om[0], xy);
 #pragma unroll
         for (int k = 0; k < NR; ++k) {
@@ -175,7 +199,8 @@ __global__ __launch_bounds__(512) void k_map2d(const Map2dParams P, const int32_
     // OCC: instead of the four maps, the five int8 nav_msgs/OccupancyGrid.data arrays the ROS node
     // derives from them (gvom_ros.py:141-165), planes [hard | soft | certainty | negative | roughness]
     visv = h00 > -1000 ? 1 : 0;
-    if (YX && wr) { if (P.occ && !DEV) st_sys(&occ[2 * n2 + c_out], (int8_t)(visv * 100)); else st_out<DEV>(&out_vis[c_out], visv); }
+    if (DELTA) { if (wr && run_store(0, visv != 0)) st_sys(&out_vis[c_out], visv); }
+    else if (YX && wr) { if (P.occ && !DEV) st_sys(&occ[2 * n2 + c_out], (int8_t)(visv * 100)); else st_out<DEV>(&out_vis[c_out], visv); }
     if (DEV && wr) out_rough[dev_map_stride(xy) + c_out] = h00;                 // map 4: height
     if (!YX) o_vis[tx][ty] = visv;
     // ---- role A: slope / roughness: 3x3 least-squares plane (gvom.py:665-734) ---------------------
@@ -246,7 +271,8 @@ __global__ __launch_bounds__(512) void k_map2d(const Map2dParams P, const int32_
         }
     }
     slope_x[c_yx] = sxv; slope_y[c_yx] = syv; rough[c_yx] = rv;
-    if (YX && wr) {
+    if (DELTA) { if (wr && run_store(1, rv != -1.0)) st_sys(&out_rough[c_out], rv); }
+    else if (YX && wr) {
         if (P.occ && !DEV) {
             // ((clip(r, min, max) + min) / (max - min)) * 100 in f64 as written (it ADDS min), then numpy's
             // float64 -> int8 cast: truncate to a 32-bit integer, keep the low byte (gvom_ros.py:162-163)
@@ -311,7 +337,8 @@ __global__ __launch_bounds__(512) void k_map2d(const Map2dParams P, const int32_
     if (role_b && mine) {
     visv = h00 > -1000 ? 1 : 0;                    // gvom.py:414-422 (stored by role A)
     pos = s_steep[cell] ? 100 : dens_pos;                    // gvom.py:489-521 (slope test done by role A)
-    if (YX && wr) {
+    if (DELTA) { if (wr && run_store(0, pos != 0)) st_sys(&out_pos[c_out], pos); }
+    else if (YX && wr) {
         if (P.occ && !DEV) st_sys(&occ[1 * n2 + c_out], (int8_t)(((double)pos <= P.occ_density_thr && pos > 0) ? 100 : 0));   // soft, :146
         else st_out<DEV>(&out_pos[c_out], pos);
     }
@@ -369,7 +396,8 @@ __global__ __launch_bounds__(512) void k_map2d(const Map2dParams P, const int32_
     }
     guessed[c_yx] = dh_out;
     negv = dh_out > P.neg_thr ? 100 : 0;           // gvom.py:479-485
-    if (YX && wr) {
+    if (DELTA) { if (wr && run_store(1, negv != 0)) st_sys(&out_neg[c_out], negv); }
+    else if (YX && wr) {
         if (P.occ && !DEV) {
             st_sys(&occ[3 * n2 + c_out], (int8_t)negv);                                                    // negative, :157
             st_sys(&occ[0 * n2 + c_out], (int8_t)max((double)pos > P.occ_density_thr ? 100 : 0, negv));   // hard, :141
@@ -388,6 +416,12 @@ __global__ __launch_bounds__(512) void k_map2d(const Map2dParams P, const int32_
             out_pos[c_xy] = o_pos[ox][oy]; out_neg[c_xy] = o_neg[ox][oy];
             out_vis[c_xy] = o_vis[ox][oy]; out_rough[c_xy] = o_rgh[ox][oy];
         }
+    }
+    if (DELTA && wr) {
+        // the record of what the buffer now holds: lanes 0 and 32 carry their half-waves' bits (a half-wave outside the window
+        // stored nothing and leaves its bits clear)
+        const uint32_t bits = (uint32_t)__builtin_amdgcn_readlane((int)rec_new, 0) | (uint32_t)__builtin_amdgcn_readlane((int)rec_new, 32);
+        if (lane == 0) out_bits[rec_idx] = (uint8_t)bits;
     }
     if (!DEV && P.done_flag) {
         // The maps lie in host memory once every wave's stores have been acknowledged (s_waitcnt vmcnt(0): system-scope
@@ -534,20 +568,23 @@ hipError_t gvom_launch_map2d(hipStream_t s, const Map2dParams &P, const int32_t 
                              const double *inferred, double *slope_x, double *slope_y,
                              double *rough, double *guessed, int32_t *out_pos, int32_t *out_neg,
                              double *out_rough, int32_t *out_vis, const uint32_t *blockcounts,
-                             int nblocks, unsigned long long *host_counter)
+                             int nblocks, unsigned long long *host_counter, uint8_t *out_bits)
 {
     if (P.y_hi <= P.y_lo) return hipSuccess;
     const int tx = P.out_yx ? 32 : 8, ty = P.out_yx ? 8 : 32;
     const dim3 grid((P.xy + tx - 1) / tx, (P.xy + ty - 1) / ty);
-#define MAP2D_LAUNCH(G, Y, D)                                                                            \
-    hipLaunchKernelGGL((k_map2d<G, Y, D>), grid, dim3(512), 0, s, P, fstate, ftags, frows, height, \
+#define MAP2D_LAUNCH(G, Y, D, L)                                                                         \
+    hipLaunchKernelGGL((k_map2d<G, Y, D, L>), grid, dim3(512), 0, s, P, fstate, ftags, frows, height, \
                        inferred, slope_x, slope_y, rough, guessed, out_pos, out_neg, out_rough, out_vis, \
-                       blockcounts, nblocks, host_counter)
+                       blockcounts, nblocks, host_counter, out_bits)
     if (P.out_dev) {                                      // a device map set: [y][x] order, unsharded, no occupancy grids, no flag
-        if (P.gathered_pos || !P.out_yx || P.occ || P.done_flag) return hipErrorInvalidValue;
-        MAP2D_LAUNCH(false, true, true);
-    } else if (P.gathered_pos) { if (P.out_yx) MAP2D_LAUNCH(true, true, false); else MAP2D_LAUNCH(true, false, false); }
-    else { if (P.out_yx) MAP2D_LAUNCH(false, true, false); else MAP2D_LAUNCH(false, false, false); }
+        if (P.gathered_pos || !P.out_yx || P.occ || P.done_flag || out_bits) return hipErrorInvalidValue;
+        MAP2D_LAUNCH(false, true, true, false);
+    } else if (out_bits) {                                // the four maps into a host buffer with a content record: changed runs only
+        if (P.gathered_pos || !P.out_yx || P.occ) return hipErrorInvalidValue;
+        MAP2D_LAUNCH(false, true, false, true);
+    } else if (P.gathered_pos) { if (P.out_yx) MAP2D_LAUNCH(true, true, false, false); else MAP2D_LAUNCH(true, false, false, false); }
+    else { if (P.out_yx) MAP2D_LAUNCH(false, true, false, false); else MAP2D_LAUNCH(false, false, false, false); }
 #undef MAP2D_LAUNCH
     return hipGetLastError();
 }

@@ -93,6 +93,8 @@ ABI = [
     ("gvom_output_buffer_alloc", _I, [_P, ctypes.POINTER(_P)]),
     ("gvom_output_buffer_free", _I, [_P, _P]),
     ("gvom_combine_maps_into", _I, [_P, _P, _P]),
+    ("gvom_output_forget", _I, [_P, _P]),
+    ("gvom_output_record", _I, [_P, _P, _P, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_uint64)]),
     ("gvom_combine_occupancy_into", _I, [_P, _P, _P, ctypes.c_double, ctypes.c_double, ctypes.c_double]),
     ("gvom_shard_scan_local", _I, [_P, _P, _I, _I64, _I64, _I, _DP, _P, ctypes.POINTER(_I64), ctypes.POINTER(_I64),
                                    ctypes.POINTER(_I)]),
@@ -1527,8 +1529,44 @@ class Gvom(object):
         self._check(self._lib.gvom_last_stage_ms(self._h, ctypes.byref(ms)))
         return dict(zip(STAGE_NAMES, [float(v) for v in ms]))
 
+    def forget(self, *arrays):
+        """The caller has WRITTEN into maps combine_maps() returned.  The returned arrays are writable views of a pinned buffer
+        that comes back to a later combine_maps() once they are all dropped, and the library stores only the runs of cells that
+        changed since it last wrote that buffer (include/gvom_hip.h, gvom_output_forget) -- it must be the buffer's only writer.
+        Call forget(array, ...) with any of the written arrays BEFORE dropping them (no argument: every buffer of this mapper),
+        or switch the mechanism off: set_tuning("delta_out", 0).  A caller that only reads the maps, or copies them, has
+        nothing to do."""
+        if not arrays:
+            self._check(self._lib.gvom_set_tuning(self._h, b"delta_out", -1))     # (-1: every record goes, the setting stays)
+            return
+        for a in arrays:
+            base = a
+            while getattr(base, "base", None) is not None:
+                base = base.base
+            ptr = getattr(base, "ptr", None)
+            if ptr is None:
+                ptr = np.asarray(a).__array_interface__["data"][0]
+            self._check(self._lib.gvom_output_forget(self._h, ctypes.c_void_p(int(ptr))))
+
+    def output_record(self, array):
+        """(bits uint8[n], generation) of the content record of the buffer behind a returned map (include/gvom_hip.h,
+        gvom_output_record), or None when it has none.  For measurements and tests."""
+        base = array
+        while getattr(base, "base", None) is not None:
+            base = base.base
+        ptr = ctypes.c_void_p(int(base.ptr))
+        n, gen = ctypes.c_size_t(0), ctypes.c_uint64(0)
+        if self._check(self._lib.gvom_output_record(self._h, ptr, None, 0, ctypes.byref(n), ctypes.byref(gen))) == GVOM_NO_DATA:
+            return None
+        bits = np.zeros(n.value, np.uint8)
+        if self._check(self._lib.gvom_output_record(self._h, ptr, _ptr(bits), n.value, ctypes.byref(n), ctypes.byref(gen))) == GVOM_NO_DATA:
+            return None
+        return bits, int(gen.value)
+
     def set_tuning(self, name, value):
-        """Performance knobs that never change a result: "segs", "period", "ep_row", "prio", "interleave", "eager" (include/gvom_hip.h)."""
+        """Performance knobs that never change a result: "segs", "period", "ep_row", "prio", "interleave", "eager", "delta_out"
+        (include/gvom_hip.h).  "delta_out" 0: combine_maps() stores every cell every time -- for callers that write into the
+        returned maps in place and do not call forget()."""
         self._check(self._lib.gvom_set_tuning(self._h, name.encode(), int(value)))
 
     def get_tuning(self, name):

@@ -245,6 +245,24 @@ int gvom_combine_maps(gvom_t *h, double origin_world[3], int32_t *positive, int3
 int gvom_output_buffer_alloc(gvom_t *h, void **host_ptr);
 int gvom_output_buffer_free(gvom_t *h, void *host_ptr);
 int gvom_combine_maps_into(gvom_t *h, double origin_world[3], void *pinned_out);
+/* ONLY WHAT CHANGED IS STORED.  Most of a window is empty, and an empty cell gets the same four values every combine (visibility 0,
+ * positive 0, negative 0, roughness -1.0).  For every buffer from gvom_output_buffer_alloc the library therefore keeps a CONTENT
+ * RECORD -- in device memory, one bit per map and run of 32 cells in x -- of where it last stored anything else, and
+ * gvom_combine_maps_into / gvom_combine_begin (occ == NULL) do not store a run again that holds only those values now and held
+ * only those values the last time the library wrote THAT buffer.  The buffer's contents after the call are exactly what a full
+ * store leaves.  The first combine into a buffer stores everything, and so does the first one after anything else has written it
+ * through the library (the occupancy grids, gvom_combine_map2d_into) or after the record was dropped (at most 8 buffers per
+ * handle have one; the one used longest ago goes).  A buffer of the caller's own allocation is always stored in full.
+ * THE CALLER'S SIDE: a recorded buffer must have no writer but the library.  Whoever writes into it and hands it to a later
+ * combine calls gvom_output_forget first (any pointer is accepted; the next combine into it stores every run), or switches
+ * the record off for the handle: gvom_set_tuning "delta_out" 0.
+ * gvom_output_record (measurements, tests): the record of `host_ptr` as the kernel keeps it -- one byte per 32 (x) x 8 (y) tile
+ * and wave of k_map2d, tile-row-major, wave w < 4: rows 2 w, 2 w + 1 of the tile, bits 0 / 1 visibility, 2 / 3 roughness; wave
+ * w >= 4: rows 2 (w - 4), + 1, bits 0 / 1 positive, 2 / 3 negative; a set bit = the run holds non-default values.  Waits for the
+ * handle's work, copies *n = ceil(xy/32) * ceil(xy/8) * 8 bytes to `bits` (NULL: only *n and *generation are set; cap < *n:
+ * GVOM_ERR_CAPACITY).  *generation changes whenever the record restarts (all runs stored).  GVOM_NO_DATA: no record. */
+int gvom_output_forget(gvom_t *h, void *host_ptr);
+int gvom_output_record(gvom_t *h, void *host_ptr, uint8_t *bits, size_t cap, size_t *n, uint64_t *generation);
 
 /* combine_maps fused with the ROS node's post-processing (gvom_ros.py:141-165):
  * advances the fusion exactly like gvom_combine_maps, but the GPU writes the five int8
@@ -610,6 +628,9 @@ int gvom_host_timing(gvom_t *h, double us[8]);
  * fusions through the general kernel), "flag_kernel" (1: round 3's completion-flag kernel).
  * "occupancy_clear" (A/B of k_occupancy's dead tile columns: 0, default, the kernel writes every byte of the grid; 1 the grid is
  * cleared with hipMemsetAsync and only tile columns with a live tile are written.  Same grid either way).
+ * "delta_out" (1, default: gvom_combine_maps_into / gvom_combine_begin store only the runs of the four maps that changed, see
+ * gvom_output_forget; 0: every run, every time, and no record is kept.  Same buffer contents either way; also readable).
+ * "output_records" (read-only, gvom_get_tuning): output buffers that have a content record now.
  * "range_image" (read-only, gvom_get_tuning): 1 when a sensor model is set (gvom_sensor_model_set), else 0.
  * "multi_origin" / "multi_origin_ran" (read-only, gvom_get_tuning): see "multi-origin scans" above.
  * "clearance_allocations" (read-only, gvom_get_tuning): see "obstacle clearance" above.

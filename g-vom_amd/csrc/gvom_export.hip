@@ -1,5 +1,5 @@
 // gvom_export.hip -- device-resident results: map sets and product sets (DevSet) with their exports, releases and DLPack capsules,
-// gvom_combine_maps_device, the 3-D products and the clearance map.
+// gvom_combine_maps_device, the 3-D products, the clearance map and ray queries.
 #include "gvom_host.h"
 
 namespace gvom_host {
@@ -37,6 +37,28 @@ void cloud_params(const gvom_handle *h, const Fused &F, Map2dParams &P)
     P.y_lo = h->sy_lo; P.y_hi = h->sy_hi;
     P.xy_res = p.xy_resolution; P.z_res = p.z_resolution;
     P.nseg = h->nseg; P.epoch = F.epoch;
+}
+
+// the frame of the fused map F as k_raycast reads it (gvom_launch_raycast names the fields), and what of a query depends on it
+void raycast_params(const gvom_handle *h, const Fused &F, ScanParams &P, RayQuery &Q)
+{
+    const gvom_params &p = h->prm;
+    memset(&P, 0, sizeof P);
+    P.xy_res = p.xy_resolution; P.z_res = p.z_resolution;
+    P.drcp[0] = 1.0 / p.xy_resolution; P.drcp[1] = 1.0 / p.z_resolution;
+    P.fastdiv = h->tune_fastdiv == 0 ? 0 : h->fastdiv_ok;
+    P.xy = p.xy_size; P.zs = p.z_size;
+    P.sy_lo = h->sy_lo; P.sy_hi = h->sy_hi;
+    P.nseg = h->nseg; P.epoch = F.epoch;
+    P.f32_sqrt = h->f32_sqrt ? 1 : 0;
+    window_phase(h, F.origin, P.om);
+    bool far = false;
+    for (int k = 0; k < 3; ++k) {
+        P.origin[k] = (double)F.origin[k];
+        far = far || F.origin[k] <= -((int64_t)1 << 24) || F.origin[k] >= ((int64_t)1 << 24);
+    }
+    Q.lit = (far || p.z_size > p.xy_size) ? 1 : 0;        // (the integer window test assumes z_size <= xy_size and a near origin)
+    Q.cap = (uint32_t)p.xy_size + (uint32_t)p.z_size;
 }
 
 hipError_t launch_height_cloud(gvom_handle *h, const Fused &F, float *out7, float *out3)
@@ -116,6 +138,7 @@ static size_t set_bytes(int kind, int xy, int zs, int64_t cap)
     case GVOM_PRODUCT_HEIGHT_CLOUD: return n2 * 28;
     case GVOM_PRODUCT_INFERRED_HEIGHT_CLOUD: return n2 * 12;
     case GVOM_PRODUCT_CLEARANCE: return align256(n2 * 4) + n2 * 4;
+    case GVOM_PRODUCT_RAYCAST: return align256((size_t)cap * 16) + (size_t)cap * 12;
     }
     return 0;
 }
@@ -154,6 +177,11 @@ static bool set_part(const DevSet *s, int part, SetPart *d)
         d->ptr = s->mem + (part ? align256((size_t)n2 * 4) : 0);
         d->shape[0] = d->shape[1] = xy; d->strides[0] = 1; d->strides[1] = xy;
         if (part) d->code = kDLInt;
+        break;
+    case GVOM_PRODUCT_RAYCAST:
+        if (part == 0) { rows(s->mem, s->cap, 4); d->code = kDLInt; }
+        else if (part == 1) rows(s->mem + align256((size_t)s->cap * 16), s->cap, 3);
+        else return false;
         break;
     default: return false;
     }
@@ -383,6 +411,7 @@ VIS int gvom_device_product(gvom_t *h, int kind, int64_t max_rows, int64_t *prod
     std::lock_guard<std::mutex> lk(h->mu);
     *product_id = -1;
     if (kind == GVOM_PRODUCT_CLEARANCE) { h->err = "gvom_device_product: a clearance product is made by gvom_clearance"; return GVOM_ERR_INVALID; }
+    if (kind == GVOM_PRODUCT_RAYCAST) { h->err = "gvom_device_product: a raycast product is made by gvom_raycast"; return GVOM_ERR_INVALID; }
     if (kind < 1 || kind > GVOM_N_PRODUCT_KINDS) { h->err = "gvom_device_product: unknown product kind"; return GVOM_ERR_INVALID; }
     if (h->sharded) { h->err = "gvom_device_product: sharded handles are not supported"; return GVOM_ERR_INVALID; }
     if (kind == GVOM_PRODUCT_VOXEL_CLOUD) stats_demand(h);                  // a read of the statistics, like gvom_debug_voxel_map
@@ -546,6 +575,73 @@ VIS int gvom_clearance(gvom_t *h, int64_t map_set_id, const int32_t *positive, c
     HIPCHK(h, hipEventRecord(set->ready, h->stream));
     set->id = ++h->pset_seq;
     *product_id = set->id;
+    return GVOM_OK;
+}
+
+// ---- ray queries (gvom_raycast) --------------------------------------------------------------------------------------------------
+// n segments walked through the CURRENT fused map by k_raycast (gvom_query.hip), read-only, on the handle's stream behind
+// whatever produced that map; the result is a product of kind GVOM_PRODUCT_RAYCAST sized by n.  Enqueues and returns; later
+// scans and combines run behind the kernel on the same stream and never touch the product.
+VIS int gvom_raycast(gvom_t *h, const float *from, int64_t K, const float *to, int64_t n, int on_device, int flags,
+                     double origin_voxels[3], int64_t *product_id)
+{
+    if (!h || !product_id) return GVOM_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(h->mu);
+    *product_id = -1;
+    if (h->sharded) { h->err = "gvom_raycast: sharded handles are not supported"; return GVOM_ERR_INVALID; }
+    if (!from || !to) { h->err = "gvom_raycast: from and to must not be NULL"; return GVOM_ERR_INVALID; }
+    if (n < 1) { h->err = "gvom_raycast: n must be at least 1"; return GVOM_ERR_INVALID; }
+    if (K != 1 && K != n) { h->err = "gvom_raycast: K must be 1 or n"; return GVOM_ERR_INVALID; }
+    if (flags & ~(GVOM_RAY_UNKNOWN_BLOCKS | GVOM_RAY_CHECK_TARGET)) { h->err = "gvom_raycast: unknown flag bits"; return GVOM_ERR_INVALID; }
+    if (n > GVOM_RAYCAST_MAX_RAYS) { h->err = "gvom_raycast: more than 2^26 rays in one call"; return GVOM_ERR_CAPACITY; }
+    if (!h->has_combined) return GVOM_NO_DATA;
+    HIPCHK(h, hipSetDevice(h->device));
+    const int kind = GVOM_PRODUCT_RAYCAST;
+    const size_t bytes = set_bytes(kind, 0, 0, n);
+    DevSet *set = set_recycle(h->psets, kind, bytes);
+    if (!set) {
+        int held = 0;
+        for (DevSet *s : h->psets) held += s->kind == kind;
+        if (held >= GVOM_MAX_PRODUCT_SETS) {
+            h->err = "gvom_raycast: all 4 device product sets of this kind are exported; release some (gvom_device_product_release, or drop the tensors)";
+            return GVOM_ERR_CAPACITY;
+        }
+        const int rc0 = set_new(h, h->psets, kind, bytes, &set);
+        if (rc0) return rc0;
+        ++h->rq_allocs;
+    }
+    set->cap = n;
+    int rc;
+    const Fused &F = h->fused[h->cur];
+    ScanParams P;
+    RayQuery Q;
+    memset(&Q, 0, sizeof Q);
+    raycast_params(h, F, P, Q);
+    Q.from = from; Q.to = to; Q.n = (long)n;
+    Q.one_origin = K == 1 ? 1 : 0;
+    Q.unknown_blocks = (flags & GVOM_RAY_UNKNOWN_BLOCKS) ? 1 : 0;
+    Q.check_target = (flags & GVOM_RAY_CHECK_TARGET) ? 1 : 0;
+    HIPCHK(h, join_second_stream(h));
+    if (!on_device) {                                                       // host segments: staged, and up before the call returns
+        const size_t kb = (size_t)K * 12, nb = (size_t)n * 12;
+        if (h->rq_stage.bytes < align256(kb) + nb) {
+            if ((rc = ensure(h, h->rq_stage, align256(kb) + nb))) return rc;
+            ++h->rq_allocs;
+        }
+        char *st = (char *)h->rq_stage.p;
+        HIPCHK(h, hipMemcpyAsync(st, from, kb, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(st + align256(kb), to, nb, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        Q.from = (const float *)st; Q.to = (const float *)(st + align256(kb));
+    }
+    if ((rc = set_wait_releases(h, set))) return rc;
+    SetPart d0, d1;
+    set_part(set, 0, &d0); set_part(set, 1, &d1);
+    HIPCHK(h, gvom_launch_raycast(h->stream, P, Q, F.state, F.tags, (int32_t *)d0.ptr, (float *)d1.ptr));
+    HIPCHK(h, hipEventRecord(set->ready, h->stream));
+    set->id = ++h->pset_seq;
+    *product_id = set->id;
+    for (int k = 0; origin_voxels && k < 3; ++k) origin_voxels[k] = (double)F.origin[k];
     return GVOM_OK;
 }
 }  // extern "C"

@@ -71,12 +71,14 @@ struct Fused {
 //                    256-byte aligned
 //   height clouds    xy*xy x 7 / x 3 floats
 //   clearance        xy*xy floats (metres), then xy*xy int32 (squared cells) at the next 256-byte boundary, both [y][x]
+//   raycast          cap x 4 int32 {status, steps, voxel, unknown}, then cap x 3 floats (stop position) at the next 256-byte
+//                    boundary; cap = the rays of the call that wrote it
 struct DevSet {
     char *mem = nullptr;
     size_t bytes = 0;
     int device = 0, xy = 0;
     int kind = 0, zs = 0;                      // GVOM_PRODUCT_* (0: a map set); z_size (occupancy)
-    int64_t cap = 0;                           // voxel cloud: rows the allocation holds
+    int64_t cap = 0;                           // voxel cloud: rows the allocation holds; raycast: rays of the product
     hipEvent_t ready = nullptr;                // recorded on the handle's stream behind the set's k_map2d
     int64_t id = -1;                           // sequence number of the combine that wrote it; -1: free
     int exports = 0;                           // live exports
@@ -85,7 +87,8 @@ struct DevSet {
     bool orphan = false;                       // the handle is gone
 };
 #define GVOM_MAX_DEVICE_SETS 8
-#define GVOM_N_PRODUCT_KINDS 4
+#define GVOM_N_PRODUCT_KINDS 4                  // the kinds gvom_device_product makes (clearance and raycast products have entry points of their own)
+#define GVOM_RAYCAST_MAX_RAYS ((int64_t)1 << 26)
 // DevSet::exports / rel* / orphan: a DLPack deleter runs on whatever thread frees the consumer's tensor, without the handle
 extern std::mutex g_set_mu;                               // (gvom_export.hip)
 }  // namespace gvom_host
@@ -305,6 +308,11 @@ struct gvom_handle {
     // (these two and its product sets: gvom_get_tuning "clearance_allocations")
     Buf cl_g, cl_stage;
     int cl_allocs = 0;
+    // RAY QUERIES (gvom_raycast): the staging copy of a caller's host segments ([K][3] origins, then [n][3] end points), grown by
+    // the first call that needs more; rq_allocs counts every device allocation the entry point has made on this handle (this
+    // buffer and its product sets: gvom_get_tuning "raycast_allocations")
+    Buf rq_stage;
+    int rq_allocs = 0;
 };
 
 namespace gvom_host {
@@ -377,5 +385,6 @@ int settle_count(gvom_handle *h);
 void set_free(DevSet *s);
 void occ_params(const gvom_handle *h, const Fused &F, OccParams &P);
 void cloud_params(const gvom_handle *h, const Fused &F, Map2dParams &P);
+void raycast_params(const gvom_handle *h, const Fused &F, ScanParams &P, RayQuery &Q);
 hipError_t launch_height_cloud(gvom_handle *h, const Fused &F, float *out7, float *out3);
 }  // namespace gvom_host

@@ -1,4 +1,4 @@
-// gvom_internal.h -- shared between the kernels (gvom_trace / gvom_fuse / gvom_map2d / gvom_stats .hip) and the C-ABI host
+// gvom_internal.h -- shared between the kernels (gvom_trace / gvom_fuse / gvom_map2d / gvom_stats / gvom_query .hip) and the C-ABI host
 // layer (the host units around gvom_host.h).  Not part of the public interface (include/gvom_hip.h is).
 //
 // STORAGE LAYOUT (DESIGN.md "Data layout in HBM")
@@ -118,6 +118,18 @@ struct RayOrigins {
     const float    *tab;  // device, [K][3]: (float)(origin / resolution), the per-return ScanParams::pt0 (gvom.py:1097-1099)
     const uint16_t *idx;  // device, [n], or nullptr: index[i] = i % K
     uint32_t        K;
+};
+
+// ray queries (gvom_raycast, k_raycast in gvom_query.hip): n segments from[K == 1 ? 0 : i] -> to[i] in world metres, walked through
+// the fused map whose frame (resolutions, window origin, storage phase, tile epoch, sqrt typing) a ScanParams carries
+struct RayQuery {
+    const float *from, *to;   // device, [K][3] / [n][3]
+    long     n;
+    int      one_origin;      // K == 1: every ray starts at from[0]
+    int      unknown_blocks;  // GVOM_RAY_UNKNOWN_BLOCKS: the first never-observed voxel stops the ray
+    int      check_target;    // GVOM_RAY_CHECK_TARGET: the end point's own voxel is examined behind the last step
+    int      lit;             // 1: the literal float64 window lookup in every step (z_size > xy_size, or |origin| >= 2^24)
+    uint32_t cap;             // xy_size + z_size: no ray takes more steps inside the window (ray_steps' cap)
 };
 
 #define GVOM_PACK_CHUNK 64     // quads per k_pack workgroup
@@ -267,6 +279,11 @@ hipError_t gvom_launch_read_dense(hipStream_t s, int xy, int zs, const int om[3]
 // with hipMemsetAsync and only tile columns with a live tile are written (otherwise the kernel writes every byte itself)
 hipError_t gvom_launch_occupancy(hipStream_t s, const OccParams &P, const int32_t *fstate, const uint32_t *ftags, uint8_t *out,
                                  bool clear_first);
+// ray queries (gvom_query.hip): P = the fused map's frame (xy_res, z_res, drcp, fastdiv, origin, xy, zs, om, nseg, epoch, f32_sqrt;
+// the rest is not read).  out4[n][4] = {status, steps, voxel, unknown}, out3[n][3] = the stop position in metres (NaN where there
+// is none); out4 must be 16-byte aligned.  Reads fstate / ftags only.
+hipError_t gvom_launch_raycast(hipStream_t s, const ScanParams &P, const RayQuery &Q, const int32_t *fstate, const uint32_t *ftags,
+                               int32_t *out4, float *out3);
 // obstacle clearance (gvom_clearance.hip): pos / neg (neg may be nullptr) are [y][x] int32 maps of xy x xy cells; a cell is an
 // obstacle iff (double)pos > thr or neg > 0.  out_d2[y][x] = exact squared distance in cells to the nearest obstacle (INT32_MAX
 // where there is none, or beyond max_cells2 when that is > 0), out_dist[y][x] = (float)(sqrt((double)d2) * res), +inf there.

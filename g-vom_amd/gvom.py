@@ -24,8 +24,8 @@ import threading
 
 import numpy as np
 
-__all__ = ["Gvom", "GvomBackendError", "DeviceMaps", "DeviceMap", "DeviceArray", "DeviceVoxelCloud", "load_library", "library_path",
-           "unproject_range_image"]
+__all__ = ["Gvom", "GvomBackendError", "DeviceMaps", "DeviceMap", "DeviceArray", "DeviceVoxelCloud", "DeviceRays", "load_library",
+           "library_path", "unproject_range_image"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -159,6 +159,7 @@ ABI = [
     ("gvom_device_product_dlpack", _I, [_P, _I64, _I, _P, _I, ctypes.POINTER(_P)]),
     ("gvom_device_product_copy", _I, [_P, _I64, _I, _P]),
     ("gvom_clearance", _I, [_P, _I64, _P, _P, _I, ctypes.c_double, ctypes.c_int32, _I, ctypes.POINTER(_I64)]),
+    ("gvom_raycast", _I, [_P, _P, _I64, _P, _I64, _I, _I, _DP, ctypes.POINTER(_I64)]),
     ("gvom_set_profiling", _I, [_P, _I]),
     ("gvom_host_timing", _I, [_P, ctypes.POINTER(ctypes.c_double * 8)]),
     ("gvom_set_tuning", _I, [_P, ctypes.c_char_p, _I]),
@@ -655,6 +656,41 @@ class DeviceClearance(object):
 
     def copy_to_host(self):
         return self.distance.copy_to_host(), self.squared_cells.copy_to_host()
+
+    def release(self):
+        self._hold.release()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.release()
+        return False
+
+
+PRODUCT_RAYCAST = 6                       # GVOM_PRODUCT_RAYCAST: made by gvom_raycast, not by gvom_device_product
+RAY_CLEAR, RAY_OCCUPIED, RAY_UNKNOWN, RAY_LEFT_WINDOW, RAY_INVALID = range(5)       # GVOM_RAY_*: result[:, 0]
+_RAY_UNKNOWN_BLOCKS, _RAY_CHECK_TARGET = 1, 2                                       # flags
+RAYCAST_MAX_RAYS = 1 << 26
+_PRODUCT_DTYPES[(PRODUCT_RAYCAST, 0)] = np.int32
+_PRODUCT_DTYPES[(PRODUCT_RAYCAST, 1)] = np.float32
+
+
+class DeviceRays(object):
+    """The result of Gvom.raycast() / raycast_device(): `.result` int32 [n, 4] -- per ray {status (RAY_*), steps, voxel, unknown
+    voxels passed} -- and `.position` float32 [n, 3], where the ray stopped in world metres (NaN where it did not stop at a
+    voxel): two DeviceArrays of one product, row i = ray i.  `.origin`: the fused map's window origin in voxels; window voxel
+    (x, y, z) = (voxel % xy, voxel // xy % xy, voxel // (xy * xy)) is world voxel origin + (x, y, z).  A snapshot: later scans
+    and combines do not change it.  copy_to_host() returns (result, position) as numpy."""
+
+    def __init__(self, hold, origin):
+        self._hold = hold
+        self.product_id = hold.product_id
+        self.origin = origin
+        self.result, self.position = DeviceArray(hold, 0), DeviceArray(hold, 1)
+
+    def copy_to_host(self):
+        return self.result.copy_to_host(), self.position.copy_to_host()
 
     def release(self):
         self._hold.release()
@@ -1310,6 +1346,46 @@ class Gvom(object):
             raise ValueError("positive_ptr must be a device address")
         return self._clearance(-1, ctypes.c_void_p(int(positive_ptr)), ctypes.c_void_p(int(negative_ptr)) if negative_ptr else None, 1,
                                density_threshold, include_negative, max_distance)
+
+    # ---- ray queries (an extension; include/gvom_hip.h "ray queries") ----
+    def _raycast(self, from_ptr, K, to_ptr, n, on_device, unknown_blocks, check_target):
+        pid = ctypes.c_int64(-1)
+        org = (ctypes.c_double * 3)()
+        flags = (_RAY_UNKNOWN_BLOCKS if unknown_blocks else 0) | (_RAY_CHECK_TARGET if check_target else 0)
+        rc = self._check_args(self._lib.gvom_raycast(self._h, from_ptr, int(K), to_ptr, int(n), int(on_device), flags, org,
+                                                     ctypes.byref(pid)))
+        if rc == GVOM_NO_DATA:
+            return None
+        return DeviceRays(_ProductHold(self, PRODUCT_RAYCAST, int(pid.value)), np.array(list(org), np.float64))
+
+    def raycast(self, origins, targets, unknown_blocks=False, check_target=False):
+        """Walks the straight segments origins -> targets (world metres) through the current fused map on the GPU, with the
+        mapper's own ray rule, and returns a DeviceRays: per ray whether it is RAY_CLEAR, stopped at an occupied voxel
+        (RAY_OCCUPIED), at a never-observed one (RAY_UNKNOWN, only with unknown_blocks=True; otherwise such voxels are counted) or
+        left the window (RAY_LEFT_WINDOW); rays with a non-finite coordinate are RAY_INVALID.  check_target=True also examines the
+        voxel the target itself lies in.  targets: (n, 3); origins: (3,), (1, 3) or (n, 3).  Arrays of any float type are
+        ROUNDED TO float32 (the library's input type; a float32 start and end are what makes the voxels walked exactly the ones
+        a scan's ray marks).  None before the first combine.  A convenience route: the arrays are copied to the device; rays in
+        a coherent order (neighbours pointing the same way) are faster."""
+        t = np.ascontiguousarray(np.asarray(targets), dtype=np.float32)
+        if t.ndim != 2 or t.shape[1] != 3 or t.shape[0] < 1:
+            raise ValueError("targets must have shape (n, 3) with n >= 1, got %r" % (t.shape,))
+        n = t.shape[0]
+        if n > RAYCAST_MAX_RAYS:
+            raise ValueError("at most 2**26 rays per call, got %d" % n)
+        o = np.ascontiguousarray(np.asarray(origins), dtype=np.float32)
+        if o.shape == (3,):
+            o = o.reshape(1, 3)
+        if o.shape not in ((1, 3), (n, 3)):
+            raise ValueError("origins must have shape (3,), (1, 3) or (%d, 3), got %r" % (n, o.shape))
+        return self._raycast(_ptr(o), o.shape[0], _ptr(t), n, 0, unknown_blocks, check_target)
+
+    def raycast_device(self, from_ptr, K, to_ptr, n, unknown_blocks=False, check_target=False):
+        """The same for segments in device memory: raw device addresses of K x 3 and n x 3 float32 (C-contiguous; K is 1 or n;
+        the data must be ready when the call is made).  Enqueues and returns: no host wait."""
+        if not from_ptr or not to_ptr:
+            raise ValueError("from_ptr and to_ptr must be device addresses")
+        return self._raycast(ctypes.c_void_p(int(from_ptr)), K, ctypes.c_void_p(int(to_ptr)), n, 1, unknown_blocks, check_target)
 
     def make_debug_voxel_map(self):
         """float32[Cc, 8] rows {x, y, z, hit/total, hit, l0-l1, l1-l2, l2} (reference gvom.py:363-378) while the mapper

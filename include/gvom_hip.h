@@ -396,6 +396,63 @@ int gvom_device_product_copy(gvom_t *h, int64_t product_id, int part, void *host
 int gvom_clearance(gvom_t *h, int64_t map_set_id, const int32_t *positive, const int32_t *negative, int on_device,
                    double density_threshold, int32_t max_cells2, int flags, int64_t *product_id);
 
+/* --- ray queries (an extension: the first 3-D question a planner asks of a voxel map -- is the straight line from A to B free, and
+ * if not, where does it stop) ---------------------------------------------------------------------------------------------------
+ * gvom_raycast walks n segments through the CURRENT fused map on the GPU (k_raycast), with the mapper's own ray rule, and leaves
+ * the answers in device memory as a product (kind GVOM_PRODUCT_RAYCAST) that gvom_device_product_export / _release / _dlpack /
+ * _copy handle like the others.  The walk is read-only.  gvom_get_tuning "raycast" (read-only): 1 -- how a caller probes a
+ * library for this entry point (an addition: GVOM_ABI_VERSION stays).
+ *
+ * INPUT.  from [K][3] and to [n][3]: world metres, C-contiguous float32; K is 1 (every ray starts at from[0]) or n.
+ * on_device == 0: host memory, copied through a staging buffer of the handle before the call returns; on_device != 0: device
+ * addresses, read in place (the data must be ready when the call is made).  The call ENQUEUES on the handle's stream behind
+ * whatever produced the current fused map and returns (no host wait on the device route); later scans and combines are ordered
+ * behind the kernel and do not change the product, which is a snapshot.  origin_voxels (may be NULL) receives the fused map's
+ * window origin W in voxels: window voxel (x, y, z) is world voxel W + (x, y, z).
+ *
+ * DEFINITION, per ray i.  Every operation is rounded once, there is no FMA; res = (xy_resolution, xy_resolution, z_resolution).
+ *     a = from[K == 1 ? 0 : i];  b = to[i]                any non-finite component: {INVALID, 0, -1, 0}, position NaN
+ *     p[k] = (float)((double)a[k] / res[k]);   e[k] = (float)((double)b[k] / res[k])
+ *     increments inc[3], step length, limit: gvom.py:1105-1126 on (p, e), with the handle's sqrt typing (GVOM_FLAG_CUDA_F32_SQRT)
+ *     S = the number of steps the loop test of gvom.py:1127 / 1150 admits
+ *     unknown = 0
+ *     for j = 1 .. S:
+ *         p += inc                                        three float32 additions, gvom.py:1128-1132
+ *         v[k] = floor((double)p[k] - W[k]);  outside the window: {LEFT_WINDOW, j - 1, -1, unknown}, position NaN, stop
+ *         s = fused state of v                            what gvom_read_dense(GVOM_WHICH_FUSED) returns; a stale tile reads -1
+ *         s >= 0:    {OCCUPIED, j, v.x + v.y*xy + v.z*xy*xy, unknown}, position[k] = (float)((double)p[k] * res[k]), stop
+ *         s == -1:   unknown += 1;  with GVOM_RAY_UNKNOWN_BLOCKS: {UNKNOWN, j, voxel, unknown}, position as above, stop
+ *     with GVOM_RAY_CHECK_TARGET, after S unstopped steps: v[k] = floor((double)b[k] / res[k] - W[k])  (gvom.py:1072-1080);
+ *         outside the window: {LEFT_WINDOW, S, -1, unknown}, position NaN;  else examined as above with steps = S + 1 and
+ *         position = b (a free target: CLEAR as below)
+ *     otherwise {CLEAR, S, -1, unknown}, position NaN
+ * min_distance plays no part.  The start voxel is not examined (the mapper's ray does not mark it either).  A ray that starts
+ * outside the window is LEFT_WINDOW with 0 steps unless its first step lands inside.  For a float32-representable start and end
+ * the voxels walked are exactly those a scan's ray from a to b adds a ray pass to: the answer is consistent with the map.
+ * part 0 = int32 [n, 4] {status, steps, voxel, unknown}; part 1 = float32 [n, 3] stop position in metres; row i = ray i.
+ *
+ * GVOM_NO_DATA before the first combine.  GVOM_ERR_INVALID: a sharded handle; n < 1; K neither 1 nor n; NULL from / to /
+ * product_id; unknown flag bits.  GVOM_ERR_CAPACITY: n > 2^26, or every set of the kind is exported.
+ * Products of this kind live in the product-set pool ("device_product_sets"), sized by n: at most GVOM_MAX_PRODUCT_SETS; an
+ * unexported one goes back to the pool with the next gvom_raycast call (a smaller one is given up for one that holds n rays).
+ * gvom_get_tuning "raycast_allocations" (read-only): device allocations the entry point has made on this handle (its product
+ * sets and the staging buffer of the host route); it does not grow in steady state at a fixed n.
+ * gvom_device_product(GVOM_PRODUCT_RAYCAST) is GVOM_ERR_INVALID (this call makes them).
+ * NOT PROVIDED: sharded handles; sorting or binning of the rays by the library (results stay indexed by i; rays in a coherent
+ * order -- neighbours in the array pointing the same way -- share cache lines and finish together, and are faster); a per-ray
+ * maximum range other than the segment's own length; hit-count or density thresholds on OCCUPIED; queries against a single ring
+ * slot. */
+#define GVOM_PRODUCT_RAYCAST 6   /* part 0 int32 [n, 4] {status, steps, voxel, unknown}; part 1 float32 [n, 3] stop position, metres */
+#define GVOM_RAY_CLEAR 0
+#define GVOM_RAY_OCCUPIED 1
+#define GVOM_RAY_UNKNOWN 2
+#define GVOM_RAY_LEFT_WINDOW 3
+#define GVOM_RAY_INVALID 4
+#define GVOM_RAY_UNKNOWN_BLOCKS 1   /* flags */
+#define GVOM_RAY_CHECK_TARGET   2
+int gvom_raycast(gvom_t *h, const float *from /* [K][3] */, int64_t K, const float *to /* [n][3] */, int64_t n,
+                 int on_device, int flags, double origin_voxels[3], int64_t *product_id);
+
 /* --- one map sharded over the GPUs of a node (one rank = one process = one GPU) -------------------
  * No counterpart in the reference (it has no multi-GPU path); semantics = SURVEY 8(e):
  * the rays are data-parallel, the per-voxel accumulators (hit / total: int32 sum, min-height: f32 min)
@@ -634,6 +691,7 @@ int gvom_host_timing(gvom_t *h, double us[8]);
  * "range_image" (read-only, gvom_get_tuning): 1 when a sensor model is set (gvom_sensor_model_set), else 0.
  * "multi_origin" / "multi_origin_ran" (read-only, gvom_get_tuning): see "multi-origin scans" above.
  * "clearance_allocations" (read-only, gvom_get_tuning): see "obstacle clearance" above.
+ * "raycast" / "raycast_allocations" (read-only, gvom_get_tuning): see "ray queries" above.
  * (Test hooks are not part of this library: include/gvom_hip_test.h, lib/libgvom_hip_test.so.) */
 int gvom_set_tuning(gvom_t *h, const char *name, int value);
 /* The value the LAST scan ran with ("segs", "period", "ep_row", "prio", "interleave": what automatic resolved to).

@@ -1,5 +1,5 @@
 // gvom_export.hip -- device-resident results: map sets and product sets (DevSet) with their exports, releases and DLPack capsules,
-// gvom_combine_maps_device, the 3-D products, the clearance map and ray queries.
+// gvom_combine_maps_device, the 3-D products, the clearance map, ray queries and cost-to-go fields.
 #include "gvom_host.h"
 
 namespace gvom_host {
@@ -139,6 +139,7 @@ static size_t set_bytes(int kind, int xy, int zs, int64_t cap)
     case GVOM_PRODUCT_INFERRED_HEIGHT_CLOUD: return n2 * 12;
     case GVOM_PRODUCT_CLEARANCE: return align256(n2 * 4) + n2 * 4;
     case GVOM_PRODUCT_RAYCAST: return align256((size_t)cap * 16) + (size_t)cap * 12;
+    case GVOM_PRODUCT_COSTFIELD: return align256(n2 * 4) + align256(n2) + n2 * 2;
     }
     return 0;
 }
@@ -182,6 +183,12 @@ static bool set_part(const DevSet *s, int part, SetPart *d)
         if (part == 0) { rows(s->mem, s->cap, 4); d->code = kDLInt; }
         else if (part == 1) rows(s->mem + align256((size_t)s->cap * 16), s->cap, 3);
         else return false;
+        break;
+    case GVOM_PRODUCT_COSTFIELD:                           // [x, y] indexing, column-major, like a device map
+        if (part < 0 || part > 2) return false;
+        d->ptr = s->mem + (part ? align256((size_t)n2 * 4) : 0) + (part == 2 ? align256((size_t)n2) : 0);
+        d->shape[0] = d->shape[1] = xy; d->strides[0] = 1; d->strides[1] = xy;
+        d->code = part ? kDLUInt : kDLInt; d->bits = part == 0 ? 32 : (part == 1 ? 8 : 16);
         break;
     default: return false;
     }
@@ -412,6 +419,7 @@ VIS int gvom_device_product(gvom_t *h, int kind, int64_t max_rows, int64_t *prod
     *product_id = -1;
     if (kind == GVOM_PRODUCT_CLEARANCE) { h->err = "gvom_device_product: a clearance product is made by gvom_clearance"; return GVOM_ERR_INVALID; }
     if (kind == GVOM_PRODUCT_RAYCAST) { h->err = "gvom_device_product: a raycast product is made by gvom_raycast"; return GVOM_ERR_INVALID; }
+    if (kind == GVOM_PRODUCT_COSTFIELD) { h->err = "gvom_device_product: a cost field is made by gvom_cost_to_go"; return GVOM_ERR_INVALID; }
     if (kind < 1 || kind > GVOM_N_PRODUCT_KINDS) { h->err = "gvom_device_product: unknown product kind"; return GVOM_ERR_INVALID; }
     if (h->sharded) { h->err = "gvom_device_product: sharded handles are not supported"; return GVOM_ERR_INVALID; }
     if (kind == GVOM_PRODUCT_VOXEL_CLOUD) stats_demand(h);                  // a read of the statistics, like gvom_debug_voxel_map
@@ -642,6 +650,151 @@ VIS int gvom_raycast(gvom_t *h, const float *from, int64_t K, const float *to, i
     set->id = ++h->pset_seq;
     *product_id = set->id;
     for (int k = 0; origin_voxels && k < 3; ++k) origin_voxels[k] = (double)F.origin[k];
+    return GVOM_OK;
+}
+// ---- cost-to-go fields (gvom_cost_to_go) ------------------------------------------------------------------------------------------
+// The navigation function of a cost map -- a caller's, or the one k_travcost builds from a device map set -- as a product of kind
+// GVOM_PRODUCT_COSTFIELD.  The kernels (gvom_costfield.hip) run on the handle's stream behind the combine that wrote the set, and
+// whatever recycles the set later runs behind them.  Unlike the other product calls this one WAITS: rounds of k_ctg_relax are
+// enqueued a batch at a time, the batch's per-round counters come back through pinned memory, and the first round that flagged no
+// tile ends the solve (the rounds enqueued behind it found nothing to do).
+VIS int gvom_cost_to_go(gvom_t *h, int64_t map_set_id, const gvom_ctg_params *params, const int32_t *cost, int on_device,
+                        const int32_t *goals, int64_t n_goals, int32_t max_cost, int32_t max_rounds, int flags,
+                        int64_t *product_id, int64_t info[4])
+{
+    if (!h || !product_id) return GVOM_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(h->mu);
+    *product_id = -1;
+    for (int k = 0; info && k < 4; ++k) info[k] = 0;
+    if (h->sharded) { h->err = "gvom_cost_to_go: sharded handles are not supported"; return GVOM_ERR_INVALID; }
+    if (flags & ~(GVOM_CTG_NO_NEGATIVE | GVOM_CTG_UNKNOWN_BLOCKS)) { h->err = "gvom_cost_to_go: unknown flag bits"; return GVOM_ERR_INVALID; }
+    if (map_set_id >= 0 && cost) { h->err = "gvom_cost_to_go: give a map set id or a cost map, not both"; return GVOM_ERR_INVALID; }
+    if (map_set_id < 0 && !cost) { h->err = "gvom_cost_to_go: give a map set id or a cost map"; return GVOM_ERR_INVALID; }
+    if (map_set_id >= 0 && !params) { h->err = "gvom_cost_to_go: a map set needs the cost parameters"; return GVOM_ERR_INVALID; }
+    if (!goals || n_goals < 1 || n_goals > GVOM_CTG_MAX_GOALS) { h->err = "gvom_cost_to_go: between 1 and 65536 goals"; return GVOM_ERR_INVALID; }
+    if (max_cost < 0 || max_cost > GVOM_CTG_MAX_COST) { h->err = "gvom_cost_to_go: max_cost outside 0 .. 2^30"; return GVOM_ERR_INVALID; }
+    if (max_rounds < 0) { h->err = "gvom_cost_to_go: max_rounds must not be negative"; return GVOM_ERR_INVALID; }
+    const int xy = h->prm.xy_size;
+    if (xy > GVOM_CLEARANCE_MAX_XY) { h->err = "gvom_cost_to_go: maps of more than 4096 cells a side are not supported"; return GVOM_ERR_CAPACITY; }
+    const size_t n2 = (size_t)xy * xy;
+    for (int64_t k = 0; k < 2 * n_goals; ++k)
+        if (goals[k] < 0 || goals[k] >= xy) { h->err = "gvom_cost_to_go: a goal lies outside the window"; return GVOM_ERR_INVALID; }
+    CtgCostParams C;
+    memset(&C, 0, sizeof C);
+    DevSet *m = nullptr;
+    if (map_set_id >= 0) {
+        const gvom_ctg_params &p = *params;
+        const bool ok = p.density_threshold == p.density_threshold && p.inflation_cells2 >= 0 && p.base >= 1 &&
+                        p.soft_weight >= 0 && p.soft_weight <= 65535 && p.unknown_cost >= 0 && p.unknown_cost <= 65535 &&
+                        p.rough_weight >= 0 && p.rough_weight <= 65535 &&
+                        (p.rough_weight == 0 || (isfinite(p.min_roughness) && isfinite(p.max_roughness) && p.max_roughness > p.min_roughness));
+        if (!ok) { h->err = "gvom_cost_to_go: bad cost parameters (NaN threshold, base < 1, a weight outside 0 .. 65535, a negative inflation, or an empty / non-finite roughness range)"; return GVOM_ERR_INVALID; }
+        m = find_set(h->dsets, map_set_id);
+        if (!m) { h->err = "unknown or stale device map set id"; return GVOM_ERR_INVALID; }
+        C.density_threshold = p.density_threshold; C.min_roughness = p.min_roughness; C.max_roughness = p.max_roughness;
+        C.inflation_cells2 = p.inflation_cells2; C.base = p.base; C.soft_weight = p.soft_weight; C.unknown_cost = p.unknown_cost;
+        C.rough_weight = p.rough_weight;
+        C.use_negative = (flags & GVOM_CTG_NO_NEGATIVE) ? 0 : 1; C.unknown_blocks = (flags & GVOM_CTG_UNKNOWN_BLOCKS) ? 1 : 0;
+    } else if (!on_device) {
+        for (size_t k = 0; k < n2; ++k)
+            if (cost[k] < 0 || cost[k] > 65535) { h->err = "gvom_cost_to_go: a host cost map holds a value outside 0 .. 65535"; return GVOM_ERR_INVALID; }
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    const int kind = GVOM_PRODUCT_COSTFIELD;
+    DevSet *set = set_recycle(h->psets, kind, set_bytes(kind, xy, 0, 0));
+    if (!set) {
+        int n = 0;
+        for (DevSet *s : h->psets) n += s->kind == kind;
+        if (n >= GVOM_MAX_PRODUCT_SETS) {
+            h->err = "gvom_cost_to_go: all 4 device product sets of this kind are exported; release some (gvom_device_product_release, or drop the tensors)";
+            return GVOM_ERR_CAPACITY;
+        }
+        const int rc0 = set_new(h, h->psets, kind, set_bytes(kind, xy, 0, 0), &set);
+        if (rc0) return rc0;
+        ++h->ctg_allocs;
+    }
+    int rc;
+    const int nt = gvom_ctg_tiles(xy), ntiles = nt * nt;
+    const size_t flags_off = 256, goals_off = flags_off + align256((size_t)2 * ntiles * 4);
+    if (!h->ctg_work.p) {
+        if ((rc = ensure(h, h->ctg_work, goals_off + (size_t)GVOM_CTG_MAX_GOALS * 8))) return rc;
+        ++h->ctg_allocs;
+    }
+    if (!h->ctg_pin) HIPCHK(h, hipHostMalloc((void **)&h->ctg_pin, 256, hipHostMallocDefault));
+    uint32_t *cnt = (uint32_t *)h->ctg_work.p;
+    uint32_t *fl = (uint32_t *)((char *)h->ctg_work.p + flags_off);
+    int32_t *gdev = (int32_t *)((char *)h->ctg_work.p + goals_off);
+    HIPCHK(h, join_second_stream(h));
+    const int32_t *cost32 = nullptr;
+    if (map_set_id < 0 && !on_device) {                                     // a host cost map: staged
+        if (!h->ctg_stage.p) {
+            if ((rc = ensure(h, h->ctg_stage, n2 * 4))) return rc;
+            ++h->ctg_allocs;
+        }
+        HIPCHK(h, hipMemcpyAsync(h->ctg_stage.p, cost, n2 * 4, hipMemcpyHostToDevice, h->stream));
+        cost32 = (const int32_t *)h->ctg_stage.p;
+    } else if (map_set_id < 0) cost32 = cost;
+    const size_t clr_g = align256(gvom_clearance_scratch_bytes(xy)), clr_map = align256(n2 * 4);
+    if (m && C.inflation_cells2 > 0 && !h->ctg_clr.p) {
+        if ((rc = ensure(h, h->ctg_clr, clr_g + 2 * clr_map))) return rc;
+        ++h->ctg_allocs;
+    }
+    HIPCHK(h, hipMemcpyAsync(gdev, goals, (size_t)n_goals * 8, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemsetAsync(cnt, 0, 256, h->stream));
+    if ((rc = set_wait_releases(h, set))) return rc;
+    SetPart d0, d1, d2;
+    set_part(set, 0, &d0); set_part(set, 1, &d1); set_part(set, 2, &d2);
+    int32_t *D = (int32_t *)d0.ptr;
+    uint16_t *c16 = (uint16_t *)d2.ptr;
+    if (m) {
+        SetPart mp, mn, mv, mr;
+        set_part(m, 0, &mp); set_part(m, 1, &mn); set_part(m, 2, &mv); set_part(m, 3, &mr);
+        const int32_t *cd2 = nullptr;
+        if (C.inflation_cells2 > 0) {
+            char *q = (char *)h->ctg_clr.p;
+            HIPCHK(h, gvom_launch_clearance(h->stream, xy, h->prm.xy_resolution, (const int32_t *)mp.ptr,
+                                            C.use_negative ? (const int32_t *)mn.ptr : nullptr, C.density_threshold, C.inflation_cells2,
+                                            (uint16_t *)q, (float *)(q + clr_g), (int32_t *)(q + clr_g + clr_map)));
+            cd2 = (const int32_t *)(q + clr_g + clr_map);
+        }
+        HIPCHK(h, gvom_launch_travcost(h->stream, xy, (const int32_t *)mp.ptr, (const int32_t *)mn.ptr, (const int32_t *)mv.ptr,
+                                       (const double *)mr.ptr, cd2, C, c16));
+    }
+    HIPCHK(h, gvom_launch_ctg_seed(h->stream, xy, cost32, c16, D, fl, gdev, (int)n_goals, cnt + CTG_CNT_SEEDED));
+    const int32_t cap = max_cost == 0 ? GVOM_CTG_MAX_COST : max_cost;
+    const int inner = h->tune_ctg_inner > 0 ? h->tune_ctg_inner : 256;
+    const int batch = h->tune_ctg_batch > 0 ? h->tune_ctg_batch : 8;
+    // by induction over the tile crossings of a shortest path the solve ends after at most (crossings + 1) rounds of tiles that
+    // reach their fixed point; the limit below is beyond anything xy <= 4096 can need and only keeps this loop finite
+    const int64_t limit = max_rounds > 0 ? (int64_t)max_rounds : (int64_t)1 << 22;
+    int64_t rounds = 0, tiles = 0;
+    bool converged = false;
+    while (!converged && rounds < limit) {
+        const int nb = (int)std::min<int64_t>(batch, limit - rounds);
+        if (rounds) HIPCHK(h, hipMemsetAsync(cnt, 0, 2 * GVOM_CTG_MAX_BATCH * 4, h->stream));
+        for (int r = 0; r < nb; ++r) {
+            const int64_t k = rounds + r;
+            HIPCHK(h, gvom_launch_ctg_relax(h->stream, xy, c16, D, fl + (k & 1) * ntiles, fl + ((k + 1) & 1) * ntiles, cnt + r,
+                                            cnt + CTG_CNT_RELAXED + r, cap, inner));
+        }
+        HIPCHK(h, hipMemcpyAsync(h->ctg_pin, cnt, 2 * GVOM_CTG_MAX_BATCH * 4, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        int ran = nb;
+        for (int r = 0; r < nb; ++r) {
+            tiles += h->ctg_pin[CTG_CNT_RELAXED + r];
+            if (h->ctg_pin[r] == 0) { converged = true; ran = r + 1; break; }
+        }
+        rounds += ran;
+    }
+    HIPCHK(h, gvom_launch_ctg_dirs(h->stream, xy, c16, D, (uint8_t *)d1.ptr, cnt + CTG_CNT_REACHED));
+    HIPCHK(h, hipEventRecord(set->ready, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->ctg_pin, cnt, 256, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (!converged && max_rounds == 0) { h->err = "gvom_cost_to_go: the field did not settle"; return GVOM_ERR_HIP; }
+    h->ctg_last_tiles = (int)std::min<int64_t>(tiles, INT32_MAX);
+    if (info) { info[0] = converged ? 1 : 0; info[1] = rounds; info[2] = h->ctg_pin[CTG_CNT_REACHED]; info[3] = h->ctg_pin[CTG_CNT_SEEDED]; }
+    set->id = ++h->pset_seq;
+    *product_id = set->id;
     return GVOM_OK;
 }
 }  // extern "C"

@@ -73,6 +73,8 @@ struct Fused {
 //   clearance        xy*xy floats (metres), then xy*xy int32 (squared cells) at the next 256-byte boundary, both [y][x]
 //   raycast          cap x 4 int32 {status, steps, voxel, unknown}, then cap x 3 floats (stop position) at the next 256-byte
 //                    boundary; cap = the rays of the call that wrote it
+//   cost field       xy*xy int32 (cost to go), then xy*xy uint8 (direction), then xy*xy uint16 (cell costs), each at the next
+//                    256-byte boundary, all [y][x]
 struct DevSet {
     char *mem = nullptr;
     size_t bytes = 0;
@@ -89,6 +91,12 @@ struct DevSet {
 #define GVOM_MAX_DEVICE_SETS 8
 #define GVOM_N_PRODUCT_KINDS 4                  // the kinds gvom_device_product makes (clearance and raycast products have entry points of their own)
 #define GVOM_RAYCAST_MAX_RAYS ((int64_t)1 << 26)
+#define GVOM_CTG_MAX_GOALS 65536
+#define GVOM_CTG_MAX_BATCH 16                   // rounds enqueued between two looks at the counters: at most
+// ctg_work's counters (uint32): [r] tiles that flagged any in round r of the batch, [16 + r] tiles that ran, [32] reached cells, [33] goals seeded
+#define CTG_CNT_RELAXED 16
+#define CTG_CNT_REACHED 32
+#define CTG_CNT_SEEDED 33
 // DevSet::exports / rel* / orphan: a DLPack deleter runs on whatever thread frees the consumer's tensor, without the handle
 extern std::mutex g_set_mu;                               // (gvom_export.hip)
 }  // namespace gvom_host
@@ -313,6 +321,16 @@ struct gvom_handle {
     // buffer and its product sets: gvom_get_tuning "raycast_allocations")
     Buf rq_stage;
     int rq_allocs = 0;
+    // COST-TO-GO FIELDS (gvom_cost_to_go): ctg_work = 256 bytes of counters (CTG_CNT_* above), the two halves of the tiles' activity
+    // flags, then the staged goals (65536 x 2 int32); ctg_stage = the staging copy of a caller's host cost map; ctg_clr = what
+    // gvom_launch_clearance needs for the inflation of the map-set route (its row scratch, a distance map nobody reads, d2).  Each
+    // is allocated by the first call that needs it; ctg_allocs counts those and the entry point's product sets (gvom_get_tuning
+    // "cost_to_go_allocations").  ctg_pin: the pinned copy of the counters the host loop reads.
+    Buf ctg_work, ctg_stage, ctg_clr;
+    uint32_t *ctg_pin = nullptr;
+    int ctg_allocs = 0;
+    int tune_ctg_inner = 0, tune_ctg_batch = 0;         // gvom_set_tuning "cost_to_go_inner" / "cost_to_go_batch" (0: the defaults)
+    int ctg_last_tiles = 0;                             // tile relaxations of the last call (gvom_get_tuning "cost_to_go_tiles")
 };
 
 namespace gvom_host {

@@ -292,6 +292,27 @@ hipError_t gvom_launch_raycast(hipStream_t s, const ScanParams &P, const RayQuer
 size_t gvom_clearance_scratch_bytes(int xy);
 hipError_t gvom_launch_clearance(hipStream_t s, int xy, double res, const int32_t *pos, const int32_t *neg, double thr,
                                  int32_t max_cells2, uint16_t *g, float *out_dist, int32_t *out_d2);
+// cost-to-go fields (gvom_costfield.hip; include/gvom_hip.h "cost-to-go fields" defines the result).  Every map is [y][x], xy x xy.
+// travcost: the uint16 cost map c (0 = blocked) from the int32 positive / negative / visibility maps, the f64 roughness map and
+// the clearance d2 (nullptr: no inflation).  seed: c from cost32 (clamped into 0..65535; nullptr: c is there already), D =
+// INT32_MAX, both halves of flags (2 * gvom_ctg_tiles(xy)^2 words) cleared, then D = 0 at the G goals ([G][2] device int32, inside
+// the window) that lie on unblocked cells, the tiles that hold or border them flagged in the first half, *seeded += their number.  relax: one round --
+// the tiles flagged in fcur relax to their local fixed point (or for `inner` sweeps) accepting nothing above max_cost, clear their
+// flag and flag in fnext the tiles that have to look again; *relaxed += tiles that ran, *activated += tiles that flagged any.
+// dirs: the direction codes from D and c; *reached += cells with D < INT32_MAX.
+struct CtgCostParams {
+    double density_threshold, min_roughness, max_roughness;
+    int32_t inflation_cells2, base, soft_weight, unknown_cost, rough_weight;
+    int32_t use_negative, unknown_blocks;
+};
+int gvom_ctg_tiles(int xy);
+hipError_t gvom_launch_travcost(hipStream_t s, int xy, const int32_t *pos, const int32_t *neg, const int32_t *vis, const double *rough,
+                                const int32_t *d2, const CtgCostParams &C, uint16_t *c);
+hipError_t gvom_launch_ctg_seed(hipStream_t s, int xy, const int32_t *cost32, uint16_t *c, int32_t *D, uint32_t *flags,
+                                const int32_t *goals, int G, uint32_t *seeded);
+hipError_t gvom_launch_ctg_relax(hipStream_t s, int xy, const uint16_t *c, int32_t *D, uint32_t *fcur, uint32_t *fnext,
+                                 uint32_t *activated, uint32_t *relaxed, int32_t max_cost, int inner);
+hipError_t gvom_launch_ctg_dirs(hipStream_t s, int xy, const uint16_t *c, const int32_t *D, uint8_t *dir, uint32_t *reached);
 // storage order [sy][sx] -> reference order [x][y] (window coordinates)
 hipError_t gvom_launch_unwrap_f64(hipStream_t s, int xy, int om0, int om1, const double *in, int in_stride, double *out_xy);
 hipError_t gvom_launch_posdens(hipStream_t s, const Map2dParams &P, const int32_t *fstate,

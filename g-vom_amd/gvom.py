@@ -160,6 +160,8 @@ ABI = [
     ("gvom_device_product_copy", _I, [_P, _I64, _I, _P]),
     ("gvom_clearance", _I, [_P, _I64, _P, _P, _I, ctypes.c_double, ctypes.c_int32, _I, ctypes.POINTER(_I64)]),
     ("gvom_raycast", _I, [_P, _P, _I64, _P, _I64, _I, _I, _DP, ctypes.POINTER(_I64)]),
+    ("gvom_cost_to_go", _I, [_P, _I64, _P, _P, _I, _P, _I64, ctypes.c_int32, ctypes.c_int32, _I, ctypes.POINTER(_I64),
+                             ctypes.POINTER(_I64)]),
     ("gvom_set_profiling", _I, [_P, _I]),
     ("gvom_host_timing", _I, [_P, ctypes.POINTER(ctypes.c_double * 8)]),
     ("gvom_set_tuning", _I, [_P, ctypes.c_char_p, _I]),
@@ -462,6 +464,24 @@ class DeviceMaps(object):
         g = self._owner
         return g._clearance(self.set_id, None, None, 0, density_threshold, include_negative, max_distance)
 
+    def cost_to_go(self, goals, goals_in_cells=False, inflation_radius=None, density_threshold=50, include_negative=True,
+                   unknown="free", base=1, soft_weight=0, rough_weight=0, roughness_range=None, max_cost=None, max_rounds=0):
+        """The navigation function of this set's maps towards `goals`: from every cell the cheapest 8-connected way to a goal
+        (`.cost`) and the first step of it (`.direction`), as a DeviceCostField computed on the GPU behind the combine that wrote
+        the set.  The call waits for the field.  goals: (G, 2) world metres (x, y) -- or window cells with goals_in_cells=True; a
+        goal outside the window raises ValueError, one on a blocked cell seeds nothing.  A cell is blocked where positive >
+        density_threshold, (include_negative and) negative > 0, within inflation_radius metres of such a cell (None: no
+        inflation; as clearance()'s max_distance), or -- unknown="blocked" -- never observed.  Elsewhere it costs base +
+        soft_weight * positive + (an int `unknown`: that much where never observed) + rough_weight * q, at most 65535, with q =
+        0 .. 100 the roughness's place in roughness_range = (min, max).  max_cost: cells dearer than that read CTG_UNREACHED.
+        max_rounds > 0 stops after that many rounds (`.converged` says whether the field is final).  include/gvom_hip.h
+        "cost-to-go fields" has the definition."""
+        g = self._owner
+        cells = _ctg_goals(goals, g.xy_size, None if goals_in_cells else (g.xy_resolution, self.origin))
+        params, flags = _ctg_params(g.xy_resolution, inflation_radius, density_threshold, include_negative, unknown, base, soft_weight,
+                                    rough_weight, roughness_range)
+        return g._cost_to_go(self.set_id, params, None, 0, cells, _ctg_max_cost(max_cost), _ctg_max_rounds(max_rounds), flags)
+
     def release(self):
         if self.__dict__.get("_held"):
             self._held = False
@@ -691,6 +711,166 @@ class DeviceRays(object):
 
     def copy_to_host(self):
         return self.result.copy_to_host(), self.position.copy_to_host()
+
+    def release(self):
+        self._hold.release()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.release()
+        return False
+
+
+PRODUCT_COSTFIELD = 7                     # GVOM_PRODUCT_COSTFIELD: made by gvom_cost_to_go, not by gvom_device_product
+CTG_UNREACHED = 2147483647                # GVOM_CTG_UNREACHED: cost where a cell is blocked, cut off, or dearer than max_cost
+CTG_MAX_COST = 1 << 30                    # GVOM_CTG_MAX_COST
+CTG_GOAL, CTG_UNSETTLED, CTG_NONE = 8, 254, 255          # GVOM_CTG_*: direction codes beside the eight steps 0 .. 7
+CTG_STEPS = ((1, 0), (1, 1), (0, 1), (-1, 1), (-1, 0), (-1, -1), (0, -1), (1, -1))   # (dx, dy) of direction code k
+CTG_MAX_GOALS = 65536
+_CTG_NO_NEGATIVE, _CTG_UNKNOWN_BLOCKS = 1, 2             # flags
+_PRODUCT_DTYPES[(PRODUCT_COSTFIELD, 0)] = np.int32
+_PRODUCT_DTYPES[(PRODUCT_COSTFIELD, 1)] = np.uint8
+_PRODUCT_DTYPES[(PRODUCT_COSTFIELD, 2)] = np.uint16
+
+
+class GvomCtgParams(ctypes.Structure):
+    """gvom_ctg_params"""
+    _fields_ = [("density_threshold", ctypes.c_double), ("min_roughness", ctypes.c_double), ("max_roughness", ctypes.c_double),
+                ("inflation_cells2", ctypes.c_int32), ("base", ctypes.c_int32), ("soft_weight", ctypes.c_int32),
+                ("unknown_cost", ctypes.c_int32), ("rough_weight", ctypes.c_int32)]
+
+
+def world_to_cells(points, xy_resolution, origin):
+    """(G, 2) world metres -> window cells of a map whose window corner is at `origin` (world metres, a multiple of the
+    resolution): floor(p / xy_resolution) - round(origin / xy_resolution), per axis in float64."""
+    p = np.asarray(points, np.float64)
+    o = np.asarray(origin, np.float64)[:2]
+    return (np.floor(p / float(xy_resolution)) - np.round(o / float(xy_resolution))).astype(np.int64)
+
+
+def _ctg_goals(goals, xy_size, frame):
+    """goals -> C-contiguous int32 (G, 2) window cells; frame = (xy_resolution, origin) for goals in world metres, None for cells"""
+    a = np.asarray(goals)
+    if a.ndim == 1 and a.shape[0] == 2:
+        a = a.reshape(1, 2)
+    if a.ndim != 2 or a.shape[1] != 2 or not 1 <= a.shape[0] <= CTG_MAX_GOALS:
+        raise ValueError("goals must have shape (G, 2) with 1 <= G <= %d, got %r" % (CTG_MAX_GOALS, a.shape))
+    if a.dtype.kind not in "iuf":
+        raise ValueError("goals must be numbers, got dtype %s" % a.dtype)
+    if a.dtype.kind == "f" and not np.isfinite(a).all():
+        raise ValueError("goals must be finite")
+    if frame is not None:
+        a = world_to_cells(a, *frame)
+    elif a.dtype.kind == "f":
+        if (a != np.floor(a)).any():
+            raise ValueError("goals in cells must be whole numbers")
+        a = a.astype(np.int64)
+    if ((a < 0) | (a >= xy_size)).any():
+        bad = a[((a < 0) | (a >= xy_size)).any(axis=1)][0]
+        raise ValueError("a goal lies outside the window: cell (%d, %d) of a %d x %d map" % (bad[0], bad[1], xy_size, xy_size))
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def _ctg_max_cost(max_cost):
+    if max_cost is None:
+        return 0
+    if isinstance(max_cost, float) and max_cost != max_cost:
+        raise ValueError("max_cost must be None or an integer in 1 .. 2**30, got %r" % (max_cost,))
+    m = int(max_cost)
+    if m != max_cost or not 1 <= m <= CTG_MAX_COST:
+        raise ValueError("max_cost must be None or an integer in 1 .. 2**30, got %r" % (max_cost,))
+    return m
+
+
+def _ctg_max_rounds(max_rounds):
+    r = int(max_rounds)
+    if r != max_rounds or not 0 <= r < 2 ** 31:
+        raise ValueError("max_rounds must be an integer >= 0 (0: until converged), got %r" % (max_rounds,))
+    return r
+
+
+def _ctg_weight(name, v, lo=0):
+    hi = 65535 if lo == 0 else 2 ** 31 - 1
+    try:
+        ok = int(v) == v and lo <= int(v) <= hi
+    except (TypeError, ValueError, OverflowError):       # (a NaN, an infinity, not a number)
+        ok = False
+    if not ok:
+        raise ValueError("%s must be an integer in %d .. %d, got %r" % (name, lo, hi, v))
+    return int(v)
+
+
+def _ctg_params(xy_resolution, inflation_radius, density_threshold, include_negative, unknown, base, soft_weight, rough_weight,
+                roughness_range):
+    """the keyword arguments of DeviceMaps.cost_to_go -> (GvomCtgParams, flags); ValueError for what the library would refuse"""
+    P = GvomCtgParams()
+    P.density_threshold = _clearance_threshold(density_threshold)
+    try:
+        P.inflation_cells2 = _clearance_cap(inflation_radius, xy_resolution)
+    except ValueError as e:
+        raise ValueError(str(e).replace("max_distance", "inflation_radius"))
+    flags = 0 if include_negative else _CTG_NO_NEGATIVE
+    if unknown == "blocked":
+        flags |= _CTG_UNKNOWN_BLOCKS
+    elif unknown != "free":
+        if isinstance(unknown, str):
+            raise ValueError('unknown must be "free", "blocked" or an integer cost in 0 .. 65535, got %r' % (unknown,))
+        P.unknown_cost = _ctg_weight("unknown", unknown)
+    P.base = _ctg_weight("base", base, 1)
+    P.soft_weight = _ctg_weight("soft_weight", soft_weight)
+    P.rough_weight = _ctg_weight("rough_weight", rough_weight)
+    if P.rough_weight:
+        if roughness_range is None or len(roughness_range) != 2:
+            raise ValueError("rough_weight > 0 needs roughness_range = (min, max)")
+        lo, hi = float(roughness_range[0]), float(roughness_range[1])
+        if not (math.isfinite(lo) and math.isfinite(hi) and hi > lo):
+            raise ValueError("roughness_range must be finite with max > min, got %r" % (roughness_range,))
+        P.min_roughness, P.max_roughness = lo, hi
+    return P, flags
+
+
+class DeviceCostField(object):
+    """The result of DeviceMaps.cost_to_go() / Gvom.cost_to_go_of() / cost_to_go_of_device(): `.cost` int32 [xy, xy], the cheapest
+    way from each cell to a goal (CTG_UNREACHED where there is none), `.direction` uint8 [xy, xy], the first step of it (code k
+    = CTG_STEPS[k]; CTG_GOAL at a goal, CTG_NONE where unreached, CTG_UNSETTLED only in a field that is not final) and
+    `.cell_cost` uint16 [xy, xy], the cost map the solver used (0 = blocked) -- three DeviceArrays of one product, [x, y]-indexed
+    with strides (1, xy) like a DeviceMap.  `.converged`, `.rounds`, `.reached` (cells with a finite cost) and `.goals_seeded` (goals
+    on unblocked cells) describe the solve.  A snapshot: later scans and combines do not change it.  copy_to_host() returns (cost,
+    direction, cell_cost) as Fortran-ordered numpy [x, y]."""
+
+    def __init__(self, hold, info):
+        self._hold = hold
+        self.product_id = hold.product_id
+        self.cost, self.direction, self.cell_cost = DeviceArray(hold, 0), DeviceArray(hold, 1), DeviceArray(hold, 2)
+        self.converged, self.rounds, self.reached, self.goals_seeded = bool(info[0]), int(info[1]), int(info[2]), int(info[3])
+        self._host = None
+
+    def copy_to_host(self):
+        return self.cost.copy_to_host(), self.direction.copy_to_host(), self.cell_cost.copy_to_host()
+
+    def path_from(self, cell):
+        """The cells from `cell` = (x, y) to a goal, both included, following `.direction` on a host copy (made once); None where
+        the cell is unreached.  RuntimeError on CTG_UNSETTLED (a field that stopped before it converged)."""
+        if self._host is None:
+            self._host = self.direction.copy_to_host()
+        d = self._host
+        x, y = int(cell[0]), int(cell[1])
+        if not (0 <= x < d.shape[0] and 0 <= y < d.shape[1]):
+            raise ValueError("cell (%d, %d) lies outside the window" % (x, y))
+        path = [(x, y)]
+        for _ in range(d.size):
+            k = int(d[x, y])
+            if k == CTG_GOAL:
+                return path
+            if k == CTG_NONE:
+                return None
+            if k >= 8:
+                raise RuntimeError("cell (%d, %d) is unsettled: the field stopped before it converged" % (x, y))
+            x, y = x + CTG_STEPS[k][0], y + CTG_STEPS[k][1]
+            path.append((x, y))
+        raise RuntimeError("the directions do not lead to a goal")
 
     def release(self):
         self._hold.release()
@@ -1386,6 +1566,41 @@ class Gvom(object):
         if not from_ptr or not to_ptr:
             raise ValueError("from_ptr and to_ptr must be device addresses")
         return self._raycast(ctypes.c_void_p(int(from_ptr)), K, ctypes.c_void_p(int(to_ptr)), n, 1, unknown_blocks, check_target)
+
+    # ---- cost-to-go fields (an extension; include/gvom_hip.h "cost-to-go fields") ----
+    def _cost_to_go(self, set_id, params, cost_ptr, on_device, cells, max_cost, max_rounds, flags):
+        pid = ctypes.c_int64(-1)
+        info = (_I64 * 4)()
+        self._check(self._lib.gvom_cost_to_go(self._h, int(set_id), ctypes.byref(params) if params is not None else None, cost_ptr,
+                                              int(on_device), _ptr(cells), cells.shape[0], max_cost, max_rounds, flags,
+                                              ctypes.byref(pid), info))
+        return DeviceCostField(_ProductHold(self, PRODUCT_COSTFIELD, int(pid.value)), list(info))
+
+    def cost_to_go_of(self, cost, goals, max_cost=None, max_rounds=0):
+        """DeviceMaps.cost_to_go() of a cost map of the caller's: a numpy [x, y] array of shape (xy_size, xy_size) in any memory
+        order, integers in 0 .. 65535 (0 = blocked); goals: (G, 2) window cells.  Needs no scan and no combine.  A convenience
+        route: the map is copied to the device."""
+        a = np.asarray(cost)
+        if a.shape != (self.xy_size, self.xy_size):
+            raise ValueError("cost must have shape (%d, %d), got %r" % (self.xy_size, self.xy_size, a.shape))
+        if a.dtype.kind == "f" and not np.isfinite(a).all():
+            raise ValueError("cost must be finite")
+        if a.dtype.kind not in "iuf" or (a.dtype.kind == "f" and (a != np.floor(a)).any()):
+            raise ValueError("cost must hold whole numbers")
+        if a.size and (a.min() < 0 or a.max() > 65535):
+            raise ValueError("cost must lie in 0 .. 65535 (0 = blocked)")
+        cells = _ctg_goals(goals, self.xy_size, None)
+        c = np.asfortranarray(a, dtype=np.int32)                        # x fastest
+        return self._cost_to_go(-1, None, _ptr(c), 0, cells, _ctg_max_cost(max_cost), _ctg_max_rounds(max_rounds), 0)
+
+    def cost_to_go_of_device(self, cost_ptr, goals, max_cost=None, max_rounds=0):
+        """The same for a cost map in device memory (the raw device address of xy_size*xy_size int32, cell (x, y) at
+        [y*xy_size + x]; the data must be ready when the call is made).  Values outside 0 .. 65535 are clamped into the range."""
+        if not cost_ptr:
+            raise ValueError("cost_ptr must be a device address")
+        cells = _ctg_goals(goals, self.xy_size, None)
+        return self._cost_to_go(-1, None, ctypes.c_void_p(int(cost_ptr)), 1, cells, _ctg_max_cost(max_cost),
+                                _ctg_max_rounds(max_rounds), 0)
 
     def make_debug_voxel_map(self):
         """float32[Cc, 8] rows {x, y, z, hit/total, hit, l0-l1, l1-l2, l2} (reference gvom.py:363-378) while the mapper

@@ -453,6 +453,95 @@ int gvom_clearance(gvom_t *h, int64_t map_set_id, const int32_t *positive, const
 int gvom_raycast(gvom_t *h, const float *from /* [K][3] */, int64_t K, const float *to /* [n][3] */, int64_t n,
                  int on_device, int flags, double origin_voxels[3], int64_t *product_id);
 
+/* --- cost-to-go fields (an extension: the global question of a ground-vehicle planner -- from every cell, what does it cost to reach
+ * the goal, and which way do I step) ------------------------------------------------------------------------------------------------
+ * gvom_cost_to_go computes, on the GPU, the navigation function (cost-to-go field, wavefront) of a 2-D cost map towards a set of
+ * goal cells and leaves it in device memory as a product (kind GVOM_PRODUCT_COSTFIELD) that gvom_device_product_export / _release /
+ * _dlpack / _copy handle like the others.  gvom_get_tuning "cost_to_go" (read-only): 1 -- how a caller probes a library for this
+ * entry point (an addition: GVOM_ABI_VERSION stays).  All arithmetic is integer: the result is exact.
+ *
+ * DEFINITION.
+ * COST MAP   c[x, y]: int32 in 0 .. 65535, cell (x, y) at [y*xy_size + x] like every device map.  0 = the cell is BLOCKED;
+ *            1 .. 65535 = the price of the cell.
+ * GRAPH      8-connected, undirected.  Direction codes k = 0 .. 7 have the offsets (dx, dy) = (1,0) (1,1) (0,1) (-1,1) (-1,0) (-1,-1)
+ *            (0,-1) (1,-1); odd k is a diagonal.  A step from u to its neighbour v is ADMISSIBLE iff v lies inside the window,
+ *            c[u] > 0 and c[v] > 0, and -- for a diagonal -- both cells that share the corner, (u.x + dx, u.y) and (u.x, u.y + dy),
+ *            are unblocked: no corner is cut.  The step weighs w(u, v) = K * (c[u] + c[v]), K = 5 straight, K = 7 diagonal (10 and
+ *            14 between free cells of cost 1; at most 7 * 131070 < 2^20).
+ * GOALS      n_goals >= 1 cells (x, y) in window coordinates.  A goal on a blocked cell seeds nothing; a goal outside the window
+ *            is GVOM_ERR_INVALID.
+ * FIELD      D[u] = the minimum over all admissible paths from u to any seeded goal of the sum of the step weights; 0 at a seeded
+ *            goal.  1 <= max_cost <= 2^30 (GVOM_CTG_MAX_COST; 0 means 2^30).  D[u] = GVOM_CTG_UNREACHED (INT32_MAX) where u is
+ *            blocked, has no path, or its minimum exceeds max_cost.  A candidate is accepted only if it is <= max_cost, so every
+ *            intermediate stays below 2^30 + 2^20: nothing can overflow int32.
+ * DIRECTION  dir[u] = the smallest k whose neighbour v is admissible with D[v] + w(u, v) == D[u]; GVOM_CTG_GOAL (8) where
+ *            D[u] == 0; GVOM_CTG_NONE (255) where D[u] is unreached; GVOM_CTG_UNSETTLED (254) where no neighbour matches, which
+ *            can only happen in a call that stopped before convergence.  A pure function of D and c: exact too.
+ * part 0 = D, int32; part 1 = dir, uint8; part 2 = the cost map as the solver used it, uint16; all three [x, y]-indexed with
+ * element strides {1, xy_size} (cell (x, y) at [y*xy_size + x]), like a clearance product.
+ *
+ * INPUT, one of two.
+ * map_set_id < 0: the caller's int32 cost map `cost`, xy_size*xy_size with x fastest; params is not read.  on_device == 0: host
+ *   memory, staged through a buffer of the handle; a value outside 0 .. 65535 is GVOM_ERR_INVALID, checked before anything is
+ *   enqueued.  on_device != 0: a device address, read in place (the data must be ready when the call is made); values outside
+ *   0 .. 65535 are CLAMPED into the range by the kernel (negative: blocked).
+ * map_set_id >= 0: a live device map set (gvom_combine_maps_device) and *params; cost must be NULL.  k_travcost builds c from map
+ *   0 (positive, int32 -- never negative in a map set), 1 (negative), 2 (visibility) and 3 (roughness, float64).  A cell is BLOCKED
+ *   iff any of
+ *       (double)positive > density_threshold
+ *       negative > 0                                            (not with GVOM_CTG_NO_NEGATIVE in flags)
+ *       inflation_cells2 > 0 and d2 <= inflation_cells2         d2: gvom_clearance's squared cells for the same threshold and
+ *                                                               negative flag with max_cells2 = inflation_cells2, into scratch
+ *       visibility == 0                                         (only with GVOM_CTG_UNKNOWN_BLOCKS in flags)
+ *   otherwise, in int64,
+ *       c = min(65535, base + soft_weight*positive + (visibility == 0 ? unknown_cost : 0) + rough_weight*q)
+ *   q (roughness r, float64, every operation rounded once): 0 if rough_weight == 0 or !(r > min_roughness); otherwise
+ *       q = (int)floor(((min(r, max_roughness) - min_roughness) / (max_roughness - min_roughness)) * 100.0)
+ *   Constraints: base >= 1; soft_weight, unknown_cost, rough_weight in 0 .. 65535; inflation_cells2 >= 0; density_threshold not NaN;
+ *   max_roughness > min_roughness, both finite, when rough_weight > 0.  Graded (distance-dependent) inflation is NOT provided: build
+ *   a cost map from the clearance product and hand over its device pointer.
+ * goals: HOST int32 [n_goals][2] = (x, y), 1 <= n_goals <= 65536.
+ *
+ * THIS CALL WAITS, unlike the other product calls: it returns when the field has converged, or when max_rounds > 0 rounds have
+ * run (max_rounds == 0: until converged).  A round is one launch in which every tile of 32 x 32 cells whose surroundings changed
+ * relaxes to its own fixed point; open terrain needs a handful, a maze as many as its longest shortest path crosses tiles.  A call
+ * that stops early returns GVOM_OK with converged = 0: every finite D it left is then the cost of a real path -- an upper bound of
+ * the true field, not necessarily the minimum -- and dir may hold GVOM_CTG_UNSETTLED.  No kernel waits on another workgroup, and
+ * every loop in every kernel has a bound fixed at launch.  The handle is held for the duration of the call: scans and combines
+ * issued by other threads on the same handle wait for it.
+ * info (may be NULL): {converged 0 / 1, rounds run, reached cells (D < GVOM_CTG_UNREACHED), goals seeded}.
+ * ORDER.  The kernels run on the handle's stream behind the combine that wrote the set; a later combine that recycles the set runs
+ * behind them: the caller needs no export of the set for the duration of the call.  The product is a snapshot.
+ * Products of this kind live in the product-set pool ("device_product_sets"): at most GVOM_MAX_PRODUCT_SETS, GVOM_ERR_CAPACITY
+ * beyond; an unexported one goes back to the pool with the next gvom_cost_to_go call.  gvom_get_tuning "cost_to_go_allocations"
+ * (read-only): device allocations the entry point has made on this handle (product sets, the work buffer, the staging buffer of the
+ * host route, the inflation scratch); it does not grow in steady state.  gvom_device_product(GVOM_PRODUCT_COSTFIELD) is
+ * GVOM_ERR_INVALID (this call makes them).
+ * GVOM_ERR_INVALID: a sharded handle; a set id AND a cost map, or neither; a set id without params; a stale or unknown set id; a goal
+ * outside the window; n_goals outside 1 .. 65536 or NULL goals; bad parameters (above; max_cost outside 0 .. 2^30; max_rounds < 0);
+ * unknown flag bits; NULL product_id.  GVOM_ERR_CAPACITY: xy_size > 4096; every set of the kind exported.
+ * gvom_set_tuning "cost_to_go_inner" (sweeps a tile makes at most per round; 0 = 256) and "cost_to_go_batch" (rounds enqueued
+ * between two looks at the counters, at most 16; 0 = 8) change how long the call takes, never its result; gvom_get_tuning
+ * "cost_to_go_tiles": tile relaxations of the last call. */
+#define GVOM_PRODUCT_COSTFIELD 7   /* part 0 int32 [xy, xy] cost to go, part 1 uint8 [xy, xy] direction, part 2 uint16 [xy, xy] cell
+                                      costs; all [x, y]-indexed with strides (1, xy), like a device map */
+#define GVOM_CTG_UNREACHED 2147483647
+#define GVOM_CTG_MAX_COST 1073741824
+#define GVOM_CTG_GOAL 8
+#define GVOM_CTG_UNSETTLED 254
+#define GVOM_CTG_NONE 255
+#define GVOM_CTG_NO_NEGATIVE 1      /* flags */
+#define GVOM_CTG_UNKNOWN_BLOCKS 2
+typedef struct gvom_ctg_params {
+    double density_threshold;
+    double min_roughness, max_roughness;
+    int32_t inflation_cells2;
+    int32_t base, soft_weight, unknown_cost, rough_weight;
+} gvom_ctg_params;
+int gvom_cost_to_go(gvom_t *h, int64_t map_set_id, const gvom_ctg_params *params, const int32_t *cost, int on_device,
+                    const int32_t *goals /* [n_goals][2] */, int64_t n_goals, int32_t max_cost, int32_t max_rounds, int flags,
+                    int64_t *product_id, int64_t info[4]);
+
 /* --- one map sharded over the GPUs of a node (one rank = one process = one GPU) -------------------
  * No counterpart in the reference (it has no multi-GPU path); semantics = SURVEY 8(e):
  * the rays are data-parallel, the per-voxel accumulators (hit / total: int32 sum, min-height: f32 min)
@@ -692,6 +781,8 @@ int gvom_host_timing(gvom_t *h, double us[8]);
  * "multi_origin" / "multi_origin_ran" (read-only, gvom_get_tuning): see "multi-origin scans" above.
  * "clearance_allocations" (read-only, gvom_get_tuning): see "obstacle clearance" above.
  * "raycast" / "raycast_allocations" (read-only, gvom_get_tuning): see "ray queries" above.
+ * "cost_to_go" / "cost_to_go_allocations" / "cost_to_go_tiles" (read-only), "cost_to_go_inner" / "cost_to_go_batch": see
+ * "cost-to-go fields" above.
  * (Test hooks are not part of this library: include/gvom_hip_test.h, lib/libgvom_hip_test.so.) */
 int gvom_set_tuning(gvom_t *h, const char *name, int value);
 /* The value the LAST scan ran with ("segs", "period", "ep_row", "prio", "interleave": what automatic resolved to).

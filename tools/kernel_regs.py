@@ -30,7 +30,8 @@ def kernels(lib):
     block = {}
     for line in notes.splitlines():
         t = line.strip()
-        if t.startswith("- .") or t.startswith("- "):           # a new kernel's record begins
+        if t.startswith("- ."):                                  # a new record begins (not the "- 2" / "- 0" of .language_version, which
+            #                                                      sit between a kernel's LDS size and its name)
             if "name" in block: out[block["name"]] = block
             block = {}
             t = t[2:].strip()

@@ -103,7 +103,7 @@ __global__ __launch_bounds__(256) void k_clearance_cols(const uint32_t *__restri
 size_t gvom_clearance_scratch_bytes(int xy) { return (size_t)((xy + 63) & ~63) * (size_t)xy * sizeof(uint16_t); }
 
 hipError_t gvom_launch_clearance(hipStream_t s, int xy, double res, const int32_t *pos, const int32_t *neg, double thr,
-                                 int32_t max_cells2, uint16_t *g, float *out_dist, int32_t *out_d2)
+                                 int32_t max_cells2, uint16_t *g, float *out_dist, int32_t *out_d2, int shape[4])
 {
     if (xy <= 0 || xy > GVOM_CLEARANCE_MAX_XY) return hipErrorInvalidValue;
     const int gp = (xy + 63) & ~63;
@@ -129,6 +129,7 @@ hipError_t gvom_launch_clearance(hipStream_t s, int xy, double res, const int32_
     while (lgw > 3 && ((size_t)nrows << lgw) * 2 > 65536) --lgw;
     const size_t lds = ((size_t)nrows << lgw) * 2;
     if (lds > 65536) return hipErrorInvalidValue;
+    if (shape) { shape[0] = lgw; shape[1] = T; shape[2] = (int)lds; shape[3] = gp >> 6; }
     hipLaunchKernelGGL(k_clearance_cols, dim3((xy + (1 << lgw) - 1) >> lgw, ytiles), dim3(256), lds, s, (const uint32_t *)g, gp, xy, lgw,
                        T, halo, lim, res, out_dist, out_d2);
     return hipGetLastError();

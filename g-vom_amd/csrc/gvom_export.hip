@@ -579,7 +579,7 @@ VIS int gvom_clearance(gvom_t *h, int64_t map_set_id, const int32_t *positive, c
     SetPart d0, d1;
     set_part(set, 0, &d0); set_part(set, 1, &d1);
     HIPCHK(h, gvom_launch_clearance(h->stream, xy, h->prm.xy_resolution, pos, neg, density_threshold, max_cells2,
-                                    (uint16_t *)h->cl_g.p, (float *)d0.ptr, (int32_t *)d1.ptr));
+                                    (uint16_t *)h->cl_g.p, (float *)d0.ptr, (int32_t *)d1.ptr, h->cl_shape));
     HIPCHK(h, hipEventRecord(set->ready, h->stream));
     set->id = ++h->pset_seq;
     *product_id = set->id;

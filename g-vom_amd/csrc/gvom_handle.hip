@@ -562,6 +562,9 @@ VIS int gvom_get_tuning(gvom_t *h, const char *name, int *value)
     if (!strcmp(name, "fuse_kernel")) { *value = h->last_fuse; return GVOM_OK; }
     if (!strcmp(name, "device_map_sets")) { *value = (int)h->dsets.size(); return GVOM_OK; }             // read-only: allocated device map sets                  // read-only, GVOM_ROUTE_*
     if (!strcmp(name, "clearance_allocations")) { *value = h->cl_allocs; return GVOM_OK; }              // read-only: device allocations gvom_clearance has made
+    static const char *const cl_names[4] = {"clearance_lgw", "clearance_rows_per_tile", "clearance_lds_bytes", "clearance_chunks"};
+    for (int k = 0; k < 4; ++k)                                                                          // read-only: the launch shape of the last gvom_clearance
+        if (!strcmp(name, cl_names[k])) { *value = h->cl_shape[k]; return GVOM_OK; }
     if (!strcmp(name, "raycast")) { *value = 1; return GVOM_OK; }                                       // read-only: the library has gvom_raycast
     if (!strcmp(name, "raycast_allocations")) { *value = h->rq_allocs; return GVOM_OK; }                // read-only: device allocations gvom_raycast has made
     if (!strcmp(name, "cost_to_go")) { *value = 1; return GVOM_OK; }                                    // read-only: the library has gvom_cost_to_go

@@ -316,6 +316,7 @@ struct gvom_handle {
     // (these two and its product sets: gvom_get_tuning "clearance_allocations")
     Buf cl_g, cl_stage;
     int cl_allocs = 0;
+    int cl_shape[4] = {0, 0, 0, 0};                     // the launch shape of the last gvom_clearance (gvom_get_tuning "clearance_lgw" ...), from gvom_launch_clearance
     // RAY QUERIES (gvom_raycast): the staging copy of a caller's host segments ([K][3] origins, then [n][3] end points), grown by
     // the first call that needs more; rq_allocs counts every device allocation the entry point has made on this handle (this
     // buffer and its product sets: gvom_get_tuning "raycast_allocations")

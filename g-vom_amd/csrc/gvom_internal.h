@@ -288,10 +288,12 @@ hipError_t gvom_launch_raycast(hipStream_t s, const ScanParams &P, const RayQuer
 // obstacle iff (double)pos > thr or neg > 0.  out_d2[y][x] = exact squared distance in cells to the nearest obstacle (INT32_MAX
 // where there is none, or beyond max_cells2 when that is > 0), out_dist[y][x] = (float)(sqrt((double)d2) * res), +inf there.
 // g: gvom_clearance_scratch_bytes(xy) of scratch (the row pass's uint16 distances).  xy <= GVOM_CLEARANCE_MAX_XY.
+// shape (may be nullptr): the launch shape the call used -- {lgw (log2 of the columns per strip of k_clearance_cols), output rows
+// per workgroup, dynamic LDS bytes, 64-cell chunks per row of k_clearance_rows}.
 #define GVOM_CLEARANCE_MAX_XY 4096
 size_t gvom_clearance_scratch_bytes(int xy);
 hipError_t gvom_launch_clearance(hipStream_t s, int xy, double res, const int32_t *pos, const int32_t *neg, double thr,
-                                 int32_t max_cells2, uint16_t *g, float *out_dist, int32_t *out_d2);
+                                 int32_t max_cells2, uint16_t *g, float *out_dist, int32_t *out_d2, int shape[4] = nullptr);
 // cost-to-go fields (gvom_costfield.hip; include/gvom_hip.h "cost-to-go fields" defines the result).  Every map is [y][x], xy x xy.
 // travcost: the uint16 cost map c (0 = blocked) from the int32 positive / negative / visibility maps, the f64 roughness map and
 // the clearance d2 (nullptr: no inflation).  seed: c from cost32 (clamped into 0..65535; nullptr: c is there already), D =

@@ -780,6 +780,11 @@ int gvom_host_timing(gvom_t *h, double us[8]);
  * "range_image" (read-only, gvom_get_tuning): 1 when a sensor model is set (gvom_sensor_model_set), else 0.
  * "multi_origin" / "multi_origin_ran" (read-only, gvom_get_tuning): see "multi-origin scans" above.
  * "clearance_allocations" (read-only, gvom_get_tuning): see "obstacle clearance" above.
+ * "clearance_lgw" / "clearance_rows_per_tile" / "clearance_lds_bytes" / "clearance_chunks" (read-only, gvom_get_tuning): the
+ * launch shape of the LAST gvom_clearance on this handle, as the launch itself chose it from xy_size and max_cells2 -- log2 of the
+ * columns per strip of the column pass (3 .. 6), output rows per workgroup of that pass (16 .. 256), its dynamic LDS in bytes (at
+ * most 65536), and the 64-cell chunks per map row of the row pass (at most 64).  All 0 before the first call.  The shape never
+ * changes a result; the names exist so that tests can show which launch regimes they ran.
  * "raycast" / "raycast_allocations" (read-only, gvom_get_tuning): see "ray queries" above.
  * "cost_to_go" / "cost_to_go_allocations" / "cost_to_go_tiles" (read-only), "cost_to_go_inner" / "cost_to_go_batch": see
  * "cost-to-go fields" above.

@@ -138,3 +138,147 @@ def patterns(xy, seed=0):
     n[1, 2] = 100
     out["negative_only"] = (np.full((xy, xy), 10, np.int32), n)
     return out
+
+
+# ---- maps of 300 to 4096 cells a side: every launch regime of the two kernels (tests/test_clearance.py "launch regimes") ------------
+# separable() is O(n^3) -- 3.8 s per mask at 1000 cells -- so the large maps have two further exact referees, both pinned to
+# separable / brute_force by tests/test_clearance_cpu.py:
+#   by_rows             min over the map rows (fixed y) that hold an obstacle of (distance along x within that row)^2 + dy^2:
+#                       O(rows * n^2), for the patterns whose obstacles lie in a handful of rows
+#   feature_transform   scipy's Euclidean feature transform (the INDEX of a nearest obstacle per cell), then the squared distance
+#                       to that obstacle in integer arithmetic: nothing of scipy's floating point reaches the result
+LARGE = (300, 520, 1000, 1024, 2049, 4096)
+
+
+def large_caps(xy):
+    """max_cells2 at the large sizes: unbounded, 1, 25, 2500 (a halo of 50 rows) and a cap whose radius is xy itself -- not
+    below xy, so the column pass loads every row as when unbounded, but cuts at the cap"""
+    return (0, 1, 25, 2500, xy * xy)
+
+
+def by_rows(mask, max_cells2=0):
+    mask = np.asarray(mask, bool)
+    n, m = mask.shape
+    big = np.int64(1) << 40
+    out = np.full((n, m), big, np.int64)
+    xs, ys = np.arange(n, dtype=np.int64), np.arange(m, dtype=np.int64)
+    for y in np.flatnonzero(mask.any(axis=0)):
+        ox = np.flatnonzero(mask[:, y]).astype(np.int64)
+        k = np.searchsorted(ox, xs)                                          # ox[k - 1] < x <= ox[k]
+        left = np.where(k > 0, xs - ox[np.maximum(k, 1) - 1], big)
+        right = np.where(k < len(ox), ox[np.minimum(k, len(ox) - 1)] - xs, big)
+        g = np.minimum(left, right)
+        np.minimum(out, (g * g)[:, None] + ((ys - y) ** 2)[None, :], out=out)
+    return cap(np.where(out >= big // 2, FAR, out), max_cells2)
+
+
+def have_scipy():
+    try:
+        import scipy.ndimage                                                 # noqa: F401
+        return True
+    except ImportError:
+        return False
+
+
+def feature_transform(mask, max_cells2=0):
+    from scipy import ndimage
+    mask = np.asarray(mask, bool)
+    n, m = mask.shape
+    if not mask.any():
+        return np.full((n, m), FAR, np.int32)
+    idx = ndimage.distance_transform_edt(~mask, return_distances=False, return_indices=True)
+    assert mask[idx[0], idx[1]].all()                                        # every index names an obstacle cell
+    dx = idx[0].astype(np.int64) - np.arange(n, dtype=np.int64)[:, None]
+    dy = idx[1].astype(np.int64) - np.arange(m, dtype=np.int64)[None, :]
+    return cap(dx * dx + dy * dy, max_cells2)
+
+
+def brute_force_near(mask, cells, r=48):
+    """brute_force at `cells` ([k, 2] of (x, y)) without the full obstacle list where it is not needed: the minimum over the
+    obstacles within r cells in x and in y IS the global minimum once it is <= r^2 (every obstacle outside that square is
+    further than r); the cells it does not settle go to brute_force itself"""
+    mask = np.asarray(mask, bool)
+    n, m = mask.shape
+    cells = np.asarray(cells, np.int64)
+    out = np.full(len(cells), -1, np.int64)
+    for k, (x, y) in enumerate(cells):
+        x0, y0 = max(0, x - r), max(0, y - r)
+        ox, oy = np.nonzero(mask[x0:x + r + 1, y0:y + r + 1])
+        if ox.size:
+            d = int(((ox + x0 - x) ** 2 + (oy + y0 - y) ** 2).min())
+            if d <= r * r:
+                out[k] = d
+    rest = np.flatnonzero(out < 0)
+    if rest.size:
+        out[rest] = brute_force(mask, 0, cells[rest])
+    return out.astype(np.int32)
+
+
+def row_tile(xy):
+    """output rows per workgroup of k_clearance_cols as gvom_launch_clearance chooses them today; the sample below needs no more
+    of it than that it is a multiple of 16"""
+    return max(16, (xy // 16 + 15) & ~15)
+
+
+def boundary_sample(xy, seed=0):
+    """[k, 2] (x, y): cells either side of every boundary the kernels have -- x = 8 j (every strip width 8 .. 64 of the column
+    pass, and the 64-cell chunks of the row pass), y = 16 j (every row tile: row_tile() is a multiple of 16) -- each x boundary at
+    a y next to a row-tile boundary and the other way round, and 2,048 random cells"""
+    assert row_tile(xy) % 16 == 0
+    xb = np.array([b + e for b in range(8, xy, 8) for e in (-1, 0)], np.int64)
+    yb = np.array([t + e for t in range(16, xy, 16) for e in (-1, 0)], np.int64)
+    a = np.stack([xb, yb[(np.arange(len(xb)) * 7) % len(yb)]], axis=1)
+    b = np.stack([xb[(np.arange(len(yb)) * 5) % len(xb)], yb], axis=1)
+    rnd = np.random.default_rng(9000 + xy + seed).integers(0, xy, (2048, 2))
+    return np.concatenate([a, b, rnd])
+
+
+def large_patterns(xy, short=False):
+    """name -> positive map [x, y] int32 (no negative map), for xy > 256.  short: the list of the largest size"""
+    rng = np.random.default_rng(77 * xy)
+    z = lambda: np.zeros((xy, xy), np.int32)                                  # noqa: E731
+    out = {}
+    p = z()
+    p[xy - 1, 0] = 100
+    out["corner_far"] = p                                                     # (0, xy - 1) lies 2 (xy - 1)^2 away: the largest d2 there is;
+    p = z()                                                                   # its row's other cells look RIGHT across every chunk
+    p[0, xy - 1] = 100
+    out["corner_0n"] = p                                                      # ... and this one's LEFT
+    p = z()
+    for b in range(64, xy, 64):                                               # x = b - 1 | b: the last lane of a chunk and the first of the next
+        p[b - 1, 5] = p[b, 5] = 100
+    out["boundary_same_row"] = p
+    p = z()
+    for b in range(64, xy, 64):
+        p[b - 1, xy // 2] = p[b, xy // 2 + 1] = 100
+    out["boundary_adjacent_rows"] = p
+    p = z()
+    p[0, 16] = p[xy - 1, 16] = 100                                            # chunk 0 and the last chunk, every chunk between empty
+    out["lonely"] = p
+    out["random_0.1"] = np.where(rng.random((xy, xy)) < 0.001, 100, 0).astype(np.int32)
+    if short:
+        return out
+    out["none"] = z()
+    out["all"] = np.full((xy, xy), 100, np.int32)
+    p = z()
+    p[0, 0] = p[0, xy - 1] = p[xy - 1, 0] = p[xy - 1, xy - 1] = 100
+    out["corners"] = p
+    p = z()
+    p[:, xy // 3] = 100
+    out["full_row"] = p                                                       # one y: a full row of the [y][x] storage
+    p = z()
+    p[xy // 3, :] = 100
+    out["full_column"] = p
+    out["random_30"] = np.where(rng.random((xy, xy)) < 0.3, 100, 0).astype(np.int32)
+    return out
+
+
+def large_referee(mask):
+    """the unbounded d2 of a large map by the cheapest exact referee that fits it; None where that is the feature transform and
+    scipy is missing (the random patterns: the caller then holds cr.boundary_sample to brute_force_near)"""
+    mask = np.asarray(mask, bool)
+    if int(mask.any(axis=0).sum()) <= 8:
+        return by_rows(mask)
+    if np.array_equal(mask, np.broadcast_to(mask.all(axis=1)[:, None], mask.shape)):      # whole columns x only (or every cell):
+        return np.ascontiguousarray(np.broadcast_to(by_rows(mask[:, :1]), mask.shape))    # the distance along x, whatever y
+    return feature_transform(mask) if have_scipy() else None

@@ -12,24 +12,28 @@ MAX_COST = 2 ** 30
 GOAL, UNSETTLED, NONE = 8, 254, 255
 STEPS = ((1, 0), (1, 1), (0, 1), (-1, 1), (-1, 0), (-1, -1), (0, -1), (1, -1))
 TILE = 32                                     # the solver's tile: the census counts tile crossings with it
-SIZES = (16, 31, 32, 33, 50, 64, 65, 100)     # one partial tile; each side of 16, 32, 64; ragged last tiles; 2 x 2 tiles; >= 3 tiles
+SIZES = (16, 31, 32, 33, 50, 64, 65, 100, 129)     # one partial tile; each side of 16, 32, 64; ragged last tiles; 2 x 2 tiles; >= 3 tiles; 5 x 5 with a last tile one cell wide
+LARGE = (1024, 4096)                          # 32 x 32 and 128 x 128 tiles (the largest map the call accepts): large_patterns() below
 INF = 2 ** 60                                 # (INF + INF fits int64)
 
 
-def weights(c, corner_rule=True):
-    """w[k][x, y]: the weight of the step from (x, y) in direction k, INF where it is not admissible"""
+def iter_weights(c, corner_rule=True):
+    """w[k][x, y], k = 0 .. 7 in turn: the weight of the step from (x, y) in direction k, INF where it is not admissible"""
     c = np.asarray(c, np.int64)
     n = c.shape[0]
     pad = np.zeros((n + 2, n + 2), np.int64)
     pad[1:-1, 1:-1] = c
     at = lambda dx, dy: pad[1 + dx:n + 1 + dx, 1 + dy:n + 1 + dy]
-    out = []
     for k, (dx, dy) in enumerate(STEPS):
         ok = (c > 0) & (at(dx, dy) > 0)
         if k & 1 and corner_rule:
             ok &= (at(dx, 0) > 0) & (at(0, dy) > 0)
-        out.append(np.where(ok, (7 if k & 1 else 5) * (c + at(dx, dy)), INF))
-    return out
+        yield np.where(ok, (7 if k & 1 else 5) * (c + at(dx, dy)), INF)
+
+
+def weights(c, corner_rule=True):
+    """the eight of them as a list (a map of 4096 cells a side is better served one direction at a time: 128 MB each)"""
+    return list(iter_weights(c, corner_rule))
 
 
 def _seed(c, goals):
@@ -147,25 +151,70 @@ def tiled(c, goals, max_cost=0, inner=256, max_rounds=0, tile=TILE):
     return out, rounds, relaxations, not active
 
 
-def matches(D, c, corner_rule=True):
-    """[8][x, y] bool: neighbour k is admissible with D[v] + w(u, v) == D[u] (only where D[u] is finite and not 0)"""
+def iter_matches(D, c, corner_rule=True):
+    """(match, offer) of neighbour k = 0 .. 7 in turn.  match [x, y] bool: the neighbour is admissible with D[v] + w(u, v) == D[u]
+    (only where D[u] is finite and not 0); offer [x, y] int64: D[v] + w(u, v), >= INF where the step is not admissible or v is
+    unreached"""
     D = np.asarray(D, np.int64)
     n = D.shape[0]
     pad = np.full((n + 2, n + 2), INF, np.int64)
     pad[1:-1, 1:-1] = np.where(D == UNREACHED, INF, D)
     live = (D != UNREACHED) & (D != 0)
-    return [live & (wk < INF) & (pad[1 + dx:n + 1 + dx, 1 + dy:n + 1 + dy] + wk == D) for wk, (dx, dy) in zip(weights(c, corner_rule), STEPS)]
+    for wk, (dx, dy) in zip(iter_weights(c, corner_rule), STEPS):
+        offer = pad[1 + dx:n + 1 + dx, 1 + dy:n + 1 + dy] + wk
+        yield live & (wk < INF) & (offer == D), offer
+
+
+def matches(D, c, corner_rule=True):
+    """[8][x, y] bool: the matches of iter_matches"""
+    return [m for m, _ in iter_matches(D, c, corner_rule)]
 
 
 def directions(D, c):
     """uint8 [x, y]: the smallest matching k; GOAL where D == 0, NONE where unreached, UNSETTLED where nothing matches"""
     D = np.asarray(D)
     out = np.full(D.shape, UNSETTLED, np.uint8)
-    for k in range(7, -1, -1):
-        out[matches(D, c)[k]] = k
+    for k, (m, _) in enumerate(iter_matches(D, c)):
+        out[m & (out == UNSETTLED)] = k
     out[D == 0] = GOAL
     out[D == UNREACHED] = NONE
     return out
+
+
+def bellman(D, c, goals, max_cost=0):
+    """What makes D THE cost-to-go field of (c, goals, max_cost), checked cell by cell without solving anything -- for the maps a
+    heap Dijkstra in Python is too slow for.  Returns ({violation: number of cells}, the directions of D), in one pass over
+    iter_matches.  The conditions:
+      goal         the cells with D == 0 are exactly the goals that lie on free cells
+      blocked      no blocked cell is reached
+      above_cap    no reached cell lies above the cap
+      no_match     every other reached cell has a neighbour with D[v] + w(u, v) == D[u] ...
+      offers_less  ... and no admissible neighbour offers less
+      left_out     no unreached free cell has a reached admissible neighbour whose offer is at or below the cap
+    Weights are positive, so the matches of a reached cell lead down a chain of strictly smaller values that can only end in a
+    goal: D[u] is the cost of a path, hence no less than the true value; offers_less (by induction along a shortest path) makes it
+    no more; left_out does the same for the cells Dijkstra would have accepted.  tests/test_costfield_cpu.py pins the check to
+    Dijkstra and shows it rejects single-cell errors."""
+    D, c = np.asarray(D), np.asarray(c)
+    cap = max_cost or MAX_COST
+    reached = D != UNREACHED
+    seeded = np.zeros(D.shape, bool)
+    for x, y in _seed(c, goals):
+        seeded[x, y] = True
+    any_match = np.zeros(D.shape, bool)
+    best = np.full(D.shape, INF, np.int64)
+    d = np.full(D.shape, UNSETTLED, np.uint8)
+    for k, (m, offer) in enumerate(iter_matches(D, c)):
+        d[m & ~any_match] = k
+        any_match |= m
+        np.minimum(best, offer, out=best)
+    d[D == 0] = GOAL
+    d[~reached] = NONE
+    inner = reached & (D != 0)
+    bad = {"goal": int(((D == 0) != seeded).sum()), "blocked": int((reached & (c <= 0)).sum()),
+           "above_cap": int((reached & (D > cap)).sum()), "no_match": int((inner & ~any_match).sum()),
+           "offers_less": int((inner & (best < D)).sum()), "left_out": int((~reached & (c > 0) & (best <= cap)).sum())}
+    return {k: v for k, v in bad.items() if v}, d
 
 
 def info(D, c, goals):
@@ -291,6 +340,49 @@ def patterns(xy):
         c.setflags(write=False)
         final[name] = (c, np.array(goals, np.int32).reshape(-1, 2), cap)
     return final
+
+
+@functools.lru_cache(maxsize=None)
+def large_patterns(xy):
+    """the patterns of the LARGE sizes, as patterns() builds them (same seeds and rules): open, random, seventeen_goals, and at
+    1024 random_cut.  No serpentine: its rounds grow with corridors x tiles.  The cap of random_cut is the median of random's own
+    field (large_expected), so it is filled in there."""
+    one = np.ones((xy, xy), np.int32)
+    rnd = _random_costs(xy, 100 + xy)
+    blocked, free = np.argwhere(rnd == 0), np.argwhere(rnd > 0)
+    rng = np.random.default_rng(7 + xy)
+    pick = [tuple(free[i]) for i in rng.choice(len(free), 12, replace=False)] + [tuple(blocked[i]) for i in rng.choice(len(blocked), 4, replace=False)]
+    out = {"open": (one, [(0, 0)]), "random": (rnd, [_free_near(rnd, xy // 2, xy // 3)]), "seventeen_goals": (rnd, pick + [pick[0]])}
+    final = {}
+    for name, (c, goals) in out.items():
+        c = np.array(c, np.int32)
+        c.setflags(write=False)
+        final[name] = (c, np.array(goals, np.int32).reshape(-1, 2))
+    return final
+
+
+def open_field(xy, goal=(0, 0)):
+    """the field of an all-ones map with one goal, in closed form: min(dx, dy) diagonal steps of 7 (1 + 1) and |dx - dy| straight
+    ones of 5 (1 + 1) -- no cheaper mix exists, since a diagonal step (14) costs less than the two straight ones it replaces (20)"""
+    dx = np.abs(np.arange(xy, dtype=np.int64) - goal[0])[:, None]
+    dy = np.abs(np.arange(xy, dtype=np.int64) - goal[1])[None, :]
+    return (14 * np.minimum(dx, dy) + 10 * np.abs(dx - dy)).astype(np.int32)
+
+
+@functools.lru_cache(maxsize=None)
+def large_expected(xy, name):
+    """(c, goals, max_cost, D, dir, (reached, seeded)) at 1024 cells by heap Dijkstra -- about 4 s a pattern, computed once"""
+    cut = name == "random_cut"
+    c, goals = large_patterns(xy)["random" if cut else name]
+    cap = 0
+    if cut:
+        full = large_expected(xy, "random")[3]
+        cap = int(np.median(full[full != UNREACHED]))
+    D = dijkstra(c, goals, cap)
+    d = directions(D, c)
+    D.setflags(write=False)
+    d.setflags(write=False)
+    return c, goals, cap, D, d, info(D, c, goals)
 
 
 @functools.lru_cache(maxsize=None)

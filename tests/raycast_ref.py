@@ -11,8 +11,20 @@ import math
 
 import numpy as np
 
+import multi_origin_ref
 import synth
-from multi_origin_ref import GRIDS
+
+# The ray tests' own grids, next to the three of tests/multi_origin_ref.py (whose parametrisation they must not change).  WIDE: the
+# smallest maps with more than one 64-cell tile segment per storage row (k_raycast's tile index is row * nseg + (sx >> 6): at
+# xy <= 64 its second term is always 0) -- a power of two with 2 segments, no power of two with 3.  FAR: the np2 grid with every
+# ego moved by FAR_OFFSET metres, which puts every axis of the window origin beyond 2^24 voxels (both signs): the query then
+# takes the literal float64 lookup whatever the grid (gvom_export.hip raycast_params).
+WIDE = {"w128": (0.2, 0.2, 128, 32), "w192": (0.2, 0.2, 192, 24)}
+FAR = {"far": multi_origin_ref.GRIDS["np2"]}
+FAR_OFFSET = (7.0e6, -7.0e6, 3.5e6)
+GRIDS = dict(multi_origin_ref.GRIDS)
+GRIDS.update(WIDE)
+GRIDS.update(FAR)
 
 CLEAR, OCCUPIED, UNKNOWN, LEFT_WINDOW, INVALID = range(5)
 N_RAYS = 4096
@@ -140,7 +152,8 @@ def ego_of(grid, k):
     scan (storage offsets != 0, tiles go stale)"""
     xr, zr, xy, zs = GRIDS[grid]
     w = xr * xy
-    return tuple(float(F32(v)) for v in (0.05 * w * k + 0.05, -0.035 * w * k, 0.11 * k))
+    off = FAR_OFFSET if grid in FAR else (0.0, 0.0, 0.0)
+    return tuple(float(F32(v + o)) for v, o in zip((0.05 * w * k + 0.05, -0.035 * w * k, 0.11 * k), off))
 
 
 def cloud_of(grid, k):
@@ -150,7 +163,7 @@ def cloud_of(grid, k):
     window is never scanned"""
     xr, zr, xy, zs = GRIDS[grid]
     ego = ego_of(grid, k)
-    if grid != "tall" and k % 2 == 0:
+    if grid not in ("tall", "far") and k % 2 == 0:            # (the scene lies around the world's origin: out of the far window's sight)
         scene = synth.make_scene(2, extent=10.0)
         return synth.lidar_scan(scene, 16, 512, ego, 0.0, k, F32, elevations_deg=np.linspace(-24.0, 3.0, 16))
     wx, wz = xr * xy, zr * zs
@@ -265,6 +278,34 @@ def census(result):
     return ([int((st == k).sum()) for k in range(5)], int((stopped & (result[:, 1] >= 8)).sum()), int((stopped & (result[:, 1] >= 4)).sum()))
 
 
+def storage_segment(vox, W, grid):
+    """the 64-cell tile segment (sx >> 6 of gvom_query.hip rq_index) of the STORAGE column that holds window voxel `vox`: the
+    window column moved by the storage offset W[0] mod xy"""
+    xy = GRIDS[grid][2]
+    return (((np.asarray(vox, np.int64) % xy) + int(W[0]) % xy) % xy) >> 6
+
+
+def segment_census(result, visits, W, grid):
+    """(stop voxels per storage segment, rays whose examined voxels lie in two or more segments) of a walk's result and its
+    recorded (ray, voxel) visits"""
+    nseg = (GRIDS[grid][2] + 63) // 64
+    stopped = result[:, 2] >= 0
+    stops = np.bincount(storage_segment(result[stopped, 2], W, grid), minlength=nseg)
+    v = np.asarray(visits, np.int64).reshape(-1, 2)
+    seen = np.zeros((len(result), nseg), bool)
+    seen[v[:, 0], storage_segment(v[:, 1], W, grid)] = True
+    return [int(s) for s in stops], int((seen.sum(axis=1) >= 2).sum())
+
+
+def state_class(state):
+    """0 occupied, 1 never observed, 2 observed free: what a ray query reads of a dense state (the indices themselves differ
+    between builders)"""
+    state = np.asarray(state)
+    return np.where(state >= 0, 0, np.where(state == -1, 1, 2)).astype(np.int8)
+
+
 CENSUS_FLAGS = dict(unknown_blocks=True, check_target=False)      # the ONE call whose rays must show every status
 STATUS_FLOOR = 32
-STEP_FLOOR = {"p2": (8, 32), "np2": (8, 32), "tall": (4, 32)}     # (step, rays that stop at a voxel at or beyond it)
+STEP_FLOOR = {"p2": (8, 32), "np2": (8, 32), "tall": (4, 32), "w128": (8, 32), "w192": (8, 32)}     # (step, rays that stop at a voxel at or beyond it)
+SEGMENT_STOP_FLOOR = 100                                          # WIDE: stop voxels in every storage segment
+SEGMENT_CROSS_FLOOR = 300                                         # WIDE: rays whose examined voxels span >= 2 segments

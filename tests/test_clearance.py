@@ -4,6 +4,11 @@ bit.  Synthetic maps on grids of 16 (less than a wave), 50 (xy % 4 != 0, partial
 row, several strips and row tiles), the obstacle scenes end to end through combine_maps_device(), snapshots, the product pool,
 errors, and a torch consumer in a child process.
 
+From 300 cells on ("launch regimes" below): 300, 520, 1000, 1024, 2049 and 4096 cells against the row-wise and feature-transform
+referees of tests/clearance_ref.py, with the launch shape of every call read back from the handle.  Wall time on the MI355X (pytest
+--durations, one run): 0.28 / 1.43 / 0.67 / 1.22 / 3.04 / 9.09 s for the six sizes (the largest existing case, 256 cells, 0.25 s);
+at 4096 five patterns run unbounded and under one cap each, of which the feature transform of the random map takes about 3 s.
+
 Census of the scenes at the last combine, threshold 50 (one_round / ragged): 166 / 368 cells with 0 < positive <= 50,
 387 / 493 with positive > 50, 5 / 1 with negative > 0 (tests/test_clearance_cpu.py holds the floors on the CPU referee)."""
 import ctypes
@@ -108,6 +113,99 @@ def test_negative_obstacles_flag_memory_orders_and_inf(handles, xy):
     asym = cr.separable(cr.obstacle_mask(rnd, None, 50))
     assert not np.array_equal(asym, asym.T)                    # an [x, y] / [y, x] mix-up would show
     _hold(g.clearance_of(rnd), asym, res, "random_1, positive only")
+
+
+# ---- launch regimes: maps of 300 to 4096 cells a side ---------------------------------------------------------------------------
+# The four sizes above all launch k_clearance_cols with strips of 16 columns (lgw 4) and 16 rows per workgroup, and k_clearance_rows
+# with at most 4 chunks per row: one trip of its loop per wave.  The sizes of cr.LARGE run the other strip widths (lgw 3, 5, 6: the
+# LDS load indexing, the column stride, the row stride), 32 to 256 rows per workgroup with a ragged last row tile, dynamic LDS of
+# exactly 65,536 bytes, and up to 64 chunks per row (the chunk loop's later trips, the search across up to 64 masks, chunk 63).
+# Which regime a call ran is read back from the handle (gvom_get_tuning "clearance_lgw" ...: what gvom_launch_clearance used).
+LARGE_RES = {300: 0.15, 520: 0.1, 1000: 0.4, 1024: 0.2, 2049: 0.25, 4096: 0.05}
+SHAPE = ("clearance_lgw", "clearance_rows_per_tile", "clearance_lds_bytes", "clearance_chunks")
+SEEN = {}                                                      # xy -> {(lgw, rows per tile, LDS bytes, chunks)} of the calls made so far
+
+
+def _large_handle(gvom, xy):
+    return gvom.Gvom(LARGE_RES[xy], 0.2, xy, 1, 1, 1.0, 0.5, 0.5, 0.3, 2.0, 4.0, 1.0, 1, 1, voxel_statistics=False)
+
+
+def _shape(g):
+    return tuple(g.get_tuning(n) for n in SHAPE)
+
+
+def _hold_sample(c, mask, cap, cells, res, what):
+    """_hold on the cells [k, 2] alone, against brute_force_near: for the random maps where the full-map referee is missing"""
+    with c:
+        dist, d2 = c.copy_to_host()
+    want = cr.cap(cr.brute_force_near(mask, cells), cap)
+    got, got_dist = d2[cells[:, 0], cells[:, 1]], dist[cells[:, 0], cells[:, 1]]
+    assert np.array_equal(got, want), "%s: squared cells differ in %d of %d sampled cells" % (what, int((got != want).sum()), len(cells))
+    assert np.array_equal(_bits(got_dist), _bits(cr.distance(want, res))), what
+
+
+def _large_caps(xy, k):
+    """the caps pattern number k runs: all five up to 1024 cells; beyond, unbounded and two (2049) or one (4096) of the capped
+    ones in turn -- every cap still runs at every size"""
+    caps = cr.large_caps(xy)
+    if xy <= 1024:
+        return caps
+    return (0, caps[1 + k % 4]) + ((caps[1 + (k + 2) % 4],) if xy < 4096 else ())
+
+
+@pytest.mark.parametrize("xy", cr.LARGE)
+def test_large_maps_match_the_referee_exactly_in_every_launch_regime(gvom, xy):
+    g, res = _large_handle(gvom, xy), LARGE_RES[xy]
+    assert _shape(g) == (0, 0, 0, 0)
+    seen, caps_run = SEEN.setdefault(xy, set()), set()
+    pats = cr.large_patterns(xy, short=xy == 4096)
+    assert {"corner_far", "corner_0n", "boundary_same_row", "boundary_adjacent_rows", "lonely", "random_0.1"} <= set(pats)
+    for k, (name, pos) in enumerate(pats.items()):
+        mask = cr.obstacle_mask(pos, None, 50)
+        full = cr.large_referee(mask)
+        assert full is not None or name.startswith("random")        # (None: no scipy here; only the random maps need it)
+        pos = np.asfortranarray(pos)
+        for c in _large_caps(xy, k):
+            what = "xy %d, %s, cap %d" % (xy, name, c)
+            got = g.clearance_of(pos, None, max_distance=_cap_metres(c, res) if c else None)
+            shape = _shape(g)
+            seen.add(shape)
+            caps_run.add(c)
+            lgw, rows, lds, chunks = shape
+            assert 3 <= lgw <= 6 and rows % 16 == 0 and 16 <= rows <= 256 and 0 < lds <= 65536 and chunks == (xy + 63) // 64, (what, shape)
+            if full is None or (xy == 300 and name == "random_0.1"):      # (at 300 both, so that this route is itself run everywhere)
+                _hold_sample(g.clearance_of(pos, None, max_distance=_cap_metres(c, res) if c else None), mask, c, cr.boundary_sample(xy), res, what + ", sampled")
+            if full is not None:
+                _hold(got, cr.cap(full, c), res, what + ", launch %r" % (shape,))
+            else:
+                got.release()
+    assert caps_run == set(cr.large_caps(xy))
+    print(xy, sorted(seen))
+    del g
+
+
+def test_every_launch_regime_ran(gvom, handles):
+    """lgw 3, 4, 5 and 6; 16, 32, 64, 128 and 256 rows per workgroup; dynamic LDS of exactly 65,536 bytes; 64 chunks per row:
+    all of them seen through the getters.  A size the test above has not run in this process (a selection of tests) is launched
+    here on an empty map, for the shapes alone."""
+    pos = cr.patterns(256)["random_1"][0]
+    handles[256].clearance_of(pos).release()
+    shapes = {_shape(handles[256])}
+    for xy in cr.LARGE:
+        if xy not in SEEN:
+            g = _large_handle(gvom, xy)
+            empty = np.zeros((xy, xy), np.int32, order="F")
+            for c in cr.large_caps(xy):
+                g.clearance_of(empty, None, max_distance=_cap_metres(c, LARGE_RES[xy]) if c else None).release()
+                SEEN.setdefault(xy, set()).add(_shape(g))
+            del g
+        shapes |= SEEN[xy]
+    print(sorted(shapes))
+    assert {s[0] for s in shapes} == {3, 4, 5, 6}, sorted(shapes)
+    assert {s[1] for s in shapes} >= {16, 32, 64, 128, 256}, sorted(shapes)
+    assert 65536 in {s[2] for s in shapes}, sorted(shapes)
+    assert 64 in {s[3] for s in shapes} and max(s[3] for s in shapes) == 64, sorted(shapes)
+    assert len({s[3] for s in shapes if s[3] > 4}) >= 5          # the chunk loop's second trip and beyond, at several widths
 
 
 def _census_floors(pos, neg, what):

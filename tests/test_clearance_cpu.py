@@ -33,6 +33,94 @@ def test_the_two_referee_forms_agree(xy):
                 assert np.array_equal(capped == cr.FAR, sep > c) and np.array_equal(capped[sep <= c], sep[sep <= c])
 
 
+@pytest.mark.parametrize("xy", cr.LARGE)
+def test_the_large_map_referees_agree(xy):
+    """by_rows and feature_transform (what tests/test_clearance.py compares the kernels with from 300 cells on) against the two
+    older forms: separable on the full map up to 520 cells, brute_force on cr.boundary_sample beyond (both sides of every chunk,
+    strip and row-tile boundary and 2,048 random cells).  At 4096 the feature transform takes 2 to 3 s a mask: there it is held on
+    the map it is the referee of (random_0.1) and on corner_far."""
+    sample = cr.boundary_sample(xy)
+    nx = 2 * len(range(8, xy, 8))                              # the sample's first part: both sides of every x boundary
+    assert len(sample) >= 2048 + nx and sample.min() >= 0 and sample.max() < xy
+    for b in range(64, xy, 64):                                # both sides of every chunk boundary, next to a row-tile boundary
+        for x in (b - 1, b):
+            ys = sample[:nx][sample[:nx, 0] == x, 1]
+            assert len(ys) and ((ys % 16 == 0) | (ys % 16 == 15)).all(), (xy, x)
+    T = cr.row_tile(xy)
+    for t in range(T, xy, T):
+        assert (sample[:, 1] == t - 1).any() and (sample[:, 1] == t).any(), (xy, t)
+    for name, pos in cr.large_patterns(xy, short=xy == 4096).items():
+        mask = cr.obstacle_mask(pos, None, 50)
+        ref = cr.large_referee(mask)
+        if ref is None:                                        # (no scipy: the GPU test holds this map on the sample instead)
+            assert name.startswith("random") and not cr.have_scipy()
+            continue
+        assert ref.dtype == np.int32 and (ref == cr.FAR).all() == (not mask.any()) and ((ref == 0) == mask).all(), (xy, name)
+        if cr.have_scipy() and (xy < 4096 or name in ("random_0.1", "corner_far")):
+            assert np.array_equal(ref, cr.feature_transform(mask)), (xy, name)
+        if xy <= 520:
+            assert np.array_equal(ref, cr.separable(mask)), (xy, name)
+            if name in ("random_0.1", "full_column", "all", "lonely"):
+                assert np.array_equal(ref, cr.by_rows(mask)), (xy, name)      # (by_rows on many rows too, where that is cheap)
+        else:
+            assert np.array_equal(ref[sample[:, 0], sample[:, 1]], cr.brute_force_near(mask, sample)), (xy, name)
+
+
+def test_brute_force_near_is_brute_force():
+    xy = 200
+    cells = cr.boundary_sample(xy)
+    for name, (pos, neg) in cr.patterns(xy).items():
+        mask = cr.obstacle_mask(pos, neg, 50)
+        assert np.array_equal(cr.brute_force_near(mask, cells, r=5 if name == "random_1" else 48), cr.brute_force(mask, 0, cells)), name
+    far = cr.brute_force_near(cr.obstacle_mask(cr.patterns(xy)["random_0.1"][0]), cells, r=5)
+    assert (far > 25).sum() > 100                              # cells the window did not settle: they went to the full list
+
+
+@pytest.mark.parametrize("xy", cr.LARGE)
+def test_large_patterns_reach_the_code_they_are_meant_for(xy):
+    """on the referee alone: what of k_clearance_rows / k_clearance_cols the large maps run that the four small sizes cannot"""
+    pats = cr.large_patterns(xy, short=xy == 4096)
+    chunks = (xy + 63) // 64
+    assert chunks > 4                                          # a wave's chunk loop makes a second trip
+    far = cr.large_referee(pats["corner_far"] > 50)
+    assert far[0, xy - 1] == far.max() == 2 * (xy - 1) ** 2 < cr.FAR
+    caps = cr.large_caps(xy)
+    assert caps[:4] == (0, 1, 25, 2500) and int(np.sqrt(caps[4])) >= xy and ((far > caps[4]) & (far < cr.FAR)).sum() > 0 and (far <= caps[4]).sum() > 0
+    for c in caps[1:4]:                                        # each cap has cells on both sides
+        assert (far <= c).any() and (far == c).any() and (far > c).any()
+    same, adj = pats["boundary_same_row"] > 50, pats["boundary_adjacent_rows"] > 50
+    bounds = list(range(64, xy, 64))
+    assert len(bounds) == (xy - 1) // 64 and same.sum() == adj.sum() == 2 * len(bounds)
+    for b in bounds:
+        assert same[b - 1, 5] and same[b, 5] and adj[b - 1, xy // 2] and adj[b, xy // 2 + 1]
+    if xy == 4096:
+        assert bounds[-1] == 4032 and same[4031, 5] and same[4032, 5] and chunks == 64      # chunk 62 | 63
+    assert same[:, 5].reshape(-1)[:64 * (xy // 64)].reshape(-1, 64).any(axis=1).all()   # every whole chunk of that row holds an obstacle
+    lonely = pats["lonely"] > 50
+    d = cr.large_referee(lonely)
+    assert lonely[:, 16].sum() == 2 and lonely[0, 16] and lonely[xy - 1, 16]                # chunks 1 .. chunks - 2 of row 16 are empty
+    xs = np.arange(xy)
+    assert lonely.sum() == 2 and np.array_equal(d[:, 16], np.minimum(xs, xy - 1 - xs) ** 2)
+    # one obstacle in the map, at the end of its row: the row's first cell finds it across every mask, xy - 1 cells away
+    assert far[0, 0] == (xy - 1) ** 2 and (pats["corner_far"] > 50).sum() == 1 and pats["corner_far"][xy - 1, 0] > 50
+    left = cr.large_referee(pats["corner_0n"] > 50)
+    assert left[xy - 1, xy - 1] == (xy - 1) ** 2 and left[xy - 1, 0] == 2 * (xy - 1) ** 2 and (pats["corner_0n"] > 50).sum() == 1
+    rnd = pats["random_0.1"] > 50
+    assert 0.0005 * xy * xy <= rnd.sum() <= 0.002 * xy * xy
+    if xy < 4096:
+        dense = pats["random_30"] > 50
+        assert 0.25 * xy * xy <= dense.sum() <= 0.35 * xy * xy and not pats["none"].any() and (pats["all"] > 50).all()
+        assert (pats["full_row"] > 50)[:, xy // 3].all() and (pats["full_column"] > 50)[xy // 3, :].all()
+        assert (pats["corners"] > 50).sum() == 4
+
+
+def test_the_launch_shape_names_are_documented():
+    header = open(os.path.join(ROOT, "include", "gvom_hip.h")).read()
+    source = open(os.path.join(ROOT, "g-vom_amd", "csrc", "gvom_handle.hip")).read()
+    for name in ("clearance_lgw", "clearance_rows_per_tile", "clearance_lds_bytes", "clearance_chunks"):
+        assert '"%s"' % name in header and '"%s"' % name in source, name
+
+
 def test_referee_mask_threshold_negative_and_distance():
     pos = np.array([[49, 50], [51, 0]], np.int32)
     neg = np.array([[0, 0], [0, 100]], np.int32)

@@ -1,9 +1,15 @@
 """Cost-to-go fields on the GPU (gvom_cost_to_go: k_ctg_seed, k_ctg_relax, k_ctg_dirs, k_travcost; DeviceMaps.cost_to_go,
 Gvom.cost_to_go_of, Gvom.cost_to_go_of_device) against the referee of tests/costfield_ref.py: the field, the directions, the cost
-map and the call's info with tolerance 0 -- everything is integer.  Synthetic maps on grids of 16, 31, 32, 33, 50, 64, 65 and 100
-cells (one partial tile; each side of the tile edges 16, 32, 64; ragged last tiles; exactly 2 x 2 tiles; 4 x 4 with a ragged rim),
+map and the call's info with tolerance 0 -- everything is integer.  Synthetic maps on grids of 16, 31, 32, 33, 50, 64, 65, 100 and
+129 cells (one partial tile; each side of the tile edges 16, 32, 64; ragged last tiles; exactly 2 x 2 tiles; 4 x 4 with a ragged
+rim; 5 x 5 with a last tile one cell wide), 1024 cells (32 x 32 tiles) against Dijkstra and 4096 cells (128 x 128 tiles, the
+largest map accepted) against a closed form and the Bellman check of tests/costfield_ref.py,
 the obstacle scenes end to end through combine_maps_device() on rings of one and two slots, an early stop, snapshots, the product
-pool, errors, and a torch consumer in a child process.  tests/test_costfield_cpu.py holds the census of every input."""
+pool, errors, and a torch consumer in a child process.  tests/test_costfield_cpu.py holds the census of every input.
+
+Wall time on the MI355X (pytest --durations, one run): 129 cells 0.30 s (100 cells: 0.18 s); 1024 cells open / random / random_cut /
+seventeen_goals 2.08 / 1.66 / 0.87 / 1.73 s (Dijkstra included; 33 / 49 / 35 / 29 rounds); 4096 cells open 1.90 s (129 rounds, 48,896
+tile relaxations), random 9.77 s (171 rounds, 601,562 tile relaxations; about half of it is the Bellman check on the host)."""
 import ctypes
 import os
 import subprocess
@@ -97,6 +103,74 @@ def test_synthetic_maps_match_the_referee_exactly(handles, xy):
     if xy > 64:
         assert rounds["serpentine"] > rounds["open"]              # the wavefront crosses a tile boundary per corridor
     assert rounds["all_blocked"] == 1 and rounds["single_free_goal"] == 1
+
+
+# ---- beyond 4 x 4 tiles: 1024 cells (32 x 32 tiles) and 4096 (128 x 128, the largest map the call accepts) ---------------------------
+# 129 cells (5 x 5 tiles, the last one cell wide) run every pattern above, as a member of cf.SIZES.
+
+@pytest.fixture(scope="module")
+def large_handles(gvom):
+    made = {}
+
+    def get(xy):
+        if xy not in made:
+            made.clear()                                           # (one large mapper at a time)
+            made[xy] = gvom.Gvom(0.4, 0.2, xy, 1, 1, 1.0, 0.5, 0.5, 0.3, 2.0, 4.0, 1.0, 1, 1, voxel_statistics=False)
+        return made[xy]
+    yield get
+    made.clear()
+
+
+@pytest.mark.parametrize("name", ["open", "random", "random_cut", "seventeen_goals"])
+def test_1024_cells_match_dijkstra(large_handles, name):
+    xy = 1024
+    g = large_handles(xy)
+    c, goals, cap, D, d, info = cf.large_expected(xy, name)
+    f = g.cost_to_go_of(np.asfortranarray(c), goals, max_cost=cap or None)
+    print(xy, name, "rounds", f.rounds, "tile relaxations", g.get_tuning("cost_to_go_tiles"))
+    assert f.rounds >= (32 if name == "open" else 2)               # (open: from the corner goal the wavefront crosses the 32 tiles of a side, one a round)
+    _hold(f, c, D, d, info, "xy %d, %s" % (xy, name))
+    if name == "random_cut":
+        full = cf.large_expected(xy, "random")[3]
+        assert 0.25 * info[0] < ((full != U) & (D == U)).sum() < 3 * info[0]      # the cap cuts about half of the reachable cells off
+
+
+def test_4096_cells_open_map_matches_the_closed_form(large_handles):
+    """one goal in the corner of an all-ones map of 128 x 128 tiles: D = 14 min(dx, dy) + 10 |dx - dy| (cf.open_field, pinned to
+    Dijkstra by tests/test_costfield_cpu.py); the far corner holds 14 * 4095"""
+    xy = 4096
+    g = large_handles(xy)
+    c, goals = cf.large_patterns(xy)["open"]
+    D = cf.open_field(xy)
+    assert D[xy - 1, xy - 1] == 14 * (xy - 1) and D[xy - 1, 0] == 10 * (xy - 1)
+    f = g.cost_to_go_of(np.asfortranarray(c), goals)
+    print(xy, "open: rounds", f.rounds, "tile relaxations", g.get_tuning("cost_to_go_tiles"))
+    assert f.rounds >= 128
+    _hold(f, c, D, cf.directions(D, c), (xy * xy, 1), "xy 4096, open")
+
+
+def test_4096_cells_random_map_passes_the_bellman_check(large_handles):
+    """random costs, a quarter of the cells blocked, 128 x 128 tiles: the field is held to cf.bellman -- the conditions that make
+    a field THE cost-to-go field, pinned to Dijkstra on the small maps -- and the directions, reached and goals_seeded to it"""
+    xy = 4096
+    g = large_handles(xy)
+    c, goals = cf.large_patterns(xy)["random"]
+    f = g.cost_to_go_of(np.asfortranarray(c), goals)
+    print(xy, "random: rounds", f.rounds, "tile relaxations", g.get_tuning("cost_to_go_tiles"))
+    with f:
+        cost, direction, cell = f.copy_to_host()
+    assert cost.dtype == np.int32 and cost.shape == direction.shape == cell.shape == (xy, xy)
+    assert np.array_equal(cell, c)
+    bad, d = cf.bellman(cost, c, goals)
+    assert bad == {}, bad
+    if not np.array_equal(direction, d):
+        wrong = np.argwhere(direction != d)
+        raise AssertionError("the directions differ in %d cells, first (%d, %d): got %d, referee %d" % (
+            len(wrong), wrong[0][0], wrong[0][1], direction[tuple(wrong[0])], d[tuple(wrong[0])]))
+    reached = int((cost != U).sum())
+    assert (f.converged, f.reached, f.goals_seeded) == (True, reached, 1) and f.rounds >= 64
+    assert 0.7 * xy * xy < reached < 0.76 * xy * xy                # (a quarter is blocked; the free cells percolate, a few pockets aside)
+    assert not np.array_equal(cost, cost.T)
 
 
 @pytest.mark.parametrize("xy", [33, 100])

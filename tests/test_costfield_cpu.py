@@ -30,6 +30,56 @@ def test_the_two_referee_forms_agree(xy):
             assert reach / 4 <= cut <= 3 * reach / 4, (xy, name, cut, reach)
 
 
+@pytest.mark.parametrize("xy", cf.SIZES)
+def test_the_bellman_check_accepts_dijkstra_and_nothing_else(xy):
+    """cf.bellman -- what tests/test_costfield.py holds the 4096-cell random map to -- on every small pattern: no violation on
+    Dijkstra's field and the same directions; a single cell raised by 1, lowered by 1, or marked unreached although reachable is
+    rejected, each under the condition it breaks"""
+    rng = np.random.default_rng(xy)
+    for name, (c, goals, cap) in cf.patterns(xy).items():
+        D, d, _ = cf.expected(xy, name)
+        bad, dirs = cf.bellman(D, c, goals, cap)
+        assert bad == {} and np.array_equal(dirs, d), (xy, name, bad)
+        inner = np.argwhere((D != U) & (D != 0))
+        if len(inner) == 0:
+            continue
+        for x, y in inner[rng.choice(len(inner), min(6, len(inner)), replace=False)]:
+            for delta, word in ((1, "no_match"), (-1, "offers_less")):
+                M = D.copy()
+                M[x, y] += delta
+                bad, _ = cf.bellman(M, c, goals, cap)
+                # raised: a neighbour now offers less than the cell holds; lowered: none of its offers equals it any more
+                assert word in bad or "no_match" in bad or "offers_less" in bad, (xy, name, x, y, delta, bad)
+            M = D.copy()
+            M[x, y] = U
+            bad, _ = cf.bellman(M, c, goals, cap)
+            assert "left_out" in bad, (xy, name, x, y, bad)         # (its best offer is the value it had: at or below the cap)
+    c, goals, cap = cf.patterns(xy)["random"]
+    D = cf.expected(xy, "random")[0]
+    gx, gy = np.argwhere(D == 0)[0]
+    for M, word in ((np.where(D == 0, 5, D), "goal"), (np.where(c == 0, 7, D), "blocked")):
+        assert word in cf.bellman(M, c, goals, cap)[0], (xy, word)
+    twice = D.copy()
+    twice[D != U] *= 2                                            # every value doubled: consistent with nothing
+    assert cf.bellman(twice, c, goals, cap)[0]
+    c, goals, cap = cf.patterns(xy)["random_cut"]
+    over = cf.dijkstra(c, goals)                                   # the uncut field under the cut's cap
+    assert "above_cap" in cf.bellman(over, c, goals, cap)[0]
+
+
+def test_the_closed_form_of_the_open_map_and_the_large_patterns():
+    for xy, goal in ((100, (0, 0)), (129, (0, 0)), (65, (64, 0)), (50, (17, 30))):
+        assert np.array_equal(cf.open_field(xy, goal), cf.dijkstra(np.ones((xy, xy), np.int32), [goal])), (xy, goal)
+    for xy in (65, 129):                                           # large_patterns builds what patterns builds, without the other ten
+        small, large = cf.patterns(xy), cf.large_patterns(xy)
+        for name in ("open", "random", "seventeen_goals"):
+            assert np.array_equal(small[name][0], large[name][0]) and np.array_equal(small[name][1], large[name][1]), (xy, name)
+        c, goals, cap, D, d, info = cf.large_expected(xy, "random_cut")
+        assert cap == small["random_cut"][2] and np.array_equal(D, cf.expected(xy, "random_cut")[0]) and info == cf.expected(xy, "random_cut")[2]
+    assert cf.LARGE == (1024, 4096) and [(xy + cf.TILE - 1) // cf.TILE for xy in cf.SIZES[-1:] + cf.LARGE] == [5, 32, 128]
+    assert 129 % cf.TILE == 1                                      # the last tile of 129 cells is one cell wide
+
+
 def test_weights_and_the_early_stop_of_the_sweeps():
     c = np.array([[1, 1], [65535, 65535]], np.int32)
     D = cf.dijkstra(c, [(0, 0)])
@@ -242,6 +292,7 @@ CENSUS_FLOOR = {
     64: dict(blocked=12900, reached=25000, pocket=290, cut=4100, corner_rule=15900, ties=13000, crossings3=3400),
     65: dict(blocked=13200, reached=26000, pocket=270, cut=4300, corner_rule=16500, ties=13500, crossings3=9000),
     100: dict(blocked=31000, reached=61000, pocket=700, cut=10000, corner_rule=39000, ties=32000, crossings3=33000),
+    129: dict(blocked=51000, reached=103000, pocket=1000, cut=16900, corner_rule=66000, ties=55000, crossings3=66000),
 }
 
 
@@ -253,6 +304,7 @@ def test_census_of_the_synthetic_patterns(xy):
        32:  3998 /  7925 /  74 /  1315 /  4802 /  3782 /     0        33:  4201 /  8452 / 114 /  1390 /  5429 /  4071 /   551
        50:  9916 / 19239 / 181 /  3164 / 12231 /  9779 /  2278        64: 16186 / 31511 / 366 /  5185 / 19943 / 16394 /  4258
        65: 16507 / 32694 / 342 /  5382 / 20712 / 16904 / 11379       100: 39096 / 77302 / 897 / 12705 / 48941 / 41150 / 42208
+      129: 64563 / 129251 / 1302 / 21217 / 82551 / 69358 / 83125
     (a map of one tile has no tile boundary: the crossings are held from 33 cells on)"""
     total, per = {}, {}
     for name, (c, goals, cap) in cf.patterns(xy).items():

@@ -5,7 +5,12 @@ moving ego: the three grids of tests/multi_origin_ref.py (power of two, no power
 adopted eager fusion) and 2 (k_fuse); 1, 63, 65 and 4,096 rays, one origin and one per ray, host and device inputs, the four flag
 combinations.  Then: self-consistency with the scan that made the map, snapshots, the product pool, errors, and a torch consumer
 in a child process.  tests/test_raycast_cpu.py holds the census floors of the inputs on the CPU referee; they are asserted again
-here on the GPU's own maps."""
+here on the GPU's own maps.  Also: two grids of 128 and 192 cells (2 and 3 tile segments per storage row: tests/raycast_ref.py
+WIDE), whose dense state is held to the oracle first, and the np2 grid with its window origin beyond 2^24 voxels (FAR).
+
+Wall time on the MI355X (pytest --durations, one run): the six cases of test_rays_match_the_referee_exactly 0.03 to 0.05 s each
+(module fixture 0.5 s); the four wide-grid cases 0.15 to 0.19 s each (their fixture, which also builds the far maps, 0.23 s);
+the two far cases 0.04 s each, the far self-consistency check 0.02 s."""
 import ctypes
 import os
 import subprocess
@@ -62,12 +67,10 @@ def hip():
     h.free()
 
 
-@pytest.fixture(scope="module")
-def maps(gvom):
-    """per (grid, buffer_size): (handle, dense fused state, window origin, rays) -- built once, never changed"""
+def _build_maps(gvom, grids):
     out = {}
-    for grid in sorted(GRIDS):
-        xr, zr, xy, zs = GRIDS[grid]
+    for grid in sorted(grids):
+        xr, zr, xy, zs = rr.GRIDS[grid]
         for bs in (1, 2):
             g = rr.build_map(gvom.Gvom, grid, bs, voxel_statistics=False)
             assert (g.get_tuning("fuse_kernel") == 6) == (bs == 1)          # 6: an adopted k_encfuse; else k_fuse*
@@ -77,6 +80,18 @@ def maps(gvom):
             assert all(int(W[k]) % (xy if k < 2 else zs) != 0 for k in range(3)), W      # non-zero storage offsets on every axis
             out[grid, bs] = (g, state, W, rr.rays_of(grid, state, W))
     return out
+
+
+@pytest.fixture(scope="module")
+def maps(gvom):
+    """per (grid, buffer_size): (handle, dense fused state, window origin, rays) -- built once, never changed"""
+    return _build_maps(gvom, GRIDS)
+
+
+@pytest.fixture(scope="module")
+def wide_maps(gvom):
+    """the same on the grids of more than one tile segment and on the far-origin grid (tests/raycast_ref.py WIDE, FAR)"""
+    return _build_maps(gvom, list(rr.WIDE) + list(rr.FAR))
 
 
 def _bits(a):
@@ -131,6 +146,65 @@ def test_rays_match_the_referee_exactly(maps, hip, grid, bs):
     assert calls == 32
 
 
+def _all_routes(g, hip, state, W, grid, A, B, what):
+    """the 4,096 rays under the four flag combinations, one origin and one per ray, host and device inputs: every answer equals the
+    referee's; returns the answer of the census call"""
+    dev = {"a": hip.upload(A), "b": hip.upload(B)}
+    census = None
+    for ub, ct in FLAGS:
+        for one in (True, False):
+            o = A[:1] if one else A
+            want = rr.walk(state, W, grid, o, B, unknown_blocks=ub, check_target=ct)
+            w = "%s, K %s, flags %d%d" % (what, "1" if one else "n", ub, ct)
+            res, _ = _hold(g.raycast(o[0] if (one and ub) else o, B, unknown_blocks=ub, check_target=ct), want, W, w + ", host")
+            _hold(g.raycast_device(dev["a"], 1 if one else len(B), dev["b"], len(B), unknown_blocks=ub, check_target=ct), want, W, w + ", device")
+            if not one and (ub, ct) == (rr.CENSUS_FLAGS["unknown_blocks"], rr.CENSUS_FLAGS["check_target"]):
+                census = res
+    return census
+
+
+@pytest.mark.parametrize("bs", [1, 2])
+@pytest.mark.parametrize("grid", sorted(rr.WIDE))
+def test_rays_on_maps_of_several_tile_segments_match_the_referee_exactly(wide_maps, hip, grid, bs):
+    """128 and 192 cells wide: 2 and 3 tile segments per storage row, so that the tile index of k_raycast (row * nseg + (sx >> 6))
+    is held for storage columns 64 and up.  The dense state the referee walks comes from the same handle (k_read_dense, which has
+    its own tile index); it is first held, class by class, to an oracle mapper fed the same scans, so that an error the two
+    kernels share cannot cancel.  Then the census: every status, stops in every storage segment, rays that cross a segment
+    boundary -- on the GPU's own map and answer.  (With sx >> 6 replaced by 0 in a scratch build this test fails on both grids
+    and both buffer sizes while the three narrow grids and the far grid pass: DESIGN.md 9.5.)"""
+    from oracle import oracle
+    g, state, W, (A, B, fam) = wide_maps[grid, bs]
+    o = rr.build_map(oracle.OracleGvom, grid, bs)
+    assert np.array_equal(np.asarray(o.combined_origin, np.float64), W)
+    got, want = rr.state_class(state), rr.state_class(np.asarray(o.combined_index_map))
+    assert np.array_equal(got, want), "%s, buffer %d: %d voxels differ from the oracle in their class, first %d: %d, oracle %d" % (
+        grid, bs, int((got != want).sum()), np.flatnonzero(got != want)[0], got[got != want][0], want[got != want][0])
+    assert min(np.bincount(got, minlength=3)) >= 64
+    res = _all_routes(g, hip, state, W, grid, A, B, "%s, buffer %d" % (grid, bs))
+    per_status, at8, at4 = rr.census(res)
+    _, _, visits = rr.walk(state, W, grid, A, B, record=True, **rr.CENSUS_FLAGS)       # (res IS this walk's result: held above)
+    stops, crossing = rr.segment_census(res, visits, W, grid)
+    print(grid, bs, per_status, at8, at4, stops, crossing)
+    assert min(per_status) >= rr.STATUS_FLOOR, per_status
+    assert rr.STEP_FLOOR[grid][0] == 8 and at8 >= rr.STEP_FLOOR[grid][1], at8
+    assert len(stops) == (rr.GRIDS[grid][2] + 63) // 64 >= 2 and min(stops) >= rr.SEGMENT_STOP_FLOOR, stops
+    assert crossing >= rr.SEGMENT_CROSS_FLOOR, crossing
+    assert (res[fam == 4, 0] == rr.INVALID).all() and (res[fam == 2, 3] == 0).all()
+
+
+@pytest.mark.parametrize("bs", [1, 2])
+def test_rays_far_from_the_world_origin_match_the_referee_exactly(wide_maps, hip, bs):
+    """every axis of the window origin beyond 2^24 voxels (tests/raycast_ref.py FAR): gvom_raycast switches to the literal float64
+    lookup (Q.lit) on a grid that otherwise takes the integer one.  Out there a float32 voxel coordinate has a spacing of 2: most
+    steps do not move the position at all -- the reference's arithmetic, which the referee and the kernel share bit for bit"""
+    g, state, W, (A, B, fam) = wide_maps["far", bs]
+    assert (np.abs(W) >= 2.0 ** 24).all() and (W > 0).any() and (W < 0).any(), W
+    res = _all_routes(g, hip, state, W, "far", A, B, "far, buffer %d" % bs)
+    per_status, _, _ = rr.census(res)
+    print("far", bs, per_status)
+    assert min(per_status) >= rr.STATUS_FLOOR, per_status
+
+
 def test_float64_inputs_are_rounded_to_float32_and_lists_are_taken(maps):
     g, state, W, (A, B, fam) = maps["np2", 2]
     a64, b64 = A[:300].astype(np.float64) + 1e-9, B[:300].astype(np.float64) + 1e-9
@@ -153,8 +227,7 @@ def test_numba_cuda_typing_changes_the_step_rule_as_in_the_scan(gvom):
     print("rays whose step count depends on the typing:", int((S32 != S64).sum()))
 
 
-@pytest.mark.parametrize("grid", sorted(GRIDS))
-def test_a_scan_and_its_own_rays_agree(gvom, grid):
+def _scan_and_own_rays(gvom, grid):
     """Independent of the referee: ONE scan with a float32-representable ego into an empty one-slot map, then combine.  The rays
     from the ego to every return that passes min_distance walk exactly the voxels the scan marked: none of them is unknown, and a
     ray whose return lies inside the window ends OCCUPIED or CLEAR -- with the one exception the reference's step rule makes: the
@@ -162,7 +235,7 @@ def test_a_scan_and_its_own_rays_agree(gvom, grid):
     return, and for a return in the outermost voxel layer of the window that sample can be outside (k_trace's ray ends there the
     same way).  Such a ray is LEFT_WINDOW: on the CPU referee 1 of 5,492 in-window returns on np2, none on p2 and tall.  The
     condition is therefore held for the returns at least one voxel away from every face, and the rim may also leave."""
-    xr, zr, xy, zs = GRIDS[grid]
+    xr, zr, xy, zs = rr.GRIDS[grid]
     g = gvom.Gvom(*rr.params(grid, 1), voxel_statistics=False)
     ego = rr.ego_of(grid, 1)
     cloud = rr.cloud_of(grid, 1)
@@ -184,7 +257,22 @@ def test_a_scan_and_its_own_rays_agree(gvom, grid):
     print(grid, "rim returns whose ray leaves the window:", int((result[inside & ~core, 0] == rr.LEFT_WINDOW).sum()), "of", int((inside & ~core).sum()))
     assert np.isin(result[inside, 0], (rr.OCCUPIED, rr.CLEAR, rr.LEFT_WINDOW)).all()
     assert np.isin(result[~inside, 0], (rr.OCCUPIED, rr.CLEAR, rr.LEFT_WINDOW)).all()
+    return result, W
+
+
+@pytest.mark.parametrize("grid", sorted(GRIDS))
+def test_a_scan_and_its_own_rays_agree(gvom, grid):
+    result, _ = _scan_and_own_rays(gvom, grid)
     assert (result[:, 0] == rr.CLEAR).sum() >= 32 and (result[:, 0] == rr.LEFT_WINDOW).sum() >= 32
+
+
+def test_a_scan_and_its_own_rays_agree_far_from_the_world_origin(gvom):
+    """the same check with the window origin beyond 2^24 voxels on every axis.  No ray leaves the window there: the ego's float32
+    voxel coordinates have a spacing of 2, a step of at most one voxel moves them at most once, and every sample stays inside (on
+    the CPU referee: 2,565 CLEAR, 5,627 OCCUPIED, 0 LEFT_WINDOW of 8,192) -- so the floor is held on OCCUPIED instead"""
+    result, W = _scan_and_own_rays(gvom, "far")
+    assert (np.abs(W) >= 2.0 ** 24).all(), W
+    assert (result[:, 0] == rr.CLEAR).sum() >= 32 and (result[:, 0] == rr.OCCUPIED).sum() >= 32
 
 
 def test_a_product_is_a_snapshot(gvom):

@@ -8,7 +8,14 @@ OCCUPIED / UNKNOWN / LEFT_WINDOW / INVALID; rays that stop at a voxel at step >=
     np2    514 / 3018 / 219 / 249 / 96;    423 / 1041
     tall   811 / 2165 / 577 / 447 / 96;    367 / 1515
 (buffer_size 2 differs by a few rays.)  The tall grid is 16 voxels wide: from its centre a ray leaves after 8 steps in x or y,
-so its step floor is 4; the census shows it would hold the floor at 8 too, through the z axis, which is not asserted."""
+so its step floor is 4; the census shows it would hold the floor at 8 too, through the z axis, which is not asserted.
+
+The grids of more than one tile segment (tests/raycast_ref.py WIDE), same call, buffer_size 1 / 2 -- rays per status; stops at
+step >= 8; stop voxels per 64-cell STORAGE segment; rays whose examined voxels span two or more segments:
+    w128   834 / 2298 / 563 / 305 / 96;  2016;  2313 / 548;        606        840 / 2307 / 549 / 304 / 96;  1993;  2362 / 494;        557
+    w192   914 / 2190 / 532 / 364 / 96;  1686;  2187 / 334 / 201;  616        916 / 2230 / 511 / 343 / 96;  1658;  2268 / 341 / 132;  534
+Storage offsets (window origin mod size) x / y / z: 83 / 50 / 17 and 125 / 75 / 13.  Floors: 100 stops in every segment, 300
+crossing rays.  The far grid (FAR): window origin 17,499,983 / -17,500,029 / 17,499,991 voxels, 2^24 = 16,777,216."""
 import ctypes
 import os
 import re
@@ -37,9 +44,22 @@ def maps():
     return out
 
 
+@pytest.fixture(scope="module")
+def wide_maps():
+    """the same on the ray tests' own grids (tests/raycast_ref.py WIDE, FAR)"""
+    out = {}
+    for grid in list(rr.WIDE) + list(rr.FAR):
+        for bs in (1, 2):
+            g = rr.build_map(oracle.OracleGvom, grid, bs)
+            W = np.asarray(g.combined_origin, np.float64)
+            assert np.array_equal(W, rr.window_origin(grid, rr.ego_of(grid, rr.N_SCANS - 1)))
+            out[grid, bs] = (np.asarray(g.combined_index_map).copy(), W)
+    return out
+
+
 def _special_rays(grid, W):
     """rays that start outside the window, end outside it, are shorter than one voxel, axis-parallel, exact diagonals"""
-    xr, zr, xy, zs = GRIDS[grid]
+    xr, zr, xy, zs = rr.GRIDS[grid]
     res = np.array([xr, xr, zr])
     lo, size = W * res, np.array([xy, xy, zs]) * res
     c = lo + 0.5 * size
@@ -64,7 +84,16 @@ def _special_rays(grid, W):
 @pytest.mark.parametrize("f32_sqrt", [False, True])
 @pytest.mark.parametrize("grid", sorted(GRIDS))
 def test_referee_walks_the_voxels_the_oracle_marks(maps, grid, f32_sqrt):
-    xr, zr, xy, zs = GRIDS[grid]
+    _referee_against_the_oracle(maps, grid, f32_sqrt)
+
+
+@pytest.mark.parametrize("grid", sorted(rr.WIDE))
+def test_referee_walks_the_voxels_the_oracle_marks_on_the_wide_grids(wide_maps, grid):
+    _referee_against_the_oracle(wide_maps, grid, False)
+
+
+def _referee_against_the_oracle(maps, grid, f32_sqrt):
+    xr, zr, xy, zs = rr.GRIDS[grid]
     state, W = maps[grid, 1]
     A, B, fam = rr.rays_of(grid, state, W)
     pick = np.flatnonzero(fam != 4)[::11]                     # ~360 finite rays of every family
@@ -157,6 +186,53 @@ def test_census_floors_of_the_gpu_inputs(maps, grid, bs):
     assert (target[fam == 0, 0] == rr.OCCUPIED).all()         # ends in one: stopped at or before it once the target is examined
     stopped = np.isin(st, (rr.OCCUPIED, rr.UNKNOWN))
     assert np.isfinite(position[stopped]).all() and np.isnan(position[~stopped]).all()
+
+
+@pytest.mark.parametrize("bs", [1, 2])
+@pytest.mark.parametrize("grid", sorted(rr.WIDE))
+def test_wide_inputs_stop_in_every_tile_segment_and_cross_between_them(wide_maps, grid, bs):
+    """the conditions under which tests/test_raycast.py's wide-grid test exercises k_raycast's tile index beyond segment 0, on
+    the referee alone: non-zero storage offsets on every axis, >= 100 stop voxels in every 64-cell storage segment, >= 300 rays
+    whose examined voxels span two or more segments, every status in >= 32 rays, >= 32 stops at step >= 8 (figures: module
+    docstring)"""
+    xr, zr, xy, zs = rr.GRIDS[grid]
+    state, W = wide_maps[grid, bs]
+    assert xy > 64 and all(int(W[k]) % (xy if k < 2 else zs) != 0 for k in range(3)), W
+    assert min(np.bincount(rr.state_class(state), minlength=3)) >= 64
+    A, B, fam = rr.rays_of(grid, state, W)
+    result, position, visits = rr.walk(state, W, grid, A, B, record=True, **rr.CENSUS_FLAGS)
+    per_status, at8, at4 = rr.census(result)
+    stops, crossing = rr.segment_census(result, visits, W, grid)
+    print(grid, bs, per_status, at8, at4, stops, crossing)
+    assert len(stops) == (xy + 63) // 64 >= 2 and min(stops) >= rr.SEGMENT_STOP_FLOOR, stops
+    assert crossing >= rr.SEGMENT_CROSS_FLOOR, crossing
+    assert min(per_status) >= rr.STATUS_FLOOR, per_status
+    assert rr.STEP_FLOOR[grid][0] == 8 and at8 >= rr.STEP_FLOOR[grid][1], at8
+    # the segment of a stop is the segment of its STORAGE column: without the offset the counts differ
+    unshifted = np.bincount((result[result[:, 2] >= 0, 2] % xy) >> 6, minlength=len(stops))
+    assert unshifted.tolist() != stops
+    assert (result[fam == 4, 0] == rr.INVALID).all() and (result[fam != 4, 0] != rr.INVALID).all()
+
+
+@pytest.mark.parametrize("bs", [1, 2])
+def test_the_far_grid_lies_beyond_2_to_the_24_voxels_on_every_axis(wide_maps, bs):
+    """where gvom_raycast takes the literal lookup for the origin's sake (gvom_export.hip raycast_params: any |origin| >= 2^24);
+    the grid itself (np2) takes the integer one.  The egos are float32-representable and still move from scan to scan."""
+    xr, zr, xy, zs = rr.GRIDS["far"]
+    assert rr.GRIDS["far"] == GRIDS["np2"] and zs <= xy
+    state, W = wide_maps["far", bs]
+    assert (np.abs(W) >= 2.0 ** 24).all() and (W > 0).any() and (W < 0).any(), W
+    egos = [rr.ego_of("far", k) for k in range(rr.N_SCANS)]
+    assert all(float(np.float32(v)) == v for e in egos for v in e)
+    origins = [rr.window_origin("far", e) for e in egos]
+    assert all((np.abs(o) >= 2.0 ** 24).all() for o in origins)
+    assert all(not np.array_equal(origins[k], origins[k + 1]) for k in range(rr.N_SCANS - 1))
+    assert all(int(W[k]) % (xy if k < 2 else zs) != 0 for k in range(3)), W
+    A, B, fam = rr.rays_of("far", state, W)
+    result, _ = rr.walk(state, W, "far", A, B, **rr.CENSUS_FLAGS)
+    per_status, _, _ = rr.census(result)
+    print("far", bs, per_status)
+    assert min(per_status) >= rr.STATUS_FLOOR, per_status
 
 
 def test_header_binding_and_library_agree():

@@ -1,5 +1,5 @@
 // gvom_capi.hip -- the scan unit of the C ABI's host side (the file keeps the name of the former single host unit; the other host
-// units are gvom_handle, gvom_combine, gvom_export and gvom_debug .hip, and gvom_host.h is what they share): parameter setup, the pipeline (upload, layout probe, directional sort, trace, encode or eager
+// units are gvom_handle, gvom_combine, gvom_sets, gvom_product_calls and gvom_debug .hip, and gvom_host.h is what they share): parameter setup, the pipeline (upload, layout probe, directional sort, trace, encode or eager
 // fusion, statistics), the commit into the ring, and the split calls of a sharded map.
 #include "gvom_host.h"
 

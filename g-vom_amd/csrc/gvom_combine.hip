@@ -1,5 +1,5 @@
 // gvom_combine.hip -- host side of a combine: the temporal fusion and the 2-D stage, their completion, the output buffers and every
-// combine entry point that ends in host memory (the device one: gvom_export.hip).
+// combine entry point that ends in host memory (the device one: gvom_sets.hip).
 #include "gvom_host.h"
 
 namespace gvom_host {

@@ -1,10 +1,11 @@
-// gvom_host.h -- private to the host units of libgvom_hip.so (gvom_handle / gvom_capi (scans) / gvom_combine / gvom_export / gvom_debug .hip):
+// gvom_host.h -- private to the host units of libgvom_hip.so (gvom_handle / gvom_capi (scans) / gvom_combine / gvom_sets / gvom_product_calls / gvom_debug .hip):
 // the handle and what it is made of, and the functions that cross those units' boundaries (namespace gvom_host; -fvisibility=hidden
 // keeps them out of the dynamic symbol table).  Not part of the public interface (include/gvom_hip.h is); no kernel unit includes it.
 #pragma once
 #include "gvom_internal.h"
 #include "gvom_ingest.h"
 #include "gvom_outrec.h"
+#include "gvom_setlayout.h"
 #include "../../include/gvom_hip.h"
 
 #include <math.h>
@@ -57,30 +58,15 @@ struct Fused {
     bool has_metrics = false;                  // k_fuse_stats merged the statistics of this map (every source had its own)
 };
 
-// DEVICE MAP SETS (gvom_combine_maps_device): one device allocation per set holding the nine maps of one combine, [y][x] order,
-// each map at a 256-byte aligned offset: the six f64 maps (3 roughness, 4 height, 5 inferred height, 6 / 7 x / y slope,
-// 8 guessed delta) at k * S doubles, then the three i32 maps (0 positive, 1 negative, 2 visibility) behind them at k * S
-// ints, S = dev_map_stride(xy): 60 bytes per cell.  A set is handed out by EXPORTS (the consumer stream waits on `ready`) and
-// taken back by RELEASES (an event recorded on the consumer stream); the combine that reuses the set first makes the handle's
-// stream wait on every release event.  A set with live exports outlives the handle (orphan) and is freed at its last release.
-// PRODUCT SETS (gvom_device_product) are the same thing with another KIND of contents: one allocation with a kind and a shape
-// (set_part() below is the only place that knows the layouts), the same ready event, export count, release events and
-// orphaning.  kind 0 = the nine maps; GVOM_PRODUCT_* otherwise:
-//   occupancy        V bytes, out[x][y][z]
-//   voxel cloud      256-byte header (the uint64 row counter k_voxel_cloud adds to), then cap x 8 and cap x 3 floats, each part
-//                    256-byte aligned
-//   height clouds    xy*xy x 7 / x 3 floats
-//   clearance        xy*xy floats (metres), then xy*xy int32 (squared cells) at the next 256-byte boundary, both [y][x]
-//   raycast          cap x 4 int32 {status, steps, voxel, unknown}, then cap x 3 floats (stop position) at the next 256-byte
-//                    boundary; cap = the rays of the call that wrote it
-//   cost field       xy*xy int32 (cost to go), then xy*xy uint8 (direction), then xy*xy uint16 (cell costs), each at the next
-//                    256-byte boundary, all [y][x]
-struct DevSet {
-    char *mem = nullptr;
+// DEVICE MAP SETS (gvom_combine_maps_device): one device allocation per set holding the nine maps of one combine.  A set is handed
+// out by EXPORTS (the consumer stream waits on `ready`) and taken back by RELEASES (an event recorded on the consumer stream); the
+// combine that reuses the set first makes the handle's stream wait on every release event.  A set with live exports outlives the
+// handle (orphan) and is freed at its last release.  PRODUCT SETS (gvom_device_product and the other product calls) are the same
+// thing with another KIND of contents: one allocation with a kind and a shape, the same ready event, export count, release events
+// and orphaning.  What a set of each kind holds, and where: gvom_setlayout.h, the only place that knows the layouts.
+struct DevSet : SetShape {                     // (mem, xy, kind, zs, cap: gvom_setlayout.h)
     size_t bytes = 0;
-    int device = 0, xy = 0;
-    int kind = 0, zs = 0;                      // GVOM_PRODUCT_* (0: a map set); z_size (occupancy)
-    int64_t cap = 0;                           // voxel cloud: rows the allocation holds; raycast: rays of the product
+    int device = 0;
     hipEvent_t ready = nullptr;                // recorded on the handle's stream behind the set's k_map2d
     int64_t id = -1;                           // sequence number of the combine that wrote it; -1: free
     int exports = 0;                           // live exports
@@ -89,7 +75,7 @@ struct DevSet {
     bool orphan = false;                       // the handle is gone
 };
 #define GVOM_MAX_DEVICE_SETS 8
-#define GVOM_N_PRODUCT_KINDS 4                  // the kinds gvom_device_product makes (clearance and raycast products have entry points of their own)
+#define GVOM_N_PRODUCT_KINDS 4                  // the kinds gvom_device_product makes (clearance products, raycast products and cost fields have entry points of their own)
 #define GVOM_RAYCAST_MAX_RAYS ((int64_t)1 << 26)
 #define GVOM_CTG_MAX_GOALS 65536
 #define GVOM_CTG_MAX_BATCH 16                   // rounds enqueued between two looks at the counters: at most
@@ -98,7 +84,7 @@ struct DevSet {
 #define CTG_CNT_REACHED 32
 #define CTG_CNT_SEEDED 33
 // DevSet::exports / rel* / orphan: a DLPack deleter runs on whatever thread frees the consumer's tensor, without the handle
-extern std::mutex g_set_mu;                               // (gvom_export.hip)
+extern std::mutex g_set_mu;                               // (gvom_sets.hip)
 }  // namespace gvom_host
 
 using namespace gvom_host;
@@ -364,8 +350,6 @@ inline int clamp_delta(int64_t d, int size)
     return (int)d;
 }
 
-inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 // the ring-window phase of a map whose window starts at world voxel `origin`: om = origin mod size (gvom_internal.h "STORAGE LAYOUT")
 inline void window_phase(const gvom_handle *h, const int64_t origin[3], int om[3])
 {
@@ -400,10 +384,14 @@ int fuse_impl(gvom_handle *h, hipStream_t on = nullptr);
 int map2d_impl(gvom_handle *h, bool gathered, bool publish, char *out_dev, bool yx, const double *occ = nullptr,
                hipStream_t on = nullptr, uint32_t done_seq = 0, bool dev_set = false, void *host_out = nullptr);
 int settle_count(gvom_handle *h);
-// gvom_export.hip
+// gvom_sets.hip
 void set_free(DevSet *s);
+DevSet *find_set(const std::vector<DevSet *> &sets, int64_t set_id);
+int set_wait_releases(gvom_handle *h, DevSet *set);
+int product_acquire(gvom_handle *h, int kind, size_t need_bytes, size_t new_bytes, const char *fn, int *allocs, DevSet **set);
+int product_publish(gvom_handle *h, DevSet *set, int64_t *product_id);
+// gvom_product_calls.hip
 void occ_params(const gvom_handle *h, const Fused &F, OccParams &P);
 void cloud_params(const gvom_handle *h, const Fused &F, Map2dParams &P);
-void raycast_params(const gvom_handle *h, const Fused &F, ScanParams &P, RayQuery &Q);
 hipError_t launch_height_cloud(gvom_handle *h, const Fused &F, float *out7, float *out3);
 }  // namespace gvom_host

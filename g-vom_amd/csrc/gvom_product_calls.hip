@@ -1,0 +1,347 @@
+// gvom_product_calls.hip -- the calls that MAKE a device product: gvom_device_product (occupancy grid, voxel cloud, the two height
+// clouds), gvom_clearance, gvom_raycast and gvom_cost_to_go, and the frame builders they and the debug reads (gvom_debug.hip) give
+// the kernels.  Every call takes its set through product_acquire and hands it out through product_publish (gvom_sets.hip); what is
+// left in each body is what is particular to that product: its argument checks, its staging and its launches.
+#include "gvom_host.h"
+
+namespace gvom_host {
+// what every kernel that reads a fused map takes of its frame: size, ring-window phase, slab rows, segment count, tile epoch
+template <class P> static void fused_frame(const gvom_handle *h, const Fused &F, P &p, int &y_lo, int &y_hi)
+{
+    memset(&p, 0, sizeof p);
+    p.xy = h->prm.xy_size; p.zs = h->prm.z_size;
+    window_phase(h, F.origin, p.om);
+    y_lo = h->sy_lo; y_hi = h->sy_hi;
+    p.nseg = h->nseg; p.epoch = F.epoch;
+}
+
+void occ_params(const gvom_handle *h, const Fused &F, OccParams &P) { fused_frame(h, F, P, P.y_lo, P.y_hi); }
+
+void cloud_params(const gvom_handle *h, const Fused &F, Map2dParams &P)
+{
+    fused_frame(h, F, P, P.y_lo, P.y_hi);
+    P.xy_res = h->prm.xy_resolution; P.z_res = h->prm.z_resolution;
+}
+
+// the frame of the fused map F as k_raycast reads it (gvom_launch_raycast names the fields), and what of a query depends on it
+static void raycast_params(const gvom_handle *h, const Fused &F, ScanParams &P, RayQuery &Q)
+{
+    const gvom_params &p = h->prm;
+    fused_frame(h, F, P, P.sy_lo, P.sy_hi);
+    P.xy_res = p.xy_resolution; P.z_res = p.z_resolution;
+    P.drcp[0] = 1.0 / p.xy_resolution; P.drcp[1] = 1.0 / p.z_resolution;
+    P.fastdiv = h->tune_fastdiv == 0 ? 0 : h->fastdiv_ok;
+    P.f32_sqrt = h->f32_sqrt ? 1 : 0;
+    bool far = false;
+    for (int k = 0; k < 3; ++k) {
+        P.origin[k] = (double)F.origin[k];
+        far = far || F.origin[k] <= -((int64_t)1 << 24) || F.origin[k] >= ((int64_t)1 << 24);
+    }
+    Q.lit = (far || p.z_size > p.xy_size) ? 1 : 0;        // (the integer window test assumes z_size <= xy_size and a near origin)
+    Q.cap = (uint32_t)p.xy_size + (uint32_t)p.z_size;
+}
+
+hipError_t launch_height_cloud(gvom_handle *h, const Fused &F, float *out7, float *out3)
+{
+    const double org[3] = {(double)F.origin[0], (double)F.origin[1], (double)F.origin[2]};
+    int om[3];
+    window_phase(h, F.origin, om);
+    return gvom_launch_debug_height(h->stream, h->prm.xy_size, om[0], om[1], org, h->prm.xy_resolution, h->prm.z_resolution,
+                                    h->height, h->hs, h->rough, h->slope_x, h->slope_y, out7, h->guessed, out3);
+}
+}  // namespace gvom_host
+
+// part `part` of a set as a launcher takes it.  The part numbers below are literals: one the set's kind does not have is a mistake
+// in this file, and stops the process instead of handing a kernel a null pointer
+template <class T> static T *part_ptr(const DevSet *s, int part)
+{
+    SetPart d;
+    if (!set_part(s, part, &d)) { fprintf(stderr, "gvom: a device set of kind %d has no part %d\n", s->kind, part); abort(); }
+    return (T *)d.ptr;
+}
+
+// grows a buffer of the handle to at least `bytes`; an allocation counts in `allocs`
+static int stage_buf(gvom_handle *h, Buf &b, size_t bytes, int &allocs)
+{
+    if (b.bytes >= bytes) return GVOM_OK;
+    const int rc = ensure(h, b, bytes);
+    if (!rc) ++allocs;
+    return rc;
+}
+
+extern "C" {
+// ---- device-resident 3-D products (gvom_device_product) ----------------------------------------------------------------------
+// A snapshot of the current fused map (occupancy grid, voxel cloud) or of the last combine's 2-D maps (the two height clouds),
+// written into a product set on the handle's stream behind whatever produced its inputs; the call enqueues and returns.  Later
+// scans and combines never touch a product: it is a copy, reused only once nobody holds an export of it and behind its
+// consumers' release events.
+
+VIS int gvom_device_product(gvom_t *h, int kind, int64_t max_rows, int64_t *product_id)
+{
+    if (!h || !product_id) return GVOM_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(h->mu);
+    *product_id = -1;
+    static const char *const elsewhere[] = {"a clearance product is made by gvom_clearance", "a raycast product is made by gvom_raycast", "a cost field is made by gvom_cost_to_go"};
+    if (kind >= GVOM_PRODUCT_CLEARANCE && kind <= GVOM_PRODUCT_COSTFIELD) { h->err = std::string("gvom_device_product: ") + elsewhere[kind - GVOM_PRODUCT_CLEARANCE]; return GVOM_ERR_INVALID; }
+    if (kind < 1 || kind > GVOM_N_PRODUCT_KINDS) { h->err = "gvom_device_product: unknown product kind"; return GVOM_ERR_INVALID; }
+    if (h->sharded) { h->err = "gvom_device_product: sharded handles are not supported"; return GVOM_ERR_INVALID; }
+    if (kind == GVOM_PRODUCT_VOXEL_CLOUD) stats_demand(h);                  // a read of the statistics, like gvom_debug_voxel_map
+    if (!h->has_combined) return GVOM_NO_DATA;
+    if ((kind == GVOM_PRODUCT_HEIGHT_CLOUD || kind == GVOM_PRODUCT_INFERRED_HEIGHT_CLOUD) && !h->maps_valid) return GVOM_NO_DATA;
+    if (kind == GVOM_PRODUCT_VOXEL_CLOUD && !h->fused[h->cur].has_metrics) return GVOM_NO_DATA;
+    HIPCHK(h, hipSetDevice(h->device));
+    int64_t cap = 0;
+    if (kind == GVOM_PRODUCT_VOXEL_CLOUD) {
+        cap = max_rows;
+        if (cap <= 0) {                                                      // the fused cell count (settles a device combine's pending count)
+            const int rc0 = settle_count(h);
+            if (rc0) return rc0;
+            cap = h->combined_cell_count;
+        }
+        if (cap < 1) cap = 1;
+    }
+    const int xy = h->prm.xy_size, zs = h->prm.z_size;
+    DevSet *set = nullptr;
+    int rc = product_acquire(h, kind, set_bytes(kind, xy, zs, cap), set_bytes(kind, xy, zs, cap + cap / 2), "gvom_device_product", nullptr, &set);   // (a cloud grows with the map: headroom)
+    if (rc) return rc;
+    set->cap = cap;
+    const Fused &F = h->fused[h->cur];
+    HIPCHK(h, join_second_stream(h));
+    if ((rc = set_wait_releases(h, set))) return rc;
+    switch (kind) {
+    case GVOM_PRODUCT_OCCUPANCY: {
+        OccParams P;
+        occ_params(h, F, P);
+        HIPCHK(h, gvom_launch_occupancy(h->stream, P, F.state, F.tags, (uint8_t *)set->mem, h->tune_occ_clear != 0));
+        break;
+    }
+    case GVOM_PRODUCT_VOXEL_CLOUD: {
+        Map2dParams P;
+        cloud_params(h, F, P);
+        HIPCHK(h, hipMemsetAsync(set->mem, 0, 8, h->stream));
+        HIPCHK(h, gvom_launch_voxel_cloud(h->stream, P, (double)F.origin[0], (double)F.origin[1], (double)F.origin[2], F.state, F.tags,
+                                          (const uint4 *)F.rows.p, (const float *)F.metrics.p, part_ptr<float>(set, 0), part_ptr<float>(set, 1), cap,
+                                          part_ptr<unsigned long long>(set, 2)));
+        break;
+    }
+    case GVOM_PRODUCT_HEIGHT_CLOUD: HIPCHK(h, launch_height_cloud(h, F, (float *)set->mem, nullptr)); break;
+    default: HIPCHK(h, launch_height_cloud(h, F, nullptr, (float *)set->mem)); break;
+    }
+    return product_publish(h, set, product_id);
+}
+
+// ---- obstacle clearance (gvom_clearance) ---------------------------------------------------------------------------------------
+// The distance from every cell to the nearest hard obstacle of a positive / negative map pair, as a product of kind
+// GVOM_PRODUCT_CLEARANCE: two kernels (gvom_clearance.hip) on the handle's stream, behind the k_map2d that wrote the map set
+// they read -- and in front of whatever recycles that set later, which runs on the same stream.  Enqueues and returns.
+VIS int gvom_clearance(gvom_t *h, int64_t map_set_id, const int32_t *positive, const int32_t *negative, int on_device,
+                       double density_threshold, int32_t max_cells2, int flags, int64_t *product_id)
+{
+    if (!h || !product_id) return GVOM_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(h->mu);
+    *product_id = -1;
+    if (h->sharded) { h->err = "gvom_clearance: sharded handles are not supported"; return GVOM_ERR_INVALID; }
+    if (flags & ~GVOM_CLEARANCE_NO_NEGATIVE) { h->err = "gvom_clearance: unknown flag bits"; return GVOM_ERR_INVALID; }
+    if (density_threshold != density_threshold) { h->err = "gvom_clearance: the density threshold is not a number"; return GVOM_ERR_INVALID; }
+    if (map_set_id >= 0 && (positive || negative)) { h->err = "gvom_clearance: give a map set id or map pointers, not both"; return GVOM_ERR_INVALID; }
+    if (map_set_id < 0 && !positive) { h->err = "gvom_clearance: give a map set id or a positive map"; return GVOM_ERR_INVALID; }
+    const int xy = h->prm.xy_size;
+    if (xy > GVOM_CLEARANCE_MAX_XY) { h->err = "gvom_clearance: maps of more than 4096 cells a side are not supported"; return GVOM_ERR_CAPACITY; }
+    const size_t n2 = (size_t)xy * xy;
+    const int32_t *pos = positive, *neg = negative;
+    if (map_set_id >= 0) {
+        DevSet *m = find_set(h->dsets, map_set_id);
+        if (!m) { h->err = "unknown or stale device map set id"; return GVOM_ERR_INVALID; }
+        pos = part_ptr<const int32_t>(m, 0); neg = part_ptr<const int32_t>(m, 1);
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    DevSet *set = nullptr;
+    const size_t bytes = set_bytes(GVOM_PRODUCT_CLEARANCE, xy, 0, 0);
+    int rc = product_acquire(h, GVOM_PRODUCT_CLEARANCE, bytes, bytes, "gvom_clearance", &h->cl_allocs, &set);
+    if (rc) return rc;
+    if ((rc = stage_buf(h, h->cl_g, gvom_clearance_scratch_bytes(xy), h->cl_allocs))) return rc;
+    HIPCHK(h, join_second_stream(h));
+    if (map_set_id < 0 && !on_device) {                                     // host maps: staged, and up before the call returns
+        if ((rc = stage_buf(h, h->cl_stage, 2 * n2 * 4, h->cl_allocs))) return rc;
+        int32_t *st = (int32_t *)h->cl_stage.p;
+        HIPCHK(h, hipMemcpyAsync(st, positive, n2 * 4, hipMemcpyHostToDevice, h->stream));
+        if (negative) HIPCHK(h, hipMemcpyAsync(st + n2, negative, n2 * 4, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        pos = st; neg = negative ? st + n2 : nullptr;
+    }
+    if (flags & GVOM_CLEARANCE_NO_NEGATIVE) neg = nullptr;
+    if ((rc = set_wait_releases(h, set))) return rc;
+    HIPCHK(h, gvom_launch_clearance(h->stream, xy, h->prm.xy_resolution, pos, neg, density_threshold, max_cells2,
+                                    (uint16_t *)h->cl_g.p, part_ptr<float>(set, 0), part_ptr<int32_t>(set, 1), h->cl_shape));
+    return product_publish(h, set, product_id);
+}
+
+// ---- ray queries (gvom_raycast) --------------------------------------------------------------------------------------------------
+// n segments walked through the CURRENT fused map by k_raycast (gvom_query.hip), read-only, on the handle's stream behind
+// whatever produced that map; the result is a product of kind GVOM_PRODUCT_RAYCAST sized by n.  Enqueues and returns; later
+// scans and combines run behind the kernel on the same stream and never touch the product.
+VIS int gvom_raycast(gvom_t *h, const float *from, int64_t K, const float *to, int64_t n, int on_device, int flags,
+                     double origin_voxels[3], int64_t *product_id)
+{
+    if (!h || !product_id) return GVOM_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(h->mu);
+    *product_id = -1;
+    if (h->sharded) { h->err = "gvom_raycast: sharded handles are not supported"; return GVOM_ERR_INVALID; }
+    if (!from || !to) { h->err = "gvom_raycast: from and to must not be NULL"; return GVOM_ERR_INVALID; }
+    if (n < 1) { h->err = "gvom_raycast: n must be at least 1"; return GVOM_ERR_INVALID; }
+    if (K != 1 && K != n) { h->err = "gvom_raycast: K must be 1 or n"; return GVOM_ERR_INVALID; }
+    if (flags & ~(GVOM_RAY_UNKNOWN_BLOCKS | GVOM_RAY_CHECK_TARGET)) { h->err = "gvom_raycast: unknown flag bits"; return GVOM_ERR_INVALID; }
+    if (n > GVOM_RAYCAST_MAX_RAYS) { h->err = "gvom_raycast: more than 2^26 rays in one call"; return GVOM_ERR_CAPACITY; }
+    if (!h->has_combined) return GVOM_NO_DATA;
+    HIPCHK(h, hipSetDevice(h->device));
+    DevSet *set = nullptr;
+    const size_t bytes = set_bytes(GVOM_PRODUCT_RAYCAST, 0, 0, n);
+    int rc = product_acquire(h, GVOM_PRODUCT_RAYCAST, bytes, bytes, "gvom_raycast", &h->rq_allocs, &set);
+    if (rc) return rc;
+    set->cap = n;
+    const Fused &F = h->fused[h->cur];
+    ScanParams P;
+    RayQuery Q;
+    memset(&Q, 0, sizeof Q);
+    raycast_params(h, F, P, Q);
+    Q.from = from; Q.to = to; Q.n = (long)n;
+    Q.one_origin = K == 1 ? 1 : 0;
+    Q.unknown_blocks = (flags & GVOM_RAY_UNKNOWN_BLOCKS) ? 1 : 0;
+    Q.check_target = (flags & GVOM_RAY_CHECK_TARGET) ? 1 : 0;
+    HIPCHK(h, join_second_stream(h));
+    if (!on_device) {                                                       // host segments: staged, and up before the call returns
+        const size_t kb = (size_t)K * 12, nb = (size_t)n * 12;
+        if ((rc = stage_buf(h, h->rq_stage, align256(kb) + nb, h->rq_allocs))) return rc;
+        char *st = (char *)h->rq_stage.p;
+        HIPCHK(h, hipMemcpyAsync(st, from, kb, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(st + align256(kb), to, nb, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        Q.from = (const float *)st; Q.to = (const float *)(st + align256(kb));
+    }
+    if ((rc = set_wait_releases(h, set))) return rc;
+    HIPCHK(h, gvom_launch_raycast(h->stream, P, Q, F.state, F.tags, part_ptr<int32_t>(set, 0), part_ptr<float>(set, 1)));
+    if ((rc = product_publish(h, set, product_id))) return rc;
+    for (int k = 0; origin_voxels && k < 3; ++k) origin_voxels[k] = (double)F.origin[k];
+    return GVOM_OK;
+}
+
+// ---- cost-to-go fields (gvom_cost_to_go) ------------------------------------------------------------------------------------------
+// The navigation function of a cost map -- a caller's, or the one k_travcost builds from a device map set -- as a product of kind
+// GVOM_PRODUCT_COSTFIELD.  The kernels (gvom_costfield.hip) run on the handle's stream behind the combine that wrote the set, and
+// whatever recycles the set later runs behind them.  Unlike the other product calls this one WAITS: rounds of k_ctg_relax are
+// enqueued a batch at a time, the batch's per-round counters come back through pinned memory, and the first round that flagged no
+// tile ends the solve (the rounds enqueued behind it found nothing to do).
+VIS int gvom_cost_to_go(gvom_t *h, int64_t map_set_id, const gvom_ctg_params *params, const int32_t *cost, int on_device,
+                        const int32_t *goals, int64_t n_goals, int32_t max_cost, int32_t max_rounds, int flags,
+                        int64_t *product_id, int64_t info[4])
+{
+    if (!h || !product_id) return GVOM_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(h->mu);
+    *product_id = -1;
+    for (int k = 0; info && k < 4; ++k) info[k] = 0;
+    if (h->sharded) { h->err = "gvom_cost_to_go: sharded handles are not supported"; return GVOM_ERR_INVALID; }
+    if (flags & ~(GVOM_CTG_NO_NEGATIVE | GVOM_CTG_UNKNOWN_BLOCKS)) { h->err = "gvom_cost_to_go: unknown flag bits"; return GVOM_ERR_INVALID; }
+    if (map_set_id >= 0 && cost) { h->err = "gvom_cost_to_go: give a map set id or a cost map, not both"; return GVOM_ERR_INVALID; }
+    if (map_set_id < 0 && !cost) { h->err = "gvom_cost_to_go: give a map set id or a cost map"; return GVOM_ERR_INVALID; }
+    if (map_set_id >= 0 && !params) { h->err = "gvom_cost_to_go: a map set needs the cost parameters"; return GVOM_ERR_INVALID; }
+    if (!goals || n_goals < 1 || n_goals > GVOM_CTG_MAX_GOALS) { h->err = "gvom_cost_to_go: between 1 and 65536 goals"; return GVOM_ERR_INVALID; }
+    if (max_cost < 0 || max_cost > GVOM_CTG_MAX_COST) { h->err = "gvom_cost_to_go: max_cost outside 0 .. 2^30"; return GVOM_ERR_INVALID; }
+    if (max_rounds < 0) { h->err = "gvom_cost_to_go: max_rounds must not be negative"; return GVOM_ERR_INVALID; }
+    const int xy = h->prm.xy_size;
+    if (xy > GVOM_CLEARANCE_MAX_XY) { h->err = "gvom_cost_to_go: maps of more than 4096 cells a side are not supported"; return GVOM_ERR_CAPACITY; }
+    const size_t n2 = (size_t)xy * xy;
+    for (int64_t k = 0; k < 2 * n_goals; ++k)
+        if (goals[k] < 0 || goals[k] >= xy) { h->err = "gvom_cost_to_go: a goal lies outside the window"; return GVOM_ERR_INVALID; }
+    CtgCostParams C;
+    memset(&C, 0, sizeof C);
+    DevSet *m = nullptr;
+    if (map_set_id >= 0) {
+        const gvom_ctg_params &p = *params;
+        const bool ok = p.density_threshold == p.density_threshold && p.inflation_cells2 >= 0 && p.base >= 1 &&
+                        p.soft_weight >= 0 && p.soft_weight <= 65535 && p.unknown_cost >= 0 && p.unknown_cost <= 65535 &&
+                        p.rough_weight >= 0 && p.rough_weight <= 65535 &&
+                        (p.rough_weight == 0 || (isfinite(p.min_roughness) && isfinite(p.max_roughness) && p.max_roughness > p.min_roughness));
+        if (!ok) { h->err = "gvom_cost_to_go: bad cost parameters (NaN threshold, base < 1, a weight outside 0 .. 65535, a negative inflation, or an empty / non-finite roughness range)"; return GVOM_ERR_INVALID; }
+        m = find_set(h->dsets, map_set_id);
+        if (!m) { h->err = "unknown or stale device map set id"; return GVOM_ERR_INVALID; }
+        C.density_threshold = p.density_threshold; C.min_roughness = p.min_roughness; C.max_roughness = p.max_roughness;
+        C.inflation_cells2 = p.inflation_cells2; C.base = p.base; C.soft_weight = p.soft_weight; C.unknown_cost = p.unknown_cost;
+        C.rough_weight = p.rough_weight;
+        C.use_negative = (flags & GVOM_CTG_NO_NEGATIVE) ? 0 : 1; C.unknown_blocks = (flags & GVOM_CTG_UNKNOWN_BLOCKS) ? 1 : 0;
+    } else if (!on_device) {
+        for (size_t k = 0; k < n2; ++k)
+            if (cost[k] < 0 || cost[k] > 65535) { h->err = "gvom_cost_to_go: a host cost map holds a value outside 0 .. 65535"; return GVOM_ERR_INVALID; }
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    DevSet *set = nullptr;
+    const size_t bytes = set_bytes(GVOM_PRODUCT_COSTFIELD, xy, 0, 0);
+    int rc = product_acquire(h, GVOM_PRODUCT_COSTFIELD, bytes, bytes, "gvom_cost_to_go", &h->ctg_allocs, &set);
+    if (rc) return rc;
+    const int nt = gvom_ctg_tiles(xy), ntiles = nt * nt;
+    const size_t flags_off = 256, goals_off = flags_off + align256((size_t)2 * ntiles * 4);
+    if ((rc = stage_buf(h, h->ctg_work, goals_off + (size_t)GVOM_CTG_MAX_GOALS * 8, h->ctg_allocs))) return rc;
+    if (!h->ctg_pin) HIPCHK(h, hipHostMalloc((void **)&h->ctg_pin, 256, hipHostMallocDefault));
+    uint32_t *cnt = (uint32_t *)h->ctg_work.p;
+    uint32_t *fl = (uint32_t *)((char *)h->ctg_work.p + flags_off);
+    int32_t *gdev = (int32_t *)((char *)h->ctg_work.p + goals_off);
+    HIPCHK(h, join_second_stream(h));
+    const int32_t *cost32 = nullptr;
+    if (map_set_id < 0 && !on_device) {                                     // a host cost map: staged
+        if ((rc = stage_buf(h, h->ctg_stage, n2 * 4, h->ctg_allocs))) return rc;
+        HIPCHK(h, hipMemcpyAsync(h->ctg_stage.p, cost, n2 * 4, hipMemcpyHostToDevice, h->stream));
+        cost32 = (const int32_t *)h->ctg_stage.p;
+    } else if (map_set_id < 0) cost32 = cost;
+    const size_t clr_g = align256(gvom_clearance_scratch_bytes(xy)), clr_map = align256(n2 * 4);
+    if (m && C.inflation_cells2 > 0 && (rc = stage_buf(h, h->ctg_clr, clr_g + 2 * clr_map, h->ctg_allocs))) return rc;
+    HIPCHK(h, hipMemcpyAsync(gdev, goals, (size_t)n_goals * 8, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemsetAsync(cnt, 0, 256, h->stream));
+    if ((rc = set_wait_releases(h, set))) return rc;
+    int32_t *D = part_ptr<int32_t>(set, 0);
+    uint16_t *c16 = part_ptr<uint16_t>(set, 2);
+    if (m) {
+        const int32_t *mp = part_ptr<const int32_t>(m, 0), *mn = part_ptr<const int32_t>(m, 1);
+        const int32_t *cd2 = nullptr;
+        if (C.inflation_cells2 > 0) {
+            char *q = (char *)h->ctg_clr.p;
+            HIPCHK(h, gvom_launch_clearance(h->stream, xy, h->prm.xy_resolution, mp, C.use_negative ? mn : nullptr, C.density_threshold,
+                                            C.inflation_cells2, (uint16_t *)q, (float *)(q + clr_g), (int32_t *)(q + clr_g + clr_map)));
+            cd2 = (const int32_t *)(q + clr_g + clr_map);
+        }
+        HIPCHK(h, gvom_launch_travcost(h->stream, xy, mp, mn, part_ptr<const int32_t>(m, 2), part_ptr<const double>(m, 3), cd2, C, c16));
+    }
+    HIPCHK(h, gvom_launch_ctg_seed(h->stream, xy, cost32, c16, D, fl, gdev, (int)n_goals, cnt + CTG_CNT_SEEDED));
+    const int32_t cap = max_cost == 0 ? GVOM_CTG_MAX_COST : max_cost;
+    const int inner = h->tune_ctg_inner > 0 ? h->tune_ctg_inner : 256;
+    const int batch = h->tune_ctg_batch > 0 ? h->tune_ctg_batch : 8;
+    // by induction over the tile crossings of a shortest path the solve ends after at most (crossings + 1) rounds of tiles that
+    // reach their fixed point; the limit below is beyond anything xy <= 4096 can need and only keeps this loop finite
+    const int64_t limit = max_rounds > 0 ? (int64_t)max_rounds : (int64_t)1 << 22;
+    int64_t rounds = 0, tiles = 0;
+    bool converged = false;
+    while (!converged && rounds < limit) {
+        const int nb = (int)std::min<int64_t>(batch, limit - rounds);
+        if (rounds) HIPCHK(h, hipMemsetAsync(cnt, 0, 2 * GVOM_CTG_MAX_BATCH * 4, h->stream));
+        for (int r = 0; r < nb; ++r) {
+            const int64_t k = rounds + r;
+            HIPCHK(h, gvom_launch_ctg_relax(h->stream, xy, c16, D, fl + (k & 1) * ntiles, fl + ((k + 1) & 1) * ntiles, cnt + r,
+                                            cnt + CTG_CNT_RELAXED + r, cap, inner));
+        }
+        HIPCHK(h, hipMemcpyAsync(h->ctg_pin, cnt, 2 * GVOM_CTG_MAX_BATCH * 4, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        int ran = nb;
+        for (int r = 0; r < nb; ++r) {
+            tiles += h->ctg_pin[CTG_CNT_RELAXED + r];
+            if (h->ctg_pin[r] == 0) { converged = true; ran = r + 1; break; }
+        }
+        rounds += ran;
+    }
+    HIPCHK(h, gvom_launch_ctg_dirs(h->stream, xy, c16, D, part_ptr<uint8_t>(set, 1), cnt + CTG_CNT_REACHED));
+    if ((rc = product_publish(h, set, product_id))) return rc;             // (`ready` goes in front of the counters' way back)
+    HIPCHK(h, hipMemcpyAsync(h->ctg_pin, cnt, 256, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (!converged && max_rounds == 0) { set->id = *product_id = -1; h->err = "gvom_cost_to_go: the field did not settle"; return GVOM_ERR_HIP; }   // (nobody gets it)
+    h->ctg_last_tiles = (int)std::min<int64_t>(tiles, INT32_MAX);
+    if (info) { info[0] = converged ? 1 : 0; info[1] = rounds; info[2] = h->ctg_pin[CTG_CNT_REACHED]; info[3] = h->ctg_pin[CTG_CNT_SEEDED]; }
+    return GVOM_OK;
+}
+}  // extern "C"

@@ -1,0 +1,106 @@
+// gvom_setlayout.h -- what a device set (DevSet, gvom_host.h) holds: the one table of the layouts of a map set and of every product
+// kind (host side; no HIP in here: tests/setlayout_host_test.cpp compiles it alone).  set_bytes() sizes the one allocation of a set,
+// set_part() says where a part of it lies and what it is; the pool, the exports and the DLPack capsules (gvom_sets.hip) and the
+// launches (gvom_product_calls.hip) go through these two.  kind 0 = the nine maps of one combine, [y][x] order: the six f64 maps (3
+// roughness, 4 height, 5 inferred height, 6 / 7 x / y slope, 8 guessed delta) at k * S doubles, each 256-byte aligned, then the three
+// i32 maps (0 positive, 1 negative, 2 visibility) behind them at k * S ints, each 128-byte aligned; S = dev_map_stride(xy), 60 bytes
+// per cell.  GVOM_PRODUCT_* otherwise, every part at a 256-byte boundary:
+//   occupancy        V bytes, out[x][y][z]
+//   voxel cloud      256-byte header (the uint64 row counter k_voxel_cloud adds to), then cap x 8 and cap x 3 floats
+//   height clouds    xy*xy x 7 / x 3 floats
+//   clearance        xy*xy floats (metres), then xy*xy int32 (squared cells), both [y][x]
+//   raycast          cap x 4 int32 {status, steps, voxel, unknown}, then cap x 3 floats (stop position); cap = the rays of the call
+//                    that wrote it
+//   cost field       xy*xy int32 (cost to go), then xy*xy uint8 (direction), then xy*xy uint16 (cell costs), all [y][x]
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+#include <string.h>
+#include "../../include/gvom_hip.h"
+
+namespace gvom_host {
+enum { kDLInt = 0, kDLUInt = 1, kDLFloat = 2 };            // DLPack type codes (DLDataTypeCode, as the DLPack specification defines them)
+
+inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+// what of a set its layout depends on (DevSet, gvom_host.h, is one of these)
+struct SetShape {
+    char *mem = nullptr;
+    int xy = 0;
+    int kind = 0, zs = 0;                      // GVOM_PRODUCT_* (0: a map set); z_size (occupancy)
+    // voxel cloud: rows the allocation holds; raycast: rays of the product; a map set: the elements from one map to the next,
+    // dev_map_stride(xy) of gvom_internal.h (which needs the HIP runtime: it comes in through here) -- a multiple of 32, >= xy*xy
+    int64_t cap = 0;
+};
+struct SetPart { void *ptr; int ndim; int64_t shape[3], strides[3]; uint8_t code, bits; size_t bytes; };
+
+inline size_t set_bytes(int kind, int xy, int zs, int64_t cap)
+{
+    const size_t n2 = (size_t)xy * xy;
+    switch (kind) {
+    case 0: return (size_t)cap * 60;
+    case GVOM_PRODUCT_OCCUPANCY: return n2 * zs;
+    case GVOM_PRODUCT_VOXEL_CLOUD: return 256 + align256((size_t)cap * 32) + align256((size_t)cap * 12);
+    case GVOM_PRODUCT_HEIGHT_CLOUD: return n2 * 28;
+    case GVOM_PRODUCT_INFERRED_HEIGHT_CLOUD: return n2 * 12;
+    case GVOM_PRODUCT_CLEARANCE: return align256(n2 * 4) + n2 * 4;
+    case GVOM_PRODUCT_RAYCAST: return align256((size_t)cap * 16) + (size_t)cap * 12;
+    case GVOM_PRODUCT_COSTFIELD: return align256(n2 * 4) + align256(n2) + n2 * 2;
+    }
+    return 0;
+}
+
+// false: the set has no such part
+inline bool set_part(const SetShape *s, int part, SetPart *d)
+{
+    const int64_t xy = s->xy, n2 = xy * xy;
+    memset(d, 0, sizeof *d);
+    d->ndim = 2; d->code = kDLFloat; d->bits = 32;
+    d->shape[2] = d->strides[2] = 1;
+    auto rows = [&](void *ptr, int64_t n, int64_t cols) { d->ptr = ptr; d->shape[0] = n; d->shape[1] = cols; d->strides[0] = cols; d->strides[1] = 1; };
+    switch (s->kind) {
+    case 0: {                                              // map `part` of a map set: [x, y] indexing, column-major
+        if (part < 0 || part > 8) return false;
+        const size_t S = (size_t)s->cap;
+        d->ptr = part >= 3 ? (void *)((double *)s->mem + (size_t)(part - 3) * S) : (void *)((int32_t *)((double *)s->mem + 6 * S) + (size_t)part * S);
+        d->shape[0] = d->shape[1] = xy; d->strides[0] = 1; d->strides[1] = xy;
+        d->code = part >= 3 ? kDLFloat : kDLInt; d->bits = part >= 3 ? 64 : 32;
+        break;
+    }
+    case GVOM_PRODUCT_OCCUPANCY:
+        if (part != 0) return false;
+        d->ptr = s->mem; d->ndim = 3; d->code = kDLUInt; d->bits = 8;
+        d->shape[0] = d->shape[1] = xy; d->shape[2] = s->zs;
+        d->strides[0] = xy * s->zs; d->strides[1] = s->zs; d->strides[2] = 1;
+        break;
+    case GVOM_PRODUCT_VOXEL_CLOUD:
+        if (part == 0) rows(s->mem + 256, s->cap, 8);
+        else if (part == 1) rows(s->mem + 256 + align256((size_t)s->cap * 32), s->cap, 3);
+        else if (part == 2) { d->ptr = s->mem; d->ndim = 1; d->shape[0] = 1; d->strides[0] = 1; d->shape[1] = d->strides[1] = 1; d->code = kDLInt; d->bits = 64; }
+        else return false;
+        break;
+    case GVOM_PRODUCT_HEIGHT_CLOUD: if (part != 0) return false; rows(s->mem, n2, 7); break;
+    case GVOM_PRODUCT_INFERRED_HEIGHT_CLOUD: if (part != 0) return false; rows(s->mem, n2, 3); break;
+    case GVOM_PRODUCT_CLEARANCE:                           // [x, y] indexing, column-major, like a device map
+        if (part < 0 || part > 1) return false;
+        d->ptr = s->mem + (part ? align256((size_t)n2 * 4) : 0);
+        d->shape[0] = d->shape[1] = xy; d->strides[0] = 1; d->strides[1] = xy;
+        if (part) d->code = kDLInt;
+        break;
+    case GVOM_PRODUCT_RAYCAST:
+        if (part == 0) { rows(s->mem, s->cap, 4); d->code = kDLInt; }
+        else if (part == 1) rows(s->mem + align256((size_t)s->cap * 16), s->cap, 3);
+        else return false;
+        break;
+    case GVOM_PRODUCT_COSTFIELD:                           // [x, y] indexing, column-major, like a device map
+        if (part < 0 || part > 2) return false;
+        d->ptr = s->mem + (part ? align256((size_t)n2 * 4) : 0) + (part == 2 ? align256((size_t)n2) : 0);
+        d->shape[0] = d->shape[1] = xy; d->strides[0] = 1; d->strides[1] = xy;
+        d->code = part ? kDLUInt : kDLInt; d->bits = part == 0 ? 32 : (part == 1 ? 8 : 16);
+        break;
+    default: return false;
+    }
+    d->bytes = (size_t)(d->shape[0] * d->shape[1] * d->shape[2]) * (d->bits / 8);
+    return true;
+}
+}  // namespace gvom_host

@@ -386,6 +386,51 @@ def _stream_arg(stream):
     return ctypes.c_void_p(s) if s else None
 
 
+def _dlpack_capsule(g, export, ident, part, what, stream, max_version, dl_device, copy):
+    """__dlpack__ of a DeviceMap (what = "map") or a DeviceArray ("array") of the mapper g: one export of part `part` of the set
+    `ident` through `export` (gvom_device_map_dlpack / gvom_device_product_dlpack), in a capsule whose destructor gives it back."""
+    device = (_KDL_ROCM, g._device)
+    if copy:
+        raise BufferError("copy=True is not supported: the %s is shared in place" % what)
+    if dl_device is not None and tuple(int(v) for v in dl_device) != device:
+        raise BufferError("the %s lives on %r; no cross-device export" % (what, device))
+    versioned = max_version is not None and int(max_version[0]) >= 1
+    managed = ctypes.c_void_p()
+    g._check(export(g._h, ident, part, _stream_arg(stream), 1 if versioned else 0, ctypes.byref(managed)))
+    name, dtor = (_DLTENSOR_VERSIONED, _DTOR_VERSIONED) if versioned else (_DLTENSOR, _DTOR_LEGACY)
+    return _capsule_api().PyCapsule_New(managed.value, name, ctypes.cast(dtor, ctypes.c_void_p))
+
+
+class _WithRelease(object):
+    """`with` support of everything that has a release()"""
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.release()
+        return False
+
+
+class _Export(_WithRelease):
+    """One export of a device set held by a Python object (`_owner`: the mapper, `_held`: not given back yet): given back once, by
+    release() or on collection, through the entry point `_release_name` with the id the attribute `_id_name` holds."""
+    _release_name = _id_name = None
+
+    def release(self):
+        if self.__dict__.get("_held"):
+            self._held = False
+            g = self._owner
+            if g._h:
+                g._check(getattr(g._lib, self._release_name)(g._h, getattr(self, self._id_name), ctypes.c_void_p(_STREAM_NOSYNC)))
+
+    def __del__(self):
+        try:
+            self.release()
+        except Exception:
+            pass
+
+
 class DeviceMap(object):
     """One map of a device map set: [x, y]-indexed, column-major in device memory (strides (1, xy) in elements).
     `__dlpack__` hands it to a GPU consumer without a copy (torch.from_dlpack); `copy_to_host()` returns numpy."""
@@ -401,19 +446,8 @@ class DeviceMap(object):
         return (_KDL_ROCM, self._maps._owner._device)
 
     def __dlpack__(self, stream=None, max_version=None, dl_device=None, copy=None):
-        if copy:
-            raise BufferError("copy=True is not supported: the map is shared in place")
-        if dl_device is not None and tuple(int(v) for v in dl_device) != self.__dlpack_device__():
-            raise BufferError("the map lives on %r; no cross-device export" % (self.__dlpack_device__(),))
-        versioned = max_version is not None and int(max_version[0]) >= 1
         g = self._maps._owner
-        managed = ctypes.c_void_p()
-        g._check(g._lib.gvom_device_map_dlpack(g._h, self._maps.set_id, self._which, _stream_arg(stream), 1 if versioned else 0,
-                                               ctypes.byref(managed)))
-        api = _capsule_api()
-        if versioned:
-            return api.PyCapsule_New(managed.value, _DLTENSOR_VERSIONED, ctypes.cast(_DTOR_VERSIONED, ctypes.c_void_p))
-        return api.PyCapsule_New(managed.value, _DLTENSOR, ctypes.cast(_DTOR_LEGACY, ctypes.c_void_p))
+        return _dlpack_capsule(g, g._lib.gvom_device_map_dlpack, self._maps.set_id, self._which, "map", stream, max_version, dl_device, copy)
 
     @property
     def ptr(self):
@@ -437,11 +471,12 @@ class DeviceMap(object):
         return a if dtype is None else a.astype(dtype)
 
 
-class DeviceMaps(object):
+class DeviceMaps(_Export):
     """The result of Gvom.combine_maps_device(): the nine maps of one combine in device memory (one map set), as DeviceMap
     attributes named after the reference's (DEVICE_MAP_NAMES), `.origin` (f64[3], world) and `.set_id`.  It holds one export
     of the set -- the set is not reused while it lives -- given back by release(), by leaving a `with` block, or when it is
     collected.  Tensors taken through DLPack hold exports of their own and stay valid after release() (and after the mapper)."""
+    _release_name, _id_name = "gvom_device_map_release", "set_id"
 
     def __init__(self, owner, set_id, origin):
         self._owner = owner
@@ -482,37 +517,19 @@ class DeviceMaps(object):
                                     rough_weight, roughness_range)
         return g._cost_to_go(self.set_id, params, None, 0, cells, _ctg_max_cost(max_cost), _ctg_max_rounds(max_rounds), flags)
 
-    def release(self):
-        if self.__dict__.get("_held"):
-            self._held = False
-            g = self._owner
-            if g._h:
-                g._check(g._lib.gvom_device_map_release(g._h, self.set_id, ctypes.c_void_p(_STREAM_NOSYNC)))
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.release()
-        return False
-
-    def __del__(self):
-        try:
-            self.release()
-        except Exception:
-            pass
-
 
 # ---- device-resident 3-D products (Gvom.occupancy_grid_device and friends) ----------------------------------------
 PRODUCT_OCCUPANCY, PRODUCT_VOXEL_CLOUD, PRODUCT_HEIGHT_CLOUD, PRODUCT_INFERRED_HEIGHT_CLOUD = 1, 2, 3, 4    # include/gvom_hip.h
-_PRODUCT_DTYPES = {(PRODUCT_OCCUPANCY, 0): np.uint8, (PRODUCT_VOXEL_CLOUD, 0): np.float32, (PRODUCT_VOXEL_CLOUD, 1): np.float32,
-                   (PRODUCT_VOXEL_CLOUD, 2): np.int64, (PRODUCT_HEIGHT_CLOUD, 0): np.float32,
-                   (PRODUCT_INFERRED_HEIGHT_CLOUD, 0): np.float32}
 PRODUCT_CLEARANCE = 5                     # GVOM_PRODUCT_CLEARANCE: made by gvom_clearance, not by gvom_device_product
+PRODUCT_RAYCAST = 6                       # GVOM_PRODUCT_RAYCAST: made by gvom_raycast, not by gvom_device_product
+PRODUCT_COSTFIELD = 7                     # GVOM_PRODUCT_COSTFIELD: made by gvom_cost_to_go, not by gvom_device_product
+# element type of part k of a product, by kind (what set_part() of csrc/gvom_setlayout.h gives as DLPack code and bits)
+_PRODUCT_DTYPES = {PRODUCT_OCCUPANCY: (np.uint8,), PRODUCT_VOXEL_CLOUD: (np.float32, np.float32, np.int64),
+                   PRODUCT_HEIGHT_CLOUD: (np.float32,), PRODUCT_INFERRED_HEIGHT_CLOUD: (np.float32,),
+                   PRODUCT_CLEARANCE: (np.float32, np.int32), PRODUCT_RAYCAST: (np.int32, np.float32),
+                   PRODUCT_COSTFIELD: (np.int32, np.uint8, np.uint16)}
 CLEARANCE_FAR = 2147483647                # GVOM_CLEARANCE_FAR: squared_cells where no obstacle is in reach
 _CLEARANCE_NO_NEGATIVE = 1                # GVOM_CLEARANCE_NO_NEGATIVE
-_PRODUCT_DTYPES[(PRODUCT_CLEARANCE, 0)] = np.float32
-_PRODUCT_DTYPES[(PRODUCT_CLEARANCE, 1)] = np.int32
 
 
 def _clearance_cap(max_distance, xy_resolution):
@@ -538,18 +555,19 @@ def _clearance_threshold(density_threshold):
     return t
 
 
-class _ProductHold(object):
+class _ProductHold(_Export):
     """One export of a device product, held for as long as the Python object that shows it lives: the product's set is not
     reused meanwhile.  Given back by release() or on collection."""
+    _release_name, _id_name = "gvom_device_product_release", "product_id"
 
     def __init__(self, owner, kind, product_id):
-        self.owner, self.kind, self.product_id = owner, kind, product_id
+        self._owner, self.kind, self.product_id = owner, kind, product_id
         self.describe(0, hold=True)
-        self.held = True
+        self._held = True
 
     def describe(self, part, hold=False):
         """(device address, shape, strides in elements) of a part; hold=True keeps the export it takes."""
-        g = self.owner
+        g = self._owner
         p, nd, sh, st = ctypes.c_void_p(), ctypes.c_int32(0), (_I64 * 3)(), (_I64 * 3)()
         nosync = ctypes.c_void_p(_STREAM_NOSYNC)
         g._check(g._lib.gvom_device_product_export(g._h, self.product_id, part, nosync, ctypes.byref(p), ctypes.byref(nd), sh, st))
@@ -558,21 +576,20 @@ class _ProductHold(object):
         n = int(nd.value)
         return int(p.value), tuple(int(v) for v in sh[:n]), tuple(int(v) for v in st[:n])
 
+
+class _ProductView(_WithRelease):
+    """What the views of a device product share: the hold on its export (`_hold`; the views of one product share one), its
+    `product_id`, and release() -- also at the end of a `with` block."""
+
+    def __init__(self, hold):
+        self._hold = hold
+        self.product_id = hold.product_id
+
     def release(self):
-        if self.__dict__.get("held"):
-            self.held = False
-            g = self.owner
-            if g._h:
-                g._check(g._lib.gvom_device_product_release(g._h, self.product_id, ctypes.c_void_p(_STREAM_NOSYNC)))
-
-    def __del__(self):
-        try:
-            self.release()
-        except Exception:
-            pass
+        self._hold.release()
 
 
-class DeviceArray(object):
+class DeviceArray(_ProductView):
     """One array of a device product in device memory, C-contiguous: the uint8 [x, y, z] occupancy grid, a float32 cloud, the
     int64 row count of a voxel cloud.  `__dlpack__` hands it to a GPU consumer without a copy (torch.from_dlpack), ordered
     behind the kernel that writes it on the consumer's stream; `copy_to_host()` returns numpy.  The product is a snapshot:
@@ -582,29 +599,17 @@ class DeviceArray(object):
     mapper)."""
 
     def __init__(self, hold, part=0):
-        self._hold = hold
+        _ProductView.__init__(self, hold)
         self._part = part
         _, self.shape, self.strides = hold.describe(part)
-        self.dtype = np.dtype(_PRODUCT_DTYPES[(hold.kind, part)])
-        self.product_id = hold.product_id
+        self.dtype = np.dtype(_PRODUCT_DTYPES[hold.kind][part])
 
     def __dlpack_device__(self):
-        return (_KDL_ROCM, self._hold.owner._device)
+        return (_KDL_ROCM, self._hold._owner._device)
 
     def __dlpack__(self, stream=None, max_version=None, dl_device=None, copy=None):
-        if copy:
-            raise BufferError("copy=True is not supported: the array is shared in place")
-        if dl_device is not None and tuple(int(v) for v in dl_device) != self.__dlpack_device__():
-            raise BufferError("the array lives on %r; no cross-device export" % (self.__dlpack_device__(),))
-        versioned = max_version is not None and int(max_version[0]) >= 1
-        g = self._hold.owner
-        managed = ctypes.c_void_p()
-        g._check(g._lib.gvom_device_product_dlpack(g._h, self.product_id, self._part, _stream_arg(stream), 1 if versioned else 0,
-                                                   ctypes.byref(managed)))
-        api = _capsule_api()
-        if versioned:
-            return api.PyCapsule_New(managed.value, _DLTENSOR_VERSIONED, ctypes.cast(_DTOR_VERSIONED, ctypes.c_void_p))
-        return api.PyCapsule_New(managed.value, _DLTENSOR, ctypes.cast(_DTOR_LEGACY, ctypes.c_void_p))
+        g = self._hold._owner
+        return _dlpack_capsule(g, g._lib.gvom_device_product_dlpack, self.product_id, self._part, "array", stream, max_version, dl_device, copy)
 
     @property
     def ptr(self):
@@ -613,7 +618,7 @@ class DeviceArray(object):
 
     def copy_to_host(self):
         """numpy array of `shape` and `dtype` (waits for the kernel that writes the product)."""
-        g = self._hold.owner
+        g = self._hold._owner
         fortran = len(self.shape) == 2 and self.strides == (1, self.shape[0]) and self.shape[0] > 1     # (a clearance map: [x, y], x fastest)
         out = np.empty(self.shape, self.dtype, order="F" if fortran else "C")
         g._check(g._lib.gvom_device_product_copy(g._h, self.product_id, self._part, ctypes.c_void_p(out.ctypes.data)))
@@ -623,25 +628,14 @@ class DeviceArray(object):
         a = self.copy_to_host()
         return a if dtype is None else a.astype(dtype)
 
-    def release(self):
-        self._hold.release()
 
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.release()
-        return False
-
-
-class DeviceVoxelCloud(object):
+class DeviceVoxelCloud(_ProductView):
     """The result of Gvom.voxel_cloud_device(): `.rows` float32 [cap, 8] (the rows of make_debug_voxel_map, in unspecified
     order), `.eigenvalues` float32 [cap, 3] (row for row) and `.count` int64 [1] (rows the map has; those beyond cap are dropped),
     three DeviceArrays of one product.  copy_to_host() returns rows[:min(count, cap)] as numpy."""
 
     def __init__(self, hold):
-        self._hold = hold
-        self.product_id = hold.product_id
+        _ProductView.__init__(self, hold)
         self.rows, self.eigenvalues, self.count = (DeviceArray(hold, k) for k in range(3))
 
     def copy_to_host(self):
@@ -652,51 +646,27 @@ class DeviceVoxelCloud(object):
         n = min(int(self.count.copy_to_host()[0]), self.rows.shape[0])
         return self.eigenvalues.copy_to_host()[:n]
 
-    def release(self):
-        self._hold.release()
 
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.release()
-        return False
-
-
-class DeviceClearance(object):
+class DeviceClearance(_ProductView):
     """The result of DeviceMaps.clearance() / Gvom.clearance_of() / clearance_of_device(): `.distance` float32 [xy, xy], metres to
     the nearest hard obstacle (+inf where none is in reach), and `.squared_cells` int32 [xy, xy], the exact squared distance in
     cells (CLEARANCE_FAR there) -- two DeviceArrays of one product, [x, y]-indexed with strides (1, xy) like a DeviceMap.
     copy_to_host() returns (distance, squared_cells) as Fortran-ordered numpy [x, y]."""
 
     def __init__(self, hold):
-        self._hold = hold
-        self.product_id = hold.product_id
+        _ProductView.__init__(self, hold)
         self.distance, self.squared_cells = DeviceArray(hold, 0), DeviceArray(hold, 1)
 
     def copy_to_host(self):
         return self.distance.copy_to_host(), self.squared_cells.copy_to_host()
 
-    def release(self):
-        self._hold.release()
 
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.release()
-        return False
-
-
-PRODUCT_RAYCAST = 6                       # GVOM_PRODUCT_RAYCAST: made by gvom_raycast, not by gvom_device_product
 RAY_CLEAR, RAY_OCCUPIED, RAY_UNKNOWN, RAY_LEFT_WINDOW, RAY_INVALID = range(5)       # GVOM_RAY_*: result[:, 0]
 _RAY_UNKNOWN_BLOCKS, _RAY_CHECK_TARGET = 1, 2                                       # flags
 RAYCAST_MAX_RAYS = 1 << 26
-_PRODUCT_DTYPES[(PRODUCT_RAYCAST, 0)] = np.int32
-_PRODUCT_DTYPES[(PRODUCT_RAYCAST, 1)] = np.float32
 
 
-class DeviceRays(object):
+class DeviceRays(_ProductView):
     """The result of Gvom.raycast() / raycast_device(): `.result` int32 [n, 4] -- per ray {status (RAY_*), steps, voxel, unknown
     voxels passed} -- and `.position` float32 [n, 3], where the ray stopped in world metres (NaN where it did not stop at a
     voxel): two DeviceArrays of one product, row i = ray i.  `.origin`: the fused map's window origin in voxels; window voxel
@@ -704,35 +674,20 @@ class DeviceRays(object):
     and combines do not change it.  copy_to_host() returns (result, position) as numpy."""
 
     def __init__(self, hold, origin):
-        self._hold = hold
-        self.product_id = hold.product_id
+        _ProductView.__init__(self, hold)
         self.origin = origin
         self.result, self.position = DeviceArray(hold, 0), DeviceArray(hold, 1)
 
     def copy_to_host(self):
         return self.result.copy_to_host(), self.position.copy_to_host()
 
-    def release(self):
-        self._hold.release()
 
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.release()
-        return False
-
-
-PRODUCT_COSTFIELD = 7                     # GVOM_PRODUCT_COSTFIELD: made by gvom_cost_to_go, not by gvom_device_product
 CTG_UNREACHED = 2147483647                # GVOM_CTG_UNREACHED: cost where a cell is blocked, cut off, or dearer than max_cost
 CTG_MAX_COST = 1 << 30                    # GVOM_CTG_MAX_COST
 CTG_GOAL, CTG_UNSETTLED, CTG_NONE = 8, 254, 255          # GVOM_CTG_*: direction codes beside the eight steps 0 .. 7
 CTG_STEPS = ((1, 0), (1, 1), (0, 1), (-1, 1), (-1, 0), (-1, -1), (0, -1), (1, -1))   # (dx, dy) of direction code k
 CTG_MAX_GOALS = 65536
 _CTG_NO_NEGATIVE, _CTG_UNKNOWN_BLOCKS = 1, 2             # flags
-_PRODUCT_DTYPES[(PRODUCT_COSTFIELD, 0)] = np.int32
-_PRODUCT_DTYPES[(PRODUCT_COSTFIELD, 1)] = np.uint8
-_PRODUCT_DTYPES[(PRODUCT_COSTFIELD, 2)] = np.uint16
 
 
 class GvomCtgParams(ctypes.Structure):
@@ -831,7 +786,7 @@ def _ctg_params(xy_resolution, inflation_radius, density_threshold, include_nega
     return P, flags
 
 
-class DeviceCostField(object):
+class DeviceCostField(_ProductView):
     """The result of DeviceMaps.cost_to_go() / Gvom.cost_to_go_of() / cost_to_go_of_device(): `.cost` int32 [xy, xy], the cheapest
     way from each cell to a goal (CTG_UNREACHED where there is none), `.direction` uint8 [xy, xy], the first step of it (code k
     = CTG_STEPS[k]; CTG_GOAL at a goal, CTG_NONE where unreached, CTG_UNSETTLED only in a field that is not final) and
@@ -841,8 +796,7 @@ class DeviceCostField(object):
     direction, cell_cost) as Fortran-ordered numpy [x, y]."""
 
     def __init__(self, hold, info):
-        self._hold = hold
-        self.product_id = hold.product_id
+        _ProductView.__init__(self, hold)
         self.cost, self.direction, self.cell_cost = DeviceArray(hold, 0), DeviceArray(hold, 1), DeviceArray(hold, 2)
         self.converged, self.rounds, self.reached, self.goals_seeded = bool(info[0]), int(info[1]), int(info[2]), int(info[3])
         self._host = None
@@ -871,16 +825,6 @@ class DeviceCostField(object):
             x, y = x + CTG_STEPS[k][0], y + CTG_STEPS[k][1]
             path.append((x, y))
         raise RuntimeError("the directions do not lead to a goal")
-
-    def release(self):
-        self._hold.release()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.release()
-        return False
 
 
 class _OutputPool(object):
@@ -1455,10 +1399,15 @@ class Gvom(object):
         return out.astype(bool)
 
     # ---- the same four, left in device memory (extensions; include/gvom_hip.h "device-resident 3-D products") ----
-    def _device_product(self, kind, max_rows=0):
+    def _make_product(self, call, kind, check=None):
+        """What the four makers share: `call(product id, by reference)` runs the entry point; the hold on the product of `kind` it
+        made, or None where it had no data."""
         pid = ctypes.c_int64(-1)
-        rc = self._check(self._lib.gvom_device_product(self._h, kind, int(max_rows), ctypes.byref(pid)))
+        rc = (check or self._check)(call(ctypes.byref(pid)))
         return None if rc == GVOM_NO_DATA else _ProductHold(self, kind, int(pid.value))
+
+    def _device_product(self, kind, max_rows=0):
+        return self._make_product(lambda pid: self._lib.gvom_device_product(self._h, kind, int(max_rows), pid), kind)
 
     def occupancy_grid_device(self):
         """get_map_as_occupancy_grid() left in device memory: a DeviceArray uint8 [xy, xy, z] (1 = occupied), a snapshot of the
@@ -1498,10 +1447,9 @@ class Gvom(object):
     def _clearance(self, set_id, pos_ptr, neg_ptr, on_device, density_threshold, include_negative, max_distance):
         thr = _clearance_threshold(density_threshold)
         cap = _clearance_cap(max_distance, self.xy_resolution)
-        pid = ctypes.c_int64(-1)
-        self._check(self._lib.gvom_clearance(self._h, int(set_id), pos_ptr, neg_ptr, int(on_device), thr, cap,
-                                             0 if include_negative else _CLEARANCE_NO_NEGATIVE, ctypes.byref(pid)))
-        return DeviceClearance(_ProductHold(self, PRODUCT_CLEARANCE, int(pid.value)))
+        flags = 0 if include_negative else _CLEARANCE_NO_NEGATIVE
+        return DeviceClearance(self._make_product(lambda pid: self._lib.gvom_clearance(
+            self._h, int(set_id), pos_ptr, neg_ptr, int(on_device), thr, cap, flags, pid), PRODUCT_CLEARANCE))
 
     def clearance_of(self, positive, negative=None, density_threshold=50, include_negative=True, max_distance=None):
         """DeviceMaps.clearance() of maps of the caller's: numpy [x, y] arrays of shape (xy_size, xy_size) in any memory order
@@ -1529,14 +1477,11 @@ class Gvom(object):
 
     # ---- ray queries (an extension; include/gvom_hip.h "ray queries") ----
     def _raycast(self, from_ptr, K, to_ptr, n, on_device, unknown_blocks, check_target):
-        pid = ctypes.c_int64(-1)
         org = (ctypes.c_double * 3)()
         flags = (_RAY_UNKNOWN_BLOCKS if unknown_blocks else 0) | (_RAY_CHECK_TARGET if check_target else 0)
-        rc = self._check_args(self._lib.gvom_raycast(self._h, from_ptr, int(K), to_ptr, int(n), int(on_device), flags, org,
-                                                     ctypes.byref(pid)))
-        if rc == GVOM_NO_DATA:
-            return None
-        return DeviceRays(_ProductHold(self, PRODUCT_RAYCAST, int(pid.value)), np.array(list(org), np.float64))
+        hold = self._make_product(lambda pid: self._lib.gvom_raycast(self._h, from_ptr, int(K), to_ptr, int(n), int(on_device), flags,
+                                                                     org, pid), PRODUCT_RAYCAST, self._check_args)
+        return None if hold is None else DeviceRays(hold, np.array(list(org), np.float64))
 
     def raycast(self, origins, targets, unknown_blocks=False, check_target=False):
         """Walks the straight segments origins -> targets (world metres) through the current fused map on the GPU, with the
@@ -1569,12 +1514,11 @@ class Gvom(object):
 
     # ---- cost-to-go fields (an extension; include/gvom_hip.h "cost-to-go fields") ----
     def _cost_to_go(self, set_id, params, cost_ptr, on_device, cells, max_cost, max_rounds, flags):
-        pid = ctypes.c_int64(-1)
         info = (_I64 * 4)()
-        self._check(self._lib.gvom_cost_to_go(self._h, int(set_id), ctypes.byref(params) if params is not None else None, cost_ptr,
-                                              int(on_device), _ptr(cells), cells.shape[0], max_cost, max_rounds, flags,
-                                              ctypes.byref(pid), info))
-        return DeviceCostField(_ProductHold(self, PRODUCT_COSTFIELD, int(pid.value)), list(info))
+        hold = self._make_product(lambda pid: self._lib.gvom_cost_to_go(
+            self._h, int(set_id), ctypes.byref(params) if params is not None else None, cost_ptr, int(on_device), _ptr(cells),
+            cells.shape[0], max_cost, max_rounds, flags, pid, info), PRODUCT_COSTFIELD)
+        return DeviceCostField(hold, list(info))
 
     def cost_to_go_of(self, cost, goals, max_cost=None, max_rounds=0):
         """DeviceMaps.cost_to_go() of a cost map of the caller's: a numpy [x, y] array of shape (xy_size, xy_size) in any memory

@@ -18,7 +18,7 @@ import synth
 # smallest maps with more than one 64-cell tile segment per storage row (k_raycast's tile index is row * nseg + (sx >> 6): at
 # xy <= 64 its second term is always 0) -- a power of two with 2 segments, no power of two with 3.  FAR: the np2 grid with every
 # ego moved by FAR_OFFSET metres, which puts every axis of the window origin beyond 2^24 voxels (both signs): the query then
-# takes the literal float64 lookup whatever the grid (gvom_export.hip raycast_params).
+# takes the literal float64 lookup whatever the grid (gvom_product_calls.hip raycast_params).
 WIDE = {"w128": (0.2, 0.2, 128, 32), "w192": (0.2, 0.2, 192, 24)}
 FAR = {"far": multi_origin_ref.GRIDS["np2"]}
 FAR_OFFSET = (7.0e6, -7.0e6, 3.5e6)

@@ -216,7 +216,7 @@ def test_wide_inputs_stop_in_every_tile_segment_and_cross_between_them(wide_maps
 
 @pytest.mark.parametrize("bs", [1, 2])
 def test_the_far_grid_lies_beyond_2_to_the_24_voxels_on_every_axis(wide_maps, bs):
-    """where gvom_raycast takes the literal lookup for the origin's sake (gvom_export.hip raycast_params: any |origin| >= 2^24);
+    """where gvom_raycast takes the literal lookup for the origin's sake (gvom_product_calls.hip raycast_params: any |origin| >= 2^24);
     the grid itself (np2) takes the integer one.  The egos are float32-representable and still move from scan to scan."""
     xr, zr, xy, zs = rr.GRIDS["far"]
     assert rr.GRIDS["far"] == GRIDS["np2"] and zs <= xy

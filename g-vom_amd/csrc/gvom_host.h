@@ -318,6 +318,14 @@ struct gvom_handle {
     int ctg_allocs = 0;
     int tune_ctg_inner = 0, tune_ctg_batch = 0;         // gvom_set_tuning "cost_to_go_inner" / "cost_to_go_batch" (0: the defaults)
     int ctg_last_tiles = 0;                             // tile relaxations of the last call (gvom_get_tuning "cost_to_go_tiles")
+    // ROLLOUT SCORING (gvom_footprint_set / gvom_score_rollouts): fp_tab = the footprint table in device memory -- start[H + 1]
+    // int32, then at fp_offs_at bytes (a multiple of 256) the offsets, 4 bytes each (dx low, dy high) -- and ro_stage = the staging
+    // copy of a caller's host maps and poses; ro_allocs counts the device allocations gvom_score_rollouts has made on this handle
+    // (ro_stage and its product sets: gvom_get_tuning "rollout_allocations")
+    Buf fp_tab, ro_stage;
+    size_t fp_offs_at = 0;
+    int fp_H = 0;                                       // 0: no footprint set
+    int ro_allocs = 0;
 };
 
 namespace gvom_host {

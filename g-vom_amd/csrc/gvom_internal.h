@@ -315,6 +315,23 @@ hipError_t gvom_launch_ctg_seed(hipStream_t s, int xy, const int32_t *cost32, ui
 hipError_t gvom_launch_ctg_relax(hipStream_t s, int xy, const uint16_t *c, int32_t *D, uint32_t *fcur, uint32_t *fnext,
                                  uint32_t *activated, uint32_t *relaxed, int32_t max_cost, int inner);
 hipError_t gvom_launch_ctg_dirs(hipStream_t s, int xy, const uint16_t *c, const int32_t *D, uint8_t *dir, uint32_t *reached);
+// rollout scoring (gvom_rollouts.hip; include/gvom_hip.h "rollout scoring" defines the result).  poses [K][T][3] float32; fstart
+// [H + 1] and foffs (dx in the low, dy in the high 16 bits, both signed) are the footprint table as gvom_footprint_set stored it;
+// cell_cost / cost_to_go (may be nullptr) are [y][x] maps of xy x xy cells.  summary [K][4] int32 (16-byte aligned), pose_cost [K][T].
+#define GVOM_ROLLOUT_MAX_T 4096
+#define GVOM_ROLLOUT_MAX_POSES ((int64_t)1 << 26)
+#define GVOM_ROLLOUT_MAX_HEADINGS 1024
+#define GVOM_ROLLOUT_MAX_CELLS 16384                   // per heading
+#define GVOM_ROLLOUT_MAX_TABLE ((int64_t)1 << 22)      // offsets of all headings together
+struct RolloutParams {
+    int xy, H, T;
+    float s;                // (float)(H / 2 pi): heading = rintf(yaw * s) mod H
+    long long K;
+    long long ox, oy;       // round(origin / xy_resolution): window cell = floor(x / xy_resolution) - ox
+    double res;
+};
+hipError_t gvom_launch_rollouts(hipStream_t s, const RolloutParams &P, const float *poses, const int32_t *fstart, const uint32_t *foffs,
+                                const uint16_t *cell_cost, const int32_t *cost_to_go, int32_t *summary, uint16_t *pose_cost);
 // storage order [sy][sx] -> reference order [x][y] (window coordinates)
 hipError_t gvom_launch_unwrap_f64(hipStream_t s, int xy, int om0, int om1, const double *in, int in_stride, double *out_xy);
 hipError_t gvom_launch_posdens(hipStream_t s, const Map2dParams &P, const int32_t *fstate,

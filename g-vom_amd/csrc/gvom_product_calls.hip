@@ -1,5 +1,5 @@
 // gvom_product_calls.hip -- the calls that MAKE a device product: gvom_device_product (occupancy grid, voxel cloud, the two height
-// clouds), gvom_clearance, gvom_raycast and gvom_cost_to_go, and the frame builders they and the debug reads (gvom_debug.hip) give
+// clouds), gvom_clearance, gvom_raycast, gvom_cost_to_go and gvom_score_rollouts (with gvom_footprint_set, which sets its table), and the frame builders they and the debug reads (gvom_debug.hip) give
 // the kernels.  Every call takes its set through product_acquire and hands it out through product_publish (gvom_sets.hip); what is
 // left in each body is what is particular to that product: its argument checks, its staging and its launches.
 #include "gvom_host.h"
@@ -83,6 +83,7 @@ VIS int gvom_device_product(gvom_t *h, int kind, int64_t max_rows, int64_t *prod
     *product_id = -1;
     static const char *const elsewhere[] = {"a clearance product is made by gvom_clearance", "a raycast product is made by gvom_raycast", "a cost field is made by gvom_cost_to_go"};
     if (kind >= GVOM_PRODUCT_CLEARANCE && kind <= GVOM_PRODUCT_COSTFIELD) { h->err = std::string("gvom_device_product: ") + elsewhere[kind - GVOM_PRODUCT_CLEARANCE]; return GVOM_ERR_INVALID; }
+    if (kind == GVOM_PRODUCT_ROLLOUTS) { h->err = "gvom_device_product: rollouts are made by gvom_score_rollouts"; return GVOM_ERR_INVALID; }
     if (kind < 1 || kind > GVOM_N_PRODUCT_KINDS) { h->err = "gvom_device_product: unknown product kind"; return GVOM_ERR_INVALID; }
     if (h->sharded) { h->err = "gvom_device_product: sharded handles are not supported"; return GVOM_ERR_INVALID; }
     if (kind == GVOM_PRODUCT_VOXEL_CLOUD) stats_demand(h);                  // a read of the statistics, like gvom_debug_voxel_map
@@ -343,5 +344,90 @@ VIS int gvom_cost_to_go(gvom_t *h, int64_t map_set_id, const gvom_ctg_params *pa
     h->ctg_last_tiles = (int)std::min<int64_t>(tiles, INT32_MAX);
     if (info) { info[0] = converged ? 1 : 0; info[1] = rounds; info[2] = h->ctg_pin[CTG_CNT_REACHED]; info[3] = h->ctg_pin[CTG_CNT_SEEDED]; }
     return GVOM_OK;
+}
+// ---- rollout scoring (gvom_footprint_set, gvom_score_rollouts) -------------------------------------------------------------------
+// K trajectories of T poses each, scored by k_rollouts (gvom_rollouts.hip) against a uint16 cost map with the footprint table of the
+// handle: a product of kind GVOM_PRODUCT_ROLLOUTS sized by K and T.  The kernel runs on the handle's stream -- behind the solve
+// that wrote the cost field it reads, and in front of whatever recycles that field later.  Enqueues and returns.
+VIS int gvom_footprint_set(gvom_t *h, int32_t n_headings, const int32_t *start, const int16_t *offsets)
+{
+    if (!h) return GVOM_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (!start || !offsets) { h->err = "gvom_footprint_set: start and offsets must not be NULL"; return GVOM_ERR_INVALID; }
+    if (n_headings < 1 || n_headings > GVOM_ROLLOUT_MAX_HEADINGS) { h->err = "gvom_footprint_set: between 1 and 1024 headings"; return GVOM_ERR_INVALID; }
+    if (start[0] != 0) { h->err = "gvom_footprint_set: start[0] must be 0"; return GVOM_ERR_INVALID; }
+    for (int k = 0; k < n_headings; ++k) {
+        const int64_t m = (int64_t)start[k + 1] - start[k];
+        if (m < 1 || m > GVOM_ROLLOUT_MAX_CELLS) { h->err = "gvom_footprint_set: every heading needs between 1 and 16384 cells"; return GVOM_ERR_INVALID; }
+        if (start[k + 1] > GVOM_ROLLOUT_MAX_TABLE) { h->err = "gvom_footprint_set: more than 2^22 offsets in the table"; return GVOM_ERR_CAPACITY; }
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    const size_t sb = (size_t)(n_headings + 1) * 4, offs_at = align256(sb), ob = (size_t)start[n_headings] * 4;
+    h->fp_H = 0;                                                            // (no table while this one is on its way)
+    if (h->fp_tab.bytes < offs_at + ob) HIPCHK(h, hipStreamSynchronize(h->stream));   // the kernels that read the table it outgrows
+    const int rc = ensure(h, h->fp_tab, offs_at + ob);
+    if (rc) return rc;
+    // on the handle's stream: behind whatever still reads the previous table
+    HIPCHK(h, hipMemcpyAsync(h->fp_tab.p, start, sb, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync((char *)h->fp_tab.p + offs_at, offsets, ob, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->fp_offs_at = offs_at; h->fp_H = n_headings;
+    return GVOM_OK;
+}
+
+VIS int gvom_score_rollouts(gvom_t *h, int64_t costfield_id, const uint16_t *cell_cost, const int32_t *cost_to_go, const float *poses,
+                            int64_t K, int64_t T, int on_device, const int64_t origin_cells[2], int64_t *product_id)
+{
+    if (!h || !product_id) return GVOM_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(h->mu);
+    *product_id = -1;
+    if (h->sharded) { h->err = "gvom_score_rollouts: sharded handles are not supported"; return GVOM_ERR_INVALID; }
+    if (h->fp_H < 1) { h->err = "gvom_score_rollouts: no footprint table is set (gvom_footprint_set)"; return GVOM_ERR_INVALID; }
+    if (!poses || !origin_cells) { h->err = "gvom_score_rollouts: poses and origin_cells must not be NULL"; return GVOM_ERR_INVALID; }
+    if (costfield_id >= 0 && (cell_cost || cost_to_go)) { h->err = "gvom_score_rollouts: give a cost field id or map pointers, not both"; return GVOM_ERR_INVALID; }
+    if (costfield_id < 0 && !cell_cost) { h->err = "gvom_score_rollouts: give a cost field id or a cell-cost map"; return GVOM_ERR_INVALID; }
+    if (T < 1 || T > GVOM_ROLLOUT_MAX_T) { h->err = "gvom_score_rollouts: T outside 1 .. 4096"; return GVOM_ERR_INVALID; }
+    if (K < 1) { h->err = "gvom_score_rollouts: K must be at least 1"; return GVOM_ERR_INVALID; }
+    if (K > GVOM_ROLLOUT_MAX_POSES / T) { h->err = "gvom_score_rollouts: more than 2^26 poses in one call"; return GVOM_ERR_CAPACITY; }
+    for (int k = 0; k < 2; ++k)
+        if (origin_cells[k] < -((int64_t)1 << 40) || origin_cells[k] > ((int64_t)1 << 40)) { h->err = "gvom_score_rollouts: an origin beyond 2^40 cells"; return GVOM_ERR_INVALID; }
+    const int xy = h->prm.xy_size;
+    if (xy > GVOM_CLEARANCE_MAX_XY) { h->err = "gvom_score_rollouts: maps of more than 4096 cells a side are not supported"; return GVOM_ERR_CAPACITY; }
+    const size_t n2 = (size_t)xy * xy;
+    const uint16_t *c16 = cell_cost;
+    const int32_t *D = cost_to_go;
+    if (costfield_id >= 0) {
+        DevSet *f = find_set(h->psets, costfield_id);
+        if (!f || f->kind != GVOM_PRODUCT_COSTFIELD) { h->err = "gvom_score_rollouts: unknown or stale cost field id"; return GVOM_ERR_INVALID; }
+        c16 = part_ptr<const uint16_t>(f, 2); D = part_ptr<const int32_t>(f, 0);
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    DevSet *set = nullptr;
+    const size_t bytes = set_bytes(GVOM_PRODUCT_ROLLOUTS, 0, 0, K, T);
+    int rc = product_acquire(h, GVOM_PRODUCT_ROLLOUTS, bytes, bytes, "gvom_score_rollouts", &h->ro_allocs, &set);
+    if (rc) return rc;
+    set->cap = K; set->cols = T;
+    const float *pdev = poses;
+    HIPCHK(h, join_second_stream(h));
+    if (!on_device) {                                                       // host poses (and maps): staged, and up before the call returns
+        const size_t pb = (size_t)K * T * 12, cb = costfield_id < 0 ? align256(n2 * 2) : 0, db = (costfield_id < 0 && cost_to_go) ? align256(n2 * 4) : 0;
+        if ((rc = stage_buf(h, h->ro_stage, cb + db + pb, h->ro_allocs))) return rc;
+        char *st = (char *)h->ro_stage.p;
+        if (cb) { HIPCHK(h, hipMemcpyAsync(st, cell_cost, n2 * 2, hipMemcpyHostToDevice, h->stream)); c16 = (const uint16_t *)st; }
+        if (db) { HIPCHK(h, hipMemcpyAsync(st + cb, cost_to_go, n2 * 4, hipMemcpyHostToDevice, h->stream)); D = (const int32_t *)(st + cb); }
+        HIPCHK(h, hipMemcpyAsync(st + cb + db, poses, pb, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        pdev = (const float *)(st + cb + db);
+    }
+    if ((rc = set_wait_releases(h, set))) return rc;
+    RolloutParams P;
+    memset(&P, 0, sizeof P);
+    P.xy = xy; P.H = h->fp_H; P.T = (int)T; P.K = K;
+    P.s = (float)((double)h->fp_H / 6.283185307179586476925286766559);
+    P.ox = origin_cells[0]; P.oy = origin_cells[1];
+    P.res = h->prm.xy_resolution;
+    HIPCHK(h, gvom_launch_rollouts(h->stream, P, pdev, (const int32_t *)h->fp_tab.p, (const uint32_t *)((char *)h->fp_tab.p + h->fp_offs_at),
+                                   c16, D, part_ptr<int32_t>(set, 0), part_ptr<uint16_t>(set, 1)));
+    return product_publish(h, set, product_id);
 }
 }  // extern "C"

@@ -12,6 +12,8 @@
 //   raycast          cap x 4 int32 {status, steps, voxel, unknown}, then cap x 3 floats (stop position); cap = the rays of the call
 //                    that wrote it
 //   cost field       xy*xy int32 (cost to go), then xy*xy uint8 (direction), then xy*xy uint16 (cell costs), all [y][x]
+//   rollouts (10)    cap x 4 int32 {status, first_blocked, path_cost, terminal}, then cap x cols uint16 (pose costs); cap = the
+//                    rollouts K and cols = the poses per rollout T of the call that wrote it.  Kinds 8 and 9 are not assigned
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -31,10 +33,11 @@ struct SetShape {
     // voxel cloud: rows the allocation holds; raycast: rays of the product; a map set: the elements from one map to the next,
     // dev_map_stride(xy) of gvom_internal.h (which needs the HIP runtime: it comes in through here) -- a multiple of 32, >= xy*xy
     int64_t cap = 0;
+    int64_t cols = 0;                          // rollouts: poses per rollout (T)
 };
 struct SetPart { void *ptr; int ndim; int64_t shape[3], strides[3]; uint8_t code, bits; size_t bytes; };
 
-inline size_t set_bytes(int kind, int xy, int zs, int64_t cap)
+inline size_t set_bytes(int kind, int xy, int zs, int64_t cap, int64_t cols = 0)
 {
     const size_t n2 = (size_t)xy * xy;
     switch (kind) {
@@ -46,6 +49,7 @@ inline size_t set_bytes(int kind, int xy, int zs, int64_t cap)
     case GVOM_PRODUCT_CLEARANCE: return align256(n2 * 4) + n2 * 4;
     case GVOM_PRODUCT_RAYCAST: return align256((size_t)cap * 16) + (size_t)cap * 12;
     case GVOM_PRODUCT_COSTFIELD: return align256(n2 * 4) + align256(n2) + n2 * 2;
+    case GVOM_PRODUCT_ROLLOUTS: return align256((size_t)cap * 16) + (size_t)cap * (size_t)cols * 2;
     }
     return 0;
 }
@@ -97,6 +101,11 @@ inline bool set_part(const SetShape *s, int part, SetPart *d)
         d->ptr = s->mem + (part ? align256((size_t)n2 * 4) : 0) + (part == 2 ? align256((size_t)n2) : 0);
         d->shape[0] = d->shape[1] = xy; d->strides[0] = 1; d->strides[1] = xy;
         d->code = part ? kDLUInt : kDLInt; d->bits = part == 0 ? 32 : (part == 1 ? 8 : 16);
+        break;
+    case GVOM_PRODUCT_ROLLOUTS:
+        if (part == 0) { rows(s->mem, s->cap, 4); d->code = kDLInt; }
+        else if (part == 1) { rows(s->mem + align256((size_t)s->cap * 16), s->cap, s->cols); d->code = kDLUInt; d->bits = 16; }
+        else return false;
         break;
     default: return false;
     }

@@ -162,6 +162,8 @@ ABI = [
     ("gvom_raycast", _I, [_P, _P, _I64, _P, _I64, _I, _I, _DP, ctypes.POINTER(_I64)]),
     ("gvom_cost_to_go", _I, [_P, _I64, _P, _P, _I, _P, _I64, ctypes.c_int32, ctypes.c_int32, _I, ctypes.POINTER(_I64),
                              ctypes.POINTER(_I64)]),
+    ("gvom_footprint_set", _I, [_P, ctypes.c_int32, _P, _P]),
+    ("gvom_score_rollouts", _I, [_P, _I64, _P, _P, _P, _I64, _I64, _I, ctypes.POINTER(_I64), ctypes.POINTER(_I64)]),
     ("gvom_set_profiling", _I, [_P, _I]),
     ("gvom_host_timing", _I, [_P, ctypes.POINTER(ctypes.c_double * 8)]),
     ("gvom_set_tuning", _I, [_P, ctypes.c_char_p, _I]),
@@ -515,7 +517,8 @@ class DeviceMaps(_Export):
         cells = _ctg_goals(goals, g.xy_size, None if goals_in_cells else (g.xy_resolution, self.origin))
         params, flags = _ctg_params(g.xy_resolution, inflation_radius, density_threshold, include_negative, unknown, base, soft_weight,
                                     rough_weight, roughness_range)
-        return g._cost_to_go(self.set_id, params, None, 0, cells, _ctg_max_cost(max_cost), _ctg_max_rounds(max_rounds), flags)
+        return g._cost_to_go(self.set_id, params, None, 0, cells, _ctg_max_cost(max_cost), _ctg_max_rounds(max_rounds), flags,
+                             origin=self.origin)
 
 
 # ---- device-resident 3-D products (Gvom.occupancy_grid_device and friends) ----------------------------------------
@@ -523,11 +526,12 @@ PRODUCT_OCCUPANCY, PRODUCT_VOXEL_CLOUD, PRODUCT_HEIGHT_CLOUD, PRODUCT_INFERRED_H
 PRODUCT_CLEARANCE = 5                     # GVOM_PRODUCT_CLEARANCE: made by gvom_clearance, not by gvom_device_product
 PRODUCT_RAYCAST = 6                       # GVOM_PRODUCT_RAYCAST: made by gvom_raycast, not by gvom_device_product
 PRODUCT_COSTFIELD = 7                     # GVOM_PRODUCT_COSTFIELD: made by gvom_cost_to_go, not by gvom_device_product
+PRODUCT_ROLLOUTS = 10                     # GVOM_PRODUCT_ROLLOUTS: made by gvom_score_rollouts (kinds 8 and 9 are not assigned)
 # element type of part k of a product, by kind (what set_part() of csrc/gvom_setlayout.h gives as DLPack code and bits)
 _PRODUCT_DTYPES = {PRODUCT_OCCUPANCY: (np.uint8,), PRODUCT_VOXEL_CLOUD: (np.float32, np.float32, np.int64),
                    PRODUCT_HEIGHT_CLOUD: (np.float32,), PRODUCT_INFERRED_HEIGHT_CLOUD: (np.float32,),
                    PRODUCT_CLEARANCE: (np.float32, np.int32), PRODUCT_RAYCAST: (np.int32, np.float32),
-                   PRODUCT_COSTFIELD: (np.int32, np.uint8, np.uint16)}
+                   PRODUCT_COSTFIELD: (np.int32, np.uint8, np.uint16), PRODUCT_ROLLOUTS: (np.int32, np.uint16)}
 CLEARANCE_FAR = 2147483647                # GVOM_CLEARANCE_FAR: squared_cells where no obstacle is in reach
 _CLEARANCE_NO_NEGATIVE = 1                # GVOM_CLEARANCE_NO_NEGATIVE
 
@@ -792,14 +796,25 @@ class DeviceCostField(_ProductView):
     = CTG_STEPS[k]; CTG_GOAL at a goal, CTG_NONE where unreached, CTG_UNSETTLED only in a field that is not final) and
     `.cell_cost` uint16 [xy, xy], the cost map the solver used (0 = blocked) -- three DeviceArrays of one product, [x, y]-indexed
     with strides (1, xy) like a DeviceMap.  `.converged`, `.rounds`, `.reached` (cells with a finite cost) and `.goals_seeded` (goals
-    on unblocked cells) describe the solve.  A snapshot: later scans and combines do not change it.  copy_to_host() returns (cost,
+    on unblocked cells) describe the solve; `.origin` is the window corner in world metres.  A snapshot: later scans and combines do not change it.  copy_to_host() returns (cost,
     direction, cell_cost) as Fortran-ordered numpy [x, y]."""
 
-    def __init__(self, hold, info):
+    def __init__(self, hold, info, origin=(0.0, 0.0)):
         _ProductView.__init__(self, hold)
         self.cost, self.direction, self.cell_cost = DeviceArray(hold, 0), DeviceArray(hold, 1), DeviceArray(hold, 2)
         self.converged, self.rounds, self.reached, self.goals_seeded = bool(info[0]), int(info[1]), int(info[2]), int(info[3])
+        self.origin = np.array(origin, np.float64)          # the window corner in world metres (x, y[, z]): what score_rollouts places poses with
         self._host = None
+
+    def score_rollouts(self, poses):
+        """Scores K candidate trajectories against this field with the mapper's footprint table (Gvom.set_footprint): per pose the
+        maximum of `.cell_cost` under the footprint turned to the pose's heading (0 where it touches a blocked cell or leaves the
+        window), per rollout where it first collides, the cost up to there and `.cost` under the last free pose -- a DeviceRollouts,
+        computed on the GPU behind the solve; no host wait once the poses are up.  poses: (K, T, 3) = (x, y, yaw) in world metres
+        and radians, ROUNDED TO float32.  include/gvom_hip.h "rollout scoring" has the definition."""
+        g = self._hold._owner
+        a = _rollout_poses(poses)
+        return g._score_rollouts(self.product_id, None, None, _ptr(a), a.shape[0], a.shape[1], 0, self.origin)
 
     def copy_to_host(self):
         return self.cost.copy_to_host(), self.direction.copy_to_host(), self.cell_cost.copy_to_host()
@@ -825,6 +840,180 @@ class DeviceCostField(_ProductView):
             x, y = x + CTG_STEPS[k][0], y + CTG_STEPS[k][1]
             path.append((x, y))
         raise RuntimeError("the directions do not lead to a goal")
+
+
+# ---- rollout scoring (Gvom.set_footprint, DeviceCostField.score_rollouts and friends; include/gvom_hip.h "rollout scoring") ----
+ROLLOUT_CLEAR, ROLLOUT_COLLISION, ROLLOUT_LEFT_WINDOW, ROLLOUT_INVALID = range(4)   # GVOM_ROLLOUT_*: summary[:, 0]
+ROLLOUT_MAX_T = 4096
+ROLLOUT_MAX_POSES = 1 << 26
+FOOTPRINT_MAX_HEADINGS = 1024
+FOOTPRINT_MAX_CELLS = 16384               # per heading
+FOOTPRINT_MAX_TABLE = 1 << 22             # offsets of all headings together
+
+
+def _box_distance(px, py, hx, hy):
+    """distance of the points (px, py) from the axis-aligned box [-hx, hx] x [-hy, hy]"""
+    return np.hypot(np.maximum(np.abs(px) - hx, 0.0), np.maximum(np.abs(py) - hy, 0.0))
+
+
+def _footprint_table(masks, n):
+    """boolean masks [H][dy + n][dx + n] -> (start int32 [H + 1], offsets int16 [total, 2]), the cells of a heading row by row"""
+    start, offs = [0], []
+    for m in masks:
+        iy, ix = np.nonzero(m)                                          # (row-major: dy ascending, then dx)
+        if iy.size < 1 or iy.size > FOOTPRINT_MAX_CELLS:
+            raise ValueError("a footprint heading must have between 1 and %d cells, got %d" % (FOOTPRINT_MAX_CELLS, iy.size))
+        offs.append(np.stack([ix - n, iy - n], axis=1))
+        start.append(start[-1] + iy.size)
+    if start[-1] > FOOTPRINT_MAX_TABLE:
+        raise ValueError("a footprint table holds at most 2**22 offsets, got %d" % start[-1])
+    return np.array(start, np.int32), np.ascontiguousarray(np.concatenate(offs), dtype=np.int16)
+
+
+def rectangle_footprint(front, rear, half_width, xy_resolution, headings=64, margin=0.0):
+    """The footprint table (start, offsets) of a rectangular vehicle for Gvom.set_footprint: heading h of `headings` turns the
+    rectangle [-rear, front] x [-half_width, half_width] (metres, x forward) by 2 pi h / headings.  The cell offset (dx, dy)
+    belongs to a heading iff the turned rectangle, grown by `margin` metres all round, meets the OPEN square of side 2 *
+    xy_resolution centred at (dx, dy) * xy_resolution -- every cell the footprint can overlap wherever inside its cell the pose
+    lies: the mask is conservative, and no cell of it is further than xy_resolution * sqrt(2) + margin from the rectangle.  Pure
+    numpy in float64; sines and cosines are exact at quarter turns."""
+    front, rear, hw, res, margin = float(front), float(rear), float(half_width), float(xy_resolution), float(margin)
+    H = int(headings)
+    if H != headings or not 1 <= H <= FOOTPRINT_MAX_HEADINGS:
+        raise ValueError("headings must be an integer in 1 .. %d, got %r" % (FOOTPRINT_MAX_HEADINGS, headings))
+    if not (math.isfinite(front) and math.isfinite(rear) and math.isfinite(hw) and front + rear >= 0 and hw >= 0):
+        raise ValueError("front + rear and half_width must be finite and >= 0, got %r, %r, %r" % (front, rear, half_width))
+    if not (math.isfinite(res) and res > 0):
+        raise ValueError("xy_resolution must be a length > 0, got %r" % (xy_resolution,))
+    if not (math.isfinite(margin) and margin >= 0):
+        raise ValueError("margin must be a distance >= 0, got %r" % (margin,))
+    n = int(math.ceil((math.hypot(max(abs(front), abs(rear)), hw) + margin) / res)) + 2
+    if n > 32767:
+        raise ValueError("the footprint reaches further than 32767 cells")
+    if (2 * n + 1) ** 2 > 64 * FOOTPRINT_MAX_CELLS:
+        raise ValueError("the footprint covers more than %d cells" % FOOTPRINT_MAX_CELLS)
+    g = np.arange(-n, n + 1, dtype=np.float64) * res
+    px, py = np.meshgrid(g, g)                                          # [dy + n][dx + n]: the squares' centres
+    mx, hx = 0.5 * (front - rear), 0.5 * (front + rear)                 # the rectangle in its own frame: centre (mx, 0), half sizes (hx, hw)
+    quarter = ((1.0, 0.0), (0.0, 1.0), (-1.0, 0.0), (0.0, -1.0))
+    masks = []
+    for h in range(H):
+        if (4 * h) % H == 0:
+            c, s = quarter[(4 * h) // H]
+        else:
+            a = 2.0 * math.pi * h / H
+            c, s = math.cos(a), math.sin(a)
+        # corners in the world frame (body (bx, by) -> (c bx - s by, s bx + c by))
+        body = [(front, hw), (front, -hw), (-rear, -hw), (-rear, hw)]
+        cwx = np.array([c * bx - s * by for bx, by in body])
+        cwy = np.array([s * bx + c * by for bx, by in body])
+        # separating axes: the square's two (world x, y) and the rectangle's two (u = (c, s), v = (-s, c)); the square is open
+        pu, pv = c * px + s * py, -s * px + c * py
+        r = res * (abs(c) + abs(s))                                     # the square's half extent along u and along v
+        hit = ((cwx.max() > px - res) & (px + res > cwx.min()) & (cwy.max() > py - res) & (py + res > cwy.min()) &
+               (front > pu - r) & (pu + r > -rear) & (hw > pv - r) & (pv + r > -hw))
+        if margin > 0.0:
+            # apart, two convex polygons are closest at a corner of one of them: the rectangle's corners against the square (a box
+            # in the world frame), the square's corners against the rectangle (a box in its own)
+            d = np.full(px.shape, np.inf)
+            for k in range(4):
+                d = np.minimum(d, _box_distance(cwx[k] - px, cwy[k] - py, res, res))
+            for sx, sy in ((1, 1), (1, -1), (-1, -1), (-1, 1)):
+                qx, qy = px + sx * res, py + sy * res
+                d = np.minimum(d, _box_distance(c * qx + s * qy - mx, -s * qx + c * qy, hx, hw))
+            hit |= d < margin
+        masks.append(hit)
+    return _footprint_table(masks, n)
+
+
+def disc_footprint(radius, xy_resolution):
+    """The footprint table (start, offsets) of a disc of `radius` metres, one heading: the offsets whose open square of side 2 *
+    xy_resolution the disc meets (the same conservative rule as rectangle_footprint)."""
+    radius, res = float(radius), float(xy_resolution)
+    if not (math.isfinite(radius) and radius >= 0):
+        raise ValueError("radius must be a distance >= 0, got %r" % (radius,))
+    if not (math.isfinite(res) and res > 0):
+        raise ValueError("xy_resolution must be a length > 0, got %r" % (xy_resolution,))
+    n = int(math.ceil(radius / res)) + 2
+    if n > 32767 or (2 * n + 1) ** 2 > 64 * FOOTPRINT_MAX_CELLS:
+        raise ValueError("the footprint covers more than %d cells" % FOOTPRINT_MAX_CELLS)
+    g = np.arange(-n, n + 1, dtype=np.float64) * res
+    px, py = np.meshgrid(g, g)
+    hit = (_box_distance(px, py, res, res) < radius) | ((px == 0.0) & (py == 0.0))
+    return _footprint_table([hit], n)
+
+
+def _footprint_arrays(table):
+    """(start, offsets) as the library takes them: C-contiguous int32 [H + 1] and int16 [total, 2]; ValueError for what it would refuse"""
+    try:
+        start, offsets = table
+    except (TypeError, ValueError):
+        raise ValueError("a footprint table is a pair (start, offsets)")
+    st, of = np.asarray(start), np.asarray(offsets)
+    if st.ndim != 1 or not 2 <= st.shape[0] <= FOOTPRINT_MAX_HEADINGS + 1 or st.dtype.kind not in "iu":
+        raise ValueError("start must be integers of shape (H + 1,) with 1 <= H <= %d, got %r %s" % (FOOTPRINT_MAX_HEADINGS, st.shape, st.dtype))
+    if of.ndim != 2 or of.shape[1] != 2 or of.dtype.kind not in "iu":
+        raise ValueError("offsets must be integers of shape (total, 2), got %r %s" % (of.shape, of.dtype))
+    st = st.astype(np.int64)
+    m = np.diff(st)
+    if st[0] != 0 or (m < 1).any() or (m > FOOTPRINT_MAX_CELLS).any():
+        raise ValueError("start must begin at 0 and give every heading between 1 and %d cells" % FOOTPRINT_MAX_CELLS)
+    if st[-1] != of.shape[0]:
+        raise ValueError("start[-1] = %d, but there are %d offsets" % (st[-1], of.shape[0]))
+    if st[-1] > FOOTPRINT_MAX_TABLE:
+        raise ValueError("a footprint table holds at most 2**22 offsets, got %d" % st[-1])
+    if of.size and (of.min() < -32768 or of.max() > 32767):
+        raise ValueError("offsets must fit int16")
+    return np.ascontiguousarray(st, dtype=np.int32), np.ascontiguousarray(of, dtype=np.int16)
+
+
+def _rollout_shape(K, T):
+    try:
+        ok = int(K) == K and int(T) == T
+    except (TypeError, ValueError, OverflowError):
+        ok = False
+    if not ok or not 1 <= int(T) <= ROLLOUT_MAX_T or int(K) < 1:
+        raise ValueError("rollouts need K >= 1 trajectories of 1 <= T <= %d poses, got K = %r, T = %r" % (ROLLOUT_MAX_T, K, T))
+    if int(K) * int(T) > ROLLOUT_MAX_POSES:
+        raise ValueError("at most 2**26 poses per call, got %d x %d" % (int(K), int(T)))
+    return int(K), int(T)
+
+
+def _rollout_poses(poses):
+    """poses -> C-contiguous float32 (K, T, 3)"""
+    a = np.asarray(poses)
+    if a.ndim != 3 or a.shape[2] != 3:
+        raise ValueError("poses must have shape (K, T, 3) = (x, y, yaw), got %r" % (a.shape,))
+    if a.dtype.kind not in "iuf":
+        raise ValueError("poses must be numbers, got dtype %s" % a.dtype)
+    _rollout_shape(a.shape[0], a.shape[1])
+    return np.ascontiguousarray(a, dtype=np.float32)
+
+
+def _rollout_origin(origin, xy_resolution):
+    """the window corner in world metres -> round(origin / xy_resolution) per axis, as world_to_cells places points"""
+    o = np.asarray(origin, np.float64).reshape(-1)
+    if o.shape[0] < 2 or not np.isfinite(o[:2]).all():
+        raise ValueError("origin must be (x, y) in finite world metres, got %r" % (origin,))
+    c = np.round(o[:2] / float(xy_resolution))
+    if (np.abs(c) > 2.0 ** 40).any():
+        raise ValueError("origin lies beyond 2**40 cells: %r" % (origin,))
+    return (_I64 * 2)(int(c[0]), int(c[1]))
+
+
+class DeviceRollouts(_ProductView):
+    """The result of DeviceCostField.score_rollouts() / Gvom.score_rollouts_of() / score_rollouts_of_device(): `.summary` int32
+    [K, 4] -- per rollout {status (ROLLOUT_*), first blocked pose (T: none), path cost (the pose costs in front of it, summed),
+    terminal (the cost-to-go under the last free pose; CTG_UNREACHED without one)} -- and `.pose_cost` uint16 [K, T], the maximum
+    cell cost under the footprint at each pose (0 = blocked): two DeviceArrays of one product, row i = rollout i.  A snapshot: later
+    scans, combines and set_footprint calls do not change it.  copy_to_host() returns (summary, pose_cost) as numpy."""
+
+    def __init__(self, hold):
+        _ProductView.__init__(self, hold)
+        self.summary, self.pose_cost = DeviceArray(hold, 0), DeviceArray(hold, 1)
+
+    def copy_to_host(self):
+        return self.summary.copy_to_host(), self.pose_cost.copy_to_host()
 
 
 class _OutputPool(object):
@@ -1513,17 +1702,17 @@ class Gvom(object):
         return self._raycast(ctypes.c_void_p(int(from_ptr)), K, ctypes.c_void_p(int(to_ptr)), n, 1, unknown_blocks, check_target)
 
     # ---- cost-to-go fields (an extension; include/gvom_hip.h "cost-to-go fields") ----
-    def _cost_to_go(self, set_id, params, cost_ptr, on_device, cells, max_cost, max_rounds, flags):
+    def _cost_to_go(self, set_id, params, cost_ptr, on_device, cells, max_cost, max_rounds, flags, origin=(0.0, 0.0)):
         info = (_I64 * 4)()
         hold = self._make_product(lambda pid: self._lib.gvom_cost_to_go(
             self._h, int(set_id), ctypes.byref(params) if params is not None else None, cost_ptr, int(on_device), _ptr(cells),
             cells.shape[0], max_cost, max_rounds, flags, pid, info), PRODUCT_COSTFIELD)
-        return DeviceCostField(hold, list(info))
+        return DeviceCostField(hold, list(info), origin)
 
-    def cost_to_go_of(self, cost, goals, max_cost=None, max_rounds=0):
+    def cost_to_go_of(self, cost, goals, max_cost=None, max_rounds=0, origin=(0.0, 0.0)):
         """DeviceMaps.cost_to_go() of a cost map of the caller's: a numpy [x, y] array of shape (xy_size, xy_size) in any memory
         order, integers in 0 .. 65535 (0 = blocked); goals: (G, 2) window cells.  Needs no scan and no combine.  A convenience
-        route: the map is copied to the device."""
+        route: the map is copied to the device.  origin: the window corner in world metres, kept as the field's `.origin`."""
         a = np.asarray(cost)
         if a.shape != (self.xy_size, self.xy_size):
             raise ValueError("cost must have shape (%d, %d), got %r" % (self.xy_size, self.xy_size, a.shape))
@@ -1535,16 +1724,65 @@ class Gvom(object):
             raise ValueError("cost must lie in 0 .. 65535 (0 = blocked)")
         cells = _ctg_goals(goals, self.xy_size, None)
         c = np.asfortranarray(a, dtype=np.int32)                        # x fastest
-        return self._cost_to_go(-1, None, _ptr(c), 0, cells, _ctg_max_cost(max_cost), _ctg_max_rounds(max_rounds), 0)
+        return self._cost_to_go(-1, None, _ptr(c), 0, cells, _ctg_max_cost(max_cost), _ctg_max_rounds(max_rounds), 0, origin=origin)
 
-    def cost_to_go_of_device(self, cost_ptr, goals, max_cost=None, max_rounds=0):
+    def cost_to_go_of_device(self, cost_ptr, goals, max_cost=None, max_rounds=0, origin=(0.0, 0.0)):
         """The same for a cost map in device memory (the raw device address of xy_size*xy_size int32, cell (x, y) at
         [y*xy_size + x]; the data must be ready when the call is made).  Values outside 0 .. 65535 are clamped into the range."""
         if not cost_ptr:
             raise ValueError("cost_ptr must be a device address")
         cells = _ctg_goals(goals, self.xy_size, None)
         return self._cost_to_go(-1, None, ctypes.c_void_p(int(cost_ptr)), 1, cells, _ctg_max_cost(max_cost),
-                                _ctg_max_rounds(max_rounds), 0)
+                                _ctg_max_rounds(max_rounds), 0, origin=origin)
+
+    # ---- rollout scoring (an extension; include/gvom_hip.h "rollout scoring") ----
+    def set_footprint(self, table):
+        """Sets the vehicle's footprint table for the score_rollouts calls: what rectangle_footprint() / disc_footprint() return, or
+        raw (start, offsets) arrays -- start int32 (H + 1,), offsets int16 (total, 2) = (dx, dy) in cells, heading h owning
+        offsets[start[h]:start[h + 1]].  Replaces a previous table; products made with it are unchanged."""
+        st, of = _footprint_arrays(table)
+        self._check(self._lib.gvom_footprint_set(self._h, st.shape[0] - 1, _ptr(st), _ptr(of)))
+
+    def _score_rollouts(self, field_id, cost_ptr, ctg_ptr, poses_ptr, K, T, on_device, origin):
+        oc = _rollout_origin(origin, self.xy_resolution)
+        return DeviceRollouts(self._make_product(lambda pid: self._lib.gvom_score_rollouts(
+            self._h, int(field_id), cost_ptr, ctg_ptr, poses_ptr, int(K), int(T), int(on_device), oc, pid), PRODUCT_ROLLOUTS,
+            self._check_args))
+
+    def score_rollouts_of(self, cell_cost, poses, cost_to_go=None, origin=(0.0, 0.0)):
+        """DeviceCostField.score_rollouts() against maps of the caller's: cell_cost a numpy [x, y] array of shape (xy_size, xy_size)
+        in any memory order, whole numbers in 0 .. 65535 (0 = blocked); cost_to_go (optional) int32 of the same shape, the field
+        the terminal column is read from; origin: the window corner in world metres.  Needs no scan and no combine.  A convenience
+        route: maps and poses are copied to the device."""
+        maps = []
+        for name, m, dt, lo, hi in (("cell_cost", cell_cost, np.uint16, 0, 65535), ("cost_to_go", cost_to_go, np.int32, -2 ** 31, 2 ** 31 - 1)):
+            if m is None:
+                if name == "cell_cost":
+                    raise ValueError("cell_cost must be an array")
+                maps.append(None)
+                continue
+            a = np.asarray(m)
+            if a.shape != (self.xy_size, self.xy_size):
+                raise ValueError("%s must have shape (%d, %d), got %r" % (name, self.xy_size, self.xy_size, a.shape))
+            if a.dtype.kind == "f" and not np.isfinite(a).all():
+                raise ValueError("%s must be finite" % name)
+            if a.dtype.kind not in "iuf" or (a.dtype.kind == "f" and (a != np.floor(a)).any()):
+                raise ValueError("%s must hold whole numbers" % name)
+            if a.size and (a.min() < lo or a.max() > hi):
+                raise ValueError("%s must lie in %d .. %d" % (name, lo, hi))
+            maps.append(np.asfortranarray(a, dtype=dt))                 # x fastest
+        p = _rollout_poses(poses)
+        return self._score_rollouts(-1, _ptr(maps[0]), _ptr(maps[1]), _ptr(p), p.shape[0], p.shape[1], 0, origin)
+
+    def score_rollouts_of_device(self, cell_cost_ptr, poses_ptr, K, T, cost_to_go_ptr=None, origin=(0.0, 0.0)):
+        """The same for maps and poses in device memory: raw device addresses of xy_size*xy_size uint16 (cell (x, y) at
+        [y*xy_size + x]), K x T x 3 float32 (C-contiguous) and, optionally, xy_size*xy_size int32; the data must be ready when the
+        call is made.  Enqueues and returns: no host wait."""
+        if not cell_cost_ptr or not poses_ptr:
+            raise ValueError("cell_cost_ptr and poses_ptr must be device addresses")
+        K, T = _rollout_shape(K, T)
+        return self._score_rollouts(-1, ctypes.c_void_p(int(cell_cost_ptr)), ctypes.c_void_p(int(cost_to_go_ptr)) if cost_to_go_ptr else None,
+                                    ctypes.c_void_p(int(poses_ptr)), K, T, 1, origin)
 
     def make_debug_voxel_map(self):
         """float32[Cc, 8] rows {x, y, z, hit/total, hit, l0-l1, l1-l2, l2} (reference gvom.py:363-378) while the mapper

@@ -542,6 +542,70 @@ int gvom_cost_to_go(gvom_t *h, int64_t map_set_id, const gvom_ctg_params *params
                     const int32_t *goals /* [n_goals][2] */, int64_t n_goals, int32_t max_cost, int32_t max_rounds, int flags,
                     int64_t *product_id, int64_t info[4]);
 
+/* --- rollout scoring (an extension: the inner loop of a sampling / MPPI planner -- what does the vehicle's footprint, turned to each
+ * pose's heading, touch on the cost map, and where does each candidate trajectory first collide) ------------------------------------
+ * gvom_score_rollouts scores, on the GPU, K trajectories of T poses each against a uint16 cost map -- a cost field's (part 2 of a
+ * GVOM_PRODUCT_COSTFIELD) or the caller's -- with the FOOTPRINT TABLE gvom_footprint_set gave the handle, and leaves the result in
+ * device memory as a product (kind GVOM_PRODUCT_ROLLOUTS) that gvom_device_product_export / _release / _dlpack / _copy handle like the
+ * others.  gvom_get_tuning "rollouts" (read-only): 1 -- how a caller probes a library for these entry points (an addition:
+ * GVOM_ABI_VERSION stays); "footprint" (read-only): 1 while a table is set.  All arithmetic that decides a result is integer but the
+ * two roundings named below: the result is exact.
+ *
+ * DEFINITION.
+ * FOOTPRINT  a table of H headings, 1 <= H <= 1024.  Heading k has the cell offsets offsets[start[k] .. start[k + 1]), each an int16
+ *            pair (dx, dy); start is int32 [H + 1] with start[0] = 0; every heading has between 1 and 16384 cells and the table at
+ *            most 2^22 offsets.  The library computes no geometry: it walks the table.  (The Python binding builds tables for
+ *            rectangles and discs.)
+ * POSES      float32 [K][T][3] = (x, y, yaw), C-contiguous, world metres and radians.  1 <= T <= 4096, K >= 1, K * T <= 2^26.
+ * CENTRE     per axis c = floor((double)x / xy_resolution) - o with o = origin_cells[axis] = round(window origin / xy_resolution), the
+ *            rule the binding's world_to_cells uses.  A finite coordinate with |x / xy_resolution| >= 2^30 lies outside the window,
+ *            however far.  |o| <= 2^40.
+ * HEADING    k = ((int)rintf(yaw * s)) mod H, made non-negative, with s = (float)(H / 2 pi) (the quotient in float64, rounded once):
+ *            one float32 multiply, no contraction, round half to even.
+ * INVALID    a pose is invalid if x, y or yaw is not finite or |yaw * s| < 2^24 does not hold.
+ * POSE COST  with c the cost map (0 = blocked, as part 2 of a cost field): 0 if the pose is invalid, or any footprint cell (centre +
+ *            offset) lies outside the window, or any footprint cell inside the window has c == 0; otherwise the maximum of c over the
+ *            footprint cells (unsigned: costs >= 32768 survive).  Every pose is evaluated: nothing depends on scheduling.
+ * SUMMARY    first_blocked = the smallest t with pose cost 0, or T.  status is decided at that pose: GVOM_ROLLOUT_CLEAR if there is
+ *            none; GVOM_ROLLOUT_INVALID if the pose is invalid; else GVOM_ROLLOUT_COLLISION if a footprint cell inside the window has
+ *            c == 0; else GVOM_ROLLOUT_LEFT_WINDOW.  path_cost = the sum of the pose costs of t < first_blocked (<= 4096 * 65535 <
+ *            2^31).  terminal = D[centre cell of pose first_blocked - 1] where a cost-to-go field D was given; GVOM_CTG_UNREACHED
+ *            when first_blocked == 0, when no field was given, and when that centre cell lies outside the window (a footprint need
+ *            not contain its own centre).
+ * part 0 = int32 [K, 4] {status, first_blocked, path_cost, terminal}; part 1 = uint16 [K, T] pose costs; row i = rollout i.
+ *
+ * gvom_footprint_set validates the table, copies it to the device and returns after the copy.  A later call replaces the table; the
+ * copy runs on the handle's stream, behind whatever still reads the previous one.  GVOM_ERR_INVALID: NULL arguments, n_headings
+ * outside 1 .. 1024, start[0] != 0, a heading with fewer than 1 or more than 16384 cells; GVOM_ERR_CAPACITY: more than 2^22 offsets.
+ *
+ * gvom_score_rollouts: INPUT, one of two.  costfield_id >= 0: a live GVOM_PRODUCT_COSTFIELD; its part 2 is c and its part 0 is D, read
+ * on the handle's stream behind the solve that wrote them; cell_cost and cost_to_go must be NULL.  costfield_id < 0: cell_cost (uint16,
+ * xy_size * xy_size, cell (x, y) at [y*xy_size + x]) and optionally cost_to_go (int32, same order; NULL: every terminal is
+ * GVOM_CTG_UNREACHED).  on_device != 0: poses and map pointers are device addresses, read in place (the data must be ready when the
+ * call is made); the call enqueues and returns without a host wait.  on_device == 0: poses and map pointers are host memory, staged
+ * through a buffer of the handle; the call returns after the upload.  (With a cost field id, on_device says where the poses are.)
+ * The product is a snapshot: later scans, combines and gvom_footprint_set calls do not change it.
+ * Products of this kind live in the product-set pool ("device_product_sets"), sized by K and T: at most GVOM_MAX_PRODUCT_SETS; an
+ * unexported one goes back to the pool with the next gvom_score_rollouts call (a smaller one is given up for one that holds K x T).
+ * gvom_get_tuning "rollout_allocations" (read-only): device allocations the entry point has made on this handle (its product sets and
+ * the staging buffer of the host route); it does not grow in steady state at a fixed K and T.
+ * gvom_device_product(GVOM_PRODUCT_ROLLOUTS) is GVOM_ERR_INVALID (this call makes them).  Kinds 8 and 9 are not assigned.
+ * GVOM_ERR_INVALID: a sharded handle; no footprint table set; a field id AND map pointers, or neither; an unknown or stale field id;
+ * T outside 1 .. 4096; K < 1; NULL poses / origin_cells / product_id; an origin beyond 2^40 cells.  GVOM_ERR_CAPACITY: K * T > 2^26;
+ * xy_size > 4096; every set of the kind exported.
+ * NOT PROVIDED: the sum or mean over the footprint (the cost is the maximum); an early stop at the first collision (every pose is
+ * scored); per-pose output into host memory (copy part 1); poses in any layout other than [K][T][3]; sharded handles;
+ * interpolation between poses (space them a cell apart). */
+#define GVOM_PRODUCT_ROLLOUTS 10   /* part 0 int32 [K, 4] {status, first_blocked, path_cost, terminal}; part 1 uint16 [K, T] pose costs */
+#define GVOM_ROLLOUT_CLEAR 0
+#define GVOM_ROLLOUT_COLLISION 1
+#define GVOM_ROLLOUT_LEFT_WINDOW 2
+#define GVOM_ROLLOUT_INVALID 3
+int gvom_footprint_set(gvom_t *h, int32_t n_headings, const int32_t *start /* [n_headings + 1] */, const int16_t *offsets /* [start[n_headings]][2] */);
+int gvom_score_rollouts(gvom_t *h, int64_t costfield_id, const uint16_t *cell_cost, const int32_t *cost_to_go,
+                        const float *poses /* [K][T][3] */, int64_t K, int64_t T, int on_device, const int64_t origin_cells[2],
+                        int64_t *product_id);
+
 /* --- one map sharded over the GPUs of a node (one rank = one process = one GPU) -------------------
  * No counterpart in the reference (it has no multi-GPU path); semantics = SURVEY 8(e):
  * the rays are data-parallel, the per-voxel accumulators (hit / total: int32 sum, min-height: f32 min)
@@ -788,6 +852,7 @@ int gvom_host_timing(gvom_t *h, double us[8]);
  * "raycast" / "raycast_allocations" (read-only, gvom_get_tuning): see "ray queries" above.
  * "cost_to_go" / "cost_to_go_allocations" / "cost_to_go_tiles" (read-only), "cost_to_go_inner" / "cost_to_go_batch": see
  * "cost-to-go fields" above.
+ * "rollouts" / "footprint" / "rollout_allocations" (read-only, gvom_get_tuning): see "rollout scoring" above.
  * (Test hooks are not part of this library: include/gvom_hip_test.h, lib/libgvom_hip_test.so.) */
 int gvom_set_tuning(gvom_t *h, const char *name, int value);
 /* The value the LAST scan ran with ("segs", "period", "ep_row", "prio", "interleave": what automatic resolved to).

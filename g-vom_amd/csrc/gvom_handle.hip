@@ -448,7 +448,7 @@ VIS void gvom_destroy(gvom_t *h)
     if (h->x_host) hipHostFree(h->x_host);
     for (auto &s : h->slots) { hipFree(s.state); hipFree(s.code16); hipFree(s.tags); fb(s.crows); fb(s.metrics); fb(s.base); fb(s.rowvox); }
     for (auto &f : h->fused) { hipFree(f.state); hipFree(f.tags); fb(f.rows); fb(f.metrics); }
-    fb(h->in_pts); fb(h->cl_g); fb(h->cl_stage); fb(h->rq_stage); fb(h->ctg_work); fb(h->ctg_stage); fb(h->ctg_clr); fb(h->fp_tab); fb(h->ro_stage); if (h->ctg_pin) hipHostFree(h->ctg_pin); fb(h->ri_model); fb(h->ri_raw); fb(h->ri_poses); if (h->ri_poses_pin) hipHostFree(h->ri_poses_pin); fb(h->mo_dev); if (h->mo_pin) hipHostFree(h->mo_pin); fb(h->world_pts[0]); fb(h->world_pts[1]); fb(h->flink[0]); fb(h->flink[1]); fb(h->tl); fb(h->dir_keys); fb(h->dir_perm); hipFree(h->dir_hist);
+    fb(h->in_pts); fb(h->cl_g); fb(h->cl_stage); fb(h->rq_stage); fb(h->ctg_work); fb(h->ctg_stage); fb(h->ctg_clr); fb(h->fp_tab); fb(h->ro_stage); fb(h->al_grid); fb(h->al_stage); if (h->ctg_pin) hipHostFree(h->ctg_pin); fb(h->ri_model); fb(h->ri_raw); fb(h->ri_poses); if (h->ri_poses_pin) hipHostFree(h->ri_poses_pin); fb(h->mo_dev); if (h->mo_pin) hipHostFree(h->mo_pin); fb(h->world_pts[0]); fb(h->world_pts[1]); fb(h->flink[0]); fb(h->flink[1]); fb(h->tl); fb(h->dir_keys); fb(h->dir_perm); hipFree(h->dir_hist);
     hipFree(h->counters); if (h->counters_host) hipHostFree(h->counters_host);
     hipFree(h->descs_dev); if (h->descs_host) hipHostFree(h->descs_host);
     hipFree(h->blockcounts); hipFree(h->blockcounts2); hipFree(h->hmaps2);
@@ -575,6 +575,11 @@ VIS int gvom_get_tuning(gvom_t *h, const char *name, int *value)
     if (!strcmp(name, "rollouts")) { *value = 1; return GVOM_OK; }                                      // read-only: the library has gvom_score_rollouts
     if (!strcmp(name, "footprint")) { *value = h->fp_H > 0 ? 1 : 0; return GVOM_OK; }                   // read-only: a footprint table is set
     if (!strcmp(name, "rollout_allocations")) { *value = h->ro_allocs; return GVOM_OK; }                // read-only: device allocations gvom_score_rollouts has made
+    if (!strcmp(name, "alignments")) { *value = 1; return GVOM_OK; }                                    // read-only: the library has gvom_score_alignments
+    if (!strcmp(name, "alignment_allocations")) { *value = h->al_allocs; return GVOM_OK; }              // read-only: device allocations gvom_score_alignments has made
+    if (!strcmp(name, "alignment_grid_bytes")) { *value = (int)(h->al_grid.bytes > 0x7fffffffu ? 0x7fffffffu : h->al_grid.bytes); return GVOM_OK; }   // read-only: the class grid's allocation
+    if (!strcmp(name, "alignment_points_per_block")) { *value = GVOM_ALIGN_PTS_BLOCK; return GVOM_OK; }  // read-only: returns per k_align_score workgroup
+    if (!strcmp(name, "alignment_candidate_group")) { *value = GVOM_ALIGN_CAND_GROUP; return GVOM_OK; }  // read-only: candidates per k_align_score workgroup
     if (!strcmp(name, "device_product_sets")) { *value = (int)h->psets.size(); return GVOM_OK; }        // read-only: allocated device product sets (every kind)
     if (!strcmp(name, "occupancy_clear")) { *value = h->tune_occ_clear; return GVOM_OK; }
     if (!strcmp(name, "delta_out")) { *value = h->tune_delta_out; return GVOM_OK; }

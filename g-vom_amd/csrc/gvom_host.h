@@ -326,6 +326,11 @@ struct gvom_handle {
     size_t fp_offs_at = 0;
     int fp_H = 0;                                       // 0: no footprint set
     int ro_allocs = 0;
+    // SCAN ALIGNMENT SCORING (gvom_score_alignments): al_grid = the class grid k_align_field rebuilds in every call (2 bits per voxel,
+    // gvom_align_grid_bytes: gvom_get_tuning "alignment_grid_bytes" reads what is allocated), al_stage = the staging copy of a caller's
+    // host cloud and transforms; al_allocs counts the device allocations the entry point has made on this handle (the two and its product sets)
+    Buf al_grid, al_stage;
+    int al_allocs = 0;
 };
 
 namespace gvom_host {

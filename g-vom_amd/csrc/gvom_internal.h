@@ -332,6 +332,31 @@ struct RolloutParams {
 };
 hipError_t gvom_launch_rollouts(hipStream_t s, const RolloutParams &P, const float *poses, const int32_t *fstart, const uint32_t *foffs,
                                 const uint16_t *cell_cost, const int32_t *cost_to_go, int32_t *summary, uint16_t *pose_cost);
+// scan alignment scoring (gvom_align.hip; include/gvom_hip.h "scan alignment scoring" defines the result).  cloud [n][3] float32 and
+// tf [K][12] float64 (rows 0..2 of each 4x4) in device memory; F = the fused map's frame as k_occupancy takes it.  grid: the class
+// grid, gvom_align_grid_bytes(xy, zs) of scratch, rebuilt by every call.  counts [K][6] int32 (cleared here, then {score, occupied,
+// near, free, unknown, outside}), best [4] int32 {best index, best score, n, K}.
+#define GVOM_ALIGN_MAX_POINTS ((int64_t)1 << 20)
+#define GVOM_ALIGN_MAX_CANDIDATES 65536
+#define GVOM_ALIGN_MAX_PAIRS ((int64_t)1 << 32)
+#define GVOM_ALIGN_MAX_WEIGHT 1024
+#define GVOM_ALIGN_PTS_BLOCK 1024                      // returns per k_align_score workgroup (gvom_get_tuning "alignment_points_per_block")
+#define GVOM_ALIGN_CAND_GROUP 32                       // candidates per k_align_score workgroup ("alignment_candidate_group")
+struct AlignParams {
+    double xy_res, z_res;
+    double drcp[2];         // RN(1 / xy_res), RN(1 / z_res) for div_by_res()
+    double origin[3];       // window origin in voxels
+    long   n;
+    int    K;
+    int    xy, zs;
+    int    rw;              // words per row of the class grid: ceil(xy / 16)
+    int    fastdiv;         // as ScanParams::fastdiv
+    int    dilate;
+    int    w[5];            // weights of {occupied, near, free, unknown, outside}
+};
+size_t gvom_align_grid_bytes(int xy, int zs);
+hipError_t gvom_launch_align(hipStream_t s, const OccParams &F, const AlignParams &P, const int32_t *fstate, const uint32_t *ftags,
+                             const float *cloud, const double *tf, uint32_t *grid, int32_t *counts, int32_t *best);
 // storage order [sy][sx] -> reference order [x][y] (window coordinates)
 hipError_t gvom_launch_unwrap_f64(hipStream_t s, int xy, int om0, int om1, const double *in, int in_stride, double *out_xy);
 hipError_t gvom_launch_posdens(hipStream_t s, const Map2dParams &P, const int32_t *fstate,

@@ -1,5 +1,5 @@
 // gvom_product_calls.hip -- the calls that MAKE a device product: gvom_device_product (occupancy grid, voxel cloud, the two height
-// clouds), gvom_clearance, gvom_raycast, gvom_cost_to_go and gvom_score_rollouts (with gvom_footprint_set, which sets its table), and the frame builders they and the debug reads (gvom_debug.hip) give
+// clouds), gvom_clearance, gvom_raycast, gvom_cost_to_go, gvom_score_rollouts (with gvom_footprint_set, which sets its table) and gvom_score_alignments, and the frame builders they and the debug reads (gvom_debug.hip) give
 // the kernels.  Every call takes its set through product_acquire and hands it out through product_publish (gvom_sets.hip); what is
 // left in each body is what is particular to that product: its argument checks, its staging and its launches.
 #include "gvom_host.h"
@@ -84,6 +84,7 @@ VIS int gvom_device_product(gvom_t *h, int kind, int64_t max_rows, int64_t *prod
     static const char *const elsewhere[] = {"a clearance product is made by gvom_clearance", "a raycast product is made by gvom_raycast", "a cost field is made by gvom_cost_to_go"};
     if (kind >= GVOM_PRODUCT_CLEARANCE && kind <= GVOM_PRODUCT_COSTFIELD) { h->err = std::string("gvom_device_product: ") + elsewhere[kind - GVOM_PRODUCT_CLEARANCE]; return GVOM_ERR_INVALID; }
     if (kind == GVOM_PRODUCT_ROLLOUTS) { h->err = "gvom_device_product: rollouts are made by gvom_score_rollouts"; return GVOM_ERR_INVALID; }
+    if (kind == GVOM_PRODUCT_ALIGNMENT) { h->err = "gvom_device_product: alignment scores are made by gvom_score_alignments"; return GVOM_ERR_INVALID; }
     if (kind < 1 || kind > GVOM_N_PRODUCT_KINDS) { h->err = "gvom_device_product: unknown product kind"; return GVOM_ERR_INVALID; }
     if (h->sharded) { h->err = "gvom_device_product: sharded handles are not supported"; return GVOM_ERR_INVALID; }
     if (kind == GVOM_PRODUCT_VOXEL_CLOUD) stats_demand(h);                  // a read of the statistics, like gvom_debug_voxel_map
@@ -428,6 +429,67 @@ VIS int gvom_score_rollouts(gvom_t *h, int64_t costfield_id, const uint16_t *cel
     P.res = h->prm.xy_resolution;
     HIPCHK(h, gvom_launch_rollouts(h->stream, P, pdev, (const int32_t *)h->fp_tab.p, (const uint32_t *)((char *)h->fp_tab.p + h->fp_offs_at),
                                    c16, D, part_ptr<int32_t>(set, 0), part_ptr<uint16_t>(set, 1)));
+    return product_publish(h, set, product_id);
+}
+
+// ---- scan alignment scoring (gvom_score_alignments) ------------------------------------------------------------------------------
+// n returns under K candidate transforms against the CURRENT fused map (gvom_align.hip): k_align_field rebuilds the class grid in a
+// grow-only buffer of the handle, k_align_score counts, k_align_best weighs -- on the handle's stream behind whatever produced the
+// map, read-only; the result is a product of kind GVOM_PRODUCT_ALIGNMENT sized by K.  Enqueues and returns; later scans and combines
+// run behind the kernels on the same stream and never touch the product.
+VIS int gvom_score_alignments(gvom_t *h, const float *cloud, int64_t n, const double *transforms, int64_t K, int on_device, int dilate,
+                              const int32_t weights[5], int64_t *product_id)
+{
+    if (!h || !product_id) return GVOM_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(h->mu);
+    *product_id = -1;
+    if (h->sharded) { h->err = "gvom_score_alignments: sharded handles are not supported"; return GVOM_ERR_INVALID; }
+    if (!cloud || !transforms || !weights) { h->err = "gvom_score_alignments: cloud, transforms and weights must not be NULL"; return GVOM_ERR_INVALID; }
+    if (n < 1) { h->err = "gvom_score_alignments: n must be at least 1"; return GVOM_ERR_INVALID; }
+    if (K < 1) { h->err = "gvom_score_alignments: K must be at least 1"; return GVOM_ERR_INVALID; }
+    if (dilate != 0 && dilate != 1) { h->err = "gvom_score_alignments: dilate must be 0 or 1"; return GVOM_ERR_INVALID; }
+    for (int c = 0; c < 5; ++c)
+        if (weights[c] < -GVOM_ALIGN_MAX_WEIGHT || weights[c] > GVOM_ALIGN_MAX_WEIGHT) { h->err = "gvom_score_alignments: a weight outside -1024 .. 1024"; return GVOM_ERR_INVALID; }
+    if (n > GVOM_ALIGN_MAX_POINTS) { h->err = "gvom_score_alignments: more than 2^20 returns in one call"; return GVOM_ERR_CAPACITY; }
+    if (K > GVOM_ALIGN_MAX_CANDIDATES) { h->err = "gvom_score_alignments: more than 65536 candidates in one call"; return GVOM_ERR_CAPACITY; }
+    if (n * K > GVOM_ALIGN_MAX_PAIRS) { h->err = "gvom_score_alignments: more than 2^32 pairs in one call"; return GVOM_ERR_CAPACITY; }
+    const int xy = h->prm.xy_size, zs = h->prm.z_size;
+    const size_t gb = gvom_align_grid_bytes(xy, zs);
+    if (gb / 4 > 0xffffffffull) { h->err = "gvom_score_alignments: the class grid of this map has 2^32 words or more"; return GVOM_ERR_CAPACITY; }
+    if (!h->has_combined) return GVOM_NO_DATA;
+    HIPCHK(h, hipSetDevice(h->device));
+    DevSet *set = nullptr;
+    const size_t bytes = set_bytes(GVOM_PRODUCT_ALIGNMENT, 0, 0, K);
+    int rc = product_acquire(h, GVOM_PRODUCT_ALIGNMENT, bytes, bytes, "gvom_score_alignments", &h->al_allocs, &set);
+    if (rc) return rc;
+    set->cap = K;
+    if ((rc = stage_buf(h, h->al_grid, gb, h->al_allocs))) return rc;
+    const Fused &F = h->fused[h->cur];
+    OccParams O;
+    occ_params(h, F, O);
+    AlignParams P;
+    memset(&P, 0, sizeof P);
+    P.xy_res = h->prm.xy_resolution; P.z_res = h->prm.z_resolution;
+    P.drcp[0] = 1.0 / h->prm.xy_resolution; P.drcp[1] = 1.0 / h->prm.z_resolution;
+    P.fastdiv = h->tune_fastdiv == 0 ? 0 : h->fastdiv_ok;
+    for (int k = 0; k < 3; ++k) P.origin[k] = (double)F.origin[k];
+    P.n = (long)n; P.K = (int)K; P.xy = xy; P.zs = zs; P.rw = (xy + 15) / 16; P.dilate = dilate;
+    for (int c = 0; c < 5; ++c) P.w[c] = weights[c];
+    const float *cdev = cloud;
+    const double *tdev = transforms;
+    HIPCHK(h, join_second_stream(h));
+    if (!on_device) {                                                       // host inputs: staged, and up before the call returns
+        const size_t tb = (size_t)K * 96, cb = (size_t)n * 12;
+        if ((rc = stage_buf(h, h->al_stage, align256(tb) + cb, h->al_allocs))) return rc;
+        char *st = (char *)h->al_stage.p;
+        HIPCHK(h, hipMemcpyAsync(st, transforms, tb, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(st + align256(tb), cloud, cb, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        tdev = (const double *)st; cdev = (const float *)(st + align256(tb));
+    }
+    if ((rc = set_wait_releases(h, set))) return rc;
+    HIPCHK(h, gvom_launch_align(h->stream, O, P, F.state, F.tags, cdev, tdev, (uint32_t *)h->al_grid.p, part_ptr<int32_t>(set, 0),
+                                part_ptr<int32_t>(set, 1)));
     return product_publish(h, set, product_id);
 }
 }  // extern "C"

@@ -13,7 +13,9 @@
 //                    that wrote it
 //   cost field       xy*xy int32 (cost to go), then xy*xy uint8 (direction), then xy*xy uint16 (cell costs), all [y][x]
 //   rollouts (10)    cap x 4 int32 {status, first_blocked, path_cost, terminal}, then cap x cols uint16 (pose costs); cap = the
-//                    rollouts K and cols = the poses per rollout T of the call that wrote it.  Kinds 8 and 9 are not assigned
+//                    rollouts K and cols = the poses per rollout T of the call that wrote it.  Kinds 8, 9 and 11 are not assigned
+//   alignment (12)   cap x 6 int32 {score, occupied, near, free, unknown, outside}, then 4 int32 {best index, best score, n, K};
+//                    cap = the candidates K of the call that wrote it
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -50,6 +52,7 @@ inline size_t set_bytes(int kind, int xy, int zs, int64_t cap, int64_t cols = 0)
     case GVOM_PRODUCT_RAYCAST: return align256((size_t)cap * 16) + (size_t)cap * 12;
     case GVOM_PRODUCT_COSTFIELD: return align256(n2 * 4) + align256(n2) + n2 * 2;
     case GVOM_PRODUCT_ROLLOUTS: return align256((size_t)cap * 16) + (size_t)cap * (size_t)cols * 2;
+    case GVOM_PRODUCT_ALIGNMENT: return align256((size_t)cap * 24) + 16;
     }
     return 0;
 }
@@ -105,6 +108,11 @@ inline bool set_part(const SetShape *s, int part, SetPart *d)
     case GVOM_PRODUCT_ROLLOUTS:
         if (part == 0) { rows(s->mem, s->cap, 4); d->code = kDLInt; }
         else if (part == 1) { rows(s->mem + align256((size_t)s->cap * 16), s->cap, s->cols); d->code = kDLUInt; d->bits = 16; }
+        else return false;
+        break;
+    case GVOM_PRODUCT_ALIGNMENT:
+        if (part == 0) { rows(s->mem, s->cap, 6); d->code = kDLInt; }
+        else if (part == 1) { d->ptr = s->mem + align256((size_t)s->cap * 24); d->ndim = 1; d->shape[0] = 4; d->strides[0] = 1; d->shape[1] = d->strides[1] = 1; d->code = kDLInt; }
         else return false;
         break;
     default: return false;

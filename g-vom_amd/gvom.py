@@ -164,6 +164,7 @@ ABI = [
                              ctypes.POINTER(_I64)]),
     ("gvom_footprint_set", _I, [_P, ctypes.c_int32, _P, _P]),
     ("gvom_score_rollouts", _I, [_P, _I64, _P, _P, _P, _I64, _I64, _I, ctypes.POINTER(_I64), ctypes.POINTER(_I64)]),
+    ("gvom_score_alignments", _I, [_P, _P, _I64, _P, _I64, _I, _I, _P, ctypes.POINTER(_I64)]),
     ("gvom_set_profiling", _I, [_P, _I]),
     ("gvom_host_timing", _I, [_P, ctypes.POINTER(ctypes.c_double * 8)]),
     ("gvom_set_tuning", _I, [_P, ctypes.c_char_p, _I]),
@@ -527,11 +528,13 @@ PRODUCT_CLEARANCE = 5                     # GVOM_PRODUCT_CLEARANCE: made by gvom
 PRODUCT_RAYCAST = 6                       # GVOM_PRODUCT_RAYCAST: made by gvom_raycast, not by gvom_device_product
 PRODUCT_COSTFIELD = 7                     # GVOM_PRODUCT_COSTFIELD: made by gvom_cost_to_go, not by gvom_device_product
 PRODUCT_ROLLOUTS = 10                     # GVOM_PRODUCT_ROLLOUTS: made by gvom_score_rollouts (kinds 8 and 9 are not assigned)
+PRODUCT_ALIGNMENT = 12                    # GVOM_PRODUCT_ALIGNMENT: made by gvom_score_alignments (kind 11 is not assigned either)
 # element type of part k of a product, by kind (what set_part() of csrc/gvom_setlayout.h gives as DLPack code and bits)
 _PRODUCT_DTYPES = {PRODUCT_OCCUPANCY: (np.uint8,), PRODUCT_VOXEL_CLOUD: (np.float32, np.float32, np.int64),
                    PRODUCT_HEIGHT_CLOUD: (np.float32,), PRODUCT_INFERRED_HEIGHT_CLOUD: (np.float32,),
                    PRODUCT_CLEARANCE: (np.float32, np.int32), PRODUCT_RAYCAST: (np.int32, np.float32),
-                   PRODUCT_COSTFIELD: (np.int32, np.uint8, np.uint16), PRODUCT_ROLLOUTS: (np.int32, np.uint16)}
+                   PRODUCT_COSTFIELD: (np.int32, np.uint8, np.uint16), PRODUCT_ROLLOUTS: (np.int32, np.uint16),
+                   PRODUCT_ALIGNMENT: (np.int32, np.int32)}
 CLEARANCE_FAR = 2147483647                # GVOM_CLEARANCE_FAR: squared_cells where no obstacle is in reach
 _CLEARANCE_NO_NEGATIVE = 1                # GVOM_CLEARANCE_NO_NEGATIVE
 
@@ -1014,6 +1017,106 @@ class DeviceRollouts(_ProductView):
 
     def copy_to_host(self):
         return self.summary.copy_to_host(), self.pose_cost.copy_to_host()
+
+
+ALIGN_MAX_POINTS = 1 << 20
+ALIGN_MAX_CANDIDATES = 65536
+ALIGN_MAX_PAIRS = 1 << 32
+ALIGN_MAX_WEIGHT = 1024
+ALIGN_DEFAULT_WEIGHTS = (2, 1, -1, 0, 0)  # {occupied, near, free, unknown, outside}
+
+
+def _align_shape(n, K):
+    try:
+        ok = int(n) == n and int(K) == K
+    except (TypeError, ValueError, OverflowError):
+        ok = False
+    if not ok or int(n) < 1 or int(K) < 1:
+        raise ValueError("alignment scoring needs n >= 1 returns and K >= 1 candidates, got n = %r, K = %r" % (n, K))
+    n, K = int(n), int(K)
+    if n > ALIGN_MAX_POINTS or K > ALIGN_MAX_CANDIDATES or n * K > ALIGN_MAX_PAIRS:
+        raise ValueError("at most 2**20 returns, 65536 candidates and 2**32 pairs per call, got %d x %d" % (n, K))
+    return n, K
+
+
+def _align_options(dilate, weights):
+    if isinstance(dilate, bool):
+        dilate = int(dilate)
+    if dilate not in (0, 1) or int(dilate) != dilate:
+        raise ValueError("dilate must be 0 or 1, got %r" % (dilate,))
+    w = np.asarray(weights)
+    if w.shape != (5,) or w.dtype.kind not in "iu":
+        raise ValueError("weights must be five integers {occupied, near, free, unknown, outside}, got %r" % (weights,))
+    if (np.abs(w.astype(np.int64)) > ALIGN_MAX_WEIGHT).any():
+        raise ValueError("weights must lie in -1024 .. 1024, got %r" % (weights,))
+    return int(dilate), (ctypes.c_int32 * 5)(*[int(v) for v in w])
+
+
+def _align_transforms(transforms):
+    """transforms float64 (K, 4, 4) or (K, 3, 4) -> C-contiguous float64 (K, 3, 4): rows 0..2"""
+    a = np.asarray(transforms)
+    if a.dtype != np.float64:
+        raise TypeError("transforms must be float64, got %s" % a.dtype)
+    if a.ndim != 3 or a.shape[1:] not in ((4, 4), (3, 4)):
+        raise ValueError("transforms must have shape (K, 4, 4) or (K, 3, 4), got %r" % (a.shape,))
+    return np.ascontiguousarray(a[:, :3, :])
+
+
+def pose_candidates(transform, xy_step, xy_steps, yaw_step, yaw_steps, z_step=0.0, z_steps=0, pivot=None):
+    """Candidate poses around `transform` (4x4) for Gvom.score_alignments: float64 [K, 4, 4] with K = (2 z_steps + 1) *
+    (2 yaw_steps + 1) * (2 xy_steps + 1)**2.  Candidate k is D_k @ transform, where D_k turns the world by a yaw of a * yaw_step
+    about the vertical through `pivot` (world metres; default: the transform's translation) and then moves it by (i * xy_step,
+    j * xy_step, l * z_step), with i, j in -xy_steps .. xy_steps, a in -yaw_steps .. yaw_steps, l in -z_steps .. z_steps.
+    INDEX ORDER: k = ((l' * A + a') * N + j') * N + i' with N = 2 xy_steps + 1, A = 2 yaw_steps + 1 and primes the indices counted
+    from 0 -- x offset fastest, then y offset, then yaw, then z offset; the centre index K // 2 is the all-zero offset, and that
+    candidate is `transform` itself, bit for bit."""
+    T = np.asarray(transform, np.float64)
+    if T.shape != (4, 4):
+        raise ValueError("transform must be a 4x4 matrix, got shape %r" % (T.shape,))
+    for name, v in (("xy_steps", xy_steps), ("yaw_steps", yaw_steps), ("z_steps", z_steps)):
+        if isinstance(v, bool) or int(v) != v or v < 0:
+            raise ValueError("%s must be a whole number >= 0, got %r" % (name, v))
+    for name, v in (("xy_step", xy_step), ("yaw_step", yaw_step), ("z_step", z_step)):
+        if not math.isfinite(float(v)):
+            raise ValueError("%s must be finite, got %r" % (name, v))
+    N, A, Z = 2 * int(xy_steps) + 1, 2 * int(yaw_steps) + 1, 2 * int(z_steps) + 1
+    if N * N * A * Z > ALIGN_MAX_CANDIDATES:
+        raise ValueError("more than 65536 candidates: %d" % (N * N * A * Z))
+    c = T[:3, 3].copy() if pivot is None else np.asarray(pivot, np.float64).reshape(-1)[:3].copy()
+    if c.shape != (3,) or not np.isfinite(c).all():
+        raise ValueError("pivot must be (x, y, z) in finite world metres, got %r" % (pivot,))
+    out = np.empty((Z, A, N, N, 4, 4), np.float64)
+    for l in range(Z):
+        for a in range(A):
+            yaw = (a - int(yaw_steps)) * float(yaw_step)
+            cs, sn = math.cos(yaw), math.sin(yaw)
+            for j in range(N):
+                for i in range(N):
+                    off = ((i - int(xy_steps)) * float(xy_step), (j - int(xy_steps)) * float(xy_step), (l - int(z_steps)) * float(z_step))
+                    if yaw == 0.0 and off == (0.0, 0.0, 0.0):
+                        out[l, a, j, i] = T                               # the input itself: no arithmetic
+                        continue
+                    D = np.identity(4)
+                    D[0, 0], D[0, 1], D[1, 0], D[1, 1] = cs, -sn, sn, cs
+                    D[:3, 3] = c - D[:3, :3].dot(c) + off                 # turn about the pivot, then move
+                    out[l, a, j, i] = D.dot(T)
+    return out.reshape(-1, 4, 4)
+
+
+class DeviceAlignments(_ProductView):
+    """The result of Gvom.score_alignments() / score_alignments_device(): `.counts` int32 [K, 6] -- per candidate {score, returns
+    that end in an occupied voxel, next to one (dilate=1 only), in a free one, in a never-observed one, outside the window} -- and
+    `.best` int32 [4] {best index (the lowest of the best score), best score, n, K}: two DeviceArrays of one product, row k =
+    candidate k.  `.origin`: the fused map's window origin in voxels when the call was made.  A snapshot: later scans and combines
+    do not change it.  copy_to_host() returns (counts, best) as numpy."""
+
+    def __init__(self, hold, origin):
+        _ProductView.__init__(self, hold)
+        self.origin = origin
+        self.counts, self.best = DeviceArray(hold, 0), DeviceArray(hold, 1)
+
+    def copy_to_host(self):
+        return self.counts.copy_to_host(), self.best.copy_to_host()
 
 
 class _OutputPool(object):
@@ -1783,6 +1886,40 @@ class Gvom(object):
         K, T = _rollout_shape(K, T)
         return self._score_rollouts(-1, ctypes.c_void_p(int(cell_cost_ptr)), ctypes.c_void_p(int(cost_to_go_ptr)) if cost_to_go_ptr else None,
                                     ctypes.c_void_p(int(poses_ptr)), K, T, 1, origin)
+
+    # ---- scan alignment scoring (an extension; include/gvom_hip.h "scan alignment scoring") ----
+    def _score_alignments(self, cloud_ptr, n, tf_ptr, K, on_device, dilate, weights):
+        dilate, w = _align_options(dilate, weights)
+        n, K = _align_shape(n, K)
+        hold = self._make_product(lambda pid: self._lib.gvom_score_alignments(self._h, cloud_ptr, n, tf_ptr, K, int(on_device), dilate,
+                                                                              w, pid), PRODUCT_ALIGNMENT, self._check_args)
+        return None if hold is None else DeviceAlignments(hold, np.array(list(self._state().combined_origin), np.float64))
+
+    def score_alignments(self, cloud, transforms, dilate=0, weights=ALIGN_DEFAULT_WEIGHTS):
+        """Holds a scan under K candidate poses against the current fused map on the GPU -- the inner loop of a correlative scan
+        matcher -- and returns a DeviceAlignments: per candidate how many of the n returns end in an occupied voxel, next to one
+        (dilate=1: within one voxel on every axis), in a free one, in a never-observed one and outside the window, the score
+        sum(weights * counts) (weights: five integers in -1024 .. 1024 for {occupied, near, free, unknown, outside}), and the best
+        candidate.  A return under a candidate is classed by the voxel process_pointcloud(cloud, ego, transform=candidate) would
+        add its hit to (without the min_distance rejection).  cloud: float32 (n, 3) -- other dtypes raise TypeError, nothing is
+        cast; transforms: float64 (K, 4, 4) or (K, 3, 4) (pose_candidates builds a grid of them; arbitrary matrices are accepted).
+        Read-only: the map does not change.  None before the first combine.  A convenience route: the arrays are copied to the
+        device."""
+        c = np.asarray(cloud)
+        if c.dtype != np.float32:
+            raise TypeError("cloud must be float32, got %s" % c.dtype)
+        if c.ndim != 2 or c.shape[1] != 3:
+            raise ValueError("cloud must have shape (n, 3), got %r" % (c.shape,))
+        c = np.ascontiguousarray(c)
+        t = _align_transforms(transforms)
+        return self._score_alignments(_ptr(c), c.shape[0], _ptr(t), t.shape[0], 0, dilate, weights)
+
+    def score_alignments_device(self, cloud_ptr, n, transforms_ptr, K, dilate=0, weights=ALIGN_DEFAULT_WEIGHTS):
+        """The same for inputs in device memory: raw device addresses of n x 3 float32 and K x 3 x 4 float64 (rows 0..2 of each
+        candidate, C-contiguous; the data must be ready when the call is made).  Enqueues and returns: no host wait."""
+        if not cloud_ptr or not transforms_ptr:
+            raise ValueError("cloud_ptr and transforms_ptr must be device addresses")
+        return self._score_alignments(ctypes.c_void_p(int(cloud_ptr)), n, ctypes.c_void_p(int(transforms_ptr)), K, 1, dilate, weights)
 
     def make_debug_voxel_map(self):
         """float32[Cc, 8] rows {x, y, z, hit/total, hit, l0-l1, l1-l2, l2} (reference gvom.py:363-378) while the mapper

@@ -606,6 +606,53 @@ int gvom_score_rollouts(gvom_t *h, int64_t costfield_id, const uint16_t *cell_co
                         const float *poses /* [K][T][3] */, int64_t K, int64_t T, int on_device, const int64_t origin_cells[2],
                         int64_t *product_id);
 
+/* --- scan alignment scoring (an extension: the inner loop of a correlative scan matcher -- does the pose a scan is about to be fused
+ * at fit the map it is fused into) -------------------------------------------------------------------------------------------------
+ * gvom_score_alignments holds, on the GPU, a float32 cloud of n returns under K candidate rigid transforms against the CURRENT fused
+ * map: per candidate it counts the returns that end in an occupied voxel, next to one, in a free one, in a never-observed one and
+ * outside the window, weighs the counts into an integer score and names the best candidate.  The result stays in device memory as a
+ * product (kind GVOM_PRODUCT_ALIGNMENT) that gvom_device_product_export / _release / _dlpack / _copy handle like the others.  READ-ONLY:
+ * nothing of the map changes.  gvom_get_tuning "alignments" (read-only): 1 -- how a caller probes a library for this entry point (an
+ * addition: GVOM_ABI_VERSION stays).  A pair (candidate, return) is classed by the voxel that gvom_process_pointcloud(cloud, ego,
+ * transform = candidate) would add the return's hit to: the result is exact.
+ *
+ * DEFINITION.  M_k = candidate k, float64 [3][4]: rows 0..2 of a 4x4, row-major; transforms is [K][3][4], C-contiguous.  p_i =
+ * (x, y, z) float32; cloud is [n][3], C-contiguous.  res = (xy_resolution, xy_resolution, z_resolution), size = (xy_size, xy_size,
+ * z_size), W = the fused map's window origin in voxels, s(v) = the fused state of window voxel v (-1 = never observed, which is also
+ * what a stale tile reads; <= -2 = observed free; >= 0 = occupied).
+ * 1 WORLD POSITION  the scan's own transform rule: w_r = (float)(((x * M[r][0] + y * M[r][1]) + z * M[r][2]) + M[r][3]), products
+ *                   and sums in float64, left to right, no contraction, rounded ONCE to float32.
+ * 2 VOXEL           the scan's endpoint rule: v_r = floor((double)w_r / res_r - W_r).  The pair is OUTSIDE unless 0 <= v_r < size_r
+ *                   on all three axes, compared in float64: NaN, infinities, non-finite matrix entries and products that overflow
+ *                   float32 fall out as OUTSIDE without a special case.  The scan's min_distance rejection is NOT applied: it
+ *                   measures from the world's origin, which says nothing about a fit.
+ * 3 CLASS           in this order: OCCUPIED if s(v) >= 0; NEAR if dilate == 1 and some window voxel u with max_r |u_r - v_r| <= 1 has
+ *                   s(u) >= 0 (voxels outside the window never count as neighbours); FREE if s(v) <= -2; otherwise UNKNOWN.
+ * 4 PER CANDIDATE   the counts {occupied, near, free, unknown, outside}, which sum to n, and score = sum of weights[c] * count[c]
+ *                   (int32; weights in the order of the counts, |weight| <= 1024, so |score| <= 2^30).
+ * 5 BEST            the lowest k whose score is the maximum.
+ * part 0 = int32 [K, 6] {score, occupied, near, free, unknown, outside}, row k = candidate k; part 1 = int32 [4] {best index, best
+ * score, n, K}.
+ *
+ * on_device != 0: cloud and transforms are device addresses, read in place (the data must be ready when the call is made); the call
+ * enqueues and returns without a host wait.  on_device == 0: both are host memory, staged through a buffer of the handle; the call
+ * returns after the upload.  The product is a snapshot of the map as it is when the call is made: later scans and combines do not
+ * change it.  Products of this kind live in the product-set pool ("device_product_sets"), sized by K: at most GVOM_MAX_PRODUCT_SETS;
+ * an unexported one goes back to the pool with the next call.  The call rebuilds, from the fused state, a CLASS GRID of 2 bits per
+ * voxel in a grow-only buffer of the handle (xy_size * ceil(xy_size / 16) * z_size * 4 bytes; gvom_get_tuning "alignment_grid_bytes",
+ * read-only); "alignment_allocations" (read-only): device allocations the entry point has made on this handle (the grid, the staging
+ * buffer of the host route and its product sets) -- it does not grow in steady state.  "alignment_points_per_block" /
+ * "alignment_candidate_group" (read-only): the tile of the scoring kernel.
+ * gvom_device_product(GVOM_PRODUCT_ALIGNMENT) is GVOM_ERR_INVALID (this call makes them).  Kinds 8, 9 and 11 are not assigned.
+ * GVOM_NO_DATA before the first combine.  GVOM_ERR_INVALID: a sharded handle; NULL cloud / transforms / weights / product_id; n < 1
+ * or K < 1; dilate other than 0 or 1; |weight| > 1024.  GVOM_ERR_CAPACITY: n > 2^20; K > 65536; n * K > 2^32; a class grid of 2^32
+ * words or more; every set of the kind exported.
+ * NOT PROVIDED: float64 clouds; per-point weights; hit-count thresholds; a dilation of more than one voxel; sharded handles; single
+ * ring slots (the fused map only); a cache of the class grid across calls. */
+#define GVOM_PRODUCT_ALIGNMENT 12   /* part 0 int32 [K, 6] {score, occupied, near, free, unknown, outside}; part 1 int32 [4] {best index, best score, n, K} */
+int gvom_score_alignments(gvom_t *h, const float *cloud /* [n][3] */, int64_t n, const double *transforms /* [K][3][4] */, int64_t K,
+                          int on_device, int dilate, const int32_t weights[5], int64_t *product_id);
+
 /* --- one map sharded over the GPUs of a node (one rank = one process = one GPU) -------------------
  * No counterpart in the reference (it has no multi-GPU path); semantics = SURVEY 8(e):
  * the rays are data-parallel, the per-voxel accumulators (hit / total: int32 sum, min-height: f32 min)
@@ -853,6 +900,8 @@ int gvom_host_timing(gvom_t *h, double us[8]);
  * "cost_to_go" / "cost_to_go_allocations" / "cost_to_go_tiles" (read-only), "cost_to_go_inner" / "cost_to_go_batch": see
  * "cost-to-go fields" above.
  * "rollouts" / "footprint" / "rollout_allocations" (read-only, gvom_get_tuning): see "rollout scoring" above.
+ * "alignments" / "alignment_allocations" / "alignment_grid_bytes" / "alignment_points_per_block" / "alignment_candidate_group"
+ * (read-only, gvom_get_tuning): see "scan alignment scoring" above.
  * (Test hooks are not part of this library: include/gvom_hip_test.h, lib/libgvom_hip_test.so.) */
 int gvom_set_tuning(gvom_t *h, const char *name, int value);
 /* The value the LAST scan ran with ("segs", "period", "ep_row", "prio", "interleave": what automatic resolved to).

@@ -216,6 +216,30 @@ def _ptr(a):
     return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
 
 
+def _dev(p):
+    """a raw device (or pinned host) address as the library takes it; None and 0 are the null pointer"""
+    return ctypes.c_void_p(int(p)) if p else None
+
+
+def _device_cloud(dtype, row_stride_bytes=None):
+    """(dtype code, row stride in bytes) of a cloud in device memory: float32 is code 0, anything else is read as float64 (1);
+    the rows are packed x, y, z unless a stride is given"""
+    code = 0 if (dtype is np.float32 or np.dtype(dtype) == np.float32) else 1
+    return code, row_stride_bytes or (12 if code == 0 else 24)
+
+
+def _warn_scan(rc):
+    """the reference's two warnings about a scan that changes nothing, for the return codes that stand for them"""
+    if rc == GVOM_EMPTY_CLOUD:
+        print("[WARNING] Processing an empty pointcloud, nothing will happen!")
+    elif rc == GVOM_NO_OVERLAP:
+        print("[WARNING] The pointcloud points don't overlap with any voxels, nothing will happen!")
+
+
+def _warn_empty_ring():
+    print("[WARNING] The map buffer is empty, nothing will happen!")
+
+
 RANGE_U16, RANGE_U32, RANGE_F32 = 0, 1, 2                   # GVOM_RANGE_*
 _RANGE_CODES = {np.dtype(np.uint16): RANGE_U16, np.dtype(np.uint32): RANGE_U32, np.dtype(np.float32): RANGE_F32}
 
@@ -1162,6 +1186,25 @@ class _PinnedOutput(object):
             pool.give_back(self.ptr)
 
 
+def _map_views(raw, xy):
+    """(positive, negative, roughness, visibility) of the pinned output buffer `raw` (uint8) a combine writes: [xy, xy] views of it"""
+    n2 = xy * xy
+    # the library writes the maps in [y][x] memory order: seen through .T they are the reference's
+    # [x, y]-indexed arrays in Fortran order (what gvom_ros.py's reshape(..., order='F') reads
+    # without a copy), and the GPU writes them as contiguous runs without a transpose
+    positive = np.ndarray((xy, xy), np.int32, raw, 0, (4, 4 * xy))
+    negative = np.ndarray((xy, xy), np.int32, raw, 4 * n2, (4, 4 * xy))
+    visibility = np.ndarray((xy, xy), np.int32, raw, 8 * n2, (4, 4 * xy))
+    roughness = np.ndarray((xy, xy), np.float64, raw, 12 * n2, (8, 8 * xy))
+    return positive, negative, roughness, visibility
+
+
+def _occupancy_grids(raw, xy):
+    """(hard, soft, certainty, negative, roughness) of the buffer an occupancy combine writes: five int8 [xy * xy] views of it"""
+    n2 = xy * xy
+    return tuple(raw[k * n2:(k + 1) * n2].view(np.int8) for k in range(5))
+
+
 def transform_from_translation_rotation(translation, rotation):
     """4x4 matrix of a translation (x, y, z) and a quaternion (x, y, z, w): what the node builds with
     tf.TransformerROS.fromTranslationRotation (gvom_ros.py:105).  Restates tf.transformations
@@ -1194,19 +1237,10 @@ class _PendingMaps(object):
     def result(self):
         if not self._done:
             g = self._owner
-            xy = g.xy_size
-            n2 = xy * xy
             origin = np.zeros(3, np.float64)
             g._check(g._lib.gvom_combine_end(g._h, _ptr(origin)))
-            raw = np.asarray(self._holder)
-            if self._occupancy:
-                self._out = (origin,) + tuple(raw[k * n2:(k + 1) * n2].view(np.int8) for k in range(5))
-            else:
-                self._out = (origin,
-                             np.ndarray((xy, xy), np.int32, raw, 0, (4, 4 * xy)),
-                             np.ndarray((xy, xy), np.int32, raw, 4 * n2, (4, 4 * xy)),
-                             np.ndarray((xy, xy), np.float64, raw, 12 * n2, (8, 8 * xy)),
-                             np.ndarray((xy, xy), np.int32, raw, 8 * n2, (4, 4 * xy)))
+            views = _occupancy_grids if self._occupancy else _map_views
+            self._out = (origin,) + views(np.asarray(self._holder), g.xy_size)
             self._done, self._holder = True, None
         return self._out
 
@@ -1305,7 +1339,7 @@ class Gvom(object):
                 if pool is not None:
                     pool.closed = True
                     for p in pool.free:
-                        self._lib.gvom_output_buffer_free(h, ctypes.c_void_p(p))
+                        self._lib.gvom_output_buffer_free(h, _dev(p))
                     pool.free = []
                 self._lib.gvom_destroy(h)
             except Exception:
@@ -1334,47 +1368,36 @@ class Gvom(object):
         stride = pc.strides[0] if pc.shape[0] > 0 else 3 * pc.itemsize
         return pc, pc.shape[0], stride, (0 if pc.dtype == np.float32 else 1)
 
-    def process_pointcloud(self, pointcloud, ego_position, transform=None):
-        """Imports a pointcloud, processes it into a voxel map then adds the map to the buffer
-        (reference gvom.py:99-175).  Returns None."""
-        self.ego_position = ego_position
-        pc, n, stride, code = self._prepare_cloud(pointcloud)
-        ego = (ctypes.c_double * 3)(float(ego_position[0]), float(ego_position[1]),
-                                    float(ego_position[2]))
+    def _scan_frame(self, ego_position, transform):
+        """The frame arguments of a scan, as every scan route hands them to the library: (ego, tf) = ego_position as double[3]
+        and `transform` as a C-contiguous float64 4x4 array, or None.  Keeps ego_position (the reference's attribute).  The
+        library reads tf[0..11], so anything but a 4x4 matrix is refused here."""
         tf = None
         if transform is not None:
             tf = np.ascontiguousarray(np.asarray(transform, dtype=np.float64))
             if tf.shape != (4, 4):
                 raise ValueError("transform must be 4x4")
-        rc = self._check(self._lib.gvom_process_pointcloud(self._h, _ptr(pc) if n else None, n,
-                                                           stride, code, ego, _ptr(tf)))
-        if rc == GVOM_EMPTY_CLOUD:
-            print("[WARNING] Processing an empty pointcloud, nothing will happen!")
-        elif rc == GVOM_NO_OVERLAP:
-            print("[WARNING] The pointcloud points don't overlap with any voxels, nothing will happen!")
+        self.ego_position = ego_position
+        return (ctypes.c_double * 3)(float(ego_position[0]), float(ego_position[1]), float(ego_position[2])), tf
+
+    def process_pointcloud(self, pointcloud, ego_position, transform=None):
+        """Imports a pointcloud, processes it into a voxel map then adds the map to the buffer
+        (reference gvom.py:99-175).  Returns None."""
+        pc, n, stride, code = self._prepare_cloud(pointcloud)
+        ego, tf = self._scan_frame(ego_position, transform)
+        _warn_scan(self._check(self._lib.gvom_process_pointcloud(self._h, _ptr(pc) if n else None, n,
+                                                                 stride, code, ego, _ptr(tf))))
         return None
 
     def process_pointcloud_device(self, dev_ptr, n, dtype, ego_position, transform=None,
                                   row_stride_bytes=None):
         """Same as process_pointcloud for a cloud already resident in HBM (raw device pointer)."""
-        self.ego_position = ego_position
-        code = 0 if (dtype is np.float32 or np.dtype(dtype) == np.float32) else 1
-        stride = row_stride_bytes or (12 if code == 0 else 24)
-        ego = (ctypes.c_double * 3)(float(ego_position[0]), float(ego_position[1]),
-                                    float(ego_position[2]))
-        tf = None
-        if transform is not None:
-            tf = np.ascontiguousarray(np.asarray(transform, dtype=np.float64))
+        code, stride = _device_cloud(dtype, row_stride_bytes)
+        ego, tf = self._scan_frame(ego_position, transform)
         return self._check(self._lib.gvom_process_pointcloud_device(
-            self._h, ctypes.c_void_p(int(dev_ptr)), int(n), int(stride), code, ego, _ptr(tf)))
+            self._h, _dev(dev_ptr), int(n), int(stride), code, ego, _ptr(tf)))
 
     # ---- multi-origin scans: every return traced from its own sensor position (include/gvom_hip.h "multi-origin scans") ----
-    def _warn_scan(self, rc):
-        if rc == GVOM_EMPTY_CLOUD:
-            print("[WARNING] Processing an empty pointcloud, nothing will happen!")
-        elif rc == GVOM_NO_OVERLAP:
-            print("[WARNING] The pointcloud points don't overlap with any voxels, nothing will happen!")
-
     def process_pointcloud_origins(self, pointcloud, origins, ego_position, transform=None, origin_index=None):
         """process_pointcloud with return i traced from origins[origin_index[i]] instead of from ego_position, which keeps
         every other role (it places the window).  origins [K, 3] world-frame sensor positions (`transform` is not applied to
@@ -1389,14 +1412,8 @@ class Gvom(object):
             if n and (raw.min() < 0 or raw.max() >= o.shape[0]):
                 raise ValueError("origin_index entries must lie in [0, %d)" % o.shape[0])
             idx = np.ascontiguousarray(raw.astype(np.uint16))
-        tf = None
-        if transform is not None:
-            tf = np.ascontiguousarray(np.asarray(transform, dtype=np.float64))
-            if tf.shape != (4, 4):
-                raise ValueError("transform must be 4x4")
-        self.ego_position = ego_position
-        ego = (ctypes.c_double * 3)(float(ego_position[0]), float(ego_position[1]), float(ego_position[2]))
-        self._warn_scan(self._check_args(self._lib.gvom_process_pointcloud_origins(
+        ego, tf = self._scan_frame(ego_position, transform)
+        _warn_scan(self._check_args(self._lib.gvom_process_pointcloud_origins(
             self._h, _ptr(pc) if n else None, 0, n, stride, code, _ptr(o), o.shape[0], _ptr(idx), ego, _ptr(tf))))
         return None
 
@@ -1405,17 +1422,11 @@ class Gvom(object):
         """process_pointcloud_origins for a cloud already resident in HBM.  origins: a HOST [K, 3] array; origin_index_ptr: a raw
         device pointer to n uint16, or None (i % K).  The device index cannot be checked by the host: a return whose index is
         not below K has no effect at all."""
-        code = 0 if (dtype is np.float32 or np.dtype(dtype) == np.float32) else 1
-        stride = row_stride_bytes or (12 if code == 0 else 24)
+        code, stride = _device_cloud(dtype, row_stride_bytes)
         o = _origin_table(origins)
-        tf = None
-        if transform is not None:
-            tf = np.ascontiguousarray(np.asarray(transform, dtype=np.float64))
-        self.ego_position = ego_position
-        ego = (ctypes.c_double * 3)(float(ego_position[0]), float(ego_position[1]), float(ego_position[2]))
+        ego, tf = self._scan_frame(ego_position, transform)
         return self._check_args(self._lib.gvom_process_pointcloud_origins(
-            self._h, ctypes.c_void_p(int(dev_ptr)), 1, int(n), int(stride), code, _ptr(o), o.shape[0],
-            None if origin_index_ptr is None else ctypes.c_void_p(int(origin_index_ptr)), ego, _ptr(tf)))
+            self._h, _dev(dev_ptr), 1, int(n), int(stride), code, _ptr(o), o.shape[0], _dev(origin_index_ptr), ego, _ptr(tf)))
 
     def _check_args(self, rc):
         """_check, with GVOM_ERR_INVALID (-1) as the ValueError the binding's own argument checks raise"""
@@ -1437,18 +1448,10 @@ class Gvom(object):
         if buf.size < int(n_points) * int(point_step):
             raise ValueError("PointCloud2 data shorter than n_points * point_step")
         code = 0 if np.dtype(field_dtype) == np.float32 else 1
-        ego = (ctypes.c_double * 3)(float(ego_position[0]), float(ego_position[1]), float(ego_position[2]))
-        self.ego_position = ego_position
-        tf = None
-        if transform is not None:
-            tf = np.ascontiguousarray(np.asarray(transform, dtype=np.float64))
-        rc = self._check(self._lib.gvom_process_pointcloud2(
+        ego, tf = self._scan_frame(ego_position, transform)
+        _warn_scan(self._check(self._lib.gvom_process_pointcloud2(
             self._h, ctypes.c_void_p(buf.ctypes.data), int(n_points), int(point_step),
-            int(offsets[0]), int(offsets[1]), int(offsets[2]), code, ego, _ptr(tf)))
-        if rc == GVOM_EMPTY_CLOUD:
-            print("[WARNING] Processing an empty pointcloud, nothing will happen!")
-        elif rc == GVOM_NO_OVERLAP:
-            print("[WARNING] The pointcloud points don't overlap with any voxels, nothing will happen!")
+            int(offsets[0]), int(offsets[1]), int(offsets[2]), code, ego, _ptr(tf))))
         return None
 
     def process_pointcloud2_msg(self, msg, ego_position, transform=None):
@@ -1488,23 +1491,14 @@ class Gvom(object):
             raise ValueError("process_range_image_origins needs column_transforms (the sensor's pose per column)")
         shape = getattr(self, "_sensor_shape", None)
         poses = _column_poses(column_transforms, shape[1]) if (column_transforms is not None and shape) else None
-        self.ego_position = ego_position
-        ego = (ctypes.c_double * 3)(float(ego_position[0]), float(ego_position[1]), float(ego_position[2]))
-        tf = None
-        if transform is not None:
-            tf = np.ascontiguousarray(np.asarray(transform, dtype=np.float64))
-            if tf.shape != (4, 4):
-                raise ValueError("transform must be 4x4")
+        ego, tf = self._scan_frame(ego_position, transform)
         if trace_from_columns:
             rc = self._check_args(self._lib.gvom_process_range_image_origins(self._h, raw_ptr, int(on_device), rcode, int(stride),
                                                                              _ptr(poses), _cloud_code(cloud_dtype), ego, _ptr(tf)))
         else:
             rc = self._check(self._lib.gvom_process_range_image(self._h, raw_ptr, int(on_device), rcode, int(stride), _ptr(poses),
                                                                 _cloud_code(cloud_dtype), ego, _ptr(tf)))
-        if rc == GVOM_EMPTY_CLOUD:
-            print("[WARNING] Processing an empty pointcloud, nothing will happen!")
-        elif rc == GVOM_NO_OVERLAP:
-            print("[WARNING] The pointcloud points don't overlap with any voxels, nothing will happen!")
+        _warn_scan(rc)
         return None
 
     def process_range_image(self, ranges, ego_position, transform=None, column_transforms=None, cloud_dtype=np.float32):
@@ -1540,20 +1534,22 @@ class Gvom(object):
                                    cloud_dtype=np.float32, row_stride_bytes=None):
         """process_range_image for an image already resident in HBM (raw device pointer, the model's H x W pixels of
         `range_dtype`, rows row_stride_bytes apart; default: packed).  The data must be ready when the call is made."""
-        rcode = _range_code(range_dtype)
-        shape = getattr(self, "_sensor_shape", None)
-        stride = row_stride_bytes or ((shape[1] if shape else 0) * np.dtype(range_dtype).itemsize)
-        return self._range_image_call(ctypes.c_void_p(int(dev_ptr)), 1, rcode, stride, ego_position, transform, column_transforms,
-                                      cloud_dtype)
+        return self._range_image_device(dev_ptr, range_dtype, ego_position, transform, column_transforms, cloud_dtype, row_stride_bytes,
+                                        False)
 
     def process_range_image_origins_device(self, dev_ptr, range_dtype, ego_position, transform=None, column_transforms=None,
                                            cloud_dtype=np.float32, row_stride_bytes=None):
         """process_range_image_origins for an image already resident in HBM (see process_range_image_device)."""
+        return self._range_image_device(dev_ptr, range_dtype, ego_position, transform, column_transforms, cloud_dtype, row_stride_bytes,
+                                        True)
+
+    def _range_image_device(self, dev_ptr, range_dtype, ego_position, transform, column_transforms, cloud_dtype, row_stride_bytes,
+                            trace_from_columns):
         rcode = _range_code(range_dtype)
         shape = getattr(self, "_sensor_shape", None)
         stride = row_stride_bytes or ((shape[1] if shape else 0) * np.dtype(range_dtype).itemsize)
-        return self._range_image_call(ctypes.c_void_p(int(dev_ptr)), 1, rcode, stride, ego_position, transform, column_transforms,
-                                      cloud_dtype, True)
+        return self._range_image_call(_dev(dev_ptr), 1, rcode, stride, ego_position, transform, column_transforms, cloud_dtype,
+                                      trace_from_columns)
 
     def combine_maps(self):
         """Combines all maps in the buffer and processes the resultant map into 2D maps
@@ -1570,7 +1566,7 @@ class Gvom(object):
         else:
             rc, out = self._combine_into(self._lib.gvom_combine_maps_into)
         if rc == GVOM_EMPTY_BUFFER:
-            print("[WARNING] The map buffer is empty, nothing will happen!")
+            _warn_empty_ring()
             return None
         return out
 
@@ -1582,46 +1578,40 @@ class Gvom(object):
         sid = ctypes.c_int64(-1)
         rc = self._check(self._lib.gvom_combine_maps_device(self._h, _ptr(origin), ctypes.byref(sid)))
         if rc == GVOM_EMPTY_BUFFER:
-            print("[WARNING] The map buffer is empty, nothing will happen!")
+            _warn_empty_ring()
             return None
         return DeviceMaps(self, int(sid.value), origin)
+
+    def _output_buffer(self):
+        """A pinned output buffer for one combine -- one the pool has free, else a new one -- in the holder that gives it back to the
+        pool once the last view of it is dropped; `.ptr` is its host address."""
+        if self._out_pool.free:
+            ptr = self._out_pool.free.pop()
+        else:
+            p = ctypes.c_void_p()
+            self._check(self._lib.gvom_output_buffer_alloc(self._h, ctypes.byref(p)))
+            ptr = p.value
+        return _PinnedOutput(self._out_pool, ptr, self.xy_size * self.xy_size * 20)
+
+    def _combine_begin(self, occupancy):
+        """the two *_async methods: `occupancy` is None for the four maps, the double[3] of thresholds for the five grids"""
+        holder = self._output_buffer()
+        rc = self._check(self._lib.gvom_combine_begin(self._h, _dev(holder.ptr), occupancy))
+        if rc == GVOM_EMPTY_BUFFER:
+            _warn_empty_ring()
+            return _PendingMaps(self, None)
+        return _PendingMaps(self, holder, occupancy=occupancy is not None)
 
     def combine_maps_async(self):
         """combine_maps() split in two (an extension; the reference's call is synchronous): enqueues the
         combine and returns a handle at once; `.result()` waits and returns what combine_maps() returns.
         Hand the next scan to process_pointcloud*() in between: its ray tracing runs on the GPU while the
         maps of this combine are written to host memory.  One combine may be pending at a time."""
-        xy = self.xy_size
-        n2 = xy * xy
-        if self._out_pool.free:
-            ptr = self._out_pool.free.pop()
-        else:
-            p = ctypes.c_void_p()
-            self._check(self._lib.gvom_output_buffer_alloc(self._h, ctypes.byref(p)))
-            ptr = p.value
-        holder = _PinnedOutput(self._out_pool, ptr, n2 * 20)
-        rc = self._check(self._lib.gvom_combine_begin(self._h, ctypes.c_void_p(ptr), None))
-        if rc == GVOM_EMPTY_BUFFER:
-            print("[WARNING] The map buffer is empty, nothing will happen!")
-            return _PendingMaps(self, None)
-        return _PendingMaps(self, holder)
+        return self._combine_begin(None)
 
     def combine_maps_occupancy_async(self, density_threshold=50, min_roughness=-10, max_roughness=0):
         """combine_maps_occupancy() split like combine_maps_async(): `.result()` returns its tuple."""
-        n2 = self.xy_size * self.xy_size
-        if self._out_pool.free:
-            ptr = self._out_pool.free.pop()
-        else:
-            p = ctypes.c_void_p()
-            self._check(self._lib.gvom_output_buffer_alloc(self._h, ctypes.byref(p)))
-            ptr = p.value
-        holder = _PinnedOutput(self._out_pool, ptr, n2 * 20)
-        occ = (ctypes.c_double * 3)(float(density_threshold), float(min_roughness), float(max_roughness))
-        rc = self._check(self._lib.gvom_combine_begin(self._h, ctypes.c_void_p(ptr), occ))
-        if rc == GVOM_EMPTY_BUFFER:
-            print("[WARNING] The map buffer is empty, nothing will happen!")
-            return _PendingMaps(self, None)
-        return _PendingMaps(self, holder, occupancy=True)
+        return self._combine_begin((ctypes.c_double * 3)(float(density_threshold), float(min_roughness), float(max_roughness)))
 
     def combine_maps_occupancy(self, density_threshold=50, min_roughness=-10, max_roughness=0):
         """combine_maps() fused with the post-processing the ROS node applies to its result
@@ -1631,53 +1621,27 @@ class Gvom(object):
         where each grid is the int8[xy*xy] array the node assigns to nav_msgs/OccupancyGrid.data
         (x fastest, i.e. np.reshape(m, -1, order='F')).  Defaults = the node's ROS parameter
         defaults (gvom_ros.py:32-35).  5 bytes per cell cross PCIe instead of 20."""
-        xy = self.xy_size
-        n2 = xy * xy
         origin = np.zeros(3, np.float64)
-        if self._out_pool.free:
-            ptr = self._out_pool.free.pop()
-        else:
-            p = ctypes.c_void_p()
-            self._check(self._lib.gvom_output_buffer_alloc(self._h, ctypes.byref(p)))
-            ptr = p.value
-        holder = _PinnedOutput(self._out_pool, ptr, n2 * 20)
+        holder = self._output_buffer()
         rc = self._check(self._lib.gvom_combine_occupancy_into(
-            self._h, _ptr(origin), ctypes.c_void_p(ptr), float(density_threshold),
+            self._h, _ptr(origin), _dev(holder.ptr), float(density_threshold),
             float(min_roughness), float(max_roughness)))
         if rc == GVOM_EMPTY_BUFFER:
-            print("[WARNING] The map buffer is empty, nothing will happen!")
+            _warn_empty_ring()
             return None
-        raw = np.asarray(holder)
-        grids = tuple(raw[k * n2:(k + 1) * n2].view(np.int8) for k in range(5))
-        return (origin,) + grids
+        return (origin,) + _occupancy_grids(np.asarray(holder), self.xy_size)
 
     def _combine_into(self, entry_point):
         """Runs `entry_point(handle, origin, pinned_buffer)` and wraps the pinned buffer as the
         reference's return tuple.  The GPU writes the four maps straight into a pinned,
         device-mapped host buffer; the returned arrays are views of it (fresh per call: a buffer
         is reused only after every array of an earlier call has been garbage-collected)."""
-        xy = self.xy_size
-        n2 = xy * xy
         origin = np.zeros(3, np.float64)
-        if self._out_pool.free:
-            ptr = self._out_pool.free.pop()
-        else:
-            p = ctypes.c_void_p()
-            self._check(self._lib.gvom_output_buffer_alloc(self._h, ctypes.byref(p)))
-            ptr = p.value
-        holder = _PinnedOutput(self._out_pool, ptr, n2 * 20)
+        holder = self._output_buffer()
         # The views are built BEFORE the (blocking) call: k_encode is still running on the GPU when
         # combine_maps is entered, so this host work is hidden; after the call only the return is left.
-        raw = np.asarray(holder)
-        # the library writes the maps in [y][x] memory order: seen through .T they are the reference's
-        # [x, y]-indexed arrays in Fortran order (what gvom_ros.py's reshape(..., order='F') reads
-        # without a copy), and the GPU writes them as contiguous runs without a transpose
-        positive = np.ndarray((xy, xy), np.int32, raw, 0, (4, 4 * xy))
-        negative = np.ndarray((xy, xy), np.int32, raw, 4 * n2, (4, 4 * xy))
-        visibility = np.ndarray((xy, xy), np.int32, raw, 8 * n2, (4, 4 * xy))
-        roughness = np.ndarray((xy, xy), np.float64, raw, 12 * n2, (8, 8 * xy))
-        out = (origin, positive, negative, roughness, visibility)
-        rc = self._check(entry_point(self._h, _ptr(origin), ctypes.c_void_p(ptr)))
+        out = (origin,) + _map_views(np.asarray(holder), self.xy_size)
+        rc = self._check(entry_point(self._h, _ptr(origin), _dev(holder.ptr)))
         if rc != GVOM_OK:
             return rc, None
         return GVOM_OK, out
@@ -1712,28 +1676,45 @@ class Gvom(object):
         """make_debug_voxel_map() left in device memory: a DeviceVoxelCloud (rows, eigenvalues, row count) of at most max_rows
         rows (default: the fused cell count); None ("No data" before the first combine) under make_debug_voxel_map's conditions.
         Counts as a read of the per-voxel statistics: statistics on demand stay on while this is called."""
-        hold = self._device_product(PRODUCT_VOXEL_CLOUD, 0 if max_rows is None else max(int(max_rows), 1))
+        return self._debug_cloud_device(PRODUCT_VOXEL_CLOUD, DeviceVoxelCloud, 0 if max_rows is None else max(int(max_rows), 1), True)
+
+    def _debug_cloud_device(self, kind, view, max_rows=0, only_before_combine=False):
+        """What the three debug-cloud makers share: `view` of the product of `kind`, or None and the reference's "No data" where the
+        mapper has none (only_before_combine: said only before the first combine, as make_debug_voxel_map does)."""
+        hold = self._device_product(kind, max_rows)
         if hold is None:
-            if not self._state().has_combined:
+            if not (only_before_combine and self._state().has_combined):
                 print("No data")
             return None
-        return DeviceVoxelCloud(hold)
+        return view(hold)
 
     def height_cloud_device(self):
         """make_debug_height_map() left in device memory: a DeviceArray float32 [xy*xy, 7]; None (and "No data") without 2-D maps."""
-        hold = self._device_product(PRODUCT_HEIGHT_CLOUD)
-        if hold is None:
-            print("No data")
-            return None
-        return DeviceArray(hold)
+        return self._debug_cloud_device(PRODUCT_HEIGHT_CLOUD, DeviceArray)
 
     def inferred_height_cloud_device(self):
         """make_debug_inferred_height_map() left in device memory: a DeviceArray float32 [xy*xy, 3]; None (and "No data") without 2-D maps."""
-        hold = self._device_product(PRODUCT_INFERRED_HEIGHT_CLOUD)
-        if hold is None:
-            print("No data")
-            return None
-        return DeviceArray(hold)
+        return self._debug_cloud_device(PRODUCT_INFERRED_HEIGHT_CLOUD, DeviceArray)
+
+    def _window_map(self, name, m, dtype, bounds=None, optional=False, range_note=""):
+        """An [x, y] map of the caller's over the window, as the library reads it: a Fortran-ordered (x fastest) array of `dtype`;
+        None for an absent `optional` map.  bounds = (lo, hi): the map must hold finite whole numbers in lo .. hi; without
+        bounds the values are cast as they are.  range_note: what the range message adds about the values."""
+        if m is None:
+            if optional:
+                return None
+            raise ValueError("%s must be an array" % name)
+        a = np.asarray(m)
+        if a.shape != (self.xy_size, self.xy_size):
+            raise ValueError("%s must have shape (%d, %d), got %r" % (name, self.xy_size, self.xy_size, a.shape))
+        if bounds is not None:
+            if a.dtype.kind == "f" and not np.isfinite(a).all():
+                raise ValueError("%s must be finite" % name)
+            if a.dtype.kind not in "iuf" or (a.dtype.kind == "f" and (a != np.floor(a)).any()):
+                raise ValueError("%s must hold whole numbers" % name)
+            if a.size and (a.min() < bounds[0] or a.max() > bounds[1]):
+                raise ValueError("%s must lie in %d .. %d%s" % (name, bounds[0], bounds[1], range_note))
+        return np.asfortranarray(a, dtype=dtype)                        # x fastest
 
     # ---- obstacle clearance (an extension; include/gvom_hip.h "obstacle clearance") ----
     def _clearance(self, set_id, pos_ptr, neg_ptr, on_device, density_threshold, include_negative, max_distance):
@@ -1746,26 +1727,16 @@ class Gvom(object):
     def clearance_of(self, positive, negative=None, density_threshold=50, include_negative=True, max_distance=None):
         """DeviceMaps.clearance() of maps of the caller's: numpy [x, y] arrays of shape (xy_size, xy_size) in any memory order
         (negative may be None).  Needs no scan and no combine.  A convenience route: the maps are copied to the device."""
-        maps = []
-        for name, m in (("positive", positive), ("negative", negative)):
-            if m is None:
-                if name == "positive":
-                    raise ValueError("positive must be an array")
-                maps.append(None)
-                continue
-            a = np.asarray(m)
-            if a.shape != (self.xy_size, self.xy_size):
-                raise ValueError("%s must have shape (%d, %d), got %r" % (name, self.xy_size, self.xy_size, a.shape))
-            maps.append(np.asfortranarray(a, dtype=np.int32))           # x fastest
-        return self._clearance(-1, _ptr(maps[0]), _ptr(maps[1]), 0, density_threshold, include_negative, max_distance)
+        pos = self._window_map("positive", positive, np.int32)
+        neg = self._window_map("negative", negative, np.int32, optional=True)
+        return self._clearance(-1, _ptr(pos), _ptr(neg), 0, density_threshold, include_negative, max_distance)
 
     def clearance_of_device(self, positive_ptr, negative_ptr=None, density_threshold=50, include_negative=True, max_distance=None):
         """The same for maps in device memory (raw device addresses of xy_size*xy_size int32, cell (x, y) at [y*xy_size + x]; the
         data must be ready when the call is made).  negative_ptr may be None."""
         if not positive_ptr:
             raise ValueError("positive_ptr must be a device address")
-        return self._clearance(-1, ctypes.c_void_p(int(positive_ptr)), ctypes.c_void_p(int(negative_ptr)) if negative_ptr else None, 1,
-                               density_threshold, include_negative, max_distance)
+        return self._clearance(-1, _dev(positive_ptr), _dev(negative_ptr), 1, density_threshold, include_negative, max_distance)
 
     # ---- ray queries (an extension; include/gvom_hip.h "ray queries") ----
     def _raycast(self, from_ptr, K, to_ptr, n, on_device, unknown_blocks, check_target):
@@ -1802,7 +1773,7 @@ class Gvom(object):
         the data must be ready when the call is made).  Enqueues and returns: no host wait."""
         if not from_ptr or not to_ptr:
             raise ValueError("from_ptr and to_ptr must be device addresses")
-        return self._raycast(ctypes.c_void_p(int(from_ptr)), K, ctypes.c_void_p(int(to_ptr)), n, 1, unknown_blocks, check_target)
+        return self._raycast(_dev(from_ptr), K, _dev(to_ptr), n, 1, unknown_blocks, check_target)
 
     # ---- cost-to-go fields (an extension; include/gvom_hip.h "cost-to-go fields") ----
     def _cost_to_go(self, set_id, params, cost_ptr, on_device, cells, max_cost, max_rounds, flags, origin=(0.0, 0.0)):
@@ -1816,17 +1787,9 @@ class Gvom(object):
         """DeviceMaps.cost_to_go() of a cost map of the caller's: a numpy [x, y] array of shape (xy_size, xy_size) in any memory
         order, integers in 0 .. 65535 (0 = blocked); goals: (G, 2) window cells.  Needs no scan and no combine.  A convenience
         route: the map is copied to the device.  origin: the window corner in world metres, kept as the field's `.origin`."""
-        a = np.asarray(cost)
-        if a.shape != (self.xy_size, self.xy_size):
-            raise ValueError("cost must have shape (%d, %d), got %r" % (self.xy_size, self.xy_size, a.shape))
-        if a.dtype.kind == "f" and not np.isfinite(a).all():
-            raise ValueError("cost must be finite")
-        if a.dtype.kind not in "iuf" or (a.dtype.kind == "f" and (a != np.floor(a)).any()):
-            raise ValueError("cost must hold whole numbers")
-        if a.size and (a.min() < 0 or a.max() > 65535):
-            raise ValueError("cost must lie in 0 .. 65535 (0 = blocked)")
+        # (np.asarray: a cost of None is held to the shape like any other value)
+        c = self._window_map("cost", np.asarray(cost), np.int32, (0, 65535), range_note=" (0 = blocked)")
         cells = _ctg_goals(goals, self.xy_size, None)
-        c = np.asfortranarray(a, dtype=np.int32)                        # x fastest
         return self._cost_to_go(-1, None, _ptr(c), 0, cells, _ctg_max_cost(max_cost), _ctg_max_rounds(max_rounds), 0, origin=origin)
 
     def cost_to_go_of_device(self, cost_ptr, goals, max_cost=None, max_rounds=0, origin=(0.0, 0.0)):
@@ -1835,8 +1798,7 @@ class Gvom(object):
         if not cost_ptr:
             raise ValueError("cost_ptr must be a device address")
         cells = _ctg_goals(goals, self.xy_size, None)
-        return self._cost_to_go(-1, None, ctypes.c_void_p(int(cost_ptr)), 1, cells, _ctg_max_cost(max_cost),
-                                _ctg_max_rounds(max_rounds), 0, origin=origin)
+        return self._cost_to_go(-1, None, _dev(cost_ptr), 1, cells, _ctg_max_cost(max_cost), _ctg_max_rounds(max_rounds), 0, origin=origin)
 
     # ---- rollout scoring (an extension; include/gvom_hip.h "rollout scoring") ----
     def set_footprint(self, table):
@@ -1857,25 +1819,10 @@ class Gvom(object):
         in any memory order, whole numbers in 0 .. 65535 (0 = blocked); cost_to_go (optional) int32 of the same shape, the field
         the terminal column is read from; origin: the window corner in world metres.  Needs no scan and no combine.  A convenience
         route: maps and poses are copied to the device."""
-        maps = []
-        for name, m, dt, lo, hi in (("cell_cost", cell_cost, np.uint16, 0, 65535), ("cost_to_go", cost_to_go, np.int32, -2 ** 31, 2 ** 31 - 1)):
-            if m is None:
-                if name == "cell_cost":
-                    raise ValueError("cell_cost must be an array")
-                maps.append(None)
-                continue
-            a = np.asarray(m)
-            if a.shape != (self.xy_size, self.xy_size):
-                raise ValueError("%s must have shape (%d, %d), got %r" % (name, self.xy_size, self.xy_size, a.shape))
-            if a.dtype.kind == "f" and not np.isfinite(a).all():
-                raise ValueError("%s must be finite" % name)
-            if a.dtype.kind not in "iuf" or (a.dtype.kind == "f" and (a != np.floor(a)).any()):
-                raise ValueError("%s must hold whole numbers" % name)
-            if a.size and (a.min() < lo or a.max() > hi):
-                raise ValueError("%s must lie in %d .. %d" % (name, lo, hi))
-            maps.append(np.asfortranarray(a, dtype=dt))                 # x fastest
+        cc = self._window_map("cell_cost", cell_cost, np.uint16, (0, 65535))
+        ctg = self._window_map("cost_to_go", cost_to_go, np.int32, (-2 ** 31, 2 ** 31 - 1), optional=True)
         p = _rollout_poses(poses)
-        return self._score_rollouts(-1, _ptr(maps[0]), _ptr(maps[1]), _ptr(p), p.shape[0], p.shape[1], 0, origin)
+        return self._score_rollouts(-1, _ptr(cc), _ptr(ctg), _ptr(p), p.shape[0], p.shape[1], 0, origin)
 
     def score_rollouts_of_device(self, cell_cost_ptr, poses_ptr, K, T, cost_to_go_ptr=None, origin=(0.0, 0.0)):
         """The same for maps and poses in device memory: raw device addresses of xy_size*xy_size uint16 (cell (x, y) at
@@ -1884,8 +1831,7 @@ class Gvom(object):
         if not cell_cost_ptr or not poses_ptr:
             raise ValueError("cell_cost_ptr and poses_ptr must be device addresses")
         K, T = _rollout_shape(K, T)
-        return self._score_rollouts(-1, ctypes.c_void_p(int(cell_cost_ptr)), ctypes.c_void_p(int(cost_to_go_ptr)) if cost_to_go_ptr else None,
-                                    ctypes.c_void_p(int(poses_ptr)), K, T, 1, origin)
+        return self._score_rollouts(-1, _dev(cell_cost_ptr), _dev(cost_to_go_ptr), _dev(poses_ptr), K, T, 1, origin)
 
     # ---- scan alignment scoring (an extension; include/gvom_hip.h "scan alignment scoring") ----
     def _score_alignments(self, cloud_ptr, n, tf_ptr, K, on_device, dilate, weights):
@@ -1919,7 +1865,7 @@ class Gvom(object):
         candidate, C-contiguous; the data must be ready when the call is made).  Enqueues and returns: no host wait."""
         if not cloud_ptr or not transforms_ptr:
             raise ValueError("cloud_ptr and transforms_ptr must be device addresses")
-        return self._score_alignments(ctypes.c_void_p(int(cloud_ptr)), n, ctypes.c_void_p(int(transforms_ptr)), K, 1, dilate, weights)
+        return self._score_alignments(_dev(cloud_ptr), n, _dev(transforms_ptr), K, 1, dilate, weights)
 
     def make_debug_voxel_map(self):
         """float32[Cc, 8] rows {x, y, z, hit/total, hit, l0-l1, l1-l2, l2} (reference gvom.py:363-378) while the mapper
@@ -2156,7 +2102,7 @@ class Gvom(object):
             ptr = getattr(base, "ptr", None)
             if ptr is None:
                 ptr = np.asarray(a).__array_interface__["data"][0]
-            self._check(self._lib.gvom_output_forget(self._h, ctypes.c_void_p(int(ptr))))
+            self._check(self._lib.gvom_output_forget(self._h, _dev(ptr)))
 
     def output_record(self, array):
         """(bits uint8[n], generation) of the content record of the buffer behind a returned map (include/gvom_hip.h,
@@ -2164,7 +2110,7 @@ class Gvom(object):
         base = array
         while getattr(base, "base", None) is not None:
             base = base.base
-        ptr = ctypes.c_void_p(int(base.ptr))
+        ptr = _dev(base.ptr)
         n, gen = ctypes.c_size_t(0), ctypes.c_uint64(0)
         if self._check(self._lib.gvom_output_record(self._h, ptr, None, 0, ctypes.byref(n), ctypes.byref(gen))) == GVOM_NO_DATA:
             return None

@@ -38,8 +38,6 @@ transport runs several ranks as threads of ONE process on ONE GPU over RCCL); te
 import ctypes
 import os
 
-import numpy as np
-
 import gvom as _gvom
 
 XBUF_SEND_IDS, XBUF_SEND_QUADS, XBUF_SEND_EPS, XBUF_RECV_IDS, XBUF_RECV_QUADS, XBUF_RECV_EPS, XBUF_SEND_RETURNS, XBUF_RECV_RETURNS = range(8)
@@ -53,6 +51,18 @@ def _nothing():
 def _vec(values):
     a = (ctypes.c_int64 * len(values))(*[int(v) for v in values])
     return a
+
+
+def _share(g, pointcloud):
+    """A rank's share of a scan as the library takes it: (array, source pointer, on_device, n, row stride in bytes, dtype code)
+    of a numpy (n, >=3) cloud or of a (device pointer, n, numpy dtype) tuple.  `array` is what a host pointer points into
+    (it may be a converted copy): the caller holds it until the library call has returned."""
+    if isinstance(pointcloud, tuple):
+        dptr, n, dt = pointcloud
+        code, stride = _gvom._device_cloud(dt)
+        return None, _gvom._dev(dptr), 1, n, stride, code
+    pc, n, stride, code = g._prepare_cloud(pointcloud)
+    return pc, (_gvom._ptr(pc) if n else None), 0, n, stride, code
 
 
 class HipShardBackend(object):
@@ -70,25 +80,12 @@ class HipShardBackend(object):
         """This rank's share of the scan -> (send_quads[world], send_eps[world], any_in_grid, n).
         pointcloud: numpy (n, >=3), or (device pointer, n, numpy dtype) for a share already in HBM."""
         g = self.g
-        g.ego_position = ego
-        on_device = isinstance(pointcloud, tuple)
-        if on_device:
-            dptr, n, dt = pointcloud
-            code = 0 if np.dtype(dt) == np.float32 else 1
-            stride = 12 if code == 0 else 24
-        else:
-            pc, n, stride, code = g._prepare_cloud(pointcloud)
-        ego_c = (ctypes.c_double * 3)(float(ego[0]), float(ego[1]), float(ego[2]))
-        t = None
-        if tf is not None:
-            t = np.ascontiguousarray(np.asarray(tf, dtype=np.float64))
-            if t.shape != (4, 4):
-                raise ValueError("transform must be 4x4")
+        pc, src, on_device, n, stride, code = _share(g, pointcloud)
+        ego_c, t = g._scan_frame(ego, tf)
         sq = (ctypes.c_int64 * self.world)()
         se = (ctypes.c_int64 * self.world)()
         any_ = ctypes.c_int(0)
-        src = ctypes.c_void_p(int(dptr)) if on_device else (_gvom._ptr(pc) if n else None)
-        g._check(self.lib.gvom_shard_scan_local(self.h, src, 1 if on_device else 0, int(n), stride, code, ego_c,
+        g._check(self.lib.gvom_shard_scan_local(self.h, src, on_device, int(n), stride, code, ego_c,
                                                 _gvom._ptr(t), sq, se, ctypes.byref(any_)))
         self.dtype_code = code
         return list(sq), list(se), int(any_.value), n
@@ -209,23 +206,10 @@ class RcclComm(object):
     # orchestration from Python cost ~25 us per step, profiles/r4_bench_sharded_w1_m256.json against r5's)
     def scan_native(self, backend, pointcloud, ego, tf):
         g = backend.g
-        on_device = isinstance(pointcloud, tuple)
-        if on_device:
-            dptr, n, dt = pointcloud
-            code = 0 if np.dtype(dt) == np.float32 else 1
-            stride, src = (12 if code == 0 else 24), ctypes.c_void_p(int(dptr))
-        else:
-            pc, n, stride, code = g._prepare_cloud(pointcloud)
-            src = _gvom._ptr(pc) if n else None
-        t = None
-        if tf is not None:
-            t = np.ascontiguousarray(np.asarray(tf, dtype=np.float64))
-            if t.shape != (4, 4):
-                raise ValueError("transform must be 4x4")
-        ego_c = (ctypes.c_double * 3)(float(ego[0]), float(ego[1]), float(ego[2]))
+        pc, src, on_device, n, stride, code = _share(g, pointcloud)
+        ego_c, t = g._scan_frame(ego, tf)
         out = (ctypes.c_int64 * 4)()
-        g.ego_position = ego
-        self._check(self.lib.gvom_comm_process_pointcloud(self.c, backend.h, src, 1 if on_device else 0, int(n), stride, code, ego_c,
+        self._check(self.lib.gvom_comm_process_pointcloud(self.c, backend.h, src, on_device, int(n), stride, code, ego_c,
                                                           _gvom._ptr(t), out))
         backend.dtype_code = code
         return bool(out[0]), int(out[1]), (int(out[2]), int(out[3]))
@@ -320,11 +304,7 @@ class ShardedGvom(object):
         W, me = self.world, self.rank
         if hasattr(self.comm, "scan_native") and not getattr(self.b, "has_stats", False) and isinstance(self.b, HipShardBackend):
             accept, total_n, self.last_exchange_bytes = self.comm.scan_native(self.b, pointcloud, ego_position, transform)
-            if me == 0:
-                if total_n == 0:
-                    print("[WARNING] Processing an empty pointcloud, nothing will happen!")
-                elif not accept:
-                    print("[WARNING] The pointcloud points don't overlap with any voxels, nothing will happen!")
+            self._warn_scan(total_n, accept)
             return None
         getattr(self.comm, "before_scan", _nothing)()                # (a transport whose peers may still be reading this rank's send regions)
         send_q, send_e, any_, n = self.b.scan_local(pointcloud, ego_position, transform)
@@ -352,12 +332,13 @@ class ShardedGvom(object):
             self.b.stats_reserve(recv_r, code)
             self.comm.exchange_stats(self.b, [send_r[d] if d != me else 0 for d in range(W)], recv_r, 12 if code == 0 else 24)
         self.b.scan_merge(recv_q, recv_e, accept)
-        if me == 0:
-            if total_n == 0:
-                print("[WARNING] Processing an empty pointcloud, nothing will happen!")
-            elif not accept:
-                print("[WARNING] The pointcloud points don't overlap with any voxels, nothing will happen!")
+        self._warn_scan(total_n, accept)
         return None
+
+    def _warn_scan(self, total_n, accept):
+        """gvom.Gvom's warnings about a scan that changes nothing, once per job (rank 0), from what the ranks saw together"""
+        if self.rank == 0:
+            _gvom._warn_scan(_gvom.GVOM_EMPTY_CLOUD if total_n == 0 else _gvom.GVOM_OK if accept else _gvom.GVOM_NO_OVERLAP)
 
     def make_debug_voxel_map(self):
         """this rank's rows of the debug voxel cloud (gvom.py:363-378); None without voxel_statistics"""
@@ -368,7 +349,7 @@ class ShardedGvom(object):
             rc, out = self.comm.combine_native(self.b)
             if rc == _gvom.GVOM_EMPTY_BUFFER:
                 if self.rank == 0:
-                    print("[WARNING] The map buffer is empty, nothing will happen!")
+                    _gvom._warn_empty_ring()
                 return None
             self._cells_dirty = True
             return out
@@ -376,7 +357,7 @@ class ShardedGvom(object):
         rc = self.b.combine_fuse()
         if rc == _gvom.GVOM_EMPTY_BUFFER:
             if self.rank == 0:
-                print("[WARNING] The map buffer is empty, nothing will happen!")
+                _gvom._warn_empty_ring()
             return None
         self._cells_dirty = True
         self.comm.allgather_rows(self.b)                              # the combine's only exchange

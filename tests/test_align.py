@@ -5,7 +5,20 @@ segments per row, a window origin beyond 2^24 voxels) with ring lengths 1 and 2,
 and four specials, dilate 0 and 1; n of 1, 63, 65, 8,192 and one more than the score kernel's returns per workgroup, K of 1, 3 and one
 more than its candidate group, through host and device pointers, with weights of both signs up to +-1024; the census floors and the
 unique best on the GPU's own maps; snapshots, the map left as it was, the product pool, errors, and a torch consumer in a child
-process.  tests/test_align_cpu.py holds the referee's pins and the figures."""
+process.  tests/test_align_cpu.py holds the referee's pins and the figures.
+
+That cloud meets the class grid of k_align_field only where the last scan's returns fall.  Two further tests do not depend on where
+returns happen to fall.  PLANTED MAPS UNDER LINE PROBES: sparse maps with single occupied voxels on both sides of every 16-voxel word
+of a row, on the bottom, middle and top level and on both sides of the boundary between two chunks of levels, on the first and last
+row and in the corners -- on six grids, two of them with rows that are no multiple of 16 voxels (72: two tile segments, the second
+partial, a half-filled last word; 37: odd) -- and three probes whose counts are the class histogram of every line of the window
+along each axis: every voxel of the class grid is held to the referee three times.  tests/test_align_cpu.py shows without a GPU that
+these inputs tell eleven plausible defects of the kernel from the referee.  THE SCORE KERNEL AT ITS EDGES: returns on exact voxel
+faces and their float32 neighbours, rotations about all three axes, resolutions that are no multiple of anything, through
+k_align_score<true> (the verified reciprocals) and k_align_score<false> (the IEEE divide, "fastdiv" knob 0).
+
+Wall time on the MI355X (pytest --durations, one run): the twelve planted cases 0.02 to 0.06 s each but for w128 (0.25 to 0.31 s) and
+w192 (0.46 s; its largest probe is 36,864 candidates x 24 returns); the fourteen edge cases 0.01 to 0.07 s each."""
 import ctypes
 import os
 import re
@@ -121,6 +134,94 @@ def test_counts_scores_and_best_match_the_referee_exactly(gvom, maps, grid, bs):
                 assert len(np.unique(counts[:ar.N_GRID], axis=0)) >= ar.DISTINCT_ROWS
     finally:
         dev.free()
+
+
+@pytest.fixture(scope="module")
+def planted(gvom):
+    """per (grid, buffer_size), built on demand and kept: (mapper, dense fused state, window origin) of a planted map"""
+    made = {}
+
+    def get(grid, bs):
+        if (grid, bs) not in made:
+            g = ar.planted_map(gvom.Gvom, grid, bs, voxel_statistics=False)
+            state, _, _, _, origin, _ = g.read_dense(gvom.GVOM_WHICH_FUSED)
+            made[grid, bs] = (g, state, np.asarray(origin, np.float64))
+        return made[grid, bs]
+    yield get
+    made.clear()
+
+
+@pytest.mark.parametrize("bs", [1, 2])
+@pytest.mark.parametrize("grid", ar.PROBE_GRIDS)
+def test_every_voxel_of_the_class_grid_is_held_to_the_referee(gvom, planted, grid, bs):
+    """k_align_field, voxel by voxel: a planted map (tests/align_ref.py: single occupied voxels on both sides of every 16-voxel word
+    of a row, on the bottom, the top and the middle level and on both sides of the boundary between the chunks of levels, on the
+    first and the last row, in the corners; 64 returns per scan besides, so that single voxels decide their neighbours' class)
+    under the three line probes, whose counts are the class histogram of every line of the window along every axis -- dilate 0
+    and 1, one axis also through device inputs.  The dense state the referee reads comes from the same handle; it is held, class
+    by class, to the CPU referee's planted map first.  Then the census, on the GPU's own map."""
+    from oracle import oracle
+    _, _, xy, zs = ar.GRIDS[grid]
+    g, state, W = planted(grid, bs)
+    o = ar.planted_map(oracle.OracleGvom, grid, bs)
+    assert np.array_equal(W, rr.window_origin(grid, rr.ego_of(grid, ar.SCAN))) and np.array_equal(np.asarray(o.combined_origin, np.float64), W)
+    assert all(int(W[k]) % (xy if k < 2 else zs) != 0 for k in range(3)), W          # non-zero storage offsets on every axis
+    got, want = rr.state_class(state), rr.state_class(np.asarray(o.combined_index_map))
+    assert np.array_equal(got, want), "%s, buffer %d: %d voxels differ from the oracle in their class, first %d: %d, oracle %d" % (
+        grid, bs, int((got != want).sum()), np.flatnonzero(got != want)[0], got[got != want][0], want[got != want][0])
+    census = ar.planted_census_holds(state, grid)
+    probes = ar.line_probes(grid, W)
+    dev = _Device()
+    try:
+        for dilate in (0, 1):
+            cls = ar.classes(state, grid, dilate)
+            for axis, (cloud, M) in enumerate(probes):
+                what = "%s bs %d dilate %d, lines along axis %d" % (grid, bs, dilate, axis)
+                want = ar.score(state, W, grid, cloud, M, dilate, cls=cls)
+                counts, _ = _hold(g.score_alignments(cloud, M, dilate=dilate), want, what)
+                # every window voxel once: over the candidates the counts are the histogram of the whole class grid
+                assert counts[:, 1:].astype(np.int64).sum(axis=0).tolist() == np.bincount(cls.ravel(), minlength=5).tolist(), what
+                if axis == 2:
+                    d = g.score_alignments_device(dev.upload(cloud), len(cloud), dev.upload(M[:, :3, :]), len(M), dilate=dilate)
+                    _hold(d, want, what + ", device")
+    finally:
+        dev.free()
+    print(grid, bs, "planted, occupied, least carry:", census, "candidates", [len(M) for _, M in probes])
+
+
+@pytest.mark.parametrize("bs", [1, 2])
+@pytest.mark.parametrize("grid", ar.EDGE_GRIDS)
+def test_the_score_kernel_at_its_edges_with_the_reciprocal_and_with_the_divide(gvom, maps, grid, bs):
+    """k_align_score where a voxel index is decided by the last bit: returns on exact voxel faces of the window and their float32
+    neighbours on both sides (ar.boundary_points), then returns of the shared cloud, 2,048 in all; under the identity, one voxel
+    up and down every axis, rotations about the window centre around each of the three axes (small, large, a quarter and a half
+    turn) and ar.rotations(); on resolutions that are no multiple of anything too (ar.OFF_GRID).  Once with the "fastdiv" knob as
+    created -- k_align_score<true>, the verified reciprocals -- and once with the knob at 0 -- k_align_score<false>, the IEEE
+    divide: both are held exactly to the referee, which divides.  (The mixed setting, one resolution verified and one not, cannot
+    be reached through the public knob: every resolution the host's check has been given passes it.)"""
+    g, state, W = maps(grid, bs)
+    (cloud, m), M = ar.edge_cloud(grid, W), ar.edge_candidates(grid, W)
+    runs = {}
+    try:
+        for knob, reads in ((None, 3), (0, 0)):
+            if knob is not None:
+                g.set_tuning("fastdiv", knob)
+            assert g.get_tuning("fastdiv") == reads
+            seen = np.zeros(5, np.int64)
+            for dilate in (0, 1):
+                what = "%s bs %d dilate %d fastdiv %d" % (grid, bs, dilate, reads)
+                counts, best = _hold(g.score_alignments(cloud, M, dilate=dilate), ar.score(state, W, grid, cloud, M, dilate), what)
+                t, up, inside, outside = ar.edge_census_holds(grid, W, dilate, cloud, m, M, counts)
+                seen += t
+                runs[reads, dilate] = counts
+                if knob is None:
+                    print(what, "totals", t, "upper 30 %", up, "boundary points inside", inside, "outside", outside, "best", best.tolist())
+            assert (seen > 0).all(), (grid, bs, seen)                      # every class, OUTSIDE included, occurs
+    finally:
+        g.set_tuning("fastdiv", -1)                                        # as created: the maps are shared
+    assert g.get_tuning("fastdiv") == 3
+    for dilate in (0, 1):
+        assert np.array_equal(runs[3, dilate], runs[0, dilate])
 
 
 @pytest.mark.parametrize("grid", ["p2", "np2", "tall", "w192"])

@@ -1,7 +1,8 @@
 """Scan alignment scoring (gvom_score_alignments), the part that needs no GPU: header, library and binding agree; the referee of
 tests/align_ref.py pinned to the CPU referee's transform and scan kernels; the census of the GPU test's inputs on maps the CPU referee
-built; the unperturbed candidate as the unique best; pose_candidates; the binding's argument checks; the product's layout under
-sanitizers; the kernels' registers.
+built; the unperturbed candidate as the unique best; what those inputs leave open, and numpy models of eleven defects of the class grid
+that the planted maps and line probes of tests/test_align.py tell from the referee; the census of its edge inputs; pose_candidates;
+the binding's argument checks; the product's layout under sanitizers; the kernels' registers.
 
 Census on the CPU referee's maps (cloud of the last scan, 245 candidates: 7 x 7 offsets of one cell, 5 yaws of 0.02 rad about the ego),
 class counts {occupied, near, free, unknown, outside} summed over the candidates, buffer_size 1 / 2, dilate 0 and dilate 1:
@@ -12,8 +13,38 @@ class counts {occupied, near, free, unknown, outside} summed over the candidates
     w192    60861 / 0 / 791137 / 497540 / 657502     60999 / ...     dilate 1: near  582867 / free 398011 / unknown 307799
 Best against second-best score under the default weights (2, 1, -1, 0, 0): p2 10846 / 3899, np2 11045 / 6555, tall 513 / 450, w128
 10862 / -474, w192 10976 / -1867; distinct count rows 242 to 245 of 245.  The far grid (window origin beyond 2^24 voxels) is in the
-referee match of tests/test_align.py but not in the census: see tests/align_ref.py CENSUS_GRIDS."""
+referee match of tests/test_align.py but not in the census: see tests/align_ref.py CENSUS_GRIDS.
+
+What those inputs leave open (test_the_gap_the_planted_maps_close): a dilation that wraps around the bottom and top face of the window
+changes the class of 2,508 (p2), 2,107 (np2), 160 (tall), 3,523 (w128) and 4,953 (w192) voxels, either ring length, and the counts of
+0 of the 249 candidates -- the clouds stop 0.15 window heights above the ego and no candidate moves them in z.
+
+The planted maps (tests/align_ref.py planted_map) under the line probes close it.  Census on the CPU referee's planted maps, the same
+for ring lengths 1 and 2 -- planted voxels (all occupied) / occupied voxels in all / the fewest voxels on one side of a multiple of
+16 in x that are NEAR only by an occupied voxel on the other side (floor 21): np2 44 / 178 / 59, tall 20 / 155 / -, w128 76 / 215 /
+24, w192 134 / 273 / 39, r72 64 / 203 / 37, r37 27 / 156 / 39.  Voxels whose class each modelled defect (classes_with_defect) changes
+there; wherever that is not 0, candidates of ALL three probes differ from the referee's counts (the test asks for one):
+             xwrap ywrap zwrap top lastrow carry_left carry_right zhalo_lo zhalo_hi sub16 lastword
+    np2        115   115   143  61      49          0           0      118       85   778        0
+    tall       118   132    63  26      79          0           0       14       59     0        0
+    w128        66    79   373  36      19         36          30      177      213  2512        0
+    w192        97   103   140  63      21         78          94      249      330  4504        0
+    r72        119   106   314  69      29         54          48      153      131  1490    11498
+    r37         91    69   222  89      56          0           0        0        0   483     2201
+
+The edge inputs of the score kernel (test_the_edge_census; 2,048 returns, 498 on tall, under 49 candidates), class counts summed over
+the candidates, dilate 0 then {near, free, unknown} of dilate 1, ring length 1 (2 is within 5 %), pairs in the upper 30 % of
+the window, boundary points inside / outside the window under the identity:
+    p2      6106 / 0 / 18941 /  9436 / 65869    23642 /  684 / 4051    2998    87 / 27
+    np2    10755 / 0 / 16410 /  5908 / 67279    19534 /   72 / 2712    3110    88 / 26
+    tall    2167 / 0 /  4073 /  2823 / 15339     6083 /  100 /  713     526    86 / 28     (ring 2: occupied 2262, free 3978, near 5994)
+    w192    2455 / 0 / 16399 / 12637 / 68861    15340 / 6086 / 7610    2914    87 / 27
+    far    19318 / 0 /     5 / 10851 / 70178     8014 /    0 / 2842    2799    46 / 71
+    third   8229 / 0 / 16695 /  4527 / 70901    18708 /  342 / 2172    2716    91 / 26
+    odd    10503 / 0 / 19372 /  5761 / 64716    22951 /   73 / 2109    2268    90 / 24
+The floors (tests/align_ref.py EDGE_FLOORS, EDGE_FLOORS_FAR, UPPER_FLOOR) lie a little under the smallest of these."""
 import ctypes
+import itertools
 import os
 import re
 import shutil
@@ -156,6 +187,116 @@ def test_census_and_the_unique_best(maps, grid, bs):
         assert (counts[:, 2] > 0).any()
     d0, _ = ar.score(state, W, grid, cloud, M[:ar.N_GRID], 0)
     assert (d0[:, 2] == 0).all() and np.array_equal(d0[:, 1], counts[:ar.N_GRID, 1]) and np.array_equal(d0[:, 5], counts[:ar.N_GRID, 5])
+
+
+DEFECTS = ("xwrap", "ywrap", "zwrap", "top", "lastrow", "carry_left", "carry_right", "zhalo_lo", "zhalo_hi", "sub16", "lastword")
+
+
+def classes_with_defect(state, grid, kind, dilate=1):
+    """ar.classes() with one of the defects the structure of k_align_field makes plausible (any other `kind`: none) --
+    xwrap, ywrap, zwrap: a neighbour beyond a face of the window is taken from the opposite face; top: the top level takes no z
+    neighbours; lastrow: row xy - 1 takes no y neighbours; carry_left, carry_right: no neighbour across a multiple of 64 in x (the
+    64-bit mask words); zhalo_lo, zhalo_hi: no neighbour across a multiple of 16 in z (the chunks of levels); sub16: the first code of
+    each 16-voxel word is the first of the word before; lastword: a partial last word of a row is left unwritten (reads OCCUPIED)"""
+    _, _, xy, zs = ar.GRIDS[grid]
+    s = np.asarray(state).reshape(zs, xy, xy)
+    occ = s >= 0
+    coord, size = np.ogrid[:zs, :xy, :xy], (zs, xy, xy)
+    z, y, x = coord
+    wraps = (kind == "zwrap", kind == "ywrap", kind == "xwrap")
+    near = np.zeros_like(occ)
+    for d in itertools.product((-1, 0, 1), repeat=3) if dilate else ():
+        dz, dy, dx = d
+        take = np.ones_like(occ)
+        for axis in range(3):
+            if d[axis] and not wraps[axis]:
+                take = take & (coord[axis] + d[axis] >= 0) & (coord[axis] + d[axis] < size[axis])
+        if kind == "top" and dz:
+            take = take & (z != zs - 1)
+        if kind == "lastrow" and dy:
+            take = take & (y != xy - 1)
+        if (kind == "carry_left" and dx == -1) or (kind == "carry_right" and dx == 1):
+            take = take & (x % 64 != (0 if dx == -1 else 63))
+        if (kind == "zhalo_lo" and dz == -1) or (kind == "zhalo_hi" and dz == 1):
+            take = take & (z % 16 != (0 if dz == -1 else 15))
+        near |= np.roll(occ, (-dz, -dy, -dx), axis=(0, 1, 2)) & take            # (rolled: the voxel at + d, wrapped)
+    cls = np.where(occ, ar.OCCUPIED, np.where(near, ar.NEAR, np.where(s <= -2, ar.FREE, ar.UNKNOWN))).astype(np.uint8)
+    if kind == "sub16":
+        first = np.arange(16, xy, 16)
+        cls[:, :, first] = cls[:, :, first - 16]
+    if kind == "lastword" and xy % 16:
+        cls[:, :, xy - xy % 16:] = ar.OCCUPIED
+    return cls
+
+
+def _oracle_map(build, grid, bs):
+    g = build(oracle.OracleGvom, grid, bs)
+    return np.asarray(g.combined_index_map).copy(), np.asarray(g.combined_origin, np.float64)
+
+
+def test_the_line_probes_on_planted_maps_catch_every_defect_of_the_class_grid():
+    """on the CPU referee's planted maps: the census of tests/align_ref.py holds; wherever a defect changes a voxel's class, the
+    counts of at least one candidate of at least one probe differ from the referee's; every defect changes a voxel somewhere"""
+    changed_somewhere = dict.fromkeys(DEFECTS, 0)
+    print("\ngrid  ring  planted / occupied / least carry | per defect: voxels changed, candidates that differ per probe axis (x y z)")
+    for grid in ar.PROBE_GRIDS:
+        first = None
+        for bs in (1, 2):
+            state, W = _oracle_map(ar.planted_map, grid, bs)
+            assert np.array_equal(W, rr.window_origin(grid, rr.ego_of(grid, ar.SCAN)))
+            census = ar.planted_census_holds(state, grid)
+            good = ar.classes(state, grid, 1)
+            assert np.array_equal(classes_with_defect(state, grid, "none"), good)
+            assert np.array_equal(classes_with_defect(state, grid, "none", 0), ar.classes(state, grid, 0))
+            if bs == 2 and np.array_equal(good, first):                    # (the same map as with ring length 1: the same table)
+                print("%-5s %d     %r | as ring length 1" % (grid, bs, census))
+                continue
+            first = good
+            at = [ar.voxels(ar.world(cloud, M), grid, W) for cloud, M in ar.line_probes(grid, W)]
+            want = [ar.class_counts(good, v, inside) for v, inside in at]
+            row = []
+            for kind in DEFECTS:
+                bad = classes_with_defect(state, grid, kind)
+                changed = int((bad != good).sum())
+                differ = [int((ar.class_counts(bad, v, inside) != w).any(axis=1).sum()) for (v, inside), w in zip(at, want)]
+                row.append("%s %d: %d %d %d" % ((kind, changed) + tuple(differ)))
+                changed_somewhere[kind] += changed
+                assert (changed > 0) == (max(differ) > 0), (grid, bs, kind, changed, differ)
+            print("%-5s %d     %r | %s" % (grid, bs, census, "; ".join(row)))
+    assert min(changed_somewhere.values()) > 0, changed_somewhere
+
+
+def test_the_gap_the_planted_maps_close(maps):
+    """the record of what the shared maps and their last scan's cloud leave open: a dilation that wraps around the bottom and the top
+    face of the window changes thousands of voxels' class on every one of them and not one count of the 249 candidates"""
+    print()
+    for grid in ar.CENSUS_GRIDS:
+        for bs in (1, 2):
+            state, W = maps[grid, bs]
+            cloud, M = ar.cloud_of(grid), ar.candidates(grid)
+            bad =classes_with_defect(state, grid, "zwrap")
+            changed = int((bad != ar.classes(state, grid, 1)).sum())
+            v, inside = ar.voxels(ar.world(cloud, M), grid, W)
+            differ = int((ar.class_counts(ar.classes(state, grid, 1), v, inside) != ar.class_counts(bad, v, inside)).any(axis=1).sum())
+            print("%-5s ring %d: zwrap changes %d voxels, %d of %d candidates" % (grid, bs, changed, differ, len(M)))
+            assert changed >= 100 and differ == 0
+
+
+def test_the_edge_census():
+    """the inputs of the score kernel's edge test (tests/test_align.py) on the CPU referee's maps: the floors of tests/align_ref.py"""
+    print()
+    for grid in ar.EDGE_GRIDS:
+        for bs in (1, 2):
+            state, W = _oracle_map(rr.build_map, grid, bs)
+            (cloud, m), M = ar.edge_cloud(grid, W), ar.edge_candidates(grid, W)
+            assert len(M) == 49 and len(cloud) == min(ar.EDGE_RETURNS, m + (384 if grid == "tall" else 8192)) and m >= 100
+            seen = np.zeros(5, np.int64)
+            for dilate in (0, 1):
+                counts, best = ar.score(state, W, grid, cloud, M, dilate)
+                t, up, inside, outside = ar.edge_census_holds(grid, W, dilate, cloud, m, M, counts)
+                print("%-5s ring %d dilate %d: totals %r, upper 30 %% %d, boundary points inside %d outside %d" % (grid, bs, dilate, t, up, inside, outside))
+                seen += t
+            assert (seen > 0).all(), (grid, bs, seen)                      # every class, OUTSIDE included, occurs
 
 
 def test_pose_candidates():

@@ -10,7 +10,8 @@ WIDE), whose dense state is held to the oracle first, and the np2 grid with its 
 
 Wall time on the MI355X (pytest --durations, one run): the six cases of test_rays_match_the_referee_exactly 0.03 to 0.05 s each
 (module fixture 0.5 s); the four wide-grid cases 0.15 to 0.19 s each (their fixture, which also builds the far maps, 0.23 s);
-the two far cases 0.04 s each, the far self-consistency check 0.02 s."""
+the two far cases 0.04 s each, the far self-consistency check 0.02 s.  One case (np2, ring length 1) runs once more with the
+"fastdiv" knob at 0, so that k_raycast's IEEE divides are executed too (0.04 s)."""
 import ctypes
 import os
 import subprocess
@@ -117,6 +118,24 @@ def _hold(rays, want, W, what):
 @pytest.mark.parametrize("bs", [1, 2])
 @pytest.mark.parametrize("grid", sorted(GRIDS))
 def test_rays_match_the_referee_exactly(maps, hip, grid, bs):
+    _rays_match_the_referee(maps, hip, grid, bs)
+
+
+def test_rays_match_the_referee_exactly_with_the_ieee_divide(maps, hip):
+    """the np2, ring length 1 case once more with the "fastdiv" knob at 0: k_raycast's `P.fastdiv &` branches take the IEEE divide
+    instead of the verified reciprocal, and the answers are held to the same referee (which divides)"""
+    g = maps["np2", 1][0]
+    assert g.get_tuning("fastdiv") == 3
+    try:
+        g.set_tuning("fastdiv", 0)
+        assert g.get_tuning("fastdiv") == 0
+        _rays_match_the_referee(maps, hip, "np2", 1)
+    finally:
+        g.set_tuning("fastdiv", -1)                            # as created: the maps are shared
+    assert g.get_tuning("fastdiv") == 3
+
+
+def _rays_match_the_referee(maps, hip, grid, bs):
     g, state, W, (A, B, fam) = maps[grid, bs]
     # 1, 63, 65 rays: a spread over all families (the 4,096 are the whole input)
     picks = {n: (np.arange(n) * rr.N_RAYS) // n + (7 if n > 1 else 2050) for n in (1, 63, 65)}

@@ -12,13 +12,18 @@
 // No MFMA: there is no dense contraction on this path.
 #include "gvom_device.h"
 
-// sum of the per-workgroup occupied-voxel counts of k_fuse -> host-mapped memory
-__device__ __forceinline__ void publish_block_counts(const uint32_t *blockcounts, int nblocks,
-                                                     volatile unsigned long long *host_counter,
-                                                     unsigned long long *s_red, int tid, int nthreads)
+// sum of the per-workgroup occupied-voxel counts of k_fuse -> host-mapped memory, in two halves: a thread's share of the counts
+// (global loads), and the workgroup's sum of the shares with its store into host memory (LDS and barriers only)
+__device__ __forceinline__ unsigned long long block_counts_share(const uint32_t *blockcounts, int nblocks, int tid, int nthreads)
 {
     unsigned long long a = 0;
     for (int i = tid; i < nblocks; i += nthreads) a += blockcounts[i];
+    return a;
+}
+
+__device__ __forceinline__ void publish_count_shares(unsigned long long a, volatile unsigned long long *host_counter,
+                                                     unsigned long long *s_red, int tid, int nthreads)
+{
     s_red[tid] = a;
     __syncthreads();
     for (int o = nthreads >> 1; o > 0; o >>= 1) {
@@ -27,6 +32,13 @@ __device__ __forceinline__ void publish_block_counts(const uint32_t *blockcounts
     }
     // (system scope: k_map2d publishes its completion before the kernel ends, the count must have left the L2 by then)
     if (tid == 0) __hip_atomic_store((unsigned long long *)host_counter, s_red[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+__device__ __forceinline__ void publish_block_counts(const uint32_t *blockcounts, int nblocks,
+                                                     volatile unsigned long long *host_counter,
+                                                     unsigned long long *s_red, int tid, int nthreads)
+{
+    publish_count_shares(block_counts_share(blockcounts, nblocks, tid, nthreads), host_counter, s_red, tid, nthreads);
 }
 
 __global__ void k_publish_count(const uint32_t *blockcounts, int nblocks, unsigned long long *host_counter,
@@ -83,6 +95,13 @@ __device__ __forceinline__ void st_out(V *p, V v)
 // Waves 0-3 therefore compute ONLY slope / roughness -- LDS data, no global load -- and store the
 // f64 roughness map (40 % of the bytes) while waves 4-7 are still waiting for their density loads;
 // those then store visibility / positive / negative.  The slope-obstacle flag crosses through LDS.
+// THE ORDER INSIDE A ROLE follows from one rule: a wave never waits on vmcnt once it has stored into host memory, except at the
+// very end.  Role A: visibility leaves after the first barrier (in front of the column masks), roughness as soon as it is final (in
+// front of the slopes' atan2).  Role B: inferred height and the first tags are requested, the ring search runs on LDS meanwhile,
+// the density rounds follow, and only then -- every load's data used -- the negative verdict is stored, the barrier passed and
+// the positive one stored.  (With the ring search BEHIND the positive store, the wait for the inferred height that opens it was
+// a wait for that store's acknowledgement over PCIe as well: two link round trips in series in every wave that stored both.)
+// Workgroup (0,0) requests the block counts with its staging loads and publishes their sum at its end.
 //
 // DEV (with YX, unsharded): the output is a MAP SET in device memory (gvom_combine_maps_device) -- nine xy*xy maps in the
 // same [y][x] order, plain stores, no completion flag.  out_pos / out_neg / out_vis are maps 0-2, out_rough is map 3 and
@@ -140,11 +159,23 @@ __global__ __launch_bounds__(512) void k_map2d(const Map2dParams P, const int32_
         rec_new |= (now ? 1u : 0u) << (2 * m + rec_half);
         return now || ((rec_old >> (2 * m + rec_half)) & 1u);
     };
-    if (host_counter && blockIdx.x == 0 && blockIdx.y == 0 && !GVOM_DBG(P, 16)) {
-        // k_fuse is complete: publish the fused occupied-voxel count (host-mapped memory)
-        __shared__ unsigned long long s_red[512];
-        publish_block_counts(blockcounts, nblocks, host_counter, s_red, tid, 512);
-    }
+    // k_fuse is complete: workgroup (0,0) publishes the fused occupied-voxel count (host-mapped memory).  Its loads go out with the
+    // staging loads; the sum and the store into host memory wait until the workgroup's maps are on their way (the end of the body)
+    const bool publish = host_counter && blockIdx.x == 0 && blockIdx.y == 0 && !GVOM_DBG(P, 16);
+    unsigned long long cnt_share = 0;
+
+    const int x0 = X0 + tx, y0 = Y0 + ty;                            // window cell
+    bool mine = x0 < xy && y0 < xy;
+    const int sx0 = wrap_add(mine ? x0 : 0, P.om[0], xy), sy0 = wrap_add(mine ? y0 : 0, P.om[1], xy);
+    mine = mine && sy0 >= P.y_lo && sy0 < P.y_hi;                      // else: another rank's row
+    const int lx = tx + M2_HALO, ly = ty + M2_HALO;
+    const size_t c_out = (size_t)y0 * xy + x0;                         // YX: [y][x] (column-major [x, y])
+    const bool wr = !GVOM_DBG(P, 1);
+    double h00 = -1000.0, inf00 = 0.0, rv = -1.0;
+    int dens_pos = 0, pos = 0, negv = 0, visv = 0;           // dens_pos: positive-obstacle density x100 (gvom.py:489-521)
+    int8_t *const occ = reinterpret_cast<int8_t *>(out_pos);
+    const size_t n2 = (size_t)xy * xy;
+    const size_t c_yx = (size_t)sy0 * xy + sx0;
 
     // ---- stage the tile (+halo) and its row masks ------------------------------------------
     {   // all of a wave's rows are fetched before the first use: independent, unconditional loads
@@ -161,6 +192,7 @@ __global__ __launch_bounds__(512) void k_map2d(const Map2dParams P, const int32_
             inw[k] = r < M2_H && lane < M2_W && gy >= 0 && gy < xy && gx >= 0 && gx < xy;
             v[k] = height[inw[k] ? (size_t)wrap_add(gy, P.om[1], xy) * P.hs + sxh : (size_t)0];
         }
+        if (publish) cnt_share = block_counts_share(blockcounts, nblocks, tid, 512);
 #pragma unroll
         for (int k = 0; k < NR; ++k) {
             const int r = wv + 8 * k;
@@ -173,29 +205,9 @@ __global__ __launch_bounds__(512) void k_map2d(const Map2dParams P, const int32_
         }
     }
     __syncthreads();
-    if (tid < M2_W) {
-        unsigned long long m = 0ull;
-        for (int r = 0; r < M2_H; ++r) m |= ((rowm[r] >> tid) & 1ull) << r;
-        colm[tid] = m;
-    }
-    __syncthreads();
-
-    const int x0 = X0 + tx, y0 = Y0 + ty;                            // window cell
-    bool mine = x0 < xy && y0 < xy;
-    const int sx0 = wrap_add(mine ? x0 : 0, P.om[0], xy), sy0 = wrap_add(mine ? y0 : 0, P.om[1], xy);
-    mine = mine && sy0 >= P.y_lo && sy0 < P.y_hi;                      // else: another rank's row
-    const int lx = tx + M2_HALO, ly = ty + M2_HALO;
-    const size_t c_out = (size_t)y0 * xy + x0;                         // YX: [y][x] (column-major [x, y])
-    const bool wr = !GVOM_DBG(P, 1);
-    double h00 = -1000.0, inf00 = 0.0, rv = -1.0;
-    int dens_pos = 0, pos = 0, negv = 0, visv = 0;           // dens_pos: positive-obstacle density x100 (gvom.py:489-521)
-    int8_t *const occ = reinterpret_cast<int8_t *>(out_pos);
-    const size_t n2 = (size_t)xy * xy;
-    const size_t c_yx = (size_t)sy0 * xy + sx0;
     if (mine) h00 = ht[ly][lx];
-    if (!role_b) {
-    if (mine) {
-    // visibility needs only the staged height: it leaves with the first stores (gvom.py:414-422)
+    if (!role_b && mine) {
+    // visibility needs only the staged height: it is the first store, in front of the column masks (gvom.py:414-422)
     // OCC: instead of the four maps, the five int8 nav_msgs/OccupancyGrid.data arrays the ROS node
     // derives from them (gvom_ros.py:141-165), planes [hard | soft | certainty | negative | roughness]
     visv = h00 > -1000 ? 1 : 0;
@@ -203,10 +215,25 @@ __global__ __launch_bounds__(512) void k_map2d(const Map2dParams P, const int32_
     else if (YX && wr) { if (P.occ && !DEV) st_sys(&occ[2 * n2 + c_out], (int8_t)(visv * 100)); else st_out<DEV>(&out_vis[c_out], visv); }
     if (DEV && wr) out_rough[dev_map_stride(xy) + c_out] = h00;                 // map 4: height
     if (!YX) o_vis[tx][ty] = visv;
+    }
+    bool tile_any;                                           // some cell of the tile or its halo has a height
+    {   // the column masks are the row masks transposed: lane r holds row r, one ballot per column, a wave's columns 8 apart
+        const unsigned long long rm = lane < M2_H ? rowm[lane] : 0ull;
+        tile_any = __ballot(rm != 0ull) != 0ull;
+        for (int c = wv; c < M2_W; c += 8) {
+            const unsigned long long m = __ballot((rm >> c) & 1ull);
+            if (lane == 0) colm[c] = m;
+        }
+    }
+    __syncthreads();
+
+    if (!role_b) {
+    if (mine) {
     // ---- role A: slope / roughness: 3x3 least-squares plane (gvom.py:665-734) ---------------------
     // cells outside the window hold -1000 in the tile, i.e. are skipped exactly like the
     // reference's clipped ranges; iteration order is x outer / y inner as in the reference.
-    double sxv = 0.0, syv = 0.0;
+    double sxv = 0.0, syv = 0.0, pa0 = 0.0, pa1 = 0.0, pm = 1.0;     // (the fitted plane, kept for the slopes)
+    bool plane = false;
     {
         int n_good = 0;
 #pragma unroll
@@ -265,12 +292,11 @@ __global__ __launch_bounds__(512) void k_map2d(const Map2dParams P, const int32_
                 err /= fi;
                 if (err > 0) err = log(err);
                 rv = err;
-                sxv = atan2(a0, 1.0 / m);
-                syv = atan2(a1, 1.0 / m);
+                plane = true; pa0 = a0; pa1 = a1; pm = m;
             }
         }
     }
-    slope_x[c_yx] = sxv; slope_y[c_yx] = syv; rough[c_yx] = rv;
+    // roughness is half of what crosses the link and is final here: it leaves in front of the two atan2 of the slopes
     if (DELTA) { if (wr && run_store(1, rv != -1.0)) st_sys(&out_rough[c_out], rv); }
     else if (YX && wr) {
         if (P.occ && !DEV) {
@@ -281,80 +307,59 @@ __global__ __launch_bounds__(512) void k_map2d(const Map2dParams P, const int32_
             st_sys(&occ[4 * n2 + c_out], (int8_t)(uint8_t)(uint32_t)ri);
         } else st_out<DEV>(&out_rough[c_out], rv);
     }
+    if (plane) {
+        sxv = atan2(pa0, 1.0 / pm);
+        syv = atan2(pa1, 1.0 / pm);
+    }
+    slope_x[c_yx] = sxv; slope_y[c_yx] = syv; rough[c_yx] = rv;
     if (DEV && wr) { out_rough[3 * dev_map_stride(xy) + c_out] = sxv; out_rough[4 * dev_map_stride(xy) + c_out] = syv; }   // maps 6, 7
     s_steep[cell] = (sqrt(sxv * sxv + syv * syv) >= P.slope_thr) ? 1 : 0;   // gvom.py:489-521, used by role B
     if (!YX) o_rgh[tx][ty] = rv;
     }   // mine
     } else {
     if (mine) {
-    // ---- role B, before the barrier: every global load of the cell.  Stores into host-mapped memory
-    // are acknowledged slowly and vmcnt is in-order: a load issued after one would stall the wave
-    // until the store has drained over PCIe, so this role stores nothing before its loads are back.
+    // ---- role B, before the barrier: every global load of the cell, and everything that hangs on one.  Stores into
+    // host-mapped memory are acknowledged slowly and vmcnt is in-order: a load issued after one -- or the wait for a load
+    // issued before one -- would stall the wave until the store has drained over PCIe, so this role stores nothing before
+    // the data of its last load has been used.  The ring search of __guess_height reads LDS only: it runs while the
+    // inferred height and the first round of tags are on their way, and the inferred height enters when it is over.
     inf00 = inferred[(size_t)sy0 * P.hs + sx0];
+    int zmin = 0, zmax = -1;                                 // the levels of the density window (none: no round)
+    uint32_t rz[8], tg[8];
+    // a round's tags: 8 levels from zb (unconditional loads, dummy level when dead)
+    auto load_tags = [&](int zb) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const int z = (zb + k <= zmax) ? zb + k : zmin;
+            rz[k] = (uint32_t)sy0 * P.zs + (uint32_t)wrap_add(z, P.om[2], P.zs);
+            tg[k] = ftags[rz[k] * P.nseg + (sx0 >> 6)];
+        }
+    };
     if (GATHERED_POS) {
         // sharded runs: the slab owner computed the density (k_posdens), all-gathered with the heights
         dens_pos = (int)height[(size_t)sy0 * P.hs + 2 * (size_t)xy + sx0];
     } else {
         const double fmin = floor(((h00 + P.pos_thr) / P.z_res) - P.origin_z) + 1.0;
         const double fmax = floor(((h00 + P.robot_height) / P.z_res) - P.origin_z);
-        if (fmin >= 0 && fmin < (double)P.zs && fmax >= 0 && fmax < (double)P.zs && !GVOM_DBG(P, 2)) {
-            const int zmin = (int)fmin, zmax = (int)fmax;
-            double density = 0.0, nn = 0.0;
-            // 8 levels per round: tags, then states, then counts -- three dependent round trips
-            // per round instead of three per level (unconditional loads, dummy index when dead)
-            for (int zb = zmin; zb <= zmax; zb += 8) {
-                uint32_t rz[8], tg[8], hc[8], tc[8];
-                int32_t row[8];
-#pragma unroll
-                for (int k = 0; k < 8; ++k) {
-                    const int z = (zb + k <= zmax) ? zb + k : zmin;
-                    rz[k] = (uint32_t)sy0 * P.zs + (uint32_t)wrap_add(z, P.om[2], P.zs);
-                    tg[k] = ftags[rz[k] * P.nseg + (sx0 >> 6)];
-                }
-#pragma unroll
-                for (int k = 0; k < 8; ++k) {
-                    const bool live = zb + k <= zmax && tg[k] == P.epoch;       // live tile
-                    row[k] = fstate[live ? rz[k] * xy + sx0 : 0u];
-                    if (!live) row[k] = -1;
-                }
-#pragma unroll
-                for (int k = 0; k < 8; ++k) {
-                    const uint32_t r = row[k] >= 0 ? (uint32_t)row[k] : 0u;
-                    const uint2 ht = *reinterpret_cast<const uint2 *>(frows + r);
-                    hc[k] = ht.x; tc[k] = ht.y;
-                }
-#pragma unroll
-                for (int k = 0; k < 8; ++k)
-                    if (row[k] >= 0 && (int32_t)hc[k] > 10) { nn += (double)(int32_t)tc[k]; density += (double)(int32_t)hc[k]; }
-            }
-            if (nn > 0.0) density /= nn;
-            dens_pos = (int)(density * 100);
-        }
-    }
-    }   // mine
-    }
-    __syncthreads();
-    if (role_b && mine) {
-    visv = h00 > -1000 ? 1 : 0;                    // gvom.py:414-422 (stored by role A)
-    pos = s_steep[cell] ? 100 : dens_pos;                    // gvom.py:489-521 (slope test done by role A)
-    if (DELTA) { if (wr && run_store(0, pos != 0)) st_sys(&out_pos[c_out], pos); }
-    else if (YX && wr) {
-        if (P.occ && !DEV) st_sys(&occ[1 * n2 + c_out], (int8_t)(((double)pos <= P.occ_density_thr && pos > 0) ? 100 : 0));   // soft, :146
-        else st_out<DEV>(&out_pos[c_out], pos);
+        if (fmin >= 0 && fmin < (double)P.zs && fmax >= 0 && fmax < (double)P.zs && !GVOM_DBG(P, 2)) { zmin = (int)fmin; zmax = (int)fmax; }
+        load_tags(zmin);
     }
 
     // ---- guess height (gvom.py:558-661), typos at :581 and :655 reproduced ---------------
     // ring i, direction +x: first valid cell of column x0+i for dy in [-i, i)   -> colm bit-scan
     //                   -x: column x0-i, dy in [-i+1, i];  +y: row y0+i, dx in [-i+1, i];
     //                   -y: row y0-i, dx in [-i, i)                               (gvom.py:588-638)
-    double dh_out = 0.0;
-    if (!(h00 > -1000 || inf00 == -1000.0) && !GVOM_DBG(P, 8)) {
+    // The search of a cell without height; whether the cell has an inferred height (the reference asks before it searches) is
+    // known only after it, and decides whether its result is used.
+    const bool searched = !(h00 > -1000) && !GVOM_DBG(P, 8);
+    double x_ph = -1000.0, x_nh = -1000.0, y_ph = -1000.0, y_nh = -1000.0;
+    if (searched) {
         bool x_p_done = false, x_n_done = false, y_p_done = false, y_n_done = false;
         // position of each direction's first valid cell in the tile (row, col); -1: none.  The four
         // masks of a ring are read together and the heights only after the search: one LDS round
         // trip per ring instead of eight dependent ones.
         int rxp = -1, cxp = 0, rxn = -1, cxn = 0, ryp = -1, cyp = 0, ryn = -1, cyn = 0;
-        int i = 0;
+        int i = tile_any ? 0 : 15;                           // (a tile without a height in reach: no ring can find one)
         while (i < 15 && !(x_n_done && x_n_done && y_p_done && y_n_done)) {
             i += 1;
             const unsigned long long span = (1ull << (2 * i)) - 1ull;
@@ -384,8 +389,43 @@ __global__ __launch_bounds__(512) void k_map2d(const Map2dParams P, const int32_
             }
         }
         const double hxp = ht[max(rxp, 0)][cxp], hxn = ht[max(rxn, 0)][cxn], hyp = ht[max(ryp, 0)][cyp], hyn = ht[max(ryn, 0)][cyn];
-        const double x_ph = rxp >= 0 ? hxp : -1000.0, x_nh = rxn >= 0 ? hxn : -1000.0;
-        const double y_ph = ryp >= 0 ? hyp : -1000.0, y_nh = ryn >= 0 ? hyn : -1000.0;
+        x_ph = rxp >= 0 ? hxp : -1000.0; x_nh = rxn >= 0 ? hxn : -1000.0;
+        y_ph = ryp >= 0 ? hyp : -1000.0; y_nh = ryn >= 0 ? hyn : -1000.0;
+    }
+
+    // ---- positive-obstacle density (gvom.py:489-521) -------------------------------------
+    if (!GATHERED_POS && zmax >= zmin) {
+        double density = 0.0, nn = 0.0;
+        // 8 levels per round: tags, then states, then counts -- three dependent round trips
+        // per round instead of three per level (unconditional loads, dummy index when dead)
+        for (int zb = zmin; zb <= zmax; zb += 8) {
+            uint32_t hc[8], tc[8];
+            int32_t row[8];
+            if (zb != zmin) load_tags(zb);
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                const bool live = zb + k <= zmax && tg[k] == P.epoch;       // live tile
+                row[k] = fstate[live ? rz[k] * xy + sx0 : 0u];
+                if (!live) row[k] = -1;
+            }
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                const uint32_t r = row[k] >= 0 ? (uint32_t)row[k] : 0u;
+                const uint2 ht = *reinterpret_cast<const uint2 *>(frows + r);
+                hc[k] = ht.x; tc[k] = ht.y;
+            }
+#pragma unroll
+            for (int k = 0; k < 8; ++k)
+                if (row[k] >= 0 && (int32_t)hc[k] > 10) { nn += (double)(int32_t)tc[k]; density += (double)(int32_t)hc[k]; }
+        }
+        if (nn > 0.0) density /= nn;
+        dens_pos = (int)(density * 100);
+    }
+
+    // ---- the negative verdict: it needs nothing of role A and leaves in front of the barrier ----
+    if (GATHERED_POS) asm volatile("" : "+v"(dens_pos));     // (the gathered density is converted HERE: its load is not waited for behind the store)
+    double dh_out = 0.0;
+    if (searched && !(inf00 == -1000.0)) {
         double min_h = 1000.0, max_h = inf00;
         if (x_ph > -1000) { min_h = py_mind(x_ph, min_h); max_h = py_maxd(x_ph, max_h); }
         if (x_nh > -1000) { min_h = py_mind(x_nh, min_h); max_h = py_maxd(x_nh, max_h); }
@@ -394,18 +434,26 @@ __global__ __launch_bounds__(512) void k_map2d(const Map2dParams P, const int32_
         const double dh = max_h - min_h;
         if (dh > 0) dh_out = dh;
     }
-    guessed[c_yx] = dh_out;
     negv = dh_out > P.neg_thr ? 100 : 0;           // gvom.py:479-485
     if (DELTA) { if (wr && run_store(1, negv != 0)) st_sys(&out_neg[c_out], negv); }
+    else if (YX && wr && !(P.occ && !DEV)) st_out<DEV>(&out_neg[c_out], negv);
+    guessed[c_yx] = dh_out;
+    if (DEV && wr) { out_rough[2 * dev_map_stride(xy) + c_out] = inf00; out_rough[5 * dev_map_stride(xy) + c_out] = dh_out; }   // maps 5, 8
+    if (!YX) o_neg[tx][ty] = negv;
+    }   // mine
+    }
+    __syncthreads();
+    if (role_b && mine) {
+    pos = s_steep[cell] ? 100 : dens_pos;                    // gvom.py:489-521 (slope test done by role A)
+    if (DELTA) { if (wr && run_store(0, pos != 0)) st_sys(&out_pos[c_out], pos); }
     else if (YX && wr) {
         if (P.occ && !DEV) {
+            st_sys(&occ[1 * n2 + c_out], (int8_t)(((double)pos <= P.occ_density_thr && pos > 0) ? 100 : 0));   // soft, :146
             st_sys(&occ[3 * n2 + c_out], (int8_t)negv);                                                    // negative, :157
             st_sys(&occ[0 * n2 + c_out], (int8_t)max((double)pos > P.occ_density_thr ? 100 : 0, negv));   // hard, :141
-        } else st_out<DEV>(&out_neg[c_out], negv);
+        } else st_out<DEV>(&out_pos[c_out], pos);
     }
-    if (DEV && wr) { out_rough[2 * dev_map_stride(xy) + c_out] = inf00; out_rough[5 * dev_map_stride(xy) + c_out] = dh_out; }   // maps 5, 8
-
-    if (!YX) { o_pos[tx][ty] = pos; o_neg[tx][ty] = negv; }
+    if (!YX) o_pos[tx][ty] = pos;
     }   // role B, mine
     if (!YX) {
         __syncthreads();
@@ -416,6 +464,11 @@ __global__ __launch_bounds__(512) void k_map2d(const Map2dParams P, const int32_
             out_pos[c_xy] = o_pos[ox][oy]; out_neg[c_xy] = o_neg[ox][oy];
             out_vis[c_xy] = o_vis[ox][oy]; out_rough[c_xy] = o_rgh[ox][oy];
         }
+    }
+    if (publish) {
+        // (in front of the arrival at done_count below: the count is in host memory before the flag)
+        __shared__ unsigned long long s_red[512];
+        publish_count_shares(cnt_share, host_counter, s_red, tid, 512);
     }
     if (DELTA && wr) {
         // the record of what the buffer now holds: lanes 0 and 32 carry their half-waves' bits (a half-wave outside the window

@@ -326,6 +326,16 @@ struct gvom_handle {
     size_t fp_offs_at = 0;
     int fp_H = 0;                                       // 0: no footprint set
     int ro_allocs = 0;
+    // TERRAIN ATTITUDE SCORING (gvom_chassis_set / gvom_score_attitude): at_tab = the chassis table in device memory -- the wheel
+    // offsets [H][4][2] float64, then at at_cs_at bytes (a multiple of 256) cos_sin [H][2] float64 --, at_ground = the ground map
+    // k_attitude_ground writes on the map-set route, at_stage = the staging copy of a caller's host ground map and poses; at_allocs
+    // counts the device allocations gvom_score_attitude has made on this handle (at_ground, at_stage and its product sets:
+    // gvom_get_tuning "attitude_allocations")
+    Buf at_tab, at_ground, at_stage;
+    size_t at_cs_at = 0;
+    int at_H = 0;                                       // 0: no chassis set
+    gvom_chassis_t at_chassis = {};
+    int at_allocs = 0;
     // SCAN ALIGNMENT SCORING (gvom_score_alignments): al_grid = the class grid k_align_field rebuilds in every call (2 bits per voxel,
     // gvom_align_grid_bytes: gvom_get_tuning "alignment_grid_bytes" reads what is allocated), al_stage = the staging copy of a caller's
     // host cloud and transforms; al_allocs counts the device allocations the entry point has made on this handle (the two and its product sets)

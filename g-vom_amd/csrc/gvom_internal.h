@@ -332,6 +332,19 @@ struct RolloutParams {
 };
 hipError_t gvom_launch_rollouts(hipStream_t s, const RolloutParams &P, const float *poses, const int32_t *fstart, const uint32_t *foffs,
                                 const uint16_t *cell_cost, const int32_t *cost_to_go, int32_t *summary, uint16_t *pose_cost);
+// terrain attitude scoring (gvom_attitude.hip; include/gvom_hip.h "terrain attitude scoring" defines the result).  R = the pose frame
+// as k_rollouts takes it; poses, fstart and foffs as above; wheels [H][4][2] and cos_sin [H][2] float64 are the chassis table as
+// gvom_chassis_set stored it; ground is ONE [y][x] float64 map of xy x xy cells (attitude_ground writes it from a map set's height and
+// inferred-height maps).  summary [K][5] int32, attitude [K][T][3] float32, status [K][T] uint8.
+struct AttitudeParams {
+    RolloutParams R;
+    double wheelbase, track, axle_mid, belly_height;   // front_axle - rear_axle, track, 0.5 * (front_axle + rear_axle), belly_height
+    float max_pitch, max_roll, min_clearance;
+};
+hipError_t gvom_launch_attitude_ground(hipStream_t s, int xy, int inferred, const double *height, const double *inferred_height, double *ground);
+hipError_t gvom_launch_attitude(hipStream_t s, const AttitudeParams &P, const float *poses, const int32_t *fstart, const uint32_t *foffs,
+                                const double *wheels, const double *cos_sin, const double *ground, int32_t *summary, float *attitude,
+                                uint8_t *status);
 // scan alignment scoring (gvom_align.hip; include/gvom_hip.h "scan alignment scoring" defines the result).  cloud [n][3] float32 and
 // tf [K][12] float64 (rows 0..2 of each 4x4) in device memory; F = the fused map's frame as k_occupancy takes it.  grid: the class
 // grid, gvom_align_grid_bytes(xy, zs) of scratch, rebuilt by every call.  counts [K][6] int32 (cleared here, then {score, occupied,

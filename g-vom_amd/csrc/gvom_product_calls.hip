@@ -1,5 +1,5 @@
 // gvom_product_calls.hip -- the calls that MAKE a device product: gvom_device_product (occupancy grid, voxel cloud, the two height
-// clouds), gvom_clearance, gvom_raycast, gvom_cost_to_go, gvom_score_rollouts (with gvom_footprint_set, which sets its table) and gvom_score_alignments, and the frame builders they and the debug reads (gvom_debug.hip) give
+// clouds), gvom_clearance, gvom_raycast, gvom_cost_to_go, gvom_score_rollouts (with gvom_footprint_set, which sets its table), gvom_score_attitude (with gvom_chassis_set) and gvom_score_alignments, and the frame builders they and the debug reads (gvom_debug.hip) give
 // the kernels.  Every call takes its set through product_acquire and hands it out through product_publish (gvom_sets.hip); what is
 // left in each body is what is particular to that product: its argument checks, its staging and its launches.
 #include "gvom_host.h"
@@ -84,6 +84,7 @@ VIS int gvom_device_product(gvom_t *h, int kind, int64_t max_rows, int64_t *prod
     static const char *const elsewhere[] = {"a clearance product is made by gvom_clearance", "a raycast product is made by gvom_raycast", "a cost field is made by gvom_cost_to_go"};
     if (kind >= GVOM_PRODUCT_CLEARANCE && kind <= GVOM_PRODUCT_COSTFIELD) { h->err = std::string("gvom_device_product: ") + elsewhere[kind - GVOM_PRODUCT_CLEARANCE]; return GVOM_ERR_INVALID; }
     if (kind == GVOM_PRODUCT_ROLLOUTS) { h->err = "gvom_device_product: rollouts are made by gvom_score_rollouts"; return GVOM_ERR_INVALID; }
+    if (kind == GVOM_PRODUCT_ATTITUDE) { h->err = "gvom_device_product: attitude scores are made by gvom_score_attitude"; return GVOM_ERR_INVALID; }
     if (kind == GVOM_PRODUCT_ALIGNMENT) { h->err = "gvom_device_product: alignment scores are made by gvom_score_alignments"; return GVOM_ERR_INVALID; }
     if (kind < 1 || kind > GVOM_N_PRODUCT_KINDS) { h->err = "gvom_device_product: unknown product kind"; return GVOM_ERR_INVALID; }
     if (h->sharded) { h->err = "gvom_device_product: sharded handles are not supported"; return GVOM_ERR_INVALID; }
@@ -429,6 +430,111 @@ VIS int gvom_score_rollouts(gvom_t *h, int64_t costfield_id, const uint16_t *cel
     P.res = h->prm.xy_resolution;
     HIPCHK(h, gvom_launch_rollouts(h->stream, P, pdev, (const int32_t *)h->fp_tab.p, (const uint32_t *)((char *)h->fp_tab.p + h->fp_offs_at),
                                    c16, D, part_ptr<int32_t>(set, 0), part_ptr<uint16_t>(set, 1)));
+    return product_publish(h, set, product_id);
+}
+
+// ---- terrain attitude scoring (gvom_chassis_set, gvom_score_attitude) -------------------------------------------------------------
+// K trajectories of T poses each, scored by k_attitude (gvom_attitude.hip) against one float64 ground map with the footprint table and
+// the chassis of the handle: a product of kind GVOM_PRODUCT_ATTITUDE sized by K and T.  With a map set, k_attitude_ground first
+// writes the ground map from the set's height and inferred-height maps into a grow-only buffer of the handle.  The kernels run on
+// the handle's stream -- behind the combine that wrote the set, and in front of whatever recycles it later.  Enqueues and returns.
+VIS int gvom_chassis_set(gvom_t *h, const gvom_chassis_t *c, int32_t n_headings, const double *cos_sin)
+{
+    if (!h) return GVOM_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (!c || !cos_sin) { h->err = "gvom_chassis_set: the chassis and cos_sin must not be NULL"; return GVOM_ERR_INVALID; }
+    if (n_headings < 1 || n_headings > GVOM_ROLLOUT_MAX_HEADINGS) { h->err = "gvom_chassis_set: between 1 and 1024 headings"; return GVOM_ERR_INVALID; }
+    if (!(isfinite(c->front_axle) && isfinite(c->rear_axle) && isfinite(c->track) && isfinite(c->belly_height))) { h->err = "gvom_chassis_set: a length is not finite"; return GVOM_ERR_INVALID; }
+    if (!(c->front_axle > c->rear_axle)) { h->err = "gvom_chassis_set: front_axle must lie in front of rear_axle"; return GVOM_ERR_INVALID; }
+    if (!(c->track > 0.0)) { h->err = "gvom_chassis_set: track must be greater than 0"; return GVOM_ERR_INVALID; }
+    if (c->max_pitch != c->max_pitch || c->max_roll != c->max_roll || c->min_clearance != c->min_clearance) { h->err = "gvom_chassis_set: a limit is not a number"; return GVOM_ERR_INVALID; }
+    for (int k = 0; k < 2 * n_headings; ++k)
+        if (!(fabs(cos_sin[k]) <= 1.0)) { h->err = "gvom_chassis_set: a cos_sin entry is not finite or exceeds 1 in magnitude"; return GVOM_ERR_INVALID; }
+    const size_t wb = (size_t)n_headings * 64, cs_at = align256(wb), cb = (size_t)n_headings * 16;
+    std::vector<double> tab((cs_at + cb) / 8, 0.0);
+    const double half = c->track / 2, ab[4][2] = {{c->front_axle, half}, {c->front_axle, -half}, {c->rear_axle, half}, {c->rear_axle, -half}};
+    for (int k = 0; k < n_headings; ++k) {
+        const double co = cos_sin[2 * k], si = cos_sin[2 * k + 1];
+        for (int i = 0; i < 4; ++i) {
+            const double wx = ab[i][0] * co - ab[i][1] * si, wy = ab[i][0] * si + ab[i][1] * co;
+            if (!(isfinite(wx) && isfinite(wy))) { h->err = "gvom_chassis_set: a wheel offset is not finite"; return GVOM_ERR_INVALID; }
+            tab[(size_t)(k * 4 + i) * 2] = wx; tab[(size_t)(k * 4 + i) * 2 + 1] = wy;
+        }
+        tab[cs_at / 8 + 2 * k] = co; tab[cs_at / 8 + 2 * k + 1] = si;
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    h->at_H = 0;                                                            // (no chassis while this one is on its way)
+    if (h->at_tab.bytes < cs_at + cb) HIPCHK(h, hipStreamSynchronize(h->stream));   // the kernels that read the table it outgrows
+    const int rc = ensure(h, h->at_tab, cs_at + cb);
+    if (rc) return rc;
+    // on the handle's stream: behind whatever still reads the previous table
+    HIPCHK(h, hipMemcpyAsync(h->at_tab.p, tab.data(), cs_at + cb, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->at_cs_at = cs_at; h->at_H = n_headings; h->at_chassis = *c;
+    return GVOM_OK;
+}
+
+VIS int gvom_score_attitude(gvom_t *h, int64_t map_set_id, const double *ground, const float *poses, int64_t K, int64_t T, int on_device,
+                            int flags, const int64_t origin_cells[2], int64_t *product_id)
+{
+    if (!h || !product_id) return GVOM_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(h->mu);
+    *product_id = -1;
+    if (h->sharded) { h->err = "gvom_score_attitude: sharded handles are not supported"; return GVOM_ERR_INVALID; }
+    if (h->fp_H < 1) { h->err = "gvom_score_attitude: no footprint table is set (gvom_footprint_set)"; return GVOM_ERR_INVALID; }
+    if (h->at_H < 1) { h->err = "gvom_score_attitude: no chassis is set (gvom_chassis_set)"; return GVOM_ERR_INVALID; }
+    if (h->at_H != h->fp_H) { h->err = "gvom_score_attitude: the chassis was set for another number of headings than the footprint table has"; return GVOM_ERR_INVALID; }
+    if (!poses || !origin_cells) { h->err = "gvom_score_attitude: poses and origin_cells must not be NULL"; return GVOM_ERR_INVALID; }
+    if (flags & ~GVOM_ATTITUDE_INFERRED_GROUND) { h->err = "gvom_score_attitude: unknown flag bits"; return GVOM_ERR_INVALID; }
+    if (map_set_id >= 0 && ground) { h->err = "gvom_score_attitude: give a map set id or a ground map, not both"; return GVOM_ERR_INVALID; }
+    if (map_set_id < 0 && !ground) { h->err = "gvom_score_attitude: give a map set id or a ground map"; return GVOM_ERR_INVALID; }
+    if (T < 1 || T > GVOM_ROLLOUT_MAX_T) { h->err = "gvom_score_attitude: T outside 1 .. 4096"; return GVOM_ERR_INVALID; }
+    if (K < 1) { h->err = "gvom_score_attitude: K must be at least 1"; return GVOM_ERR_INVALID; }
+    if (K > GVOM_ROLLOUT_MAX_POSES / T) { h->err = "gvom_score_attitude: more than 2^26 poses in one call"; return GVOM_ERR_CAPACITY; }
+    for (int k = 0; k < 2; ++k)
+        if (origin_cells[k] < -((int64_t)1 << 40) || origin_cells[k] > ((int64_t)1 << 40)) { h->err = "gvom_score_attitude: an origin beyond 2^40 cells"; return GVOM_ERR_INVALID; }
+    const int xy = h->prm.xy_size;
+    if (xy > GVOM_CLEARANCE_MAX_XY) { h->err = "gvom_score_attitude: maps of more than 4096 cells a side are not supported"; return GVOM_ERR_CAPACITY; }
+    const size_t n2 = (size_t)xy * xy;
+    DevSet *m = nullptr;
+    if (map_set_id >= 0) {
+        m = find_set(h->dsets, map_set_id);
+        if (!m) { h->err = "unknown or stale device map set id"; return GVOM_ERR_INVALID; }
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    DevSet *set = nullptr;
+    const size_t bytes = set_bytes(GVOM_PRODUCT_ATTITUDE, 0, 0, K, T);
+    int rc = product_acquire(h, GVOM_PRODUCT_ATTITUDE, bytes, bytes, "gvom_score_attitude", &h->at_allocs, &set);
+    if (rc) return rc;
+    set->cap = K; set->cols = T;
+    if (m && (rc = stage_buf(h, h->at_ground, n2 * 8, h->at_allocs))) return rc;
+    const float *pdev = poses;
+    const double *gdev = m ? (const double *)h->at_ground.p : ground;
+    HIPCHK(h, join_second_stream(h));
+    if (!on_device) {                                                       // host poses (and ground): staged, and up before the call returns
+        const size_t pb = (size_t)K * T * 12, gb = m ? 0 : align256(n2 * 8);
+        if ((rc = stage_buf(h, h->at_stage, gb + pb, h->at_allocs))) return rc;
+        char *st = (char *)h->at_stage.p;
+        if (gb) { HIPCHK(h, hipMemcpyAsync(st, ground, n2 * 8, hipMemcpyHostToDevice, h->stream)); gdev = (const double *)st; }
+        HIPCHK(h, hipMemcpyAsync(st + gb, poses, pb, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        pdev = (const float *)(st + gb);
+    }
+    if ((rc = set_wait_releases(h, set))) return rc;
+    if (m) HIPCHK(h, gvom_launch_attitude_ground(h->stream, xy, (flags & GVOM_ATTITUDE_INFERRED_GROUND) ? 1 : 0, part_ptr<const double>(m, 4),
+                                                part_ptr<const double>(m, 5), (double *)h->at_ground.p));
+    const gvom_chassis_t &c = h->at_chassis;
+    AttitudeParams P;
+    memset(&P, 0, sizeof P);
+    P.R.xy = xy; P.R.H = h->fp_H; P.R.T = (int)T; P.R.K = K;
+    P.R.s = (float)((double)h->fp_H / 6.283185307179586476925286766559);
+    P.R.ox = origin_cells[0]; P.R.oy = origin_cells[1];
+    P.R.res = h->prm.xy_resolution;
+    P.wheelbase = c.front_axle - c.rear_axle; P.track = c.track; P.axle_mid = 0.5 * (c.front_axle + c.rear_axle); P.belly_height = c.belly_height;
+    P.max_pitch = c.max_pitch; P.max_roll = c.max_roll; P.min_clearance = c.min_clearance;
+    HIPCHK(h, gvom_launch_attitude(h->stream, P, pdev, (const int32_t *)h->fp_tab.p, (const uint32_t *)((char *)h->fp_tab.p + h->fp_offs_at),
+                                   (const double *)h->at_tab.p, (const double *)((char *)h->at_tab.p + h->at_cs_at), gdev,
+                                   part_ptr<int32_t>(set, 0), part_ptr<float>(set, 1), part_ptr<uint8_t>(set, 2)));
     return product_publish(h, set, product_id);
 }
 

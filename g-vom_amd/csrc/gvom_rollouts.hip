@@ -12,38 +12,15 @@
 // READ-ONLY on the maps.  No scratch, no atomics, no wave waits on another workgroup; every loop is bounded at launch (T <= 4096
 // poses, <= 16384 cells per heading).  Integer arithmetic throughout but the pose's two divisions (float64, IEEE) and one float32
 // multiply (-ffp-contract=off): the result is exact.
-#include "gvom_device.h"
+#include "gvom_rollouts.h"       // RO_FAR, ro_cell, ro_pose: the pose frame, shared with gvom_attitude.hip
 
 #define RO_WAVES 4          // waves per workgroup (fewer where T is smaller)
 #define RO_DEPTH 4          // footprint cells per lane whose loads are in flight together
-#define RO_FAR 100000       // a centre this far out has every footprint cell (|offset| < 2^15) outside any window (xy <= 4096)
-
 // status words (include/gvom_hip.h GVOM_ROLLOUT_*)
 #define RO_CLEAR 0
 #define RO_COLLISION 1
 #define RO_LEFT_WINDOW 2
 #define RO_INVALID 3
-
-// floor((double)x / res) - o, clamped to +-RO_FAR; -RO_FAR for NaN, an infinity and |x / res| >= 2^30
-__device__ __forceinline__ int ro_cell(float x, double res, long long o)
-{
-    const double q = (double)x / res;
-    if (!(fabs(q) < 1073741824.0)) return -RO_FAR;
-    const long long c = (long long)floor(q) - o;
-    return (int)max(min(c, (long long)RO_FAR), (long long)-RO_FAR);
-}
-
-// centre cell, heading and validity of a pose (x, y, yaw)
-__device__ __forceinline__ bool ro_pose(const RolloutParams &P, const float *__restrict__ p, int &cx, int &cy, int &h)
-{
-    const float x = p[0], y = p[1], yaw = p[2];
-    const float a = yaw * P.s;
-    const bool valid = fabsf(x) < INFINITY && fabsf(y) < INFINITY && fabsf(yaw) < INFINITY && fabsf(a) < 16777216.0f;
-    cx = ro_cell(x, P.res, P.ox); cy = ro_cell(y, P.res, P.oy);
-    const int r = valid ? (int)rintf(a) % P.H : 0;          // (|a| < 2^24: the conversion is exact)
-    h = r < 0 ? r + P.H : r;
-    return valid;
-}
 
 __global__ __launch_bounds__(RO_WAVES * WAVE) void k_rollouts(const RolloutParams P, const float *__restrict__ poses,
                                                               const int32_t *__restrict__ fstart, const uint32_t *__restrict__ foffs,

@@ -16,6 +16,9 @@
 //                    rollouts K and cols = the poses per rollout T of the call that wrote it.  Kinds 8, 9 and 11 are not assigned
 //   alignment (12)   cap x 6 int32 {score, occupied, near, free, unknown, outside}, then 4 int32 {best index, best score, n, K};
 //                    cap = the candidates K of the call that wrote it
+//   attitude (14)    cap x 5 int32 {status, first_bad, steepest_pitch_pose, steepest_roll_pose, lowest_belly_pose}, then cap x cols x 3
+//                    floats {pitch, roll, belly}, then cap x cols uint8 (pose status); cap = K and cols = T as for rollouts.  Kind 13
+//                    is not assigned
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -35,7 +38,7 @@ struct SetShape {
     // voxel cloud: rows the allocation holds; raycast: rays of the product; a map set: the elements from one map to the next,
     // dev_map_stride(xy) of gvom_internal.h (which needs the HIP runtime: it comes in through here) -- a multiple of 32, >= xy*xy
     int64_t cap = 0;
-    int64_t cols = 0;                          // rollouts: poses per rollout (T)
+    int64_t cols = 0;                          // rollouts, attitude: poses per rollout (T)
 };
 struct SetPart { void *ptr; int ndim; int64_t shape[3], strides[3]; uint8_t code, bits; size_t bytes; };
 
@@ -53,6 +56,7 @@ inline size_t set_bytes(int kind, int xy, int zs, int64_t cap, int64_t cols = 0)
     case GVOM_PRODUCT_COSTFIELD: return align256(n2 * 4) + align256(n2) + n2 * 2;
     case GVOM_PRODUCT_ROLLOUTS: return align256((size_t)cap * 16) + (size_t)cap * (size_t)cols * 2;
     case GVOM_PRODUCT_ALIGNMENT: return align256((size_t)cap * 24) + 16;
+    case GVOM_PRODUCT_ATTITUDE: return align256((size_t)cap * 20) + align256((size_t)cap * (size_t)cols * 12) + (size_t)cap * (size_t)cols;
     }
     return 0;
 }
@@ -115,6 +119,18 @@ inline bool set_part(const SetShape *s, int part, SetPart *d)
         else if (part == 1) { d->ptr = s->mem + align256((size_t)s->cap * 24); d->ndim = 1; d->shape[0] = 4; d->strides[0] = 1; d->shape[1] = d->strides[1] = 1; d->code = kDLInt; }
         else return false;
         break;
+    case GVOM_PRODUCT_ATTITUDE: {
+        char *const att = s->mem + align256((size_t)s->cap * 20);
+        if (part == 0) { rows(s->mem, s->cap, 5); d->code = kDLInt; }
+        else if (part == 1) {
+            d->ptr = att; d->ndim = 3;
+            d->shape[0] = s->cap; d->shape[1] = s->cols; d->shape[2] = 3;
+            d->strides[0] = s->cols * 3; d->strides[1] = 3; d->strides[2] = 1;
+        }
+        else if (part == 2) { rows(att + align256((size_t)s->cap * (size_t)s->cols * 12), s->cap, s->cols); d->code = kDLUInt; d->bits = 8; }
+        else return false;
+        break;
+    }
     default: return false;
     }
     d->bytes = (size_t)(d->shape[0] * d->shape[1] * d->shape[2]) * (d->bits / 8);

@@ -164,6 +164,8 @@ ABI = [
                              ctypes.POINTER(_I64)]),
     ("gvom_footprint_set", _I, [_P, ctypes.c_int32, _P, _P]),
     ("gvom_score_rollouts", _I, [_P, _I64, _P, _P, _P, _I64, _I64, _I, ctypes.POINTER(_I64), ctypes.POINTER(_I64)]),
+    ("gvom_chassis_set", _I, [_P, _P, ctypes.c_int32, _P]),
+    ("gvom_score_attitude", _I, [_P, _I64, _P, _P, _I64, _I64, _I, _I, ctypes.POINTER(_I64), ctypes.POINTER(_I64)]),
     ("gvom_score_alignments", _I, [_P, _P, _I64, _P, _I64, _I, _I, _P, ctypes.POINTER(_I64)]),
     ("gvom_set_profiling", _I, [_P, _I]),
     ("gvom_host_timing", _I, [_P, ctypes.POINTER(ctypes.c_double * 8)]),
@@ -526,6 +528,16 @@ class DeviceMaps(_Export):
         g = self._owner
         return g._clearance(self.set_id, None, None, 0, density_threshold, include_negative, max_distance)
 
+    def score_attitude(self, poses, inferred_ground=True):
+        """How the vehicle would sit on this set's ground at every pose of K candidate trajectories: pitch, roll and belly clearance
+        from the `height` map (and, with inferred_ground, the `inferred height` map where the height is unknown), with the mapper's
+        footprint table and chassis (Gvom.set_footprint, Gvom.set_chassis) -- a DeviceAttitude, computed on the GPU behind the
+        combine that wrote the set; no host wait once the poses are up.  poses: (K, T, 3) = (x, y, yaw) in world metres and radians,
+        ROUNDED TO float32.  include/gvom_hip.h "terrain attitude scoring" has the definition."""
+        g = self._owner
+        a = _rollout_poses(poses)
+        return g._score_attitude(self.set_id, None, _ptr(a), a.shape[0], a.shape[1], 0, bool(inferred_ground), self.origin)
+
     def cost_to_go(self, goals, goals_in_cells=False, inflation_radius=None, density_threshold=50, include_negative=True,
                    unknown="free", base=1, soft_weight=0, rough_weight=0, roughness_range=None, max_cost=None, max_rounds=0):
         """The navigation function of this set's maps towards `goals`: from every cell the cheapest 8-connected way to a goal
@@ -553,12 +565,13 @@ PRODUCT_RAYCAST = 6                       # GVOM_PRODUCT_RAYCAST: made by gvom_r
 PRODUCT_COSTFIELD = 7                     # GVOM_PRODUCT_COSTFIELD: made by gvom_cost_to_go, not by gvom_device_product
 PRODUCT_ROLLOUTS = 10                     # GVOM_PRODUCT_ROLLOUTS: made by gvom_score_rollouts (kinds 8 and 9 are not assigned)
 PRODUCT_ALIGNMENT = 12                    # GVOM_PRODUCT_ALIGNMENT: made by gvom_score_alignments (kind 11 is not assigned either)
+PRODUCT_ATTITUDE = 14                     # GVOM_PRODUCT_ATTITUDE: made by gvom_score_attitude (kind 13 is not assigned)
 # element type of part k of a product, by kind (what set_part() of csrc/gvom_setlayout.h gives as DLPack code and bits)
 _PRODUCT_DTYPES = {PRODUCT_OCCUPANCY: (np.uint8,), PRODUCT_VOXEL_CLOUD: (np.float32, np.float32, np.int64),
                    PRODUCT_HEIGHT_CLOUD: (np.float32,), PRODUCT_INFERRED_HEIGHT_CLOUD: (np.float32,),
                    PRODUCT_CLEARANCE: (np.float32, np.int32), PRODUCT_RAYCAST: (np.int32, np.float32),
                    PRODUCT_COSTFIELD: (np.int32, np.uint8, np.uint16), PRODUCT_ROLLOUTS: (np.int32, np.uint16),
-                   PRODUCT_ALIGNMENT: (np.int32, np.int32)}
+                   PRODUCT_ALIGNMENT: (np.int32, np.int32), PRODUCT_ATTITUDE: (np.int32, np.float32, np.uint8)}
 CLEARANCE_FAR = 2147483647                # GVOM_CLEARANCE_FAR: squared_cells where no obstacle is in reach
 _CLEARANCE_NO_NEGATIVE = 1                # GVOM_CLEARANCE_NO_NEGATIVE
 
@@ -1041,6 +1054,76 @@ class DeviceRollouts(_ProductView):
 
     def copy_to_host(self):
         return self.summary.copy_to_host(), self.pose_cost.copy_to_host()
+
+
+# ---- terrain attitude scoring (Gvom.set_chassis, DeviceMaps.score_attitude and friends; include/gvom_hip.h "terrain attitude scoring") ----
+ATTITUDE_OK, ATTITUDE_PITCH, ATTITUDE_ROLL, ATTITUDE_BELLY, ATTITUDE_UNKNOWN_GROUND, ATTITUDE_LEFT_WINDOW, ATTITUDE_INVALID = range(7)   # GVOM_ATTITUDE_*
+_ATTITUDE_INFERRED_GROUND = 1             # flags
+
+
+class GvomChassis(ctypes.Structure):
+    """gvom_chassis_t"""
+    _fields_ = [("front_axle", ctypes.c_double), ("rear_axle", ctypes.c_double), ("track", ctypes.c_double), ("belly_height", ctypes.c_double),
+                ("max_pitch", ctypes.c_float), ("max_roll", ctypes.c_float), ("min_clearance", ctypes.c_float)]
+
+
+def _chassis_angle(name, a):
+    """a limit angle in radians -> its tangent as float32; None: no limit (+inf)"""
+    if a is None:
+        return np.float32(np.inf)
+    a = float(a)
+    if not 0.0 <= a < math.pi / 2:
+        raise ValueError("%s must be None or an angle in [0, pi / 2) radians, got %r" % (name, a))
+    return np.float32(np.tan(a))
+
+
+def chassis(front_axle, rear_axle, track, belly_height, max_pitch=None, max_roll=None, min_clearance=None):
+    """The chassis for Gvom.set_chassis (a GvomChassis): the axles' body x in metres (x forward, front_axle > rear_axle), the track
+    width, the belly's height above the wheels' contact plane; max_pitch / max_roll: limit angles in radians, stored as
+    np.float32(np.tan(a)); min_clearance: the least belly clearance in metres.  None: no limit."""
+    fa, ra, tr, bh = float(front_axle), float(rear_axle), float(track), float(belly_height)
+    if not (math.isfinite(fa) and math.isfinite(ra) and math.isfinite(tr) and math.isfinite(bh)):
+        raise ValueError("front_axle, rear_axle, track and belly_height must be finite, got %r, %r, %r, %r" % (front_axle, rear_axle, track, belly_height))
+    if not fa > ra:
+        raise ValueError("front_axle must lie in front of rear_axle, got %r <= %r" % (front_axle, rear_axle))
+    if not tr > 0:
+        raise ValueError("track must be a width > 0, got %r" % (track,))
+    c = GvomChassis()
+    c.front_axle, c.rear_axle, c.track, c.belly_height = fa, ra, tr, bh
+    c.max_pitch, c.max_roll = _chassis_angle("max_pitch", max_pitch), _chassis_angle("max_roll", max_roll)
+    mc = -math.inf if min_clearance is None else float(min_clearance)
+    if mc != mc:
+        raise ValueError("min_clearance must be None or a height in metres, got %r" % (min_clearance,))
+    c.min_clearance = np.float32(mc)
+    return c
+
+
+def heading_cos_sin(headings):
+    """float64 [H, 2] = (cos, sin) of 2 pi k / H, exact at quarter turns like rectangle_footprint's"""
+    H = int(headings)
+    a = 2.0 * np.pi * np.arange(H, dtype=np.float64) / H
+    cs = np.stack([np.cos(a), np.sin(a)], axis=1)
+    quarter = ((1.0, 0.0), (0.0, 1.0), (-1.0, 0.0), (0.0, -1.0))
+    for k in range(H):
+        if (4 * k) % H == 0:
+            cs[k] = quarter[(4 * k) // H]
+    return np.ascontiguousarray(cs)
+
+
+class DeviceAttitude(_ProductView):
+    """The result of DeviceMaps.score_attitude() / Gvom.score_attitude_of() / score_attitude_of_device(): `.summary` int32 [K, 5] --
+    per rollout {status (ATTITUDE_*), first bad pose (T: none), the poses of the steepest pitch, the steepest roll and the lowest
+    belly in front of it (-1 without one)} --, `.attitude` float32 [K, T, 3] {pitch tangent (nose up positive), roll tangent (left
+    side up positive), belly clearance in metres} and `.status` uint8 [K, T]: three DeviceArrays of one product, row i = rollout i.
+    A snapshot: later scans, combines, set_footprint and set_chassis calls do not change it.  copy_to_host() returns (summary,
+    attitude, status) as numpy."""
+
+    def __init__(self, hold):
+        _ProductView.__init__(self, hold)
+        self.summary, self.attitude, self.status = DeviceArray(hold, 0), DeviceArray(hold, 1), DeviceArray(hold, 2)
+
+    def copy_to_host(self):
+        return self.summary.copy_to_host(), self.attitude.copy_to_host(), self.status.copy_to_host()
 
 
 ALIGN_MAX_POINTS = 1 << 20
@@ -1807,6 +1890,7 @@ class Gvom(object):
         offsets[start[h]:start[h + 1]].  Replaces a previous table; products made with it are unchanged."""
         st, of = _footprint_arrays(table)
         self._check(self._lib.gvom_footprint_set(self._h, st.shape[0] - 1, _ptr(st), _ptr(of)))
+        self._footprint_headings = st.shape[0] - 1
 
     def _score_rollouts(self, field_id, cost_ptr, ctg_ptr, poses_ptr, K, T, on_device, origin):
         oc = _rollout_origin(origin, self.xy_resolution)
@@ -1832,6 +1916,46 @@ class Gvom(object):
             raise ValueError("cell_cost_ptr and poses_ptr must be device addresses")
         K, T = _rollout_shape(K, T)
         return self._score_rollouts(-1, _dev(cell_cost_ptr), _dev(cost_to_go_ptr), _dev(poses_ptr), K, T, 1, origin)
+
+    # ---- terrain attitude scoring (an extension; include/gvom_hip.h "terrain attitude scoring") ----
+    def set_chassis(self, chassis):
+        """Sets the vehicle's chassis (what chassis() returns) for the score_attitude calls, after set_footprint: the headings are
+        the footprint table's, and `.cos_sin` -- float64 [H, 2], the (cos, sin) of each heading the library turns the wheels and the
+        belly with -- is kept readable.  Replaces a previous chassis; products made with it are unchanged.  Set the chassis again
+        after a set_footprint with another number of headings."""
+        if not isinstance(chassis, GvomChassis):
+            raise ValueError("set_chassis takes what chassis() returns, got %r" % (type(chassis).__name__,))
+        H = getattr(self, "_footprint_headings", None)
+        if H is None:
+            raise ValueError("set_footprint comes first: the chassis takes its headings from the footprint table")
+        cs = heading_cos_sin(H)
+        self._check_args(self._lib.gvom_chassis_set(self._h, ctypes.byref(chassis), H, _ptr(cs)))
+        self.cos_sin = cs
+
+    def _score_attitude(self, set_id, ground_ptr, poses_ptr, K, T, on_device, inferred_ground, origin):
+        oc = _rollout_origin(origin, self.xy_resolution)
+        flags = _ATTITUDE_INFERRED_GROUND if inferred_ground else 0
+        return DeviceAttitude(self._make_product(lambda pid: self._lib.gvom_score_attitude(
+            self._h, int(set_id), ground_ptr, poses_ptr, int(K), int(T), int(on_device), flags, oc, pid), PRODUCT_ATTITUDE,
+            self._check_args))
+
+    def score_attitude_of(self, ground, poses, origin=(0.0, 0.0)):
+        """DeviceMaps.score_attitude() against a ground map of the caller's: a numpy [x, y] array of shape (xy_size, xy_size) in any
+        memory order, heights in metres cast to float64 as they are (NaN, infinities and values <= -1000 are unknown ground);
+        origin: the window corner in world metres.  Needs no scan and no combine.  A convenience route: map and poses are copied
+        to the device."""
+        gm = self._window_map("ground", ground, np.float64)
+        p = _rollout_poses(poses)
+        return self._score_attitude(-1, _ptr(gm), _ptr(p), p.shape[0], p.shape[1], 0, False, origin)
+
+    def score_attitude_of_device(self, ground_ptr, poses_ptr, K, T, origin=(0.0, 0.0)):
+        """The same for a map and poses in device memory: raw device addresses of xy_size*xy_size float64 (cell (x, y) at
+        [y*xy_size + x]) and K x T x 3 float32 (C-contiguous); the data must be ready when the call is made.  Enqueues and returns:
+        no host wait."""
+        if not ground_ptr or not poses_ptr:
+            raise ValueError("ground_ptr and poses_ptr must be device addresses")
+        K, T = _rollout_shape(K, T)
+        return self._score_attitude(-1, _dev(ground_ptr), _dev(poses_ptr), K, T, 1, False, origin)
 
     # ---- scan alignment scoring (an extension; include/gvom_hip.h "scan alignment scoring") ----
     def _score_alignments(self, cloud_ptr, n, tf_ptr, K, on_device, dilate, weights):

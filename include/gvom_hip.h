@@ -606,6 +606,81 @@ int gvom_score_rollouts(gvom_t *h, int64_t costfield_id, const uint16_t *cell_co
                         const float *poses /* [K][T][3] */, int64_t K, int64_t T, int on_device, const int64_t origin_cells[2],
                         int64_t *product_id);
 
+/* --- terrain attitude scoring (an extension: the off-road half of a sampling planner's inner loop -- how would the vehicle SIT on the
+ * ground at each pose: nose up or down, tilted sideways, high-centred on a crest) ----------------------------------------------------
+ * gvom_score_attitude scores, on the GPU, K trajectories of T poses each against ONE float64 ground map -- a device map set's height
+ * and inferred-height maps, or the caller's -- with the footprint table gvom_footprint_set gave the handle and the CHASSIS
+ * gvom_chassis_set gave it, and leaves the result in device memory as a product (kind GVOM_PRODUCT_ATTITUDE) that
+ * gvom_device_product_export / _release / _dlpack / _copy handle like the others.  gvom_get_tuning "attitude" (read-only): 1 -- how a
+ * caller probes a library for these entry points (an addition: GVOM_ABI_VERSION stays); "chassis" (read-only): 1 while a chassis is
+ * set.  Every float64 operation below is ONE IEEE operation in the order written, parentheses binding, no contraction; the library
+ * calls no trigonometric function (the caller supplies cos_sin): the result is exact, and every decision is made on the float32
+ * values that are stored, so a consumer can re-derive it from part 1.
+ *
+ * DEFINITION.  res = xy_resolution, xy = xy_size, o = origin_cells.
+ * GROUND     g, float64, cell (x, y) at [y*xy + x].  A cell is KNOWN iff g > -1000 && g < +inf (NaN, +-inf and exactly -1000 are
+ *            unknown).  map_set_id >= 0: a live device map set; g = height (map 4) where height > -1000, otherwise the inferred
+ *            height (map 5) if flags has GVOM_ATTITUDE_INFERRED_GROUND, else -1000; ground must be NULL.  map_set_id < 0: g is the
+ *            caller's ground, host or device memory as on_device says.
+ * POSES, CENTRE, HEADING, INVALID   those of rollout scoring above, word for word (the same s, H, rintf, the 2^30 and 2^24 bounds);
+ *            H is the footprint table's.  In addition fx = q - floor(q) with q = (double)x / res, and fy likewise: where in its
+ *            cell the pose lies.
+ * CHASSIS    front_axle > rear_axle (the axles' body x, metres; body frame: x forward, y left), track > 0, belly_height (the
+ *            belly above the wheels' contact plane), and cos_sin [H][2] = (cos, sin) of heading k's angle.  WHEELS FL, FR, RL, RR
+ *            have the body coordinates (a, b) = (front_axle, +track/2), (front_axle, -track/2), (rear_axle, +track/2),
+ *            (rear_axle, -track/2); at gvom_chassis_set, on the host, with (c, s) = cos_sin[k]: wx = a*c - b*s, wy = a*s + b*c,
+ *            kept per heading and wheel.  Wheel cell, per axis: floor(((double)x + wx) / res) - o; it is OUTSIDE the window if it
+ *            is not in [0, xy) or |quotient| < 2^30 does not hold.  z_i = g at that cell.
+ * ATTITUDE   zF = 0.5*(zFL + zFR), zR = 0.5*(zRL + zRR), zL = 0.5*(zFL + zRL), zT = 0.5*(zFR + zRR);
+ *            sp = (zF - zR) / (front_axle - rear_axle)   the pitch tangent, nose up positive;
+ *            sr = (zL - zT) / track                      the roll tangent, left side up positive;
+ *            z0 = 0.25*((zFL + zFR) + (zRL + zRR)), am = 0.5*(front_axle + rear_axle).
+ * BELLY      over the footprint cells (dx, dy) of heading k that lie inside the window and whose ground is known:
+ *            du = (((double)dx + 0.5) - fx) * res, dv likewise with dy and fy; u = du*c + dv*s, v = dv*c - du*s;
+ *            plane = (z0 + sp*(u - am)) + sr*v; clr = (plane + belly_height) - g; belly = the least clr, +inf where there is no
+ *            such cell.  (A clr that is NaN -- only heights whose sums overflow float64 make one -- is skipped.)
+ * STATUS     per pose, the first that applies: GVOM_ATTITUDE_INVALID; _LEFT_WINDOW: a wheel cell or a footprint cell is outside
+ *            the window; _UNKNOWN_GROUND: a wheel cell's ground is unknown; _PITCH: fabsf((float)sp) > max_pitch; _ROLL:
+ *            fabsf((float)sr) > max_roll; _BELLY: (float)belly < min_clearance; _OK.  An infinite limit disables its test.
+ * part 1 = float32 [K, T, 3] {(float)sp, (float)sr, (float)belly}; {0, 0, 0} where the status is INVALID, LEFT_WINDOW or
+ *            UNKNOWN_GROUND.  part 2 = uint8 [K, T], the pose status.
+ * part 0 = int32 [K, 5] {status, first_bad, steepest_pitch_pose, steepest_roll_pose, lowest_belly_pose}: first_bad = the smallest t
+ *            whose status is not OK, or T; status = that pose's, or OK; the three indices are the lowest t < first_bad with the
+ *            largest fabsf(pitch), the largest fabsf(roll) and the smallest belly (a NaN tangent ranks below every number), -1
+ *            when first_bad == 0.  Row i = rollout i.
+ *
+ * gvom_chassis_set computes the wheel table on the host, copies it and cos_sin to the device and returns after the copy; a later
+ * call replaces the chassis.  GVOM_ERR_INVALID: NULL arguments; n_headings outside 1 .. 1024; a non-finite length; front_axle <=
+ * rear_axle; track <= 0; a NaN limit; a cos_sin entry that is not finite or exceeds 1 in magnitude; a wheel offset that is not finite.
+ * gvom_score_attitude: on_device, staging, the snapshot, the pool (sized by K and T) and the limits are gvom_score_rollouts' -- read
+ * a map set id for the field id and ground for the map pointers.  It rebuilds the ground map of a map set in a grow-only buffer of
+ * the handle.  gvom_get_tuning "attitude_allocations" (read-only): device allocations the entry point has made on this handle (that
+ * buffer, the staging buffer of the host route and its product sets); it does not grow in steady state at a fixed K and T.
+ * gvom_device_product(GVOM_PRODUCT_ATTITUDE) is GVOM_ERR_INVALID (this call makes them).  Kind 13 is not assigned.
+ * GVOM_ERR_INVALID: a sharded handle; no footprint table set, no chassis set, or a chassis whose n_headings is not the table's; a set
+ * id AND a ground pointer, or neither; an unknown or stale set id; unknown flag bits; T outside 1 .. 4096; K < 1; NULL poses /
+ * origin_cells / product_id; an origin beyond 2^40 cells.  GVOM_ERR_CAPACITY: K * T > 2^26; xy_size > 4096; every set of the kind
+ * exported.
+ * NOT PROVIDED: suspension or tyre models; three-wheel contact (the plane is the least-squares one of four heights, not a stable
+ * stance); sharded handles; interpolation between poses. */
+#define GVOM_PRODUCT_ATTITUDE 14   /* part 0 int32 [K, 5] {status, first_bad, steepest pitch, steepest roll, lowest belly}; part 1 float32 [K, T, 3] {pitch, roll, belly}; part 2 uint8 [K, T] pose status */
+/* 13 stays unassigned: tests/align_layout_host_test.cpp holds 8, 9, 11 and 13 to "no such kind" */
+#define GVOM_ATTITUDE_OK 0
+#define GVOM_ATTITUDE_PITCH 1
+#define GVOM_ATTITUDE_ROLL 2
+#define GVOM_ATTITUDE_BELLY 3
+#define GVOM_ATTITUDE_UNKNOWN_GROUND 4
+#define GVOM_ATTITUDE_LEFT_WINDOW 5
+#define GVOM_ATTITUDE_INVALID 6
+#define GVOM_ATTITUDE_INFERRED_GROUND 1   /* flags: where the height is unknown, stand on the inferred height */
+typedef struct {
+    double front_axle, rear_axle, track, belly_height;   /* metres, body frame: x forward, y left */
+    float max_pitch, max_roll, min_clearance;            /* tangents, tangents, metres */
+} gvom_chassis_t;
+int gvom_chassis_set(gvom_t *h, const gvom_chassis_t *c, int32_t n_headings, const double *cos_sin /* [n_headings][2] */);
+int gvom_score_attitude(gvom_t *h, int64_t map_set_id, const double *ground, const float *poses /* [K][T][3] */, int64_t K, int64_t T,
+                        int on_device, int flags, const int64_t origin_cells[2], int64_t *product_id);
+
 /* --- scan alignment scoring (an extension: the inner loop of a correlative scan matcher -- does the pose a scan is about to be fused
  * at fit the map it is fused into) -------------------------------------------------------------------------------------------------
  * gvom_score_alignments holds, on the GPU, a float32 cloud of n returns under K candidate rigid transforms against the CURRENT fused
@@ -900,6 +975,7 @@ int gvom_host_timing(gvom_t *h, double us[8]);
  * "cost_to_go" / "cost_to_go_allocations" / "cost_to_go_tiles" (read-only), "cost_to_go_inner" / "cost_to_go_batch": see
  * "cost-to-go fields" above.
  * "rollouts" / "footprint" / "rollout_allocations" (read-only, gvom_get_tuning): see "rollout scoring" above.
+ * "attitude" / "chassis" / "attitude_allocations" (read-only, gvom_get_tuning): see "terrain attitude scoring" above.
  * "alignments" / "alignment_allocations" / "alignment_grid_bytes" / "alignment_points_per_block" / "alignment_candidate_group"
  * (read-only, gvom_get_tuning): see "scan alignment scoring" above.
  * (Test hooks are not part of this library: include/gvom_hip_test.h, lib/libgvom_hip_test.so.) */

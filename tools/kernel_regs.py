@@ -8,10 +8,10 @@ LLVM = "/opt/rocm/lib/llvm/bin"
 
 
 def kernels(lib):
-    """{mangled kernel name: {"vgpr", "sgpr", "scratch", "lds"}} over EVERY code object of the library (one offload bundle per
-    translation unit, behind one another in .hip_fatbin)."""
+    """{mangled kernel name: {"vgpr", "sgpr", "scratch", "lds", "code"}} over EVERY code object of the library (one offload bundle
+    per translation unit, behind one another in .hip_fatbin); "code" = the bytes of the kernel's function symbol."""
     magic = b"__CLANG_OFFLOAD_BUNDLE__"
-    notes = ""
+    notes, sizes = "", {}
     with tempfile.TemporaryDirectory() as t:
         fat = os.path.join(t, "fat.bin")
         subprocess.check_call([os.path.join(LLVM, "llvm-objcopy"), "--dump-section", ".hip_fatbin=" + fat, lib, os.path.join(t, "discard.so")])
@@ -25,6 +25,10 @@ def kernels(lib):
                                    "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--output=" + co])
             if os.path.getsize(co):
                 notes += subprocess.check_output([os.path.join(LLVM, "llvm-readelf"), "--notes", co]).decode() + "\n"
+                for row in subprocess.check_output([os.path.join(LLVM, "llvm-readelf"), "--symbols", "--wide", co]).decode().splitlines():
+                    f = row.split()                              # Num: Value Size Type Bind Vis Ndx Name
+                    if len(f) == 8 and f[3] == "FUNC":
+                        sizes[f[7]] = int(f[2], 0)
     out, cur = {}, None
     keys = {".private_segment_fixed_size": "scratch", ".vgpr_count": "vgpr", ".sgpr_count": "sgpr", ".group_segment_fixed_size": "lds"}
     block = {}
@@ -40,6 +44,8 @@ def kernels(lib):
             if k == ".name": block["name"] = v.strip()
             elif k in keys: block[keys[k]] = int(v)
     if "name" in block: out[block["name"]] = block
+    for name, b in out.items():
+        if name in sizes: b["code"] = sizes[name]
     return out
 
 
@@ -54,4 +60,4 @@ if __name__ == "__main__":
     for raw, nice in sorted(zip(ks, names), key=lambda p: p[1]):
         if pat.search(nice) and "vgpr" in ks[raw]:
             b = ks[raw]
-            print("%-70s vgpr %3d sgpr %3d scratch %3d lds %6d" % (nice.split("(")[0][:70], b.get("vgpr", -1), b.get("sgpr", -1), b.get("scratch", -1), b.get("lds", -1)))
+            print("%-70s vgpr %3d sgpr %3d scratch %3d lds %6d code %6d" % (nice.split("(")[0][:70], b.get("vgpr", -1), b.get("sgpr", -1), b.get("scratch", -1), b.get("lds", -1), b.get("code", -1)))

@@ -83,6 +83,12 @@ struct DevSet : SetShape {                     // (mem, xy, kind, zs, cap: gvom_
 #define CTG_CNT_RELAXED 16
 #define CTG_CNT_REACHED 32
 #define CTG_CNT_SEEDED 33
+#define GVOM_FRONTIER_MAX_CLUSTERS (1 << 20)
+// fr_work's counters (uint32): [r] tiles that flagged any in round r of the batch, [16 + r] tiles that ran, [32] frontier cells,
+// [33] kept clusters, [34] clusters dropped by min_cells, [35] frontier cells in kept clusters
+#define FR_CNT_RELAXED 16
+#define FR_CNT_CELLS 32
+#define FR_CNT_KEPT 33
 // DevSet::exports / rel* / orphan: a DLPack deleter runs on whatever thread frees the consumer's tensor, without the handle
 extern std::mutex g_set_mu;                               // (gvom_sets.hip)
 }  // namespace gvom_host
@@ -341,6 +347,15 @@ struct gvom_handle {
     // host cloud and transforms; al_allocs counts the device allocations the entry point has made on this handle (the two and its product sets)
     Buf al_grid, al_stage;
     int al_allocs = 0;
+    // FRONTIER EXTRACTION (gvom_frontiers): fr_work = 256 bytes of counters (FR_CNT_* above), the two halves of the tiles' activity
+    // flags, the block counts of the ranking, then the label and the count / rank arrays, int32 per cell each; fr_stage = the staging
+    // copy of a caller's host maps.  Each is allocated by the first call that needs it; fr_allocs counts those and the entry point's
+    // product sets (gvom_get_tuning "frontier_allocations").  fr_pin: the pinned copy of the counters the host loop reads.
+    Buf fr_work, fr_stage;
+    uint32_t *fr_pin = nullptr;
+    int fr_allocs = 0;
+    int tune_fr_inner = 0, tune_fr_batch = 0;           // gvom_set_tuning "frontier_inner" / "frontier_batch" (0: the defaults)
+    int fr_last_rounds = 0, fr_last_tiles = 0;          // of the last call (gvom_get_tuning "frontier_rounds" / "frontier_tiles")
 };
 
 namespace gvom_host {

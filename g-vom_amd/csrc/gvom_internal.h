@@ -370,6 +370,24 @@ struct AlignParams {
 size_t gvom_align_grid_bytes(int xy, int zs);
 hipError_t gvom_launch_align(hipStream_t s, const OccParams &F, const AlignParams &P, const int32_t *fstate, const uint32_t *ftags,
                              const float *cloud, const double *tf, uint32_t *grid, int32_t *counts, int32_t *best);
+// frontier extraction (gvom_frontier.hip; include/gvom_hip.h "frontier extraction" defines the result).  Every map is [y][x], xy x xy:
+// c uint16 cell costs, vis int32 visibility, D int32 cost to go (may be nullptr).  L and count are the two int32 work arrays of
+// xy*xy cells.  mark: L = own index at a frontier cell / 0xffffffff elsewhere, count = 0, flags[tile] = 1 where a tile
+// (gvom_frontier_tiles(xy)^2 of them, cleared by the caller) holds one, *n_frontier += frontier cells.  relax: one round, as
+// gvom_launch_ctg_relax.  rows: phase 0 initialises the cap rows of parts 0 and 1 (before finish).  finish: count, the ordered ranks
+// (bc: 2 * gvom_frontier_blocks(xy) words of scratch; totals[3] = {kept, dropped, cells in kept clusters}, cleared by the caller),
+// the cluster map, the rows' statistics, and part 3.
+int gvom_frontier_tiles(int xy);
+int gvom_frontier_blocks(int xy);
+hipError_t gvom_launch_frontier_mark(hipStream_t s, int xy, const uint16_t *c, const int32_t *vis, const int32_t *D, uint32_t *L,
+                                     uint32_t *count, uint32_t *flags, uint32_t *n_frontier);
+hipError_t gvom_launch_frontier_relax(hipStream_t s, int xy, uint32_t *L, uint32_t *fcur, uint32_t *fnext, uint32_t *activated,
+                                      uint32_t *relaxed, int inner);
+hipError_t gvom_launch_frontier_rows(hipStream_t s, int phase, int cap, int32_t *rows, int64_t *sums, const uint32_t *totals,
+                                     const uint32_t *n_frontier, int32_t *counts);
+hipError_t gvom_launch_frontier_finish(hipStream_t s, int xy, int32_t min_cells, int cap, const int32_t *D, const uint32_t *L, uint32_t *count,
+                                       uint32_t *bc, uint32_t *totals, const uint32_t *n_frontier, int32_t *rows, int64_t *sums,
+                                       int32_t *cmap, int32_t *counts);
 // storage order [sy][sx] -> reference order [x][y] (window coordinates)
 hipError_t gvom_launch_unwrap_f64(hipStream_t s, int xy, int om0, int om1, const double *in, int in_stride, double *out_xy);
 hipError_t gvom_launch_posdens(hipStream_t s, const Map2dParams &P, const int32_t *fstate,

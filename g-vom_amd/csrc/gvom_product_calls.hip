@@ -1,5 +1,5 @@
 // gvom_product_calls.hip -- the calls that MAKE a device product: gvom_device_product (occupancy grid, voxel cloud, the two height
-// clouds), gvom_clearance, gvom_raycast, gvom_cost_to_go, gvom_score_rollouts (with gvom_footprint_set, which sets its table), gvom_score_attitude (with gvom_chassis_set) and gvom_score_alignments, and the frame builders they and the debug reads (gvom_debug.hip) give
+// clouds), gvom_clearance, gvom_raycast, gvom_cost_to_go, gvom_score_rollouts (with gvom_footprint_set, which sets its table), gvom_score_attitude (with gvom_chassis_set), gvom_score_alignments and gvom_frontiers, and the frame builders they and the debug reads (gvom_debug.hip) give
 // the kernels.  Every call takes its set through product_acquire and hands it out through product_publish (gvom_sets.hip); what is
 // left in each body is what is particular to that product: its argument checks, its staging and its launches.
 #include "gvom_host.h"
@@ -86,6 +86,7 @@ VIS int gvom_device_product(gvom_t *h, int kind, int64_t max_rows, int64_t *prod
     if (kind == GVOM_PRODUCT_ROLLOUTS) { h->err = "gvom_device_product: rollouts are made by gvom_score_rollouts"; return GVOM_ERR_INVALID; }
     if (kind == GVOM_PRODUCT_ATTITUDE) { h->err = "gvom_device_product: attitude scores are made by gvom_score_attitude"; return GVOM_ERR_INVALID; }
     if (kind == GVOM_PRODUCT_ALIGNMENT) { h->err = "gvom_device_product: alignment scores are made by gvom_score_alignments"; return GVOM_ERR_INVALID; }
+    if (kind == GVOM_PRODUCT_FRONTIERS) { h->err = "gvom_device_product: frontiers are made by gvom_frontiers"; return GVOM_ERR_INVALID; }
     if (kind < 1 || kind > GVOM_N_PRODUCT_KINDS) { h->err = "gvom_device_product: unknown product kind"; return GVOM_ERR_INVALID; }
     if (h->sharded) { h->err = "gvom_device_product: sharded handles are not supported"; return GVOM_ERR_INVALID; }
     if (kind == GVOM_PRODUCT_VOXEL_CLOUD) stats_demand(h);                  // a read of the statistics, like gvom_debug_voxel_map
@@ -597,5 +598,103 @@ VIS int gvom_score_alignments(gvom_t *h, const float *cloud, int64_t n, const do
     HIPCHK(h, gvom_launch_align(h->stream, O, P, F.state, F.tags, cdev, tdev, (uint32_t *)h->al_grid.p, part_ptr<int32_t>(set, 0),
                                 part_ptr<int32_t>(set, 1)));
     return product_publish(h, set, product_id);
+}
+
+// ---- frontier extraction (gvom_frontiers) -----------------------------------------------------------------------------------------
+// The frontier cells of a cost map, clustered, ranked and summarised (gvom_frontier.hip), as a product of kind GVOM_PRODUCT_FRONTIERS
+// sized by the map and max_clusters.  The kernels run on the handle's stream behind whatever wrote the field and the map set they
+// read, and whatever recycles those later runs behind them.  Like gvom_cost_to_go this call WAITS: rounds of k_frontier_relax are
+// enqueued a batch at a time, the batch's per-round counters come back through pinned memory, and the first round that flagged no
+// tile ends the labelling (the rounds enqueued behind it found nothing to do).
+VIS int gvom_frontiers(gvom_t *h, int64_t costfield_id, int64_t map_set_id, const uint16_t *cell_cost, const int32_t *cost_to_go,
+                       const int32_t *visibility, int on_device, int32_t min_cells, int32_t max_clusters, int64_t *product_id, int64_t info[4])
+{
+    if (!h || !product_id) return GVOM_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(h->mu);
+    *product_id = -1;
+    for (int k = 0; info && k < 4; ++k) info[k] = 0;
+    if (h->sharded) { h->err = "gvom_frontiers: sharded handles are not supported"; return GVOM_ERR_INVALID; }
+    const bool ids = costfield_id >= 0 && map_set_id >= 0;
+    if ((costfield_id >= 0) != (map_set_id >= 0)) { h->err = "gvom_frontiers: the ids route needs a cost field id AND a map set id"; return GVOM_ERR_INVALID; }
+    if (ids && (cell_cost || cost_to_go || visibility)) { h->err = "gvom_frontiers: give the two ids or map pointers, not both"; return GVOM_ERR_INVALID; }
+    if (!ids && (!cell_cost || !visibility)) { h->err = "gvom_frontiers: give the two ids, or a cell-cost map and a visibility map"; return GVOM_ERR_INVALID; }
+    if (min_cells < 1) { h->err = "gvom_frontiers: min_cells must be at least 1"; return GVOM_ERR_INVALID; }
+    if (max_clusters < 1 || max_clusters > GVOM_FRONTIER_MAX_CLUSTERS) { h->err = "gvom_frontiers: max_clusters outside 1 .. 2^20"; return GVOM_ERR_INVALID; }
+    const int xy = h->prm.xy_size;
+    if (xy > GVOM_CLEARANCE_MAX_XY) { h->err = "gvom_frontiers: maps of more than 4096 cells a side are not supported"; return GVOM_ERR_CAPACITY; }
+    const size_t n2 = (size_t)xy * xy;
+    const uint16_t *c16 = cell_cost;
+    const int32_t *D = cost_to_go, *vis = visibility;
+    if (ids) {
+        DevSet *f = find_set(h->psets, costfield_id);
+        if (!f || f->kind != GVOM_PRODUCT_COSTFIELD) { h->err = "gvom_frontiers: unknown or stale cost field id"; return GVOM_ERR_INVALID; }
+        DevSet *m = find_set(h->dsets, map_set_id);
+        if (!m) { h->err = "unknown or stale device map set id"; return GVOM_ERR_INVALID; }
+        c16 = part_ptr<const uint16_t>(f, 2); D = part_ptr<const int32_t>(f, 0); vis = part_ptr<const int32_t>(m, 2);
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    DevSet *set = nullptr;
+    const size_t bytes = set_bytes(GVOM_PRODUCT_FRONTIERS, xy, 0, max_clusters);
+    int rc = product_acquire(h, GVOM_PRODUCT_FRONTIERS, bytes, bytes, "gvom_frontiers", &h->fr_allocs, &set);
+    if (rc) return rc;
+    set->cap = max_clusters;
+    const int nt = gvom_frontier_tiles(xy), ntiles = nt * nt, nb = gvom_frontier_blocks(xy);
+    const size_t flags_off = 256, bc_off = flags_off + align256((size_t)2 * ntiles * 4), L_off = bc_off + align256((size_t)2 * nb * 4),
+                 count_off = L_off + align256(n2 * 4);
+    if ((rc = stage_buf(h, h->fr_work, count_off + n2 * 4, h->fr_allocs))) return rc;
+    if (!h->fr_pin) HIPCHK(h, hipHostMalloc((void **)&h->fr_pin, 256, hipHostMallocDefault));
+    char *const w = (char *)h->fr_work.p;
+    uint32_t *cnt = (uint32_t *)w, *fl = (uint32_t *)(w + flags_off), *bc = (uint32_t *)(w + bc_off), *L = (uint32_t *)(w + L_off),
+             *count = (uint32_t *)(w + count_off);
+    HIPCHK(h, join_second_stream(h));
+    if (!ids && !on_device) {                                               // host maps: staged
+        const size_t cb = align256(n2 * 2), vb = align256(n2 * 4);
+        if ((rc = stage_buf(h, h->fr_stage, cb + vb + (cost_to_go ? n2 * 4 : 0), h->fr_allocs))) return rc;
+        char *st = (char *)h->fr_stage.p;
+        HIPCHK(h, hipMemcpyAsync(st, cell_cost, n2 * 2, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(st + cb, visibility, n2 * 4, hipMemcpyHostToDevice, h->stream));
+        if (cost_to_go) HIPCHK(h, hipMemcpyAsync(st + cb + vb, cost_to_go, n2 * 4, hipMemcpyHostToDevice, h->stream));
+        c16 = (const uint16_t *)st; vis = (const int32_t *)(st + cb); D = cost_to_go ? (const int32_t *)(st + cb + vb) : nullptr;
+    }
+    HIPCHK(h, hipMemsetAsync(w, 0, bc_off, h->stream));                     // the counters and both halves of the flags
+    if ((rc = set_wait_releases(h, set))) return rc;
+    int32_t *rows = part_ptr<int32_t>(set, 0);
+    int64_t *sums = part_ptr<int64_t>(set, 1);
+    HIPCHK(h, gvom_launch_frontier_rows(h->stream, 0, max_clusters, rows, sums, cnt + FR_CNT_KEPT, cnt + FR_CNT_CELLS, part_ptr<int32_t>(set, 3)));
+    HIPCHK(h, gvom_launch_frontier_mark(h->stream, xy, c16, vis, D, L, count, fl, cnt + FR_CNT_CELLS));
+    const int inner = h->tune_fr_inner > 0 ? h->tune_fr_inner : 256;
+    const int batch = h->tune_fr_batch > 0 ? h->tune_fr_batch : 8;
+    // labels only go down and there are n2 of them: a round that lowers none flags no tile, so fewer than n2 + 1 rounds lower one.
+    // The limit cannot be reached and only keeps this loop finite
+    const int64_t limit = (int64_t)n2 + 1;
+    int64_t rounds = 0, tiles = 0;
+    bool converged = false;
+    while (!converged && rounds < limit) {
+        const int nr = (int)std::min<int64_t>(batch, limit - rounds);
+        if (rounds) HIPCHK(h, hipMemsetAsync(cnt, 0, 2 * GVOM_CTG_MAX_BATCH * 4, h->stream));
+        for (int r = 0; r < nr; ++r) {
+            const int64_t k = rounds + r;
+            HIPCHK(h, gvom_launch_frontier_relax(h->stream, xy, L, fl + (k & 1) * ntiles, fl + ((k + 1) & 1) * ntiles, cnt + r,
+                                                 cnt + FR_CNT_RELAXED + r, inner));
+        }
+        HIPCHK(h, hipMemcpyAsync(h->fr_pin, cnt, 2 * GVOM_CTG_MAX_BATCH * 4, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        int ran = nr;
+        for (int r = 0; r < nr; ++r) {
+            tiles += h->fr_pin[FR_CNT_RELAXED + r];
+            if (h->fr_pin[r] == 0) { converged = true; ran = r + 1; break; }
+        }
+        rounds += ran;
+    }
+    if (!converged) { h->err = "gvom_frontiers: the labels did not settle"; return GVOM_ERR_HIP; }   // (the set keeps id -1: nobody gets it)
+    HIPCHK(h, gvom_launch_frontier_finish(h->stream, xy, min_cells, max_clusters, D, L, count, bc, cnt + FR_CNT_KEPT, cnt + FR_CNT_CELLS, rows, sums,
+                                          part_ptr<int32_t>(set, 2), part_ptr<int32_t>(set, 3)));
+    if ((rc = product_publish(h, set, product_id))) return rc;             // (`ready` goes in front of the counters' way back)
+    HIPCHK(h, hipMemcpyAsync(h->fr_pin, cnt, 256, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->fr_last_rounds = (int)std::min<int64_t>(rounds, INT32_MAX);
+    h->fr_last_tiles = (int)std::min<int64_t>(tiles, INT32_MAX);
+    if (info) { info[0] = rounds; info[1] = h->fr_pin[FR_CNT_KEPT]; info[2] = h->fr_pin[FR_CNT_CELLS]; info[3] = h->fr_pin[FR_CNT_KEPT + 1]; }
+    return GVOM_OK;
 }
 }  // extern "C"

@@ -19,6 +19,9 @@
 //   attitude (14)    cap x 5 int32 {status, first_bad, steepest_pitch_pose, steepest_roll_pose, lowest_belly_pose}, then cap x cols x 3
 //                    floats {pitch, roll, belly}, then cap x cols uint8 (pose status); cap = K and cols = T as for rollouts.  Kind 13
 //                    is not assigned
+//   frontiers (16)   cap x 8 int32 {label, cells, min x, min y, max x, max y, best cell, best D}, then cap x 2 int64 {sum x, sum y},
+//                    then xy*xy int32 (the cluster map, [y][x]), then 4 int32 {n_kept, frontier cells, those in kept clusters, cap};
+//                    cap = max_clusters of the call that wrote it.  Kind 15 is not assigned
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -57,6 +60,7 @@ inline size_t set_bytes(int kind, int xy, int zs, int64_t cap, int64_t cols = 0)
     case GVOM_PRODUCT_ROLLOUTS: return align256((size_t)cap * 16) + (size_t)cap * (size_t)cols * 2;
     case GVOM_PRODUCT_ALIGNMENT: return align256((size_t)cap * 24) + 16;
     case GVOM_PRODUCT_ATTITUDE: return align256((size_t)cap * 20) + align256((size_t)cap * (size_t)cols * 12) + (size_t)cap * (size_t)cols;
+    case GVOM_PRODUCT_FRONTIERS: return align256((size_t)cap * 32) + align256((size_t)cap * 16) + align256(n2 * 4) + 16;
     }
     return 0;
 }
@@ -128,6 +132,15 @@ inline bool set_part(const SetShape *s, int part, SetPart *d)
             d->strides[0] = s->cols * 3; d->strides[1] = 3; d->strides[2] = 1;
         }
         else if (part == 2) { rows(att + align256((size_t)s->cap * (size_t)s->cols * 12), s->cap, s->cols); d->code = kDLUInt; d->bits = 8; }
+        else return false;
+        break;
+    }
+    case GVOM_PRODUCT_FRONTIERS: {
+        char *const sums = s->mem + align256((size_t)s->cap * 32), *const cmap = sums + align256((size_t)s->cap * 16);
+        if (part == 0) { rows(s->mem, s->cap, 8); d->code = kDLInt; }
+        else if (part == 1) { rows(sums, s->cap, 2); d->code = kDLInt; d->bits = 64; }
+        else if (part == 2) { d->ptr = cmap; d->shape[0] = d->shape[1] = xy; d->strides[0] = 1; d->strides[1] = xy; d->code = kDLInt; }   // [x, y] indexing, column-major, like a device map
+        else if (part == 3) { d->ptr = cmap + align256((size_t)n2 * 4); d->ndim = 1; d->shape[0] = 4; d->strides[0] = 1; d->shape[1] = d->strides[1] = 1; d->code = kDLInt; }
         else return false;
         break;
     }

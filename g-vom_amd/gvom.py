@@ -167,6 +167,7 @@ ABI = [
     ("gvom_chassis_set", _I, [_P, _P, ctypes.c_int32, _P]),
     ("gvom_score_attitude", _I, [_P, _I64, _P, _P, _I64, _I64, _I, _I, ctypes.POINTER(_I64), ctypes.POINTER(_I64)]),
     ("gvom_score_alignments", _I, [_P, _P, _I64, _P, _I64, _I, _I, _P, ctypes.POINTER(_I64)]),
+    ("gvom_frontiers", _I, [_P, _I64, _I64, _P, _P, _P, _I, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(_I64), ctypes.POINTER(_I64)]),
     ("gvom_set_profiling", _I, [_P, _I]),
     ("gvom_host_timing", _I, [_P, ctypes.POINTER(ctypes.c_double * 8)]),
     ("gvom_set_tuning", _I, [_P, ctypes.c_char_p, _I]),
@@ -566,12 +567,14 @@ PRODUCT_COSTFIELD = 7                     # GVOM_PRODUCT_COSTFIELD: made by gvom
 PRODUCT_ROLLOUTS = 10                     # GVOM_PRODUCT_ROLLOUTS: made by gvom_score_rollouts (kinds 8 and 9 are not assigned)
 PRODUCT_ALIGNMENT = 12                    # GVOM_PRODUCT_ALIGNMENT: made by gvom_score_alignments (kind 11 is not assigned either)
 PRODUCT_ATTITUDE = 14                     # GVOM_PRODUCT_ATTITUDE: made by gvom_score_attitude (kind 13 is not assigned)
+PRODUCT_FRONTIERS = 16                    # GVOM_PRODUCT_FRONTIERS: made by gvom_frontiers (kind 15 is not assigned)
 # element type of part k of a product, by kind (what set_part() of csrc/gvom_setlayout.h gives as DLPack code and bits)
 _PRODUCT_DTYPES = {PRODUCT_OCCUPANCY: (np.uint8,), PRODUCT_VOXEL_CLOUD: (np.float32, np.float32, np.int64),
                    PRODUCT_HEIGHT_CLOUD: (np.float32,), PRODUCT_INFERRED_HEIGHT_CLOUD: (np.float32,),
                    PRODUCT_CLEARANCE: (np.float32, np.int32), PRODUCT_RAYCAST: (np.int32, np.float32),
                    PRODUCT_COSTFIELD: (np.int32, np.uint8, np.uint16), PRODUCT_ROLLOUTS: (np.int32, np.uint16),
-                   PRODUCT_ALIGNMENT: (np.int32, np.int32), PRODUCT_ATTITUDE: (np.int32, np.float32, np.uint8)}
+                   PRODUCT_ALIGNMENT: (np.int32, np.int32), PRODUCT_ATTITUDE: (np.int32, np.float32, np.uint8),
+                   PRODUCT_FRONTIERS: (np.int32, np.int64, np.int32, np.int32)}
 CLEARANCE_FAR = 2147483647                # GVOM_CLEARANCE_FAR: squared_cells where no obstacle is in reach
 _CLEARANCE_NO_NEGATIVE = 1                # GVOM_CLEARANCE_NO_NEGATIVE
 
@@ -859,6 +862,17 @@ class DeviceCostField(_ProductView):
     def copy_to_host(self):
         return self.cost.copy_to_host(), self.direction.copy_to_host(), self.cell_cost.copy_to_host()
 
+    def frontiers(self, device_maps, min_cells=4, max_clusters=1024):
+        """Where to explore next: the cells of this field that can be driven on (`.cell_cost` > 0), have been seen (`visibility` of
+        device_maps, a DeviceMaps, > 0), can be reached (`.cost` < CTG_UNREACHED: seed the field AT the vehicle, the graph is
+        undirected) and border never-seen ground, clustered under 8-connectivity on the GPU -- a DeviceFrontiers.  Clusters of fewer
+        than min_cells cells are dropped; the rows of at most max_clusters clusters are kept, in ascending order of their least
+        cell index.  The call waits for the labelling.  include/gvom_hip.h "frontier extraction" has the definition."""
+        g = self._hold._owner
+        if not isinstance(device_maps, DeviceMaps):
+            raise ValueError("frontiers takes the DeviceMaps whose visibility it reads, got %r" % (type(device_maps).__name__,))
+        return g._frontiers(self.product_id, device_maps.set_id, None, None, None, 0, min_cells, max_clusters, self.origin)
+
     def path_from(self, cell):
         """The cells from `cell` = (x, y) to a goal, both included, following `.direction` on a host copy (made once); None where
         the cell is unreached.  RuntimeError on CTG_UNSETTLED (a field that stopped before it converged)."""
@@ -1124,6 +1138,62 @@ class DeviceAttitude(_ProductView):
 
     def copy_to_host(self):
         return self.summary.copy_to_host(), self.attitude.copy_to_host(), self.status.copy_to_host()
+
+
+# ---- frontier extraction (DeviceCostField.frontiers, Gvom.frontiers_of and friends; include/gvom_hip.h "frontier extraction") ----
+FRONTIER_MAX_CLUSTERS = 1 << 20
+FRONTIER_NONE, FRONTIER_SMALL = -1, -2    # cluster map: no frontier cell; a frontier cell of a cluster below min_cells
+
+
+def _frontier_limits(min_cells, max_clusters):
+    try:
+        ok = int(min_cells) == min_cells and int(max_clusters) == max_clusters
+    except (TypeError, ValueError, OverflowError):
+        ok = False
+    if not ok or not 1 <= int(min_cells) < 2 ** 31:
+        raise ValueError("min_cells must be an integer >= 1, got %r" % (min_cells,))
+    if not 1 <= int(max_clusters) <= FRONTIER_MAX_CLUSTERS:
+        raise ValueError("max_clusters must be an integer in 1 .. 2**20, got %r" % (max_clusters,))
+    return int(min_cells), int(max_clusters)
+
+
+class DeviceFrontiers(_ProductView):
+    """The result of DeviceCostField.frontiers() / Gvom.frontiers_of() / frontiers_of_device(): `.clusters` int32 [cap, 8] -- per kept
+    cluster, in ascending label order, {label (its least cell index y * xy + x), cells, min x, min y, max x, max y, best cell (the
+    member with the least cost to go, on ties the lowest index), best D} --, `.sums` int64 [cap, 2] {sum x, sum y} (the centroid is
+    theirs divided by cells), `.cluster_map` int32 [xy, xy], [x, y]-indexed with strides (1, xy) like a DeviceMap (the cell's cluster
+    rank, FRONTIER_NONE where it is no frontier cell, FRONTIER_SMALL where its cluster is below min_cells) and `.counts` int32 [4]
+    {kept clusters, frontier cells, frontier cells in kept clusters, cap}: four DeviceArrays of one product.  Rows from
+    min(n_clusters, cap) on are zero.  `.rounds`, `.n_clusters` (kept clusters, also those beyond cap), `.frontier_cells` and
+    `.dropped` (clusters below min_cells) describe the call; `.origin` is the window corner in world metres.  A snapshot: later
+    scans, combines and solves do not change it.  copy_to_host() returns (clusters, sums, cluster_map, counts) as numpy."""
+
+    def __init__(self, hold, info, xy_resolution, origin=(0.0, 0.0)):
+        _ProductView.__init__(self, hold)
+        self.clusters, self.sums, self.cluster_map, self.counts = (DeviceArray(hold, k) for k in range(4))
+        self.rounds, self.n_clusters, self.frontier_cells, self.dropped = int(info[0]), int(info[1]), int(info[2]), int(info[3])
+        self.origin = np.array(origin, np.float64)
+        self._res = float(xy_resolution)
+
+    def copy_to_host(self):
+        return self.clusters.copy_to_host(), self.sums.copy_to_host(), self.cluster_map.copy_to_host(), self.counts.copy_to_host()
+
+    def goals(self, order="cost"):
+        """Exploration goals on the host: (best, centroid, rows) -- float64 [n, 2] world metres (x, y) of the centre of each kept
+        cluster's best cell and of its centroid, and the int64 [n] rows of `.clusters` they come from; n = min(n_clusters, cap).
+        order="cost": the cheapest to reach first (best D ascending, then label); "size": the largest first (cells descending, then
+        label)."""
+        if order not in ("cost", "size"):
+            raise ValueError('order must be "cost" or "size", got %r' % (order,))
+        n = min(self.n_clusters, self.clusters.shape[0])
+        rows, sums = self.clusters.copy_to_host()[:n].astype(np.int64), self.sums.copy_to_host()[:n]
+        xy = self.cluster_map.shape[0]
+        key = rows[:, 7] if order == "cost" else -rows[:, 1]
+        pick = np.lexsort((rows[:, 0], key))
+        oc = np.round(self.origin[:2] / self._res)
+        best = np.stack([rows[:, 6] % xy, rows[:, 6] // xy], axis=1).astype(np.float64)
+        centroid = sums.astype(np.float64) / np.maximum(rows[:, 1:2], 1)
+        return ((best + oc + 0.5) * self._res)[pick], ((centroid + oc + 0.5) * self._res)[pick], pick
 
 
 ALIGN_MAX_POINTS = 1 << 20
@@ -1956,6 +2026,32 @@ class Gvom(object):
             raise ValueError("ground_ptr and poses_ptr must be device addresses")
         K, T = _rollout_shape(K, T)
         return self._score_attitude(-1, _dev(ground_ptr), _dev(poses_ptr), K, T, 1, False, origin)
+
+    # ---- frontier extraction (an extension; include/gvom_hip.h "frontier extraction") ----
+    def _frontiers(self, field_id, set_id, cost_ptr, ctg_ptr, vis_ptr, on_device, min_cells, max_clusters, origin):
+        min_cells, max_clusters = _frontier_limits(min_cells, max_clusters)
+        info = (_I64 * 4)()
+        hold = self._make_product(lambda pid: self._lib.gvom_frontiers(
+            self._h, int(field_id), int(set_id), cost_ptr, ctg_ptr, vis_ptr, int(on_device), min_cells, max_clusters, pid, info),
+            PRODUCT_FRONTIERS, self._check_args)
+        return DeviceFrontiers(hold, list(info), self.xy_resolution, origin)
+
+    def frontiers_of(self, cell_cost, visibility, cost_to_go=None, min_cells=4, max_clusters=1024, origin=(0.0, 0.0)):
+        """DeviceCostField.frontiers() of maps of the caller's: cell_cost a numpy [x, y] array of shape (xy_size, xy_size) in any
+        memory order, whole numbers in 0 .. 65535 (0 = blocked); visibility int32 of the same shape (> 0: seen); cost_to_go
+        (optional) int32 of the same shape -- without it every seen, unblocked cell counts as reachable.  Needs no scan and no
+        combine.  A convenience route: the maps are copied to the device.  origin: the window corner in world metres."""
+        cc = self._window_map("cell_cost", cell_cost, np.uint16, (0, 65535))
+        vis = self._window_map("visibility", visibility, np.int32, (-2 ** 31, 2 ** 31 - 1))
+        ctg = self._window_map("cost_to_go", cost_to_go, np.int32, (-2 ** 31, 2 ** 31 - 1), optional=True)
+        return self._frontiers(-1, -1, _ptr(cc), _ptr(ctg), _ptr(vis), 0, min_cells, max_clusters, origin)
+
+    def frontiers_of_device(self, cell_cost_ptr, visibility_ptr, cost_to_go_ptr=None, min_cells=4, max_clusters=1024, origin=(0.0, 0.0)):
+        """The same for maps in device memory: raw device addresses of xy_size*xy_size uint16, int32 and, optionally, int32 (cell
+        (x, y) at [y*xy_size + x]); the data must be ready when the call is made."""
+        if not cell_cost_ptr or not visibility_ptr:
+            raise ValueError("cell_cost_ptr and visibility_ptr must be device addresses")
+        return self._frontiers(-1, -1, _dev(cell_cost_ptr), _dev(cost_to_go_ptr), _dev(visibility_ptr), 1, min_cells, max_clusters, origin)
 
     # ---- scan alignment scoring (an extension; include/gvom_hip.h "scan alignment scoring") ----
     def _score_alignments(self, cloud_ptr, n, tf_ptr, K, on_device, dilate, weights):

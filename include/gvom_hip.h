@@ -728,6 +728,60 @@ int gvom_score_attitude(gvom_t *h, int64_t map_set_id, const double *ground, con
 int gvom_score_alignments(gvom_t *h, const float *cloud /* [n][3] */, int64_t n, const double *transforms /* [K][3][4] */, int64_t K,
                           int on_device, int dilate, const int32_t weights[5], int64_t *product_id);
 
+/* --- frontier extraction (an extension: where to go next when nobody supplies a goal -- the boundary between ground that has been
+ * seen and can be driven on, and ground that has never been seen) -------------------------------------------------------------------
+ * gvom_frontiers finds, on the GPU, the frontier cells of a cost map, clusters them, and leaves per cluster its size, box, nearest
+ * member and coordinate sums in device memory as a product (kind GVOM_PRODUCT_FRONTIERS) that gvom_device_product_export / _release /
+ * _dlpack / _copy handle like the others.  gvom_get_tuning "frontiers" (read-only): 1 -- how a caller probes a library for this entry
+ * point (an addition: GVOM_ABI_VERSION stays).  All arithmetic is integer: the result is exact and does not depend on scheduling.
+ *
+ * DEFINITION.  Three maps of xy_size * xy_size cells, cell (x, y) at [y*xy_size + x]:
+ *   c    uint16 cell cost, 0 = blocked, as part 2 of a cost field;
+ *   vis  int32 visibility, as map 2 of a map set; a cell is KNOWN iff vis > 0;
+ *   D    int32 cost to go; it may be absent.  The graph of a cost field is undirected: a field seeded AT the vehicle holds the
+ *        travel cost TO every cell.
+ * FRONTIER CELL u: c[u] > 0, and vis[u] > 0, and at least one of its four edge neighbours lies inside the window and has vis == 0,
+ *            and, where D is given, D[u] < GVOM_CTG_UNREACHED.  Cells outside the window are not unknown.
+ * CLUSTER    a connected component of the frontier cells under 8-connectivity.  Its LABEL is the smallest linear index
+ *            y*xy_size + x among its members.
+ * KEPT       clusters are those with at least min_cells members (min_cells >= 1).  Their RANK is their position in ascending label
+ *            order, 0 .. n_kept - 1.
+ * PER KEPT CLUSTER of rank r < cap, cap = max_clusters: label; cells; min x, min y, max x, max y; best cell and best D -- the member
+ *            with the least D, on ties the lowest index: one unsigned 64-bit minimum over ((uint32)D << 32) | index; without D, best
+ *            D = GVOM_CTG_UNREACHED and the best cell is the label --; sum x, sum y as int64 (the centroid is theirs divided by
+ *            cells; the caller divides).  Clusters of rank >= cap are dropped from the rows and still counted.
+ * part 0 = int32 [cap, 8] {label, cells, min x, min y, max x, max y, best cell, best D}; part 1 = int64 [cap, 2] {sum x, sum y};
+ * part 2 = int32 [xy, xy], the cluster map, [x, y]-indexed with strides (1, xy) like a device map: the rank of the cell's cluster
+ * (also for ranks >= cap), -1 where the cell is no frontier cell, -2 where it is one of a cluster below min_cells; part 3 = int32 [4]
+ * {n_kept, frontier cells, frontier cells in kept clusters, cap}.  Rows >= min(n_kept, cap) of parts 0 and 1 are zero.
+ *
+ * INPUT, one of two.  costfield_id >= 0 AND map_set_id >= 0: a live GVOM_PRODUCT_COSTFIELD, whose part 2 is c and whose part 0 is D,
+ * and a live device map set, whose map 2 is vis; the three pointers must be NULL; the kernels run on the handle's stream behind
+ * whatever wrote the field and the set.  Both ids < 0: cell_cost and visibility are required, cost_to_go is optional; on_device != 0:
+ * device addresses, read in place (the data must be ready when the call is made); on_device == 0: host arrays, staged through a
+ * buffer of the handle.
+ * Like gvom_cost_to_go, THIS CALL WAITS: it returns once the labels have converged.  Rounds of label relaxation over 32 x 32 tiles
+ * are enqueued a batch at a time ("frontier_batch", gvom_set_tuning: rounds between two looks at the counters, 1 .. 16, 0 = 8;
+ * "frontier_inner": sweeps a tile makes at most per round, 0 = 256; both change the time, never the result); the first round that
+ * flags no tile ends the labelling.  Labels only go down, so it ends; the call additionally gives up with GVOM_ERR_HIP after
+ * xy_size * xy_size + 1 rounds, which cannot be reached.  There is no max_rounds: a stopped labelling has labels that are not roots,
+ * and its pieces are not well defined.
+ * info (may be NULL): {rounds run, n_kept, frontier cells, clusters dropped by min_cells}.
+ * The product is a snapshot: later scans, combines and solves do not change it.  Products of this kind live in the product-set pool
+ * ("device_product_sets"), sized by the map and max_clusters: at most GVOM_MAX_PRODUCT_SETS, GVOM_ERR_CAPACITY beyond; an unexported
+ * one goes back to the pool with the next call.  "frontier_allocations" (read-only): device allocations the entry point has made on
+ * this handle (its work buffer of 8 bytes per cell plus flags and counters, the staging buffer of the host route and its product
+ * sets); it does not grow in steady state.  "frontier_rounds" / "frontier_tiles" (read-only): rounds and tile relaxations of the last
+ * call.  gvom_device_product(GVOM_PRODUCT_FRONTIERS) is GVOM_ERR_INVALID (this call makes them).  Kinds 8, 9, 11, 13 and 15 are not
+ * assigned.
+ * GVOM_ERR_INVALID: a sharded handle; ids and pointers mixed, or neither; only one of the two ids; a stale id; min_cells < 1;
+ * max_clusters outside 1 .. 2^20; NULL product_id.  GVOM_ERR_CAPACITY: xy_size > 4096; every set of the kind exported.
+ * NOT PROVIDED: 4-connected clusters; the window edge as a frontier; frontiers in 3-D; splitting of long clusters; a
+ * distance-to-robot filter other than reachability; sharded handles; an early stop. */
+#define GVOM_PRODUCT_FRONTIERS 16   /* part 0 int32 [cap, 8]; part 1 int64 [cap, 2] {sum x, sum y}; part 2 int32 [xy, xy] cluster map; part 3 int32 [4] */
+int gvom_frontiers(gvom_t *h, int64_t costfield_id, int64_t map_set_id, const uint16_t *cell_cost, const int32_t *cost_to_go /* may be NULL */,
+                   const int32_t *visibility, int on_device, int32_t min_cells, int32_t max_clusters, int64_t *product_id, int64_t info[4]);
+
 /* --- one map sharded over the GPUs of a node (one rank = one process = one GPU) -------------------
  * No counterpart in the reference (it has no multi-GPU path); semantics = SURVEY 8(e):
  * the rays are data-parallel, the per-voxel accumulators (hit / total: int32 sum, min-height: f32 min)

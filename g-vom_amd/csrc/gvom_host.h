@@ -84,6 +84,10 @@ struct DevSet : SetShape {                     // (mem, xy, kind, zs, cap: gvom_
 #define CTG_CNT_REACHED 32
 #define CTG_CNT_SEEDED 33
 #define GVOM_FRONTIER_MAX_CLUSTERS (1 << 20)
+#define GVOM_VIEWPOINT_MAX_POSES 65536
+#define GVOM_VIEWPOINT_MAX_BEAMS ((int64_t)1 << 22)
+#define GVOM_VIEWPOINT_DEFAULT_MB 256
+#define GVOM_VIEWPOINT_MAX_MB 4096
 // fr_work's counters (uint32): [r] tiles that flagged any in round r of the batch, [16 + r] tiles that ran, [32] frontier cells,
 // [33] kept clusters, [34] clusters dropped by min_cells, [35] frontier cells in kept clusters
 #define FR_CNT_RELAXED 16
@@ -356,6 +360,15 @@ struct gvom_handle {
     int fr_allocs = 0;
     int tune_fr_inner = 0, tune_fr_batch = 0;           // gvom_set_tuning "frontier_inner" / "frontier_batch" (0: the defaults)
     int fr_last_rounds = 0, fr_last_tiles = 0;          // of the last call (gvom_get_tuning "frontier_rounds" / "frontier_tiles")
+    // VIEWPOINT SCORING (gvom_score_viewpoints): vp_bitmaps = one bitmap of the window's voxels per viewpoint of a batch, cleared on the
+    // stream before every batch; at most tune_vp_mb megabytes ("viewpoint_bitmap_mb"; a bitmap that alone is larger makes batches of
+    // one).  vp_stage = the staging copy of a caller's host poses.  Each is allocated by the first call that needs it; vp_allocs counts
+    // those and the entry point's product sets (gvom_get_tuning "viewpoint_allocations"); vp_last_batch: viewpoints per launch of the
+    // last call ("viewpoint_batch", read-only)
+    Buf vp_bitmaps, vp_stage;
+    int vp_allocs = 0;
+    int tune_vp_mb = GVOM_VIEWPOINT_DEFAULT_MB;
+    int vp_last_batch = 0;
 };
 
 namespace gvom_host {

@@ -132,6 +132,26 @@ struct RayQuery {
     uint32_t cap;             // xy_size + z_size: no ray takes more steps inside the window (ray_steps' cap)
 };
 
+// viewpoint scoring (gvom_score_viewpoints, gvom_viewpoint.hip): K sensor poses, the selected beams h = 0, stride_h, .. < H and
+// w = 0, stride_w, .. < W of the handle's sensor model, walked like RayQuery's segments through the fused map of a ScanParams
+struct ViewQuery {
+    const double *poses;      // device, [K][12]: rows 0..2 of the sensor-to-world matrices
+    const double *dir, *off;  // device, [H*W][3] each: the sensor model
+    double   max_range;
+    int      W;               // columns of the model
+    int      stride_h, stride_w;
+    int      nh, nw;          // selected rows and columns
+    int      nwc;             // waves per selected row: ceil(nw / 64)
+    int      nb;              // nh * nw
+    int      K;
+    int      k0;              // first viewpoint of the launch (its blockIdx.y = 0)
+    int      unknown_blocks;  // GVOM_RAY_UNKNOWN_BLOCKS
+    int      lit;             // as RayQuery::lit
+    uint32_t cap;             // as RayQuery::cap
+    uint32_t bm_words;        // 32-bit words from one viewpoint's bitmap to the next (>= ceil(xy*xy*zs / 32))
+};
+#define GVOM_VIEWPOINT_MAX_BATCH 32768   // viewpoints per launch (the grid's y extent)
+
 #define GVOM_PACK_CHUNK 64     // quads per k_pack workgroup
 #define GVOM_BASE_PITCH 16     // doubles per row of a scan's own-voxel moments (10 used): one 128-byte block per row
 // rank exchange, owner side: received quads of all source ranks are unpacked by one launch
@@ -388,6 +408,14 @@ hipError_t gvom_launch_frontier_rows(hipStream_t s, int phase, int cap, int32_t 
 hipError_t gvom_launch_frontier_finish(hipStream_t s, int xy, int32_t min_cells, int cap, const int32_t *D, const uint32_t *L, uint32_t *count,
                                        uint32_t *bc, uint32_t *totals, const uint32_t *n_frontier, int32_t *rows, int64_t *sums,
                                        int32_t *cmap, int32_t *counts);
+// viewpoint scoring (gvom_viewpoint.hip; include/gvom_hip.h "viewpoint scoring" defines the result).  viewpoints: the `batch`
+// viewpoints from Q.k0 on; bitmaps = batch x Q.bm_words words, CLEARED by the caller; rows = part 0, int32 [K][8], cleared by the
+// caller before the first batch (columns 1 .. 7 are added to).  best: behind the last batch; column 0 of every row, the rows of
+// invalid poses, and part 1.
+hipError_t gvom_launch_viewpoints(hipStream_t s, const ScanParams &P, const ViewQuery &Q, int batch, const int32_t *fstate, const uint32_t *ftags,
+                                  uint32_t *bitmaps, int32_t *rows);
+hipError_t gvom_launch_viewpoint_best(hipStream_t s, const ScanParams &P, const ViewQuery &Q, const int32_t *fstate, const uint32_t *ftags,
+                                      int32_t *rows, int32_t *best);
 // storage order [sy][sx] -> reference order [x][y] (window coordinates)
 hipError_t gvom_launch_unwrap_f64(hipStream_t s, int xy, int om0, int om1, const double *in, int in_stride, double *out_xy);
 hipError_t gvom_launch_posdens(hipStream_t s, const Map2dParams &P, const int32_t *fstate,

@@ -1,5 +1,5 @@
 // gvom_product_calls.hip -- the calls that MAKE a device product: gvom_device_product (occupancy grid, voxel cloud, the two height
-// clouds), gvom_clearance, gvom_raycast, gvom_cost_to_go, gvom_score_rollouts (with gvom_footprint_set, which sets its table), gvom_score_attitude (with gvom_chassis_set), gvom_score_alignments and gvom_frontiers, and the frame builders they and the debug reads (gvom_debug.hip) give
+// clouds), gvom_clearance, gvom_raycast, gvom_cost_to_go, gvom_score_rollouts (with gvom_footprint_set, which sets its table), gvom_score_attitude (with gvom_chassis_set), gvom_score_alignments, gvom_frontiers and gvom_score_viewpoints, and the frame builders they and the debug reads (gvom_debug.hip) give
 // the kernels.  Every call takes its set through product_acquire and hands it out through product_publish (gvom_sets.hip); what is
 // left in each body is what is particular to that product: its argument checks, its staging and its launches.
 #include "gvom_host.h"
@@ -87,6 +87,7 @@ VIS int gvom_device_product(gvom_t *h, int kind, int64_t max_rows, int64_t *prod
     if (kind == GVOM_PRODUCT_ATTITUDE) { h->err = "gvom_device_product: attitude scores are made by gvom_score_attitude"; return GVOM_ERR_INVALID; }
     if (kind == GVOM_PRODUCT_ALIGNMENT) { h->err = "gvom_device_product: alignment scores are made by gvom_score_alignments"; return GVOM_ERR_INVALID; }
     if (kind == GVOM_PRODUCT_FRONTIERS) { h->err = "gvom_device_product: frontiers are made by gvom_frontiers"; return GVOM_ERR_INVALID; }
+    if (kind == GVOM_PRODUCT_VIEWPOINTS) { h->err = "gvom_device_product: viewpoint scores are made by gvom_score_viewpoints"; return GVOM_ERR_INVALID; }
     if (kind < 1 || kind > GVOM_N_PRODUCT_KINDS) { h->err = "gvom_device_product: unknown product kind"; return GVOM_ERR_INVALID; }
     if (h->sharded) { h->err = "gvom_device_product: sharded handles are not supported"; return GVOM_ERR_INVALID; }
     if (kind == GVOM_PRODUCT_VOXEL_CLOUD) stats_demand(h);                  // a read of the statistics, like gvom_debug_voxel_map
@@ -695,6 +696,82 @@ VIS int gvom_frontiers(gvom_t *h, int64_t costfield_id, int64_t map_set_id, cons
     h->fr_last_rounds = (int)std::min<int64_t>(rounds, INT32_MAX);
     h->fr_last_tiles = (int)std::min<int64_t>(tiles, INT32_MAX);
     if (info) { info[0] = rounds; info[1] = h->fr_pin[FR_CNT_KEPT]; info[2] = h->fr_pin[FR_CNT_CELLS]; info[3] = h->fr_pin[FR_CNT_KEPT + 1]; }
+    return GVOM_OK;
+}
+
+// ---- viewpoint scoring (gvom_score_viewpoints) -------------------------------------------------------------------------------------
+// The selected beams of the handle's sensor model cast from K poses through the CURRENT fused map (gvom_viewpoint.hip), read-only, on
+// the handle's stream behind whatever produced that map; the result is a product of kind GVOM_PRODUCT_VIEWPOINTS sized by K.  The
+// viewpoints are walked a batch at a time -- as many as have their bitmaps in "viewpoint_bitmap_mb" megabytes --, the bitmaps cleared
+// on the stream in front of every batch; the kernel boundary orders the batches.  Enqueues and returns.  gvom_sensor_model_set drains
+// the stream under this mutex before it replaces the model: no kernel of an earlier call reads a model that is being overwritten.
+VIS int gvom_score_viewpoints(gvom_t *h, const double *poses, int64_t K, int on_device, double max_range, int32_t stride_h, int32_t stride_w,
+                              int flags, double origin_voxels[3], int64_t *product_id)
+{
+    if (!h || !product_id) return GVOM_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(h->mu);
+    *product_id = -1;
+    if (h->sharded) { h->err = "gvom_score_viewpoints: sharded handles are not supported"; return GVOM_ERR_INVALID; }
+    if (!poses) { h->err = "gvom_score_viewpoints: poses must not be NULL"; return GVOM_ERR_INVALID; }
+    if (h->ri_H <= 0) { h->err = "gvom_score_viewpoints: no sensor model (gvom_sensor_model_set)"; return GVOM_ERR_INVALID; }
+    if (K < 1) { h->err = "gvom_score_viewpoints: K must be at least 1"; return GVOM_ERR_INVALID; }
+    if (stride_h < 1 || stride_w < 1) { h->err = "gvom_score_viewpoints: the beam strides must be at least 1"; return GVOM_ERR_INVALID; }
+    if (!std::isfinite(max_range) || !(max_range > 0.0)) { h->err = "gvom_score_viewpoints: max_range must be finite and > 0"; return GVOM_ERR_INVALID; }
+    if (flags & ~GVOM_RAY_UNKNOWN_BLOCKS) { h->err = "gvom_score_viewpoints: unknown flag bits"; return GVOM_ERR_INVALID; }
+    if (K > GVOM_VIEWPOINT_MAX_POSES) { h->err = "gvom_score_viewpoints: more than 65536 viewpoints in one call"; return GVOM_ERR_CAPACITY; }
+    const int xy = h->prm.xy_size, zs = h->prm.z_size;
+    const int64_t nh = ((int64_t)h->ri_H + stride_h - 1) / stride_h, nw = ((int64_t)h->ri_W + stride_w - 1) / stride_w, nb = nh * nw;
+    if (nb > GVOM_VIEWPOINT_MAX_BEAMS) { h->err = "gvom_score_viewpoints: more than 2^22 selected beams"; return GVOM_ERR_CAPACITY; }
+    if (nb * ((int64_t)xy + zs + 1) >= ((int64_t)1 << 31)) { h->err = "gvom_score_viewpoints: beams x (xy_size + z_size + 1) reaches 2^31"; return GVOM_ERR_CAPACITY; }
+    const int64_t V = (int64_t)xy * xy * zs;
+    if (V >= ((int64_t)1 << 31)) { h->err = "gvom_score_viewpoints: the window has 2^31 voxels or more"; return GVOM_ERR_CAPACITY; }
+    if (!h->has_combined) return GVOM_NO_DATA;
+    HIPCHK(h, hipSetDevice(h->device));
+    DevSet *set = nullptr;
+    const size_t bytes = set_bytes(GVOM_PRODUCT_VIEWPOINTS, 0, 0, K);
+    int rc = product_acquire(h, GVOM_PRODUCT_VIEWPOINTS, bytes, bytes, "gvom_score_viewpoints", &h->vp_allocs, &set);
+    if (rc) return rc;
+    set->cap = K;
+    const size_t bm_words = (((size_t)V + 31) / 32 + 63) & ~(size_t)63, bm_bytes = bm_words * 4;       // whole 256-byte lines
+    int64_t batch = (int64_t)(((size_t)h->tune_vp_mb << 20) / bm_bytes);
+    batch = std::max<int64_t>(1, std::min<int64_t>(batch, std::min<int64_t>(K, GVOM_VIEWPOINT_MAX_BATCH)));
+    if ((rc = stage_buf(h, h->vp_bitmaps, (size_t)batch * bm_bytes, h->vp_allocs))) return rc;
+    const Fused &F = h->fused[h->cur];
+    ScanParams P;
+    RayQuery R;
+    memset(&R, 0, sizeof R);
+    raycast_params(h, F, P, R);
+    ViewQuery Q;
+    memset(&Q, 0, sizeof Q);
+    Q.poses = poses;
+    Q.dir = (const double *)h->ri_model.p; Q.off = Q.dir + (size_t)h->ri_H * h->ri_W * 3;
+    Q.max_range = max_range;
+    Q.W = h->ri_W; Q.stride_h = stride_h; Q.stride_w = stride_w;
+    Q.nh = (int)nh; Q.nw = (int)nw; Q.nwc = (int)((nw + 63) / 64); Q.nb = (int)nb; Q.K = (int)K;
+    Q.unknown_blocks = (flags & GVOM_RAY_UNKNOWN_BLOCKS) ? 1 : 0;
+    Q.lit = R.lit; Q.cap = R.cap; Q.bm_words = (uint32_t)bm_words;
+    HIPCHK(h, join_second_stream(h));
+    if (!on_device) {                                                       // host poses: staged, and up before the call returns
+        const size_t pb = (size_t)K * 96;
+        if ((rc = stage_buf(h, h->vp_stage, pb, h->vp_allocs))) return rc;
+        HIPCHK(h, hipMemcpyAsync(h->vp_stage.p, poses, pb, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        Q.poses = (const double *)h->vp_stage.p;
+    }
+    if ((rc = set_wait_releases(h, set))) return rc;
+    int32_t *rows = part_ptr<int32_t>(set, 0);
+    HIPCHK(h, hipMemsetAsync(rows, 0, (size_t)K * 32, h->stream));
+    for (int64_t k0 = 0; k0 < K; k0 += batch) {
+        const int nk = (int)std::min<int64_t>(batch, K - k0);
+        Q.k0 = (int)k0;
+        HIPCHK(h, hipMemsetAsync(h->vp_bitmaps.p, 0, (size_t)nk * bm_bytes, h->stream));
+        HIPCHK(h, gvom_launch_viewpoints(h->stream, P, Q, nk, F.state, F.tags, (uint32_t *)h->vp_bitmaps.p, rows));
+    }
+    Q.k0 = 0;
+    HIPCHK(h, gvom_launch_viewpoint_best(h->stream, P, Q, F.state, F.tags, rows, part_ptr<int32_t>(set, 1)));
+    h->vp_last_batch = (int)batch;
+    if ((rc = product_publish(h, set, product_id))) return rc;
+    for (int k = 0; origin_voxels && k < 3; ++k) origin_voxels[k] = (double)F.origin[k];
     return GVOM_OK;
 }
 }  // extern "C"

@@ -22,6 +22,8 @@
 //   frontiers (16)   cap x 8 int32 {label, cells, min x, min y, max x, max y, best cell, best D}, then cap x 2 int64 {sum x, sum y},
 //                    then xy*xy int32 (the cluster map, [y][x]), then 4 int32 {n_kept, frontier cells, those in kept clusters, cap};
 //                    cap = max_clusters of the call that wrote it.  Kind 15 is not assigned
+//   viewpoints (18)  cap x 8 int32 {status, gain, visits, beams OCCUPIED, CLEAR, LEFT_WINDOW, UNKNOWN, INVALID}, then 4 int32 {best
+//                    index, its gain, K, beams per viewpoint}; cap = the viewpoints K of the call that wrote it.  Kind 17 is not assigned
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -61,6 +63,7 @@ inline size_t set_bytes(int kind, int xy, int zs, int64_t cap, int64_t cols = 0)
     case GVOM_PRODUCT_ALIGNMENT: return align256((size_t)cap * 24) + 16;
     case GVOM_PRODUCT_ATTITUDE: return align256((size_t)cap * 20) + align256((size_t)cap * (size_t)cols * 12) + (size_t)cap * (size_t)cols;
     case GVOM_PRODUCT_FRONTIERS: return align256((size_t)cap * 32) + align256((size_t)cap * 16) + align256(n2 * 4) + 16;
+    case GVOM_PRODUCT_VIEWPOINTS: return align256((size_t)cap * 32) + 16;
     }
     return 0;
 }
@@ -144,6 +147,11 @@ inline bool set_part(const SetShape *s, int part, SetPart *d)
         else return false;
         break;
     }
+    case GVOM_PRODUCT_VIEWPOINTS:
+        if (part == 0) { rows(s->mem, s->cap, 8); d->code = kDLInt; }
+        else if (part == 1) { d->ptr = s->mem + align256((size_t)s->cap * 32); d->ndim = 1; d->shape[0] = 4; d->strides[0] = 1; d->shape[1] = d->strides[1] = 1; d->code = kDLInt; }
+        else return false;
+        break;
     default: return false;
     }
     d->bytes = (size_t)(d->shape[0] * d->shape[1] * d->shape[2]) * (d->bits / 8);

@@ -168,6 +168,7 @@ ABI = [
     ("gvom_score_attitude", _I, [_P, _I64, _P, _P, _I64, _I64, _I, _I, ctypes.POINTER(_I64), ctypes.POINTER(_I64)]),
     ("gvom_score_alignments", _I, [_P, _P, _I64, _P, _I64, _I, _I, _P, ctypes.POINTER(_I64)]),
     ("gvom_frontiers", _I, [_P, _I64, _I64, _P, _P, _P, _I, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(_I64), ctypes.POINTER(_I64)]),
+    ("gvom_score_viewpoints", _I, [_P, _P, _I64, _I, ctypes.c_double, ctypes.c_int32, ctypes.c_int32, _I, _P, ctypes.POINTER(_I64)]),
     ("gvom_set_profiling", _I, [_P, _I]),
     ("gvom_host_timing", _I, [_P, ctypes.POINTER(ctypes.c_double * 8)]),
     ("gvom_set_tuning", _I, [_P, ctypes.c_char_p, _I]),
@@ -568,13 +569,14 @@ PRODUCT_ROLLOUTS = 10                     # GVOM_PRODUCT_ROLLOUTS: made by gvom_
 PRODUCT_ALIGNMENT = 12                    # GVOM_PRODUCT_ALIGNMENT: made by gvom_score_alignments (kind 11 is not assigned either)
 PRODUCT_ATTITUDE = 14                     # GVOM_PRODUCT_ATTITUDE: made by gvom_score_attitude (kind 13 is not assigned)
 PRODUCT_FRONTIERS = 16                    # GVOM_PRODUCT_FRONTIERS: made by gvom_frontiers (kind 15 is not assigned)
+PRODUCT_VIEWPOINTS = 18                   # GVOM_PRODUCT_VIEWPOINTS: made by gvom_score_viewpoints (kind 17 is not assigned)
 # element type of part k of a product, by kind (what set_part() of csrc/gvom_setlayout.h gives as DLPack code and bits)
 _PRODUCT_DTYPES = {PRODUCT_OCCUPANCY: (np.uint8,), PRODUCT_VOXEL_CLOUD: (np.float32, np.float32, np.int64),
                    PRODUCT_HEIGHT_CLOUD: (np.float32,), PRODUCT_INFERRED_HEIGHT_CLOUD: (np.float32,),
                    PRODUCT_CLEARANCE: (np.float32, np.int32), PRODUCT_RAYCAST: (np.int32, np.float32),
                    PRODUCT_COSTFIELD: (np.int32, np.uint8, np.uint16), PRODUCT_ROLLOUTS: (np.int32, np.uint16),
                    PRODUCT_ALIGNMENT: (np.int32, np.int32), PRODUCT_ATTITUDE: (np.int32, np.float32, np.uint8),
-                   PRODUCT_FRONTIERS: (np.int32, np.int64, np.int32, np.int32)}
+                   PRODUCT_FRONTIERS: (np.int32, np.int64, np.int32, np.int32), PRODUCT_VIEWPOINTS: (np.int32, np.int32)}
 CLEARANCE_FAR = 2147483647                # GVOM_CLEARANCE_FAR: squared_cells where no obstacle is in reach
 _CLEARANCE_NO_NEGATIVE = 1                # GVOM_CLEARANCE_NO_NEGATIVE
 
@@ -1194,6 +1196,103 @@ class DeviceFrontiers(_ProductView):
         best = np.stack([rows[:, 6] % xy, rows[:, 6] // xy], axis=1).astype(np.float64)
         centroid = sums.astype(np.float64) / np.maximum(rows[:, 1:2], 1)
         return ((best + oc + 0.5) * self._res)[pick], ((centroid + oc + 0.5) * self._res)[pick], pick
+
+
+# ---- viewpoint scoring (Gvom.score_viewpoints and friends; include/gvom_hip.h "viewpoint scoring") ----
+VIEWPOINT_MAX_POSES = 65536
+VIEWPOINT_MAX_BEAMS = 1 << 22
+
+
+def _viewpoint_poses(poses):
+    """poses float64 (K, 4, 4), (K, 3, 4), (4, 4) or (3, 4) -> C-contiguous float64 (K, 3, 4): rows 0..2"""
+    a = np.asarray(poses)
+    if a.dtype != np.float64:
+        raise TypeError("poses must be float64, got %s" % a.dtype)
+    if a.ndim == 2:
+        a = a[None]
+    if a.ndim != 3 or a.shape[1:] not in ((4, 4), (3, 4)) or a.shape[0] < 1:
+        raise ValueError("poses must have shape (K, 4, 4) or (K, 3, 4) with K >= 1, or be one such matrix, got %r" % (a.shape,))
+    return np.ascontiguousarray(a[:, :3, :])
+
+
+def _viewpoint_options(K, max_range, beam_stride):
+    try:
+        ok = int(K) == K and not isinstance(K, bool)
+    except (TypeError, ValueError, OverflowError):
+        ok = False
+    if not ok or not 1 <= int(K) <= VIEWPOINT_MAX_POSES:
+        raise ValueError("viewpoint scoring needs 1 .. 65536 poses, got K = %r" % (K,))
+    try:
+        r = float(max_range)
+    except (TypeError, ValueError):
+        r = float("nan")
+    if not (math.isfinite(r) and r > 0.0):
+        raise ValueError("max_range must be finite and > 0, got %r" % (max_range,))
+    try:
+        sh, sw = beam_stride
+        ok = int(sh) == sh and int(sw) == sw and 1 <= int(sh) < 2 ** 31 and 1 <= int(sw) < 2 ** 31
+    except (TypeError, ValueError, OverflowError):
+        ok = False
+    if not ok:
+        raise ValueError("beam_stride must be two integers >= 1 (rows, columns), got %r" % (beam_stride,))
+    return int(K), r, int(sh), int(sw)
+
+
+def viewpoint_poses(points_xyz, yaws, sensor_to_body=None):
+    """Candidate sensor poses for Gvom.score_viewpoints: float64 [len(points) * len(yaws), 4, 4], sensor to world.  Pose
+    k = i * len(yaws) + j puts the BODY at points_xyz[i] (world metres; with the `best` of DeviceFrontiers.goals() and a sensor height:
+    np.column_stack([best, np.full(len(best), z)])) turned by yaws[j] about the vertical: B = [[c, -s, 0, x], [s, c, 0, y],
+    [0, 0, 1, z], [0, 0, 0, 1]] with c = math.cos(yaw), s = math.sin(yaw), and is B itself without sensor_to_body, else
+    B.dot(sensor_to_body) (numpy's float64 matrix product of the two 4x4; sensor_to_body: the sensor's pose in the body frame).
+    INDEX ORDER: the yaw is the fastest index."""
+    pts = np.asarray(points_xyz, np.float64)
+    if pts.ndim == 1:
+        pts = pts[None]
+    if pts.ndim != 2 or pts.shape[1] != 3:
+        raise ValueError("points_xyz must have shape (n, 3), got %r" % (pts.shape,))
+    yw = np.asarray(yaws, np.float64).reshape(-1)
+    S = None
+    if sensor_to_body is not None:
+        S = np.asarray(sensor_to_body, np.float64)
+        if S.shape != (4, 4):
+            raise ValueError("sensor_to_body must be a 4x4 matrix, got shape %r" % (S.shape,))
+    if pts.shape[0] * yw.shape[0] > VIEWPOINT_MAX_POSES:
+        raise ValueError("more than 65536 poses: %d" % (pts.shape[0] * yw.shape[0]))
+    out = np.empty((pts.shape[0], yw.shape[0], 4, 4), np.float64)
+    for i in range(pts.shape[0]):
+        for j in range(yw.shape[0]):
+            c, s = math.cos(float(yw[j])), math.sin(float(yw[j]))
+            B = np.identity(4)
+            B[0, 0], B[0, 1], B[1, 0], B[1, 1] = c, -s, s, c
+            B[:3, 3] = pts[i]
+            out[i, j] = B if S is None else B.dot(S)
+    return out.reshape(-1, 4, 4)
+
+
+class DeviceViewpoints(_ProductView):
+    """The result of Gvom.score_viewpoints() / score_viewpoints_device(): `.rows` int32 [K, 8] -- per pose {status of the pose's own
+    voxel (RAY_*), gain (DISTINCT never-observed voxels its beams examined), visits (the same with multiplicity), beams that ended
+    RAY_OCCUPIED, RAY_CLEAR, RAY_LEFT_WINDOW, RAY_UNKNOWN, RAY_INVALID} -- and `.best` int32 [4] {best index (the lowest of the
+    largest gain among the poses whose own voxel is observed free; -1 where there is none), its gain, K, beams per pose}: two
+    DeviceArrays of one product, row k = pose k.  `.origin`: the fused map's window origin in voxels when the call was made.  A
+    snapshot: later scans and combines do not change it.  copy_to_host() returns (rows, best) as numpy."""
+
+    def __init__(self, hold, origin, poses=None):
+        _ProductView.__init__(self, hold)
+        self.origin = origin
+        self._poses = poses
+        self.rows, self.best = DeviceArray(hold, 0), DeviceArray(hold, 1)
+
+    def copy_to_host(self):
+        return self.rows.copy_to_host(), self.best.copy_to_host()
+
+    def best_pose(self):
+        """(index, gain, pose) of the best viewpoint -- pose: float64 [3, 4], rows 0..2 of the matrix handed to score_viewpoints()
+        (None on the device route, which keeps no host copy) --, or None where no pose lies in an observed-free voxel."""
+        k, gain = (int(v) for v in self.best.copy_to_host()[:2])
+        if k < 0:
+            return None
+        return k, gain, (None if self._poses is None else self._poses[k].copy())
 
 
 ALIGN_MAX_POINTS = 1 << 20
@@ -2052,6 +2151,34 @@ class Gvom(object):
         if not cell_cost_ptr or not visibility_ptr:
             raise ValueError("cell_cost_ptr and visibility_ptr must be device addresses")
         return self._frontiers(-1, -1, _dev(cell_cost_ptr), _dev(cost_to_go_ptr), _dev(visibility_ptr), 1, min_cells, max_clusters, origin)
+
+    # ---- viewpoint scoring (an extension; include/gvom_hip.h "viewpoint scoring") ----
+    def _score_viewpoints(self, poses_ptr, K, on_device, max_range, beam_stride, unknown_blocks, host_poses=None):
+        K, r, sh, sw = _viewpoint_options(K, max_range, beam_stride)
+        org = (ctypes.c_double * 3)()
+        flags = _RAY_UNKNOWN_BLOCKS if unknown_blocks else 0
+        hold = self._make_product(lambda pid: self._lib.gvom_score_viewpoints(self._h, poses_ptr, K, int(on_device), r, sh, sw, flags,
+                                                                              org, pid), PRODUCT_VIEWPOINTS, self._check_args)
+        return None if hold is None else DeviceViewpoints(hold, np.array(list(org), np.float64), host_poses)
+
+    def score_viewpoints(self, poses, max_range, beam_stride=(1, 1), unknown_blocks=False):
+        """Next-best-view scoring on the GPU: puts the sensor whose model set_sensor_model() holds at each of K poses and casts its
+        beams, max_range metres long, through the current fused map with raycast()'s ray rule -- a DeviceViewpoints: per pose how
+        many DISTINCT never-observed voxels the beams pass before they stop (gain), the same counted once per beam (visits), how the
+        beams ended, whether the pose itself lies in an observed-free voxel, and the best such pose.  poses: float64 (K, 4, 4) or
+        (K, 3, 4), sensor to world (viewpoint_poses() builds them from points and yaws), or one matrix; beam_stride = (rows,
+        columns): every how-manyth beam of the model is cast; unknown_blocks=True: a beam stops at the first never-observed voxel.
+        Every beam starts at the pose's translation.  Read-only: the map does not change.  None before the first combine.  A
+        convenience route: the poses are copied to the device."""
+        t = _viewpoint_poses(poses)
+        return self._score_viewpoints(_ptr(t), t.shape[0], 0, max_range, beam_stride, unknown_blocks, t)
+
+    def score_viewpoints_device(self, poses_ptr, K, max_range, beam_stride=(1, 1), unknown_blocks=False):
+        """The same for poses in device memory: the raw device address of K x 3 x 4 float64 (rows 0..2 of each matrix,
+        C-contiguous; the data must be ready when the call is made).  Enqueues and returns: no host wait."""
+        if not poses_ptr:
+            raise ValueError("poses_ptr must be a device address")
+        return self._score_viewpoints(_dev(poses_ptr), K, 1, max_range, beam_stride, unknown_blocks)
 
     # ---- scan alignment scoring (an extension; include/gvom_hip.h "scan alignment scoring") ----
     def _score_alignments(self, cloud_ptr, n, tf_ptr, K, on_device, dilate, weights):

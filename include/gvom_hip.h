@@ -782,6 +782,64 @@ int gvom_score_alignments(gvom_t *h, const float *cloud /* [n][3] */, int64_t n,
 int gvom_frontiers(gvom_t *h, int64_t costfield_id, int64_t map_set_id, const uint16_t *cell_cost, const int32_t *cost_to_go /* may be NULL */,
                    const int32_t *visibility, int on_device, int32_t min_cells, int32_t max_clusters, int64_t *product_id, int64_t info[4]);
 
+/* --- viewpoint scoring (an extension: the next-best-view question of an exploration stack -- put my sensor at this pose, with its
+ * real beam pattern: how many voxels that nobody has observed would its beams pass before they hit something) ----------------------
+ * gvom_score_viewpoints casts the selected beams of the handle's sensor model (gvom_sensor_model_set) from K poses through the CURRENT
+ * fused map on the GPU (k_viewpoints, k_viewpoint_best), with gvom_raycast's ray rule, and leaves per pose the number of DISTINCT
+ * never-observed voxels the beams examined, the same with multiplicity, and how the beams ended, in device memory as a product (kind
+ * GVOM_PRODUCT_VIEWPOINTS) that gvom_device_product_export / _release / _dlpack / _copy handle like the others.  Read-only on the map.
+ * gvom_get_tuning "viewpoints" (read-only): 1 -- how a caller probes a library for this entry point (an addition: GVOM_ABI_VERSION
+ * stays).
+ *
+ * POSES.  poses [K][12]: rows 0..2 of the 4x4 sensor-to-world matrices, row-major, float64.  on_device == 0: host memory, copied
+ * through a staging buffer of the handle before the call returns; on_device != 0: a device address, read in place (the data must be
+ * ready when the call is made).  The call ENQUEUES on the handle's stream behind whatever produced the current fused map and returns
+ * (no host wait on the device route); later scans and combines are ordered behind the kernels and do not change the product, which is
+ * a snapshot; a sensor model that replaces another is ordered behind the calls that read the old one.  origin_voxels (may be NULL)
+ * receives the fused map's window origin W in voxels.
+ * BEAMS.  Of the model's H x W pixels the selected ones are h = 0, stride_h, 2*stride_h, .. < H and w = 0, stride_w, .. < W; nb is
+ * their number, ceil(H / stride_h) * ceil(W / stride_w).  The model's range gate and range scale play no part.
+ *
+ * DEFINITION, per viewpoint k with matrix C = poses[k] and selected pixel i = h*W + w.  float64, every operation rounded once, in this
+ * order, no FMA -- the arithmetic of "range images" above with r = max_range:
+ *     p[c] = max_range * dir[i][c] + off[i][c]                               c = 0, 1, 2
+ *     q[c] = ((p[0]*C[4c] + p[1]*C[4c+1]) + p[2]*C[4c+2]) + C[4c+3]
+ *     b[c] = (float)q[c];   a[c] = (float)C[4c+3]                            one origin per viewpoint: the pose's translation
+ * The ray a -> b is walked exactly as gvom_raycast walks the segment a -> b ("ray queries" above: the same set-up, step count S,
+ * three float32 additions per step, window lookup, a stale tile reads never observed, the handle's sqrt typing), with
+ * GVOM_RAY_UNKNOWN_BLOCKS if `flags` has it and never with GVOM_RAY_CHECK_TARGET.  A beam with a non-finite component in a or b is
+ * INVALID, as gvom_raycast's ray is.
+ * part 0 = int32 [K, 8], row k:
+ *     0  status   a GVOM_RAY_* code for the origin's own voxel v[c] = floor((double)a[c] / res[c] - W[c]): CLEAR observed free,
+ *                 OCCUPIED, UNKNOWN never observed (a stale tile included), LEFT_WINDOW outside the window; INVALID: an entry of
+ *                 C is not finite, and then every other column is 0 except column 7 = nb
+ *     1  gain     the number of DISTINCT window voxels whose fused state is never-observed (-1) and that at least one beam of k
+ *                 examined (the voxel that stops a beam under GVOM_RAY_UNKNOWN_BLOCKS included)
+ *     2  visits   the sum over the beams of gvom_raycast's `unknown` column: the same voxels, with multiplicity
+ *     3 .. 7      beams that ended OCCUPIED, CLEAR, LEFT_WINDOW, UNKNOWN (only with the flag), INVALID; they sum to nb
+ * part 1 = int32 [4] {best, gain[best], K, nb}: best = the lowest index of the largest gain among the rows whose status is CLEAR;
+ * -1 and gain 0 where no row is CLEAR.
+ * All results are integers; integer sums and bit-ORs commute: the product does not depend on scheduling.  Deduplication: one bitmap
+ * of the window's voxels per viewpoint (bit x + y*xy + z*xy*xy), an atomic OR per examined never-observed voxel; the beam that finds
+ * the bit clear counts the voxel.  The bitmaps live in a grow-only work buffer of the handle of at most "viewpoint_bitmap_mb"
+ * megabytes (gvom_set_tuning / gvom_get_tuning; default 256, 0 .. 4096, a negative value restores the default): a call walks
+ * B = max(1, that / the bytes of one bitmap) viewpoints per launch (at most 32768; "viewpoint_batch", read-only: B of the last call)
+ * and clears the bitmaps in front of every launch.  The setting changes the time and the memory, never the result.
+ *
+ * GVOM_NO_DATA before the first combine.  GVOM_ERR_INVALID: a sharded handle; no sensor model; K < 1; a stride < 1; max_range not
+ * finite or <= 0; NULL poses / product_id; unknown flag bits.  GVOM_ERR_CAPACITY: K > 65536; nb > 2^22;
+ * nb * (xy_size + z_size + 1) >= 2^31 (visits cannot overflow); a window of 2^31 voxels or more; every set of the kind exported.
+ * Products of this kind live in the product-set pool ("device_product_sets"), sized by K: at most GVOM_MAX_PRODUCT_SETS; an
+ * unexported one goes back to the pool with the next call.  "viewpoint_allocations" (read-only): device allocations the entry point
+ * has made on this handle (the bitmaps, the staging buffer of the host route and its product sets); it does not grow in steady state.
+ * gvom_device_product(GVOM_PRODUCT_VIEWPOINTS) is GVOM_ERR_INVALID (this call makes them).  Kind 17 is not assigned, like 8, 9, 11, 13
+ * and 15.
+ * NOT PROVIDED: per-beam results (that is gvom_raycast); a per-beam origin from `off` (off moves the beam's end, every beam starts at
+ * the pose's translation); range weighting of the gain; a 2-D cell gain; sharded handles. */
+#define GVOM_PRODUCT_VIEWPOINTS 18   /* part 0 int32 [K, 8] {status, gain, visits, beams OCCUPIED, CLEAR, LEFT_WINDOW, UNKNOWN, INVALID}; part 1 int32 [4] {best, its gain, K, nb} */
+int gvom_score_viewpoints(gvom_t *h, const double *poses /* [K][12] */, int64_t K, int on_device, double max_range,
+                          int32_t stride_h, int32_t stride_w, int flags, double origin_voxels[3], int64_t *product_id);
+
 /* --- one map sharded over the GPUs of a node (one rank = one process = one GPU) -------------------
  * No counterpart in the reference (it has no multi-GPU path); semantics = SURVEY 8(e):
  * the rays are data-parallel, the per-voxel accumulators (hit / total: int32 sum, min-height: f32 min)
@@ -1032,6 +1090,8 @@ int gvom_host_timing(gvom_t *h, double us[8]);
  * "attitude" / "chassis" / "attitude_allocations" (read-only, gvom_get_tuning): see "terrain attitude scoring" above.
  * "alignments" / "alignment_allocations" / "alignment_grid_bytes" / "alignment_points_per_block" / "alignment_candidate_group"
  * (read-only, gvom_get_tuning): see "scan alignment scoring" above.
+ * "viewpoints" / "viewpoint_allocations" / "viewpoint_batch" (read-only, gvom_get_tuning), "viewpoint_bitmap_mb": see "viewpoint
+ * scoring" above.
  * (Test hooks are not part of this library: include/gvom_hip_test.h, lib/libgvom_hip_test.so.) */
 int gvom_set_tuning(gvom_t *h, const char *name, int value);
 /* The value the LAST scan ran with ("segs", "period", "ep_row", "prio", "interleave": what automatic resolved to).

@@ -448,7 +448,7 @@ VIS void gvom_destroy(gvom_t *h)
     if (h->x_host) hipHostFree(h->x_host);
     for (auto &s : h->slots) { hipFree(s.state); hipFree(s.code16); hipFree(s.tags); fb(s.crows); fb(s.metrics); fb(s.base); fb(s.rowvox); }
     for (auto &f : h->fused) { hipFree(f.state); hipFree(f.tags); fb(f.rows); fb(f.metrics); }
-    fb(h->in_pts); fb(h->cl_g); fb(h->cl_stage); fb(h->rq_stage); fb(h->ctg_work); fb(h->ctg_stage); fb(h->ctg_clr); fb(h->fp_tab); fb(h->ro_stage); fb(h->at_tab); fb(h->at_ground); fb(h->at_stage); fb(h->al_grid); fb(h->al_stage); fb(h->fr_work); fb(h->fr_stage); fb(h->vp_bitmaps); fb(h->vp_stage); if (h->fr_pin) hipHostFree(h->fr_pin); if (h->ctg_pin) hipHostFree(h->ctg_pin); fb(h->ri_model); fb(h->ri_raw); fb(h->ri_poses); if (h->ri_poses_pin) hipHostFree(h->ri_poses_pin); fb(h->mo_dev); if (h->mo_pin) hipHostFree(h->mo_pin); fb(h->world_pts[0]); fb(h->world_pts[1]); fb(h->flink[0]); fb(h->flink[1]); fb(h->tl); fb(h->dir_keys); fb(h->dir_perm); hipFree(h->dir_hist);
+    fb(h->in_pts); fb(h->cl_g); fb(h->cl_stage); fb(h->rq_stage); fb(h->ctg_work); fb(h->ctg_stage); fb(h->ctg_clr); fb(h->fp_tab); fb(h->ro_stage); fb(h->at_tab); fb(h->at_ground); fb(h->at_stage); fb(h->al_grid); fb(h->al_stage); fb(h->fr_work); fb(h->fr_stage); fb(h->vp_bitmaps); fb(h->vp_stage); fb(h->pf_tab); fb(h->pf_work); fb(h->pf_stage); if (h->pf_pin) hipHostFree(h->pf_pin); if (h->fr_pin) hipHostFree(h->fr_pin); if (h->ctg_pin) hipHostFree(h->ctg_pin); fb(h->ri_model); fb(h->ri_raw); fb(h->ri_poses); if (h->ri_poses_pin) hipHostFree(h->ri_poses_pin); fb(h->mo_dev); if (h->mo_pin) hipHostFree(h->mo_pin); fb(h->world_pts[0]); fb(h->world_pts[1]); fb(h->flink[0]); fb(h->flink[1]); fb(h->tl); fb(h->dir_keys); fb(h->dir_perm); hipFree(h->dir_hist);
     hipFree(h->counters); if (h->counters_host) hipHostFree(h->counters_host);
     hipFree(h->descs_dev); if (h->descs_host) hipHostFree(h->descs_host);
     hipFree(h->blockcounts); hipFree(h->blockcounts2); hipFree(h->hmaps2);
@@ -540,6 +540,8 @@ VIS int gvom_set_tuning(gvom_t *h, const char *name, int value)
     else if (!strcmp(name, "cost_to_go_batch")) h->tune_ctg_batch = value < 0 ? 0 : (value > GVOM_CTG_MAX_BATCH ? GVOM_CTG_MAX_BATCH : value);   // rounds per look at the counters (0: 8)
     else if (!strcmp(name, "frontier_inner")) h->tune_fr_inner = value < 0 ? 0 : value;        // sweeps a tile makes at most per round (0: 256)
     else if (!strcmp(name, "frontier_batch")) h->tune_fr_batch = value < 0 ? 0 : (value > GVOM_CTG_MAX_BATCH ? GVOM_CTG_MAX_BATCH : value);   // rounds per look at the counters (0: 8)
+    else if (!strcmp(name, "pose_field_inner")) h->tune_pf_inner = value < 0 ? 0 : value;      // sweeps a tile makes at most per round (0: 64)
+    else if (!strcmp(name, "pose_field_batch")) h->tune_pf_batch = value < 0 ? 0 : (value > GVOM_CTG_MAX_BATCH ? GVOM_CTG_MAX_BATCH : value);   // rounds per look at the counters (0: 8)
     else if (!strcmp(name, "viewpoint_bitmap_mb")) h->tune_vp_mb = value < 0 ? GVOM_VIEWPOINT_DEFAULT_MB : (value > GVOM_VIEWPOINT_MAX_MB ? GVOM_VIEWPOINT_MAX_MB : value);   // megabytes of bitmaps per launch (0: one viewpoint per launch; < 0: the default, 256)
     else if (!strcmp(name, "occupancy_clear")) h->tune_occ_clear = value;   // k_occupancy: 1 = clear the grid first, write live tile columns only
     else if (!strcmp(name, "exported")) h->exported = value != 0;       // (set by the peer transport, gvom_comm.hip)
@@ -592,6 +594,13 @@ VIS int gvom_get_tuning(gvom_t *h, const char *name, int *value)
     if (!strcmp(name, "viewpoint_allocations")) { *value = h->vp_allocs; return GVOM_OK; }              // read-only: device allocations gvom_score_viewpoints has made
     if (!strcmp(name, "viewpoint_batch")) { *value = h->vp_last_batch; return GVOM_OK; }                // read-only: viewpoints per launch of the last gvom_score_viewpoints
     if (!strcmp(name, "viewpoint_bitmap_mb")) { *value = h->tune_vp_mb; return GVOM_OK; }
+    if (!strcmp(name, "pose_field")) { *value = 1; return GVOM_OK; }                                    // read-only: the library has gvom_pose_field
+    if (!strcmp(name, "primitives")) { *value = h->pf_H > 0 ? 1 : 0; return GVOM_OK; }                  // read-only: a primitive table is set
+    if (!strcmp(name, "pose_field_allocations")) { *value = h->pf_allocs; return GVOM_OK; }             // read-only: device allocations gvom_primitives_set / gvom_pose_field have made
+    if (!strcmp(name, "pose_field_rounds")) { *value = h->pf_last_rounds; return GVOM_OK; }             // read-only: rounds of the last gvom_pose_field
+    if (!strcmp(name, "pose_field_tiles")) { *value = h->pf_last_tiles; return GVOM_OK; }               // read-only: tile relaxations of the last gvom_pose_field
+    if (!strcmp(name, "pose_field_inner")) { *value = h->tune_pf_inner; return GVOM_OK; }
+    if (!strcmp(name, "pose_field_batch")) { *value = h->tune_pf_batch; return GVOM_OK; }
     if (!strcmp(name, "alignment_allocations")) { *value = h->al_allocs; return GVOM_OK; }              // read-only: device allocations gvom_score_alignments has made
     if (!strcmp(name, "alignment_grid_bytes")) { *value = (int)(h->al_grid.bytes > 0x7fffffffu ? 0x7fffffffu : h->al_grid.bytes); return GVOM_OK; }   // read-only: the class grid's allocation
     if (!strcmp(name, "alignment_points_per_block")) { *value = GVOM_ALIGN_PTS_BLOCK; return GVOM_OK; }  // read-only: returns per k_align_score workgroup

@@ -369,6 +369,19 @@ struct gvom_handle {
     int vp_allocs = 0;
     int tune_vp_mb = GVOM_VIEWPOINT_DEFAULT_MB;
     int vp_last_batch = 0;
+    // POSE FIELDS (gvom_primitives_set / gvom_pose_field): pf_tab = the primitive table in device memory -- start[H + 1] int32, then at
+    // pf_prims_at bytes (a multiple of 256) the primitives, 8 bytes each (int16 dx, dy, h_to, w) --, pf_H its headings (0: none set) and
+    // pf_R its largest |dx|, |dy|: the halo of a tile.  pf_work = 256 bytes of counters (CTG_CNT_* above), the two halves of the tiles'
+    // activity flags, the staged goals (65536 x 3 int32), then the uint16 cost map converted from a caller's int32 one; pf_stage = the
+    // staging copy of a caller's host cost map.  Each is allocated by the first call that needs it; pf_allocs counts those and the entry
+    // point's product sets (gvom_get_tuning "pose_field_allocations").  pf_pin: the pinned copy of the counters the host loop reads.
+    Buf pf_tab, pf_work, pf_stage;
+    size_t pf_prims_at = 0;
+    int pf_H = 0, pf_R = 0;
+    uint32_t *pf_pin = nullptr;
+    int pf_allocs = 0;
+    int tune_pf_inner = 0, tune_pf_batch = 0;           // gvom_set_tuning "pose_field_inner" / "pose_field_batch" (0: the defaults)
+    int pf_last_rounds = 0, pf_last_tiles = 0;          // of the last call (gvom_get_tuning "pose_field_rounds" / "pose_field_tiles")
 };
 
 namespace gvom_host {

@@ -416,6 +416,25 @@ hipError_t gvom_launch_viewpoints(hipStream_t s, const ScanParams &P, const View
                                   uint32_t *bitmaps, int32_t *rows);
 hipError_t gvom_launch_viewpoint_best(hipStream_t s, const ScanParams &P, const ViewQuery &Q, const int32_t *fstate, const uint32_t *ftags,
                                       int32_t *rows, int32_t *best);
+// pose fields (gvom_posefield.hip; include/gvom_hip.h "pose fields" defines the result).  c [y][x] uint16 cell costs; fstart / foffs
+// the footprint table as above; C, D, action [H][y][x] volumes; pstart [H + 1] and prims [total][4] int16 (dx, dy, h_to, w) the
+// primitive table as gvom_primitives_set stored it, R its largest |dx|, |dy|.  seed: phase 0 clears D and the 2 * tiles^2 flags and
+// converts cost32 (may be nullptr) into c16; phase 1, behind cspace, seeds the goals [G][3] int32 (x, y, h; h < 0: every heading).
+// relax: one round, as gvom_launch_ctg_relax, with gvom_pose_relax_lds(H, R) bytes of dynamic LDS.
+#define GVOM_POSE_MAX_HEADINGS 64
+#define GVOM_POSE_MAX_REACH 4
+#define GVOM_POSE_MAX_PRIMS 64                         // per heading
+#define GVOM_POSE_MAX_STATES ((int64_t)1 << 28)
+int gvom_pose_tiles(int xy);
+size_t gvom_pose_relax_lds(int H, int R);
+hipError_t gvom_launch_cspace(hipStream_t s, int xy, int H, const uint16_t *c, const int32_t *fstart, const uint32_t *foffs, uint16_t *C);
+hipError_t gvom_launch_pose_seed(hipStream_t s, int phase, int xy, int H, int R, const int32_t *cost32, uint16_t *c16, const uint16_t *C,
+                                 int32_t *D, uint32_t *flags, const int32_t *goals, int G, uint32_t *seeded);
+hipError_t gvom_launch_pose_relax(hipStream_t s, int xy, int H, int R, const uint16_t *C, int32_t *D, const int32_t *pstart,
+                                  const int16_t *prims, uint32_t *fcur, uint32_t *fnext, uint32_t *activated, uint32_t *relaxed,
+                                  int32_t max_cost, int inner);
+hipError_t gvom_launch_pose_actions(hipStream_t s, int xy, int H, const uint16_t *C, const int32_t *D, const int32_t *pstart,
+                                    const int16_t *prims, uint8_t *action, uint32_t *reached);
 // storage order [sy][sx] -> reference order [x][y] (window coordinates)
 hipError_t gvom_launch_unwrap_f64(hipStream_t s, int xy, int om0, int om1, const double *in, int in_stride, double *out_xy);
 hipError_t gvom_launch_posdens(hipStream_t s, const Map2dParams &P, const int32_t *fstate,

@@ -1,5 +1,5 @@
 // gvom_product_calls.hip -- the calls that MAKE a device product: gvom_device_product (occupancy grid, voxel cloud, the two height
-// clouds), gvom_clearance, gvom_raycast, gvom_cost_to_go, gvom_score_rollouts (with gvom_footprint_set, which sets its table), gvom_score_attitude (with gvom_chassis_set), gvom_score_alignments, gvom_frontiers and gvom_score_viewpoints, and the frame builders they and the debug reads (gvom_debug.hip) give
+// clouds), gvom_clearance, gvom_raycast, gvom_cost_to_go, gvom_score_rollouts (with gvom_footprint_set, which sets its table), gvom_score_attitude (with gvom_chassis_set), gvom_score_alignments, gvom_frontiers, gvom_score_viewpoints and gvom_pose_field (with gvom_primitives_set), and the frame builders they and the debug reads (gvom_debug.hip) give
 // the kernels.  Every call takes its set through product_acquire and hands it out through product_publish (gvom_sets.hip); what is
 // left in each body is what is particular to that product: its argument checks, its staging and its launches.
 #include "gvom_host.h"
@@ -88,6 +88,7 @@ VIS int gvom_device_product(gvom_t *h, int kind, int64_t max_rows, int64_t *prod
     if (kind == GVOM_PRODUCT_ALIGNMENT) { h->err = "gvom_device_product: alignment scores are made by gvom_score_alignments"; return GVOM_ERR_INVALID; }
     if (kind == GVOM_PRODUCT_FRONTIERS) { h->err = "gvom_device_product: frontiers are made by gvom_frontiers"; return GVOM_ERR_INVALID; }
     if (kind == GVOM_PRODUCT_VIEWPOINTS) { h->err = "gvom_device_product: viewpoint scores are made by gvom_score_viewpoints"; return GVOM_ERR_INVALID; }
+    if (kind == GVOM_PRODUCT_POSEFIELD) { h->err = "gvom_device_product: pose fields are made by gvom_pose_field"; return GVOM_ERR_INVALID; }
     if (kind < 1 || kind > GVOM_N_PRODUCT_KINDS) { h->err = "gvom_device_product: unknown product kind"; return GVOM_ERR_INVALID; }
     if (h->sharded) { h->err = "gvom_device_product: sharded handles are not supported"; return GVOM_ERR_INVALID; }
     if (kind == GVOM_PRODUCT_VOXEL_CLOUD) stats_demand(h);                  // a read of the statistics, like gvom_debug_voxel_map
@@ -772,6 +773,144 @@ VIS int gvom_score_viewpoints(gvom_t *h, const double *poses, int64_t K, int on_
     h->vp_last_batch = (int)batch;
     if ((rc = product_publish(h, set, product_id))) return rc;
     for (int k = 0; origin_voxels && k < 3; ++k) origin_voxels[k] = (double)F.origin[k];
+    return GVOM_OK;
+}
+
+// ---- pose fields (gvom_primitives_set, gvom_pose_field) ----------------------------------------------------------------------------
+// The navigation function on (x, y, heading) of a cost map -- a cost field's or the caller's -- under the handle's footprint table and
+// primitive table, as a product of kind GVOM_PRODUCT_POSEFIELD.  The kernels (gvom_posefield.hip) run on the handle's stream: the pose
+// cost volume first, then gvom_cost_to_go's loop -- rounds of k_pose_relax a batch at a time, the batch's counters back through pinned
+// memory, the first round that flagged no tile ends the solve.  Like gvom_cost_to_go this call WAITS.
+VIS int gvom_primitives_set(gvom_t *h, int32_t n_headings, const int32_t *start, const int16_t *prims)
+{
+    if (!h) return GVOM_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (!start || !prims) { h->err = "gvom_primitives_set: start and prims must not be NULL"; return GVOM_ERR_INVALID; }
+    if (n_headings < 1 || n_headings > GVOM_POSE_MAX_HEADINGS) { h->err = "gvom_primitives_set: between 1 and 64 headings"; return GVOM_ERR_INVALID; }
+    if (start[0] != 0) { h->err = "gvom_primitives_set: start[0] must be 0"; return GVOM_ERR_INVALID; }
+    int R = 0;
+    for (int k = 0; k < n_headings; ++k) {
+        const int64_t m = (int64_t)start[k + 1] - start[k];
+        if (m < 0 || m > GVOM_POSE_MAX_PRIMS) { h->err = "gvom_primitives_set: every heading has at most 64 primitives"; return GVOM_ERR_INVALID; }
+        for (int p = start[k]; p < start[k + 1]; ++p) {
+            const int dx = prims[4 * p], dy = prims[4 * p + 1], hto = prims[4 * p + 2], w = prims[4 * p + 3];
+            const bool ok = abs(dx) <= GVOM_POSE_MAX_REACH && abs(dy) <= GVOM_POSE_MAX_REACH && hto >= 0 && hto < n_headings && w >= 1 && w <= 255 &&
+                            !(dx == 0 && dy == 0 && hto == k);
+            if (!ok) { h->err = "gvom_primitives_set: a primitive outside the limits (|dx|, |dy| <= 4, 0 <= h_to < H, 1 <= w <= 255, not a self loop)"; return GVOM_ERR_INVALID; }
+            R = std::max(R, std::max(abs(dx), abs(dy)));
+        }
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    const size_t sb = (size_t)(n_headings + 1) * 4, prims_at = align256(sb), pb = (size_t)start[n_headings] * 8;
+    h->pf_H = 0;                                                            // (no table while this one is on its way)
+    const int rc = stage_buf(h, h->pf_tab, prims_at + (size_t)GVOM_POSE_MAX_HEADINGS * GVOM_POSE_MAX_PRIMS * 8, h->pf_allocs);   // (the largest table: never grows again)
+    if (rc) return rc;
+    HIPCHK(h, hipMemcpyAsync(h->pf_tab.p, start, sb, hipMemcpyHostToDevice, h->stream));
+    if (pb) HIPCHK(h, hipMemcpyAsync((char *)h->pf_tab.p + prims_at, prims, pb, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->pf_prims_at = prims_at; h->pf_H = n_headings; h->pf_R = R;
+    return GVOM_OK;
+}
+
+VIS int gvom_pose_field(gvom_t *h, int64_t costfield_id, const int32_t *cost, int on_device, const int32_t *goals, int64_t n_goals,
+                        int32_t max_cost, int32_t max_rounds, int64_t *product_id, int64_t info[4])
+{
+    if (!h || !product_id) return GVOM_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(h->mu);
+    *product_id = -1;
+    for (int k = 0; info && k < 4; ++k) info[k] = 0;
+    if (h->sharded) { h->err = "gvom_pose_field: sharded handles are not supported"; return GVOM_ERR_INVALID; }
+    if (h->fp_H < 1) { h->err = "gvom_pose_field: no footprint table is set (gvom_footprint_set)"; return GVOM_ERR_INVALID; }
+    if (h->pf_H < 1) { h->err = "gvom_pose_field: no primitive table is set (gvom_primitives_set)"; return GVOM_ERR_INVALID; }
+    if (h->fp_H > GVOM_POSE_MAX_HEADINGS) { h->err = "gvom_pose_field: footprint tables of more than 64 headings are not supported"; return GVOM_ERR_CAPACITY; }
+    if (h->pf_H != h->fp_H) { h->err = "gvom_pose_field: the primitives were set for another number of headings than the footprint table has"; return GVOM_ERR_INVALID; }
+    if (costfield_id >= 0 && cost) { h->err = "gvom_pose_field: give a cost field id or a cost map, not both"; return GVOM_ERR_INVALID; }
+    if (costfield_id < 0 && !cost) { h->err = "gvom_pose_field: give a cost field id or a cost map"; return GVOM_ERR_INVALID; }
+    if (!goals || n_goals < 1 || n_goals > GVOM_CTG_MAX_GOALS) { h->err = "gvom_pose_field: between 1 and 65536 goals"; return GVOM_ERR_INVALID; }
+    if (max_cost < 0 || max_cost > GVOM_CTG_MAX_COST) { h->err = "gvom_pose_field: max_cost outside 0 .. 2^30"; return GVOM_ERR_INVALID; }
+    if (max_rounds < 0) { h->err = "gvom_pose_field: max_rounds must not be negative"; return GVOM_ERR_INVALID; }
+    const int xy = h->prm.xy_size, H = h->pf_H, R = h->pf_R;
+    if (xy > GVOM_CLEARANCE_MAX_XY) { h->err = "gvom_pose_field: maps of more than 4096 cells a side are not supported"; return GVOM_ERR_CAPACITY; }
+    const size_t n2 = (size_t)xy * xy;
+    if ((int64_t)H * (int64_t)n2 > GVOM_POSE_MAX_STATES) { h->err = "gvom_pose_field: more than 2^28 states (headings x xy_size^2)"; return GVOM_ERR_CAPACITY; }
+    for (int64_t k = 0; k < n_goals; ++k) {
+        if (goals[3 * k] < 0 || goals[3 * k] >= xy || goals[3 * k + 1] < 0 || goals[3 * k + 1] >= xy) { h->err = "gvom_pose_field: a goal lies outside the window"; return GVOM_ERR_INVALID; }
+        if (goals[3 * k + 2] >= H) { h->err = "gvom_pose_field: a goal's heading is not one of the table's"; return GVOM_ERR_INVALID; }
+    }
+    const DevSet *f = nullptr;
+    if (costfield_id >= 0) {
+        f = find_set(h->psets, costfield_id);
+        if (!f || f->kind != GVOM_PRODUCT_COSTFIELD) { h->err = "gvom_pose_field: unknown or stale cost field id"; return GVOM_ERR_INVALID; }
+    } else if (!on_device) {
+        for (size_t k = 0; k < n2; ++k)
+            if (cost[k] < 0 || cost[k] > 65535) { h->err = "gvom_pose_field: a host cost map holds a value outside 0 .. 65535"; return GVOM_ERR_INVALID; }
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    DevSet *set = nullptr;
+    const size_t bytes = set_bytes(GVOM_PRODUCT_POSEFIELD, xy, 0, H);
+    int rc = product_acquire(h, GVOM_PRODUCT_POSEFIELD, bytes, bytes, "gvom_pose_field", &h->pf_allocs, &set);
+    if (rc) return rc;
+    set->cap = H;
+    const int nt = gvom_pose_tiles(xy), ntiles = nt * nt;
+    const size_t flags_off = 256, goals_off = flags_off + align256((size_t)2 * ntiles * 4), c16_off = goals_off + align256((size_t)GVOM_CTG_MAX_GOALS * 12);
+    if ((rc = stage_buf(h, h->pf_work, c16_off + n2 * 2, h->pf_allocs))) return rc;
+    if (!h->pf_pin) HIPCHK(h, hipHostMalloc((void **)&h->pf_pin, 256, hipHostMallocDefault));
+    uint32_t *cnt = (uint32_t *)h->pf_work.p;
+    uint32_t *fl = (uint32_t *)((char *)h->pf_work.p + flags_off);
+    int32_t *gdev = (int32_t *)((char *)h->pf_work.p + goals_off);
+    uint16_t *c16w = (uint16_t *)((char *)h->pf_work.p + c16_off);
+    HIPCHK(h, join_second_stream(h));
+    const int32_t *cost32 = nullptr;
+    if (!f && !on_device) {                                                 // a host cost map: staged
+        if ((rc = stage_buf(h, h->pf_stage, n2 * 4, h->pf_allocs))) return rc;
+        HIPCHK(h, hipMemcpyAsync(h->pf_stage.p, cost, n2 * 4, hipMemcpyHostToDevice, h->stream));
+        cost32 = (const int32_t *)h->pf_stage.p;
+    } else if (!f) cost32 = cost;
+    const uint16_t *c16 = f ? part_ptr<const uint16_t>(f, 2) : c16w;
+    HIPCHK(h, hipMemcpyAsync(gdev, goals, (size_t)n_goals * 12, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemsetAsync(cnt, 0, 256, h->stream));
+    if ((rc = set_wait_releases(h, set))) return rc;
+    int32_t *D = part_ptr<int32_t>(set, 0);
+    uint16_t *C = part_ptr<uint16_t>(set, 2);
+    const int32_t *pstart = (const int32_t *)h->pf_tab.p;
+    const int16_t *prims = (const int16_t *)((char *)h->pf_tab.p + h->pf_prims_at);
+    HIPCHK(h, gvom_launch_pose_seed(h->stream, 0, xy, H, R, cost32, c16w, C, D, fl, gdev, (int)n_goals, cnt + CTG_CNT_SEEDED));
+    HIPCHK(h, gvom_launch_cspace(h->stream, xy, H, c16, (const int32_t *)h->fp_tab.p, (const uint32_t *)((char *)h->fp_tab.p + h->fp_offs_at), C));
+    HIPCHK(h, gvom_launch_pose_seed(h->stream, 1, xy, H, R, cost32, c16w, C, D, fl, gdev, (int)n_goals, cnt + CTG_CNT_SEEDED));
+    const int32_t cap = max_cost == 0 ? GVOM_CTG_MAX_COST : max_cost;
+    const int inner = h->tune_pf_inner > 0 ? h->tune_pf_inner : 64;
+    const int batch = h->tune_pf_batch > 0 ? h->tune_pf_batch : 8;
+    // a state's final value is in memory at the latest one round after the round in which its successor's was, so
+    // the solve ends after at most (primitives on a cheapest drive + 1) rounds of tiles that reach their fixed point; the limit below
+    // is beyond that for 2^28 states and only keeps this loop finite
+    const int64_t limit = max_rounds > 0 ? (int64_t)max_rounds : (int64_t)1 << 29;
+    int64_t rounds = 0, tiles = 0;
+    bool converged = false;
+    while (!converged && rounds < limit) {
+        const int nb = (int)std::min<int64_t>(batch, limit - rounds);
+        if (rounds) HIPCHK(h, hipMemsetAsync(cnt, 0, 2 * GVOM_CTG_MAX_BATCH * 4, h->stream));
+        for (int r = 0; r < nb; ++r) {
+            const int64_t k = rounds + r;
+            HIPCHK(h, gvom_launch_pose_relax(h->stream, xy, H, R, C, D, pstart, prims, fl + (k & 1) * ntiles, fl + ((k + 1) & 1) * ntiles,
+                                             cnt + r, cnt + CTG_CNT_RELAXED + r, cap, inner));
+        }
+        HIPCHK(h, hipMemcpyAsync(h->pf_pin, cnt, 2 * GVOM_CTG_MAX_BATCH * 4, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        int ran = nb;
+        for (int r = 0; r < nb; ++r) {
+            tiles += h->pf_pin[CTG_CNT_RELAXED + r];
+            if (h->pf_pin[r] == 0) { converged = true; ran = r + 1; break; }
+        }
+        rounds += ran;
+    }
+    HIPCHK(h, gvom_launch_pose_actions(h->stream, xy, H, C, D, pstart, prims, part_ptr<uint8_t>(set, 1), cnt + CTG_CNT_REACHED));
+    if ((rc = product_publish(h, set, product_id))) return rc;             // (`ready` goes in front of the counters' way back)
+    HIPCHK(h, hipMemcpyAsync(h->pf_pin, cnt, 256, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (!converged && max_rounds == 0) { set->id = *product_id = -1; h->err = "gvom_pose_field: the field did not settle"; return GVOM_ERR_HIP; }   // (nobody gets it)
+    h->pf_last_rounds = (int)std::min<int64_t>(rounds, INT32_MAX);
+    h->pf_last_tiles = (int)std::min<int64_t>(tiles, INT32_MAX);
+    if (info) { info[0] = converged ? 1 : 0; info[1] = rounds; info[2] = h->pf_pin[CTG_CNT_REACHED]; info[3] = h->pf_pin[CTG_CNT_SEEDED]; }
     return GVOM_OK;
 }
 }  // extern "C"

@@ -24,6 +24,9 @@
 //                    cap = max_clusters of the call that wrote it.  Kind 15 is not assigned
 //   viewpoints (18)  cap x 8 int32 {status, gain, visits, beams OCCUPIED, CLEAR, LEFT_WINDOW, UNKNOWN, INVALID}, then 4 int32 {best
 //                    index, its gain, K, beams per viewpoint}; cap = the viewpoints K of the call that wrote it.  Kind 17 is not assigned
+//   pose field (20)  cap x xy*xy int32 (cost to go), then cap x xy*xy uint8 (action), then cap x xy*xy uint16 (pose costs): volumes
+//                    [h][y][x], every plane laid out like a cost field's maps; cap = the headings H of the call that wrote it.  Kind 19
+//                    is not assigned
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -64,6 +67,7 @@ inline size_t set_bytes(int kind, int xy, int zs, int64_t cap, int64_t cols = 0)
     case GVOM_PRODUCT_ATTITUDE: return align256((size_t)cap * 20) + align256((size_t)cap * (size_t)cols * 12) + (size_t)cap * (size_t)cols;
     case GVOM_PRODUCT_FRONTIERS: return align256((size_t)cap * 32) + align256((size_t)cap * 16) + align256(n2 * 4) + 16;
     case GVOM_PRODUCT_VIEWPOINTS: return align256((size_t)cap * 32) + 16;
+    case GVOM_PRODUCT_POSEFIELD: return align256((size_t)cap * n2 * 4) + align256((size_t)cap * n2) + (size_t)cap * n2 * 2;
     }
     return 0;
 }
@@ -152,6 +156,16 @@ inline bool set_part(const SetShape *s, int part, SetPart *d)
         else if (part == 1) { d->ptr = s->mem + align256((size_t)s->cap * 32); d->ndim = 1; d->shape[0] = 4; d->strides[0] = 1; d->shape[1] = d->strides[1] = 1; d->code = kDLInt; }
         else return false;
         break;
+    case GVOM_PRODUCT_POSEFIELD: {                         // [h, x, y] indexing: every plane column-major, like a device map
+        if (part < 0 || part > 2) return false;
+        const size_t vol = (size_t)s->cap * (size_t)n2;
+        d->ptr = s->mem + (part ? align256(vol * 4) : 0) + (part == 2 ? align256(vol) : 0);
+        d->ndim = 3;
+        d->shape[0] = s->cap; d->shape[1] = d->shape[2] = xy;
+        d->strides[0] = n2; d->strides[1] = 1; d->strides[2] = xy;
+        d->code = part ? kDLUInt : kDLInt; d->bits = part == 0 ? 32 : (part == 1 ? 8 : 16);
+        break;
+    }
     default: return false;
     }
     d->bytes = (size_t)(d->shape[0] * d->shape[1] * d->shape[2]) * (d->bits / 8);

@@ -169,6 +169,8 @@ ABI = [
     ("gvom_score_alignments", _I, [_P, _P, _I64, _P, _I64, _I, _I, _P, ctypes.POINTER(_I64)]),
     ("gvom_frontiers", _I, [_P, _I64, _I64, _P, _P, _P, _I, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(_I64), ctypes.POINTER(_I64)]),
     ("gvom_score_viewpoints", _I, [_P, _P, _I64, _I, ctypes.c_double, ctypes.c_int32, ctypes.c_int32, _I, _P, ctypes.POINTER(_I64)]),
+    ("gvom_primitives_set", _I, [_P, ctypes.c_int32, _P, _P]),
+    ("gvom_pose_field", _I, [_P, _I64, _P, _I, _P, _I64, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(_I64), ctypes.POINTER(_I64)]),
     ("gvom_set_profiling", _I, [_P, _I]),
     ("gvom_host_timing", _I, [_P, ctypes.POINTER(ctypes.c_double * 8)]),
     ("gvom_set_tuning", _I, [_P, ctypes.c_char_p, _I]),
@@ -570,13 +572,15 @@ PRODUCT_ALIGNMENT = 12                    # GVOM_PRODUCT_ALIGNMENT: made by gvom
 PRODUCT_ATTITUDE = 14                     # GVOM_PRODUCT_ATTITUDE: made by gvom_score_attitude (kind 13 is not assigned)
 PRODUCT_FRONTIERS = 16                    # GVOM_PRODUCT_FRONTIERS: made by gvom_frontiers (kind 15 is not assigned)
 PRODUCT_VIEWPOINTS = 18                   # GVOM_PRODUCT_VIEWPOINTS: made by gvom_score_viewpoints (kind 17 is not assigned)
+PRODUCT_POSEFIELD = 20                    # GVOM_PRODUCT_POSEFIELD: made by gvom_pose_field (kind 19 is not assigned)
 # element type of part k of a product, by kind (what set_part() of csrc/gvom_setlayout.h gives as DLPack code and bits)
 _PRODUCT_DTYPES = {PRODUCT_OCCUPANCY: (np.uint8,), PRODUCT_VOXEL_CLOUD: (np.float32, np.float32, np.int64),
                    PRODUCT_HEIGHT_CLOUD: (np.float32,), PRODUCT_INFERRED_HEIGHT_CLOUD: (np.float32,),
                    PRODUCT_CLEARANCE: (np.float32, np.int32), PRODUCT_RAYCAST: (np.int32, np.float32),
                    PRODUCT_COSTFIELD: (np.int32, np.uint8, np.uint16), PRODUCT_ROLLOUTS: (np.int32, np.uint16),
                    PRODUCT_ALIGNMENT: (np.int32, np.int32), PRODUCT_ATTITUDE: (np.int32, np.float32, np.uint8),
-                   PRODUCT_FRONTIERS: (np.int32, np.int64, np.int32, np.int32), PRODUCT_VIEWPOINTS: (np.int32, np.int32)}
+                   PRODUCT_FRONTIERS: (np.int32, np.int64, np.int32, np.int32), PRODUCT_VIEWPOINTS: (np.int32, np.int32),
+                   PRODUCT_POSEFIELD: (np.int32, np.uint8, np.uint16)}
 CLEARANCE_FAR = 2147483647                # GVOM_CLEARANCE_FAR: squared_cells where no obstacle is in reach
 _CLEARANCE_NO_NEGATIVE = 1                # GVOM_CLEARANCE_NO_NEGATIVE
 
@@ -863,6 +867,20 @@ class DeviceCostField(_ProductView):
 
     def copy_to_host(self):
         return self.cost.copy_to_host(), self.direction.copy_to_host(), self.cell_cost.copy_to_host()
+
+    def pose_field(self, goals, goals_in_cells=False, max_cost=None, max_rounds=0):
+        """The heading-aware navigation function of this field's `.cell_cost` under the mapper's footprint table (Gvom.set_footprint;
+        build THIS field without inflation: the footprint does that, per heading) and primitive table (Gvom.set_primitives): from
+        every state (x, y, heading) the cheapest drive to a goal state that the primitives allow -- a DevicePoseField, computed on the
+        GPU behind the solve that wrote this field.  The call waits for it.  goals: (G, 2) = (x, y) seeds every heading of the cell,
+        (G, 3) = (x, y, yaw) only the heading rint(yaw * H / 2 pi) mod H (float32, the rollouts' rule); world metres -- or window
+        cells with goals_in_cells=True; the yaw is radians either way.  A goal outside the window raises ValueError; a goal state
+        the footprint blocks seeds nothing.  max_cost, max_rounds: as cost_to_go().  include/gvom_hip.h "pose fields" has the
+        definition."""
+        g = self._hold._owner
+        H = g._pose_headings()
+        cells = _pose_goals(goals, g.xy_size, H, None if goals_in_cells else (g.xy_resolution, self.origin))
+        return g._pose_field(self.product_id, None, 0, cells, _ctg_max_cost(max_cost), _ctg_max_rounds(max_rounds), self.origin)
 
     def frontiers(self, device_maps, min_cells=4, max_clusters=1024):
         """Where to explore next: the cells of this field that can be driven on (`.cell_cost` > 0), have been seen (`visibility` of
@@ -1293,6 +1311,215 @@ class DeviceViewpoints(_ProductView):
         if k < 0:
             return None
         return k, gain, (None if self._poses is None else self._poses[k].copy())
+
+
+# ---- pose fields (Gvom.set_primitives, DeviceCostField.pose_field and friends; include/gvom_hip.h "pose fields") ----
+POSE_GOAL = 253                           # GVOM_POSE_GOAL: the action at a seeded state (beside CTG_NONE and CTG_UNSETTLED)
+POSE_MAX_HEADINGS = 64
+POSE_MAX_REACH = 4                        # |dx|, |dy| of a primitive, in cells
+POSE_MAX_PRIMITIVES = 64                  # per heading
+POSE_MAX_STATES = 1 << 28                 # headings * xy_size ** 2
+_RO_FAR = 100000                          # csrc/gvom_rollouts.h RO_FAR: where pose_states puts a centre that is outside however far
+
+
+def _primitive_arrays(table):
+    """(start, prims) as the library takes them: C-contiguous int32 [H + 1] and int16 [total, 4]; ValueError for what it would refuse"""
+    try:
+        start, prims = table
+    except (TypeError, ValueError):
+        raise ValueError("a primitive table is a pair (start, prims)")
+    st, pr = np.asarray(start), np.asarray(prims)
+    if st.ndim != 1 or not 2 <= st.shape[0] <= POSE_MAX_HEADINGS + 1 or st.dtype.kind not in "iu":
+        raise ValueError("start must be integers of shape (H + 1,) with 1 <= H <= %d, got %r %s" % (POSE_MAX_HEADINGS, st.shape, st.dtype))
+    if pr.ndim != 2 or pr.shape[1] != 4 or pr.dtype.kind not in "iu":
+        raise ValueError("prims must be integers of shape (total, 4) = (dx, dy, h_to, w), got %r %s" % (pr.shape, pr.dtype))
+    st, pr = st.astype(np.int64), pr.astype(np.int64)
+    H = st.shape[0] - 1
+    m = np.diff(st)
+    if st[0] != 0 or (m < 0).any() or (m > POSE_MAX_PRIMITIVES).any():
+        raise ValueError("start must begin at 0 and give every heading at most %d primitives" % POSE_MAX_PRIMITIVES)
+    if st[-1] != pr.shape[0]:
+        raise ValueError("start[-1] = %d, but there are %d primitives" % (st[-1], pr.shape[0]))
+    own = np.repeat(np.arange(H), m)
+    bad = ((np.abs(pr[:, 0]) > POSE_MAX_REACH) | (np.abs(pr[:, 1]) > POSE_MAX_REACH) | (pr[:, 2] < 0) | (pr[:, 2] >= H) | (pr[:, 3] < 1) |
+           (pr[:, 3] > 255) | ((pr[:, 0] == 0) & (pr[:, 1] == 0) & (pr[:, 2] == own)))
+    if bad.any():
+        k = int(np.nonzero(bad)[0][0])
+        raise ValueError("primitive %d = %r of heading %d is outside the limits: |dx|, |dy| <= %d, 0 <= h_to < %d, 1 <= w <= 255, "
+                         "not (0, 0, its own heading)" % (k, tuple(int(v) for v in pr[k]), own[k], POSE_MAX_REACH, H))
+    return np.ascontiguousarray(st, dtype=np.int32), np.ascontiguousarray(pr, dtype=np.int16)
+
+
+def arc_primitives(headings, min_turn_radius, xy_resolution, reach=3, reverse_weight=None):
+    """The primitive table (start, prims) of a car-like vehicle for Gvom.set_primitives, by a constructive definition: per heading
+    three forward primitives -- straight, left, right, in this order -- each an arc of length l = reach * xy_resolution.  A turn
+    changes the heading by k = floor(l / min_turn_radius / (2 pi / headings)) bins, at most headings // 4 (ValueError where k is 0:
+    the arc is too short to reach the next heading), that is by phi = k * 2 pi / headings on a radius l / phi >= min_turn_radius.
+    The end cell is the rint of the arc's end point in cells (float64); w = max(1, rint(10 * the arc length, in cells, through the
+    ROUNDED chord)) -- the chord itself for a straight primitive, chord * (phi / 2) / sin(phi / 2) for a turn.  reverse_weight = r adds
+    the three mirrored reverse primitives (straight back, back with the wheels left: the heading turns right, back with the wheels
+    right) behind them in the same order, w multiplied by r and clipped to 255.  For headings % 4 == 0 the first quarter is built and
+    rotated for the rest: the table is exactly symmetric under quarter turns."""
+    H = int(headings)
+    if H != headings or not 4 <= H <= POSE_MAX_HEADINGS:
+        raise ValueError("headings must be an integer in 4 .. %d, got %r" % (POSE_MAX_HEADINGS, headings))
+    res, rad, n = float(xy_resolution), float(min_turn_radius), float(reach)
+    if not (math.isfinite(res) and res > 0 and math.isfinite(rad) and rad > 0 and math.isfinite(n) and 0 < n <= POSE_MAX_REACH):
+        raise ValueError("arc_primitives needs xy_resolution > 0, min_turn_radius > 0 and 0 < reach <= %d cells" % POSE_MAX_REACH)
+    if reverse_weight is not None and not (math.isfinite(float(reverse_weight)) and float(reverse_weight) > 0):
+        raise ValueError("reverse_weight must be None or a factor > 0, got %r" % (reverse_weight,))
+    length = n * res
+    step = 2.0 * math.pi / H
+    k = int(math.floor(length / rad / step))
+    if k == 0:
+        raise ValueError("an arc of %g m on a radius of %g m does not reach the next of %d headings: raise reach or lower headings"
+                         % (length, rad, H))
+    k = min(k, H // 4)
+    phi = k * step
+    r = length / phi
+
+    def one(h):
+        th = h * step
+        c, s = math.cos(th), math.sin(th)
+        rows = []
+        ends = ((length, 0.0, 0), (r * math.sin(phi), r * (1.0 - math.cos(phi)), k), (r * math.sin(phi), -r * (1.0 - math.cos(phi)), -k))
+        for sign, factor in ((1.0, None), (-1.0, reverse_weight)):
+            if sign < 0 and reverse_weight is None:
+                break
+            for ex, ey, dk in ends:
+                ex, dk = sign * ex, int(sign) * dk                          # mirrored through the lateral axis: backing up turns the other way
+                dx, dy = int(np.rint((c * ex - s * ey) / res)), int(np.rint((s * ex + c * ey) / res))
+                chord = math.hypot(dx, dy)
+                arc = chord if dk == 0 else chord * (phi / 2.0) / math.sin(phi / 2.0)
+                w = max(1, int(np.rint(10.0 * arc)))
+                if factor is not None:
+                    w = max(1, int(np.rint(w * float(factor))))
+                rows.append((dx, dy, (h + dk) % H, min(w, 255)))
+        return rows
+
+    per = []
+    if H % 4 == 0:
+        q = H // 4
+        base = [one(h) for h in range(q)]
+        for turn in range(4):
+            for h in range(q):
+                rows = base[h]
+                for _ in range(turn):
+                    rows = [(-dy, dx, (ht + q) % H, w) for dx, dy, ht, w in rows]
+                per.append(rows)
+    else:
+        per = [one(h) for h in range(H)]
+    start = np.concatenate([[0], np.cumsum([len(rows) for rows in per])]).astype(np.int32)
+    prims = np.array([row for rows in per for row in rows], np.int16)
+    return _primitive_arrays((start, prims))
+
+
+def pose_states(poses, origin, xy_resolution, H):
+    """The states of poses [..., 3] = (x, y, yaw) in world metres and radians, ROUNDED TO float32, with exactly the arithmetic the
+    rollout kernels place a pose with (include/gvom_hip.h "rollout scoring", CENTRE / HEADING / INVALID): (states, valid) -- states
+    int32 [..., 3] = (cx, cy, h), the centre in window cells of a map whose window corner is at `origin` and the heading bin of H;
+    valid bool [...].  A centre may lie outside the window (test it against xy_size); one that is outside however far (a
+    non-finite coordinate, |x / xy_resolution| >= 2**30) reads -100000, and a centre is clamped to +-100000.  An invalid pose has
+    heading 0.  A torch consumer gathers a DevicePoseField's cost[h, cx, cy] with these as a rollout's terminal cost."""
+    p = np.asarray(poses)
+    if p.ndim < 1 or p.shape[-1] != 3 or p.dtype.kind not in "iuf":
+        raise ValueError("poses must be numbers of shape (..., 3) = (x, y, yaw), got %r %s" % (p.shape, p.dtype))
+    H = int(H)
+    if H < 1:
+        raise ValueError("H must be at least 1")
+    p = p.astype(np.float32)
+    oc = _rollout_origin(origin, xy_resolution)
+    x, y, yaw = p[..., 0], p[..., 1], p[..., 2]
+    out = np.zeros(p.shape[:-1] + (3,), np.int32)
+    with np.errstate(all="ignore"):
+        a = yaw * np.float32(H / 6.283185307179586476925286766559)       # one float32 multiply
+        valid = (np.abs(x) < np.inf) & (np.abs(y) < np.inf) & (np.abs(yaw) < np.inf) & (np.abs(a) < np.float32(16777216.0))
+        out[..., 2] = np.where(valid, np.rint(a), np.float32(0)).astype(np.int64) % H
+        for k, v in enumerate((x, y)):
+            q = v.astype(np.float64) / float(xy_resolution)
+            near = np.abs(q) < 1073741824.0                               # (False for NaN)
+            c = np.floor(np.where(near, q, 0.0)).astype(np.int64) - int(oc[k])
+            out[..., k] = np.where(near, np.clip(c, -_RO_FAR, _RO_FAR), -_RO_FAR)
+    return out, valid
+
+
+def _pose_goals(goals, xy_size, H, frame):
+    """goals -> C-contiguous int32 (G, 3) = (x, y, h) window cells and heading, h = -1 for a goal without a yaw; frame as _ctg_goals"""
+    a = np.asarray(goals)
+    if a.ndim == 1 and a.shape[0] in (2, 3):
+        a = a.reshape(1, -1)
+    if a.ndim != 2 or a.shape[1] not in (2, 3) or not 1 <= a.shape[0] <= CTG_MAX_GOALS:
+        raise ValueError("goals must have shape (G, 2) or (G, 3) = (x, y[, yaw]) with 1 <= G <= %d, got %r" % (CTG_MAX_GOALS, a.shape))
+    if a.dtype.kind not in "iuf":
+        raise ValueError("goals must be numbers, got dtype %s" % a.dtype)
+    cells = _ctg_goals(a[:, :2], xy_size, frame)
+    out = np.full((a.shape[0], 3), -1, np.int32)
+    out[:, :2] = cells
+    if a.shape[1] == 3:
+        yaw = a[:, 2].astype(np.float32)
+        with np.errstate(all="ignore"):
+            s = yaw * np.float32(H / 6.283185307179586476925286766559)
+        if not (np.isfinite(yaw).all() and (np.abs(s) < np.float32(16777216.0)).all()):
+            raise ValueError("a goal's yaw must be finite (and below 2**24 heading bins)")
+        out[:, 2] = np.rint(s).astype(np.int64) % H
+    return np.ascontiguousarray(out)
+
+
+class _PoseVolume(DeviceArray):
+    """One [H, xy, xy] volume of a pose field, indexed [h, x, y] with strides (xy*xy, 1, xy): every plane lies in memory like a
+    DeviceCostField's maps.  copy_to_host() returns numpy of the same indexing (a transposed view of the [h][y][x] copy)."""
+
+    def copy_to_host(self):
+        g = self._hold._owner
+        raw = np.empty((self.shape[0], self.shape[2], self.shape[1]), self.dtype)
+        g._check(g._lib.gvom_device_product_copy(g._h, self.product_id, self._part, ctypes.c_void_p(raw.ctypes.data)))
+        return raw.transpose(0, 2, 1)
+
+
+class DevicePoseField(_ProductView):
+    """The result of DeviceCostField.pose_field() / Gvom.pose_field_of() / pose_field_of_device(): `.cost` int32 [H, xy, xy], the
+    cheapest drive from each state (heading, x, y) to a goal state under the mapper's footprint and primitive tables (CTG_UNREACHED
+    where there is none), `.action` uint8 [H, xy, xy], the index of its first primitive within the heading's list (POSE_GOAL at a
+    seeded state, CTG_NONE where unreached, CTG_UNSETTLED only in a field that is not final) and `.pose_cost` uint16 [H, xy, xy],
+    the cost volume the solver used (0 = the footprint touches a blocked cell or leaves the window) -- three volumes of one product,
+    indexed [h, x, y].  `.converged`, `.rounds`, `.reached` (states with a finite cost) and `.goals_seeded` (distinct states seeded)
+    describe the solve; `.origin` is the window corner in world metres; `.primitives` the table it was made with.  A snapshot: later
+    scans, combines, set_footprint and set_primitives calls do not change it.  copy_to_host() returns (cost, action, pose_cost)."""
+
+    def __init__(self, hold, info, origin, primitives):
+        _ProductView.__init__(self, hold)
+        self.cost, self.action, self.pose_cost = _PoseVolume(hold, 0), _PoseVolume(hold, 1), _PoseVolume(hold, 2)
+        self.converged, self.rounds, self.reached, self.goals_seeded = bool(info[0]), int(info[1]), int(info[2]), int(info[3])
+        self.origin = np.array(origin, np.float64)
+        self.primitives = primitives
+        self._host = None
+
+    def copy_to_host(self):
+        return self.cost.copy_to_host(), self.action.copy_to_host(), self.pose_cost.copy_to_host()
+
+    def path_from(self, x, y, h):
+        """The states [(x, y, h), ...] from the given one to a seeded goal state, both included, following `.action` on a host copy
+        (made once); None where the state is unreached.  RuntimeError on CTG_UNSETTLED (a field that stopped before it converged)."""
+        if self._host is None:
+            self._host = self.action.copy_to_host()
+        a = self._host
+        start, prims = self.primitives
+        x, y, h = int(x), int(y), int(h)
+        if not (0 <= h < a.shape[0] and 0 <= x < a.shape[1] and 0 <= y < a.shape[2]):
+            raise ValueError("state (%d, %d, %d) lies outside the field" % (x, y, h))
+        path = [(x, y, h)]
+        for _ in range(a.size):
+            k = int(a[h, x, y])
+            if k == POSE_GOAL:
+                return path
+            if k == CTG_NONE:
+                return None
+            if k >= start[h + 1] - start[h]:
+                raise RuntimeError("state (%d, %d, %d) is unsettled: the field stopped before it converged" % (x, y, h))
+            dx, dy, ht, _w = (int(v) for v in prims[start[h] + k])
+            x, y, h = x + dx, y + dy, ht
+            path.append((x, y, h))
+        raise RuntimeError("the actions do not lead to a goal")
 
 
 ALIGN_MAX_POINTS = 1 << 20
@@ -2179,6 +2406,47 @@ class Gvom(object):
         if not poses_ptr:
             raise ValueError("poses_ptr must be a device address")
         return self._score_viewpoints(_dev(poses_ptr), K, 1, max_range, beam_stride, unknown_blocks)
+
+    # ---- pose fields (an extension; include/gvom_hip.h "pose fields") ----
+    def set_primitives(self, table):
+        """Sets the vehicle's motion primitives for the pose_field calls: what arc_primitives() returns, or raw (start, prims) arrays
+        -- start int32 (H + 1,), prims int16 (total, 4) = (dx, dy, h_to, w), heading h owning prims[start[h]:start[h + 1]]: from the
+        state (x, y, h) to (x + dx, y + dy, h_to) at the price w * (pose cost at both ends).  H must be the footprint table's when a
+        field is made.  Replaces a previous table; products made with it are unchanged."""
+        st, pr = _primitive_arrays(table)
+        self._check_args(self._lib.gvom_primitives_set(self._h, st.shape[0] - 1, _ptr(st), _ptr(pr)))
+        self._primitives = (st, pr)
+
+    def _pose_headings(self):
+        if getattr(self, "_primitives", None) is None:
+            raise ValueError("no primitive table is set (Gvom.set_primitives)")
+        return self._primitives[0].shape[0] - 1
+
+    def _pose_field(self, field_id, cost_ptr, on_device, cells, max_cost, max_rounds, origin):
+        info = (_I64 * 4)()
+        table = self._primitives
+        hold = self._make_product(lambda pid: self._lib.gvom_pose_field(
+            self._h, int(field_id), cost_ptr, int(on_device), _ptr(cells), cells.shape[0], max_cost, max_rounds, pid, info),
+            PRODUCT_POSEFIELD, self._check_args)
+        return DevicePoseField(hold, list(info), origin, table)
+
+    def pose_field_of(self, cost, goals, max_cost=None, max_rounds=0, origin=(0.0, 0.0)):
+        """DeviceCostField.pose_field() of a cost map of the caller's: a numpy [x, y] array of shape (xy_size, xy_size) in any memory
+        order, integers in 0 .. 65535 (0 = blocked); goals: (G, 2) or (G, 3) = (x, y[, yaw]) in window cells and radians.  Needs no
+        scan and no combine.  A convenience route: the map is copied to the device.  origin: kept as the field's `.origin`."""
+        H = self._pose_headings()
+        c = self._window_map("cost", np.asarray(cost), np.int32, (0, 65535), range_note=" (0 = blocked)")
+        cells = _pose_goals(goals, self.xy_size, H, None)
+        return self._pose_field(-1, _ptr(c), 0, cells, _ctg_max_cost(max_cost), _ctg_max_rounds(max_rounds), origin)
+
+    def pose_field_of_device(self, cost_ptr, goals, max_cost=None, max_rounds=0, origin=(0.0, 0.0)):
+        """The same for a cost map in device memory (the raw device address of xy_size*xy_size int32, cell (x, y) at
+        [y*xy_size + x]; the data must be ready when the call is made).  Values outside 0 .. 65535 are clamped into the range."""
+        if not cost_ptr:
+            raise ValueError("cost_ptr must be a device address")
+        H = self._pose_headings()
+        cells = _pose_goals(goals, self.xy_size, H, None)
+        return self._pose_field(-1, _dev(cost_ptr), 1, cells, _ctg_max_cost(max_cost), _ctg_max_rounds(max_rounds), origin)
 
     # ---- scan alignment scoring (an extension; include/gvom_hip.h "scan alignment scoring") ----
     def _score_alignments(self, cloud_ptr, n, tf_ptr, K, on_device, dilate, weights):

@@ -840,6 +840,66 @@ int gvom_frontiers(gvom_t *h, int64_t costfield_id, int64_t map_set_id, const ui
 int gvom_score_viewpoints(gvom_t *h, const double *poses /* [K][12] */, int64_t K, int on_device, double max_range,
                           int32_t stride_h, int32_t stride_w, int flags, double origin_voxels[3], int64_t *product_id);
 
+/* --- pose fields (an extension: the navigation function on (x, y, heading) -- heading-aware cost-to-go under the oriented footprint,
+ * for a vehicle that cannot turn on the spot; what makes a rollout's terminal cost honest for a car) ------------------------------------
+ * gvom_pose_field computes, on the GPU, from every STATE (x, y, h) of a window -- a cell and one of the H headings of the footprint
+ * table gvom_footprint_set gave the handle -- the cheapest way to a goal state that the MOTION PRIMITIVES gvom_primitives_set gave the
+ * handle allow, and the first primitive of it, and leaves the result in device memory as a product (kind GVOM_PRODUCT_POSEFIELD) that
+ * gvom_device_product_export / _release / _dlpack / _copy handle like the others.  gvom_get_tuning "pose_field" (read-only): 1 -- how
+ * a caller probes a library for these entry points (an addition: GVOM_ABI_VERSION stays); "primitives" (read-only): 1 while a table is
+ * set.  All arithmetic is integer: the result is exact and does not depend on scheduling.
+ *
+ * DEFINITION.
+ * COST MAP    c, uint16 per cell, 0 = blocked: part 2 of a live GVOM_PRODUCT_COSTFIELD, or the caller's int32 map as gvom_cost_to_go
+ *             takes it (cell (x, y) at [y*xy_size + x]; a device map is clamped into 0 .. 65535, a host map outside it is refused).
+ * POSE COST   C[h][cell], uint16: exactly the POSE COST of "rollout scoring" for a pose centred in `cell` with heading h -- 0 where a
+ *             footprint cell of heading h lies outside the window or on a cell with c == 0, otherwise the maximum of c under the
+ *             footprint.
+ * PRIMITIVES  start int32 [H + 1] with start[0] = 0, prims int16 [start[H]][4], each row (dx, dy, h_to, w).  Primitive p of heading h,
+ *             start[h] <= p < start[h + 1], leads from the state u = (x, y, h) to v = (x + dx, y + dy, h_to).  |dx|, |dy| <= 4;
+ *             0 <= h_to < H; 1 <= w <= 255; at most 64 primitives per heading; (dx, dy, h_to) != (0, 0, h).  The graph is DIRECTED:
+ *             the vehicle reverses only where the table says so.
+ * ADMISSIBLE  a primitive is admissible iff v lies in the window, C[u] != 0 and C[v] != 0; its PRICE is w * (C[u] + C[v]).  The
+ *             cells swept between the two ends are not examined.
+ * FIELD       D, int32: the least solution of D[u] = min over the admissible primitives of u of (price + D[v]) with D = 0 at the
+ *             seeded goal states; GVOM_CTG_UNREACHED elsewhere.  max_cost > 0: states dearer than max_cost read GVOM_CTG_UNREACHED
+ *             (0: the limit is GVOM_CTG_MAX_COST), as in "cost-to-go fields".
+ * ACTION      uint8 per state: the index, within heading h's list, of the first primitive in table order that attains the minimum;
+ *             GVOM_POSE_GOAL (253) at a seeded state; GVOM_CTG_NONE (255) where D is unreached; GVOM_CTG_UNSETTLED (254) where no
+ *             primitive matches, which happens only in a field stopped by max_rounds.
+ * GOALS       int32 [n_goals][3] = (x, y, h) in window cells.  h < 0 seeds every heading of the cell.  A goal state with C == 0 seeds
+ *             nothing.  info[3] counts the distinct states seeded.
+ * part 0 = int32 D, part 1 = uint8 action, part 2 = uint16 C, each [H, xy, xy] indexed [h, x, y] with strides (xy*xy, 1, xy): every
+ * plane has the memory layout of a cost field's maps.
+ *
+ * gvom_primitives_set validates the table, copies it to the device and returns after the copy; a later call replaces the table.
+ * GVOM_ERR_INVALID: NULL arguments, n_headings outside 1 .. 64, start[0] != 0, a heading with more than 64 primitives (none is
+ * allowed: a dead end), and any primitive outside the limits above.
+ *
+ * gvom_pose_field: the solver is gvom_cost_to_go's scheme (tiles of 8 x 8 cells x all headings relax in LDS, rounds are enqueued a
+ * batch at a time, the first round that flagged no tile ends the solve), so the call WAITS for the field.  max_rounds > 0 stops after
+ * that many rounds: info[0] = 0 then, every finite D is the cost of a real drive (an upper bound of the field).  max_rounds == 0 and
+ * no convergence is GVOM_ERR_HIP.  info = {converged, rounds, reached states, seeded states}.  gvom_set_tuning "pose_field_inner"
+ * (sweeps a tile makes at most per round; 0: 64) and "pose_field_batch" (rounds per look at the counters, at most 16; 0: 8) change
+ * the time, never the result; "pose_field_rounds" / "pose_field_tiles" (read-only): rounds and tile relaxations of the last call.
+ * The product is a snapshot: later scans, combines, gvom_footprint_set and gvom_primitives_set calls do not change it.  Products of
+ * this kind live in the product-set pool ("device_product_sets"), sized by H and xy_size: at most GVOM_MAX_PRODUCT_SETS; an
+ * unexported one goes back to the pool with the next call.  "pose_field_allocations" (read-only): device allocations the entry points
+ * have made on this handle (the table, the work and staging buffers and the product sets); it does not grow in steady state.
+ * gvom_device_product(GVOM_PRODUCT_POSEFIELD) is GVOM_ERR_INVALID (this call makes them).  Kind 19 is not assigned.
+ * GVOM_ERR_INVALID: a sharded handle; no footprint table or no primitive table set, or tables of different H; a field id AND a cost
+ * map, or neither; an unknown or stale field id; goals NULL, n_goals outside 1 .. 65536, a goal outside the window or with h >= H;
+ * max_cost outside 0 .. 2^30; max_rounds < 0; a host cost outside 0 .. 65535.  GVOM_ERR_CAPACITY: H > 64; xy_size > 4096;
+ * H * xy_size^2 > 2^28; every set of the kind exported.
+ * NOT PROVIDED: the cells swept between a primitive's two ends (keep the primitives short, or grow the footprint's margin);
+ * primitives longer than 4 cells; a heading tolerance at goals; reading the field inside gvom_score_rollouts (gather D at the
+ * rollouts' last poses); incremental repair after a map change; sharded handles. */
+#define GVOM_PRODUCT_POSEFIELD 20   /* part 0 int32 D, part 1 uint8 action, part 2 uint16 pose cost: [H, xy, xy], strides (xy*xy, 1, xy) */
+#define GVOM_POSE_GOAL 253
+int gvom_primitives_set(gvom_t *h, int32_t n_headings, const int32_t *start /* [n_headings + 1] */, const int16_t *prims /* [start[n_headings]][4] */);
+int gvom_pose_field(gvom_t *h, int64_t costfield_id, const int32_t *cost, int on_device, const int32_t *goals /* [n_goals][3] */,
+                    int64_t n_goals, int32_t max_cost, int32_t max_rounds, int64_t *product_id, int64_t info[4]);
+
 /* --- one map sharded over the GPUs of a node (one rank = one process = one GPU) -------------------
  * No counterpart in the reference (it has no multi-GPU path); semantics = SURVEY 8(e):
  * the rays are data-parallel, the per-voxel accumulators (hit / total: int32 sum, min-height: f32 min)

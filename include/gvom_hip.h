@@ -402,6 +402,10 @@ int gvom_clearance(gvom_t *h, int64_t map_set_id, const int32_t *positive, const
  * the answers in device memory as a product (kind GVOM_PRODUCT_RAYCAST) that gvom_device_product_export / _release / _dlpack /
  * _copy handle like the others.  The walk is read-only.  gvom_get_tuning "raycast" (read-only): 1 -- how a caller probes a
  * library for this entry point (an addition: GVOM_ABI_VERSION stays).
+ * The CURRENT fused map -- here and for every call that reads it (gvom_device_product, gvom_score_alignments,
+ * gvom_score_viewpoints, gvom_get_occupancy, gvom_read_dense) -- is the map of the most recently BEGUN combine, synchronous or
+ * asynchronous (from gvom_combine_begin on, before gvom_combine_end); a scan, accepted or rejected, changes nothing a query sees
+ * until the next combine (tests/test_query_cycle.py holds the calls to this at every point of the scan cycle).
  *
  * INPUT.  from [K][3] and to [n][3]: world metres, C-contiguous float32; K is 1 (every ray starts at from[0]) or n.
  * on_device == 0: host memory, copied through a staging buffer of the handle before the call returns; on_device != 0: device

@@ -199,9 +199,10 @@ def _centres(vox, W, grid):
     return (W + v + 0.5) * _res(grid)
 
 
-def rays_of(grid, state, W):
+def rays_of(grid, state, W, last=None):
     """(origins [4096, 3], targets [4096, 3], family [4096]) float32: the ray families of tests/test_raycast.py on the map
-    (state, W) built by build_map -- the outcome of each is known by construction:
+    (state, W) built by build_map -- the outcome of each is known by construction (last: the (ego, cloud) that stand for "the
+    last scan" below, for a map whose last scan is not scan N_SCANS - 1: tests/query_cycle.py):
       0  1024  end in (even rows) or 3 voxels behind (odd rows) the centre of an occupied voxel, from the last ego: stopped at or
                before it (the walk samples the dominant axis once per voxel, so it looks into the voxel around a centre it passes)
       1  1024  returns of scan 2 from that scan's ego, cut to half their range: mostly CLEAR
@@ -216,7 +217,8 @@ def rays_of(grid, state, W):
                inside and outside the window"""
     xr, zr, xy, zs = GRIDS[grid]
     res = _res(grid)
-    last = np.array(ego_of(grid, N_SCANS - 1), np.float64)
+    last_ego, last_cloud = last if last is not None else (ego_of(grid, N_SCANS - 1), cloud_of(grid, N_SCANS - 1))
+    last = np.array(last_ego, np.float64)
     rng = np.random.default_rng(7)
     A, B, fam = [], [], []
 
@@ -234,7 +236,7 @@ def rays_of(grid, state, W):
     ret = cloud_of(grid, 2).astype(np.float64)
     ret = ret[_spread(np.arange(len(ret)), 1024)]
     add(ego2, ego2 + 0.5 * (ret - ego2), 1)
-    ret = cloud_of(grid, N_SCANS - 1).astype(np.float64)
+    ret = last_cloud.astype(np.float64)
     v = np.floor(ret / res - W)
     outside = ~((v >= 0) & (v < np.array([xy, xy, zs]))).all(axis=1)
     outside &= ((ret - last) ** 2).sum(axis=1) >= synth.REF_TAIL[0] ** 2           # (the scan drops returns closer than min_distance)

@@ -291,9 +291,36 @@ def test_asynchronous_combine_with_several_scans_before_its_end(gvom_mod):
     oldest slot -- a source of the fusion in flight -- the next spare one, and the SECOND scan writes it.  A long
     ring (40 slots of a 256 x 256 x 64 grid: a fusion of several hundred microseconds) and tiny clouds (a scan
     of a few tens) make that overlap certain; the main stream must wait for the fusion before it touches the
-    slot, and the read hooks before they read the fused map.  Everything equals the synchronous mapper's."""
+    slot, and the read hooks before they read the fused map.  Everything equals the synchronous mapper's.
+    The product calls read the fused map too: in rounds 2 to 5 raycast, occupancy_grid_device and score_alignments are issued on
+    both mappers -- on the asynchronous one while its fusion is in flight, each kind once as the FIRST call behind
+    combine_maps_async() (the call that has to join the second stream; round 3 keeps the read hook first) -- and their products
+    must be bit-identical.  Two schedules of the same kernels are compared here; tests/test_query_cycle.py holds the same calls to
+    their referees on small maps."""
     params = (0.2, 0.2, 256, 64, 40, 0.5, 0.5, 0.5, 0.3, 2.0, 4.0, 1.0, 1, 1)
     rng = np.random.default_rng(21)
+    # 512 segments and 2,048 returns inside the window of every round (the egos of rounds 0 .. 5 lie within 3 m of (11, -7, 0.5);
+    # the window is 51.2 m wide and 12.8 m high), 16 candidate poses; a generator of their own: the clouds' stay as they were
+    qrng = np.random.default_rng(77)
+    centre = np.array([10.0, -6.0, 0.5])
+    seg_a, seg_b = ((centre + qrng.uniform(-1, 1, (512, 3)) * (20.0, 20.0, 4.5)).astype(np.float32) for _ in range(2))
+    returns = (centre + qrng.uniform(-1, 1, (2048, 3)) * (20.0, 20.0, 2.0)).astype(np.float32)
+    poses = np.tile(np.identity(4), (16, 1, 1))
+    poses[:, :3, 3] = qrng.uniform(-0.6, 0.6, (16, 3)) * (1.0, 1.0, 0.2)
+    calls = {"raycast": lambda g: g.raycast(seg_a, seg_b, unknown_blocks=True),
+             "occupancy": lambda g: g.occupancy_grid_device(),
+             "alignments": lambda g: g.score_alignments(returns, poses, dilate=1)}
+    first = {2: "raycast", 3: "raycast", 4: "occupancy", 5: "alignments"}
+
+    def products(g, rnd):
+        """the three products of mapper g as bytes, the kind `first[rnd]` first"""
+        out = {}
+        for kind in [first[rnd]] + [k for k in sorted(calls) if k != first[rnd]]:
+            with calls[kind](g) as p:
+                parts = p.copy_to_host()
+                parts = parts if isinstance(parts, tuple) else (parts,)
+                out[kind] = [a.tobytes() for a in parts] + ([p.origin.tobytes()] if kind != "occupancy" else [])
+        return out
 
     def cloud(k, n):
         ego = (0.21 * k, -0.13 * k, 0.01 * k)
@@ -311,6 +338,11 @@ def test_asynchronous_combine_with_several_scans_before_its_end(gvom_mod):
             ad, bd = a.read_dense(gvom_mod.GVOM_WHICH_FUSED), b.read_dense(gvom_mod.GVOM_WHICH_FUSED)
             for j in range(4):
                 assert np.array_equal(ad[j], bd[j]), ("fused map read during the combine", j)
+        if rnd in first:                                             # the product calls while the fusion is in flight
+            bp, ap = products(b, rnd), products(a, rnd)
+            for kind in sorted(calls):
+                assert ap[kind] == bp[kind], ("round %d: the %s product differs between the two mappers" % (rnd, kind))
+            assert np.frombuffer(bp["occupancy"][0], np.uint8).sum() > 10000 and len(set(bp["raycast"][0])) > 4
         for _ in range(3 + rnd % 2):                                 # several tiny scans before the combine is ended
             pc, ego = cloud(k, 300); k += 1
             a.process_pointcloud(pc, ego); b.process_pointcloud(pc, ego)

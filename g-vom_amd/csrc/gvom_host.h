@@ -73,6 +73,7 @@ struct DevSet : SetShape {                     // (mem, xy, kind, zs, cap: gvom_
     std::vector<hipStream_t> rel_streams;      // release events since the set was written, one per consumer stream
     std::vector<hipEvent_t> rel, rel_spare;
     bool orphan = false;                       // the handle is gone
+    int64_t origin[3] = {0, 0, 0};             // a map set: the integer voxel origin of its window (the combine's, or the recall's x and y)
 };
 #define GVOM_MAX_DEVICE_SETS 8
 #define GVOM_N_PRODUCT_KINDS 4                  // the kinds gvom_device_product makes (clearance products, raycast products and cost fields have entry points of their own)
@@ -382,6 +383,18 @@ struct gvom_handle {
     int pf_allocs = 0;
     int tune_pf_inner = 0, tune_pf_batch = 0;           // gvom_set_tuning "pose_field_inner" / "pose_field_batch" (0: the defaults)
     int pf_last_rounds = 0, pf_last_tiles = 0;          // of the last call (gvom_get_tuning "pose_field_rounds" / "pose_field_tiles")
+    // MAP ATLAS (gvom_atlas_*): atl_mem = the ten planes of atl_A x atl_A cells (gvom_internal.h "map atlas"; atl_A == 0: none
+    // configured), atl_cnt = 256 bytes of int32 counters in device memory and atl_pin their pinned copy for gvom_atlas_counts,
+    // atl_stage = the staging copy of a caller's nine host maps.  atl_E = the extent's origin in world cells, atl_seq = integrates so far,
+    // atl_last = the origin of the last integrated set (the default of a recall; z is what a recall reports).  atl_allocs counts the
+    // device allocations the entry points have made on this handle (gvom_get_tuning "atlas_allocations")
+    char *atl_mem = nullptr;
+    int32_t *atl_cnt = nullptr, *atl_pin = nullptr;
+    Buf atl_stage;
+    int atl_A = 0, atl_follow = 1;
+    int64_t atl_E[2] = {0, 0}, atl_last[3] = {0, 0, 0};
+    int32_t atl_seq = 0;
+    int atl_allocs = 0;
 };
 
 namespace gvom_host {
@@ -454,6 +467,7 @@ DevSet *find_set(const std::vector<DevSet *> &sets, int64_t set_id);
 int set_wait_releases(gvom_handle *h, DevSet *set);
 int product_acquire(gvom_handle *h, int kind, size_t need_bytes, size_t new_bytes, const char *fn, int *allocs, DevSet **set);
 int product_publish(gvom_handle *h, DevSet *set, int64_t *product_id);
+int map_set_acquire(gvom_handle *h, const char *fn, DevSet **set);
 // gvom_product_calls.hip
 void occ_params(const gvom_handle *h, const Fused &F, OccParams &P);
 void cloud_params(const gvom_handle *h, const Fused &F, Map2dParams &P);

@@ -435,6 +435,29 @@ hipError_t gvom_launch_pose_relax(hipStream_t s, int xy, int H, int R, const uin
                                   int32_t max_cost, int inner);
 hipError_t gvom_launch_pose_actions(hipStream_t s, int xy, int H, const uint16_t *C, const int32_t *D, const int32_t *pstart,
                                     const int16_t *prims, uint8_t *action, uint32_t *reached);
+// map atlas (gvom_atlas.hip; include/gvom_hip.h "map atlas" defines the result).  The atlas is ten planes of A x A cells behind one
+// base address, A a power of two: the six f64 maps of a set (maps 3 .. 8) at k * A*A doubles, then the three i32 maps (0 .. 2) and
+// the int32 stamp at k * A*A ints; world cell (X, Y) at [(Y & (A-1)) * A + (X & (A-1))].  AtlasMaps = nine [y][x] maps of n x n cells
+// in set order (i[0..2] the i32 maps 0 .. 2, f[0..5] the f64 maps 3 .. 8, as bit patterns) and a stamp map; the recall skips a null
+// pointer.  Every window is given RELATIVE to the extent: rx, ry = window origin - extent origin (|.| <= 2^30, the host clamps), and
+// by its storage phase px, py = window origin & (A-1).  cnt = the atlas's counters, int32: [0..5] of the last integrate {written,
+// kept, uninformative, outside, made UNKNOWN by the move, of those known}, [6] cells of rank >= 1.
+#define GVOM_ATLAS_MIN_CELLS 64
+#define GVOM_ATLAS_MAX_CELLS 4096
+struct AtlasMaps {
+    int32_t *i[3];
+    unsigned long long *f[6];
+    int32_t *stamp;
+};
+inline size_t gvom_atlas_bytes(int A) { return (size_t)A * A * 64; }
+hipError_t gvom_launch_atlas_fill(hipStream_t s, char *atlas, int A, size_t first, size_t n);
+// move: the w x hgt cells from (rx, ry) / (px, py) on become UNKNOWN; counts them, and those that were known, into cnt[4], cnt[5], cnt[6]
+hipError_t gvom_launch_atlas_move(hipStream_t s, char *atlas, int A, int px, int py, int w, int hgt, int32_t *cnt);
+hipError_t gvom_launch_atlas_merge(hipStream_t s, char *atlas, int A, const AtlasMaps &in, int n, int rx, int ry, int px, int py,
+                                   int32_t seq, int32_t *cnt);
+// recall: n x n cells into `out`; counts (may be nullptr, else CLEARED by the caller) = {cells of rank 2, of rank 1, outside the extent, seq}
+hipError_t gvom_launch_atlas_recall(hipStream_t s, const char *atlas, int A, const AtlasMaps &out, int n, int rx, int ry, int px, int py,
+                                    int32_t seq, int32_t *counts);
 // storage order [sy][sx] -> reference order [x][y] (window coordinates)
 hipError_t gvom_launch_unwrap_f64(hipStream_t s, int xy, int om0, int om1, const double *in, int in_stride, double *out_xy);
 hipError_t gvom_launch_posdens(hipStream_t s, const Map2dParams &P, const int32_t *fstate,

@@ -27,6 +27,10 @@
 //   pose field (20)  cap x xy*xy int32 (cost to go), then cap x xy*xy uint8 (action), then cap x xy*xy uint16 (pose costs): volumes
 //                    [h][y][x], every plane laid out like a cost field's maps; cap = the headings H of the call that wrote it.  Kind 19
 //                    is not assigned
+//   recall (22)      xy*xy int32 (the stamps of a recalled map set, [y][x] like a device map), then 4 int32 {cells of rank 2, of rank 1,
+//                    outside the extent, seq}.  Kind 21 is not assigned
+//   extent (24)      the atlas's whole extent unwrapped, cap x cap cells, cap = the atlas's side A: the f64 maps roughness and height,
+//                    then the int32 maps positive, negative, visibility and stamp, all [y][x].  Kind 23 is not assigned
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -68,6 +72,8 @@ inline size_t set_bytes(int kind, int xy, int zs, int64_t cap, int64_t cols = 0)
     case GVOM_PRODUCT_FRONTIERS: return align256((size_t)cap * 32) + align256((size_t)cap * 16) + align256(n2 * 4) + 16;
     case GVOM_PRODUCT_VIEWPOINTS: return align256((size_t)cap * 32) + 16;
     case GVOM_PRODUCT_POSEFIELD: return align256((size_t)cap * n2 * 4) + align256((size_t)cap * n2) + (size_t)cap * n2 * 2;
+    case GVOM_PRODUCT_ATLAS_RECALL: return align256(n2 * 4) + 16;
+    case GVOM_PRODUCT_ATLAS_EXTENT: return (size_t)cap * (size_t)cap * 32;
     }
     return 0;
 }
@@ -164,6 +170,21 @@ inline bool set_part(const SetShape *s, int part, SetPart *d)
         d->shape[0] = s->cap; d->shape[1] = d->shape[2] = xy;
         d->strides[0] = n2; d->strides[1] = 1; d->strides[2] = xy;
         d->code = part ? kDLUInt : kDLInt; d->bits = part == 0 ? 32 : (part == 1 ? 8 : 16);
+        break;
+    }
+    case GVOM_PRODUCT_ATLAS_RECALL:
+        if (part == 0) { d->ptr = s->mem; d->shape[0] = d->shape[1] = xy; d->strides[0] = 1; d->strides[1] = xy; d->code = kDLInt; }   // [x, y] indexing, column-major, like a device map
+        else if (part == 1) { d->ptr = s->mem + align256((size_t)n2 * 4); d->ndim = 1; d->shape[0] = 4; d->strides[0] = 1; d->shape[1] = d->strides[1] = 1; d->code = kDLInt; }
+        else return false;
+        break;
+    case GVOM_PRODUCT_ATLAS_EXTENT: {                      // [x, y] indexing over the extent, column-major: parts 0 .. 2 and 5 int32, 3 and 4 f64
+        if (part < 0 || part > 5) return false;
+        const size_t a2 = (size_t)s->cap * (size_t)s->cap;
+        static const int at[6] = {0, 1, 2, 0, 1, 3};       // the part's place among the int32 maps / the f64 maps
+        const bool f64 = part == 3 || part == 4;
+        d->ptr = f64 ? s->mem + (size_t)at[part] * a2 * 8 : s->mem + 16 * a2 + (size_t)at[part] * a2 * 4;
+        d->shape[0] = d->shape[1] = s->cap; d->strides[0] = 1; d->strides[1] = s->cap;
+        d->code = f64 ? kDLFloat : kDLInt; d->bits = f64 ? 64 : 32;
         break;
     }
     default: return false;

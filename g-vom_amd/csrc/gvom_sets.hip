@@ -105,7 +105,28 @@ static int set_new(gvom_handle *h, std::vector<DevSet *> &sets, int kind, size_t
     return GVOM_OK;
 }
 
+// a new map set (at most GVOM_MAX_DEVICE_SETS; GVOM_ERR_CAPACITY, in fn's name, beyond)
+static int map_set_new(gvom_handle *h, const char *fn, DevSet **set)
+{
+    if ((int)h->dsets.size() >= GVOM_MAX_DEVICE_SETS) {
+        h->err = std::string(fn) + ": all 8 device map sets are exported; release some (gvom_device_map_release, or drop the tensors)";
+        return GVOM_ERR_CAPACITY;
+    }
+    const int rc = set_new(h, h->dsets, 0, set_bytes(0, h->prm.xy_size, 0, (int64_t)dev_map_stride(h->prm.xy_size)), set);
+    if (rc) return rc;
+    (*set)->cap = (int64_t)dev_map_stride(h->prm.xy_size);                  // (a map set: the elements from one map to the next)
+    return GVOM_OK;
+}
+
 namespace gvom_host {
+// the pool path of a call that writes a map set (gvom_atlas_recall; gvom_combine_maps_device has the same two steps around its empty-ring
+// answer): unused sets go back to the pool, then a free one, or a new one
+int map_set_acquire(gvom_handle *h, const char *fn, DevSet **set)
+{
+    if ((*set = set_recycle(h->dsets, 0, 0))) return GVOM_OK;
+    return map_set_new(h, fn, set);
+}
+
 // a reused set: its consumers' reads come first (the handle's stream waits on every release event)
 int set_wait_releases(gvom_handle *h, DevSet *set)
 {
@@ -118,13 +139,15 @@ int set_wait_releases(gvom_handle *h, DevSet *set)
 
 // the pool path of every product call: a free set of `kind` that holds need_bytes (free sets of the kind that are too small are given
 // up), or a new one of new_bytes counted in *allocs (null: not counted); GVOM_ERR_CAPACITY, in fn's name, with GVOM_MAX_PRODUCT_SETS held
+// (GVOM_MAX_DEVICE_SETS of the stamps of recalled map sets)
 int product_acquire(gvom_handle *h, int kind, size_t need_bytes, size_t new_bytes, const char *fn, int *allocs, DevSet **set)
 {
     if ((*set = set_recycle(h->psets, kind, need_bytes))) return GVOM_OK;
     int n = 0;
     for (DevSet *s : h->psets) n += s->kind == kind;
-    if (n >= GVOM_MAX_PRODUCT_SETS) {
-        h->err = std::string(fn) + ": all 4 device product sets of this kind are exported; release some (gvom_device_product_release, or drop the tensors)";
+    const int most = kind == GVOM_PRODUCT_ATLAS_RECALL ? GVOM_MAX_DEVICE_SETS : GVOM_MAX_PRODUCT_SETS;   // (a recall's stamps go with its map set: as many)
+    if (n >= most) {
+        h->err = std::string(fn) + ": all " + std::to_string(most) + " device product sets of this kind are exported; release some (gvom_device_product_release, or drop the tensors)";
         return GVOM_ERR_CAPACITY;
     }
     const int rc = set_new(h, h->psets, kind, new_bytes, set);
@@ -252,13 +275,8 @@ VIS int gvom_combine_maps_device(gvom_t *h, double origin_world[3], int64_t *set
     DevSet *set = set_recycle(h->dsets, 0, 0);
     if (!set && !h->slots[h->ring[h->last_buffer_index]].filled) return GVOM_EMPTY_BUFFER;
     if (!set) {
-        if ((int)h->dsets.size() >= GVOM_MAX_DEVICE_SETS) {
-            h->err = "gvom_combine_maps_device: all 8 device map sets are exported; release some (gvom_device_map_release, or drop the tensors)";
-            return GVOM_ERR_CAPACITY;
-        }
-        const int rc0 = set_new(h, h->dsets, 0, set_bytes(0, h->prm.xy_size, 0, (int64_t)dev_map_stride(h->prm.xy_size)), &set);
+        const int rc0 = map_set_new(h, "gvom_combine_maps_device", &set);
         if (rc0) return rc0;
-        set->cap = (int64_t)dev_map_stride(h->prm.xy_size);                 // (a map set: the elements from one map to the next)
     }
     if (!h->ev_dcount) HIPCHK(h, hipEventCreateWithFlags(&h->ev_dcount, hipEventDisableTiming));
     int rc = fuse_impl(h);
@@ -270,6 +288,7 @@ VIS int gvom_combine_maps_device(gvom_t *h, double origin_world[3], int64_t *set
     h->count_pending = true;
     set->id = ++h->dset_seq;
     *set_id = set->id;
+    for (int k = 0; k < 3; ++k) set->origin[k] = h->fused[h->cur].origin[k];
     HT(h, 2, t0);
     world_origin(h, h->fused[h->cur], origin_world);
     return GVOM_OK;
@@ -285,6 +304,16 @@ VIS int gvom_device_map_export(gvom_t *h, int64_t set_id, int which, void *consu
     if (rc) return rc;
     *ptr = d.ptr;
     strides[0] = d.strides[0]; strides[1] = d.strides[1];
+    return GVOM_OK;
+}
+
+VIS int gvom_device_map_origin(gvom_t *h, int64_t set_id, int64_t origin_cells[3])
+{
+    if (!h || !origin_cells) return GVOM_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(h->mu);
+    DevSet *s = find_set(h->dsets, set_id);
+    if (!s) { h->err = "unknown or stale device map set id"; return GVOM_ERR_INVALID; }
+    for (int k = 0; k < 3; ++k) origin_cells[k] = s->origin[k];
     return GVOM_OK;
 }
 

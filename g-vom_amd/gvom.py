@@ -171,6 +171,13 @@ ABI = [
     ("gvom_score_viewpoints", _I, [_P, _P, _I64, _I, ctypes.c_double, ctypes.c_int32, ctypes.c_int32, _I, _P, ctypes.POINTER(_I64)]),
     ("gvom_primitives_set", _I, [_P, ctypes.c_int32, _P, _P]),
     ("gvom_pose_field", _I, [_P, _I64, _P, _I, _P, _I64, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(_I64), ctypes.POINTER(_I64)]),
+    ("gvom_device_map_origin", _I, [_P, _I64, ctypes.POINTER(_I64)]),
+    ("gvom_atlas_configure", _I, [_P, ctypes.c_int32, _I, ctypes.POINTER(_I64)]),
+    ("gvom_atlas_integrate", _I, [_P, _I64, ctypes.POINTER(_P), _I, ctypes.POINTER(_I64)]),
+    ("gvom_atlas_recall", _I, [_P, ctypes.POINTER(_I64), ctypes.POINTER(_I64), ctypes.POINTER(_I64), _P]),
+    ("gvom_atlas_extent", _I, [_P, ctypes.POINTER(_I64), ctypes.POINTER(_I64)]),
+    ("gvom_atlas_clear", _I, [_P]),
+    ("gvom_atlas_counts", _I, [_P, ctypes.POINTER(_I64)]),
     ("gvom_set_profiling", _I, [_P, _I]),
     ("gvom_host_timing", _I, [_P, ctypes.POINTER(ctypes.c_double * 8)]),
     ("gvom_set_tuning", _I, [_P, ctypes.c_char_p, _I]),
@@ -506,7 +513,9 @@ class DeviceMap(object):
 
 class DeviceMaps(_Export):
     """The result of Gvom.combine_maps_device(): the nine maps of one combine in device memory (one map set), as DeviceMap
-    attributes named after the reference's (DEVICE_MAP_NAMES), `.origin` (f64[3], world) and `.set_id`.  It holds one export
+    attributes named after the reference's (DEVICE_MAP_NAMES), `.origin` (f64[3], world), `.origin_cells` (the same corner as the
+    three integer voxel indices the library counts it in) and `.set_id`.  A set an Atlas recalled also has `.stamps` (a DeviceArray,
+    int32 [x, y]: the integrate that last wrote each cell, 0 = never) and `.recall_counts`.  It holds one export
     of the set -- the set is not reused while it lives -- given back by release(), by leaving a `with` block, or when it is
     collected.  Tensors taken through DLPack hold exports of their own and stay valid after release() (and after the mapper)."""
     _release_name, _id_name = "gvom_device_map_release", "set_id"
@@ -518,11 +527,21 @@ class DeviceMaps(_Export):
         p, st = ctypes.c_void_p(), (_I64 * 2)()
         owner._check(owner._lib.gvom_device_map_export(owner._h, set_id, 0, ctypes.c_void_p(_STREAM_NOSYNC), ctypes.byref(p), st))
         self._held = True
+        cells = (_I64 * 3)()
+        owner._check(owner._lib.gvom_device_map_origin(owner._h, set_id, cells))
+        self.origin_cells = tuple(int(v) for v in cells)
 
     def __getattr__(self, name):
         if name in DEVICE_MAP_NAMES:
             return DeviceMap(self, DEVICE_MAP_NAMES.index(name))
         raise AttributeError(name)
+
+    def release(self):
+        """Gives the export back -- and, of a recalled set, the one its `.stamps` and `.recall_counts` share."""
+        _Export.release(self)
+        hold = self.__dict__.get("_recall_hold")
+        if hold is not None:
+            hold.release()
 
     def clearance(self, density_threshold=50, include_negative=True, max_distance=None):
         """Distance of every cell to the nearest hard obstacle of this set's positive / negative maps -- a cell is one iff
@@ -573,6 +592,8 @@ PRODUCT_ATTITUDE = 14                     # GVOM_PRODUCT_ATTITUDE: made by gvom_
 PRODUCT_FRONTIERS = 16                    # GVOM_PRODUCT_FRONTIERS: made by gvom_frontiers (kind 15 is not assigned)
 PRODUCT_VIEWPOINTS = 18                   # GVOM_PRODUCT_VIEWPOINTS: made by gvom_score_viewpoints (kind 17 is not assigned)
 PRODUCT_POSEFIELD = 20                    # GVOM_PRODUCT_POSEFIELD: made by gvom_pose_field (kind 19 is not assigned)
+PRODUCT_ATLAS_RECALL = 22                 # GVOM_PRODUCT_ATLAS_RECALL: made by gvom_atlas_recall, beside its map set (kind 21 is not assigned)
+PRODUCT_ATLAS_EXTENT = 24                 # GVOM_PRODUCT_ATLAS_EXTENT: made by gvom_atlas_extent (kind 23 is not assigned)
 # element type of part k of a product, by kind (what set_part() of csrc/gvom_setlayout.h gives as DLPack code and bits)
 _PRODUCT_DTYPES = {PRODUCT_OCCUPANCY: (np.uint8,), PRODUCT_VOXEL_CLOUD: (np.float32, np.float32, np.int64),
                    PRODUCT_HEIGHT_CLOUD: (np.float32,), PRODUCT_INFERRED_HEIGHT_CLOUD: (np.float32,),
@@ -580,7 +601,8 @@ _PRODUCT_DTYPES = {PRODUCT_OCCUPANCY: (np.uint8,), PRODUCT_VOXEL_CLOUD: (np.floa
                    PRODUCT_COSTFIELD: (np.int32, np.uint8, np.uint16), PRODUCT_ROLLOUTS: (np.int32, np.uint16),
                    PRODUCT_ALIGNMENT: (np.int32, np.int32), PRODUCT_ATTITUDE: (np.int32, np.float32, np.uint8),
                    PRODUCT_FRONTIERS: (np.int32, np.int64, np.int32, np.int32), PRODUCT_VIEWPOINTS: (np.int32, np.int32),
-                   PRODUCT_POSEFIELD: (np.int32, np.uint8, np.uint16)}
+                   PRODUCT_POSEFIELD: (np.int32, np.uint8, np.uint16), PRODUCT_ATLAS_RECALL: (np.int32, np.int32),
+                   PRODUCT_ATLAS_EXTENT: (np.int32, np.int32, np.int32, np.float64, np.float64, np.int32)}
 CLEARANCE_FAR = 2147483647                # GVOM_CLEARANCE_FAR: squared_cells where no obstacle is in reach
 _CLEARANCE_NO_NEGATIVE = 1                # GVOM_CLEARANCE_NO_NEGATIVE
 
@@ -1622,6 +1644,170 @@ class DeviceAlignments(_ProductView):
         return self.counts.copy_to_host(), self.best.copy_to_host()
 
 
+# ---- map atlas (Gvom.create_atlas; include/gvom_hip.h "map atlas") ----------------------------------------------------
+ATLAS_MIN_CELLS, ATLAS_MAX_CELLS = 64, 4096
+ATLAS_FOLLOW, ATLAS_FIXED = 0, 1          # GVOM_ATLAS_FOLLOW, GVOM_ATLAS_FIXED
+ATLAS_EXTENT_NAMES = ("positive", "negative", "visibility", "roughness", "height_map", "stamp")    # part 0..5 of an extent export
+
+
+def cells_of(points_xy, xy_resolution):
+    """World metres -> the integer world cells the atlas counts in: floor(p / xy_resolution), int64, same shape."""
+    p = np.asarray(points_xy, dtype=np.float64)
+    if not np.isfinite(p).all():
+        raise ValueError("points_xy must be finite")
+    return np.floor(p / float(xy_resolution)).astype(np.int64)
+
+
+def _atlas_cells(cells, xy_size):
+    c = int(cells)
+    if c != cells or c < ATLAS_MIN_CELLS or c > ATLAS_MAX_CELLS or c & (c - 1):
+        raise ValueError("cells must be a power of two in %d .. %d, got %r" % (ATLAS_MIN_CELLS, ATLAS_MAX_CELLS, cells))
+    if c < xy_size:
+        raise ValueError("cells must be at least xy_size (%d), got %d" % (xy_size, c))
+    return c
+
+
+def _atlas_origin(origin_cells, what="origin_cells"):
+    o = np.asarray(origin_cells)
+    if o.shape != (2,) or o.dtype.kind not in "iu":
+        raise ValueError("%s must be two integers (x, y) in world cells, got %r" % (what, origin_cells))
+    if (np.abs(o.astype(np.int64)) > (1 << 40)).any():
+        raise ValueError("%s lies beyond 2^40 cells" % what)
+    return (_I64 * 2)(int(o[0]), int(o[1]))
+
+
+def _atlas_maps(maps, xy_size):
+    """nine [x, y] numpy maps in set order -> Fortran-ordered arrays of the set's dtypes (nothing is cast: bit patterns count)"""
+    if len(maps) != 9:
+        raise ValueError("maps must be the nine maps of a set (DEVICE_MAP_NAMES), got %d" % len(maps))
+    out = []
+    for k, m in enumerate(maps):
+        a = np.asarray(m)
+        want = np.int32 if k < 3 else np.float64
+        if a.shape != (xy_size, xy_size):
+            raise ValueError("%s must have shape (%d, %d), got %r" % (DEVICE_MAP_NAMES[k], xy_size, xy_size, a.shape))
+        if a.dtype != want:
+            raise TypeError("%s must be %s, got %s" % (DEVICE_MAP_NAMES[k], np.dtype(want), a.dtype))
+        out.append(np.asfortranarray(a))
+    return out
+
+
+class DeviceAtlasExtent(_ProductView):
+    """The result of Atlas.extent_device(): the whole extent unwrapped, six DeviceArrays of one product named as in
+    ATLAS_EXTENT_NAMES, each [A, A], [x, y]-indexed with strides (1, A): cell (origin_cells[0] + x, origin_cells[1] + y) at [x, y]."""
+
+    def __init__(self, hold, origin_cells):
+        _ProductView.__init__(self, hold)
+        self.origin_cells = origin_cells
+        for k, name in enumerate(ATLAS_EXTENT_NAMES):
+            setattr(self, name, DeviceArray(hold, k))
+
+    def copy_to_host(self):
+        return tuple(getattr(self, name).copy_to_host() for name in ATLAS_EXTENT_NAMES)
+
+
+class Atlas(object):
+    """The map atlas of a mapper (Gvom.create_atlas): a world-fixed, toroidally stored memory of the nine 2-D maps, `cells` x `cells`
+    world cells of device memory (64 bytes each), that keeps what the rolling window forgets.  integrate() merges a combine's set
+    into it on the GPU -- observed ground is never overwritten by an inference or by nothing --, recall() returns any window-sized
+    part of it as an ordinary DeviceMaps, on which clearance(), cost_to_go(), score_attitude() and DeviceCostField.frontiers() work
+    as on a combine's.  Only counts() waits for the GPU.  include/gvom_hip.h "map atlas" has the definition."""
+
+    def __init__(self, owner, cells, follow, origin_cells):
+        self._owner = owner
+        self.cells = _atlas_cells(cells, owner.xy_size)
+        self.follow = bool(follow)
+        if not self.follow and origin_cells is None:
+            raise ValueError("a fixed atlas needs origin_cells, the corner of its extent")
+        org = None if origin_cells is None else _atlas_origin(origin_cells)
+        owner._check_args(owner._lib.gvom_atlas_configure(owner._h, self.cells, ATLAS_FOLLOW if self.follow else ATLAS_FIXED, org))
+        self.extent_origin = (0, 0) if org is None else (int(org[0]), int(org[1]))
+        self.seq = 0
+        self._last = None                       # the last integrated set's origin: the default of recall()
+
+    def _integrated(self, origin):
+        g = self._owner
+        self._last = (int(origin[0]), int(origin[1]))
+        self.seq += 1
+        if self.follow:
+            self.extent_origin = tuple(o + g.xy_size // 2 - self.cells // 2 for o in self._last)
+
+    def integrate(self, device_maps):
+        """Merges a live DeviceMaps (a combine's, or a recall's) into the atlas, behind the kernel that wrote it; no host wait."""
+        g = self._owner
+        g._check_args(g._lib.gvom_atlas_integrate(g._h, int(device_maps.set_id), None, 0, None))
+        self._integrated(device_maps.origin_cells)
+
+    def integrate_of(self, maps, origin_cells):
+        """The same for nine numpy maps in set order (DEVICE_MAP_NAMES), [x, y] of shape (xy_size, xy_size), int32 / float64 as
+        DeviceMap.copy_to_host() gives them, and the integer origin of their window.  The maps are copied to the device."""
+        g = self._owner
+        arrs = _atlas_maps(maps, g.xy_size)
+        org = _atlas_origin(origin_cells)
+        ptrs = (_P * 9)(*[a.ctypes.data for a in arrs])
+        g._check_args(g._lib.gvom_atlas_integrate(g._h, -1, ptrs, 0, org))
+        self._integrated(org)
+
+    def integrate_of_device(self, ptrs, origin_cells):
+        """The same for nine maps in device memory: raw device addresses in set order (cell (x, y) at [y*xy_size + x]); the data
+        must be ready when the call is made."""
+        g = self._owner
+        if len(ptrs) != 9 or not all(ptrs):
+            raise ValueError("ptrs must be nine device addresses, the maps of a set in order")
+        org = _atlas_origin(origin_cells)
+        g._check_args(g._lib.gvom_atlas_integrate(g._h, -1, (_P * 9)(*[int(p) for p in ptrs]), 1, org))
+        self._integrated(org)
+
+    def recall(self, origin_cells=None, center=None):
+        """A window-sized part of the atlas as a DeviceMaps -- with `.stamps` and `.recall_counts` = DeviceArrays of int32 [x, y]
+        and {cells of rank 2, of rank 1, outside the extent, seq} -- whose corner is origin_cells (integer world cells), or the
+        window a scan with its ego at `center` (x, y in world metres) would have: floor(c / xy_resolution - xy_size / 2), the
+        scan's own arithmetic.  Default: the last integrated set's origin.  Cells outside the extent read UNKNOWN.  No host wait."""
+        g = self._owner
+        if origin_cells is not None and center is not None:
+            raise ValueError("give origin_cells or center, not both")
+        if center is not None:
+            c = np.asarray(center, dtype=np.float64)
+            if c.shape != (2,) or not np.isfinite(c).all():
+                raise ValueError("center must be two finite numbers (x, y) in metres, got %r" % (center,))
+            origin_cells = [int(math.floor(v / g.xy_resolution - g.xy_size / 2.0)) for v in c]
+        org = None if origin_cells is None else _atlas_origin(origin_cells)
+        sid, pid, world = ctypes.c_int64(-1), ctypes.c_int64(-1), np.zeros(3, np.float64)
+        g._check_args(g._lib.gvom_atlas_recall(g._h, org, ctypes.byref(sid), ctypes.byref(pid), _ptr(world)))
+        maps = DeviceMaps(g, int(sid.value), world)
+        hold = _ProductHold(g, PRODUCT_ATLAS_RECALL, int(pid.value))
+        maps.stamps, maps.recall_counts = DeviceArray(hold, 0), DeviceArray(hold, 1)
+        maps._recall_hold = hold
+        return maps
+
+    def extent_device(self):
+        """The whole extent unwrapped, as a DeviceAtlasExtent (32 bytes per cell).  No host wait."""
+        g = self._owner
+        e = (_I64 * 2)()
+        hold = g._make_product(lambda pid: g._lib.gvom_atlas_extent(g._h, pid, e), PRODUCT_ATLAS_EXTENT, g._check_args)
+        return DeviceAtlasExtent(hold, (int(e[0]), int(e[1])))
+
+    def clear(self):
+        """Every cell becomes UNKNOWN; the extent and seq stay."""
+        g = self._owner
+        g._check_args(g._lib.gvom_atlas_clear(g._h))
+
+    def counts(self):
+        """Waits for the GPU.  A dict: of the last integrate `written`, `kept`, `uninformative`, `outside`, `cleared`,
+        `cleared_known`; of the atlas `known` (cells of rank >= 1) and `seq`."""
+        g = self._owner
+        out = (_I64 * 8)()
+        g._check_args(g._lib.gvom_atlas_counts(g._h, out))
+        names = ("written", "kept", "uninformative", "outside", "cleared", "cleared_known", "known", "seq")
+        return dict(zip(names, (int(v) for v in out)))
+
+    def release(self):
+        """Frees the atlas's device memory."""
+        g = self._owner
+        if g._h:
+            g._check_args(g._lib.gvom_atlas_configure(g._h, 0, 0, None))
+
+
 class _OutputPool(object):
     """Free pinned output buffers of one Gvom.  Outlives the Gvom if returned arrays do: a buffer that
     comes back after the mapper is gone is released at once (pinned host memory is not tied to the
@@ -2447,6 +2633,14 @@ class Gvom(object):
         H = self._pose_headings()
         cells = _pose_goals(goals, self.xy_size, H, None)
         return self._pose_field(-1, _dev(cost_ptr), 1, cells, _ctg_max_cost(max_cost), _ctg_max_rounds(max_rounds), origin)
+
+    # ---- map atlas (an extension; include/gvom_hip.h "map atlas") ----
+    def create_atlas(self, cells, follow=True, origin_cells=None):
+        """Configures the mapper's atlas -- one per mapper; a second call replaces the first -- and returns it: `cells` x `cells`
+        world cells (a power of two in 64 .. 4096, at least xy_size; 64 bytes of device memory each).  follow=True: the extent
+        re-centres on every integrated set and forgets what leaves it; follow=False: it stays at origin_cells (its corner, integer
+        world cells) and sets outside it are skipped.  See Atlas."""
+        return Atlas(self, cells, follow, origin_cells)
 
     # ---- scan alignment scoring (an extension; include/gvom_hip.h "scan alignment scoring") ----
     def _score_alignments(self, cloud_ptr, n, tf_ptr, K, on_device, dilate, weights):

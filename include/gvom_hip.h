@@ -904,6 +904,77 @@ int gvom_primitives_set(gvom_t *h, int32_t n_headings, const int32_t *start /* [
 int gvom_pose_field(gvom_t *h, int64_t costfield_id, const int32_t *cost, int on_device, const int32_t *goals /* [n_goals][3] */,
                     int64_t n_goals, int32_t max_cost, int32_t max_rounds, int64_t *product_id, int64_t info[4]);
 
+/* --- map atlas (an extension: a world-fixed memory of the 2-D maps beyond the rolling window -- what the vehicle drove over a minute
+ * ago is still known when it has to plan a way back) ------------------------------------------------------------------------------------
+ * The atlas is a larger, toroidally stored copy of the nine maps of a map set plus a last-written stamp, in device memory, one per
+ * handle.  Each device combine's set can be merged into it on the GPU (gvom_atlas_integrate), and any window-sized part of it comes
+ * back as an ordinary map set (gvom_atlas_recall) that every call taking a map_set_id accepts.  gvom_get_tuning "atlas" (read-only):
+ * the side A of the configured atlas, 0 without one -- how a caller probes a library for these entry points (an addition:
+ * GVOM_ABI_VERSION stays).  Everything is copied or counted: the results are exact and do not depend on scheduling.
+ *
+ * DEFINITION.
+ * CELLS      world cell (X, Y) is the integer voxel column index a map set's origin is counted in: a set with integer origin (Ox, Oy)
+ *            holds cell (Ox + x, Oy + y) at [y*xy_size + x].  gvom_device_map_origin reads the integer origin of a live set.
+ * STORAGE    A x A cells, A a power of two, 64 <= A <= 4096, A >= xy_size; ten planes: the six f64 maps and the three i32 maps of a
+ *            set, and an int32 stamp; cell (X, Y) at [(Y & (A-1)) * A + (X & (A-1))] of each plane (the AND is the floor-modulo, also
+ *            of negative coordinates).  64 bytes per cell, 1 GiB at 4096, allocated once by gvom_atlas_configure.
+ * EXTENT     the A x A world cells [Ex, Ex+A) x [Ey, Ey+A) the atlas currently stands for.  gvom_atlas_configure sets E to
+ *            fixed_origin ((0, 0) where that is NULL) and every cell to UNKNOWN.
+ * UNKNOWN    positive 0, negative 0, visibility 0, roughness -1.0, height -1000.0, inferred height -1000.0, x slope 0.0, y slope 0.0,
+ *            guessed delta 0.0, stamp 0: what a combine writes where it knows nothing.
+ * RANK       of a cell's nine values: 2 (observed) iff visibility > 0; 1 (inferred) iff visibility <= 0 and (negative > 0 or inferred
+ *            height > -1000.0); 0 otherwise.
+ * INTEGRATE  of a set with origin O, two steps.  MOVE (GVOM_ATLAS_FOLLOW only): the extent goes to E' = O + floor(xy_size/2) - A/2 per
+ *            axis; every cell of the new extent that was not in the old one becomes UNKNOWN (the cells that left lose their storage to
+ *            these); a move of A or more on an axis makes everything UNKNOWN.  With GVOM_ATLAS_FIXED the extent never moves.  MERGE:
+ *            seq is incremented (the first integrate after a configure has seq 1); for every cell of the set inside the extent, with
+ *            r_new the rank of the set's values and r_old the rank of the atlas's, the cell is WRITTEN iff r_new >= 1 and r_new >=
+ *            r_old -- all nine values copied bit for bit, stamp = seq -- and stays as it is otherwise.  Observed ground is never
+ *            overwritten by an inference or by nothing; a cell that re-enters the window unseen keeps what was known about it.
+ * COUNTERS   int32, in device memory, filled by wave-combined integer atomics.  gvom_atlas_counts -- the only atlas call that WAITS --
+ *            reads out[0..5] of the last integrate: {written, kept (r_new >= 1 but < r_old), uninformative (inside the extent, r_new
+ *            == 0), outside the extent, cells made UNKNOWN by the move, of those how many had rank >= 1}; out[6] cells of rank >= 1 in
+ *            the atlas; out[7] seq.  The first four sum to xy_size^2.
+ * RECALL     for any integer origin (Rx, Ry) (NULL: the last integrated set's): a complete map set of xy_size x xy_size cells -- the
+ *            atlas's nine values where a cell lies in the extent, UNKNOWN elsewhere.  The set comes from the pool of at most 8 sets
+ *            gvom_combine_maps_device takes its sets from, under the same rule: an unexported set goes back to the pool when the next
+ *            device combine OR RECALL begins; its ready event is recorded on the handle's stream and its id comes from the same
+ *            sequence: it is a map set in every respect.  origin_world (may be NULL) = (Rx, Ry) * xy_resolution, and the last
+ *            integrated set's z origin * z_resolution (0 where pointers were integrated), which is informational: heights are world
+ *            metres.  With it comes a product of kind GVOM_PRODUCT_ATLAS_RECALL: part 0 int32 [xy, xy], the stamps, [x, y]-indexed
+ *            with strides (1, xy) like a device map; part 1 int32 [4] {cells of rank 2, cells of rank 1, cells outside the extent, seq}.
+ *            Of this kind a handle holds up to 8 product sets, one per map set, not GVOM_MAX_PRODUCT_SETS.
+ * EXTENT EXPORT   gvom_atlas_extent: a product of kind GVOM_PRODUCT_ATLAS_EXTENT, the whole extent unwrapped -- [A, A], [x, y]-indexed
+ *            with strides (1, A), cell (Ex + x, Ey + y) at [y*A + x]: parts 0 positive, 1 negative, 2 visibility (int32), 3 roughness,
+ *            4 height (f64), 5 stamp (int32); 32 bytes per cell.  extent_origin (may be NULL) receives (Ex, Ey).  Consumers that plan
+ *            at atlas scale read it in place, or on a second handle through the *_of_device calls.
+ *
+ * INPUT of gvom_atlas_integrate, one of two.  map_set_id >= 0: a live device map set (maps and origin_cells must be NULL); the merge
+ * runs on the handle's stream behind the combine or recall that wrote it.  map_set_id < 0: `maps`, nine pointers in set order (0
+ * positive .. 8 guessed delta, [y][x], xy_size^2 elements each), and their integer origin; on_device != 0: device addresses, read in
+ * place (the data must be ready when the call is made); on_device == 0: host arrays, staged through a buffer of the handle.
+ * Integrate, recall, extent and clear ENQUEUE on the handle's stream and return (the host route of integrate waits for its upload).
+ * gvom_atlas_configure(cells, mode, fixed_origin) allocates or re-allocates; cells == 0 frees.  gvom_atlas_clear sets every cell to
+ * UNKNOWN and the counters to 0; the extent and seq stay.  "atlas_allocations" (read-only): device allocations the entry points have
+ * made on this handle (the planes, the counters, the staging buffer of the host route and the product sets); it does not grow in
+ * steady state.  gvom_device_product(kind 22 / 24) is GVOM_ERR_INVALID (these calls make them).  Kinds 21 and 23 are not assigned.
+ * GVOM_ERR_INVALID: a sharded handle; no atlas configured; cells not a power of two, outside 64 .. 4096 or below xy_size; an unknown
+ * mode; id and pointers mixed, or neither; a NULL map; a stale id; an origin beyond 2^40 cells; NULL outputs.  GVOM_ERR_CAPACITY: a
+ * recall with all 8 map sets exported; every product set of the kind exported.
+ * NOT PROVIDED: a coarser level or pyramid; a "latest wins" policy; time decay; 3-D memory; more than one atlas per handle; sharded
+ * handles; saving to disk; DLPack views of the toroidal planes themselves. */
+#define GVOM_PRODUCT_ATLAS_RECALL 22   /* part 0 int32 [xy, xy] stamps; part 1 int32 [4] {rank 2, rank 1, outside, seq} */
+#define GVOM_PRODUCT_ATLAS_EXTENT 24   /* parts 0 .. 2 int32 positive, negative, visibility; 3, 4 f64 roughness, height; 5 int32 stamp: [A, A], strides (1, A) */
+#define GVOM_ATLAS_FOLLOW 0
+#define GVOM_ATLAS_FIXED  1
+int gvom_device_map_origin(gvom_t *h, int64_t map_set_id, int64_t origin_cells[3]);
+int gvom_atlas_configure(gvom_t *h, int32_t cells, int mode, const int64_t fixed_origin[2] /* may be NULL */);
+int gvom_atlas_integrate(gvom_t *h, int64_t map_set_id, const void *const maps[9], int on_device, const int64_t origin_cells[2]);
+int gvom_atlas_recall(gvom_t *h, const int64_t origin_cells[2] /* may be NULL */, int64_t *map_set_id, int64_t *product_id, double origin_world[3]);
+int gvom_atlas_extent(gvom_t *h, int64_t *product_id, int64_t extent_origin[2]);
+int gvom_atlas_clear(gvom_t *h);
+int gvom_atlas_counts(gvom_t *h, int64_t out[8]);
+
 /* --- one map sharded over the GPUs of a node (one rank = one process = one GPU) -------------------
  * No counterpart in the reference (it has no multi-GPU path); semantics = SURVEY 8(e):
  * the rays are data-parallel, the per-voxel accumulators (hit / total: int32 sum, min-height: f32 min)

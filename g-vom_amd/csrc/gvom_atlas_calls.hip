@@ -2,7 +2,8 @@
 // _extent, _clear and _counts.  The kernels are gvom_atlas.hip's; everything runs on the handle's stream -- behind the combine that
 // wrote the set an integrate reads, in front of whatever recycles that set later -- and only gvom_atlas_counts waits for it.  A recall
 // writes a map set of the pool gvom_combine_maps_device takes its sets from (map_set_acquire, gvom_sets.hip) and a product set for the
-// stamps; the extent export is a product like the others.
+// stamps; the extent export is a product like the others.  Below them the atlas fields (include/gvom_hip.h "atlas fields"):
+// gvom_atlas_cost_to_go, which waits like gvom_cost_to_go, and gvom_atlas_field_window; their kernels are gvom_atlas_field.hip's.
 #include "gvom_host.h"
 
 namespace {
@@ -233,5 +234,124 @@ VIS int gvom_atlas_counts(gvom_t *h, int64_t out[8])
     for (int k = 0; k < 7; ++k) out[k] = h->atl_pin[k];
     out[7] = h->atl_seq;
     return GVOM_OK;
+}
+
+// ---- atlas fields (include/gvom_hip.h "atlas fields") -----------------------------------------------------------------------------------
+// gvom_cost_to_go's solve at the atlas's side: the front ends of gvom_atlas_field.hip read the toroidal planes in place and write the
+// unwrapped obstacle distances and cost map, k_clearance_cols and the solver (ctg_solve, gvom_product_calls.hip) run on those as on any
+// [y][x] map of A x A cells.  The buffers are the handle's own at side A (af_work, af_clr): gvom_cost_to_go's stay as they are.
+VIS int gvom_atlas_cost_to_go(gvom_t *h, const gvom_ctg_params *params, const int64_t *goals, int64_t n_goals, int32_t max_cost,
+                              int32_t max_rounds, int flags, int64_t *product_id, int64_t info[4], int64_t extent_origin[2])
+{
+    if (!h || !product_id) return GVOM_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(h->mu);
+    *product_id = -1;
+    for (int k = 0; info && k < 4; ++k) info[k] = 0;
+    int rc = need_atlas(h, "gvom_atlas_cost_to_go");
+    if (rc) return rc;
+    if (flags & ~(GVOM_CTG_NO_NEGATIVE | GVOM_CTG_UNKNOWN_BLOCKS)) { h->err = "gvom_atlas_cost_to_go: unknown flag bits"; return GVOM_ERR_INVALID; }
+    if (!params) { h->err = "gvom_atlas_cost_to_go: the cost parameters must not be NULL"; return GVOM_ERR_INVALID; }
+    if (!goals || n_goals < 1 || n_goals > GVOM_CTG_MAX_GOALS) { h->err = "gvom_atlas_cost_to_go: between 1 and 65536 goals"; return GVOM_ERR_INVALID; }
+    if (max_cost < 0 || max_cost > GVOM_CTG_MAX_COST) { h->err = "gvom_atlas_cost_to_go: max_cost outside 0 .. 2^30"; return GVOM_ERR_INVALID; }
+    if (max_rounds < 0) { h->err = "gvom_atlas_cost_to_go: max_rounds must not be negative"; return GVOM_ERR_INVALID; }
+    CtgCostParams C;
+    if ((rc = ctg_cost_params(h, "gvom_atlas_cost_to_go", params, flags, &C))) return rc;
+    const int A = h->atl_A;
+    const int64_t E[2] = {h->atl_E[0], h->atl_E[1]};
+    std::vector<int32_t> rel((size_t)2 * n_goals);                          // the goals as the solver takes them: extent cells
+    for (int64_t k = 0; k < 2 * n_goals; ++k) {
+        const int64_t g = goals[k], e = E[k & 1];
+        if (g < e || g >= e + A) {
+            h->err = "gvom_atlas_cost_to_go: a goal lies outside the extent: cell (" + std::to_string(goals[k & ~(int64_t)1]) + ", " +
+                     std::to_string(goals[k | 1]) + "), extent [" + std::to_string(E[0]) + ", " + std::to_string(E[0] + A) + ") x [" +
+                     std::to_string(E[1]) + ", " + std::to_string(E[1] + A) + ")";
+            return GVOM_ERR_INVALID;
+        }
+        rel[k] = (int32_t)(g - e);
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    DevSet *set = nullptr;
+    const size_t a2 = (size_t)A * A, bytes = set_bytes(GVOM_PRODUCT_ATLAS_FIELD, 0, 0, A);
+    if ((rc = product_acquire(h, GVOM_PRODUCT_ATLAS_FIELD, bytes, bytes, "gvom_atlas_cost_to_go", &h->af_allocs, &set))) return rc;
+    set->cap = A;
+    const int nt = gvom_ctg_tiles(A), ntiles = nt * nt;
+    const size_t flags_off = 256, goals_off = flags_off + align256((size_t)2 * ntiles * 4), work = goals_off + (size_t)GVOM_CTG_MAX_GOALS * 8;
+    if (h->af_work.bytes < work) {
+        if ((rc = ensure(h, h->af_work, work))) return rc;
+        ++h->af_allocs;
+    }
+    const size_t clr_g = align256(a2 * 2), clr_map = align256(a2 * 4);
+    if (C.inflation_cells2 > 0 && h->af_clr.bytes < clr_g + 2 * clr_map) {
+        if ((rc = ensure(h, h->af_clr, clr_g + 2 * clr_map))) return rc;
+        ++h->af_allocs;
+    }
+    if (!h->af_pin) HIPCHK(h, hipHostMalloc((void **)&h->af_pin, 256, hipHostMallocDefault));
+    uint32_t *cnt = (uint32_t *)h->af_work.p;
+    uint32_t *fl = (uint32_t *)((char *)h->af_work.p + flags_off);
+    int32_t *gdev = (int32_t *)((char *)h->af_work.p + goals_off);
+    HIPCHK(h, join_second_stream(h));
+    HIPCHK(h, hipMemcpyAsync(gdev, rel.data(), (size_t)n_goals * 8, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemsetAsync(cnt, 0, 256, h->stream));
+    if ((rc = set_wait_releases(h, set))) return rc;
+    SetPart d;
+    set_part(set, 0, &d); int32_t *D = (int32_t *)d.ptr;
+    set_part(set, 1, &d); uint8_t *dir = (uint8_t *)d.ptr;
+    set_part(set, 2, &d); uint16_t *c16 = (uint16_t *)d.ptr;
+    const Window w = window_of(h, E);                                       // (its storage phase is the extent's)
+    const int32_t *cd2 = nullptr;
+    if (C.inflation_cells2 > 0) {
+        char *q = (char *)h->af_clr.p;
+        HIPCHK(h, gvom_launch_atlas_clearance_rows(h->stream, h->atl_mem, A, w.px, w.py, C.use_negative != 0, C.density_threshold, (uint16_t *)q));
+        HIPCHK(h, gvom_launch_clearance_cols(h->stream, A, h->prm.xy_resolution, C.inflation_cells2, (const uint16_t *)q, (float *)(q + clr_g),
+                                             (int32_t *)(q + clr_g + clr_map)));
+        cd2 = (const int32_t *)(q + clr_g + clr_map);
+    }
+    HIPCHK(h, gvom_launch_atlas_travcost(h->stream, h->atl_mem, A, w.px, w.py, cd2, C, c16));
+    CtgSolve S;
+    if ((rc = ctg_solve(h, A, nullptr, c16, D, dir, cnt, fl, gdev, (int)n_goals, max_cost, max_rounds, h->af_pin, &S))) return rc;
+    set->origin[0] = E[0]; set->origin[1] = E[1]; set->origin[2] = 0;
+    if ((rc = product_publish(h, set, product_id))) return rc;             // (`ready` goes in front of the counters' way back)
+    HIPCHK(h, hipMemcpyAsync(h->af_pin, cnt, 256, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (!S.converged && max_rounds == 0) { set->id = *product_id = -1; h->err = "gvom_atlas_cost_to_go: the field did not settle"; return GVOM_ERR_HIP; }   // (nobody gets it)
+    h->af_last_tiles = (int)std::min<int64_t>(S.tiles, INT32_MAX);
+    if (info) { info[0] = S.converged ? 1 : 0; info[1] = S.rounds; info[2] = h->af_pin[CTG_CNT_REACHED]; info[3] = h->af_pin[CTG_CNT_SEEDED]; }
+    if (extent_origin) { extent_origin[0] = E[0]; extent_origin[1] = E[1]; }
+    return GVOM_OK;
+}
+
+VIS int gvom_atlas_field_window(gvom_t *h, int64_t field_id, int64_t map_set_id, const int64_t origin_cells[2], int64_t *product_id)
+{
+    if (!h || !product_id) return GVOM_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(h->mu);
+    *product_id = -1;
+    if (h->sharded) { h->err = "gvom_atlas_field_window: sharded handles are not supported"; return GVOM_ERR_INVALID; }
+    DevSet *f = find_set(h->psets, field_id);
+    if (!f || f->kind != GVOM_PRODUCT_ATLAS_FIELD) { h->err = "gvom_atlas_field_window: unknown or stale atlas field id"; return GVOM_ERR_INVALID; }
+    if (map_set_id >= 0 && origin_cells) { h->err = "gvom_atlas_field_window: give a map set id or origin_cells, not both"; return GVOM_ERR_INVALID; }
+    if (map_set_id < 0 && !origin_cells) { h->err = "gvom_atlas_field_window: give a map set id or origin_cells"; return GVOM_ERR_INVALID; }
+    int64_t R[2];
+    if (map_set_id >= 0) {
+        DevSet *m = find_set(h->dsets, map_set_id);
+        if (!m) { h->err = "unknown or stale device map set id"; return GVOM_ERR_INVALID; }
+        R[0] = m->origin[0]; R[1] = m->origin[1];
+    } else {
+        if (!origin_ok(origin_cells)) { h->err = "gvom_atlas_field_window: an origin beyond 2^40 cells"; return GVOM_ERR_INVALID; }
+        R[0] = origin_cells[0]; R[1] = origin_cells[1];
+    }
+    const int xy = h->prm.xy_size, A = (int)f->cap;
+    HIPCHK(h, hipSetDevice(h->device));
+    DevSet *set = nullptr;
+    const size_t bytes = set_bytes(GVOM_PRODUCT_COSTFIELD, xy, 0, 0);
+    int rc = product_acquire(h, GVOM_PRODUCT_COSTFIELD, bytes, bytes, "gvom_atlas_field_window", &h->af_allocs, &set);
+    if (rc) return rc;
+    HIPCHK(h, join_second_stream(h));
+    if ((rc = set_wait_releases(h, set))) return rc;
+    SetPart fd[3], od[3];
+    for (int k = 0; k < 3; ++k) { set_part(f, k, &fd[k]); set_part(set, k, &od[k]); }
+    const int rx = (int)std::max(-AT_REL, std::min(AT_REL, R[0] - f->origin[0])), ry = (int)std::max(-AT_REL, std::min(AT_REL, R[1] - f->origin[1]));
+    HIPCHK(h, gvom_launch_atlas_field_window(h->stream, A, (const int32_t *)fd[0].ptr, (const uint8_t *)fd[1].ptr, (const uint16_t *)fd[2].ptr, xy, rx, ry,
+                                             (int32_t *)od[0].ptr, (uint8_t *)od[1].ptr, (uint16_t *)od[2].ptr));
+    return product_publish(h, set, product_id);
 }
 }  // extern "C"

@@ -7,56 +7,19 @@
 // arithmetic below 2^31 (xy <= 4096: at most 2 * 4095^2), so the result is exact; the metres are one float64 square root and one
 // float64 multiply rounded once to float32 (the build has no contraction and no fast math).
 #include "gvom_device.h"
+#include "gvom_clearance_rows.h"
 
-// "no obstacle in this row": 46341^2 = 2,147,488,281 > INT32_MAX, so as an unsigned candidate it never beats a limit that
-// fits int32, and 46341^2 + 4095^2 still fits 32 bits: the column pass needs no test for it
-#define GVOM_CLR_NONE 46341u
-
-// One workgroup per map row, one wave per 64 cells.  Pass 1: every wave's obstacle ballot goes to LDS (at most 64 masks:
-// xy <= 4096).  Pass 2: the nearest obstacle to the left / right of a lane is found in the wave's own mask with clz / ffs on
-// the bits at or below / at or above the lane; where the mask has none, in the nearest non-empty mask on that side, which one
-// more ballot (over the masks themselves) names.  No loop over cells, no division.
+// the row pass over a [y][x] map pair (gvom_clearance_rows.h has the body)
 __global__ __launch_bounds__(256) void k_clearance_rows(const int32_t *__restrict__ pos, const int32_t *__restrict__ neg,
                                                         const double thr, const int xy, const int gp, uint16_t *__restrict__ g)
 {
     __shared__ unsigned long long s_mask[64];
-    const int lane = threadIdx.x & (WAVE - 1);
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int y = blockIdx.x;
-    const int nchunks = gp >> 6;
-    for (int c = wave; c < nchunks; c += 4) {
-        const int x = c * 64 + lane;
-        bool ob = false;
-        if (x < xy) {
-            ob = (double)pos[(size_t)y * xy + x] > thr;
-            if (neg) ob = ob || neg[(size_t)y * xy + x] > 0;
-        }
-        const unsigned long long m = __ballot(ob);
-        if (lane == 0) s_mask[c] = m;
-    }
-    __syncthreads();
-    const unsigned long long nz = __ballot(lane < nchunks && s_mask[lane < nchunks ? lane : 0] != 0ull);
-    for (int c = wave; c < nchunks; c += 4) {
-        const unsigned long long own = s_mask[c];
-        const unsigned long long lo = nz & ((1ull << c) - 1ull);           // non-empty chunks left of c
-        const unsigned long long hi = c == 63 ? 0ull : nz >> (c + 1);      // ... right of c
-        int lpos = -(1 << 20), rpos = 1 << 20;                            // (wave-uniform) nearest obstacle outside the chunk
-        if (lo) {
-            const int cc = 63 - __clzll((long long)lo);
-            lpos = cc * 64 + 63 - __clzll((long long)s_mask[cc]);
-        }
-        if (hi) {
-            const int cc = c + __ffsll((unsigned long long)hi);
-            rpos = cc * 64 + __ffsll((unsigned long long)s_mask[cc]) - 1;
-        }
-        const int x = c * 64 + lane;
-        const unsigned long long ml = own & (~0ull >> (63 - lane));        // obstacles at or left of the lane
-        const unsigned long long mr = own >> lane;                         // at or right of it
-        const int dl = ml ? lane - (63 - __clzll((long long)ml)) : x - lpos;
-        const int dr = mr ? __ffsll((unsigned long long)mr) - 1 : rpos - x;
-        const int d = min(dl, dr);
-        g[(size_t)y * gp + x] = (uint16_t)(d > 4095 ? GVOM_CLR_NONE : (unsigned)d);
-    }
+    clearance_row([&](int x) {
+        bool ob = (double)pos[(size_t)y * xy + x] > thr;
+        if (neg) ob = ob || neg[(size_t)y * xy + x] > 0;
+        return ob;
+    }, xy, gp, g + (size_t)y * gp, s_mask);
 }
 
 // One workgroup per strip of W = 2^lgw columns and T output rows.  The rows of g the strip can need -- all of them, or the
@@ -102,14 +65,11 @@ __global__ __launch_bounds__(256) void k_clearance_cols(const uint32_t *__restri
 
 size_t gvom_clearance_scratch_bytes(int xy) { return (size_t)((xy + 63) & ~63) * (size_t)xy * sizeof(uint16_t); }
 
-hipError_t gvom_launch_clearance(hipStream_t s, int xy, double res, const int32_t *pos, const int32_t *neg, double thr,
-                                 int32_t max_cells2, uint16_t *g, float *out_dist, int32_t *out_d2, int shape[4])
+hipError_t gvom_launch_clearance_cols(hipStream_t s, int xy, double res, int32_t max_cells2, const uint16_t *g, float *out_dist,
+                                      int32_t *out_d2, int shape[4])
 {
     if (xy <= 0 || xy > GVOM_CLEARANCE_MAX_XY) return hipErrorInvalidValue;
     const int gp = (xy + 63) & ~63;
-    hipLaunchKernelGGL(k_clearance_rows, dim3(xy), dim3(256), 0, s, pos, neg, thr, xy, gp, g);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
     const bool capped = max_cells2 > 0 && max_cells2 < INT32_MAX;
     const uint32_t lim = capped ? (uint32_t)max_cells2 + 1u : (uint32_t)INT32_MAX;
     int halo = -1;
@@ -133,4 +93,15 @@ hipError_t gvom_launch_clearance(hipStream_t s, int xy, double res, const int32_
     hipLaunchKernelGGL(k_clearance_cols, dim3((xy + (1 << lgw) - 1) >> lgw, ytiles), dim3(256), lds, s, (const uint32_t *)g, gp, xy, lgw,
                        T, halo, lim, res, out_dist, out_d2);
     return hipGetLastError();
+}
+
+hipError_t gvom_launch_clearance(hipStream_t s, int xy, double res, const int32_t *pos, const int32_t *neg, double thr,
+                                 int32_t max_cells2, uint16_t *g, float *out_dist, int32_t *out_d2, int shape[4])
+{
+    if (xy <= 0 || xy > GVOM_CLEARANCE_MAX_XY) return hipErrorInvalidValue;
+    const int gp = (xy + 63) & ~63;
+    hipLaunchKernelGGL(k_clearance_rows, dim3(xy), dim3(256), 0, s, pos, neg, thr, xy, gp, g);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    return gvom_launch_clearance_cols(s, xy, res, max_cells2, g, out_dist, out_d2, shape);
 }

@@ -13,6 +13,7 @@
 // EARLIER launches wrote.  Every loop has a bound fixed at launch.
 // All arithmetic is unsigned 32-bit below 2^31 + 2^31 (UNREACHED + the "no step" weight): nothing wraps.
 #include "gvom_device.h"
+#include "gvom_travcost.h"
 
 #define CTG_T 32                       // cells per tile side
 #define CTG_P (CTG_T + 2)              // LDS pitch: the tile and its halo
@@ -34,12 +35,6 @@ __device__ __forceinline__ uint32_t ctg_weight(uint32_t cu, int k, F at)
     return ok ? (k & 1 ? 7u : 5u) * (cu + cv) : CTG_NOSTEP;
 }
 
-struct TravParams {
-    double thr, rmin, rmax;
-    int32_t infl2, base, soft, unknown, rough;
-    int32_t use_neg, unknown_blocks;
-};
-
 __global__ __launch_bounds__(256) void k_travcost(const int32_t *__restrict__ pos, const int32_t *__restrict__ neg,
                                                   const int32_t *__restrict__ vis, const double *__restrict__ rough,
                                                   const int32_t *__restrict__ d2, const TravParams P, const int n2,
@@ -47,19 +42,7 @@ __global__ __launch_bounds__(256) void k_travcost(const int32_t *__restrict__ po
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n2) return;
-    const int32_t p = pos[i], v = vis[i];
-    bool blocked = (double)p > P.thr;
-    if (P.use_neg) blocked = blocked || neg[i] > 0;
-    if (P.infl2 > 0) blocked = blocked || d2[i] <= P.infl2;
-    if (P.unknown_blocks) blocked = blocked || v == 0;
-    int64_t q = 0;
-    if (P.rough > 0) {
-        const double r = rough[i];
-        if (r > P.rmin) q = (int64_t)floor(((py_mind(r, P.rmax) - P.rmin) / (P.rmax - P.rmin)) * 100.0);
-    }
-    int64_t cost = (int64_t)P.base + (int64_t)P.soft * p + (v == 0 ? (int64_t)P.unknown : 0) + (int64_t)P.rough * q;
-    cost = cost > 65535 ? 65535 : cost;
-    c[i] = blocked ? (uint16_t)0 : (uint16_t)cost;
+    c[i] = trav_cell<false>(P, pos, neg, vis, rough, d2, i, i);       // (gvom_travcost.h)
 }
 
 __global__ __launch_bounds__(256) void k_ctg_seed(const int phase, const int xy, const int n2, const int32_t *__restrict__ cost32,

@@ -395,6 +395,15 @@ struct gvom_handle {
     int64_t atl_E[2] = {0, 0}, atl_last[3] = {0, 0, 0};
     int32_t atl_seq = 0;
     int atl_allocs = 0;
+    // ATLAS FIELDS (gvom_atlas_cost_to_go / gvom_atlas_field_window): the solver's buffers at the atlas's side A, apart from the
+    // window-sized ones of gvom_cost_to_go -- af_work = 256 bytes of counters (CTG_CNT_* above), the two halves of the tiles' activity
+    // flags, then the staged goals (65536 x 2 int32, relative to the extent); af_clr = the inflation's row distances (A*A uint16), a
+    // distance map nobody reads and d2 (A*A x 4 bytes each), allocated by the first call that inflates.  af_allocs counts those and the
+    // two entry points' product sets (gvom_get_tuning "atlas_field_allocations").  af_pin: the pinned copy of the counters.
+    Buf af_work, af_clr;
+    uint32_t *af_pin = nullptr;
+    int af_allocs = 0;
+    int af_last_tiles = 0;                              // tile relaxations of the last gvom_atlas_cost_to_go (gvom_get_tuning "atlas_field_tiles")
 };
 
 namespace gvom_host {
@@ -472,4 +481,13 @@ int map_set_acquire(gvom_handle *h, const char *fn, DevSet **set);
 void occ_params(const gvom_handle *h, const Fused &F, OccParams &P);
 void cloud_params(const gvom_handle *h, const Fused &F, Map2dParams &P);
 hipError_t launch_height_cloud(gvom_handle *h, const Fused &F, float *out7, float *out3);
+// the parts of gvom_cost_to_go that gvom_atlas_cost_to_go shares.  ctg_cost_params: the caller's cost parameters and flags checked
+// and turned into what the launchers take (GVOM_ERR_INVALID, in fn's name, for what the header says).  ctg_solve: seed, the batches
+// of rounds with the host's look at the counters between them, and the directions, on a map of n x n cells whose uint16 costs are in
+// c16 (or come from cost32); cnt / fl / gdev are the counters, the flags and the staged goals of a work buffer laid out for n, pin
+// the pinned copy of the counters.  It waits; the caller publishes the product and fetches the final counters.
+struct CtgSolve { bool converged = false; int64_t rounds = 0, tiles = 0; };
+int ctg_cost_params(gvom_handle *h, const char *fn, const gvom_ctg_params *params, int flags, CtgCostParams *C);
+int ctg_solve(gvom_handle *h, int n, const int32_t *cost32, uint16_t *c16, int32_t *D, uint8_t *dir, uint32_t *cnt, uint32_t *fl,
+              const int32_t *gdev, int n_goals, int32_t max_cost, int32_t max_rounds, uint32_t *pin, CtgSolve *out);
 }  // namespace gvom_host

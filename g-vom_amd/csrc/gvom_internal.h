@@ -314,6 +314,9 @@ hipError_t gvom_launch_raycast(hipStream_t s, const ScanParams &P, const RayQuer
 size_t gvom_clearance_scratch_bytes(int xy);
 hipError_t gvom_launch_clearance(hipStream_t s, int xy, double res, const int32_t *pos, const int32_t *neg, double thr,
                                  int32_t max_cells2, uint16_t *g, float *out_dist, int32_t *out_d2, int shape[4] = nullptr);
+// the column pass alone, over row distances somebody else wrote into g (pitch (xy + 63) & ~63): gvom_launch_clearance ends in it
+hipError_t gvom_launch_clearance_cols(hipStream_t s, int xy, double res, int32_t max_cells2, const uint16_t *g, float *out_dist,
+                                      int32_t *out_d2, int shape[4] = nullptr);
 // cost-to-go fields (gvom_costfield.hip; include/gvom_hip.h "cost-to-go fields" defines the result).  Every map is [y][x], xy x xy.
 // travcost: the uint16 cost map c (0 = blocked) from the int32 positive / negative / visibility maps, the f64 roughness map and
 // the clearance d2 (nullptr: no inflation).  seed: c from cost32 (clamped into 0..65535; nullptr: c is there already), D =
@@ -458,6 +461,18 @@ hipError_t gvom_launch_atlas_merge(hipStream_t s, char *atlas, int A, const Atla
 // recall: n x n cells into `out`; counts (may be nullptr, else CLEARED by the caller) = {cells of rank 2, of rank 1, outside the extent, seq}
 hipError_t gvom_launch_atlas_recall(hipStream_t s, const char *atlas, int A, const AtlasMaps &out, int n, int rx, int ry, int px, int py,
                                     int32_t seq, int32_t *counts);
+// atlas fields (gvom_atlas_field.hip; include/gvom_hip.h "atlas fields" defines the result).  The first two read the atlas's planes in
+// place through the extent's storage phase px, py = extent origin & (A-1) and write UNWRAPPED [y][x] arrays of A x A cells, extent cell
+// (x, y) at [y*A + x]: clearance_rows = the row pass of gvom_launch_clearance (g: A*A uint16, the pitch is A), to be followed by
+// gvom_launch_clearance_cols at side A; travcost = gvom_launch_travcost's cost map under the atlas's cell rule (d2 unwrapped, nullptr:
+// no inflation).  field_window: the n x n cells from (rx, ry) RELATIVE to the field's corner (|.| <= 2^30) of the three [A][A] planes
+// of a field into the three [n][n] planes of a cost field; INT32_MAX, 255 and 0 outside the field.
+hipError_t gvom_launch_atlas_clearance_rows(hipStream_t s, const char *atlas, int A, int px, int py, bool use_negative, double thr,
+                                            uint16_t *g);
+hipError_t gvom_launch_atlas_travcost(hipStream_t s, const char *atlas, int A, int px, int py, const int32_t *d2, const CtgCostParams &C,
+                                      uint16_t *c);
+hipError_t gvom_launch_atlas_field_window(hipStream_t s, int A, const int32_t *fD, const uint8_t *fdir, const uint16_t *fc, int n, int rx,
+                                          int ry, int32_t *oD, uint8_t *odir, uint16_t *oc);
 // storage order [sy][sx] -> reference order [x][y] (window coordinates)
 hipError_t gvom_launch_unwrap_f64(hipStream_t s, int xy, int om0, int om1, const double *in, int in_stride, double *out_xy);
 hipError_t gvom_launch_posdens(hipStream_t s, const Map2dParams &P, const int32_t *fstate,

@@ -49,6 +49,56 @@ hipError_t launch_height_cloud(gvom_handle *h, const Fused &F, float *out7, floa
     return gvom_launch_debug_height(h->stream, h->prm.xy_size, om[0], om[1], org, h->prm.xy_resolution, h->prm.z_resolution,
                                     h->height, h->hs, h->rough, h->slope_x, h->slope_y, out7, h->guessed, out3);
 }
+int ctg_cost_params(gvom_handle *h, const char *fn, const gvom_ctg_params *params, int flags, CtgCostParams *C)
+{
+    const gvom_ctg_params &p = *params;
+    const bool ok = p.density_threshold == p.density_threshold && p.inflation_cells2 >= 0 && p.base >= 1 &&
+                    p.soft_weight >= 0 && p.soft_weight <= 65535 && p.unknown_cost >= 0 && p.unknown_cost <= 65535 &&
+                    p.rough_weight >= 0 && p.rough_weight <= 65535 &&
+                    (p.rough_weight == 0 || (isfinite(p.min_roughness) && isfinite(p.max_roughness) && p.max_roughness > p.min_roughness));
+    if (!ok) { h->err = std::string(fn) + ": bad cost parameters (NaN threshold, base < 1, a weight outside 0 .. 65535, a negative inflation, or an empty / non-finite roughness range)"; return GVOM_ERR_INVALID; }
+    memset(C, 0, sizeof *C);
+    C->density_threshold = p.density_threshold; C->min_roughness = p.min_roughness; C->max_roughness = p.max_roughness;
+    C->inflation_cells2 = p.inflation_cells2; C->base = p.base; C->soft_weight = p.soft_weight; C->unknown_cost = p.unknown_cost;
+    C->rough_weight = p.rough_weight;
+    C->use_negative = (flags & GVOM_CTG_NO_NEGATIVE) ? 0 : 1; C->unknown_blocks = (flags & GVOM_CTG_UNKNOWN_BLOCKS) ? 1 : 0;
+    return GVOM_OK;
+}
+
+int ctg_solve(gvom_handle *h, int n, const int32_t *cost32, uint16_t *c16, int32_t *D, uint8_t *dir, uint32_t *cnt, uint32_t *fl,
+              const int32_t *gdev, int n_goals, int32_t max_cost, int32_t max_rounds, uint32_t *pin, CtgSolve *out)
+{
+    const int nt = gvom_ctg_tiles(n), ntiles = nt * nt;
+    HIPCHK(h, gvom_launch_ctg_seed(h->stream, n, cost32, c16, D, fl, gdev, n_goals, cnt + CTG_CNT_SEEDED));
+    const int32_t cap = max_cost == 0 ? GVOM_CTG_MAX_COST : max_cost;
+    const int inner = h->tune_ctg_inner > 0 ? h->tune_ctg_inner : 256;
+    const int batch = h->tune_ctg_batch > 0 ? h->tune_ctg_batch : 8;
+    // by induction over the tile crossings of a shortest path the solve ends after at most (crossings + 1) rounds of tiles that
+    // reach their fixed point; the limit below is beyond anything n <= 4096 can need and only keeps this loop finite
+    const int64_t limit = max_rounds > 0 ? (int64_t)max_rounds : (int64_t)1 << 22;
+    int64_t rounds = 0, tiles = 0;
+    bool converged = false;
+    while (!converged && rounds < limit) {
+        const int nb = (int)std::min<int64_t>(batch, limit - rounds);
+        if (rounds) HIPCHK(h, hipMemsetAsync(cnt, 0, 2 * GVOM_CTG_MAX_BATCH * 4, h->stream));
+        for (int r = 0; r < nb; ++r) {
+            const int64_t k = rounds + r;
+            HIPCHK(h, gvom_launch_ctg_relax(h->stream, n, c16, D, fl + (k & 1) * ntiles, fl + ((k + 1) & 1) * ntiles, cnt + r,
+                                            cnt + CTG_CNT_RELAXED + r, cap, inner));
+        }
+        HIPCHK(h, hipMemcpyAsync(pin, cnt, 2 * GVOM_CTG_MAX_BATCH * 4, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        int ran = nb;
+        for (int r = 0; r < nb; ++r) {
+            tiles += pin[CTG_CNT_RELAXED + r];
+            if (pin[r] == 0) { converged = true; ran = r + 1; break; }
+        }
+        rounds += ran;
+    }
+    HIPCHK(h, gvom_launch_ctg_dirs(h->stream, n, c16, D, dir, cnt + CTG_CNT_REACHED));
+    out->converged = converged; out->rounds = rounds; out->tiles = tiles;
+    return GVOM_OK;
+}
 }  // namespace gvom_host
 
 // part `part` of a set as a launcher takes it.  The part numbers below are literals: one the set's kind does not have is a mistake
@@ -262,18 +312,10 @@ VIS int gvom_cost_to_go(gvom_t *h, int64_t map_set_id, const gvom_ctg_params *pa
     memset(&C, 0, sizeof C);
     DevSet *m = nullptr;
     if (map_set_id >= 0) {
-        const gvom_ctg_params &p = *params;
-        const bool ok = p.density_threshold == p.density_threshold && p.inflation_cells2 >= 0 && p.base >= 1 &&
-                        p.soft_weight >= 0 && p.soft_weight <= 65535 && p.unknown_cost >= 0 && p.unknown_cost <= 65535 &&
-                        p.rough_weight >= 0 && p.rough_weight <= 65535 &&
-                        (p.rough_weight == 0 || (isfinite(p.min_roughness) && isfinite(p.max_roughness) && p.max_roughness > p.min_roughness));
-        if (!ok) { h->err = "gvom_cost_to_go: bad cost parameters (NaN threshold, base < 1, a weight outside 0 .. 65535, a negative inflation, or an empty / non-finite roughness range)"; return GVOM_ERR_INVALID; }
+        const int rcp = ctg_cost_params(h, "gvom_cost_to_go", params, flags, &C);
+        if (rcp) return rcp;
         m = find_set(h->dsets, map_set_id);
         if (!m) { h->err = "unknown or stale device map set id"; return GVOM_ERR_INVALID; }
-        C.density_threshold = p.density_threshold; C.min_roughness = p.min_roughness; C.max_roughness = p.max_roughness;
-        C.inflation_cells2 = p.inflation_cells2; C.base = p.base; C.soft_weight = p.soft_weight; C.unknown_cost = p.unknown_cost;
-        C.rough_weight = p.rough_weight;
-        C.use_negative = (flags & GVOM_CTG_NO_NEGATIVE) ? 0 : 1; C.unknown_blocks = (flags & GVOM_CTG_UNKNOWN_BLOCKS) ? 1 : 0;
     } else if (!on_device) {
         for (size_t k = 0; k < n2; ++k)
             if (cost[k] < 0 || cost[k] > 65535) { h->err = "gvom_cost_to_go: a host cost map holds a value outside 0 .. 65535"; return GVOM_ERR_INVALID; }
@@ -315,33 +357,10 @@ VIS int gvom_cost_to_go(gvom_t *h, int64_t map_set_id, const gvom_ctg_params *pa
         }
         HIPCHK(h, gvom_launch_travcost(h->stream, xy, mp, mn, part_ptr<const int32_t>(m, 2), part_ptr<const double>(m, 3), cd2, C, c16));
     }
-    HIPCHK(h, gvom_launch_ctg_seed(h->stream, xy, cost32, c16, D, fl, gdev, (int)n_goals, cnt + CTG_CNT_SEEDED));
-    const int32_t cap = max_cost == 0 ? GVOM_CTG_MAX_COST : max_cost;
-    const int inner = h->tune_ctg_inner > 0 ? h->tune_ctg_inner : 256;
-    const int batch = h->tune_ctg_batch > 0 ? h->tune_ctg_batch : 8;
-    // by induction over the tile crossings of a shortest path the solve ends after at most (crossings + 1) rounds of tiles that
-    // reach their fixed point; the limit below is beyond anything xy <= 4096 can need and only keeps this loop finite
-    const int64_t limit = max_rounds > 0 ? (int64_t)max_rounds : (int64_t)1 << 22;
-    int64_t rounds = 0, tiles = 0;
-    bool converged = false;
-    while (!converged && rounds < limit) {
-        const int nb = (int)std::min<int64_t>(batch, limit - rounds);
-        if (rounds) HIPCHK(h, hipMemsetAsync(cnt, 0, 2 * GVOM_CTG_MAX_BATCH * 4, h->stream));
-        for (int r = 0; r < nb; ++r) {
-            const int64_t k = rounds + r;
-            HIPCHK(h, gvom_launch_ctg_relax(h->stream, xy, c16, D, fl + (k & 1) * ntiles, fl + ((k + 1) & 1) * ntiles, cnt + r,
-                                            cnt + CTG_CNT_RELAXED + r, cap, inner));
-        }
-        HIPCHK(h, hipMemcpyAsync(h->ctg_pin, cnt, 2 * GVOM_CTG_MAX_BATCH * 4, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        int ran = nb;
-        for (int r = 0; r < nb; ++r) {
-            tiles += h->ctg_pin[CTG_CNT_RELAXED + r];
-            if (h->ctg_pin[r] == 0) { converged = true; ran = r + 1; break; }
-        }
-        rounds += ran;
-    }
-    HIPCHK(h, gvom_launch_ctg_dirs(h->stream, xy, c16, D, part_ptr<uint8_t>(set, 1), cnt + CTG_CNT_REACHED));
+    CtgSolve S;
+    if ((rc = ctg_solve(h, xy, cost32, c16, D, part_ptr<uint8_t>(set, 1), cnt, fl, gdev, (int)n_goals, max_cost, max_rounds, h->ctg_pin, &S))) return rc;
+    const bool converged = S.converged;
+    const int64_t rounds = S.rounds, tiles = S.tiles;
     if ((rc = product_publish(h, set, product_id))) return rc;             // (`ready` goes in front of the counters' way back)
     HIPCHK(h, hipMemcpyAsync(h->ctg_pin, cnt, 256, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));

@@ -31,6 +31,9 @@
 //                    outside the extent, seq}.  Kind 21 is not assigned
 //   extent (24)      the atlas's whole extent unwrapped, cap x cap cells, cap = the atlas's side A: the f64 maps roughness and height,
 //                    then the int32 maps positive, negative, visibility and stamp, all [y][x].  Kind 23 is not assigned
+//   atlas field (26) a cost field at the atlas's scale, cap x cap cells, cap = the side A of the atlas that made it: cap*cap int32 (cost
+//                    to go), then cap*cap uint8 (direction), then cap*cap uint16 (cell costs), all [y][x] over the field's own extent.
+//                    Kind 25 is not assigned
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -74,6 +77,7 @@ inline size_t set_bytes(int kind, int xy, int zs, int64_t cap, int64_t cols = 0)
     case GVOM_PRODUCT_POSEFIELD: return align256((size_t)cap * n2 * 4) + align256((size_t)cap * n2) + (size_t)cap * n2 * 2;
     case GVOM_PRODUCT_ATLAS_RECALL: return align256(n2 * 4) + 16;
     case GVOM_PRODUCT_ATLAS_EXTENT: return (size_t)cap * (size_t)cap * 32;
+    case GVOM_PRODUCT_ATLAS_FIELD: return align256((size_t)cap * (size_t)cap * 4) + align256((size_t)cap * (size_t)cap) + (size_t)cap * (size_t)cap * 2;
     }
     return 0;
 }
@@ -185,6 +189,14 @@ inline bool set_part(const SetShape *s, int part, SetPart *d)
         d->ptr = f64 ? s->mem + (size_t)at[part] * a2 * 8 : s->mem + 16 * a2 + (size_t)at[part] * a2 * 4;
         d->shape[0] = d->shape[1] = s->cap; d->strides[0] = 1; d->strides[1] = s->cap;
         d->code = f64 ? kDLFloat : kDLInt; d->bits = f64 ? 64 : 32;
+        break;
+    }
+    case GVOM_PRODUCT_ATLAS_FIELD: {                       // [x, y] indexing over the field's extent, column-major, like a cost field's maps
+        if (part < 0 || part > 2) return false;
+        const size_t a2 = (size_t)s->cap * (size_t)s->cap;
+        d->ptr = s->mem + (part ? align256(a2 * 4) : 0) + (part == 2 ? align256(a2) : 0);
+        d->shape[0] = d->shape[1] = s->cap; d->strides[0] = 1; d->strides[1] = s->cap;
+        d->code = part ? kDLUInt : kDLInt; d->bits = part == 0 ? 32 : (part == 1 ? 8 : 16);
         break;
     }
     default: return false;

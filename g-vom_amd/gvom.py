@@ -178,6 +178,9 @@ ABI = [
     ("gvom_atlas_extent", _I, [_P, ctypes.POINTER(_I64), ctypes.POINTER(_I64)]),
     ("gvom_atlas_clear", _I, [_P]),
     ("gvom_atlas_counts", _I, [_P, ctypes.POINTER(_I64)]),
+    ("gvom_atlas_cost_to_go", _I, [_P, _P, ctypes.POINTER(_I64), _I64, ctypes.c_int32, ctypes.c_int32, _I, ctypes.POINTER(_I64),
+                                   ctypes.POINTER(_I64), ctypes.POINTER(_I64)]),
+    ("gvom_atlas_field_window", _I, [_P, _I64, _I64, ctypes.POINTER(_I64), ctypes.POINTER(_I64)]),
     ("gvom_set_profiling", _I, [_P, _I]),
     ("gvom_host_timing", _I, [_P, ctypes.POINTER(ctypes.c_double * 8)]),
     ("gvom_set_tuning", _I, [_P, ctypes.c_char_p, _I]),
@@ -594,6 +597,7 @@ PRODUCT_VIEWPOINTS = 18                   # GVOM_PRODUCT_VIEWPOINTS: made by gvo
 PRODUCT_POSEFIELD = 20                    # GVOM_PRODUCT_POSEFIELD: made by gvom_pose_field (kind 19 is not assigned)
 PRODUCT_ATLAS_RECALL = 22                 # GVOM_PRODUCT_ATLAS_RECALL: made by gvom_atlas_recall, beside its map set (kind 21 is not assigned)
 PRODUCT_ATLAS_EXTENT = 24                 # GVOM_PRODUCT_ATLAS_EXTENT: made by gvom_atlas_extent (kind 23 is not assigned)
+PRODUCT_ATLAS_FIELD = 26                  # GVOM_PRODUCT_ATLAS_FIELD: made by gvom_atlas_cost_to_go (kind 25 is not assigned)
 # element type of part k of a product, by kind (what set_part() of csrc/gvom_setlayout.h gives as DLPack code and bits)
 _PRODUCT_DTYPES = {PRODUCT_OCCUPANCY: (np.uint8,), PRODUCT_VOXEL_CLOUD: (np.float32, np.float32, np.int64),
                    PRODUCT_HEIGHT_CLOUD: (np.float32,), PRODUCT_INFERRED_HEIGHT_CLOUD: (np.float32,),
@@ -602,7 +606,8 @@ _PRODUCT_DTYPES = {PRODUCT_OCCUPANCY: (np.uint8,), PRODUCT_VOXEL_CLOUD: (np.floa
                    PRODUCT_ALIGNMENT: (np.int32, np.int32), PRODUCT_ATTITUDE: (np.int32, np.float32, np.uint8),
                    PRODUCT_FRONTIERS: (np.int32, np.int64, np.int32, np.int32), PRODUCT_VIEWPOINTS: (np.int32, np.int32),
                    PRODUCT_POSEFIELD: (np.int32, np.uint8, np.uint16), PRODUCT_ATLAS_RECALL: (np.int32, np.int32),
-                   PRODUCT_ATLAS_EXTENT: (np.int32, np.int32, np.int32, np.float64, np.float64, np.int32)}
+                   PRODUCT_ATLAS_EXTENT: (np.int32, np.int32, np.int32, np.float64, np.float64, np.int32),
+                   PRODUCT_ATLAS_FIELD: (np.int32, np.uint8, np.uint16)}
 CLEARANCE_FAR = 2147483647                # GVOM_CLEARANCE_FAR: squared_cells where no obstacle is in reach
 _CLEARANCE_NO_NEGATIVE = 1                # GVOM_CLEARANCE_NO_NEGATIVE
 
@@ -1706,6 +1711,129 @@ class DeviceAtlasExtent(_ProductView):
         return tuple(getattr(self, name).copy_to_host() for name in ATLAS_EXTENT_NAMES)
 
 
+def _atlas_field_goals(goals, xy_resolution, extent_origin, cells):
+    """goals -> C-contiguous int64 (G, 2) WORLD cells inside the extent; xy_resolution for goals in world metres (cells_of), None for
+    cells.  ValueError for what gvom_atlas_cost_to_go would refuse; a goal outside the extent names the cell and the extent."""
+    a = np.asarray(goals)
+    if a.ndim == 1 and a.shape[0] == 2:
+        a = a.reshape(1, 2)
+    if a.ndim != 2 or a.shape[1] != 2 or not 1 <= a.shape[0] <= CTG_MAX_GOALS:
+        raise ValueError("goals must have shape (G, 2) with 1 <= G <= %d, got %r" % (CTG_MAX_GOALS, a.shape))
+    if a.dtype.kind not in "iuf":
+        raise ValueError("goals must be numbers, got dtype %s" % a.dtype)
+    if a.dtype.kind == "f" and not np.isfinite(a).all():
+        raise ValueError("goals must be finite")
+    if xy_resolution is not None:
+        a = cells_of(a, xy_resolution)
+    elif a.dtype.kind == "f":
+        if (a != np.floor(a)).any():
+            raise ValueError("goals in cells must be whole numbers")
+    a = a.astype(np.int64)
+    lo = np.array(extent_origin, np.int64)
+    out = ((a < lo) | (a >= lo + cells)).any(axis=1)
+    if out.any():
+        bad = a[out][0]
+        raise ValueError("a goal lies outside the extent: cell (%d, %d), extent [%d, %d) x [%d, %d)" % (
+            bad[0], bad[1], lo[0], lo[0] + cells, lo[1], lo[1] + cells))
+    return np.ascontiguousarray(a)
+
+
+def _follow_directions(d, x, y, stop_at_border):
+    """the cells from (x, y) down the direction codes of the [x, y] array d, both ends included; None from an unreached cell.  A
+    step that leaves the array ends the path at the last cell inside (stop_at_border) or is an error."""
+    path = [(x, y)]
+    for _ in range(d.size):
+        k = int(d[x, y])
+        if k == CTG_GOAL:
+            return path
+        if k == CTG_NONE:
+            return None
+        if k >= 8:
+            raise RuntimeError("cell (%d, %d) is unsettled: the field stopped before it converged" % (x, y))
+        x, y = x + CTG_STEPS[k][0], y + CTG_STEPS[k][1]
+        if not (0 <= x < d.shape[0] and 0 <= y < d.shape[1]):
+            if stop_at_border:
+                return path
+            raise RuntimeError("the directions lead out of the field")
+        path.append((x, y))
+    raise RuntimeError("the directions do not lead to a goal")
+
+
+class DeviceAtlasFieldWindow(DeviceCostField):
+    """The result of DeviceAtlasField.window(): the part of an atlas field under a window, as a DeviceCostField -- score_rollouts(),
+    frontiers() and pose_field() work on it as on any other.  `.origin` is the window corner in world metres, `.origin_cells` the same
+    in world cells; `.converged`, `.rounds`, `.reached` and `.goals_seeded` are the FIELD's.  Cells outside the field's extent read
+    CTG_UNREACHED / CTG_NONE / 0.  `.direction` is the field's: at the border a step may point out of the window."""
+
+    def __init__(self, hold, info, origin, origin_cells):
+        DeviceCostField.__init__(self, hold, info, origin)
+        self.origin_cells = (int(origin_cells[0]), int(origin_cells[1]))
+
+    def path_from(self, cell):
+        """The part of the path from window cell (x, y) that lies inside the window: it ends at a goal, or at the last cell before
+        the step that leaves the window (the global path goes on there: DeviceAtlasField.path_from).  None where unreached."""
+        if self._host is None:
+            self._host = self.direction.copy_to_host()
+        x, y = int(cell[0]), int(cell[1])
+        if not (0 <= x < self._host.shape[0] and 0 <= y < self._host.shape[1]):
+            raise ValueError("cell (%d, %d) lies outside the window" % (x, y))
+        return _follow_directions(self._host, x, y, True)
+
+
+class DeviceAtlasField(_ProductView):
+    """The result of Atlas.cost_to_go(): the cost-to-go field of the atlas's whole extent -- `.cost` int32, `.direction` uint8 and
+    `.cell_cost` uint16, each [A, A], three DeviceArrays of one product, [x, y]-indexed with strides (1, A): world cell
+    (origin_cells[0] + x, origin_cells[1] + y) at [x, y], with the values of a DeviceCostField.  `.origin_cells` is the extent's
+    corner when the field was made, `.origin` the same in world metres; `.converged`, `.rounds`, `.reached` and `.goals_seeded`
+    describe the solve.  A snapshot: later integrates, moves of the extent, clear() and a new create_atlas() do not change it.
+    copy_to_host() returns (cost, direction, cell_cost) as Fortran-ordered numpy [x, y]."""
+
+    def __init__(self, hold, info, origin_cells, xy_resolution):
+        _ProductView.__init__(self, hold)
+        self.cost, self.direction, self.cell_cost = DeviceArray(hold, 0), DeviceArray(hold, 1), DeviceArray(hold, 2)
+        self.converged, self.rounds, self.reached, self.goals_seeded = bool(info[0]), int(info[1]), int(info[2]), int(info[3])
+        self.origin_cells = (int(origin_cells[0]), int(origin_cells[1]))
+        self._res = float(xy_resolution)
+        self.origin = np.array(self.origin_cells, np.float64) * self._res
+        self._host = None
+
+    def copy_to_host(self):
+        return self.cost.copy_to_host(), self.direction.copy_to_host(), self.cell_cost.copy_to_host()
+
+    def path_from(self, cell):
+        """The WORLD cells from world cell `cell` = (x, y) to a goal, both included, following `.direction` on a host copy (made
+        once); None where the cell is unreached.  RuntimeError on CTG_UNSETTLED (a field that stopped before it converged)."""
+        if self._host is None:
+            self._host = self.direction.copy_to_host()
+        ox, oy = self.origin_cells
+        x, y = int(cell[0]) - ox, int(cell[1]) - oy
+        if not (0 <= x < self._host.shape[0] and 0 <= y < self._host.shape[1]):
+            raise ValueError("cell (%d, %d) lies outside the field's extent" % (int(cell[0]), int(cell[1])))
+        path = _follow_directions(self._host, x, y, False)
+        return None if path is None else [(px + ox, py + oy) for px, py in path]
+
+    def window(self, device_maps=None, origin_cells=None):
+        """The part of this field under a window as a DeviceAtlasFieldWindow (a DeviceCostField): the window of a live DeviceMaps
+        -- a combine's or a recall's --, or the one whose corner is origin_cells (integer world cells).  Cropped on the GPU behind
+        the solve; no host wait.  Window cell (x, y) is world cell (corner + (x, y)); outside the field's extent it reads
+        unreached.  The local planner's terminal cost: window(maps).score_rollouts(poses)."""
+        g = self._hold._owner
+        if (device_maps is None) == (origin_cells is None):
+            raise ValueError("give device_maps or origin_cells, one of the two")
+        if device_maps is not None:
+            if not isinstance(device_maps, DeviceMaps):
+                raise ValueError("window takes the DeviceMaps whose window it crops to, got %r" % (type(device_maps).__name__,))
+            sid, org, cells, origin = int(device_maps.set_id), None, device_maps.origin_cells[:2], device_maps.origin
+        else:
+            org = _atlas_origin(origin_cells)
+            sid, cells = -1, (int(org[0]), int(org[1]))
+            origin = np.array(cells, np.float64) * self._res
+        hold = g._make_product(lambda pid: g._lib.gvom_atlas_field_window(g._h, int(self.product_id), sid, org, pid), PRODUCT_COSTFIELD,
+                               g._check_args)
+        info = [self.converged, self.rounds, self.reached, self.goals_seeded]
+        return DeviceAtlasFieldWindow(hold, info, origin, cells)
+
+
 class Atlas(object):
     """The map atlas of a mapper (Gvom.create_atlas): a world-fixed, toroidally stored memory of the nine 2-D maps, `cells` x `cells`
     world cells of device memory (64 bytes each), that keeps what the rolling window forgets.  integrate() merges a combine's set
@@ -1786,6 +1914,24 @@ class Atlas(object):
         e = (_I64 * 2)()
         hold = g._make_product(lambda pid: g._lib.gvom_atlas_extent(g._h, pid, e), PRODUCT_ATLAS_EXTENT, g._check_args)
         return DeviceAtlasExtent(hold, (int(e[0]), int(e[1])))
+
+    def cost_to_go(self, goals, goals_in_cells=False, inflation_radius=None, density_threshold=50, include_negative=True,
+                   unknown="free", base=1, soft_weight=0, rough_weight=0, roughness_range=None, max_cost=None, max_rounds=0):
+        """The navigation function of EVERYTHING the atlas holds towards `goals`: DeviceMaps.cost_to_go() on the whole extent, read
+        from the atlas in place, as a DeviceAtlasField ([A, A]; its window() is the DeviceCostField a local planner scores
+        rollouts against).  The call waits for the field.  goals: (G, 2) world metres (x, y), converted by cells_of -- or integer
+        WORLD cells with goals_in_cells=True; a goal outside the extent raises ValueError, one on a blocked cell seeds nothing.
+        The other keywords are DeviceMaps.cost_to_go()'s; never observed means visibility <= 0 here, and obstacles anywhere in the
+        extent inflate.  The extent's opposite edges are not neighbours.  include/gvom_hip.h "atlas fields" has the definition."""
+        g = self._owner
+        cells = _atlas_field_goals(goals, None if goals_in_cells else g.xy_resolution, self.extent_origin, self.cells)
+        params, flags = _ctg_params(g.xy_resolution, inflation_radius, density_threshold, include_negative, unknown, base, soft_weight,
+                                    rough_weight, roughness_range)
+        info, e = (_I64 * 4)(), (_I64 * 2)()
+        hold = g._make_product(lambda pid: g._lib.gvom_atlas_cost_to_go(
+            g._h, ctypes.byref(params), cells.ctypes.data_as(ctypes.POINTER(_I64)), cells.shape[0], _ctg_max_cost(max_cost),
+            _ctg_max_rounds(max_rounds), flags, pid, info, e), PRODUCT_ATLAS_FIELD, g._check_args)
+        return DeviceAtlasField(hold, list(info), (int(e[0]), int(e[1])), g.xy_resolution)
 
     def clear(self):
         """Every cell becomes UNKNOWN; the extent and seq stay."""

@@ -947,7 +947,8 @@ int gvom_pose_field(gvom_t *h, int64_t costfield_id, const int32_t *cost, int on
  * EXTENT EXPORT   gvom_atlas_extent: a product of kind GVOM_PRODUCT_ATLAS_EXTENT, the whole extent unwrapped -- [A, A], [x, y]-indexed
  *            with strides (1, A), cell (Ex + x, Ey + y) at [y*A + x]: parts 0 positive, 1 negative, 2 visibility (int32), 3 roughness,
  *            4 height (f64), 5 stamp (int32); 32 bytes per cell.  extent_origin (may be NULL) receives (Ex, Ey).  Consumers that plan
- *            at atlas scale read it in place, or on a second handle through the *_of_device calls.
+ *            at atlas scale read it in place, or on a second handle through the *_of_device calls; the cost-to-go field of the whole
+ *            extent needs neither ("atlas fields" below).
  *
  * INPUT of gvom_atlas_integrate, one of two.  map_set_id >= 0: a live device map set (maps and origin_cells must be NULL); the merge
  * runs on the handle's stream behind the combine or recall that wrote it.  map_set_id < 0: `maps`, nine pointers in set order (0
@@ -974,6 +975,58 @@ int gvom_atlas_recall(gvom_t *h, const int64_t origin_cells[2] /* may be NULL */
 int gvom_atlas_extent(gvom_t *h, int64_t *product_id, int64_t extent_origin[2]);
 int gvom_atlas_clear(gvom_t *h);
 int gvom_atlas_counts(gvom_t *h, int64_t out[8]);
+
+/* --- atlas fields (an extension: the cost-to-go field of everything the atlas remembers, and the part of it under any window -- the
+ * global navigation function a local planner takes its terminal cost from) ---------------------------------------------------------------
+ * gvom_atlas_cost_to_go solves "cost-to-go fields" on the atlas's WHOLE extent, reading the toroidal planes in place: no extent export,
+ * no second handle.  gvom_atlas_field_window crops the result to any window as an ordinary cost field, which gvom_score_rollouts,
+ * gvom_frontiers and gvom_pose_field accept like one gvom_cost_to_go made.  gvom_get_tuning "atlas_cost_to_go" (read-only) reads 1: how
+ * a caller probes a library for these entry points (additions: GVOM_ABI_VERSION stays).  Integer arithmetic throughout: the results are
+ * exact and do not depend on scheduling.
+ *
+ * DEFINITION of gvom_atlas_cost_to_go.
+ * MAP        the extent at the moment of the call, [Ex, Ex+A) x [Ey, Ey+A): extent cell (x, y) is world cell (Ex + x, Ey + y), read from
+ *            [((Ey+y) & (A-1)) * A + ((Ex+x) & (A-1))] of the atlas's planes.  The graph is the FLAT A x A grid: cells on opposite edges
+ *            of the extent are adjacent in storage and are NOT neighbours.
+ * HARD       a cell is hard iff (double)positive > density_threshold, or negative > 0 (not with GVOM_CTG_NO_NEGATIVE in flags).  d2 =
+ *            gvom_clearance's squared cells of that obstacle set on the flat A x A grid, capped at inflation_cells2: obstacles anywhere
+ *            in the extent inflate, nothing inflates across the extent's edge.
+ * COST       the rule of "cost-to-go fields", cell for cell, with two clarifications an atlas needs because gvom_atlas_integrate lets
+ *            any bit pattern in.  "Never observed" is visibility <= 0 (the atlas's rank < 2; in a map set the same as == 0): such a
+ *            cell is blocked with GVOM_CTG_UNKNOWN_BLOCKS and pays unknown_cost.  An unblocked cost is min(65535, max(1, base +
+ *            soft_weight * positive + ... )) in int64, which is the same wherever positive >= 0.  A NaN roughness gives q = 0 (r >
+ *            min_roughness is false).
+ * FIELD, DIRECTION   exactly D and dir of gvom_cost_to_go on that cost map: the eight steps, the corner rule, K = 5 / 7, max_cost,
+ *            GVOM_CTG_UNREACHED / _GOAL / _NONE / _UNSETTLED.  goals: [n_goals][2] WORLD cells (x, y), 1 <= n_goals <= 65536; a goal
+ *            outside the extent is GVOM_ERR_INVALID, a goal on a blocked cell seeds nothing.
+ * The call WAITS like gvom_cost_to_go -- it returns on convergence or after max_rounds (> 0) rounds, with the same promises about a field
+ * that is not final -- and runs on the handle's stream behind the last integrate.  info (may be NULL): the same four fields.
+ * "cost_to_go_inner" / "cost_to_go_batch" shape its rounds too; "atlas_field_tiles" (read-only): tile relaxations of the last call.
+ * The product, of kind GVOM_PRODUCT_ATLAS_FIELD, is a SNAPSHOT with its own memory and its own recorded extent origin, which
+ * extent_origin (may be NULL) receives: later integrates, moves of the extent, gvom_atlas_clear and a re-configure do not touch it.
+ * 7 bytes per cell, 117 MB at 4096.  At most GVOM_MAX_PRODUCT_SETS fields per handle; an unexported field goes back to the pool with
+ * the next gvom_atlas_cost_to_go; with every one exported the call returns GVOM_ERR_CAPACITY.  The solver's buffers at side A (counters,
+ * flags, goals; with an inflation the row distances and d2, 10 bytes per cell) are the handle's, apart from gvom_cost_to_go's.
+ * GVOM_ERR_INVALID: a sharded handle; no atlas configured; NULL params, goals or product_id; unknown flag bits; the parameter errors of
+ * gvom_cost_to_go; a goal outside the extent.
+ *
+ * gvom_atlas_field_window ENQUEUES and returns.  Give exactly one of map_set_id >= 0 (a live map set: its integer origin is the
+ * window's) and origin_cells = (Rx, Ry) (within 2^40).  The result is a product of kind GVOM_PRODUCT_COSTFIELD, [xy, xy] with strides
+ * (1, xy): cell (x, y) holds the field's D, dir and c of world cell (Rx + x, Ry + y), and GVOM_CTG_UNREACHED, GVOM_CTG_NONE and 0 where
+ * that cell lies outside the FIELD's extent (the one it was made with, wherever the atlas is now).  It lives in the cost-field pool under
+ * its rule -- an unexported one goes back with the next gvom_cost_to_go OR gvom_atlas_field_window -- and is a cost field in every
+ * respect.  dir is copied as it is: at the crop's border a step may point out of the window, where the path goes on in the field.
+ * GVOM_ERR_INVALID: a stale or unknown field_id; a set id and origin_cells, or neither; a stale set id; an origin beyond 2^40 cells; a
+ * NULL product_id.  "atlas_field_allocations" (read-only): device allocations the two entry points have made on this handle (the
+ * solver's buffers and the product sets of both kinds); it does not grow in steady state.  gvom_device_product(kind 26) is
+ * GVOM_ERR_INVALID.  Kind 25 is not assigned.
+ * NOT PROVIDED: a pose field at atlas scale; an age or stamp term in the cost; incremental repair of a field after an integrate; a coarser
+ * level; sharded handles; goals in device memory; a path walk on the device; fields that follow the extent. */
+#define GVOM_PRODUCT_ATLAS_FIELD 26   /* part 0 int32 D, part 1 uint8 dir, part 2 uint16 c: [A, A], strides (1, A); kind 25 stays unassigned */
+int gvom_atlas_cost_to_go(gvom_t *h, const gvom_ctg_params *params, const int64_t *goals /* [n_goals][2] WORLD cells */,
+                          int64_t n_goals, int32_t max_cost, int32_t max_rounds, int flags,
+                          int64_t *product_id, int64_t info[4], int64_t extent_origin[2]);
+int gvom_atlas_field_window(gvom_t *h, int64_t field_id, int64_t map_set_id, const int64_t origin_cells[2], int64_t *product_id);
 
 /* --- one map sharded over the GPUs of a node (one rank = one process = one GPU) -------------------
  * No counterpart in the reference (it has no multi-GPU path); semantics = SURVEY 8(e):

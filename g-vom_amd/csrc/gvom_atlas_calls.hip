@@ -3,7 +3,8 @@
 // wrote the set an integrate reads, in front of whatever recycles that set later -- and only gvom_atlas_counts waits for it.  A recall
 // writes a map set of the pool gvom_combine_maps_device takes its sets from (map_set_acquire, gvom_sets.hip) and a product set for the
 // stamps; the extent export is a product like the others.  Below them the atlas fields (include/gvom_hip.h "atlas fields"):
-// gvom_atlas_cost_to_go, which waits like gvom_cost_to_go, and gvom_atlas_field_window; their kernels are gvom_atlas_field.hip's.
+// gvom_atlas_cost_to_go, which waits like gvom_cost_to_go, and gvom_atlas_field_window; their kernels are gvom_atlas_field.hip's.  Last
+// the atlas frontiers (include/gvom_hip.h "atlas frontiers"): gvom_atlas_frontiers, which waits like gvom_frontiers.
 #include "gvom_host.h"
 
 namespace {
@@ -353,5 +354,54 @@ VIS int gvom_atlas_field_window(gvom_t *h, int64_t field_id, int64_t map_set_id,
     HIPCHK(h, gvom_launch_atlas_field_window(h->stream, A, (const int32_t *)fd[0].ptr, (const uint8_t *)fd[1].ptr, (const uint16_t *)fd[2].ptr, xy, rx, ry,
                                              (int32_t *)od[0].ptr, (uint8_t *)od[1].ptr, (uint16_t *)od[2].ptr));
     return product_publish(h, set, product_id);
+}
+
+// ---- atlas frontiers (include/gvom_hip.h "atlas frontiers") ------------------------------------------------------------------------------
+// gvom_frontiers at the side of an atlas field: k_atlas_frontier_mark (gvom_atlas_frontier.hip) reads c and D from the field and the
+// visibility in place from the atlas as it is now, everything behind it is frontier_solve (gvom_product_calls.hip) on a work buffer of
+// the handle's own at that side (afr_work): gvom_frontiers' window-sized one stays as it is.
+VIS int gvom_atlas_frontiers(gvom_t *h, int64_t field_id, int32_t min_cells, int32_t max_clusters, int64_t *product_id, int64_t info[4],
+                             int64_t extent_origin[2])
+{
+    if (!h || !product_id) return GVOM_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(h->mu);
+    *product_id = -1;
+    for (int k = 0; info && k < 4; ++k) info[k] = 0;
+    int rc = need_atlas(h, "gvom_atlas_frontiers");
+    if (rc) return rc;
+    DevSet *f = find_set(h->psets, field_id);
+    if (!f || f->kind != GVOM_PRODUCT_ATLAS_FIELD) { h->err = "gvom_atlas_frontiers: unknown or stale atlas field id"; return GVOM_ERR_INVALID; }
+    if (min_cells < 1) { h->err = "gvom_atlas_frontiers: min_cells must be at least 1"; return GVOM_ERR_INVALID; }
+    if (max_clusters < 1 || max_clusters > GVOM_FRONTIER_MAX_CLUSTERS) { h->err = "gvom_atlas_frontiers: max_clusters outside 1 .. 2^20"; return GVOM_ERR_INVALID; }
+    const int Af = (int)f->cap;
+    const int64_t F[2] = {f->origin[0], f->origin[1]};
+    HIPCHK(h, hipSetDevice(h->device));
+    DevSet *set = nullptr;
+    const size_t bytes = set_bytes(GVOM_PRODUCT_ATLAS_FRONTIERS, 0, 0, max_clusters, Af);
+    if ((rc = product_acquire(h, GVOM_PRODUCT_ATLAS_FRONTIERS, bytes, bytes, "gvom_atlas_frontiers", &h->afr_allocs, &set))) return rc;
+    set->cap = max_clusters; set->cols = Af;
+    if (h->afr_work.bytes < fr_work_bytes(Af)) {
+        if ((rc = ensure(h, h->afr_work, fr_work_bytes(Af)))) return rc;
+        ++h->afr_allocs;
+    }
+    if (!h->afr_pin) HIPCHK(h, hipHostMalloc((void **)&h->afr_pin, 256, hipHostMallocDefault));
+    const FrWork W = fr_work_layout(Af, (char *)h->afr_work.p);
+    HIPCHK(h, join_second_stream(h));
+    HIPCHK(h, hipMemsetAsync(W.cnt, 0, W.clear_bytes, h->stream));          // the counters and both halves of the flags
+    if ((rc = set_wait_releases(h, set))) return rc;
+    SetPart d;
+    set_part(f, 0, &d); const int32_t *D = (const int32_t *)d.ptr;
+    set_part(f, 2, &d); const uint16_t *c16 = (const uint16_t *)d.ptr;
+    const Window w = window_of(h, F);                                       // the field's corner relative to the extent as it is now
+    const Window e = window_of(h, h->atl_E);                                // (its storage phase is the extent's)
+    HIPCHK(h, gvom_launch_atlas_frontier_mark(h->stream, Af, c16, D, h->atl_mem, h->atl_A, w.rx, w.ry, e.px, e.py, W.L, W.count, W.fl,
+                                              W.cnt + FR_CNT_CELLS));
+    FrSolve S;
+    if ((rc = frontier_solve(h, "gvom_atlas_frontiers", Af, D, W, h->afr_pin, min_cells, max_clusters, set, product_id, info, &S))) return rc;
+    set->origin[0] = F[0]; set->origin[1] = F[1]; set->origin[2] = 0;
+    h->afr_last_rounds = (int)std::min<int64_t>(S.rounds, INT32_MAX);
+    h->afr_last_tiles = (int)std::min<int64_t>(S.tiles, INT32_MAX);
+    if (extent_origin) { extent_origin[0] = F[0]; extent_origin[1] = F[1]; }
+    return GVOM_OK;
 }
 }  // extern "C"

@@ -448,7 +448,7 @@ VIS void gvom_destroy(gvom_t *h)
     if (h->x_host) hipHostFree(h->x_host);
     for (auto &s : h->slots) { hipFree(s.state); hipFree(s.code16); hipFree(s.tags); fb(s.crows); fb(s.metrics); fb(s.base); fb(s.rowvox); }
     for (auto &f : h->fused) { hipFree(f.state); hipFree(f.tags); fb(f.rows); fb(f.metrics); }
-    fb(h->in_pts); fb(h->cl_g); fb(h->cl_stage); fb(h->rq_stage); fb(h->ctg_work); fb(h->ctg_stage); fb(h->ctg_clr); fb(h->fp_tab); fb(h->ro_stage); fb(h->at_tab); fb(h->at_ground); fb(h->at_stage); fb(h->al_grid); fb(h->al_stage); fb(h->fr_work); fb(h->fr_stage); fb(h->vp_bitmaps); fb(h->vp_stage); fb(h->pf_tab); fb(h->pf_work); fb(h->pf_stage); fb(h->atl_stage); fb(h->af_work); fb(h->af_clr); if (h->af_pin) hipHostFree(h->af_pin); hipFree(h->atl_mem); hipFree(h->atl_cnt); if (h->atl_pin) hipHostFree(h->atl_pin); if (h->pf_pin) hipHostFree(h->pf_pin); if (h->fr_pin) hipHostFree(h->fr_pin); if (h->ctg_pin) hipHostFree(h->ctg_pin); fb(h->ri_model); fb(h->ri_raw); fb(h->ri_poses); if (h->ri_poses_pin) hipHostFree(h->ri_poses_pin); fb(h->mo_dev); if (h->mo_pin) hipHostFree(h->mo_pin); fb(h->world_pts[0]); fb(h->world_pts[1]); fb(h->flink[0]); fb(h->flink[1]); fb(h->tl); fb(h->dir_keys); fb(h->dir_perm); hipFree(h->dir_hist);
+    fb(h->in_pts); fb(h->cl_g); fb(h->cl_stage); fb(h->rq_stage); fb(h->ctg_work); fb(h->ctg_stage); fb(h->ctg_clr); fb(h->fp_tab); fb(h->ro_stage); fb(h->at_tab); fb(h->at_ground); fb(h->at_stage); fb(h->al_grid); fb(h->al_stage); fb(h->fr_work); fb(h->fr_stage); fb(h->vp_bitmaps); fb(h->vp_stage); fb(h->pf_tab); fb(h->pf_work); fb(h->pf_stage); fb(h->atl_stage); fb(h->af_work); fb(h->af_clr); fb(h->afr_work); if (h->af_pin) hipHostFree(h->af_pin); if (h->afr_pin) hipHostFree(h->afr_pin); hipFree(h->atl_mem); hipFree(h->atl_cnt); if (h->atl_pin) hipHostFree(h->atl_pin); if (h->pf_pin) hipHostFree(h->pf_pin); if (h->fr_pin) hipHostFree(h->fr_pin); if (h->ctg_pin) hipHostFree(h->ctg_pin); fb(h->ri_model); fb(h->ri_raw); fb(h->ri_poses); if (h->ri_poses_pin) hipHostFree(h->ri_poses_pin); fb(h->mo_dev); if (h->mo_pin) hipHostFree(h->mo_pin); fb(h->world_pts[0]); fb(h->world_pts[1]); fb(h->flink[0]); fb(h->flink[1]); fb(h->tl); fb(h->dir_keys); fb(h->dir_perm); hipFree(h->dir_hist);
     hipFree(h->counters); if (h->counters_host) hipHostFree(h->counters_host);
     hipFree(h->descs_dev); if (h->descs_host) hipHostFree(h->descs_host);
     hipFree(h->blockcounts); hipFree(h->blockcounts2); hipFree(h->hmaps2);
@@ -605,6 +605,10 @@ VIS int gvom_get_tuning(gvom_t *h, const char *name, int *value)
     if (!strcmp(name, "atlas_cost_to_go")) { *value = 1; return GVOM_OK; }                              // read-only: the library has gvom_atlas_cost_to_go and gvom_atlas_field_window
     if (!strcmp(name, "atlas_field_allocations")) { *value = h->af_allocs; return GVOM_OK; }            // read-only: device allocations those two have made
     if (!strcmp(name, "atlas_field_tiles")) { *value = h->af_last_tiles; return GVOM_OK; }              // read-only: tile relaxations of the last gvom_atlas_cost_to_go
+    if (!strcmp(name, "atlas_frontiers")) { *value = 1; return GVOM_OK; }                               // read-only: the library has gvom_atlas_frontiers
+    if (!strcmp(name, "atlas_frontier_allocations")) { *value = h->afr_allocs; return GVOM_OK; }        // read-only: device allocations gvom_atlas_frontiers has made
+    if (!strcmp(name, "atlas_frontier_rounds")) { *value = h->afr_last_rounds; return GVOM_OK; }        // read-only: rounds of the last gvom_atlas_frontiers
+    if (!strcmp(name, "atlas_frontier_tiles")) { *value = h->afr_last_tiles; return GVOM_OK; }          // read-only: tile relaxations of the last gvom_atlas_frontiers
     if (!strcmp(name, "atlas_allocations")) { *value = h->atl_allocs; return GVOM_OK; }                  // read-only: device allocations the gvom_atlas_* calls have made
     if (!strcmp(name, "alignment_allocations")) { *value = h->al_allocs; return GVOM_OK; }              // read-only: device allocations gvom_score_alignments has made
     if (!strcmp(name, "alignment_grid_bytes")) { *value = (int)(h->al_grid.bytes > 0x7fffffffu ? 0x7fffffffu : h->al_grid.bytes); return GVOM_OK; }   // read-only: the class grid's allocation

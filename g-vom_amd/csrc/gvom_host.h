@@ -404,6 +404,14 @@ struct gvom_handle {
     uint32_t *af_pin = nullptr;
     int af_allocs = 0;
     int af_last_tiles = 0;                              // tile relaxations of the last gvom_atlas_cost_to_go (gvom_get_tuning "atlas_field_tiles")
+    // ATLAS FRONTIERS (gvom_atlas_frontiers): afr_work = gvom_frontiers' work buffer (fr_work_layout) at the side of the FIELD the call
+    // was given, 8 bytes per cell plus flags and counters -- apart from the window-sized fr_work, which an atlas call never touches.
+    // afr_allocs counts it and the entry point's product sets (gvom_get_tuning "atlas_frontier_allocations").  afr_pin: the pinned
+    // copy of the counters the host loop reads.
+    Buf afr_work;
+    uint32_t *afr_pin = nullptr;
+    int afr_allocs = 0;
+    int afr_last_rounds = 0, afr_last_tiles = 0;        // of the last call (gvom_get_tuning "atlas_frontier_rounds" / "atlas_frontier_tiles")
 };
 
 namespace gvom_host {
@@ -490,4 +498,15 @@ struct CtgSolve { bool converged = false; int64_t rounds = 0, tiles = 0; };
 int ctg_cost_params(gvom_handle *h, const char *fn, const gvom_ctg_params *params, int flags, CtgCostParams *C);
 int ctg_solve(gvom_handle *h, int n, const int32_t *cost32, uint16_t *c16, int32_t *D, uint8_t *dir, uint32_t *cnt, uint32_t *fl,
               const int32_t *gdev, int n_goals, int32_t max_cost, int32_t max_rounds, uint32_t *pin, CtgSolve *out);
+// the part of gvom_frontiers that gvom_atlas_frontiers shares: everything behind the marking kernel.  fr_work_bytes / fr_work_layout: the
+// size and the parts of a work buffer for n x n cells -- 256 bytes of counters (FR_CNT_* above), the two halves of the tiles' activity
+// flags, the block counts of the ranking, then the label and the count / rank arrays; the caller clears the first clear_bytes on the
+// stream and runs its marking kernel.  frontier_solve: the rows' initialisation, the batches of relaxation rounds with the host's look
+// at the counters between them (pin: their pinned copy), the finish, the set's publication and info; errors are in fn's name.  It waits.
+struct FrWork { uint32_t *cnt, *fl, *bc, *L, *count; size_t clear_bytes; };
+struct FrSolve { int64_t rounds = 0, tiles = 0; };
+size_t fr_work_bytes(int n);
+FrWork fr_work_layout(int n, char *w);
+int frontier_solve(gvom_handle *h, const char *fn, int n, const int32_t *D, const FrWork &W, uint32_t *pin, int32_t min_cells,
+                   int32_t max_clusters, DevSet *set, int64_t *product_id, int64_t info[4], FrSolve *out);
 }  // namespace gvom_host

@@ -473,6 +473,12 @@ hipError_t gvom_launch_atlas_travcost(hipStream_t s, const char *atlas, int A, i
                                       uint16_t *c);
 hipError_t gvom_launch_atlas_field_window(hipStream_t s, int A, const int32_t *fD, const uint8_t *fdir, const uint16_t *fc, int n, int rx,
                                           int ry, int32_t *oD, uint8_t *odir, uint16_t *oc);
+// atlas frontiers (gvom_atlas_frontier.hip; include/gvom_hip.h "atlas frontiers" defines the result): gvom_launch_frontier_mark on the
+// unwrapped [y][x] planes c and D of a field of xy x xy cells, the visibility read in place from the atlas of side A: field cell (x, y)
+// is extent cell (ox + x, oy + y) (|ox|, |oy| <= 2^30; outside the extent a cell is neither known nor unknown), px, py the extent's
+// storage phase.  L, count, flags and n_frontier as for gvom_launch_frontier_mark; relax, rows and finish follow at side xy.
+hipError_t gvom_launch_atlas_frontier_mark(hipStream_t s, int xy, const uint16_t *c, const int32_t *D, const char *atlas, int A, int ox,
+                                           int oy, int px, int py, uint32_t *L, uint32_t *count, uint32_t *flags, uint32_t *n_frontier);
 // storage order [sy][sx] -> reference order [x][y] (window coordinates)
 hipError_t gvom_launch_unwrap_f64(hipStream_t s, int xy, int om0, int om1, const double *in, int in_stride, double *out_xy);
 hipError_t gvom_launch_posdens(hipStream_t s, const Map2dParams &P, const int32_t *fstate,

@@ -99,6 +99,76 @@ int ctg_solve(gvom_handle *h, int n, const int32_t *cost32, uint16_t *c16, int32
     out->converged = converged; out->rounds = rounds; out->tiles = tiles;
     return GVOM_OK;
 }
+
+// ---- what gvom_frontiers and gvom_atlas_frontiers (gvom_atlas_calls.hip) share ----------------------------------------------------------
+namespace {
+struct FrOffsets { size_t flags, bc, L, count, end; };
+FrOffsets fr_offsets(int n)
+{
+    const size_t n2 = (size_t)n * n;
+    const int nt = gvom_frontier_tiles(n), nb = gvom_frontier_blocks(n);
+    FrOffsets o;
+    o.flags = 256; o.bc = o.flags + align256((size_t)2 * nt * nt * 4); o.L = o.bc + align256((size_t)2 * nb * 4);
+    o.count = o.L + align256(n2 * 4); o.end = o.count + n2 * 4;
+    return o;
+}
+}  // namespace
+
+size_t fr_work_bytes(int n) { return fr_offsets(n).end; }
+
+FrWork fr_work_layout(int n, char *w)
+{
+    const FrOffsets o = fr_offsets(n);
+    return FrWork{(uint32_t *)w, (uint32_t *)(w + o.flags), (uint32_t *)(w + o.bc), (uint32_t *)(w + o.L), (uint32_t *)(w + o.count), o.bc};
+}
+
+int frontier_solve(gvom_handle *h, const char *fn, int n, const int32_t *D, const FrWork &W, uint32_t *pin, int32_t min_cells,
+                   int32_t max_clusters, DevSet *set, int64_t *product_id, int64_t info[4], FrSolve *out)
+{
+    const size_t n2 = (size_t)n * n;
+    const int nt = gvom_frontier_tiles(n), ntiles = nt * nt;
+    uint32_t *const cnt = W.cnt, *const fl = W.fl;
+    SetPart d;
+    set_part(set, 0, &d); int32_t *rows = (int32_t *)d.ptr;
+    set_part(set, 1, &d); int64_t *sums = (int64_t *)d.ptr;
+    set_part(set, 2, &d); int32_t *cmap = (int32_t *)d.ptr;
+    set_part(set, 3, &d); int32_t *counts = (int32_t *)d.ptr;
+    HIPCHK(h, gvom_launch_frontier_rows(h->stream, 0, max_clusters, rows, sums, cnt + FR_CNT_KEPT, cnt + FR_CNT_CELLS, counts));
+    const int inner = h->tune_fr_inner > 0 ? h->tune_fr_inner : 256;
+    const int batch = h->tune_fr_batch > 0 ? h->tune_fr_batch : 8;
+    // labels only go down and there are n2 of them: a round that lowers none flags no tile, so fewer than n2 + 1 rounds lower one.
+    // The limit cannot be reached and only keeps this loop finite
+    const int64_t limit = (int64_t)n2 + 1;
+    int64_t rounds = 0, tiles = 0;
+    bool converged = false;
+    while (!converged && rounds < limit) {
+        const int nr = (int)std::min<int64_t>(batch, limit - rounds);
+        if (rounds) HIPCHK(h, hipMemsetAsync(cnt, 0, 2 * GVOM_CTG_MAX_BATCH * 4, h->stream));
+        for (int r = 0; r < nr; ++r) {
+            const int64_t k = rounds + r;
+            HIPCHK(h, gvom_launch_frontier_relax(h->stream, n, W.L, fl + (k & 1) * ntiles, fl + ((k + 1) & 1) * ntiles, cnt + r,
+                                                 cnt + FR_CNT_RELAXED + r, inner));
+        }
+        HIPCHK(h, hipMemcpyAsync(pin, cnt, 2 * GVOM_CTG_MAX_BATCH * 4, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        int ran = nr;
+        for (int r = 0; r < nr; ++r) {
+            tiles += pin[FR_CNT_RELAXED + r];
+            if (pin[r] == 0) { converged = true; ran = r + 1; break; }
+        }
+        rounds += ran;
+    }
+    if (!converged) { h->err = std::string(fn) + ": the labels did not settle"; return GVOM_ERR_HIP; }   // (the set keeps id -1: nobody gets it)
+    HIPCHK(h, gvom_launch_frontier_finish(h->stream, n, min_cells, max_clusters, D, W.L, W.count, W.bc, cnt + FR_CNT_KEPT, cnt + FR_CNT_CELLS, rows,
+                                          sums, cmap, counts));
+    const int rc = product_publish(h, set, product_id);                    // (`ready` goes in front of the counters' way back)
+    if (rc) return rc;
+    HIPCHK(h, hipMemcpyAsync(pin, cnt, 256, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    out->rounds = rounds; out->tiles = tiles;
+    if (info) { info[0] = rounds; info[1] = pin[FR_CNT_KEPT]; info[2] = pin[FR_CNT_CELLS]; info[3] = pin[FR_CNT_KEPT + 1]; }
+    return GVOM_OK;
+}
 }  // namespace gvom_host
 
 // part `part` of a set as a launcher takes it.  The part numbers below are literals: one the set's kind does not have is a mistake
@@ -626,7 +696,7 @@ VIS int gvom_score_alignments(gvom_t *h, const float *cloud, int64_t n, const do
 // sized by the map and max_clusters.  The kernels run on the handle's stream behind whatever wrote the field and the map set they
 // read, and whatever recycles those later runs behind them.  Like gvom_cost_to_go this call WAITS: rounds of k_frontier_relax are
 // enqueued a batch at a time, the batch's per-round counters come back through pinned memory, and the first round that flagged no
-// tile ends the labelling (the rounds enqueued behind it found nothing to do).
+// tile ends the labelling (the rounds enqueued behind it found nothing to do): frontier_solve above, everything behind the marking.
 VIS int gvom_frontiers(gvom_t *h, int64_t costfield_id, int64_t map_set_id, const uint16_t *cell_cost, const int32_t *cost_to_go,
                        const int32_t *visibility, int on_device, int32_t min_cells, int32_t max_clusters, int64_t *product_id, int64_t info[4])
 {
@@ -659,14 +729,9 @@ VIS int gvom_frontiers(gvom_t *h, int64_t costfield_id, int64_t map_set_id, cons
     int rc = product_acquire(h, GVOM_PRODUCT_FRONTIERS, bytes, bytes, "gvom_frontiers", &h->fr_allocs, &set);
     if (rc) return rc;
     set->cap = max_clusters;
-    const int nt = gvom_frontier_tiles(xy), ntiles = nt * nt, nb = gvom_frontier_blocks(xy);
-    const size_t flags_off = 256, bc_off = flags_off + align256((size_t)2 * ntiles * 4), L_off = bc_off + align256((size_t)2 * nb * 4),
-                 count_off = L_off + align256(n2 * 4);
-    if ((rc = stage_buf(h, h->fr_work, count_off + n2 * 4, h->fr_allocs))) return rc;
+    if ((rc = stage_buf(h, h->fr_work, fr_work_bytes(xy), h->fr_allocs))) return rc;
     if (!h->fr_pin) HIPCHK(h, hipHostMalloc((void **)&h->fr_pin, 256, hipHostMallocDefault));
-    char *const w = (char *)h->fr_work.p;
-    uint32_t *cnt = (uint32_t *)w, *fl = (uint32_t *)(w + flags_off), *bc = (uint32_t *)(w + bc_off), *L = (uint32_t *)(w + L_off),
-             *count = (uint32_t *)(w + count_off);
+    const FrWork W = fr_work_layout(xy, (char *)h->fr_work.p);
     HIPCHK(h, join_second_stream(h));
     if (!ids && !on_device) {                                               // host maps: staged
         const size_t cb = align256(n2 * 2), vb = align256(n2 * 4);
@@ -677,45 +742,13 @@ VIS int gvom_frontiers(gvom_t *h, int64_t costfield_id, int64_t map_set_id, cons
         if (cost_to_go) HIPCHK(h, hipMemcpyAsync(st + cb + vb, cost_to_go, n2 * 4, hipMemcpyHostToDevice, h->stream));
         c16 = (const uint16_t *)st; vis = (const int32_t *)(st + cb); D = cost_to_go ? (const int32_t *)(st + cb + vb) : nullptr;
     }
-    HIPCHK(h, hipMemsetAsync(w, 0, bc_off, h->stream));                     // the counters and both halves of the flags
+    HIPCHK(h, hipMemsetAsync(W.cnt, 0, W.clear_bytes, h->stream));          // the counters and both halves of the flags
     if ((rc = set_wait_releases(h, set))) return rc;
-    int32_t *rows = part_ptr<int32_t>(set, 0);
-    int64_t *sums = part_ptr<int64_t>(set, 1);
-    HIPCHK(h, gvom_launch_frontier_rows(h->stream, 0, max_clusters, rows, sums, cnt + FR_CNT_KEPT, cnt + FR_CNT_CELLS, part_ptr<int32_t>(set, 3)));
-    HIPCHK(h, gvom_launch_frontier_mark(h->stream, xy, c16, vis, D, L, count, fl, cnt + FR_CNT_CELLS));
-    const int inner = h->tune_fr_inner > 0 ? h->tune_fr_inner : 256;
-    const int batch = h->tune_fr_batch > 0 ? h->tune_fr_batch : 8;
-    // labels only go down and there are n2 of them: a round that lowers none flags no tile, so fewer than n2 + 1 rounds lower one.
-    // The limit cannot be reached and only keeps this loop finite
-    const int64_t limit = (int64_t)n2 + 1;
-    int64_t rounds = 0, tiles = 0;
-    bool converged = false;
-    while (!converged && rounds < limit) {
-        const int nr = (int)std::min<int64_t>(batch, limit - rounds);
-        if (rounds) HIPCHK(h, hipMemsetAsync(cnt, 0, 2 * GVOM_CTG_MAX_BATCH * 4, h->stream));
-        for (int r = 0; r < nr; ++r) {
-            const int64_t k = rounds + r;
-            HIPCHK(h, gvom_launch_frontier_relax(h->stream, xy, L, fl + (k & 1) * ntiles, fl + ((k + 1) & 1) * ntiles, cnt + r,
-                                                 cnt + FR_CNT_RELAXED + r, inner));
-        }
-        HIPCHK(h, hipMemcpyAsync(h->fr_pin, cnt, 2 * GVOM_CTG_MAX_BATCH * 4, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        int ran = nr;
-        for (int r = 0; r < nr; ++r) {
-            tiles += h->fr_pin[FR_CNT_RELAXED + r];
-            if (h->fr_pin[r] == 0) { converged = true; ran = r + 1; break; }
-        }
-        rounds += ran;
-    }
-    if (!converged) { h->err = "gvom_frontiers: the labels did not settle"; return GVOM_ERR_HIP; }   // (the set keeps id -1: nobody gets it)
-    HIPCHK(h, gvom_launch_frontier_finish(h->stream, xy, min_cells, max_clusters, D, L, count, bc, cnt + FR_CNT_KEPT, cnt + FR_CNT_CELLS, rows, sums,
-                                          part_ptr<int32_t>(set, 2), part_ptr<int32_t>(set, 3)));
-    if ((rc = product_publish(h, set, product_id))) return rc;             // (`ready` goes in front of the counters' way back)
-    HIPCHK(h, hipMemcpyAsync(h->fr_pin, cnt, 256, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    h->fr_last_rounds = (int)std::min<int64_t>(rounds, INT32_MAX);
-    h->fr_last_tiles = (int)std::min<int64_t>(tiles, INT32_MAX);
-    if (info) { info[0] = rounds; info[1] = h->fr_pin[FR_CNT_KEPT]; info[2] = h->fr_pin[FR_CNT_CELLS]; info[3] = h->fr_pin[FR_CNT_KEPT + 1]; }
+    HIPCHK(h, gvom_launch_frontier_mark(h->stream, xy, c16, vis, D, W.L, W.count, W.fl, W.cnt + FR_CNT_CELLS));
+    FrSolve S;
+    if ((rc = frontier_solve(h, "gvom_frontiers", xy, D, W, h->fr_pin, min_cells, max_clusters, set, product_id, info, &S))) return rc;
+    h->fr_last_rounds = (int)std::min<int64_t>(S.rounds, INT32_MAX);
+    h->fr_last_tiles = (int)std::min<int64_t>(S.tiles, INT32_MAX);
     return GVOM_OK;
 }
 

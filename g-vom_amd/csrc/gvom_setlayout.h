@@ -34,6 +34,9 @@
 //   atlas field (26) a cost field at the atlas's scale, cap x cap cells, cap = the side A of the atlas that made it: cap*cap int32 (cost
 //                    to go), then cap*cap uint8 (direction), then cap*cap uint16 (cell costs), all [y][x] over the field's own extent.
 //                    Kind 25 is not assigned
+//   atlas frontiers (28)  the four parts of frontiers (16) with the window's side replaced by cols = the side of the atlas FIELD the call
+//                    was given: cap x 8 int32, cap x 2 int64, cols*cols int32 (the cluster map, [y][x] over the field's extent), 4 int32;
+//                    cap = max_clusters of the call that wrote it.  Kind 27 is not assigned
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -53,7 +56,7 @@ struct SetShape {
     // voxel cloud: rows the allocation holds; raycast: rays of the product; a map set: the elements from one map to the next,
     // dev_map_stride(xy) of gvom_internal.h (which needs the HIP runtime: it comes in through here) -- a multiple of 32, >= xy*xy
     int64_t cap = 0;
-    int64_t cols = 0;                          // rollouts, attitude: poses per rollout (T)
+    int64_t cols = 0;                          // rollouts, attitude: poses per rollout (T); atlas frontiers: the side of the field
 };
 struct SetPart { void *ptr; int ndim; int64_t shape[3], strides[3]; uint8_t code, bits; size_t bytes; };
 
@@ -78,6 +81,7 @@ inline size_t set_bytes(int kind, int xy, int zs, int64_t cap, int64_t cols = 0)
     case GVOM_PRODUCT_ATLAS_RECALL: return align256(n2 * 4) + 16;
     case GVOM_PRODUCT_ATLAS_EXTENT: return (size_t)cap * (size_t)cap * 32;
     case GVOM_PRODUCT_ATLAS_FIELD: return align256((size_t)cap * (size_t)cap * 4) + align256((size_t)cap * (size_t)cap) + (size_t)cap * (size_t)cap * 2;
+    case GVOM_PRODUCT_ATLAS_FRONTIERS: return align256((size_t)cap * 32) + align256((size_t)cap * 16) + align256((size_t)cols * (size_t)cols * 4) + 16;
     }
     return 0;
 }
@@ -152,12 +156,14 @@ inline bool set_part(const SetShape *s, int part, SetPart *d)
         else return false;
         break;
     }
-    case GVOM_PRODUCT_FRONTIERS: {
+    case GVOM_PRODUCT_FRONTIERS:
+    case GVOM_PRODUCT_ATLAS_FRONTIERS: {                   // (28: the same four parts, the cluster map at the side of the atlas field)
+        const int64_t side = s->kind == GVOM_PRODUCT_FRONTIERS ? xy : s->cols;
         char *const sums = s->mem + align256((size_t)s->cap * 32), *const cmap = sums + align256((size_t)s->cap * 16);
         if (part == 0) { rows(s->mem, s->cap, 8); d->code = kDLInt; }
         else if (part == 1) { rows(sums, s->cap, 2); d->code = kDLInt; d->bits = 64; }
-        else if (part == 2) { d->ptr = cmap; d->shape[0] = d->shape[1] = xy; d->strides[0] = 1; d->strides[1] = xy; d->code = kDLInt; }   // [x, y] indexing, column-major, like a device map
-        else if (part == 3) { d->ptr = cmap + align256((size_t)n2 * 4); d->ndim = 1; d->shape[0] = 4; d->strides[0] = 1; d->shape[1] = d->strides[1] = 1; d->code = kDLInt; }
+        else if (part == 2) { d->ptr = cmap; d->shape[0] = d->shape[1] = side; d->strides[0] = 1; d->strides[1] = side; d->code = kDLInt; }   // [x, y] indexing, column-major, like a device map
+        else if (part == 3) { d->ptr = cmap + align256((size_t)(side * side) * 4); d->ndim = 1; d->shape[0] = 4; d->strides[0] = 1; d->shape[1] = d->strides[1] = 1; d->code = kDLInt; }
         else return false;
         break;
     }

@@ -181,6 +181,7 @@ ABI = [
     ("gvom_atlas_cost_to_go", _I, [_P, _P, ctypes.POINTER(_I64), _I64, ctypes.c_int32, ctypes.c_int32, _I, ctypes.POINTER(_I64),
                                    ctypes.POINTER(_I64), ctypes.POINTER(_I64)]),
     ("gvom_atlas_field_window", _I, [_P, _I64, _I64, ctypes.POINTER(_I64), ctypes.POINTER(_I64)]),
+    ("gvom_atlas_frontiers", _I, [_P, _I64, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(_I64), ctypes.POINTER(_I64), ctypes.POINTER(_I64)]),
     ("gvom_set_profiling", _I, [_P, _I]),
     ("gvom_host_timing", _I, [_P, ctypes.POINTER(ctypes.c_double * 8)]),
     ("gvom_set_tuning", _I, [_P, ctypes.c_char_p, _I]),
@@ -598,6 +599,7 @@ PRODUCT_POSEFIELD = 20                    # GVOM_PRODUCT_POSEFIELD: made by gvom
 PRODUCT_ATLAS_RECALL = 22                 # GVOM_PRODUCT_ATLAS_RECALL: made by gvom_atlas_recall, beside its map set (kind 21 is not assigned)
 PRODUCT_ATLAS_EXTENT = 24                 # GVOM_PRODUCT_ATLAS_EXTENT: made by gvom_atlas_extent (kind 23 is not assigned)
 PRODUCT_ATLAS_FIELD = 26                  # GVOM_PRODUCT_ATLAS_FIELD: made by gvom_atlas_cost_to_go (kind 25 is not assigned)
+PRODUCT_ATLAS_FRONTIERS = 28              # GVOM_PRODUCT_ATLAS_FRONTIERS: made by gvom_atlas_frontiers (kind 27 is not assigned)
 # element type of part k of a product, by kind (what set_part() of csrc/gvom_setlayout.h gives as DLPack code and bits)
 _PRODUCT_DTYPES = {PRODUCT_OCCUPANCY: (np.uint8,), PRODUCT_VOXEL_CLOUD: (np.float32, np.float32, np.int64),
                    PRODUCT_HEIGHT_CLOUD: (np.float32,), PRODUCT_INFERRED_HEIGHT_CLOUD: (np.float32,),
@@ -607,7 +609,8 @@ _PRODUCT_DTYPES = {PRODUCT_OCCUPANCY: (np.uint8,), PRODUCT_VOXEL_CLOUD: (np.floa
                    PRODUCT_FRONTIERS: (np.int32, np.int64, np.int32, np.int32), PRODUCT_VIEWPOINTS: (np.int32, np.int32),
                    PRODUCT_POSEFIELD: (np.int32, np.uint8, np.uint16), PRODUCT_ATLAS_RECALL: (np.int32, np.int32),
                    PRODUCT_ATLAS_EXTENT: (np.int32, np.int32, np.int32, np.float64, np.float64, np.int32),
-                   PRODUCT_ATLAS_FIELD: (np.int32, np.uint8, np.uint16)}
+                   PRODUCT_ATLAS_FIELD: (np.int32, np.uint8, np.uint16),
+                   PRODUCT_ATLAS_FRONTIERS: (np.int32, np.int64, np.int32, np.int32)}
 CLEARANCE_FAR = 2147483647                # GVOM_CLEARANCE_FAR: squared_cells where no obstacle is in reach
 _CLEARANCE_NO_NEGATIVE = 1                # GVOM_CLEARANCE_NO_NEGATIVE
 
@@ -1780,6 +1783,44 @@ class DeviceAtlasFieldWindow(DeviceCostField):
         return _follow_directions(self._host, x, y, True)
 
 
+class DeviceAtlasFrontiers(DeviceFrontiers):
+    """The result of DeviceAtlasField.frontiers(): a DeviceFrontiers over the field's WHOLE extent -- the same four DeviceArrays
+    (`.cluster_map` is [A, A] with strides (1, A), A the field's side), the same info attributes and copy_to_host().  Labels, boxes and
+    best cells are in the FIELD's frame: field cell (x, y) is world cell (origin_cells[0] + x, origin_cells[1] + y) and has the linear
+    index y * A + x.  `.origin_cells` is the field's corner in world cells, `.origin` the same in world metres.  goals() returns world
+    metres, goal_cells() world cells, which Atlas.cost_to_go(goals_in_cells=True) and DeviceAtlasField.path_from() take as they are."""
+
+    def __init__(self, hold, info, xy_resolution, origin_cells):
+        self.origin_cells = (int(origin_cells[0]), int(origin_cells[1]))
+        DeviceFrontiers.__init__(self, hold, info, xy_resolution, np.array(self.origin_cells, np.float64) * float(xy_resolution))
+
+    def _picked(self, order):
+        """(rows int64 [n, 8], sums int64 [n, 2], pick): the kept rows on the host and their order"""
+        if order not in ("cost", "size"):
+            raise ValueError('order must be "cost" or "size", got %r' % (order,))
+        n = min(self.n_clusters, self.clusters.shape[0])
+        rows, sums = self.clusters.copy_to_host()[:n].astype(np.int64), self.sums.copy_to_host()[:n]
+        key = rows[:, 7] if order == "cost" else -rows[:, 1]
+        return rows, sums, np.lexsort((rows[:, 0], key))
+
+    def goal_cells(self, order="cost"):
+        """(best, rows): int64 [n, 2] WORLD cells (x, y) of each kept cluster's best cell, in the order of goals(), and the int64 [n]
+        rows of `.clusters` they come from."""
+        rows, _, pick = self._picked(order)
+        A = self.cluster_map.shape[0]
+        best = np.stack([rows[:, 6] % A, rows[:, 6] // A], axis=1) + np.array(self.origin_cells, np.int64)
+        return best[pick], pick
+
+    def goals(self, order="cost"):
+        """DeviceFrontiers.goals() in world metres, computed from `.origin_cells` exactly (no float origin is rounded back to cells)."""
+        rows, sums, pick = self._picked(order)
+        A = self.cluster_map.shape[0]
+        oc = np.array(self.origin_cells, np.float64)
+        best = np.stack([rows[:, 6] % A, rows[:, 6] // A], axis=1).astype(np.float64)
+        centroid = sums.astype(np.float64) / np.maximum(rows[:, 1:2], 1)
+        return ((best + oc + 0.5) * self._res)[pick], ((centroid + oc + 0.5) * self._res)[pick], pick
+
+
 class DeviceAtlasField(_ProductView):
     """The result of Atlas.cost_to_go(): the cost-to-go field of the atlas's whole extent -- `.cost` int32, `.direction` uint8 and
     `.cell_cost` uint16, each [A, A], three DeviceArrays of one product, [x, y]-indexed with strides (1, A): world cell
@@ -1811,6 +1852,19 @@ class DeviceAtlasField(_ProductView):
             raise ValueError("cell (%d, %d) lies outside the field's extent" % (int(cell[0]), int(cell[1])))
         path = _follow_directions(self._host, x, y, False)
         return None if path is None else [(px + ox, py + oy) for px, py in path]
+
+    def frontiers(self, min_cells=4, max_clusters=1024):
+        """Where unexplored ground remains ANYWHERE this field reaches: DeviceCostField.frontiers() on the field's whole extent, with
+        the atlas's visibility as it is now (seen: visibility > 0; never seen: <= 0; a cell outside the atlas's present extent is
+        neither) -- a DeviceAtlasFrontiers whose clusters are not cut at window borders and whose best cells carry the global cost to
+        go.  Seed the field AT the vehicle.  Neither the field's edge nor the atlas's is a frontier.  The call waits for the labelling.
+        include/gvom_hip.h "atlas frontiers" has the definition."""
+        g = self._hold._owner
+        min_cells, max_clusters = _frontier_limits(min_cells, max_clusters)
+        info, e = (_I64 * 4)(), (_I64 * 2)()
+        hold = g._make_product(lambda pid: g._lib.gvom_atlas_frontiers(g._h, int(self.product_id), min_cells, max_clusters, pid, info, e),
+                               PRODUCT_ATLAS_FRONTIERS, g._check_args)
+        return DeviceAtlasFrontiers(hold, list(info), self._res, (int(e[0]), int(e[1])))
 
     def window(self, device_maps=None, origin_cells=None):
         """The part of this field under a window as a DeviceAtlasFieldWindow (a DeviceCostField): the window of a live DeviceMaps

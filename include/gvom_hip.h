@@ -1028,6 +1028,45 @@ int gvom_atlas_cost_to_go(gvom_t *h, const gvom_ctg_params *params, const int64_
                           int64_t *product_id, int64_t info[4], int64_t extent_origin[2]);
 int gvom_atlas_field_window(gvom_t *h, int64_t field_id, int64_t map_set_id, const int64_t origin_cells[2], int64_t *product_id);
 
+/* --- atlas frontiers (an extension: where unexplored ground remains anywhere the vehicle has been, when the live window has no
+ * frontier left -- one call instead of a recall, a crop and gvom_frontiers per window position, and no cluster cut at a window border) ---
+ * gvom_atlas_frontiers runs "frontier extraction" on the WHOLE extent of an atlas field: the field's cell costs and cost to go, and the
+ * atlas's visibility plane read in place as the atlas is NOW.  Every cluster comes with its nearest member and the global cost to reach
+ * it.  gvom_get_tuning "atlas_frontiers" (read-only) reads 1: how a caller probes a library for this entry point (an addition:
+ * GVOM_ABI_VERSION stays).  All arithmetic is integer: the result is exact and does not depend on scheduling.
+ *
+ * DEFINITION.
+ * MAPS       field_id names a live GVOM_PRODUCT_ATLAS_FIELD of side Af with recorded origin F: c is its part 2, D its part 0; field cell
+ *            (x, y) is world cell F + (x, y) and has linear index y*Af + x.
+ * VISIBILITY comes from the atlas as it is at the moment of the call, with present extent E, side A and the storage phase of E: a world
+ *            cell is KNOWN iff it lies in the present extent and visibility > 0, UNKNOWN iff it lies in the present extent and
+ *            visibility <= 0 (the rule of "atlas fields": gvom_atlas_integrate lets any bit pattern in), and NEITHER outside the present
+ *            extent.  The field is a snapshot: the extent may have moved, or the atlas may have been re-configured to another side,
+ *            since the field was made.  The product lives in the FIELD's frame.
+ * FRONTIER CELL u: c[u] > 0, and u is KNOWN, and D[u] < GVOM_CTG_UNREACHED, and at least one of its four edge neighbours lies inside
+ *            the field's extent and is UNKNOWN.  The graph is the FLAT Af x Af grid: cells on opposite edges of the extent are not
+ *            neighbours, and neither the field's edge nor the atlas's edge is a frontier.
+ * CLUSTER, KEPT, RANK, the rows, the sums, the cluster map and the counts are exactly those of "frontier extraction" with xy_size
+ *            replaced by Af: part 0 int32 [cap, 8], part 1 int64 [cap, 2], part 2 int32 [Af, Af] with strides (1, Af), part 3 int32 [4].
+ *            Labels and best cells are linear indices in the field's frame; extent_origin (may be NULL) receives F.
+ * The call WAITS, like gvom_frontiers, and runs on the handle's stream behind the last integrate and behind whatever wrote the field.
+ * "frontier_batch" and "frontier_inner" shape its rounds too; "atlas_frontier_rounds" / "atlas_frontier_tiles" (read-only): rounds and
+ * tile relaxations of the last call.  info (may be NULL): the four fields of gvom_frontiers.  A field that stopped early (max_rounds) is
+ * accepted: the definition uses only D < GVOM_CTG_UNREACHED.
+ * The product, of kind GVOM_PRODUCT_ATLAS_FRONTIERS, is a SNAPSHOT in the product-set pool under its rule: later integrates, moves,
+ * clears and solves do not change it; an unexported one goes back with the next gvom_atlas_frontiers; with every one exported the call
+ * returns GVOM_ERR_CAPACITY.  The work buffer at side Af (8 bytes per cell plus flags and counters, 128 MB at 4096) is the handle's,
+ * apart from gvom_frontiers' window-sized one, which this call never touches.  "atlas_frontier_allocations" (read-only): device
+ * allocations the entry point has made on this handle (that buffer and its product sets); it does not grow in steady state.
+ * gvom_device_product(kind 28) is GVOM_ERR_INVALID.  Kind 27 is not assigned.
+ * GVOM_ERR_INVALID: a sharded handle; no atlas configured; an unknown, stale or wrong-kind field_id; min_cells < 1; max_clusters outside
+ * 1 .. 2^20; a NULL product_id.
+ * NOT PROVIDED: a crop of the cluster map to a window; caller-supplied planes at atlas scale (the *_of routes); frontiers without D;
+ * splitting of long clusters; a stamp or age filter; incremental re-labelling after an integrate. */
+#define GVOM_PRODUCT_ATLAS_FRONTIERS 28   /* the four parts of kind 16 at side A; kind 27 stays unassigned */
+int gvom_atlas_frontiers(gvom_t *h, int64_t field_id, int32_t min_cells, int32_t max_clusters,
+                         int64_t *product_id, int64_t info[4], int64_t extent_origin[2] /* may be NULL */);
+
 /* --- one map sharded over the GPUs of a node (one rank = one process = one GPU) -------------------
  * No counterpart in the reference (it has no multi-GPU path); semantics = SURVEY 8(e):
  * the rays are data-parallel, the per-voxel accumulators (hit / total: int32 sum, min-height: f32 min)

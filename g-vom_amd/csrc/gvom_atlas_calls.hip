@@ -4,7 +4,8 @@
 // writes a map set of the pool gvom_combine_maps_device takes its sets from (map_set_acquire, gvom_sets.hip) and a product set for the
 // stamps; the extent export is a product like the others.  Below them the atlas fields (include/gvom_hip.h "atlas fields"):
 // gvom_atlas_cost_to_go, which waits like gvom_cost_to_go, and gvom_atlas_field_window; their kernels are gvom_atlas_field.hip's.  Last
-// the atlas frontiers (include/gvom_hip.h "atlas frontiers"): gvom_atlas_frontiers, which waits like gvom_frontiers.
+// the atlas frontiers (include/gvom_hip.h "atlas frontiers"): gvom_atlas_frontiers, which waits like gvom_frontiers.  The checks, the work
+// buffers, the solves and their epilogues that these share with the window's calls are gvom_product_calls.hip's (gvom_host.h lists them).
 #include "gvom_host.h"
 
 namespace {
@@ -23,11 +24,8 @@ Window window_of(const gvom_handle *h, const int64_t origin[2])
 AtlasMaps maps_of_set(const DevSet *s)
 {
     AtlasMaps M;
-    SetPart d;
-    for (int k = 0; k < 9; ++k) {
-        set_part(s, k, &d);
-        if (k < 3) M.i[k] = (int32_t *)d.ptr; else M.f[k - 3] = (unsigned long long *)d.ptr;
-    }
+    for (int k = 0; k < 3; ++k) M.i[k] = part_ptr<int32_t>(s, k);
+    for (int k = 3; k < 9; ++k) M.f[k - 3] = part_ptr<unsigned long long>(s, k);
     M.stamp = nullptr;
     return M;
 }
@@ -53,9 +51,8 @@ int move_extent(gvom_handle *h, const int64_t to[2])
 
 int need_atlas(gvom_handle *h, const char *fn)
 {
-    if (h->sharded) { h->err = std::string(fn) + ": sharded handles are not supported"; return GVOM_ERR_INVALID; }
-    if (!h->atl_A) { h->err = std::string(fn) + ": no atlas is configured (gvom_atlas_configure)"; return GVOM_ERR_INVALID; }
-    return GVOM_OK;
+    if (h->sharded) return refuse(h, fn, "sharded handles are not supported");
+    return h->atl_A ? GVOM_OK : refuse(h, fn, "no atlas is configured (gvom_atlas_configure)");
 }
 }  // namespace
 
@@ -64,7 +61,7 @@ VIS int gvom_atlas_configure(gvom_t *h, int32_t cells, int mode, const int64_t f
 {
     if (!h) return GVOM_ERR_INVALID;
     std::lock_guard<std::mutex> lk(h->mu);
-    if (h->sharded) { h->err = "gvom_atlas_configure: sharded handles are not supported"; return GVOM_ERR_INVALID; }
+    if (h->sharded) return refuse(h, "gvom_atlas_configure", "sharded handles are not supported");
     if (cells != 0) {
         if (cells < GVOM_ATLAS_MIN_CELLS || cells > GVOM_ATLAS_MAX_CELLS || (cells & (cells - 1))) { h->err = "gvom_atlas_configure: the side must be a power of two in 64 .. 4096"; return GVOM_ERR_INVALID; }
         if (cells < h->prm.xy_size) { h->err = "gvom_atlas_configure: the atlas must be at least as large as the window (xy_size)"; return GVOM_ERR_INVALID; }
@@ -119,8 +116,8 @@ VIS int gvom_atlas_integrate(gvom_t *h, int64_t map_set_id, const void *const ma
     int64_t O[3] = {0, 0, h->atl_last[2]};
     AtlasMaps in;
     if (map_set_id >= 0) {
-        DevSet *m = find_set(h->dsets, map_set_id);
-        if (!m) { h->err = "unknown or stale device map set id"; return GVOM_ERR_INVALID; }
+        DevSet *m = nullptr;
+        if ((rc = map_set_of(h, map_set_id, &m))) return rc;
         in = maps_of_set(m);
         for (int k = 0; k < 3; ++k) O[k] = m->origin[k];
     } else {
@@ -132,10 +129,7 @@ VIS int gvom_atlas_integrate(gvom_t *h, int64_t map_set_id, const void *const ma
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, join_second_stream(h));
     if (map_set_id < 0 && !on_device) {                                     // host maps: staged, and up before the call returns
-        if (h->atl_stage.bytes < n2 * 60) {
-            if ((rc = ensure(h, h->atl_stage, n2 * 60))) return rc;
-            ++h->atl_allocs;
-        }
+        if ((rc = stage_buf(h, h->atl_stage, n2 * 60, h->atl_allocs))) return rc;
         char *st = (char *)h->atl_stage.p;
         for (int k = 0; k < 9; ++k) {
             char *at = k >= 3 ? st + (size_t)(k - 3) * n2 * 8 : st + 6 * n2 * 8 + (size_t)k * n2 * 4;
@@ -178,12 +172,11 @@ VIS int gvom_atlas_recall(gvom_t *h, const int64_t origin_cells[2], int64_t *set
     HIPCHK(h, join_second_stream(h));
     if ((rc = set_wait_releases(h, set)) || (rc = set_wait_releases(h, pset))) return rc;
     AtlasMaps out = maps_of_set(set);
-    SetPart d;
-    set_part(pset, 0, &d); out.stamp = (int32_t *)d.ptr;
-    set_part(pset, 1, &d);
-    HIPCHK(h, hipMemsetAsync(d.ptr, 0, 16, h->stream));
+    out.stamp = part_ptr<int32_t>(pset, 0);
+    int32_t *const counts = part_ptr<int32_t>(pset, 1);
+    HIPCHK(h, hipMemsetAsync(counts, 0, 16, h->stream));
     const Window w = window_of(h, R);
-    HIPCHK(h, gvom_launch_atlas_recall(h->stream, h->atl_mem, h->atl_A, out, xy, w.rx, w.ry, w.px, w.py, h->atl_seq, (int32_t *)d.ptr));
+    HIPCHK(h, gvom_launch_atlas_recall(h->stream, h->atl_mem, h->atl_A, out, xy, w.rx, w.ry, w.px, w.py, h->atl_seq, counts));
     HIPCHK(h, hipEventRecord(set->ready, h->stream));
     if ((rc = product_publish(h, pset, product_id))) return rc;
     set->origin[0] = R[0]; set->origin[1] = R[1]; set->origin[2] = h->atl_last[2];
@@ -213,10 +206,9 @@ VIS int gvom_atlas_extent(gvom_t *h, int64_t *product_id, int64_t extent_origin[
     if ((rc = set_wait_releases(h, pset))) return rc;
     AtlasMaps out;
     memset(&out, 0, sizeof out);
-    SetPart d;
-    for (int k = 0; k < 3; ++k) { set_part(pset, k, &d); out.i[k] = (int32_t *)d.ptr; }
-    for (int k = 0; k < 2; ++k) { set_part(pset, 3 + k, &d); out.f[k] = (unsigned long long *)d.ptr; }
-    set_part(pset, 5, &d); out.stamp = (int32_t *)d.ptr;
+    for (int k = 0; k < 3; ++k) out.i[k] = part_ptr<int32_t>(pset, k);
+    for (int k = 0; k < 2; ++k) out.f[k] = part_ptr<unsigned long long>(pset, 3 + k);
+    out.stamp = part_ptr<int32_t>(pset, 5);
     const Window w = window_of(h, h->atl_E);
     HIPCHK(h, gvom_launch_atlas_recall(h->stream, h->atl_mem, A, out, A, 0, 0, w.px, w.py, h->atl_seq, nullptr));
     if (extent_origin) { extent_origin[0] = h->atl_E[0]; extent_origin[1] = h->atl_E[1]; }
@@ -240,7 +232,7 @@ VIS int gvom_atlas_counts(gvom_t *h, int64_t out[8])
 // ---- atlas fields (include/gvom_hip.h "atlas fields") -----------------------------------------------------------------------------------
 // gvom_cost_to_go's solve at the atlas's side: the front ends of gvom_atlas_field.hip read the toroidal planes in place and write the
 // unwrapped obstacle distances and cost map, k_clearance_cols and the solver (ctg_solve, gvom_product_calls.hip) run on those as on any
-// [y][x] map of A x A cells.  The buffers are the handle's own at side A (af_work, af_clr): gvom_cost_to_go's stay as they are.
+// [y][x] map of A x A cells.  The buffers are the handle's own at side A (af.work, af_clr): gvom_cost_to_go's stay as they are.
 VIS int gvom_atlas_cost_to_go(gvom_t *h, const gvom_ctg_params *params, const int64_t *goals, int64_t n_goals, int32_t max_cost,
                               int32_t max_rounds, int flags, int64_t *product_id, int64_t info[4], int64_t extent_origin[2])
 {
@@ -248,15 +240,14 @@ VIS int gvom_atlas_cost_to_go(gvom_t *h, const gvom_ctg_params *params, const in
     std::lock_guard<std::mutex> lk(h->mu);
     *product_id = -1;
     for (int k = 0; info && k < 4; ++k) info[k] = 0;
-    int rc = need_atlas(h, "gvom_atlas_cost_to_go");
+    const char *const fn = "gvom_atlas_cost_to_go";
+    int rc = need_atlas(h, fn);
     if (rc) return rc;
     if (flags & ~(GVOM_CTG_NO_NEGATIVE | GVOM_CTG_UNKNOWN_BLOCKS)) { h->err = "gvom_atlas_cost_to_go: unknown flag bits"; return GVOM_ERR_INVALID; }
     if (!params) { h->err = "gvom_atlas_cost_to_go: the cost parameters must not be NULL"; return GVOM_ERR_INVALID; }
-    if (!goals || n_goals < 1 || n_goals > GVOM_CTG_MAX_GOALS) { h->err = "gvom_atlas_cost_to_go: between 1 and 65536 goals"; return GVOM_ERR_INVALID; }
-    if (max_cost < 0 || max_cost > GVOM_CTG_MAX_COST) { h->err = "gvom_atlas_cost_to_go: max_cost outside 0 .. 2^30"; return GVOM_ERR_INVALID; }
-    if (max_rounds < 0) { h->err = "gvom_atlas_cost_to_go: max_rounds must not be negative"; return GVOM_ERR_INVALID; }
+    if ((rc = check_goals(h, fn, goals, n_goals, max_cost, max_rounds))) return rc;
     CtgCostParams C;
-    if ((rc = ctg_cost_params(h, "gvom_atlas_cost_to_go", params, flags, &C))) return rc;
+    if ((rc = ctg_cost_params(h, fn, params, flags, &C))) return rc;
     const int A = h->atl_A;
     const int64_t E[2] = {h->atl_E[0], h->atl_E[1]};
     std::vector<int32_t> rel((size_t)2 * n_goals);                          // the goals as the solver takes them: extent cells
@@ -273,31 +264,19 @@ VIS int gvom_atlas_cost_to_go(gvom_t *h, const gvom_ctg_params *params, const in
     HIPCHK(h, hipSetDevice(h->device));
     DevSet *set = nullptr;
     const size_t a2 = (size_t)A * A, bytes = set_bytes(GVOM_PRODUCT_ATLAS_FIELD, 0, 0, A);
-    if ((rc = product_acquire(h, GVOM_PRODUCT_ATLAS_FIELD, bytes, bytes, "gvom_atlas_cost_to_go", &h->af_allocs, &set))) return rc;
+    if ((rc = product_acquire(h, GVOM_PRODUCT_ATLAS_FIELD, bytes, bytes, fn, &h->af_allocs, &set))) return rc;
     set->cap = A;
-    const int nt = gvom_ctg_tiles(A), ntiles = nt * nt;
-    const size_t flags_off = 256, goals_off = flags_off + align256((size_t)2 * ntiles * 4), work = goals_off + (size_t)GVOM_CTG_MAX_GOALS * 8;
-    if (h->af_work.bytes < work) {
-        if ((rc = ensure(h, h->af_work, work))) return rc;
-        ++h->af_allocs;
-    }
+    const int nt = gvom_ctg_tiles(A);
+    const GoalWork lay = goal_work(nt * nt, 8, 0);
+    if ((rc = solve_work_reserve(h, h->af, lay.end, h->af_allocs))) return rc;
     const size_t clr_g = align256(a2 * 2), clr_map = align256(a2 * 4);
-    if (C.inflation_cells2 > 0 && h->af_clr.bytes < clr_g + 2 * clr_map) {
-        if ((rc = ensure(h, h->af_clr, clr_g + 2 * clr_map))) return rc;
-        ++h->af_allocs;
-    }
-    if (!h->af_pin) HIPCHK(h, hipHostMalloc((void **)&h->af_pin, 256, hipHostMallocDefault));
-    uint32_t *cnt = (uint32_t *)h->af_work.p;
-    uint32_t *fl = (uint32_t *)((char *)h->af_work.p + flags_off);
-    int32_t *gdev = (int32_t *)((char *)h->af_work.p + goals_off);
+    if (C.inflation_cells2 > 0 && (rc = stage_buf(h, h->af_clr, clr_g + 2 * clr_map, h->af_allocs))) return rc;
+    const GoalWorkPtrs G = goal_work_ptrs(h->af, lay);
     HIPCHK(h, join_second_stream(h));
-    HIPCHK(h, hipMemcpyAsync(gdev, rel.data(), (size_t)n_goals * 8, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemsetAsync(cnt, 0, 256, h->stream));
-    if ((rc = set_wait_releases(h, set))) return rc;
-    SetPart d;
-    set_part(set, 0, &d); int32_t *D = (int32_t *)d.ptr;
-    set_part(set, 1, &d); uint8_t *dir = (uint8_t *)d.ptr;
-    set_part(set, 2, &d); uint16_t *c16 = (uint16_t *)d.ptr;
+    if ((rc = goal_work_start(h, G, rel.data(), (size_t)n_goals * 8)) || (rc = set_wait_releases(h, set))) return rc;
+    int32_t *D = part_ptr<int32_t>(set, 0);
+    uint8_t *dir = part_ptr<uint8_t>(set, 1);
+    uint16_t *c16 = part_ptr<uint16_t>(set, 2);
     const Window w = window_of(h, E);                                       // (its storage phase is the extent's)
     const int32_t *cd2 = nullptr;
     if (C.inflation_cells2 > 0) {
@@ -308,15 +287,10 @@ VIS int gvom_atlas_cost_to_go(gvom_t *h, const gvom_ctg_params *params, const in
         cd2 = (const int32_t *)(q + clr_g + clr_map);
     }
     HIPCHK(h, gvom_launch_atlas_travcost(h->stream, h->atl_mem, A, w.px, w.py, cd2, C, c16));
-    CtgSolve S;
-    if ((rc = ctg_solve(h, A, nullptr, c16, D, dir, cnt, fl, gdev, (int)n_goals, max_cost, max_rounds, h->af_pin, &S))) return rc;
+    SolveRounds S;
+    if ((rc = ctg_solve(h, h->af, G, A, nullptr, c16, D, dir, (int)n_goals, max_cost, max_rounds, &S))) return rc;
     set->origin[0] = E[0]; set->origin[1] = E[1]; set->origin[2] = 0;
-    if ((rc = product_publish(h, set, product_id))) return rc;             // (`ready` goes in front of the counters' way back)
-    HIPCHK(h, hipMemcpyAsync(h->af_pin, cnt, 256, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (!S.converged && max_rounds == 0) { set->id = *product_id = -1; h->err = "gvom_atlas_cost_to_go: the field did not settle"; return GVOM_ERR_HIP; }   // (nobody gets it)
-    h->af_last_tiles = (int)std::min<int64_t>(S.tiles, INT32_MAX);
-    if (info) { info[0] = S.converged ? 1 : 0; info[1] = S.rounds; info[2] = h->af_pin[CTG_CNT_REACHED]; info[3] = h->af_pin[CTG_CNT_SEEDED]; }
+    if ((rc = goal_solve_finish(h, fn, h->af, set, product_id, S, max_rounds, info))) return rc;
     if (extent_origin) { extent_origin[0] = E[0]; extent_origin[1] = E[1]; }
     return GVOM_OK;
 }
@@ -326,15 +300,15 @@ VIS int gvom_atlas_field_window(gvom_t *h, int64_t field_id, int64_t map_set_id,
     if (!h || !product_id) return GVOM_ERR_INVALID;
     std::lock_guard<std::mutex> lk(h->mu);
     *product_id = -1;
-    if (h->sharded) { h->err = "gvom_atlas_field_window: sharded handles are not supported"; return GVOM_ERR_INVALID; }
-    DevSet *f = find_set(h->psets, field_id);
-    if (!f || f->kind != GVOM_PRODUCT_ATLAS_FIELD) { h->err = "gvom_atlas_field_window: unknown or stale atlas field id"; return GVOM_ERR_INVALID; }
-    if (map_set_id >= 0 && origin_cells) { h->err = "gvom_atlas_field_window: give a map set id or origin_cells, not both"; return GVOM_ERR_INVALID; }
-    if (map_set_id < 0 && !origin_cells) { h->err = "gvom_atlas_field_window: give a map set id or origin_cells"; return GVOM_ERR_INVALID; }
+    const char *const fn = "gvom_atlas_field_window";
+    if (h->sharded) return refuse(h, fn, "sharded handles are not supported");
+    DevSet *f = nullptr;
+    int rc;
+    if ((rc = atlas_field_of(h, fn, field_id, &f)) || (rc = check_one_source(h, fn, map_set_id >= 0, origin_cells, !origin_cells, "a map set id", "origin_cells", "origin_cells"))) return rc;
     int64_t R[2];
     if (map_set_id >= 0) {
-        DevSet *m = find_set(h->dsets, map_set_id);
-        if (!m) { h->err = "unknown or stale device map set id"; return GVOM_ERR_INVALID; }
+        DevSet *m = nullptr;
+        if ((rc = map_set_of(h, map_set_id, &m))) return rc;
         R[0] = m->origin[0]; R[1] = m->origin[1];
     } else {
         if (!origin_ok(origin_cells)) { h->err = "gvom_atlas_field_window: an origin beyond 2^40 cells"; return GVOM_ERR_INVALID; }
@@ -344,22 +318,19 @@ VIS int gvom_atlas_field_window(gvom_t *h, int64_t field_id, int64_t map_set_id,
     HIPCHK(h, hipSetDevice(h->device));
     DevSet *set = nullptr;
     const size_t bytes = set_bytes(GVOM_PRODUCT_COSTFIELD, xy, 0, 0);
-    int rc = product_acquire(h, GVOM_PRODUCT_COSTFIELD, bytes, bytes, "gvom_atlas_field_window", &h->af_allocs, &set);
-    if (rc) return rc;
+    if ((rc = product_acquire(h, GVOM_PRODUCT_COSTFIELD, bytes, bytes, fn, &h->af_allocs, &set))) return rc;
     HIPCHK(h, join_second_stream(h));
     if ((rc = set_wait_releases(h, set))) return rc;
-    SetPart fd[3], od[3];
-    for (int k = 0; k < 3; ++k) { set_part(f, k, &fd[k]); set_part(set, k, &od[k]); }
     const int rx = (int)std::max(-AT_REL, std::min(AT_REL, R[0] - f->origin[0])), ry = (int)std::max(-AT_REL, std::min(AT_REL, R[1] - f->origin[1]));
-    HIPCHK(h, gvom_launch_atlas_field_window(h->stream, A, (const int32_t *)fd[0].ptr, (const uint8_t *)fd[1].ptr, (const uint16_t *)fd[2].ptr, xy, rx, ry,
-                                             (int32_t *)od[0].ptr, (uint8_t *)od[1].ptr, (uint16_t *)od[2].ptr));
+    HIPCHK(h, gvom_launch_atlas_field_window(h->stream, A, part_ptr<const int32_t>(f, 0), part_ptr<const uint8_t>(f, 1), part_ptr<const uint16_t>(f, 2), xy, rx, ry,
+                                             part_ptr<int32_t>(set, 0), part_ptr<uint8_t>(set, 1), part_ptr<uint16_t>(set, 2)));
     return product_publish(h, set, product_id);
 }
 
 // ---- atlas frontiers (include/gvom_hip.h "atlas frontiers") ------------------------------------------------------------------------------
 // gvom_frontiers at the side of an atlas field: k_atlas_frontier_mark (gvom_atlas_frontier.hip) reads c and D from the field and the
 // visibility in place from the atlas as it is now, everything behind it is frontier_solve (gvom_product_calls.hip) on a work buffer of
-// the handle's own at that side (afr_work): gvom_frontiers' window-sized one stays as it is.
+// the handle's own at that side (afr.work): gvom_frontiers' window-sized one stays as it is.
 VIS int gvom_atlas_frontiers(gvom_t *h, int64_t field_id, int32_t min_cells, int32_t max_clusters, int64_t *product_id, int64_t info[4],
                              int64_t extent_origin[2])
 {
@@ -367,40 +338,31 @@ VIS int gvom_atlas_frontiers(gvom_t *h, int64_t field_id, int32_t min_cells, int
     std::lock_guard<std::mutex> lk(h->mu);
     *product_id = -1;
     for (int k = 0; info && k < 4; ++k) info[k] = 0;
-    int rc = need_atlas(h, "gvom_atlas_frontiers");
+    const char *const fn = "gvom_atlas_frontiers";
+    int rc = need_atlas(h, fn);
     if (rc) return rc;
-    DevSet *f = find_set(h->psets, field_id);
-    if (!f || f->kind != GVOM_PRODUCT_ATLAS_FIELD) { h->err = "gvom_atlas_frontiers: unknown or stale atlas field id"; return GVOM_ERR_INVALID; }
-    if (min_cells < 1) { h->err = "gvom_atlas_frontiers: min_cells must be at least 1"; return GVOM_ERR_INVALID; }
-    if (max_clusters < 1 || max_clusters > GVOM_FRONTIER_MAX_CLUSTERS) { h->err = "gvom_atlas_frontiers: max_clusters outside 1 .. 2^20"; return GVOM_ERR_INVALID; }
+    DevSet *f = nullptr;
+    if ((rc = atlas_field_of(h, fn, field_id, &f)) || (rc = check_clusters(h, fn, min_cells, max_clusters))) return rc;
     const int Af = (int)f->cap;
     const int64_t F[2] = {f->origin[0], f->origin[1]};
     HIPCHK(h, hipSetDevice(h->device));
     DevSet *set = nullptr;
     const size_t bytes = set_bytes(GVOM_PRODUCT_ATLAS_FRONTIERS, 0, 0, max_clusters, Af);
-    if ((rc = product_acquire(h, GVOM_PRODUCT_ATLAS_FRONTIERS, bytes, bytes, "gvom_atlas_frontiers", &h->afr_allocs, &set))) return rc;
+    if ((rc = product_acquire(h, GVOM_PRODUCT_ATLAS_FRONTIERS, bytes, bytes, fn, &h->afr_allocs, &set))) return rc;
     set->cap = max_clusters; set->cols = Af;
-    if (h->afr_work.bytes < fr_work_bytes(Af)) {
-        if ((rc = ensure(h, h->afr_work, fr_work_bytes(Af)))) return rc;
-        ++h->afr_allocs;
-    }
-    if (!h->afr_pin) HIPCHK(h, hipHostMalloc((void **)&h->afr_pin, 256, hipHostMallocDefault));
-    const FrWork W = fr_work_layout(Af, (char *)h->afr_work.p);
+    FrWork W;
+    if ((rc = frontier_work(h, h->afr, Af, h->afr_allocs, &W))) return rc;
     HIPCHK(h, join_second_stream(h));
     HIPCHK(h, hipMemsetAsync(W.cnt, 0, W.clear_bytes, h->stream));          // the counters and both halves of the flags
     if ((rc = set_wait_releases(h, set))) return rc;
-    SetPart d;
-    set_part(f, 0, &d); const int32_t *D = (const int32_t *)d.ptr;
-    set_part(f, 2, &d); const uint16_t *c16 = (const uint16_t *)d.ptr;
+    const int32_t *D = part_ptr<const int32_t>(f, 0);
+    const uint16_t *c16 = part_ptr<const uint16_t>(f, 2);
     const Window w = window_of(h, F);                                       // the field's corner relative to the extent as it is now
     const Window e = window_of(h, h->atl_E);                                // (its storage phase is the extent's)
     HIPCHK(h, gvom_launch_atlas_frontier_mark(h->stream, Af, c16, D, h->atl_mem, h->atl_A, w.rx, w.ry, e.px, e.py, W.L, W.count, W.fl,
                                               W.cnt + FR_CNT_CELLS));
-    FrSolve S;
-    if ((rc = frontier_solve(h, "gvom_atlas_frontiers", Af, D, W, h->afr_pin, min_cells, max_clusters, set, product_id, info, &S))) return rc;
+    if ((rc = frontier_solve(h, fn, h->afr, Af, D, W, min_cells, max_clusters, set, product_id, info))) return rc;
     set->origin[0] = F[0]; set->origin[1] = F[1]; set->origin[2] = 0;
-    h->afr_last_rounds = (int)std::min<int64_t>(S.rounds, INT32_MAX);
-    h->afr_last_tiles = (int)std::min<int64_t>(S.tiles, INT32_MAX);
     if (extent_origin) { extent_origin[0] = F[0]; extent_origin[1] = F[1]; }
     return GVOM_OK;
 }

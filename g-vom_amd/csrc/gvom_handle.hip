@@ -448,7 +448,8 @@ VIS void gvom_destroy(gvom_t *h)
     if (h->x_host) hipHostFree(h->x_host);
     for (auto &s : h->slots) { hipFree(s.state); hipFree(s.code16); hipFree(s.tags); fb(s.crows); fb(s.metrics); fb(s.base); fb(s.rowvox); }
     for (auto &f : h->fused) { hipFree(f.state); hipFree(f.tags); fb(f.rows); fb(f.metrics); }
-    fb(h->in_pts); fb(h->cl_g); fb(h->cl_stage); fb(h->rq_stage); fb(h->ctg_work); fb(h->ctg_stage); fb(h->ctg_clr); fb(h->fp_tab); fb(h->ro_stage); fb(h->at_tab); fb(h->at_ground); fb(h->at_stage); fb(h->al_grid); fb(h->al_stage); fb(h->fr_work); fb(h->fr_stage); fb(h->vp_bitmaps); fb(h->vp_stage); fb(h->pf_tab); fb(h->pf_work); fb(h->pf_stage); fb(h->atl_stage); fb(h->af_work); fb(h->af_clr); fb(h->afr_work); if (h->af_pin) hipHostFree(h->af_pin); if (h->afr_pin) hipHostFree(h->afr_pin); hipFree(h->atl_mem); hipFree(h->atl_cnt); if (h->atl_pin) hipHostFree(h->atl_pin); if (h->pf_pin) hipHostFree(h->pf_pin); if (h->fr_pin) hipHostFree(h->fr_pin); if (h->ctg_pin) hipHostFree(h->ctg_pin); fb(h->ri_model); fb(h->ri_raw); fb(h->ri_poses); if (h->ri_poses_pin) hipHostFree(h->ri_poses_pin); fb(h->mo_dev); if (h->mo_pin) hipHostFree(h->mo_pin); fb(h->world_pts[0]); fb(h->world_pts[1]); fb(h->flink[0]); fb(h->flink[1]); fb(h->tl); fb(h->dir_keys); fb(h->dir_perm); hipFree(h->dir_hist);
+    fb(h->in_pts); fb(h->cl_g); fb(h->cl_stage); fb(h->rq_stage); fb(h->ctg_stage); fb(h->ctg_clr); fb(h->fp_tab); fb(h->ro_stage); fb(h->at_tab); fb(h->at_ground); fb(h->at_stage); fb(h->al_grid); fb(h->al_stage); fb(h->fr_stage); fb(h->vp_bitmaps); fb(h->vp_stage); fb(h->pf_tab); fb(h->pf_stage); fb(h->atl_stage); fb(h->af_clr); hipFree(h->atl_mem); hipFree(h->atl_cnt); if (h->atl_pin) hipHostFree(h->atl_pin); fb(h->ri_model); fb(h->ri_raw); fb(h->ri_poses); if (h->ri_poses_pin) hipHostFree(h->ri_poses_pin); fb(h->mo_dev); if (h->mo_pin) hipHostFree(h->mo_pin); fb(h->world_pts[0]); fb(h->world_pts[1]); fb(h->flink[0]); fb(h->flink[1]); fb(h->tl); fb(h->dir_keys); fb(h->dir_perm); hipFree(h->dir_hist);
+    for (SolveWork *w : {&h->ctg, &h->fr, &h->pf, &h->af, &h->afr}) { fb(w->work); if (w->pin) hipHostFree(w->pin); }   // the calls that wait: work buffer and pinned counters
     hipFree(h->counters); if (h->counters_host) hipHostFree(h->counters_host);
     hipFree(h->descs_dev); if (h->descs_host) hipHostFree(h->descs_host);
     hipFree(h->blockcounts); hipFree(h->blockcounts2); hipFree(h->hmaps2);
@@ -536,12 +537,12 @@ VIS int gvom_set_tuning(gvom_t *h, const char *name, int value)
     else if (!strcmp(name, "fastdiv")) h->tune_fastdiv = value;
     else if (!strcmp(name, "eager")) { h->tune_eager = value; h->eager_waste = 0; }
     else if (!strcmp(name, "delta_out")) { if (value >= 0) h->tune_delta_out = value != 0; if (value <= 0) h->out_rec.clear(); }   // (-1: drop every record, keep the setting)   // 0: every run of the returned maps is stored, no record kept
-    else if (!strcmp(name, "cost_to_go_inner")) h->tune_ctg_inner = value < 0 ? 0 : value;     // sweeps a tile makes at most per round (0: 256)
-    else if (!strcmp(name, "cost_to_go_batch")) h->tune_ctg_batch = value < 0 ? 0 : (value > GVOM_CTG_MAX_BATCH ? GVOM_CTG_MAX_BATCH : value);   // rounds per look at the counters (0: 8)
-    else if (!strcmp(name, "frontier_inner")) h->tune_fr_inner = value < 0 ? 0 : value;        // sweeps a tile makes at most per round (0: 256)
-    else if (!strcmp(name, "frontier_batch")) h->tune_fr_batch = value < 0 ? 0 : (value > GVOM_CTG_MAX_BATCH ? GVOM_CTG_MAX_BATCH : value);   // rounds per look at the counters (0: 8)
-    else if (!strcmp(name, "pose_field_inner")) h->tune_pf_inner = value < 0 ? 0 : value;      // sweeps a tile makes at most per round (0: 64)
-    else if (!strcmp(name, "pose_field_batch")) h->tune_pf_batch = value < 0 ? 0 : (value > GVOM_CTG_MAX_BATCH ? GVOM_CTG_MAX_BATCH : value);   // rounds per look at the counters (0: 8)
+    else if (!strcmp(name, "cost_to_go_inner")) h->ctg.tune_inner = value < 0 ? 0 : value;     // sweeps a tile makes at most per round (0: 256)
+    else if (!strcmp(name, "cost_to_go_batch")) h->ctg.tune_batch = value < 0 ? 0 : (value > GVOM_CTG_MAX_BATCH ? GVOM_CTG_MAX_BATCH : value);   // rounds per look at the counters (0: 8)
+    else if (!strcmp(name, "frontier_inner")) h->fr.tune_inner = value < 0 ? 0 : value;        // sweeps a tile makes at most per round (0: 256)
+    else if (!strcmp(name, "frontier_batch")) h->fr.tune_batch = value < 0 ? 0 : (value > GVOM_CTG_MAX_BATCH ? GVOM_CTG_MAX_BATCH : value);   // rounds per look at the counters (0: 8)
+    else if (!strcmp(name, "pose_field_inner")) h->pf.tune_inner = value < 0 ? 0 : value;      // sweeps a tile makes at most per round (0: 64)
+    else if (!strcmp(name, "pose_field_batch")) h->pf.tune_batch = value < 0 ? 0 : (value > GVOM_CTG_MAX_BATCH ? GVOM_CTG_MAX_BATCH : value);   // rounds per look at the counters (0: 8)
     else if (!strcmp(name, "viewpoint_bitmap_mb")) h->tune_vp_mb = value < 0 ? GVOM_VIEWPOINT_DEFAULT_MB : (value > GVOM_VIEWPOINT_MAX_MB ? GVOM_VIEWPOINT_MAX_MB : value);   // megabytes of bitmaps per launch (0: one viewpoint per launch; < 0: the default, 256)
     else if (!strcmp(name, "occupancy_clear")) h->tune_occ_clear = value;   // k_occupancy: 1 = clear the grid first, write live tile columns only
     else if (!strcmp(name, "exported")) h->exported = value != 0;       // (set by the peer transport, gvom_comm.hip)
@@ -574,9 +575,9 @@ VIS int gvom_get_tuning(gvom_t *h, const char *name, int *value)
     if (!strcmp(name, "raycast_allocations")) { *value = h->rq_allocs; return GVOM_OK; }                // read-only: device allocations gvom_raycast has made
     if (!strcmp(name, "cost_to_go")) { *value = 1; return GVOM_OK; }                                    // read-only: the library has gvom_cost_to_go
     if (!strcmp(name, "cost_to_go_allocations")) { *value = h->ctg_allocs; return GVOM_OK; }            // read-only: device allocations gvom_cost_to_go has made
-    if (!strcmp(name, "cost_to_go_tiles")) { *value = h->ctg_last_tiles; return GVOM_OK; }              // read-only: tile relaxations of the last gvom_cost_to_go
-    if (!strcmp(name, "cost_to_go_inner")) { *value = h->tune_ctg_inner; return GVOM_OK; }
-    if (!strcmp(name, "cost_to_go_batch")) { *value = h->tune_ctg_batch; return GVOM_OK; }
+    if (!strcmp(name, "cost_to_go_tiles")) { *value = h->ctg.last_tiles; return GVOM_OK; }              // read-only: tile relaxations of the last gvom_cost_to_go
+    if (!strcmp(name, "cost_to_go_inner")) { *value = h->ctg.tune_inner; return GVOM_OK; }
+    if (!strcmp(name, "cost_to_go_batch")) { *value = h->ctg.tune_batch; return GVOM_OK; }
     if (!strcmp(name, "rollouts")) { *value = 1; return GVOM_OK; }                                      // read-only: the library has gvom_score_rollouts
     if (!strcmp(name, "footprint")) { *value = h->fp_H > 0 ? 1 : 0; return GVOM_OK; }                   // read-only: a footprint table is set
     if (!strcmp(name, "rollout_allocations")) { *value = h->ro_allocs; return GVOM_OK; }                // read-only: device allocations gvom_score_rollouts has made
@@ -586,10 +587,10 @@ VIS int gvom_get_tuning(gvom_t *h, const char *name, int *value)
     if (!strcmp(name, "attitude_allocations")) { *value = h->at_allocs; return GVOM_OK; }               // read-only: device allocations gvom_score_attitude has made
     if (!strcmp(name, "frontiers")) { *value = 1; return GVOM_OK; }                                     // read-only: the library has gvom_frontiers
     if (!strcmp(name, "frontier_allocations")) { *value = h->fr_allocs; return GVOM_OK; }               // read-only: device allocations gvom_frontiers has made
-    if (!strcmp(name, "frontier_rounds")) { *value = h->fr_last_rounds; return GVOM_OK; }               // read-only: rounds of the last gvom_frontiers
-    if (!strcmp(name, "frontier_tiles")) { *value = h->fr_last_tiles; return GVOM_OK; }                 // read-only: tile relaxations of the last gvom_frontiers
-    if (!strcmp(name, "frontier_inner")) { *value = h->tune_fr_inner; return GVOM_OK; }
-    if (!strcmp(name, "frontier_batch")) { *value = h->tune_fr_batch; return GVOM_OK; }
+    if (!strcmp(name, "frontier_rounds")) { *value = h->fr.last_rounds; return GVOM_OK; }               // read-only: rounds of the last gvom_frontiers
+    if (!strcmp(name, "frontier_tiles")) { *value = h->fr.last_tiles; return GVOM_OK; }                 // read-only: tile relaxations of the last gvom_frontiers
+    if (!strcmp(name, "frontier_inner")) { *value = h->fr.tune_inner; return GVOM_OK; }
+    if (!strcmp(name, "frontier_batch")) { *value = h->fr.tune_batch; return GVOM_OK; }
     if (!strcmp(name, "viewpoints")) { *value = 1; return GVOM_OK; }                                    // read-only: the library has gvom_score_viewpoints
     if (!strcmp(name, "viewpoint_allocations")) { *value = h->vp_allocs; return GVOM_OK; }              // read-only: device allocations gvom_score_viewpoints has made
     if (!strcmp(name, "viewpoint_batch")) { *value = h->vp_last_batch; return GVOM_OK; }                // read-only: viewpoints per launch of the last gvom_score_viewpoints
@@ -597,18 +598,18 @@ VIS int gvom_get_tuning(gvom_t *h, const char *name, int *value)
     if (!strcmp(name, "pose_field")) { *value = 1; return GVOM_OK; }                                    // read-only: the library has gvom_pose_field
     if (!strcmp(name, "primitives")) { *value = h->pf_H > 0 ? 1 : 0; return GVOM_OK; }                  // read-only: a primitive table is set
     if (!strcmp(name, "pose_field_allocations")) { *value = h->pf_allocs; return GVOM_OK; }             // read-only: device allocations gvom_primitives_set / gvom_pose_field have made
-    if (!strcmp(name, "pose_field_rounds")) { *value = h->pf_last_rounds; return GVOM_OK; }             // read-only: rounds of the last gvom_pose_field
-    if (!strcmp(name, "pose_field_tiles")) { *value = h->pf_last_tiles; return GVOM_OK; }               // read-only: tile relaxations of the last gvom_pose_field
-    if (!strcmp(name, "pose_field_inner")) { *value = h->tune_pf_inner; return GVOM_OK; }
-    if (!strcmp(name, "pose_field_batch")) { *value = h->tune_pf_batch; return GVOM_OK; }
+    if (!strcmp(name, "pose_field_rounds")) { *value = h->pf.last_rounds; return GVOM_OK; }             // read-only: rounds of the last gvom_pose_field
+    if (!strcmp(name, "pose_field_tiles")) { *value = h->pf.last_tiles; return GVOM_OK; }               // read-only: tile relaxations of the last gvom_pose_field
+    if (!strcmp(name, "pose_field_inner")) { *value = h->pf.tune_inner; return GVOM_OK; }
+    if (!strcmp(name, "pose_field_batch")) { *value = h->pf.tune_batch; return GVOM_OK; }
     if (!strcmp(name, "atlas")) { *value = h->atl_A; return GVOM_OK; }                                   // read-only: the side of the configured atlas in cells, 0 without one
     if (!strcmp(name, "atlas_cost_to_go")) { *value = 1; return GVOM_OK; }                              // read-only: the library has gvom_atlas_cost_to_go and gvom_atlas_field_window
     if (!strcmp(name, "atlas_field_allocations")) { *value = h->af_allocs; return GVOM_OK; }            // read-only: device allocations those two have made
-    if (!strcmp(name, "atlas_field_tiles")) { *value = h->af_last_tiles; return GVOM_OK; }              // read-only: tile relaxations of the last gvom_atlas_cost_to_go
+    if (!strcmp(name, "atlas_field_tiles")) { *value = h->af.last_tiles; return GVOM_OK; }              // read-only: tile relaxations of the last gvom_atlas_cost_to_go
     if (!strcmp(name, "atlas_frontiers")) { *value = 1; return GVOM_OK; }                               // read-only: the library has gvom_atlas_frontiers
     if (!strcmp(name, "atlas_frontier_allocations")) { *value = h->afr_allocs; return GVOM_OK; }        // read-only: device allocations gvom_atlas_frontiers has made
-    if (!strcmp(name, "atlas_frontier_rounds")) { *value = h->afr_last_rounds; return GVOM_OK; }        // read-only: rounds of the last gvom_atlas_frontiers
-    if (!strcmp(name, "atlas_frontier_tiles")) { *value = h->afr_last_tiles; return GVOM_OK; }          // read-only: tile relaxations of the last gvom_atlas_frontiers
+    if (!strcmp(name, "atlas_frontier_rounds")) { *value = h->afr.last_rounds; return GVOM_OK; }        // read-only: rounds of the last gvom_atlas_frontiers
+    if (!strcmp(name, "atlas_frontier_tiles")) { *value = h->afr.last_tiles; return GVOM_OK; }          // read-only: tile relaxations of the last gvom_atlas_frontiers
     if (!strcmp(name, "atlas_allocations")) { *value = h->atl_allocs; return GVOM_OK; }                  // read-only: device allocations the gvom_atlas_* calls have made
     if (!strcmp(name, "alignment_allocations")) { *value = h->al_allocs; return GVOM_OK; }              // read-only: device allocations gvom_score_alignments has made
     if (!strcmp(name, "alignment_grid_bytes")) { *value = (int)(h->al_grid.bytes > 0x7fffffffu ? 0x7fffffffu : h->al_grid.bytes); return GVOM_OK; }   // read-only: the class grid's allocation

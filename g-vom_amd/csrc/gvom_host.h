@@ -1,11 +1,14 @@
-// gvom_host.h -- private to the host units of libgvom_hip.so (gvom_handle / gvom_capi (scans) / gvom_combine / gvom_sets / gvom_product_calls / gvom_debug .hip):
-// the handle and what it is made of, and the functions that cross those units' boundaries (namespace gvom_host; -fvisibility=hidden
-// keeps them out of the dynamic symbol table).  Not part of the public interface (include/gvom_hip.h is); no kernel unit includes it.
+// gvom_host.h -- private to the host units of libgvom_hip.so (gvom_handle / gvom_capi (scans) / gvom_combine / gvom_sets / gvom_product_calls /
+// gvom_atlas_calls / gvom_debug .hip): the handle and what it is made of, and the functions that cross those units' boundaries (namespace
+// gvom_host; -fvisibility=hidden keeps them out of the dynamic symbol table) -- among them what the product calls and the atlas calls
+// share: the round driver of the calls that wait, their epilogue, the argument checks, the staging of host inputs (at the end of this
+// file).  Not part of the public interface (include/gvom_hip.h is); no kernel unit includes it.
 #pragma once
 #include "gvom_internal.h"
 #include "gvom_ingest.h"
 #include "gvom_outrec.h"
 #include "gvom_setlayout.h"
+#include "gvom_solvework.h"
 #include "../../include/gvom_hip.h"
 
 #include <math.h>
@@ -78,10 +81,7 @@ struct DevSet : SetShape {                     // (mem, xy, kind, zs, cap: gvom_
 #define GVOM_MAX_DEVICE_SETS 8
 #define GVOM_N_PRODUCT_KINDS 4                  // the kinds gvom_device_product makes (clearance products, raycast products and cost fields have entry points of their own)
 #define GVOM_RAYCAST_MAX_RAYS ((int64_t)1 << 26)
-#define GVOM_CTG_MAX_GOALS 65536
-#define GVOM_CTG_MAX_BATCH 16                   // rounds enqueued between two looks at the counters: at most
-// ctg_work's counters (uint32): [r] tiles that flagged any in round r of the batch, [16 + r] tiles that ran, [32] reached cells, [33] goals seeded
-#define CTG_CNT_RELAXED 16
+// a goal solver's counters (uint32) behind the rounds' (gvom_solvework.h): [32] reached cells, [33] goals seeded
 #define CTG_CNT_REACHED 32
 #define CTG_CNT_SEEDED 33
 #define GVOM_FRONTIER_MAX_CLUSTERS (1 << 20)
@@ -89,13 +89,23 @@ struct DevSet : SetShape {                     // (mem, xy, kind, zs, cap: gvom_
 #define GVOM_VIEWPOINT_MAX_BEAMS ((int64_t)1 << 22)
 #define GVOM_VIEWPOINT_DEFAULT_MB 256
 #define GVOM_VIEWPOINT_MAX_MB 4096
-// fr_work's counters (uint32): [r] tiles that flagged any in round r of the batch, [16 + r] tiles that ran, [32] frontier cells,
-// [33] kept clusters, [34] clusters dropped by min_cells, [35] frontier cells in kept clusters
-#define FR_CNT_RELAXED 16
+// the frontier labelling's counters (uint32) behind the rounds': [32] frontier cells, [33] kept clusters, [34] clusters dropped by
+// min_cells, [35] frontier cells in kept clusters
 #define FR_CNT_CELLS 32
 #define FR_CNT_KEPT 33
 // DevSet::exports / rel* / orphan: a DLPack deleter runs on whatever thread frees the consumer's tensor, without the handle
 extern std::mutex g_set_mu;                               // (gvom_sets.hip)
+
+// what a call that WAITS keeps on the handle: the work buffer its rounds run on (gvom_solvework.h has the layouts), the pinned copy of
+// the counters the host loop reads, its tuning (gvom_set_tuning "<call>_inner" / "<call>_batch"; 0: the defaults) and the rounds and
+// tile relaxations of the last call (gvom_get_tuning "<call>_rounds" / "<call>_tiles").  The atlas forms run under the tuning of the
+// window's calls: their own is never set
+struct SolveWork {
+    Buf work;
+    uint32_t *pin = nullptr;
+    int tune_inner = 0, tune_batch = 0;
+    int last_rounds = 0, last_tiles = 0;
+};
 }  // namespace gvom_host
 
 using namespace gvom_host;
@@ -319,16 +329,13 @@ struct gvom_handle {
     // buffer and its product sets: gvom_get_tuning "raycast_allocations")
     Buf rq_stage;
     int rq_allocs = 0;
-    // COST-TO-GO FIELDS (gvom_cost_to_go): ctg_work = 256 bytes of counters (CTG_CNT_* above), the two halves of the tiles' activity
-    // flags, then the staged goals (65536 x 2 int32); ctg_stage = the staging copy of a caller's host cost map; ctg_clr = what
-    // gvom_launch_clearance needs for the inflation of the map-set route (its row scratch, a distance map nobody reads, d2).  Each
-    // is allocated by the first call that needs it; ctg_allocs counts those and the entry point's product sets (gvom_get_tuning
-    // "cost_to_go_allocations").  ctg_pin: the pinned copy of the counters the host loop reads.
-    Buf ctg_work, ctg_stage, ctg_clr;
-    uint32_t *ctg_pin = nullptr;
+    // COST-TO-GO FIELDS (gvom_cost_to_go): ctg.work = goal_work() with goals of 2 int32; ctg_stage = the staging copy of a caller's
+    // host cost map; ctg_clr = what gvom_launch_clearance needs for the inflation of the map-set route (its row scratch, a distance
+    // map nobody reads, d2).  Each is allocated by the first call that needs it; ctg_allocs counts those and the entry point's product
+    // sets (gvom_get_tuning "cost_to_go_allocations")
+    SolveWork ctg;
+    Buf ctg_stage, ctg_clr;
     int ctg_allocs = 0;
-    int tune_ctg_inner = 0, tune_ctg_batch = 0;         // gvom_set_tuning "cost_to_go_inner" / "cost_to_go_batch" (0: the defaults)
-    int ctg_last_tiles = 0;                             // tile relaxations of the last call (gvom_get_tuning "cost_to_go_tiles")
     // ROLLOUT SCORING (gvom_footprint_set / gvom_score_rollouts): fp_tab = the footprint table in device memory -- start[H + 1]
     // int32, then at fp_offs_at bytes (a multiple of 256) the offsets, 4 bytes each (dx low, dy high) -- and ro_stage = the staging
     // copy of a caller's host maps and poses; ro_allocs counts the device allocations gvom_score_rollouts has made on this handle
@@ -352,15 +359,12 @@ struct gvom_handle {
     // host cloud and transforms; al_allocs counts the device allocations the entry point has made on this handle (the two and its product sets)
     Buf al_grid, al_stage;
     int al_allocs = 0;
-    // FRONTIER EXTRACTION (gvom_frontiers): fr_work = 256 bytes of counters (FR_CNT_* above), the two halves of the tiles' activity
-    // flags, the block counts of the ranking, then the label and the count / rank arrays, int32 per cell each; fr_stage = the staging
-    // copy of a caller's host maps.  Each is allocated by the first call that needs it; fr_allocs counts those and the entry point's
-    // product sets (gvom_get_tuning "frontier_allocations").  fr_pin: the pinned copy of the counters the host loop reads.
-    Buf fr_work, fr_stage;
-    uint32_t *fr_pin = nullptr;
+    // FRONTIER EXTRACTION (gvom_frontiers): fr.work = fr_offsets() at the window's side; fr_stage = the staging copy of a caller's host
+    // maps.  Each is allocated by the first call that needs it; fr_allocs counts those and the entry point's product sets
+    // (gvom_get_tuning "frontier_allocations")
+    SolveWork fr;
+    Buf fr_stage;
     int fr_allocs = 0;
-    int tune_fr_inner = 0, tune_fr_batch = 0;           // gvom_set_tuning "frontier_inner" / "frontier_batch" (0: the defaults)
-    int fr_last_rounds = 0, fr_last_tiles = 0;          // of the last call (gvom_get_tuning "frontier_rounds" / "frontier_tiles")
     // VIEWPOINT SCORING (gvom_score_viewpoints): vp_bitmaps = one bitmap of the window's voxels per viewpoint of a batch, cleared on the
     // stream before every batch; at most tune_vp_mb megabytes ("viewpoint_bitmap_mb"; a bitmap that alone is larger makes batches of
     // one).  vp_stage = the staging copy of a caller's host poses.  Each is allocated by the first call that needs it; vp_allocs counts
@@ -372,17 +376,14 @@ struct gvom_handle {
     int vp_last_batch = 0;
     // POSE FIELDS (gvom_primitives_set / gvom_pose_field): pf_tab = the primitive table in device memory -- start[H + 1] int32, then at
     // pf_prims_at bytes (a multiple of 256) the primitives, 8 bytes each (int16 dx, dy, h_to, w) --, pf_H its headings (0: none set) and
-    // pf_R its largest |dx|, |dy|: the halo of a tile.  pf_work = 256 bytes of counters (CTG_CNT_* above), the two halves of the tiles'
-    // activity flags, the staged goals (65536 x 3 int32), then the uint16 cost map converted from a caller's int32 one; pf_stage = the
-    // staging copy of a caller's host cost map.  Each is allocated by the first call that needs it; pf_allocs counts those and the entry
-    // point's product sets (gvom_get_tuning "pose_field_allocations").  pf_pin: the pinned copy of the counters the host loop reads.
-    Buf pf_tab, pf_work, pf_stage;
+    // pf_R its largest |dx|, |dy|: the halo of a tile.  pf.work = goal_work() with goals of 3 int32 and, as its tail,
+    // the uint16 cost map converted from a caller's int32 one; pf_stage = the staging copy of a caller's host cost map.  Each is allocated
+    // by the first call that needs it; pf_allocs counts those and the entry point's product sets (gvom_get_tuning "pose_field_allocations")
+    SolveWork pf;
+    Buf pf_tab, pf_stage;
     size_t pf_prims_at = 0;
     int pf_H = 0, pf_R = 0;
-    uint32_t *pf_pin = nullptr;
     int pf_allocs = 0;
-    int tune_pf_inner = 0, tune_pf_batch = 0;           // gvom_set_tuning "pose_field_inner" / "pose_field_batch" (0: the defaults)
-    int pf_last_rounds = 0, pf_last_tiles = 0;          // of the last call (gvom_get_tuning "pose_field_rounds" / "pose_field_tiles")
     // MAP ATLAS (gvom_atlas_*): atl_mem = the ten planes of atl_A x atl_A cells (gvom_internal.h "map atlas"; atl_A == 0: none
     // configured), atl_cnt = 256 bytes of int32 counters in device memory and atl_pin their pinned copy for gvom_atlas_counts,
     // atl_stage = the staging copy of a caller's nine host maps.  atl_E = the extent's origin in world cells, atl_seq = integrates so far,
@@ -396,22 +397,17 @@ struct gvom_handle {
     int32_t atl_seq = 0;
     int atl_allocs = 0;
     // ATLAS FIELDS (gvom_atlas_cost_to_go / gvom_atlas_field_window): the solver's buffers at the atlas's side A, apart from the
-    // window-sized ones of gvom_cost_to_go -- af_work = 256 bytes of counters (CTG_CNT_* above), the two halves of the tiles' activity
-    // flags, then the staged goals (65536 x 2 int32, relative to the extent); af_clr = the inflation's row distances (A*A uint16), a
-    // distance map nobody reads and d2 (A*A x 4 bytes each), allocated by the first call that inflates.  af_allocs counts those and the
-    // two entry points' product sets (gvom_get_tuning "atlas_field_allocations").  af_pin: the pinned copy of the counters.
-    Buf af_work, af_clr;
-    uint32_t *af_pin = nullptr;
+    // window-sized ones of gvom_cost_to_go -- af.work = goal_work() at that side (the goals relative to the extent); af_clr = the
+    // inflation's row distances (A*A uint16), a distance map nobody reads and d2 (A*A x 4 bytes each), allocated by the first call that
+    // inflates.  af_allocs counts those and the two entry points' product sets (gvom_get_tuning "atlas_field_allocations")
+    SolveWork af;
+    Buf af_clr;
     int af_allocs = 0;
-    int af_last_tiles = 0;                              // tile relaxations of the last gvom_atlas_cost_to_go (gvom_get_tuning "atlas_field_tiles")
-    // ATLAS FRONTIERS (gvom_atlas_frontiers): afr_work = gvom_frontiers' work buffer (fr_work_layout) at the side of the FIELD the call
-    // was given, 8 bytes per cell plus flags and counters -- apart from the window-sized fr_work, which an atlas call never touches.
-    // afr_allocs counts it and the entry point's product sets (gvom_get_tuning "atlas_frontier_allocations").  afr_pin: the pinned
-    // copy of the counters the host loop reads.
-    Buf afr_work;
-    uint32_t *afr_pin = nullptr;
+    // ATLAS FRONTIERS (gvom_atlas_frontiers): afr.work = gvom_frontiers' work buffer (fr_offsets) at the side of the FIELD the call was
+    // given, 8 bytes per cell plus flags and counters -- apart from the window-sized fr.work, which an atlas call never touches.
+    // afr_allocs counts it and the entry point's product sets (gvom_get_tuning "atlas_frontier_allocations")
+    SolveWork afr;
     int afr_allocs = 0;
-    int afr_last_rounds = 0, afr_last_tiles = 0;        // of the last call (gvom_get_tuning "atlas_frontier_rounds" / "atlas_frontier_tiles")
 };
 
 namespace gvom_host {
@@ -489,24 +485,76 @@ int map_set_acquire(gvom_handle *h, const char *fn, DevSet **set);
 void occ_params(const gvom_handle *h, const Fused &F, OccParams &P);
 void cloud_params(const gvom_handle *h, const Fused &F, Map2dParams &P);
 hipError_t launch_height_cloud(gvom_handle *h, const Fused &F, float *out7, float *out3);
-// the parts of gvom_cost_to_go that gvom_atlas_cost_to_go shares.  ctg_cost_params: the caller's cost parameters and flags checked
-// and turned into what the launchers take (GVOM_ERR_INVALID, in fn's name, for what the header says).  ctg_solve: seed, the batches
-// of rounds with the host's look at the counters between them, and the directions, on a map of n x n cells whose uint16 costs are in
-// c16 (or come from cost32); cnt / fl / gdev are the counters, the flags and the staged goals of a work buffer laid out for n, pin
-// the pinned copy of the counters.  It waits; the caller publishes the product and fetches the final counters.
-struct CtgSolve { bool converged = false; int64_t rounds = 0, tiles = 0; };
+// ---- what the product calls and the atlas calls (gvom_atlas_calls.hip) share; defined in gvom_product_calls.hip unless inline ----
+// part `part` of a set as a launcher takes it.  The part numbers are literals at the call sites: one the set's kind does not have is
+// a mistake in the calling unit, and stops the process instead of handing a kernel a null pointer
+template <class T> inline T *part_ptr(const DevSet *s, int part)
+{
+    SetPart d;
+    if (!set_part(s, part, &d)) { fprintf(stderr, "gvom: a device set of kind %d has no part %d\n", s->kind, part); abort(); }
+    return (T *)d.ptr;
+}
+
+// grows a buffer of the handle to at least `bytes`; an allocation counts in `allocs`
+inline int stage_buf(gvom_handle *h, Buf &b, size_t bytes, int &allocs)
+{
+    if (b.bytes >= bytes) return GVOM_OK;
+    const int rc = ensure(h, b, bytes);
+    allocs += rc ? 0 : 1;
+    return rc;
+}
+
+// HOST INPUTS: the present ones of `n` parts (src null: absent) copied into `b`, grown as stage_buf does, each but the last listed
+// padded to 256 bytes; dev[i] = where part i went (null: absent).  sync: the call returns with the copies done (the caller's arrays
+// are free again); otherwise they are in flight on the handle's stream, as a call that waits anyway leaves them
+struct HostPart { const void *src; size_t bytes; };
+int stage_host(gvom_handle *h, Buf &b, int &allocs, const HostPart *parts, int n, bool sync, const void **dev);
+
+// THE ARGUMENT CHECKS.  refuse: h->err = fn + ": " + what, and the code.  The others are what more than one entry point checks: each
+// refuses in fn's name and returns the code, or GVOM_OK.  A caller keeps the order its checks always had: these fold only runs of
+// checks that stand together in every caller
+int refuse(gvom_handle *h, const char *fn, const std::string &what, int code = GVOM_ERR_INVALID);
+int check_one_source(gvom_handle *h, const char *fn, bool id, bool also, bool missing, const char *by_id, const char *both, const char *other);   // "give <by_id> or <both>, not both" / "give <by_id> or <other>"
+int check_goals(gvom_handle *h, const char *fn, const void *goals, int64_t n_goals, int32_t max_cost, int32_t max_rounds);
+int check_rollout_shape(gvom_handle *h, const char *fn, int64_t K, int64_t T, const int64_t origin_cells[2]);
+int check_side(gvom_handle *h, const char *fn);                            // windows of more than 4096 cells a side
+int check_clusters(gvom_handle *h, const char *fn, int32_t min_cells, int32_t max_clusters);
+int check_host_cost(gvom_handle *h, const char *fn, const int32_t *cost, size_t n2);
+int cost_field_of(gvom_handle *h, const char *fn, int64_t id, DevSet **f);
+int atlas_field_of(gvom_handle *h, const char *fn, int64_t id, DevSet **f);
+int map_set_of(gvom_handle *h, int64_t id, DevSet **m);                    // (its text names no function)
+// ctg_cost_params: the caller's cost parameters and flags checked and turned into what the launchers take
 int ctg_cost_params(gvom_handle *h, const char *fn, const gvom_ctg_params *params, int flags, CtgCostParams *C);
-int ctg_solve(gvom_handle *h, int n, const int32_t *cost32, uint16_t *c16, int32_t *D, uint8_t *dir, uint32_t *cnt, uint32_t *fl,
-              const int32_t *gdev, int n_goals, int32_t max_cost, int32_t max_rounds, uint32_t *pin, CtgSolve *out);
-// the part of gvom_frontiers that gvom_atlas_frontiers shares: everything behind the marking kernel.  fr_work_bytes / fr_work_layout: the
-// size and the parts of a work buffer for n x n cells -- 256 bytes of counters (FR_CNT_* above), the two halves of the tiles' activity
-// flags, the block counts of the ranking, then the label and the count / rank arrays; the caller clears the first clear_bytes on the
-// stream and runs its marking kernel.  frontier_solve: the rows' initialisation, the batches of relaxation rounds with the host's look
-// at the counters between them (pin: their pinned copy), the finish, the set's publication and info; errors are in fn's name.  It waits.
+
+// THE CALLS THAT WAIT.  solve_rounds is the one loop: batches of at most `batch` relaxation rounds up to `limit` rounds in all, round
+// k enqueued by enqueue(k, flags in, flags out, &any[r], &ran[r]) -- a hipError_t -- on the two halves of fl, the batch's counters
+// back through pin, and the first round that flagged no tile ends it (solve_look).  No allocation, nothing but the handle's stream.
+struct SolveRounds { bool converged = false; int64_t rounds = 0, tiles = 0; };
+template <class Enqueue> int solve_rounds(gvom_handle *h, uint32_t *cnt, uint32_t *fl, uint32_t *pin, int ntiles, int batch, int64_t limit,
+                                          Enqueue enqueue, SolveRounds *out);
+int solve_work_reserve(gvom_handle *h, SolveWork &w, size_t bytes, int &allocs);     // a work buffer of at least `bytes`, and the pinned counters
+// the goal solvers (gvom_cost_to_go, gvom_atlas_cost_to_go, gvom_pose_field): the parts of their work buffer, the goals sent up and
+// the counters cleared on the stream, and -- behind the solve -- the epilogue: the set published, the counters fetched, a solve that
+// did not settle under max_rounds == 0 retracted in fn's name, info and w.last_* filled
+struct GoalWorkPtrs { uint32_t *cnt, *fl; int32_t *goals; char *tail; };
+inline GoalWorkPtrs goal_work_ptrs(const SolveWork &w, const GoalWork &o)
+{
+    char *p = (char *)w.work.p;
+    return GoalWorkPtrs{(uint32_t *)p, (uint32_t *)(p + o.flags), (int32_t *)(p + o.goals), p + o.tail};
+}
+int goal_work_start(gvom_handle *h, const GoalWorkPtrs &G, const void *goals, size_t bytes);
+int goal_solve_finish(gvom_handle *h, const char *fn, SolveWork &w, DevSet *set, int64_t *product_id, const SolveRounds &S, int32_t max_rounds,
+                      int64_t info[4]);
+// ctg_solve: seed, the rounds and the directions on a map of n x n cells whose uint16 costs are in c16 (or come from cost32), on a
+// work buffer laid out for n; the rounds run under gvom_cost_to_go's tuning.  It waits; the caller finishes with goal_solve_finish
+int ctg_solve(gvom_handle *h, SolveWork &w, const GoalWorkPtrs &G, int n, const int32_t *cost32, uint16_t *c16, int32_t *D, uint8_t *dir,
+              int n_goals, int32_t max_cost, int32_t max_rounds, SolveRounds *out);
+// the part of gvom_frontiers that gvom_atlas_frontiers shares: everything around the marking kernel.  frontier_work: the work buffer
+// for n x n cells (fr_offsets) reserved in w, and its parts; the caller clears the first clear_bytes -- counters and flags -- on the
+// stream, waits for its set's releases and marks.  frontier_solve: the rows' initialisation, the rounds under gvom_frontiers' tuning,
+// the finish, the set's publication, info and w.last_*; errors are in fn's name.  It waits.
 struct FrWork { uint32_t *cnt, *fl, *bc, *L, *count; size_t clear_bytes; };
-struct FrSolve { int64_t rounds = 0, tiles = 0; };
-size_t fr_work_bytes(int n);
-FrWork fr_work_layout(int n, char *w);
-int frontier_solve(gvom_handle *h, const char *fn, int n, const int32_t *D, const FrWork &W, uint32_t *pin, int32_t min_cells,
-                   int32_t max_clusters, DevSet *set, int64_t *product_id, int64_t info[4], FrSolve *out);
+int frontier_work(gvom_handle *h, SolveWork &w, int n, int &allocs, FrWork *W);
+int frontier_solve(gvom_handle *h, const char *fn, SolveWork &w, int n, const int32_t *D, const FrWork &W, int32_t min_cells,
+                   int32_t max_clusters, DevSet *set, int64_t *product_id, int64_t info[4]);
 }  // namespace gvom_host

@@ -1,7 +1,12 @@
 // gvom_product_calls.hip -- the calls that MAKE a device product: gvom_device_product (occupancy grid, voxel cloud, the two height
-// clouds), gvom_clearance, gvom_raycast, gvom_cost_to_go, gvom_score_rollouts (with gvom_footprint_set, which sets its table), gvom_score_attitude (with gvom_chassis_set), gvom_score_alignments, gvom_frontiers, gvom_score_viewpoints and gvom_pose_field (with gvom_primitives_set), and the frame builders they and the debug reads (gvom_debug.hip) give
-// the kernels.  Every call takes its set through product_acquire and hands it out through product_publish (gvom_sets.hip); what is
-// left in each body is what is particular to that product: its argument checks, its staging and its launches.
+// clouds), gvom_clearance, gvom_raycast, gvom_cost_to_go, gvom_score_rollouts (with gvom_footprint_set, which sets its table),
+// gvom_score_attitude (with gvom_chassis_set), gvom_score_alignments, gvom_frontiers, gvom_score_viewpoints and gvom_pose_field (with
+// gvom_primitives_set), and the frame builders they and the debug reads (gvom_debug.hip) give the kernels.  Every call takes its set
+// through product_acquire and hands it out through product_publish (gvom_sets.hip).  What several calls do alike stands once, in
+// front of the entry points, and serves the atlas calls (gvom_atlas_calls.hip) too: the argument checks (check_*, *_of), the staging
+// of host inputs (stage_host), the frames (metric_frame, rollout_frame) and, for the calls that wait, the round driver (solve_rounds;
+// its arithmetic and the work buffers' layouts are gvom_solvework.h's), the work buffers and the epilogue (goal_solve_finish).  What
+// is left in each body is what is particular to that product: its own checks, in the order they always had, and its launches.
 #include "gvom_host.h"
 
 namespace gvom_host {
@@ -23,18 +28,25 @@ void cloud_params(const gvom_handle *h, const Fused &F, Map2dParams &P)
     P.xy_res = h->prm.xy_resolution; P.z_res = h->prm.z_resolution;
 }
 
+// the metric frame of the fused map F for the kernels that turn world coordinates into voxels (ScanParams, AlignParams): the
+// resolutions, their reciprocals, whether the verified reciprocal form may be used, the window's corner
+template <class P> static void metric_frame(const gvom_handle *h, const Fused &F, P &p)
+{
+    p.xy_res = h->prm.xy_resolution; p.z_res = h->prm.z_resolution;
+    p.drcp[0] = 1.0 / h->prm.xy_resolution; p.drcp[1] = 1.0 / h->prm.z_resolution;
+    p.fastdiv = h->tune_fastdiv == 0 ? 0 : h->fastdiv_ok;
+    for (int k = 0; k < 3; ++k) p.origin[k] = (double)F.origin[k];
+}
+
 // the frame of the fused map F as k_raycast reads it (gvom_launch_raycast names the fields), and what of a query depends on it
 static void raycast_params(const gvom_handle *h, const Fused &F, ScanParams &P, RayQuery &Q)
 {
     const gvom_params &p = h->prm;
     fused_frame(h, F, P, P.sy_lo, P.sy_hi);
-    P.xy_res = p.xy_resolution; P.z_res = p.z_resolution;
-    P.drcp[0] = 1.0 / p.xy_resolution; P.drcp[1] = 1.0 / p.z_resolution;
-    P.fastdiv = h->tune_fastdiv == 0 ? 0 : h->fastdiv_ok;
+    metric_frame(h, F, P);
     P.f32_sqrt = h->f32_sqrt ? 1 : 0;
     bool far = false;
     for (int k = 0; k < 3; ++k) {
-        P.origin[k] = (double)F.origin[k];
         far = far || F.origin[k] <= -((int64_t)1 << 24) || F.origin[k] >= ((int64_t)1 << 24);
     }
     Q.lit = (far || p.z_size > p.xy_size) ? 1 : 0;        // (the integer window test assumes z_size <= xy_size and a near origin)
@@ -49,6 +61,94 @@ hipError_t launch_height_cloud(gvom_handle *h, const Fused &F, float *out7, floa
     return gvom_launch_debug_height(h->stream, h->prm.xy_size, om[0], om[1], org, h->prm.xy_resolution, h->prm.z_resolution,
                                     h->height, h->hs, h->rough, h->slope_x, h->slope_y, out7, h->guessed, out3);
 }
+
+// what k_rollouts, and k_attitude in its P.R, take of a call of K trajectories of T poses
+static void rollout_frame(const gvom_handle *h, int64_t K, int64_t T, const int64_t origin_cells[2], RolloutParams &R)
+{
+    memset(&R, 0, sizeof R);
+    R.xy = h->prm.xy_size; R.H = h->fp_H; R.T = (int)T; R.K = K;
+    R.s = (float)((double)h->fp_H / 6.283185307179586476925286766559);
+    R.ox = origin_cells[0]; R.oy = origin_cells[1];
+    R.res = h->prm.xy_resolution;
+}
+
+// ---- the argument checks more than one entry point makes (gvom_host.h) ----------------------------------------------------------------
+int refuse(gvom_handle *h, const char *fn, const std::string &what, int code) { h->err = std::string(fn) + ": " + what; return code; }
+
+int check_one_source(gvom_handle *h, const char *fn, bool id, bool also, bool missing, const char *by_id, const char *both, const char *other)
+{
+    if (id && also) return refuse(h, fn, std::string("give ") + by_id + " or " + both + ", not both");
+    if (!id && missing) return refuse(h, fn, std::string("give ") + by_id + " or " + other);
+    return GVOM_OK;
+}
+
+int check_goals(gvom_handle *h, const char *fn, const void *goals, int64_t n_goals, int32_t max_cost, int32_t max_rounds)
+{
+    if (!goals || n_goals < 1 || n_goals > GVOM_CTG_MAX_GOALS) return refuse(h, fn, "between 1 and 65536 goals");
+    if (max_cost < 0 || max_cost > GVOM_CTG_MAX_COST) return refuse(h, fn, "max_cost outside 0 .. 2^30");
+    if (max_rounds < 0) return refuse(h, fn, "max_rounds must not be negative");
+    return GVOM_OK;
+}
+
+int check_rollout_shape(gvom_handle *h, const char *fn, int64_t K, int64_t T, const int64_t origin_cells[2])
+{
+    if (T < 1 || T > GVOM_ROLLOUT_MAX_T) return refuse(h, fn, "T outside 1 .. 4096");
+    if (K < 1) return refuse(h, fn, "K must be at least 1");
+    if (K > GVOM_ROLLOUT_MAX_POSES / T) return refuse(h, fn, "more than 2^26 poses in one call", GVOM_ERR_CAPACITY);
+    for (int k = 0; k < 2; ++k)
+        if (origin_cells[k] < -((int64_t)1 << 40) || origin_cells[k] > ((int64_t)1 << 40)) return refuse(h, fn, "an origin beyond 2^40 cells");
+    return GVOM_OK;
+}
+
+int check_side(gvom_handle *h, const char *fn) { return h->prm.xy_size > GVOM_CLEARANCE_MAX_XY ? refuse(h, fn, "maps of more than 4096 cells a side are not supported", GVOM_ERR_CAPACITY) : GVOM_OK; }
+
+int check_clusters(gvom_handle *h, const char *fn, int32_t min_cells, int32_t max_clusters)
+{
+    if (min_cells < 1) return refuse(h, fn, "min_cells must be at least 1");
+    if (max_clusters < 1 || max_clusters > GVOM_FRONTIER_MAX_CLUSTERS) return refuse(h, fn, "max_clusters outside 1 .. 2^20");
+    return GVOM_OK;
+}
+
+int check_host_cost(gvom_handle *h, const char *fn, const int32_t *cost, size_t n2)
+{
+    for (size_t k = 0; k < n2; ++k)
+        if (cost[k] < 0 || cost[k] > 65535) return refuse(h, fn, "a host cost map holds a value outside 0 .. 65535");
+    return GVOM_OK;
+}
+
+static int product_of_kind(gvom_handle *h, const char *fn, int64_t id, int kind, const char *what, DevSet **f)
+{
+    *f = find_set(h->psets, id);
+    return *f && (*f)->kind == kind ? GVOM_OK : refuse(h, fn, what);
+}
+
+int cost_field_of(gvom_handle *h, const char *fn, int64_t id, DevSet **f) { return product_of_kind(h, fn, id, GVOM_PRODUCT_COSTFIELD, "unknown or stale cost field id", f); }
+int atlas_field_of(gvom_handle *h, const char *fn, int64_t id, DevSet **f) { return product_of_kind(h, fn, id, GVOM_PRODUCT_ATLAS_FIELD, "unknown or stale atlas field id", f); }
+
+int map_set_of(gvom_handle *h, int64_t id, DevSet **m)
+{
+    if ((*m = find_set(h->dsets, id))) return GVOM_OK;
+    h->err = "unknown or stale device map set id";
+    return GVOM_ERR_INVALID;
+}
+
+// ---- host inputs (gvom_host.h) -----------------------------------------------------------------------------------------------------------
+int stage_host(gvom_handle *h, Buf &b, int &allocs, const HostPart *parts, int n, bool sync, const void **dev)
+{
+    size_t at[4], need = 0;
+    for (int i = 0; i < n; ++i) {
+        at[i] = need;
+        if (parts[i].src) need += i + 1 < n ? align256(parts[i].bytes) : parts[i].bytes;
+    }
+    if (const int rc = stage_buf(h, b, need, allocs)) return rc;
+    for (int i = 0; i < n; ++i) {
+        dev[i] = parts[i].src ? (char *)b.p + at[i] : nullptr;
+        if (parts[i].src) HIPCHK(h, hipMemcpyAsync((char *)b.p + at[i], parts[i].src, parts[i].bytes, hipMemcpyHostToDevice, h->stream));
+    }
+    if (sync) HIPCHK(h, hipStreamSynchronize(h->stream));
+    return GVOM_OK;
+}
+
 int ctg_cost_params(gvom_handle *h, const char *fn, const gvom_ctg_params *params, int flags, CtgCostParams *C)
 {
     const gvom_ctg_params &p = *params;
@@ -65,129 +165,112 @@ int ctg_cost_params(gvom_handle *h, const char *fn, const gvom_ctg_params *param
     return GVOM_OK;
 }
 
-int ctg_solve(gvom_handle *h, int n, const int32_t *cost32, uint16_t *c16, int32_t *D, uint8_t *dir, uint32_t *cnt, uint32_t *fl,
-              const int32_t *gdev, int n_goals, int32_t max_cost, int32_t max_rounds, uint32_t *pin, CtgSolve *out)
+// ---- the calls that wait (gvom_host.h) ---------------------------------------------------------------------------------------------------
+template <class Enqueue> int solve_rounds(gvom_handle *h, uint32_t *cnt, uint32_t *fl, uint32_t *pin, int ntiles, int batch, int64_t limit,
+                                          Enqueue enqueue, SolveRounds *out)
 {
-    const int nt = gvom_ctg_tiles(n), ntiles = nt * nt;
-    HIPCHK(h, gvom_launch_ctg_seed(h->stream, n, cost32, c16, D, fl, gdev, n_goals, cnt + CTG_CNT_SEEDED));
-    const int32_t cap = max_cost == 0 ? GVOM_CTG_MAX_COST : max_cost;
-    const int inner = h->tune_ctg_inner > 0 ? h->tune_ctg_inner : 256;
-    const int batch = h->tune_ctg_batch > 0 ? h->tune_ctg_batch : 8;
-    // by induction over the tile crossings of a shortest path the solve ends after at most (crossings + 1) rounds of tiles that
-    // reach their fixed point; the limit below is beyond anything n <= 4096 can need and only keeps this loop finite
-    const int64_t limit = max_rounds > 0 ? (int64_t)max_rounds : (int64_t)1 << 22;
     int64_t rounds = 0, tiles = 0;
     bool converged = false;
     while (!converged && rounds < limit) {
-        const int nb = (int)std::min<int64_t>(batch, limit - rounds);
-        if (rounds) HIPCHK(h, hipMemsetAsync(cnt, 0, 2 * GVOM_CTG_MAX_BATCH * 4, h->stream));
+        const int nb = solve_batch_len(batch, limit, rounds);
+        if (rounds) HIPCHK(h, hipMemsetAsync(cnt, 0, SOLVE_CNT_BATCH_BYTES, h->stream));
         for (int r = 0; r < nb; ++r) {
             const int64_t k = rounds + r;
-            HIPCHK(h, gvom_launch_ctg_relax(h->stream, n, c16, D, fl + (k & 1) * ntiles, fl + ((k + 1) & 1) * ntiles, cnt + r,
-                                            cnt + CTG_CNT_RELAXED + r, cap, inner));
+            HIPCHK(h, enqueue(k, fl + (k & 1) * ntiles, fl + ((k + 1) & 1) * ntiles, cnt + r, cnt + SOLVE_CNT_RAN + r));
         }
-        HIPCHK(h, hipMemcpyAsync(pin, cnt, 2 * GVOM_CTG_MAX_BATCH * 4, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(pin, cnt, SOLVE_CNT_BATCH_BYTES, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
-        int ran = nb;
-        for (int r = 0; r < nb; ++r) {
-            tiles += pin[CTG_CNT_RELAXED + r];
-            if (pin[r] == 0) { converged = true; ran = r + 1; break; }
-        }
-        rounds += ran;
+        const SolveLook look = solve_look(pin, nb);
+        converged = look.converged; rounds += look.ran; tiles += look.tiles;
     }
-    HIPCHK(h, gvom_launch_ctg_dirs(h->stream, n, c16, D, dir, cnt + CTG_CNT_REACHED));
     out->converged = converged; out->rounds = rounds; out->tiles = tiles;
     return GVOM_OK;
 }
 
-// ---- what gvom_frontiers and gvom_atlas_frontiers (gvom_atlas_calls.hip) share ----------------------------------------------------------
-namespace {
-struct FrOffsets { size_t flags, bc, L, count, end; };
-FrOffsets fr_offsets(int n)
+int solve_work_reserve(gvom_handle *h, SolveWork &w, size_t bytes, int &allocs)
 {
-    const size_t n2 = (size_t)n * n;
-    const int nt = gvom_frontier_tiles(n), nb = gvom_frontier_blocks(n);
-    FrOffsets o;
-    o.flags = 256; o.bc = o.flags + align256((size_t)2 * nt * nt * 4); o.L = o.bc + align256((size_t)2 * nb * 4);
-    o.count = o.L + align256(n2 * 4); o.end = o.count + n2 * 4;
-    return o;
-}
-}  // namespace
-
-size_t fr_work_bytes(int n) { return fr_offsets(n).end; }
-
-FrWork fr_work_layout(int n, char *w)
-{
-    const FrOffsets o = fr_offsets(n);
-    return FrWork{(uint32_t *)w, (uint32_t *)(w + o.flags), (uint32_t *)(w + o.bc), (uint32_t *)(w + o.L), (uint32_t *)(w + o.count), o.bc};
+    if (const int rc = stage_buf(h, w.work, bytes, allocs)) return rc;
+    if (!w.pin) HIPCHK(h, hipHostMalloc((void **)&w.pin, 256, hipHostMallocDefault));
+    return GVOM_OK;
 }
 
-int frontier_solve(gvom_handle *h, const char *fn, int n, const int32_t *D, const FrWork &W, uint32_t *pin, int32_t min_cells,
-                   int32_t max_clusters, DevSet *set, int64_t *product_id, int64_t info[4], FrSolve *out)
+int goal_work_start(gvom_handle *h, const GoalWorkPtrs &G, const void *goals, size_t bytes)
 {
-    const size_t n2 = (size_t)n * n;
-    const int nt = gvom_frontier_tiles(n), ntiles = nt * nt;
-    uint32_t *const cnt = W.cnt, *const fl = W.fl;
-    SetPart d;
-    set_part(set, 0, &d); int32_t *rows = (int32_t *)d.ptr;
-    set_part(set, 1, &d); int64_t *sums = (int64_t *)d.ptr;
-    set_part(set, 2, &d); int32_t *cmap = (int32_t *)d.ptr;
-    set_part(set, 3, &d); int32_t *counts = (int32_t *)d.ptr;
+    HIPCHK(h, hipMemcpyAsync(G.goals, goals, bytes, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemsetAsync(G.cnt, 0, 256, h->stream));
+    return GVOM_OK;
+}
+
+int goal_solve_finish(gvom_handle *h, const char *fn, SolveWork &w, DevSet *set, int64_t *product_id, const SolveRounds &S, int32_t max_rounds,
+                      int64_t info[4])
+{
+    if (const int rc = product_publish(h, set, product_id)) return rc;     // (`ready` goes in front of the counters' way back)
+    HIPCHK(h, hipMemcpyAsync(w.pin, w.work.p, 256, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (!S.converged && max_rounds == 0) { set->id = *product_id = -1; return refuse(h, fn, "the field did not settle", GVOM_ERR_HIP); }   // (nobody gets it)
+    w.last_rounds = (int)std::min<int64_t>(S.rounds, INT32_MAX);
+    w.last_tiles = (int)std::min<int64_t>(S.tiles, INT32_MAX);
+    if (info) { info[0] = S.converged ? 1 : 0; info[1] = S.rounds; info[2] = w.pin[CTG_CNT_REACHED]; info[3] = w.pin[CTG_CNT_SEEDED]; }
+    return GVOM_OK;
+}
+
+int ctg_solve(gvom_handle *h, SolveWork &w, const GoalWorkPtrs &G, int n, const int32_t *cost32, uint16_t *c16, int32_t *D, uint8_t *dir,
+              int n_goals, int32_t max_cost, int32_t max_rounds, SolveRounds *out)
+{
+    const int nt = gvom_ctg_tiles(n);
+    HIPCHK(h, gvom_launch_ctg_seed(h->stream, n, cost32, c16, D, G.fl, G.goals, n_goals, G.cnt + CTG_CNT_SEEDED));
+    const int32_t cap = max_cost == 0 ? GVOM_CTG_MAX_COST : max_cost;
+    const int inner = h->ctg.tune_inner > 0 ? h->ctg.tune_inner : 256;
+    const int batch = h->ctg.tune_batch > 0 ? h->ctg.tune_batch : 8;
+    // by induction over the tile crossings of a shortest path the solve ends after at most (crossings + 1) rounds of tiles that
+    // reach their fixed point; the limit below is beyond anything n <= 4096 can need and only keeps the loop finite
+    const int64_t limit = max_rounds > 0 ? (int64_t)max_rounds : (int64_t)1 << 22;
+    const int rc = solve_rounds(h, G.cnt, G.fl, w.pin, nt * nt, batch, limit, [&](int64_t, uint32_t *fin, uint32_t *fout, uint32_t *any, uint32_t *ran) {
+        return gvom_launch_ctg_relax(h->stream, n, c16, D, fin, fout, any, ran, cap, inner);
+    }, out);
+    if (rc) return rc;
+    HIPCHK(h, gvom_launch_ctg_dirs(h->stream, n, c16, D, dir, G.cnt + CTG_CNT_REACHED));
+    return GVOM_OK;
+}
+
+int frontier_work(gvom_handle *h, SolveWork &w, int n, int &allocs, FrWork *W)
+{
+    const FrOffsets o = fr_offsets(n, gvom_frontier_tiles(n), gvom_frontier_blocks(n));
+    if (const int rc = solve_work_reserve(h, w, o.end, allocs)) return rc;
+    char *p = (char *)w.work.p;
+    *W = FrWork{(uint32_t *)p, (uint32_t *)(p + o.flags), (uint32_t *)(p + o.bc), (uint32_t *)(p + o.L), (uint32_t *)(p + o.count), o.bc};
+    return GVOM_OK;
+}
+
+int frontier_solve(gvom_handle *h, const char *fn, SolveWork &w, int n, const int32_t *D, const FrWork &W, int32_t min_cells,
+                   int32_t max_clusters, DevSet *set, int64_t *product_id, int64_t info[4])
+{
+    const int nt = gvom_frontier_tiles(n);
+    uint32_t *const cnt = W.cnt;
+    int32_t *rows = part_ptr<int32_t>(set, 0), *cmap = part_ptr<int32_t>(set, 2), *counts = part_ptr<int32_t>(set, 3);
+    int64_t *sums = part_ptr<int64_t>(set, 1);
     HIPCHK(h, gvom_launch_frontier_rows(h->stream, 0, max_clusters, rows, sums, cnt + FR_CNT_KEPT, cnt + FR_CNT_CELLS, counts));
-    const int inner = h->tune_fr_inner > 0 ? h->tune_fr_inner : 256;
-    const int batch = h->tune_fr_batch > 0 ? h->tune_fr_batch : 8;
-    // labels only go down and there are n2 of them: a round that lowers none flags no tile, so fewer than n2 + 1 rounds lower one.
-    // The limit cannot be reached and only keeps this loop finite
-    const int64_t limit = (int64_t)n2 + 1;
-    int64_t rounds = 0, tiles = 0;
-    bool converged = false;
-    while (!converged && rounds < limit) {
-        const int nr = (int)std::min<int64_t>(batch, limit - rounds);
-        if (rounds) HIPCHK(h, hipMemsetAsync(cnt, 0, 2 * GVOM_CTG_MAX_BATCH * 4, h->stream));
-        for (int r = 0; r < nr; ++r) {
-            const int64_t k = rounds + r;
-            HIPCHK(h, gvom_launch_frontier_relax(h->stream, n, W.L, fl + (k & 1) * ntiles, fl + ((k + 1) & 1) * ntiles, cnt + r,
-                                                 cnt + FR_CNT_RELAXED + r, inner));
-        }
-        HIPCHK(h, hipMemcpyAsync(pin, cnt, 2 * GVOM_CTG_MAX_BATCH * 4, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        int ran = nr;
-        for (int r = 0; r < nr; ++r) {
-            tiles += pin[FR_CNT_RELAXED + r];
-            if (pin[r] == 0) { converged = true; ran = r + 1; break; }
-        }
-        rounds += ran;
-    }
-    if (!converged) { h->err = std::string(fn) + ": the labels did not settle"; return GVOM_ERR_HIP; }   // (the set keeps id -1: nobody gets it)
+    const int inner = h->fr.tune_inner > 0 ? h->fr.tune_inner : 256;
+    const int batch = h->fr.tune_batch > 0 ? h->fr.tune_batch : 8;
+    // labels only go down and there are n * n of them: a round that lowers none flags no tile, so fewer than n * n + 1 rounds lower
+    // one.  The limit cannot be reached and only keeps the loop finite
+    SolveRounds S;
+    int rc = solve_rounds(h, cnt, W.fl, w.pin, nt * nt, batch, (int64_t)n * n + 1, [&](int64_t, uint32_t *fin, uint32_t *fout, uint32_t *any, uint32_t *ran) {
+        return gvom_launch_frontier_relax(h->stream, n, W.L, fin, fout, any, ran, inner);
+    }, &S);
+    if (rc) return rc;
+    if (!S.converged) return refuse(h, fn, "the labels did not settle", GVOM_ERR_HIP);                  // (the set keeps id -1: nobody gets it)
     HIPCHK(h, gvom_launch_frontier_finish(h->stream, n, min_cells, max_clusters, D, W.L, W.count, W.bc, cnt + FR_CNT_KEPT, cnt + FR_CNT_CELLS, rows,
                                           sums, cmap, counts));
-    const int rc = product_publish(h, set, product_id);                    // (`ready` goes in front of the counters' way back)
-    if (rc) return rc;
-    HIPCHK(h, hipMemcpyAsync(pin, cnt, 256, hipMemcpyDeviceToHost, h->stream));
+    if ((rc = product_publish(h, set, product_id))) return rc;             // (`ready` goes in front of the counters' way back)
+    HIPCHK(h, hipMemcpyAsync(w.pin, cnt, 256, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    out->rounds = rounds; out->tiles = tiles;
-    if (info) { info[0] = rounds; info[1] = pin[FR_CNT_KEPT]; info[2] = pin[FR_CNT_CELLS]; info[3] = pin[FR_CNT_KEPT + 1]; }
+    w.last_rounds = (int)std::min<int64_t>(S.rounds, INT32_MAX);
+    w.last_tiles = (int)std::min<int64_t>(S.tiles, INT32_MAX);
+    if (info) { info[0] = S.rounds; info[1] = w.pin[FR_CNT_KEPT]; info[2] = w.pin[FR_CNT_CELLS]; info[3] = w.pin[FR_CNT_KEPT + 1]; }
     return GVOM_OK;
 }
 }  // namespace gvom_host
-
-// part `part` of a set as a launcher takes it.  The part numbers below are literals: one the set's kind does not have is a mistake
-// in this file, and stops the process instead of handing a kernel a null pointer
-template <class T> static T *part_ptr(const DevSet *s, int part)
-{
-    SetPart d;
-    if (!set_part(s, part, &d)) { fprintf(stderr, "gvom: a device set of kind %d has no part %d\n", s->kind, part); abort(); }
-    return (T *)d.ptr;
-}
-
-// grows a buffer of the handle to at least `bytes`; an allocation counts in `allocs`
-static int stage_buf(gvom_handle *h, Buf &b, size_t bytes, int &allocs)
-{
-    if (b.bytes >= bytes) return GVOM_OK;
-    const int rc = ensure(h, b, bytes);
-    if (!rc) ++allocs;
-    return rc;
-}
 
 extern "C" {
 // ---- device-resident 3-D products (gvom_device_product) ----------------------------------------------------------------------
@@ -201,16 +284,14 @@ VIS int gvom_device_product(gvom_t *h, int kind, int64_t max_rows, int64_t *prod
     if (!h || !product_id) return GVOM_ERR_INVALID;
     std::lock_guard<std::mutex> lk(h->mu);
     *product_id = -1;
-    static const char *const elsewhere[] = {"a clearance product is made by gvom_clearance", "a raycast product is made by gvom_raycast", "a cost field is made by gvom_cost_to_go"};
-    if (kind >= GVOM_PRODUCT_CLEARANCE && kind <= GVOM_PRODUCT_COSTFIELD) { h->err = std::string("gvom_device_product: ") + elsewhere[kind - GVOM_PRODUCT_CLEARANCE]; return GVOM_ERR_INVALID; }
-    if (kind == GVOM_PRODUCT_ROLLOUTS) { h->err = "gvom_device_product: rollouts are made by gvom_score_rollouts"; return GVOM_ERR_INVALID; }
-    if (kind == GVOM_PRODUCT_ATTITUDE) { h->err = "gvom_device_product: attitude scores are made by gvom_score_attitude"; return GVOM_ERR_INVALID; }
-    if (kind == GVOM_PRODUCT_ALIGNMENT) { h->err = "gvom_device_product: alignment scores are made by gvom_score_alignments"; return GVOM_ERR_INVALID; }
-    if (kind == GVOM_PRODUCT_FRONTIERS) { h->err = "gvom_device_product: frontiers are made by gvom_frontiers"; return GVOM_ERR_INVALID; }
-    if (kind == GVOM_PRODUCT_VIEWPOINTS) { h->err = "gvom_device_product: viewpoint scores are made by gvom_score_viewpoints"; return GVOM_ERR_INVALID; }
-    if (kind == GVOM_PRODUCT_POSEFIELD) { h->err = "gvom_device_product: pose fields are made by gvom_pose_field"; return GVOM_ERR_INVALID; }
-    if (kind < 1 || kind > GVOM_N_PRODUCT_KINDS) { h->err = "gvom_device_product: unknown product kind"; return GVOM_ERR_INVALID; }
-    if (h->sharded) { h->err = "gvom_device_product: sharded handles are not supported"; return GVOM_ERR_INVALID; }
+    static const char *const elsewhere[GVOM_PRODUCT_POSEFIELD + 1] = {                                  // by kind: who makes it instead
+        nullptr, nullptr, nullptr, nullptr, nullptr, "a clearance product is made by gvom_clearance", "a raycast product is made by gvom_raycast",
+        "a cost field is made by gvom_cost_to_go", nullptr, nullptr, "rollouts are made by gvom_score_rollouts", nullptr,
+        "alignment scores are made by gvom_score_alignments", nullptr, "attitude scores are made by gvom_score_attitude", nullptr,
+        "frontiers are made by gvom_frontiers", nullptr, "viewpoint scores are made by gvom_score_viewpoints", nullptr, "pose fields are made by gvom_pose_field"};
+    const char *const maker = kind >= 0 && kind <= GVOM_PRODUCT_POSEFIELD ? elsewhere[kind] : nullptr;
+    if (maker || kind < 1 || kind > GVOM_N_PRODUCT_KINDS) { h->err = std::string("gvom_device_product: ") + (maker ? maker : "unknown product kind"); return GVOM_ERR_INVALID; }
+    if (h->sharded) return refuse(h, "gvom_device_product", "sharded handles are not supported");
     if (kind == GVOM_PRODUCT_VOXEL_CLOUD) stats_demand(h);                  // a read of the statistics, like gvom_debug_voxel_map
     if (!h->has_combined) return GVOM_NO_DATA;
     if ((kind == GVOM_PRODUCT_HEIGHT_CLOUD || kind == GVOM_PRODUCT_INFERRED_HEIGHT_CLOUD) && !h->maps_valid) return GVOM_NO_DATA;
@@ -266,24 +347,24 @@ VIS int gvom_clearance(gvom_t *h, int64_t map_set_id, const int32_t *positive, c
     if (!h || !product_id) return GVOM_ERR_INVALID;
     std::lock_guard<std::mutex> lk(h->mu);
     *product_id = -1;
-    if (h->sharded) { h->err = "gvom_clearance: sharded handles are not supported"; return GVOM_ERR_INVALID; }
+    const char *const fn = "gvom_clearance";
+    int rc;
+    if (h->sharded) return refuse(h, fn, "sharded handles are not supported");
     if (flags & ~GVOM_CLEARANCE_NO_NEGATIVE) { h->err = "gvom_clearance: unknown flag bits"; return GVOM_ERR_INVALID; }
     if (density_threshold != density_threshold) { h->err = "gvom_clearance: the density threshold is not a number"; return GVOM_ERR_INVALID; }
-    if (map_set_id >= 0 && (positive || negative)) { h->err = "gvom_clearance: give a map set id or map pointers, not both"; return GVOM_ERR_INVALID; }
-    if (map_set_id < 0 && !positive) { h->err = "gvom_clearance: give a map set id or a positive map"; return GVOM_ERR_INVALID; }
+    if ((rc = check_one_source(h, fn, map_set_id >= 0, positive || negative, !positive, "a map set id", "map pointers", "a positive map")) || (rc = check_side(h, fn))) return rc;
     const int xy = h->prm.xy_size;
-    if (xy > GVOM_CLEARANCE_MAX_XY) { h->err = "gvom_clearance: maps of more than 4096 cells a side are not supported"; return GVOM_ERR_CAPACITY; }
     const size_t n2 = (size_t)xy * xy;
     const int32_t *pos = positive, *neg = negative;
     if (map_set_id >= 0) {
-        DevSet *m = find_set(h->dsets, map_set_id);
-        if (!m) { h->err = "unknown or stale device map set id"; return GVOM_ERR_INVALID; }
+        DevSet *m = nullptr;
+        if ((rc = map_set_of(h, map_set_id, &m))) return rc;
         pos = part_ptr<const int32_t>(m, 0); neg = part_ptr<const int32_t>(m, 1);
     }
     HIPCHK(h, hipSetDevice(h->device));
     DevSet *set = nullptr;
     const size_t bytes = set_bytes(GVOM_PRODUCT_CLEARANCE, xy, 0, 0);
-    int rc = product_acquire(h, GVOM_PRODUCT_CLEARANCE, bytes, bytes, "gvom_clearance", &h->cl_allocs, &set);
+    rc = product_acquire(h, GVOM_PRODUCT_CLEARANCE, bytes, bytes, fn, &h->cl_allocs, &set);
     if (rc) return rc;
     if ((rc = stage_buf(h, h->cl_g, gvom_clearance_scratch_bytes(xy), h->cl_allocs))) return rc;
     HIPCHK(h, join_second_stream(h));
@@ -312,7 +393,7 @@ VIS int gvom_raycast(gvom_t *h, const float *from, int64_t K, const float *to, i
     if (!h || !product_id) return GVOM_ERR_INVALID;
     std::lock_guard<std::mutex> lk(h->mu);
     *product_id = -1;
-    if (h->sharded) { h->err = "gvom_raycast: sharded handles are not supported"; return GVOM_ERR_INVALID; }
+    if (h->sharded) return refuse(h, "gvom_raycast", "sharded handles are not supported");
     if (!from || !to) { h->err = "gvom_raycast: from and to must not be NULL"; return GVOM_ERR_INVALID; }
     if (n < 1) { h->err = "gvom_raycast: n must be at least 1"; return GVOM_ERR_INVALID; }
     if (K != 1 && K != n) { h->err = "gvom_raycast: K must be 1 or n"; return GVOM_ERR_INVALID; }
@@ -336,13 +417,10 @@ VIS int gvom_raycast(gvom_t *h, const float *from, int64_t K, const float *to, i
     Q.check_target = (flags & GVOM_RAY_CHECK_TARGET) ? 1 : 0;
     HIPCHK(h, join_second_stream(h));
     if (!on_device) {                                                       // host segments: staged, and up before the call returns
-        const size_t kb = (size_t)K * 12, nb = (size_t)n * 12;
-        if ((rc = stage_buf(h, h->rq_stage, align256(kb) + nb, h->rq_allocs))) return rc;
-        char *st = (char *)h->rq_stage.p;
-        HIPCHK(h, hipMemcpyAsync(st, from, kb, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(h, hipMemcpyAsync(st + align256(kb), to, nb, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        Q.from = (const float *)st; Q.to = (const float *)(st + align256(kb));
+        const HostPart parts[2] = {{from, (size_t)K * 12}, {to, (size_t)n * 12}};
+        const void *dev[2];
+        if ((rc = stage_host(h, h->rq_stage, h->rq_allocs, parts, 2, true, dev))) return rc;
+        Q.from = (const float *)dev[0]; Q.to = (const float *)dev[1];
     }
     if ((rc = set_wait_releases(h, set))) return rc;
     HIPCHK(h, gvom_launch_raycast(h->stream, P, Q, F.state, F.tags, part_ptr<int32_t>(set, 0), part_ptr<float>(set, 1)));
@@ -365,16 +443,14 @@ VIS int gvom_cost_to_go(gvom_t *h, int64_t map_set_id, const gvom_ctg_params *pa
     std::lock_guard<std::mutex> lk(h->mu);
     *product_id = -1;
     for (int k = 0; info && k < 4; ++k) info[k] = 0;
-    if (h->sharded) { h->err = "gvom_cost_to_go: sharded handles are not supported"; return GVOM_ERR_INVALID; }
+    const char *const fn = "gvom_cost_to_go";
+    int rc;
+    if (h->sharded) return refuse(h, fn, "sharded handles are not supported");
     if (flags & ~(GVOM_CTG_NO_NEGATIVE | GVOM_CTG_UNKNOWN_BLOCKS)) { h->err = "gvom_cost_to_go: unknown flag bits"; return GVOM_ERR_INVALID; }
-    if (map_set_id >= 0 && cost) { h->err = "gvom_cost_to_go: give a map set id or a cost map, not both"; return GVOM_ERR_INVALID; }
-    if (map_set_id < 0 && !cost) { h->err = "gvom_cost_to_go: give a map set id or a cost map"; return GVOM_ERR_INVALID; }
+    if ((rc = check_one_source(h, fn, map_set_id >= 0, cost, !cost, "a map set id", "a cost map", "a cost map"))) return rc;
     if (map_set_id >= 0 && !params) { h->err = "gvom_cost_to_go: a map set needs the cost parameters"; return GVOM_ERR_INVALID; }
-    if (!goals || n_goals < 1 || n_goals > GVOM_CTG_MAX_GOALS) { h->err = "gvom_cost_to_go: between 1 and 65536 goals"; return GVOM_ERR_INVALID; }
-    if (max_cost < 0 || max_cost > GVOM_CTG_MAX_COST) { h->err = "gvom_cost_to_go: max_cost outside 0 .. 2^30"; return GVOM_ERR_INVALID; }
-    if (max_rounds < 0) { h->err = "gvom_cost_to_go: max_rounds must not be negative"; return GVOM_ERR_INVALID; }
+    if ((rc = check_goals(h, fn, goals, n_goals, max_cost, max_rounds)) || (rc = check_side(h, fn))) return rc;
     const int xy = h->prm.xy_size;
-    if (xy > GVOM_CLEARANCE_MAX_XY) { h->err = "gvom_cost_to_go: maps of more than 4096 cells a side are not supported"; return GVOM_ERR_CAPACITY; }
     const size_t n2 = (size_t)xy * xy;
     for (int64_t k = 0; k < 2 * n_goals; ++k)
         if (goals[k] < 0 || goals[k] >= xy) { h->err = "gvom_cost_to_go: a goal lies outside the window"; return GVOM_ERR_INVALID; }
@@ -382,38 +458,25 @@ VIS int gvom_cost_to_go(gvom_t *h, int64_t map_set_id, const gvom_ctg_params *pa
     memset(&C, 0, sizeof C);
     DevSet *m = nullptr;
     if (map_set_id >= 0) {
-        const int rcp = ctg_cost_params(h, "gvom_cost_to_go", params, flags, &C);
-        if (rcp) return rcp;
-        m = find_set(h->dsets, map_set_id);
-        if (!m) { h->err = "unknown or stale device map set id"; return GVOM_ERR_INVALID; }
-    } else if (!on_device) {
-        for (size_t k = 0; k < n2; ++k)
-            if (cost[k] < 0 || cost[k] > 65535) { h->err = "gvom_cost_to_go: a host cost map holds a value outside 0 .. 65535"; return GVOM_ERR_INVALID; }
-    }
+        if ((rc = ctg_cost_params(h, fn, params, flags, &C)) || (rc = map_set_of(h, map_set_id, &m))) return rc;
+    } else if (!on_device && (rc = check_host_cost(h, fn, cost, n2))) return rc;
     HIPCHK(h, hipSetDevice(h->device));
     DevSet *set = nullptr;
     const size_t bytes = set_bytes(GVOM_PRODUCT_COSTFIELD, xy, 0, 0);
-    int rc = product_acquire(h, GVOM_PRODUCT_COSTFIELD, bytes, bytes, "gvom_cost_to_go", &h->ctg_allocs, &set);
-    if (rc) return rc;
-    const int nt = gvom_ctg_tiles(xy), ntiles = nt * nt;
-    const size_t flags_off = 256, goals_off = flags_off + align256((size_t)2 * ntiles * 4);
-    if ((rc = stage_buf(h, h->ctg_work, goals_off + (size_t)GVOM_CTG_MAX_GOALS * 8, h->ctg_allocs))) return rc;
-    if (!h->ctg_pin) HIPCHK(h, hipHostMalloc((void **)&h->ctg_pin, 256, hipHostMallocDefault));
-    uint32_t *cnt = (uint32_t *)h->ctg_work.p;
-    uint32_t *fl = (uint32_t *)((char *)h->ctg_work.p + flags_off);
-    int32_t *gdev = (int32_t *)((char *)h->ctg_work.p + goals_off);
+    if ((rc = product_acquire(h, GVOM_PRODUCT_COSTFIELD, bytes, bytes, fn, &h->ctg_allocs, &set))) return rc;
+    const int nt = gvom_ctg_tiles(xy);
+    const GoalWork lay = goal_work(nt * nt, 8, 0);
+    if ((rc = solve_work_reserve(h, h->ctg, lay.end, h->ctg_allocs))) return rc;
+    const GoalWorkPtrs G = goal_work_ptrs(h->ctg, lay);
     HIPCHK(h, join_second_stream(h));
-    const int32_t *cost32 = nullptr;
+    const void *cost32 = map_set_id < 0 ? cost : nullptr;
     if (map_set_id < 0 && !on_device) {                                     // a host cost map: staged
-        if ((rc = stage_buf(h, h->ctg_stage, n2 * 4, h->ctg_allocs))) return rc;
-        HIPCHK(h, hipMemcpyAsync(h->ctg_stage.p, cost, n2 * 4, hipMemcpyHostToDevice, h->stream));
-        cost32 = (const int32_t *)h->ctg_stage.p;
-    } else if (map_set_id < 0) cost32 = cost;
+        const HostPart part = {cost, n2 * 4};
+        if ((rc = stage_host(h, h->ctg_stage, h->ctg_allocs, &part, 1, false, &cost32))) return rc;
+    }
     const size_t clr_g = align256(gvom_clearance_scratch_bytes(xy)), clr_map = align256(n2 * 4);
     if (m && C.inflation_cells2 > 0 && (rc = stage_buf(h, h->ctg_clr, clr_g + 2 * clr_map, h->ctg_allocs))) return rc;
-    HIPCHK(h, hipMemcpyAsync(gdev, goals, (size_t)n_goals * 8, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemsetAsync(cnt, 0, 256, h->stream));
-    if ((rc = set_wait_releases(h, set))) return rc;
+    if ((rc = goal_work_start(h, G, goals, (size_t)n_goals * 8)) || (rc = set_wait_releases(h, set))) return rc;
     int32_t *D = part_ptr<int32_t>(set, 0);
     uint16_t *c16 = part_ptr<uint16_t>(set, 2);
     if (m) {
@@ -427,17 +490,9 @@ VIS int gvom_cost_to_go(gvom_t *h, int64_t map_set_id, const gvom_ctg_params *pa
         }
         HIPCHK(h, gvom_launch_travcost(h->stream, xy, mp, mn, part_ptr<const int32_t>(m, 2), part_ptr<const double>(m, 3), cd2, C, c16));
     }
-    CtgSolve S;
-    if ((rc = ctg_solve(h, xy, cost32, c16, D, part_ptr<uint8_t>(set, 1), cnt, fl, gdev, (int)n_goals, max_cost, max_rounds, h->ctg_pin, &S))) return rc;
-    const bool converged = S.converged;
-    const int64_t rounds = S.rounds, tiles = S.tiles;
-    if ((rc = product_publish(h, set, product_id))) return rc;             // (`ready` goes in front of the counters' way back)
-    HIPCHK(h, hipMemcpyAsync(h->ctg_pin, cnt, 256, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (!converged && max_rounds == 0) { set->id = *product_id = -1; h->err = "gvom_cost_to_go: the field did not settle"; return GVOM_ERR_HIP; }   // (nobody gets it)
-    h->ctg_last_tiles = (int)std::min<int64_t>(tiles, INT32_MAX);
-    if (info) { info[0] = converged ? 1 : 0; info[1] = rounds; info[2] = h->ctg_pin[CTG_CNT_REACHED]; info[3] = h->ctg_pin[CTG_CNT_SEEDED]; }
-    return GVOM_OK;
+    SolveRounds S;
+    if ((rc = ctg_solve(h, h->ctg, G, xy, (const int32_t *)cost32, c16, D, part_ptr<uint8_t>(set, 1), (int)n_goals, max_cost, max_rounds, &S))) return rc;
+    return goal_solve_finish(h, fn, h->ctg, set, product_id, S, max_rounds, info);
 }
 // ---- rollout scoring (gvom_footprint_set, gvom_score_rollouts) -------------------------------------------------------------------
 // K trajectories of T poses each, scored by k_rollouts (gvom_rollouts.hip) against a uint16 cost map with the footprint table of the
@@ -475,51 +530,41 @@ VIS int gvom_score_rollouts(gvom_t *h, int64_t costfield_id, const uint16_t *cel
     if (!h || !product_id) return GVOM_ERR_INVALID;
     std::lock_guard<std::mutex> lk(h->mu);
     *product_id = -1;
-    if (h->sharded) { h->err = "gvom_score_rollouts: sharded handles are not supported"; return GVOM_ERR_INVALID; }
+    const char *const fn = "gvom_score_rollouts";
+    int rc;
+    if (h->sharded) return refuse(h, fn, "sharded handles are not supported");
     if (h->fp_H < 1) { h->err = "gvom_score_rollouts: no footprint table is set (gvom_footprint_set)"; return GVOM_ERR_INVALID; }
     if (!poses || !origin_cells) { h->err = "gvom_score_rollouts: poses and origin_cells must not be NULL"; return GVOM_ERR_INVALID; }
-    if (costfield_id >= 0 && (cell_cost || cost_to_go)) { h->err = "gvom_score_rollouts: give a cost field id or map pointers, not both"; return GVOM_ERR_INVALID; }
-    if (costfield_id < 0 && !cell_cost) { h->err = "gvom_score_rollouts: give a cost field id or a cell-cost map"; return GVOM_ERR_INVALID; }
-    if (T < 1 || T > GVOM_ROLLOUT_MAX_T) { h->err = "gvom_score_rollouts: T outside 1 .. 4096"; return GVOM_ERR_INVALID; }
-    if (K < 1) { h->err = "gvom_score_rollouts: K must be at least 1"; return GVOM_ERR_INVALID; }
-    if (K > GVOM_ROLLOUT_MAX_POSES / T) { h->err = "gvom_score_rollouts: more than 2^26 poses in one call"; return GVOM_ERR_CAPACITY; }
-    for (int k = 0; k < 2; ++k)
-        if (origin_cells[k] < -((int64_t)1 << 40) || origin_cells[k] > ((int64_t)1 << 40)) { h->err = "gvom_score_rollouts: an origin beyond 2^40 cells"; return GVOM_ERR_INVALID; }
+    if ((rc = check_one_source(h, fn, costfield_id >= 0, cell_cost || cost_to_go, !cell_cost, "a cost field id", "map pointers", "a cell-cost map")) ||
+        (rc = check_rollout_shape(h, fn, K, T, origin_cells)) || (rc = check_side(h, fn))) return rc;
     const int xy = h->prm.xy_size;
-    if (xy > GVOM_CLEARANCE_MAX_XY) { h->err = "gvom_score_rollouts: maps of more than 4096 cells a side are not supported"; return GVOM_ERR_CAPACITY; }
     const size_t n2 = (size_t)xy * xy;
     const uint16_t *c16 = cell_cost;
     const int32_t *D = cost_to_go;
     if (costfield_id >= 0) {
-        DevSet *f = find_set(h->psets, costfield_id);
-        if (!f || f->kind != GVOM_PRODUCT_COSTFIELD) { h->err = "gvom_score_rollouts: unknown or stale cost field id"; return GVOM_ERR_INVALID; }
+        DevSet *f = nullptr;
+        if ((rc = cost_field_of(h, fn, costfield_id, &f))) return rc;
         c16 = part_ptr<const uint16_t>(f, 2); D = part_ptr<const int32_t>(f, 0);
     }
     HIPCHK(h, hipSetDevice(h->device));
     DevSet *set = nullptr;
     const size_t bytes = set_bytes(GVOM_PRODUCT_ROLLOUTS, 0, 0, K, T);
-    int rc = product_acquire(h, GVOM_PRODUCT_ROLLOUTS, bytes, bytes, "gvom_score_rollouts", &h->ro_allocs, &set);
+    rc = product_acquire(h, GVOM_PRODUCT_ROLLOUTS, bytes, bytes, fn, &h->ro_allocs, &set);
     if (rc) return rc;
     set->cap = K; set->cols = T;
     const float *pdev = poses;
     HIPCHK(h, join_second_stream(h));
     if (!on_device) {                                                       // host poses (and maps): staged, and up before the call returns
-        const size_t pb = (size_t)K * T * 12, cb = costfield_id < 0 ? align256(n2 * 2) : 0, db = (costfield_id < 0 && cost_to_go) ? align256(n2 * 4) : 0;
-        if ((rc = stage_buf(h, h->ro_stage, cb + db + pb, h->ro_allocs))) return rc;
-        char *st = (char *)h->ro_stage.p;
-        if (cb) { HIPCHK(h, hipMemcpyAsync(st, cell_cost, n2 * 2, hipMemcpyHostToDevice, h->stream)); c16 = (const uint16_t *)st; }
-        if (db) { HIPCHK(h, hipMemcpyAsync(st + cb, cost_to_go, n2 * 4, hipMemcpyHostToDevice, h->stream)); D = (const int32_t *)(st + cb); }
-        HIPCHK(h, hipMemcpyAsync(st + cb + db, poses, pb, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        pdev = (const float *)(st + cb + db);
+        const HostPart parts[3] = {{cell_cost, n2 * 2}, {cost_to_go, n2 * 4}, {poses, (size_t)K * T * 12}};
+        const void *dev[3];
+        if ((rc = stage_host(h, h->ro_stage, h->ro_allocs, parts, 3, true, dev))) return rc;
+        if (dev[0]) c16 = (const uint16_t *)dev[0];
+        if (dev[1]) D = (const int32_t *)dev[1];
+        pdev = (const float *)dev[2];
     }
     if ((rc = set_wait_releases(h, set))) return rc;
     RolloutParams P;
-    memset(&P, 0, sizeof P);
-    P.xy = xy; P.H = h->fp_H; P.T = (int)T; P.K = K;
-    P.s = (float)((double)h->fp_H / 6.283185307179586476925286766559);
-    P.ox = origin_cells[0]; P.oy = origin_cells[1];
-    P.res = h->prm.xy_resolution;
+    rollout_frame(h, K, T, origin_cells, P);
     HIPCHK(h, gvom_launch_rollouts(h->stream, P, pdev, (const int32_t *)h->fp_tab.p, (const uint32_t *)((char *)h->fp_tab.p + h->fp_offs_at),
                                    c16, D, part_ptr<int32_t>(set, 0), part_ptr<uint16_t>(set, 1)));
     return product_publish(h, set, product_id);
@@ -572,31 +617,24 @@ VIS int gvom_score_attitude(gvom_t *h, int64_t map_set_id, const double *ground,
     if (!h || !product_id) return GVOM_ERR_INVALID;
     std::lock_guard<std::mutex> lk(h->mu);
     *product_id = -1;
-    if (h->sharded) { h->err = "gvom_score_attitude: sharded handles are not supported"; return GVOM_ERR_INVALID; }
+    const char *const fn = "gvom_score_attitude";
+    int rc;
+    if (h->sharded) return refuse(h, fn, "sharded handles are not supported");
     if (h->fp_H < 1) { h->err = "gvom_score_attitude: no footprint table is set (gvom_footprint_set)"; return GVOM_ERR_INVALID; }
     if (h->at_H < 1) { h->err = "gvom_score_attitude: no chassis is set (gvom_chassis_set)"; return GVOM_ERR_INVALID; }
     if (h->at_H != h->fp_H) { h->err = "gvom_score_attitude: the chassis was set for another number of headings than the footprint table has"; return GVOM_ERR_INVALID; }
     if (!poses || !origin_cells) { h->err = "gvom_score_attitude: poses and origin_cells must not be NULL"; return GVOM_ERR_INVALID; }
     if (flags & ~GVOM_ATTITUDE_INFERRED_GROUND) { h->err = "gvom_score_attitude: unknown flag bits"; return GVOM_ERR_INVALID; }
-    if (map_set_id >= 0 && ground) { h->err = "gvom_score_attitude: give a map set id or a ground map, not both"; return GVOM_ERR_INVALID; }
-    if (map_set_id < 0 && !ground) { h->err = "gvom_score_attitude: give a map set id or a ground map"; return GVOM_ERR_INVALID; }
-    if (T < 1 || T > GVOM_ROLLOUT_MAX_T) { h->err = "gvom_score_attitude: T outside 1 .. 4096"; return GVOM_ERR_INVALID; }
-    if (K < 1) { h->err = "gvom_score_attitude: K must be at least 1"; return GVOM_ERR_INVALID; }
-    if (K > GVOM_ROLLOUT_MAX_POSES / T) { h->err = "gvom_score_attitude: more than 2^26 poses in one call"; return GVOM_ERR_CAPACITY; }
-    for (int k = 0; k < 2; ++k)
-        if (origin_cells[k] < -((int64_t)1 << 40) || origin_cells[k] > ((int64_t)1 << 40)) { h->err = "gvom_score_attitude: an origin beyond 2^40 cells"; return GVOM_ERR_INVALID; }
+    if ((rc = check_one_source(h, fn, map_set_id >= 0, ground, !ground, "a map set id", "a ground map", "a ground map"))) return rc;
+    if ((rc = check_rollout_shape(h, fn, K, T, origin_cells)) || (rc = check_side(h, fn))) return rc;
     const int xy = h->prm.xy_size;
-    if (xy > GVOM_CLEARANCE_MAX_XY) { h->err = "gvom_score_attitude: maps of more than 4096 cells a side are not supported"; return GVOM_ERR_CAPACITY; }
     const size_t n2 = (size_t)xy * xy;
     DevSet *m = nullptr;
-    if (map_set_id >= 0) {
-        m = find_set(h->dsets, map_set_id);
-        if (!m) { h->err = "unknown or stale device map set id"; return GVOM_ERR_INVALID; }
-    }
+    if (map_set_id >= 0 && (rc = map_set_of(h, map_set_id, &m))) return rc;
     HIPCHK(h, hipSetDevice(h->device));
     DevSet *set = nullptr;
     const size_t bytes = set_bytes(GVOM_PRODUCT_ATTITUDE, 0, 0, K, T);
-    int rc = product_acquire(h, GVOM_PRODUCT_ATTITUDE, bytes, bytes, "gvom_score_attitude", &h->at_allocs, &set);
+    rc = product_acquire(h, GVOM_PRODUCT_ATTITUDE, bytes, bytes, fn, &h->at_allocs, &set);
     if (rc) return rc;
     set->cap = K; set->cols = T;
     if (m && (rc = stage_buf(h, h->at_ground, n2 * 8, h->at_allocs))) return rc;
@@ -604,13 +642,11 @@ VIS int gvom_score_attitude(gvom_t *h, int64_t map_set_id, const double *ground,
     const double *gdev = m ? (const double *)h->at_ground.p : ground;
     HIPCHK(h, join_second_stream(h));
     if (!on_device) {                                                       // host poses (and ground): staged, and up before the call returns
-        const size_t pb = (size_t)K * T * 12, gb = m ? 0 : align256(n2 * 8);
-        if ((rc = stage_buf(h, h->at_stage, gb + pb, h->at_allocs))) return rc;
-        char *st = (char *)h->at_stage.p;
-        if (gb) { HIPCHK(h, hipMemcpyAsync(st, ground, n2 * 8, hipMemcpyHostToDevice, h->stream)); gdev = (const double *)st; }
-        HIPCHK(h, hipMemcpyAsync(st + gb, poses, pb, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        pdev = (const float *)(st + gb);
+        const HostPart parts[2] = {{ground, n2 * 8}, {poses, (size_t)K * T * 12}};
+        const void *dev[2];
+        if ((rc = stage_host(h, h->at_stage, h->at_allocs, parts, 2, true, dev))) return rc;
+        if (dev[0]) gdev = (const double *)dev[0];
+        pdev = (const float *)dev[1];
     }
     if ((rc = set_wait_releases(h, set))) return rc;
     if (m) HIPCHK(h, gvom_launch_attitude_ground(h->stream, xy, (flags & GVOM_ATTITUDE_INFERRED_GROUND) ? 1 : 0, part_ptr<const double>(m, 4),
@@ -618,10 +654,7 @@ VIS int gvom_score_attitude(gvom_t *h, int64_t map_set_id, const double *ground,
     const gvom_chassis_t &c = h->at_chassis;
     AttitudeParams P;
     memset(&P, 0, sizeof P);
-    P.R.xy = xy; P.R.H = h->fp_H; P.R.T = (int)T; P.R.K = K;
-    P.R.s = (float)((double)h->fp_H / 6.283185307179586476925286766559);
-    P.R.ox = origin_cells[0]; P.R.oy = origin_cells[1];
-    P.R.res = h->prm.xy_resolution;
+    rollout_frame(h, K, T, origin_cells, P.R);
     P.wheelbase = c.front_axle - c.rear_axle; P.track = c.track; P.axle_mid = 0.5 * (c.front_axle + c.rear_axle); P.belly_height = c.belly_height;
     P.max_pitch = c.max_pitch; P.max_roll = c.max_roll; P.min_clearance = c.min_clearance;
     HIPCHK(h, gvom_launch_attitude(h->stream, P, pdev, (const int32_t *)h->fp_tab.p, (const uint32_t *)((char *)h->fp_tab.p + h->fp_offs_at),
@@ -641,7 +674,7 @@ VIS int gvom_score_alignments(gvom_t *h, const float *cloud, int64_t n, const do
     if (!h || !product_id) return GVOM_ERR_INVALID;
     std::lock_guard<std::mutex> lk(h->mu);
     *product_id = -1;
-    if (h->sharded) { h->err = "gvom_score_alignments: sharded handles are not supported"; return GVOM_ERR_INVALID; }
+    if (h->sharded) return refuse(h, "gvom_score_alignments", "sharded handles are not supported");
     if (!cloud || !transforms || !weights) { h->err = "gvom_score_alignments: cloud, transforms and weights must not be NULL"; return GVOM_ERR_INVALID; }
     if (n < 1) { h->err = "gvom_score_alignments: n must be at least 1"; return GVOM_ERR_INVALID; }
     if (K < 1) { h->err = "gvom_score_alignments: K must be at least 1"; return GVOM_ERR_INVALID; }
@@ -667,23 +700,17 @@ VIS int gvom_score_alignments(gvom_t *h, const float *cloud, int64_t n, const do
     occ_params(h, F, O);
     AlignParams P;
     memset(&P, 0, sizeof P);
-    P.xy_res = h->prm.xy_resolution; P.z_res = h->prm.z_resolution;
-    P.drcp[0] = 1.0 / h->prm.xy_resolution; P.drcp[1] = 1.0 / h->prm.z_resolution;
-    P.fastdiv = h->tune_fastdiv == 0 ? 0 : h->fastdiv_ok;
-    for (int k = 0; k < 3; ++k) P.origin[k] = (double)F.origin[k];
+    metric_frame(h, F, P);
     P.n = (long)n; P.K = (int)K; P.xy = xy; P.zs = zs; P.rw = (xy + 15) / 16; P.dilate = dilate;
     for (int c = 0; c < 5; ++c) P.w[c] = weights[c];
     const float *cdev = cloud;
     const double *tdev = transforms;
     HIPCHK(h, join_second_stream(h));
     if (!on_device) {                                                       // host inputs: staged, and up before the call returns
-        const size_t tb = (size_t)K * 96, cb = (size_t)n * 12;
-        if ((rc = stage_buf(h, h->al_stage, align256(tb) + cb, h->al_allocs))) return rc;
-        char *st = (char *)h->al_stage.p;
-        HIPCHK(h, hipMemcpyAsync(st, transforms, tb, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(h, hipMemcpyAsync(st + align256(tb), cloud, cb, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        tdev = (const double *)st; cdev = (const float *)(st + align256(tb));
+        const HostPart parts[2] = {{transforms, (size_t)K * 96}, {cloud, (size_t)n * 12}};
+        const void *dev[2];
+        if ((rc = stage_host(h, h->al_stage, h->al_allocs, parts, 2, true, dev))) return rc;
+        tdev = (const double *)dev[0]; cdev = (const float *)dev[1];
     }
     if ((rc = set_wait_releases(h, set))) return rc;
     HIPCHK(h, gvom_launch_align(h->stream, O, P, F.state, F.tags, cdev, tdev, (uint32_t *)h->al_grid.p, part_ptr<int32_t>(set, 0),
@@ -704,52 +731,41 @@ VIS int gvom_frontiers(gvom_t *h, int64_t costfield_id, int64_t map_set_id, cons
     std::lock_guard<std::mutex> lk(h->mu);
     *product_id = -1;
     for (int k = 0; info && k < 4; ++k) info[k] = 0;
-    if (h->sharded) { h->err = "gvom_frontiers: sharded handles are not supported"; return GVOM_ERR_INVALID; }
+    const char *const fn = "gvom_frontiers";
+    int rc;
+    if (h->sharded) return refuse(h, fn, "sharded handles are not supported");
     const bool ids = costfield_id >= 0 && map_set_id >= 0;
     if ((costfield_id >= 0) != (map_set_id >= 0)) { h->err = "gvom_frontiers: the ids route needs a cost field id AND a map set id"; return GVOM_ERR_INVALID; }
     if (ids && (cell_cost || cost_to_go || visibility)) { h->err = "gvom_frontiers: give the two ids or map pointers, not both"; return GVOM_ERR_INVALID; }
     if (!ids && (!cell_cost || !visibility)) { h->err = "gvom_frontiers: give the two ids, or a cell-cost map and a visibility map"; return GVOM_ERR_INVALID; }
-    if (min_cells < 1) { h->err = "gvom_frontiers: min_cells must be at least 1"; return GVOM_ERR_INVALID; }
-    if (max_clusters < 1 || max_clusters > GVOM_FRONTIER_MAX_CLUSTERS) { h->err = "gvom_frontiers: max_clusters outside 1 .. 2^20"; return GVOM_ERR_INVALID; }
+    if ((rc = check_clusters(h, fn, min_cells, max_clusters)) || (rc = check_side(h, fn))) return rc;
     const int xy = h->prm.xy_size;
-    if (xy > GVOM_CLEARANCE_MAX_XY) { h->err = "gvom_frontiers: maps of more than 4096 cells a side are not supported"; return GVOM_ERR_CAPACITY; }
     const size_t n2 = (size_t)xy * xy;
     const uint16_t *c16 = cell_cost;
     const int32_t *D = cost_to_go, *vis = visibility;
     if (ids) {
-        DevSet *f = find_set(h->psets, costfield_id);
-        if (!f || f->kind != GVOM_PRODUCT_COSTFIELD) { h->err = "gvom_frontiers: unknown or stale cost field id"; return GVOM_ERR_INVALID; }
-        DevSet *m = find_set(h->dsets, map_set_id);
-        if (!m) { h->err = "unknown or stale device map set id"; return GVOM_ERR_INVALID; }
+        DevSet *f = nullptr, *m = nullptr;
+        if ((rc = cost_field_of(h, fn, costfield_id, &f)) || (rc = map_set_of(h, map_set_id, &m))) return rc;
         c16 = part_ptr<const uint16_t>(f, 2); D = part_ptr<const int32_t>(f, 0); vis = part_ptr<const int32_t>(m, 2);
     }
     HIPCHK(h, hipSetDevice(h->device));
     DevSet *set = nullptr;
     const size_t bytes = set_bytes(GVOM_PRODUCT_FRONTIERS, xy, 0, max_clusters);
-    int rc = product_acquire(h, GVOM_PRODUCT_FRONTIERS, bytes, bytes, "gvom_frontiers", &h->fr_allocs, &set);
-    if (rc) return rc;
+    if ((rc = product_acquire(h, GVOM_PRODUCT_FRONTIERS, bytes, bytes, fn, &h->fr_allocs, &set))) return rc;
     set->cap = max_clusters;
-    if ((rc = stage_buf(h, h->fr_work, fr_work_bytes(xy), h->fr_allocs))) return rc;
-    if (!h->fr_pin) HIPCHK(h, hipHostMalloc((void **)&h->fr_pin, 256, hipHostMallocDefault));
-    const FrWork W = fr_work_layout(xy, (char *)h->fr_work.p);
+    FrWork W;
+    if ((rc = frontier_work(h, h->fr, xy, h->fr_allocs, &W))) return rc;
     HIPCHK(h, join_second_stream(h));
     if (!ids && !on_device) {                                               // host maps: staged
-        const size_t cb = align256(n2 * 2), vb = align256(n2 * 4);
-        if ((rc = stage_buf(h, h->fr_stage, cb + vb + (cost_to_go ? n2 * 4 : 0), h->fr_allocs))) return rc;
-        char *st = (char *)h->fr_stage.p;
-        HIPCHK(h, hipMemcpyAsync(st, cell_cost, n2 * 2, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(h, hipMemcpyAsync(st + cb, visibility, n2 * 4, hipMemcpyHostToDevice, h->stream));
-        if (cost_to_go) HIPCHK(h, hipMemcpyAsync(st + cb + vb, cost_to_go, n2 * 4, hipMemcpyHostToDevice, h->stream));
-        c16 = (const uint16_t *)st; vis = (const int32_t *)(st + cb); D = cost_to_go ? (const int32_t *)(st + cb + vb) : nullptr;
+        const HostPart parts[3] = {{cell_cost, n2 * 2}, {visibility, n2 * 4}, {cost_to_go, n2 * 4}};
+        const void *dev[3];
+        if ((rc = stage_host(h, h->fr_stage, h->fr_allocs, parts, 3, false, dev))) return rc;
+        c16 = (const uint16_t *)dev[0]; vis = (const int32_t *)dev[1]; D = (const int32_t *)dev[2];
     }
     HIPCHK(h, hipMemsetAsync(W.cnt, 0, W.clear_bytes, h->stream));          // the counters and both halves of the flags
     if ((rc = set_wait_releases(h, set))) return rc;
     HIPCHK(h, gvom_launch_frontier_mark(h->stream, xy, c16, vis, D, W.L, W.count, W.fl, W.cnt + FR_CNT_CELLS));
-    FrSolve S;
-    if ((rc = frontier_solve(h, "gvom_frontiers", xy, D, W, h->fr_pin, min_cells, max_clusters, set, product_id, info, &S))) return rc;
-    h->fr_last_rounds = (int)std::min<int64_t>(S.rounds, INT32_MAX);
-    h->fr_last_tiles = (int)std::min<int64_t>(S.tiles, INT32_MAX);
-    return GVOM_OK;
+    return frontier_solve(h, fn, h->fr, xy, D, W, min_cells, max_clusters, set, product_id, info);
 }
 
 // ---- viewpoint scoring (gvom_score_viewpoints) -------------------------------------------------------------------------------------
@@ -764,7 +780,7 @@ VIS int gvom_score_viewpoints(gvom_t *h, const double *poses, int64_t K, int on_
     if (!h || !product_id) return GVOM_ERR_INVALID;
     std::lock_guard<std::mutex> lk(h->mu);
     *product_id = -1;
-    if (h->sharded) { h->err = "gvom_score_viewpoints: sharded handles are not supported"; return GVOM_ERR_INVALID; }
+    if (h->sharded) return refuse(h, "gvom_score_viewpoints", "sharded handles are not supported");
     if (!poses) { h->err = "gvom_score_viewpoints: poses must not be NULL"; return GVOM_ERR_INVALID; }
     if (h->ri_H <= 0) { h->err = "gvom_score_viewpoints: no sensor model (gvom_sensor_model_set)"; return GVOM_ERR_INVALID; }
     if (K < 1) { h->err = "gvom_score_viewpoints: K must be at least 1"; return GVOM_ERR_INVALID; }
@@ -805,11 +821,10 @@ VIS int gvom_score_viewpoints(gvom_t *h, const double *poses, int64_t K, int on_
     Q.lit = R.lit; Q.cap = R.cap; Q.bm_words = (uint32_t)bm_words;
     HIPCHK(h, join_second_stream(h));
     if (!on_device) {                                                       // host poses: staged, and up before the call returns
-        const size_t pb = (size_t)K * 96;
-        if ((rc = stage_buf(h, h->vp_stage, pb, h->vp_allocs))) return rc;
-        HIPCHK(h, hipMemcpyAsync(h->vp_stage.p, poses, pb, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        Q.poses = (const double *)h->vp_stage.p;
+        const HostPart part = {poses, (size_t)K * 96};
+        const void *dev;
+        if ((rc = stage_host(h, h->vp_stage, h->vp_allocs, &part, 1, true, &dev))) return rc;
+        Q.poses = (const double *)dev;
     }
     if ((rc = set_wait_releases(h, set))) return rc;
     int32_t *rows = part_ptr<int32_t>(set, 0);
@@ -871,98 +886,64 @@ VIS int gvom_pose_field(gvom_t *h, int64_t costfield_id, const int32_t *cost, in
     std::lock_guard<std::mutex> lk(h->mu);
     *product_id = -1;
     for (int k = 0; info && k < 4; ++k) info[k] = 0;
-    if (h->sharded) { h->err = "gvom_pose_field: sharded handles are not supported"; return GVOM_ERR_INVALID; }
+    const char *const fn = "gvom_pose_field";
+    int rc;
+    if (h->sharded) return refuse(h, fn, "sharded handles are not supported");
     if (h->fp_H < 1) { h->err = "gvom_pose_field: no footprint table is set (gvom_footprint_set)"; return GVOM_ERR_INVALID; }
     if (h->pf_H < 1) { h->err = "gvom_pose_field: no primitive table is set (gvom_primitives_set)"; return GVOM_ERR_INVALID; }
     if (h->fp_H > GVOM_POSE_MAX_HEADINGS) { h->err = "gvom_pose_field: footprint tables of more than 64 headings are not supported"; return GVOM_ERR_CAPACITY; }
     if (h->pf_H != h->fp_H) { h->err = "gvom_pose_field: the primitives were set for another number of headings than the footprint table has"; return GVOM_ERR_INVALID; }
-    if (costfield_id >= 0 && cost) { h->err = "gvom_pose_field: give a cost field id or a cost map, not both"; return GVOM_ERR_INVALID; }
-    if (costfield_id < 0 && !cost) { h->err = "gvom_pose_field: give a cost field id or a cost map"; return GVOM_ERR_INVALID; }
-    if (!goals || n_goals < 1 || n_goals > GVOM_CTG_MAX_GOALS) { h->err = "gvom_pose_field: between 1 and 65536 goals"; return GVOM_ERR_INVALID; }
-    if (max_cost < 0 || max_cost > GVOM_CTG_MAX_COST) { h->err = "gvom_pose_field: max_cost outside 0 .. 2^30"; return GVOM_ERR_INVALID; }
-    if (max_rounds < 0) { h->err = "gvom_pose_field: max_rounds must not be negative"; return GVOM_ERR_INVALID; }
+    if ((rc = check_one_source(h, fn, costfield_id >= 0, cost, !cost, "a cost field id", "a cost map", "a cost map"))) return rc;
+    if ((rc = check_goals(h, fn, goals, n_goals, max_cost, max_rounds)) || (rc = check_side(h, fn))) return rc;
     const int xy = h->prm.xy_size, H = h->pf_H, R = h->pf_R;
-    if (xy > GVOM_CLEARANCE_MAX_XY) { h->err = "gvom_pose_field: maps of more than 4096 cells a side are not supported"; return GVOM_ERR_CAPACITY; }
     const size_t n2 = (size_t)xy * xy;
     if ((int64_t)H * (int64_t)n2 > GVOM_POSE_MAX_STATES) { h->err = "gvom_pose_field: more than 2^28 states (headings x xy_size^2)"; return GVOM_ERR_CAPACITY; }
     for (int64_t k = 0; k < n_goals; ++k) {
         if (goals[3 * k] < 0 || goals[3 * k] >= xy || goals[3 * k + 1] < 0 || goals[3 * k + 1] >= xy) { h->err = "gvom_pose_field: a goal lies outside the window"; return GVOM_ERR_INVALID; }
         if (goals[3 * k + 2] >= H) { h->err = "gvom_pose_field: a goal's heading is not one of the table's"; return GVOM_ERR_INVALID; }
     }
-    const DevSet *f = nullptr;
+    DevSet *f = nullptr;
     if (costfield_id >= 0) {
-        f = find_set(h->psets, costfield_id);
-        if (!f || f->kind != GVOM_PRODUCT_COSTFIELD) { h->err = "gvom_pose_field: unknown or stale cost field id"; return GVOM_ERR_INVALID; }
-    } else if (!on_device) {
-        for (size_t k = 0; k < n2; ++k)
-            if (cost[k] < 0 || cost[k] > 65535) { h->err = "gvom_pose_field: a host cost map holds a value outside 0 .. 65535"; return GVOM_ERR_INVALID; }
-    }
+        if ((rc = cost_field_of(h, fn, costfield_id, &f))) return rc;
+    } else if (!on_device && (rc = check_host_cost(h, fn, cost, n2))) return rc;
     HIPCHK(h, hipSetDevice(h->device));
     DevSet *set = nullptr;
     const size_t bytes = set_bytes(GVOM_PRODUCT_POSEFIELD, xy, 0, H);
-    int rc = product_acquire(h, GVOM_PRODUCT_POSEFIELD, bytes, bytes, "gvom_pose_field", &h->pf_allocs, &set);
-    if (rc) return rc;
+    if ((rc = product_acquire(h, GVOM_PRODUCT_POSEFIELD, bytes, bytes, fn, &h->pf_allocs, &set))) return rc;
     set->cap = H;
-    const int nt = gvom_pose_tiles(xy), ntiles = nt * nt;
-    const size_t flags_off = 256, goals_off = flags_off + align256((size_t)2 * ntiles * 4), c16_off = goals_off + align256((size_t)GVOM_CTG_MAX_GOALS * 12);
-    if ((rc = stage_buf(h, h->pf_work, c16_off + n2 * 2, h->pf_allocs))) return rc;
-    if (!h->pf_pin) HIPCHK(h, hipHostMalloc((void **)&h->pf_pin, 256, hipHostMallocDefault));
-    uint32_t *cnt = (uint32_t *)h->pf_work.p;
-    uint32_t *fl = (uint32_t *)((char *)h->pf_work.p + flags_off);
-    int32_t *gdev = (int32_t *)((char *)h->pf_work.p + goals_off);
-    uint16_t *c16w = (uint16_t *)((char *)h->pf_work.p + c16_off);
+    const int nt = gvom_pose_tiles(xy);
+    const GoalWork lay = goal_work(nt * nt, 12, n2 * 2);                     // (the tail: the uint16 cost map converted from cost32)
+    if ((rc = solve_work_reserve(h, h->pf, lay.end, h->pf_allocs))) return rc;
+    const GoalWorkPtrs G = goal_work_ptrs(h->pf, lay);
+    uint16_t *c16w = (uint16_t *)G.tail;
     HIPCHK(h, join_second_stream(h));
-    const int32_t *cost32 = nullptr;
+    const void *cost32 = f ? nullptr : cost;
     if (!f && !on_device) {                                                 // a host cost map: staged
-        if ((rc = stage_buf(h, h->pf_stage, n2 * 4, h->pf_allocs))) return rc;
-        HIPCHK(h, hipMemcpyAsync(h->pf_stage.p, cost, n2 * 4, hipMemcpyHostToDevice, h->stream));
-        cost32 = (const int32_t *)h->pf_stage.p;
-    } else if (!f) cost32 = cost;
+        const HostPart part = {cost, n2 * 4};
+        if ((rc = stage_host(h, h->pf_stage, h->pf_allocs, &part, 1, false, &cost32))) return rc;
+    }
     const uint16_t *c16 = f ? part_ptr<const uint16_t>(f, 2) : c16w;
-    HIPCHK(h, hipMemcpyAsync(gdev, goals, (size_t)n_goals * 12, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemsetAsync(cnt, 0, 256, h->stream));
-    if ((rc = set_wait_releases(h, set))) return rc;
+    if ((rc = goal_work_start(h, G, goals, (size_t)n_goals * 12)) || (rc = set_wait_releases(h, set))) return rc;
     int32_t *D = part_ptr<int32_t>(set, 0);
     uint16_t *C = part_ptr<uint16_t>(set, 2);
     const int32_t *pstart = (const int32_t *)h->pf_tab.p;
     const int16_t *prims = (const int16_t *)((char *)h->pf_tab.p + h->pf_prims_at);
-    HIPCHK(h, gvom_launch_pose_seed(h->stream, 0, xy, H, R, cost32, c16w, C, D, fl, gdev, (int)n_goals, cnt + CTG_CNT_SEEDED));
+    HIPCHK(h, gvom_launch_pose_seed(h->stream, 0, xy, H, R, (const int32_t *)cost32, c16w, C, D, G.fl, G.goals, (int)n_goals, G.cnt + CTG_CNT_SEEDED));
     HIPCHK(h, gvom_launch_cspace(h->stream, xy, H, c16, (const int32_t *)h->fp_tab.p, (const uint32_t *)((char *)h->fp_tab.p + h->fp_offs_at), C));
-    HIPCHK(h, gvom_launch_pose_seed(h->stream, 1, xy, H, R, cost32, c16w, C, D, fl, gdev, (int)n_goals, cnt + CTG_CNT_SEEDED));
+    HIPCHK(h, gvom_launch_pose_seed(h->stream, 1, xy, H, R, (const int32_t *)cost32, c16w, C, D, G.fl, G.goals, (int)n_goals, G.cnt + CTG_CNT_SEEDED));
     const int32_t cap = max_cost == 0 ? GVOM_CTG_MAX_COST : max_cost;
-    const int inner = h->tune_pf_inner > 0 ? h->tune_pf_inner : 64;
-    const int batch = h->tune_pf_batch > 0 ? h->tune_pf_batch : 8;
+    const int inner = h->pf.tune_inner > 0 ? h->pf.tune_inner : 64;
+    const int batch = h->pf.tune_batch > 0 ? h->pf.tune_batch : 8;
     // a state's final value is in memory at the latest one round after the round in which its successor's was, so
     // the solve ends after at most (primitives on a cheapest drive + 1) rounds of tiles that reach their fixed point; the limit below
-    // is beyond that for 2^28 states and only keeps this loop finite
+    // is beyond that for 2^28 states and only keeps the loop finite
     const int64_t limit = max_rounds > 0 ? (int64_t)max_rounds : (int64_t)1 << 29;
-    int64_t rounds = 0, tiles = 0;
-    bool converged = false;
-    while (!converged && rounds < limit) {
-        const int nb = (int)std::min<int64_t>(batch, limit - rounds);
-        if (rounds) HIPCHK(h, hipMemsetAsync(cnt, 0, 2 * GVOM_CTG_MAX_BATCH * 4, h->stream));
-        for (int r = 0; r < nb; ++r) {
-            const int64_t k = rounds + r;
-            HIPCHK(h, gvom_launch_pose_relax(h->stream, xy, H, R, C, D, pstart, prims, fl + (k & 1) * ntiles, fl + ((k + 1) & 1) * ntiles,
-                                             cnt + r, cnt + CTG_CNT_RELAXED + r, cap, inner));
-        }
-        HIPCHK(h, hipMemcpyAsync(h->pf_pin, cnt, 2 * GVOM_CTG_MAX_BATCH * 4, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        int ran = nb;
-        for (int r = 0; r < nb; ++r) {
-            tiles += h->pf_pin[CTG_CNT_RELAXED + r];
-            if (h->pf_pin[r] == 0) { converged = true; ran = r + 1; break; }
-        }
-        rounds += ran;
-    }
-    HIPCHK(h, gvom_launch_pose_actions(h->stream, xy, H, C, D, pstart, prims, part_ptr<uint8_t>(set, 1), cnt + CTG_CNT_REACHED));
-    if ((rc = product_publish(h, set, product_id))) return rc;             // (`ready` goes in front of the counters' way back)
-    HIPCHK(h, hipMemcpyAsync(h->pf_pin, cnt, 256, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (!converged && max_rounds == 0) { set->id = *product_id = -1; h->err = "gvom_pose_field: the field did not settle"; return GVOM_ERR_HIP; }   // (nobody gets it)
-    h->pf_last_rounds = (int)std::min<int64_t>(rounds, INT32_MAX);
-    h->pf_last_tiles = (int)std::min<int64_t>(tiles, INT32_MAX);
-    if (info) { info[0] = converged ? 1 : 0; info[1] = rounds; info[2] = h->pf_pin[CTG_CNT_REACHED]; info[3] = h->pf_pin[CTG_CNT_SEEDED]; }
-    return GVOM_OK;
+    SolveRounds S;
+    rc = solve_rounds(h, G.cnt, G.fl, h->pf.pin, nt * nt, batch, limit, [&](int64_t, uint32_t *fin, uint32_t *fout, uint32_t *any, uint32_t *ran) {
+        return gvom_launch_pose_relax(h->stream, xy, H, R, C, D, pstart, prims, fin, fout, any, ran, cap, inner);
+    }, &S);
+    if (rc) return rc;
+    HIPCHK(h, gvom_launch_pose_actions(h->stream, xy, H, C, D, pstart, prims, part_ptr<uint8_t>(set, 1), G.cnt + CTG_CNT_REACHED));
+    return goal_solve_finish(h, fn, h->pf, set, product_id, S, max_rounds, info);
 }
 }  // extern "C"

@@ -255,6 +255,23 @@ def test_the_frontier_layout_under_sanitizers(tmp_path):
     assert "frontier layout host test ok" in run.stdout
 
 
+def test_the_solve_arithmetic_and_work_layouts_under_sanitizers(tmp_path):
+    """g-vom_amd/csrc/gvom_solvework.h: the look at a batch's counters, the batch lengths and the work buffers' layouts of every call
+    that waits (tests/solvework_host_test.cpp)"""
+    cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
+    if cxx is None:
+        pytest.skip("no host C++ compiler")
+    exe = str(tmp_path / "solvework_host_test")
+    src = os.path.join(ROOT, "tests", "solvework_host_test.cpp")
+    build = subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
+                            "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", src, "-o", exe],
+                           capture_output=True, text=True, timeout=300)
+    assert build.returncode == 0, build.stderr[-3000:]
+    run = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    assert run.returncode == 0, (run.stdout + run.stderr)[-3000:]
+    assert "solvework host test ok" in run.stdout
+
+
 def test_the_kernels_use_no_scratch_and_the_relaxation_fits_8_kb_of_lds():
     import gvom
     sys.path.insert(0, os.path.join(ROOT, "tools"))

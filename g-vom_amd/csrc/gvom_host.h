@@ -408,6 +408,17 @@ struct gvom_handle {
     // afr_allocs counts it and the entry point's product sets (gvom_get_tuning "atlas_frontier_allocations")
     SolveWork afr;
     int afr_allocs = 0;
+    // ATTITUDE VOLUMES (gvom_attitude_volume): av_tab = what k_volume_attitude_table makes of the footprint table and the chassis --
+    // (u - am, v) float64 pairs of every footprint cell, then at av_wcell_at bytes (a multiple of 256) per heading the wheels' cell offsets and the
+    // footprint's box, [H][12] int32 --, rebuilt by the first call after a gvom_footprint_set / gvom_chassis_set (fp_gen / at_gen count those; av_fp_gen
+    // / av_at_gen say which pair the table was made of; fp_total = the offsets of the footprint table).  av_ground = the ground map of
+    // the map-set route, av_stage = the staging copy of a caller's host ground map.  av_allocs counts the device allocations the entry
+    // point has made on this handle (the three and its product sets: gvom_get_tuning "attitude_volume_allocations")
+    Buf av_tab, av_ground, av_stage;
+    size_t av_wcell_at = 0;
+    uint64_t fp_gen = 0, at_gen = 0, av_fp_gen = 0, av_at_gen = 0;
+    int fp_total = 0;
+    int av_allocs = 0;
 };
 
 namespace gvom_host {

@@ -438,6 +438,22 @@ hipError_t gvom_launch_pose_relax(hipStream_t s, int xy, int H, int R, const uin
                                   int32_t max_cost, int inner);
 hipError_t gvom_launch_pose_actions(hipStream_t s, int xy, int H, const uint16_t *C, const int32_t *D, const int32_t *pstart,
                                     const int16_t *prims, uint8_t *action, uint32_t *reached);
+// attitude volumes (gvom_attitude_volume.hip; include/gvom_hip.h "attitude volumes" defines the result).  fstart / foffs, wheels and
+// cos_sin as above.  table: uv [total][2] float64 = (u - am, v) of every footprint cell and wcell [H][12] int32 = the wheels' four cell
+// offsets (dx, dy) and the footprint's box {least dx, largest dx, least dy, largest dy}, from the two tables.  volume: ground ONE [y][x] float64 map; status and tilt [H][y][x] uint8; counts [8] int32, words
+// 0 .. 6 CLEARED by the caller (added to), word 7 = H.  cspace_attitude: C [H][y][x] in place.
+struct AttitudeVolumeParams {
+    int xy, H;
+    double wheelbase, track, belly_height;             // front_axle - rear_axle, track, belly_height
+    float max_pitch, max_roll, min_clearance;
+};
+hipError_t gvom_launch_attitude_volume_table(hipStream_t s, int H, int total, double res, double axle_mid, const int32_t *fstart,
+                                             const uint32_t *foffs, const double *wheels, const double *cos_sin, double *uv, int32_t *wcell);
+hipError_t gvom_launch_attitude_volume(hipStream_t s, const AttitudeVolumeParams &P, const int32_t *fstart, const uint32_t *foffs,
+                                       const double *uv, const int32_t *wcell, const double *ground, uint8_t *status, uint8_t *tilt,
+                                       int32_t *counts);
+hipError_t gvom_launch_cspace_attitude(hipStream_t s, int xy, int H, const uint8_t *status, const uint8_t *tilt, uint32_t block_mask,
+                                       uint32_t tilt_weight, uint16_t *C);
 // map atlas (gvom_atlas.hip; include/gvom_hip.h "map atlas" defines the result).  The atlas is ten planes of A x A cells behind one
 // base address, A a power of two: the six f64 maps of a set (maps 3 .. 8) at k * A*A doubles, then the three i32 maps (0 .. 2) and
 // the int32 stamp at k * A*A ints; world cell (X, Y) at [(Y & (A-1)) * A + (X & (A-1))].  AtlasMaps = nine [y][x] maps of n x n cells

@@ -1,7 +1,7 @@
 // gvom_product_calls.hip -- the calls that MAKE a device product: gvom_device_product (occupancy grid, voxel cloud, the two height
 // clouds), gvom_clearance, gvom_raycast, gvom_cost_to_go, gvom_score_rollouts (with gvom_footprint_set, which sets its table),
-// gvom_score_attitude (with gvom_chassis_set), gvom_score_alignments, gvom_frontiers, gvom_score_viewpoints and gvom_pose_field (with
-// gvom_primitives_set), and the frame builders they and the debug reads (gvom_debug.hip) give the kernels.  Every call takes its set
+// gvom_score_attitude (with gvom_chassis_set), gvom_score_alignments, gvom_frontiers, gvom_score_viewpoints, gvom_pose_field / gvom_pose_field_attitude (with
+// gvom_primitives_set) and gvom_attitude_volume, and the frame builders they and the debug reads (gvom_debug.hip) give the kernels.  Every call takes its set
 // through product_acquire and hands it out through product_publish (gvom_sets.hip).  What several calls do alike stands once, in
 // front of the entry points, and serves the atlas calls (gvom_atlas_calls.hip) too: the argument checks (check_*, *_of), the staging
 // of host inputs (stage_host), the frames (metric_frame, rollout_frame) and, for the calls that wait, the round driver (solve_rounds;
@@ -521,6 +521,7 @@ VIS int gvom_footprint_set(gvom_t *h, int32_t n_headings, const int32_t *start, 
     HIPCHK(h, hipMemcpyAsync((char *)h->fp_tab.p + offs_at, offsets, ob, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     h->fp_offs_at = offs_at; h->fp_H = n_headings;
+    h->fp_total = start[n_headings]; ++h->fp_gen;                           // (gvom_attitude_volume rebuilds its table)
     return GVOM_OK;
 }
 
@@ -608,6 +609,7 @@ VIS int gvom_chassis_set(gvom_t *h, const gvom_chassis_t *c, int32_t n_headings,
     HIPCHK(h, hipMemcpyAsync(h->at_tab.p, tab.data(), cs_at + cb, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     h->at_cs_at = cs_at; h->at_H = n_headings; h->at_chassis = *c;
+    ++h->at_gen;                                                            // (gvom_attitude_volume rebuilds its table)
     return GVOM_OK;
 }
 
@@ -879,33 +881,41 @@ VIS int gvom_primitives_set(gvom_t *h, int32_t n_headings, const int32_t *start,
     return GVOM_OK;
 }
 
-VIS int gvom_pose_field(gvom_t *h, int64_t costfield_id, const int32_t *cost, int on_device, const int32_t *goals, int64_t n_goals,
-                        int32_t max_cost, int32_t max_rounds, int64_t *product_id, int64_t info[4])
+// the one host path of gvom_pose_field and gvom_pose_field_attitude (fn says which): with_volume = the second, whose volume_id names
+// the attitude volume k_cspace_attitude takes into the pose cost volume behind k_cspace
+static int pose_field_call(gvom_t *h, const char *fn, int64_t costfield_id, const int32_t *cost, int on_device, bool with_volume,
+                           int64_t volume_id, uint32_t block_mask, int32_t tilt_weight, const int32_t *goals, int64_t n_goals,
+                           int32_t max_cost, int32_t max_rounds, int64_t *product_id, int64_t info[4])
 {
     if (!h || !product_id) return GVOM_ERR_INVALID;
     std::lock_guard<std::mutex> lk(h->mu);
     *product_id = -1;
     for (int k = 0; info && k < 4; ++k) info[k] = 0;
-    const char *const fn = "gvom_pose_field";
     int rc;
     if (h->sharded) return refuse(h, fn, "sharded handles are not supported");
-    if (h->fp_H < 1) { h->err = "gvom_pose_field: no footprint table is set (gvom_footprint_set)"; return GVOM_ERR_INVALID; }
-    if (h->pf_H < 1) { h->err = "gvom_pose_field: no primitive table is set (gvom_primitives_set)"; return GVOM_ERR_INVALID; }
-    if (h->fp_H > GVOM_POSE_MAX_HEADINGS) { h->err = "gvom_pose_field: footprint tables of more than 64 headings are not supported"; return GVOM_ERR_CAPACITY; }
-    if (h->pf_H != h->fp_H) { h->err = "gvom_pose_field: the primitives were set for another number of headings than the footprint table has"; return GVOM_ERR_INVALID; }
+    if (h->fp_H < 1) return refuse(h, fn, "no footprint table is set (gvom_footprint_set)");
+    if (h->pf_H < 1) return refuse(h, fn, "no primitive table is set (gvom_primitives_set)");
+    if (h->fp_H > GVOM_POSE_MAX_HEADINGS) return refuse(h, fn, "footprint tables of more than 64 headings are not supported", GVOM_ERR_CAPACITY);
+    if (h->pf_H != h->fp_H) return refuse(h, fn, "the primitives were set for another number of headings than the footprint table has");
     if ((rc = check_one_source(h, fn, costfield_id >= 0, cost, !cost, "a cost field id", "a cost map", "a cost map"))) return rc;
     if ((rc = check_goals(h, fn, goals, n_goals, max_cost, max_rounds)) || (rc = check_side(h, fn))) return rc;
     const int xy = h->prm.xy_size, H = h->pf_H, R = h->pf_R;
     const size_t n2 = (size_t)xy * xy;
-    if ((int64_t)H * (int64_t)n2 > GVOM_POSE_MAX_STATES) { h->err = "gvom_pose_field: more than 2^28 states (headings x xy_size^2)"; return GVOM_ERR_CAPACITY; }
+    if ((int64_t)H * (int64_t)n2 > GVOM_POSE_MAX_STATES) return refuse(h, fn, "more than 2^28 states (headings x xy_size^2)", GVOM_ERR_CAPACITY);
     for (int64_t k = 0; k < n_goals; ++k) {
-        if (goals[3 * k] < 0 || goals[3 * k] >= xy || goals[3 * k + 1] < 0 || goals[3 * k + 1] >= xy) { h->err = "gvom_pose_field: a goal lies outside the window"; return GVOM_ERR_INVALID; }
-        if (goals[3 * k + 2] >= H) { h->err = "gvom_pose_field: a goal's heading is not one of the table's"; return GVOM_ERR_INVALID; }
+        if (goals[3 * k] < 0 || goals[3 * k] >= xy || goals[3 * k + 1] < 0 || goals[3 * k + 1] >= xy) return refuse(h, fn, "a goal lies outside the window");
+        if (goals[3 * k + 2] >= H) return refuse(h, fn, "a goal's heading is not one of the table's");
     }
-    DevSet *f = nullptr;
+    DevSet *f = nullptr, *vol = nullptr;
     if (costfield_id >= 0) {
         if ((rc = cost_field_of(h, fn, costfield_id, &f))) return rc;
     } else if (!on_device && (rc = check_host_cost(h, fn, cost, n2))) return rc;
+    if (with_volume) {
+        if (block_mask > 0x7fu) return refuse(h, fn, "block_mask outside 0 .. 0x7f");
+        if (tilt_weight < 0 || tilt_weight > 255) return refuse(h, fn, "tilt_weight outside 0 .. 255");
+        if ((rc = product_of_kind(h, fn, volume_id, GVOM_PRODUCT_ATTITUDE_VOLUME, "unknown or stale attitude volume id", &vol))) return rc;
+        if (vol->cap != H || vol->xy != xy) return refuse(h, fn, "the attitude volume was made for another number of headings or another window side");
+    }
     HIPCHK(h, hipSetDevice(h->device));
     DevSet *set = nullptr;
     const size_t bytes = set_bytes(GVOM_PRODUCT_POSEFIELD, xy, 0, H);
@@ -930,6 +940,8 @@ VIS int gvom_pose_field(gvom_t *h, int64_t costfield_id, const int32_t *cost, in
     const int16_t *prims = (const int16_t *)((char *)h->pf_tab.p + h->pf_prims_at);
     HIPCHK(h, gvom_launch_pose_seed(h->stream, 0, xy, H, R, (const int32_t *)cost32, c16w, C, D, G.fl, G.goals, (int)n_goals, G.cnt + CTG_CNT_SEEDED));
     HIPCHK(h, gvom_launch_cspace(h->stream, xy, H, c16, (const int32_t *)h->fp_tab.p, (const uint32_t *)((char *)h->fp_tab.p + h->fp_offs_at), C));
+    if (vol) HIPCHK(h, gvom_launch_cspace_attitude(h->stream, xy, H, part_ptr<const uint8_t>(vol, 0), part_ptr<const uint8_t>(vol, 1), block_mask,
+                                                   (uint32_t)tilt_weight, C));
     HIPCHK(h, gvom_launch_pose_seed(h->stream, 1, xy, H, R, (const int32_t *)cost32, c16w, C, D, G.fl, G.goals, (int)n_goals, G.cnt + CTG_CNT_SEEDED));
     const int32_t cap = max_cost == 0 ? GVOM_CTG_MAX_COST : max_cost;
     const int inner = h->pf.tune_inner > 0 ? h->pf.tune_inner : 64;
@@ -945,5 +957,86 @@ VIS int gvom_pose_field(gvom_t *h, int64_t costfield_id, const int32_t *cost, in
     if (rc) return rc;
     HIPCHK(h, gvom_launch_pose_actions(h->stream, xy, H, C, D, pstart, prims, part_ptr<uint8_t>(set, 1), G.cnt + CTG_CNT_REACHED));
     return goal_solve_finish(h, fn, h->pf, set, product_id, S, max_rounds, info);
+}
+
+VIS int gvom_pose_field(gvom_t *h, int64_t costfield_id, const int32_t *cost, int on_device, const int32_t *goals, int64_t n_goals,
+                        int32_t max_cost, int32_t max_rounds, int64_t *product_id, int64_t info[4])
+{
+    return pose_field_call(h, "gvom_pose_field", costfield_id, cost, on_device, false, -1, 0u, 0, goals, n_goals, max_cost, max_rounds, product_id, info);
+}
+
+VIS int gvom_pose_field_attitude(gvom_t *h, int64_t costfield_id, const int32_t *cost, int on_device, int64_t volume_id, uint32_t block_mask,
+                                 int32_t tilt_weight, const int32_t *goals, int64_t n_goals, int32_t max_cost, int32_t max_rounds,
+                                 int64_t *product_id, int64_t info[4])
+{
+    return pose_field_call(h, "gvom_pose_field_attitude", costfield_id, cost, on_device, true, volume_id, block_mask, tilt_weight, goals, n_goals,
+                           max_cost, max_rounds, product_id, info);
+}
+
+// ---- attitude volumes (gvom_attitude_volume) ----------------------------------------------------------------------------------------
+// The status and the tilt of terrain attitude scoring at every state (cell centre, heading) of the window, by k_volume_attitude
+// (gvom_attitude_volume.hip) against one float64 ground map with the footprint table and the chassis of the handle: a product of kind
+// GVOM_PRODUCT_ATTITUDE_VOLUME sized by H.  What depends on (heading, footprint cell) only -- and the wheels' cell offsets -- is a
+// table of the handle that the first call after a gvom_footprint_set / gvom_chassis_set rebuilds on the stream.  With a map set,
+// k_attitude_ground first writes the ground map into a grow-only buffer of the handle.  Enqueues and returns.
+VIS int gvom_attitude_volume(gvom_t *h, int64_t map_set_id, const double *ground, int on_device, int flags, int64_t *product_id)
+{
+    if (!h || !product_id) return GVOM_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(h->mu);
+    *product_id = -1;
+    const char *const fn = "gvom_attitude_volume";
+    int rc;
+    if (h->sharded) return refuse(h, fn, "sharded handles are not supported");
+    if (h->fp_H < 1) return refuse(h, fn, "no footprint table is set (gvom_footprint_set)");
+    if (h->at_H < 1) return refuse(h, fn, "no chassis is set (gvom_chassis_set)");
+    if (h->fp_H > GVOM_POSE_MAX_HEADINGS) return refuse(h, fn, "footprint tables of more than 64 headings are not supported", GVOM_ERR_CAPACITY);
+    if (h->at_H != h->fp_H) return refuse(h, fn, "the chassis was set for another number of headings than the footprint table has");
+    if (flags & ~GVOM_ATTITUDE_INFERRED_GROUND) return refuse(h, fn, "unknown flag bits");
+    if ((rc = check_one_source(h, fn, map_set_id >= 0, ground, !ground, "a map set id", "a ground map", "a ground map")) || (rc = check_side(h, fn))) return rc;
+    const int xy = h->prm.xy_size, H = h->fp_H;
+    const size_t n2 = (size_t)xy * xy;
+    if ((int64_t)H * (int64_t)n2 > GVOM_POSE_MAX_STATES) return refuse(h, fn, "more than 2^28 states (headings x xy_size^2)", GVOM_ERR_CAPACITY);
+    DevSet *m = nullptr;
+    if (map_set_id >= 0 && (rc = map_set_of(h, map_set_id, &m))) return rc;
+    HIPCHK(h, hipSetDevice(h->device));
+    DevSet *set = nullptr;
+    const size_t bytes = set_bytes(GVOM_PRODUCT_ATTITUDE_VOLUME, xy, 0, H);
+    if ((rc = product_acquire(h, GVOM_PRODUCT_ATTITUDE_VOLUME, bytes, bytes, fn, &h->av_allocs, &set))) return rc;
+    set->cap = H;
+    const gvom_chassis_t &c = h->at_chassis;
+    const size_t wcell_at = align256((size_t)h->fp_total * 16), tab_bytes = wcell_at + (size_t)H * 48;
+    const bool rebuild = h->av_fp_gen != h->fp_gen || h->av_at_gen != h->at_gen;
+    if (rebuild && h->av_tab.bytes < tab_bytes) HIPCHK(h, hipStreamSynchronize(h->stream));   // the kernels that read the table it outgrows
+    if (rebuild && (rc = stage_buf(h, h->av_tab, tab_bytes, h->av_allocs))) return rc;
+    if (m && (rc = stage_buf(h, h->av_ground, n2 * 8, h->av_allocs))) return rc;
+    const double *gdev = m ? (const double *)h->av_ground.p : ground;
+    HIPCHK(h, join_second_stream(h));
+    if (!m && !on_device) {                                                 // a host ground map: staged, and up before the call returns
+        const HostPart part = {ground, n2 * 8};
+        const void *dev;
+        if ((rc = stage_host(h, h->av_stage, h->av_allocs, &part, 1, true, &dev))) return rc;
+        gdev = (const double *)dev;
+    }
+    const int32_t *fstart = (const int32_t *)h->fp_tab.p;
+    const uint32_t *foffs = (const uint32_t *)((char *)h->fp_tab.p + h->fp_offs_at);
+    if (rebuild) {                                                          // on the handle's stream: behind whatever still reads the previous table
+        HIPCHK(h, gvom_launch_attitude_volume_table(h->stream, H, h->fp_total, h->prm.xy_resolution, 0.5 * (c.front_axle + c.rear_axle), fstart, foffs,
+                                                    (const double *)h->at_tab.p, (const double *)((char *)h->at_tab.p + h->at_cs_at),
+                                                    (double *)h->av_tab.p, (int32_t *)((char *)h->av_tab.p + wcell_at)));
+        h->av_wcell_at = wcell_at; h->av_fp_gen = h->fp_gen; h->av_at_gen = h->at_gen;
+    }
+    if ((rc = set_wait_releases(h, set))) return rc;
+    if (m) HIPCHK(h, gvom_launch_attitude_ground(h->stream, xy, (flags & GVOM_ATTITUDE_INFERRED_GROUND) ? 1 : 0, part_ptr<const double>(m, 4),
+                                                part_ptr<const double>(m, 5), (double *)h->av_ground.p));
+    AttitudeVolumeParams P;
+    memset(&P, 0, sizeof P);
+    P.xy = xy; P.H = H;
+    P.wheelbase = c.front_axle - c.rear_axle; P.track = c.track; P.belly_height = c.belly_height;
+    P.max_pitch = c.max_pitch; P.max_roll = c.max_roll; P.min_clearance = c.min_clearance;
+    int32_t *counts = part_ptr<int32_t>(set, 2);
+    HIPCHK(h, hipMemsetAsync(counts, 0, 32, h->stream));
+    HIPCHK(h, gvom_launch_attitude_volume(h->stream, P, fstart, foffs, (const double *)h->av_tab.p, (const int32_t *)((char *)h->av_tab.p + h->av_wcell_at),
+                                          gdev, part_ptr<uint8_t>(set, 0), part_ptr<uint8_t>(set, 1), counts));
+    return product_publish(h, set, product_id);
 }
 }  // extern "C"

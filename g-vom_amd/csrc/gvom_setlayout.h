@@ -37,6 +37,9 @@
 //   atlas frontiers (28)  the four parts of frontiers (16) with the window's side replaced by cols = the side of the atlas FIELD the call
 //                    was given: cap x 8 int32, cap x 2 int64, cols*cols int32 (the cluster map, [y][x] over the field's extent), 4 int32;
 //                    cap = max_clusters of the call that wrote it.  Kind 27 is not assigned
+//   attitude volume (30)  cap x xy*xy uint8 (status), then cap x xy*xy uint8 (tilt): volumes [h][y][x], every plane laid out like a pose
+//                    field's; then 8 int32 {states per status 0 .. 6, H}; cap = the headings H of the call that wrote it.  Kind 29 is
+//                    not assigned
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -82,6 +85,7 @@ inline size_t set_bytes(int kind, int xy, int zs, int64_t cap, int64_t cols = 0)
     case GVOM_PRODUCT_ATLAS_EXTENT: return (size_t)cap * (size_t)cap * 32;
     case GVOM_PRODUCT_ATLAS_FIELD: return align256((size_t)cap * (size_t)cap * 4) + align256((size_t)cap * (size_t)cap) + (size_t)cap * (size_t)cap * 2;
     case GVOM_PRODUCT_ATLAS_FRONTIERS: return align256((size_t)cap * 32) + align256((size_t)cap * 16) + align256((size_t)cols * (size_t)cols * 4) + 16;
+    case GVOM_PRODUCT_ATTITUDE_VOLUME: return 2 * align256((size_t)cap * n2) + 32;
     }
     return 0;
 }
@@ -203,6 +207,17 @@ inline bool set_part(const SetShape *s, int part, SetPart *d)
         d->ptr = s->mem + (part ? align256(a2 * 4) : 0) + (part == 2 ? align256(a2) : 0);
         d->shape[0] = d->shape[1] = s->cap; d->strides[0] = 1; d->strides[1] = s->cap;
         d->code = part ? kDLUInt : kDLInt; d->bits = part == 0 ? 32 : (part == 1 ? 8 : 16);
+        break;
+    }
+    case GVOM_PRODUCT_ATTITUDE_VOLUME: {                   // parts 0 and 1 [h, x, y] indexing: every plane column-major, like a pose field's
+        if (part < 0 || part > 2) return false;
+        const size_t vol = (size_t)s->cap * (size_t)n2;
+        d->ptr = s->mem + (size_t)part * align256(vol);
+        if (part == 2) { d->ndim = 1; d->shape[0] = 8; d->strides[0] = 1; d->shape[1] = d->strides[1] = 1; d->code = kDLInt; break; }
+        d->ndim = 3;
+        d->shape[0] = s->cap; d->shape[1] = d->shape[2] = xy;
+        d->strides[0] = n2; d->strides[1] = 1; d->strides[2] = xy;
+        d->code = kDLUInt; d->bits = 8;
         break;
     }
     default: return false;

@@ -171,6 +171,9 @@ ABI = [
     ("gvom_score_viewpoints", _I, [_P, _P, _I64, _I, ctypes.c_double, ctypes.c_int32, ctypes.c_int32, _I, _P, ctypes.POINTER(_I64)]),
     ("gvom_primitives_set", _I, [_P, ctypes.c_int32, _P, _P]),
     ("gvom_pose_field", _I, [_P, _I64, _P, _I, _P, _I64, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(_I64), ctypes.POINTER(_I64)]),
+    ("gvom_attitude_volume", _I, [_P, _I64, _P, _I, _I, ctypes.POINTER(_I64)]),
+    ("gvom_pose_field_attitude", _I, [_P, _I64, _P, _I, _I64, ctypes.c_uint32, ctypes.c_int32, _P, _I64, ctypes.c_int32, ctypes.c_int32,
+                                      ctypes.POINTER(_I64), ctypes.POINTER(_I64)]),
     ("gvom_device_map_origin", _I, [_P, _I64, ctypes.POINTER(_I64)]),
     ("gvom_atlas_configure", _I, [_P, ctypes.c_int32, _I, ctypes.POINTER(_I64)]),
     ("gvom_atlas_integrate", _I, [_P, _I64, ctypes.POINTER(_P), _I, ctypes.POINTER(_I64)]),
@@ -565,6 +568,14 @@ class DeviceMaps(_Export):
         a = _rollout_poses(poses)
         return g._score_attitude(self.set_id, None, _ptr(a), a.shape[0], a.shape[1], 0, bool(inferred_ground), self.origin)
 
+    def attitude_volume(self, inferred_ground=True):
+        """How the vehicle would sit on this set's ground at EVERY state of the window -- the centre of each cell at each heading of
+        the mapper's footprint table, with its chassis (Gvom.set_footprint, Gvom.set_chassis) -- a DeviceAttitudeVolume (status and
+        tilt per state), computed on the GPU behind the combine that wrote the set; no host wait.  The ground is score_attitude()'s.
+        DeviceCostField.pose_field(attitude=...) takes it into a pose field.  include/gvom_hip.h "attitude volumes" has the
+        definition."""
+        return self._owner._attitude_volume(self.set_id, None, 0, bool(inferred_ground))
+
     def cost_to_go(self, goals, goals_in_cells=False, inflation_radius=None, density_threshold=50, include_negative=True,
                    unknown="free", base=1, soft_weight=0, rough_weight=0, roughness_range=None, max_cost=None, max_rounds=0):
         """The navigation function of this set's maps towards `goals`: from every cell the cheapest 8-connected way to a goal
@@ -600,6 +611,8 @@ PRODUCT_ATLAS_RECALL = 22                 # GVOM_PRODUCT_ATLAS_RECALL: made by g
 PRODUCT_ATLAS_EXTENT = 24                 # GVOM_PRODUCT_ATLAS_EXTENT: made by gvom_atlas_extent (kind 23 is not assigned)
 PRODUCT_ATLAS_FIELD = 26                  # GVOM_PRODUCT_ATLAS_FIELD: made by gvom_atlas_cost_to_go (kind 25 is not assigned)
 PRODUCT_ATLAS_FRONTIERS = 28              # GVOM_PRODUCT_ATLAS_FRONTIERS: made by gvom_atlas_frontiers (kind 27 is not assigned)
+_ATTITUDE_BLOCKS = (1, 2, 3)              # (ATTITUDE_PITCH, ATTITUDE_ROLL, ATTITUDE_BELLY): the statuses a pose field blocks by default
+PRODUCT_ATTITUDE_VOLUME = 30              # GVOM_PRODUCT_ATTITUDE_VOLUME: made by gvom_attitude_volume (kind 29 is not assigned)
 # element type of part k of a product, by kind (what set_part() of csrc/gvom_setlayout.h gives as DLPack code and bits)
 _PRODUCT_DTYPES = {PRODUCT_OCCUPANCY: (np.uint8,), PRODUCT_VOXEL_CLOUD: (np.float32, np.float32, np.int64),
                    PRODUCT_HEIGHT_CLOUD: (np.float32,), PRODUCT_INFERRED_HEIGHT_CLOUD: (np.float32,),
@@ -610,7 +623,8 @@ _PRODUCT_DTYPES = {PRODUCT_OCCUPANCY: (np.uint8,), PRODUCT_VOXEL_CLOUD: (np.floa
                    PRODUCT_POSEFIELD: (np.int32, np.uint8, np.uint16), PRODUCT_ATLAS_RECALL: (np.int32, np.int32),
                    PRODUCT_ATLAS_EXTENT: (np.int32, np.int32, np.int32, np.float64, np.float64, np.int32),
                    PRODUCT_ATLAS_FIELD: (np.int32, np.uint8, np.uint16),
-                   PRODUCT_ATLAS_FRONTIERS: (np.int32, np.int64, np.int32, np.int32)}
+                   PRODUCT_ATLAS_FRONTIERS: (np.int32, np.int64, np.int32, np.int32),
+                   PRODUCT_ATTITUDE_VOLUME: (np.uint8, np.uint8, np.int32)}
 CLEARANCE_FAR = 2147483647                # GVOM_CLEARANCE_FAR: squared_cells where no obstacle is in reach
 _CLEARANCE_NO_NEGATIVE = 1                # GVOM_CLEARANCE_NO_NEGATIVE
 
@@ -898,19 +912,22 @@ class DeviceCostField(_ProductView):
     def copy_to_host(self):
         return self.cost.copy_to_host(), self.direction.copy_to_host(), self.cell_cost.copy_to_host()
 
-    def pose_field(self, goals, goals_in_cells=False, max_cost=None, max_rounds=0):
+    def pose_field(self, goals, goals_in_cells=False, max_cost=None, max_rounds=0, attitude=None, attitude_blocks=_ATTITUDE_BLOCKS, tilt_weight=0):
         """The heading-aware navigation function of this field's `.cell_cost` under the mapper's footprint table (Gvom.set_footprint;
         build THIS field without inflation: the footprint does that, per heading) and primitive table (Gvom.set_primitives): from
         every state (x, y, heading) the cheapest drive to a goal state that the primitives allow -- a DevicePoseField, computed on the
         GPU behind the solve that wrote this field.  The call waits for it.  goals: (G, 2) = (x, y) seeds every heading of the cell,
         (G, 3) = (x, y, yaw) only the heading rint(yaw * H / 2 pi) mod H (float32, the rollouts' rule); world metres -- or window
         cells with goals_in_cells=True; the yaw is radians either way.  A goal outside the window raises ValueError; a goal state
-        the footprint blocks seeds nothing.  max_cost, max_rounds: as cost_to_go().  include/gvom_hip.h "pose fields" has the
-        definition."""
+        the footprint blocks seeds nothing.  max_cost, max_rounds: as cost_to_go().  attitude: a DeviceAttitudeVolume of the same
+        headings and window -- a state whose status is one of attitude_blocks (ATTITUDE_* codes) is
+        blocked, every other state costs tilt_weight (0 .. 255) times its tilt more, at most 65535; without one
+        the field is what it always was.  include/gvom_hip.h "pose fields" and "attitude volumes" have the definition."""
         g = self._hold._owner
         H = g._pose_headings()
         cells = _pose_goals(goals, g.xy_size, H, None if goals_in_cells else (g.xy_resolution, self.origin))
-        return g._pose_field(self.product_id, None, 0, cells, _ctg_max_cost(max_cost), _ctg_max_rounds(max_rounds), self.origin)
+        return g._pose_field(self.product_id, None, 0, cells, _ctg_max_cost(max_cost), _ctg_max_rounds(max_rounds), self.origin,
+                             _pose_attitude(attitude, attitude_blocks, tilt_weight))
 
     def frontiers(self, device_maps, min_cells=4, max_clusters=1024):
         """Where to explore next: the cells of this field that can be driven on (`.cell_cost` > 0), have been seen (`visibility` of
@@ -1188,6 +1205,64 @@ class DeviceAttitude(_ProductView):
 
     def copy_to_host(self):
         return self.summary.copy_to_host(), self.attitude.copy_to_host(), self.status.copy_to_host()
+
+
+class _AttitudePlanes(DeviceArray):
+    """One [H, xy, xy] uint8 volume of an attitude volume, indexed [h, x, y] with strides (xy*xy, 1, xy) like a pose field's volumes.
+    copy_to_host() returns numpy of the same indexing (a transposed view of the [h][y][x] copy)."""
+
+    def copy_to_host(self):
+        g = self._hold._owner
+        raw = np.empty((self.shape[0], self.shape[2], self.shape[1]), self.dtype)
+        g._check(g._lib.gvom_device_product_copy(g._h, self.product_id, self._part, ctypes.c_void_p(raw.ctypes.data)))
+        return raw.transpose(0, 2, 1)
+
+
+class DeviceAttitudeVolume(_ProductView):
+    """The result of DeviceMaps.attitude_volume() / Gvom.attitude_volume_of() / attitude_volume_of_device(): `.status` uint8
+    [H, xy, xy] -- ATTITUDE_* of the vehicle standing in the centre of cell (x, y) at heading h -- and `.tilt` uint8 [H, xy, xy] -- how
+    much of the nearer of the pitch and the roll limit the state uses, 0 .. 100 percent (0 on unknown ground and outside the window)
+    --, both indexed [h, x, y], and `.counts` int32 [8]: the states per status code 0 .. 6, then H.  Three DeviceArrays of one
+    product; `__dlpack__` hands out `.status`.  A snapshot: later scans, combines, set_footprint and set_chassis calls do not change
+    it.  copy_to_host() returns (status, tilt, counts) as numpy."""
+
+    def __init__(self, hold):
+        _ProductView.__init__(self, hold)
+        self.status, self.tilt, self.counts = _AttitudePlanes(hold, 0), _AttitudePlanes(hold, 1), DeviceArray(hold, 2)
+
+    def copy_to_host(self):
+        return self.status.copy_to_host(), self.tilt.copy_to_host(), self.counts.copy_to_host()
+
+    def __dlpack_device__(self):
+        return self.status.__dlpack_device__()
+
+    def __dlpack__(self, stream=None, max_version=None, dl_device=None, copy=None):
+        return self.status.__dlpack__(stream=stream, max_version=max_version, dl_device=dl_device, copy=copy)
+
+
+def _pose_attitude(attitude, attitude_blocks, tilt_weight):
+    """the attitude keywords of the pose_field calls -> None, or (the volume's product id, block mask, tilt weight)"""
+    if attitude is None:
+        if tilt_weight != 0:
+            raise ValueError("tilt_weight needs an attitude volume (attitude=...)")
+        return None
+    if not isinstance(attitude, DeviceAttitudeVolume):
+        raise TypeError("attitude must be a DeviceAttitudeVolume (DeviceMaps.attitude_volume()), got %r" % (type(attitude).__name__,))
+    mask = 0
+    try:
+        for b in attitude_blocks:
+            if isinstance(b, bool) or int(b) != b or not 0 <= int(b) <= 6:
+                raise ValueError
+            mask |= 1 << int(b)
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError("attitude_blocks must be a sequence of ATTITUDE_* codes 0 .. 6, got %r" % (attitude_blocks,))
+    try:
+        ok = not isinstance(tilt_weight, bool) and int(tilt_weight) == tilt_weight and 0 <= int(tilt_weight) <= 255
+    except (TypeError, ValueError, OverflowError):
+        ok = False
+    if not ok:
+        raise ValueError("tilt_weight must be an integer in 0 .. 255, got %r" % (tilt_weight,))
+    return attitude.product_id, mask, int(tilt_weight)
 
 
 # ---- frontier extraction (DeviceCostField.frontiers, Gvom.frontiers_of and friends; include/gvom_hip.h "frontier extraction") ----
@@ -2739,6 +2814,26 @@ class Gvom(object):
         K, T = _rollout_shape(K, T)
         return self._score_attitude(-1, _dev(ground_ptr), _dev(poses_ptr), K, T, 1, False, origin)
 
+    # ---- attitude volumes (an extension; include/gvom_hip.h "attitude volumes") ----
+    def _attitude_volume(self, set_id, ground_ptr, on_device, inferred_ground):
+        flags = _ATTITUDE_INFERRED_GROUND if inferred_ground else 0
+        return DeviceAttitudeVolume(self._make_product(lambda pid: self._lib.gvom_attitude_volume(
+            self._h, int(set_id), ground_ptr, int(on_device), flags, pid), PRODUCT_ATTITUDE_VOLUME, self._check_args))
+
+    def attitude_volume_of(self, ground):
+        """DeviceMaps.attitude_volume() of a ground map of the caller's: a numpy [x, y] array of shape (xy_size, xy_size) in any
+        memory order, heights in metres cast to float64 as they are (NaN, infinities and values <= -1000 are unknown ground).  Needs
+        no scan and no combine.  A convenience route: the map is copied to the device."""
+        gm = self._window_map("ground", ground, np.float64)
+        return self._attitude_volume(-1, _ptr(gm), 0, False)
+
+    def attitude_volume_of_device(self, ground_ptr):
+        """The same for a map in device memory: the raw device address of xy_size*xy_size float64 (cell (x, y) at [y*xy_size + x]);
+        the data must be ready when the call is made.  Enqueues and returns: no host wait."""
+        if not ground_ptr:
+            raise ValueError("ground_ptr must be a device address")
+        return self._attitude_volume(-1, _dev(ground_ptr), 1, False)
+
     # ---- frontier extraction (an extension; include/gvom_hip.h "frontier extraction") ----
     def _frontiers(self, field_id, set_id, cost_ptr, ctg_ptr, vis_ptr, on_device, min_cells, max_clusters, origin):
         min_cells, max_clusters = _frontier_limits(min_cells, max_clusters)
@@ -2808,31 +2903,40 @@ class Gvom(object):
             raise ValueError("no primitive table is set (Gvom.set_primitives)")
         return self._primitives[0].shape[0] - 1
 
-    def _pose_field(self, field_id, cost_ptr, on_device, cells, max_cost, max_rounds, origin):
+    def _pose_field(self, field_id, cost_ptr, on_device, cells, max_cost, max_rounds, origin, attitude=None):
         info = (_I64 * 4)()
         table = self._primitives
-        hold = self._make_product(lambda pid: self._lib.gvom_pose_field(
-            self._h, int(field_id), cost_ptr, int(on_device), _ptr(cells), cells.shape[0], max_cost, max_rounds, pid, info),
-            PRODUCT_POSEFIELD, self._check_args)
+        if attitude is None:
+            call = lambda pid: self._lib.gvom_pose_field(
+                self._h, int(field_id), cost_ptr, int(on_device), _ptr(cells), cells.shape[0], max_cost, max_rounds, pid, info)
+        else:
+            call = lambda pid: self._lib.gvom_pose_field_attitude(
+                self._h, int(field_id), cost_ptr, int(on_device), attitude[0], attitude[1], attitude[2], _ptr(cells), cells.shape[0],
+                max_cost, max_rounds, pid, info)
+        hold = self._make_product(call, PRODUCT_POSEFIELD, self._check_args)
         return DevicePoseField(hold, list(info), origin, table)
 
-    def pose_field_of(self, cost, goals, max_cost=None, max_rounds=0, origin=(0.0, 0.0)):
+    def pose_field_of(self, cost, goals, max_cost=None, max_rounds=0, origin=(0.0, 0.0), attitude=None, attitude_blocks=_ATTITUDE_BLOCKS, tilt_weight=0):
         """DeviceCostField.pose_field() of a cost map of the caller's: a numpy [x, y] array of shape (xy_size, xy_size) in any memory
         order, integers in 0 .. 65535 (0 = blocked); goals: (G, 2) or (G, 3) = (x, y[, yaw]) in window cells and radians.  Needs no
-        scan and no combine.  A convenience route: the map is copied to the device.  origin: kept as the field's `.origin`."""
+        scan and no combine.  A convenience route: the map is copied to the device.  origin: kept as the field's `.origin`.
+        attitude, attitude_blocks, tilt_weight: as DeviceCostField.pose_field()."""
         H = self._pose_headings()
         c = self._window_map("cost", np.asarray(cost), np.int32, (0, 65535), range_note=" (0 = blocked)")
         cells = _pose_goals(goals, self.xy_size, H, None)
-        return self._pose_field(-1, _ptr(c), 0, cells, _ctg_max_cost(max_cost), _ctg_max_rounds(max_rounds), origin)
+        return self._pose_field(-1, _ptr(c), 0, cells, _ctg_max_cost(max_cost), _ctg_max_rounds(max_rounds), origin,
+                                _pose_attitude(attitude, attitude_blocks, tilt_weight))
 
-    def pose_field_of_device(self, cost_ptr, goals, max_cost=None, max_rounds=0, origin=(0.0, 0.0)):
+    def pose_field_of_device(self, cost_ptr, goals, max_cost=None, max_rounds=0, origin=(0.0, 0.0), attitude=None, attitude_blocks=_ATTITUDE_BLOCKS,
+                             tilt_weight=0):
         """The same for a cost map in device memory (the raw device address of xy_size*xy_size int32, cell (x, y) at
         [y*xy_size + x]; the data must be ready when the call is made).  Values outside 0 .. 65535 are clamped into the range."""
         if not cost_ptr:
             raise ValueError("cost_ptr must be a device address")
         H = self._pose_headings()
         cells = _pose_goals(goals, self.xy_size, H, None)
-        return self._pose_field(-1, _dev(cost_ptr), 1, cells, _ctg_max_cost(max_cost), _ctg_max_rounds(max_rounds), origin)
+        return self._pose_field(-1, _dev(cost_ptr), 1, cells, _ctg_max_cost(max_cost), _ctg_max_rounds(max_rounds), origin,
+                                _pose_attitude(attitude, attitude_blocks, tilt_weight))
 
     # ---- map atlas (an extension; include/gvom_hip.h "map atlas") ----
     def create_atlas(self, cells, follow=True, origin_cells=None):

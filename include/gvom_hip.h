@@ -904,6 +904,59 @@ int gvom_primitives_set(gvom_t *h, int32_t n_headings, const int32_t *start /* [
 int gvom_pose_field(gvom_t *h, int64_t costfield_id, const int32_t *cost, int on_device, const int32_t *goals /* [n_goals][3] */,
                     int64_t n_goals, int32_t max_cost, int32_t max_rounds, int64_t *product_id, int64_t info[4]);
 
+/* --- attitude volumes (an extension: pitch, roll and belly limits per heading, for the pose field -- a side slope the vehicle can climb
+ * nose-first but would roll over on when crossing it is open in one heading and closed in another) ------------------------------------
+ * gvom_attitude_volume computes, on the GPU, how the vehicle would sit on ONE float64 ground map at EVERY state of the window -- the
+ * centre of each cell at each of the H headings of the footprint table -- with the footprint table gvom_footprint_set and the chassis
+ * gvom_chassis_set gave the handle, and leaves the status and the tilt of every state in device memory as a product (kind
+ * GVOM_PRODUCT_ATTITUDE_VOLUME) that gvom_device_product_export / _release / _dlpack / _copy handle like the others.
+ * gvom_pose_field_attitude is gvom_pose_field with such a volume taken into its pose cost volume.  gvom_get_tuning "attitude_volume"
+ * (read-only): 1 -- how a caller probes a library for the two entry points (an addition: GVOM_ABI_VERSION stays).
+ *
+ * DEFINITION.  The arithmetic is "terrain attitude scoring" above, word for word, for a pose that lies exactly in the centre of window
+ * cell (cx, cy) with heading h, written relative to the window: the result does not depend on the window's origin.  All float64, one
+ * IEEE operation each in the order written, no contraction.
+ * GROUND     that section's, from a map set (map_set_id >= 0, flags GVOM_ATTITUDE_INFERRED_GROUND or 0) or the caller's (host or
+ *            device memory as on_device says).
+ * WHEEL CELL wheel i of heading h stands in cell (cx + floor(0.5 + wx[h][i] / res), cy + floor(0.5 + wy[h][i] / res)), wx and wy the
+ *            wheel table of gvom_chassis_set.  A cell outside [0, xy) is outside the window.  z_i = g at that cell.
+ * ATTITUDE, BELLY   zF, zR, zL, zT, sp, sr, z0, am, du, dv, u, v, plane, clr and belly are that section's formulas with fx = fy = 0.5;
+ *            KNOWN is its rule.
+ * STATUS     the first that applies: GVOM_ATTITUDE_LEFT_WINDOW: a wheel cell or a footprint cell is outside the window;
+ *            _UNKNOWN_GROUND: a wheel cell's ground is unknown; _PITCH, _ROLL, _BELLY: decided on (float)sp, (float)sr, (float)belly
+ *            against the float32 limits as there; _OK.  GVOM_ATTITUDE_INVALID cannot occur.
+ * TILT       uint8.  0 where the status is UNKNOWN_GROUND or LEFT_WINDOW.  Elsewhere tp = (double)fabsf((float)sp) / (double)max_pitch
+ *            * 100.0 if max_pitch is finite, else 0; tr likewise from the roll; t = tp > tr ? tp : tr;
+ *            tilt = !(t > 0) ? 0 : (t >= 100 ? 100 : (uint8)floor(t)): how much of the nearer limit the state uses, in percent.
+ * part 0 = uint8 status, part 1 = uint8 tilt: [H, xy, xy], indexed [h, x, y], strides (xy*xy, 1, xy) -- every plane has a pose field
+ * plane's layout.  part 2 = int32 [8]: the number of states per status code 0 .. 6, then H.
+ *
+ * gvom_attitude_volume: on_device and the staging of a host ground map are gvom_score_attitude's; the call is enqueued on the handle's
+ * stream and returns without a host wait (after the upload of a host map).  What depends on (heading, footprint cell) only is kept in a
+ * table in device memory that the FIRST call after a gvom_footprint_set / gvom_chassis_set rebuilds on the stream (those two calls
+ * allocate nothing for it).  The product is a snapshot: later scans, combines, gvom_footprint_set and gvom_chassis_set calls do not
+ * change it.  Products of this kind live in the product-set pool ("device_product_sets"), sized by H and xy_size: at most
+ * GVOM_MAX_PRODUCT_SETS; an unexported one goes back to the pool with the next gvom_attitude_volume call.
+ * "attitude_volume_allocations" (read-only): device allocations the entry point has made on this handle (the table, the ground map of
+ * the map-set route, the staging buffer of the host route and its product sets); it does not grow in steady state.
+ * gvom_device_product(GVOM_PRODUCT_ATTITUDE_VOLUME) is GVOM_ERR_INVALID (this call makes them).  Kind 29 is not assigned.
+ * GVOM_ERR_INVALID: a sharded handle; no footprint table set, no chassis set, or a chassis whose n_headings is not the table's; a set
+ * id AND a ground pointer, or neither; an unknown or stale set id; unknown flag bits; NULL product_id.  GVOM_ERR_CAPACITY: H > 64;
+ * xy_size > 4096; H * xy_size^2 > 2^28; every set of the kind exported.
+ *
+ * gvom_pose_field_attitude is gvom_pose_field -- the same arguments, checks, codes, product, info, tuning names and pool -- with
+ * volume_id naming a live GVOM_PRODUCT_ATTITUDE_VOLUME of the same H and xy_size, read on the handle's stream behind the call that
+ * wrote it.  Behind the pose cost volume C of "pose fields", C'[h][cell] = 0 where C == 0 or bit `status` of block_mask is set
+ * (bit k = status code k), otherwise C' = min(65535, C + tilt_weight * tilt); seeding, relaxation, actions and part 2 of the product
+ * take C' for C.  In addition GVOM_ERR_INVALID: block_mask > 0x7f; tilt_weight outside 0 .. 255; a stale volume id, an id of
+ * another kind, or a volume of another H or xy_size.
+ * NOT PROVIDED: float32 pitch / roll / belly volumes; states between cell centres; volumes over the atlas; sharded handles. */
+#define GVOM_PRODUCT_ATTITUDE_VOLUME 30   /* part 0 uint8 status, part 1 uint8 tilt: [H, xy, xy], strides (xy*xy, 1, xy); part 2 int32 [8]; kind 29 stays unassigned */
+int gvom_attitude_volume(gvom_t *h, int64_t map_set_id, const double *ground, int on_device, int flags, int64_t *product_id);
+int gvom_pose_field_attitude(gvom_t *h, int64_t costfield_id, const int32_t *cost, int on_device, int64_t volume_id, uint32_t block_mask,
+                             int32_t tilt_weight, const int32_t *goals /* [n_goals][3] */, int64_t n_goals, int32_t max_cost,
+                             int32_t max_rounds, int64_t *product_id, int64_t info[4]);
+
 /* --- map atlas (an extension: a world-fixed memory of the 2-D maps beyond the rolling window -- what the vehicle drove over a minute
  * ago is still known when it has to plan a way back) ------------------------------------------------------------------------------------
  * The atlas is a larger, toroidally stored copy of the nine maps of a map set plus a last-written stamp, in device memory, one per
@@ -1319,6 +1372,7 @@ int gvom_host_timing(gvom_t *h, double us[8]);
  * (read-only, gvom_get_tuning): see "scan alignment scoring" above.
  * "viewpoints" / "viewpoint_allocations" / "viewpoint_batch" (read-only, gvom_get_tuning), "viewpoint_bitmap_mb": see "viewpoint
  * scoring" above.
+ * "attitude_volume" / "attitude_volume_allocations" (read-only, gvom_get_tuning): see "attitude volumes" above.
  * (Test hooks are not part of this library: include/gvom_hip_test.h, lib/libgvom_hip_test.so.) */
 int gvom_set_tuning(gvom_t *h, const char *name, int value);
 /* The value the LAST scan ran with ("segs", "period", "ep_row", "prio", "interleave": what automatic resolved to).

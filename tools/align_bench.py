@@ -17,10 +17,8 @@ and the ray query alone.  Everything goes into ONE file, profiles/align_<lib sha
                        --parent LIB (the parent commit's libgvom_hip.so), the same step without a query on that library,
                        alternating with this one
 
-    tools/align_bench.py [--resources [--parent REV]] [--parent LIB] [out.json]
+    tools/align_bench.py [--resources [--parent REV]] [--parent LIB] [--configs m256,c4] [--turns N] [out.json]
 """
-import csv
-import glob
 import json
 import os
 import subprocess
@@ -28,24 +26,22 @@ import sys
 import tempfile
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import benchkit as bk
+
+ROOT = bk.ROOT
 PKG = os.path.join(ROOT, "g-vom_amd")
-sys.path.insert(0, PKG)
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-CONFIGS = (("m256", 400), ("c4", 100))                     # (config, timed steps per repetition)
+CONFIGS = {"m256": 400, "c4": 100}                         # config: timed steps per repetition
+TURNS = 2
+CHILD_TIMEOUT = 900                                        # seconds, per child process
+KERNELS = ("k_align_field", "k_align_score", "k_align_best")
 SHAPES = ((4096, 16384), (9261, 4096))                     # (K, n)
 STEP_SHAPE = (9261, 4096)
 TORCH_WEIGHTS = (3, 0, -1, -1, 0)                          # free and unknown weigh the same: what an occupancy grid can tell
 TORCH_CHUNK = 128                                          # candidates per chunk of the torch form
 
 
-def _median(v):
-    v = sorted(v)
-    return v[len(v) // 2] if len(v) % 2 else 0.5 * (v[len(v) // 2 - 1] + v[len(v) // 2])
-
-
 # ---- resources (CPU) ---------------------------------------------------------------------------------------------------------
-def resources(parent):
+def compiled_resources(parent):
     import raycast_bench as rb
     units = ("gvom_trace.hip", "gvom_query.hip")
     before = {}
@@ -66,29 +62,12 @@ def resources(parent):
 
 
 # ---- timing (GPU) ------------------------------------------------------------------------------------------------------------
-def _gvom():
-    """The binding, also over the parent's library: it is bound with the entry points it has."""
-    import ctypes
-    import gvom
-    lib = ctypes.CDLL(gvom.library_path())
-    gvom.ABI = [e for e in gvom.ABI if hasattr(lib, e[0])]
-    return gvom
-
-
 def _setup(name):
-    import numpy as np
-    import torch
-    import synth
-    torch.cuda.init()
-    gvom = _gvom()
-    params, scans = synth.config_inputs(name, n_scans=3)
-    dev = [(torch.from_numpy(np.ascontiguousarray(pc)).cuda(), ego, tf) for pc, ego, tf in scans]
-    torch.cuda.synchronize()
-    g = gvom.Gvom(*params, voxel_statistics=False)
-    for t, ego, tf in dev:
-        g.process_pointcloud_device(t.data_ptr(), t.shape[0], np.float32, ego, tf)
-        g.combine_maps_device().release()
-    return np, torch, gvom, g, dev, scans
+    """bk.setup() with the three scans fused, and the scans once more as host arrays"""
+    np, torch, gvom, g, dev = bk.setup(name)
+    for scan in dev:
+        bk.scan_combine(np, g, scan).release()
+    return np, torch, gvom, g, dev, [(t.cpu().numpy(), ego, tf) for t, ego, tf in dev]
 
 
 def _inputs(np, torch, gvom, g, scans, K, n):
@@ -158,15 +137,15 @@ def child_call(name):
                                  ("torch_us", lambda: _torch_score(torch, g, tc, tm, TORCH_WEIGHTS), 2)):
             for _ in range(2):
                 fn()
-            g._check(g._lib.gvom_sync(g._h)); torch.cuda.synchronize()
+            bk.sync(g); torch.cuda.synchronize()
             us = []
             for _ in range(5):
                 t0 = time.perf_counter()
                 for _ in range(calls):
                     fn()
-                g._check(g._lib.gvom_sync(g._h)); torch.cuda.synchronize()
+                bk.sync(g); torch.cuda.synchronize()
                 us.append(round((time.perf_counter() - t0) / calls * 1e6, 2))
-            row[label] = {"per_call": us, "median": _median(us)}
+            row[label] = {"per_call": us, "median": bk.median(us)}
         row["torch_over_library"] = round(row["torch_us"]["median"] / row["library_us_dilate0"]["median"], 2)
         out["shapes"]["%dx%d" % (K, n)] = row
         del tc, tm
@@ -183,22 +162,10 @@ def child_step(name, steps, with_query):
         torch.cuda.synchronize()
 
     def step(k):
-        t, e, tf = dev[k % len(dev)]
-        g.process_pointcloud_device(t.data_ptr(), t.shape[0], np.float32, e, tf)
-        g.combine_maps_device().release()
+        bk.scan_combine(np, g, dev[k % len(dev)]).release()
         if with_query:
             g.score_alignments_device(tc.data_ptr(), n, tm.data_ptr(), K, dilate=1).release()
-    for k in range(20):
-        step(k)
-    g._check(g._lib.gvom_sync(g._h))
-    us = []
-    for _ in range(3):
-        t0 = time.perf_counter()
-        for k in range(steps):
-            step(k)
-        g._check(g._lib.gvom_sync(g._h))
-        us.append(round((time.perf_counter() - t0) / steps * 1e6, 2))
-    return {"us_per_step": us}
+    return {"us_per_step": bk.step_loop(g, step, steps, warm=20)["us_per_step"]}
 
 
 def child_kernel(name, K, n, dilate):
@@ -208,87 +175,47 @@ def child_kernel(name, K, n, dilate):
     torch.cuda.synchronize()
     for _ in range(20):
         g.score_alignments_device(tc.data_ptr(), n, tm.data_ptr(), K, dilate=dilate).release()
-    g._check(g._lib.gvom_sync(g._h))
+    bk.sync(g)
     return {"calls": 20}
 
 
-def _spawn(mode, args, profile_dir=None, lib=None):
-    cmd = [sys.executable, os.path.abspath(__file__), "--child", mode] + [str(x) for x in args]
-    if profile_dir:
-        cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", profile_dir, "--"] + cmd
-    env = dict(os.environ, GVOM_HIP_LIBRARY=os.path.abspath(lib)) if lib else None
-    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900, env=env)
-    if r.returncode != 0:
-        raise SystemExit("%s %r failed (%d):\n%s" % (mode, args, r.returncode, r.stderr[-3000:]))
-    return json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("RESULT ")][-1][7:])
-
-
-def _kernel_stats(profile_dir):
-    out = {}
-    for f in glob.glob(os.path.join(profile_dir, "**", "*kernel_stats.csv"), recursive=True):
-        for r in csv.DictReader(open(f)):
-            for k in ("k_align_field", "k_align_score", "k_align_best"):
-                if k in r["Name"]:
-                    out[k] = {"calls": int(r["Calls"]), "avg_us": round(float(r["AverageNs"]) / 1e3, 2), "min_us": round(float(r["MinNs"]) / 1e3, 2),
-                              "max_us": round(float(r["MaxNs"]) / 1e3, 2)}
-    return out
-
-
 def main():
-    argv = sys.argv[1:]
-    if len(argv) > 1 and argv[0] == "--child":
-        mode, a = argv[1], argv[2:]
-        res = (child_call(a[0]) if mode == "call" else child_step(a[0], int(a[1]), a[2] == "1") if mode == "step" else
-               child_kernel(a[0], int(a[1]), int(a[2]), int(a[3])))
-        print("RESULT " + json.dumps(res))
+    if bk.child(sys.argv[1:], {"call": lambda a: child_call(a[0]), "step": lambda a: child_step(a[0], int(a[1]), a[2] == "1"),
+                               "kernel": lambda a: child_kernel(a[0], int(a[1]), int(a[2]), int(a[3]))}):
         return
-    import lib_identity
-    ident = lib_identity.identity()
-    do_resources = "--resources" in argv
-    argv = [x for x in argv if x != "--resources"]
-    parent = None
-    if "--parent" in argv:
-        k = argv.index("--parent")
-        parent, argv = argv[k + 1], argv[:k] + argv[k + 2:]
-    path = argv[0] if argv else os.path.join(ROOT, "profiles", "align_%s.json" % (ident.get("lib_sha256") or "unknown")[:8])
-    out = json.load(open(path)) if os.path.exists(path) else {}
-    out["library"] = ident
-    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-
-    def save():
-        with open(path, "w") as f:
-            f.write(json.dumps(out, indent=1) + "\n")
-    if do_resources:
-        out["resources"] = resources(parent or "HEAD")
-        save()
+    args = bk.read_args(sys.argv[1:], configs=CONFIGS, turns=TURNS)        # (--parent: a revision with --resources, a library without)
+    parent = args["parent"]
+    spawn = lambda mode, a, **kw: bk.spawn(__file__, mode, a, CHILD_TIMEOUT, **kw)
+    report = bk.Report("align", args["path"], None if args["resources"] else parent)
+    out = report.out
+    if args["resources"]:
+        out["resources"] = compiled_resources(parent or "HEAD")
+        report.save()
         print(json.dumps({k: v for k, v in out["resources"].items() if k.startswith(("trace_and", "k_align"))}))
         print(json.dumps(out["resources"]["gvom_align.hip"]["kernels"], indent=1))
         return
-    if parent:
-        out["parent_library"] = {"lib_sha256": lib_identity.sha256_file(parent)}
     out["configs"] = {}
-    for name, steps in CONFIGS:
-        res = _spawn("call", (name,))
+    for name in args["configs"]:
+        steps = CONFIGS[name]
+        res = spawn("call", (name,))
         for key, row in res["shapes"].items():
             K, n = (int(v) for v in key.split("x"))
             for dilate in (0, 1):
                 with tempfile.TemporaryDirectory() as d:
-                    _spawn("kernel", (name, K, n, dilate), profile_dir=d)
-                    ks = _kernel_stats(d)
+                    spawn("kernel", (name, K, n, dilate), profile_dir=d, stats=True)
+                    stats = bk.kernel_stats(d, KERNELS)
+                ks = {k: v for k in KERNELS for full, v in stats.items() if k in full}
                 if "k_align_score" in ks:
                     ks["pairs_per_s"] = round(K * n / (ks["k_align_score"]["avg_us"] * 1e-6))
                 row["kernels_dilate%d" % dilate] = ks
-        runs = {"without": [], "with": [], "parent_without": []}
-        for _ in range(2):                                         # alternating: parent, without, with, ...
-            if parent:
-                runs["parent_without"].append(_spawn("step", (name, steps, 0), lib=parent)["us_per_step"])
-            runs["without"].append(_spawn("step", (name, steps, 0))["us_per_step"])
-            runs["with"].append(_spawn("step", (name, steps, 1))["us_per_step"])
-        step = {}
+        runs = bk.alternate(args["turns"], {"parent_without": parent and (lambda: spawn("step", (name, steps, 0), lib=parent)["us_per_step"]),
+                                            "without": lambda: spawn("step", (name, steps, 0))["us_per_step"],
+                                            "with": lambda: spawn("step", (name, steps, 1))["us_per_step"]})
+        step = {}                                                  # (this file's keys are older than spreads(): the repetitions run by run)
         for k, v in runs.items():
             flat = [u for r in v for u in r]
             if flat:
-                step[k] = {"us_per_step": v, "median": _median(flat), "spread_us": round(max(flat) - min(flat), 2)}
+                step[k] = {"us_per_step": v, "median": bk.median(flat), "spread_us": round(max(flat) - min(flat), 2)}
         if parent:
             d = step["without"]["median"] - step["parent_without"]["median"]
             step["without_minus_parent_us"] = round(d, 2)
@@ -296,7 +223,7 @@ def main():
         step["query"] = "%d x %d, dilate 1" % STEP_SHAPE
         res["step"] = step
         out["configs"][name] = res
-        save()                                                     # (after every config: a long run leaves what it has)
+        report.save()                                              # (after every config: a long run leaves what it has)
     print(json.dumps(out["configs"], indent=1))
 
 

@@ -17,23 +17,18 @@ extent of A = 1024 and 4096 cells, so that the whole extent holds terrain.  Ever
   resources  tools/kernel_regs.py: the new kernels, and registers, scratch, LDS and code size of every kernel that existed before on
              the parent and on this library (--resources alone: no GPU needed)
 
-    tools/atlas_field_bench.py [--resources] [--parent LIB] [--configs m256,c4] [--sides 1024,4096] [out.json]
+    tools/atlas_field_bench.py [--resources] [--parent LIB] [--configs m256,c4] [--turns N] [--sides 1024,4096] [out.json]
                                                                      (default: profiles/atlas_field_<lib sha8>.json)
 """
-import csv
-import glob
 import json
-import os
 import shutil
-import subprocess
 import sys
 import tempfile
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "g-vom_amd"))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+import benchkit as bk
+
 CONFIGS = {"m256": 60, "c4": 30}                         # config: timed steps per repetition
+TURNS = 5
 SIDES = (1024, 4096)
 ROBOT_RADIUS = 0.6                                        # metres
 CHILD_TIMEOUT = 400                                       # seconds, per child process
@@ -42,39 +37,11 @@ SHOWN = ("k_atlas_clearance_rows", "k_clearance_cols", "k_atlas_travcost", "k_ct
          "k_clearance_rows", "k_travcost", "k_atlas_merge", "k_atlas_recall")
 
 
-def _median(v):
-    v = sorted(v)
-    return v[len(v) // 2] if len(v) % 2 else 0.5 * (v[len(v) // 2 - 1] + v[len(v) // 2])
-
-
-def _gvom():
-    """The binding, also over the parent's library: it is bound with the entry points it has."""
-    import ctypes
-    import gvom
-    lib = ctypes.CDLL(gvom.library_path())
-    gvom.ABI = [e for e in gvom.ABI if hasattr(lib, e[0])]
-    return gvom
-
-
-def _setup(name):
-    import numpy as np
-    import torch
-    import synth
-    torch.cuda.init()
-    gvom = _gvom()
-    params, scans = synth.config_inputs(name, n_scans=3)
-    dev = [(torch.from_numpy(np.ascontiguousarray(pc)).cuda(), ego, tf) for pc, ego, tf in scans]
-    torch.cuda.synchronize()
-    g = gvom.Gvom(*params, voxel_statistics=False)
-    return np, torch, gvom, g, dev
-
-
 def _filled(np, torch, gvom, g, dev, A):
     """the drive, then the last set at every tile of a fixed extent: (atlas, last set, extent origin, a goal in the first tile)"""
     m = None
-    for t, ego, tf in dev:
-        g.process_pointcloud_device(t.data_ptr(), t.shape[0], np.float32, ego, tf)
-        m = g.combine_maps_device()
+    for scan in dev:
+        m = bk.scan_combine(np, g, scan)
     xy = g.xy_size
     o = m.origin_cells[:2]
     a = g.create_atlas(A, follow=False, origin_cells=o)
@@ -91,21 +58,12 @@ def _filled(np, torch, gvom, g, dev, A):
 
 
 def child_events(name, A, reps=7):
-    np, torch, gvom, g, dev = _setup(name)
+    np, torch, gvom, g, dev = bk.setup(name)
     a, m, o, goal, tm = _filled(np, torch, gvom, g, dev, A)
     stream = torch.cuda.ExternalStream(int(g._lib.gvom_stream(g._h)))
 
     def timed(call, n):
-        us, last = [], None
-        for k in range(n + 2):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(stream)
-            last = call()
-            e1.record(stream)
-            e1.synchronize()
-            if k >= 2:
-                us.append(e0.elapsed_time(e1) * 1e3)
-        return {"median_us": round(_median(us), 2), "min_us": round(min(us), 2), "max_us": round(max(us), 2), "calls": n}, last
+        return bk.timed_events(torch, stream, call, n)
 
     def solve(**kw):
         f = a.cost_to_go([goal], goals_in_cells=True, **kw)
@@ -140,164 +98,87 @@ def child_events(name, A, reps=7):
 
 def child_profiled(name, A):
     """the calls of child_events once more, three of each: run under rocprofv3 by the parent process"""
-    np, torch, gvom, g, dev = _setup(name)
+    np, torch, gvom, g, dev = bk.setup(name)
     a, m, o, goal, tm = _filled(np, torch, gvom, g, dev, A)
     for kw in ({}, {"inflation_radius": ROBOT_RADIUS}):
         for _ in range(3):
             with a.cost_to_go([goal], goals_in_cells=True, **kw) as f:
                 f.window(m).release()
-    g._check(g._lib.gvom_sync(g._h))
+    bk.sync(g)
     del tm
     return {"calls": 6}
 
 
 def child_step(name, steps, mode, A):
-    np, torch, gvom, g, dev = _setup(name)
+    np, torch, gvom, g, dev = bk.setup(name)
     a = g.create_atlas(A)
     goal = None
 
     def step(k):
         nonlocal goal
-        t, ego, tf = dev[k % 3]
-        g.process_pointcloud_device(t.data_ptr(), t.shape[0], np.float32, ego, tf)
-        m = g.combine_maps_device()
+        m = bk.scan_combine(np, g, dev[k % 3])
         a.integrate(m)
         if mode:
             if goal is None:
                 goal = [m.origin_cells[0] + g.xy_size // 2, m.origin_cells[1] + g.xy_size // 2]
             a.cost_to_go([goal], goals_in_cells=True).release()
         m.release()
-
-    for k in range(min(10, steps)):
-        step(k)
-    g._check(g._lib.gvom_sync(g._h))
-    us = []
-    for rep in range(3):
-        t0 = time.perf_counter()
-        for k in range(steps):
-            step(k)
-        g._check(g._lib.gvom_sync(g._h))
-        us.append(round((time.perf_counter() - t0) / steps * 1e6, 2))
-    return {"us_per_step": us, "us_per_step_median": _median(us), "steps": steps}
+    return bk.step_loop(g, step, steps, warm=min(10, steps))
 
 
-def _spawn(mode, args, lib=None, wrap=()):
-    """one child under its own time limit; a child that fails (or runs into the limit) ends the whole run"""
-    cmd = ["timeout", "-k", "10", str(CHILD_TIMEOUT)] + list(wrap) + [sys.executable, os.path.abspath(__file__), "--child", mode] + [str(a) for a in args]
-    env = dict(os.environ, GVOM_HIP_LIBRARY=os.path.abspath(lib)) if lib else None
-    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=env)
-    if r.returncode != 0:
-        raise SystemExit("%s %r failed (%d): nothing more is started\n%s" % (mode, args, r.returncode, r.stderr[-3000:]))
-    line = [ln for ln in r.stdout.splitlines() if ln.startswith("RESULT ")][-1]
-    return json.loads(line[7:])
-
-
-def kernels_one_by_one(name, A):
-    """average microseconds per kernel from a kernel trace of child_profiled, in a run of its own"""
+def kernels_one_by_one(script, args, shown, limit, total=False):
+    """average microseconds per kernel of `shown` from a kernel trace of `script`'s child "profiled", in a run of its own.  Best
+    effort: the events stand without it, so its failure is noted and the run goes on"""
     if not shutil.which("rocprofv3"):
         return {"not_measured": "no rocprofv3 on this machine"}
-    d = tempfile.mkdtemp(prefix="atlas_field_prof_")
+    d = tempfile.mkdtemp(prefix="atlas_prof_")
     try:
-        _spawn("profiled", (name, A), wrap=("rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "--"))
-        files = glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True)
-        if not files:
+        bk.spawn(script, "profiled", args, limit, profile_dir=d, stats=True)
+        stats = bk.kernel_stats(d, total=total)
+        if not stats:
             return {"not_measured": "the trace left no kernel_stats.csv"}
         out = {}
-        for r in csv.DictReader(open(files[0])):
-            short = r["Name"].split("(")[0].replace("void ", "")
-            if short in SHOWN:
-                out[short] = {"calls": int(r["Calls"]), "average_us": round(float(r["AverageNs"]) / 1e3, 2),
-                              "min_us": round(float(r.get("MinNs", 0)) / 1e3, 2), "max_us": round(float(r.get("MaxNs", 0)) / 1e3, 2)}
+        for name, v in stats.items():
+            if name.replace("void ", "") in shown:
+                v["average_us"] = v.pop("avg_us")
+                out[name.replace("void ", "")] = v
         return out
-    except SystemExit as e:                                         # best effort: the events above stand without it
+    except SystemExit as e:
         return {"not_measured": str(e)[:500]}
     finally:
         shutil.rmtree(d, ignore_errors=True)
 
 
-def resources(new, parent):
-    """the new kernels, and every other kernel on the parent and on this library: registers, scratch, LDS, code size"""
-    import kernel_regs
-    mine = kernel_regs.kernels(new)
-    is_new = lambda k: any(n in k for n in NEW_KERNELS)              # noqa: E731
-    out = {"new_kernels": {k: v for k, v in mine.items() if is_new(k)}}
-    if parent:
-        theirs = kernel_regs.kernels(parent)
-        rest = {k: v for k, v in mine.items() if not is_new(k)}
-        keys = ("vgpr", "sgpr", "scratch", "lds", "code")
-        changed = {k: {"parent": theirs.get(k), "new": v} for k, v in rest.items() if any((theirs.get(k) or {}).get(q) != v.get(q) for q in keys)}
-        out["other_kernels"] = {"count": len(rest), "identical_to_parent": len(rest) - len(changed), "changed": changed,
-                                "only_on_parent": sorted(k for k in theirs if k not in mine)}
-    return out
-
-
 def main():
-    if len(sys.argv) > 2 and sys.argv[1] == "--child":
-        mode, a = sys.argv[2], sys.argv[3:]
-        res = {"events": lambda: child_events(a[0], int(a[1])), "profiled": lambda: child_profiled(a[0], int(a[1])),
-               "step": lambda: child_step(a[0], int(a[1]), int(a[2]), int(a[3]))}[mode]()
-        print("RESULT " + json.dumps(res))
+    if bk.child(sys.argv[1:], {"events": lambda a: child_events(a[0], int(a[1])), "profiled": lambda a: child_profiled(a[0], int(a[1])),
+                               "step": lambda a: child_step(a[0], int(a[1]), int(a[2]), int(a[3]))}):
         return
-    import lib_identity
-    args = sys.argv[1:]
-    parent, only_resources, configs, sides = None, False, list(CONFIGS), list(SIDES)
-    while args and args[0] in ("--parent", "--resources", "--configs", "--sides"):
-        if args[0] == "--parent":
-            parent, args = args[1], args[2:]
-        elif args[0] == "--configs":
-            configs, args = args[1].split(","), args[2:]
-        elif args[0] == "--sides":
-            sides, args = [int(v) for v in args[1].split(",")], args[2:]
-        else:
-            only_resources, args = True, args[1:]
-    new = os.path.join(ROOT, "g-vom_amd", "lib", "libgvom_hip.so")
-    path = args[0] if args else os.path.join(ROOT, "profiles", "atlas_field_%s.json" % (lib_identity.identity().get("lib_sha256") or "unknown")[:8])
-    out = json.load(open(path)) if os.path.exists(path) else {}
-    out.update({"library": lib_identity.identity(), "sides": sides, "robot_radius_m": ROBOT_RADIUS})
-    out["resources"] = resources(new, parent)
-    if parent:
-        out["parent_library"] = {"lib_sha256": lib_identity.sha256_file(parent)}
-    out.setdefault("not_measured", ["follow mode and a moving extent during the solve's fill", "goals far from the first tile, more than one goal",
-                                    "soft and roughness weights, unknown=\"blocked\"", "windows other than the config's own",
-                                    "terrain other than the config's set repeated over the extent: the round count depends on it"])
-    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-
-    def save():
-        with open(path, "w") as f:                                  # (after every part: a run that ends early leaves what it has)
-            f.write(json.dumps(out, indent=1) + "\n")
-    save()
-    if only_resources:
-        out.setdefault("configs", "not measured")
-        save()
+    args = bk.read_args(sys.argv[1:], configs=CONFIGS, turns=TURNS, extra={"--sides": (list(SIDES), lambda s: [int(v) for v in s.split(",")])})
+    parent, sides = args["parent"], args["sides"]
+    spawn = lambda mode, a, **kw: bk.spawn(__file__, mode, a, CHILD_TIMEOUT, **kw)
+    report, configs = bk.product_report(
+        "atlas_field", args, {"sides": sides, "robot_radius_m": ROBOT_RADIUS}, lambda k: any(n in k for n in NEW_KERNELS),
+        ["follow mode and a moving extent during the solve's fill", "goals far from the first tile, more than one goal",
+         "soft and roughness weights, unknown=\"blocked\"", "windows other than the config's own",
+         "terrain other than the config's set repeated over the extent: the round count depends on it"])
+    if configs is None:
         return
-    if not isinstance(out.get("configs"), dict):
-        out["configs"] = {}
-    for name in configs:
+    for name in args["configs"]:
         steps = CONFIGS[name]
-        res = out["configs"].setdefault(name, {})
-        res["events"] = {"A %d" % A: _spawn("events", (name, A)) for A in sides}
-        save()
-        res["kernels one by one (rocprofv3 --kernel-trace --stats, a run of its own)"] = {"A %d" % A: kernels_one_by_one(name, A) for A in sides}
-        save()
-        runs = {"without": [], "field_per_step": [], "parent_without": []}
-        for rnd in range(5):                                        # alternating: parent, without, with, ...
-            if parent:
-                runs["parent_without"].append(_spawn("step", (name, steps, 0, 1024), lib=parent))
-            runs["without"].append(_spawn("step", (name, steps, 0, 1024)))
-            runs["field_per_step"].append(_spawn("step", (name, max(5, steps // 6), 1, 1024)))
-        step = {}
-        for who, rs in runs.items():
-            if rs:
-                meds = [r["us_per_step_median"] for r in rs]
-                step[who] = {"run_medians_us": meds, "median": _median(meds), "min": min(meds), "max": max(meds)}
+        res = configs.setdefault(name, {})
+        res["events"] = {"A %d" % A: spawn("events", (name, A)) for A in sides}
+        report.save()
+        res["kernels one by one (rocprofv3 --kernel-trace --stats, a run of its own)"] = {
+            "A %d" % A: kernels_one_by_one(__file__, (name, A), SHOWN, CHILD_TIMEOUT) for A in sides}
+        report.save()
+        runs = bk.alternate(args["turns"], {"parent_without": parent and (lambda: spawn("step", (name, steps, 0, 1024), lib=parent)),
+                                            "without": lambda: spawn("step", (name, steps, 0, 1024)),
+                                            "field_per_step": lambda: spawn("step", (name, max(5, steps // 6), 1, 1024))})
+        step = bk.spreads(runs)
         step["a_field_per_step_adds_us_per_step"] = round(step["field_per_step"]["median"] - step["without"]["median"], 2)
-        if parent:
-            p = step["parent_without"]
-            step["without_inside_parents_own_spread"] = bool(p["min"] <= step["without"]["median"] <= p["max"])
-            step["without_minus_parent_median_us"] = round(step["without"]["median"] - p["median"], 2)
-        res["step: scan + combine_maps_device + integrate (+ a field per step), A 1024"] = step
-        save()
-    print(json.dumps(out, indent=1))
+        res["step: scan + combine_maps_device + integrate (+ a field per step), A 1024"] = bk.against_parent(step, "without", "parent_without", "without_")
+        report.save()
+    print(json.dumps(report.out, indent=1))
 
 
 if __name__ == "__main__":

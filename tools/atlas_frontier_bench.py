@@ -18,48 +18,27 @@ ends the run (the per-kernel part alone is best effort: its failure is noted):
   resources  tools/kernel_regs.py: the new kernel, and registers, scratch, LDS and code size of every kernel that existed before on
              the parent and on this library (--resources alone: no GPU needed)
 
-    tools/atlas_frontier_bench.py [--resources] [--parent LIB] [--config m256] [--step-configs m256,c4] [--sides 1024,4096] [out.json]
+    tools/atlas_frontier_bench.py [--resources] [--parent LIB] [--config m256] [--configs m256,c4] [--turns N] [--sides 1024,4096] [out.json]
                                                                      (default: profiles/atlas_frontiers_<lib sha8>.json)
 """
-import csv
-import glob
 import json
-import os
-import shutil
-import subprocess
 import sys
-import tempfile
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "g-vom_amd"))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-import atlas_field_bench as afb                                       # noqa: E402  (the painted terrain, the set-up and the medians are its)
+import atlas_field_bench as afb                                       # (the painted terrain and the per-kernel run are its)
+import benchkit as bk
 
 STEP_CONFIGS = {"m256": 60, "c4": 30}                    # config: timed steps per repetition
+TURNS = 5
 SIDES = (1024, 4096)
 CHILD_TIMEOUT = 400                                       # seconds, per child process
 NEW_KERNELS = ("k_atlas_frontier_mark",)
 SHOWN = ("k_atlas_frontier_mark", "k_frontier_mark", "k_frontier_relax", "k_frontier_count", "k_frontier_rank", "k_frontier_rows", "k_frontier_stats",
          "k_atlas_recall", "k_atlas_field_window")
-_median = afb._median
-
-
-def _timed(torch, stream, call, n, warm=2):
-    us, last = [], None
-    for k in range(n + warm):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(stream)
-        last = call()
-        e1.record(stream)
-        e1.synchronize()
-        if k >= warm:
-            us.append(e0.elapsed_time(e1) * 1e3)
-    return {"median_us": round(_median(us), 2), "min_us": round(min(us), 2), "max_us": round(max(us), 2), "calls": n}, last
 
 
 def child_events(name, A, reps=9):
-    np, torch, gvom, g, dev = afb._setup(name)
+    np, torch, gvom, g, dev = bk.setup(name)
     a, m, o, goal, tm = afb._filled(np, torch, gvom, g, dev, A)
     stream = torch.cuda.ExternalStream(int(g._lib.gvom_stream(g._h)))
     xy = g.xy_size
@@ -71,7 +50,7 @@ def child_events(name, A, reps=9):
         with f.frontiers() as p:
             return {"rounds": p.rounds, "tile_relaxations": g.get_tuning("atlas_frontier_tiles"), "kept_clusters": p.n_clusters,
                     "frontier_cells": p.frontier_cells, "dropped_by_min_cells": p.dropped}
-    t, info = _timed(torch, stream, whole, reps)
+    t, info = bk.timed_events(torch,stream, whole, reps)
     info["tiles_launched"] = info["rounds"] * out["tiles_launched_per_round"]
     out["frontiers() on the whole extent"] = dict(t, **info)
 
@@ -83,7 +62,7 @@ def child_events(name, A, reps=9):
                     kept, cells = kept + p.n_clusters, cells + p.frontier_cells
                     r.stamps.release()
         return {"windows": (A // xy) ** 2, "kept_clusters_summed_over_windows": kept, "frontier_cells_summed_over_windows": cells}
-    t, info = _timed(torch, stream, tiled, 3, warm=1)
+    t, info = bk.timed_events(torch,stream, tiled, 3, warm=1)
     out["for scale: recall() + window() + frontiers() per window over the extent (clusters cut at window borders: not an equal product)"] = dict(t, **info)
 
     from scipy import ndimage
@@ -121,138 +100,56 @@ def child_events(name, A, reps=9):
 
 def child_profiled(name, A):
     """three calls: run under rocprofv3 by the parent process"""
-    np, torch, gvom, g, dev = afb._setup(name)
+    np, torch, gvom, g, dev = bk.setup(name)
     a, m, o, goal, tm = afb._filled(np, torch, gvom, g, dev, A)
     with a.cost_to_go([goal], goals_in_cells=True) as f:
         for _ in range(3):
             f.frontiers().release()
-    g._check(g._lib.gvom_sync(g._h))
+    bk.sync(g)
     del tm
     return {"calls": 3}
 
 
 def child_step(name, steps):
     """scan + combine_maps_device() per step, no atlas anywhere"""
-    np, torch, gvom, g, dev = afb._setup(name)
+    np, torch, gvom, g, dev = bk.setup(name)
 
     def step(k):
-        t, ego, tf = dev[k % 3]
-        g.process_pointcloud_device(t.data_ptr(), t.shape[0], np.float32, ego, tf)
-        g.combine_maps_device().release()
-
-    for k in range(min(10, steps)):
-        step(k)
-    g._check(g._lib.gvom_sync(g._h))
-    us = []
-    for rep in range(3):
-        t0 = time.perf_counter()
-        for k in range(steps):
-            step(k)
-        g._check(g._lib.gvom_sync(g._h))
-        us.append(round((time.perf_counter() - t0) / steps * 1e6, 2))
-    return {"us_per_step": us, "us_per_step_median": _median(us), "steps": steps}
-
-
-def _spawn(mode, args, lib=None, wrap=()):
-    """one child under its own time limit; a child that fails (or runs into the limit) ends the whole run"""
-    cmd = ["timeout", "-k", "10", str(CHILD_TIMEOUT)] + list(wrap) + [sys.executable, os.path.abspath(__file__), "--child", mode] + [str(a) for a in args]
-    env = dict(os.environ, GVOM_HIP_LIBRARY=os.path.abspath(lib)) if lib else None
-    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=env)
-    if r.returncode != 0:
-        raise SystemExit("%s %r failed (%d): nothing more is started\n%s" % (mode, args, r.returncode, (r.stdout + r.stderr)[-3000:]))
-    line = [ln for ln in r.stdout.splitlines() if ln.startswith("RESULT ")][-1]
-    return json.loads(line[7:])
-
-
-def kernels_one_by_one(name, A):
-    """average microseconds per kernel from a kernel trace of child_profiled, in a run of its own"""
-    if not shutil.which("rocprofv3"):
-        return {"not_measured": "no rocprofv3 on this machine"}
-    d = tempfile.mkdtemp(prefix="atlas_frontier_prof_")
-    try:
-        _spawn("profiled", (name, A), wrap=("rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "--"))
-        files = glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True)
-        if not files:
-            return {"not_measured": "the trace left no kernel_stats.csv"}
-        out = {}
-        for r in csv.DictReader(open(files[0])):
-            short = r["Name"].split("(")[0].replace("void ", "")
-            if short in SHOWN:
-                out[short] = {"calls": int(r["Calls"]), "average_us": round(float(r["AverageNs"]) / 1e3, 2), "total_us": round(float(r["TotalDurationNs"]) / 1e3, 2)
-                              if "TotalDurationNs" in r else None, "min_us": round(float(r.get("MinNs", 0)) / 1e3, 2), "max_us": round(float(r.get("MaxNs", 0)) / 1e3, 2)}
-        return out
-    except SystemExit as e:                                         # best effort: the events above stand without it
-        return {"not_measured": str(e)[:500]}
-    finally:
-        shutil.rmtree(d, ignore_errors=True)
+        bk.scan_combine(np, g, dev[k % 3]).release()
+    return bk.step_loop(g, step, steps, warm=min(10, steps))
 
 
 def main():
-    if len(sys.argv) > 2 and sys.argv[1] == "--child":
-        mode, a = sys.argv[2], sys.argv[3:]
-        res = {"events": lambda: child_events(a[0], int(a[1])), "profiled": lambda: child_profiled(a[0], int(a[1])),
-               "step": lambda: child_step(a[0], int(a[1]))}[mode]()
-        print("RESULT " + json.dumps(res))
+    if bk.child(sys.argv[1:], {"events": lambda a: child_events(a[0], int(a[1])), "profiled": lambda a: child_profiled(a[0], int(a[1])),
+                               "step": lambda a: child_step(a[0], int(a[1]))}):
         return
-    import lib_identity
-    args = sys.argv[1:]
-    parent, only_resources, config, step_configs, sides = None, False, "m256", list(STEP_CONFIGS), list(SIDES)
-    while args and args[0] in ("--parent", "--resources", "--config", "--step-configs", "--sides"):
-        if args[0] == "--parent":
-            parent, args = args[1], args[2:]
-        elif args[0] == "--config":
-            config, args = args[1], args[2:]
-        elif args[0] == "--step-configs":
-            step_configs, args = [v for v in args[1].split(",") if v], args[2:]
-        elif args[0] == "--sides":
-            sides, args = [int(v) for v in args[1].split(",") if v], args[2:]
-        else:
-            only_resources, args = True, args[1:]
-    new = os.path.join(ROOT, "g-vom_amd", "lib", "libgvom_hip.so")
-    path = args[0] if args else os.path.join(ROOT, "profiles", "atlas_frontiers_%s.json" % (lib_identity.identity().get("lib_sha256") or "unknown")[:8])
-    out = json.load(open(path)) if os.path.exists(path) else {}
-    out.update({"library": lib_identity.identity(), "sides": sides, "config": config})
-    afb.NEW_KERNELS = NEW_KERNELS
-    out["resources"] = afb.resources(new, parent)
-    if parent:
-        out["parent_library"] = {"lib_sha256": lib_identity.sha256_file(parent)}
-    out.setdefault("not_measured", ["a compacted tile list: every round launches all (A / 32)^2 tiles, most of which return at once",
-                                    "follow mode, a moved extent and an atlas of another side than the field's",
-                                    "terrain other than the config's set repeated over the extent: rounds and clusters depend on it",
-                                    "min_cells and max_clusters other than the defaults; windows other than the config's own in the tiled loop"])
-    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-
-    def save():
-        with open(path, "w") as f:                                  # (after every part: a run that ends early leaves what it has)
-            f.write(json.dumps(out, indent=1) + "\n")
-    save()
-    if only_resources:
-        out.setdefault("events", "not measured")
-        save()
+    names = lambda s: [v for v in s.split(",") if v]
+    args = bk.read_args(sys.argv[1:], configs=STEP_CONFIGS, turns=TURNS,           # (--configs: the step's, as --step-configs)
+                        extra={"--config": ("m256", str), "--step-configs": (None, names), "--sides": (list(SIDES), lambda s: [int(v) for v in names(s)])})
+    parent, config, sides = args["parent"], args["config"], args["sides"]
+    step_configs = args["configs"] if args["step_configs"] is None else args["step_configs"]
+    spawn = lambda mode, a, **kw: bk.spawn(__file__, mode, a, CHILD_TIMEOUT, **kw)
+    report, events = bk.product_report(
+        "atlas_frontiers", args, {"sides": sides, "config": config}, lambda k: any(n in k for n in NEW_KERNELS),
+        ["a compacted tile list: every round launches all (A / 32)^2 tiles, most of which return at once",
+         "follow mode, a moved extent and an atlas of another side than the field's",
+         "terrain other than the config's set repeated over the extent: rounds and clusters depend on it",
+         "min_cells and max_clusters other than the defaults; windows other than the config's own in the tiled loop"], section="events")
+    if events is None:
         return
+    out = report.out
     if sides:
-        out["events"] = {"A %d" % A: _spawn("events", (config, A)) for A in sides}
-        save()
-        out["kernels one by one (rocprofv3 --kernel-trace --stats, a run of its own)"] = {"A %d" % A: kernels_one_by_one(config, A) for A in sides}
-        save()
+        events.update({"A %d" % A: spawn("events", (config, A)) for A in sides})
+        report.save()
+        out["kernels one by one (rocprofv3 --kernel-trace --stats, a run of its own)"] = {
+            "A %d" % A: afb.kernels_one_by_one(__file__, (config, A), SHOWN, CHILD_TIMEOUT, total=True) for A in sides}
+        report.save()
     for name in step_configs:
         steps = STEP_CONFIGS[name]
-        runs = {"this_library": [], "parent": []}
-        for rnd in range(5):                                        # alternating: parent, this, parent, ...
-            if parent:
-                runs["parent"].append(_spawn("step", (name, steps), lib=parent))
-            runs["this_library"].append(_spawn("step", (name, steps)))
-        step = {}
-        for who, rs in runs.items():
-            if rs:
-                meds = [r["us_per_step_median"] for r in rs]
-                step[who] = {"run_medians_us": meds, "median": _median(meds), "min": min(meds), "max": max(meds)}
-        if parent:
-            p = step["parent"]
-            step["inside_parents_own_spread"] = bool(p["min"] <= step["this_library"]["median"] <= p["max"])
-            step["minus_parent_median_us"] = round(step["this_library"]["median"] - p["median"], 2)
-        out.setdefault("step: scan + combine_maps_device, no atlas call", {})[name] = step
-        save()
+        runs = bk.alternate(args["turns"], {"parent": parent and (lambda: spawn("step", (name, steps), lib=parent)),
+                                            "this_library": lambda: spawn("step", (name, steps))})
+        out.setdefault("step: scan + combine_maps_device, no atlas call", {})[name] = bk.against_parent(bk.spreads(runs), "this_library", "parent", "")
+        report.save()
     print(json.dumps(out, indent=1))
 
 

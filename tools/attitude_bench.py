@@ -17,54 +17,23 @@ first child that fails ends the run:
   resources  tools/kernel_regs.py: the new kernels, and registers, scratch, LDS and code size of every kernel outside the new
              unit on the parent and on this library (--resources alone: no GPU needed)
 
-    tools/attitude_bench.py [--resources] [--parent LIB] [out.json]      (default: profiles/attitude_<lib sha8>.json)
+    tools/attitude_bench.py [--resources] [--parent LIB] [--configs m256,c4] [--turns N] [out.json]      (default: profiles/attitude_<lib sha8>.json)
 """
-import csv
-import glob
 import json
-import os
-import subprocess
 import sys
 import tempfile
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "g-vom_amd"))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-CONFIGS = (("m256", 100), ("c4", 40))                      # (config, timed steps per repetition)
+import benchkit as bk
+
+CONFIGS = {"m256": 100, "c4": 40}                          # config: timed steps per repetition
+TURNS = 5
 SHAPES = ((4096, 64), (16384, 128))
 CAR = dict(front=3.6, rear=1.0, half_width=1.1)            # metres: tests/rollouts_ref.py CAR
 CHASSIS = dict(front_axle=2.7, rear_axle=0.0, track=1.7, belly_height=0.25, max_pitch=0.35, max_roll=0.3, min_clearance=0.1)   # angles in radians
 HEADINGS = 64
 CHUNK = 512                                                # rollouts per chunk of the torch form
 CHILD_TIMEOUT = 420                                        # seconds, per child process
-
-
-def _median(v):
-    v = sorted(v)
-    return v[len(v) // 2] if len(v) % 2 else 0.5 * (v[len(v) // 2 - 1] + v[len(v) // 2])
-
-
-def _gvom():
-    """The binding, also over the parent's library: it is bound with the entry points it has."""
-    import ctypes
-    import gvom
-    lib = ctypes.CDLL(gvom.library_path())
-    gvom.ABI = [e for e in gvom.ABI if hasattr(lib, e[0])]
-    return gvom
-
-
-def _setup(name):
-    import numpy as np
-    import torch
-    import synth
-    torch.cuda.init()
-    gvom = _gvom()
-    params, scans = synth.config_inputs(name, n_scans=3)
-    dev = [(torch.from_numpy(np.ascontiguousarray(pc)).cuda(), ego, tf) for pc, ego, tf in scans]
-    torch.cuda.synchronize()
-    g = gvom.Gvom(*params, voxel_statistics=False)
-    return np, torch, gvom, g, dev
 
 
 def _vehicle(gvom, g):
@@ -140,10 +109,9 @@ def _torch_score(torch, gflat, poses, offs_pad, live, wheels, cs, ch, res, oc, x
 
 
 def child_score(name, profiled):
-    np, torch, gvom, g, dev = _setup(name)
-    for t, ego, tf in dev:
-        g.process_pointcloud_device(t.data_ptr(), t.shape[0], np.float32, ego, tf)
-        m = g.combine_maps_device()
+    np, torch, gvom, g, dev = bk.setup(name)
+    for scan in dev:
+        m = bk.scan_combine(np, g, scan)
     ego = dev[2][1]
     res, xy = g.xy_resolution, g.xy_size
     table = _vehicle(gvom, g)
@@ -179,22 +147,12 @@ def child_score(name, profiled):
             for _, call in calls:
                 for _ in range(reps):
                     call().release()
-                g._check(g._lib.gvom_sync(g._h))
+                bk.sync(g)
             continue
         out = {"xy": xy, "K": K, "T": T, "cells_per_heading_mean": round(float(cells.mean()), 1)}
         for what, call in calls:
-            for _ in range(3):
-                call().release()
-            g._check(g._lib.gvom_sync(g._h))
-            us = []
-            for rep in range(5):
-                t0 = time.perf_counter()
-                for _ in range(reps):
-                    call().release()
-                g._check(g._lib.gvom_sync(g._h))
-                us.append(round((time.perf_counter() - t0) / reps * 1e6, 2))
-            out[what + "_call_us"] = us
-            out[what + "_call_us_median"] = _median(us)
+            t = bk.timed(g, lambda: call().release(), reps, digits=2)
+            out[what + "_call_us"], out[what + "_call_us_median"] = t["us"], t["us_median"]
         r = by_set()
         summary, att, status = r.copy_to_host()
         r2 = by_ptr()
@@ -219,14 +177,14 @@ def child_score(name, profiled):
             tus.append(round((time.perf_counter() - t0) * 1e6, 1))
         out["torch"] = {"statuses_equal": bool(same.all()), "statuses_that_differ": int((~same).sum()),
                         "largest_value_difference_where_statuses_agree": float(diff[same].max()) if same.any() else None,
-                        "us": tus, "us_median": _median(tus), "chunk_rollouts": CHUNK, "padded_cells_per_pose": mmax}
+                        "us": tus, "us_median": bk.median(tus), "chunk_rollouts": CHUNK, "padded_cells_per_pose": mmax}
         r.release()
         results.append(out)
     return {"calls": reps, "order": ["attitude_map_set", "attitude_pointer", "rollouts"]} if profiled else {"scoring": results}
 
 
 def child_step(name, steps, score):
-    np, torch, gvom, g, dev = _setup(name)
+    np, torch, gvom, g, dev = bk.setup(name)
     K, T = SHAPES[0]
     res = g.xy_resolution
     if score:
@@ -235,57 +193,22 @@ def child_step(name, steps, score):
     torch.cuda.synchronize()
 
     def step(k):
-        t, ego, tf = dev[k % 3]
-        g.process_pointcloud_device(t.data_ptr(), t.shape[0], np.float32, ego, tf)
-        m = g.combine_maps_device()
+        m = bk.scan_combine(np, g, dev[k % 3])
         if score:
             g._score_attitude(m.set_id, None, gvom._dev(tp[k % 3].data_ptr()), K, T, 1, True, m.origin).release()
         m.release()
-
-    for k in range(min(10, steps)):
-        step(k)
-    g._check(g._lib.gvom_sync(g._h))
-    us = []
-    for rep in range(3):
-        t0 = time.perf_counter()
-        for k in range(steps):
-            step(k)
-        g._check(g._lib.gvom_sync(g._h))
-        us.append(round((time.perf_counter() - t0) / steps * 1e6, 2))
-    return {"us_per_step": us, "us_per_step_median": _median(us), "steps": steps, "K": K if score else 0, "T": T if score else 0}
-
-
-def _spawn(mode, args, profile_dir=None, lib=None):
-    """one child under its own time limit; a child that fails (or runs into the limit) ends the whole run"""
-    cmd = [sys.executable, os.path.abspath(__file__), "--child", mode] + [str(a) for a in args]
-    if profile_dir:
-        cmd = ["rocprofv3", "--kernel-trace", "--output-format", "csv", "-d", profile_dir, "--"] + cmd
-    cmd = ["timeout", "-k", "10", str(CHILD_TIMEOUT)] + cmd
-    env = dict(os.environ, GVOM_HIP_LIBRARY=os.path.abspath(lib)) if lib else None
-    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=env)
-    if r.returncode != 0:
-        raise SystemExit("%s %r failed (%d): nothing more is started\n%s" % (mode, args, r.returncode, r.stderr[-3000:]))
-    line = [ln for ln in r.stdout.splitlines() if ln.startswith("RESULT ")][-1]
-    return json.loads(line[7:])
+    return dict(bk.step_loop(g, step, steps, warm=min(10, steps)), K=K if score else 0, T=T if score else 0)
 
 
 def _kernel_times(profile_dir, calls):
     """the dispatches of a profiled run in launch order: per shape and call the kernels' times without the first three launches"""
-    rows = {"k_attitude_ground": [], "k_attitude": [], "k_rollouts": []}
-    for f in glob.glob(os.path.join(profile_dir, "**", "*kernel_trace.csv"), recursive=True):
-        for r in csv.DictReader(open(f)):
-            name = r["Kernel_Name"]
-            key = "k_attitude_ground" if "k_attitude_ground" in name else ("k_attitude" if "k_attitude" in name else ("k_rollouts" if "k_rollouts" in name else None))
-            if key:
-                rows[key].append((int(r["Start_Timestamp"]), (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3))
+    rows = bk.kernel_trace_rows(profile_dir, ("k_attitude_ground", "k_attitude", "k_rollouts"))
 
     def stats(us):
         us = us[3:]
-        return {"launches": len(us), "median_us": round(_median(us), 2), "min_us": round(min(us), 2), "max_us": round(max(us), 2)}
-    for v in rows.values():
-        v.sort()
+        return {"launches": len(us), "median_us": round(bk.median(us), 2), "min_us": round(min(us), 2), "max_us": round(max(us), 2)}
     out = []
-    att, gnd, ro = ([u for _, u in rows[k]] for k in ("k_attitude", "k_attitude_ground", "k_rollouts"))
+    att, gnd, ro = ([u for _, kk, u in rows if kk == k] for k in ("k_attitude", "k_attitude_ground", "k_rollouts"))
     if len(att) != 2 * calls * len(SHAPES) or len(gnd) != calls * len(SHAPES) or len(ro) != calls * len(SHAPES):
         return None
     for n in range(len(SHAPES)):
@@ -294,84 +217,47 @@ def _kernel_times(profile_dir, calls):
     return out
 
 
-def resources(new, parent):
-    """the new unit's kernels, and every other kernel on the parent and on this library: registers, scratch, LDS, code size"""
+def _table(parent):
+    """every kernel outside the new unit, its figures on the parent beside those on this library"""
     import kernel_regs
-    mine = kernel_regs.kernels(new)
-    out = {"new_kernels": {k: v for k, v in mine.items() if "k_attitude" in k}}
-    if parent:
-        theirs = kernel_regs.kernels(parent)
-        rest = {k: v for k, v in mine.items() if "k_attitude" not in k}
-        keys = ("vgpr", "sgpr", "scratch", "lds", "code")
-        changed = {k: {"parent": theirs.get(k), "new": v} for k, v in rest.items() if any((theirs.get(k) or {}).get(q) != v.get(q) for q in keys)}
-        gone = sorted(k for k in theirs if k not in mine)
-        out["other_kernels"] = {"count": len(rest), "identical_to_parent": len(rest) - len(changed), "changed": changed, "only_on_parent": gone,
-                                "table": {k: {"parent": {q: (theirs.get(k) or {}).get(q) for q in keys}, "new": {q: v.get(q) for q in keys}} for k, v in sorted(rest.items())}}
-    return out
+    mine, theirs = kernel_regs.kernels(bk.NEW_LIB), kernel_regs.kernels(parent)
+    keys = ("vgpr", "sgpr", "scratch", "lds", "code")
+    return {k: {"parent": {q: (theirs.get(k) or {}).get(q) for q in keys}, "new": {q: v.get(q) for q in keys}}
+            for k, v in sorted(mine.items()) if "k_attitude" not in k}
 
 
 def main():
-    if len(sys.argv) > 2 and sys.argv[1] == "--child":
-        mode, a = sys.argv[2], sys.argv[3:]
-        res = child_score(a[0], a[1] == "1") if mode == "score" else child_step(a[0], int(a[1]), a[2] == "1")
-        print("RESULT " + json.dumps(res))
+    if bk.child(sys.argv[1:], {"score": lambda a: child_score(a[0], a[1] == "1"), "step": lambda a: child_step(a[0], int(a[1]), a[2] == "1")}):
         return
-    import lib_identity
-    args = sys.argv[1:]
-    parent, only_resources = None, False
-    while args and args[0] in ("--parent", "--resources"):
-        if args[0] == "--parent":
-            parent, args = args[1], args[2:]
-        else:
-            only_resources, args = True, args[1:]
-    new = os.path.join(ROOT, "g-vom_amd", "lib", "libgvom_hip.so")
-    path = args[0] if args else os.path.join(ROOT, "profiles", "attitude_%s.json" % (lib_identity.identity().get("lib_sha256") or "unknown")[:8])
-    out = json.load(open(path)) if os.path.exists(path) else {}
-    out.update({"library": lib_identity.identity(), "footprint_metres": CAR, "chassis": CHASSIS, "headings": HEADINGS})
-    out["resources"] = resources(new, parent)
+    args = bk.read_args(sys.argv[1:], configs=CONFIGS, turns=TURNS)
+    parent = args["parent"]
+    spawn = lambda mode, a, **kw: bk.spawn(__file__, mode, a, CHILD_TIMEOUT, **kw)
+    report, configs = bk.product_report(
+        "attitude", args, {"footprint_metres": CAR, "chassis": CHASSIS, "headings": HEADINGS}, lambda k: "k_attitude" in k,
+        ["footprints and chassis of other sizes", "maps larger than c4's 512 x 512", "shuffled poses",
+         "static instead of dynamic LDS in k_attitude", "a summary made by a second kernel"])
     if parent:
-        out["parent_library"] = {"lib_sha256": lib_identity.sha256_file(parent)}
-    out.setdefault("not_measured", ["footprints and chassis of other sizes", "maps larger than c4's 512 x 512", "shuffled poses",
-                                    "static instead of dynamic LDS in k_attitude", "a summary made by a second kernel"])
-    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-
-    def save():
-        with open(path, "w") as f:                                  # (after every part: a run that ends early leaves what it has)
-            f.write(json.dumps(out, indent=1) + "\n")
-    save()
-    if only_resources:
-        out.setdefault("configs", "not measured")
-        save()
+        report.out["resources"]["other_kernels"]["table"] = _table(parent)
+        report.save()
+    if configs is None:
         return
-    out["configs"] = {}
-    for name, steps in CONFIGS:
-        res = _spawn("score", (name, 0))
+    for name in args["configs"]:
+        steps = CONFIGS[name]
+        res = spawn("score", (name, 0))
         with tempfile.TemporaryDirectory() as d:
-            prof = _spawn("score", (name, 1), profile_dir=d)
+            prof = spawn("score", (name, 1), profile_dir=d)
             kernel = _kernel_times(d, prof["calls"])
         for k, rec in enumerate(res["scoring"]):
             rec["kernels"] = kernel[k] if kernel else "not measured (the trace did not hold the expected launches)"
-        out["configs"][name] = res
-        save()
-        runs = {"without": [], "with": [], "parent_without": []}
-        for rnd in range(5):                                        # alternating: parent, without, with, ...
-            if parent:
-                runs["parent_without"].append(_spawn("step", (name, steps, 0), lib=parent))
-            runs["without"].append(_spawn("step", (name, steps, 0)))
-            runs["with"].append(_spawn("step", (name, steps, 1)))
-        step = {}
-        for who, rs in runs.items():
-            if rs:
-                meds = [r["us_per_step_median"] for r in rs]
-                step[who] = {"run_medians_us": meds, "median": _median(meds), "min": min(meds), "max": max(meds)}
+        configs[name] = res
+        report.save()
+        runs = bk.alternate(args["turns"], {"parent_without": parent and (lambda: spawn("step", (name, steps, 0), lib=parent)),
+                                            "without": lambda: spawn("step", (name, steps, 0)), "with": lambda: spawn("step", (name, steps, 1))})
+        step = bk.spreads(runs)
         step["query_adds_us_per_step"] = round(step["with"]["median"] - step["without"]["median"], 2)
-        if parent:
-            p = step["parent_without"]
-            step["without_inside_parents_own_spread"] = bool(p["min"] <= step["without"]["median"] <= p["max"])
-            step["without_minus_parent_median_us"] = round(step["without"]["median"] - p["median"], 2)
-        res["step: scan + combine_maps_device (+ score_attitude %d x %d)" % SHAPES[0]] = step
-        save()
-    print(json.dumps(out, indent=1))
+        res["step: scan + combine_maps_device (+ score_attitude %d x %d)" % SHAPES[0]] = bk.against_parent(step, "without", "parent_without", "without_")
+        report.save()
+    print(json.dumps(report.out, indent=1))
 
 
 if __name__ == "__main__":

@@ -16,20 +16,15 @@ process, every child under a `timeout` of its own, and the first child that fail
   resources  tools/kernel_regs.py: the new kernels, and registers, scratch, LDS and code size of every kernel outside the new unit on
              the parent and on this library (--resources alone: no GPU needed)
 
-    tools/attitude_volume_bench.py [--resources] [--parent LIB] [--configs m256,c4] [out.json]   (default: profiles/attitude_volume_<lib sha8>.json)
+    tools/attitude_volume_bench.py [--resources] [--parent LIB] [--configs m256,c4] [--turns N] [out.json]   (default: profiles/attitude_volume_<lib sha8>.json)
 """
-import csv
-import glob
 import json
-import os
-import subprocess
 import sys
 import tempfile
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "g-vom_amd"))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+import benchkit as bk
+
 CONFIGS = {"m256": 60, "c4": 24}                          # config: timed steps per repetition
 CAR = dict(front=3.6, rear=1.0, half_width=1.1)
 CHASSIS = dict(front_axle=2.7, rear_axle=0.0, track=1.7, belly_height=0.25, max_pitch=0.35, max_roll=0.3, min_clearance=0.1)
@@ -37,33 +32,7 @@ SHAPES = ((16, 2.0), (64, 6.0))                           # (headings, minimum t
 CHILD_TIMEOUT = 300                                       # seconds, per child process
 KERNELS = ("k_volume_attitude_table", "k_volume_attitude", "k_attitude_ground", "k_cspace_attitude", "k_cspace", "k_attitude")
 NEW_UNIT = ("k_volume_attitude", "k_cspace_attitude")
-
-
-def _median(v):
-    v = sorted(v)
-    return v[len(v) // 2] if len(v) % 2 else 0.5 * (v[len(v) // 2 - 1] + v[len(v) // 2])
-
-
-def _gvom():
-    """The binding, also over the parent's library: it is bound with the entry points it has."""
-    import ctypes
-    import gvom
-    lib = ctypes.CDLL(gvom.library_path())
-    gvom.ABI = [e for e in gvom.ABI if hasattr(lib, e[0])]
-    return gvom
-
-
-def _setup(name):
-    import numpy as np
-    import torch
-    import synth
-    torch.cuda.init()
-    gvom = _gvom()
-    params, scans = synth.config_inputs(name, n_scans=3)
-    dev = [(torch.from_numpy(np.ascontiguousarray(pc)).cuda(), ego, tf) for pc, ego, tf in scans]
-    torch.cuda.synchronize()
-    g = gvom.Gvom(*params, voxel_statistics=False)
-    return np, torch, gvom, g, dev
+TURNS = 5
 
 
 def _tables(gvom, g, H, radius):
@@ -72,25 +41,6 @@ def _tables(gvom, g, H, radius):
     g.set_chassis(gvom.chassis(**CHASSIS))
     g.set_primitives(gvom.arc_primitives(H, radius, g.xy_resolution, reach=4))
     return footprint
-
-
-def _sync(g):
-    g._check(g._lib.gvom_sync(g._h))
-
-
-def _timed(g, call, reps=10, rounds=5):
-    """microseconds per call, enqueue to the drained stream, `rounds` times over `reps` calls"""
-    for _ in range(3):
-        call()
-    _sync(g)
-    us = []
-    for _ in range(rounds):
-        t0 = time.perf_counter()
-        for _ in range(reps):
-            call()
-        _sync(g)
-        us.append(round((time.perf_counter() - t0) / reps * 1e6, 1))
-    return {"us": us, "us_median": _median(us)}
 
 
 def _torch_volume(torch, np, ground, footprint, g, chassis):
@@ -149,10 +99,9 @@ def _torch_volume(torch, np, ground, footprint, g, chassis):
 
 
 def child_call(name, profiled):
-    np, torch, gvom, g, dev = _setup(name)
-    for t, ego, tf in dev:
-        g.process_pointcloud_device(t.data_ptr(), t.shape[0], np.float32, ego, tf)
-        m = g.combine_maps_device()
+    np, torch, gvom, g, dev = bk.setup(name)
+    for scan in dev:
+        m = bk.scan_combine(np, g, scan)
     ego = dev[2][1]
     xy, res = g.xy_size, g.xy_resolution
     results, calls = {}, 13
@@ -169,16 +118,16 @@ def child_call(name, profiled):
                 for _ in range(calls):
                     field.pose_field(goal, goals_in_cells=True, attitude=vol, tilt_weight=3).release()
             field.release()
-            _sync(g)
+            bk.sync(g)
             continue
         out = {"xy": xy, "H": H, "states": H * xy * xy, "footprint_cells_heading_0": int(footprint[0][1]), "footprint_cells_mean": round(float(np.diff(footprint[0]).mean()), 1)}
-        out["call"] = _timed(g, volume)
+        out["call"] = bk.timed(g, volume)
         vol = m.attitude_volume()
         status, tilt, counts = vol.copy_to_host()
         out["states_per_status"] = counts[:7].tolist()
         out["allocations"] = g.get_tuning("attitude_volume_allocations")
-        out["pose_field_without_volume"] = _timed(g, lambda: field.pose_field(goal, goals_in_cells=True).release(), reps=5)
-        out["pose_field_with_volume"] = _timed(g, lambda: field.pose_field(goal, goals_in_cells=True, attitude=vol, tilt_weight=3).release(), reps=5)
+        out["pose_field_without_volume"] = bk.timed(g, lambda: field.pose_field(goal, goals_in_cells=True).release(), reps=5)
+        out["pose_field_with_volume"] = bk.timed(g, lambda: field.pose_field(goal, goals_in_cells=True, attitude=vol, tilt_weight=3).release(), reps=5)
         with field.pose_field(goal, goals_in_cells=True) as f0, field.pose_field(goal, goals_in_cells=True, attitude=vol, tilt_weight=3) as f1:
             out["pose_field_reached_states"] = {"without": f0.reached, "with": f1.reached, "rounds_without": f0.rounds, "rounds_with": f1.rounds}
         try:                                                              # the same volume through score_attitude() on the cell-centre poses
@@ -189,7 +138,7 @@ def child_call(name, profiled):
             poses[..., 2] = (np.arange(H) * (2.0 * np.pi) / H).astype(np.float32)[:, None, None]
             poses = poses.reshape(H * xy, xy, 3)
             score = lambda: m.score_attitude(poses).release()
-            rec = _timed(g, score, reps=3, rounds=3)
+            rec = bk.timed(g, score, reps=3, rounds=3)
             with m.score_attitude(poses) as s:
                 pose_status = s.status.copy_to_host().reshape(H, xy, xy)
             rec["pose_bytes_uploaded"] = int(poses.nbytes)
@@ -210,7 +159,7 @@ def child_call(name, profiled):
                 _torch_volume(torch, np, ground, footprint, g, chassis)
                 torch.cuda.synchronize()
                 us.append(round((time.perf_counter() - t0) * 1e6, 1))
-            out["torch_same_volume"] = {"us": us, "us_median": _median(us), "status_equal_to_the_product": bool(np.array_equal(ts.cpu().numpy(), status)),
+            out["torch_same_volume"] = {"us": us, "us_median": bk.median(us), "status_equal_to_the_product": bool(np.array_equal(ts.cpu().numpy(), status)),
                                         "tilt_equal_to_the_product": bool(np.array_equal(tt.cpu().numpy(), tilt))}
             del height, inferred, ground, ts, tt
         except Exception as e:
@@ -222,51 +171,17 @@ def child_call(name, profiled):
 
 
 def child_step(name, steps):
-    np, torch, gvom, g, dev = _setup(name)
+    np, torch, gvom, g, dev = bk.setup(name)
 
     def step(k):
-        t, ego, tf = dev[k % 3]
-        g.process_pointcloud_device(t.data_ptr(), t.shape[0], np.float32, ego, tf)
-        g.combine_maps_device().release()
-
-    for k in range(min(6, steps)):
-        step(k)
-    _sync(g)
-    us = []
-    for rep in range(3):
-        t0 = time.perf_counter()
-        for k in range(steps):
-            step(k)
-        _sync(g)
-        us.append(round((time.perf_counter() - t0) / steps * 1e6, 2))
-    return {"us_per_step": us, "us_per_step_median": _median(us), "steps": steps}
+        bk.scan_combine(np, g, dev[k % 3]).release()
+    return bk.step_loop(g, step, steps, warm=min(6, steps))
 
 
-def _spawn(mode, args, profile_dir=None, lib=None):
-    """one child under its own time limit; a child that fails (or runs into the limit) ends the whole run"""
-    cmd = [sys.executable, os.path.abspath(__file__), "--child", mode] + [str(a) for a in args]
-    if profile_dir:
-        cmd = ["rocprofv3", "--kernel-trace", "--output-format", "csv", "-d", profile_dir, "--"] + cmd
-    cmd = ["timeout", "-k", "10", str(CHILD_TIMEOUT)] + cmd
-    env = dict(os.environ, GVOM_HIP_LIBRARY=os.path.abspath(lib)) if lib else None
-    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=env)
-    if r.returncode != 0:
-        raise SystemExit("%s %r failed (%d): nothing more is started\n%s" % (mode, args, r.returncode, r.stderr[-3000:]))
-    line = [ln for ln in r.stdout.splitlines() if ln.startswith("RESULT ")][-1]
-    return json.loads(line[7:])
-
-
-def _kernel_times(profile_dir, calls):
+def _kernel_times(profile_dir):
     """per shape: the kernels' microseconds per launch (median) and how often each ran; the shapes follow one another in the trace, H = 16
     first -- the launches of k_volume_attitude are split evenly between them"""
-    rows = []
-    for f in glob.glob(os.path.join(profile_dir, "**", "*kernel_trace.csv"), recursive=True):
-        for r in csv.DictReader(open(f)):
-            name = r["Kernel_Name"].split("(")[0]
-            key = [k for k in KERNELS if name == k or name.endswith(" " + k)]
-            if key:
-                rows.append((int(r["Start_Timestamp"]), key[0], (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3))
-    rows.sort()
+    rows = bk.kernel_trace_rows(profile_dir, KERNELS, exact=True)
     out = {}
     for k in KERNELS:
         us = [u for _, kk, u in rows if kk == k]
@@ -275,91 +190,37 @@ def _kernel_times(profile_dir, calls):
             continue
         for n, (H, _) in enumerate(SHAPES):
             part = us[n * per:(n + 1) * per]
-            out.setdefault("H%d" % H, {})[k] = {"launches": len(part), "median_us_per_launch": round(_median(part), 2), "min_us": round(min(part), 2)}
+            out.setdefault("H%d" % H, {})[k] = {"launches": len(part), "median_us_per_launch": round(bk.median(part), 2), "min_us": round(min(part), 2)}
     return out or None
 
 
-def resources(new, parent):
-    """the new unit's kernels, and every other kernel on the parent and on this library: registers, scratch, LDS, code size"""
-    import kernel_regs
-    mine = kernel_regs.kernels(new)
-    ours = lambda k: any(n in k for n in NEW_UNIT)
-    out = {"new_kernels": {k: v for k, v in mine.items() if ours(k)}}
-    if parent:
-        theirs = kernel_regs.kernels(parent)
-        rest = {k: v for k, v in mine.items() if not ours(k)}
-        keys = ("vgpr", "sgpr", "scratch", "lds", "code")
-        changed = {k: {"parent": theirs.get(k), "new": v} for k, v in rest.items() if any((theirs.get(k) or {}).get(q) != v.get(q) for q in keys)}
-        out["other_kernels"] = {"count": len(rest), "identical_to_parent": len(rest) - len(changed), "changed": changed,
-                                "only_on_parent": sorted(k for k in theirs if k not in mine)}
-    return out
-
-
 def main():
-    if len(sys.argv) > 2 and sys.argv[1] == "--child":
-        mode, a = sys.argv[2], sys.argv[3:]
-        res = child_call(a[0], a[1] == "1") if mode == "call" else child_step(a[0], int(a[1]))
-        print("RESULT " + json.dumps(res))
+    if bk.child(sys.argv[1:], {"call": lambda a: child_call(a[0], a[1] == "1"), "step": lambda a: child_step(a[0], int(a[1]))}):
         return
-    import lib_identity
-    args = sys.argv[1:]
-    parent, only_resources, configs = None, False, list(CONFIGS)
-    while args and args[0] in ("--parent", "--resources", "--configs"):
-        if args[0] == "--parent":
-            parent, args = args[1], args[2:]
-        elif args[0] == "--configs":
-            configs, args = args[1].split(","), args[2:]
-        else:
-            only_resources, args = True, args[1:]
-    new = os.path.join(ROOT, "g-vom_amd", "lib", "libgvom_hip.so")
-    path = args[0] if args else os.path.join(ROOT, "profiles", "attitude_volume_%s.json" % (lib_identity.identity().get("lib_sha256") or "unknown")[:8])
-    out = json.load(open(path)) if os.path.exists(path) else {}
-    out.update({"library": lib_identity.identity(), "car_m": CAR, "chassis": CHASSIS, "shapes": [list(s) for s in SHAPES]})
-    out["resources"] = resources(new, parent)
-    if parent:
-        out["parent_library"] = {"lib_sha256": lib_identity.sha256_file(parent)}
-    out.setdefault("not_measured", ["c5", "windows other than 256 and 512 cells", "the host and device-pointer routes", "AV_DEPTH other than 4",
-                                    "the (U, V) table in LDS instead of scalar loads (not built)", "hardware counters",
-                                    "score_attitude() agreement at a resolution whose cell centres are float32 numbers (the GPU test does that at 0.5 m)"])
-    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-
-    def save():
-        with open(path, "w") as f:                                  # (after every part: a run that ends early leaves what it has)
-            f.write(json.dumps(out, indent=1) + "\n")
-    save()
-    if only_resources:
-        out.setdefault("configs", "not measured")
-        save()
+    args = bk.read_args(sys.argv[1:], configs=CONFIGS, turns=TURNS)
+    parent = args["parent"]
+    spawn = lambda mode, a, **kw: bk.spawn(__file__, mode, a, CHILD_TIMEOUT, **kw)
+    report, configs = bk.product_report(
+        "attitude_volume", args, {"car_m": CAR, "chassis": CHASSIS, "shapes": [list(s) for s in SHAPES]}, lambda k: any(n in k for n in NEW_UNIT),
+        ["c5", "windows other than 256 and 512 cells", "the host and device-pointer routes", "AV_DEPTH other than 4",
+         "the (U, V) table in LDS instead of scalar loads (not built)", "hardware counters",
+         "score_attitude() agreement at a resolution whose cell centres are float32 numbers (the GPU test does that at 0.5 m)"])
+    if configs is None:
         return
-    if not isinstance(out.get("configs"), dict):
-        out["configs"] = {}
-    for name in configs:
-        steps = CONFIGS[name]
-        res = _spawn("call", (name, 0))
+    for name in args["configs"]:
+        res = spawn("call", (name, 0))
         with tempfile.TemporaryDirectory() as d:
-            prof = _spawn("call", (name, 1), profile_dir=d)
-            kernel = _kernel_times(d, prof["calls"])
+            spawn("call", (name, 1), profile_dir=d)
+            kernel = _kernel_times(d)
         for key in res:
             res[key]["kernels"] = (kernel or {}).get(key) or "not measured (the trace did not hold the expected launches)"
-        out["configs"][name] = res
-        save()
-        runs = {"this": [], "parent": []}
-        for rnd in range(5):                                        # alternating: parent, this, ...
-            if parent:
-                runs["parent"].append(_spawn("step", (name, steps), lib=parent))
-            runs["this"].append(_spawn("step", (name, steps)))
-        step = {}
-        for who, rs in runs.items():
-            if rs:
-                meds = [r["us_per_step_median"] for r in rs]
-                step[who] = {"run_medians_us": meds, "median": _median(meds), "min": min(meds), "max": max(meds)}
-        if parent:
-            p = step["parent"]
-            step["this_inside_parents_own_spread"] = bool(p["min"] <= step["this"]["median"] <= p["max"])
-            step["this_minus_parent_median_us"] = round(step["this"]["median"] - p["median"], 2)
-        res["step: scan + combine_maps_device"] = step
-        save()
-    print(json.dumps(out, indent=1))
+        configs[name] = res
+        report.save()
+        runs = bk.alternate(args["turns"], {"parent": parent and (lambda: spawn("step", (name, CONFIGS[name]), lib=parent)),
+                                            "this": lambda: spawn("step", (name, CONFIGS[name]))})
+        res["step: scan + combine_maps_device"] = bk.against_parent(bk.spreads(runs), "this", "parent", "this_")
+        report.save()
+    print(json.dumps(report.out, indent=1))
 
 
 if __name__ == "__main__":

@@ -9,27 +9,17 @@ unbounded and with max_distance = robot_radius, every loop in a fresh child proc
             library's squared cells once before the timing.
   registers tools/kernel_regs.py on the library's k_clearance* kernels
 
-    tools/clearance_bench.py [out.json]      (default: profiles/clearance_<lib sha8>.json)
+    tools/clearance_bench.py [--configs m256,c4,c5] [out.json]      (default: profiles/clearance_<lib sha8>.json)
 """
-import csv
-import glob
 import json
-import os
-import subprocess
 import sys
 import tempfile
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "g-vom_amd"))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-CONFIGS = (("m256", 400), ("c4", 100), ("c5", 30))          # (config, timed steps per repetition)
+import benchkit as bk
+
+CONFIGS = {"m256": 400, "c4": 100, "c5": 30}                # config: timed steps per repetition
 THRESHOLD = 50
-
-
-def _median(v):
-    v = sorted(v)
-    return v[len(v) // 2] if len(v) % 2 else 0.5 * (v[len(v) // 2 - 1] + v[len(v) // 2])
+CHILD_TIMEOUT = 900                                         # seconds, per child process
 
 
 def _torch_clearance(torch, pos, neg, thr, res, cap2):
@@ -54,29 +44,14 @@ def _torch_clearance(torch, pos, neg, thr, res, cap2):
     return dist, d2
 
 
-def _setup(name, poses):
-    import numpy as np
-    import torch
-    import gvom
-    import synth
-    torch.cuda.init()
-    params, scans = synth.config_inputs(name, n_scans=poses)
-    dev = [(torch.from_numpy(np.ascontiguousarray(pc)).cuda(), ego, tf) for pc, ego, tf in scans]
-    torch.cuda.synchronize()
-    g = gvom.Gvom(*params, voxel_statistics=False)
-    return np, torch, gvom, g, dev
-
-
 def child_step(name, steps):
     poses = 3
-    np, torch, gvom, g, dev = _setup(name, poses)
+    np, torch, gvom, g, dev = bk.setup(name, poses)
     radius = float(g.robot_radius)
     cap2 = gvom._clearance_cap(radius, g.xy_resolution)
 
     def scan(k):
-        t, ego, tf = dev[k % poses]
-        g.process_pointcloud_device(t.data_ptr(), t.shape[0], np.float32, ego, tf)
-        return g.combine_maps_device()
+        return bk.scan_combine(np, g, dev[k % poses])
 
     def plain(k):
         scan(k).release()
@@ -116,84 +91,43 @@ def child_step(name, steps):
              ("+torch transform unbounded", in_torch(0), max(steps // 10, 5)),
              ("+torch transform max_distance=robot_radius", in_torch(cap2), max(steps // 10, 5)))
     for label, step, n in loops:
-        for k in range(min(20, n)):
-            step(k)
-        g._check(g._lib.gvom_sync(g._h))
-        torch.cuda.synchronize()
-        us = []
-        for rep in range(3):
-            t0 = time.perf_counter()
-            for k in range(n):
-                step(k)
-            g._check(g._lib.gvom_sync(g._h))
-            torch.cuda.synchronize()
-            us.append(round((time.perf_counter() - t0) / n * 1e6, 2))
-        out[label] = {"us_per_step": us, "us_per_step_median": _median(us), "steps": n}
+        out[label] = bk.step_loop(g, step, n, warm=min(20, n), also=torch.cuda.synchronize)
     return out
 
 
 def child_kernels(name, capped):
     """Run under rocprofv3: the calls whose kernels are to be timed."""
-    np, torch, gvom, g, dev = _setup(name, 3)
-    for t, ego, tf in dev:
-        g.process_pointcloud_device(t.data_ptr(), t.shape[0], np.float32, ego, tf)
-        m = g.combine_maps_device()
+    np, torch, gvom, g, dev = bk.setup(name)
+    for scan in dev:
+        m = bk.scan_combine(np, g, scan)
     for _ in range(50):
         m.clearance(THRESHOLD, max_distance=float(g.robot_radius) if capped else None).release()
-    g._check(g._lib.gvom_sync(g._h))
+    bk.sync(g)
     return {"calls": 50}
 
 
-def _spawn(mode, args, profile_dir=None):
-    cmd = [sys.executable, os.path.abspath(__file__), "--child", mode] + [str(a) for a in args]
-    if profile_dir:
-        cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", profile_dir, "--"] + cmd
-    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
-    if r.returncode != 0:
-        raise SystemExit("%s %r failed (%d):\n%s" % (mode, args, r.returncode, r.stderr[-3000:]))
-    line = [ln for ln in r.stdout.splitlines() if ln.startswith("RESULT ")][-1]
-    return json.loads(line[7:])
-
-
-def _kernel_stats(profile_dir):
-    rows = {}
-    for f in glob.glob(os.path.join(profile_dir, "**", "*kernel_stats.csv"), recursive=True):
-        for r in csv.DictReader(open(f)):
-            if "k_clearance" in r["Name"]:
-                rows[r["Name"].split("(")[0]] = {"calls": int(r["Calls"]), "avg_us": round(float(r["AverageNs"]) / 1e3, 2),
-                                                 "min_us": round(float(r["MinNs"]) / 1e3, 2), "max_us": round(float(r["MaxNs"]) / 1e3, 2)}
-    return rows
-
-
 def main():
-    if len(sys.argv) > 2 and sys.argv[1] == "--child":
-        mode = sys.argv[2]
-        res = child_step(sys.argv[3], int(sys.argv[4])) if mode == "step" else child_kernels(sys.argv[3], sys.argv[4] == "1")
-        print("RESULT " + json.dumps(res))
+    if bk.child(sys.argv[1:], {"step": lambda a: child_step(a[0], int(a[1])), "kernels": lambda a: child_kernels(a[0], a[1] == "1")}):
         return
     import kernel_regs
-    import lib_identity
-    new = os.path.join(ROOT, "g-vom_amd", "lib", "libgvom_hip.so")
-    out = {"library": lib_identity.identity(), "density_threshold": THRESHOLD,
-           "registers": {k: v for k, v in kernel_regs.kernels(new).items() if "k_clearance" in k}, "configs": {}}
-    path = sys.argv[1] if len(sys.argv) > 1 else os.path.join(
-        ROOT, "profiles", "clearance_%s.json" % (out["library"].get("lib_sha256") or "unknown")[:8])
-    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-    for name, steps in CONFIGS:
-        res = _spawn("step", (name, steps))
+    args = bk.read_args(sys.argv[1:], has_parent=False, has_resources=False, configs=CONFIGS)
+    report = bk.Report("clearance", args["path"], fresh=True)
+    out = report.out
+    out.update({"density_threshold": THRESHOLD, "registers": {k: v for k, v in kernel_regs.kernels(bk.NEW_LIB).items() if "k_clearance" in k}, "configs": {}})
+    for name in args["configs"]:
+        res = bk.spawn(__file__, "step", (name, CONFIGS[name]), CHILD_TIMEOUT)
         res["kernel_us"] = {}
         for label, capped in (("unbounded", 0), ("max_distance=robot_radius", 1)):
             with tempfile.TemporaryDirectory() as d:
-                _spawn("kernels", (name, capped), profile_dir=d)
-                stats = _kernel_stats(d)
+                bk.spawn(__file__, "kernels", (name, capped), CHILD_TIMEOUT, profile_dir=d, stats=True)
+                stats = bk.kernel_stats(d, ("k_clearance",))
             stats["both"] = round(sum(v["avg_us"] for v in stats.values()), 2)
             res["kernel_us"][label] = stats
         base = res["scan+combine_maps_device"]["us_per_step_median"]
         res["added_us_per_step"] = {k[1:]: round(v["us_per_step_median"] - base, 2) for k, v in res.items()
                                     if k.startswith("+") and isinstance(v, dict)}
         out["configs"][name] = res
-        with open(path, "w") as f:                                  # (after every config: a long run leaves what it has)
-            f.write(json.dumps(out, indent=1) + "\n")
+        report.save()                                              # (after every config: a long run leaves what it has)
     print(json.dumps(out, indent=1))
 
 

@@ -12,44 +12,23 @@ unblocked cell nearest the ego, and the cell of its field furthest from it ("far
              Dijkstra (scipy.sparse.csgraph.dijkstra where importable, otherwise the heap form of tests/costfield_ref.py)
   registers  tools/kernel_regs.py on the four kernels
 
-    tools/costfield_bench.py [out.json]      (default: profiles/costfield_<lib sha8>.json)
+    tools/costfield_bench.py [--configs m256,c4,c5] [out.json]      (default: profiles/costfield_<lib sha8>.json)
 """
-import csv
-import glob
 import json
 import os
-import subprocess
 import sys
 import tempfile
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "g-vom_amd"))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-CONFIGS = (("m256", 100), ("c4", 40), ("c5", 15))           # (config, timed steps per repetition)
+import benchkit as bk
+
+sys.path.insert(0, os.path.join(bk.ROOT, "tests"))
+CONFIGS = {"m256": 100, "c4": 40, "c5": 15}                 # config: timed steps per repetition
+CHILD_TIMEOUT = 900                                         # seconds, per child process
 THRESHOLD, SOFT = 50, 10
 KERNELS = ("k_travcost", "k_ctg_", "k_clearance")
 STEPS = ((1, 0), (1, 1), (0, 1), (-1, 1), (-1, 0), (-1, -1), (0, -1), (1, -1))
 UNREACHED = 2 ** 31 - 1
-
-
-def _median(v):
-    v = sorted(v)
-    return v[len(v) // 2] if len(v) % 2 else 0.5 * (v[len(v) // 2 - 1] + v[len(v) // 2])
-
-
-def _setup(name):
-    import numpy as np
-    import torch
-    import gvom
-    import synth
-    torch.cuda.init()
-    params, scans = synth.config_inputs(name, n_scans=3)
-    dev = [(torch.from_numpy(np.ascontiguousarray(pc)).cuda(), ego, tf) for pc, ego, tf in scans]
-    torch.cuda.synchronize()
-    g = gvom.Gvom(*params, voxel_statistics=False)
-    return np, torch, gvom, g, dev
 
 
 def _field_args(g):
@@ -129,12 +108,10 @@ def _cpu_dijkstra(np, c, goal):
 
 
 def child_step(name, steps):
-    np, torch, gvom, g, dev = _setup(name)
+    np, torch, gvom, g, dev = bk.setup(name)
 
     def scan(k):
-        t, ego, tf = dev[k % 3]
-        g.process_pointcloud_device(t.data_ptr(), t.shape[0], np.float32, ego, tf)
-        return g.combine_maps_device()
+        return bk.scan_combine(np, g, dev[k % 3])
 
     for k in range(3):
         m = scan(k)
@@ -149,7 +126,7 @@ def child_step(name, steps):
             rec.setdefault("call_us", []).append(round((time.perf_counter() - t0) * 1e6, 1))
             if trial < 6:
                 f.release()
-        rec["call_us_median"] = _median(rec["call_us"][1:])
+        rec["call_us_median"] = bk.median(rec["call_us"][1:])
         rec.update(rounds=f.rounds, converged=f.converged, reached=f.reached, goals_seeded=f.goals_seeded,
                    tile_relaxations=g.get_tuning("cost_to_go_tiles"), tiles=((g.xy_size + 31) // 32) ** 2)
         D, _, c = f.copy_to_host()
@@ -181,7 +158,7 @@ def child_step(name, steps):
             us.append(round((time.perf_counter() - t0) * 1e6, 1))
             wide = {"rounds": f.rounds, "reached": f.reached, "tile_relaxations": g.get_tuning("cost_to_go_tiles")}
             f.release()
-        rec["without_inflation"] = dict(wide, call_us_median=_median(us[1:]))
+        rec["without_inflation"] = dict(wide, call_us_median=bk.median(us[1:]))
         out["field"][label] = rec
     # the alternatives tried: inner bound and batch length, whole call towards the far goal (tile size 32 and all-tiles launches
     # are the only forms built)
@@ -197,7 +174,7 @@ def child_step(name, steps):
             us.append(round((time.perf_counter() - t0) * 1e6, 1))
             rounds, tiles = f.rounds, g.get_tuning("cost_to_go_tiles")
             f.release()
-        alts["inner %d, batch %d" % (inner, batch)] = {"call_us_median": _median(us[1:]), "rounds": rounds, "tile_relaxations": tiles}
+        alts["inner %d, batch %d" % (inner, batch)] = {"call_us_median": bk.median(us[1:]), "rounds": rounds, "tile_relaxations": tiles}
     g.set_tuning("cost_to_go_inner", 0)
     g.set_tuning("cost_to_go_batch", 0)
     out["alternatives_far_goal"] = alts
@@ -215,85 +192,49 @@ def child_step(name, steps):
 
     loops = [("scan+combine_maps_device", plain)] + [("+field to the %s goal" % label, with_field(goal)) for label, goal in goals.items()]
     for label, step in loops:
-        for k in range(min(10, steps)):
-            step(k)
-        g._check(g._lib.gvom_sync(g._h))
-        us = []
-        for rep in range(3):
-            t0 = time.perf_counter()
-            for k in range(steps):
-                step(k)
-            g._check(g._lib.gvom_sync(g._h))
-            us.append(round((time.perf_counter() - t0) / steps * 1e6, 2))
-        out[label] = {"us_per_step": us, "us_per_step_median": _median(us)}
+        out[label] = bk.step_loop(g, step, steps, warm=min(10, steps))
+        del out[label]["steps"]                                # (the record's own "steps" says it)
     return out
 
 
 def child_kernels(name, gx, gy):
     """Run under rocprofv3: the calls whose kernels are to be timed."""
-    np, torch, gvom, g, dev = _setup(name)
-    for t, ego, tf in dev:
-        g.process_pointcloud_device(t.data_ptr(), t.shape[0], np.float32, ego, tf)
-        m = g.combine_maps_device()
+    np, torch, gvom, g, dev = bk.setup(name)
+    for scan in dev:
+        m = bk.scan_combine(np, g, scan)
     for _ in range(20):
         m.cost_to_go([(gx, gy)], **_field_args(g)).release()
-    g._check(g._lib.gvom_sync(g._h))
+    bk.sync(g)
     return {"calls": 20}
 
 
-def _spawn(mode, args, profile_dir=None):
-    cmd = [sys.executable, os.path.abspath(__file__), "--child", mode] + [str(a) for a in args]
-    if profile_dir:
-        cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", profile_dir, "--"] + cmd
-    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
-    if r.returncode != 0:
-        raise SystemExit("%s %r failed (%d):\n%s" % (mode, args, r.returncode, r.stderr[-3000:]))
-    line = [ln for ln in r.stdout.splitlines() if ln.startswith("RESULT ")][-1]
-    return json.loads(line[7:])
-
-
-def _kernel_stats(profile_dir, calls):
-    rows = {}
-    for f in glob.glob(os.path.join(profile_dir, "**", "*kernel_stats.csv"), recursive=True):
-        for r in csv.DictReader(open(f)):
-            if any(k in r["Name"] for k in KERNELS):
-                rows[r["Name"].split("(")[0]] = {"launches_per_call": round(int(r["Calls"]) / calls, 2), "avg_us": round(float(r["AverageNs"]) / 1e3, 2),
-                                                 "us_per_call": round(float(r["TotalDurationNs"]) / 1e3 / calls, 2)}
-    return rows
-
-
 def main():
-    if len(sys.argv) > 2 and sys.argv[1] == "--child":
-        mode = sys.argv[2]
-        res = child_step(sys.argv[3], int(sys.argv[4])) if mode == "step" else child_kernels(sys.argv[3], int(sys.argv[4]), int(sys.argv[5]))
-        print("RESULT " + json.dumps(res))
+    if bk.child(sys.argv[1:], {"step": lambda a: child_step(a[0], int(a[1])), "kernels": lambda a: child_kernels(a[0], int(a[1]), int(a[2]))}):
         return
     import kernel_regs
-    import lib_identity
-    new = os.path.join(ROOT, "g-vom_amd", "lib", "libgvom_hip.so")
-    out = {"library": lib_identity.identity(), "density_threshold": THRESHOLD, "soft_weight": SOFT, "inflation": "robot_radius",
-           "registers": {k: v for k, v in kernel_regs.kernels(new).items() if "k_ctg_" in k or "k_travcost" in k},
-           "unmeasured": ["tile sizes other than 32 x 32 and a launch over a compacted tile list (neither is built)",
-                          "maps larger than c5's 1024 x 1024"],
-           "configs": {}}
-    path = sys.argv[1] if len(sys.argv) > 1 else os.path.join(
-        ROOT, "profiles", "costfield_%s.json" % (out["library"].get("lib_sha256") or "unknown")[:8])
-    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-    for name, steps in CONFIGS:
-        res = _spawn("step", (name, steps))
+    args = bk.read_args(sys.argv[1:], has_parent=False, has_resources=False, configs=CONFIGS)
+    report = bk.Report("costfield", args["path"], fresh=True)
+    out = report.out
+    out.update({"density_threshold": THRESHOLD, "soft_weight": SOFT, "inflation": "robot_radius",
+                "registers": {k: v for k, v in kernel_regs.kernels(bk.NEW_LIB).items() if "k_ctg_" in k or "k_travcost" in k},
+                "unmeasured": ["tile sizes other than 32 x 32 and a launch over a compacted tile list (neither is built)",
+                               "maps larger than c5's 1024 x 1024"],
+                "configs": {}})
+    for name in args["configs"]:
+        res = bk.spawn(__file__, "step", (name, CONFIGS[name]), CHILD_TIMEOUT)
         res["kernel_us"] = {}
         for label, goal in res["goals"].items():
             with tempfile.TemporaryDirectory() as d:
-                calls = _spawn("kernels", (name, goal[0], goal[1]), profile_dir=d)["calls"]
-                stats = _kernel_stats(d, calls)
+                calls = bk.spawn(__file__, "kernels", (name, goal[0], goal[1]), CHILD_TIMEOUT, profile_dir=d, stats=True)["calls"]
+                stats = {k: {"launches_per_call": round(v["calls"] / calls, 2), "avg_us": v["avg_us"], "us_per_call": round(v["total_us"] / calls, 2)}
+                         for k, v in bk.kernel_stats(d, KERNELS, total=True).items()}
             stats["all"] = round(sum(v["us_per_call"] for v in stats.values()), 2)
             res["kernel_us"][label] = stats
         base = res["scan+combine_maps_device"]["us_per_step_median"]
         res["added_us_per_step"] = {k[1:]: round(v["us_per_step_median"] - base, 2) for k, v in res.items()
                                     if k.startswith("+") and isinstance(v, dict)}
         out["configs"][name] = res
-        with open(path, "w") as f:                                  # (after every config: a long run leaves what it has)
-            f.write(json.dumps(out, indent=1) + "\n")
+        report.save()                                              # (after every config: a long run leaves what it has)
     print(json.dumps(out, indent=1))
 
 

@@ -11,43 +11,34 @@ fresh child process, the two libraries alternating (parent, new, parent, new):
                    dead-column handling ("occupancy_clear" 0 / 1, the second with its fill kernel), k_read_dense on the same map;
                    bytes moved (tile tags + live state rows + V output bytes) and the bandwidth that makes
 
-    tools/device_products_bench.py PARENT_LIB [out.json]      (default: profiles/device_products_<lib sha8>.json)
+    tools/device_products_bench.py PARENT_LIB [--turns N] [out.json]      (default: profiles/device_products_<lib sha8>.json)
 """
-import csv
-import glob
 import json
-import os
-import subprocess
 import sys
 import tempfile
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "g-vom_amd"))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+import benchkit as bk
+
 COPY_CEILING_TBS = 6.29                                   # the project's own device copy ceiling (DESIGN.md, profiles/)
+TURNS = 2
+CHILD_TIMEOUT = 900                                       # seconds, per child process
 
 
-def _gvom():
-    """The binding, also over a library of an OLDER ABI (the parent): it is bound with the entry points it has."""
+def _older_abi(gvom, lib):
+    """a library of an OLDER ABI (the parent): the binding takes its version for its own"""
     import ctypes
-    import gvom
-    lib = ctypes.CDLL(gvom.library_path())
     lib.gvom_abi_version.restype = ctypes.c_int
-    if lib.gvom_abi_version() != gvom.ABI_VERSION:
-        gvom.ABI = [e for e in gvom.ABI if hasattr(lib, e[0])]
-        gvom.ABI_VERSION = lib.gvom_abi_version()
-    return gvom
+    gvom.ABI_VERSION = lib.gvom_abi_version()
 
 
-def _median(v):
-    v = sorted(v)
-    return v[len(v) // 2] if len(v) % 2 else 0.5 * (v[len(v) // 2 - 1] + v[len(v) // 2])
+def _binding():
+    return bk.gvom_for_library(adapt=_older_abi)
 
 
 def child_occupancy_host():
     import synth
-    gvom = _gvom()
+    gvom = _binding()
     out = {}
     for name, reps in (("m256", 30), ("c4", 12)):
         params, scans = synth.config_inputs(name, n_scans=1)
@@ -61,49 +52,28 @@ def child_occupancy_host():
             t0 = time.perf_counter()
             grid = g.get_map_as_occupancy_grid()
             ms.append((time.perf_counter() - t0) * 1e3)
-        out[name] = {"ms_median": round(_median(ms), 3), "ms_min": round(min(ms), 3), "ms_max": round(max(ms), 3), "reps": reps,
+        out[name] = {"ms_median": round(bk.median(ms), 3), "ms_min": round(min(ms), 3), "ms_max": round(max(ms), 3), "reps": reps,
                      "voxels": int(grid.size), "occupied": int(grid.sum())}
         del g
     return out
 
 
 def child_step(with_occupancy):
-    import numpy as np
-    import torch
-    import synth
-    torch.cuda.init()
-    gvom = _gvom()
     steps, poses = 1500, 8
-    params, scans = synth.config_inputs("m256", n_scans=poses)
-    dev = [(torch.from_numpy(np.ascontiguousarray(pc)).cuda(), ego, tf) for pc, ego, tf in scans]
-    torch.cuda.synchronize()
-    g = gvom.Gvom(*params, voxel_statistics=False)
+    np, torch, gvom, g, dev = bk.setup("m256", poses, adapt=_older_abi)
 
     def step(k):
-        t, ego, tf = dev[k % poses]
-        g.process_pointcloud_device(t.data_ptr(), t.shape[0], np.float32, ego, tf)
-        g.combine_maps_device().release()
+        bk.scan_combine(np, g, dev[k % poses]).release()
         if with_occupancy:
             g.occupancy_grid_device().release()
-
-    for k in range(100):
-        step(k)
-    g._check(g._lib.gvom_sync(g._h))
-    us = []
-    for rep in range(5):
-        t0 = time.perf_counter()
-        for k in range(steps):
-            step(k)
-        g._check(g._lib.gvom_sync(g._h))
-        us.append(round((time.perf_counter() - t0) / steps * 1e6, 2))
-    return {"us_per_step": us, "us_per_step_median": _median(us), "steps": steps}
+    return bk.step_loop(g, step, steps, warm=100, reps=5)
 
 
 def child_kernels(name):
     """Run under rocprofv3: the calls whose kernels are to be timed."""
     import numpy as np
     import synth
-    gvom = _gvom()
+    gvom = _binding()
     params, scans = synth.config_inputs(name, n_scans=1)
     g = gvom.Gvom(*params, voxel_statistics=False)
     g.process_pointcloud(*scans[0])
@@ -112,7 +82,7 @@ def child_kernels(name):
         g.set_tuning("occupancy_clear", clear)
         for _ in range(40):
             g.occupancy_grid_device().release()
-        g._check(g._lib.gvom_sync(g._h))
+        bk.sync(g)
     g.set_tuning("occupancy_clear", 0)
     for _ in range(3):
         state, _, _, _, origin, _ = g.read_dense(gvom.GVOM_WHICH_FUSED)
@@ -128,51 +98,24 @@ def child_kernels(name):
             "bytes_moved": xy * zs * nseg * 4 + live * 256 + xy * xy * zs}
 
 
-def _spawn(mode, lib, arg=None, profile_dir=None):
-    cmd = [sys.executable, os.path.abspath(__file__), "--child", mode] + ([arg] if arg else [])
-    if profile_dir:
-        cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", profile_dir, "--"] + cmd
-    env = dict(os.environ, GVOM_HIP_LIBRARY=os.path.abspath(lib))
-    r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
-    if r.returncode != 0:
-        raise SystemExit("%s on %s failed (%d):\n%s" % (mode, lib, r.returncode, r.stderr[-3000:]))
-    line = [ln for ln in r.stdout.splitlines() if ln.startswith("RESULT ")][-1]
-    return json.loads(line[7:])
-
-
-def _kernel_stats(profile_dir):
-    rows = {}
-    for f in glob.glob(os.path.join(profile_dir, "**", "*kernel_stats.csv"), recursive=True):
-        for r in csv.DictReader(open(f)):
-            rows[r["Name"]] = {"calls": int(r["Calls"]), "avg_us": round(float(r["AverageNs"]) / 1e3, 2),
-                               "min_us": round(float(r["MinNs"]) / 1e3, 2), "max_us": round(float(r["MaxNs"]) / 1e3, 2)}
-    return rows
-
-
 def main():
-    if len(sys.argv) > 2 and sys.argv[1] == "--child":
-        mode = sys.argv[2]
-        res = {"occupancy_host": child_occupancy_host, "step": lambda: child_step(False), "step_occupancy": lambda: child_step(True),
-               "kernels": lambda: child_kernels(sys.argv[3])}[mode]()
-        print("RESULT " + json.dumps(res))
+    if bk.child(sys.argv[1:], {"occupancy_host": lambda a: child_occupancy_host(), "step": lambda a: child_step(False),
+                               "step_occupancy": lambda a: child_step(True), "kernels": lambda a: child_kernels(a[0])}):
         return
-    import lib_identity
-    parent = sys.argv[1]
-    new = os.path.join(ROOT, "g-vom_amd", "lib", "libgvom_hip.so")
-    out = {"library": lib_identity.identity(), "parent_library": {"lib_sha256": lib_identity.sha256_file(parent)},
-           "copy_ceiling_TBps": COPY_CEILING_TBS}
-    runs = {"parent": [], "new": []}
-    for rnd in range(2):                                           # parent, new, parent, new
-        for who, lib in (("parent", parent), ("new", new)):
-            runs[who].append(_spawn("step", lib))
-    p = [u for r in runs["parent"] for u in r["us_per_step"]]
-    n = [u for r in runs["new"] for u in r["us_per_step"]]
+    args = bk.read_args(sys.argv[1:], positional_parent=True, has_resources=False, turns=TURNS)
+    parent, new = args["parent"], bk.NEW_LIB
+    spawn = lambda mode, lib, a=(), **kw: bk.spawn(__file__, mode, a, CHILD_TIMEOUT, lib=lib, **kw)
+    report = bk.Report("device_products", args["path"], parent, fresh=True)
+    out = report.out
+    out["copy_ceiling_TBps"] = COPY_CEILING_TBS
+    runs = bk.alternate(args["turns"], {"parent": lambda: spawn("step", parent), "new": lambda: spawn("step", new)})
+    p, n = bk.pooled(runs["parent"]), bk.pooled(runs["new"])
     out["step m256 scan+combine_maps_device"] = {
-        "parent_us_per_step": p, "new_us_per_step": n, "parent_median": _median(p), "new_median": _median(n),
-        "parent_spread_us": round(max(p) - min(p), 2), "new_minus_parent_us": round(_median(n) - _median(p), 2),
-        "within_parent_spread": _median(n) - _median(p) <= max(p) - min(p)}
-    out["step m256 scan+combine_maps_device+occupancy_grid_device"] = _spawn("step_occupancy", new)
-    occ = {who: _spawn("occupancy_host", lib) for who, lib in (("parent", parent), ("new", new))}
+        "parent_us_per_step": p["us_per_step"], "new_us_per_step": n["us_per_step"], "parent_median": p["median"], "new_median": n["median"],
+        "parent_spread_us": p["spread_us"], "new_minus_parent_us": round(n["median"] - p["median"], 2),
+        "within_parent_spread": n["median"] - p["median"] <= p["spread_us"]}
+    out["step m256 scan+combine_maps_device+occupancy_grid_device"] = spawn("step_occupancy", new)
+    occ = {who: spawn("occupancy_host", lib) for who, lib in (("parent", parent), ("new", new))}
     out["get_map_as_occupancy_grid wall"] = {
         cfg: {"parent_ms_median": occ["parent"][cfg]["ms_median"], "new_ms_median": occ["new"][cfg]["ms_median"],
               "speedup": round(occ["parent"][cfg]["ms_median"] / occ["new"][cfg]["ms_median"], 2),
@@ -180,20 +123,15 @@ def main():
     out["kernels"] = {}
     for cfg in ("m256", "c4"):
         with tempfile.TemporaryDirectory() as d:
-            info = _spawn("kernels", new, cfg, profile_dir=d)
-            stats = _kernel_stats(d)
-        pick = {k.split("(")[0]: v for k, v in stats.items() if "k_occupancy" in k or "k_read_dense" in k or "fill" in k.lower()}
+            info = spawn("kernels", new, (cfg,), profile_dir=d, stats=True)
+            stats = bk.kernel_stats(d)
+        pick = {k: v for k, v in stats.items() if "k_occupancy" in k or "k_read_dense" in k or "fill" in k.lower()}
         for k, v in pick.items():
             if "k_occupancy" in k:
                 v["TBps_of_bytes_moved"] = round(info["bytes_moved"] / (v["avg_us"] * 1e-6) / 1e12, 3)
         out["kernels"][cfg] = dict(info, kernel_us=pick)
-    text = json.dumps(out, indent=1)
-    print(text)
-    path = sys.argv[2] if len(sys.argv) > 2 else os.path.join(
-        ROOT, "profiles", "device_products_%s.json" % (out["library"].get("lib_sha256") or "unknown")[:8])
-    os.makedirs(os.path.dirname(path), exist_ok=True)
-    with open(path, "w") as f:
-        f.write(text + "\n")
+    print(json.dumps(out, indent=1))
+    report.save()
 
 
 if __name__ == "__main__":

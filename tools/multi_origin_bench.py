@@ -12,48 +12,25 @@ fresh child process:
   + k_trace's stage time (last_stage_ms) for each, and one `rocprofv3 --kernel-trace --stats` run of d and e (kernel times of
   the per-lane-origin instantiation next to the single-origin one's)
 
-    tools/multi_origin_bench.py PARENT_LIB [out.json] [--regs FILE]   (default: profiles/multi_origin_<lib sha8>.json; FILE: the
-                                                                       register comparison of tools/kernel_regs.py, copied in)
+    tools/multi_origin_bench.py PARENT_LIB [out.json] [--regs FILE] [--turns N]   (default: profiles/multi_origin_<lib sha8>.json;
+                                                            FILE: the register comparison of tools/kernel_regs.py, copied in)
 """
-import csv
-import glob
 import json
-import os
-import subprocess
 import sys
 import tempfile
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "g-vom_amd"))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+import benchkit as bk
+
 WARMUP, STEPS, POSES = 20, 200, 8                          # bench.py's defaults
-
-
-def _gvom():
-    """The binding, also over the parent's library: it is bound with the entry points it has."""
-    import ctypes
-    import gvom
-    lib = ctypes.CDLL(gvom.library_path())
-    gvom.ABI = [e for e in gvom.ABI if hasattr(lib, e[0])]
-    return gvom
-
-
-def _median(v):
-    v = sorted(v)
-    return v[len(v) // 2] if len(v) % 2 else 0.5 * (v[len(v) // 2 - 1] + v[len(v) // 2])
+TURNS = 3
+CHILD_TIMEOUT = 600                                        # seconds, per child process
 
 
 def child(mode, steps=STEPS):
-    import numpy as np
-    import torch
     import synth
-    torch.cuda.init()
-    gvom = _gvom()
-    params, scans = synth.config_inputs("m256", n_scans=POSES)
-    g = gvom.Gvom(*params, voxel_statistics=False)
-    n = scans[0][0].shape[0]
-    dev = [(torch.from_numpy(np.ascontiguousarray(pc)).cuda(), ego, tf) for pc, ego, tf in scans]
+    np, torch, gvom, g, dev = bk.setup("m256", POSES)
+    n = dev[0][0].shape[0]
     idx4 = torch.from_numpy((np.arange(n) * 4 // n).astype(np.int16)).cuda()
     images = None
     if mode in ("f", "f_plain"):
@@ -94,88 +71,52 @@ def child(mode, steps=STEPS):
     g.set_profiling(True)
     for k in range(WARMUP):
         step(k)
-    g._check(g._lib.gvom_sync(g._h))
+    bk.sync(g)
     trace_ms = []
     t0 = time.perf_counter()
     for k in range(steps):
         step(k)
         if k % 8 == 0:
             trace_ms.append(float(g.last_stage_ms()["trace"]))
-    g._check(g._lib.gvom_sync(g._h))
+    bk.sync(g)
     us = (time.perf_counter() - t0) / steps * 1e6
-    return {"us_per_step": round(us, 2), "k_trace_stage_us_median": round(_median(trace_ms) * 1e3, 2), "steps": steps,
+    return {"us_per_step": round(us, 2), "k_trace_stage_us_median": round(bk.median(trace_ms) * 1e3, 2), "steps": steps,
             "knobs": {nm: g.get_tuning(nm) for nm in ("segs", "period", "interleave", "dirsort")}}
 
 
-def _spawn(mode, lib, profile_dir=None, steps=STEPS):
-    cmd = [sys.executable, os.path.abspath(__file__), "--child", mode, str(steps)]
-    if profile_dir:
-        cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", profile_dir, "--"] + cmd
-    env = dict(os.environ, GVOM_HIP_LIBRARY=os.path.abspath(lib))
-    r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
-    if r.returncode != 0:
-        raise SystemExit("%s on %s failed (%d):\n%s" % (mode, lib, r.returncode, r.stderr[-3000:]))
-    line = [ln for ln in r.stdout.splitlines() if ln.startswith("RESULT ")][-1]
-    return json.loads(line[7:])
-
-
-def _kernel_stats(profile_dir):
-    rows = {}
-    for f in glob.glob(os.path.join(profile_dir, "**", "*kernel_stats.csv"), recursive=True):
-        for r in csv.DictReader(open(f)):
-            rows[r["Name"].split("(")[0]] = {"calls": int(r["Calls"]), "avg_us": round(float(r["AverageNs"]) / 1e3, 2),
-                                             "min_us": round(float(r["MinNs"]) / 1e3, 2), "max_us": round(float(r["MaxNs"]) / 1e3, 2)}
-    return rows
-
-
 def main():
-    if len(sys.argv) > 2 and sys.argv[1] == "--child":
-        print("RESULT " + json.dumps(child(sys.argv[2], int(sys.argv[3]))))
+    if bk.child(sys.argv[1:], {mode: (lambda a, mode=mode: child(mode, int(a[0]))) for mode in ("a", "b", "c", "d", "e", "f", "f_plain")}):
         return
-    import lib_identity
-    args = [a for a in sys.argv[1:]]
-    regs = None
-    if "--regs" in args:
-        i = args.index("--regs")
-        regs = json.load(open(args[i + 1]))
-        del args[i:i + 2]
-    parent = args[0]
-    new = os.path.join(ROOT, "g-vom_amd", "lib", "libgvom_hip.so")
-    out = {"library": lib_identity.identity(), "parent_library": {"lib_sha256": lib_identity.sha256_file(parent)},
-           "workload": "m256: 256^3 voxels, 131,072 returns, %d moving poses, device-resident cloud, scan + combine_maps, warm-up %d, %d steps"
-                       % (POSES, WARMUP, STEPS)}
-    runs = {"a": [], "b": []}
-    for _ in range(3):                                             # a, b, a, b, a, b
-        runs["a"].append(_spawn("a", parent))
-        runs["b"].append(_spawn("b", new))
+    args = bk.read_args(sys.argv[1:], positional_parent=True, has_resources=False, turns=TURNS,
+                        extra={"--regs": (None, lambda f: json.load(open(f)))})
+    parent, new = args["parent"], bk.NEW_LIB
+    spawn = lambda mode, lib, steps=STEPS, **kw: bk.spawn(__file__, mode, (steps,), CHILD_TIMEOUT, lib=lib, **kw)
+    report = bk.Report("multi_origin", args["path"], parent, fresh=True)
+    out = report.out
+    out["workload"] = ("m256: 256^3 voxels, 131,072 returns, %d moving poses, device-resident cloud, scan + combine_maps, warm-up %d, %d steps"
+                       % (POSES, WARMUP, STEPS))
+    runs = bk.alternate(args["turns"], {"a": lambda: spawn("a", parent), "b": lambda: spawn("b", new)})      # a, b, a, b, a, b
     a = [r["us_per_step"] for r in runs["a"]]
     b = [r["us_per_step"] for r in runs["b"]]
     out["a parent library, process_pointcloud_device"] = {"us_per_step": a, "k_trace_stage_us": [r["k_trace_stage_us_median"] for r in runs["a"]]}
     out["b this library, process_pointcloud_device"] = {"us_per_step": b, "k_trace_stage_us": [r["k_trace_stage_us_median"] for r in runs["b"]]}
-    out["b against a"] = {"a_median": _median(a), "b_median": _median(b), "a_spread_us": round(max(a) - min(a), 2),
-                          "b_minus_a_us": round(_median(b) - _median(a), 2),
-                          "within_a_spread": _median(b) - _median(a) <= max(a) - min(a)}
+    out["b against a"] = {"a_median": bk.median(a), "b_median": bk.median(b), "a_spread_us": round(max(a) - min(a), 2),
+                          "b_minus_a_us": round(bk.median(b) - bk.median(a), 2),
+                          "within_a_spread": bk.median(b) - bk.median(a) <= max(a) - min(a)}
     for mode, what in (("c", "c origins K=1 at the ego"), ("d", "d origins K=4 contiguous groups, sensors 1 m apart"),
                        ("e", "e origins K=1024, index=None, 1.5 m of travel"),
                        ("f_plain", "f (plain) process_range_image_device, column poses, traced from the ego"),
                        ("f", "f process_range_image_origins_device")):
-        out[what] = _spawn(mode, new)
-    out["kernels (rocprofv3 --kernel-trace --stats, 60 steps each)"] = {}
+        out[what] = spawn(mode, new)
+    kernels = out["kernels (rocprofv3 --kernel-trace --stats, 60 steps each)"] = {}
     for mode in ("b", "d", "e"):
         with tempfile.TemporaryDirectory() as d:
-            _spawn(mode, new, profile_dir=d, steps=60)
-            stats = _kernel_stats(d)
-        out["kernels (rocprofv3 --kernel-trace --stats, 60 steps each)"][mode] = {
-            k: v for k, v in stats.items() if "k_trace" in k or "k_encfuse" in k or "k_map2d" in k}
-    if regs is not None:
-        out["k_trace registers, parent against this tree (--save-temps)"] = regs
-    text = json.dumps(out, indent=1)
-    print(text)
-    path = args[1] if len(args) > 1 else os.path.join(
-        ROOT, "profiles", "multi_origin_%s.json" % (out["library"].get("lib_sha256") or "unknown")[:8])
-    os.makedirs(os.path.dirname(path), exist_ok=True)
-    with open(path, "w") as f:
-        f.write(text + "\n")
+            spawn(mode, new, steps=60, profile_dir=d, stats=True)
+            kernels[mode] = bk.kernel_stats(d, ("k_trace", "k_encfuse", "k_map2d"))
+    if args["regs"] is not None:
+        out["k_trace registers, parent against this tree (--save-temps)"] = args["regs"]
+    print(json.dumps(out, indent=1))
+    report.save()
 
 
 if __name__ == "__main__":

@@ -18,54 +18,23 @@ under a `timeout` of its own, and the first child that fails ends the run:
 The 6 m turning radius: an arc of 4 cells of 0.2 m turns by 0.133 rad, one bin of H = 64 (0.098 rad) but not one of H = 16 (0.393 rad),
 where arc_primitives raises; H = 16 is measured with a 2 m radius, the largest whole metre that reaches the next bin.
 
-    tools/posefield_bench.py [--resources] [--parent LIB] [--configs m256,c4] [out.json]   (default: profiles/posefield_<lib sha8>.json)
+    tools/posefield_bench.py [--resources] [--parent LIB] [--configs m256,c4] [--turns N] [out.json]   (default: profiles/posefield_<lib sha8>.json)
 """
-import csv
-import glob
 import json
 import math
-import os
-import subprocess
 import sys
 import tempfile
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "g-vom_amd"))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+import benchkit as bk
+
 CONFIGS = {"m256": 60, "c4": 24}                          # config: timed steps per repetition
+TURNS = 5
 CAR = dict(front=3.6, rear=1.0, half_width=1.1)
 SHAPES = ((16, 2.0), (64, 6.0))                           # (headings, minimum turning radius in metres)
 GOALS = ("near", "far")
 CHILD_TIMEOUT = 300                                       # seconds, per child process
 KERNELS = ("k_cspace", "k_pose_relax", "k_pose_seed", "k_pose_actions")
-
-
-def _median(v):
-    v = sorted(v)
-    return v[len(v) // 2] if len(v) % 2 else 0.5 * (v[len(v) // 2 - 1] + v[len(v) // 2])
-
-
-def _gvom():
-    """The binding, also over the parent's library: it is bound with the entry points it has."""
-    import ctypes
-    import gvom
-    lib = ctypes.CDLL(gvom.library_path())
-    gvom.ABI = [e for e in gvom.ABI if hasattr(lib, e[0])]
-    return gvom
-
-
-def _setup(name):
-    import numpy as np
-    import torch
-    import synth
-    torch.cuda.init()
-    gvom = _gvom()
-    params, scans = synth.config_inputs(name, n_scans=3)
-    dev = [(torch.from_numpy(np.ascontiguousarray(pc)).cuda(), ego, tf) for pc, ego, tf in scans]
-    torch.cuda.synchronize()
-    g = gvom.Gvom(*params, voxel_statistics=False)
-    return np, torch, gvom, g, dev
 
 
 def _tables(gvom, g, H, radius):
@@ -135,10 +104,9 @@ def _torch_sweeps(torch, C, D0, table, cap):
 
 
 def child_call(name, profiled):
-    np, torch, gvom, g, dev = _setup(name)
-    for t, ego, tf in dev:
-        g.process_pointcloud_device(t.data_ptr(), t.shape[0], np.float32, ego, tf)
-        m = g.combine_maps_device()
+    np, torch, gvom, g, dev = bk.setup(name)
+    for scan in dev:
+        m = bk.scan_combine(np, g, scan)
     ego = dev[2][1]
     reps, results = 5, {}
     for H, radius in SHAPES:
@@ -153,26 +121,14 @@ def child_call(name, profiled):
                     call().release()
                 field.release()
                 continue
-            for _ in range(3):
-                call().release()
-            us = []
-            for rep in range(5):
-                t0 = time.perf_counter()
-                for _ in range(reps):
-                    call().release()
-                us.append(round((time.perf_counter() - t0) / reps * 1e6, 1))
+            us = bk.timed(None, lambda: call().release(), reps)["us"]      # (the call waits itself)
             f = call()
             out = {"xy": g.xy_size, "H": H, "goal_cell": [int(v) for v in goal[0]], "min_turn_radius_m": radius, "primitives_per_heading": int(table[0][1]), "halo_cells": int(np.abs(table[1][:, :2]).max()),
                    "footprint_cells_heading_0": fp_cells,
-                   "call_us": us, "call_us_median": _median(us), "rounds": f.rounds, "tile_relaxations": g.get_tuning("pose_field_tiles"),
+                   "call_us": us, "call_us_median": bk.median(us), "rounds": f.rounds, "tile_relaxations": g.get_tuning("pose_field_tiles"),
                    "tiles": int(math.ceil(g.xy_size / 8.0)) ** 2, "reached_states": f.reached, "seeded_states": f.goals_seeded, "converged": f.converged}
-            two = []
-            for rep in range(5):
-                t0 = time.perf_counter()
-                for _ in range(reps):
-                    m.cost_to_go(goal, goals_in_cells=True).release()
-                two.append(round((time.perf_counter() - t0) / reps * 1e6, 1))
-            out["cost_to_go_2d_same_map"] = {"call_us": two, "call_us_median": _median(two), "rounds": field.rounds, "reached_cells": field.reached}
+            two = bk.timed(None, lambda: m.cost_to_go(goal, goals_in_cells=True).release(), reps, warm=0)["us"]
+            out["cost_to_go_2d_same_map"] = {"call_us": two, "call_us_median": bk.median(two), "rounds": field.rounds, "reached_cells": field.reached}
             if name == "m256" and H == 16 and which == "near":
                 try:
                     import scipy.sparse.csgraph as csg
@@ -205,57 +161,25 @@ def child_call(name, profiled):
 
 
 def child_step(name, steps, with_field):
-    np, torch, gvom, g, dev = _setup(name)
+    np, torch, gvom, g, dev = bk.setup(name)
     if with_field:
         _tables(gvom, g, *SHAPES[0])
 
     def step(k):
-        t, ego, tf = dev[k % 3]
-        g.process_pointcloud_device(t.data_ptr(), t.shape[0], np.float32, ego, tf)
-        m = g.combine_maps_device()
+        ego = dev[k % 3][1]
+        m = bk.scan_combine(np, g, dev[k % 3])
         goal = np.array([[ego[0] + 2.0, ego[1]]])
         f = m.cost_to_go(goal)
         if with_field:
             f.pose_field(goal).release()
         f.release()
         m.release()
-
-    for k in range(min(6, steps)):
-        step(k)
-    g._check(g._lib.gvom_sync(g._h))
-    us = []
-    for rep in range(3):
-        t0 = time.perf_counter()
-        for k in range(steps):
-            step(k)
-        g._check(g._lib.gvom_sync(g._h))
-        us.append(round((time.perf_counter() - t0) / steps * 1e6, 2))
-    return {"us_per_step": us, "us_per_step_median": _median(us), "steps": steps}
-
-
-def _spawn(mode, args, profile_dir=None, lib=None):
-    """one child under its own time limit; a child that fails (or runs into the limit) ends the whole run"""
-    cmd = [sys.executable, os.path.abspath(__file__), "--child", mode] + [str(a) for a in args]
-    if profile_dir:
-        cmd = ["rocprofv3", "--kernel-trace", "--output-format", "csv", "-d", profile_dir, "--"] + cmd
-    cmd = ["timeout", "-k", "10", str(CHILD_TIMEOUT)] + cmd
-    env = dict(os.environ, GVOM_HIP_LIBRARY=os.path.abspath(lib)) if lib else None
-    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=env)
-    if r.returncode != 0:
-        raise SystemExit("%s %r failed (%d): nothing more is started\n%s" % (mode, args, r.returncode, r.stderr[-3000:]))
-    line = [ln for ln in r.stdout.splitlines() if ln.startswith("RESULT ")][-1]
-    return json.loads(line[7:])
+    return bk.step_loop(g, step, steps, warm=min(6, steps))
 
 
 def _kernel_times(profile_dir, calls):
     """per shape and goal (k_pose_actions ends a call): the kernels' microseconds per call, without the first three calls"""
-    rows = []
-    for f in glob.glob(os.path.join(profile_dir, "**", "*kernel_trace.csv"), recursive=True):
-        for r in csv.DictReader(open(f)):
-            key = [k for k in KERNELS if k in r["Kernel_Name"]]
-            if key:
-                rows.append((int(r["Start_Timestamp"]), key[0], (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3))
-    rows.sort()
+    rows = bk.kernel_trace_rows(profile_dir, KERNELS)
     ends = [i for i, r in enumerate(rows) if r[1] == "k_pose_actions"]
     keys = ["H%d_%s" % (H, which) for H, _ in SHAPES for which in GOALS]
     extra = [1 if key.endswith("far") else 0 for key in keys]      # choosing the far goal makes one pose field of its own, first
@@ -271,97 +195,46 @@ def _kernel_times(profile_dir, calls):
         rec = {}
         for k in KERNELS:
             us = [u for _, kk, u in part if kk == k]
-            rec[k] = {"launches_per_call": round(len(us) / used, 2), "us_per_call": round(sum(us) / used, 2), "median_us_per_launch": round(_median(us), 2) if us else None}
+            rec[k] = {"launches_per_call": round(len(us) / used, 2), "us_per_call": round(sum(us) / used, 2), "median_us_per_launch": round(bk.median(us), 2) if us else None}
         rec["device_us_per_call"] = round(sum(u for _, _, u in part) / used, 2)
         out[key] = rec
     return out
 
 
-def resources(new, parent):
-    """the new unit's kernels, and every other kernel on the parent and on this library: registers, scratch, LDS, code size"""
-    import kernel_regs
-    mine = kernel_regs.kernels(new)
-    ours = lambda k: "k_cspace" in k or "k_pose_" in k
-    out = {"new_kernels": {k: v for k, v in mine.items() if ours(k)},
-           "k_pose_relax_dynamic_lds_bytes": "6 * H * (8 + 2 * halo)^2: 18,816 at H = 16, halo 3; 98,304 at H = 64, halo 4"}
-    if parent:
-        theirs = kernel_regs.kernels(parent)
-        rest = {k: v for k, v in mine.items() if not ours(k)}
-        keys = ("vgpr", "sgpr", "scratch", "lds", "code")
-        changed = {k: {"parent": theirs.get(k), "new": v} for k, v in rest.items() if any((theirs.get(k) or {}).get(q) != v.get(q) for q in keys)}
-        out["other_kernels"] = {"count": len(rest), "identical_to_parent": len(rest) - len(changed), "changed": changed,
-                                "only_on_parent": sorted(k for k in theirs if k not in mine)}
-    return out
-
-
 def main():
-    if len(sys.argv) > 2 and sys.argv[1] == "--child":
-        mode, a = sys.argv[2], sys.argv[3:]
-        res = child_call(a[0], a[1] == "1") if mode == "call" else child_step(a[0], int(a[1]), a[2] == "1")
-        print("RESULT " + json.dumps(res))
+    if bk.child(sys.argv[1:], {"call": lambda a: child_call(a[0], a[1] == "1"), "step": lambda a: child_step(a[0], int(a[1]), a[2] == "1")}):
         return
-    import lib_identity
-    args = sys.argv[1:]
-    parent, only_resources, configs = None, False, list(CONFIGS)
-    while args and args[0] in ("--parent", "--resources", "--configs"):
-        if args[0] == "--parent":
-            parent, args = args[1], args[2:]
-        elif args[0] == "--configs":
-            configs, args = args[1].split(","), args[2:]
-        else:
-            only_resources, args = True, args[1:]
-    new = os.path.join(ROOT, "g-vom_amd", "lib", "libgvom_hip.so")
-    path = args[0] if args else os.path.join(ROOT, "profiles", "posefield_%s.json" % (lib_identity.identity().get("lib_sha256") or "unknown")[:8])
-    out = json.load(open(path)) if os.path.exists(path) else {}
-    out.update({"library": lib_identity.identity(), "car_m": CAR, "shapes": [list(s) for s in SHAPES], "goals": list(GOALS), "reach_cells": 4})
-    out["resources"] = resources(new, parent)
-    if parent:
-        out["parent_library"] = {"lib_sha256": lib_identity.sha256_file(parent)}
-    out.setdefault("not_measured", ["c5", "H = 16 with a 6 m radius (arc_primitives raises: 0.8 m of arc does not reach the next of 16 headings)",
-                                    "a row-span or sliding-maximum k_cspace in LDS (not built)", "tiles other than 8 x 8 cells x all headings (not built)",
-                                    "scipy and the torch sweeps beyond m256, H = 16, near goal", "reverse primitives", "the host and device-pointer routes",
-                                    "pose_field_inner / pose_field_batch other than the defaults", "hardware counters, LDS bank conflicts of k_pose_relax"])
-    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-
-    def save():
-        with open(path, "w") as f:                                  # (after every part: a run that ends early leaves what it has)
-            f.write(json.dumps(out, indent=1) + "\n")
-    save()
-    if only_resources:
-        out.setdefault("configs", "not measured")
-        save()
+    args = bk.read_args(sys.argv[1:], configs=CONFIGS, turns=TURNS)
+    parent = args["parent"]
+    spawn = lambda mode, a, **kw: bk.spawn(__file__, mode, a, CHILD_TIMEOUT, **kw)
+    report, configs = bk.product_report(
+        "posefield", args, {"car_m": CAR, "shapes": [list(s) for s in SHAPES], "goals": list(GOALS), "reach_cells": 4},
+        lambda k: "k_cspace" in k or "k_pose_" in k,
+        ["c5", "H = 16 with a 6 m radius (arc_primitives raises: 0.8 m of arc does not reach the next of 16 headings)",
+         "a row-span or sliding-maximum k_cspace in LDS (not built)", "tiles other than 8 x 8 cells x all headings (not built)",
+         "scipy and the torch sweeps beyond m256, H = 16, near goal", "reverse primitives", "the host and device-pointer routes",
+         "pose_field_inner / pose_field_batch other than the defaults", "hardware counters, LDS bank conflicts of k_pose_relax"])
+    report.out["resources"]["k_pose_relax_dynamic_lds_bytes"] = "6 * H * (8 + 2 * halo)^2: 18,816 at H = 16, halo 3; 98,304 at H = 64, halo 4"
+    report.save()
+    if configs is None:
         return
-    if not isinstance(out.get("configs"), dict):
-        out["configs"] = {}
-    for name in configs:
+    for name in args["configs"]:
         steps = CONFIGS[name]
-        res = _spawn("call", (name, 0))
+        res = spawn("call", (name, 0))
         with tempfile.TemporaryDirectory() as d:
-            prof = _spawn("call", (name, 1), profile_dir=d)
+            prof = spawn("call", (name, 1), profile_dir=d)
             kernel = _kernel_times(d, prof["calls"])
         for key in res:
             res[key]["kernels"] = kernel[key] if kernel else "not measured (the trace did not hold the expected launches)"
-        out["configs"][name] = res
-        save()
-        runs = {"without": [], "with": [], "parent_without": []}
-        for rnd in range(5):                                        # alternating: parent, without, with, ...
-            if parent:
-                runs["parent_without"].append(_spawn("step", (name, steps, 0), lib=parent))
-            runs["without"].append(_spawn("step", (name, steps, 0)))
-            runs["with"].append(_spawn("step", (name, steps, 1)))
-        step = {}
-        for who, rs in runs.items():
-            if rs:
-                meds = [r["us_per_step_median"] for r in rs]
-                step[who] = {"run_medians_us": meds, "median": _median(meds), "min": min(meds), "max": max(meds)}
+        configs[name] = res
+        report.save()
+        runs = bk.alternate(args["turns"], {"parent_without": parent and (lambda: spawn("step", (name, steps, 0), lib=parent)),
+                                            "without": lambda: spawn("step", (name, steps, 0)), "with": lambda: spawn("step", (name, steps, 1))})
+        step = bk.spreads(runs)
         step["pose_field_adds_us_per_step"] = round(step["with"]["median"] - step["without"]["median"], 2)
-        if parent:
-            p = step["parent_without"]
-            step["without_inside_parents_own_spread"] = bool(p["min"] <= step["without"]["median"] <= p["max"])
-            step["without_minus_parent_median_us"] = round(step["without"]["median"] - p["median"], 2)
-        res["step: scan + combine_maps_device + cost_to_go (+ a pose field of H = 16, near goal)"] = step
-        save()
-    print(json.dumps(out, indent=1))
+        res["step: scan + combine_maps_device + cost_to_go (+ a pose field of H = 16, near goal)"] = bk.against_parent(step, "without", "parent_without", "without_")
+        report.save()
+    print(json.dumps(report.out, indent=1))
 
 
 if __name__ == "__main__":

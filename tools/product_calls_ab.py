@@ -15,32 +15,15 @@ Per measurement the median over each library's turns and the parent's own min ..
 """
 import json
 import os
-import subprocess
 import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in ("g-vom_amd", "tools", "tests"):
-    sys.path.insert(0, os.path.join(ROOT, p))
+import benchkit as bk
+
+sys.path.insert(0, os.path.join(bk.ROOT, "tests"))
 TURNS, WARM, CALLS, MANY = 5, 3, 20, 2000
 REST = (1, 1.0, 0.5, 0.5, 0.3, 2.0, 4.0, 1.0, 1, 1)
-
-
-def _median(v):
-    v = sorted(v)
-    return v[len(v) // 2] if len(v) % 2 else 0.5 * (v[len(v) // 2 - 1] + v[len(v) // 2])
-
-
-def _timed(call, warm, n):
-    """ms per call: the median of n calls behind `warm` warm-up calls; `call` waits for its own work"""
-    for _ in range(warm):
-        call()
-    ms = []
-    for _ in range(n):
-        t0 = time.perf_counter()
-        call()
-        ms.append((time.perf_counter() - t0) * 1e3)
-    return _median(ms)
+CHILD_TIMEOUT = 600                                                        # seconds, per child process and per bench.py run
 
 
 def child():
@@ -58,17 +41,17 @@ def child():
     ctg = np.asarray(field.copy_to_host()[0])
     out["cost_to_go_info"] = [int(field.rounds), int(field.reached)]
     field.release()
-    out["cost_to_go_m256_ms"] = _timed(lambda: g.cost_to_go_of(cost, [(2, 2)]).release(), WARM, CALLS)
+    out["cost_to_go_m256_ms"] = bk.timed_waiting(lambda: g.cost_to_go_of(cost, [(2, 2)]).release(), WARM, CALLS)
     fr = g.frontiers_of(cost, vis, cost_to_go=ctg)
     out["frontiers_info"] = [fr.rounds, fr.n_clusters, fr.frontier_cells]
     fr.release()
-    out["frontiers_m256_ms"] = _timed(lambda: g.frontiers_of(cost, vis, cost_to_go=ctg).release(), WARM, CALLS)
+    out["frontiers_m256_ms"] = bk.timed_waiting(lambda: g.frontiers_of(cost, vis, cost_to_go=ctg).release(), WARM, CALLS)
     g.set_footprint(posefield_ref.point_footprint(16))
     g.set_primitives(gvom.arc_primitives(16, 1.0, 0.4))
     pf = g.pose_field_of(cost, [(2, 2)])
     out["pose_field_info"] = [int(pf.rounds), int(pf.reached)]
     pf.release()
-    out["pose_field_m256_ms"] = _timed(lambda: g.pose_field_of(cost, [(2, 2)]).release(), WARM, max(5, CALLS // 4))
+    out["pose_field_m256_ms"] = bk.timed_waiting(lambda: g.pose_field_of(cost, [(2, 2)]).release(), WARM, max(5, CALLS // 4))
     del g
     # the atlas: an extent of 1024 cells, one 64-cell window of seen ground in the middle of never-seen ground
     A, w = 1024, 64
@@ -79,12 +62,12 @@ def child():
     a.integrate_of(maps, (480, 480))
     f = a.cost_to_go([(512, 512)], goals_in_cells=True)
     out["atlas_cost_to_go_info"] = [int(f.rounds), int(f.reached)]
-    out["atlas_frontiers_A1024_ms"] = _timed(lambda: f.frontiers(min_cells=1).release(), WARM, CALLS)
+    out["atlas_frontiers_A1024_ms"] = bk.timed_waiting(lambda: f.frontiers(min_cells=1).release(), WARM, CALLS)
     fr = f.frontiers(min_cells=1)
     out["atlas_frontiers_info"] = [fr.rounds, fr.n_clusters, fr.frontier_cells]
     fr.release()
     f.release()
-    out["atlas_cost_to_go_A1024_ms"] = _timed(lambda: a.cost_to_go([(512, 512)], goals_in_cells=True).release(), WARM, CALLS)
+    out["atlas_cost_to_go_A1024_ms"] = bk.timed_waiting(lambda: a.cost_to_go([(512, 512)], goals_in_cells=True).release(), WARM, CALLS)
     del a, ga
     # host overhead: the smallest calls, many of them
     s = 16
@@ -107,36 +90,31 @@ def child():
         return (time.perf_counter() - t0) / MANY * 1e6
     out["raycast_n1_us"] = many(lambda: gs.raycast(o, t).release())
     out["score_rollouts_K1T1_us"] = many(lambda: gs.score_rollouts_of(small, pose).release())
-    print("RESULT " + json.dumps(out))
+    return out
 
 
 def _bench(lib, config, steps, warmup):
-    env = dict(os.environ, GVOM_HIP_LIBRARY=lib)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--config", config, "--steps", str(steps), "--warmup", str(warmup)],
-                       env=env, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    return json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])["ms_per_step"]
+    argv = [sys.executable, os.path.join(bk.ROOT, "bench.py"), "--gpus", "1", "--config", config, "--steps", str(steps), "--warmup", str(warmup)]
+    out = bk.run(argv, CHILD_TIMEOUT, "bench.py --config %s" % config, lib=lib)
+    return json.loads([ln for ln in out.splitlines() if ln.startswith("{")][-1])["ms_per_step"]
 
 
 def main():
+    if bk.child(sys.argv[1:], {"calls": lambda a: child()}):
+        return
     import gvom
-    import lib_identity
-    args = sys.argv[1:]
-    parent = os.path.abspath(args[args.index("--parent") + 1])
-    n_turns = int(args[args.index("--turns") + 1]) if "--turns" in args else TURNS
-    rest = [a for k, a in enumerate(args) if a not in ("--parent", "--turns") and (k == 0 or args[k - 1] not in ("--parent", "--turns"))]
-    libs = {"parent": parent, "tree": os.path.abspath(gvom.library_path())}
-    turns = {name: [] for name in libs}
-    for turn in range(n_turns):
-        for name, lib in libs.items():                                     # parent, tree, parent, tree ...
-            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child"], env=dict(os.environ, GVOM_HIP_LIBRARY=lib),
-                               capture_output=True, text=True, timeout=600)
-            assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-            res = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("RESULT ")][-1][7:])
-            res["bench_m256_ms_per_step"] = _bench(lib, "m256", 300, 60)
-            res["bench_c4_ms_per_step"] = _bench(lib, "c4", 40, 10)
-            turns[name].append(res)
-            print(turn, name, json.dumps(res), flush=True)
+    args = bk.read_args(sys.argv[1:], has_resources=False, turns=TURNS)
+    if not args["parent"]:
+        raise SystemExit("--parent PATH/libgvom_hip.so: the library before")
+    libs = {"parent": os.path.abspath(args["parent"]), "tree": os.path.abspath(gvom.library_path())}
+
+    def one(name):
+        res = bk.spawn(__file__, "calls", (), CHILD_TIMEOUT, lib=libs[name])
+        res["bench_m256_ms_per_step"] = _bench(libs[name], "m256", 300, 60)
+        res["bench_c4_ms_per_step"] = _bench(libs[name], "c4", 40, 10)
+        print(name, json.dumps(res), flush=True)
+        return res
+    turns = bk.alternate(args["turns"], {name: (lambda name=name: one(name)) for name in libs})      # parent, tree, parent, tree ...
     table = {}
     for key in turns["parent"][0]:
         if key.endswith("_info"):
@@ -144,20 +122,15 @@ def main():
             table[key] = turns["parent"][0][key]
             continue
         p, t = [x[key] for x in turns["parent"]], [x[key] for x in turns["tree"]]
-        table[key] = {"parent_median": _median(p), "parent_min": min(p), "parent_max": max(p), "tree_median": _median(t), "tree_min": min(t),
-                      "tree_max": max(t), "tree_median_inside_parent_spread": min(p) <= _median(t) <= max(p)}
-    ident = lib_identity.identity()
-    out = {"what": __doc__.split("\n\n")[0], "turns": n_turns, "calls": CALLS, "many": MANY, "library": ident,
-           "parent_library": {"lib_sha256": lib_identity.sha256_file(parent)}, "table": table, "runs": turns}
-    sha8 = (ident.get("lib_sha256") or "unknown")[:8]
-    path = rest[0] if rest else os.path.join(ROOT, "profiles", "product_calls_%s.json" % sha8)
-    with open(path, "w") as f:
-        json.dump(out, f, indent=1)
-        f.write("\n")
+        table[key] = {"parent_median": bk.median(p), "parent_min": min(p), "parent_max": max(p), "tree_median": bk.median(t), "tree_min": min(t),
+                      "tree_max": max(t), "tree_median_inside_parent_spread": min(p) <= bk.median(t) <= max(p)}
+    report = bk.Report("product_calls", args["path"], args["parent"], fresh=True)
+    report.out.update({"what": __doc__.split("\n\n")[0], "turns": args["turns"], "calls": CALLS, "many": MANY, "table": table, "runs": turns})
+    report.save()
     for key, v in table.items():
         print(key, json.dumps(v))
-    print("wrote", path)
+    print("wrote", report.path)
 
 
 if __name__ == "__main__":
-    child() if "--child" in sys.argv else main()
+    main()

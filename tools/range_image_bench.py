@@ -13,39 +13,21 @@ session, every loop in a fresh child process, the two libraries alternating (par
   kernels   one `rocprofv3 --kernel-trace --stats` run per pose mode: k_unproject per raw type and cloud type, beside its bytes
             (raw + 48 B/pixel of model + 12 or 24 B/pixel out, + 96 B/column of poses) and the bandwidth that makes
 
-    tools/range_image_bench.py PARENT_LIB [out.json]      (default: profiles/range_image_<lib sha8>.json)
+    tools/range_image_bench.py PARENT_LIB [--turns N] [out.json]      (default: profiles/range_image_<lib sha8>.json)
 """
-import csv
-import glob
 import json
-import os
-import subprocess
 import sys
 import tempfile
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "g-vom_amd"))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+import benchkit as bk
+
 COPY_CEILING_TBS = 6.29                                   # the project's own device copy ceiling (DESIGN.md, profiles/)
+TURNS = 2
+CHILD_TIMEOUT = 600                                       # seconds, per child process
 H, W, POSES = 64, 2048, 8
 CLOUD_ROUTES = ("cloud_host", "cloud_dev", "cloud_dev_maps_dev")
 IMAGE_ROUTES = ("image_host_u16", "image_host_u32", "image_host_u16_poses", "image_host_u32_poses", "image_dev_u16", "image_dev_u32",
                 "image_dev_u32_poses")
-
-
-def _gvom():
-    """The binding, also over the parent's library: it is bound with the entry points it has."""
-    import ctypes
-    import gvom
-    lib = ctypes.CDLL(gvom.library_path())
-    gvom.ABI = [e for e in gvom.ABI if hasattr(lib, e[0])]
-    return gvom
-
-
-def _median(v):
-    v = sorted(v)
-    return v[len(v) // 2] if len(v) % 2 else 0.5 * (v[len(v) // 2 - 1] + v[len(v) // 2])
 
 
 class _Hbm(object):
@@ -79,24 +61,14 @@ def _images(np, synth, scans, rdt):
 
 
 def _time_steps(g, step, steps):
-    for k in range(100):
-        step(k)
-    g._check(g._lib.gvom_sync(g._h))
-    us = []
-    for rep in range(5):
-        t0 = time.perf_counter()
-        for k in range(steps):
-            step(k)
-        g._check(g._lib.gvom_sync(g._h))
-        us.append(round((time.perf_counter() - t0) / steps * 1e6, 2))
-    return {"us_per_step": us, "us_per_step_median": _median(us), "steps": steps, "interleave": g.get_tuning("interleave"),
-            "dirsort": g.get_tuning("dirsort"), "eager_adopted_share": round(g.get_tuning("eager_adopted") / (100.0 + 5 * steps), 3)}
+    return dict(bk.step_loop(g, step, steps, warm=100, reps=5), interleave=g.get_tuning("interleave"), dirsort=g.get_tuning("dirsort"),
+                eager_adopted_share=round(g.get_tuning("eager_adopted") / (100.0 + 5 * steps), 3))
 
 
 def child_step(route):
     import numpy as np
     import synth
-    gvom = _gvom()
+    gvom = bk.gvom_for_library()
     params, scans = synth.config_inputs("m256", n_scans=POSES)
     g = gvom.Gvom(*params, voxel_statistics=False)
     hbm = _Hbm()
@@ -143,7 +115,7 @@ def child_dropout(arg):
     """arg = "<pct>_cloud" (host clouds with the returns removed: a different length every scan) or "<pct>_image" """
     import numpy as np
     import synth
-    gvom = _gvom()
+    gvom = bk.gvom_for_library()
     pct, kind = arg.split("_")
     name = "m256_d" + pct
     params, scans = synth.config_inputs(name, n_scans=POSES)
@@ -175,7 +147,7 @@ def child_kernels(posed):
     """Run under rocprofv3: 40 scans per raw type and cloud type."""
     import numpy as np
     import synth
-    gvom = _gvom()
+    gvom = bk.gvom_for_library()
     params, scans = synth.config_inputs("m256", n_scans=1)
     g = gvom.Gvom(*params, voxel_statistics=False)
     cols = np.tile(np.eye(4), (W, 1, 1)) if posed == "1" else None
@@ -188,55 +160,33 @@ def child_kernels(posed):
             for _ in range(40):
                 g.process_range_image(raw, ego, tf, cols, cdt)
                 g.combine_maps()
-    g._check(g._lib.gvom_sync(g._h))
+    bk.sync(g)
     return {"pixels": H * W}
 
 
-def _spawn(mode, lib, arg, profile_dir=None):
-    cmd = [sys.executable, os.path.abspath(__file__), "--child", mode, arg]
-    if profile_dir:
-        cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", profile_dir, "--"] + cmd
-    env = dict(os.environ, GVOM_HIP_LIBRARY=os.path.abspath(lib))
-    r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
-    if r.returncode != 0:
-        raise SystemExit("%s %s on %s failed (%d):\n%s" % (mode, arg, lib, r.returncode, r.stderr[-3000:]))
-    line = [ln for ln in r.stdout.splitlines() if ln.startswith("RESULT ")][-1]
-    return json.loads(line[7:])
-
-
-def _kernel_stats(profile_dir):
-    rows = {}
-    for f in glob.glob(os.path.join(profile_dir, "**", "*kernel_stats.csv"), recursive=True):
-        for r in csv.DictReader(open(f)):
-            rows[r["Name"]] = {"calls": int(r["Calls"]), "avg_us": round(float(r["AverageNs"]) / 1e3, 2),
-                               "min_us": round(float(r["MinNs"]) / 1e3, 2), "max_us": round(float(r["MaxNs"]) / 1e3, 2)}
-    return rows
-
-
 def _both(runs):
-    v = [u for r in runs for u in r["us_per_step"]]
-    return {"us_per_step": v, "median": _median(v), "spread_us": round(max(v) - min(v), 2), "interleave": runs[-1]["interleave"],
-            "dirsort": runs[-1]["dirsort"], "eager_adopted_share": runs[-1]["eager_adopted_share"]}
+    return dict(bk.pooled(runs), interleave=runs[-1]["interleave"], dirsort=runs[-1]["dirsort"], eager_adopted_share=runs[-1]["eager_adopted_share"])
 
 
 def main():
-    if len(sys.argv) > 3 and sys.argv[1] == "--child":
-        res = {"step": child_step, "dropout": child_dropout, "kernels": child_kernels}[sys.argv[2]](sys.argv[3])
-        print("RESULT " + json.dumps(res))
+    if bk.child(sys.argv[1:], {"step": lambda a: child_step(a[0]), "dropout": lambda a: child_dropout(a[0]), "kernels": lambda a: child_kernels(a[0])}):
         return
-    import lib_identity
-    parent = sys.argv[1]
-    new = os.path.join(ROOT, "g-vom_amd", "lib", "libgvom_hip.so")
-    out = {"library": lib_identity.identity(), "parent_library": {"lib_sha256": lib_identity.sha256_file(parent)},
-           "copy_ceiling_TBps": COPY_CEILING_TBS, "config": "m256, %d x %d pixels, %d moving poses, buffer 1, scan + combine per step" % (H, W, POSES)}
+    args = bk.read_args(sys.argv[1:], positional_parent=True, has_resources=False, turns=TURNS)
+    parent, new = args["parent"], bk.NEW_LIB
+    spawn = lambda mode, lib, arg, **kw: bk.spawn(__file__, mode, (arg,), CHILD_TIMEOUT, lib=lib, **kw)
+    report = bk.Report("range_image", args["path"], parent, fresh=True)
+    out = report.out
+    out.update({"copy_ceiling_TBps": COPY_CEILING_TBS,
+                "config": "m256, %d x %d pixels, %d moving poses, buffer 1, scan + combine per step" % (H, W, POSES)})
     jobs = [("parent", parent, "step", r) for r in CLOUD_ROUTES] + [("new", new, "step", r) for r in CLOUD_ROUTES + IMAGE_ROUTES]
     for pct in ("10", "25", "40"):
         jobs += [("parent", parent, "dropout", pct + "_cloud"), ("new", new, "dropout", pct + "_image")]
-    runs = {}
-    for rnd in range(2):                                           # the whole list twice: parent and new alternate inside it
-        for who, lib, mode, arg in sorted(jobs, key=lambda j: (j[2], j[3], j[0] != "parent")):
-            print("round %d: %s %s %s" % (rnd, who, mode, arg), file=sys.stderr, flush=True)
-            runs.setdefault((who, mode, arg), []).append(_spawn(mode, lib, arg))
+
+    def start(who, lib, mode, arg):
+        print("%s %s %s" % (who, mode, arg), file=sys.stderr, flush=True)
+        return spawn(mode, lib, arg)
+    jobs.sort(key=lambda j: (j[2], j[3], j[0] != "parent"))         # the whole list `turns` times: parent and new alternate inside it
+    runs = bk.alternate(args["turns"], {(who, mode, arg): (lambda j=(who, lib, mode, arg): start(*j)) for who, lib, mode, arg in jobs})
     res = {k: _both(v) for k, v in runs.items()}
     yard = res[("parent", "step", "cloud_host")]
     out["yardstick parent cloud_host"] = yard
@@ -260,11 +210,9 @@ def main():
     out["k_unproject"] = {}
     for posed in ("0", "1"):
         with tempfile.TemporaryDirectory() as d:
-            info = _spawn("kernels", new, posed, profile_dir=d)
-            stats = _kernel_stats(d)
+            info = spawn("kernels", new, posed, profile_dir=d, stats=True)
+            stats = bk.kernel_stats(d, ("k_unproject",), strip_args=False)
         for name, v in stats.items():
-            if "k_unproject" not in name:
-                continue
             targs = name[name.index("<") + 1:name.index(">")] if "<" in name else name
             rb = 2 if "short" in targs else 4
             cb = 24 if "double" in targs else 12
@@ -272,13 +220,8 @@ def main():
             out["k_unproject"]["<%s>%s" % (targs, " column poses" if posed == "1" else "")] = dict(
                 v, bytes=nbytes, TBps=round(nbytes / (v["avg_us"] * 1e-6) / 1e12, 3),
                 share_of_copy_ceiling=round(nbytes / (v["avg_us"] * 1e-6) / 1e12 / COPY_CEILING_TBS, 3))
-    text = json.dumps(out, indent=1)
-    print(text)
-    path = sys.argv[2] if len(sys.argv) > 2 else os.path.join(
-        ROOT, "profiles", "range_image_%s.json" % (out["library"].get("lib_sha256") or "unknown")[:8])
-    os.makedirs(os.path.dirname(path), exist_ok=True)
-    with open(path, "w") as f:
-        f.write(text + "\n")
+    print(json.dumps(out, indent=1))
+    report.save()
 
 
 if __name__ == "__main__":

@@ -16,10 +16,8 @@ alone.  Everything goes into ONE file, profiles/raycast_<lib sha8>.json; a part 
                        library's answer without flags on OCCUPIED / LEFT_WINDOW / CLEAR only.  ratio = torch us / library us,
                        written down whatever it is.
 
-    tools/raycast_bench.py [--resources [--parent REV]] [out.json]
+    tools/raycast_bench.py [--resources [--parent REV]] [--configs m256,c4] [out.json]
 """
-import csv
-import glob
 import json
 import os
 import re
@@ -28,18 +26,14 @@ import sys
 import tempfile
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import benchkit as bk
+
+ROOT = bk.ROOT
 PKG = os.path.join(ROOT, "g-vom_amd")
-sys.path.insert(0, PKG)
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-CONFIGS = (("m256", 400), ("c4", 100))                     # (config, timed steps per repetition)
+CONFIGS = {"m256": 400, "c4": 100}                         # config: timed steps per repetition
+CHILD_TIMEOUT = 900                                        # seconds, per child process
 RAYS = (16384, 131072, 1048576)
 STEP_QUERY = 131072
-
-
-def _median(v):
-    v = sorted(v)
-    return v[len(v) // 2] if len(v) % 2 else 0.5 * (v[len(v) // 2 - 1] + v[len(v) // 2])
 
 
 # ---- resources (CPU) ---------------------------------------------------------------------------------------------------------
@@ -81,7 +75,7 @@ def _kernel_resources(src, include_dir):
     return out, listing
 
 
-def resources(parent):
+def compiled_resources(parent):
     with tempfile.TemporaryDirectory() as d:
         tar = subprocess.run(["git", "-C", ROOT, "archive", parent, "g-vom_amd/csrc", "include"], capture_output=True, check=True).stdout
         subprocess.run(["tar", "-x", "-C", d], input=tar, check=True)
@@ -98,19 +92,6 @@ def resources(parent):
 
 
 # ---- timing (GPU) ------------------------------------------------------------------------------------------------------------
-def _setup(name, poses=3):
-    import numpy as np
-    import torch
-    import gvom
-    import synth
-    torch.cuda.init()
-    params, scans = synth.config_inputs(name, n_scans=poses)
-    dev = [(torch.from_numpy(np.ascontiguousarray(pc)).cuda(), ego, tf) for pc, ego, tf in scans]
-    torch.cuda.synchronize()
-    g = gvom.Gvom(*params, voxel_statistics=False)
-    return np, torch, gvom, g, dev
-
-
 def _rays(np, g, ego, n, shuffled):
     """n targets 0.45 window widths from the ego on a 2:1 (azimuth, elevation) grid, azimuth fastest: a sweep"""
     cols = int(round((2 * n) ** 0.5))
@@ -165,10 +146,9 @@ def _torch_walk(torch, gvom, g, a, b):
 
 
 def child_step(name, steps):
-    np, torch, gvom, g, dev = _setup(name)
-    for t, ego, tf in dev:
-        g.process_pointcloud_device(t.data_ptr(), t.shape[0], np.float32, ego, tf)
-        g.combine_maps_device().release()
+    np, torch, gvom, g, dev = bk.setup(name)
+    for scan in dev:
+        bk.scan_combine(np, g, scan).release()
     ego = dev[-1][1]
     a = torch.from_numpy(np.asarray(ego, np.float32).reshape(1, 3)).cuda()
     out = {"steps": steps, "rays": {}}
@@ -195,15 +175,15 @@ def child_step(name, steps):
             for label, fn, calls in (("library_us", lib, 20), ("torch_us", yard, 3)):
                 for _ in range(3):
                     fn()
-                g._check(g._lib.gvom_sync(g._h)); torch.cuda.synchronize()
+                bk.sync(g); torch.cuda.synchronize()
                 us = []
                 for _ in range(reps):
                     t0 = time.perf_counter()
                     for _ in range(calls):
                         fn()
-                    g._check(g._lib.gvom_sync(g._h)); torch.cuda.synchronize()
+                    bk.sync(g); torch.cuda.synchronize()
                     us.append(round((time.perf_counter() - t0) / calls * 1e6, 2))
-                row[label] = {"per_call": us, "median": _median(us)}
+                row[label] = {"per_call": us, "median": bk.median(us)}
             row["torch_over_library"] = round(row["torch_us"]["median"] / row["library_us"]["median"], 2)
             out["rays"]["%d %s" % (n, order)] = row
             del b, an
@@ -211,99 +191,52 @@ def child_step(name, steps):
     torch.cuda.synchronize()
 
     def plain(k):
-        t, e, tf = dev[k % len(dev)]
-        g.process_pointcloud_device(t.data_ptr(), t.shape[0], np.float32, e, tf)
-        g.combine_maps_device().release()
+        bk.scan_combine(np, g, dev[k % len(dev)]).release()
 
     def with_query(k):
         plain(k)
         g.raycast_device(a.data_ptr(), 1, b.data_ptr(), STEP_QUERY).release()
     for label, step in (("scan+combine_maps_device", plain), ("+one %d-ray query" % STEP_QUERY, with_query)):
-        for k in range(20):
-            step(k)
-        g._check(g._lib.gvom_sync(g._h))
-        us = []
-        for _ in range(3):
-            t0 = time.perf_counter()
-            for k in range(steps):
-                step(k)
-            g._check(g._lib.gvom_sync(g._h))
-            us.append(round((time.perf_counter() - t0) / steps * 1e6, 2))
-        out[label] = {"us_per_step": us, "us_per_step_median": _median(us)}
+        out[label] = bk.step_loop(g, step, steps, warm=20)
+        del out[label]["steps"]                                # (the record's own "steps" says it)
     out["allocations"] = g.get_tuning("raycast_allocations")
     return out
 
 
 def child_kernel(name, n, shuffled):
     """Run under rocprofv3: the calls whose kernel is to be timed."""
-    np, torch, gvom, g, dev = _setup(name)
-    for t, ego, tf in dev:
-        g.process_pointcloud_device(t.data_ptr(), t.shape[0], np.float32, ego, tf)
-        g.combine_maps_device().release()
+    np, torch, gvom, g, dev = bk.setup(name)
+    for scan in dev:
+        bk.scan_combine(np, g, scan).release()
     ego = dev[-1][1]
     a = torch.from_numpy(np.asarray(ego, np.float32).reshape(1, 3)).cuda()
     b = torch.from_numpy(_rays(np, g, ego, n, shuffled)).cuda()
     torch.cuda.synchronize()
     for _ in range(30):
         g.raycast_device(a.data_ptr(), 1, b.data_ptr(), n).release()
-    g._check(g._lib.gvom_sync(g._h))
+    bk.sync(g)
     return {"calls": 30}
 
 
-def _spawn(mode, args, profile_dir=None):
-    cmd = [sys.executable, os.path.abspath(__file__), "--child", mode] + [str(x) for x in args]
-    if profile_dir:
-        cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", profile_dir, "--"] + cmd
-    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
-    if r.returncode != 0:
-        raise SystemExit("%s %r failed (%d):\n%s" % (mode, args, r.returncode, r.stderr[-3000:]))
-    return json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("RESULT ")][-1][7:])
-
-
-def _kernel_stats(profile_dir):
-    for f in glob.glob(os.path.join(profile_dir, "**", "*kernel_stats.csv"), recursive=True):
-        for r in csv.DictReader(open(f)):
-            if "k_raycast" in r["Name"]:
-                return {"calls": int(r["Calls"]), "avg_us": round(float(r["AverageNs"]) / 1e3, 2), "min_us": round(float(r["MinNs"]) / 1e3, 2),
-                        "max_us": round(float(r["MaxNs"]) / 1e3, 2)}
-    return None
-
-
 def main():
-    argv = sys.argv[1:]
-    if len(argv) > 1 and argv[0] == "--child":
-        res = child_step(argv[2], int(argv[3])) if argv[1] == "step" else child_kernel(argv[2], int(argv[3]), argv[4] == "1")
-        print("RESULT " + json.dumps(res))
+    if bk.child(sys.argv[1:], {"step": lambda a: child_step(a[0], int(a[1])), "kernel": lambda a: child_kernel(a[0], int(a[1]), a[2] == "1")}):
         return
-    import lib_identity
-    ident = lib_identity.identity()
-    do_resources = "--resources" in argv
-    parent = "HEAD"
-    if "--parent" in argv:
-        parent = argv[argv.index("--parent") + 1]
-        argv = [x for k, x in enumerate(argv) if x != "--parent" and (k == 0 or argv[k - 1] != "--parent")]
-    rest = [x for x in argv if x != "--resources"]
-    path = rest[0] if rest else os.path.join(ROOT, "profiles", "raycast_%s.json" % (ident.get("lib_sha256") or "unknown")[:8])
-    out = json.load(open(path)) if os.path.exists(path) else {}
-    out["library"] = ident
-    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-
-    def save():
-        with open(path, "w") as f:
-            f.write(json.dumps(out, indent=1) + "\n")
-    if do_resources:
-        out["resources"] = resources(parent)
-        save()
+    args = bk.read_args(sys.argv[1:], configs=CONFIGS)                     # (--parent: a revision, for --resources)
+    report = bk.Report("raycast", args["path"])
+    out = report.out
+    if args["resources"]:
+        out["resources"] = compiled_resources(args["parent"] or "HEAD")
+        report.save()
         print(json.dumps({k: v for k, v in out["resources"].items() if k.startswith(("trace_kernels", "k_raycast"))}))
         return
     out["configs"] = {}
-    for name, steps in CONFIGS:
-        res = _spawn("step", (name, steps))
+    for name in args["configs"]:
+        res = bk.spawn(__file__, "step", (name, CONFIGS[name]), CHILD_TIMEOUT)
         for key, row in res["rays"].items():
             n, order = key.split()
             with tempfile.TemporaryDirectory() as d:
-                _spawn("kernel", (name, n, 1 if order == "shuffled" else 0), profile_dir=d)
-                k = _kernel_stats(d)
+                bk.spawn(__file__, "kernel", (name, n, 1 if order == "shuffled" else 0), CHILD_TIMEOUT, profile_dir=d, stats=True)
+                k = next(iter(bk.kernel_stats(d, ("k_raycast",)).values()), None)
             if k:
                 k["rays_per_s"] = round(int(n) / (k["avg_us"] * 1e-6))
                 k["steps_per_s"] = round(row["total_steps"] / (k["avg_us"] * 1e-6))
@@ -311,7 +244,7 @@ def main():
         base = res["scan+combine_maps_device"]["us_per_step_median"]
         res["query_added_us_per_step"] = round(res["+one %d-ray query" % STEP_QUERY]["us_per_step_median"] - base, 2)
         out["configs"][name] = res
-        save()                                                 # (after every config: a long run leaves what it has)
+        report.save()                                          # (after every config: a long run leaves what it has)
     print(json.dumps(out["configs"], indent=1))
 
 

@@ -15,54 +15,24 @@ neighbours of a rollout are neighbours on the map) -- every loop in a fresh chil
              parent commit's libgvom_hip.so), the same step without scoring on that library, alternating with this one
   registers  tools/kernel_regs.py on the kernel
 
-    tools/rollouts_bench.py [--parent LIB] [out.json]      (default: profiles/rollouts_<lib sha8>.json)
+    tools/rollouts_bench.py [--parent LIB] [--configs m256,c4] [--turns N] [out.json]      (default: profiles/rollouts_<lib sha8>.json)
 """
-import csv
-import glob
 import json
-import os
-import subprocess
 import sys
 import tempfile
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "g-vom_amd"))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-CONFIGS = (("m256", 100), ("c4", 40))                      # (config, timed steps per repetition)
+import benchkit as bk
+
+CONFIGS = {"m256": 100, "c4": 40}                          # config: timed steps per repetition
+TURNS = 2
+CHILD_TIMEOUT = 900                                        # seconds, per child process
 SHAPES = ((4096, 64), (16384, 128))
 ORDERS = ("coherent", "shuffled")
 CAR_CELLS = dict(front=18.0, rear=5.0, half_width=5.5)     # in cells of the config's xy_resolution
 HEADINGS = 64
 THRESHOLD, SOFT = 50, 10
 CHUNK = 2048                                               # rollouts per chunk of the torch form
-
-
-def _median(v):
-    v = sorted(v)
-    return v[len(v) // 2] if len(v) % 2 else 0.5 * (v[len(v) // 2 - 1] + v[len(v) // 2])
-
-
-def _gvom():
-    """The binding, also over the parent's library: it is bound with the entry points it has."""
-    import ctypes
-    import gvom
-    lib = ctypes.CDLL(gvom.library_path())
-    gvom.ABI = [e for e in gvom.ABI if hasattr(lib, e[0])]
-    return gvom
-
-
-def _setup(name):
-    import numpy as np
-    import torch
-    import synth
-    torch.cuda.init()
-    gvom = _gvom()
-    params, scans = synth.config_inputs(name, n_scans=3)
-    dev = [(torch.from_numpy(np.ascontiguousarray(pc)).cuda(), ego, tf) for pc, ego, tf in scans]
-    torch.cuda.synchronize()
-    g = gvom.Gvom(*params, voxel_statistics=False)
-    return np, torch, gvom, g, dev
 
 
 def _field_args(g):
@@ -115,10 +85,9 @@ def _torch_score(torch, cflat, poses, offs_pad, res, oc, xy):
 
 
 def child_score(name, profiled):
-    np, torch, gvom, g, dev = _setup(name)
-    for t, ego, tf in dev:
-        g.process_pointcloud_device(t.data_ptr(), t.shape[0], np.float32, ego, tf)
-        m = g.combine_maps_device()
+    np, torch, gvom, g, dev = bk.setup(name)
+    for scan in dev:
+        m = bk.scan_combine(np, g, scan)
     ego = dev[2][1]
     res, xy = g.xy_resolution, g.xy_size
     table = _car(gvom, g)
@@ -142,23 +111,13 @@ def child_score(name, profiled):
             if profiled:                                           # under rocprofv3: `reps` launches per combination, in this order
                 for _ in range(reps):
                     call().release()
-                g._check(g._lib.gvom_sync(g._h))
+                bk.sync(g)
                 continue
             # the gathers the poses ask for: the cells of every pose's heading (every pose here is valid)
             hs = np.rint(poses[..., 2] * np.float32(HEADINGS / (2.0 * np.pi))).astype(np.int64) % HEADINGS
             out = {"xy": xy, "K": K, "T": T, "order": order, "cells_per_heading_mean": round(float(cells.mean()), 1), "gathers": int(cells[hs].sum())}
-            for _ in range(3):
-                call().release()
-            g._check(g._lib.gvom_sync(g._h))
-            us = []
-            for rep in range(5):
-                t0 = time.perf_counter()
-                for _ in range(reps):
-                    call().release()
-                g._check(g._lib.gvom_sync(g._h))
-                us.append(round((time.perf_counter() - t0) / reps * 1e6, 2))
-            out["call_us"] = us
-            out["call_us_median"] = _median(us)
+            t = bk.timed(g, lambda: call().release(), reps, digits=2)
+            out["call_us"], out["call_us_median"] = t["us"], t["us_median"]
             r = call()
             summary, cost = r.copy_to_host()
             out["status_counts"] = np.bincount(summary[:, 0], minlength=4).tolist()
@@ -175,7 +134,7 @@ def child_score(name, profiled):
                 _torch_score(torch, cflat, tp, offs_pad, res, oc, xy)
                 torch.cuda.synchronize()
                 tus.append(round((time.perf_counter() - t0) * 1e6, 1))
-            out["torch"] = {"equals_product": same, "us": tus, "us_median": _median(tus), "chunk_rollouts": CHUNK, "padded_cells_per_pose": mmax,
+            out["torch"] = {"equals_product": same, "us": tus, "us_median": bk.median(tus), "chunk_rollouts": CHUNK, "padded_cells_per_pose": mmax,
                             "index_bytes_per_call": int(K) * int(T) * mmax * 4}
             r.release()
             results.append(out)
@@ -183,7 +142,7 @@ def child_score(name, profiled):
 
 
 def child_step(name, steps, score):
-    np, torch, gvom, g, dev = _setup(name)
+    np, torch, gvom, g, dev = bk.setup(name)
     K, T = SHAPES[0]
     res = g.xy_resolution
     if score:
@@ -192,87 +151,48 @@ def child_step(name, steps, score):
     torch.cuda.synchronize()
 
     def step(k):
-        t, ego, tf = dev[k % 3]
-        g.process_pointcloud_device(t.data_ptr(), t.shape[0], np.float32, ego, tf)
-        m = g.combine_maps_device()
+        ego = dev[k % 3][1]
+        m = bk.scan_combine(np, g, dev[k % 3])
         e = gvom.world_to_cells([ego[:2]], res, m.origin)[0]
         f = m.cost_to_go([e], **_field_args(g))
         if score:
             g.score_rollouts_of_device(f.cell_cost.ptr, tp[k % 3].data_ptr(), K, T, cost_to_go_ptr=f.cost.ptr, origin=m.origin).release()
         f.release()
         m.release()
-
-    for k in range(min(10, steps)):
-        step(k)
-    g._check(g._lib.gvom_sync(g._h))
-    us = []
-    for rep in range(3):
-        t0 = time.perf_counter()
-        for k in range(steps):
-            step(k)
-        g._check(g._lib.gvom_sync(g._h))
-        us.append(round((time.perf_counter() - t0) / steps * 1e6, 2))
-    return {"us_per_step": us, "us_per_step_median": _median(us), "steps": steps, "K": K if score else 0, "T": T if score else 0}
-
-
-def _spawn(mode, args, profile_dir=None, lib=None):
-    cmd = [sys.executable, os.path.abspath(__file__), "--child", mode] + [str(a) for a in args]
-    if profile_dir:
-        cmd = ["rocprofv3", "--kernel-trace", "--output-format", "csv", "-d", profile_dir, "--"] + cmd
-    env = dict(os.environ, GVOM_HIP_LIBRARY=os.path.abspath(lib)) if lib else None
-    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900, env=env)
-    if r.returncode != 0:
-        raise SystemExit("%s %r failed (%d):\n%s" % (mode, args, r.returncode, r.stderr[-3000:]))
-    line = [ln for ln in r.stdout.splitlines() if ln.startswith("RESULT ")][-1]
-    return json.loads(line[7:])
+    return dict(bk.step_loop(g, step, steps, warm=min(10, steps)), K=K if score else 0, T=T if score else 0)
 
 
 def _kernel_times(profile_dir, calls):
     """the k_rollouts dispatches of a profiled run in launch order, `calls` per combination: per combination the kernel's times
     without its first three launches"""
-    rows = []
-    for f in glob.glob(os.path.join(profile_dir, "**", "*kernel_trace.csv"), recursive=True):
-        for r in csv.DictReader(open(f)):
-            if "k_rollouts" in r["Kernel_Name"]:
-                rows.append((int(r["Start_Timestamp"]), (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3))
-    rows.sort()
+    rows = bk.kernel_trace_rows(profile_dir, ("k_rollouts",))
     out = []
     for k in range(len(rows) // calls):
-        us = [u for _, u in rows[k * calls + 3:(k + 1) * calls]]
-        out.append({"launches": len(us), "avg_us": round(sum(us) / len(us), 2), "median_us": round(_median(us), 2), "min_us": round(min(us), 2),
+        us = [u for _, _, u in rows[k * calls + 3:(k + 1) * calls]]
+        out.append({"launches": len(us), "avg_us": round(sum(us) / len(us), 2), "median_us": round(bk.median(us), 2), "min_us": round(min(us), 2),
                     "max_us": round(max(us), 2)})
     return out
 
 
 def main():
-    if len(sys.argv) > 2 and sys.argv[1] == "--child":
-        mode, a = sys.argv[2], sys.argv[3:]
-        if mode == "score":
-            res = child_score(a[0], a[1] == "1")
-        else:
-            res = child_step(a[0], int(a[1]), a[2] == "1")
-        print("RESULT " + json.dumps(res))
+    if bk.child(sys.argv[1:], {"score": lambda a: child_score(a[0], a[1] == "1"), "step": lambda a: child_step(a[0], int(a[1]), a[2] == "1")}):
         return
     import kernel_regs
-    import lib_identity
-    args = sys.argv[1:]
-    parent = None
-    if args and args[0] == "--parent":
-        parent, args = args[1], args[2:]
-    new = os.path.join(ROOT, "g-vom_amd", "lib", "libgvom_hip.so")
-    out = {"library": lib_identity.identity(), "footprint_cells": CAR_CELLS, "headings": HEADINGS, "density_threshold": THRESHOLD, "soft_weight": SOFT,
-           "registers": {k: v for k, v in kernel_regs.kernels(new).items() if "k_rollouts" in k},
-           "unmeasured": ["a two-kernel form (poses, then summaries) and row spans instead of cell lists (neither is built)",
-                          "maps larger than c4's 512 x 512", "footprints of other sizes"],
-           "configs": {}}
-    if parent:
-        out["parent_library"] = {"lib_sha256": lib_identity.sha256_file(parent)}
-    path = args[0] if args else os.path.join(ROOT, "profiles", "rollouts_%s.json" % (out["library"].get("lib_sha256") or "unknown")[:8])
-    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-    for name, steps in CONFIGS:
-        res = _spawn("score", (name, 0))
+    args = bk.read_args(sys.argv[1:], has_resources=False, configs=CONFIGS, turns=TURNS)
+    parent = args["parent"]
+    spawn = lambda mode, a, **kw: bk.spawn(__file__, mode, a, CHILD_TIMEOUT, **kw)
+    report = bk.Report("rollouts", args["path"], parent, fresh=True)
+    out = report.out
+    out.update({"footprint_cells": CAR_CELLS, "headings": HEADINGS, "density_threshold": THRESHOLD, "soft_weight": SOFT,
+                "registers": {k: v for k, v in kernel_regs.kernels(bk.NEW_LIB).items() if "k_rollouts" in k},
+                "unmeasured": ["a two-kernel form (poses, then summaries) and row spans instead of cell lists (neither is built)",
+                               "maps larger than c4's 512 x 512", "footprints of other sizes"],
+                "configs": {}})
+    for name in args["configs"]:
+        steps = CONFIGS[name]
+        res = spawn("score", (name, 0))
         with tempfile.TemporaryDirectory() as d:
-            calls = _spawn("score", (name, 1), profile_dir=d)["calls"]
+            calls = spawn("score", (name, 1), profile_dir=d)["calls"]
             kernel = _kernel_times(d, calls)
         for k, rec in enumerate(res["scoring"]):
             rec["kernel"] = kernel[k] if len(kernel) == len(res["scoring"]) else None
@@ -282,17 +202,9 @@ def main():
             rec["torch_over_call"] = round(rec["torch"]["us_median"] / rec["call_us_median"], 1)
             # beaten by more than the spread of both: the slowest call against the fastest torch run
             rec["beats_torch_beyond_spread"] = bool(max(rec["call_us"]) < min(rec["torch"]["us"]))
-        runs = {"without": [], "with": [], "parent_without": []}
-        for rnd in range(2):                                        # alternating: parent, without, with, ...
-            if parent:
-                runs["parent_without"].append(_spawn("step", (name, steps, 0), lib=parent))
-            runs["without"].append(_spawn("step", (name, steps, 0)))
-            runs["with"].append(_spawn("step", (name, steps, 1)))
-        step = {}
-        for who, rs in runs.items():
-            if rs:
-                us = [u for r in rs for u in r["us_per_step"]]
-                step[who] = {"us_per_step": us, "median": _median(us), "spread_us": round(max(us) - min(us), 2)}
+        runs = bk.alternate(args["turns"], {"parent_without": parent and (lambda: spawn("step", (name, steps, 0), lib=parent)),
+                                            "without": lambda: spawn("step", (name, steps, 0)), "with": lambda: spawn("step", (name, steps, 1))})
+        step = {who: bk.pooled(rs) for who, rs in runs.items() if rs}      # (this file's keys are older than spreads())
         step["scoring_adds_us_per_step"] = round(step["with"]["median"] - step["without"]["median"], 2)
         if parent:
             d = step["without"]["median"] - step["parent_without"]["median"]
@@ -300,8 +212,7 @@ def main():
             step["within_parent_spread"] = bool(abs(d) <= step["parent_without"]["spread_us"])
         res["step: scan + combine_maps_device + cost_to_go (+ score_rollouts %d x %d)" % SHAPES[0]] = step
         out["configs"][name] = res
-        with open(path, "w") as f:                                  # (after every config: a long run leaves what it has)
-            f.write(json.dumps(out, indent=1) + "\n")
+        report.save()                                              # (after every config: a long run leaves what it has)
     print(json.dumps(out, indent=1))
 
 

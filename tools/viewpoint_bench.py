@@ -17,41 +17,23 @@ first child that fails ends the run:
   resources  tools/kernel_regs.py: the new kernels, and registers, scratch, LDS and code size of every kernel outside the new
              unit on the parent and on this library (--resources alone: no GPU needed)
 
-    tools/viewpoint_bench.py [--resources] [--parent LIB] [--configs m256,c4] [out.json]   (default: profiles/viewpoints_<lib sha8>.json)
+    tools/viewpoint_bench.py [--resources] [--parent LIB] [--configs m256,c4] [--turns N] [out.json]   (default: profiles/viewpoints_<lib sha8>.json)
 """
-import csv
-import glob
 import json
 import math
-import os
-import subprocess
 import sys
 import tempfile
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "g-vom_amd"))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+import benchkit as bk
+
 CONFIGS = {"m256": 100, "c4": 40}                         # config: timed steps per repetition
+TURNS = 5
 MODEL = (64, 1024)
 SHAPES = ((64, (1, 1)), (64, (2, 4)), (512, (1, 1)), (512, (2, 4)))      # (K, beam strides)
 MAX_RANGE = 20.0
 CHILD_TIMEOUT = 300                                       # seconds, per child process
 KERNELS = ("k_viewpoints", "k_viewpoint_best", "fillBuffer")
-
-
-def _median(v):
-    v = sorted(v)
-    return v[len(v) // 2] if len(v) % 2 else 0.5 * (v[len(v) // 2 - 1] + v[len(v) // 2])
-
-
-def _gvom():
-    """The binding, also over the parent's library: it is bound with the entry points it has."""
-    import ctypes
-    import gvom
-    lib = ctypes.CDLL(gvom.library_path())
-    gvom.ABI = [e for e in gvom.ABI if hasattr(lib, e[0])]
-    return gvom
 
 
 def _model(np):
@@ -69,15 +51,7 @@ def _poses(np, gvom, ego, K):
 
 
 def _setup(name, with_model=True):
-    import numpy as np
-    import torch
-    import synth
-    torch.cuda.init()
-    gvom = _gvom()
-    params, scans = synth.config_inputs(name, n_scans=3)
-    dev = [(torch.from_numpy(np.ascontiguousarray(pc)).cuda(), ego, tf) for pc, ego, tf in scans]
-    torch.cuda.synchronize()
-    g = gvom.Gvom(*params, voxel_statistics=False)
+    np, torch, gvom, g, dev = bk.setup(name)
     if with_model:
         g.set_sensor_model(_model(np))
     return np, torch, gvom, g, dev
@@ -96,9 +70,8 @@ def _targets(np, d, pose, r, strides):
 
 def child_call(name, profiled):
     np, torch, gvom, g, dev = _setup(name)
-    for t, ego, tf in dev:
-        g.process_pointcloud_device(t.data_ptr(), t.shape[0], np.float32, ego, tf)
-        g.combine_maps_device().release()
+    for scan in dev:
+        bk.scan_combine(np, g, scan).release()
     ego = dev[2][1]
     reps, results = 20, {}
     for K, strides in SHAPES:
@@ -110,23 +83,14 @@ def child_call(name, profiled):
         if profiled:
             for _ in range(reps):
                 call().release()
-            g._check(g._lib.gvom_sync(g._h))
+            bk.sync(g)
             continue
-        for _ in range(3):
-            call().release()
-        g._check(g._lib.gvom_sync(g._h))
-        us = []
-        for rep in range(5):
-            t0 = time.perf_counter()
-            for _ in range(reps):
-                call().release()
-            g._check(g._lib.gvom_sync(g._h))
-            us.append(round((time.perf_counter() - t0) / reps * 1e6, 2))
+        us = bk.timed(g, lambda: call().release(), reps, digits=2)["us"]
         v = call()
         rows, best = v.copy_to_host()
         v.release()
         nb = int(best[3])
-        out = {"xy": g.xy_size, "z": g.z_size, "K": K, "beams_per_viewpoint": nb, "call_us": us, "call_us_median": _median(us),
+        out = {"xy": g.xy_size, "z": g.z_size, "K": K, "beams_per_viewpoint": nb, "call_us": us, "call_us_median": bk.median(us),
                "viewpoints_per_launch": g.get_tuning("viewpoint_batch"), "best": best.tolist(), "gain_sum": int(rows[:, 1].sum()),
                "visits_sum": int(rows[:, 2].sum()), "visits_over_gain": round(float(rows[:, 2].sum()) / max(int(rows[:, 1].sum()), 1), 2),
                "beam_endings": rows[:, 3:].sum(axis=0).tolist(), "origin_statuses": np.bincount(rows[:, 0], minlength=5).tolist()}
@@ -160,26 +124,17 @@ def child_call(name, profiled):
             B = torch.from_numpy(np.ascontiguousarray(np.concatenate([b for _, b in ab]))).cuda()
             torch.cuda.synchronize()
             one = lambda: g.raycast_device(A.data_ptr(), A.shape[0], B.data_ptr(), B.shape[0])
-            for _ in range(3):
-                one().release()
-            g._check(g._lib.gvom_sync(g._h))
-            ws = []
-            for rep in range(5):
-                t0 = time.perf_counter()
-                for _ in range(10):
-                    one().release()
-                g._check(g._lib.gvom_sync(g._h))
-                ws.append(round((time.perf_counter() - t0) / 10 * 1e6, 2))
+            ws = bk.timed(g, lambda: one().release(), digits=2)["us"]
             with one() as rays:
                 walk_visits = int(rays.result.copy_to_host()[:, 3].astype(np.int64).sum())
-            out["walk_alone_one_raycast_call"] = {"rays": int(A.shape[0]), "call_us": ws, "call_us_median": _median(ws),
+            out["walk_alone_one_raycast_call"] = {"rays": int(A.shape[0]), "call_us": ws, "call_us_median": bk.median(ws),
                                                   "unknown_sum_equals_visits": bool(walk_visits == int(rows[:, 2].sum()))}
             del A, B
             out["from_existing_parts"] = {"covers": "visits and the beam endings; the gain has no such form",
                                           "equal_to_the_product": bool(np.array_equal(got, rows[:, 2:].astype(np.int64))),
                                           "us_build_targets_on_host": [t[0] for t in ts], "us_upload": [t[1] for t in ts],
                                           "us_K_raycast_calls_and_sums": [t[2] for t in ts],
-                                          "us_median_total": _median([sum(t) for t in ts]), "uploaded_bytes": K * nb * 12}
+                                          "us_median_total": bk.median([sum(t) for t in ts]), "uploaded_bytes": K * nb * 12}
         results[key] = out
     return {"calls": reps} if profiled else results
 
@@ -190,9 +145,7 @@ def child_step(name, steps, with_query):
     tp = None
 
     def step(k):
-        t, ego, tf = dev[k % 3]
-        g.process_pointcloud_device(t.data_ptr(), t.shape[0], np.float32, ego, tf)
-        m = g.combine_maps_device()
+        m = bk.scan_combine(np, g, dev[k % 3])
         if with_query:
             g.score_viewpoints_device(tp.data_ptr(), K, MAX_RANGE, beam_stride=strides).release()
         m.release()
@@ -200,42 +153,12 @@ def child_step(name, steps, with_query):
     if with_query:
         tp = torch.from_numpy(_poses(np, gvom, dev[2][1], K)).cuda()
         torch.cuda.synchronize()
-    for k in range(min(10, steps)):
-        step(k)
-    g._check(g._lib.gvom_sync(g._h))
-    us = []
-    for rep in range(3):
-        t0 = time.perf_counter()
-        for k in range(steps):
-            step(k)
-        g._check(g._lib.gvom_sync(g._h))
-        us.append(round((time.perf_counter() - t0) / steps * 1e6, 2))
-    return {"us_per_step": us, "us_per_step_median": _median(us), "steps": steps}
-
-
-def _spawn(mode, args, profile_dir=None, lib=None):
-    """one child under its own time limit; a child that fails (or runs into the limit) ends the whole run"""
-    cmd = [sys.executable, os.path.abspath(__file__), "--child", mode] + [str(a) for a in args]
-    if profile_dir:
-        cmd = ["rocprofv3", "--kernel-trace", "--output-format", "csv", "-d", profile_dir, "--"] + cmd
-    cmd = ["timeout", "-k", "10", str(CHILD_TIMEOUT)] + cmd
-    env = dict(os.environ, GVOM_HIP_LIBRARY=os.path.abspath(lib)) if lib else None
-    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=env)
-    if r.returncode != 0:
-        raise SystemExit("%s %r failed (%d): nothing more is started\n%s" % (mode, args, r.returncode, r.stderr[-3000:]))
-    line = [ln for ln in r.stdout.splitlines() if ln.startswith("RESULT ")][-1]
-    return json.loads(line[7:])
+    return bk.step_loop(g, step, steps, warm=min(10, steps))
 
 
 def _kernel_times(profile_dir, calls):
     """per shape (k_viewpoint_best ends a call): the kernels' and the fills' microseconds per call, without the first three calls"""
-    rows = []
-    for f in glob.glob(os.path.join(profile_dir, "**", "*kernel_trace.csv"), recursive=True):
-        for r in csv.DictReader(open(f)):
-            key = [k for k in KERNELS if k in r["Kernel_Name"]]
-            if key:
-                rows.append((int(r["Start_Timestamp"]), key[0], (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3))
-    rows.sort()
+    rows = bk.kernel_trace_rows(profile_dir, KERNELS)
     ends = [i for i, r in enumerate(rows) if r[1] == "k_viewpoint_best"]
     if len(ends) != calls * len(SHAPES):
         return None
@@ -247,7 +170,7 @@ def _kernel_times(profile_dir, calls):
         rec = {}
         for k in KERNELS:
             us = [u for _, kk, u in part if kk == k]
-            rec[k] = {"launches_per_call": round(len(us) / used, 2), "us_per_call": round(sum(us) / used, 2), "median_us_per_launch": round(_median(us), 2) if us else None}
+            rec[k] = {"launches_per_call": round(len(us) / used, 2), "us_per_call": round(sum(us) / used, 2), "median_us_per_launch": round(bk.median(us), 2) if us else None}
         total = sum(u for _, _, u in part) / used
         rec["device_us_per_call"] = round(total, 2)
         rec["clears_share_of_device_time"] = round(rec["fillBuffer"]["us_per_call"] / total, 4) if total else None
@@ -255,90 +178,41 @@ def _kernel_times(profile_dir, calls):
     return out
 
 
-def resources(new, parent):
-    """the new unit's kernels, and every other kernel on the parent and on this library: registers, scratch, LDS, code size"""
-    import kernel_regs
-    mine = kernel_regs.kernels(new)
-    out = {"new_kernels": {k: v for k, v in mine.items() if "k_viewpoint" in k}}
-    if parent:
-        theirs = kernel_regs.kernels(parent)
-        rest = {k: v for k, v in mine.items() if "k_viewpoint" not in k}
-        keys = ("vgpr", "sgpr", "scratch", "lds", "code")
-        changed = {k: {"parent": theirs.get(k), "new": v} for k, v in rest.items() if any((theirs.get(k) or {}).get(q) != v.get(q) for q in keys)}
-        out["other_kernels"] = {"count": len(rest), "identical_to_parent": len(rest) - len(changed), "changed": changed,
-                                "only_on_parent": sorted(k for k in theirs if k not in mine)}
-        out["k_raycast"] = {k: v for k, v in rest.items() if "k_raycast" in k}
-    return out
-
-
 def main():
-    if len(sys.argv) > 2 and sys.argv[1] == "--child":
-        mode, a = sys.argv[2], sys.argv[3:]
-        res = child_call(a[0], a[1] == "1") if mode == "call" else child_step(a[0], int(a[1]), a[2] == "1")
-        print("RESULT " + json.dumps(res))
+    if bk.child(sys.argv[1:], {"call": lambda a: child_call(a[0], a[1] == "1"), "step": lambda a: child_step(a[0], int(a[1]), a[2] == "1")}):
         return
-    import lib_identity
-    args = sys.argv[1:]
-    parent, only_resources, configs = None, False, list(CONFIGS)
-    while args and args[0] in ("--parent", "--resources", "--configs"):
-        if args[0] == "--parent":
-            parent, args = args[1], args[2:]
-        elif args[0] == "--configs":
-            configs, args = args[1].split(","), args[2:]
-        else:
-            only_resources, args = True, args[1:]
-    new = os.path.join(ROOT, "g-vom_amd", "lib", "libgvom_hip.so")
-    path = args[0] if args else os.path.join(ROOT, "profiles", "viewpoints_%s.json" % (lib_identity.identity().get("lib_sha256") or "unknown")[:8])
-    out = json.load(open(path)) if os.path.exists(path) else {}
-    out.update({"library": lib_identity.identity(), "model": list(MODEL), "max_range_m": MAX_RANGE, "shapes": [[K, list(s)] for K, s in SHAPES]})
-    out["resources"] = resources(new, parent)
-    if parent:
-        out["parent_library"] = {"lib_sha256": lib_identity.sha256_file(parent)}
-    out.setdefault("not_measured", ["c5", "RQ_DEPTH other than 4", "per-wave combining of ORs to the same word (not built)",
-                                    "non-returning ORs plus a population-count pass over the bitmaps (not built)",
-                                    "viewpoint_bitmap_mb other than the default 256", "the gain from existing parts (k_raycast records no voxels)",
-                                    "from_existing_parts and the walk alone at K = 512", "the host route", "hardware counters"])
-    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-
-    def save():
-        with open(path, "w") as f:                                  # (after every part: a run that ends early leaves what it has)
-            f.write(json.dumps(out, indent=1) + "\n")
-    save()
-    if only_resources:
-        out.setdefault("configs", "not measured")
-        save()
+    args = bk.read_args(sys.argv[1:], configs=CONFIGS, turns=TURNS)
+    parent = args["parent"]
+    spawn = lambda mode, a, **kw: bk.spawn(__file__, mode, a, CHILD_TIMEOUT, **kw)
+    report, configs = bk.product_report(
+        "viewpoints", args, {"model": list(MODEL), "max_range_m": MAX_RANGE, "shapes": [[K, list(s)] for K, s in SHAPES]}, lambda k: "k_viewpoint" in k,
+        ["c5", "RQ_DEPTH other than 4", "per-wave combining of ORs to the same word (not built)",
+         "non-returning ORs plus a population-count pass over the bitmaps (not built)",
+         "viewpoint_bitmap_mb other than the default 256", "the gain from existing parts (k_raycast records no voxels)",
+         "from_existing_parts and the walk alone at K = 512", "the host route", "hardware counters"])
+    if parent:                                                      # (the kernel whose step body k_viewpoints shares, shown beside the new ones)
+        import kernel_regs
+        report.out["resources"]["k_raycast"] = {k: v for k, v in kernel_regs.kernels(bk.NEW_LIB).items() if "k_raycast" in k}
+        report.save()
+    if configs is None:
         return
-    if not isinstance(out.get("configs"), dict):
-        out["configs"] = {}
-    for name in configs:
+    for name in args["configs"]:
         steps = CONFIGS[name]
-        res = _spawn("call", (name, 0))
+        res = spawn("call", (name, 0))
         with tempfile.TemporaryDirectory() as d:
-            prof = _spawn("call", (name, 1), profile_dir=d)
+            prof = spawn("call", (name, 1), profile_dir=d)
             kernel = _kernel_times(d, prof["calls"])
         for key in res:
             res[key]["kernels"] = kernel[key] if kernel else "not measured (the trace did not hold the expected launches)"
-        out["configs"][name] = res
-        save()
-        runs = {"without": [], "with": [], "parent_without": []}
-        for rnd in range(5):                                        # alternating: parent, without, with, ...
-            if parent:
-                runs["parent_without"].append(_spawn("step", (name, steps, 0), lib=parent))
-            runs["without"].append(_spawn("step", (name, steps, 0)))
-            runs["with"].append(_spawn("step", (name, steps, 1)))
-        step = {}
-        for who, rs in runs.items():
-            if rs:
-                meds = [r["us_per_step_median"] for r in rs]
-                step[who] = {"run_medians_us": meds, "median": _median(meds), "min": min(meds), "max": max(meds)}
+        configs[name] = res
+        report.save()
+        runs = bk.alternate(args["turns"], {"parent_without": parent and (lambda: spawn("step", (name, steps, 0), lib=parent)),
+                                            "without": lambda: spawn("step", (name, steps, 0)), "with": lambda: spawn("step", (name, steps, 1))})
+        step = bk.spreads(runs)
         step["query_adds_us_per_step"] = round(step["with"]["median"] - step["without"]["median"], 2)
-        if parent:
-            p = step["parent_without"]
-            step["without_inside_parents_own_spread"] = bool(p["min"] <= step["without"]["median"] <= p["max"])
-            step["without_minus_parent_median_us"] = round(step["without"]["median"] - p["median"], 2)
-        res["step: scan + combine_maps_device (+ a query of K = 64, strides (2, 4))"] = step
-        save()
-    print(json.dumps(out, indent=1))
+        res["step: scan + combine_maps_device (+ a query of K = 64, strides (2, 4))"] = bk.against_parent(step, "without", "parent_without", "without_")
+        report.save()
+    print(json.dumps(report.out, indent=1))
 
 
 if __name__ == "__main__":

@@ -755,6 +755,7 @@ VIS int gvom_sensor_model_set(gvom_t *h, int32_t H, int32_t W, const double *dir
     else HIPCHK(h, hipMemsetAsync(m + half, 0, half, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     h->ri_H = H; h->ri_W = W;
+    ++h->ri_gen;                                                            // (what the voxel atlas keeps of the model is stale from here on)
     h->ri_scale = range_scale; h->ri_min = min_range; h->ri_max = max_range;
     return GVOM_OK;
 }

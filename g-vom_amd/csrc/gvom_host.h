@@ -1,5 +1,5 @@
 // gvom_host.h -- private to the host units of libgvom_hip.so (gvom_handle / gvom_capi (scans) / gvom_combine / gvom_sets / gvom_product_calls /
-// gvom_atlas_calls / gvom_debug .hip): the handle and what it is made of, and the functions that cross those units' boundaries (namespace
+// gvom_atlas_calls / gvom_voxel_atlas_calls / gvom_debug .hip): the handle and what it is made of, and the functions that cross those units' boundaries (namespace
 // gvom_host; -fvisibility=hidden keeps them out of the dynamic symbol table) -- among them what the product calls and the atlas calls
 // share: the round driver of the calls that wait, their epilogue, the argument checks, the staging of host inputs (at the end of this
 // file).  Not part of the public interface (include/gvom_hip.h is); no kernel unit includes it.
@@ -408,6 +408,23 @@ struct gvom_handle {
     // afr_allocs counts it and the entry point's product sets (gvom_get_tuning "atlas_frontier_allocations")
     SolveWork afr;
     int afr_allocs = 0;
+    // VOXEL ATLAS (gvom_voxel_atlas_*): va_mem = the pairs of va_A x va_A x va_Z voxels (gvom_voxel_atlas.hip has the layout; va_A == 0: none
+    // configured), va_cnt = 256 bytes of uint64 counters in device memory (gvom_internal.h VA_CNT_*) and va_pin their pinned copy for
+    // gvom_voxel_atlas_counts; va_E = the extent's origin in world voxels, va_seq = integrates so far, va_last = the window origin of the last
+    // integrate (the default of a box), va_outside / va_moved = counts [5] and [6] of the last integrate, which the host computes.  va_stage =
+    // the staging copy of a caller's host segments or poses, with the viewpoints' boxes behind them; va_bitmaps = the viewpoints' bitmaps
+    // under "viewpoint_bitmap_mb".  va_dmax / va_omax = the sensor model's largest finite |direction| and |offset| per axis, read back by the
+    // first viewpoint call after a gvom_sensor_model_set (ri_gen counts those; va_model_gen says which model the two were made of).
+    // va_allocs counts the device allocations the entry points have made on this handle (gvom_get_tuning "voxel_atlas_allocations")
+    unsigned long long *va_mem = nullptr, *va_cnt = nullptr, *va_pin = nullptr;
+    Buf va_stage, va_bitmaps;
+    int va_A = 0, va_Z = 0, va_follow = 1;
+    int64_t va_E[3] = {0, 0, 0}, va_last[3] = {0, 0, 0};
+    int64_t va_seq = 0, va_outside = 0, va_moved = 0;
+    double va_dmax[3] = {0, 0, 0}, va_omax[3] = {0, 0, 0};
+    uint64_t ri_gen = 0, va_model_gen = 0;
+    int va_allocs = 0;
+    int va_last_batch = 0;                              // poses per launch of the last gvom_voxel_atlas_score_viewpoints ("voxel_atlas_viewpoint_batch", read-only)
     // ATTITUDE VOLUMES (gvom_attitude_volume): av_tab = what k_volume_attitude_table makes of the footprint table and the chassis --
     // (u - am, v) float64 pairs of every footprint cell, then at av_wcell_at bytes (a multiple of 256) per heading the wheels' cell offsets and the
     // footprint's box, [H][12] int32 --, rebuilt by the first call after a gvom_footprint_set / gvom_chassis_set (fp_gen / at_gen count those; av_fp_gen

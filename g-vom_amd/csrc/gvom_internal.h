@@ -495,6 +495,59 @@ hipError_t gvom_launch_atlas_field_window(hipStream_t s, int A, const int32_t *f
 // storage phase.  L, count, flags and n_frontier as for gvom_launch_frontier_mark; relax, rows and finish follow at side xy.
 hipError_t gvom_launch_atlas_frontier_mark(hipStream_t s, int xy, const uint16_t *c, const int32_t *D, const char *atlas, int A, int ox,
                                            int oy, int px, int py, uint32_t *L, uint32_t *count, uint32_t *flags, uint32_t *n_frontier);
+// voxel atlas (gvom_voxel_atlas.hip; include/gvom_hip.h "voxel atlas" defines the result).  The atlas is A x A x Z voxels at 2 bits each,
+// A and Z powers of two, behind one base address; the layout is that unit's own.  Every box of voxels is given RELATIVE to the extent:
+// r = box origin - extent origin (|.| <= 2^30, the host clamps); pe* = extent origin & (size - 1), the storage phase of extent voxel 0.
+// cnt = the atlas's counters, uint64 [16]: the slots below (two's complement sums; the host keeps what it can compute itself).
+#define GVOM_VATLAS_MIN_CELLS 64
+#define GVOM_VATLAS_MAX_CELLS 4096
+#define VA_CNT_MOVED_OBS 7     // [0..4] of the last integrate {first seen, free -> occupied, occupied -> free, confirmed, uninformative}
+#define VA_CNT_OBSERVED 8      // [7] observed voxels the last move cleared; [8], [9] observed / occupied voxels the atlas holds
+#define VA_CNT_OCCUPIED 9
+struct VAtlas {
+    unsigned long long *pairs;
+    int A, Z;
+    int lgZ, lgP;             // log2 Z, log2 (A / 64)
+};
+inline size_t gvom_vatlas_bytes(int A, int Z) { return (size_t)A * A / 4 * Z; }
+// merge: the window rows [y0, y0 + ny) and levels [z0, z0 + nz) that lie inside the extent; of the columns, the npx STORAGE pair columns
+// from bx on (mod A/64) that hold the window's columns inside the extent; npairs = ny * nz * npx, the pairs the merge visits (the launcher holds the three to it).  F = the fused map's frame as
+// k_occupancy takes it.  Adds to cnt[0..4], cnt[8], cnt[9].
+struct VAtlasWindow {
+    int y0, ny, z0, nz;
+    int rx, ry, rz;
+    int pex, pey, pez;
+    int bx, npx;
+    uint32_t npairs;
+};
+// move: the pairs of storage rows [ys, ys + ny) mod A and levels [zs, zs + nz) mod Z lose the bits of storage columns [xs, xs + wx) mod A;
+// npairs = ny * nz * (A / 64).  Adds the observed voxels it clears to cnt[7] and takes what it clears from cnt[8], cnt[9].
+struct VAtlasSlab {
+    int ys, ny, zs, nz, xs, wx;
+    uint64_t npairs;
+};
+// box: n x n x zs voxels from r on, p* = box origin & (size - 1); out[x][y][z] uint8 = 0 never observed (and outside the extent), 1
+// observed free, 2 occupied; counts int32 [4], words 0 and 1 CLEARED by the caller (added to) = {occupied, free}, words 2 and 3 =
+// outside, seq as given.  zc, yb: the launcher's.
+struct VAtlasBox {
+    int n, zs;
+    int rx, ry, rz;
+    int px, py, pz;
+    int outside, seq;
+    int zc, yb;
+};
+hipError_t gvom_launch_vatlas_merge(hipStream_t s, const VAtlas &V, const VAtlasWindow &D, const OccParams &F, const int32_t *fstate,
+                                    const uint32_t *ftags, unsigned long long *cnt);
+hipError_t gvom_launch_vatlas_move(hipStream_t s, const VAtlas &V, const VAtlasSlab &S, unsigned long long *cnt);
+hipError_t gvom_launch_vatlas_box(hipStream_t s, const VAtlas &V, VAtlasBox B, uint8_t *out, int32_t *counts);
+// the walks: P = gvom_launch_raycast's frame with the extent in the window's place (origin = E, xy = A, zs = Z, om = E & (size - 1)), Q as
+// there with cap = A + Z.  raycast: out3 [n][3] = {status, steps, unknown}, pos3 [n][3] the stop position in metres, vox3 [n][3] the world
+// voxel of the stop.  viewpoints / viewpoint_best: as gvom_launch_viewpoints / _viewpoint_best; boxes [K][8] int32 = {lx, ly, lz, dx, dy,
+// dz, 0, 0}, the box of extent voxels of every pose (inside the extent, dx * dy * dz <= 32 * Q.bm_words).
+hipError_t gvom_launch_vatlas_raycast(hipStream_t s, const ScanParams &P, const RayQuery &Q, const VAtlas &V, int32_t *out3, float *pos3, int32_t *vox3);
+hipError_t gvom_launch_vatlas_viewpoints(hipStream_t s, const ScanParams &P, const ViewQuery &Q, const VAtlas &V, int batch, const int32_t *boxes,
+                                         uint32_t *bitmaps, int32_t *rows);
+hipError_t gvom_launch_vatlas_viewpoint_best(hipStream_t s, const ScanParams &P, const ViewQuery &Q, const VAtlas &V, int32_t *rows, int32_t *best);
 // storage order [sy][sx] -> reference order [x][y] (window coordinates)
 hipError_t gvom_launch_unwrap_f64(hipStream_t s, int xy, int om0, int om1, const double *in, int in_stride, double *out_xy);
 hipError_t gvom_launch_posdens(hipStream_t s, const Map2dParams &P, const int32_t *fstate,

@@ -40,6 +40,11 @@
 //   attitude volume (30)  cap x xy*xy uint8 (status), then cap x xy*xy uint8 (tilt): volumes [h][y][x], every plane laid out like a pose
 //                    field's; then 8 int32 {states per status 0 .. 6, H}; cap = the headings H of the call that wrote it.  Kind 29 is
 //                    not assigned
+//   voxel box (32)   xy*xy*zs bytes, out[x][y][z] like the occupancy grid: the class codes 0 / 1 / 2 of a box of the voxel atlas; then 4 int32
+//                    {occupied, free, outside the extent, seq}.  Kind 31 is not assigned
+//   atlas rays (34)  cap x 3 int32 {status, steps, unknown}, then cap x 3 floats (stop position), then cap x 3 int32 (the world voxel of the
+//                    stop); cap = the rays of the call that wrote it.  Kind 33 is not assigned
+//   atlas viewpoints (36)  the two parts of viewpoints (18).  Kind 35 is not assigned
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -86,6 +91,9 @@ inline size_t set_bytes(int kind, int xy, int zs, int64_t cap, int64_t cols = 0)
     case GVOM_PRODUCT_ATLAS_FIELD: return align256((size_t)cap * (size_t)cap * 4) + align256((size_t)cap * (size_t)cap) + (size_t)cap * (size_t)cap * 2;
     case GVOM_PRODUCT_ATLAS_FRONTIERS: return align256((size_t)cap * 32) + align256((size_t)cap * 16) + align256((size_t)cols * (size_t)cols * 4) + 16;
     case GVOM_PRODUCT_ATTITUDE_VOLUME: return 2 * align256((size_t)cap * n2) + 32;
+    case GVOM_PRODUCT_VOXEL_BOX: return align256(n2 * zs) + 16;
+    case GVOM_PRODUCT_VOXEL_ATLAS_RAYS: return 2 * align256((size_t)cap * 12) + (size_t)cap * 12;
+    case GVOM_PRODUCT_VOXEL_ATLAS_VIEWPOINTS: return align256((size_t)cap * 32) + 16;
     }
     return 0;
 }
@@ -172,6 +180,7 @@ inline bool set_part(const SetShape *s, int part, SetPart *d)
         break;
     }
     case GVOM_PRODUCT_VIEWPOINTS:
+    case GVOM_PRODUCT_VOXEL_ATLAS_VIEWPOINTS:              // (36: the same two parts)
         if (part == 0) { rows(s->mem, s->cap, 8); d->code = kDLInt; }
         else if (part == 1) { d->ptr = s->mem + align256((size_t)s->cap * 32); d->ndim = 1; d->shape[0] = 4; d->strides[0] = 1; d->shape[1] = d->strides[1] = 1; d->code = kDLInt; }
         else return false;
@@ -220,6 +229,20 @@ inline bool set_part(const SetShape *s, int part, SetPart *d)
         d->code = kDLUInt; d->bits = 8;
         break;
     }
+    case GVOM_PRODUCT_VOXEL_BOX:
+        if (part == 0) {
+            d->ptr = s->mem; d->ndim = 3; d->code = kDLUInt; d->bits = 8;
+            d->shape[0] = d->shape[1] = xy; d->shape[2] = s->zs;
+            d->strides[0] = xy * s->zs; d->strides[1] = s->zs; d->strides[2] = 1;
+        }
+        else if (part == 1) { d->ptr = s->mem + align256((size_t)n2 * s->zs); d->ndim = 1; d->shape[0] = 4; d->strides[0] = 1; d->shape[1] = d->strides[1] = 1; d->code = kDLInt; }
+        else return false;
+        break;
+    case GVOM_PRODUCT_VOXEL_ATLAS_RAYS:
+        if (part < 0 || part > 2) return false;
+        rows(s->mem + (size_t)part * align256((size_t)s->cap * 12), s->cap, 3);
+        if (part != 1) d->code = kDLInt;
+        break;
     default: return false;
     }
     d->bytes = (size_t)(d->shape[0] * d->shape[1] * d->shape[2]) * (d->bits / 8);

@@ -1,0 +1,447 @@
+// gvom_voxel_atlas_calls.hip -- the voxel atlas's entry points (include/gvom_hip.h "voxel atlas"): gvom_voxel_atlas_configure, _integrate,
+// _clear, _counts, _box, _raycast and _score_viewpoints.  The kernels are gvom_voxel_atlas.hip's; everything runs on the handle's stream --
+// an integrate behind whatever produced the current fused map, a query behind the integrates before it -- and only gvom_voxel_atlas_counts
+// waits for it (the viewpoint call waits where it has to read poses or the sensor model back: the boxes of its bitmaps are proved here, on
+// the host).  The products go through the pool path of every product call (product_acquire / product_publish, gvom_sets.hip), host inputs
+// through stage_host, the checks through refuse (gvom_host.h).
+#include "gvom_host.h"
+
+namespace {
+const int64_t VA_FAR = (int64_t)1 << 30;                   // E and W stay below this in magnitude; a box this far from the extent lies outside it
+
+int need_atlas(gvom_handle *h, const char *fn)
+{
+    if (h->sharded) return refuse(h, fn, "sharded handles are not supported");
+    return h->va_A ? GVOM_OK : refuse(h, fn, "no voxel atlas is configured (gvom_voxel_atlas_configure)");
+}
+
+int lg2(int v) { int k = 0; while ((1 << k) < v) ++k; return k; }
+
+VAtlas atlas_of(const gvom_handle *h)
+{
+    VAtlas V;
+    V.pairs = h->va_mem; V.A = h->va_A; V.Z = h->va_Z;
+    V.lgZ = lg2(h->va_Z); V.lgP = lg2(h->va_A / 64);
+    return V;
+}
+
+int side(const gvom_handle *h, int k) { return k < 2 ? h->va_A : h->va_Z; }
+int window_side(const gvom_handle *h, int k) { return k < 2 ? h->prm.xy_size : h->prm.z_size; }
+bool near_origin(const int64_t o[3]) { return o[0] > -VA_FAR && o[0] < VA_FAR && o[1] > -VA_FAR && o[1] < VA_FAR && o[2] > -VA_FAR && o[2] < VA_FAR; }
+
+// box origin - extent origin on axis k, clamped to +-2^30 (|E| < 2^30: the comparisons cannot overflow)
+int rel_of(const gvom_handle *h, const int64_t B[3], int k)
+{
+    const int64_t e = h->va_E[k];
+    if (B[k] >= e + VA_FAR) return (int)VA_FAR;
+    if (B[k] <= e - VA_FAR) return -(int)VA_FAR;
+    return (int)(B[k] - e);
+}
+
+// the part [lo, lo + n) of a box side of `len` voxels at relative origin r that lies inside the extent's side of `size`
+void clip(int r, int len, int size, int *lo, int *n)
+{
+    const int64_t a = std::max<int64_t>(0, -(int64_t)r), b = std::min<int64_t>(len, (int64_t)size - r);
+    *lo = b > a ? (int)a : 0;
+    *n = b > a ? (int)(b - a) : 0;
+}
+
+// follow mode: the extent goes to `to`; the voxels that entered it become NEVER -- the slab of columns over every row and level, the slab
+// of rows over the remaining columns, the slab of levels over the remaining rows and columns: every cleared voxel is counted once.  A move
+// of a whole side or more on an axis is the first slab alone, A wide
+int move_extent(gvom_handle *h, const int64_t to[3])
+{
+    const VAtlas V = atlas_of(h);
+    const int A = V.A, Z = V.Z;
+    int w[3], s[3];                                                          // per axis: how many storage coordinates entered, from where on
+    bool all = false;
+    for (int k = 0; k < 3; ++k) {
+        const int64_t d = to[k] - h->va_E[k], ad = d < 0 ? -d : d;
+        const int size = side(h, k);
+        all = all || ad >= size;
+        w[k] = (int)std::min<int64_t>(ad, size);
+        s[k] = (int)((d > 0 ? to[k] + size - w[k] : to[k]) & (size - 1));
+    }
+    const int64_t total = (int64_t)A * A * Z;
+    h->va_moved = all ? total : total - (int64_t)(A - w[0]) * (A - w[1]) * (Z - w[2]);
+    auto slab = [&](int ys, int ny, int zs, int nz, int xs, int wx) {
+        VAtlasSlab S;
+        S.ys = ys; S.ny = ny; S.zs = zs; S.nz = nz; S.xs = xs; S.wx = wx;
+        S.npairs = (uint64_t)ny * (uint64_t)nz * (uint64_t)(A / 64);
+        return gvom_launch_vatlas_move(h->stream, V, S, h->va_cnt);
+    };
+    if (all) HIPCHK(h, slab(0, A, 0, Z, 0, A));
+    else {
+        const int ox = (s[0] + w[0]) & (A - 1), oy = (s[1] + w[1]) & (A - 1);      // where the columns / rows that stayed begin
+        HIPCHK(h, slab(0, A, 0, Z, s[0], w[0]));
+        HIPCHK(h, slab(s[1], w[1], 0, Z, ox, A - w[0]));
+        HIPCHK(h, slab(oy, A - w[1], s[2], w[2], ox, A - w[0]));
+    }
+    for (int k = 0; k < 3; ++k) h->va_E[k] = to[k];
+    return GVOM_OK;
+}
+
+// the frame of the walk kernels: gvom_raycast's (gvom_launch_raycast names the fields) with the extent in the window's place
+void walk_frame(const gvom_handle *h, ScanParams &P, RayQuery &Q)
+{
+    memset(&P, 0, sizeof P);
+    memset(&Q, 0, sizeof Q);
+    P.xy = h->va_A; P.zs = h->va_Z;
+    P.xy_res = h->prm.xy_resolution; P.z_res = h->prm.z_resolution;
+    P.drcp[0] = 1.0 / h->prm.xy_resolution; P.drcp[1] = 1.0 / h->prm.z_resolution;
+    P.fastdiv = h->tune_fastdiv == 0 ? 0 : h->fastdiv_ok;
+    P.f32_sqrt = h->f32_sqrt ? 1 : 0;
+    bool far = false;
+    for (int k = 0; k < 3; ++k) {
+        P.origin[k] = (double)h->va_E[k];
+        P.om[k] = (int)(h->va_E[k] & (side(h, k) - 1));
+        far = far || h->va_E[k] <= -((int64_t)1 << 24) || h->va_E[k] >= ((int64_t)1 << 24);
+    }
+    Q.lit = far ? 1 : 0;                                                    // (Z <= A: the integer extent test holds for every near origin)
+    Q.cap = (uint32_t)h->va_A + (uint32_t)h->va_Z;
+}
+
+// the sensor model's largest finite |direction| and |offset| per axis, read back once per gvom_sensor_model_set (which drains the stream
+// and leaves the model complete in device memory).  A pixel with a non-finite entry casts no beam: it bounds nothing.
+int model_bounds(gvom_handle *h)
+{
+    if (h->va_model_gen == h->ri_gen) return GVOM_OK;
+    const size_t n = (size_t)h->ri_H * h->ri_W;
+    std::vector<double> m(n * 6);
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipMemcpy(m.data(), h->ri_model.p, n * 48, hipMemcpyDeviceToHost));
+    for (int e = 0; e < 3; ++e) h->va_dmax[e] = h->va_omax[e] = 0.0;
+    const double *d = m.data(), *o = d + n * 3;
+    for (size_t i = 0; i < n; ++i) {
+        bool fin = true;
+        for (int e = 0; e < 3; ++e) fin = fin && std::isfinite(d[3 * i + e]) && std::isfinite(o[3 * i + e]);
+        for (int e = 0; fin && e < 3; ++e) {
+            h->va_dmax[e] = std::max(h->va_dmax[e], fabs(d[3 * i + e]));
+            h->va_omax[e] = std::max(h->va_omax[e], fabs(o[3 * i + e]));
+        }
+    }
+    h->va_model_gen = h->ri_gen;
+    return GVOM_OK;
+}
+
+// THE BOX OF A POSE: extent voxels {lx, ly, lz, dx, dy, dz} that hold every voxel a beam of the pose c (rows 0..2 of its matrix) can
+// examine.  A beam's end in the sensor frame is p = max_range * dir + off, |p[j]| <= M[j] = max_range * dmax[j] + omax[j]; in the world
+// q[e] = sum_j c[e][j] p[j] + t[e], so |q[e] - t[e]| <= sum_j |c[e][j]| M[j] = R[e] (no assumption on the matrix or on |dir|).  The walk
+// starts at (float)(t / res), advances along the segment towards (float)(q / res) and takes steps only while the length walked is below
+// the segment's length - 1 + one step (gvom.py:1127, 1150): less than one voxel beyond the end on any axis.  Its positions are float32
+// sums: at most cap additions, each rounded by half an ulp at the largest magnitude met, as are the two end points and the increments.
+// So with m = 3 + (cap + 4) * ulp32(largest |coordinate| in voxels) every examined voxel v[e] lies in
+// [floor((t[e] - R[e]) / res[e] - m), floor((t[e] + R[e]) / res[e] + m)], which is clipped to the extent.  Returns the box's voxels.
+int64_t pose_box(const gvom_handle *h, const double *c, double max_range, int32_t box[8])
+{
+    for (int e = 0; e < 8; ++e) box[e] = e >= 3 && e < 6 ? 1 : 0;
+    for (int e = 0; e < 12; ++e)
+        if (!std::isfinite(c[e])) return 1;                                  // an invalid pose casts no beam
+    const double cap = (double)h->va_A + h->va_Z + 1.0;
+    int64_t bits = 1;
+    for (int e = 0; e < 3; ++e) {
+        double R = 0.0;
+        for (int j = 0; j < 3; ++j) R += fabs(c[4 * e + j]) * (max_range * h->va_dmax[j] + h->va_omax[j]);
+        R = R * (1.0 + 1e-9) + 1e-300;                                       // (the sum's own rounding)
+        const double res = e < 2 ? h->prm.xy_resolution : h->prm.z_resolution, t = c[4 * e + 3];
+        const int size = side(h, e);
+        const double E = (double)h->va_E[e];
+        const double lo_w = (t - R) / res, hi_w = (t + R) / res;
+        const double mag = std::max(std::max(fabs(lo_w), fabs(hi_w)), fabs(E) + size);
+        const double m = 3.0 + (cap + 4.0) * mag * 0x1p-23;
+        const double lo = floor(lo_w - m) - E, hi = floor(hi_w + m) - E;       // extent voxels, as doubles (possibly huge, infinite or NaN)
+        int l = 0, u = size - 1;                                              // NaN: the whole side
+        if (lo > 0.0) l = lo < (double)size ? (int)lo : size;
+        if (hi < (double)(size - 1)) u = hi >= 0.0 ? (int)hi : -1;
+        if (u < l) { l = 0; u = 0; }                                          // the beams never meet the extent on this axis: any box does
+        box[e] = l; box[3 + e] = u - l + 1;
+        bits *= box[3 + e];
+    }
+    return bits;
+}
+}  // namespace
+
+extern "C" {
+VIS int gvom_voxel_atlas_configure(gvom_t *h, int32_t cells, int32_t levels, int mode, const int64_t fixed_origin[3])
+{
+    if (!h) return GVOM_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(h->mu);
+    const char *const fn = "gvom_voxel_atlas_configure";
+    if (h->sharded) return refuse(h, fn, "sharded handles are not supported");
+    if (cells != 0) {
+        if (cells < GVOM_VATLAS_MIN_CELLS || cells > GVOM_VATLAS_MAX_CELLS || (cells & (cells - 1))) return refuse(h, fn, "the side must be a power of two in 64 .. 4096");
+        if (cells < h->prm.xy_size) return refuse(h, fn, "the voxel atlas must be at least as wide as the window (xy_size)");
+        if (levels < 1 || levels > cells || (levels & (levels - 1))) return refuse(h, fn, "the levels must be a power of two, at most the side");
+        if (levels < h->prm.z_size) return refuse(h, fn, "the voxel atlas must be at least as high as the window (z_size)");
+        if ((int64_t)cells * cells * levels > ((int64_t)1 << 32)) return refuse(h, fn, "more than 2^32 voxels");
+        if (mode != GVOM_ATLAS_FOLLOW && mode != GVOM_ATLAS_FIXED) return refuse(h, fn, "unknown mode");
+        if (fixed_origin && !near_origin(fixed_origin)) return refuse(h, fn, "an origin at or beyond 2^30 voxels");
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    if (cells != h->va_A || (cells && levels != h->va_Z)) {                 // another size, or none: the kernels that use the old one first
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        if (h->va_mem) HIPCHK(h, hipFree(h->va_mem));
+        h->va_mem = nullptr; h->va_A = h->va_Z = 0;
+        if (cells == 0) return GVOM_OK;
+        HIPCHK(h, hipMalloc((void **)&h->va_mem, gvom_vatlas_bytes(cells, levels)));
+        ++h->va_allocs;
+    }
+    if (cells == 0) return GVOM_OK;
+    if (!h->va_cnt) { HIPCHK(h, hipMalloc((void **)&h->va_cnt, 256)); ++h->va_allocs; }
+    if (!h->va_pin) HIPCHK(h, hipHostMalloc((void **)&h->va_pin, 256, hipHostMallocDefault));
+    h->va_A = cells; h->va_Z = levels; h->va_follow = mode == GVOM_ATLAS_FOLLOW ? 1 : 0;
+    for (int k = 0; k < 3; ++k) { h->va_E[k] = fixed_origin ? fixed_origin[k] : 0; h->va_last[k] = 0; }
+    h->va_seq = h->va_outside = h->va_moved = 0;
+    HIPCHK(h, join_second_stream(h));
+    HIPCHK(h, hipMemsetAsync(h->va_cnt, 0, 256, h->stream));
+    HIPCHK(h, hipMemsetAsync(h->va_mem, 0, gvom_vatlas_bytes(cells, levels), h->stream));
+    return GVOM_OK;
+}
+
+VIS int gvom_voxel_atlas_clear(gvom_t *h)
+{
+    if (!h) return GVOM_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(h->mu);
+    const int rc = need_atlas(h, "gvom_voxel_atlas_clear");
+    if (rc) return rc;
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, join_second_stream(h));
+    HIPCHK(h, hipMemsetAsync(h->va_cnt, 0, 256, h->stream));
+    HIPCHK(h, hipMemsetAsync(h->va_mem, 0, gvom_vatlas_bytes(h->va_A, h->va_Z), h->stream));
+    h->va_outside = h->va_moved = 0;
+    return GVOM_OK;
+}
+
+// The CURRENT fused map merged into the atlas by k_vatlas_merge, behind the move of a following extent: on the handle's stream behind
+// whatever produced that map, as gvom_raycast reads it; later scans and combines are ordered behind the kernel.  Enqueues and returns.
+VIS int gvom_voxel_atlas_integrate(gvom_t *h)
+{
+    if (!h) return GVOM_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(h->mu);
+    const char *const fn = "gvom_voxel_atlas_integrate";
+    int rc = need_atlas(h, fn);
+    if (rc) return rc;
+    if (!h->has_combined) return GVOM_NO_DATA;
+    const Fused &F = h->fused[h->cur];
+    if (!near_origin(F.origin)) return refuse(h, fn, "the window's origin lies at or beyond 2^30 voxels");
+    int64_t to[3];
+    for (int k = 0; k < 3; ++k) to[k] = F.origin[k] + window_side(h, k) / 2 - side(h, k) / 2;
+    if (h->va_follow && !near_origin(to)) return refuse(h, fn, "the extent would lie at or beyond 2^30 voxels");
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, join_second_stream(h));
+    HIPCHK(h, hipMemsetAsync(h->va_cnt, 0, 64, h->stream));                 // the counters of the last integrate and its move
+    h->va_moved = 0;
+    if (h->va_follow && (rc = move_extent(h, to))) return rc;
+    const VAtlas V = atlas_of(h);
+    VAtlasWindow D;
+    memset(&D, 0, sizeof D);
+    int r[3], lo[3], n[3];
+    for (int k = 0; k < 3; ++k) {
+        r[k] = rel_of(h, F.origin, k);
+        clip(r[k], window_side(h, k), side(h, k), &lo[k], &n[k]);
+    }
+    const int64_t inside = (int64_t)n[0] * n[1] * n[2];
+    D.rx = r[0]; D.ry = r[1]; D.rz = r[2];
+    D.pex = (int)(h->va_E[0] & (V.A - 1)); D.pey = (int)(h->va_E[1] & (V.A - 1)); D.pez = (int)(h->va_E[2] & (V.Z - 1));
+    if (inside > 0) {
+        D.y0 = lo[1]; D.ny = n[1]; D.z0 = lo[2]; D.nz = n[2];
+        const int s0 = (r[0] + lo[0] + D.pex) & (V.A - 1);                  // storage column of the first window column inside the extent
+        D.bx = s0 >> 6;
+        D.npx = std::min(V.A / 64, ((s0 & 63) + n[0] + 63) / 64);
+        const int64_t pairs = (int64_t)D.ny * D.nz * D.npx;
+        if (pairs >= ((int64_t)1 << 31)) return refuse(h, fn, "the window is too large for one merge", GVOM_ERR_CAPACITY);
+        D.npairs = (uint32_t)pairs;
+    }
+    OccParams P;
+    occ_params(h, F, P);
+    ++h->va_seq;
+    for (int k = 0; k < 3; ++k) h->va_last[k] = F.origin[k];
+    h->va_outside = (int64_t)h->prm.xy_size * h->prm.xy_size * h->prm.z_size - inside;
+    HIPCHK(h, gvom_launch_vatlas_merge(h->stream, V, D, P, F.state, F.tags, h->va_cnt));
+    return GVOM_OK;
+}
+
+VIS int gvom_voxel_atlas_counts(gvom_t *h, int64_t out[11])
+{
+    if (!h || !out) return GVOM_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(h->mu);
+    const int rc = need_atlas(h, "gvom_voxel_atlas_counts");
+    if (rc) return rc;
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipMemcpyAsync(h->va_pin, h->va_cnt, 128, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    for (int k = 0; k < 5; ++k) out[k] = (int64_t)h->va_pin[k];
+    out[5] = h->va_outside; out[6] = h->va_moved;
+    out[7] = (int64_t)h->va_pin[VA_CNT_MOVED_OBS]; out[8] = (int64_t)h->va_pin[VA_CNT_OBSERVED]; out[9] = (int64_t)h->va_pin[VA_CNT_OCCUPIED];
+    out[10] = h->va_seq;
+    return GVOM_OK;
+}
+
+// A window-sized box of the atlas as the class grid out[x][y][z] (k_vatlas_box), a product of kind GVOM_PRODUCT_VOXEL_BOX.  Enqueues and returns.
+VIS int gvom_voxel_atlas_box(gvom_t *h, const int64_t origin[3], int64_t *product_id, int64_t origin_out[3])
+{
+    if (!h || !product_id) return GVOM_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(h->mu);
+    *product_id = -1;
+    const char *const fn = "gvom_voxel_atlas_box";
+    int rc = need_atlas(h, fn);
+    if (rc) return rc;
+    if (!h->has_combined || (!origin && h->va_seq == 0)) return GVOM_NO_DATA;     // (NULL: the last integrated window, and there is none yet)
+    const int64_t B[3] = {origin ? origin[0] : h->va_last[0], origin ? origin[1] : h->va_last[1], origin ? origin[2] : h->va_last[2]};
+    const int xy = h->prm.xy_size, zs = h->prm.z_size;
+    HIPCHK(h, hipSetDevice(h->device));
+    DevSet *set = nullptr;
+    const size_t bytes = set_bytes(GVOM_PRODUCT_VOXEL_BOX, xy, zs, 0);
+    if ((rc = product_acquire(h, GVOM_PRODUCT_VOXEL_BOX, bytes, bytes, fn, &h->va_allocs, &set))) return rc;
+    HIPCHK(h, join_second_stream(h));
+    if ((rc = set_wait_releases(h, set))) return rc;
+    VAtlasBox X;
+    memset(&X, 0, sizeof X);
+    X.n = xy; X.zs = zs;
+    int r[3], lo[3], n[3];
+    for (int k = 0; k < 3; ++k) {
+        r[k] = rel_of(h, B, k);
+        clip(r[k], window_side(h, k), side(h, k), &lo[k], &n[k]);
+    }
+    X.rx = r[0]; X.ry = r[1]; X.rz = r[2];
+    X.px = (int)(B[0] & (h->va_A - 1)); X.py = (int)(B[1] & (h->va_A - 1)); X.pz = (int)(B[2] & (h->va_Z - 1));
+    X.outside = (int)((int64_t)xy * xy * zs - (int64_t)n[0] * n[1] * n[2]);
+    X.seq = (int)std::min<int64_t>(h->va_seq, INT32_MAX);
+    int32_t *counts = part_ptr<int32_t>(set, 1);
+    HIPCHK(h, hipMemsetAsync(counts, 0, 16, h->stream));
+    HIPCHK(h, gvom_launch_vatlas_box(h->stream, atlas_of(h), X, part_ptr<uint8_t>(set, 0), counts));
+    for (int k = 0; k < 3; ++k) set->origin[k] = B[k];
+    for (int k = 0; origin_out && k < 3; ++k) origin_out[k] = B[k];
+    return product_publish(h, set, product_id);
+}
+
+// gvom_raycast on the atlas: n segments walked by k_vatlas_raycast, read-only, behind the integrates before the call; the result is a
+// product of kind GVOM_PRODUCT_VOXEL_ATLAS_RAYS sized by n.  Enqueues and returns (the host route waits for its upload).
+VIS int gvom_voxel_atlas_raycast(gvom_t *h, const float *from, int64_t K, const float *to, int64_t n, int on_device, int flags,
+                                 int64_t extent_voxels[3], int64_t *product_id)
+{
+    if (!h || !product_id) return GVOM_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(h->mu);
+    *product_id = -1;
+    const char *const fn = "gvom_voxel_atlas_raycast";
+    int rc = need_atlas(h, fn);
+    if (rc) return rc;
+    if (!from || !to) return refuse(h, fn, "from and to must not be NULL");
+    if (n < 1) return refuse(h, fn, "n must be at least 1");
+    if (K != 1 && K != n) return refuse(h, fn, "K must be 1 or n");
+    if (flags & ~(GVOM_RAY_UNKNOWN_BLOCKS | GVOM_RAY_CHECK_TARGET)) return refuse(h, fn, "unknown flag bits");
+    if (n > GVOM_RAYCAST_MAX_RAYS) return refuse(h, fn, "more than 2^26 rays in one call", GVOM_ERR_CAPACITY);
+    if (!h->has_combined) return GVOM_NO_DATA;
+    HIPCHK(h, hipSetDevice(h->device));
+    DevSet *set = nullptr;
+    const size_t bytes = set_bytes(GVOM_PRODUCT_VOXEL_ATLAS_RAYS, 0, 0, n);
+    if ((rc = product_acquire(h, GVOM_PRODUCT_VOXEL_ATLAS_RAYS, bytes, bytes, fn, &h->va_allocs, &set))) return rc;
+    set->cap = n;
+    ScanParams P;
+    RayQuery Q;
+    walk_frame(h, P, Q);
+    Q.from = from; Q.to = to; Q.n = (long)n;
+    Q.one_origin = K == 1 ? 1 : 0;
+    Q.unknown_blocks = (flags & GVOM_RAY_UNKNOWN_BLOCKS) ? 1 : 0;
+    Q.check_target = (flags & GVOM_RAY_CHECK_TARGET) ? 1 : 0;
+    HIPCHK(h, join_second_stream(h));
+    if (!on_device) {                                                       // host segments: staged, and up before the call returns
+        const HostPart parts[2] = {{from, (size_t)K * 12}, {to, (size_t)n * 12}};
+        const void *dev[2];
+        if ((rc = stage_host(h, h->va_stage, h->va_allocs, parts, 2, true, dev))) return rc;
+        Q.from = (const float *)dev[0]; Q.to = (const float *)dev[1];
+    }
+    if ((rc = set_wait_releases(h, set))) return rc;
+    HIPCHK(h, gvom_launch_vatlas_raycast(h->stream, P, Q, atlas_of(h), part_ptr<int32_t>(set, 0), part_ptr<float>(set, 1), part_ptr<int32_t>(set, 2)));
+    for (int k = 0; k < 3; ++k) set->origin[k] = h->va_E[k];
+    if ((rc = product_publish(h, set, product_id))) return rc;
+    for (int k = 0; extent_voxels && k < 3; ++k) extent_voxels[k] = h->va_E[k];
+    return GVOM_OK;
+}
+
+// gvom_score_viewpoints on the atlas: the selected beams of the handle's sensor model cast from K poses by k_vatlas_viewpoints, a batch of
+// poses at a time -- as many as have their bitmaps in "viewpoint_bitmap_mb" megabytes, every bitmap as large as the largest box of the
+// call --, the bitmaps cleared on the stream in front of every batch; then k_vatlas_viewpoint_best.  The boxes are proved on the host
+// (pose_box): the poses of the device route are read back first.
+VIS int gvom_voxel_atlas_score_viewpoints(gvom_t *h, const double *poses, int64_t K, int on_device, double max_range, int32_t stride_h,
+                                          int32_t stride_w, int flags, int64_t extent_voxels[3], int64_t *product_id)
+{
+    if (!h || !product_id) return GVOM_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(h->mu);
+    *product_id = -1;
+    const char *const fn = "gvom_voxel_atlas_score_viewpoints";
+    int rc = need_atlas(h, fn);
+    if (rc) return rc;
+    if (!poses) return refuse(h, fn, "poses must not be NULL");
+    if (h->ri_H <= 0) return refuse(h, fn, "no sensor model (gvom_sensor_model_set)");
+    if (K < 1) return refuse(h, fn, "K must be at least 1");
+    if (stride_h < 1 || stride_w < 1) return refuse(h, fn, "the beam strides must be at least 1");
+    if (!std::isfinite(max_range) || !(max_range > 0.0)) return refuse(h, fn, "max_range must be finite and > 0");
+    if (flags & ~GVOM_RAY_UNKNOWN_BLOCKS) return refuse(h, fn, "unknown flag bits");
+    if (K > GVOM_VIEWPOINT_MAX_POSES) return refuse(h, fn, "more than 65536 viewpoints in one call", GVOM_ERR_CAPACITY);
+    const int A = h->va_A, Z = h->va_Z;
+    const int64_t nh = ((int64_t)h->ri_H + stride_h - 1) / stride_h, nw = ((int64_t)h->ri_W + stride_w - 1) / stride_w, nb = nh * nw;
+    if (nb > GVOM_VIEWPOINT_MAX_BEAMS) return refuse(h, fn, "more than 2^22 selected beams", GVOM_ERR_CAPACITY);
+    if (nb * ((int64_t)A + Z + 1) >= ((int64_t)1 << 31)) return refuse(h, fn, "beams x (cells + levels + 1) reaches 2^31", GVOM_ERR_CAPACITY);
+    if (!h->has_combined) return GVOM_NO_DATA;
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, join_second_stream(h));
+    if ((rc = model_bounds(h))) return rc;
+    std::vector<double> back;
+    const double *hp = poses;
+    if (on_device) {                                                        // the boxes need the poses: read back behind whatever wrote them
+        back.resize((size_t)K * 12);
+        HIPCHK(h, hipMemcpyAsync(back.data(), poses, (size_t)K * 96, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        hp = back.data();
+    }
+    std::vector<int32_t> boxes((size_t)K * 8);
+    int64_t most = 1;
+    for (int64_t k = 0; k < K; ++k) {
+        const int64_t bits = pose_box(h, hp + k * 12, max_range, boxes.data() + k * 8);
+        if (bits >= ((int64_t)1 << 31)) return refuse(h, fn, "the box of a pose holds 2^31 voxels or more (a shorter max_range, or a smaller atlas)", GVOM_ERR_CAPACITY);
+        most = std::max(most, bits);
+    }
+    DevSet *set = nullptr;
+    const size_t bytes = set_bytes(GVOM_PRODUCT_VOXEL_ATLAS_VIEWPOINTS, 0, 0, K);
+    if ((rc = product_acquire(h, GVOM_PRODUCT_VOXEL_ATLAS_VIEWPOINTS, bytes, bytes, fn, &h->va_allocs, &set))) return rc;
+    set->cap = K;
+    const size_t bm_words = (((size_t)most + 31) / 32 + 63) & ~(size_t)63, bm_bytes = bm_words * 4;       // whole 256-byte lines
+    int64_t batch = (int64_t)(((size_t)h->tune_vp_mb << 20) / bm_bytes);
+    batch = std::max<int64_t>(1, std::min<int64_t>(batch, std::min<int64_t>(K, GVOM_VIEWPOINT_MAX_BATCH)));
+    if ((rc = stage_buf(h, h->va_bitmaps, (size_t)batch * bm_bytes, h->va_allocs))) return rc;
+    ScanParams P;
+    RayQuery R;
+    walk_frame(h, P, R);
+    ViewQuery Q;
+    memset(&Q, 0, sizeof Q);
+    Q.dir = (const double *)h->ri_model.p; Q.off = Q.dir + (size_t)h->ri_H * h->ri_W * 3;
+    Q.max_range = max_range;
+    Q.W = h->ri_W; Q.stride_h = stride_h; Q.stride_w = stride_w;
+    Q.nh = (int)nh; Q.nw = (int)nw; Q.nwc = (int)((nw + 63) / 64); Q.nb = (int)nb; Q.K = (int)K;
+    Q.unknown_blocks = (flags & GVOM_RAY_UNKNOWN_BLOCKS) ? 1 : 0;
+    Q.lit = R.lit; Q.cap = R.cap; Q.bm_words = (uint32_t)bm_words;
+    const HostPart parts[2] = {{on_device ? nullptr : poses, (size_t)K * 96}, {boxes.data(), (size_t)K * 32}};
+    const void *dev[2];
+    if ((rc = stage_host(h, h->va_stage, h->va_allocs, parts, 2, true, dev))) return rc;
+    Q.poses = on_device ? poses : (const double *)dev[0];
+    const int32_t *dboxes = (const int32_t *)dev[1];
+    if ((rc = set_wait_releases(h, set))) return rc;
+    const VAtlas V = atlas_of(h);
+    int32_t *rows = part_ptr<int32_t>(set, 0);
+    HIPCHK(h, hipMemsetAsync(rows, 0, (size_t)K * 32, h->stream));
+    for (int64_t k0 = 0; k0 < K; k0 += batch) {
+        const int nk = (int)std::min<int64_t>(batch, K - k0);
+        Q.k0 = (int)k0;
+        HIPCHK(h, hipMemsetAsync(h->va_bitmaps.p, 0, (size_t)nk * bm_bytes, h->stream));
+        HIPCHK(h, gvom_launch_vatlas_viewpoints(h->stream, P, Q, V, nk, dboxes, (uint32_t *)h->va_bitmaps.p, rows));
+    }
+    Q.k0 = 0;
+    HIPCHK(h, gvom_launch_vatlas_viewpoint_best(h->stream, P, Q, V, rows, part_ptr<int32_t>(set, 1)));
+    h->va_last_batch = (int)batch;
+    for (int k = 0; k < 3; ++k) set->origin[k] = h->va_E[k];
+    if ((rc = product_publish(h, set, product_id))) return rc;
+    for (int k = 0; extent_voxels && k < 3; ++k) extent_voxels[k] = h->va_E[k];
+    return GVOM_OK;
+}
+}  // extern "C"

@@ -185,6 +185,14 @@ ABI = [
                                    ctypes.POINTER(_I64), ctypes.POINTER(_I64)]),
     ("gvom_atlas_field_window", _I, [_P, _I64, _I64, ctypes.POINTER(_I64), ctypes.POINTER(_I64)]),
     ("gvom_atlas_frontiers", _I, [_P, _I64, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(_I64), ctypes.POINTER(_I64), ctypes.POINTER(_I64)]),
+    ("gvom_voxel_atlas_configure", _I, [_P, ctypes.c_int32, ctypes.c_int32, _I, ctypes.POINTER(_I64)]),
+    ("gvom_voxel_atlas_integrate", _I, [_P]),
+    ("gvom_voxel_atlas_clear", _I, [_P]),
+    ("gvom_voxel_atlas_counts", _I, [_P, ctypes.POINTER(_I64)]),
+    ("gvom_voxel_atlas_box", _I, [_P, ctypes.POINTER(_I64), ctypes.POINTER(_I64), ctypes.POINTER(_I64)]),
+    ("gvom_voxel_atlas_raycast", _I, [_P, _P, _I64, _P, _I64, _I, _I, ctypes.POINTER(_I64), ctypes.POINTER(_I64)]),
+    ("gvom_voxel_atlas_score_viewpoints", _I, [_P, _P, _I64, _I, ctypes.c_double, ctypes.c_int32, ctypes.c_int32, _I, ctypes.POINTER(_I64),
+                                               ctypes.POINTER(_I64)]),
     ("gvom_set_profiling", _I, [_P, _I]),
     ("gvom_host_timing", _I, [_P, ctypes.POINTER(ctypes.c_double * 8)]),
     ("gvom_set_tuning", _I, [_P, ctypes.c_char_p, _I]),
@@ -613,6 +621,9 @@ PRODUCT_ATLAS_FIELD = 26                  # GVOM_PRODUCT_ATLAS_FIELD: made by gv
 PRODUCT_ATLAS_FRONTIERS = 28              # GVOM_PRODUCT_ATLAS_FRONTIERS: made by gvom_atlas_frontiers (kind 27 is not assigned)
 _ATTITUDE_BLOCKS = (1, 2, 3)              # (ATTITUDE_PITCH, ATTITUDE_ROLL, ATTITUDE_BELLY): the statuses a pose field blocks by default
 PRODUCT_ATTITUDE_VOLUME = 30              # GVOM_PRODUCT_ATTITUDE_VOLUME: made by gvom_attitude_volume (kind 29 is not assigned)
+PRODUCT_VOXEL_BOX = 32                    # GVOM_PRODUCT_VOXEL_BOX: made by gvom_voxel_atlas_box (kind 31 is not assigned)
+PRODUCT_VOXEL_ATLAS_RAYS = 34             # GVOM_PRODUCT_VOXEL_ATLAS_RAYS: made by gvom_voxel_atlas_raycast (kind 33 is not assigned)
+PRODUCT_VOXEL_ATLAS_VIEWPOINTS = 36       # GVOM_PRODUCT_VOXEL_ATLAS_VIEWPOINTS: made by gvom_voxel_atlas_score_viewpoints (kind 35 is not assigned)
 # element type of part k of a product, by kind (what set_part() of csrc/gvom_setlayout.h gives as DLPack code and bits)
 _PRODUCT_DTYPES = {PRODUCT_OCCUPANCY: (np.uint8,), PRODUCT_VOXEL_CLOUD: (np.float32, np.float32, np.int64),
                    PRODUCT_HEIGHT_CLOUD: (np.float32,), PRODUCT_INFERRED_HEIGHT_CLOUD: (np.float32,),
@@ -624,7 +635,9 @@ _PRODUCT_DTYPES = {PRODUCT_OCCUPANCY: (np.uint8,), PRODUCT_VOXEL_CLOUD: (np.floa
                    PRODUCT_ATLAS_EXTENT: (np.int32, np.int32, np.int32, np.float64, np.float64, np.int32),
                    PRODUCT_ATLAS_FIELD: (np.int32, np.uint8, np.uint16),
                    PRODUCT_ATLAS_FRONTIERS: (np.int32, np.int64, np.int32, np.int32),
-                   PRODUCT_ATTITUDE_VOLUME: (np.uint8, np.uint8, np.int32)}
+                   PRODUCT_ATTITUDE_VOLUME: (np.uint8, np.uint8, np.int32),
+                   PRODUCT_VOXEL_BOX: (np.uint8, np.int32), PRODUCT_VOXEL_ATLAS_RAYS: (np.int32, np.float32, np.int32),
+                   PRODUCT_VOXEL_ATLAS_VIEWPOINTS: (np.int32, np.int32)}
 CLEARANCE_FAR = 2147483647                # GVOM_CLEARANCE_FAR: squared_cells where no obstacle is in reach
 _CLEARANCE_NO_NEGATIVE = 1                # GVOM_CLEARANCE_NO_NEGATIVE
 
@@ -2083,6 +2096,208 @@ class Atlas(object):
             g._check_args(g._lib.gvom_atlas_configure(g._h, 0, 0, None))
 
 
+# ---- voxel atlas (Gvom.create_voxel_atlas; include/gvom_hip.h "voxel atlas") ----------------------------------------------
+VOXEL_NEVER, VOXEL_FREE, VOXEL_OCCUPIED = 0, 1, 2       # GVOM_VOXEL_*: the class codes of a DeviceVoxelBox
+VOXEL_ATLAS_COUNTS = ("first_seen", "free_to_occupied", "occupied_to_free", "confirmed", "uninformative", "outside", "cleared",
+                      "cleared_observed", "observed", "occupied", "seq")
+
+
+def _voxel_atlas_sizes(cells, levels, xy_size, z_size):
+    c = _atlas_cells(cells, xy_size)
+    z = int(levels)
+    if z != levels or z < 1 or z > c or z & (z - 1):
+        raise ValueError("levels must be a power of two, at most cells (%d), got %r" % (c, levels))
+    if z < z_size:
+        raise ValueError("levels must be at least z_size (%d), got %d" % (z_size, z))
+    if c * c * z > 1 << 32:
+        raise ValueError("cells * cells * levels must not exceed 2**32, got %d" % (c * c * z))
+    return c, z
+
+
+def _voxel_origin(origin_voxels, what="origin_voxels", limit=None):
+    o = np.asarray(origin_voxels)
+    if o.shape != (3,) or o.dtype.kind not in "iu":
+        raise ValueError("%s must be three integers (x, y, z) in world voxels, got %r" % (what, origin_voxels))
+    if limit is not None and (np.abs(o.astype(np.int64)) >= limit).any():
+        raise ValueError("%s lies at or beyond 2^30 voxels" % what)
+    return (_I64 * 3)(int(o[0]), int(o[1]), int(o[2]))
+
+
+class DeviceVoxelBox(_ProductView):
+    """The result of VoxelAtlas.box(): `.classes` uint8 [xy, xy, z] in the occupancy grid's layout -- VOXEL_NEVER, VOXEL_FREE or
+    VOXEL_OCCUPIED per voxel, VOXEL_NEVER outside the extent -- and `.counts` int32 [4] {occupied, free, voxels outside the extent,
+    seq}: two DeviceArrays of one product.  `.origin_voxels`: the box's corner in world voxels.  `classes == VOXEL_OCCUPIED` is an
+    occupancy grid of remembered space.  A snapshot.  DLPack hands over the class grid.  copy_to_host() returns (classes, counts)."""
+
+    def __init__(self, hold, origin_voxels):
+        _ProductView.__init__(self, hold)
+        self.origin_voxels = origin_voxels
+        self.classes, self.counts = DeviceArray(hold, 0), DeviceArray(hold, 1)
+
+    def copy_to_host(self):
+        return self.classes.copy_to_host(), self.counts.copy_to_host()
+
+    def __dlpack_device__(self):
+        return self.classes.__dlpack_device__()
+
+    def __dlpack__(self, stream=None, max_version=None, dl_device=None, copy=None):
+        return self.classes.__dlpack__(stream=stream, max_version=max_version, dl_device=dl_device, copy=copy)
+
+
+class DeviceAtlasRays(_ProductView):
+    """The result of VoxelAtlas.raycast() / raycast_device(): `.result` int32 [n, 3] -- per ray {status (RAY_*; RAY_LEFT_WINDOW: it left
+    the extent), steps, unknown voxels passed} --, `.position` float32 [n, 3], where the ray stopped in world metres (NaN where it did
+    not stop at a voxel), and `.voxel` int32 [n, 3], the WORLD voxel of the stop ((0, 0, 0) where there is none): three DeviceArrays of
+    one product, row i = ray i.  `.extent_origin`: the extent's corner in world voxels when the call was made.  A snapshot.
+    copy_to_host() returns (result, position, voxel) as numpy."""
+
+    def __init__(self, hold, extent_origin):
+        _ProductView.__init__(self, hold)
+        self.extent_origin = extent_origin
+        self.result, self.position, self.voxel = DeviceArray(hold, 0), DeviceArray(hold, 1), DeviceArray(hold, 2)
+
+    def copy_to_host(self):
+        return self.result.copy_to_host(), self.position.copy_to_host(), self.voxel.copy_to_host()
+
+
+class DeviceAtlasViewpoints(DeviceViewpoints):
+    """The result of VoxelAtlas.score_viewpoints() / score_viewpoints_device(): a DeviceViewpoints whose beams were cast through the
+    voxel atlas -- RAY_LEFT_WINDOW means "left the extent", the gain counts distinct never-observed WORLD voxels -- with best_pose().
+    `.origin` and `.extent_origin`: the extent's corner in world voxels when the call was made."""
+
+    def __init__(self, hold, extent_origin, poses=None):
+        DeviceViewpoints.__init__(self, hold, np.array(extent_origin, np.float64), poses)
+        self.extent_origin = extent_origin
+
+
+class VoxelAtlas(object):
+    """The voxel atlas of a mapper (Gvom.create_voxel_atlas): a world-fixed, toroidally stored memory of the voxels' classes --
+    never observed, observed free, occupied -- `cells` x `cells` x `levels` voxels at 2 bits each, that keeps what the rolling window
+    forgets.  integrate() merges the current fused map into it on the GPU (what the window has observed wins; what it has not stays as
+    it was known), raycast() and score_viewpoints() are Gvom.raycast() and Gvom.score_viewpoints() on the whole extent, box() returns any
+    window-sized part as a class grid.  Only counts() waits for the GPU (score_viewpoints_device() reads its poses back).
+    include/gvom_hip.h "voxel atlas" has the definition."""
+
+    def __init__(self, owner, cells, levels, follow, origin_voxels):
+        self._owner = owner
+        self.cells, self.levels = _voxel_atlas_sizes(cells, levels, owner.xy_size, owner.z_size)
+        self.follow = bool(follow)
+        if not self.follow and origin_voxels is None:
+            raise ValueError("a fixed voxel atlas needs origin_voxels, the corner of its extent")
+        org = None if origin_voxels is None else _voxel_origin(origin_voxels, limit=1 << 30)
+        owner._check_args(owner._lib.gvom_voxel_atlas_configure(owner._h, self.cells, self.levels, ATLAS_FOLLOW if self.follow else ATLAS_FIXED, org))
+        self.extent_origin = (0, 0, 0) if org is None else tuple(int(v) for v in org)
+        self.seq = 0
+
+    def integrate(self):
+        """Merges the CURRENT fused map (the map of the most recently begun combine) into the atlas; no host wait.  False before the
+        first combine (nothing was merged), else True."""
+        g = self._owner
+        if g._check_args(g._lib.gvom_voxel_atlas_integrate(g._h)) == GVOM_NO_DATA:
+            return False
+        self.seq += 1
+        if self.follow:
+            W = tuple(int(v) for v in g._state().combined_origin)
+            sizes, sides = (g.xy_size, g.xy_size, g.z_size), (self.cells, self.cells, self.levels)
+            self.extent_origin = tuple(w + n // 2 - s // 2 for w, n, s in zip(W, sizes, sides))
+        return True
+
+    def box(self, origin_voxels=None, center=None):
+        """A window-sized part of the atlas as a DeviceVoxelBox whose corner is origin_voxels (integer world voxels), or the window a
+        scan with its ego at `center` (x, y, z in world metres) would have: floor(c / resolution - size / 2) per axis, the scan's own
+        arithmetic.  Default: the last integrated window (None before the first integrate).  Voxels outside the extent read VOXEL_NEVER.  None before
+        the first combine.
+        No host wait."""
+        g = self._owner
+        if origin_voxels is not None and center is not None:
+            raise ValueError("give origin_voxels or center, not both")
+        if center is not None:
+            c = np.asarray(center, dtype=np.float64)
+            if c.shape != (3,) or not np.isfinite(c).all():
+                raise ValueError("center must be three finite numbers (x, y, z) in metres, got %r" % (center,))
+            res, size = (g.xy_resolution, g.xy_resolution, g.z_resolution), (g.xy_size, g.xy_size, g.z_size)
+            origin_voxels = [int(math.floor(v / r - n / 2.0)) for v, r, n in zip(c, res, size)]
+        org = None if origin_voxels is None else _voxel_origin(origin_voxels)
+        out = (_I64 * 3)()
+        hold = g._make_product(lambda pid: g._lib.gvom_voxel_atlas_box(g._h, org, pid, out), PRODUCT_VOXEL_BOX, g._check_args)
+        return None if hold is None else DeviceVoxelBox(hold, tuple(int(v) for v in out))
+
+    def _raycast(self, from_ptr, K, to_ptr, n, on_device, unknown_blocks, check_target):
+        g = self._owner
+        e = (_I64 * 3)()
+        flags = (_RAY_UNKNOWN_BLOCKS if unknown_blocks else 0) | (_RAY_CHECK_TARGET if check_target else 0)
+        hold = g._make_product(lambda pid: g._lib.gvom_voxel_atlas_raycast(g._h, from_ptr, int(K), to_ptr, int(n), int(on_device), flags, e, pid),
+                               PRODUCT_VOXEL_ATLAS_RAYS, g._check_args)
+        return None if hold is None else DeviceAtlasRays(hold, tuple(int(v) for v in e))
+
+    def raycast(self, origins, targets, unknown_blocks=False, check_target=False):
+        """Gvom.raycast() through the atlas: the same segments, flags and ray rule, with the extent in the window's place -- a ray
+        stops at the first remembered occupied voxel, never-observed voxels count as unknown, RAY_LEFT_WINDOW means it left the
+        extent.  Returns a DeviceAtlasRays; None before the first combine."""
+        t = np.ascontiguousarray(np.asarray(targets), dtype=np.float32)
+        if t.ndim != 2 or t.shape[1] != 3 or t.shape[0] < 1:
+            raise ValueError("targets must have shape (n, 3) with n >= 1, got %r" % (t.shape,))
+        n = t.shape[0]
+        if n > RAYCAST_MAX_RAYS:
+            raise ValueError("at most 2**26 rays per call, got %d" % n)
+        o = np.ascontiguousarray(np.asarray(origins), dtype=np.float32)
+        if o.shape == (3,):
+            o = o.reshape(1, 3)
+        if o.shape not in ((1, 3), (n, 3)):
+            raise ValueError("origins must have shape (3,), (1, 3) or (%d, 3), got %r" % (n, o.shape))
+        return self._raycast(_ptr(o), o.shape[0], _ptr(t), n, 0, unknown_blocks, check_target)
+
+    def raycast_device(self, from_ptr, K, to_ptr, n, unknown_blocks=False, check_target=False):
+        """The same for segments in device memory, as Gvom.raycast_device().  Enqueues and returns: no host wait."""
+        if not from_ptr or not to_ptr:
+            raise ValueError("from_ptr and to_ptr must be device addresses")
+        return self._raycast(_dev(from_ptr), K, _dev(to_ptr), n, 1, unknown_blocks, check_target)
+
+    def _score_viewpoints(self, poses_ptr, K, on_device, max_range, beam_stride, unknown_blocks, host_poses=None):
+        g = self._owner
+        K, r, sh, sw = _viewpoint_options(K, max_range, beam_stride)
+        e = (_I64 * 3)()
+        flags = _RAY_UNKNOWN_BLOCKS if unknown_blocks else 0
+        hold = g._make_product(lambda pid: g._lib.gvom_voxel_atlas_score_viewpoints(g._h, poses_ptr, K, int(on_device), r, sh, sw, flags, e, pid),
+                               PRODUCT_VOXEL_ATLAS_VIEWPOINTS, g._check_args)
+        return None if hold is None else DeviceAtlasViewpoints(hold, tuple(int(v) for v in e), host_poses)
+
+    def score_viewpoints(self, poses, max_range, beam_stride=(1, 1), unknown_blocks=False):
+        """Gvom.score_viewpoints() through the atlas: the same poses, sensor model, strides and flag; the gain of a pose is the number
+        of DISTINCT never-observed world voxels its beams pass anywhere in the extent -- the last step of the exploration loop
+        atlas field -> frontiers -> viewpoint_poses() -> score_viewpoints() -> best_pose() for goals outside the window.  Returns a
+        DeviceAtlasViewpoints; None before the first combine."""
+        t = _viewpoint_poses(poses)
+        return self._score_viewpoints(_ptr(t), t.shape[0], 0, max_range, beam_stride, unknown_blocks, t)
+
+    def score_viewpoints_device(self, poses_ptr, K, max_range, beam_stride=(1, 1), unknown_blocks=False):
+        """The same for poses in device memory, as Gvom.score_viewpoints_device().  The library reads the poses back (K x 96 bytes):
+        this route waits for the mapper's stream."""
+        if not poses_ptr:
+            raise ValueError("poses_ptr must be a device address")
+        return self._score_viewpoints(_dev(poses_ptr), K, 1, max_range, beam_stride, unknown_blocks)
+
+    def clear(self):
+        """Every voxel becomes VOXEL_NEVER and the counters 0; the extent and seq stay."""
+        g = self._owner
+        g._check_args(g._lib.gvom_voxel_atlas_clear(g._h))
+
+    def counts(self):
+        """Waits for the GPU.  A dict (VOXEL_ATLAS_COUNTS): of the last integrate `first_seen`, `free_to_occupied`, `occupied_to_free`,
+        `confirmed`, `uninformative`, `outside` (they sum to the window's voxels), `cleared` and `cleared_observed` (by the move); of the
+        atlas `observed`, `occupied` and `seq`."""
+        g = self._owner
+        out = (_I64 * 11)()
+        g._check_args(g._lib.gvom_voxel_atlas_counts(g._h, out))
+        return dict(zip(VOXEL_ATLAS_COUNTS, (int(v) for v in out)))
+
+    def release(self):
+        """Frees the atlas's device memory."""
+        g = self._owner
+        if g._h:
+            g._check_args(g._lib.gvom_voxel_atlas_configure(g._h, 0, 0, 0, None))
+
+
 class _OutputPool(object):
     """Free pinned output buffers of one Gvom.  Outlives the Gvom if returned arrays do: a buffer that
     comes back after the mapper is gone is released at once (pinned host memory is not tied to the
@@ -2945,6 +3160,14 @@ class Gvom(object):
         re-centres on every integrated set and forgets what leaves it; follow=False: it stays at origin_cells (its corner, integer
         world cells) and sets outside it are skipped.  See Atlas."""
         return Atlas(self, cells, follow, origin_cells)
+
+    # ---- voxel atlas (an extension; include/gvom_hip.h "voxel atlas") ----
+    def create_voxel_atlas(self, cells, levels, follow=True, origin_voxels=None):
+        """Configures the mapper's voxel atlas -- one per mapper; a second call replaces the first -- and returns it: `cells` x `cells`
+        x `levels` world voxels at 2 bits each (cells a power of two in 64 .. 4096, at least xy_size; levels a power of two from z_size
+        to cells; at most 2**32 voxels, 1 GiB).  follow=True: the extent re-centres on every integrated window, as the map atlas's does,
+        and forgets what leaves it; follow=False: it stays at origin_voxels (its corner, integer world voxels).  See VoxelAtlas."""
+        return VoxelAtlas(self, cells, levels, follow, origin_voxels)
 
     # ---- scan alignment scoring (an extension; include/gvom_hip.h "scan alignment scoring") ----
     def _score_alignments(self, cloud_ptr, n, tf_ptr, K, on_device, dilate, weights):

@@ -1015,8 +1015,8 @@ int gvom_pose_field_attitude(gvom_t *h, int64_t costfield_id, const int32_t *cos
  * GVOM_ERR_INVALID: a sharded handle; no atlas configured; cells not a power of two, outside 64 .. 4096 or below xy_size; an unknown
  * mode; id and pointers mixed, or neither; a NULL map; a stale id; an origin beyond 2^40 cells; NULL outputs.  GVOM_ERR_CAPACITY: a
  * recall with all 8 map sets exported; every product set of the kind exported.
- * NOT PROVIDED: a coarser level or pyramid; a "latest wins" policy; time decay; 3-D memory; more than one atlas per handle; sharded
- * handles; saving to disk; DLPack views of the toroidal planes themselves. */
+ * NOT PROVIDED: a coarser level or pyramid; a "latest wins" policy; time decay; more than one atlas per handle; sharded
+ * handles; saving to disk; DLPack views of the toroidal planes themselves.  3-D memory is the voxel atlas's ("voxel atlas" below). */
 #define GVOM_PRODUCT_ATLAS_RECALL 22   /* part 0 int32 [xy, xy] stamps; part 1 int32 [4] {rank 2, rank 1, outside, seq} */
 #define GVOM_PRODUCT_ATLAS_EXTENT 24   /* parts 0 .. 2 int32 positive, negative, visibility; 3, 4 f64 roughness, height; 5 int32 stamp: [A, A], strides (1, A) */
 #define GVOM_ATLAS_FOLLOW 0
@@ -1119,6 +1119,87 @@ int gvom_atlas_field_window(gvom_t *h, int64_t field_id, int64_t map_set_id, con
 #define GVOM_PRODUCT_ATLAS_FRONTIERS 28   /* the four parts of kind 16 at side A; kind 27 stays unassigned */
 int gvom_atlas_frontiers(gvom_t *h, int64_t field_id, int32_t min_cells, int32_t max_clusters,
                          int64_t *product_id, int64_t info[4], int64_t extent_origin[2] /* may be NULL */);
+
+/* --- voxel atlas (an extension: the 3-D side of the map atlas -- a world-fixed memory of the voxels' classes beyond the rolling window,
+ * with ray and viewpoint queries that run on it in place) -------------------------------------------------------------------------------
+ * The exploration loop  atlas field -> frontiers -> viewpoint poses -> score viewpoints  hands back goals far outside the window, where
+ * every beam of gvom_score_viewpoints is LEFT_WINDOW and a line of sight along a planned way back cannot be checked.  The voxel atlas
+ * keeps, per handle, a toroidally stored, world-anchored grid of A x A x Z voxels at 2 bits each and answers gvom_raycast's and
+ * gvom_score_viewpoints' questions on it.  Everything is exact: a voxel's class is a function of the fused state, the merge is bit
+ * operations, the walk is k_raycast's with the extent in the window's place.  An addition: GVOM_ABI_VERSION stays.  gvom_get_tuning
+ * "voxel_atlas" (read-only): A, or 0 without a voxel atlas -- how a caller probes a library for these entry points;
+ * "voxel_atlas_levels": Z.
+ *
+ * VOXELS.  World voxel (X, Y, Zv) is the integer voxel index in which the fused map's window origin W is counted: window voxel
+ * (x, y, z) is world voxel W + (x, y, z).
+ * CLASS of a fused state s (what gvom_read_dense(GVOM_WHICH_FUSED) returns; a stale tile reads -1):  s >= 0: OCCUPIED (2);  s == -1:
+ * NEVER (0);  otherwise FREE (1).
+ * STORAGE.  A is a power of two, 64 <= A <= 4096, A >= xy_size; Z is a power of two, z_size <= Z <= A; A*A*Z <= 2^32 (1 GiB).  The
+ * atlas is toroidal on all three axes.  Nothing outside the library depends on the layout.
+ * EXTENT.  [Ex, Ex+A) x [Ey, Ey+A) x [Ez, Ez+Z).  gvom_voxel_atlas_configure sets E to fixed_origin ((0, 0, 0) where that is NULL) and
+ * every voxel to NEVER.  Every component of E and of an integrated W must stay below 2^30 in magnitude (GVOM_ERR_INVALID otherwise).
+ *
+ * INTEGRATE (gvom_voxel_atlas_integrate) merges the CURRENT fused map -- the map of the most recently begun combine, exactly as for
+ * gvom_raycast -- in two steps.
+ *   MOVE, in GVOM_ATLAS_FOLLOW mode only:  E'xy = Wxy + floor(xy_size / 2) - A / 2 (the map atlas's rule: both atlases cover the same
+ *   cells when they follow the same combines),  E'z = Wz + floor(z_size / 2) - Z / 2.  Every voxel of the new extent that was not in the
+ *   old one becomes NEVER; a move of a whole side or more on any axis clears everything.  GVOM_ATLAS_FIXED never moves.
+ *   MERGE increments seq.  For every window voxel inside the extent, with c the class of its fused state:  c == NEVER: the atlas voxel
+ *   stays as it is;  otherwise the atlas voxel becomes c.  The current window is the authority wherever it has observed something; a
+ *   voxel that left the ring buffer, or re-enters the window unseen, keeps what was known.
+ * COUNTS (gvom_voxel_atlas_counts, the only call that waits).  int64 out[11].  Of the last integrate: [0] first seen (old NEVER), [1]
+ * free -> occupied, [2] occupied -> free, [3] confirmed (same class), [4] uninformative (inside the extent, c == NEVER), [5] outside the
+ * extent -- [0] .. [5] sum to xy_size^2 * z_size --, [6] voxels made NEVER by the move, [7] of those, how many were observed.  Of the
+ * atlas: [8] observed voxels, [9] occupied voxels, [10] seq.  All are integer sums of population counts, exact whatever the schedule.
+ * BOX (gvom_voxel_atlas_box).  Any integer origin (Bx, By, Bz) -- NULL: the last integrated window's W, and GVOM_NO_DATA where nothing
+ * has been integrated since gvom_voxel_atlas_configure -- gives a product of kind
+ * GVOM_PRODUCT_VOXEL_BOX: part 0 uint8 [xy, xy, z] in the occupancy grid's layout, the class codes 0 / 1 / 2, 0 outside the extent;
+ * part 1 int32 [4] {occupied, free, voxels outside the extent, seq}.  part 0 == 2 is an occupancy grid of remembered space.
+ * origin_out (may be NULL) receives B.
+ * RAYS.  gvom_voxel_atlas_raycast is gvom_raycast's DEFINITION word for word with  W := E,  the window's sizes (A, A, Z),  "fused state
+ * of v" := the atlas class of v (OCCUPIED stops, NEVER counts as unknown),  LEFT_WINDOW := left the extent,  and the step cap A + Z + 1.
+ * The ray set-up, the float32 additions, the literal float64 lookup, the sqrt typing, the flags and the INVALID rule are the same.
+ * Product kind GVOM_PRODUCT_VOXEL_ATLAS_RAYS: part 0 int32 [n, 3] {status, steps, unknown}; part 1 float32 [n, 3] stop position; part 2
+ * int32 [n, 3] the WORLD voxel of the stop, (0, 0, 0) where gvom_raycast reports voxel -1 (a window voxel index would not fit int32 at
+ * A = 4096).  n <= 2^26; host and device routes, no host wait on the device route; a snapshot product, as for gvom_raycast.
+ * extent_voxels (may be NULL) receives E.
+ * VIEWPOINTS.  gvom_voxel_atlas_score_viewpoints takes gvom_score_viewpoints' arguments and has its definition with the same
+ * substitutions; kind GVOM_PRODUCT_VOXEL_ATLAS_VIEWPOINTS in the layout of kind 18.  Only the result is defined: the gain counts
+ * DISTINCT world voxels.  The library deduplicates in one bitmap per pose over a box that it proves to contain every voxel a beam of
+ * that pose can examine -- from the model's largest |direction| and |offset| per axis, max_range, the pose's matrix and translation
+ * (directions need not be unit vectors), widened by the float32 rounding of the walk and clipped to the extent.  The bitmaps live under
+ * the "viewpoint_bitmap_mb" budget with gvom_score_viewpoints' batching; the setting changes time and memory, never the result.  The
+ * boxes are the host's to prove: the device route reads the poses back (K x 96 bytes) and so WAITS for the handle's stream, and the
+ * first call after a gvom_sensor_model_set reads the model back once.
+ * GVOM_ERR_CAPACITY: K > 65536; more than 2^22 selected beams; beams * (A + Z + 1) >= 2^31; a per-pose box of 2^31 bits or more.
+ *
+ * GVOM_NO_DATA before the first combine (integrate and the queries).  GVOM_ERR_INVALID: a sharded handle; no voxel atlas configured;
+ * sizes outside the rules above; an unknown mode; an origin at or beyond 2^30; NULL outputs; unknown flag bits; gvom_raycast's and
+ * gvom_score_viewpoints' argument errors.  Products live in the product-set pool: at most GVOM_MAX_PRODUCT_SETS per kind; an unexported
+ * one goes back to the pool with the next call of its kind.  gvom_voxel_atlas_configure(cells, levels, mode, fixed_origin) allocates or
+ * re-allocates; cells == 0 frees.  gvom_voxel_atlas_clear sets every voxel to NEVER and the counters to 0; the extent and seq stay.
+ * "voxel_atlas_allocations" (read-only): device allocations the entry points have made on this handle (the atlas, its counters, the
+ * staging buffer, bitmaps and product sets); it does not grow in steady state.  "voxel_atlas_viewpoint_batch" (read-only, a
+ * diagnostic): poses per kernel launch of the last gvom_voxel_atlas_score_viewpoints, 0 before the first -- what the
+ * "viewpoint_bitmap_mb" budget came to.  gvom_device_product(kind 32 / 34 / 36) is
+ * GVOM_ERR_INVALID (these calls make them).  Kinds 31, 33 and 35 are not assigned.
+ * NOT PROVIDED: stamps or time decay; hit counts; a "near" class and alignment scoring against the atlas; integrating a caller's dense
+ * grid; more than one voxel atlas per handle; sharded handles; saving to disk. */
+#define GVOM_PRODUCT_VOXEL_BOX 32               /* part 0 uint8 [xy, xy, z] class codes; part 1 int32 [4] {occupied, free, outside, seq} */
+#define GVOM_PRODUCT_VOXEL_ATLAS_RAYS 34        /* part 0 int32 [n, 3] {status, steps, unknown}; part 1 float32 [n, 3]; part 2 int32 [n, 3] world voxel */
+#define GVOM_PRODUCT_VOXEL_ATLAS_VIEWPOINTS 36  /* the two parts of kind 18 */
+#define GVOM_VOXEL_NEVER 0
+#define GVOM_VOXEL_FREE 1
+#define GVOM_VOXEL_OCCUPIED 2
+int gvom_voxel_atlas_configure(gvom_t *h, int32_t cells, int32_t levels, int mode, const int64_t fixed_origin[3] /* may be NULL */);
+int gvom_voxel_atlas_integrate(gvom_t *h);
+int gvom_voxel_atlas_clear(gvom_t *h);
+int gvom_voxel_atlas_counts(gvom_t *h, int64_t out[11]);
+int gvom_voxel_atlas_box(gvom_t *h, const int64_t origin[3] /* may be NULL */, int64_t *product_id, int64_t origin_out[3] /* may be NULL */);
+int gvom_voxel_atlas_raycast(gvom_t *h, const float *from /* [K][3] */, int64_t K, const float *to /* [n][3] */, int64_t n,
+                             int on_device, int flags, int64_t extent_voxels[3], int64_t *product_id);
+int gvom_voxel_atlas_score_viewpoints(gvom_t *h, const double *poses /* [K][12] */, int64_t K, int on_device, double max_range,
+                                      int32_t stride_h, int32_t stride_w, int flags, int64_t extent_voxels[3], int64_t *product_id);
 
 /* --- one map sharded over the GPUs of a node (one rank = one process = one GPU) -------------------
  * No counterpart in the reference (it has no multi-GPU path); semantics = SURVEY 8(e):

@@ -23,32 +23,14 @@
 // fma() calls of div_by_res are its own.
 #include "gvom_device.h"
 #include "gvom_ray.h"
+#include "gvom_classgrid.h"           // the codes, al_spread16 and the field kernels' sizing: shared with k_vatlas_align_field
 
-#define AL_ZC_MAX 16                // levels per k_align_field workgroup, at most
-#define AL_LDS_BUDGET (48 * 1024)   // k_align_field: bytes of masks a workgroup may hold
 #define AL_BLOCK 256
 #define AL_PTS 4                    // returns per lane of k_align_score
 #define AL_UNROLL 2                 // candidates whose loads are in flight together
 
-// the 2-bit codes; count column of part 0 = 1 + code
-#define AL_OCC 0u
-#define AL_NEAR 1u
-#define AL_FREE 2u
-#define AL_UNK 3u
-
 static_assert(GVOM_ALIGN_PTS_BLOCK == AL_BLOCK * AL_PTS, "points per block");
 static_assert(GVOM_ALIGN_CAND_GROUP % AL_UNROLL == 0, "candidate group");
-
-// bit i of the low 16 bits of v -> bit 2 i
-__device__ __forceinline__ uint32_t al_spread16(uint32_t v)
-{
-    v &= 0xffffu;
-    v = (v | (v << 8)) & 0x00ff00ffu;
-    v = (v | (v << 4)) & 0x0f0f0f0fu;
-    v = (v | (v << 2)) & 0x33333333u;
-    v = (v | (v << 1)) & 0x55555555u;
-    return v;
-}
 
 // LDS: three planes of (zc + 2) levels x nq 64-bit words -- [0] occupied in rows y - 1 .. y + 1, [1] occupied in row y, [2] free in row y.
 // Level l of a plane is window level z0 - 1 + l.
@@ -238,20 +220,32 @@ size_t gvom_align_grid_bytes(int xy, int zs)
     return (size_t)zs * (size_t)xy * (size_t)((xy + 15) / 16) * 4;
 }
 
+static bool al_ok(const AlignParams &P)
+{
+    if (P.n < 1 || P.n > GVOM_ALIGN_MAX_POINTS || P.K < 1 || P.K > GVOM_ALIGN_MAX_CANDIDATES || P.xy < 1 || P.zs < 1 ||
+        P.rw != (P.xy + 15) / 16 || (P.dilate != 0 && P.dilate != 1))
+        return false;
+    return gvom_align_grid_bytes(P.xy, P.zs) / 4 <= 0xffffffffull;                                // (word indices are 32 bits)
+}
+
 hipError_t gvom_launch_align(hipStream_t s, const OccParams &F, const AlignParams &P, const int32_t *fstate, const uint32_t *ftags,
                              const float *cloud, const double *tf, uint32_t *grid, int32_t *counts, int32_t *best)
 {
-    if (P.n < 1 || P.n > GVOM_ALIGN_MAX_POINTS || P.K < 1 || P.K > GVOM_ALIGN_MAX_CANDIDATES || P.xy < 1 || P.zs < 1 || P.xy != F.xy ||
-        P.zs != F.zs || P.rw != (P.xy + 15) / 16 || (P.dilate != 0 && P.dilate != 1))
-        return hipErrorInvalidValue;
-    if (gvom_align_grid_bytes(P.xy, P.zs) / 4 > 0xffffffffull) return hipErrorInvalidValue;       // (word indices are 32 bits)
+    if (!al_ok(P) || P.xy != F.xy || P.zs != F.zs) return hipErrorInvalidValue;
     const int zc = al_zc(P.xy, P.zs), nq = (P.xy + 63) / 64;
     if (zc < 1) return hipErrorInvalidValue;
-    hipError_t e = hipMemsetAsync(counts, 0, (size_t)P.K * 24, s);
-    if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_align_field, dim3((unsigned)P.xy, (unsigned)((P.zs + zc - 1) / zc)), dim3(AL_BLOCK), (size_t)3 * (zc + 2) * nq * 8, s,
                        F, zc, nq, P.rw, P.dilate, fstate, ftags, grid);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
+    const hipError_t e = hipGetLastError();
+    return e != hipSuccess ? e : gvom_launch_align_grid(s, P, cloud, tf, grid, counts, best);
+}
+
+hipError_t gvom_launch_align_grid(hipStream_t s, const AlignParams &P, const float *cloud, const double *tf, const uint32_t *grid,
+                                  int32_t *counts, int32_t *best)
+{
+    if (!al_ok(P) || !grid) return hipErrorInvalidValue;
+    hipError_t e = hipMemsetAsync(counts, 0, (size_t)P.K * 24, s);
+    if (e != hipSuccess) return e;
     const dim3 sg((unsigned)((P.n + GVOM_ALIGN_PTS_BLOCK - 1) / GVOM_ALIGN_PTS_BLOCK), (unsigned)((P.K + GVOM_ALIGN_CAND_GROUP - 1) / GVOM_ALIGN_CAND_GROUP));
     if ((P.fastdiv & 3) == 3) hipLaunchKernelGGL(k_align_score<true>, sg, dim3(AL_BLOCK), 0, s, P, cloud, tf, grid, counts);
     else hipLaunchKernelGGL(k_align_score<false>, sg, dim3(AL_BLOCK), 0, s, P, cloud, tf, grid, counts);

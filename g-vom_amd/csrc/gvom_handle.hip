@@ -614,6 +614,7 @@ VIS int gvom_get_tuning(gvom_t *h, const char *name, int *value)
     if (!strcmp(name, "attitude_volume_allocations")) { *value = h->av_allocs; return GVOM_OK; }        // read-only: device allocations gvom_attitude_volume has made
     if (!strcmp(name, "atlas_allocations")) { *value = h->atl_allocs; return GVOM_OK; }                  // read-only: device allocations the gvom_atlas_* calls have made
     if (!strcmp(name, "voxel_atlas")) { *value = h->va_A; return GVOM_OK; }                              // read-only: the side A of the configured voxel atlas, 0 without one
+    if (!strcmp(name, "voxel_atlas_alignments")) { *value = 1; return GVOM_OK; }                         // read-only: the library has gvom_voxel_atlas_score_alignments
     if (!strcmp(name, "voxel_atlas_levels")) { *value = h->va_A ? h->va_Z : 0; return GVOM_OK; }         // read-only: its levels Z
     if (!strcmp(name, "voxel_atlas_allocations")) { *value = h->va_allocs; return GVOM_OK; }             // read-only: device allocations the gvom_voxel_atlas_* calls have made
     if (!strcmp(name, "voxel_atlas_viewpoint_batch")) { *value = h->va_last_batch; return GVOM_OK; }     // read-only: poses per launch of the last gvom_voxel_atlas_score_viewpoints

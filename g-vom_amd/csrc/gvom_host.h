@@ -523,6 +523,16 @@ template <class T> inline T *part_ptr(const DevSet *s, int part)
     return (T *)d.ptr;
 }
 
+// the metric frame of the fused map F for the kernels that turn world coordinates into voxels (ScanParams, AlignParams): the
+// resolutions, their reciprocals, whether the verified reciprocal form may be used, the window's corner
+template <class P> inline void metric_frame(const gvom_handle *h, const Fused &F, P &p)
+{
+    p.xy_res = h->prm.xy_resolution; p.z_res = h->prm.z_resolution;
+    p.drcp[0] = 1.0 / h->prm.xy_resolution; p.drcp[1] = 1.0 / h->prm.z_resolution;
+    p.fastdiv = h->tune_fastdiv == 0 ? 0 : h->fastdiv_ok;
+    for (int k = 0; k < 3; ++k) p.origin[k] = (double)F.origin[k];
+}
+
 // grows a buffer of the handle to at least `bytes`; an allocation counts in `allocs`
 inline int stage_buf(gvom_handle *h, Buf &b, size_t bytes, int &allocs)
 {

@@ -393,6 +393,10 @@ struct AlignParams {
 size_t gvom_align_grid_bytes(int xy, int zs);
 hipError_t gvom_launch_align(hipStream_t s, const OccParams &F, const AlignParams &P, const int32_t *fstate, const uint32_t *ftags,
                              const float *cloud, const double *tf, uint32_t *grid, int32_t *counts, int32_t *best);
+// the same behind a class grid that is READY on the stream (k_align_field's layout: gvom_launch_align's own, or the voxel atlas's
+// gvom_launch_vatlas_align_field): clears counts, k_align_score, k_align_best.  P.origin is the origin of whatever the grid shows.
+hipError_t gvom_launch_align_grid(hipStream_t s, const AlignParams &P, const float *cloud, const double *tf, const uint32_t *grid,
+                                  int32_t *counts, int32_t *best);
 // frontier extraction (gvom_frontier.hip; include/gvom_hip.h "frontier extraction" defines the result).  Every map is [y][x], xy x xy:
 // c uint16 cell costs, vis int32 visibility, D int32 cost to go (may be nullptr).  L and count are the two int32 work arrays of
 // xy*xy cells.  mark: L = own index at a frontier cell / 0xffffffff elsewhere, count = 0, flags[tile] = 1 where a tile
@@ -540,6 +544,10 @@ hipError_t gvom_launch_vatlas_merge(hipStream_t s, const VAtlas &V, const VAtlas
                                     const uint32_t *ftags, unsigned long long *cnt);
 hipError_t gvom_launch_vatlas_move(hipStream_t s, const VAtlas &V, const VAtlasSlab &S, unsigned long long *cnt);
 hipError_t gvom_launch_vatlas_box(hipStream_t s, const VAtlas &V, VAtlasBox B, uint8_t *out, int32_t *counts);
+// the same box (n, zs, r*, p*; the other fields are not read) as the class grid of scan alignment scoring, gvom_align_grid_bytes(n, zs)
+// of it, in k_align_field's layout and codes: what gvom_launch_align_grid scores against.  A voxel's class is the atlas's alone (NEAR
+// looks at the extent's voxels outside the box too); a box voxel outside the extent is UNKNOWN.
+hipError_t gvom_launch_vatlas_align_field(hipStream_t s, const VAtlas &V, const VAtlasBox &B, int dilate, uint32_t *grid);
 // the walks: P = gvom_launch_raycast's frame with the extent in the window's place (origin = E, xy = A, zs = Z, om = E & (size - 1)), Q as
 // there with cap = A + Z.  raycast: out3 [n][3] = {status, steps, unknown}, pos3 [n][3] the stop position in metres, vox3 [n][3] the world
 // voxel of the stop.  viewpoints / viewpoint_best: as gvom_launch_viewpoints / _viewpoint_best; boxes [K][8] int32 = {lx, ly, lz, dx, dy,

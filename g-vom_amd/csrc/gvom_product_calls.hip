@@ -28,16 +28,6 @@ void cloud_params(const gvom_handle *h, const Fused &F, Map2dParams &P)
     P.xy_res = h->prm.xy_resolution; P.z_res = h->prm.z_resolution;
 }
 
-// the metric frame of the fused map F for the kernels that turn world coordinates into voxels (ScanParams, AlignParams): the
-// resolutions, their reciprocals, whether the verified reciprocal form may be used, the window's corner
-template <class P> static void metric_frame(const gvom_handle *h, const Fused &F, P &p)
-{
-    p.xy_res = h->prm.xy_resolution; p.z_res = h->prm.z_resolution;
-    p.drcp[0] = 1.0 / h->prm.xy_resolution; p.drcp[1] = 1.0 / h->prm.z_resolution;
-    p.fastdiv = h->tune_fastdiv == 0 ? 0 : h->fastdiv_ok;
-    for (int k = 0; k < 3; ++k) p.origin[k] = (double)F.origin[k];
-}
-
 // the frame of the fused map F as k_raycast reads it (gvom_launch_raycast names the fields), and what of a query depends on it
 static void raycast_params(const gvom_handle *h, const Fused &F, ScanParams &P, RayQuery &Q)
 {

@@ -45,6 +45,7 @@
 //   atlas rays (34)  cap x 3 int32 {status, steps, unknown}, then cap x 3 floats (stop position), then cap x 3 int32 (the world voxel of the
 //                    stop); cap = the rays of the call that wrote it.  Kind 33 is not assigned
 //   atlas viewpoints (36)  the two parts of viewpoints (18).  Kind 35 is not assigned
+//   atlas alignment (38)   the two parts of alignment (12).  Kind 37 is not assigned
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -94,6 +95,7 @@ inline size_t set_bytes(int kind, int xy, int zs, int64_t cap, int64_t cols = 0)
     case GVOM_PRODUCT_VOXEL_BOX: return align256(n2 * zs) + 16;
     case GVOM_PRODUCT_VOXEL_ATLAS_RAYS: return 2 * align256((size_t)cap * 12) + (size_t)cap * 12;
     case GVOM_PRODUCT_VOXEL_ATLAS_VIEWPOINTS: return align256((size_t)cap * 32) + 16;
+    case GVOM_PRODUCT_VOXEL_ATLAS_ALIGNMENT: return align256((size_t)cap * 24) + 16;
     }
     return 0;
 }
@@ -152,6 +154,7 @@ inline bool set_part(const SetShape *s, int part, SetPart *d)
         else return false;
         break;
     case GVOM_PRODUCT_ALIGNMENT:
+    case GVOM_PRODUCT_VOXEL_ATLAS_ALIGNMENT:               // (38: the same two parts)
         if (part == 0) { rows(s->mem, s->cap, 6); d->code = kDLInt; }
         else if (part == 1) { d->ptr = s->mem + align256((size_t)s->cap * 24); d->ndim = 1; d->shape[0] = 4; d->strides[0] = 1; d->shape[1] = d->strides[1] = 1; d->code = kDLInt; }
         else return false;

@@ -14,6 +14,11 @@
 //   k_vatlas_move            clears one slab of pairs (cyclic intervals of rows, levels and columns, the columns as edge masks)
 //   k_vatlas_box             any window-sized box as the uint8 class grid out[x][y][z]: a thread holds the 64 x bits of one (y, z) row
 //                            and stores a byte per x; for one x the workgroup's (y, z) are consecutive bytes.  No LDS
+//   k_vatlas_align_field     any window-sized box as k_align_field's class grid (gvom_align.hip: 2-bit codes, 16 voxels per uint32, box
+//                            order [z][y][x]), so that k_align_score and k_align_best run on remembered space unchanged: k_align_field's
+//                            shape -- one box row and a chunk of levels per workgroup, three planes of 64-bit masks in LDS, the
+//                            26-neighbourhood by ORs and shifts -- with the masks assembled from pairs as k_vatlas_box assembles its rows,
+//                            no ballots; the halo rows, levels and the two x carries are the atlas's own voxels where the extent has them
 //   k_vatlas_raycast         k_raycast's walk (gvom_ray.h: set-up and step count) on the atlas: one ray per lane, RQ_DEPTH 16-byte
 //                            loads in flight, the lookup masks and shifts only -- no tile tags, no epoch
 //   k_vatlas_viewpoints      k_viewpoints' shape on the same lookup; the distinct never-observed voxels of a pose are counted in a bitmap
@@ -25,6 +30,7 @@
 #include "gvom_device.h"
 #include "gvom_ray.h"
 #include "gvom_raywalk.h"
+#include "gvom_classgrid.h"
 #include <algorithm>
 
 #define VA_BLOCK 256
@@ -191,6 +197,91 @@ __global__ __launch_bounds__(VA_BLOCK) void k_vatlas_box(const VAtlas V, const V
         uint8_t *o = out + ((size_t)x0 * n + y) * zs + z;
         const size_t pitch = (size_t)n * zs;
         for (uint32_t b = 0; b < nx; ++b) o[b * pitch] = (uint8_t)(((obs >> b) & 1ull) + ((occ >> b) & 1ull));     // 0 never, 1 free, 2 occupied
+    }
+}
+
+// ---- the class grid of scan alignment scoring ---------------------------------------------------------------------------------------------
+// which of the 64 box columns x0 .. x0 + 63 of box row y and box level z lie inside the extent (0 where the row or the level does not)
+__device__ __forceinline__ unsigned long long va_box_inside(const VAtlas &V, const VAtlasBox &B, int x0, int y, int z)
+{
+    const uint32_t ey = (uint32_t)(B.ry + y), ez = (uint32_t)(B.rz + z);                   // (|r| <= 2^30, |y|, |z| <= 4160: no overflow)
+    const int e0 = B.rx + x0;                                                              // extent voxel of bit 0
+    const int lo_b = e0 < 0 ? -e0 : 0, hi_b = min(64, V.A - e0);                           // bits [lo_b, hi_b)
+    if (ey >= (uint32_t)V.A || ez >= (uint32_t)V.Z || lo_b >= hi_b) return 0ull;
+    return bits_below((uint32_t)hi_b) & ~bits_below((uint32_t)lo_b);
+}
+
+// the pair of the 64 box columns x0 .. x0 + 63 (x0 a multiple of 64; -64 and past the box's last column included) of box row y and box
+// level z, both possibly one outside the box: two storage pairs shifted together, the bits outside the extent cleared.  Every wrap is an AND
+__device__ __forceinline__ v2ull va_box_segment(const VAtlas &V, const VAtlasBox &B, int x0, int y, int z)
+{
+    const uint32_t uA = (uint32_t)V.A, uZ = (uint32_t)V.Z;
+    v2ull r = {0ull, 0ull};
+    const unsigned long long valid = va_box_inside(V, B, x0, y, z);
+    if (valid != 0ull) {
+        const uint32_t sy = ((uint32_t)B.py + (uint32_t)y) & (uA - 1u), sz = ((uint32_t)B.pz + (uint32_t)z) & (uZ - 1u);
+        const uint32_t sx = ((uint32_t)B.px + (uint32_t)x0) & (uA - 1u), sh = sx & 63u;
+        const v2ull lo = ((const v2ull *)V.pairs)[va_pair(V, sx, sy, sz)];
+        r.x = lo.x >> sh; r.y = lo.y >> sh;
+        if (sh) {
+            const v2ull hi = ((const v2ull *)V.pairs)[va_pair(V, (sx + 64u) & (uA - 1u), sy, sz)];
+            r.x |= hi.x << (64u - sh); r.y |= hi.y << (64u - sh);
+        }
+        r.x &= valid; r.y &= valid;
+    }
+    return r;
+}
+
+// LDS: plane [0], (zc + 2) levels x (nq + 2) 64-bit words: occupied in box rows y - 1 .. y + 1, segments -1 .. nq (the two outer ones
+// carry the voxels next to the box's first and last column); planes [1] and [2], (zc + 2) levels x nq words: occupied / free in row y.
+// Level l of a plane is box level z0 - 1 + l.  A thread assembles one segment of one level: up to six 16-byte loads in flight, no ballots.
+// dilate == 0 loads no halo: rows y +- 1, levels z0 - 1 and z0 + zc and the outer segments stay zero.
+__global__ __launch_bounds__(VA_BLOCK) void k_vatlas_align_field(const VAtlas V, const VAtlasBox B, const int zc, const int nq, const int rw,
+                                                                 const int dilate, uint32_t *__restrict__ grid)
+{
+    extern __shared__ unsigned long long s_va[];
+    const int y = (int)blockIdx.x, z0 = (int)blockIdx.y * zc;
+    const int nl = zc + 2, na = nq + 2;
+    unsigned long long *const s_around = s_va, *const s_own = s_va + nl * na, *const s_free = s_own + nl * nq;
+    const int nlev = min(zc, B.zs - z0);                                                   // the box levels this workgroup writes
+    for (int it = (int)threadIdx.x; it < nl * na; it += VA_BLOCK) {
+        const int l = it / na, q = it - l * na - 1;                                        // segment q = -1 .. nq
+        const int z = z0 - 1 + l, x0 = q * 64;
+        const bool inner = q >= 0 && q < nq && l >= 1 && l <= nlev;                        // a segment of the box itself
+        unsigned long long around = 0ull, own = 0ull, fre = 0ull;
+        if (dilate ? l <= nlev + 1 : inner) {
+            v2ull p[3] = {{0ull, 0ull}, {0ull, 0ull}, {0ull, 0ull}};
+#pragma unroll
+            for (int d = 0; d < 3; ++d)                                                    // rows y - 1, y, y + 1: their loads in flight together
+                if (d == 1 || dilate) p[d] = va_box_segment(V, B, x0, y + d - 1, z);
+            around = p[0].y | p[1].y | p[2].y;
+            const unsigned long long box = bits_below((uint32_t)min(64, max(0, B.n - x0)));   // the columns inside the box
+            own = p[1].y & box; fre = p[1].x & ~p[1].y & box;
+        }
+        s_around[it] = around;
+        if (q >= 0 && q < nq) { s_own[l * nq + q] = inner ? own : 0ull; s_free[l * nq + q] = inner ? fre : 0ull; }
+    }
+    __syncthreads();
+    for (int it = (int)threadIdx.x; it < nlev * nq * 4; it += VA_BLOCK) {
+        const int j = it & 3, lq = it >> 2;
+        const int l = lq / nq + 1, q = lq - (l - 1) * nq;
+        if (q * 4 + j >= rw) continue;
+        const unsigned long long own = s_own[l * nq + q], fre = s_free[l * nq + q];
+        unsigned long long near = 0ull;
+        if (dilate) {
+            unsigned long long m = 0ull, left = 0ull, right = 0ull;
+#pragma unroll
+            for (int dl = -1; dl <= 1; ++dl) {
+                const unsigned long long *row = s_around + (l + dl) * na + q + 1;
+                m |= row[0]; left |= row[-1]; right |= row[1];
+            }
+            near = (m | (m << 1) | (m >> 1) | (left >> 63) | (right << 63)) & va_box_inside(V, B, q * 64, y, z0 + l - 1);   // a voxel outside the extent is UNKNOWN
+        }
+        const uint32_t o16 = (uint32_t)(own >> (16 * j)), n16 = (uint32_t)(near >> (16 * j)), f16 = (uint32_t)(fre >> (16 * j));
+        // AL_OCC 0, AL_NEAR 1, AL_FREE 2, AL_UNK 3: high bit = neither occupied nor near, low bit = not occupied and (near or not free)
+        const uint32_t hi = ~o16 & ~n16, lo = ~o16 & (n16 | ~f16);
+        const int z = z0 + l - 1;
+        grid[((size_t)z * B.n + y) * rw + q * 4 + j] = al_spread16(lo) | (al_spread16(hi) << 1);
     }
 }
 
@@ -564,6 +655,24 @@ hipError_t gvom_launch_vatlas_box(hipStream_t s, const VAtlas &V, VAtlasBox B, u
     B.yb = VA_BLOCK / B.zc;
     const dim3 grid((unsigned)((B.n + 63) / 64), (unsigned)((B.n + B.yb - 1) / B.yb), (unsigned)((B.zs + B.zc - 1) / B.zc));
     hipLaunchKernelGGL(k_vatlas_box, grid, dim3(VA_BLOCK), 0, s, V, B, out, counts);
+    return hipGetLastError();
+}
+
+// levels per workgroup of k_vatlas_align_field: what fits the LDS budget ((zc + 2) levels of 3 nq + 2 64-bit words), at most AL_ZC_MAX
+hipError_t gvom_launch_vatlas_align_field(hipStream_t s, const VAtlas &V, const VAtlasBox &B, int dilate, uint32_t *grid)
+{
+    if (!va_ok(V) || B.n < 1 || B.n > GVOM_VATLAS_MAX_CELLS || B.zs < 1 || B.zs > GVOM_VATLAS_MAX_CELLS || !grid || (dilate != 0 && dilate != 1))
+        return hipErrorInvalidValue;
+    if (B.px < 0 || B.px >= V.A || B.py < 0 || B.py >= V.A || B.pz < 0 || B.pz >= V.Z) return hipErrorInvalidValue;
+    const int lim = 1 << 30;
+    if (B.rx < -lim || B.rx > lim || B.ry < -lim || B.ry > lim || B.rz < -lim || B.rz > lim) return hipErrorInvalidValue;
+    const int nq = (B.n + 63) / 64, rw = (B.n + 15) / 16;
+    int zc = AL_LDS_BUDGET / (8 * (3 * nq + 2)) - 2;
+    zc = zc > AL_ZC_MAX ? AL_ZC_MAX : zc;
+    zc = zc > B.zs ? B.zs : zc;
+    if (zc < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_vatlas_align_field, dim3((unsigned)B.n, (unsigned)((B.zs + zc - 1) / zc)), dim3(VA_BLOCK), (size_t)(zc + 2) * (3 * nq + 2) * 8, s,
+                       V, B, zc, nq, rw, dilate, grid);
     return hipGetLastError();
 }
 

@@ -1,5 +1,5 @@
 // gvom_voxel_atlas_calls.hip -- the voxel atlas's entry points (include/gvom_hip.h "voxel atlas"): gvom_voxel_atlas_configure, _integrate,
-// _clear, _counts, _box, _raycast and _score_viewpoints.  The kernels are gvom_voxel_atlas.hip's; everything runs on the handle's stream --
+// _clear, _counts, _box, _raycast, _score_viewpoints and _score_alignments.  The kernels are gvom_voxel_atlas.hip's; everything runs on the handle's stream --
 // an integrate behind whatever produced the current fused map, a query behind the integrates before it -- and only gvom_voxel_atlas_counts
 // waits for it (the viewpoint call waits where it has to read poses or the sensor model back: the boxes of its bitmaps are proved here, on
 // the host).  The products go through the pool path of every product call (product_acquire / product_publish, gvom_sets.hip), host inputs
@@ -44,6 +44,22 @@ void clip(int r, int len, int size, int *lo, int *n)
     const int64_t a = std::max<int64_t>(0, -(int64_t)r), b = std::min<int64_t>(len, (int64_t)size - r);
     *lo = b > a ? (int)a : 0;
     *n = b > a ? (int)(b - a) : 0;
+}
+
+// the window-sized box at world voxel B as the box kernels take it: relative to the extent, with its storage phase.  Returns how many of
+// its voxels lie inside the extent
+int64_t box_frame(const gvom_handle *h, const int64_t B[3], VAtlasBox &X)
+{
+    memset(&X, 0, sizeof X);
+    X.n = h->prm.xy_size; X.zs = h->prm.z_size;
+    int r[3], lo[3], n[3];
+    for (int k = 0; k < 3; ++k) {
+        r[k] = rel_of(h, B, k);
+        clip(r[k], window_side(h, k), side(h, k), &lo[k], &n[k]);
+    }
+    X.rx = r[0]; X.ry = r[1]; X.rz = r[2];
+    X.px = (int)(B[0] & (h->va_A - 1)); X.py = (int)(B[1] & (h->va_A - 1)); X.pz = (int)(B[2] & (h->va_Z - 1));
+    return (int64_t)n[0] * n[1] * n[2];
 }
 
 // follow mode: the extent goes to `to`; the voxels that entered it become NEVER -- the slab of columns over every row and level, the slab
@@ -296,16 +312,7 @@ VIS int gvom_voxel_atlas_box(gvom_t *h, const int64_t origin[3], int64_t *produc
     HIPCHK(h, join_second_stream(h));
     if ((rc = set_wait_releases(h, set))) return rc;
     VAtlasBox X;
-    memset(&X, 0, sizeof X);
-    X.n = xy; X.zs = zs;
-    int r[3], lo[3], n[3];
-    for (int k = 0; k < 3; ++k) {
-        r[k] = rel_of(h, B, k);
-        clip(r[k], window_side(h, k), side(h, k), &lo[k], &n[k]);
-    }
-    X.rx = r[0]; X.ry = r[1]; X.rz = r[2];
-    X.px = (int)(B[0] & (h->va_A - 1)); X.py = (int)(B[1] & (h->va_A - 1)); X.pz = (int)(B[2] & (h->va_Z - 1));
-    X.outside = (int)((int64_t)xy * xy * zs - (int64_t)n[0] * n[1] * n[2]);
+    X.outside = (int)((int64_t)xy * xy * zs - box_frame(h, B, X));
     X.seq = (int)std::min<int64_t>(h->va_seq, INT32_MAX);
     int32_t *counts = part_ptr<int32_t>(set, 1);
     HIPCHK(h, hipMemsetAsync(counts, 0, 16, h->stream));
@@ -443,5 +450,64 @@ VIS int gvom_voxel_atlas_score_viewpoints(gvom_t *h, const double *poses, int64_
     if ((rc = product_publish(h, set, product_id))) return rc;
     for (int k = 0; extent_voxels && k < 3; ++k) extent_voxels[k] = h->va_E[k];
     return GVOM_OK;
+}
+
+// gvom_score_alignments on the atlas: k_vatlas_align_field turns the box at B into the class grid -- in the handle's class-grid buffer,
+// gvom_score_alignments' own: both rebuild it in every call, on the one stream -- and gvom_launch_align_grid scores against it with
+// origin = B.  The resolutions and the division form are the current fused map's frame.  Read-only on the atlas; enqueues and returns
+// (the host route waits for its upload).
+VIS int gvom_voxel_atlas_score_alignments(gvom_t *h, const float *cloud, int64_t n, const double *transforms, int64_t K, int on_device, int dilate,
+                                          const int32_t weights[5], const int64_t origin[3], int64_t origin_out[3], int64_t *product_id)
+{
+    if (!h || !product_id) return GVOM_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(h->mu);
+    *product_id = -1;
+    const char *const fn = "gvom_voxel_atlas_score_alignments";
+    int rc = need_atlas(h, fn);
+    if (rc) return rc;
+    if (!cloud || !transforms || !weights) return refuse(h, fn, "cloud, transforms and weights must not be NULL");
+    if (n < 1) return refuse(h, fn, "n must be at least 1");
+    if (K < 1) return refuse(h, fn, "K must be at least 1");
+    if (dilate != 0 && dilate != 1) return refuse(h, fn, "dilate must be 0 or 1");
+    for (int c = 0; c < 5; ++c)
+        if (weights[c] < -GVOM_ALIGN_MAX_WEIGHT || weights[c] > GVOM_ALIGN_MAX_WEIGHT) return refuse(h, fn, "a weight outside -1024 .. 1024");
+    if (n > GVOM_ALIGN_MAX_POINTS) return refuse(h, fn, "more than 2^20 returns in one call", GVOM_ERR_CAPACITY);
+    if (K > GVOM_ALIGN_MAX_CANDIDATES) return refuse(h, fn, "more than 65536 candidates in one call", GVOM_ERR_CAPACITY);
+    if (n * K > GVOM_ALIGN_MAX_PAIRS) return refuse(h, fn, "more than 2^32 pairs in one call", GVOM_ERR_CAPACITY);
+    const int xy = h->prm.xy_size, zs = h->prm.z_size;
+    const size_t gb = gvom_align_grid_bytes(xy, zs);
+    if (gb / 4 > 0xffffffffull) return refuse(h, fn, "the class grid of this map has 2^32 words or more", GVOM_ERR_CAPACITY);
+    if (!h->has_combined || (!origin && h->va_seq == 0)) return GVOM_NO_DATA;     // (NULL: the last integrated window, and there is none yet)
+    const int64_t B[3] = {origin ? origin[0] : h->va_last[0], origin ? origin[1] : h->va_last[1], origin ? origin[2] : h->va_last[2]};
+    HIPCHK(h, hipSetDevice(h->device));
+    DevSet *set = nullptr;
+    const size_t bytes = set_bytes(GVOM_PRODUCT_VOXEL_ATLAS_ALIGNMENT, 0, 0, K);
+    if ((rc = product_acquire(h, GVOM_PRODUCT_VOXEL_ATLAS_ALIGNMENT, bytes, bytes, fn, &h->va_allocs, &set))) return rc;
+    set->cap = K;
+    if ((rc = stage_buf(h, h->al_grid, gb, h->al_allocs))) return rc;
+    AlignParams P;
+    memset(&P, 0, sizeof P);
+    metric_frame(h, h->fused[h->cur], P);
+    for (int k = 0; k < 3; ++k) P.origin[k] = (double)B[k];
+    P.n = (long)n; P.K = (int)K; P.xy = xy; P.zs = zs; P.rw = (xy + 15) / 16; P.dilate = dilate;
+    for (int c = 0; c < 5; ++c) P.w[c] = weights[c];
+    const float *cdev = cloud;
+    const double *tdev = transforms;
+    HIPCHK(h, join_second_stream(h));
+    if (!on_device) {                                                       // host inputs: staged, and up before the call returns
+        const HostPart parts[2] = {{transforms, (size_t)K * 96}, {cloud, (size_t)n * 12}};
+        const void *dev[2];
+        if ((rc = stage_host(h, h->va_stage, h->va_allocs, parts, 2, true, dev))) return rc;
+        tdev = (const double *)dev[0]; cdev = (const float *)dev[1];
+    }
+    if ((rc = set_wait_releases(h, set))) return rc;
+    VAtlasBox X;
+    box_frame(h, B, X);
+    uint32_t *const grid = (uint32_t *)h->al_grid.p;
+    HIPCHK(h, gvom_launch_vatlas_align_field(h->stream, atlas_of(h), X, dilate, grid));
+    HIPCHK(h, gvom_launch_align_grid(h->stream, P, cdev, tdev, grid, part_ptr<int32_t>(set, 0), part_ptr<int32_t>(set, 1)));
+    for (int k = 0; k < 3; ++k) set->origin[k] = B[k];
+    for (int k = 0; origin_out && k < 3; ++k) origin_out[k] = B[k];
+    return product_publish(h, set, product_id);
 }
 }  // extern "C"

@@ -193,6 +193,7 @@ ABI = [
     ("gvom_voxel_atlas_raycast", _I, [_P, _P, _I64, _P, _I64, _I, _I, ctypes.POINTER(_I64), ctypes.POINTER(_I64)]),
     ("gvom_voxel_atlas_score_viewpoints", _I, [_P, _P, _I64, _I, ctypes.c_double, ctypes.c_int32, ctypes.c_int32, _I, ctypes.POINTER(_I64),
                                                ctypes.POINTER(_I64)]),
+    ("gvom_voxel_atlas_score_alignments", _I, [_P, _P, _I64, _P, _I64, _I, _I, _P, ctypes.POINTER(_I64), ctypes.POINTER(_I64), ctypes.POINTER(_I64)]),
     ("gvom_set_profiling", _I, [_P, _I]),
     ("gvom_host_timing", _I, [_P, ctypes.POINTER(ctypes.c_double * 8)]),
     ("gvom_set_tuning", _I, [_P, ctypes.c_char_p, _I]),
@@ -624,6 +625,7 @@ PRODUCT_ATTITUDE_VOLUME = 30              # GVOM_PRODUCT_ATTITUDE_VOLUME: made b
 PRODUCT_VOXEL_BOX = 32                    # GVOM_PRODUCT_VOXEL_BOX: made by gvom_voxel_atlas_box (kind 31 is not assigned)
 PRODUCT_VOXEL_ATLAS_RAYS = 34             # GVOM_PRODUCT_VOXEL_ATLAS_RAYS: made by gvom_voxel_atlas_raycast (kind 33 is not assigned)
 PRODUCT_VOXEL_ATLAS_VIEWPOINTS = 36       # GVOM_PRODUCT_VOXEL_ATLAS_VIEWPOINTS: made by gvom_voxel_atlas_score_viewpoints (kind 35 is not assigned)
+PRODUCT_VOXEL_ATLAS_ALIGNMENT = 38        # GVOM_PRODUCT_VOXEL_ATLAS_ALIGNMENT: made by gvom_voxel_atlas_score_alignments (kind 37 is not assigned)
 # element type of part k of a product, by kind (what set_part() of csrc/gvom_setlayout.h gives as DLPack code and bits)
 _PRODUCT_DTYPES = {PRODUCT_OCCUPANCY: (np.uint8,), PRODUCT_VOXEL_CLOUD: (np.float32, np.float32, np.int64),
                    PRODUCT_HEIGHT_CLOUD: (np.float32,), PRODUCT_INFERRED_HEIGHT_CLOUD: (np.float32,),
@@ -637,7 +639,7 @@ _PRODUCT_DTYPES = {PRODUCT_OCCUPANCY: (np.uint8,), PRODUCT_VOXEL_CLOUD: (np.floa
                    PRODUCT_ATLAS_FRONTIERS: (np.int32, np.int64, np.int32, np.int32),
                    PRODUCT_ATTITUDE_VOLUME: (np.uint8, np.uint8, np.int32),
                    PRODUCT_VOXEL_BOX: (np.uint8, np.int32), PRODUCT_VOXEL_ATLAS_RAYS: (np.int32, np.float32, np.int32),
-                   PRODUCT_VOXEL_ATLAS_VIEWPOINTS: (np.int32, np.int32)}
+                   PRODUCT_VOXEL_ATLAS_VIEWPOINTS: (np.int32, np.int32), PRODUCT_VOXEL_ATLAS_ALIGNMENT: (np.int32, np.int32)}
 CLEARANCE_FAR = 2147483647                # GVOM_CLEARANCE_FAR: squared_cells where no obstacle is in reach
 _CLEARANCE_NO_NEGATIVE = 1                # GVOM_CLEARANCE_NO_NEGATIVE
 
@@ -2170,12 +2172,23 @@ class DeviceAtlasViewpoints(DeviceViewpoints):
         self.extent_origin = extent_origin
 
 
+class DeviceAtlasAlignments(DeviceAlignments):
+    """The result of VoxelAtlas.score_alignments() / score_alignments_device(): a DeviceAlignments whose returns were classed by the
+    voxel atlas -- "outside" means outside the box, "near" looks at remembered occupied voxels beyond the box's faces too.
+    `.origin_voxels`: the box's corner in world voxels; `.origin` the same as float64."""
+
+    def __init__(self, hold, origin_voxels):
+        DeviceAlignments.__init__(self, hold, np.array(origin_voxels, np.float64))
+        self.origin_voxels = origin_voxels
+
+
 class VoxelAtlas(object):
     """The voxel atlas of a mapper (Gvom.create_voxel_atlas): a world-fixed, toroidally stored memory of the voxels' classes --
     never observed, observed free, occupied -- `cells` x `cells` x `levels` voxels at 2 bits each, that keeps what the rolling window
     forgets.  integrate() merges the current fused map into it on the GPU (what the window has observed wins; what it has not stays as
     it was known), raycast() and score_viewpoints() are Gvom.raycast() and Gvom.score_viewpoints() on the whole extent, box() returns any
-    window-sized part as a class grid.  Only counts() waits for the GPU (score_viewpoints_device() reads its poses back).
+    window-sized part as a class grid, score_alignments() is Gvom.score_alignments() against any such part.  Only counts() waits for
+    the GPU (score_viewpoints_device() reads its poses back).
     include/gvom_hip.h "voxel atlas" has the definition."""
 
     def __init__(self, owner, cells, levels, follow, origin_voxels):
@@ -2209,6 +2222,15 @@ class VoxelAtlas(object):
         the first combine.
         No host wait."""
         g = self._owner
+        org = self._box_origin(origin_voxels, center)
+        out = (_I64 * 3)()
+        hold = g._make_product(lambda pid: g._lib.gvom_voxel_atlas_box(g._h, org, pid, out), PRODUCT_VOXEL_BOX, g._check_args)
+        return None if hold is None else DeviceVoxelBox(hold, tuple(int(v) for v in out))
+
+    def _box_origin(self, origin_voxels, center):
+        """the corner of a window-sized box as the library takes it: origin_voxels, or the window of a scan with its ego at `center`,
+        or None (the last integrated window)"""
+        g = self._owner
         if origin_voxels is not None and center is not None:
             raise ValueError("give origin_voxels or center, not both")
         if center is not None:
@@ -2217,10 +2239,39 @@ class VoxelAtlas(object):
                 raise ValueError("center must be three finite numbers (x, y, z) in metres, got %r" % (center,))
             res, size = (g.xy_resolution, g.xy_resolution, g.z_resolution), (g.xy_size, g.xy_size, g.z_size)
             origin_voxels = [int(math.floor(v / r - n / 2.0)) for v, r, n in zip(c, res, size)]
-        org = None if origin_voxels is None else _voxel_origin(origin_voxels)
+        return None if origin_voxels is None else _voxel_origin(origin_voxels)
+
+    def _score_alignments(self, cloud_ptr, n, tf_ptr, K, on_device, dilate, weights, origin_voxels, center):
+        g = self._owner
+        dilate, w = _align_options(dilate, weights)
+        n, K = _align_shape(n, K)
+        org = self._box_origin(origin_voxels, center)
         out = (_I64 * 3)()
-        hold = g._make_product(lambda pid: g._lib.gvom_voxel_atlas_box(g._h, org, pid, out), PRODUCT_VOXEL_BOX, g._check_args)
-        return None if hold is None else DeviceVoxelBox(hold, tuple(int(v) for v in out))
+        hold = g._make_product(lambda pid: g._lib.gvom_voxel_atlas_score_alignments(g._h, cloud_ptr, n, tf_ptr, K, int(on_device), dilate, w, org,
+                                                                                    out, pid), PRODUCT_VOXEL_ATLAS_ALIGNMENT, g._check_args)
+        return None if hold is None else DeviceAtlasAlignments(hold, tuple(int(v) for v in out))
+
+    def score_alignments(self, cloud, transforms, dilate=0, weights=ALIGN_DEFAULT_WEIGHTS, origin_voxels=None, center=None):
+        """Gvom.score_alignments() against the atlas -- relocalising on remembered space: the same cloud, candidates, dilate and
+        weights, held against the window-sized box whose corner is origin_voxels or the window of a scan with its ego at `center`
+        (both as in box(); default: the last integrated window).  A voxel's class is the atlas's: occupied, near (dilate=1: an
+        occupied voxel anywhere in the extent within one voxel on every axis), free, never observed (also: outside the extent);
+        "outside" is outside the box.  Returns a DeviceAtlasAlignments; None before the first combine and, without an origin, before
+        the first integrate."""
+        c = np.asarray(cloud)
+        if c.dtype != np.float32:
+            raise TypeError("cloud must be float32, got %s" % c.dtype)
+        if c.ndim != 2 or c.shape[1] != 3:
+            raise ValueError("cloud must have shape (n, 3), got %r" % (c.shape,))
+        c = np.ascontiguousarray(c)
+        t = _align_transforms(transforms)
+        return self._score_alignments(_ptr(c), c.shape[0], _ptr(t), t.shape[0], 0, dilate, weights, origin_voxels, center)
+
+    def score_alignments_device(self, cloud_ptr, n, transforms_ptr, K, dilate=0, weights=ALIGN_DEFAULT_WEIGHTS, origin_voxels=None, center=None):
+        """The same for inputs in device memory, as Gvom.score_alignments_device().  Enqueues and returns: no host wait."""
+        if not cloud_ptr or not transforms_ptr:
+            raise ValueError("cloud_ptr and transforms_ptr must be device addresses")
+        return self._score_alignments(_dev(cloud_ptr), n, _dev(transforms_ptr), K, 1, dilate, weights, origin_voxels, center)
 
     def _raycast(self, from_ptr, K, to_ptr, n, on_device, unknown_blocks, check_target):
         g = self._owner

@@ -1183,8 +1183,8 @@ int gvom_atlas_frontiers(gvom_t *h, int64_t field_id, int32_t min_cells, int32_t
  * diagnostic): poses per kernel launch of the last gvom_voxel_atlas_score_viewpoints, 0 before the first -- what the
  * "viewpoint_bitmap_mb" budget came to.  gvom_device_product(kind 32 / 34 / 36) is
  * GVOM_ERR_INVALID (these calls make them).  Kinds 31, 33 and 35 are not assigned.
- * NOT PROVIDED: stamps or time decay; hit counts; a "near" class and alignment scoring against the atlas; integrating a caller's dense
- * grid; more than one voxel atlas per handle; sharded handles; saving to disk. */
+ * NOT PROVIDED: stamps or time decay; hit counts; a stored "near" plane ("voxel atlas alignment" below derives the class per call);
+ * integrating a caller's dense grid; more than one voxel atlas per handle; sharded handles; saving to disk. */
 #define GVOM_PRODUCT_VOXEL_BOX 32               /* part 0 uint8 [xy, xy, z] class codes; part 1 int32 [4] {occupied, free, outside, seq} */
 #define GVOM_PRODUCT_VOXEL_ATLAS_RAYS 34        /* part 0 int32 [n, 3] {status, steps, unknown}; part 1 float32 [n, 3]; part 2 int32 [n, 3] world voxel */
 #define GVOM_PRODUCT_VOXEL_ATLAS_VIEWPOINTS 36  /* the two parts of kind 18 */
@@ -1200,6 +1200,46 @@ int gvom_voxel_atlas_raycast(gvom_t *h, const float *from /* [K][3] */, int64_t 
                              int on_device, int flags, int64_t extent_voxels[3], int64_t *product_id);
 int gvom_voxel_atlas_score_viewpoints(gvom_t *h, const double *poses /* [K][12] */, int64_t K, int on_device, double max_range,
                                       int32_t stride_h, int32_t stride_w, int flags, int64_t extent_voxels[3], int64_t *product_id);
+
+/* --- voxel atlas alignment (an extension: relocalise on remembered space -- scan alignment scoring against the voxel atlas, for a scan
+ * whose returns end outside the rolling window) ----------------------------------------------------------------------------------------
+ * gvom_score_alignments reads only the current fused map: a scan held against what the vehicle saw a minute ago finds every return
+ * OUTSIDE.  gvom_voxel_atlas_score_alignments holds the cloud against any window-sized BOX of the voxel atlas instead.  Everything is
+ * exact.  An addition: GVOM_ABI_VERSION stays.  gvom_get_tuning "voxel_atlas_alignments" (read-only): 1 -- how a caller probes a library
+ * for this entry point.
+ *
+ * DEFINITION.  gvom_voxel_atlas_score_alignments is gvom_score_alignments' DEFINITION ("scan alignment scoring") word for word, with
+ * three substitutions.
+ * window := the BOX  [Bx, Bx+xy_size) x [By, By+xy_size) x [Bz, Bz+z_size) in world voxels: the size of the mapper's window, at any
+ *            integer origin that gvom_voxel_atlas_box accepts.  A NULL origin means the last integrated window's W, and the call returns
+ *            GVOM_NO_DATA where nothing has been integrated since gvom_voxel_atlas_configure, exactly as the box call does.  The window
+ *            origin of the endpoint rule  floor((double)w / res - W)  becomes B, and OUTSIDE means outside the box.
+ * class of a voxel := a function of the ATLAS alone, never of where the box lies, in this order:  OCCUPIED if the atlas class is
+ *            GVOM_VOXEL_OCCUPIED;  NEAR if dilate == 1 and an occupied voxel OF THE EXTENT lies within one voxel on every axis -- voxels
+ *            outside the box but inside the extent count; voxels outside the extent are NEVER and do not count;  FREE if the atlas class
+ *            is GVOM_VOXEL_FREE;  UNKNOWN otherwise.  A box voxel outside the extent is UNKNOWN.
+ * Everything else is unchanged: the transform rule, the float64 inside test, n, K, the pair and weight limits, the score and the lowest
+ *            index of the best score.  res and the division form are the mapper's.
+ * CONSEQUENCES.  Two boxes give a world voxel the same class.  After ONE integrate into a fresh atlas, with B = W, the result equals
+ * gvom_score_alignments' bit for bit, dilate 1 included: nothing outside the window is known yet.  The call is read-only on the atlas.
+ * It enqueues and returns: the handle knows the extent on the host, so there is no host wait on the device route, and the host route
+ * waits only for its upload.
+ * The product, of kind GVOM_PRODUCT_VOXEL_ATLAS_ALIGNMENT, has the two parts of kind 12: part 0 int32 [K, 6] {score, occupied, near,
+ * free, unknown, outside}, part 1 int32 [4] {best index, best score, n, K}; a snapshot in the product-set pool under its rule.
+ * origin_out (may be NULL) receives B.  The class grid is rebuilt from the atlas's bit planes in every call, in the buffer that
+ * gvom_score_alignments uses ("alignment_grid_bytes"; its allocation counts in "alignment_allocations", the product sets and the host
+ * route's staging buffer in "voxel_atlas_allocations"; neither grows in steady state).  gvom_device_product(kind 38) is
+ * GVOM_ERR_INVALID.  Kind 37 is not assigned.
+ * The refusals are gvom_score_alignments' (GVOM_ERR_INVALID: NULL cloud / transforms / weights / product_id, n < 1, K < 1, dilate other
+ * than 0 or 1, |weight| > 1024;  GVOM_ERR_CAPACITY: n > 2^20, K > 65536, n * K > 2^32, a class grid of 2^32 words or more, every set of
+ * the kind exported) and the voxel atlas calls' (GVOM_ERR_INVALID: a sharded handle, no voxel atlas configured;  GVOM_NO_DATA before the
+ * first combine, and with a NULL origin before the first integrate).
+ * NOT PROVIDED: boxes of other sizes than the window; a cache of the class grid keyed on the atlas's seq; float64 clouds; sharded
+ * handles; a coarse-to-fine search driver. */
+#define GVOM_PRODUCT_VOXEL_ATLAS_ALIGNMENT 38   /* the two parts of kind 12; kind 37 stays unassigned */
+int gvom_voxel_atlas_score_alignments(gvom_t *h, const float *cloud /* [n][3] */, int64_t n, const double *transforms /* [K][3][4] */, int64_t K,
+                                      int on_device, int dilate, const int32_t weights[5], const int64_t origin[3] /* may be NULL */,
+                                      int64_t origin_out[3] /* may be NULL */, int64_t *product_id);
 
 /* --- one map sharded over the GPUs of a node (one rank = one process = one GPU) -------------------
  * No counterpart in the reference (it has no multi-GPU path); semantics = SURVEY 8(e):

@@ -318,6 +318,10 @@ class Cycle(object):
             hold_maps(got, m, label + ": result()")
             hold_dense(self.g, self.mod, m, label + ": result()")
 
+    def P0(self, what):
+        """run_script's two points before the first combine, behind no_data(): for what a subclass attaches to the handle
+        (tests/voxel_atlas_cycle.py: a voxel atlas)"""
+
     def Q(self, label):
         others = [m for m in (self.prev,) if m is not None]
         if self.g is None and self.fresh:
@@ -360,9 +364,11 @@ def run_script(c):
     g, grid = c.g, c.grid
     if g is not None:
         no_data(g, c.mod, grid, "P0")
+    c.P0("P0")
     c.scan(0)
     if g is not None:
         no_data(g, c.mod, grid, "P0, after scan 0")
+    c.P0("P0, after scan 0")
     c.combine("sync", "A"); c.Q("A"); c.keep("A")
     c.scan(1); c.Q("B")
     c.scan(2); c.Q("C")

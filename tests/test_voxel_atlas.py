@@ -7,7 +7,7 @@ atlas, not the mapper.  Tolerance 0 everywhere; float positions are compared thr
   first integrate        on tests/raycast_ref.py's grids a ray that gvom_raycast does not report LEFT_WINDOW has the same answer in the atlas
   remembered space       rays to and between remembered voxels outside the final window; gvom_raycast answers LEFT_WINDOW there
   viewpoints             poses outside and inside the final window; gvom_score_viewpoints' rows after one integrate; the bitmap budget
-  cycle, housekeeping    a scan alone changes nothing an integrate merges; errors, the pool, allocations, clear, free, the largest atlas"""
+  cycle, housekeeping    a scan alone changes nothing an integrate merges (the full cycle: tests/test_voxel_atlas_cycle.py); errors, the pool, allocations, clear, free, the largest atlas"""
 import ctypes
 
 import numpy as np
@@ -278,6 +278,8 @@ def test_after_one_integrate_viewpoints_without_a_beam_that_leaves_equal_the_win
 # ---- 7. the scan cycle -----------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("ring", [1, 2])
 def test_a_scan_changes_what_is_merged_only_after_its_combine(gvom, ring):
+    """one scan that has not been combined, with the referee fed from the handle's own read_dense.  The full cycle -- every point of
+    tests/query_cycle.py's scripts, the referee fed from the CPU oracle's maps alone -- is tests/test_voxel_atlas_cycle.py"""
     grid = "np2"
     xr, zr, xy, zs = rr.GRIDS[grid]
     g = rr.build_map(gvom.Gvom, grid, ring, voxel_statistics=False)

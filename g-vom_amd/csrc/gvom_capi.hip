@@ -175,7 +175,7 @@ static int eager_launch(gvom_handle *h, const ScanParams &P, Slot &st, const int
     FuseParams FP;
     fill_fuse_frame(h, origin, FP);
     FP.nslots = 1; FP.has_prev = prev ? 1 : 0;
-    FP.nz = h->tune_encfuse & 15; FP.cpw = (h->tune_encfuse >> 4) & 1;      // A/B knob (waves per column block, XCD pairing off)
+    FP.nz = h->tune_encfuse & 15; FP.cpw = (h->tune_encfuse >> 4) & 3;      // A/B knob (waves per column block; bit 0 blocks in dispatch order, bit 1 the 16-sx form)
     MapDesc pd;
     memset(&pd, 0, sizeof pd);
     if (prev) {
@@ -185,8 +185,9 @@ static int eager_launch(gvom_handle *h, const ScanParams &P, Slot &st, const int
         pd.d[2] = clamp_delta(origin[2] - prev->origin[2], p.z_size);
         pd.epoch = prev->epoch; pd.tags = prev->tags;
     }
-    int nw, nblocks; size_t row_cap;
-    gvom_encfuse_shape(p.xy_size, p.z_size, FP.nz, &nw, &nblocks, &row_cap);
+    int bw, nw, nblocks; size_t row_cap;
+    gvom_encfuse_shape(p.xy_size, p.z_size, FP.nz | (FP.cpw << 4), &bw, &nw, &nblocks, &row_cap);
+    h->last_encfuse[0] = bw; h->last_encfuse[1] = nw;
     if (row_cap >= 2147483648ull) { h->err = "fused row space exceeds 31 bits"; return GVOM_ERR_CAPACITY; }
     int rc;
     if ((rc = ensure(h, F.rows, row_cap * 16))) return rc;

@@ -960,30 +960,41 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(6, 8))) voi
 // The scan's window IS the fused window (the fused frame is the newest slot's, gvom.py:184), so only the previous
 // map needs the shifted-window test.
 //
-// Workgroup = a QUAD COLUMN BLOCK: 16 sx x 4 storage rows (sy = 4Q .. 4Q+3) x all z, NW waves.  Lane (zl = lane >> 4,
-// p = (lane >> 2) & 3, r = lane & 3) owns the 4 voxels sx = 16 bx + 4 p .. + 3 of row 4Q + r at level 4 (it NW + w) + zl:
-// its quarter of a 4x4 accumulator patch line (a wave instruction = 4 levels x 4 whole lines = 4 x 256 B), 16 bytes
-// of every state array.  A lane owns its 4 COLUMNS for all the levels its wave visits: the column tails are
-// lane-private minima, combined over zl and over the waves once, at the end.  Four workgroups share a 64-voxel tile,
-// so a tile that is live in a source is written and stamped whole by each of them (never "only if it has content").
-// The two workgroups that share the 128-byte lines of the state arrays get neighbouring dispatch slots of ONE XCD
-// (block ids 8 apart; speed only).
+// Workgroup = a QUAD COLUMN BLOCK: BW sx x 4 storage rows (sy = 4Q .. 4Q+3) x all z, NW waves; BW = 32 or 16, one body.
+// A wave instruction covers LV = 64 / BW levels: lane (zl = lane / BW, p = (lane >> 2) & (BW / 4 - 1), r = lane & 3) owns
+// the 4 voxels sx = BW bx + 4 p .. + 3 of row 4Q + r at level LV (it NW + w) + zl: its quarter of a 4x4 accumulator patch
+// line and 16 bytes of every state array.
+//   BW = 32 (xy % 32 == 0): 2 levels x 4 rows = eight WHOLE 128-byte lines of each state array per wave instruction, and
+//     512 contiguous bytes of accumulators per level; two workgroups share a 64-voxel tile; up to 8 waves.  An XCD takes
+//     whole row bands, so the tile-tag lines a band's blocks share are fetched by one L2, not by eight (speed only).
+//   BW = 16 (other xy % 16 == 0 grids; tuning "encfuse" bit 5): 4 levels x 4 rows = sixteen 64-byte HALF lines, 256 bytes
+//     of accumulators per level; four workgroups share a tile; up to 4 waves.  The two workgroups that share the 128-byte
+//     lines of the state arrays get neighbouring dispatch slots of ONE XCD (block ids 8 apart; speed only).
+// On streams that miss the caches half lines move at 3.3-3.4 TB/s, whole lines at 4.85 (profiles/encfuse_lines.txt).
+// A lane owns its 4 COLUMNS for all the levels its wave visits: the column tails are lane-private minima, combined over
+// zl and over the waves once, at the end.  The workgroups that share a tile each write it whole where it is live in a
+// source (never "only if it has content").
 // ------------------------------------------------------------------------------------------
 #define ENCFUSE_MAXIT 8                                    // wave iterations whose tile tags are fetched together
 #define ENCFUSE_LIST 128                                   // per wave: occupied voxels listed before they are settled
-__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(7, 8))) void k_encfuse(
+#define ENCFUSE_MAXW(BW) ((BW) == 32 ? 8 : 4)              // waves per column block at most
+template <int BW, int MAXW>
+__global__ __launch_bounds__(64 * MAXW) __attribute__((amdgpu_waves_per_eu(7, 8))) void k_encfuse(
     const ScanParams P, const FuseParams F, const MapDesc prev, int32_t *flink, uint32_t *hit, uint32_t *total, uint32_t *mh,
     int32_t *state, uint4 *crows, const uint32_t *__restrict__ stags, int32_t *fstate, uint4 *frows, uint32_t *ftags,
     uint32_t *blockcounts, double *height, double *inferred, uint32_t *counters, unsigned long long *host_flag, uint32_t seq)
 {
-    // (per-wave arrays of FOUR: gvom_encfuse_shape never launches more than four waves)
-    __shared__ unsigned long long s_zh[4][WAVE];            // per wave and column: min of (window z << 32 | min-height bits) over occupied voxels
-    __shared__ uint32_t s_zf[4][WAVE];                      // per wave and column: lowest observed-free window z
-    __shared__ uint32_t s_cnt[4];
+    constexpr int LV = WAVE / BW;                           // levels of a wave instruction
+    constexpr int NT = 4 * LV;                              // (level, row) tiles of a wave instruction
+    constexpr int NCOL = 4 * BW;                            // columns of the block, row-major 4 x BW
+    static_assert(MAXW <= ENCFUSE_MAXW(BW), "gvom_encfuse_shape never launches more waves");   // (the per-wave arrays are sized by MAXW)
+    __shared__ unsigned long long s_zh[MAXW][NCOL];         // per wave and column: min of (window z << 32 | min-height bits) over occupied voxels
+    __shared__ uint32_t s_zf[MAXW][NCOL];                   // per wave and column: lowest observed-free window z
+    __shared__ uint32_t s_cnt[MAXW];
     // per wave: the occupied voxels of the levels in hand, one entry each -- storage voxel, accumulator index, the scan's hit and
-    // total there, the previous map's state, {window z | column << 10 | occupied in the scan << 16}
-    __shared__ uint32_t s_eL[4][ENCFUSE_LIST], s_eA[4][ENCFUSE_LIST], s_eh[4][ENCFUSE_LIST], s_et[4][ENCFUSE_LIST], s_em[4][ENCFUSE_LIST];
-    __shared__ int32_t s_ep[4][ENCFUSE_LIST];
+    // total there, the previous map's state, {window z | column << 10 | occupied in the scan << 17}
+    __shared__ uint32_t s_eL[MAXW][ENCFUSE_LIST], s_eA[MAXW][ENCFUSE_LIST], s_eh[MAXW][ENCFUSE_LIST], s_et[MAXW][ENCFUSE_LIST], s_em[MAXW][ENCFUSE_LIST];
+    __shared__ int32_t s_ep[MAXW][ENCFUSE_LIST];
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         // k_trace has completed: {seq, any-in-grid} to the spinning host, as k_encode's first thread does
         const uint32_t any = counters[GVOM_CNT_INGRID] ? 0x80000000u : 0u;
@@ -994,16 +1005,20 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(7, 8))) voi
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int nw = (int)(blockDim.x >> 6);
     const int xy = P.xy, zs = P.zs, nseg = P.nseg;
-    const uint32_t nbx = (uint32_t)xy >> 4;
-    // dispatch slot -> column block: ids b and b + 8 share an XCD (observed round-robin placement), so the two blocks
-    // that split a 32-sx run (the 128-byte lines of state / fstate) are ids 8 apart
+    const uint32_t nbx = (uint32_t)xy / (uint32_t)BW;
+    // dispatch slot -> column block.  16-sx form: ids b and b + 8 share an XCD (observed round-robin placement), so the two
+    // blocks that split a 32-sx run (the 128-byte lines of state / fstate) are ids 8 apart
     uint32_t M = blockIdx.x;
-    if ((gridDim.x & 15u) == 0u && !(F.cpw & 1)) { const uint32_t slot = M >> 3, xcd = M & 7u; M = ((slot >> 1) << 4) + (xcd << 1) + (slot & 1u); }
+    if (BW == 16 && (gridDim.x & 15u) == 0u && !(F.cpw & 1)) { const uint32_t slot = M >> 3, xcd = M & 7u; M = ((slot >> 1) << 4) + (xcd << 1) + (slot & 1u); }
+    // 32-sx form: an XCD takes WHOLE row bands (its slot-th block is block slot % nbx of band 8 (slot / nbx) + xcd).  All the
+    // blocks of a band read the same 128-byte lines of the two tile-tag arrays (8 levels x 4 tile columns each); dealt
+    // round-robin, every XCD's L2 fetched every line: 8 x 2 MB on the 256^3 grid (profiles/encfuse_lines.txt, section 3)
+    if (BW == 32 && ((xy >> 2) & 7) == 0 && !(F.cpw & 1)) { const uint32_t slot = M >> 3, xcd = M & 7u; M = ((slot / nbx) * 8u + xcd) * nbx + slot % nbx; }
     const uint32_t bx = M % nbx, Q = M / nbx;
-    const int zl = lane >> 4, p4 = (lane >> 2) & 3, r = lane & 3;
-    const uint32_t sx0 = bx * 16u + (uint32_t)p4 * 4u, sy = Q * 4u + (uint32_t)r;
-    const uint32_t seg = sx0 >> 6;
-    const uint32_t col0 = (uint32_t)(r * 16 + p4 * 4);      // this lane's first column inside the block (row-major 4 x 16)
+    const int zl = lane / BW, p4 = (lane >> 2) & (BW / 4 - 1), r = lane & 3;
+    const uint32_t sx0 = bx * (uint32_t)BW + (uint32_t)p4 * 4u, sy = Q * 4u + (uint32_t)r;
+    const uint32_t seg = sx0 >> 6;                          // (BW divides 64: the block lies inside one tile column)
+    const uint32_t col0 = (uint32_t)(r * BW + p4 * 4);      // this lane's first column inside the block (row-major 4 x BW)
     const int y = wrap_sub((int)sy, F.om[1], xy);
     const bool has_prev = F.has_prev != 0;
     const int dpx = has_prev ? prev.d[0] : 0, dpy = has_prev ? prev.d[1] : 0, dpz = has_prev ? prev.d[2] : 0;
@@ -1020,12 +1035,13 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(7, 8))) voi
     const gptr_i32 sp = has_prev ? (gptr_i32)prev.state : (gptr_i32)state;
     const gptr_u32 ptags = has_prev ? (gptr_u32)prev.tags : (gptr_u32)stags;
     const gptr_v4u prows = has_prev ? (gptr_v4u)prev.rows : (gptr_v4u)crows;
-    const int niter = (zs + 4 * nw - 1) / (4 * nw);         // wave iterations (4 levels each)
+    const int niter = (zs + LV * nw - 1) / (LV * nw);       // wave iterations (LV levels each)
     // every wave numbers its occupied voxels inside a static range of the fused compact rows (as k_fuse1)
     const uint32_t rbase = (M * (uint32_t)nw + (uint32_t)w) * (uint32_t)(niter * 256);
     uint32_t running = 0, n = 0;
     uint32_t zf[4] = {(uint32_t)INT_MAX, (uint32_t)INT_MAX, (uint32_t)INT_MAX, (uint32_t)INT_MAX};
-    s_zh[w][lane] = ((unsigned long long)INT_MAX << 32) | 0x3f800000ull;      // wave-private until the tail
+#pragma unroll
+    for (int c = lane; c < NCOL; c += WAVE) s_zh[w][c] = ((unsigned long long)INT_MAX << 32) | 0x3f800000ull;   // wave-private until the tail
     // the occupied voxels listed so far, one lane each: the slot's row (k_trace's endpoint blocks left it in the slot's state),
     // the min-height accumulator and the previous map's row in ONE round trip; then the slot's compact row (k_encode's move,
     // gvom.py:1164-1168, 1303-1329), the fused row (gvom.py:910-912) and the fused state
@@ -1039,7 +1055,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(7, 8))) voi
             const uint32_t ei = on ? e : 0u;
             const uint32_t L = s_eL[w][ei], A = s_eA[w][ei], h_ = s_eh[w][ei], t_ = s_et[w][ei], meta = s_em[w][ei];
             const int stp = on ? s_ep[w][ei] : -1;
-            const bool so = on && ((meta >> 16) & 1u);
+            const bool so = on && ((meta >> 17) & 1u);
             const int32_t row_s = state[so ? L : 0u];
             const uint32_t mraw = mh[so ? A : 0u];
             const v4u rp = prows[stp >= 0 ? (uint32_t)stp : 0u];
@@ -1057,7 +1073,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(7, 8))) voi
                 frows[row] = make_uint4(hh, tt, mn, 0u);
                 fstate[L] = (int32_t)row;
                 if (flink) flink[row] = stp;                   // (statistics: which row of the previous map merges into this one, if any)
-                atomicMin(&s_zh[w][(meta >> 10) & 63u], ((unsigned long long)(meta & 1023u) << 32) | mn);   // lowest occupied level wins
+                atomicMin(&s_zh[w][(meta >> 10) & (uint32_t)(NCOL - 1)], ((unsigned long long)(meta & 1023u) << 32) | mn);   // lowest occupied level wins
             }
             running += (uint32_t)__popcll(ob);
         }
@@ -1066,32 +1082,32 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(7, 8))) voi
     };
 
     for (int it0 = 0; it0 < niter; it0 += ENCFUSE_MAXIT) {
-        // tile tags of up to ENCFUSE_MAXIT iterations: lane l < 16 the scan's tag of (level l >> 2, row l & 3), lanes
-        // 16..31 the previous map's; all fetched before the first use
+        // tile tags of up to ENCFUSE_MAXIT iterations: lane l < NT the scan's tag of (level l >> 2, row l & 3), lanes
+        // NT .. 2 NT - 1 the previous map's; all fetched before the first use
         uint32_t tv_[ENCFUSE_MAXIT];
 #pragma unroll
         for (int k = 0; k < ENCFUSE_MAXIT; ++k) {
-            const int szt = ((it0 + k) * nw + w) * 4 + ((lane >> 2) & 3);
-            const bool okt = it0 + k < niter && lane < 32 && szt < zs && (lane < 16 || has_prev);
+            const int szt = ((it0 + k) * nw + w) * LV + ((lane >> 2) & (LV - 1));
+            const bool okt = it0 + k < niter && lane < 2 * NT && szt < zs && (lane < NT || has_prev);
             const uint32_t ti = ((Q * 4u + (uint32_t)(lane & 3)) * (uint32_t)zs + (uint32_t)(okt ? szt : 0)) * (uint32_t)nseg + seg;
-            tv_[k] = okt ? (lane < 16 ? stags[ti] : ptags[ti]) : 0u;
+            tv_[k] = okt ? (lane < NT ? stags[ti] : ptags[ti]) : 0u;
         }
-        // iteration k's mask in lane k: bits 0..15 scan-live (level, row), bits 16..31 the previous map's
+        // iteration k's mask in lane k: bits 0 .. NT - 1 scan-live (level, row), bits NT .. 2 NT - 1 the previous map's
         uint32_t lmv = 0u;
 #pragma unroll
         for (int k = 0; k < ENCFUSE_MAXIT; ++k) {
-            const uint32_t b_ = (uint32_t)__ballot(it0 + k < niter && lane < 32 && tv_[k] != 0u && tv_[k] == (lane < 16 ? P.epoch : prev.epoch));
+            const uint32_t b_ = (uint32_t)__ballot(it0 + k < niter && lane < 2 * NT && tv_[k] != 0u && tv_[k] == (lane < NT ? P.epoch : prev.epoch));
             if (lane == k) lmv = b_;
         }
         const int kend = min(ENCFUSE_MAXIT, niter - it0);
 #pragma unroll 1
         for (int k = 0; k < kend; ++k) {
             const uint32_t m = (uint32_t)__builtin_amdgcn_readlane((int)lmv, k);
-            if (m == 0u) continue;                           // wave-uniform: the 4 levels are dead in both sources
-            const int sz = ((it0 + k) * nw + w) * 4 + zl;
+            if (m == 0u) continue;                           // wave-uniform: the LV levels are dead in both sources
+            const int sz = ((it0 + k) * nw + w) * LV + zl;
             const bool zok = sz < zs;
             const bool live_s = zok && ((m >> (zl * 4 + r)) & 1u);
-            const bool live_p = zok && ((m >> (16 + zl * 4 + r)) & 1u);
+            const bool live_p = zok && ((m >> (NT + zl * 4 + r)) & 1u);
             const uint32_t A0 = acc_idx((int)sx0, (int)sy, zok ? sz : 0, zs, P.sxq);
             const uint32_t L0 = (sy * (uint32_t)zs + (uint32_t)(zok ? sz : 0)) * (uint32_t)xy + sx0;
             // unconditional 16-byte loads (a dead tile reads a valid dummy address): all in flight together
@@ -1142,7 +1158,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(7, 8))) voi
                 for (int i = 0; i < 4; ++i)
                     if (!((occ >> i) & 1u) && c[i] < -1) zf[i] = min(zf[i], (uint32_t)zw);  // gvom.py:551
             }
-            if (__builtin_amdgcn_readfirstlane((int)(__ballot(occ != 0u) != 0ull))) {       // rare: occupied voxels in these 4 levels
+            if (__builtin_amdgcn_readfirstlane((int)(__ballot(occ != 0u) != 0ull))) {       // rare: occupied voxels in these levels
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     const bool o = (occ >> i) & 1u;
@@ -1151,7 +1167,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(7, 8))) voi
                         const uint32_t at = n + (uint32_t)__popcll(bm & lanemask_lt());
                         s_eL[w][at] = L0 + (uint32_t)i; s_eA[w][at] = A0 + (uint32_t)i; s_eh[w][at] = h[i]; s_et[w][at] = t[i];
                         s_ep[w][at] = stp[i];
-                        s_em[w][at] = (uint32_t)zw | ((col0 + (uint32_t)i) << 10) | (((socc >> i) & 1u) << 16);
+                        s_em[w][at] = (uint32_t)zw | ((col0 + (uint32_t)i) << 10) | (((socc >> i) & 1u) << 17);
                     }
                     n += (uint32_t)__popcll(bm);
                     if (n > ENCFUSE_LIST - WAVE) emit();       // the next batch (<= 64 voxels) might not fit
@@ -1161,11 +1177,11 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(7, 8))) voi
     }
     if (n) emit();
 
-    // ---- column tails: over the 4 level groups of the wave (lanes l, l ^ 16, l ^ 32, l ^ 48), then over the waves
+    // ---- column tails: over the LV level groups of the wave (lanes l, l ^ BW, ...), then over the waves
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-        zf[i] = min(zf[i], (uint32_t)__shfl_xor((int)zf[i], 16));
-        zf[i] = min(zf[i], (uint32_t)__shfl_xor((int)zf[i], 32));
+#pragma unroll
+        for (int o = BW; o < WAVE; o <<= 1) zf[i] = min(zf[i], (uint32_t)__shfl_xor((int)zf[i], o));
     }
     if (zl == 0) {
 #pragma unroll
@@ -1178,11 +1194,11 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(7, 8))) voi
         for (int k = 0; k < nw; ++k) tot += s_cnt[k];
         blockcounts[M] = tot;
     }
-    if (w == 0) {                                            // lane = column: row 4Q + (lane >> 4), sx = 16 bx + (lane & 15)
-        const int csx = (int)(bx * 16u) + (lane & 15), csy = (int)(Q * 4u) + (lane >> 4);
+    for (int c = w * WAVE + lane; c < NCOL; c += nw * WAVE) {  // thread = column c: row 4Q + c / BW, sx = BW bx + c % BW
+        const int csx = (int)(bx * (uint32_t)BW) + (c & (BW - 1)), csy = (int)(Q * 4u) + c / BW;
         unsigned long long zhm = ((unsigned long long)INT_MAX << 32) | 0x3f800000ull;
         uint32_t zfm = (uint32_t)INT_MAX;
-        for (int k = 0; k < nw; ++k) { zhm = min(zhm, s_zh[k][lane]); zfm = min(zfm, s_zf[k][lane]); }
+        for (int k = 0; k < nw; ++k) { zhm = min(zhm, s_zh[k][c]); zfm = min(zfm, s_zf[k][c]); }
         const int x = wrap_sub(csx, F.om[0], xy), yy = wrap_sub(csy, F.om[1], xy);
         const int zo = (int)(zhm >> 32), zfi = (int)zfm;
         double hval = -1000.0;
@@ -1276,21 +1292,26 @@ hipError_t gvom_launch_fuse(hipStream_t s, const FuseParams &P, const FuseDescs 
 }
 
 // k_encfuse (one-slot rings; the host has checked xy % 16 == 0, z_size >= 4, the whole grid on this handle): grid = one
-// workgroup per 16-sx x 4-row column block, up to 4 waves of 4 levels per iteration.  Returns the number of workgroups
-// (= entries of blockcounts written) in *nblocks and the fused compact rows the launch may number in *row_cap.
-// nw_override (A/B knob "encfuse", 0: none): fewer waves per column block; the row range follows the shape that is
-// LAUNCHED -- a wave numbers rows from (block * nw + wave) * niter * 256, and nw' * ceil(zs / 4 nw') can exceed the default
-// shape's product (z_size 16: 4 x 1 = 4 against 3 x 2 = 6).
-void gvom_encfuse_shape(int xy, int zs, int nw_override, int *nw, int *nblocks, size_t *row_cap)
+// workgroup per BW-sx x 4-row column block.  The form follows from the grid's shape alone: BW = 32 (whole 128-byte lines of
+// the state arrays, up to 8 waves of 2 levels per iteration) where xy % 32 == 0, else BW = 16 (up to 4 waves of 4 levels).
+// Returns the block width in *bw, the waves per block in *nw, the number of workgroups (= entries of blockcounts written) in
+// *nblocks and the fused compact rows the launch may number in *row_cap.
+// tune (A/B knob "encfuse", 0: none): low 4 bits = fewer waves per column block, bit 4 = blocks in dispatch order (read by the
+// kernel), bit 5 = the 16-sx form everywhere.  The row range follows the shape that is LAUNCHED -- a wave numbers rows from
+// (block * nw + wave) * niter * 256, and nw' * ceil(zs / 4 nw') can exceed the default shape's product (16-sx form, z_size 16:
+// 4 x 1 = 4 against 3 x 2 = 6).
+void gvom_encfuse_shape(int xy, int zs, int tune, int *bw, int *nw, int *nblocks, size_t *row_cap)
 {
-    // 4 waves per block (measured against 8 / 2: m256 98.9 / 100.2 / 102.2 us per step, c2 87.1 / 91.1 / 88.4): at 70 VGPRs a
-    // SIMD holds 7 waves, i.e. 7 four-wave blocks per CU but only 3 eight-wave ones
-    int w = (zs + 3) / 4;
-    if (w > 4) w = 4;
+    // BW = 16, 4 waves per block (measured against 8 / 2: m256 98.9 / 100.2 / 102.2 us per step, c2 87.1 / 91.1 / 88.4): at 70 VGPRs a
+    // SIMD holds 7 waves, i.e. 7 four-wave blocks per CU but only 3 eight-wave ones.  BW = 32: profiles/encfuse_lines.txt
+    const int B = (xy % 32 == 0 && !(tune & 32)) ? 32 : 16;
+    const int lv = 64 / B, nw_override = tune & 15;
+    int w = (zs + lv - 1) / lv;
+    if (w > ENCFUSE_MAXW(B)) w = ENCFUSE_MAXW(B);
     if (w < 1) w = 1;
     if (nw_override > 0 && nw_override <= w) w = nw_override;
-    const int niter = (zs + 4 * w - 1) / (4 * w);
-    *nw = w; *nblocks = (xy / 16) * (xy / 4);
+    const int niter = (zs + lv * w - 1) / (lv * w);
+    *bw = B; *nw = w; *nblocks = (xy / B) * (xy / 4);
     *row_cap = (size_t)*nblocks * (size_t)w * (size_t)niter * 256;
 }
 hipError_t gvom_launch_encfuse(hipStream_t s, const ScanParams &P, const FuseParams &F, const MapDesc &prev, int32_t *flink, uint32_t *hit,
@@ -1298,9 +1319,17 @@ hipError_t gvom_launch_encfuse(hipStream_t s, const ScanParams &P, const FusePar
                                int32_t *fstate, uint4 *frows, uint32_t *ftags, uint32_t *blockcounts, double *height,
                                double *inferred, uint32_t *counters, unsigned long long *host_flag, uint32_t seq)
 {
-    int nw, nblocks; size_t cap;
-    gvom_encfuse_shape(P.xy, P.zs, F.nz, &nw, &nblocks, &cap);   // (F.nz: A/B knob "encfuse"; the caller sized the fused rows with the same call)
-    hipLaunchKernelGGL(k_encfuse, dim3((unsigned)nblocks), dim3(64u * (unsigned)nw), 0, s, P, F, prev, flink, hit, total, mh, state, crows,
-                       stags, fstate, frows, ftags, blockcounts, height, inferred, counters, host_flag, seq);
+    int bw, nw, nblocks; size_t cap;
+    gvom_encfuse_shape(P.xy, P.zs, F.nz | (F.cpw << 4), &bw, &nw, &nblocks, &cap);   // (A/B knob "encfuse"; the caller sized the fused rows with the same call)
+    // (the per-wave LDS arrays follow the waves that are launched: a four-wave block of the 32-sx form holds half of them)
+    if (bw == 32 && nw > 4)
+        hipLaunchKernelGGL((k_encfuse<32, 8>), dim3((unsigned)nblocks), dim3(64u * (unsigned)nw), 0, s, P, F, prev, flink, hit, total, mh, state, crows,
+                           stags, fstate, frows, ftags, blockcounts, height, inferred, counters, host_flag, seq);
+    else if (bw == 32)
+        hipLaunchKernelGGL((k_encfuse<32, 4>), dim3((unsigned)nblocks), dim3(64u * (unsigned)nw), 0, s, P, F, prev, flink, hit, total, mh, state, crows,
+                           stags, fstate, frows, ftags, blockcounts, height, inferred, counters, host_flag, seq);
+    else
+        hipLaunchKernelGGL((k_encfuse<16, 4>), dim3((unsigned)nblocks), dim3(64u * (unsigned)nw), 0, s, P, F, prev, flink, hit, total, mh, state, crows,
+                           stags, fstate, frows, ftags, blockcounts, height, inferred, counters, host_flag, seq);
     return hipGetLastError();
 }

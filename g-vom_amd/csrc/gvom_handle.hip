@@ -566,6 +566,8 @@ VIS int gvom_get_tuning(gvom_t *h, const char *name, int *value)
     if (!strcmp(name, "eager_adopted")) { *value = h->eager_stat[0]; return GVOM_OK; }
     if (!strcmp(name, "eager_dropped")) { *value = h->eager_stat[1]; return GVOM_OK; }
     if (!strcmp(name, "fuse_kernel")) { *value = h->last_fuse; return GVOM_OK; }
+    if (!strcmp(name, "encfuse_width")) { *value = h->last_encfuse[0]; return GVOM_OK; }                // read-only: sx per column block of the last k_encfuse (32 / 16; 0: none yet)
+    if (!strcmp(name, "encfuse_waves")) { *value = h->last_encfuse[1]; return GVOM_OK; }                // read-only: its waves per column block
     if (!strcmp(name, "device_map_sets")) { *value = (int)h->dsets.size(); return GVOM_OK; }             // read-only: allocated device map sets                  // read-only, GVOM_ROUTE_*
     if (!strcmp(name, "clearance_allocations")) { *value = h->cl_allocs; return GVOM_OK; }              // read-only: device allocations gvom_clearance has made
     static const char *const cl_names[4] = {"clearance_lgw", "clearance_rows_per_tile", "clearance_lds_bytes", "clearance_chunks"};

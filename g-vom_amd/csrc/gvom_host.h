@@ -206,7 +206,8 @@ struct gvom_handle {
     uint32_t *dir_hist = nullptr;                       // [3][GVOM_DIRBINS]: two histograms (alternating, zero between uses) + the bins' cursors
     uint32_t dir_flip = 0;
     int last_dirsort = 0;                               // gvom_get_tuning "dirsort": the last scan ran in directional order
-    int tune_encfuse = 0;                               // gvom_set_tuning "encfuse": A/B of k_encfuse's shape (low 4 bits: waves per block, bit 4: no XCD pairing)
+    int tune_encfuse = 0;                               // gvom_set_tuning "encfuse": A/B of k_encfuse's shape (low 4 bits: waves per block, bit 4: blocks in dispatch order, bit 5: the 16-sx form)
+    int last_encfuse[2] = {0, 0};                       // gvom_get_tuning "encfuse_width" / "encfuse_waves": the shape of the last k_encfuse launched
     int tune_fastdiv = -1;                              // gvom_set_tuning "fastdiv": 0 = IEEE divides by the resolutions in k_trace, else the verified reciprocal form
     int fastdiv_ok = 0;                                 // bit 0 / 1: div_by_res() verified for xy_resolution / z_resolution (verify_fastdiv)
     int tune_eager = -1;                                // gvom_set_tuning "eager": 0 off, 1 always, -1 automatic (off after 3 wasted in a row)

@@ -264,7 +264,7 @@ enum { GVOM_ROUTE_FUSE1 = 1, GVOM_ROUTE_FUSE4_2 = 2, GVOM_ROUTE_FUSE4_4 = 3, GVO
 hipError_t gvom_launch_fuse(hipStream_t s, const FuseParams &P, const FuseDescs &KD,
                             const MapDesc *descs_dev, int32_t *fstate, uint4 *frows,
                             uint32_t *ftags, uint32_t *blockcounts, double *height, double *inferred, int *route);
-void gvom_encfuse_shape(int xy, int zs, int nw_override, int *nw, int *nblocks, size_t *row_cap);
+void gvom_encfuse_shape(int xy, int zs, int tune, int *bw, int *nw, int *nblocks, size_t *row_cap);
 // flink (or nullptr): per fused row, the voxel's row in the previous map -- what the statistics merge of this speculative fusion needs
 hipError_t gvom_launch_encfuse(hipStream_t s, const ScanParams &P, const FuseParams &F, const MapDesc &prev, int32_t *flink, uint32_t *hit,
                                uint32_t *total, uint32_t *mh, int32_t *state, uint4 *crows, const uint32_t *stags,

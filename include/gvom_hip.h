@@ -1469,7 +1469,9 @@ int gvom_host_timing(gvom_t *h, double us[8]);
  * 2^23 float32 significands, which gvom_create checks on the host for both resolutions (once per value and process); a
  * resolution that fails the check, float64 clouds and hosts without hardware fma keep the divide.  -1 (default): use it where
  * verified; 0: always divide.  gvom_get_tuning("fastdiv"): bit 0 / 1 = in use for xy_resolution / z_resolution.
- * "encfuse" (A/B of that kernel's shape: low 4 bits waves per column block, bit 4 no XCD pairing), "fuse1" (1: one-slot
+ * "encfuse" (A/B of that kernel's shape: low 4 bits waves per column block, bit 4 blocks in dispatch order -- no XCD per row band
+ * in the 32-sx form, no XCD pairing in the 16-sx one --, bit 5 the 16-sx form on every grid; gvom_get_tuning "encfuse_width" /
+ * "encfuse_waves", read-only: sx and waves per column block of the last k_encfuse launched, 0 before the first), "fuse1" (1: one-slot
  * fusions through the general kernel), "flag_kernel" (1: round 3's completion-flag kernel).
  * "occupancy_clear" (A/B of k_occupancy's dead tile columns: 0, default, the kernel writes every byte of the grid; 1 the grid is
  * cleared with hipMemsetAsync and only tile columns with a live tile are written.  Same grid either way).

@@ -448,7 +448,7 @@ VIS void gvom_destroy(gvom_t *h)
     if (h->x_host) hipHostFree(h->x_host);
     for (auto &s : h->slots) { hipFree(s.state); hipFree(s.code16); hipFree(s.tags); fb(s.crows); fb(s.metrics); fb(s.base); fb(s.rowvox); }
     for (auto &f : h->fused) { hipFree(f.state); hipFree(f.tags); fb(f.rows); fb(f.metrics); }
-    fb(h->in_pts); fb(h->cl_g); fb(h->cl_stage); fb(h->rq_stage); fb(h->ctg_stage); fb(h->ctg_clr); fb(h->fp_tab); fb(h->ro_stage); fb(h->at_tab); fb(h->at_ground); fb(h->at_stage); fb(h->al_grid); fb(h->al_stage); fb(h->fr_stage); fb(h->vp_bitmaps); fb(h->vp_stage); fb(h->pf_tab); fb(h->pf_stage); fb(h->atl_stage); fb(h->af_clr); fb(h->av_tab); fb(h->av_ground); fb(h->av_stage); hipFree(h->atl_mem); hipFree(h->atl_cnt); if (h->atl_pin) hipHostFree(h->atl_pin); fb(h->va_stage); fb(h->va_bitmaps); hipFree(h->va_mem); hipFree(h->va_cnt); if (h->va_pin) hipHostFree(h->va_pin); fb(h->ri_model); fb(h->ri_raw); fb(h->ri_poses); if (h->ri_poses_pin) hipHostFree(h->ri_poses_pin); fb(h->mo_dev); if (h->mo_pin) hipHostFree(h->mo_pin); fb(h->world_pts[0]); fb(h->world_pts[1]); fb(h->flink[0]); fb(h->flink[1]); fb(h->tl); fb(h->dir_keys); fb(h->dir_perm); hipFree(h->dir_hist);
+    fb(h->in_pts); fb(h->cl_g); fb(h->cl_stage); fb(h->rq_stage); fb(h->ctg_stage); fb(h->ctg_clr); fb(h->fp_tab); fb(h->ro_stage); fb(h->at_tab); fb(h->at_ground); fb(h->at_stage); fb(h->al_grid); fb(h->al_stage); fb(h->fr_stage); fb(h->vp_bitmaps); fb(h->vp_stage); fb(h->pf_tab); fb(h->pf_stage); fb(h->atl_stage); fb(h->af_clr); fb(h->av_tab); fb(h->av_ground); fb(h->av_stage); hipFree(h->atl_mem); hipFree(h->atl_cnt); if (h->atl_pin) hipHostFree(h->atl_pin); fb(h->va_stage); fb(h->va_bitmaps); fb(h->va_dist); hipFree(h->va_mem); hipFree(h->va_cnt); if (h->va_pin) hipHostFree(h->va_pin); fb(h->ri_model); fb(h->ri_raw); fb(h->ri_poses); if (h->ri_poses_pin) hipHostFree(h->ri_poses_pin); fb(h->mo_dev); if (h->mo_pin) hipHostFree(h->mo_pin); fb(h->world_pts[0]); fb(h->world_pts[1]); fb(h->flink[0]); fb(h->flink[1]); fb(h->tl); fb(h->dir_keys); fb(h->dir_perm); hipFree(h->dir_hist);
     for (SolveWork *w : {&h->ctg, &h->fr, &h->pf, &h->af, &h->afr}) { fb(w->work); if (w->pin) hipHostFree(w->pin); }   // the calls that wait: work buffer and pinned counters
     hipFree(h->counters); if (h->counters_host) hipHostFree(h->counters_host);
     hipFree(h->descs_dev); if (h->descs_host) hipHostFree(h->descs_host);
@@ -544,6 +544,7 @@ VIS int gvom_set_tuning(gvom_t *h, const char *name, int value)
     else if (!strcmp(name, "pose_field_inner")) h->pf.tune_inner = value < 0 ? 0 : value;      // sweeps a tile makes at most per round (0: 64)
     else if (!strcmp(name, "pose_field_batch")) h->pf.tune_batch = value < 0 ? 0 : (value > GVOM_CTG_MAX_BATCH ? GVOM_CTG_MAX_BATCH : value);   // rounds per look at the counters (0: 8)
     else if (!strcmp(name, "viewpoint_bitmap_mb")) h->tune_vp_mb = value < 0 ? GVOM_VIEWPOINT_DEFAULT_MB : (value > GVOM_VIEWPOINT_MAX_MB ? GVOM_VIEWPOINT_MAX_MB : value);   // megabytes of bitmaps per launch (0: one viewpoint per launch; < 0: the default, 256)
+    else if (!strcmp(name, "voxel_distance_mb")) h->tune_vd_mb = value < 0 ? GVOM_VDIST_DEFAULT_MB : (value > GVOM_VDIST_MAX_MB ? GVOM_VDIST_MAX_MB : value);   // megabytes of halo-grown intermediates a distance field may use (< 0: the default, 256)
     else if (!strcmp(name, "occupancy_clear")) h->tune_occ_clear = value;   // k_occupancy: 1 = clear the grid first, write live tile columns only
     else if (!strcmp(name, "exported")) h->exported = value != 0;       // (set by the peer transport, gvom_comm.hip)
 #ifdef GVOM_HOOKS
@@ -620,6 +621,10 @@ VIS int gvom_get_tuning(gvom_t *h, const char *name, int *value)
     if (!strcmp(name, "voxel_atlas_levels")) { *value = h->va_A ? h->va_Z : 0; return GVOM_OK; }         // read-only: its levels Z
     if (!strcmp(name, "voxel_atlas_allocations")) { *value = h->va_allocs; return GVOM_OK; }             // read-only: device allocations the gvom_voxel_atlas_* calls have made
     if (!strcmp(name, "voxel_atlas_viewpoint_batch")) { *value = h->va_last_batch; return GVOM_OK; }     // read-only: poses per launch of the last gvom_voxel_atlas_score_viewpoints
+    if (!strcmp(name, "voxel_distance_field")) { *value = 1; return GVOM_OK; }                           // read-only: the library has gvom_voxel_atlas_distance_field and gvom_voxel_distance_sample
+    if (!strcmp(name, "voxel_distance_mb")) { *value = h->tune_vd_mb; return GVOM_OK; }
+    if (!strcmp(name, "voxel_distance_halo_xy")) { *value = h->vd_halo[0]; return GVOM_OK; }             // read-only: Hxy of the last gvom_voxel_atlas_distance_field
+    if (!strcmp(name, "voxel_distance_halo_z")) { *value = h->vd_halo[1]; return GVOM_OK; }              // read-only: its Hz
     if (!strcmp(name, "alignment_allocations")) { *value = h->al_allocs; return GVOM_OK; }              // read-only: device allocations gvom_score_alignments has made
     if (!strcmp(name, "alignment_grid_bytes")) { *value = (int)(h->al_grid.bytes > 0x7fffffffu ? 0x7fffffffu : h->al_grid.bytes); return GVOM_OK; }   // read-only: the class grid's allocation
     if (!strcmp(name, "alignment_points_per_block")) { *value = GVOM_ALIGN_PTS_BLOCK; return GVOM_OK; }  // read-only: returns per k_align_score workgroup

@@ -89,6 +89,9 @@ struct DevSet : SetShape {                     // (mem, xy, kind, zs, cap: gvom_
 #define GVOM_VIEWPOINT_MAX_BEAMS ((int64_t)1 << 22)
 #define GVOM_VIEWPOINT_DEFAULT_MB 256
 #define GVOM_VIEWPOINT_MAX_MB 4096
+#define GVOM_VDIST_DEFAULT_MB 256
+#define GVOM_VDIST_MAX_MB 4096
+#define GVOM_VDIST_MAX_POINTS ((int64_t)1 << 26)
 // the frontier labelling's counters (uint32) behind the rounds': [32] frontier cells, [33] kept clusters, [34] clusters dropped by
 // min_cells, [35] frontier cells in kept clusters
 #define FR_CNT_CELLS 32
@@ -426,6 +429,12 @@ struct gvom_handle {
     uint64_t ri_gen = 0, va_model_gen = 0;
     int va_allocs = 0;
     int va_last_batch = 0;                              // poses per launch of the last gvom_voxel_atlas_score_viewpoints ("voxel_atlas_viewpoint_batch", read-only)
+    // VOXEL DISTANCE FIELDS (gvom_voxel_atlas_distance_field): va_dist = the halo-grown intermediates of the x and y passes (gvom_internal.h
+    // VDistFrame), grow-only, counted in va_allocs, at most tune_vd_mb megabytes ("voxel_distance_mb"); vd_halo = {Hxy, Hz} of the last
+    // call ("voxel_distance_halo_xy" / "_z", read-only)
+    Buf va_dist;
+    int tune_vd_mb = GVOM_VDIST_DEFAULT_MB;
+    int vd_halo[2] = {0, 0};
     // ATTITUDE VOLUMES (gvom_attitude_volume): av_tab = what k_volume_attitude_table makes of the footprint table and the chassis --
     // (u - am, v) float64 pairs of every footprint cell, then at av_wcell_at bytes (a multiple of 256) per heading the wheels' cell offsets and the
     // footprint's box, [H][12] int32 --, rebuilt by the first call after a gvom_footprint_set / gvom_chassis_set (fp_gen / at_gen count those; av_fp_gen

@@ -556,6 +556,33 @@ hipError_t gvom_launch_vatlas_raycast(hipStream_t s, const ScanParams &P, const 
 hipError_t gvom_launch_vatlas_viewpoints(hipStream_t s, const ScanParams &P, const ViewQuery &Q, const VAtlas &V, int batch, const int32_t *boxes,
                                          uint32_t *bitmaps, int32_t *rows);
 hipError_t gvom_launch_vatlas_viewpoint_best(hipStream_t s, const ScanParams &P, const ViewQuery &Q, const VAtlas &V, int32_t *rows, int32_t *best);
+// voxel distance fields (gvom_voxel_distance.hip; include/gvom_hip.h "voxel distance field" defines the result).  B = the box as the box
+// kernels take it (n, zs, r*, p*, outside, seq).  The passes in y and z run on the box GROWN by the halo where a source can lie: hby rows
+// below the box, nyg rows in all (>= hby + n); hbz levels below, nzg in all.  kx = 64-bit words the x pass searches on either side, hxy =
+// the y walk's cap; a, b = fl64(resolution^2) of xy and z; cap2 = fl64(max_distance^2); nw = ceil(n / 64).
+#define GVOM_VDIST_MAX_HALO 32767               // the halo of a cap, in voxels: squared offsets and their sums of two stay below 2^32
+struct VDistFrame {
+    VAtlasBox B;
+    int hby, nyg, hbz, nzg;
+    int kx, hxy, nw;
+    int unknown;              // GVOM_DISTANCE_UNKNOWN_BLOCKS: NEVER voxels are sources
+    double a, b, cap2;
+};
+// sample: n points against the field float32 [n][n][zs] of the box whose corner is world voxel `origin`
+struct VDistSample {
+    double xy_res, z_res;
+    double origin[3];
+    int n, zs;
+    int64_t npts;
+};
+size_t gvom_vdist_rows_bytes(const VDistFrame &F);            // the x pass's output; 256-byte aligned behind it:
+size_t gvom_vdist_cols_bytes(const VDistFrame &F);            // the y pass's output
+// work = the two buffers above; out float32 [n][n][zs] metres (+inf beyond the cap); counts int32 [4], words 0 and 1 CLEARED by the caller
+// = {voxels at 0, voxels with a finite distance}, words 2 and 3 = B.outside, B.seq
+hipError_t gvom_launch_vdist_field(hipStream_t s, const VAtlas &V, const VDistFrame &F, void *work, float *out, int32_t *counts);
+// out float32 [npts] = the field at the voxel of every point, NaN outside the box or where a coordinate is not finite; counts int32 [4]
+// CLEARED by the caller = {inside the box, of those finite, of those 0, npts}
+hipError_t gvom_launch_vdist_sample(hipStream_t s, const VDistSample &Q, const float *pts, const float *field, float *out, int32_t *counts);
 // storage order [sy][sx] -> reference order [x][y] (window coordinates)
 hipError_t gvom_launch_unwrap_f64(hipStream_t s, int xy, int om0, int om1, const double *in, int in_stride, double *out_xy);
 hipError_t gvom_launch_posdens(hipStream_t s, const Map2dParams &P, const int32_t *fstate,

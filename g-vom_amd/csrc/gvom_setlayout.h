@@ -46,6 +46,10 @@
 //                    stop); cap = the rays of the call that wrote it.  Kind 33 is not assigned
 //   atlas viewpoints (36)  the two parts of viewpoints (18).  Kind 35 is not assigned
 //   atlas alignment (38)   the two parts of alignment (12).  Kind 37 is not assigned
+//   voxel distance (40)    xy*xy*zs floats, out[x][y][z] like the voxel box: metres to the nearest source, +inf beyond the cap; then 4 int32
+//                    {voxels at 0, voxels with a finite distance, outside the extent, seq}.  Kind 39 is not assigned
+//   distance samples (42)  cap floats (the field at the voxel of every point, NaN outside its box), then 4 int32 {inside the box, of those
+//                    finite, of those 0, n}; cap = the points of the call that wrote it.  Kind 41 is not assigned
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -96,6 +100,8 @@ inline size_t set_bytes(int kind, int xy, int zs, int64_t cap, int64_t cols = 0)
     case GVOM_PRODUCT_VOXEL_ATLAS_RAYS: return 2 * align256((size_t)cap * 12) + (size_t)cap * 12;
     case GVOM_PRODUCT_VOXEL_ATLAS_VIEWPOINTS: return align256((size_t)cap * 32) + 16;
     case GVOM_PRODUCT_VOXEL_ATLAS_ALIGNMENT: return align256((size_t)cap * 24) + 16;
+    case GVOM_PRODUCT_VOXEL_DISTANCE: return align256(n2 * zs * 4) + 16;
+    case GVOM_PRODUCT_VOXEL_DISTANCE_SAMPLES: return align256((size_t)cap * 4) + 16;
     }
     return 0;
 }
@@ -245,6 +251,20 @@ inline bool set_part(const SetShape *s, int part, SetPart *d)
         if (part < 0 || part > 2) return false;
         rows(s->mem + (size_t)part * align256((size_t)s->cap * 12), s->cap, 3);
         if (part != 1) d->code = kDLInt;
+        break;
+    case GVOM_PRODUCT_VOXEL_DISTANCE:
+        if (part == 0) {
+            d->ptr = s->mem; d->ndim = 3;
+            d->shape[0] = d->shape[1] = xy; d->shape[2] = s->zs;
+            d->strides[0] = xy * s->zs; d->strides[1] = s->zs; d->strides[2] = 1;
+        }
+        else if (part == 1) { d->ptr = s->mem + align256((size_t)n2 * s->zs * 4); d->ndim = 1; d->shape[0] = 4; d->strides[0] = 1; d->shape[1] = d->strides[1] = 1; d->code = kDLInt; }
+        else return false;
+        break;
+    case GVOM_PRODUCT_VOXEL_DISTANCE_SAMPLES:
+        if (part == 0) { d->ptr = s->mem; d->ndim = 1; d->shape[0] = s->cap; d->strides[0] = 1; d->shape[1] = d->strides[1] = 1; }
+        else if (part == 1) { d->ptr = s->mem + align256((size_t)s->cap * 4); d->ndim = 1; d->shape[0] = 4; d->strides[0] = 1; d->shape[1] = d->strides[1] = 1; d->code = kDLInt; }
+        else return false;
         break;
     default: return false;
     }

@@ -175,6 +175,18 @@ int64_t pose_box(const gvom_handle *h, const double *c, double max_range, int32_
     }
     return bits;
 }
+
+// THE HALO OF A CAP: the largest h with fl64(c * (double)(h * h)) <= cap2 -- a source further away on the axis cannot be within the cap --
+// in the arithmetic of the distance itself; GVOM_VDIST_MAX_HALO + 1 where it is larger than that.  The float64 root is a first guess only
+int64_t distance_halo(double c, double cap2)
+{
+    const double guess = sqrt(cap2 / c);
+    if (!(guess < (double)(GVOM_VDIST_MAX_HALO + 1))) return GVOM_VDIST_MAX_HALO + 1;
+    int64_t h = (int64_t)guess;
+    while (c * (double)((h + 1) * (h + 1)) <= cap2) ++h;
+    while (h > 0 && c * (double)(h * h) > cap2) --h;
+    return h;
+}
 }  // namespace
 
 extern "C" {
@@ -508,6 +520,105 @@ VIS int gvom_voxel_atlas_score_alignments(gvom_t *h, const float *cloud, int64_t
     HIPCHK(h, gvom_launch_align_grid(h->stream, P, cdev, tdev, grid, part_ptr<int32_t>(set, 0), part_ptr<int32_t>(set, 1)));
     for (int k = 0; k < 3; ++k) set->origin[k] = B[k];
     for (int k = 0; origin_out && k < 3; ++k) origin_out[k] = B[k];
+    return product_publish(h, set, product_id);
+}
+
+// The distance field of the box at B (include/gvom_hip.h "voxel distance field"): the three passes of gvom_voxel_distance.hip on the
+// handle's stream, behind the integrates before the call; read-only on the atlas.  The halos are the host's to compute, in the
+// definition's own arithmetic; the passes in y and z run on the box grown by them, clipped to where a source can lie -- the extent, one
+// voxel further under the flag (everything outside is a source there, and the nearest such voxel on an axis is the first one), never
+// less than the box itself.  Enqueues and returns.
+VIS int gvom_voxel_atlas_distance_field(gvom_t *h, const int64_t origin[3], double max_distance, int flags, int64_t *product_id, int64_t origin_out[3])
+{
+    if (!h || !product_id) return GVOM_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(h->mu);
+    *product_id = -1;
+    const char *const fn = "gvom_voxel_atlas_distance_field";
+    int rc = need_atlas(h, fn);
+    if (rc) return rc;
+    if (!std::isfinite(max_distance) || !(max_distance > 0.0)) return refuse(h, fn, "max_distance must be finite and > 0");
+    if (flags & ~GVOM_DISTANCE_UNKNOWN_BLOCKS) return refuse(h, fn, "unknown flag bits");
+    if (!h->has_combined || (!origin && h->va_seq == 0)) return GVOM_NO_DATA;     // (NULL: the last integrated window, and there is none yet)
+    const int64_t B[3] = {origin ? origin[0] : h->va_last[0], origin ? origin[1] : h->va_last[1], origin ? origin[2] : h->va_last[2]};
+    const int xy = h->prm.xy_size, zs = h->prm.z_size;
+    VDistFrame F;
+    memset(&F, 0, sizeof F);
+    F.a = h->prm.xy_resolution * h->prm.xy_resolution; F.b = h->prm.z_resolution * h->prm.z_resolution;
+    F.cap2 = max_distance * max_distance;
+    if (!std::isfinite(F.cap2) || !(F.a > 0.0) || !(F.b > 0.0)) return refuse(h, fn, "max_distance squared is not finite", GVOM_ERR_CAPACITY);
+    const int64_t hxy = distance_halo(F.a, F.cap2), hz = distance_halo(F.b, F.cap2);
+    if (hxy > GVOM_VDIST_MAX_HALO || hz > GVOM_VDIST_MAX_HALO) return refuse(h, fn, "max_distance reaches further than 32767 voxels", GVOM_ERR_CAPACITY);
+    F.B.outside = (int)((int64_t)xy * xy * zs - box_frame(h, B, F.B));
+    F.B.seq = (int)std::min<int64_t>(h->va_seq, INT32_MAX);
+    F.unknown = (flags & GVOM_DISTANCE_UNKNOWN_BLOCKS) ? 1 : 0;
+    F.hxy = (int)hxy; F.kx = (int)((hxy + 63) / 64) + 1; F.nw = (xy + 63) / 64;
+    // rows of the extent (and the one beyond it) below and above the box, as far as the halo reaches: (r + f) below, (size + f) - (r + n) above
+    auto grown = [&](int r, int n, int size, int64_t halo, int *below, int *all) {
+        const int64_t e0 = -(int64_t)r - F.unknown, e1 = (int64_t)size + F.unknown - r;   // where a source can lie, in box coordinates: [e0, e1)
+        const int64_t lo = e1 > -halo ? std::max<int64_t>(0, std::min<int64_t>(halo, -e0)) : 0;
+        const int64_t hi = e0 < n + halo ? std::max<int64_t>(0, std::min<int64_t>(halo, e1 - n)) : 0;
+        *below = (int)lo; *all = (int)(lo + n + hi);
+    };
+    grown(F.B.ry, xy, h->va_A, hxy, &F.hby, &F.nyg);
+    grown(F.B.rz, zs, h->va_Z, hz, &F.hbz, &F.nzg);
+    const size_t rows_bytes = align256(gvom_vdist_rows_bytes(F)), work_bytes = rows_bytes + gvom_vdist_cols_bytes(F);
+    if (work_bytes > ((size_t)h->tune_vd_mb << 20))
+        return refuse(h, fn, "the working buffers of this cap need " + std::to_string((work_bytes >> 20) + 1) + " MB, more than \"voxel_distance_mb\" allows", GVOM_ERR_CAPACITY);
+    HIPCHK(h, hipSetDevice(h->device));
+    DevSet *set = nullptr;
+    const size_t bytes = set_bytes(GVOM_PRODUCT_VOXEL_DISTANCE, xy, zs, 0);
+    if ((rc = product_acquire(h, GVOM_PRODUCT_VOXEL_DISTANCE, bytes, bytes, fn, &h->va_allocs, &set))) return rc;
+    HIPCHK(h, join_second_stream(h));
+    if (h->va_dist.bytes < work_bytes) HIPCHK(h, hipStreamSynchronize(h->stream));         // the passes that still run on the buffer it outgrows
+    if ((rc = stage_buf(h, h->va_dist, work_bytes, h->va_allocs))) return rc;
+    if ((rc = set_wait_releases(h, set))) return rc;
+    int32_t *counts = part_ptr<int32_t>(set, 1);
+    HIPCHK(h, hipMemsetAsync(counts, 0, 16, h->stream));
+    HIPCHK(h, gvom_launch_vdist_field(h->stream, atlas_of(h), F, h->va_dist.p, part_ptr<float>(set, 0), counts));
+    h->vd_halo[0] = (int)hxy; h->vd_halo[1] = (int)hz;
+    for (int k = 0; k < 3; ++k) set->origin[k] = B[k];
+    for (int k = 0; origin_out && k < 3; ++k) origin_out[k] = B[k];
+    return product_publish(h, set, product_id);
+}
+
+// The field of a live distance product gathered at n world points by k_vdist_sample, on the handle's stream: behind the passes that
+// wrote the field and in front of whatever reuses its set.  Enqueues and returns (the host route waits for its upload).
+VIS int gvom_voxel_distance_sample(gvom_t *h, int64_t field_product_id, const float *points, int64_t n, int on_device, int64_t *product_id)
+{
+    if (!h || !product_id) return GVOM_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(h->mu);
+    *product_id = -1;
+    const char *const fn = "gvom_voxel_distance_sample";
+    int rc;
+    if (h->sharded) return refuse(h, fn, "sharded handles are not supported");
+    if (!points) return refuse(h, fn, "points must not be NULL");
+    if (n < 1) return refuse(h, fn, "n must be at least 1");
+    if (n > GVOM_VDIST_MAX_POINTS) return refuse(h, fn, "more than 2^26 points in one call", GVOM_ERR_CAPACITY);
+    DevSet *const f = find_set(h->psets, field_product_id);
+    if (!f || f->kind != GVOM_PRODUCT_VOXEL_DISTANCE) return refuse(h, fn, "unknown or stale distance field id");
+    HIPCHK(h, hipSetDevice(h->device));
+    DevSet *set = nullptr;
+    const size_t bytes = set_bytes(GVOM_PRODUCT_VOXEL_DISTANCE_SAMPLES, 0, 0, n);
+    if ((rc = product_acquire(h, GVOM_PRODUCT_VOXEL_DISTANCE_SAMPLES, bytes, bytes, fn, &h->va_allocs, &set))) return rc;
+    set->cap = n;
+    const float *pdev = points;
+    HIPCHK(h, join_second_stream(h));
+    if (!on_device) {                                                       // host points: staged, and up before the call returns
+        const HostPart parts[1] = {{points, (size_t)n * 12}};
+        const void *dev[1];
+        if ((rc = stage_host(h, h->va_stage, h->va_allocs, parts, 1, true, dev))) return rc;
+        pdev = (const float *)dev[0];
+    }
+    if ((rc = set_wait_releases(h, set))) return rc;
+    VDistSample Q;
+    memset(&Q, 0, sizeof Q);
+    Q.xy_res = h->prm.xy_resolution; Q.z_res = h->prm.z_resolution;
+    for (int k = 0; k < 3; ++k) Q.origin[k] = (double)f->origin[k];
+    Q.n = f->xy; Q.zs = f->zs; Q.npts = n;
+    int32_t *counts = part_ptr<int32_t>(set, 1);
+    HIPCHK(h, hipMemsetAsync(counts, 0, 16, h->stream));
+    HIPCHK(h, gvom_launch_vdist_sample(h->stream, Q, pdev, part_ptr<const float>(f, 0), part_ptr<float>(set, 0), counts));
+    for (int k = 0; k < 3; ++k) set->origin[k] = f->origin[k];
     return product_publish(h, set, product_id);
 }
 }  // extern "C"

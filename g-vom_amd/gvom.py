@@ -194,6 +194,8 @@ ABI = [
     ("gvom_voxel_atlas_score_viewpoints", _I, [_P, _P, _I64, _I, ctypes.c_double, ctypes.c_int32, ctypes.c_int32, _I, ctypes.POINTER(_I64),
                                                ctypes.POINTER(_I64)]),
     ("gvom_voxel_atlas_score_alignments", _I, [_P, _P, _I64, _P, _I64, _I, _I, _P, ctypes.POINTER(_I64), ctypes.POINTER(_I64), ctypes.POINTER(_I64)]),
+    ("gvom_voxel_atlas_distance_field", _I, [_P, ctypes.POINTER(_I64), ctypes.c_double, _I, ctypes.POINTER(_I64), ctypes.POINTER(_I64)]),
+    ("gvom_voxel_distance_sample", _I, [_P, _I64, _P, _I64, _I, ctypes.POINTER(_I64)]),
     ("gvom_set_profiling", _I, [_P, _I]),
     ("gvom_host_timing", _I, [_P, ctypes.POINTER(ctypes.c_double * 8)]),
     ("gvom_set_tuning", _I, [_P, ctypes.c_char_p, _I]),
@@ -626,6 +628,8 @@ PRODUCT_VOXEL_BOX = 32                    # GVOM_PRODUCT_VOXEL_BOX: made by gvom
 PRODUCT_VOXEL_ATLAS_RAYS = 34             # GVOM_PRODUCT_VOXEL_ATLAS_RAYS: made by gvom_voxel_atlas_raycast (kind 33 is not assigned)
 PRODUCT_VOXEL_ATLAS_VIEWPOINTS = 36       # GVOM_PRODUCT_VOXEL_ATLAS_VIEWPOINTS: made by gvom_voxel_atlas_score_viewpoints (kind 35 is not assigned)
 PRODUCT_VOXEL_ATLAS_ALIGNMENT = 38        # GVOM_PRODUCT_VOXEL_ATLAS_ALIGNMENT: made by gvom_voxel_atlas_score_alignments (kind 37 is not assigned)
+PRODUCT_VOXEL_DISTANCE = 40               # GVOM_PRODUCT_VOXEL_DISTANCE: made by gvom_voxel_atlas_distance_field (kind 39 is not assigned)
+PRODUCT_VOXEL_DISTANCE_SAMPLES = 42       # GVOM_PRODUCT_VOXEL_DISTANCE_SAMPLES: made by gvom_voxel_distance_sample (kind 41 is not assigned)
 # element type of part k of a product, by kind (what set_part() of csrc/gvom_setlayout.h gives as DLPack code and bits)
 _PRODUCT_DTYPES = {PRODUCT_OCCUPANCY: (np.uint8,), PRODUCT_VOXEL_CLOUD: (np.float32, np.float32, np.int64),
                    PRODUCT_HEIGHT_CLOUD: (np.float32,), PRODUCT_INFERRED_HEIGHT_CLOUD: (np.float32,),
@@ -639,7 +643,8 @@ _PRODUCT_DTYPES = {PRODUCT_OCCUPANCY: (np.uint8,), PRODUCT_VOXEL_CLOUD: (np.floa
                    PRODUCT_ATLAS_FRONTIERS: (np.int32, np.int64, np.int32, np.int32),
                    PRODUCT_ATTITUDE_VOLUME: (np.uint8, np.uint8, np.int32),
                    PRODUCT_VOXEL_BOX: (np.uint8, np.int32), PRODUCT_VOXEL_ATLAS_RAYS: (np.int32, np.float32, np.int32),
-                   PRODUCT_VOXEL_ATLAS_VIEWPOINTS: (np.int32, np.int32), PRODUCT_VOXEL_ATLAS_ALIGNMENT: (np.int32, np.int32)}
+                   PRODUCT_VOXEL_ATLAS_VIEWPOINTS: (np.int32, np.int32), PRODUCT_VOXEL_ATLAS_ALIGNMENT: (np.int32, np.int32),
+                   PRODUCT_VOXEL_DISTANCE: (np.float32, np.int32), PRODUCT_VOXEL_DISTANCE_SAMPLES: (np.float32, np.int32)}
 CLEARANCE_FAR = 2147483647                # GVOM_CLEARANCE_FAR: squared_cells where no obstacle is in reach
 _CLEARANCE_NO_NEGATIVE = 1                # GVOM_CLEARANCE_NO_NEGATIVE
 
@@ -2182,6 +2187,99 @@ class DeviceAtlasAlignments(DeviceAlignments):
         self.origin_voxels = origin_voxels
 
 
+_DISTANCE_UNKNOWN_BLOCKS = 1              # GVOM_DISTANCE_UNKNOWN_BLOCKS
+DISTANCE_MAX_POINTS = 1 << 26
+DISTANCE_MAX_HALO = 32767                 # voxels a cap may reach on an axis
+
+
+def distance_halo(max_distance, resolution):
+    """The halo of a cap on an axis of `resolution` metres per voxel, as the library computes it: the largest h with
+    fl64(a * (double)(h*h)) <= fl64(max_distance * max_distance), a = fl64(resolution * resolution) -- a source further away on that
+    axis cannot be within the cap (include/gvom_hip.h "voxel distance field")."""
+    a, cap2 = float(resolution) * float(resolution), float(max_distance) * float(max_distance)
+    h = int(math.sqrt(cap2 / a))
+    while a * float((h + 1) * (h + 1)) <= cap2:
+        h += 1
+    while h > 0 and a * float(h * h) > cap2:
+        h -= 1
+    return h
+
+
+def _distance_cap(max_distance, xy_resolution, z_resolution):
+    """max_distance of VoxelAtlas.distance_field() as a float: ValueError for NaN, infinite and non-positive values and for less
+    than the finer of the two resolutions (a field that could only read 0 or +inf)."""
+    try:
+        d = float(max_distance)
+    except (TypeError, ValueError):
+        raise ValueError("max_distance must be a finite distance > 0 in metres, got %r" % (max_distance,))
+    if d != d or d <= 0 or d == float("inf"):
+        raise ValueError("max_distance must be a finite distance > 0 in metres, got %r" % (max_distance,))
+    finer = min(float(xy_resolution), float(z_resolution))
+    if d < finer:
+        raise ValueError("max_distance must be at least one voxel of the finer resolution (%r m), got %r" % (finer, max_distance))
+    return d
+
+
+class DeviceDistanceSamples(_ProductView):
+    """The result of DeviceDistanceField.sample() / sample_device(): `.distance` float32 [n], the field's value at the voxel of every
+    point (NaN where the voxel lies outside the field's box or a coordinate is not finite), and `.counts` int32 [4] {points inside
+    the box, of those finite, of those at 0, n}: two DeviceArrays of one product.  A snapshot.  copy_to_host() returns (distance,
+    counts)."""
+
+    def __init__(self, hold):
+        _ProductView.__init__(self, hold)
+        self.distance, self.counts = DeviceArray(hold, 0), DeviceArray(hold, 1)
+
+    def copy_to_host(self):
+        return self.distance.copy_to_host(), self.counts.copy_to_host()
+
+
+class DeviceDistanceField(_ProductView):
+    """The result of VoxelAtlas.distance_field(): `.distance` float32 [xy, xy, z] in the class grid's layout -- metres from the
+    voxel's centre to the centre of the nearest source voxel anywhere in the atlas's extent, 0 at a source, +inf beyond
+    `.max_distance` -- and `.counts` int32 [4] {voxels at 0, voxels with a finite distance, voxels outside the extent, seq}: two
+    DeviceArrays of one product.  `.origin_voxels`: the box's corner in world voxels; the field lines up voxel for voxel with
+    VoxelAtlas.box() at the same origin.  A snapshot.  DLPack hands over `.distance`; copy_to_host() returns (distance, counts)."""
+
+    def __init__(self, hold, origin_voxels, max_distance):
+        _ProductView.__init__(self, hold)
+        self.origin_voxels, self.max_distance = origin_voxels, max_distance
+        self.distance, self.counts = DeviceArray(hold, 0), DeviceArray(hold, 1)
+
+    def copy_to_host(self):
+        return self.distance.copy_to_host(), self.counts.copy_to_host()
+
+    def __dlpack_device__(self):
+        return self.distance.__dlpack_device__()
+
+    def __dlpack__(self, stream=None, max_version=None, dl_device=None, copy=None):
+        return self.distance.__dlpack__(stream=stream, max_version=max_version, dl_device=dl_device, copy=copy)
+
+    def _sample(self, points_ptr, n, on_device):
+        g = self._hold._owner
+        n = int(n)
+        if n < 1 or n > DISTANCE_MAX_POINTS:
+            raise ValueError("between 1 and 2**26 points per call, got %d" % n)
+        hold = g._make_product(lambda pid: g._lib.gvom_voxel_distance_sample(g._h, self.product_id, points_ptr, n, int(on_device), pid),
+                               PRODUCT_VOXEL_DISTANCE_SAMPLES, g._check_args)
+        return DeviceDistanceSamples(hold)
+
+    def sample(self, points):
+        """The field at the voxels of world points float32 [n, 3] in metres -- floor(p / resolution) per axis, no interpolation: a
+        DeviceDistanceSamples.  A body sphere of radius r at p is clear of every source where sample(p) >= r + the voxel's half
+        diagonal.  Waits only for the upload of the points."""
+        p = np.ascontiguousarray(np.asarray(points), dtype=np.float32)
+        if p.ndim != 2 or p.shape[1] != 3 or p.shape[0] < 1:
+            raise ValueError("points must have shape (n, 3) with n >= 1, got %r" % (p.shape,))
+        return self._sample(_ptr(p), p.shape[0], 0)
+
+    def sample_device(self, points_ptr, n):
+        """The same for n points float32 [n, 3] in device memory.  Enqueues and returns: no host wait."""
+        if not points_ptr:
+            raise ValueError("points_ptr must be a device address")
+        return self._sample(_dev(points_ptr), n, 1)
+
+
 class VoxelAtlas(object):
     """The voxel atlas of a mapper (Gvom.create_voxel_atlas): a world-fixed, toroidally stored memory of the voxels' classes --
     never observed, observed free, occupied -- `cells` x `cells` x `levels` voxels at 2 bits each, that keeps what the rolling window
@@ -2226,6 +2324,22 @@ class VoxelAtlas(object):
         out = (_I64 * 3)()
         hold = g._make_product(lambda pid: g._lib.gvom_voxel_atlas_box(g._h, org, pid, out), PRODUCT_VOXEL_BOX, g._check_args)
         return None if hold is None else DeviceVoxelBox(hold, tuple(int(v) for v in out))
+
+    def distance_field(self, max_distance, origin_voxels=None, center=None, unknown_blocks=False):
+        """The exact 3-D clearance of a window-sized part of the atlas, truncated at max_distance metres: a DeviceDistanceField whose
+        `.distance` float32 [xy, xy, z] is, per voxel, the Euclidean distance in metres (xy_resolution in x and y, z_resolution in z,
+        voxel centre to voxel centre) to the nearest remembered OCCUPIED voxel -- anywhere in the extent, not only in the box --, 0 at
+        such a voxel and +inf where none lies within max_distance.  unknown_blocks=True: never-observed voxels are sources too,
+        everything outside the extent among them.  The box as for box(): origin_voxels, or the window of a scan with its ego at
+        `center`; default: the last integrated window.  None where box() returns None.  ValueError for a cap that is not a finite
+        distance > 0 or lies below the finer of the two resolutions.  No host wait."""
+        g = self._owner
+        cap = _distance_cap(max_distance, g.xy_resolution, g.z_resolution)
+        org = self._box_origin(origin_voxels, center)
+        out = (_I64 * 3)()
+        flags = _DISTANCE_UNKNOWN_BLOCKS if unknown_blocks else 0
+        hold = g._make_product(lambda pid: g._lib.gvom_voxel_atlas_distance_field(g._h, org, cap, flags, pid, out), PRODUCT_VOXEL_DISTANCE, g._check_args)
+        return None if hold is None else DeviceDistanceField(hold, tuple(int(v) for v in out), cap)
 
     def _box_origin(self, origin_voxels, center):
         """the corner of a window-sized box as the library takes it: origin_voxels, or the window of a scan with its ego at `center`,

@@ -1241,6 +1241,57 @@ int gvom_voxel_atlas_score_alignments(gvom_t *h, const float *cloud /* [n][3] */
                                       int on_device, int dilate, const int32_t weights[5], const int64_t origin[3] /* may be NULL */,
                                       int64_t origin_out[3] /* may be NULL */, int64_t *product_id);
 
+/* --- voxel distance field (an extension: exact 3-D clearance from the voxel atlas -- how far every voxel of a box is from the nearest
+ * remembered obstacle, under overhangs that a 2-D column reduction flattens away) ---------------------------------------------------------
+ * gvom_clearance is the distance transform of the 2-D obstacle mask; the 3-D side answered only "what class is this voxel" and "where
+ * does this ray stop".  gvom_voxel_atlas_distance_field gives the truncated Euclidean distance field of a window-sized box of the voxel
+ * atlas, in metres, exact under the definition below; gvom_voxel_distance_sample reads such a field at world points (body spheres, scan
+ * returns).  An addition: GVOM_ABI_VERSION stays.  gvom_get_tuning "voxel_distance_field" (read-only): 1 -- how a caller probes a
+ * library for these entry points.
+ *
+ * BOX.  [Bx, Bx+xy_size) x [By, By+xy_size) x [Bz, Bz+z_size) in world voxels, at any integer origin that gvom_voxel_atlas_box accepts.
+ * A NULL origin means the last integrated window's W; GVOM_NO_DATA exactly where gvom_voxel_atlas_box returns it.  Part 0 has the
+ * class grid's layout, out[x][y][z]: it lines up voxel for voxel with the box call's classes and with the occupancy grid.
+ * SOURCES.  Every world voxel whose atlas class is GVOM_VOXEL_OCCUPIED; with GVOM_DISTANCE_UNKNOWN_BLOCKS also every voxel whose class
+ * is GVOM_VOXEL_NEVER.  A voxel outside the extent is NEVER, as for the box call: under the flag everything outside the extent is a
+ * source.  Sources are NOT restricted to the box: a remembered obstacle just beyond a face of the box decides the distances near it.
+ * VALUE.  For a box voxel v,
+ *     d2(v) = min over sources s of  fl64( fl64(a * n) + fl64(b * m) ),   n = (sx-vx)^2 + (sy-vy)^2,  m = (sz-vz)^2,
+ * n and m exact integers converted to double,  a = fl64(xy_resolution * xy_resolution),  b = fl64(z_resolution * z_resolution), from
+ * the handle's double parameters, no contraction.  out(v) = (float)sqrt(d2) -- a float64 root, rounded once to float32 -- where
+ * d2 <= cap2 = fl64(max_distance * max_distance), else +infinity.  Distances run between voxel centres; a source voxel reads 0.
+ * max_distance is mandatory, finite and > 0: the field is truncated.
+ * EXACTNESS.  The result inside the box is exact with respect to the WHOLE extent: a source further than the halo on an axis cannot be
+ * within the cap.  Hxy = the largest h with fl64(a * (double)(h*h)) <= cap2, Hz the same with b; the host computes both in exactly
+ * this arithmetic ("voxel_distance_halo_xy" / "voxel_distance_halo_z", read-only: those of the last call).  Both terms are monotone in
+ * |dx|, |dy| and |dz| and fl64 is monotone, so the minimum commutes with a separable evaluation -- integer passes in x and y that give
+ * n_min per level, then a float64 pass over fl64(a * n_min(dz)) + fl64(b * dz^2) -- and the minimum of a set of doubles is unique even
+ * where the nearest source is not: the result does not depend on the schedule.
+ * COUNTS.  Part 1, int32 [4]: voxels at distance 0; voxels with a finite distance; box voxels outside the extent; the atlas's seq.
+ * SAMPLE.  gvom_voxel_distance_sample takes a live product of kind GVOM_PRODUCT_VOXEL_DISTANCE of this handle and n world points in
+ * metres, float32 [n][3], 1 <= n <= 2^26, in host memory or (on_device) in device memory.  The voxel of a point is
+ * floor((double)p / resolution) per axis, a float64 division.  Part 0, float32 [n]: the field's value at that voxel; NaN where the voxel
+ * lies outside the field's box or a coordinate is not finite.  Part 1, int32 [4]: {points inside the box, of those finite, of those at
+ * 0, n}.  Read-only on the field; the gather runs on the handle's stream, in front of whatever reuses the field's set later, so the
+ * caller may release the field as soon as the call returns (as gvom_score_rollouts treats its cost field).
+ *
+ * Neither call waits for the GPU (the host route of the sample call waits for its upload).  GVOM_ERR_INVALID: a sharded handle; no voxel
+ * atlas configured; NULL product_id; a NaN, non-positive or infinite max_distance; unknown flag bits; NULL points; n < 1; a
+ * field_product_id that is not a live product of kind 40 of this handle.  GVOM_ERR_CAPACITY, with the handle unchanged: a halo of more
+ * than 32767 voxels; n > 2^26; working buffers -- the halo-grown intermediates of the x and y passes -- beyond the budget
+ * "voxel_distance_mb" megabytes (gvom_set_tuning; default 256, at most 4096, < 0: the default); every set of the kind exported.  The
+ * working buffer is grow-only; it and the product sets count in "voxel_atlas_allocations", which does not grow in steady state.
+ * gvom_device_product(kind 40 / 42) is GVOM_ERR_INVALID.  Kinds 39 and 41 are not assigned.
+ * NOT PROVIDED: a signed distance inside obstacles; nearest-source indices and gradients; interpolation between voxels in the sample
+ * call; an unbounded field; incremental updates between integrates; sharded handles; a field of the whole extent. */
+#define GVOM_PRODUCT_VOXEL_DISTANCE 40          /* part 0 float32 [xy, xy, z] metres, part 1 int32 [4]; kind 39 is not assigned */
+#define GVOM_PRODUCT_VOXEL_DISTANCE_SAMPLES 42  /* part 0 float32 [n], part 1 int32 [4]; kind 41 is not assigned */
+#define GVOM_DISTANCE_UNKNOWN_BLOCKS 1          /* flags */
+int gvom_voxel_atlas_distance_field(gvom_t *h, const int64_t origin[3] /* may be NULL */, double max_distance, int flags,
+                                    int64_t *product_id, int64_t origin_out[3] /* may be NULL */);
+int gvom_voxel_distance_sample(gvom_t *h, int64_t field_product_id, const float *points /* [n][3] */, int64_t n, int on_device,
+                               int64_t *product_id);
+
 /* --- one map sharded over the GPUs of a node (one rank = one process = one GPU) -------------------
  * No counterpart in the reference (it has no multi-GPU path); semantics = SURVEY 8(e):
  * the rays are data-parallel, the per-voxel accumulators (hit / total: int32 sum, min-height: f32 min)
@@ -1496,6 +1547,8 @@ int gvom_host_timing(gvom_t *h, double us[8]);
  * "viewpoints" / "viewpoint_allocations" / "viewpoint_batch" (read-only, gvom_get_tuning), "viewpoint_bitmap_mb": see "viewpoint
  * scoring" above.
  * "attitude_volume" / "attitude_volume_allocations" (read-only, gvom_get_tuning): see "attitude volumes" above.
+ * "voxel_distance_field" / "voxel_distance_halo_xy" / "voxel_distance_halo_z" (read-only, gvom_get_tuning), "voxel_distance_mb": see
+ * "voxel distance field" above.
  * (Test hooks are not part of this library: include/gvom_hip_test.h, lib/libgvom_hip_test.so.) */
 int gvom_set_tuning(gvom_t *h, const char *name, int value);
 /* The value the LAST scan ran with ("segs", "period", "ep_row", "prio", "interleave": what automatic resolved to).

@@ -46,7 +46,7 @@ int fuse_impl(gvom_handle *h, hipStream_t on)
     if (!last.filled) return GVOM_EMPTY_BUFFER;                        // gvom.py:179-181
     // before any map descriptor below copies an epoch
     if (h->epoch >= 0xFFFFFF00u) { int rc0 = renumber_epochs(h); if (rc0) return rc0; }
-    // statistics on demand: three combines in a row that nobody read the statistics of -> the scans stop computing them
+    // statistics on demand: the fourth combine in a row that nobody read the statistics before -> it merges none, the scans stop computing them
     if (h->stats_auto && h->stats && ++h->stats_idle > 3) { h->stats = false; h->stats_release = true; }
     if (h->spec_valid && !on && h->spec_slot == h->ring[h->last_buffer_index] && h->spec_nxt == (h->has_combined ? 1 - h->cur : 0)) {
         // eager fusion: k_encfuse has (or will have, in stream order) written exactly what this call would compute -- the one

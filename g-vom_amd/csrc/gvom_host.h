@@ -286,9 +286,10 @@ struct gvom_handle {
     bool host_timing = false;
     bool stats = false;                                 // per-voxel statistics computed by the NEXT scan / merged by the next fusion
     // ON DEMAND (GVOM_FLAG_STATISTICS_ON_DEMAND): the statistics start ON -- the reference computes them in every scan and
-    // combine (gvom.py:159, 276-284) and its node reads them every tick (gvom_ros.py:171) -- and go OFF when three combines
-    // in a row went by without anybody reading them (gvom_debug_voxel_map*, gvom_read_rows, gvom_gather_metrics); a later read
-    // finds no data and switches them ON again for the scans that follow
+    // combine (gvom.py:159, 276-284) and its node reads them every tick (gvom_ros.py:171) -- and go OFF at the fourth combine
+    // in a row that nobody read them before (fuse_impl: ++stats_idle > 3; a read is stats_demand(): gvom_gather_metrics,
+    // gvom_debug_voxel_map / _eigen and the voxel-cloud device product -- NOT gvom_read_rows); a later read finds no data and
+    // switches them ON again for the scans that follow
     bool stats_auto = false;
     int stats_idle = 0;                                 // combines since the statistics were last read
     bool stats_release = false;                         // they have just been switched off: their buffers go at the end of this combine

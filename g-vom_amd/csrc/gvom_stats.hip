@@ -322,7 +322,9 @@ __global__ __launch_bounds__(256) void k_fuse_stats(const FuseParams P, const Fu
                 for (int u = 0; u < 2; ++u) {
                     if (!ok[u]) continue;
                     if (s0 + u < P.nslots) merge_metrics<double>(c, sm[u]);
-                    else merge_metrics<float>(c, pm);
+                    // a row of the previous map WITHOUT returns (count 0: a voxel that only a map fused without statistics knew, one
+                    // combine after statistics on demand were switched on again) merges nothing -- 0 / 0 otherwise, for good
+                    else if (pm[9] > 0.0f) merge_metrics<float>(c, pm);
                 }
             }
 #pragma unroll

@@ -2580,10 +2580,15 @@ class Gvom(object):
       device            HIP device of the map (default 0)
       voxel_statistics  the per-voxel mean / covariance path behind make_debug_voxel_map (gvom.py:159, 276-284, 363-378).
                         None (default): ON DEMAND -- it runs from the first scan on, as in the reference, for as long as somebody
-                        reads it (make_debug_voxel_map, metrics_buffer, combined_metrics, voxels_eigenvalues: the unchanged
-                        node does every tick, gvom_ros.py:171); three combines in a row without a read switch it off (the
-                        scans then cost what the north-star path costs), a later read returns None once and switches it on
-                        again for the scans that follow.  True: always.  False: never (make_debug_voxel_map returns None).
+                        reads it (make_debug_voxel_map, voxel_cloud_device, metrics_buffer, combined_metrics,
+                        voxels_eigenvalues: the unchanged node does every tick, gvom_ros.py:171; read_dense, the returned maps
+                        and the other debug products are not reads); the FOURTH combine in a row with no read before it
+                        switches it off and merges no statistics (the scans then cost what the north-star path costs), a later
+                        read returns None once and switches it on again for the scans that follow; the fused map has statistics
+                        again once every filled ring slot was scanned with them -- restarted from the ring: a voxel only the
+                        map from before knows has an all-zero row (count 0) until a scan reaches its neighbourhood.  A reader
+                        of every fourth combine or fewer never gets data: pin them with True.  True: always.  False: never
+                        (make_debug_voxel_map returns None).
       c_order           False (default): combine_maps returns the four maps as FORTRAN-ordered views of pinned host memory the
                         GPU has written -- same [x, y] indexing, shapes, dtypes and values as the reference's arrays; its
                         caller flattens them with order='F' (gvom_ros.py:141-162), which is then a no-copy reshape.  True:

@@ -82,13 +82,22 @@ typedef struct gvom_params {
                                         * The environment variable GVOM_VOXEL_STATISTICS=0/1 overrides. */
 #define GVOM_FLAG_STATISTICS_ON_DEMAND 4 /* (unsharded handles, ignored with GVOM_FLAG_VOXEL_STATISTICS) the per-voxel path runs
                                         * WHILE SOMEBODY READS IT: it starts on -- the reference computes it in every scan and
-                                        * combine and its node reads it every tick (gvom_ros.py:171) -- goes off when three
-                                        * combines in a row passed without a call of gvom_debug_voxel_map / _eigen /
-                                        * gvom_gather_metrics (its buffers go back to the allocator then: 40 bytes per voxel and
-                                        * fused map alone), and comes back with the next such call: that call returns
-                                        * GVOM_NO_DATA, the scans that follow carry statistics again, and the fused map has them
-                                        * once every ring slot does (they then restart from the ring: what the map had merged
-                                        * before the pause is not in them).  g-vom_amd/gvom.py's default. */
+                                        * combine and its node reads it every tick (gvom_ros.py:171) -- and goes off AT THE FOURTH
+                                        * COMBINE IN A ROW that no read preceded: that combine merges no statistics, and their
+                                        * buffers go back to the allocator (40 bytes per voxel and fused map alone).  A READ is a
+                                        * call of gvom_gather_metrics, gvom_debug_voxel_map, gvom_debug_voxel_eigen or
+                                        * gvom_device_product(GVOM_PRODUCT_VOXEL_CLOUD), whatever it returns; gvom_read_rows,
+                                        * gvom_read_dense and every other call are not.  Only combines that find a filled last
+                                        * slot count; rejected scans change nothing.  The path comes back with the next read:
+                                        * that call returns GVOM_NO_DATA, the scans accepted after it carry statistics (a slot's
+                                        * can be read at once), and the fused map has them from the first combine at which every
+                                        * filled ring slot does.  They then RESTART FROM THE RING: a previous map without
+                                        * statistics contributes its hit counts and minimum heights and nothing else, so a voxel
+                                        * that only such a map knows has an all-zero statistics row (count 0) until a scan with
+                                        * statistics reaches its neighbourhood; a previous row of count 0 merges no statistics
+                                        * at later combines either (the reference's merge, gvom.py:858-909, would divide 0 by 0).
+                                        * What the map had merged before the pause is not in them.  A reader of every fourth
+                                        * combine or fewer therefore never gets data.  g-vom_amd/gvom.py's default. */
 #define GVOM_FLAG_NUMBA_CUDA_TYPING 2  /* the types Numba 0.54.1 infers for a REAL CUDA device where they differ from its simulator's
                                         * (profiles/numba_cuda_typing.txt: its type inference with the CUDA target's typing context
                                         * over gvom.py:1060-1150, 1303-1329): ray_length = math.sqrt(float32) is

@@ -149,9 +149,10 @@ def compare_cloud(cloud, want_cloud, tol=None, what="", eigen=True):
     return a, b
 
 
-def compare_statistics(g, w, tol=None, what=""):
+def compare_statistics(g, w, tol=None, what="", fused=True):
     """Per-voxel statistics of the HIP mapper `g` against the oracle mapper `w` (both with voxel_statistics, same inputs, just
-    combined), rows in voxel order on both sides:
+    combined), rows in voxel order on both sides (fused=False: statistics on demand that are restarting -- the last slot has its
+    own, the fused map has none yet on EITHER side: the slot's are held as always, and the fused map's must be absent):
       metrics_buffer[last slot] (float64), combined_metrics and last_combined_metrics (float32): count column exact, the rest
         to tol["slot"] / tol["fused"];
       voxels_eigenvalues: see above (the oracle's where the fused metrics are the same, the oracle's solver on HIP's own fused
@@ -169,6 +170,12 @@ def compare_statistics(g, w, tol=None, what=""):
     assert gm.dtype == np.float64 and gm.shape == wm.shape, (what, gm.shape, wm.shape)
     assert np.array_equal(gm[:, _COUNT], wm[:, _COUNT]), what + "slot counts"
     _within("slot", gm[:, :_COUNT], wm[:, :_COUNT], tol, dev, what)
+    if not fused:
+        assert w.combined_metrics is None and w.voxels_eigenvalues is None, what + "the referee has fused statistics"
+        assert g.combined_metrics is None and g.last_combined_metrics is None and g.voxels_eigenvalues is None \
+            and g.make_debug_voxel_map() is None, what + "fused statistics where the referee has none"
+        _log(dev, what, gm.shape[0])
+        return dev
 
     wc = voxel_order(w.combined_index_map, w.combined_metrics)
     gc = g.combined_metrics.copy_to_host()

@@ -80,7 +80,7 @@ def test_hip_voxel_statistics_match_reference_golden(gvom_mod, name):
 def test_voxel_statistics_run_on_demand(gvom_mod):
     """voxel_statistics=None (the default): the reference's per-voxel path runs from the first scan on and for as long as somebody
     reads it (the unchanged node calls make_debug_voxel_map every tick, gvom_ros.py:171) -- golden F1-F6 above hold that form to
-    the reference's rows.  Here the other half: a caller that never asks stops paying after three combines (the scans then take
+    the reference's rows.  Here the other half: a caller that never asks stops paying at the fourth unread combine (the scans then take
     the north-star path: eager fusion on this one-slot ring); a later make_debug_voxel_map() returns None once -- which the node
     tolerates, gvom_ros.py:172 -- and switches the statistics on again for the scans that follow; the cloud is back once the
     ring has been replaced.  Its position / solid-factor / hit columns are exact at every moment (they do not depend on the
@@ -89,6 +89,8 @@ def test_voxel_statistics_run_on_demand(gvom_mod):
     params = (0.4, 0.2, 32, 16, 1, 0.5, 0.5, 0.5, 0.3, 2.0, 4.0, 1.0, 1, 1)
     rng = np.random.default_rng(77)
     auto, always, never = gvom_mod.DefaultGvom(*params), gvom_mod.Gvom(*params, voxel_statistics=True), gvom_mod.Gvom(*params, voxel_statistics=False)
+    import stats_demand_ref
+    mirror = stats_demand_ref.DemandOracle(*params)             # the rule in plain Python (tests/test_stats_on_demand.py holds it at length)
 
     def step(k, read):
         ego = (0.3 * k, -0.2 * k, 0.02 * k)
@@ -97,10 +99,16 @@ def test_voxel_statistics_run_on_demand(gvom_mod):
         for g in (auto, always, never):
             g.process_pointcloud(pc, ego)
             outs.append(g.combine_maps())
+        mirror.process_pointcloud(pc.copy(), ego)
+        mirror.combine_maps()
         for o in outs[1:]:
             for a, b in zip(outs[0], o):
                 assert np.array_equal(a, b)
-        return (auto.make_debug_voxel_map(), always.make_debug_voxel_map(), never.make_debug_voxel_map()) if read else None
+        if not read:
+            return None
+        a = auto.make_debug_voxel_map()
+        assert mirror.read() == (a is not None), k
+        return a, always.make_debug_voxel_map(), never.make_debug_voxel_map()
 
     def same_cloud(a, b, eigen):
         a, b = a[np.lexsort((a[:, 2], a[:, 1], a[:, 0]))], b[np.lexsort((b[:, 2], b[:, 1], b[:, 0]))]
@@ -115,7 +123,7 @@ def test_voxel_statistics_run_on_demand(gvom_mod):
     # (one-slot ring: with or without statistics the scan's second kernel is the eager encode-and-fuse, and the statistics' own
     # merge -- k_fuse_stats -- is enqueued with the scan as well; the combines adopt both)
     assert auto.get_tuning("eager_adopted") == 3 and always.get_tuning("eager_adopted") == 3
-    for k in range(3, 9):                                       # nobody asks: off after three unread combines
+    for k in range(3, 9):                                       # nobody asks: off at the fourth unread combine (number 6)
         step(k, False)
     assert auto.get_tuning("eager_adopted") == 9 and always.get_tuning("eager_adopted") == 9 and never.get_tuning("eager_adopted") == 9
     a, w, n = step(9, True)
@@ -123,8 +131,10 @@ def test_voxel_statistics_run_on_demand(gvom_mod):
     a, w, n = step(10, True)                                    # one-slot ring: replaced by the next scan
     assert a is not None and n is None
     same_cloud(a, w, False)
+    compare_statistics(auto, mirror, what="restarted, step 10: ")      # means, covariances, counts, eigenvalues: restarted from the ring
     a, w, n = step(11, True)
     same_cloud(a, w, False)
+    compare_statistics(auto, mirror, what="restarted, step 11: ")
 
 
 def test_hip_voxel_statistics_match_oracle_c2(gvom_mod):

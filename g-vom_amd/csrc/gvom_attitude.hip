@@ -16,7 +16,7 @@
 // outside the window read nothing, and a pose whose wheels stand on unknown ground reads no footprint cell.  No scratch, no atomics,
 // no wait on another workgroup; every loop is bounded at launch (T <= 4096 poses, <= 16384 cells per heading).  Every float64
 // operation is one IEEE operation in the header's order (-ffp-contract=off): the result is exact.
-#include "gvom_rollouts.h"
+#include "gvom_rollouts.h"                                  // (with the wheel and plane arithmetic k_body shares: at_known, at_cell, at_stance, at_better)
 
 #define AT_WAVES 4          // waves per workgroup (fewer where T is smaller)
 #define AT_DEPTH 4          // footprint cells per lane whose loads are in flight together
@@ -30,17 +30,6 @@
 #define AT_LEFT_WINDOW 5
 #define AT_INVALID 6
 
-__device__ __forceinline__ bool at_known(double g) { return g > -1000.0 && g < (double)INFINITY; }
-
-// floor(xx / res) - o, clamped to +-RO_FAR; -RO_FAR unless |xx / res| < 2^30 (NaN included)
-__device__ __forceinline__ int at_cell(double xx, double res, long long o)
-{
-    const double q = xx / res;
-    if (!(fabs(q) < 1073741824.0)) return -RO_FAR;
-    const long long c = (long long)floor(q) - o;
-    return (int)max(min(c, (long long)RO_FAR), (long long)-RO_FAR);
-}
-
 __global__ __launch_bounds__(256) void k_attitude_ground(int n2, int inferred, const double *__restrict__ height,
                                                          const double *__restrict__ inferred_height, double *__restrict__ ground)
 {
@@ -48,23 +37,6 @@ __global__ __launch_bounds__(256) void k_attitude_ground(int n2, int inferred, c
     if (i >= n2) return;
     const double hgt = height[i];
     ground[i] = hgt > -1000.0 ? hgt : (inferred ? inferred_height[i] : -1000.0);
-}
-
-// the better of two candidates for an arg-extreme: the larger key, the lower pose where the keys are equal (keys are never NaN)
-__device__ __forceinline__ void at_better(float &key, int &t, float ko, int to)
-{
-    if (ko > key || (ko == key && to < t)) { key = ko; t = to; }
-}
-
-__device__ __forceinline__ int at_arg_wave(float key, int t)
-{
-#pragma unroll
-    for (int s = 32; s > 0; s >>= 1) {
-        const float ko = __shfl_xor(key, s);
-        const int to = __shfl_xor(t, s);
-        at_better(key, t, ko, to);
-    }
-    return t;
 }
 
 __global__ __launch_bounds__(AT_WAVES * WAVE) void k_attitude(const AttitudeParams P, const float *__restrict__ poses,
@@ -103,10 +75,10 @@ __global__ __launch_bounds__(AT_WAVES * WAVE) void k_attitude(const AttitudePara
                     wheel_unknown = wheel_unknown || !at_known(z[i]);
                 }
                 const bool ok = !wheel_unknown;
-                const double zF = 0.5 * (z[0] + z[1]), zR = 0.5 * (z[2] + z[3]), zL = 0.5 * (z[0] + z[2]), zT = 0.5 * (z[1] + z[3]);
-                sp = (zF - zR) / P.wheelbase;
-                sr = (zL - zT) / P.track;
-                const double z0 = 0.25 * ((z[0] + z[1]) + (z[2] + z[3]));
+                const AtStance a = at_stance(z, P.wheelbase, P.track);
+                sp = a.sp;
+                sr = a.sr;
+                const double z0 = a.z0;
                 const double qx = x / P.R.res, qy = y / P.R.res;
                 const double fx = qx - floor(qx), fy = qy - floor(qy);
                 const double c = cos_sin[2 * h], s = cos_sin[2 * h + 1];

@@ -1,0 +1,162 @@
+// gvom_body.hip -- body clearance scoring (gfx950, wave64): where a body made of spheres lies in 3-D once the vehicle sits on the ground at
+// each pose of K candidate trajectories of T poses, and how close it comes to anything a voxel distance field remembers
+// (include/gvom_hip.h "body clearance scoring" defines the result).
+//
+//   k_body   one workgroup per rollout, ONE POSE PER LANE (k_volume_attitude's shape, not k_attitude's: a pose's work is S gathers, not a
+//            footprint of thousands of cells).  A lane makes its pose's frame once -- the pose frame of gvom_rollouts.h, the four wheel
+//            heights and the stance as k_attitude makes them, then e1, e2, n and q0 -- and keeps it in registers.  The sphere table is
+//            walked by a wave-uniform index, so (bx, by, bz, r) are scalar loads; each lane issues one 4-byte gather per sphere,
+//            BD_DEPTH spheres' gathers in flight.  Status, clearance and tightest sphere go to LDS, 6 bytes per pose; behind one barrier
+//            wave 0 makes the four summary words -- a ballot finds the first bad pose, a shuffle the least clearance in front of it --
+//            and all waves store parts 1 and 2, coalesced.
+//
+// READ-ONLY on the ground map and the field.  No load without its bounds test in front of it: invalid poses, wheels outside the window and
+// spheres outside the box read nothing, and a pose whose wheels stand outside or on unknown ground reads no field value.  No scratch, no
+// atomics, no cross-lane reduction per pose, no wait on another workgroup; every loop is bounded at launch (T <= 4096 poses, S <= 256
+// spheres).  Every float64 operation is one IEEE operation in the header's order (-ffp-contract=off): the result is exact.
+#include "gvom_rollouts.h"
+
+#define BD_WAVES 4          // waves per workgroup (fewer where T is smaller)
+#define BD_DEPTH 4          // spheres per lane whose gathers are in flight together
+
+// status words (include/gvom_hip.h GVOM_BODY_*)
+#define BD_OK 0
+#define BD_COLLISION 1
+#define BD_LEFT_BOX 2
+#define BD_UNKNOWN_GROUND 3
+#define BD_LEFT_WINDOW 4
+#define BD_INVALID 5
+
+#define BD_OUT 0xffffffffu
+
+// floor(xx / res) - o where that lies in [0, n), else BD_OUT; BD_OUT unless |xx / res| < 2^30 (NaN included).  |o| <= 2^40: no overflow
+__device__ __forceinline__ uint32_t bd_voxel(double xx, double res, long long o, int n)
+{
+    const double q = xx / res;
+    if (!(fabs(q) < 1073741824.0)) return BD_OUT;
+    const long long c = (long long)floor(q) - o;
+    return c >= 0 && c < (long long)n ? (uint32_t)c : BD_OUT;
+}
+
+__global__ __launch_bounds__(BD_WAVES * WAVE) void k_body(const BodyParams P, const float *__restrict__ poses, const double *__restrict__ wheels,
+                                                          const double *__restrict__ cos_sin, const double *__restrict__ G,
+                                                          const float4 *__restrict__ body, const float *__restrict__ field,
+                                                          int32_t *__restrict__ summary, float *__restrict__ clearance, uint16_t *__restrict__ pairs)
+{
+    extern __shared__ float s_clr[];                          // [T] clearance, then [T] uint16 {status, tightest << 8}
+    const int T = P.R.T, S = P.S;
+    uint16_t *s_pr = (uint16_t *)(s_clr + T);
+    const int lane = (int)(threadIdx.x & 63u);
+    const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const size_t k = blockIdx.x;
+    const float *pk = poses + k * (size_t)T * 3;
+    const uint32_t uxy = (uint32_t)P.R.xy;
+    for (int t = (int)threadIdx.x; t < T; t += (int)blockDim.x) {
+        int cx, cy, h;
+        const bool valid = ro_pose(P.R, pk + 3 * t, cx, cy, h);
+        int st = valid ? BD_OK : BD_INVALID;
+        const double x = (double)pk[3 * t], y = (double)pk[3 * t + 1];
+        double z[4] = {0.0, 0.0, 0.0, 0.0}, c = 1.0, s = 0.0;
+        if (valid) {
+            uint32_t wxc[4], wyc[4];
+            bool wheel_out = false, wheel_unknown = false;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                wxc[i] = (uint32_t)at_cell(x + wheels[(h * 4 + i) * 2], P.R.res, P.R.ox);
+                wyc[i] = (uint32_t)at_cell(y + wheels[(h * 4 + i) * 2 + 1], P.R.res, P.R.oy);
+                wheel_out = wheel_out || !(wxc[i] < uxy && wyc[i] < uxy);
+            }
+            if (wheel_out) st = BD_LEFT_WINDOW;
+            else {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    z[i] = G[mad24s(wyc[i], uxy, wxc[i])];
+                    wheel_unknown = wheel_unknown || !at_known(z[i]);
+                }
+                if (wheel_unknown) st = BD_UNKNOWN_GROUND;
+            }
+            c = cos_sin[2 * h]; s = cos_sin[2 * h + 1];
+        }
+        const bool ok = st == BD_OK;
+        // FRAME: e1 along the chassis, n its normal, e2 = n x e1, q0 the contact plane's height under the pose
+        const AtStance a = at_stance(z, P.wheelbase, P.track);
+        const double sp = a.sp, sr = a.sr, z0 = a.z0;
+        const double one = 1.0 + sp * sp;
+        const double lu = sqrt(one), ln = sqrt(one + sr * sr);
+        const double e1u = 1.0 / lu, e1w = sp / lu;
+        const double nu = -sp / ln, nv = -sr / ln, nw = 1.0 / ln;
+        const double e2u = nv * e1w, e2v = nw * e1u - nu * e1w, e2w = -(nv * e1u);
+        const double q0 = z0 - sp * P.axle_mid;
+        float clr = INFINITY;
+        int tight = -1;
+        bool left = false;
+        for (int s0 = 0; s0 < S; s0 += BD_DEPTH) {
+            float d[BD_DEPTH], r[BD_DEPTH];
+#pragma unroll
+            for (int j = 0; j < BD_DEPTH; ++j) {
+                d[j] = NAN; r[j] = 0.0f;                      // (a sphere that is not read: skipped by the minimum)
+                if (s0 + j < S) {                             // (wave-uniform)
+                    const float4 b = body[s0 + j];
+                    const double bx = (double)b.x, by = (double)b.y, bz = (double)b.z;
+                    const double Cu = (bx * e1u + by * e2u) + bz * nu;
+                    const double Cv = by * e2v + bz * nv;
+                    const double Cw = ((bx * e1w + by * e2w) + bz * nw) + q0;
+                    const double X = x + (Cu * c - Cv * s);
+                    const double Y = y + (Cu * s + Cv * c);
+                    const uint32_t vx = bd_voxel(X, P.R.res, P.bx, P.n), vy = bd_voxel(Y, P.R.res, P.by, P.n), vz = bd_voxel(Cw, P.z_res, P.bz, P.zs);
+                    const bool in = vx != BD_OUT && vy != BD_OUT && vz != BD_OUT;
+                    left = left || !in;
+                    if (ok && in) d[j] = field[((size_t)vx * (uint32_t)P.n + vy) * (uint32_t)P.zs + vz];
+                    r[j] = b.w;
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < BD_DEPTH; ++j) {
+                const float m = d[j] - r[j];
+                if (m < clr || (tight < 0 && m == m)) { clr = m; tight = s0 + j; }      // (a NaN margin is skipped)
+            }
+        }
+        if (ok) st = left ? BD_LEFT_BOX : (clr < P.min_margin ? BD_COLLISION : BD_OK);
+        if (st >= BD_LEFT_BOX) { clr = 0.0f; tight = 0; }
+        s_clr[t] = clr;
+        s_pr[t] = (uint16_t)((uint32_t)st | ((uint32_t)(tight < 0 ? 255 : tight) << 8));
+    }
+    __syncthreads();
+    if (w == 0) {                                             // the summary: the first bad pose, the least clearance in front of it
+        int first = T;
+        for (int t0 = 0; t0 < T; t0 += WAVE) {
+            const int t = t0 + lane;
+            const unsigned long long bad = lanes(t < T && (s_pr[t] & 0xffu) != BD_OK);
+            if (bad != 0ull) { first = t0 + __builtin_ctzll(bad); break; }
+        }
+        float kc = -INFINITY;
+        int tc = INT_MAX;
+        for (int t = lane; t < first; t += WAVE) at_better(kc, tc, -s_clr[t], t);        // (a clearance is never NaN)
+        tc = at_arg_wave(kc, tc);
+        if (lane < 4) {
+            const int st = first < T ? (int)(s_pr[first] & 0xffu) : BD_OK;
+            const int none = first == 0;
+            const int word = lane == 0 ? st : (lane == 1 ? first : (none ? -1 : (lane == 2 ? tc : (int)(s_pr[tc] >> 8))));
+            summary[k * 4 + lane] = word;
+        }
+    }
+    float *pc = clearance + k * (size_t)T;
+    uint16_t *pp = pairs + k * (size_t)T;
+    for (int t = (int)threadIdx.x; t < T; t += (int)blockDim.x) { pc[t] = s_clr[t]; pp[t] = s_pr[t]; }
+}
+
+hipError_t gvom_launch_body(hipStream_t s, const BodyParams &P, const float *poses, const double *wheels, const double *cos_sin,
+                            const double *ground, const float *body, const float *field, int32_t *summary, float *clearance, uint8_t *pairs)
+{
+    const RolloutParams &R = P.R;
+    const long long far = 1ll << 40;
+    if (R.K < 1 || R.K > GVOM_ROLLOUT_MAX_POSES || R.T < 1 || R.T > GVOM_ROLLOUT_MAX_T || R.xy < 1 || R.xy > 4096 || R.H < 1 ||
+        R.H > GVOM_ROLLOUT_MAX_HEADINGS || P.S < 1 || P.S > GVOM_BODY_MAX_SPHERES || P.n < 1 || P.n > 4096 || P.zs < 1 || P.zs > 4096)
+        return hipErrorInvalidValue;
+    if (P.bx < -far || P.bx > far || P.by < -far || P.by > far || P.bz < -far || P.bz > far) return hipErrorInvalidValue;
+    const int nw = (R.T + WAVE - 1) / WAVE < BD_WAVES ? (R.T + WAVE - 1) / WAVE : BD_WAVES;
+    const size_t lds = (size_t)R.T * 6;                       // <= 24,576 bytes
+    hipLaunchKernelGGL(k_body, dim3((unsigned)R.K), dim3((unsigned)(nw * WAVE)), lds, s, P, poses, wheels, cos_sin, ground, (const float4 *)body,
+                       field, summary, clearance, (uint16_t *)pairs);
+    return hipGetLastError();
+}

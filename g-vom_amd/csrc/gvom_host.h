@@ -359,6 +359,13 @@ struct gvom_handle {
     int at_H = 0;                                       // 0: no chassis set
     gvom_chassis_t at_chassis = {};
     int at_allocs = 0;
+    // BODY CLEARANCE SCORING (gvom_body_set / gvom_score_body): bd_tab = the sphere table in device memory, [256][4] float32 of which bd_S
+    // are set (0: no body), bd_ground = the ground map k_attitude_ground writes on the map-set route, bd_stage = the staging copy of a
+    // caller's host field, ground map and poses; bd_allocs counts the device allocations the two entry points have made on this handle
+    // (the three and the product sets: gvom_get_tuning "body_allocations")
+    Buf bd_tab, bd_ground, bd_stage;
+    int bd_S = 0;
+    int bd_allocs = 0;
     // SCAN ALIGNMENT SCORING (gvom_score_alignments): al_grid = the class grid k_align_field rebuilds in every call (2 bits per voxel,
     // gvom_align_grid_bytes: gvom_get_tuning "alignment_grid_bytes" reads what is allocated), al_stage = the staging copy of a caller's
     // host cloud and transforms; al_allocs counts the device allocations the entry point has made on this handle (the two and its product sets)

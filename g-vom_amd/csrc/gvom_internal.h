@@ -368,6 +368,21 @@ hipError_t gvom_launch_attitude_ground(hipStream_t s, int xy, int inferred, cons
 hipError_t gvom_launch_attitude(hipStream_t s, const AttitudeParams &P, const float *poses, const int32_t *fstart, const uint32_t *foffs,
                                 const double *wheels, const double *cos_sin, const double *ground, int32_t *summary, float *attitude,
                                 uint8_t *status);
+// body clearance scoring (gvom_body.hip; include/gvom_hip.h "body clearance scoring" defines the result).  R, poses, wheels, cos_sin and
+// ground as k_attitude takes them; body [S][4] float32 (bx, by, bz, r), 16-byte aligned; field float32 [n][n][zs] in the class grid's
+// layout, its corner at world voxel (bx, by, bz), each within 2^40.  summary [K][4] int32, clearance [K][T] float32, pairs [K][T][2] uint8
+// {status, tightest}, 2-byte aligned.
+#define GVOM_BODY_MAX_SPHERES 256
+struct BodyParams {
+    RolloutParams R;
+    double wheelbase, track, axle_mid;                 // front_axle - rear_axle, track, 0.5 * (front_axle + rear_axle)
+    double z_res;                                      // (xy_resolution is R.res)
+    long long bx, by, bz;
+    int n, zs, S;
+    float min_margin;
+};
+hipError_t gvom_launch_body(hipStream_t s, const BodyParams &P, const float *poses, const double *wheels, const double *cos_sin,
+                            const double *ground, const float *body, const float *field, int32_t *summary, float *clearance, uint8_t *pairs);
 // scan alignment scoring (gvom_align.hip; include/gvom_hip.h "scan alignment scoring" defines the result).  cloud [n][3] float32 and
 // tf [K][12] float64 (rows 0..2 of each 4x4) in device memory; F = the fused map's frame as k_occupancy takes it.  grid: the class
 // grid, gvom_align_grid_bytes(xy, zs) of scratch, rebuilt by every call.  counts [K][6] int32 (cleared here, then {score, occupied,

@@ -1,6 +1,6 @@
 // gvom_product_calls.hip -- the calls that MAKE a device product: gvom_device_product (occupancy grid, voxel cloud, the two height
 // clouds), gvom_clearance, gvom_raycast, gvom_cost_to_go, gvom_score_rollouts (with gvom_footprint_set, which sets its table),
-// gvom_score_attitude (with gvom_chassis_set), gvom_score_alignments, gvom_frontiers, gvom_score_viewpoints, gvom_pose_field / gvom_pose_field_attitude (with
+// gvom_score_attitude (with gvom_chassis_set), gvom_score_body (with gvom_body_set), gvom_score_alignments, gvom_frontiers, gvom_score_viewpoints, gvom_pose_field / gvom_pose_field_attitude (with
 // gvom_primitives_set) and gvom_attitude_volume, and the frame builders they and the debug reads (gvom_debug.hip) give the kernels.  Every call takes its set
 // through product_acquire and hands it out through product_publish (gvom_sets.hip).  What several calls do alike stands once, in
 // front of the entry points, and serves the atlas calls (gvom_atlas_calls.hip) too: the argument checks (check_*, *_of), the staging
@@ -652,6 +652,106 @@ VIS int gvom_score_attitude(gvom_t *h, int64_t map_set_id, const double *ground,
     HIPCHK(h, gvom_launch_attitude(h->stream, P, pdev, (const int32_t *)h->fp_tab.p, (const uint32_t *)((char *)h->fp_tab.p + h->fp_offs_at),
                                    (const double *)h->at_tab.p, (const double *)((char *)h->at_tab.p + h->at_cs_at), gdev,
                                    part_ptr<int32_t>(set, 0), part_ptr<float>(set, 1), part_ptr<uint8_t>(set, 2)));
+    return product_publish(h, set, product_id);
+}
+
+// ---- body clearance scoring (gvom_body_set, gvom_score_body) ----------------------------------------------------------------------
+// K trajectories of T poses each, scored by k_body (gvom_body.hip) against one float64 ground map and one voxel distance field with the
+// chassis and the sphere table of the handle: a product of kind GVOM_PRODUCT_BODY sized by K and T.  The ground of a map set is
+// k_attitude_ground's, in a grow-only buffer of the handle.  The kernels run on the handle's stream -- behind the passes that wrote the
+// field and the combine that wrote the set, and in front of whatever recycles either later.  Enqueues and returns.
+VIS int gvom_body_set(gvom_t *h, const float *spheres, int32_t S)
+{
+    if (!h) return GVOM_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(h->mu);
+    const char *const fn = "gvom_body_set";
+    if (!spheres) return refuse(h, fn, "spheres must not be NULL");
+    if (S < 1 || S > GVOM_BODY_MAX_SPHERES) return refuse(h, fn, "between 1 and 256 spheres");
+    for (int k = 0; k < 4 * S; ++k)
+        if (!std::isfinite(spheres[k])) return refuse(h, fn, "an entry is not finite");
+    for (int k = 0; k < S; ++k)
+        if (spheres[4 * k + 3] < 0.0f) return refuse(h, fn, "a radius is negative");
+    HIPCHK(h, hipSetDevice(h->device));
+    h->bd_S = 0;                                                            // (no body while this one is on its way)
+    const int rc = stage_buf(h, h->bd_tab, (size_t)GVOM_BODY_MAX_SPHERES * 16, h->bd_allocs);     // (allocated once: it holds every S)
+    if (rc) return rc;
+    // on the handle's stream: behind whatever still reads the previous table
+    HIPCHK(h, hipMemcpyAsync(h->bd_tab.p, spheres, (size_t)S * 16, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->bd_S = S;
+    return GVOM_OK;
+}
+
+VIS int gvom_score_body(gvom_t *h, int64_t field_product_id, const float *field, const int64_t field_origin[3], int64_t map_set_id,
+                        const double *ground, const float *poses, int64_t K, int64_t T, int on_device, int flags, const int64_t origin_cells[2],
+                        float min_margin, int64_t *product_id)
+{
+    if (!h || !product_id) return GVOM_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(h->mu);
+    *product_id = -1;
+    const char *const fn = "gvom_score_body";
+    int rc;
+    if (h->sharded) return refuse(h, fn, "sharded handles are not supported");
+    if (h->fp_H < 1) return refuse(h, fn, "no footprint table is set (gvom_footprint_set)");
+    if (h->at_H < 1) return refuse(h, fn, "no chassis is set (gvom_chassis_set)");
+    if (h->at_H != h->fp_H) return refuse(h, fn, "the chassis was set for another number of headings than the footprint table has");
+    if (h->bd_S < 1) return refuse(h, fn, "no body is set (gvom_body_set)");
+    if (!poses || !origin_cells) return refuse(h, fn, "poses and origin_cells must not be NULL");
+    if (flags & ~GVOM_ATTITUDE_INFERRED_GROUND) return refuse(h, fn, "unknown flag bits");
+    if (!std::isfinite(min_margin)) return refuse(h, fn, "min_margin must be finite");
+    if ((rc = check_one_source(h, fn, map_set_id >= 0, ground, !ground, "a map set id", "a ground map", "a ground map"))) return rc;
+    if ((rc = check_one_source(h, fn, field_product_id >= 0, field || field_origin, !field, "a distance field id", "a field pointer", "a field pointer"))) return rc;
+    if (field_product_id < 0 && !field_origin) return refuse(h, fn, "a field pointer needs field_origin");
+    if ((rc = check_rollout_shape(h, fn, K, T, origin_cells)) || (rc = check_side(h, fn))) return rc;
+    const int xy = h->prm.xy_size;
+    const size_t n2 = (size_t)xy * xy;
+    DevSet *m = nullptr, *f = nullptr;
+    if (map_set_id >= 0 && (rc = map_set_of(h, map_set_id, &m))) return rc;
+    int64_t B[3];
+    int fn_xy = xy, fn_zs = h->prm.z_size;
+    if (field_product_id >= 0) {
+        f = find_set(h->psets, field_product_id);
+        if (!f || f->kind != GVOM_PRODUCT_VOXEL_DISTANCE) return refuse(h, fn, "unknown or stale distance field id");
+        for (int k = 0; k < 3; ++k) B[k] = f->origin[k];
+        fn_xy = f->xy; fn_zs = f->zs;
+    } else {
+        for (int k = 0; k < 3; ++k) {
+            if (field_origin[k] < -((int64_t)1 << 40) || field_origin[k] > ((int64_t)1 << 40)) return refuse(h, fn, "a field origin beyond 2^40 voxels");
+            B[k] = field_origin[k];
+        }
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    DevSet *set = nullptr;
+    const size_t bytes = set_bytes(GVOM_PRODUCT_BODY, 0, 0, K, T);
+    rc = product_acquire(h, GVOM_PRODUCT_BODY, bytes, bytes, fn, &h->bd_allocs, &set);
+    if (rc) return rc;
+    set->cap = K; set->cols = T;
+    if (m && (rc = stage_buf(h, h->bd_ground, n2 * 8, h->bd_allocs))) return rc;
+    const float *pdev = poses;
+    const double *gdev = m ? (const double *)h->bd_ground.p : ground;
+    const float *fdev = f ? part_ptr<const float>(f, 0) : field;
+    HIPCHK(h, join_second_stream(h));
+    if (!on_device) {                                                       // host poses (field and ground): staged, and up before the call returns
+        const HostPart parts[3] = {{field, n2 * (size_t)fn_zs * 4}, {ground, n2 * 8}, {poses, (size_t)K * T * 12}};
+        const void *dev[3];
+        if ((rc = stage_host(h, h->bd_stage, h->bd_allocs, parts, 3, true, dev))) return rc;
+        if (dev[0]) fdev = (const float *)dev[0];
+        if (dev[1]) gdev = (const double *)dev[1];
+        pdev = (const float *)dev[2];
+    }
+    if ((rc = set_wait_releases(h, set))) return rc;
+    if (m) HIPCHK(h, gvom_launch_attitude_ground(h->stream, xy, (flags & GVOM_ATTITUDE_INFERRED_GROUND) ? 1 : 0, part_ptr<const double>(m, 4),
+                                                part_ptr<const double>(m, 5), (double *)h->bd_ground.p));
+    const gvom_chassis_t &c = h->at_chassis;
+    BodyParams P;
+    memset(&P, 0, sizeof P);
+    rollout_frame(h, K, T, origin_cells, P.R);
+    P.wheelbase = c.front_axle - c.rear_axle; P.track = c.track; P.axle_mid = 0.5 * (c.front_axle + c.rear_axle);
+    P.z_res = h->prm.z_resolution;
+    P.bx = B[0]; P.by = B[1]; P.bz = B[2];
+    P.n = fn_xy; P.zs = fn_zs; P.S = h->bd_S; P.min_margin = min_margin;
+    HIPCHK(h, gvom_launch_body(h->stream, P, pdev, (const double *)h->at_tab.p, (const double *)((char *)h->at_tab.p + h->at_cs_at), gdev,
+                               (const float *)h->bd_tab.p, fdev, part_ptr<int32_t>(set, 0), part_ptr<float>(set, 1), part_ptr<uint8_t>(set, 2)));
     return product_publish(h, set, product_id);
 }
 

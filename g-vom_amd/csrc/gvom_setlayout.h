@@ -50,6 +50,8 @@
 //                    {voxels at 0, voxels with a finite distance, outside the extent, seq}.  Kind 39 is not assigned
 //   distance samples (42)  cap floats (the field at the voxel of every point, NaN outside its box), then 4 int32 {inside the box, of those
 //                    finite, of those 0, n}; cap = the points of the call that wrote it.  Kind 41 is not assigned
+//   body (44)        cap x 4 int32 {status, first_bad, tightest_pose, tightest_sphere}, then cap x cols floats (pose clearance), then cap x
+//                    cols x 2 uint8 {pose status, tightest sphere}; cap = K and cols = T as for rollouts.  Kind 43 is not assigned
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -69,7 +71,7 @@ struct SetShape {
     // voxel cloud: rows the allocation holds; raycast: rays of the product; a map set: the elements from one map to the next,
     // dev_map_stride(xy) of gvom_internal.h (which needs the HIP runtime: it comes in through here) -- a multiple of 32, >= xy*xy
     int64_t cap = 0;
-    int64_t cols = 0;                          // rollouts, attitude: poses per rollout (T); atlas frontiers: the side of the field
+    int64_t cols = 0;                          // rollouts, attitude, body: poses per rollout (T); atlas frontiers: the side of the field
 };
 struct SetPart { void *ptr; int ndim; int64_t shape[3], strides[3]; uint8_t code, bits; size_t bytes; };
 
@@ -102,6 +104,7 @@ inline size_t set_bytes(int kind, int xy, int zs, int64_t cap, int64_t cols = 0)
     case GVOM_PRODUCT_VOXEL_ATLAS_ALIGNMENT: return align256((size_t)cap * 24) + 16;
     case GVOM_PRODUCT_VOXEL_DISTANCE: return align256(n2 * zs * 4) + 16;
     case GVOM_PRODUCT_VOXEL_DISTANCE_SAMPLES: return align256((size_t)cap * 4) + 16;
+    case GVOM_PRODUCT_BODY: return align256((size_t)cap * 16) + align256((size_t)cap * (size_t)cols * 4) + (size_t)cap * (size_t)cols * 2;
     }
     return 0;
 }
@@ -266,6 +269,18 @@ inline bool set_part(const SetShape *s, int part, SetPart *d)
         else if (part == 1) { d->ptr = s->mem + align256((size_t)s->cap * 4); d->ndim = 1; d->shape[0] = 4; d->strides[0] = 1; d->shape[1] = d->strides[1] = 1; d->code = kDLInt; }
         else return false;
         break;
+    case GVOM_PRODUCT_BODY: {
+        char *const clr = s->mem + align256((size_t)s->cap * 16);
+        if (part == 0) { rows(s->mem, s->cap, 4); d->code = kDLInt; }
+        else if (part == 1) rows(clr, s->cap, s->cols);
+        else if (part == 2) {
+            d->ptr = clr + align256((size_t)s->cap * (size_t)s->cols * 4); d->ndim = 3; d->code = kDLUInt; d->bits = 8;
+            d->shape[0] = s->cap; d->shape[1] = s->cols; d->shape[2] = 2;
+            d->strides[0] = s->cols * 2; d->strides[1] = 2; d->strides[2] = 1;
+        }
+        else return false;
+        break;
+    }
     default: return false;
     }
     d->bytes = (size_t)(d->shape[0] * d->shape[1] * d->shape[2]) * (d->bits / 8);

@@ -166,6 +166,9 @@ ABI = [
     ("gvom_score_rollouts", _I, [_P, _I64, _P, _P, _P, _I64, _I64, _I, ctypes.POINTER(_I64), ctypes.POINTER(_I64)]),
     ("gvom_chassis_set", _I, [_P, _P, ctypes.c_int32, _P]),
     ("gvom_score_attitude", _I, [_P, _I64, _P, _P, _I64, _I64, _I, _I, ctypes.POINTER(_I64), ctypes.POINTER(_I64)]),
+    ("gvom_body_set", _I, [_P, _P, ctypes.c_int32]),
+    ("gvom_score_body", _I, [_P, _I64, _P, ctypes.POINTER(_I64), _I64, _P, _P, _I64, _I64, _I, _I, ctypes.POINTER(_I64), ctypes.c_float,
+                             ctypes.POINTER(_I64)]),
     ("gvom_score_alignments", _I, [_P, _P, _I64, _P, _I64, _I, _I, _P, ctypes.POINTER(_I64)]),
     ("gvom_frontiers", _I, [_P, _I64, _I64, _P, _P, _P, _I, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(_I64), ctypes.POINTER(_I64)]),
     ("gvom_score_viewpoints", _I, [_P, _P, _I64, _I, ctypes.c_double, ctypes.c_int32, ctypes.c_int32, _I, _P, ctypes.POINTER(_I64)]),
@@ -630,6 +633,7 @@ PRODUCT_VOXEL_ATLAS_VIEWPOINTS = 36       # GVOM_PRODUCT_VOXEL_ATLAS_VIEWPOINTS:
 PRODUCT_VOXEL_ATLAS_ALIGNMENT = 38        # GVOM_PRODUCT_VOXEL_ATLAS_ALIGNMENT: made by gvom_voxel_atlas_score_alignments (kind 37 is not assigned)
 PRODUCT_VOXEL_DISTANCE = 40               # GVOM_PRODUCT_VOXEL_DISTANCE: made by gvom_voxel_atlas_distance_field (kind 39 is not assigned)
 PRODUCT_VOXEL_DISTANCE_SAMPLES = 42       # GVOM_PRODUCT_VOXEL_DISTANCE_SAMPLES: made by gvom_voxel_distance_sample (kind 41 is not assigned)
+PRODUCT_BODY = 44                         # GVOM_PRODUCT_BODY: made by gvom_score_body (kind 43 is not assigned)
 # element type of part k of a product, by kind (what set_part() of csrc/gvom_setlayout.h gives as DLPack code and bits)
 _PRODUCT_DTYPES = {PRODUCT_OCCUPANCY: (np.uint8,), PRODUCT_VOXEL_CLOUD: (np.float32, np.float32, np.int64),
                    PRODUCT_HEIGHT_CLOUD: (np.float32,), PRODUCT_INFERRED_HEIGHT_CLOUD: (np.float32,),
@@ -644,7 +648,8 @@ _PRODUCT_DTYPES = {PRODUCT_OCCUPANCY: (np.uint8,), PRODUCT_VOXEL_CLOUD: (np.floa
                    PRODUCT_ATTITUDE_VOLUME: (np.uint8, np.uint8, np.int32),
                    PRODUCT_VOXEL_BOX: (np.uint8, np.int32), PRODUCT_VOXEL_ATLAS_RAYS: (np.int32, np.float32, np.int32),
                    PRODUCT_VOXEL_ATLAS_VIEWPOINTS: (np.int32, np.int32), PRODUCT_VOXEL_ATLAS_ALIGNMENT: (np.int32, np.int32),
-                   PRODUCT_VOXEL_DISTANCE: (np.float32, np.int32), PRODUCT_VOXEL_DISTANCE_SAMPLES: (np.float32, np.int32)}
+                   PRODUCT_VOXEL_DISTANCE: (np.float32, np.int32), PRODUCT_VOXEL_DISTANCE_SAMPLES: (np.float32, np.int32),
+                   PRODUCT_BODY: (np.int32, np.float32, np.uint8)}
 CLEARANCE_FAR = 2147483647                # GVOM_CLEARANCE_FAR: squared_cells where no obstacle is in reach
 _CLEARANCE_NO_NEGATIVE = 1                # GVOM_CLEARANCE_NO_NEGATIVE
 
@@ -1225,6 +1230,68 @@ class DeviceAttitude(_ProductView):
 
     def copy_to_host(self):
         return self.summary.copy_to_host(), self.attitude.copy_to_host(), self.status.copy_to_host()
+
+
+# ---- body clearance scoring (Gvom.set_body, DeviceDistanceField.score_body and friends; include/gvom_hip.h "body clearance scoring") ----
+BODY_OK, BODY_COLLISION, BODY_LEFT_BOX, BODY_UNKNOWN_GROUND, BODY_LEFT_WINDOW, BODY_INVALID = range(6)   # GVOM_BODY_*
+BODY_MAX_SPHERES = 256
+
+
+def _body_spheres(spheres):
+    """spheres -> C-contiguous float32 (S, 4) = (bx, by, bz, r)"""
+    a = np.asarray(spheres)
+    if a.ndim != 2 or a.shape[1] != 4 or not 1 <= a.shape[0] <= BODY_MAX_SPHERES:
+        raise ValueError("spheres must have shape (S, 4) = (bx, by, bz, r) with 1 <= S <= %d, got %r" % (BODY_MAX_SPHERES, a.shape))
+    if a.dtype.kind not in "iuf":
+        raise ValueError("spheres must be numbers, got dtype %s" % a.dtype)
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    if not np.isfinite(a).all() or (a[:, 3] < 0).any():
+        raise ValueError("spheres must be finite with radii >= 0")
+    return a
+
+
+def box_spheres(x0, x1, half_width, z0, z1, radius):
+    """A body for Gvom.set_body: float32 (S, 4) spheres of one radius on a lattice whose union covers the box x0 .. x1 (body x,
+    forward) by -half_width .. +half_width (body y) by z0 .. z1 (height above the wheels' contact plane).  Per axis the side is cut
+    into the fewest equal parts of at most radius * 2 / sqrt(3) -- the side of the cube inscribed in a sphere -- and a centre stands
+    in the middle of each part: the cuboids around the centres tile the box and every point of it lies within `radius` of a centre.
+    The union reaches radius - part / 2 beyond a face, along the axis through a centre: at most `radius`, and at least
+    radius * (1 - 1 / sqrt(3)) = 0.42 radius.  ValueError where the lattice would need more than 256 spheres: choose a larger
+    radius."""
+    lo = np.array([x0, -float(half_width), z0], np.float64)
+    hi = np.array([x1, float(half_width), z1], np.float64)
+    r = float(radius)
+    if not (np.isfinite(lo).all() and np.isfinite(hi).all() and (hi > lo).all() and math.isfinite(r) and r > 0):
+        raise ValueError("box_spheres needs x0 < x1, half_width > 0, z0 < z1 and radius > 0, all finite")
+    pitch = r * 2.0 / math.sqrt(3.0)
+    n = np.maximum(1, np.ceil((hi - lo) / pitch - 1e-12)).astype(np.int64)
+    if int(n.prod()) > BODY_MAX_SPHERES:
+        raise ValueError("a box of %r m at radius %r needs %d spheres, more than %d" % ((hi - lo).tolist(), r, int(n.prod()), BODY_MAX_SPHERES))
+    axes = [l + (np.arange(k, dtype=np.float64) + 0.5) * ((h - l) / k) for l, h, k in zip(lo, hi, n)]
+    g = np.stack(np.meshgrid(*axes, indexing="ij"), axis=-1).reshape(-1, 3)
+    return np.ascontiguousarray(np.concatenate([g, np.full((g.shape[0], 1), r)], axis=1), dtype=np.float32)
+
+
+class DeviceBodyClearance(_ProductView):
+    """The result of DeviceDistanceField.score_body() / score_body_of() / Gvom.score_body_of() / score_body_of_device(): `.summary`
+    int32 [K, 4] -- per rollout {status (BODY_*), first bad pose (T: none), the pose of the least clearance in front of it and that
+    pose's tightest sphere (-1 without one)} --, `.clearance` float32 [K, T] -- the least of (field at the sphere's voxel - radius)
+    over the body, metres, +inf where nothing is within the field's cap -- and `.status` uint8 [K, T, 2] {BODY_*, tightest sphere}:
+    three DeviceArrays of one product, row i = rollout i.  A snapshot: later scans, combines, integrates, set_body and set_chassis
+    calls do not change it.  DLPack hands over `.clearance`; copy_to_host() returns (summary, clearance, status) as numpy."""
+
+    def __init__(self, hold):
+        _ProductView.__init__(self, hold)
+        self.summary, self.clearance, self.status = DeviceArray(hold, 0), DeviceArray(hold, 1), DeviceArray(hold, 2)
+
+    def copy_to_host(self):
+        return self.summary.copy_to_host(), self.clearance.copy_to_host(), self.status.copy_to_host()
+
+    def __dlpack_device__(self):
+        return self.clearance.__dlpack_device__()
+
+    def __dlpack__(self, stream=None, max_version=None, dl_device=None, copy=None):
+        return self.clearance.__dlpack__(stream=stream, max_version=max_version, dl_device=dl_device, copy=copy)
 
 
 class _AttitudePlanes(DeviceArray):
@@ -2264,6 +2331,27 @@ class DeviceDistanceField(_ProductView):
                                PRODUCT_VOXEL_DISTANCE_SAMPLES, g._check_args)
         return DeviceDistanceSamples(hold)
 
+    def score_body(self, device_maps, poses, min_margin=0.0, inferred_ground=True):
+        """Where the mapper's body (Gvom.set_body) lies in this field once the vehicle sits on the ground of `device_maps` (a DeviceMaps:
+        its `height` map and, with inferred_ground, its `inferred height` map) at every pose of K candidate trajectories, and how
+        close it comes to a remembered obstacle: a DeviceBodyClearance, one kernel on the GPU behind the passes that wrote the field
+        and the combine that wrote the set; no host wait once the poses are up.  poses: (K, T, 3) = (x, y, yaw) in world metres and
+        radians, ROUNDED TO float32.  A pose collides where its clearance < min_margin (metres); a body is clear of every remembered
+        voxel centre where the clearance is at least the voxel's half diagonal.  Needs set_footprint, set_chassis and set_body.
+        include/gvom_hip.h "body clearance scoring" has the definition."""
+        g = self._hold._owner
+        a = _rollout_poses(poses)
+        return g._score_body(self.product_id, None, None, device_maps.set_id, None, _ptr(a), a.shape[0], a.shape[1], 0, bool(inferred_ground),
+                             device_maps.origin, min_margin)
+
+    def score_body_of(self, ground, poses, origin=(0.0, 0.0), min_margin=0.0):
+        """score_body() on a ground map of the caller's: a numpy [x, y] array of shape (xy_size, xy_size), heights in metres as
+        Gvom.score_attitude_of takes them; origin: the window corner in world metres."""
+        g = self._hold._owner
+        gm = g._window_map("ground", ground, np.float64)
+        a = _rollout_poses(poses)
+        return g._score_body(self.product_id, None, None, -1, _ptr(gm), _ptr(a), a.shape[0], a.shape[1], 0, False, origin, min_margin)
+
     def sample(self, points):
         """The field at the voxels of world points float32 [n, 3] in metres -- floor(p / resolution) per axis, no interpolation: a
         DeviceDistanceSamples.  A body sphere of radius r at p is clear of every source where sample(p) >= r + the voxel's half
@@ -3198,6 +3286,48 @@ class Gvom(object):
             raise ValueError("ground_ptr and poses_ptr must be device addresses")
         K, T = _rollout_shape(K, T)
         return self._score_attitude(-1, _dev(ground_ptr), _dev(poses_ptr), K, T, 1, False, origin)
+
+    # ---- body clearance scoring (an extension; include/gvom_hip.h "body clearance scoring") ----
+    def set_body(self, spheres):
+        """Sets the vehicle's body for the score_body calls: float32 (S, 4) = (bx, by, bz, r), 1 <= S <= 256 -- sphere centres in the
+        chassis's body frame (x forward, y left, bz above the wheels' contact plane) and radii >= 0, in metres; box_spheres() makes
+        one of a box.  Replaces a previous body; products made with it are unchanged."""
+        a = _body_spheres(spheres)
+        self._check_args(self._lib.gvom_body_set(self._h, _ptr(a), a.shape[0]))
+
+    def _score_body(self, field_id, field_ptr, field_origin, set_id, ground_ptr, poses_ptr, K, T, on_device, inferred_ground, origin, min_margin):
+        oc = _rollout_origin(origin, self.xy_resolution)
+        flags = _ATTITUDE_INFERRED_GROUND if inferred_ground else 0
+        with np.errstate(over="ignore"):
+            mm = float(np.float32(min_margin))
+        if not math.isfinite(mm):
+            raise ValueError("min_margin must be a finite distance in metres, got %r" % (min_margin,))
+        return DeviceBodyClearance(self._make_product(lambda pid: self._lib.gvom_score_body(
+            self._h, int(field_id), field_ptr, field_origin, int(set_id), ground_ptr, poses_ptr, int(K), int(T), int(on_device), flags, oc,
+            ctypes.c_float(mm), pid), PRODUCT_BODY, self._check_args))
+
+    def score_body_of(self, field, field_origin_voxels, ground, poses, origin=(0.0, 0.0), min_margin=0.0):
+        """DeviceDistanceField.score_body() with a field AND a ground map of the caller's: field a numpy float32 array of shape
+        (xy_size, xy_size, z_size) in the class grid's layout, its corner at field_origin_voxels (three integers, world voxels);
+        ground as score_attitude_of takes it; origin: the window corner in world metres.  Needs no scan and no combine.  A
+        convenience route: field, map and poses are copied to the device."""
+        f = np.ascontiguousarray(np.asarray(field), dtype=np.float32)
+        if f.shape != (self.xy_size, self.xy_size, self.z_size):
+            raise ValueError("field must have shape (%d, %d, %d), got %r" % (self.xy_size, self.xy_size, self.z_size, f.shape))
+        gm = self._window_map("ground", ground, np.float64)
+        p = _rollout_poses(poses)
+        return self._score_body(-1, _ptr(f), _voxel_origin(field_origin_voxels, "field_origin_voxels"), -1, _ptr(gm), _ptr(p), p.shape[0],
+                                p.shape[1], 0, False, origin, min_margin)
+
+    def score_body_of_device(self, field_ptr, field_origin_voxels, ground_ptr, poses_ptr, K, T, origin=(0.0, 0.0), min_margin=0.0):
+        """The same for a field, a map and poses in device memory: raw device addresses of xy_size*xy_size*z_size float32 ([x][y][z]),
+        xy_size*xy_size float64 (cell (x, y) at [y*xy_size + x]) and K x T x 3 float32 (C-contiguous); the data must be ready when the
+        call is made.  Enqueues and returns: no host wait."""
+        if not field_ptr or not ground_ptr or not poses_ptr:
+            raise ValueError("field_ptr, ground_ptr and poses_ptr must be device addresses")
+        K, T = _rollout_shape(K, T)
+        return self._score_body(-1, _dev(field_ptr), _voxel_origin(field_origin_voxels, "field_origin_voxels"), -1, _dev(ground_ptr),
+                                _dev(poses_ptr), K, T, 1, False, origin, min_margin)
 
     # ---- attitude volumes (an extension; include/gvom_hip.h "attitude volumes") ----
     def _attitude_volume(self, set_id, ground_ptr, on_device, inferred_ground):

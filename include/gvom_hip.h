@@ -1301,6 +1301,85 @@ int gvom_voxel_atlas_distance_field(gvom_t *h, const int64_t origin[3] /* may be
 int gvom_voxel_distance_sample(gvom_t *h, int64_t field_product_id, const float *points /* [n][3] */, int64_t n, int on_device,
                                int64_t *product_id);
 
+/* --- body clearance scoring (an extension: rollouts against the 3-D distance field -- does the body pass under the branch, the gate bar,
+ * the bridge once the vehicle sits on that ground, nose up on the ramp or tilted on the side slope) -----------------------------------------
+ * gvom_score_rollouts says what the footprint touches on the 2-D cost map and gvom_score_attitude how the vehicle sits on the ground.
+ * gvom_score_body places a BODY of spheres, set once with gvom_body_set, at K trajectories of T poses each on ONE float64 ground map, reads
+ * a voxel distance field at every sphere's centre -- one kernel, one gather per sphere -- and leaves the result in device memory as a
+ * product (kind GVOM_PRODUCT_BODY) that gvom_device_product_export / _release / _dlpack / _copy handle like the others.  gvom_get_tuning
+ * "body" (read-only): 1 -- how a caller probes a library for these entry points (an addition: GVOM_ABI_VERSION stays); "body_spheres"
+ * (read-only): S while a table is set, else 0.  Every float64 operation below is ONE IEEE operation in the order written, parentheses
+ * binding, no contraction; sqrt and / are the correctly rounded float64 ones; the library calls no trigonometric function: the result is
+ * exact, and every decision is taken on the float32 values that are stored.
+ *
+ * DEFINITION.  res = xy_resolution, zres = z_resolution, xy = xy_size, o = origin_cells.
+ * BODY       S spheres, 1 <= S <= 256, float32 [S][4] = (bx, by, bz, r): (bx, by) in the chassis's body frame (x forward, y left, origin
+ *            at the pose), bz the height above the wheels' contact plane, r >= 0 the radius, all metres.
+ * POSES, CENTRE, HEADING, INVALID   those of rollout scoring above, word for word; H is the footprint table's and (c, s) = cos_sin[k]
+ *            comes from gvom_chassis_set.  A footprint table and a chassis with equal H must be set, as for gvom_score_attitude.
+ * GROUND     terrain attitude scoring's GROUND, word for word: map_set_id >= 0 with GVOM_ATTITUDE_INFERRED_GROUND or 0 in flags (ground
+ *            must be NULL), or the caller's float64 map with origin_cells.  The wheel cells, zFL .. zRR, sp, sr, z0 and am are that
+ *            section's, word for word.  Only the four wheel cells are tested against the window: the footprint cells are not walked.
+ * FIELD      one of two.  field_product_id >= 0: a live product of kind GVOM_PRODUCT_VOXEL_DISTANCE of this handle; (Bx, By, Bz) is the box
+ *            origin it was made with, field and field_origin must be NULL.  field_product_id < 0: the caller's float32
+ *            [xy_size][xy_size][z_size] in the class grid's layout, out[x][y][z], with (Bx, By, Bz) = field_origin[3] in world voxels,
+ *            each within 2^40; host or device memory as on_device says, like the ground.  READ-ONLY on the field: the kernel runs on the
+ *            handle's stream in front of whatever reuses the field's set, so the caller may release the field as soon as the call
+ *            returns (gvom_voxel_distance_sample's rule).
+ * FRAME      per pose, float64:  lu = sqrt(1.0 + sp*sp);  ln = sqrt((1.0 + sp*sp) + sr*sr);
+ *            e1 = (e1u, 0, e1w) = (1.0/lu, 0, sp/lu)          along the chassis, nose up positive;
+ *            n  = (nu, nv, nw)  = (-sp/ln, -sr/ln, 1.0/ln)    the contact plane's normal;
+ *            e2 = n x e1 = (e2u, e2v, e2w) = (nv*e1w, nw*e1u - nu*e1w, -(nv*e1u))   to the left;
+ *            q0 = z0 - sp*am                                  the contact plane's height under the pose.
+ * SPHERE CENTRE   for (bx, by, bz), each widened to double:
+ *            Cu = (bx*e1u + by*e2u) + bz*nu;  Cv = by*e2v + bz*nv;  Cw = ((bx*e1w + by*e2w) + bz*nw) + q0;
+ *            X = (double)x + (Cu*c - Cv*s);  Y = (double)y + (Cu*s + Cv*c);  Z = Cw.
+ *            Its voxel: floor(X / res) - Bx, floor(Y / res) - By, floor(Z / zres) - Bz.  It is OUTSIDE the box if it is not in range or
+ *            |quotient| < 2^30 does not hold on some axis (NaN included).  The world height of the maps is (min_height + z + origin_z) *
+ *            z_resolution, so the ground under a wheel lies in the voxel floor(g / zres): the frames agree without an offset.
+ * MARGIN     m_i = d_i - r_i, one float32 subtraction, d_i the field's value at the sphere's voxel (+inf stays +inf).  clearance = the
+ *            least m_i; a NaN m_i is skipped by the minimum (a caller's field may contain NaN, a product's cannot).  tightest = the
+ *            lowest i that attains the least margin; 255 with clearance = +inf if every margin was skipped.
+ * STATUS     per pose, the first that applies: GVOM_BODY_INVALID; _LEFT_WINDOW: a wheel cell is outside the window; _UNKNOWN_GROUND: a
+ *            wheel cell's ground is unknown; _LEFT_BOX: a sphere's voxel is outside the box; _COLLISION: clearance < min_margin, a
+ *            float32 comparison; _OK.  min_margin is finite.
+ * part 1 = float32 [K, T] clearance, 0 where the status is INVALID, LEFT_WINDOW, UNKNOWN_GROUND or LEFT_BOX.
+ * part 2 = uint8 [K, T, 2] {status, tightest}, tightest = 0 in those four cases.
+ * part 0 = int32 [K, 4] {status, first_bad, tightest_pose, tightest_sphere}: first_bad = the smallest t whose status is not OK, or T;
+ *            status = that pose's, or OK; tightest_pose = the lowest t < first_bad with the least clearance and tightest_sphere that
+ *            pose's tightest, both -1 when first_bad == 0.  Row i = rollout i.  Every pose is evaluated: nothing depends on scheduling.
+ * WHAT THE NUMBER MEANS   the field runs between voxel centres, and the ground is remembered as occupied voxels too: a body is clear of
+ *            every remembered voxel centre where clearance >= the voxel's half diagonal.  Spheres model the body above the belly, not
+ *            the wheels.
+ *
+ * gvom_body_set validates the table, copies it to the device on the handle's stream -- behind whatever still reads the previous one --
+ * and returns after the copy.  A later call replaces the table; products made with the old table are unchanged.  GVOM_ERR_INVALID: NULL
+ * arguments, S outside 1 .. 256, a non-finite entry, r < 0.
+ * gvom_score_body: on_device, staging, the snapshot, the pool (sized by K and T) and the limits (T in 1 .. 4096, K * T <= 2^26, xy_size
+ * <= 4096) are gvom_score_attitude's; on_device says where the poses, the ground and the field pointers lie.  gvom_get_tuning
+ * "body_allocations" (read-only): device allocations the two entry points have made on this handle (the table, the ground map of the
+ * map-set route, the staging buffer of the host route and the product sets); it does not grow in steady state at a fixed K, T and route.
+ * gvom_device_product(GVOM_PRODUCT_BODY) is GVOM_ERR_INVALID (this call makes them).  Kind 43 is not assigned.
+ * GVOM_ERR_INVALID: a sharded handle; no footprint table, no chassis, or unequal H; no body table; a set id AND a ground pointer, or
+ * neither; an unknown or stale set id; a field id AND a field pointer or origin, or neither; a stale field id or one of another kind; a
+ * NULL field_origin on the pointer route or one beyond 2^40 voxels; a NaN or infinite min_margin; unknown flag bits; T outside 1 .. 4096;
+ * K < 1; NULL poses / origin_cells / product_id; an origin beyond 2^40 cells.  GVOM_ERR_CAPACITY: K * T > 2^26; xy_size > 4096; every set
+ * of the kind exported.
+ * NOT PROVIDED: interpolation in the field; capsules or boxes; poses with their own z; suspension; sharded handles; interpolation
+ * between poses. */
+#define GVOM_PRODUCT_BODY 44   /* part 0 int32 [K, 4] {status, first_bad, tightest_pose, tightest_sphere}; part 1 float32 [K, T] clearance; part 2 uint8 [K, T, 2] {status, tightest} */
+/* 43 stays unassigned: tests/body_layout_host_test.cpp holds it to "no such kind" */
+#define GVOM_BODY_OK 0
+#define GVOM_BODY_COLLISION 1
+#define GVOM_BODY_LEFT_BOX 2
+#define GVOM_BODY_UNKNOWN_GROUND 3
+#define GVOM_BODY_LEFT_WINDOW 4
+#define GVOM_BODY_INVALID 5
+int gvom_body_set(gvom_t *h, const float *spheres /* [S][4] */, int32_t S);
+int gvom_score_body(gvom_t *h, int64_t field_product_id, const float *field, const int64_t field_origin[3], int64_t map_set_id,
+                    const double *ground, const float *poses /* [K][T][3] */, int64_t K, int64_t T, int on_device, int flags,
+                    const int64_t origin_cells[2], float min_margin, int64_t *product_id);
+
 /* --- one map sharded over the GPUs of a node (one rank = one process = one GPU) -------------------
  * No counterpart in the reference (it has no multi-GPU path); semantics = SURVEY 8(e):
  * the rays are data-parallel, the per-voxel accumulators (hit / total: int32 sum, min-height: f32 min)
@@ -1551,6 +1630,7 @@ int gvom_host_timing(gvom_t *h, double us[8]);
  * "cost-to-go fields" above.
  * "rollouts" / "footprint" / "rollout_allocations" (read-only, gvom_get_tuning): see "rollout scoring" above.
  * "attitude" / "chassis" / "attitude_allocations" (read-only, gvom_get_tuning): see "terrain attitude scoring" above.
+ * "body" / "body_spheres" / "body_allocations" (read-only, gvom_get_tuning): see "body clearance scoring" above.
  * "alignments" / "alignment_allocations" / "alignment_grid_bytes" / "alignment_points_per_block" / "alignment_candidate_group"
  * (read-only, gvom_get_tuning): see "scan alignment scoring" above.
  * "viewpoints" / "viewpoint_allocations" / "viewpoint_batch" (read-only, gvom_get_tuning), "viewpoint_bitmap_mb": see "viewpoint

@@ -14,29 +14,10 @@
 // spheres outside the box read nothing, and a pose whose wheels stand outside or on unknown ground reads no field value.  No scratch, no
 // atomics, no cross-lane reduction per pose, no wait on another workgroup; every loop is bounded at launch (T <= 4096 poses, S <= 256
 // spheres).  Every float64 operation is one IEEE operation in the header's order (-ffp-contract=off): the result is exact.
-#include "gvom_rollouts.h"
+#include "gvom_bodyframe.h"
 
 #define BD_WAVES 4          // waves per workgroup (fewer where T is smaller)
 #define BD_DEPTH 4          // spheres per lane whose gathers are in flight together
-
-// status words (include/gvom_hip.h GVOM_BODY_*)
-#define BD_OK 0
-#define BD_COLLISION 1
-#define BD_LEFT_BOX 2
-#define BD_UNKNOWN_GROUND 3
-#define BD_LEFT_WINDOW 4
-#define BD_INVALID 5
-
-#define BD_OUT 0xffffffffu
-
-// floor(xx / res) - o where that lies in [0, n), else BD_OUT; BD_OUT unless |xx / res| < 2^30 (NaN included).  |o| <= 2^40: no overflow
-__device__ __forceinline__ uint32_t bd_voxel(double xx, double res, long long o, int n)
-{
-    const double q = xx / res;
-    if (!(fabs(q) < 1073741824.0)) return BD_OUT;
-    const long long c = (long long)floor(q) - o;
-    return c >= 0 && c < (long long)n ? (uint32_t)c : BD_OUT;
-}
 
 __global__ __launch_bounds__(BD_WAVES * WAVE) void k_body(const BodyParams P, const float *__restrict__ poses, const double *__restrict__ wheels,
                                                           const double *__restrict__ cos_sin, const double *__restrict__ G,
@@ -78,15 +59,7 @@ __global__ __launch_bounds__(BD_WAVES * WAVE) void k_body(const BodyParams P, co
             c = cos_sin[2 * h]; s = cos_sin[2 * h + 1];
         }
         const bool ok = st == BD_OK;
-        // FRAME: e1 along the chassis, n its normal, e2 = n x e1, q0 the contact plane's height under the pose
-        const AtStance a = at_stance(z, P.wheelbase, P.track);
-        const double sp = a.sp, sr = a.sr, z0 = a.z0;
-        const double one = 1.0 + sp * sp;
-        const double lu = sqrt(one), ln = sqrt(one + sr * sr);
-        const double e1u = 1.0 / lu, e1w = sp / lu;
-        const double nu = -sp / ln, nv = -sr / ln, nw = 1.0 / ln;
-        const double e2u = nv * e1w, e2v = nw * e1u - nu * e1w, e2w = -(nv * e1u);
-        const double q0 = z0 - sp * P.axle_mid;
+        const BdFrame F = bd_frame(at_stance(z, P.wheelbase, P.track), P.axle_mid);      // FRAME (gvom_bodyframe.h)
         float clr = INFINITY;
         int tight = -1;
         bool left = false;
@@ -97,24 +70,15 @@ __global__ __launch_bounds__(BD_WAVES * WAVE) void k_body(const BodyParams P, co
                 d[j] = NAN; r[j] = 0.0f;                      // (a sphere that is not read: skipped by the minimum)
                 if (s0 + j < S) {                             // (wave-uniform)
                     const float4 b = body[s0 + j];
-                    const double bx = (double)b.x, by = (double)b.y, bz = (double)b.z;
-                    const double Cu = (bx * e1u + by * e2u) + bz * nu;
-                    const double Cv = by * e2v + bz * nv;
-                    const double Cw = ((bx * e1w + by * e2w) + bz * nw) + q0;
-                    const double X = x + (Cu * c - Cv * s);
-                    const double Y = y + (Cu * s + Cv * c);
-                    const uint32_t vx = bd_voxel(X, P.R.res, P.bx, P.n), vy = bd_voxel(Y, P.R.res, P.by, P.n), vz = bd_voxel(Cw, P.z_res, P.bz, P.zs);
-                    const bool in = vx != BD_OUT && vy != BD_OUT && vz != BD_OUT;
+                    uint32_t vx, vy, vz;
+                    const bool in = bd_sphere(P, F, b, x, y, c, s, vx, vy, vz);
                     left = left || !in;
-                    if (ok && in) d[j] = field[((size_t)vx * (uint32_t)P.n + vy) * (uint32_t)P.zs + vz];
+                    if (ok && in) d[j] = field[bd_at(P, vx, vy, vz)];
                     r[j] = b.w;
                 }
             }
 #pragma unroll
-            for (int j = 0; j < BD_DEPTH; ++j) {
-                const float m = d[j] - r[j];
-                if (m < clr || (tight < 0 && m == m)) { clr = m; tight = s0 + j; }      // (a NaN margin is skipped)
-            }
+            for (int j = 0; j < BD_DEPTH; ++j) bd_margin(clr, tight, d[j], r[j], s0 + j);
         }
         if (ok) st = left ? BD_LEFT_BOX : (clr < P.min_margin ? BD_COLLISION : BD_OK);
         if (st >= BD_LEFT_BOX) { clr = 0.0f; tight = 0; }

@@ -454,6 +454,12 @@ struct gvom_handle {
     uint64_t fp_gen = 0, at_gen = 0, av_fp_gen = 0, av_at_gen = 0;
     int fp_total = 0;
     int av_allocs = 0;
+    // BODY VOLUMES (gvom_body_volume): the wheel offsets come from av_tab (rebuilt by the same rule, allocated once for both entry
+    // points and counted in av_allocs); bv_ground = the ground map of the map-set route, bv_stage = the staging copy of a caller's host
+    // field and ground map.  bv_allocs counts the device allocations the entry point has made on this handle (the two and its product
+    // sets: gvom_get_tuning "body_volume_allocations")
+    Buf bv_ground, bv_stage;
+    int bv_allocs = 0;
 };
 
 namespace gvom_host {

@@ -473,6 +473,13 @@ hipError_t gvom_launch_attitude_volume(hipStream_t s, const AttitudeVolumeParams
                                        int32_t *counts);
 hipError_t gvom_launch_cspace_attitude(hipStream_t s, int xy, int H, const uint8_t *status, const uint8_t *tilt, uint32_t block_mask,
                                        uint32_t tilt_weight, uint16_t *C);
+// body volumes (gvom_body_volume.hip; include/gvom_hip.h "body volumes" defines the result).  P as k_body takes it, of which R.xy, R.H,
+// R.ox, R.oy and R.res say what the window is (R.K, R.T and R.s are not read); wcell the attitude volume table's [H][12] int32; cos_sin,
+// ground, body and field as k_body takes them.  status, squeeze [H][y][x] uint8 and clearance [H][y][x] float32; counts [8] int32, words
+// 0 .. 5 CLEARED by the caller (added to), words 6 and 7 = H and S.
+hipError_t gvom_launch_body_volume(hipStream_t s, const BodyParams &P, float soft_margin, const int32_t *wcell, const double *cos_sin,
+                                   const double *ground, const float *body, const float *field, uint8_t *status, uint8_t *squeeze,
+                                   float *clearance, int32_t *counts);
 // map atlas (gvom_atlas.hip; include/gvom_hip.h "map atlas" defines the result).  The atlas is ten planes of A x A cells behind one
 // base address, A a power of two: the six f64 maps of a set (maps 3 .. 8) at k * A*A doubles, then the three i32 maps (0 .. 2) and
 // the int32 stamp at k * A*A ints; world cell (X, Y) at [(Y & (A-1)) * A + (X & (A-1))].  AtlasMaps = nine [y][x] maps of n x n cells

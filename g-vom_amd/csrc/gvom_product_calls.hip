@@ -1,7 +1,7 @@
 // gvom_product_calls.hip -- the calls that MAKE a device product: gvom_device_product (occupancy grid, voxel cloud, the two height
 // clouds), gvom_clearance, gvom_raycast, gvom_cost_to_go, gvom_score_rollouts (with gvom_footprint_set, which sets its table),
-// gvom_score_attitude (with gvom_chassis_set), gvom_score_body (with gvom_body_set), gvom_score_alignments, gvom_frontiers, gvom_score_viewpoints, gvom_pose_field / gvom_pose_field_attitude (with
-// gvom_primitives_set) and gvom_attitude_volume, and the frame builders they and the debug reads (gvom_debug.hip) give the kernels.  Every call takes its set
+// gvom_score_attitude (with gvom_chassis_set), gvom_score_body (with gvom_body_set), gvom_score_alignments, gvom_frontiers, gvom_score_viewpoints, gvom_pose_field / gvom_pose_field_attitude / gvom_pose_field_volumes (with
+// gvom_primitives_set), gvom_attitude_volume and gvom_body_volume, and the frame builders they and the debug reads (gvom_debug.hip) give the kernels.  Every call takes its set
 // through product_acquire and hands it out through product_publish (gvom_sets.hip).  What several calls do alike stands once, in
 // front of the entry points, and serves the atlas calls (gvom_atlas_calls.hip) too: the argument checks (check_*, *_of), the staging
 // of host inputs (stage_host), the frames (metric_frame, rollout_frame) and, for the calls that wait, the round driver (solve_rounds;
@@ -971,11 +971,13 @@ VIS int gvom_primitives_set(gvom_t *h, int32_t n_headings, const int32_t *start,
     return GVOM_OK;
 }
 
-// the one host path of gvom_pose_field and gvom_pose_field_attitude (fn says which): with_volume = the second, whose volume_id names
-// the attitude volume k_cspace_attitude takes into the pose cost volume behind k_cspace
+// the one host path of gvom_pose_field, gvom_pose_field_attitude and gvom_pose_field_volumes (fn says which): with_volume = volume_id names
+// the attitude volume k_cspace_attitude takes into the pose cost volume behind k_cspace; with_body = body_id names the body volume the
+// same kernel takes in behind that (its parts 0 and 1 are the same elementwise rule's status and weight byte)
 static int pose_field_call(gvom_t *h, const char *fn, int64_t costfield_id, const int32_t *cost, int on_device, bool with_volume,
-                           int64_t volume_id, uint32_t block_mask, int32_t tilt_weight, const int32_t *goals, int64_t n_goals,
-                           int32_t max_cost, int32_t max_rounds, int64_t *product_id, int64_t info[4])
+                           int64_t volume_id, uint32_t block_mask, int32_t tilt_weight, bool with_body, int64_t body_id, uint32_t body_mask,
+                           int32_t squeeze_weight, const int32_t *goals, int64_t n_goals, int32_t max_cost, int32_t max_rounds,
+                           int64_t *product_id, int64_t info[4])
 {
     if (!h || !product_id) return GVOM_ERR_INVALID;
     std::lock_guard<std::mutex> lk(h->mu);
@@ -996,7 +998,7 @@ static int pose_field_call(gvom_t *h, const char *fn, int64_t costfield_id, cons
         if (goals[3 * k] < 0 || goals[3 * k] >= xy || goals[3 * k + 1] < 0 || goals[3 * k + 1] >= xy) return refuse(h, fn, "a goal lies outside the window");
         if (goals[3 * k + 2] >= H) return refuse(h, fn, "a goal's heading is not one of the table's");
     }
-    DevSet *f = nullptr, *vol = nullptr;
+    DevSet *f = nullptr, *vol = nullptr, *bvol = nullptr;
     if (costfield_id >= 0) {
         if ((rc = cost_field_of(h, fn, costfield_id, &f))) return rc;
     } else if (!on_device && (rc = check_host_cost(h, fn, cost, n2))) return rc;
@@ -1005,6 +1007,12 @@ static int pose_field_call(gvom_t *h, const char *fn, int64_t costfield_id, cons
         if (tilt_weight < 0 || tilt_weight > 255) return refuse(h, fn, "tilt_weight outside 0 .. 255");
         if ((rc = product_of_kind(h, fn, volume_id, GVOM_PRODUCT_ATTITUDE_VOLUME, "unknown or stale attitude volume id", &vol))) return rc;
         if (vol->cap != H || vol->xy != xy) return refuse(h, fn, "the attitude volume was made for another number of headings or another window side");
+    }
+    if (with_body) {
+        if (body_mask > 0x3fu) return refuse(h, fn, "body_block_mask outside 0 .. 0x3f");
+        if (squeeze_weight < 0 || squeeze_weight > 255) return refuse(h, fn, "squeeze_weight outside 0 .. 255");
+        if ((rc = product_of_kind(h, fn, body_id, GVOM_PRODUCT_BODY_VOLUME, "unknown or stale body volume id", &bvol))) return rc;
+        if (bvol->cap != H || bvol->xy != xy) return refuse(h, fn, "the body volume was made for another number of headings or another window side");
     }
     HIPCHK(h, hipSetDevice(h->device));
     DevSet *set = nullptr;
@@ -1032,6 +1040,8 @@ static int pose_field_call(gvom_t *h, const char *fn, int64_t costfield_id, cons
     HIPCHK(h, gvom_launch_cspace(h->stream, xy, H, c16, (const int32_t *)h->fp_tab.p, (const uint32_t *)((char *)h->fp_tab.p + h->fp_offs_at), C));
     if (vol) HIPCHK(h, gvom_launch_cspace_attitude(h->stream, xy, H, part_ptr<const uint8_t>(vol, 0), part_ptr<const uint8_t>(vol, 1), block_mask,
                                                    (uint32_t)tilt_weight, C));
+    if (bvol) HIPCHK(h, gvom_launch_cspace_attitude(h->stream, xy, H, part_ptr<const uint8_t>(bvol, 0), part_ptr<const uint8_t>(bvol, 1), body_mask,
+                                                    (uint32_t)squeeze_weight, C));
     HIPCHK(h, gvom_launch_pose_seed(h->stream, 1, xy, H, R, (const int32_t *)cost32, c16w, C, D, G.fl, G.goals, (int)n_goals, G.cnt + CTG_CNT_SEEDED));
     const int32_t cap = max_cost == 0 ? GVOM_CTG_MAX_COST : max_cost;
     const int inner = h->pf.tune_inner > 0 ? h->pf.tune_inner : 64;
@@ -1052,15 +1062,58 @@ static int pose_field_call(gvom_t *h, const char *fn, int64_t costfield_id, cons
 VIS int gvom_pose_field(gvom_t *h, int64_t costfield_id, const int32_t *cost, int on_device, const int32_t *goals, int64_t n_goals,
                         int32_t max_cost, int32_t max_rounds, int64_t *product_id, int64_t info[4])
 {
-    return pose_field_call(h, "gvom_pose_field", costfield_id, cost, on_device, false, -1, 0u, 0, goals, n_goals, max_cost, max_rounds, product_id, info);
+    return pose_field_call(h, "gvom_pose_field", costfield_id, cost, on_device, false, -1, 0u, 0, false, -1, 0u, 0, goals, n_goals, max_cost, max_rounds,
+                           product_id, info);
 }
 
 VIS int gvom_pose_field_attitude(gvom_t *h, int64_t costfield_id, const int32_t *cost, int on_device, int64_t volume_id, uint32_t block_mask,
                                  int32_t tilt_weight, const int32_t *goals, int64_t n_goals, int32_t max_cost, int32_t max_rounds,
                                  int64_t *product_id, int64_t info[4])
 {
-    return pose_field_call(h, "gvom_pose_field_attitude", costfield_id, cost, on_device, true, volume_id, block_mask, tilt_weight, goals, n_goals,
-                           max_cost, max_rounds, product_id, info);
+    return pose_field_call(h, "gvom_pose_field_attitude", costfield_id, cost, on_device, true, volume_id, block_mask, tilt_weight, false, -1, 0u, 0,
+                           goals, n_goals, max_cost, max_rounds, product_id, info);
+}
+
+VIS int gvom_pose_field_volumes(gvom_t *h, int64_t costfield_id, const int32_t *cost, int on_device, int64_t attitude_volume_id,
+                                uint32_t attitude_block_mask, int32_t tilt_weight, int64_t body_volume_id, uint32_t body_block_mask,
+                                int32_t squeeze_weight, const int32_t *goals, int64_t n_goals, int32_t max_cost, int32_t max_rounds,
+                                int64_t *product_id, int64_t info[4])
+{
+    const char *const fn = "gvom_pose_field_volumes";
+    if (!h || !product_id) return GVOM_ERR_INVALID;
+    if ((attitude_volume_id < 0 && (attitude_block_mask != 0u || tilt_weight != 0)) || (body_volume_id < 0 && (body_block_mask != 0u || squeeze_weight != 0))) {
+        std::lock_guard<std::mutex> lk(h->mu);
+        *product_id = -1;
+        for (int k = 0; info && k < 4; ++k) info[k] = 0;
+        return refuse(h, fn, "a mask or a weight that is not 0 beside a volume id of -1");
+    }
+    return pose_field_call(h, fn, costfield_id, cost, on_device, attitude_volume_id >= 0, attitude_volume_id, attitude_block_mask, tilt_weight,
+                           body_volume_id >= 0, body_volume_id, body_block_mask, squeeze_weight, goals, n_goals, max_cost, max_rounds, product_id, info);
+}
+
+// the table of "attitude volumes" (av_tab: (u - am, v) of every footprint cell and per heading the wheels' cell offsets and the footprint's
+// box), shared by gvom_attitude_volume and gvom_body_volume: the first call of either after a gvom_footprint_set / gvom_chassis_set
+// rebuilds it.  reserve: room for it, in front of the call's uploads; rebuild: k_volume_attitude_table on the handle's stream, behind
+// whatever still reads the previous table
+static bool volume_table_stale(const gvom_t *h) { return h->av_fp_gen != h->fp_gen || h->av_at_gen != h->at_gen; }
+static int volume_table_reserve(gvom_t *h, int H)
+{
+    if (!volume_table_stale(h)) return GVOM_OK;
+    const size_t tab_bytes = align256((size_t)h->fp_total * 16) + (size_t)H * 48;
+    if (h->av_tab.bytes < tab_bytes) HIPCHK(h, hipStreamSynchronize(h->stream));   // the kernels that read the table it outgrows
+    return stage_buf(h, h->av_tab, tab_bytes, h->av_allocs);
+}
+static int volume_table_rebuild(gvom_t *h, int H)
+{
+    if (!volume_table_stale(h)) return GVOM_OK;
+    const gvom_chassis_t &c = h->at_chassis;
+    const size_t wcell_at = align256((size_t)h->fp_total * 16);
+    HIPCHK(h, gvom_launch_attitude_volume_table(h->stream, H, h->fp_total, h->prm.xy_resolution, 0.5 * (c.front_axle + c.rear_axle),
+                                                (const int32_t *)h->fp_tab.p, (const uint32_t *)((char *)h->fp_tab.p + h->fp_offs_at),
+                                                (const double *)h->at_tab.p, (const double *)((char *)h->at_tab.p + h->at_cs_at),
+                                                (double *)h->av_tab.p, (int32_t *)((char *)h->av_tab.p + wcell_at)));
+    h->av_wcell_at = wcell_at; h->av_fp_gen = h->fp_gen; h->av_at_gen = h->at_gen;
+    return GVOM_OK;
 }
 
 // ---- attitude volumes (gvom_attitude_volume) ----------------------------------------------------------------------------------------
@@ -1094,10 +1147,7 @@ VIS int gvom_attitude_volume(gvom_t *h, int64_t map_set_id, const double *ground
     if ((rc = product_acquire(h, GVOM_PRODUCT_ATTITUDE_VOLUME, bytes, bytes, fn, &h->av_allocs, &set))) return rc;
     set->cap = H;
     const gvom_chassis_t &c = h->at_chassis;
-    const size_t wcell_at = align256((size_t)h->fp_total * 16), tab_bytes = wcell_at + (size_t)H * 48;
-    const bool rebuild = h->av_fp_gen != h->fp_gen || h->av_at_gen != h->at_gen;
-    if (rebuild && h->av_tab.bytes < tab_bytes) HIPCHK(h, hipStreamSynchronize(h->stream));   // the kernels that read the table it outgrows
-    if (rebuild && (rc = stage_buf(h, h->av_tab, tab_bytes, h->av_allocs))) return rc;
+    if ((rc = volume_table_reserve(h, H))) return rc;
     if (m && (rc = stage_buf(h, h->av_ground, n2 * 8, h->av_allocs))) return rc;
     const double *gdev = m ? (const double *)h->av_ground.p : ground;
     HIPCHK(h, join_second_stream(h));
@@ -1109,12 +1159,7 @@ VIS int gvom_attitude_volume(gvom_t *h, int64_t map_set_id, const double *ground
     }
     const int32_t *fstart = (const int32_t *)h->fp_tab.p;
     const uint32_t *foffs = (const uint32_t *)((char *)h->fp_tab.p + h->fp_offs_at);
-    if (rebuild) {                                                          // on the handle's stream: behind whatever still reads the previous table
-        HIPCHK(h, gvom_launch_attitude_volume_table(h->stream, H, h->fp_total, h->prm.xy_resolution, 0.5 * (c.front_axle + c.rear_axle), fstart, foffs,
-                                                    (const double *)h->at_tab.p, (const double *)((char *)h->at_tab.p + h->at_cs_at),
-                                                    (double *)h->av_tab.p, (int32_t *)((char *)h->av_tab.p + wcell_at)));
-        h->av_wcell_at = wcell_at; h->av_fp_gen = h->fp_gen; h->av_at_gen = h->at_gen;
-    }
+    if ((rc = volume_table_rebuild(h, H))) return rc;
     if ((rc = set_wait_releases(h, set))) return rc;
     if (m) HIPCHK(h, gvom_launch_attitude_ground(h->stream, xy, (flags & GVOM_ATTITUDE_INFERRED_GROUND) ? 1 : 0, part_ptr<const double>(m, 4),
                                                 part_ptr<const double>(m, 5), (double *)h->av_ground.p));
@@ -1127,6 +1172,92 @@ VIS int gvom_attitude_volume(gvom_t *h, int64_t map_set_id, const double *ground
     HIPCHK(h, hipMemsetAsync(counts, 0, 32, h->stream));
     HIPCHK(h, gvom_launch_attitude_volume(h->stream, P, fstart, foffs, (const double *)h->av_tab.p, (const int32_t *)((char *)h->av_tab.p + h->av_wcell_at),
                                           gdev, part_ptr<uint8_t>(set, 0), part_ptr<uint8_t>(set, 1), counts));
+    return product_publish(h, set, product_id);
+}
+
+// ---- body volumes (gvom_body_volume) -------------------------------------------------------------------------------------------------
+// The status, the squeeze and the clearance of body clearance scoring at every state (cell centre, heading) of the window, by
+// k_volume_body (gvom_body_volume.hip) against one float64 ground map and one voxel distance field with the chassis and the sphere table
+// of the handle: a product of kind GVOM_PRODUCT_BODY_VOLUME sized by H.  The wheels' cell offsets are the attitude volume's table (above).
+// The field and ground routes are gvom_score_body's.  Enqueues and returns.
+VIS int gvom_body_volume(gvom_t *h, int64_t field_product_id, const float *field, const int64_t field_origin[3], int64_t map_set_id,
+                         const double *ground, int on_device, int flags, const int64_t origin_cells[2], float min_margin, float soft_margin,
+                         int64_t *product_id)
+{
+    if (!h || !product_id) return GVOM_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(h->mu);
+    *product_id = -1;
+    const char *const fn = "gvom_body_volume";
+    int rc;
+    if (h->sharded) return refuse(h, fn, "sharded handles are not supported");
+    if (h->fp_H < 1) return refuse(h, fn, "no footprint table is set (gvom_footprint_set)");
+    if (h->at_H < 1) return refuse(h, fn, "no chassis is set (gvom_chassis_set)");
+    if (h->fp_H > GVOM_POSE_MAX_HEADINGS) return refuse(h, fn, "footprint tables of more than 64 headings are not supported", GVOM_ERR_CAPACITY);
+    if (h->at_H != h->fp_H) return refuse(h, fn, "the chassis was set for another number of headings than the footprint table has");
+    if (h->bd_S < 1) return refuse(h, fn, "no body is set (gvom_body_set)");
+    if (!origin_cells) return refuse(h, fn, "origin_cells must not be NULL");
+    if (flags & ~GVOM_ATTITUDE_INFERRED_GROUND) return refuse(h, fn, "unknown flag bits");
+    if (!std::isfinite(min_margin)) return refuse(h, fn, "min_margin must be finite");
+    if (!std::isfinite(soft_margin)) return refuse(h, fn, "soft_margin must be finite");
+    if (soft_margin < min_margin) return refuse(h, fn, "soft_margin must not be less than min_margin");
+    if ((rc = check_one_source(h, fn, map_set_id >= 0, ground, !ground, "a map set id", "a ground map", "a ground map"))) return rc;
+    if ((rc = check_one_source(h, fn, field_product_id >= 0, field || field_origin, !field, "a distance field id", "a field pointer", "a field pointer"))) return rc;
+    if (field_product_id < 0 && !field_origin) return refuse(h, fn, "a field pointer needs field_origin");
+    for (int k = 0; k < 2; ++k)
+        if (origin_cells[k] < -((int64_t)1 << 40) || origin_cells[k] > ((int64_t)1 << 40)) return refuse(h, fn, "an origin beyond 2^40 cells");
+    if ((rc = check_side(h, fn))) return rc;
+    const int xy = h->prm.xy_size, H = h->fp_H;
+    const size_t n2 = (size_t)xy * xy;
+    if ((int64_t)H * (int64_t)n2 > GVOM_POSE_MAX_STATES) return refuse(h, fn, "more than 2^28 states (headings x xy_size^2)", GVOM_ERR_CAPACITY);
+    DevSet *m = nullptr, *f = nullptr;
+    if (map_set_id >= 0 && (rc = map_set_of(h, map_set_id, &m))) return rc;
+    int64_t B[3];
+    int fn_xy = xy, fn_zs = h->prm.z_size;
+    if (field_product_id >= 0) {
+        f = find_set(h->psets, field_product_id);
+        if (!f || f->kind != GVOM_PRODUCT_VOXEL_DISTANCE) return refuse(h, fn, "unknown or stale distance field id");
+        for (int k = 0; k < 3; ++k) B[k] = f->origin[k];
+        fn_xy = f->xy; fn_zs = f->zs;
+    } else {
+        for (int k = 0; k < 3; ++k) {
+            if (field_origin[k] < -((int64_t)1 << 40) || field_origin[k] > ((int64_t)1 << 40)) return refuse(h, fn, "a field origin beyond 2^40 voxels");
+            B[k] = field_origin[k];
+        }
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    DevSet *set = nullptr;
+    const size_t bytes = set_bytes(GVOM_PRODUCT_BODY_VOLUME, xy, 0, H);
+    if ((rc = product_acquire(h, GVOM_PRODUCT_BODY_VOLUME, bytes, bytes, fn, &h->bv_allocs, &set))) return rc;
+    set->cap = H;
+    if ((rc = volume_table_reserve(h, H))) return rc;
+    if (m && (rc = stage_buf(h, h->bv_ground, n2 * 8, h->bv_allocs))) return rc;
+    const double *gdev = m ? (const double *)h->bv_ground.p : ground;
+    const float *fdev = f ? part_ptr<const float>(f, 0) : field;
+    HIPCHK(h, join_second_stream(h));
+    if (!on_device && (field || ground)) {                                  // a host field and / or ground map: staged, and up before the call returns
+        const HostPart parts[2] = {{field, n2 * (size_t)fn_zs * 4}, {ground, n2 * 8}};
+        const void *dev[2];
+        if ((rc = stage_host(h, h->bv_stage, h->bv_allocs, parts, 2, true, dev))) return rc;
+        if (dev[0]) fdev = (const float *)dev[0];
+        if (dev[1]) gdev = (const double *)dev[1];
+    }
+    if ((rc = volume_table_rebuild(h, H))) return rc;
+    if ((rc = set_wait_releases(h, set))) return rc;
+    if (m) HIPCHK(h, gvom_launch_attitude_ground(h->stream, xy, (flags & GVOM_ATTITUDE_INFERRED_GROUND) ? 1 : 0, part_ptr<const double>(m, 4),
+                                                part_ptr<const double>(m, 5), (double *)h->bv_ground.p));
+    const gvom_chassis_t &c = h->at_chassis;
+    BodyParams P;
+    memset(&P, 0, sizeof P);
+    P.R.xy = xy; P.R.H = H; P.R.res = h->prm.xy_resolution; P.R.ox = origin_cells[0]; P.R.oy = origin_cells[1];
+    P.wheelbase = c.front_axle - c.rear_axle; P.track = c.track; P.axle_mid = 0.5 * (c.front_axle + c.rear_axle);
+    P.z_res = h->prm.z_resolution;
+    P.bx = B[0]; P.by = B[1]; P.bz = B[2];
+    P.n = fn_xy; P.zs = fn_zs; P.S = h->bd_S; P.min_margin = min_margin;
+    int32_t *counts = part_ptr<int32_t>(set, 3);
+    HIPCHK(h, hipMemsetAsync(counts, 0, 32, h->stream));
+    HIPCHK(h, gvom_launch_body_volume(h->stream, P, soft_margin, (const int32_t *)((char *)h->av_tab.p + h->av_wcell_at),
+                                      (const double *)((char *)h->at_tab.p + h->at_cs_at), gdev, (const float *)h->bd_tab.p, fdev,
+                                      part_ptr<uint8_t>(set, 0), part_ptr<uint8_t>(set, 1), part_ptr<float>(set, 2), counts));
     return product_publish(h, set, product_id);
 }
 }  // extern "C"

@@ -52,6 +52,9 @@
 //                    finite, of those 0, n}; cap = the points of the call that wrote it.  Kind 41 is not assigned
 //   body (44)        cap x 4 int32 {status, first_bad, tightest_pose, tightest_sphere}, then cap x cols floats (pose clearance), then cap x
 //                    cols x 2 uint8 {pose status, tightest sphere}; cap = K and cols = T as for rollouts.  Kind 43 is not assigned
+//   body volume (46) cap x xy*xy uint8 (status), then cap x xy*xy uint8 (squeeze), then cap x xy*xy floats (clearance): volumes [h][y][x],
+//                    every plane laid out like a pose field's; then 8 int32 {states per status 0 .. 5, H, S}; cap = the headings H of the
+//                    call that wrote it.  Kind 45 is not assigned
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -105,6 +108,7 @@ inline size_t set_bytes(int kind, int xy, int zs, int64_t cap, int64_t cols = 0)
     case GVOM_PRODUCT_VOXEL_DISTANCE: return align256(n2 * zs * 4) + 16;
     case GVOM_PRODUCT_VOXEL_DISTANCE_SAMPLES: return align256((size_t)cap * 4) + 16;
     case GVOM_PRODUCT_BODY: return align256((size_t)cap * 16) + align256((size_t)cap * (size_t)cols * 4) + (size_t)cap * (size_t)cols * 2;
+    case GVOM_PRODUCT_BODY_VOLUME: return 2 * align256((size_t)cap * n2) + align256((size_t)cap * n2 * 4) + 32;
     }
     return 0;
 }
@@ -279,6 +283,17 @@ inline bool set_part(const SetShape *s, int part, SetPart *d)
             d->strides[0] = s->cols * 2; d->strides[1] = 2; d->strides[2] = 1;
         }
         else return false;
+        break;
+    }
+    case GVOM_PRODUCT_BODY_VOLUME: {                       // parts 0 .. 2 [h, x, y] indexing: every plane column-major, like a pose field's
+        if (part < 0 || part > 3) return false;
+        const size_t vol = (size_t)s->cap * (size_t)n2;
+        d->ptr = s->mem + (size_t)(part < 2 ? part : 2) * align256(vol) + (part == 3 ? align256(vol * 4) : 0);
+        if (part == 3) { d->ndim = 1; d->shape[0] = 8; d->strides[0] = 1; d->shape[1] = d->strides[1] = 1; d->code = kDLInt; break; }
+        d->ndim = 3;
+        d->shape[0] = s->cap; d->shape[1] = d->shape[2] = xy;
+        d->strides[0] = n2; d->strides[1] = 1; d->strides[2] = xy;
+        if (part < 2) { d->code = kDLUInt; d->bits = 8; }
         break;
     }
     default: return false;

@@ -177,6 +177,10 @@ ABI = [
     ("gvom_attitude_volume", _I, [_P, _I64, _P, _I, _I, ctypes.POINTER(_I64)]),
     ("gvom_pose_field_attitude", _I, [_P, _I64, _P, _I, _I64, ctypes.c_uint32, ctypes.c_int32, _P, _I64, ctypes.c_int32, ctypes.c_int32,
                                       ctypes.POINTER(_I64), ctypes.POINTER(_I64)]),
+    ("gvom_body_volume", _I, [_P, _I64, _P, ctypes.POINTER(_I64), _I64, _P, _I, _I, ctypes.POINTER(_I64), ctypes.c_float, ctypes.c_float,
+                              ctypes.POINTER(_I64)]),
+    ("gvom_pose_field_volumes", _I, [_P, _I64, _P, _I, _I64, ctypes.c_uint32, ctypes.c_int32, _I64, ctypes.c_uint32, ctypes.c_int32, _P, _I64,
+                                     ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(_I64), ctypes.POINTER(_I64)]),
     ("gvom_device_map_origin", _I, [_P, _I64, ctypes.POINTER(_I64)]),
     ("gvom_atlas_configure", _I, [_P, ctypes.c_int32, _I, ctypes.POINTER(_I64)]),
     ("gvom_atlas_integrate", _I, [_P, _I64, ctypes.POINTER(_P), _I, ctypes.POINTER(_I64)]),
@@ -634,6 +638,8 @@ PRODUCT_VOXEL_ATLAS_ALIGNMENT = 38        # GVOM_PRODUCT_VOXEL_ATLAS_ALIGNMENT: 
 PRODUCT_VOXEL_DISTANCE = 40               # GVOM_PRODUCT_VOXEL_DISTANCE: made by gvom_voxel_atlas_distance_field (kind 39 is not assigned)
 PRODUCT_VOXEL_DISTANCE_SAMPLES = 42       # GVOM_PRODUCT_VOXEL_DISTANCE_SAMPLES: made by gvom_voxel_distance_sample (kind 41 is not assigned)
 PRODUCT_BODY = 44                         # GVOM_PRODUCT_BODY: made by gvom_score_body (kind 43 is not assigned)
+PRODUCT_BODY_VOLUME = 46                  # GVOM_PRODUCT_BODY_VOLUME: made by gvom_body_volume (kind 45 is not assigned)
+_BODY_BLOCKS = (1, 2)                     # (BODY_COLLISION, BODY_LEFT_BOX): the statuses a pose field blocks by default -- an unknown clearance is not a free one
 # element type of part k of a product, by kind (what set_part() of csrc/gvom_setlayout.h gives as DLPack code and bits)
 _PRODUCT_DTYPES = {PRODUCT_OCCUPANCY: (np.uint8,), PRODUCT_VOXEL_CLOUD: (np.float32, np.float32, np.int64),
                    PRODUCT_HEIGHT_CLOUD: (np.float32,), PRODUCT_INFERRED_HEIGHT_CLOUD: (np.float32,),
@@ -649,7 +655,8 @@ _PRODUCT_DTYPES = {PRODUCT_OCCUPANCY: (np.uint8,), PRODUCT_VOXEL_CLOUD: (np.floa
                    PRODUCT_VOXEL_BOX: (np.uint8, np.int32), PRODUCT_VOXEL_ATLAS_RAYS: (np.int32, np.float32, np.int32),
                    PRODUCT_VOXEL_ATLAS_VIEWPOINTS: (np.int32, np.int32), PRODUCT_VOXEL_ATLAS_ALIGNMENT: (np.int32, np.int32),
                    PRODUCT_VOXEL_DISTANCE: (np.float32, np.int32), PRODUCT_VOXEL_DISTANCE_SAMPLES: (np.float32, np.int32),
-                   PRODUCT_BODY: (np.int32, np.float32, np.uint8)}
+                   PRODUCT_BODY: (np.int32, np.float32, np.uint8),
+                   PRODUCT_BODY_VOLUME: (np.uint8, np.uint8, np.float32, np.int32)}
 CLEARANCE_FAR = 2147483647                # GVOM_CLEARANCE_FAR: squared_cells where no obstacle is in reach
 _CLEARANCE_NO_NEGATIVE = 1                # GVOM_CLEARANCE_NO_NEGATIVE
 
@@ -937,7 +944,8 @@ class DeviceCostField(_ProductView):
     def copy_to_host(self):
         return self.cost.copy_to_host(), self.direction.copy_to_host(), self.cell_cost.copy_to_host()
 
-    def pose_field(self, goals, goals_in_cells=False, max_cost=None, max_rounds=0, attitude=None, attitude_blocks=_ATTITUDE_BLOCKS, tilt_weight=0):
+    def pose_field(self, goals, goals_in_cells=False, max_cost=None, max_rounds=0, attitude=None, attitude_blocks=_ATTITUDE_BLOCKS, tilt_weight=0,
+                   body=None, body_blocks=_BODY_BLOCKS, squeeze_weight=0):
         """The heading-aware navigation function of this field's `.cell_cost` under the mapper's footprint table (Gvom.set_footprint;
         build THIS field without inflation: the footprint does that, per heading) and primitive table (Gvom.set_primitives): from
         every state (x, y, heading) the cheapest drive to a goal state that the primitives allow -- a DevicePoseField, computed on the
@@ -947,12 +955,15 @@ class DeviceCostField(_ProductView):
         the footprint blocks seeds nothing.  max_cost, max_rounds: as cost_to_go().  attitude: a DeviceAttitudeVolume of the same
         headings and window -- a state whose status is one of attitude_blocks (ATTITUDE_* codes) is
         blocked, every other state costs tilt_weight (0 .. 255) times its tilt more, at most 65535; without one
-        the field is what it always was.  include/gvom_hip.h "pose fields" and "attitude volumes" have the definition."""
+        the field is what it always was.  body: a DeviceBodyVolume of the same headings and window -- behind the attitude volume, a
+        state whose status is one of body_blocks (BODY_* codes; by default a collision and a body outside the field's box: an unknown
+        clearance is not a free one) is blocked, every other state costs squeeze_weight (0 .. 255) times its squeeze more.
+        include/gvom_hip.h "pose fields", "attitude volumes" and "body volumes" have the definition."""
         g = self._hold._owner
         H = g._pose_headings()
         cells = _pose_goals(goals, g.xy_size, H, None if goals_in_cells else (g.xy_resolution, self.origin))
         return g._pose_field(self.product_id, None, 0, cells, _ctg_max_cost(max_cost), _ctg_max_rounds(max_rounds), self.origin,
-                             _pose_attitude(attitude, attitude_blocks, tilt_weight))
+                             _pose_attitude(attitude, attitude_blocks, tilt_weight), _pose_body(body, body_blocks, squeeze_weight))
 
     def frontiers(self, device_maps, min_cells=4, max_clusters=1024):
         """Where to explore next: the cells of this field that can be driven on (`.cell_cost` > 0), have been seen (`visibility` of
@@ -1295,7 +1306,7 @@ class DeviceBodyClearance(_ProductView):
 
 
 class _AttitudePlanes(DeviceArray):
-    """One [H, xy, xy] uint8 volume of an attitude volume, indexed [h, x, y] with strides (xy*xy, 1, xy) like a pose field's volumes.
+    """One [H, xy, xy] volume of an attitude volume or a body volume, indexed [h, x, y] with strides (xy*xy, 1, xy) like a pose field's volumes.
     copy_to_host() returns numpy of the same indexing (a transposed view of the [h][y][x] copy)."""
 
     def copy_to_host(self):
@@ -1350,6 +1361,70 @@ def _pose_attitude(attitude, attitude_blocks, tilt_weight):
     if not ok:
         raise ValueError("tilt_weight must be an integer in 0 .. 255, got %r" % (tilt_weight,))
     return attitude.product_id, mask, int(tilt_weight)
+
+
+class DeviceBodyVolume(_ProductView):
+    """The result of DeviceDistanceField.body_volume() / body_volume_of() / Gvom.body_volume_of() / body_volume_of_device(): `.status`
+    uint8 [H, xy, xy] -- BODY_* of the sphere body (Gvom.set_body) with the vehicle standing in the centre of cell (x, y) at heading h
+    --, `.squeeze` uint8 [H, xy, xy] -- how much of the band between soft_margin and min_margin the state has used up, 0 .. 100 percent
+    (0 outside the window, on unknown ground and outside the field's box) -- and `.clearance` float32 [H, xy, xy] -- the least of
+    (field at the sphere's voxel - radius) over the body, metres, +inf where nothing is within the field's cap, 0 in those three cases
+    --, all indexed [h, x, y], and `.counts` int32 [8]: the states per status code 0 .. 5, then H and S.  Four DeviceArrays of one
+    product; `__dlpack__` hands out `.status`.  A snapshot: later scans, combines, integrates, set_footprint, set_chassis and set_body
+    calls do not change it.  copy_to_host() returns (status, squeeze, clearance, counts) as numpy."""
+
+    def __init__(self, hold):
+        _ProductView.__init__(self, hold)
+        self.status, self.squeeze, self.clearance = _AttitudePlanes(hold, 0), _AttitudePlanes(hold, 1), _AttitudePlanes(hold, 2)
+        self.counts = DeviceArray(hold, 3)
+
+    def copy_to_host(self):
+        return self.status.copy_to_host(), self.squeeze.copy_to_host(), self.clearance.copy_to_host(), self.counts.copy_to_host()
+
+    def __dlpack_device__(self):
+        return self.status.__dlpack_device__()
+
+    def __dlpack__(self, stream=None, max_version=None, dl_device=None, copy=None):
+        return self.status.__dlpack__(stream=stream, max_version=max_version, dl_device=dl_device, copy=copy)
+
+
+def _body_margins(min_margin, soft_margin):
+    """the margins of the body_volume calls -> (min_margin, soft_margin) as float32-exact Python floats; soft_margin None: min_margin"""
+    with np.errstate(over="ignore"):
+        mm = float(np.float32(min_margin))
+        sm = mm if soft_margin is None else float(np.float32(soft_margin))
+    if not math.isfinite(mm):
+        raise ValueError("min_margin must be a finite distance in metres, got %r" % (min_margin,))
+    if not math.isfinite(sm):
+        raise ValueError("soft_margin must be a finite distance in metres, got %r" % (soft_margin,))
+    if sm < mm:
+        raise ValueError("soft_margin must not be less than min_margin, got %r < %r" % (soft_margin, min_margin))
+    return mm, sm
+
+
+def _pose_body(body, body_blocks, squeeze_weight):
+    """the body keywords of the pose_field calls -> None, or (the volume's product id, block mask, squeeze weight)"""
+    if body is None:
+        if squeeze_weight != 0:
+            raise ValueError("squeeze_weight needs a body volume (body=...)")
+        return None
+    if not isinstance(body, DeviceBodyVolume):
+        raise TypeError("body must be a DeviceBodyVolume (DeviceDistanceField.body_volume()), got %r" % (type(body).__name__,))
+    mask = 0
+    try:
+        for b in body_blocks:
+            if isinstance(b, bool) or int(b) != b or not 0 <= int(b) <= 5:
+                raise ValueError
+            mask |= 1 << int(b)
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError("body_blocks must be a sequence of BODY_* codes 0 .. 5, got %r" % (body_blocks,))
+    try:
+        ok = not isinstance(squeeze_weight, bool) and int(squeeze_weight) == squeeze_weight and 0 <= int(squeeze_weight) <= 255
+    except (TypeError, ValueError, OverflowError):
+        ok = False
+    if not ok:
+        raise ValueError("squeeze_weight must be an integer in 0 .. 255, got %r" % (squeeze_weight,))
+    return body.product_id, mask, int(squeeze_weight)
 
 
 # ---- frontier extraction (DeviceCostField.frontiers, Gvom.frontiers_of and friends; include/gvom_hip.h "frontier extraction") ----
@@ -2352,6 +2427,24 @@ class DeviceDistanceField(_ProductView):
         a = _rollout_poses(poses)
         return g._score_body(self.product_id, None, None, -1, _ptr(gm), _ptr(a), a.shape[0], a.shape[1], 0, False, origin, min_margin)
 
+    def body_volume(self, device_maps, min_margin=0.0, soft_margin=None, inferred_ground=True):
+        """score_body() at EVERY state of the window -- the centre of each cell of `device_maps` (a DeviceMaps) at each heading of the
+        mapper's footprint table -- without a pose array: a DeviceBodyVolume (status, squeeze and clearance per state), one kernel on
+        the GPU behind the passes that wrote the field and the combine that wrote the set; no host wait.  A state collides where its
+        clearance < min_margin; its squeeze says how much of the band from soft_margin (None: min_margin -- squeeze is 100 at a
+        collision and 0 elsewhere) down to min_margin it has used up.  DeviceCostField.pose_field(body=...) takes it into a pose
+        field.  Needs set_footprint, set_chassis and set_body.  include/gvom_hip.h "body volumes" has the definition."""
+        g = self._hold._owner
+        return g._body_volume(self.product_id, None, None, device_maps.set_id, None, 0, bool(inferred_ground), device_maps.origin, min_margin,
+                              soft_margin)
+
+    def body_volume_of(self, ground, origin=(0.0, 0.0), min_margin=0.0, soft_margin=None):
+        """body_volume() on a ground map of the caller's: a numpy [x, y] array of shape (xy_size, xy_size), heights in metres as
+        Gvom.score_attitude_of takes them; origin: the window corner in world metres."""
+        g = self._hold._owner
+        gm = g._window_map("ground", ground, np.float64)
+        return g._body_volume(self.product_id, None, None, -1, _ptr(gm), 0, False, origin, min_margin, soft_margin)
+
     def sample(self, points):
         """The field at the voxels of world points float32 [n, 3] in metres -- floor(p / resolution) per axis, no interpolation: a
         DeviceDistanceSamples.  A body sphere of radius r at p is clear of every source where sample(p) >= r + the voxel's half
@@ -3329,6 +3422,35 @@ class Gvom(object):
         return self._score_body(-1, _dev(field_ptr), _voxel_origin(field_origin_voxels, "field_origin_voxels"), -1, _dev(ground_ptr),
                                 _dev(poses_ptr), K, T, 1, False, origin, min_margin)
 
+    # ---- body volumes (an extension; include/gvom_hip.h "body volumes") ----
+    def _body_volume(self, field_id, field_ptr, field_origin, set_id, ground_ptr, on_device, inferred_ground, origin, min_margin, soft_margin):
+        oc = _rollout_origin(origin, self.xy_resolution)
+        flags = _ATTITUDE_INFERRED_GROUND if inferred_ground else 0
+        mm, sm = _body_margins(min_margin, soft_margin)
+        return DeviceBodyVolume(self._make_product(lambda pid: self._lib.gvom_body_volume(
+            self._h, int(field_id), field_ptr, field_origin, int(set_id), ground_ptr, int(on_device), flags, oc, ctypes.c_float(mm),
+            ctypes.c_float(sm), pid), PRODUCT_BODY_VOLUME, self._check_args))
+
+    def body_volume_of(self, field, field_origin_voxels, ground, origin=(0.0, 0.0), min_margin=0.0, soft_margin=None):
+        """DeviceDistanceField.body_volume() with a field AND a ground map of the caller's: field and field_origin_voxels as
+        score_body_of takes them, ground as score_attitude_of takes it; origin: the window corner in world metres.  Needs no scan and
+        no combine.  A convenience route: field and map are copied to the device."""
+        f = np.ascontiguousarray(np.asarray(field), dtype=np.float32)
+        if f.shape != (self.xy_size, self.xy_size, self.z_size):
+            raise ValueError("field must have shape (%d, %d, %d), got %r" % (self.xy_size, self.xy_size, self.z_size, f.shape))
+        gm = self._window_map("ground", ground, np.float64)
+        return self._body_volume(-1, _ptr(f), _voxel_origin(field_origin_voxels, "field_origin_voxels"), -1, _ptr(gm), 0, False, origin,
+                                 min_margin, soft_margin)
+
+    def body_volume_of_device(self, field_ptr, field_origin_voxels, ground_ptr, origin=(0.0, 0.0), min_margin=0.0, soft_margin=None):
+        """The same for a field and a map in device memory: raw device addresses of xy_size*xy_size*z_size float32 ([x][y][z]) and
+        xy_size*xy_size float64 (cell (x, y) at [y*xy_size + x]); the data must be ready when the call is made.  Enqueues and returns:
+        no host wait."""
+        if not field_ptr or not ground_ptr:
+            raise ValueError("field_ptr and ground_ptr must be device addresses")
+        return self._body_volume(-1, _dev(field_ptr), _voxel_origin(field_origin_voxels, "field_origin_voxels"), -1, _dev(ground_ptr), 1,
+                                 False, origin, min_margin, soft_margin)
+
     # ---- attitude volumes (an extension; include/gvom_hip.h "attitude volumes") ----
     def _attitude_volume(self, set_id, ground_ptr, on_device, inferred_ground):
         flags = _ATTITUDE_INFERRED_GROUND if inferred_ground else 0
@@ -3418,10 +3540,15 @@ class Gvom(object):
             raise ValueError("no primitive table is set (Gvom.set_primitives)")
         return self._primitives[0].shape[0] - 1
 
-    def _pose_field(self, field_id, cost_ptr, on_device, cells, max_cost, max_rounds, origin, attitude=None):
+    def _pose_field(self, field_id, cost_ptr, on_device, cells, max_cost, max_rounds, origin, attitude=None, body=None):
         info = (_I64 * 4)()
         table = self._primitives
-        if attitude is None:
+        if body is not None:
+            a = attitude if attitude is not None else (-1, 0, 0)
+            call = lambda pid: self._lib.gvom_pose_field_volumes(
+                self._h, int(field_id), cost_ptr, int(on_device), a[0], a[1], a[2], body[0], body[1], body[2], _ptr(cells), cells.shape[0],
+                max_cost, max_rounds, pid, info)
+        elif attitude is None:
             call = lambda pid: self._lib.gvom_pose_field(
                 self._h, int(field_id), cost_ptr, int(on_device), _ptr(cells), cells.shape[0], max_cost, max_rounds, pid, info)
         else:
@@ -3431,19 +3558,20 @@ class Gvom(object):
         hold = self._make_product(call, PRODUCT_POSEFIELD, self._check_args)
         return DevicePoseField(hold, list(info), origin, table)
 
-    def pose_field_of(self, cost, goals, max_cost=None, max_rounds=0, origin=(0.0, 0.0), attitude=None, attitude_blocks=_ATTITUDE_BLOCKS, tilt_weight=0):
+    def pose_field_of(self, cost, goals, max_cost=None, max_rounds=0, origin=(0.0, 0.0), attitude=None, attitude_blocks=_ATTITUDE_BLOCKS, tilt_weight=0,
+                      body=None, body_blocks=_BODY_BLOCKS, squeeze_weight=0):
         """DeviceCostField.pose_field() of a cost map of the caller's: a numpy [x, y] array of shape (xy_size, xy_size) in any memory
         order, integers in 0 .. 65535 (0 = blocked); goals: (G, 2) or (G, 3) = (x, y[, yaw]) in window cells and radians.  Needs no
         scan and no combine.  A convenience route: the map is copied to the device.  origin: kept as the field's `.origin`.
-        attitude, attitude_blocks, tilt_weight: as DeviceCostField.pose_field()."""
+        attitude, attitude_blocks, tilt_weight, body, body_blocks, squeeze_weight: as DeviceCostField.pose_field()."""
         H = self._pose_headings()
         c = self._window_map("cost", np.asarray(cost), np.int32, (0, 65535), range_note=" (0 = blocked)")
         cells = _pose_goals(goals, self.xy_size, H, None)
         return self._pose_field(-1, _ptr(c), 0, cells, _ctg_max_cost(max_cost), _ctg_max_rounds(max_rounds), origin,
-                                _pose_attitude(attitude, attitude_blocks, tilt_weight))
+                                _pose_attitude(attitude, attitude_blocks, tilt_weight), _pose_body(body, body_blocks, squeeze_weight))
 
     def pose_field_of_device(self, cost_ptr, goals, max_cost=None, max_rounds=0, origin=(0.0, 0.0), attitude=None, attitude_blocks=_ATTITUDE_BLOCKS,
-                             tilt_weight=0):
+                             tilt_weight=0, body=None, body_blocks=_BODY_BLOCKS, squeeze_weight=0):
         """The same for a cost map in device memory (the raw device address of xy_size*xy_size int32, cell (x, y) at
         [y*xy_size + x]; the data must be ready when the call is made).  Values outside 0 .. 65535 are clamped into the range."""
         if not cost_ptr:
@@ -3451,7 +3579,7 @@ class Gvom(object):
         H = self._pose_headings()
         cells = _pose_goals(goals, self.xy_size, H, None)
         return self._pose_field(-1, _dev(cost_ptr), 1, cells, _ctg_max_cost(max_cost), _ctg_max_rounds(max_rounds), origin,
-                                _pose_attitude(attitude, attitude_blocks, tilt_weight))
+                                _pose_attitude(attitude, attitude_blocks, tilt_weight), _pose_body(body, body_blocks, squeeze_weight))
 
     # ---- map atlas (an extension; include/gvom_hip.h "map atlas") ----
     def create_atlas(self, cells, follow=True, origin_cells=None):

@@ -1380,6 +1380,73 @@ int gvom_score_body(gvom_t *h, int64_t field_product_id, const float *field, con
                     const double *ground, const float *poses /* [K][T][3] */, int64_t K, int64_t T, int on_device, int flags,
                     const int64_t origin_cells[2], float min_margin, int64_t *product_id);
 
+/* --- body volumes (an extension: 3-D body clearance per heading at every cell of the window, and the pose field that plans through it --
+ * the gate bar the low vehicle drives under is no wall, and the tall vehicle goes round) --------------------------------------------------
+ * gvom_score_body says whether the sphere body passes at poses a caller already chose.  gvom_body_volume evaluates the same arithmetic at
+ * EVERY state (cell centre, heading) of the window -- one kernel, no pose array -- and leaves the result in device memory as a product
+ * (kind GVOM_PRODUCT_BODY_VOLUME) that gvom_device_product_export / _release / _dlpack / _copy handle like the others.
+ * gvom_pose_field_volumes is gvom_pose_field with an attitude volume, a body volume, or both taken into its pose cost volume.
+ * gvom_get_tuning "body_volume" (read-only): 1 -- how a caller probes a library for these entry points (an addition: GVOM_ABI_VERSION
+ * stays).  Every float64 operation below is ONE IEEE operation in the order written, no contraction: the result is exact, and every
+ * decision is taken on the float32 values that are stored.
+ *
+ * DEFINITION.  res = xy_resolution, xy = xy_size, o = origin_cells, |o| <= 2^40.
+ * STATE      (cx, cy, h): the centre of window cell (cx, cy) at heading h of the footprint table; (c, s) = cos_sin[h] of gvom_chassis_set.
+ *            A footprint table, a chassis of equal H and a body table (gvom_body_set) must be set.  GVOM_BODY_INVALID cannot occur.
+ * GROUND, FIELD   "body clearance scoring"'s, word for word: a map set (flags GVOM_ATTITUDE_INFERRED_GROUND or 0) or the caller's float64
+ *            map; a live GVOM_PRODUCT_VOXEL_DISTANCE or the caller's float32 field with field_origin[3].  READ-ONLY on the field: the
+ *            caller may release it as soon as the call returns.
+ * WHEEL CELLS, STANCE   "attitude volumes"' rule, word for word: wheel i of heading h stands in cell (cx + floor(0.5 + wx[h][i] / res),
+ *            cy + floor(0.5 + wy[h][i] / res)), window-relative; z_i = g at that cell; KNOWN, sp, sr, z0 and am are that section's.  Only
+ *            the four wheel cells are tested against the window: the footprint cells are not walked.
+ * FRAME, SPHERE CENTRE, MARGIN   "body clearance scoring"'s, word for word: e1, n, e2, q0; Cu, Cv, Cw; m_i, clearance and tightest.  The
+ *            pose's world position is X0 = ((double)(ox + cx) + 0.5) * res, Y0 = ((double)(oy + cy) + 0.5) * res;
+ *            X = X0 + (Cu*c - Cv*s);  Y = Y0 + (Cu*s + Cv*c);  Z = Cw.  The voxel and the OUTSIDE rule are that section's.
+ * STATUS     the first that applies: GVOM_BODY_LEFT_WINDOW: a wheel cell is outside the window; _UNKNOWN_GROUND: a wheel cell's ground is
+ *            unknown; _LEFT_BOX: a sphere's voxel is outside the box; _COLLISION: clearance < min_margin, a float32 comparison; _OK.
+ * SQUEEZE    uint8: how much of the band between soft_margin and min_margin the state has used up.  0 where the status is LEFT_WINDOW,
+ *            UNKNOWN_GROUND or LEFT_BOX.  Elsewhere, with m = min_margin, f = soft_margin (finite, f >= m), k = clearance, all float32:
+ *            0 if k >= f; 100 if k <= m or f == m; otherwise t = ((double)f - (double)k) / ((double)f - (double)m) * 100.0 and
+ *            squeeze = !(t > 0) ? 0 : (t >= 100 ? 100 : (uint8)floor(t)).  A clearance of +inf gives 0.
+ * part 0 = uint8 status, part 1 = uint8 squeeze, part 2 = float32 clearance (0 where the status is LEFT_WINDOW, UNKNOWN_GROUND or
+ * LEFT_BOX): each [H, xy, xy], indexed [h, x, y], strides (xy*xy, 1, xy) -- every plane has a pose field plane's layout.
+ * part 3 = int32 [8]: the number of states per status code 0 .. 5, then H, then S.
+ *
+ * gvom_body_volume: on_device, the flags and the staging of a host field and ground map are gvom_score_body's; the call is enqueued on the
+ * handle's stream and returns without a host wait (after the upload of host inputs).  The wheel offsets come from the attitude volume's
+ * table, rebuilt by the same rule (the first call of either entry point after a gvom_footprint_set / gvom_chassis_set).  The product is a
+ * snapshot: later scans, combines, integrates, gvom_footprint_set, gvom_chassis_set and gvom_body_set calls do not change it.  Products
+ * of this kind live in the product-set pool ("device_product_sets"), sized by H and xy_size: at most GVOM_MAX_PRODUCT_SETS.
+ * "body_volume_allocations" (read-only): device allocations the entry point has made on this handle (the ground map of the map-set
+ * route, the staging buffer of the host route and its product sets); it does not grow in steady state.
+ * gvom_device_product(GVOM_PRODUCT_BODY_VOLUME) is GVOM_ERR_INVALID (this call makes them).  Kind 45 is not assigned.
+ * Errors: the union of gvom_score_body's and gvom_attitude_volume's.  GVOM_ERR_INVALID: a sharded handle; no footprint table, no
+ * chassis, or unequal H; no body table; a set id AND a ground pointer, or neither; an unknown or stale set id; a field id AND a field
+ * pointer or origin, or neither; a stale field id or one of another kind; a NULL field_origin on the pointer route or one beyond 2^40
+ * voxels; a NaN or infinite min_margin; a NaN or infinite soft_margin; soft_margin < min_margin; unknown flag bits; NULL origin_cells /
+ * product_id; an origin beyond 2^40 cells.  GVOM_ERR_CAPACITY: H > 64; xy_size > 4096; H * xy_size^2 > 2^28; every set of the kind
+ * exported.
+ *
+ * gvom_pose_field_volumes is gvom_pose_field -- the same arguments, checks, codes, product, info, tuning names and pool -- with two
+ * optional volumes.  Either volume id may be -1 (none); its mask and weight must then be 0.  Behind the pose cost volume C of "pose
+ * fields", the attitude volume gives C' as gvom_pose_field_attitude does (C' = C without one).  Then C''[h][cell] = 0 where C' == 0 or bit
+ * `status` of body_block_mask is set (bit k = GVOM_BODY_* code k), otherwise C'' = min(65535, C' + squeeze_weight * squeeze); seeding,
+ * relaxation, actions and part 2 of the product take C''.  With body_volume_id = -1 the result is gvom_pose_field_attitude's bit for bit;
+ * with both -1 it is gvom_pose_field's.  In addition GVOM_ERR_INVALID: attitude_block_mask > 0x7f; body_block_mask > 0x3f; tilt_weight or
+ * squeeze_weight outside 0 .. 255; a mask or weight that is not 0 beside an id of -1; a stale volume id, an id of another kind, or a
+ * volume of another H or xy_size.
+ * NOT PROVIDED: interpolation in the field; states between cell centres; swept volumes between a primitive's ends; body volumes over the
+ * atlas extent; a float32 clearance taken into the cost other than through squeeze; sharded handles. */
+#define GVOM_PRODUCT_BODY_VOLUME 46   /* parts 0, 1 uint8 status, squeeze, part 2 float32 clearance: [H, xy, xy], strides (xy*xy, 1, xy); part 3 int32 [8] */
+/* 45 stays unassigned: tests/body_volume_layout_host_test.cpp holds it to "no such kind" */
+int gvom_body_volume(gvom_t *h, int64_t field_product_id, const float *field, const int64_t field_origin[3], int64_t map_set_id,
+                     const double *ground, int on_device, int flags, const int64_t origin_cells[2], float min_margin, float soft_margin,
+                     int64_t *product_id);
+int gvom_pose_field_volumes(gvom_t *h, int64_t costfield_id, const int32_t *cost, int on_device, int64_t attitude_volume_id,
+                            uint32_t attitude_block_mask, int32_t tilt_weight, int64_t body_volume_id, uint32_t body_block_mask,
+                            int32_t squeeze_weight, const int32_t *goals /* [n_goals][3] */, int64_t n_goals, int32_t max_cost,
+                            int32_t max_rounds, int64_t *product_id, int64_t info[4]);
+
 /* --- one map sharded over the GPUs of a node (one rank = one process = one GPU) -------------------
  * No counterpart in the reference (it has no multi-GPU path); semantics = SURVEY 8(e):
  * the rays are data-parallel, the per-voxel accumulators (hit / total: int32 sum, min-height: f32 min)
@@ -1636,6 +1703,7 @@ int gvom_host_timing(gvom_t *h, double us[8]);
  * "viewpoints" / "viewpoint_allocations" / "viewpoint_batch" (read-only, gvom_get_tuning), "viewpoint_bitmap_mb": see "viewpoint
  * scoring" above.
  * "attitude_volume" / "attitude_volume_allocations" (read-only, gvom_get_tuning): see "attitude volumes" above.
+ * "body_volume" / "body_volume_allocations" (read-only, gvom_get_tuning): see "body volumes" above.
  * "voxel_distance_field" / "voxel_distance_halo_xy" / "voxel_distance_halo_z" (read-only, gvom_get_tuning), "voxel_distance_mb": see
  * "voxel distance field" above.
  * (Test hooks are not part of this library: include/gvom_hip_test.h, lib/libgvom_hip_test.so.) */

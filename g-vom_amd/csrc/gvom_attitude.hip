@@ -16,19 +16,10 @@
 // outside the window read nothing, and a pose whose wheels stand on unknown ground reads no footprint cell.  No scratch, no atomics,
 // no wait on another workgroup; every loop is bounded at launch (T <= 4096 poses, <= 16384 cells per heading).  Every float64
 // operation is one IEEE operation in the header's order (-ffp-contract=off): the result is exact.
-#include "gvom_rollouts.h"                                  // (with the wheel and plane arithmetic k_body shares: at_known, at_cell, at_stance, at_better)
+#include "gvom_rollouts.h"                                  // (the one text of the vehicle on the ground and of a rollout's summary: AT_*, at_*)
 
 #define AT_WAVES 4          // waves per workgroup (fewer where T is smaller)
 #define AT_DEPTH 4          // footprint cells per lane whose loads are in flight together
-
-// status words (include/gvom_hip.h GVOM_ATTITUDE_*)
-#define AT_OK 0
-#define AT_PITCH 1
-#define AT_ROLL 2
-#define AT_BELLY 3
-#define AT_UNKNOWN_GROUND 4
-#define AT_LEFT_WINDOW 5
-#define AT_INVALID 6
 
 __global__ __launch_bounds__(256) void k_attitude_ground(int n2, int inferred, const double *__restrict__ height,
                                                          const double *__restrict__ inferred_height, double *__restrict__ ground)
@@ -60,20 +51,11 @@ __global__ __launch_bounds__(AT_WAVES * WAVE) void k_attitude(const AttitudePara
         double sp = 0.0, sr = 0.0, belly = (double)INFINITY;
         if (valid) {
             const double x = (double)pk[3 * t], y = (double)pk[3 * t + 1];
-            uint32_t wxc[4], wyc[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                wxc[i] = (uint32_t)at_cell(x + wheels[(h * 4 + i) * 2], P.R.res, P.R.ox);
-                wyc[i] = (uint32_t)at_cell(y + wheels[(h * 4 + i) * 2 + 1], P.R.res, P.R.oy);
-                wheel_out = wheel_out || !(wxc[i] < uxy && wyc[i] < uxy);
-            }
+            AtCells wc;
+            wheel_out = at_pose_cells(P.R, wheels, h, x, y, wc);
             if (!wheel_out) {
                 double z[4];
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    z[i] = G[mad24s(wyc[i], uxy, wxc[i])];
-                    wheel_unknown = wheel_unknown || !at_known(z[i]);
-                }
+                wheel_unknown = at_pose_heights(G, uxy, wc, z);
                 const bool ok = !wheel_unknown;
                 const AtStance a = at_stance(z, P.wheelbase, P.track);
                 sp = a.sp;
@@ -135,12 +117,7 @@ __global__ __launch_bounds__(AT_WAVES * WAVE) void k_attitude(const AttitudePara
     }
     __syncthreads();
     if (w == 0) {                                             // the summary: the first bad pose, the three arg-extremes in front of it
-        int first = T;
-        for (int t0 = 0; t0 < T; t0 += WAVE) {
-            const int t = t0 + lane;
-            const unsigned long long bad = lanes(t < T && s_st[t] != AT_OK);
-            if (bad != 0ull) { first = t0 + __builtin_ctzll(bad); break; }
-        }
+        const int first = at_first_bad(T, lane, [=](int t) { return s_st[t] != AT_OK; });
         float kp = -INFINITY, kr = -INFINITY, kb = -INFINITY;
         int tp = INT_MAX, tr = INT_MAX, tb = INT_MAX;
         for (int t = lane; t < first; t += WAVE) {

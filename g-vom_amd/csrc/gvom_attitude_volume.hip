@@ -7,10 +7,10 @@
 //                            same order), and per heading the four wheels' cell offsets floor(0.5 + w / res) and the footprint's box.
 //   k_volume_attitude        k_cspace's shape: blockIdx.y is the heading, the lanes run over consecutive cells of a row.  The wheel
 //                            offsets, the footprint list and the (U, V) table are wave-uniform and come through scalar loads; a lane
-//                            loads its four wheel heights and tests the footprint's box against the window once, then per footprint
+//                            loads its four wheel heights (gvom_rollouts.h at_state_wheels, at_stance: k_attitude's text) and tests the footprint's box against the window once, then per footprint
 //                            cell ONE coalesced 8-byte ground height at (a uniform address) + (its own cell), AV_DEPTH of them in
-//                            flight, and keeps the least of ((z0 + sp*U) + sr*V + belly_height) - g.  A wave ends in one ballot
-//                            and one population count per status: at most six int32 atomics per wave, integer sums.
+//                            flight, and keeps the least of ((z0 + sp*U) + sr*V + belly_height) - g.  A wave ends in at_tally: one ballot
+//                            and one population count per status, at most six int32 atomics per wave, integer sums.
 //   k_cspace_attitude        elementwise over a pose cost volume: C' = 0 where C == 0 or the state's status is one of block_mask's,
 //                            min(65535, C + tilt_weight * tilt) elsewhere.
 //
@@ -18,20 +18,10 @@
 // whose wheels stand outside the window or on unknown ground reads no footprint cell.  No scratch, no LDS, no wait on another
 // workgroup; every loop is bounded at launch (<= 16384 cells per heading).  Every float64 operation is one IEEE operation in the
 // header's order (-ffp-contract=off): the result is exact.
-#include "gvom_device.h"
+#include "gvom_rollouts.h"                                  // (the status words, the wheels, the stance and the census: AT_*, at_*)
 
 #define AV_DEPTH 4          // footprint cells per lane whose loads are in flight together
 #define AV_FAR (1 << 20)    // a wheel offset that lies outside every window (xy <= 4096)
-
-// status words (include/gvom_hip.h GVOM_ATTITUDE_*)
-#define AV_OK 0
-#define AV_PITCH 1
-#define AV_ROLL 2
-#define AV_BELLY 3
-#define AV_UNKNOWN_GROUND 4
-#define AV_LEFT_WINDOW 5
-
-__device__ __forceinline__ bool av_known(double g) { return g > -1000.0 && g < (double)INFINITY; }
 
 // floor(0.5 + w / res), +-AV_FAR where that is no cell of any window
 __device__ __forceinline__ int av_wheel_offset(double w, double res)
@@ -87,26 +77,10 @@ __global__ __launch_bounds__(256) void k_volume_attitude(const AttitudeVolumePar
     const int y = i / P.xy, x = i - y * P.xy;
     const uint32_t uxy = (uint32_t)P.xy;
     if (blockIdx.x == 0 && h == 0 && threadIdx.x == 0) counts[7] = P.H;
-    bool wheel_out = false, wheel_unknown = false;
-    uint32_t wi[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const uint32_t X = (uint32_t)(x + wcell[h * 12 + 2 * k]), Y = (uint32_t)(y + wcell[h * 12 + 2 * k + 1]);
-        wheel_out = wheel_out || !(X < uxy && Y < uxy);
-        wi[k] = Y * uxy + X;
-    }
-    const bool wheels_in = live && !wheel_out;
-    double z[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        z[k] = wheels_in ? G[wi[k]] : -1000.0;                            // (a wheel that is not read: unknown)
-        wheel_unknown = wheel_unknown || !av_known(z[k]);
-    }
-    const bool ok = wheels_in && !wheel_unknown;
-    const double zF = 0.5 * (z[0] + z[1]), zR = 0.5 * (z[2] + z[3]), zL = 0.5 * (z[0] + z[2]), zT = 0.5 * (z[1] + z[3]);
-    const double sp = (zF - zR) / P.wheelbase;
-    const double sr = (zL - zT) / P.track;
-    const double z0 = 0.25 * ((z[0] + z[1]) + (z[2] + z[3]));
+    const AtWheels W = at_state_wheels(wcell, G, h, x, y, uxy, live);
+    const bool wheel_out = W.out, wheel_unknown = W.unknown, ok = W.ok;
+    const AtStance a = at_stance(W.z, P.wheelbase, P.track);
+    const double sp = a.sp, sr = a.sr, z0 = a.z0;
     // a footprint cell lies outside the window iff the footprint's box does (its corners are offsets of the list): ONE test per state
     // instead of one per cell, and the states that pass it read every cell of the list unconditionally
     const int lo_x = wcell[h * 12 + 8], hi_x = wcell[h * 12 + 9], lo_y = wcell[h * 12 + 10], hi_y = wcell[h * 12 + 11];
@@ -127,7 +101,7 @@ __global__ __launch_bounds__(256) void k_volume_attitude(const AttitudeVolumePar
             for (int d = 0; d < AV_DEPTH; ++d) {
                 const double2 q = uv[b + m + d];
                 const double clr = (((z0 + sp * q.x) + sr * q.y) + P.belly_height) - g[d];
-                if (av_known(g[d]) && clr < belly) belly = clr;           // (a NaN clearance is skipped)
+                if (at_known(g[d]) && clr < belly) belly = clr;           // (a NaN clearance is skipped)
             }
         }
         for (; m < M; ++m) {
@@ -136,19 +110,19 @@ __global__ __launch_bounds__(256) void k_volume_attitude(const AttitudeVolumePar
             const double g = Gm[i];
             const double2 q = uv[b + m];
             const double clr = (((z0 + sp * q.x) + sr * q.y) + P.belly_height) - g;
-            if (av_known(g) && clr < belly) belly = clr;
+            if (at_known(g) && clr < belly) belly = clr;
         }
     }
     const float p = (float)sp, r = (float)sr, bl = (float)belly;
     int st;
-    if (wheel_out || out) st = AV_LEFT_WINDOW;
-    else if (wheel_unknown) st = AV_UNKNOWN_GROUND;
-    else if (fabsf(p) > P.max_pitch) st = AV_PITCH;
-    else if (fabsf(r) > P.max_roll) st = AV_ROLL;
-    else if (bl < P.min_clearance) st = AV_BELLY;
-    else st = AV_OK;
+    if (wheel_out || out) st = AT_LEFT_WINDOW;
+    else if (wheel_unknown) st = AT_UNKNOWN_GROUND;
+    else if (fabsf(p) > P.max_pitch) st = AT_PITCH;
+    else if (fabsf(r) > P.max_roll) st = AT_ROLL;
+    else if (bl < P.min_clearance) st = AT_BELLY;
+    else st = AT_OK;
     uint32_t tl = 0u;
-    if (st < AV_UNKNOWN_GROUND) {
+    if (st < AT_UNKNOWN_GROUND) {
         const double tp = av_share(p, P.max_pitch), tr = av_share(r, P.max_roll);
         const double t = tp > tr ? tp : tr;
         tl = !(t > 0.0) ? 0u : (t >= 100.0 ? 100u : (uint32_t)floor(t));
@@ -158,12 +132,7 @@ __global__ __launch_bounds__(256) void k_volume_attitude(const AttitudeVolumePar
         status[at] = (uint8_t)st;
         tilt[at] = (uint8_t)tl;
     }
-    const int lane = (int)(threadIdx.x & 63u);
-#pragma unroll
-    for (int s = 0; s <= AV_LEFT_WINDOW; ++s) {
-        const int n = __builtin_popcountll(lanes(live && st == s));
-        if (n != 0 && lane == 0) atomicAdd(&counts[s], n);
-    }
+    at_tally(counts, AT_LEFT_WINDOW, live, st);
 }
 
 __global__ __launch_bounds__(256) void k_cspace_attitude(const size_t n, const uint8_t *__restrict__ status, const uint8_t *__restrict__ tilt,

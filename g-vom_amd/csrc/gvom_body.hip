@@ -3,8 +3,8 @@
 // (include/gvom_hip.h "body clearance scoring" defines the result).
 //
 //   k_body   one workgroup per rollout, ONE POSE PER LANE (k_volume_attitude's shape, not k_attitude's: a pose's work is S gathers, not a
-//            footprint of thousands of cells).  A lane makes its pose's frame once -- the pose frame of gvom_rollouts.h, the four wheel
-//            heights and the stance as k_attitude makes them, then e1, e2, n and q0 -- and keeps it in registers.  The sphere table is
+//            footprint of thousands of cells).  A lane makes its pose's frame once -- the pose frame, the four wheel heights and the
+//            stance of gvom_rollouts.h (k_attitude's text), then e1, e2, n and q0 -- and keeps it in registers.  The sphere table is
 //            walked by a wave-uniform index, so (bx, by, bz, r) are scalar loads; each lane issues one 4-byte gather per sphere,
 //            BD_DEPTH spheres' gathers in flight.  Status, clearance and tightest sphere go to LDS, 6 bytes per pose; behind one barrier
 //            wave 0 makes the four summary words -- a ballot finds the first bad pose, a shuffle the least clearance in front of it --
@@ -31,7 +31,6 @@ __global__ __launch_bounds__(BD_WAVES * WAVE) void k_body(const BodyParams P, co
     const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const size_t k = blockIdx.x;
     const float *pk = poses + k * (size_t)T * 3;
-    const uint32_t uxy = (uint32_t)P.R.xy;
     for (int t = (int)threadIdx.x; t < T; t += (int)blockDim.x) {
         int cx, cy, h;
         const bool valid = ro_pose(P.R, pk + 3 * t, cx, cy, h);
@@ -39,23 +38,9 @@ __global__ __launch_bounds__(BD_WAVES * WAVE) void k_body(const BodyParams P, co
         const double x = (double)pk[3 * t], y = (double)pk[3 * t + 1];
         double z[4] = {0.0, 0.0, 0.0, 0.0}, c = 1.0, s = 0.0;
         if (valid) {
-            uint32_t wxc[4], wyc[4];
-            bool wheel_out = false, wheel_unknown = false;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                wxc[i] = (uint32_t)at_cell(x + wheels[(h * 4 + i) * 2], P.R.res, P.R.ox);
-                wyc[i] = (uint32_t)at_cell(y + wheels[(h * 4 + i) * 2 + 1], P.R.res, P.R.oy);
-                wheel_out = wheel_out || !(wxc[i] < uxy && wyc[i] < uxy);
-            }
-            if (wheel_out) st = BD_LEFT_WINDOW;
-            else {
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    z[i] = G[mad24s(wyc[i], uxy, wxc[i])];
-                    wheel_unknown = wheel_unknown || !at_known(z[i]);
-                }
-                if (wheel_unknown) st = BD_UNKNOWN_GROUND;
-            }
+            AtCells wc;
+            if (at_pose_cells(P.R, wheels, h, x, y, wc)) st = BD_LEFT_WINDOW;
+            else if (at_pose_heights(G, (uint32_t)P.R.xy, wc, z)) st = BD_UNKNOWN_GROUND;
             c = cos_sin[2 * h]; s = cos_sin[2 * h + 1];
         }
         const bool ok = st == BD_OK;
@@ -87,12 +72,7 @@ __global__ __launch_bounds__(BD_WAVES * WAVE) void k_body(const BodyParams P, co
     }
     __syncthreads();
     if (w == 0) {                                             // the summary: the first bad pose, the least clearance in front of it
-        int first = T;
-        for (int t0 = 0; t0 < T; t0 += WAVE) {
-            const int t = t0 + lane;
-            const unsigned long long bad = lanes(t < T && (s_pr[t] & 0xffu) != BD_OK);
-            if (bad != 0ull) { first = t0 + __builtin_ctzll(bad); break; }
-        }
+        const int first = at_first_bad(T, lane, [=](int t) { return (s_pr[t] & 0xffu) != BD_OK; });
         float kc = -INFINITY;
         int tc = INT_MAX;
         for (int t = lane; t < first; t += WAVE) at_better(kc, tc, -s_clr[t], t);        // (a clearance is never NaN)

@@ -5,12 +5,12 @@
 //   k_volume_body   a workgroup takes a 16 x 16 TILE of cells at one heading (blockIdx.z), ONE STATE PER LANE, x the fast lane index: a
 //                   wave is 16 cells of x by 4 of y.  The field is out[x][y][z], so one sphere's 256 gathers of a workgroup fall into a
 //                   (16 + tilt spread)^2 x few-levels neighbourhood instead of a whole row's xy*zs*4-byte stride.  The four wheel gathers
-//                   come through the attitude volume's per-heading wheel-offset table (wcell), the stance and the frame are made once per
-//                   lane (gvom_bodyframe.h: k_body's text), the sphere table is walked by a wave-uniform index -- (bx, by, bz, r) are
+//                   come through the attitude volume's per-heading wheel-offset table (wcell; gvom_rollouts.h at_state_wheels:
+//                   k_volume_attitude's text), the stance and the frame are made once per lane (gvom_bodyframe.h: k_body's text), the sphere table is walked by a wave-uniform index -- (bx, by, bz, r) are
 //                   scalar loads --, one 4-byte gather per sphere, BV_DEPTH in flight.  A wave none of whose states stands on known
 //                   ground inside the window walks no sphere.  With x the fast lane index the three stores are already runs along x (16
-//                   bytes of status, 16 of squeeze, 64 of clearance per tile row): no LDS.  A wave ends in one ballot and one population
-//                   count per status: at most five int32 atomics per wave (INVALID cannot occur), integer sums.
+//                   bytes of status, 16 of squeeze, 64 of clearance per tile row): no LDS.  A wave ends in at_tally: one ballot and one
+//                   population count per status, at most five int32 atomics per wave (INVALID cannot occur), integer sums.
 //
 // READ-ONLY on the ground map and the field.  No load without its bounds test in front of it: a wheel outside the window reads nothing,
 // a sphere outside the box reads nothing, and a state whose wheels stand outside or on unknown ground reads no field value.  No scratch,
@@ -33,25 +33,11 @@ __global__ __launch_bounds__(BV_TILE * BV_TILE) void k_volume_body(const BodyPar
     const bool live = cx < xy && cy < xy;                                // (no early return: the ballots below take whole waves)
     const uint32_t uxy = (uint32_t)xy;
     if (blockIdx.x == 0 && blockIdx.y == 0 && h == 0 && threadIdx.x == 0) { counts[6] = P.R.H; counts[7] = S; }
-    bool wheel_out = false, wheel_unknown = false;
-    uint32_t wi[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const uint32_t X = (uint32_t)(cx + wcell[h * 12 + 2 * k]), Y = (uint32_t)(cy + wcell[h * 12 + 2 * k + 1]);
-        wheel_out = wheel_out || !(X < uxy && Y < uxy);
-        wi[k] = Y * uxy + X;
-    }
-    const bool wheels_in = live && !wheel_out;
-    double z[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        z[k] = wheels_in ? G[wi[k]] : -1000.0;                           // (a wheel that is not read: unknown)
-        wheel_unknown = wheel_unknown || !at_known(z[k]);
-    }
-    const bool ok = wheels_in && !wheel_unknown;
+    const AtWheels W = at_state_wheels(wcell, G, h, cx, cy, uxy, live);
+    const bool wheel_out = W.out, wheel_unknown = W.unknown, ok = W.ok;
     const double c = cos_sin[2 * h], s = cos_sin[2 * h + 1];
     const double x = ((double)(P.R.ox + cx) + 0.5) * P.R.res, y = ((double)(P.R.oy + cy) + 0.5) * P.R.res;
-    const BdFrame F = bd_frame(at_stance(z, P.wheelbase, P.track), P.axle_mid);      // FRAME (gvom_bodyframe.h)
+    const BdFrame F = bd_frame(at_stance(W.z, P.wheelbase, P.track), P.axle_mid);      // FRAME (gvom_bodyframe.h)
     float clr = INFINITY;
     int tight = -1;
     bool left = false;
@@ -92,12 +78,7 @@ __global__ __launch_bounds__(BV_TILE * BV_TILE) void k_volume_body(const BodyPar
         squeeze[at] = (uint8_t)sq;
         clearance[at] = clr;
     }
-    const int lane = (int)(threadIdx.x & 63u);
-#pragma unroll
-    for (int k = 0; k <= BD_LEFT_WINDOW; ++k) {
-        const int n = __builtin_popcountll(lanes(live && st == k));
-        if (n != 0 && lane == 0) atomicAdd(&counts[k], n);
-    }
+    at_tally(counts, BD_LEFT_WINDOW, live, st);
 }
 
 hipError_t gvom_launch_body_volume(hipStream_t s, const BodyParams &P, float soft_margin, const int32_t *wcell, const double *cos_sin,

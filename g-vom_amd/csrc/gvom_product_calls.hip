@@ -4,7 +4,8 @@
 // gvom_primitives_set), gvom_attitude_volume and gvom_body_volume, and the frame builders they and the debug reads (gvom_debug.hip) give the kernels.  Every call takes its set
 // through product_acquire and hands it out through product_publish (gvom_sets.hip).  What several calls do alike stands once, in
 // front of the entry points, and serves the atlas calls (gvom_atlas_calls.hip) too: the argument checks (check_*, *_of), the staging
-// of host inputs (stage_host), the frames (metric_frame, rollout_frame) and, for the calls that wait, the round driver (solve_rounds;
+// of host inputs (stage_host), the frames (metric_frame, rollout_frame), the vehicle on the ground of the four calls that stand it there
+// (check_standing, the Ground and the Field a call reads, the chassis as the kernels take it) and, for the calls that wait, the round driver (solve_rounds;
 // its arithmetic and the work buffers' layouts are gvom_solvework.h's), the work buffers and the epilogue (goal_solve_finish).  What
 // is left in each body is what is particular to that product: its own checks, in the order they always had, and its launches.
 #include "gvom_host.h"
@@ -65,6 +66,76 @@ static void rollout_frame(const gvom_handle *h, int64_t K, int64_t T, const int6
 // ---- the argument checks more than one entry point makes (gvom_host.h) ----------------------------------------------------------------
 int refuse(gvom_handle *h, const char *fn, const std::string &what, int code) { h->err = std::string(fn) + ": " + what; return code; }
 
+static int product_of_kind(gvom_handle *h, const char *fn, int64_t id, int kind, const char *what, DevSet **f)
+{
+    *f = find_set(h->psets, id);
+    return *f && (*f)->kind == kind ? GVOM_OK : refuse(h, fn, what);
+}
+
+// ---- the vehicle on the ground: what gvom_score_attitude, gvom_score_body, gvom_attitude_volume and gvom_body_volume do alike ---------
+// the standing checks, in the order each of the four has them; volume: at most 64 headings too (GVOM_POSE_MAX_HEADINGS)
+static int check_standing(gvom_handle *h, const char *fn, bool volume)
+{
+    if (h->sharded) return refuse(h, fn, "sharded handles are not supported");
+    if (h->fp_H < 1) return refuse(h, fn, "no footprint table is set (gvom_footprint_set)");
+    if (h->at_H < 1) return refuse(h, fn, "no chassis is set (gvom_chassis_set)");
+    if (volume && h->fp_H > GVOM_POSE_MAX_HEADINGS) return refuse(h, fn, "footprint tables of more than 64 headings are not supported", GVOM_ERR_CAPACITY);
+    if (h->at_H != h->fp_H) return refuse(h, fn, "the chassis was set for another number of headings than the footprint table has");
+    return GVOM_OK;
+}
+static int check_states(gvom_handle *h, const char *fn, int64_t H, int64_t xy) { return H * xy * xy > GVOM_POSE_MAX_STATES ? refuse(h, fn, "more than 2^28 states (headings x xy_size^2)", GVOM_ERR_CAPACITY) : GVOM_OK; }
+
+// THE GROUND a call reads: the caller's map (a staged host map takes dev over), or a map set's, which k_attitude_ground writes into the
+// call's own grow-only buffer.  ground_reserve, in front of the call's uploads: room for it, counted in the call's allocs;
+// ground_write, behind the call's set_wait_releases: the pass itself, on the handle's stream
+struct Ground { DevSet *m = nullptr; double *own = nullptr; const double *dev = nullptr; };
+static int ground_reserve(gvom_handle *h, Ground &g, Buf &buf, int &allocs, const double *ground)
+{
+    const size_t xy = (size_t)h->prm.xy_size;
+    if (const int rc = g.m ? stage_buf(h, buf, xy * xy * 8, allocs) : GVOM_OK) return rc;
+    g.own = g.m ? (double *)buf.p : nullptr;
+    g.dev = g.m ? g.own : ground;
+    return GVOM_OK;
+}
+static int ground_write(gvom_handle *h, const Ground &g, int flags)
+{
+    if (g.m) HIPCHK(h, gvom_launch_attitude_ground(h->stream, h->prm.xy_size, (flags & GVOM_ATTITUDE_INFERRED_GROUND) ? 1 : 0, part_ptr<const double>(g.m, 4),
+                                                  part_ptr<const double>(g.m, 5), g.own));
+    return GVOM_OK;
+}
+
+// THE FIELD of gvom_score_body and gvom_body_volume, whose arguments are past check_one_source: a voxel distance product's (f) or the
+// caller's pointer with its origin.  B = its corner in world voxels, n and zs = its sides
+struct Field { DevSet *f = nullptr; int64_t B[3]; int n, zs; };
+static int field_of(gvom_handle *h, const char *fn, int64_t id, const int64_t origin[3], Field &F)
+{
+    if (const int rc = id >= 0 ? product_of_kind(h, fn, id, GVOM_PRODUCT_VOXEL_DISTANCE, "unknown or stale distance field id", &F.f) : GVOM_OK) return rc;
+    F.n = F.f ? F.f->xy : h->prm.xy_size; F.zs = F.f ? F.f->zs : h->prm.z_size;
+    for (int k = 0; k < 3; ++k) {
+        if (!F.f && (origin[k] < -((int64_t)1 << 40) || origin[k] > ((int64_t)1 << 40))) return refuse(h, fn, "a field origin beyond 2^40 voxels");
+        F.B[k] = F.f ? F.f->origin[k] : origin[k];
+    }
+    return GVOM_OK;
+}
+
+// the chassis as AttitudeParams, AttitudeVolumeParams and BodyParams take it: the lengths (axle_mid where the params have one), the limits
+static void chassis_lengths(const gvom_handle *h, double &wheelbase, double &track, double *axle_mid)
+{
+    const gvom_chassis_t &c = h->at_chassis;
+    wheelbase = c.front_axle - c.rear_axle; track = c.track;
+    if (axle_mid) *axle_mid = 0.5 * (c.front_axle + c.rear_axle);
+}
+template <class P> static void chassis_limits(const gvom_chassis_t &c, P &p) { p.belly_height = c.belly_height; p.max_pitch = c.max_pitch; p.max_roll = c.max_roll; p.min_clearance = c.min_clearance; }
+
+// what k_body and k_volume_body take beside P.R: the chassis lengths, the field's box and the sphere count
+static void body_params(const gvom_handle *h, const Field &F, float min_margin, BodyParams &P)
+{
+    chassis_lengths(h, P.wheelbase, P.track, &P.axle_mid);
+    P.z_res = h->prm.z_resolution;
+    P.bx = F.B[0]; P.by = F.B[1]; P.bz = F.B[2];
+    P.n = F.n; P.zs = F.zs; P.S = h->bd_S; P.min_margin = min_margin;
+}
+
 int check_one_source(gvom_handle *h, const char *fn, bool id, bool also, bool missing, const char *by_id, const char *both, const char *other)
 {
     if (id && also) return refuse(h, fn, std::string("give ") + by_id + " or " + both + ", not both");
@@ -106,12 +177,6 @@ int check_host_cost(gvom_handle *h, const char *fn, const int32_t *cost, size_t 
     return GVOM_OK;
 }
 
-static int product_of_kind(gvom_handle *h, const char *fn, int64_t id, int kind, const char *what, DevSet **f)
-{
-    *f = find_set(h->psets, id);
-    return *f && (*f)->kind == kind ? GVOM_OK : refuse(h, fn, what);
-}
-
 int cost_field_of(gvom_handle *h, const char *fn, int64_t id, DevSet **f) { return product_of_kind(h, fn, id, GVOM_PRODUCT_COSTFIELD, "unknown or stale cost field id", f); }
 int atlas_field_of(gvom_handle *h, const char *fn, int64_t id, DevSet **f) { return product_of_kind(h, fn, id, GVOM_PRODUCT_ATLAS_FIELD, "unknown or stale atlas field id", f); }
 
@@ -146,7 +211,7 @@ int ctg_cost_params(gvom_handle *h, const char *fn, const gvom_ctg_params *param
                     p.soft_weight >= 0 && p.soft_weight <= 65535 && p.unknown_cost >= 0 && p.unknown_cost <= 65535 &&
                     p.rough_weight >= 0 && p.rough_weight <= 65535 &&
                     (p.rough_weight == 0 || (isfinite(p.min_roughness) && isfinite(p.max_roughness) && p.max_roughness > p.min_roughness));
-    if (!ok) { h->err = std::string(fn) + ": bad cost parameters (NaN threshold, base < 1, a weight outside 0 .. 65535, a negative inflation, or an empty / non-finite roughness range)"; return GVOM_ERR_INVALID; }
+    if (!ok) return refuse(h, fn, "bad cost parameters (NaN threshold, base < 1, a weight outside 0 .. 65535, a negative inflation, or an empty / non-finite roughness range)");
     memset(C, 0, sizeof *C);
     C->density_threshold = p.density_threshold; C->min_roughness = p.min_roughness; C->max_roughness = p.max_roughness;
     C->inflation_cells2 = p.inflation_cells2; C->base = p.base; C->soft_weight = p.soft_weight; C->unknown_cost = p.unknown_cost;
@@ -280,7 +345,7 @@ VIS int gvom_device_product(gvom_t *h, int kind, int64_t max_rows, int64_t *prod
         "alignment scores are made by gvom_score_alignments", nullptr, "attitude scores are made by gvom_score_attitude", nullptr,
         "frontiers are made by gvom_frontiers", nullptr, "viewpoint scores are made by gvom_score_viewpoints", nullptr, "pose fields are made by gvom_pose_field"};
     const char *const maker = kind >= 0 && kind <= GVOM_PRODUCT_POSEFIELD ? elsewhere[kind] : nullptr;
-    if (maker || kind < 1 || kind > GVOM_N_PRODUCT_KINDS) { h->err = std::string("gvom_device_product: ") + (maker ? maker : "unknown product kind"); return GVOM_ERR_INVALID; }
+    if (maker || kind < 1 || kind > GVOM_N_PRODUCT_KINDS) return refuse(h, "gvom_device_product", maker ? maker : "unknown product kind");
     if (h->sharded) return refuse(h, "gvom_device_product", "sharded handles are not supported");
     if (kind == GVOM_PRODUCT_VOXEL_CLOUD) stats_demand(h);                  // a read of the statistics, like gvom_debug_voxel_map
     if (!h->has_combined) return GVOM_NO_DATA;
@@ -340,8 +405,8 @@ VIS int gvom_clearance(gvom_t *h, int64_t map_set_id, const int32_t *positive, c
     const char *const fn = "gvom_clearance";
     int rc;
     if (h->sharded) return refuse(h, fn, "sharded handles are not supported");
-    if (flags & ~GVOM_CLEARANCE_NO_NEGATIVE) { h->err = "gvom_clearance: unknown flag bits"; return GVOM_ERR_INVALID; }
-    if (density_threshold != density_threshold) { h->err = "gvom_clearance: the density threshold is not a number"; return GVOM_ERR_INVALID; }
+    if (flags & ~GVOM_CLEARANCE_NO_NEGATIVE) return refuse(h, "gvom_clearance", "unknown flag bits");
+    if (density_threshold != density_threshold) return refuse(h, "gvom_clearance", "the density threshold is not a number");
     if ((rc = check_one_source(h, fn, map_set_id >= 0, positive || negative, !positive, "a map set id", "map pointers", "a positive map")) || (rc = check_side(h, fn))) return rc;
     const int xy = h->prm.xy_size;
     const size_t n2 = (size_t)xy * xy;
@@ -384,11 +449,11 @@ VIS int gvom_raycast(gvom_t *h, const float *from, int64_t K, const float *to, i
     std::lock_guard<std::mutex> lk(h->mu);
     *product_id = -1;
     if (h->sharded) return refuse(h, "gvom_raycast", "sharded handles are not supported");
-    if (!from || !to) { h->err = "gvom_raycast: from and to must not be NULL"; return GVOM_ERR_INVALID; }
-    if (n < 1) { h->err = "gvom_raycast: n must be at least 1"; return GVOM_ERR_INVALID; }
-    if (K != 1 && K != n) { h->err = "gvom_raycast: K must be 1 or n"; return GVOM_ERR_INVALID; }
-    if (flags & ~(GVOM_RAY_UNKNOWN_BLOCKS | GVOM_RAY_CHECK_TARGET)) { h->err = "gvom_raycast: unknown flag bits"; return GVOM_ERR_INVALID; }
-    if (n > GVOM_RAYCAST_MAX_RAYS) { h->err = "gvom_raycast: more than 2^26 rays in one call"; return GVOM_ERR_CAPACITY; }
+    if (!from || !to) return refuse(h, "gvom_raycast", "from and to must not be NULL");
+    if (n < 1) return refuse(h, "gvom_raycast", "n must be at least 1");
+    if (K != 1 && K != n) return refuse(h, "gvom_raycast", "K must be 1 or n");
+    if (flags & ~(GVOM_RAY_UNKNOWN_BLOCKS | GVOM_RAY_CHECK_TARGET)) return refuse(h, "gvom_raycast", "unknown flag bits");
+    if (n > GVOM_RAYCAST_MAX_RAYS) return refuse(h, "gvom_raycast", "more than 2^26 rays in one call", GVOM_ERR_CAPACITY);
     if (!h->has_combined) return GVOM_NO_DATA;
     HIPCHK(h, hipSetDevice(h->device));
     DevSet *set = nullptr;
@@ -436,14 +501,14 @@ VIS int gvom_cost_to_go(gvom_t *h, int64_t map_set_id, const gvom_ctg_params *pa
     const char *const fn = "gvom_cost_to_go";
     int rc;
     if (h->sharded) return refuse(h, fn, "sharded handles are not supported");
-    if (flags & ~(GVOM_CTG_NO_NEGATIVE | GVOM_CTG_UNKNOWN_BLOCKS)) { h->err = "gvom_cost_to_go: unknown flag bits"; return GVOM_ERR_INVALID; }
+    if (flags & ~(GVOM_CTG_NO_NEGATIVE | GVOM_CTG_UNKNOWN_BLOCKS)) return refuse(h, "gvom_cost_to_go", "unknown flag bits");
     if ((rc = check_one_source(h, fn, map_set_id >= 0, cost, !cost, "a map set id", "a cost map", "a cost map"))) return rc;
-    if (map_set_id >= 0 && !params) { h->err = "gvom_cost_to_go: a map set needs the cost parameters"; return GVOM_ERR_INVALID; }
+    if (map_set_id >= 0 && !params) return refuse(h, "gvom_cost_to_go", "a map set needs the cost parameters");
     if ((rc = check_goals(h, fn, goals, n_goals, max_cost, max_rounds)) || (rc = check_side(h, fn))) return rc;
     const int xy = h->prm.xy_size;
     const size_t n2 = (size_t)xy * xy;
     for (int64_t k = 0; k < 2 * n_goals; ++k)
-        if (goals[k] < 0 || goals[k] >= xy) { h->err = "gvom_cost_to_go: a goal lies outside the window"; return GVOM_ERR_INVALID; }
+        if (goals[k] < 0 || goals[k] >= xy) return refuse(h, "gvom_cost_to_go", "a goal lies outside the window");
     CtgCostParams C;
     memset(&C, 0, sizeof C);
     DevSet *m = nullptr;
@@ -492,13 +557,13 @@ VIS int gvom_footprint_set(gvom_t *h, int32_t n_headings, const int32_t *start, 
 {
     if (!h) return GVOM_ERR_INVALID;
     std::lock_guard<std::mutex> lk(h->mu);
-    if (!start || !offsets) { h->err = "gvom_footprint_set: start and offsets must not be NULL"; return GVOM_ERR_INVALID; }
-    if (n_headings < 1 || n_headings > GVOM_ROLLOUT_MAX_HEADINGS) { h->err = "gvom_footprint_set: between 1 and 1024 headings"; return GVOM_ERR_INVALID; }
-    if (start[0] != 0) { h->err = "gvom_footprint_set: start[0] must be 0"; return GVOM_ERR_INVALID; }
+    if (!start || !offsets) return refuse(h, "gvom_footprint_set", "start and offsets must not be NULL");
+    if (n_headings < 1 || n_headings > GVOM_ROLLOUT_MAX_HEADINGS) return refuse(h, "gvom_footprint_set", "between 1 and 1024 headings");
+    if (start[0] != 0) return refuse(h, "gvom_footprint_set", "start[0] must be 0");
     for (int k = 0; k < n_headings; ++k) {
         const int64_t m = (int64_t)start[k + 1] - start[k];
-        if (m < 1 || m > GVOM_ROLLOUT_MAX_CELLS) { h->err = "gvom_footprint_set: every heading needs between 1 and 16384 cells"; return GVOM_ERR_INVALID; }
-        if (start[k + 1] > GVOM_ROLLOUT_MAX_TABLE) { h->err = "gvom_footprint_set: more than 2^22 offsets in the table"; return GVOM_ERR_CAPACITY; }
+        if (m < 1 || m > GVOM_ROLLOUT_MAX_CELLS) return refuse(h, "gvom_footprint_set", "every heading needs between 1 and 16384 cells");
+        if (start[k + 1] > GVOM_ROLLOUT_MAX_TABLE) return refuse(h, "gvom_footprint_set", "more than 2^22 offsets in the table", GVOM_ERR_CAPACITY);
     }
     HIPCHK(h, hipSetDevice(h->device));
     const size_t sb = (size_t)(n_headings + 1) * 4, offs_at = align256(sb), ob = (size_t)start[n_headings] * 4;
@@ -524,8 +589,8 @@ VIS int gvom_score_rollouts(gvom_t *h, int64_t costfield_id, const uint16_t *cel
     const char *const fn = "gvom_score_rollouts";
     int rc;
     if (h->sharded) return refuse(h, fn, "sharded handles are not supported");
-    if (h->fp_H < 1) { h->err = "gvom_score_rollouts: no footprint table is set (gvom_footprint_set)"; return GVOM_ERR_INVALID; }
-    if (!poses || !origin_cells) { h->err = "gvom_score_rollouts: poses and origin_cells must not be NULL"; return GVOM_ERR_INVALID; }
+    if (h->fp_H < 1) return refuse(h, "gvom_score_rollouts", "no footprint table is set (gvom_footprint_set)");
+    if (!poses || !origin_cells) return refuse(h, "gvom_score_rollouts", "poses and origin_cells must not be NULL");
     if ((rc = check_one_source(h, fn, costfield_id >= 0, cell_cost || cost_to_go, !cell_cost, "a cost field id", "map pointers", "a cell-cost map")) ||
         (rc = check_rollout_shape(h, fn, K, T, origin_cells)) || (rc = check_side(h, fn))) return rc;
     const int xy = h->prm.xy_size;
@@ -570,14 +635,14 @@ VIS int gvom_chassis_set(gvom_t *h, const gvom_chassis_t *c, int32_t n_headings,
 {
     if (!h) return GVOM_ERR_INVALID;
     std::lock_guard<std::mutex> lk(h->mu);
-    if (!c || !cos_sin) { h->err = "gvom_chassis_set: the chassis and cos_sin must not be NULL"; return GVOM_ERR_INVALID; }
-    if (n_headings < 1 || n_headings > GVOM_ROLLOUT_MAX_HEADINGS) { h->err = "gvom_chassis_set: between 1 and 1024 headings"; return GVOM_ERR_INVALID; }
-    if (!(isfinite(c->front_axle) && isfinite(c->rear_axle) && isfinite(c->track) && isfinite(c->belly_height))) { h->err = "gvom_chassis_set: a length is not finite"; return GVOM_ERR_INVALID; }
-    if (!(c->front_axle > c->rear_axle)) { h->err = "gvom_chassis_set: front_axle must lie in front of rear_axle"; return GVOM_ERR_INVALID; }
-    if (!(c->track > 0.0)) { h->err = "gvom_chassis_set: track must be greater than 0"; return GVOM_ERR_INVALID; }
-    if (c->max_pitch != c->max_pitch || c->max_roll != c->max_roll || c->min_clearance != c->min_clearance) { h->err = "gvom_chassis_set: a limit is not a number"; return GVOM_ERR_INVALID; }
+    if (!c || !cos_sin) return refuse(h, "gvom_chassis_set", "the chassis and cos_sin must not be NULL");
+    if (n_headings < 1 || n_headings > GVOM_ROLLOUT_MAX_HEADINGS) return refuse(h, "gvom_chassis_set", "between 1 and 1024 headings");
+    if (!(isfinite(c->front_axle) && isfinite(c->rear_axle) && isfinite(c->track) && isfinite(c->belly_height))) return refuse(h, "gvom_chassis_set", "a length is not finite");
+    if (!(c->front_axle > c->rear_axle)) return refuse(h, "gvom_chassis_set", "front_axle must lie in front of rear_axle");
+    if (!(c->track > 0.0)) return refuse(h, "gvom_chassis_set", "track must be greater than 0");
+    if (c->max_pitch != c->max_pitch || c->max_roll != c->max_roll || c->min_clearance != c->min_clearance) return refuse(h, "gvom_chassis_set", "a limit is not a number");
     for (int k = 0; k < 2 * n_headings; ++k)
-        if (!(fabs(cos_sin[k]) <= 1.0)) { h->err = "gvom_chassis_set: a cos_sin entry is not finite or exceeds 1 in magnitude"; return GVOM_ERR_INVALID; }
+        if (!(fabs(cos_sin[k]) <= 1.0)) return refuse(h, "gvom_chassis_set", "a cos_sin entry is not finite or exceeds 1 in magnitude");
     const size_t wb = (size_t)n_headings * 64, cs_at = align256(wb), cb = (size_t)n_headings * 16;
     std::vector<double> tab((cs_at + cb) / 8, 0.0);
     const double half = c->track / 2, ab[4][2] = {{c->front_axle, half}, {c->front_axle, -half}, {c->rear_axle, half}, {c->rear_axle, -half}};
@@ -585,7 +650,7 @@ VIS int gvom_chassis_set(gvom_t *h, const gvom_chassis_t *c, int32_t n_headings,
         const double co = cos_sin[2 * k], si = cos_sin[2 * k + 1];
         for (int i = 0; i < 4; ++i) {
             const double wx = ab[i][0] * co - ab[i][1] * si, wy = ab[i][0] * si + ab[i][1] * co;
-            if (!(isfinite(wx) && isfinite(wy))) { h->err = "gvom_chassis_set: a wheel offset is not finite"; return GVOM_ERR_INVALID; }
+            if (!(isfinite(wx) && isfinite(wy))) return refuse(h, "gvom_chassis_set", "a wheel offset is not finite");
             tab[(size_t)(k * 4 + i) * 2] = wx; tab[(size_t)(k * 4 + i) * 2 + 1] = wy;
         }
         tab[cs_at / 8 + 2 * k] = co; tab[cs_at / 8 + 2 * k + 1] = si;
@@ -611,46 +676,38 @@ VIS int gvom_score_attitude(gvom_t *h, int64_t map_set_id, const double *ground,
     *product_id = -1;
     const char *const fn = "gvom_score_attitude";
     int rc;
-    if (h->sharded) return refuse(h, fn, "sharded handles are not supported");
-    if (h->fp_H < 1) { h->err = "gvom_score_attitude: no footprint table is set (gvom_footprint_set)"; return GVOM_ERR_INVALID; }
-    if (h->at_H < 1) { h->err = "gvom_score_attitude: no chassis is set (gvom_chassis_set)"; return GVOM_ERR_INVALID; }
-    if (h->at_H != h->fp_H) { h->err = "gvom_score_attitude: the chassis was set for another number of headings than the footprint table has"; return GVOM_ERR_INVALID; }
-    if (!poses || !origin_cells) { h->err = "gvom_score_attitude: poses and origin_cells must not be NULL"; return GVOM_ERR_INVALID; }
-    if (flags & ~GVOM_ATTITUDE_INFERRED_GROUND) { h->err = "gvom_score_attitude: unknown flag bits"; return GVOM_ERR_INVALID; }
+    if ((rc = check_standing(h, fn, false))) return rc;
+    if (!poses || !origin_cells) return refuse(h, fn, "poses and origin_cells must not be NULL");
+    if (flags & ~GVOM_ATTITUDE_INFERRED_GROUND) return refuse(h, fn, "unknown flag bits");
     if ((rc = check_one_source(h, fn, map_set_id >= 0, ground, !ground, "a map set id", "a ground map", "a ground map"))) return rc;
     if ((rc = check_rollout_shape(h, fn, K, T, origin_cells)) || (rc = check_side(h, fn))) return rc;
     const int xy = h->prm.xy_size;
     const size_t n2 = (size_t)xy * xy;
-    DevSet *m = nullptr;
-    if (map_set_id >= 0 && (rc = map_set_of(h, map_set_id, &m))) return rc;
+    Ground g;
+    if (map_set_id >= 0 && (rc = map_set_of(h, map_set_id, &g.m))) return rc;
     HIPCHK(h, hipSetDevice(h->device));
     DevSet *set = nullptr;
     const size_t bytes = set_bytes(GVOM_PRODUCT_ATTITUDE, 0, 0, K, T);
-    rc = product_acquire(h, GVOM_PRODUCT_ATTITUDE, bytes, bytes, fn, &h->at_allocs, &set);
-    if (rc) return rc;
+    if ((rc = product_acquire(h, GVOM_PRODUCT_ATTITUDE, bytes, bytes, fn, &h->at_allocs, &set))) return rc;
     set->cap = K; set->cols = T;
-    if (m && (rc = stage_buf(h, h->at_ground, n2 * 8, h->at_allocs))) return rc;
+    if ((rc = ground_reserve(h, g, h->at_ground, h->at_allocs, ground))) return rc;
     const float *pdev = poses;
-    const double *gdev = m ? (const double *)h->at_ground.p : ground;
     HIPCHK(h, join_second_stream(h));
     if (!on_device) {                                                       // host poses (and ground): staged, and up before the call returns
         const HostPart parts[2] = {{ground, n2 * 8}, {poses, (size_t)K * T * 12}};
         const void *dev[2];
         if ((rc = stage_host(h, h->at_stage, h->at_allocs, parts, 2, true, dev))) return rc;
-        if (dev[0]) gdev = (const double *)dev[0];
+        if (dev[0]) g.dev = (const double *)dev[0];
         pdev = (const float *)dev[1];
     }
-    if ((rc = set_wait_releases(h, set))) return rc;
-    if (m) HIPCHK(h, gvom_launch_attitude_ground(h->stream, xy, (flags & GVOM_ATTITUDE_INFERRED_GROUND) ? 1 : 0, part_ptr<const double>(m, 4),
-                                                part_ptr<const double>(m, 5), (double *)h->at_ground.p));
-    const gvom_chassis_t &c = h->at_chassis;
+    if ((rc = set_wait_releases(h, set)) || (rc = ground_write(h, g, flags))) return rc;
     AttitudeParams P;
     memset(&P, 0, sizeof P);
     rollout_frame(h, K, T, origin_cells, P.R);
-    P.wheelbase = c.front_axle - c.rear_axle; P.track = c.track; P.axle_mid = 0.5 * (c.front_axle + c.rear_axle); P.belly_height = c.belly_height;
-    P.max_pitch = c.max_pitch; P.max_roll = c.max_roll; P.min_clearance = c.min_clearance;
+    chassis_lengths(h, P.wheelbase, P.track, &P.axle_mid);
+    chassis_limits(h->at_chassis, P);
     HIPCHK(h, gvom_launch_attitude(h->stream, P, pdev, (const int32_t *)h->fp_tab.p, (const uint32_t *)((char *)h->fp_tab.p + h->fp_offs_at),
-                                   (const double *)h->at_tab.p, (const double *)((char *)h->at_tab.p + h->at_cs_at), gdev,
+                                   (const double *)h->at_tab.p, (const double *)((char *)h->at_tab.p + h->at_cs_at), g.dev,
                                    part_ptr<int32_t>(set, 0), part_ptr<float>(set, 1), part_ptr<uint8_t>(set, 2)));
     return product_publish(h, set, product_id);
 }
@@ -691,10 +748,7 @@ VIS int gvom_score_body(gvom_t *h, int64_t field_product_id, const float *field,
     *product_id = -1;
     const char *const fn = "gvom_score_body";
     int rc;
-    if (h->sharded) return refuse(h, fn, "sharded handles are not supported");
-    if (h->fp_H < 1) return refuse(h, fn, "no footprint table is set (gvom_footprint_set)");
-    if (h->at_H < 1) return refuse(h, fn, "no chassis is set (gvom_chassis_set)");
-    if (h->at_H != h->fp_H) return refuse(h, fn, "the chassis was set for another number of headings than the footprint table has");
+    if ((rc = check_standing(h, fn, false))) return rc;
     if (h->bd_S < 1) return refuse(h, fn, "no body is set (gvom_body_set)");
     if (!poses || !origin_cells) return refuse(h, fn, "poses and origin_cells must not be NULL");
     if (flags & ~GVOM_ATTITUDE_INFERRED_GROUND) return refuse(h, fn, "unknown flag bits");
@@ -705,52 +759,32 @@ VIS int gvom_score_body(gvom_t *h, int64_t field_product_id, const float *field,
     if ((rc = check_rollout_shape(h, fn, K, T, origin_cells)) || (rc = check_side(h, fn))) return rc;
     const int xy = h->prm.xy_size;
     const size_t n2 = (size_t)xy * xy;
-    DevSet *m = nullptr, *f = nullptr;
-    if (map_set_id >= 0 && (rc = map_set_of(h, map_set_id, &m))) return rc;
-    int64_t B[3];
-    int fn_xy = xy, fn_zs = h->prm.z_size;
-    if (field_product_id >= 0) {
-        f = find_set(h->psets, field_product_id);
-        if (!f || f->kind != GVOM_PRODUCT_VOXEL_DISTANCE) return refuse(h, fn, "unknown or stale distance field id");
-        for (int k = 0; k < 3; ++k) B[k] = f->origin[k];
-        fn_xy = f->xy; fn_zs = f->zs;
-    } else {
-        for (int k = 0; k < 3; ++k) {
-            if (field_origin[k] < -((int64_t)1 << 40) || field_origin[k] > ((int64_t)1 << 40)) return refuse(h, fn, "a field origin beyond 2^40 voxels");
-            B[k] = field_origin[k];
-        }
-    }
+    Ground g;
+    Field F;
+    if ((map_set_id >= 0 && (rc = map_set_of(h, map_set_id, &g.m))) || (rc = field_of(h, fn, field_product_id, field_origin, F))) return rc;
     HIPCHK(h, hipSetDevice(h->device));
     DevSet *set = nullptr;
     const size_t bytes = set_bytes(GVOM_PRODUCT_BODY, 0, 0, K, T);
-    rc = product_acquire(h, GVOM_PRODUCT_BODY, bytes, bytes, fn, &h->bd_allocs, &set);
-    if (rc) return rc;
+    if ((rc = product_acquire(h, GVOM_PRODUCT_BODY, bytes, bytes, fn, &h->bd_allocs, &set))) return rc;
     set->cap = K; set->cols = T;
-    if (m && (rc = stage_buf(h, h->bd_ground, n2 * 8, h->bd_allocs))) return rc;
+    if ((rc = ground_reserve(h, g, h->bd_ground, h->bd_allocs, ground))) return rc;
     const float *pdev = poses;
-    const double *gdev = m ? (const double *)h->bd_ground.p : ground;
-    const float *fdev = f ? part_ptr<const float>(f, 0) : field;
+    const float *fdev = F.f ? part_ptr<const float>(F.f, 0) : field;
     HIPCHK(h, join_second_stream(h));
     if (!on_device) {                                                       // host poses (field and ground): staged, and up before the call returns
-        const HostPart parts[3] = {{field, n2 * (size_t)fn_zs * 4}, {ground, n2 * 8}, {poses, (size_t)K * T * 12}};
+        const HostPart parts[3] = {{field, n2 * (size_t)F.zs * 4}, {ground, n2 * 8}, {poses, (size_t)K * T * 12}};
         const void *dev[3];
         if ((rc = stage_host(h, h->bd_stage, h->bd_allocs, parts, 3, true, dev))) return rc;
         if (dev[0]) fdev = (const float *)dev[0];
-        if (dev[1]) gdev = (const double *)dev[1];
+        if (dev[1]) g.dev = (const double *)dev[1];
         pdev = (const float *)dev[2];
     }
-    if ((rc = set_wait_releases(h, set))) return rc;
-    if (m) HIPCHK(h, gvom_launch_attitude_ground(h->stream, xy, (flags & GVOM_ATTITUDE_INFERRED_GROUND) ? 1 : 0, part_ptr<const double>(m, 4),
-                                                part_ptr<const double>(m, 5), (double *)h->bd_ground.p));
-    const gvom_chassis_t &c = h->at_chassis;
+    if ((rc = set_wait_releases(h, set)) || (rc = ground_write(h, g, flags))) return rc;
     BodyParams P;
     memset(&P, 0, sizeof P);
     rollout_frame(h, K, T, origin_cells, P.R);
-    P.wheelbase = c.front_axle - c.rear_axle; P.track = c.track; P.axle_mid = 0.5 * (c.front_axle + c.rear_axle);
-    P.z_res = h->prm.z_resolution;
-    P.bx = B[0]; P.by = B[1]; P.bz = B[2];
-    P.n = fn_xy; P.zs = fn_zs; P.S = h->bd_S; P.min_margin = min_margin;
-    HIPCHK(h, gvom_launch_body(h->stream, P, pdev, (const double *)h->at_tab.p, (const double *)((char *)h->at_tab.p + h->at_cs_at), gdev,
+    body_params(h, F, min_margin, P);
+    HIPCHK(h, gvom_launch_body(h->stream, P, pdev, (const double *)h->at_tab.p, (const double *)((char *)h->at_tab.p + h->at_cs_at), g.dev,
                                (const float *)h->bd_tab.p, fdev, part_ptr<int32_t>(set, 0), part_ptr<float>(set, 1), part_ptr<uint8_t>(set, 2)));
     return product_publish(h, set, product_id);
 }
@@ -767,18 +801,18 @@ VIS int gvom_score_alignments(gvom_t *h, const float *cloud, int64_t n, const do
     std::lock_guard<std::mutex> lk(h->mu);
     *product_id = -1;
     if (h->sharded) return refuse(h, "gvom_score_alignments", "sharded handles are not supported");
-    if (!cloud || !transforms || !weights) { h->err = "gvom_score_alignments: cloud, transforms and weights must not be NULL"; return GVOM_ERR_INVALID; }
-    if (n < 1) { h->err = "gvom_score_alignments: n must be at least 1"; return GVOM_ERR_INVALID; }
-    if (K < 1) { h->err = "gvom_score_alignments: K must be at least 1"; return GVOM_ERR_INVALID; }
-    if (dilate != 0 && dilate != 1) { h->err = "gvom_score_alignments: dilate must be 0 or 1"; return GVOM_ERR_INVALID; }
+    if (!cloud || !transforms || !weights) return refuse(h, "gvom_score_alignments", "cloud, transforms and weights must not be NULL");
+    if (n < 1) return refuse(h, "gvom_score_alignments", "n must be at least 1");
+    if (K < 1) return refuse(h, "gvom_score_alignments", "K must be at least 1");
+    if (dilate != 0 && dilate != 1) return refuse(h, "gvom_score_alignments", "dilate must be 0 or 1");
     for (int c = 0; c < 5; ++c)
-        if (weights[c] < -GVOM_ALIGN_MAX_WEIGHT || weights[c] > GVOM_ALIGN_MAX_WEIGHT) { h->err = "gvom_score_alignments: a weight outside -1024 .. 1024"; return GVOM_ERR_INVALID; }
-    if (n > GVOM_ALIGN_MAX_POINTS) { h->err = "gvom_score_alignments: more than 2^20 returns in one call"; return GVOM_ERR_CAPACITY; }
-    if (K > GVOM_ALIGN_MAX_CANDIDATES) { h->err = "gvom_score_alignments: more than 65536 candidates in one call"; return GVOM_ERR_CAPACITY; }
-    if (n * K > GVOM_ALIGN_MAX_PAIRS) { h->err = "gvom_score_alignments: more than 2^32 pairs in one call"; return GVOM_ERR_CAPACITY; }
+        if (weights[c] < -GVOM_ALIGN_MAX_WEIGHT || weights[c] > GVOM_ALIGN_MAX_WEIGHT) return refuse(h, "gvom_score_alignments", "a weight outside -1024 .. 1024");
+    if (n > GVOM_ALIGN_MAX_POINTS) return refuse(h, "gvom_score_alignments", "more than 2^20 returns in one call", GVOM_ERR_CAPACITY);
+    if (K > GVOM_ALIGN_MAX_CANDIDATES) return refuse(h, "gvom_score_alignments", "more than 65536 candidates in one call", GVOM_ERR_CAPACITY);
+    if (n * K > GVOM_ALIGN_MAX_PAIRS) return refuse(h, "gvom_score_alignments", "more than 2^32 pairs in one call", GVOM_ERR_CAPACITY);
     const int xy = h->prm.xy_size, zs = h->prm.z_size;
     const size_t gb = gvom_align_grid_bytes(xy, zs);
-    if (gb / 4 > 0xffffffffull) { h->err = "gvom_score_alignments: the class grid of this map has 2^32 words or more"; return GVOM_ERR_CAPACITY; }
+    if (gb / 4 > 0xffffffffull) return refuse(h, "gvom_score_alignments", "the class grid of this map has 2^32 words or more", GVOM_ERR_CAPACITY);
     if (!h->has_combined) return GVOM_NO_DATA;
     HIPCHK(h, hipSetDevice(h->device));
     DevSet *set = nullptr;
@@ -827,9 +861,9 @@ VIS int gvom_frontiers(gvom_t *h, int64_t costfield_id, int64_t map_set_id, cons
     int rc;
     if (h->sharded) return refuse(h, fn, "sharded handles are not supported");
     const bool ids = costfield_id >= 0 && map_set_id >= 0;
-    if ((costfield_id >= 0) != (map_set_id >= 0)) { h->err = "gvom_frontiers: the ids route needs a cost field id AND a map set id"; return GVOM_ERR_INVALID; }
-    if (ids && (cell_cost || cost_to_go || visibility)) { h->err = "gvom_frontiers: give the two ids or map pointers, not both"; return GVOM_ERR_INVALID; }
-    if (!ids && (!cell_cost || !visibility)) { h->err = "gvom_frontiers: give the two ids, or a cell-cost map and a visibility map"; return GVOM_ERR_INVALID; }
+    if ((costfield_id >= 0) != (map_set_id >= 0)) return refuse(h, "gvom_frontiers", "the ids route needs a cost field id AND a map set id");
+    if (ids && (cell_cost || cost_to_go || visibility)) return refuse(h, "gvom_frontiers", "give the two ids or map pointers, not both");
+    if (!ids && (!cell_cost || !visibility)) return refuse(h, "gvom_frontiers", "give the two ids, or a cell-cost map and a visibility map");
     if ((rc = check_clusters(h, fn, min_cells, max_clusters)) || (rc = check_side(h, fn))) return rc;
     const int xy = h->prm.xy_size;
     const size_t n2 = (size_t)xy * xy;
@@ -873,19 +907,19 @@ VIS int gvom_score_viewpoints(gvom_t *h, const double *poses, int64_t K, int on_
     std::lock_guard<std::mutex> lk(h->mu);
     *product_id = -1;
     if (h->sharded) return refuse(h, "gvom_score_viewpoints", "sharded handles are not supported");
-    if (!poses) { h->err = "gvom_score_viewpoints: poses must not be NULL"; return GVOM_ERR_INVALID; }
-    if (h->ri_H <= 0) { h->err = "gvom_score_viewpoints: no sensor model (gvom_sensor_model_set)"; return GVOM_ERR_INVALID; }
-    if (K < 1) { h->err = "gvom_score_viewpoints: K must be at least 1"; return GVOM_ERR_INVALID; }
-    if (stride_h < 1 || stride_w < 1) { h->err = "gvom_score_viewpoints: the beam strides must be at least 1"; return GVOM_ERR_INVALID; }
-    if (!std::isfinite(max_range) || !(max_range > 0.0)) { h->err = "gvom_score_viewpoints: max_range must be finite and > 0"; return GVOM_ERR_INVALID; }
-    if (flags & ~GVOM_RAY_UNKNOWN_BLOCKS) { h->err = "gvom_score_viewpoints: unknown flag bits"; return GVOM_ERR_INVALID; }
-    if (K > GVOM_VIEWPOINT_MAX_POSES) { h->err = "gvom_score_viewpoints: more than 65536 viewpoints in one call"; return GVOM_ERR_CAPACITY; }
+    if (!poses) return refuse(h, "gvom_score_viewpoints", "poses must not be NULL");
+    if (h->ri_H <= 0) return refuse(h, "gvom_score_viewpoints", "no sensor model (gvom_sensor_model_set)");
+    if (K < 1) return refuse(h, "gvom_score_viewpoints", "K must be at least 1");
+    if (stride_h < 1 || stride_w < 1) return refuse(h, "gvom_score_viewpoints", "the beam strides must be at least 1");
+    if (!std::isfinite(max_range) || !(max_range > 0.0)) return refuse(h, "gvom_score_viewpoints", "max_range must be finite and > 0");
+    if (flags & ~GVOM_RAY_UNKNOWN_BLOCKS) return refuse(h, "gvom_score_viewpoints", "unknown flag bits");
+    if (K > GVOM_VIEWPOINT_MAX_POSES) return refuse(h, "gvom_score_viewpoints", "more than 65536 viewpoints in one call", GVOM_ERR_CAPACITY);
     const int xy = h->prm.xy_size, zs = h->prm.z_size;
     const int64_t nh = ((int64_t)h->ri_H + stride_h - 1) / stride_h, nw = ((int64_t)h->ri_W + stride_w - 1) / stride_w, nb = nh * nw;
-    if (nb > GVOM_VIEWPOINT_MAX_BEAMS) { h->err = "gvom_score_viewpoints: more than 2^22 selected beams"; return GVOM_ERR_CAPACITY; }
-    if (nb * ((int64_t)xy + zs + 1) >= ((int64_t)1 << 31)) { h->err = "gvom_score_viewpoints: beams x (xy_size + z_size + 1) reaches 2^31"; return GVOM_ERR_CAPACITY; }
+    if (nb > GVOM_VIEWPOINT_MAX_BEAMS) return refuse(h, "gvom_score_viewpoints", "more than 2^22 selected beams", GVOM_ERR_CAPACITY);
+    if (nb * ((int64_t)xy + zs + 1) >= ((int64_t)1 << 31)) return refuse(h, "gvom_score_viewpoints", "beams x (xy_size + z_size + 1) reaches 2^31", GVOM_ERR_CAPACITY);
     const int64_t V = (int64_t)xy * xy * zs;
-    if (V >= ((int64_t)1 << 31)) { h->err = "gvom_score_viewpoints: the window has 2^31 voxels or more"; return GVOM_ERR_CAPACITY; }
+    if (V >= ((int64_t)1 << 31)) return refuse(h, "gvom_score_viewpoints", "the window has 2^31 voxels or more", GVOM_ERR_CAPACITY);
     if (!h->has_combined) return GVOM_NO_DATA;
     HIPCHK(h, hipSetDevice(h->device));
     DevSet *set = nullptr;
@@ -944,18 +978,18 @@ VIS int gvom_primitives_set(gvom_t *h, int32_t n_headings, const int32_t *start,
 {
     if (!h) return GVOM_ERR_INVALID;
     std::lock_guard<std::mutex> lk(h->mu);
-    if (!start || !prims) { h->err = "gvom_primitives_set: start and prims must not be NULL"; return GVOM_ERR_INVALID; }
-    if (n_headings < 1 || n_headings > GVOM_POSE_MAX_HEADINGS) { h->err = "gvom_primitives_set: between 1 and 64 headings"; return GVOM_ERR_INVALID; }
-    if (start[0] != 0) { h->err = "gvom_primitives_set: start[0] must be 0"; return GVOM_ERR_INVALID; }
+    if (!start || !prims) return refuse(h, "gvom_primitives_set", "start and prims must not be NULL");
+    if (n_headings < 1 || n_headings > GVOM_POSE_MAX_HEADINGS) return refuse(h, "gvom_primitives_set", "between 1 and 64 headings");
+    if (start[0] != 0) return refuse(h, "gvom_primitives_set", "start[0] must be 0");
     int R = 0;
     for (int k = 0; k < n_headings; ++k) {
         const int64_t m = (int64_t)start[k + 1] - start[k];
-        if (m < 0 || m > GVOM_POSE_MAX_PRIMS) { h->err = "gvom_primitives_set: every heading has at most 64 primitives"; return GVOM_ERR_INVALID; }
+        if (m < 0 || m > GVOM_POSE_MAX_PRIMS) return refuse(h, "gvom_primitives_set", "every heading has at most 64 primitives");
         for (int p = start[k]; p < start[k + 1]; ++p) {
             const int dx = prims[4 * p], dy = prims[4 * p + 1], hto = prims[4 * p + 2], w = prims[4 * p + 3];
             const bool ok = abs(dx) <= GVOM_POSE_MAX_REACH && abs(dy) <= GVOM_POSE_MAX_REACH && hto >= 0 && hto < n_headings && w >= 1 && w <= 255 &&
                             !(dx == 0 && dy == 0 && hto == k);
-            if (!ok) { h->err = "gvom_primitives_set: a primitive outside the limits (|dx|, |dy| <= 4, 0 <= h_to < H, 1 <= w <= 255, not a self loop)"; return GVOM_ERR_INVALID; }
+            if (!ok) return refuse(h, "gvom_primitives_set", "a primitive outside the limits (|dx|, |dy| <= 4, 0 <= h_to < H, 1 <= w <= 255, not a self loop)");
             R = std::max(R, std::max(abs(dx), abs(dy)));
         }
     }
@@ -971,13 +1005,16 @@ VIS int gvom_primitives_set(gvom_t *h, int32_t n_headings, const int32_t *start,
     return GVOM_OK;
 }
 
-// the one host path of gvom_pose_field, gvom_pose_field_attitude and gvom_pose_field_volumes (fn says which): with_volume = volume_id names
-// the attitude volume k_cspace_attitude takes into the pose cost volume behind k_cspace; with_body = body_id names the body volume the
-// same kernel takes in behind that (its parts 0 and 1 are the same elementwise rule's status and weight byte)
-static int pose_field_call(gvom_t *h, const char *fn, int64_t costfield_id, const int32_t *cost, int on_device, bool with_volume,
-                           int64_t volume_id, uint32_t block_mask, int32_t tilt_weight, bool with_body, int64_t body_id, uint32_t body_mask,
-                           int32_t squeeze_weight, const int32_t *goals, int64_t n_goals, int32_t max_cost, int32_t max_rounds,
-                           int64_t *product_id, int64_t info[4])
+// the two volumes k_cspace_attitude takes into the pose cost volume behind k_cspace, in this order (parts 0 and 1 of either are the
+// elementwise rule's status and weight byte): what a call says of one, and what the checks and their texts need to know of it
+struct PoseVolume { bool present; int64_t id; uint32_t mask; int32_t weight; };
+static const struct { int kind; uint32_t mask_limit; const char *mask_name, *mask_top, *weight_name, *noun; } POSE_VOLUMES[2] = {
+    {GVOM_PRODUCT_ATTITUDE_VOLUME, 0x7fu, "block_mask", "0x7f", "tilt_weight", "attitude"},
+    {GVOM_PRODUCT_BODY_VOLUME, 0x3fu, "body_block_mask", "0x3f", "squeeze_weight", "body"}};
+
+// the one host path of gvom_pose_field, gvom_pose_field_attitude and gvom_pose_field_volumes (fn says which)
+static int pose_field_call(gvom_t *h, const char *fn, int64_t costfield_id, const int32_t *cost, int on_device, const PoseVolume (&volumes)[2],
+                           const int32_t *goals, int64_t n_goals, int32_t max_cost, int32_t max_rounds, int64_t *product_id, int64_t info[4])
 {
     if (!h || !product_id) return GVOM_ERR_INVALID;
     std::lock_guard<std::mutex> lk(h->mu);
@@ -993,26 +1030,24 @@ static int pose_field_call(gvom_t *h, const char *fn, int64_t costfield_id, cons
     if ((rc = check_goals(h, fn, goals, n_goals, max_cost, max_rounds)) || (rc = check_side(h, fn))) return rc;
     const int xy = h->prm.xy_size, H = h->pf_H, R = h->pf_R;
     const size_t n2 = (size_t)xy * xy;
-    if ((int64_t)H * (int64_t)n2 > GVOM_POSE_MAX_STATES) return refuse(h, fn, "more than 2^28 states (headings x xy_size^2)", GVOM_ERR_CAPACITY);
+    if ((rc = check_states(h, fn, H, xy))) return rc;
     for (int64_t k = 0; k < n_goals; ++k) {
         if (goals[3 * k] < 0 || goals[3 * k] >= xy || goals[3 * k + 1] < 0 || goals[3 * k + 1] >= xy) return refuse(h, fn, "a goal lies outside the window");
         if (goals[3 * k + 2] >= H) return refuse(h, fn, "a goal's heading is not one of the table's");
     }
-    DevSet *f = nullptr, *vol = nullptr, *bvol = nullptr;
+    DevSet *f = nullptr;
     if (costfield_id >= 0) {
         if ((rc = cost_field_of(h, fn, costfield_id, &f))) return rc;
     } else if (!on_device && (rc = check_host_cost(h, fn, cost, n2))) return rc;
-    if (with_volume) {
-        if (block_mask > 0x7fu) return refuse(h, fn, "block_mask outside 0 .. 0x7f");
-        if (tilt_weight < 0 || tilt_weight > 255) return refuse(h, fn, "tilt_weight outside 0 .. 255");
-        if ((rc = product_of_kind(h, fn, volume_id, GVOM_PRODUCT_ATTITUDE_VOLUME, "unknown or stale attitude volume id", &vol))) return rc;
-        if (vol->cap != H || vol->xy != xy) return refuse(h, fn, "the attitude volume was made for another number of headings or another window side");
-    }
-    if (with_body) {
-        if (body_mask > 0x3fu) return refuse(h, fn, "body_block_mask outside 0 .. 0x3f");
-        if (squeeze_weight < 0 || squeeze_weight > 255) return refuse(h, fn, "squeeze_weight outside 0 .. 255");
-        if ((rc = product_of_kind(h, fn, body_id, GVOM_PRODUCT_BODY_VOLUME, "unknown or stale body volume id", &bvol))) return rc;
-        if (bvol->cap != H || bvol->xy != xy) return refuse(h, fn, "the body volume was made for another number of headings or another window side");
+    DevSet *vol[2] = {nullptr, nullptr};
+    for (int i = 0; i < 2; ++i) {
+        const PoseVolume &v = volumes[i];
+        const auto &is = POSE_VOLUMES[i];
+        if (!v.present) continue;
+        if (v.mask > is.mask_limit) return refuse(h, fn, std::string(is.mask_name) + " outside 0 .. " + is.mask_top);
+        if (v.weight < 0 || v.weight > 255) return refuse(h, fn, std::string(is.weight_name) + " outside 0 .. 255");
+        if ((rc = product_of_kind(h, fn, v.id, is.kind, (std::string("unknown or stale ") + is.noun + " volume id").c_str(), &vol[i]))) return rc;
+        if (vol[i]->cap != H || vol[i]->xy != xy) return refuse(h, fn, std::string("the ") + is.noun + " volume was made for another number of headings or another window side");
     }
     HIPCHK(h, hipSetDevice(h->device));
     DevSet *set = nullptr;
@@ -1038,10 +1073,9 @@ static int pose_field_call(gvom_t *h, const char *fn, int64_t costfield_id, cons
     const int16_t *prims = (const int16_t *)((char *)h->pf_tab.p + h->pf_prims_at);
     HIPCHK(h, gvom_launch_pose_seed(h->stream, 0, xy, H, R, (const int32_t *)cost32, c16w, C, D, G.fl, G.goals, (int)n_goals, G.cnt + CTG_CNT_SEEDED));
     HIPCHK(h, gvom_launch_cspace(h->stream, xy, H, c16, (const int32_t *)h->fp_tab.p, (const uint32_t *)((char *)h->fp_tab.p + h->fp_offs_at), C));
-    if (vol) HIPCHK(h, gvom_launch_cspace_attitude(h->stream, xy, H, part_ptr<const uint8_t>(vol, 0), part_ptr<const uint8_t>(vol, 1), block_mask,
-                                                   (uint32_t)tilt_weight, C));
-    if (bvol) HIPCHK(h, gvom_launch_cspace_attitude(h->stream, xy, H, part_ptr<const uint8_t>(bvol, 0), part_ptr<const uint8_t>(bvol, 1), body_mask,
-                                                    (uint32_t)squeeze_weight, C));
+    for (int i = 0; i < 2; ++i)
+        if (vol[i]) HIPCHK(h, gvom_launch_cspace_attitude(h->stream, xy, H, part_ptr<const uint8_t>(vol[i], 0), part_ptr<const uint8_t>(vol[i], 1),
+                                                          volumes[i].mask, (uint32_t)volumes[i].weight, C));
     HIPCHK(h, gvom_launch_pose_seed(h->stream, 1, xy, H, R, (const int32_t *)cost32, c16w, C, D, G.fl, G.goals, (int)n_goals, G.cnt + CTG_CNT_SEEDED));
     const int32_t cap = max_cost == 0 ? GVOM_CTG_MAX_COST : max_cost;
     const int inner = h->pf.tune_inner > 0 ? h->pf.tune_inner : 64;
@@ -1062,16 +1096,16 @@ static int pose_field_call(gvom_t *h, const char *fn, int64_t costfield_id, cons
 VIS int gvom_pose_field(gvom_t *h, int64_t costfield_id, const int32_t *cost, int on_device, const int32_t *goals, int64_t n_goals,
                         int32_t max_cost, int32_t max_rounds, int64_t *product_id, int64_t info[4])
 {
-    return pose_field_call(h, "gvom_pose_field", costfield_id, cost, on_device, false, -1, 0u, 0, false, -1, 0u, 0, goals, n_goals, max_cost, max_rounds,
-                           product_id, info);
+    const PoseVolume none[2] = {};
+    return pose_field_call(h, "gvom_pose_field", costfield_id, cost, on_device, none, goals, n_goals, max_cost, max_rounds, product_id, info);
 }
 
 VIS int gvom_pose_field_attitude(gvom_t *h, int64_t costfield_id, const int32_t *cost, int on_device, int64_t volume_id, uint32_t block_mask,
                                  int32_t tilt_weight, const int32_t *goals, int64_t n_goals, int32_t max_cost, int32_t max_rounds,
                                  int64_t *product_id, int64_t info[4])
 {
-    return pose_field_call(h, "gvom_pose_field_attitude", costfield_id, cost, on_device, true, volume_id, block_mask, tilt_weight, false, -1, 0u, 0,
-                           goals, n_goals, max_cost, max_rounds, product_id, info);
+    const PoseVolume v[2] = {{true, volume_id, block_mask, tilt_weight}, {}};
+    return pose_field_call(h, "gvom_pose_field_attitude", costfield_id, cost, on_device, v, goals, n_goals, max_cost, max_rounds, product_id, info);
 }
 
 VIS int gvom_pose_field_volumes(gvom_t *h, int64_t costfield_id, const int32_t *cost, int on_device, int64_t attitude_volume_id,
@@ -1087,8 +1121,9 @@ VIS int gvom_pose_field_volumes(gvom_t *h, int64_t costfield_id, const int32_t *
         for (int k = 0; info && k < 4; ++k) info[k] = 0;
         return refuse(h, fn, "a mask or a weight that is not 0 beside a volume id of -1");
     }
-    return pose_field_call(h, fn, costfield_id, cost, on_device, attitude_volume_id >= 0, attitude_volume_id, attitude_block_mask, tilt_weight,
-                           body_volume_id >= 0, body_volume_id, body_block_mask, squeeze_weight, goals, n_goals, max_cost, max_rounds, product_id, info);
+    const PoseVolume v[2] = {{attitude_volume_id >= 0, attitude_volume_id, attitude_block_mask, tilt_weight},
+                             {body_volume_id >= 0, body_volume_id, body_block_mask, squeeze_weight}};
+    return pose_field_call(h, fn, costfield_id, cost, on_device, v, goals, n_goals, max_cost, max_rounds, product_id, info);
 }
 
 // the table of "attitude volumes" (av_tab: (u - am, v) of every footprint cell and per heading the wheels' cell offsets and the footprint's
@@ -1129,49 +1164,37 @@ VIS int gvom_attitude_volume(gvom_t *h, int64_t map_set_id, const double *ground
     *product_id = -1;
     const char *const fn = "gvom_attitude_volume";
     int rc;
-    if (h->sharded) return refuse(h, fn, "sharded handles are not supported");
-    if (h->fp_H < 1) return refuse(h, fn, "no footprint table is set (gvom_footprint_set)");
-    if (h->at_H < 1) return refuse(h, fn, "no chassis is set (gvom_chassis_set)");
-    if (h->fp_H > GVOM_POSE_MAX_HEADINGS) return refuse(h, fn, "footprint tables of more than 64 headings are not supported", GVOM_ERR_CAPACITY);
-    if (h->at_H != h->fp_H) return refuse(h, fn, "the chassis was set for another number of headings than the footprint table has");
+    if ((rc = check_standing(h, fn, true))) return rc;
     if (flags & ~GVOM_ATTITUDE_INFERRED_GROUND) return refuse(h, fn, "unknown flag bits");
     if ((rc = check_one_source(h, fn, map_set_id >= 0, ground, !ground, "a map set id", "a ground map", "a ground map")) || (rc = check_side(h, fn))) return rc;
     const int xy = h->prm.xy_size, H = h->fp_H;
     const size_t n2 = (size_t)xy * xy;
-    if ((int64_t)H * (int64_t)n2 > GVOM_POSE_MAX_STATES) return refuse(h, fn, "more than 2^28 states (headings x xy_size^2)", GVOM_ERR_CAPACITY);
-    DevSet *m = nullptr;
-    if (map_set_id >= 0 && (rc = map_set_of(h, map_set_id, &m))) return rc;
+    if ((rc = check_states(h, fn, H, xy))) return rc;
+    Ground g;
+    if (map_set_id >= 0 && (rc = map_set_of(h, map_set_id, &g.m))) return rc;
     HIPCHK(h, hipSetDevice(h->device));
     DevSet *set = nullptr;
     const size_t bytes = set_bytes(GVOM_PRODUCT_ATTITUDE_VOLUME, xy, 0, H);
     if ((rc = product_acquire(h, GVOM_PRODUCT_ATTITUDE_VOLUME, bytes, bytes, fn, &h->av_allocs, &set))) return rc;
     set->cap = H;
-    const gvom_chassis_t &c = h->at_chassis;
-    if ((rc = volume_table_reserve(h, H))) return rc;
-    if (m && (rc = stage_buf(h, h->av_ground, n2 * 8, h->av_allocs))) return rc;
-    const double *gdev = m ? (const double *)h->av_ground.p : ground;
+    if ((rc = volume_table_reserve(h, H)) || (rc = ground_reserve(h, g, h->av_ground, h->av_allocs, ground))) return rc;
     HIPCHK(h, join_second_stream(h));
-    if (!m && !on_device) {                                                 // a host ground map: staged, and up before the call returns
+    if (!g.m && !on_device) {                                               // a host ground map: staged, and up before the call returns
         const HostPart part = {ground, n2 * 8};
         const void *dev;
         if ((rc = stage_host(h, h->av_stage, h->av_allocs, &part, 1, true, &dev))) return rc;
-        gdev = (const double *)dev;
+        g.dev = (const double *)dev;
     }
-    const int32_t *fstart = (const int32_t *)h->fp_tab.p;
-    const uint32_t *foffs = (const uint32_t *)((char *)h->fp_tab.p + h->fp_offs_at);
-    if ((rc = volume_table_rebuild(h, H))) return rc;
-    if ((rc = set_wait_releases(h, set))) return rc;
-    if (m) HIPCHK(h, gvom_launch_attitude_ground(h->stream, xy, (flags & GVOM_ATTITUDE_INFERRED_GROUND) ? 1 : 0, part_ptr<const double>(m, 4),
-                                                part_ptr<const double>(m, 5), (double *)h->av_ground.p));
+    if ((rc = volume_table_rebuild(h, H)) || (rc = set_wait_releases(h, set)) || (rc = ground_write(h, g, flags))) return rc;
     AttitudeVolumeParams P;
     memset(&P, 0, sizeof P);
     P.xy = xy; P.H = H;
-    P.wheelbase = c.front_axle - c.rear_axle; P.track = c.track; P.belly_height = c.belly_height;
-    P.max_pitch = c.max_pitch; P.max_roll = c.max_roll; P.min_clearance = c.min_clearance;
+    chassis_lengths(h, P.wheelbase, P.track, nullptr);
+    chassis_limits(h->at_chassis, P);
     int32_t *counts = part_ptr<int32_t>(set, 2);
     HIPCHK(h, hipMemsetAsync(counts, 0, 32, h->stream));
-    HIPCHK(h, gvom_launch_attitude_volume(h->stream, P, fstart, foffs, (const double *)h->av_tab.p, (const int32_t *)((char *)h->av_tab.p + h->av_wcell_at),
-                                          gdev, part_ptr<uint8_t>(set, 0), part_ptr<uint8_t>(set, 1), counts));
+    HIPCHK(h, gvom_launch_attitude_volume(h->stream, P, (const int32_t *)h->fp_tab.p, (const uint32_t *)((char *)h->fp_tab.p + h->fp_offs_at), (const double *)h->av_tab.p,
+                                          (const int32_t *)((char *)h->av_tab.p + h->av_wcell_at), g.dev, part_ptr<uint8_t>(set, 0), part_ptr<uint8_t>(set, 1), counts));
     return product_publish(h, set, product_id);
 }
 
@@ -1189,11 +1212,7 @@ VIS int gvom_body_volume(gvom_t *h, int64_t field_product_id, const float *field
     *product_id = -1;
     const char *const fn = "gvom_body_volume";
     int rc;
-    if (h->sharded) return refuse(h, fn, "sharded handles are not supported");
-    if (h->fp_H < 1) return refuse(h, fn, "no footprint table is set (gvom_footprint_set)");
-    if (h->at_H < 1) return refuse(h, fn, "no chassis is set (gvom_chassis_set)");
-    if (h->fp_H > GVOM_POSE_MAX_HEADINGS) return refuse(h, fn, "footprint tables of more than 64 headings are not supported", GVOM_ERR_CAPACITY);
-    if (h->at_H != h->fp_H) return refuse(h, fn, "the chassis was set for another number of headings than the footprint table has");
+    if ((rc = check_standing(h, fn, true))) return rc;
     if (h->bd_S < 1) return refuse(h, fn, "no body is set (gvom_body_set)");
     if (!origin_cells) return refuse(h, fn, "origin_cells must not be NULL");
     if (flags & ~GVOM_ATTITUDE_INFERRED_GROUND) return refuse(h, fn, "unknown flag bits");
@@ -1208,55 +1227,34 @@ VIS int gvom_body_volume(gvom_t *h, int64_t field_product_id, const float *field
     if ((rc = check_side(h, fn))) return rc;
     const int xy = h->prm.xy_size, H = h->fp_H;
     const size_t n2 = (size_t)xy * xy;
-    if ((int64_t)H * (int64_t)n2 > GVOM_POSE_MAX_STATES) return refuse(h, fn, "more than 2^28 states (headings x xy_size^2)", GVOM_ERR_CAPACITY);
-    DevSet *m = nullptr, *f = nullptr;
-    if (map_set_id >= 0 && (rc = map_set_of(h, map_set_id, &m))) return rc;
-    int64_t B[3];
-    int fn_xy = xy, fn_zs = h->prm.z_size;
-    if (field_product_id >= 0) {
-        f = find_set(h->psets, field_product_id);
-        if (!f || f->kind != GVOM_PRODUCT_VOXEL_DISTANCE) return refuse(h, fn, "unknown or stale distance field id");
-        for (int k = 0; k < 3; ++k) B[k] = f->origin[k];
-        fn_xy = f->xy; fn_zs = f->zs;
-    } else {
-        for (int k = 0; k < 3; ++k) {
-            if (field_origin[k] < -((int64_t)1 << 40) || field_origin[k] > ((int64_t)1 << 40)) return refuse(h, fn, "a field origin beyond 2^40 voxels");
-            B[k] = field_origin[k];
-        }
-    }
+    if ((rc = check_states(h, fn, H, xy))) return rc;
+    Ground g;
+    Field F;
+    if ((map_set_id >= 0 && (rc = map_set_of(h, map_set_id, &g.m))) || (rc = field_of(h, fn, field_product_id, field_origin, F))) return rc;
     HIPCHK(h, hipSetDevice(h->device));
     DevSet *set = nullptr;
     const size_t bytes = set_bytes(GVOM_PRODUCT_BODY_VOLUME, xy, 0, H);
     if ((rc = product_acquire(h, GVOM_PRODUCT_BODY_VOLUME, bytes, bytes, fn, &h->bv_allocs, &set))) return rc;
     set->cap = H;
-    if ((rc = volume_table_reserve(h, H))) return rc;
-    if (m && (rc = stage_buf(h, h->bv_ground, n2 * 8, h->bv_allocs))) return rc;
-    const double *gdev = m ? (const double *)h->bv_ground.p : ground;
-    const float *fdev = f ? part_ptr<const float>(f, 0) : field;
+    if ((rc = volume_table_reserve(h, H)) || (rc = ground_reserve(h, g, h->bv_ground, h->bv_allocs, ground))) return rc;
+    const float *fdev = F.f ? part_ptr<const float>(F.f, 0) : field;
     HIPCHK(h, join_second_stream(h));
     if (!on_device && (field || ground)) {                                  // a host field and / or ground map: staged, and up before the call returns
-        const HostPart parts[2] = {{field, n2 * (size_t)fn_zs * 4}, {ground, n2 * 8}};
+        const HostPart parts[2] = {{field, n2 * (size_t)F.zs * 4}, {ground, n2 * 8}};
         const void *dev[2];
         if ((rc = stage_host(h, h->bv_stage, h->bv_allocs, parts, 2, true, dev))) return rc;
         if (dev[0]) fdev = (const float *)dev[0];
-        if (dev[1]) gdev = (const double *)dev[1];
+        if (dev[1]) g.dev = (const double *)dev[1];
     }
-    if ((rc = volume_table_rebuild(h, H))) return rc;
-    if ((rc = set_wait_releases(h, set))) return rc;
-    if (m) HIPCHK(h, gvom_launch_attitude_ground(h->stream, xy, (flags & GVOM_ATTITUDE_INFERRED_GROUND) ? 1 : 0, part_ptr<const double>(m, 4),
-                                                part_ptr<const double>(m, 5), (double *)h->bv_ground.p));
-    const gvom_chassis_t &c = h->at_chassis;
+    if ((rc = volume_table_rebuild(h, H)) || (rc = set_wait_releases(h, set)) || (rc = ground_write(h, g, flags))) return rc;
     BodyParams P;
     memset(&P, 0, sizeof P);
     P.R.xy = xy; P.R.H = H; P.R.res = h->prm.xy_resolution; P.R.ox = origin_cells[0]; P.R.oy = origin_cells[1];
-    P.wheelbase = c.front_axle - c.rear_axle; P.track = c.track; P.axle_mid = 0.5 * (c.front_axle + c.rear_axle);
-    P.z_res = h->prm.z_resolution;
-    P.bx = B[0]; P.by = B[1]; P.bz = B[2];
-    P.n = fn_xy; P.zs = fn_zs; P.S = h->bd_S; P.min_margin = min_margin;
+    body_params(h, F, min_margin, P);
     int32_t *counts = part_ptr<int32_t>(set, 3);
     HIPCHK(h, hipMemsetAsync(counts, 0, 32, h->stream));
     HIPCHK(h, gvom_launch_body_volume(h->stream, P, soft_margin, (const int32_t *)((char *)h->av_tab.p + h->av_wcell_at),
-                                      (const double *)((char *)h->at_tab.p + h->at_cs_at), gdev, (const float *)h->bd_tab.p, fdev,
+                                      (const double *)((char *)h->at_tab.p + h->at_cs_at), g.dev, (const float *)h->bd_tab.p, fdev,
                                       part_ptr<uint8_t>(set, 0), part_ptr<uint8_t>(set, 1), part_ptr<float>(set, 2), counts));
     return product_publish(h, set, product_id);
 }

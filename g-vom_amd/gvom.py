@@ -758,6 +758,16 @@ class DeviceArray(_ProductView):
         return a if dtype is None else a.astype(dtype)
 
 
+class _OnePartDLPack(object):
+    """DLPack of a view of several arrays hands out ONE of them: the DeviceArray that the view's `_dlpack_part` names."""
+
+    def __dlpack_device__(self):
+        return getattr(self, self._dlpack_part).__dlpack_device__()
+
+    def __dlpack__(self, stream=None, max_version=None, dl_device=None, copy=None):
+        return getattr(self, self._dlpack_part).__dlpack__(stream=stream, max_version=max_version, dl_device=dl_device, copy=copy)
+
+
 class DeviceVoxelCloud(_ProductView):
     """The result of Gvom.voxel_cloud_device(): `.rows` float32 [cap, 8] (the rows of make_debug_voxel_map, in unspecified
     order), `.eigenvalues` float32 [cap, 3] (row for row) and `.count` int64 [1] (rows the map has; those beyond cap are dropped),
@@ -1283,13 +1293,14 @@ def box_spheres(x0, x1, half_width, z0, z1, radius):
     return np.ascontiguousarray(np.concatenate([g, np.full((g.shape[0], 1), r)], axis=1), dtype=np.float32)
 
 
-class DeviceBodyClearance(_ProductView):
+class DeviceBodyClearance(_OnePartDLPack, _ProductView):
     """The result of DeviceDistanceField.score_body() / score_body_of() / Gvom.score_body_of() / score_body_of_device(): `.summary`
     int32 [K, 4] -- per rollout {status (BODY_*), first bad pose (T: none), the pose of the least clearance in front of it and that
     pose's tightest sphere (-1 without one)} --, `.clearance` float32 [K, T] -- the least of (field at the sphere's voxel - radius)
     over the body, metres, +inf where nothing is within the field's cap -- and `.status` uint8 [K, T, 2] {BODY_*, tightest sphere}:
     three DeviceArrays of one product, row i = rollout i.  A snapshot: later scans, combines, integrates, set_body and set_chassis
     calls do not change it.  DLPack hands over `.clearance`; copy_to_host() returns (summary, clearance, status) as numpy."""
+    _dlpack_part = "clearance"
 
     def __init__(self, hold):
         _ProductView.__init__(self, hold)
@@ -1297,12 +1308,6 @@ class DeviceBodyClearance(_ProductView):
 
     def copy_to_host(self):
         return self.summary.copy_to_host(), self.clearance.copy_to_host(), self.status.copy_to_host()
-
-    def __dlpack_device__(self):
-        return self.clearance.__dlpack_device__()
-
-    def __dlpack__(self, stream=None, max_version=None, dl_device=None, copy=None):
-        return self.clearance.__dlpack__(stream=stream, max_version=max_version, dl_device=dl_device, copy=copy)
 
 
 class _AttitudePlanes(DeviceArray):
@@ -1316,13 +1321,14 @@ class _AttitudePlanes(DeviceArray):
         return raw.transpose(0, 2, 1)
 
 
-class DeviceAttitudeVolume(_ProductView):
+class DeviceAttitudeVolume(_OnePartDLPack, _ProductView):
     """The result of DeviceMaps.attitude_volume() / Gvom.attitude_volume_of() / attitude_volume_of_device(): `.status` uint8
     [H, xy, xy] -- ATTITUDE_* of the vehicle standing in the centre of cell (x, y) at heading h -- and `.tilt` uint8 [H, xy, xy] -- how
     much of the nearer of the pitch and the roll limit the state uses, 0 .. 100 percent (0 on unknown ground and outside the window)
     --, both indexed [h, x, y], and `.counts` int32 [8]: the states per status code 0 .. 6, then H.  Three DeviceArrays of one
     product; `__dlpack__` hands out `.status`.  A snapshot: later scans, combines, set_footprint and set_chassis calls do not change
     it.  copy_to_host() returns (status, tilt, counts) as numpy."""
+    _dlpack_part = "status"
 
     def __init__(self, hold):
         _ProductView.__init__(self, hold)
@@ -1331,39 +1337,42 @@ class DeviceAttitudeVolume(_ProductView):
     def copy_to_host(self):
         return self.status.copy_to_host(), self.tilt.copy_to_host(), self.counts.copy_to_host()
 
-    def __dlpack_device__(self):
-        return self.status.__dlpack_device__()
 
-    def __dlpack__(self, stream=None, max_version=None, dl_device=None, copy=None):
-        return self.status.__dlpack__(stream=stream, max_version=max_version, dl_device=dl_device, copy=copy)
-
-
-def _pose_attitude(attitude, attitude_blocks, tilt_weight):
-    """the attitude keywords of the pose_field calls -> None, or (the volume's product id, block mask, tilt weight)"""
-    if attitude is None:
-        if tilt_weight != 0:
-            raise ValueError("tilt_weight needs an attitude volume (attitude=...)")
+def _pose_volume(volume, blocks, weight, word, cls, maker, top, weight_word):
+    """the keywords of one volume of the pose_field calls (word = "attitude" or "body") -> None, or (the volume's product id, block
+    mask, weight)"""
+    if volume is None:
+        if weight != 0:
+            raise ValueError("%s needs %s %s volume (%s=...)" % (weight_word, "an" if word[0] in "aeiou" else "a", word, word))
         return None
-    if not isinstance(attitude, DeviceAttitudeVolume):
-        raise TypeError("attitude must be a DeviceAttitudeVolume (DeviceMaps.attitude_volume()), got %r" % (type(attitude).__name__,))
+    if not isinstance(volume, cls):
+        raise TypeError("%s must be a %s (%s), got %r" % (word, cls.__name__, maker, type(volume).__name__))
     mask = 0
     try:
-        for b in attitude_blocks:
-            if isinstance(b, bool) or int(b) != b or not 0 <= int(b) <= 6:
+        for b in blocks:
+            if isinstance(b, bool) or int(b) != b or not 0 <= int(b) <= top:
                 raise ValueError
             mask |= 1 << int(b)
     except (TypeError, ValueError, OverflowError):
-        raise ValueError("attitude_blocks must be a sequence of ATTITUDE_* codes 0 .. 6, got %r" % (attitude_blocks,))
+        raise ValueError("%s_blocks must be a sequence of %s_* codes 0 .. %d, got %r" % (word, word.upper(), top, blocks))
     try:
-        ok = not isinstance(tilt_weight, bool) and int(tilt_weight) == tilt_weight and 0 <= int(tilt_weight) <= 255
+        ok = not isinstance(weight, bool) and int(weight) == weight and 0 <= int(weight) <= 255
     except (TypeError, ValueError, OverflowError):
         ok = False
     if not ok:
-        raise ValueError("tilt_weight must be an integer in 0 .. 255, got %r" % (tilt_weight,))
-    return attitude.product_id, mask, int(tilt_weight)
+        raise ValueError("%s must be an integer in 0 .. 255, got %r" % (weight_word, weight))
+    return volume.product_id, mask, int(weight)
 
 
-class DeviceBodyVolume(_ProductView):
+def _pose_attitude(attitude, attitude_blocks, tilt_weight):
+    return _pose_volume(attitude, attitude_blocks, tilt_weight, "attitude", DeviceAttitudeVolume, "DeviceMaps.attitude_volume()", 6, "tilt_weight")
+
+
+def _pose_body(body, body_blocks, squeeze_weight):
+    return _pose_volume(body, body_blocks, squeeze_weight, "body", DeviceBodyVolume, "DeviceDistanceField.body_volume()", 5, "squeeze_weight")
+
+
+class DeviceBodyVolume(_OnePartDLPack, _ProductView):
     """The result of DeviceDistanceField.body_volume() / body_volume_of() / Gvom.body_volume_of() / body_volume_of_device(): `.status`
     uint8 [H, xy, xy] -- BODY_* of the sphere body (Gvom.set_body) with the vehicle standing in the centre of cell (x, y) at heading h
     --, `.squeeze` uint8 [H, xy, xy] -- how much of the band between soft_margin and min_margin the state has used up, 0 .. 100 percent
@@ -1372,6 +1381,7 @@ class DeviceBodyVolume(_ProductView):
     --, all indexed [h, x, y], and `.counts` int32 [8]: the states per status code 0 .. 5, then H and S.  Four DeviceArrays of one
     product; `__dlpack__` hands out `.status`.  A snapshot: later scans, combines, integrates, set_footprint, set_chassis and set_body
     calls do not change it.  copy_to_host() returns (status, squeeze, clearance, counts) as numpy."""
+    _dlpack_part = "status"
 
     def __init__(self, hold):
         _ProductView.__init__(self, hold)
@@ -1381,15 +1391,9 @@ class DeviceBodyVolume(_ProductView):
     def copy_to_host(self):
         return self.status.copy_to_host(), self.squeeze.copy_to_host(), self.clearance.copy_to_host(), self.counts.copy_to_host()
 
-    def __dlpack_device__(self):
-        return self.status.__dlpack_device__()
-
-    def __dlpack__(self, stream=None, max_version=None, dl_device=None, copy=None):
-        return self.status.__dlpack__(stream=stream, max_version=max_version, dl_device=dl_device, copy=copy)
-
 
 def _body_margins(min_margin, soft_margin):
-    """the margins of the body_volume calls -> (min_margin, soft_margin) as float32-exact Python floats; soft_margin None: min_margin"""
+    """the margins of the score_body and body_volume calls -> (min_margin, soft_margin) as float32-exact Python floats; soft_margin None: min_margin"""
     with np.errstate(over="ignore"):
         mm = float(np.float32(min_margin))
         sm = mm if soft_margin is None else float(np.float32(soft_margin))
@@ -1400,31 +1404,6 @@ def _body_margins(min_margin, soft_margin):
     if sm < mm:
         raise ValueError("soft_margin must not be less than min_margin, got %r < %r" % (soft_margin, min_margin))
     return mm, sm
-
-
-def _pose_body(body, body_blocks, squeeze_weight):
-    """the body keywords of the pose_field calls -> None, or (the volume's product id, block mask, squeeze weight)"""
-    if body is None:
-        if squeeze_weight != 0:
-            raise ValueError("squeeze_weight needs a body volume (body=...)")
-        return None
-    if not isinstance(body, DeviceBodyVolume):
-        raise TypeError("body must be a DeviceBodyVolume (DeviceDistanceField.body_volume()), got %r" % (type(body).__name__,))
-    mask = 0
-    try:
-        for b in body_blocks:
-            if isinstance(b, bool) or int(b) != b or not 0 <= int(b) <= 5:
-                raise ValueError
-            mask |= 1 << int(b)
-    except (TypeError, ValueError, OverflowError):
-        raise ValueError("body_blocks must be a sequence of BODY_* codes 0 .. 5, got %r" % (body_blocks,))
-    try:
-        ok = not isinstance(squeeze_weight, bool) and int(squeeze_weight) == squeeze_weight and 0 <= int(squeeze_weight) <= 255
-    except (TypeError, ValueError, OverflowError):
-        ok = False
-    if not ok:
-        raise ValueError("squeeze_weight must be an integer in 0 .. 255, got %r" % (squeeze_weight,))
-    return body.product_id, mask, int(squeeze_weight)
 
 
 # ---- frontier extraction (DeviceCostField.frontiers, Gvom.frontiers_of and friends; include/gvom_hip.h "frontier extraction") ----
@@ -2272,11 +2251,12 @@ def _voxel_origin(origin_voxels, what="origin_voxels", limit=None):
     return (_I64 * 3)(int(o[0]), int(o[1]), int(o[2]))
 
 
-class DeviceVoxelBox(_ProductView):
+class DeviceVoxelBox(_OnePartDLPack, _ProductView):
     """The result of VoxelAtlas.box(): `.classes` uint8 [xy, xy, z] in the occupancy grid's layout -- VOXEL_NEVER, VOXEL_FREE or
     VOXEL_OCCUPIED per voxel, VOXEL_NEVER outside the extent -- and `.counts` int32 [4] {occupied, free, voxels outside the extent,
     seq}: two DeviceArrays of one product.  `.origin_voxels`: the box's corner in world voxels.  `classes == VOXEL_OCCUPIED` is an
     occupancy grid of remembered space.  A snapshot.  DLPack hands over the class grid.  copy_to_host() returns (classes, counts)."""
+    _dlpack_part = "classes"
 
     def __init__(self, hold, origin_voxels):
         _ProductView.__init__(self, hold)
@@ -2285,12 +2265,6 @@ class DeviceVoxelBox(_ProductView):
 
     def copy_to_host(self):
         return self.classes.copy_to_host(), self.counts.copy_to_host()
-
-    def __dlpack_device__(self):
-        return self.classes.__dlpack_device__()
-
-    def __dlpack__(self, stream=None, max_version=None, dl_device=None, copy=None):
-        return self.classes.__dlpack__(stream=stream, max_version=max_version, dl_device=dl_device, copy=copy)
 
 
 class DeviceAtlasRays(_ProductView):
@@ -2376,12 +2350,13 @@ class DeviceDistanceSamples(_ProductView):
         return self.distance.copy_to_host(), self.counts.copy_to_host()
 
 
-class DeviceDistanceField(_ProductView):
+class DeviceDistanceField(_OnePartDLPack, _ProductView):
     """The result of VoxelAtlas.distance_field(): `.distance` float32 [xy, xy, z] in the class grid's layout -- metres from the
     voxel's centre to the centre of the nearest source voxel anywhere in the atlas's extent, 0 at a source, +inf beyond
     `.max_distance` -- and `.counts` int32 [4] {voxels at 0, voxels with a finite distance, voxels outside the extent, seq}: two
     DeviceArrays of one product.  `.origin_voxels`: the box's corner in world voxels; the field lines up voxel for voxel with
     VoxelAtlas.box() at the same origin.  A snapshot.  DLPack hands over `.distance`; copy_to_host() returns (distance, counts)."""
+    _dlpack_part = "distance"
 
     def __init__(self, hold, origin_voxels, max_distance):
         _ProductView.__init__(self, hold)
@@ -2390,12 +2365,6 @@ class DeviceDistanceField(_ProductView):
 
     def copy_to_host(self):
         return self.distance.copy_to_host(), self.counts.copy_to_host()
-
-    def __dlpack_device__(self):
-        return self.distance.__dlpack_device__()
-
-    def __dlpack__(self, stream=None, max_version=None, dl_device=None, copy=None):
-        return self.distance.__dlpack__(stream=stream, max_version=max_version, dl_device=dl_device, copy=copy)
 
     def _sample(self, points_ptr, n, on_device):
         g = self._hold._owner
@@ -3388,13 +3357,16 @@ class Gvom(object):
         a = _body_spheres(spheres)
         self._check_args(self._lib.gvom_body_set(self._h, _ptr(a), a.shape[0]))
 
+    def _host_field(self, field):
+        f = np.ascontiguousarray(np.asarray(field), dtype=np.float32)
+        if f.shape != (self.xy_size, self.xy_size, self.z_size):
+            raise ValueError("field must have shape (%d, %d, %d), got %r" % (self.xy_size, self.xy_size, self.z_size, f.shape))
+        return f
+
     def _score_body(self, field_id, field_ptr, field_origin, set_id, ground_ptr, poses_ptr, K, T, on_device, inferred_ground, origin, min_margin):
         oc = _rollout_origin(origin, self.xy_resolution)
         flags = _ATTITUDE_INFERRED_GROUND if inferred_ground else 0
-        with np.errstate(over="ignore"):
-            mm = float(np.float32(min_margin))
-        if not math.isfinite(mm):
-            raise ValueError("min_margin must be a finite distance in metres, got %r" % (min_margin,))
+        mm, _ = _body_margins(min_margin, None)
         return DeviceBodyClearance(self._make_product(lambda pid: self._lib.gvom_score_body(
             self._h, int(field_id), field_ptr, field_origin, int(set_id), ground_ptr, poses_ptr, int(K), int(T), int(on_device), flags, oc,
             ctypes.c_float(mm), pid), PRODUCT_BODY, self._check_args))
@@ -3404,9 +3376,7 @@ class Gvom(object):
         (xy_size, xy_size, z_size) in the class grid's layout, its corner at field_origin_voxels (three integers, world voxels);
         ground as score_attitude_of takes it; origin: the window corner in world metres.  Needs no scan and no combine.  A
         convenience route: field, map and poses are copied to the device."""
-        f = np.ascontiguousarray(np.asarray(field), dtype=np.float32)
-        if f.shape != (self.xy_size, self.xy_size, self.z_size):
-            raise ValueError("field must have shape (%d, %d, %d), got %r" % (self.xy_size, self.xy_size, self.z_size, f.shape))
+        f = self._host_field(field)
         gm = self._window_map("ground", ground, np.float64)
         p = _rollout_poses(poses)
         return self._score_body(-1, _ptr(f), _voxel_origin(field_origin_voxels, "field_origin_voxels"), -1, _ptr(gm), _ptr(p), p.shape[0],
@@ -3435,9 +3405,7 @@ class Gvom(object):
         """DeviceDistanceField.body_volume() with a field AND a ground map of the caller's: field and field_origin_voxels as
         score_body_of takes them, ground as score_attitude_of takes it; origin: the window corner in world metres.  Needs no scan and
         no combine.  A convenience route: field and map are copied to the device."""
-        f = np.ascontiguousarray(np.asarray(field), dtype=np.float32)
-        if f.shape != (self.xy_size, self.xy_size, self.z_size):
-            raise ValueError("field must have shape (%d, %d, %d), got %r" % (self.xy_size, self.xy_size, self.z_size, f.shape))
+        f = self._host_field(field)
         gm = self._window_map("ground", ground, np.float64)
         return self._body_volume(-1, _ptr(f), _voxel_origin(field_origin_voxels, "field_origin_voxels"), -1, _ptr(gm), 0, False, origin,
                                  min_margin, soft_margin)

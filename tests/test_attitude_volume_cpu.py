@@ -30,6 +30,21 @@ def test_header_library_and_binding_agree():
         gvom.ATTITUDE_INVALID)
     assert gvom._ATTITUDE_BLOCKS == (gvom.ATTITUDE_PITCH, gvom.ATTITUDE_ROLL, gvom.ATTITUDE_BELLY)
     assert gvom._PRODUCT_DTYPES[30] == (np.uint8, np.uint8, np.int32)
+    # one text of the definition: k_attitude and k_volume_attitude take the status words, the known-ground rule, the wheels and the
+    # stance from gvom_rollouts.h; the volume kernel has no copy of its own
+    csrc = os.path.join(ROOT, "g-vom_amd", "csrc")
+    shared = open(os.path.join(csrc, "gvom_rollouts.h")).read()
+    for word in ("#define AT_OK 0", "#define AT_LEFT_WINDOW 5", "#define AT_INVALID 6", "bool at_known(", "AtStance at_stance(", "AtWheels at_state_wheels(",
+                 "bool at_pose_cells(", "bool at_pose_heights(", "void at_tally(", "int at_first_bad("):
+        assert word in shared, word
+    for unit, words in (("gvom_attitude.hip", ("at_pose_cells(", "at_pose_heights(", "at_stance(", "at_first_bad(", "AT_LEFT_WINDOW")),
+                        ("gvom_attitude_volume.hip", ("at_state_wheels(", "at_stance(", "at_known(", "at_tally(", "AT_LEFT_WINDOW"))):
+        text = open(os.path.join(csrc, unit)).read()
+        assert '#include "gvom_rollouts.h"' in text
+        for word in words:
+            assert word in text, (unit, word)
+        for own in ("av_known", "0.25 * (", "#define AT_OK", "#define AV_OK", "AV_LEFT_WINDOW", "wcell[h * 12 + 2", "wheels[(h * 4"):
+            assert own not in text, (unit, own)
 
 
 def test_the_products_layout_under_sanitizers(tmp_path):

@@ -60,6 +60,22 @@ def test_the_symbols_the_defines_and_the_binding():
     for unit in ("gvom_body.hip", "gvom_body_volume.hip"):
         text = open(os.path.join(ROOT, "g-vom_amd", "csrc", unit)).read()
         assert '#include "gvom_bodyframe.h"' in text and "bd_frame(" in text and "bd_sphere(" in text and "bd_margin(" in text and "sqrt(" not in text
+    # one text of the vehicle on the ground: all four kernels that stand it there take the wheels, the stance, the census and the first
+    # bad pose from gvom_rollouts.h, and none spells them out again
+    csrc = os.path.join(ROOT, "g-vom_amd", "csrc")
+    shared = open(os.path.join(csrc, "gvom_rollouts.h")).read()
+    assert '#include "gvom_rollouts.h"' in open(os.path.join(csrc, "gvom_bodyframe.h")).read()
+    calls = {"gvom_attitude.hip": ("at_pose_cells(", "at_pose_heights(", "at_stance(", "at_first_bad("),
+             "gvom_body.hip": ("at_pose_cells(", "at_pose_heights(", "at_stance(", "at_first_bad("),
+             "gvom_attitude_volume.hip": ("at_state_wheels(", "at_stance(", "at_known(", "at_tally("),
+             "gvom_body_volume.hip": ("at_state_wheels(", "at_stance(", "at_tally(")}
+    for unit, words in calls.items():
+        text = open(os.path.join(csrc, unit)).read()
+        assert '#include "gvom_rollouts.h"' in text or '#include "gvom_bodyframe.h"' in text, unit
+        for word in words:
+            assert word in text and "__device__ __forceinline__" in shared and re.search(r"\b%s" % re.escape(word), shared), (unit, word)
+        for own in ("wcell[h * 12 + 2", "wheels[(h * 4", "at_cell(", "__builtin_popcountll", "__builtin_ctzll", "0.5 * (z[", "0.25 * ("):
+            assert own not in text, (unit, own)
 
 
 def test_the_header_carries_the_phrases_the_definition_rests_on():

@@ -448,8 +448,8 @@ VIS void gvom_destroy(gvom_t *h)
     if (h->x_host) hipHostFree(h->x_host);
     for (auto &s : h->slots) { hipFree(s.state); hipFree(s.code16); hipFree(s.tags); fb(s.crows); fb(s.metrics); fb(s.base); fb(s.rowvox); }
     for (auto &f : h->fused) { hipFree(f.state); hipFree(f.tags); fb(f.rows); fb(f.metrics); }
-    fb(h->in_pts); fb(h->cl_g); fb(h->cl_stage); fb(h->rq_stage); fb(h->ctg_stage); fb(h->ctg_clr); fb(h->fp_tab); fb(h->ro_stage); fb(h->at_tab); fb(h->at_ground); fb(h->at_stage); fb(h->bd_tab); fb(h->bd_ground); fb(h->bd_stage); fb(h->al_grid); fb(h->al_stage); fb(h->fr_stage); fb(h->vp_bitmaps); fb(h->vp_stage); fb(h->pf_tab); fb(h->pf_stage); fb(h->atl_stage); fb(h->af_clr); fb(h->av_tab); fb(h->av_ground); fb(h->av_stage); fb(h->bv_ground); fb(h->bv_stage);hipFree(h->atl_mem); hipFree(h->atl_cnt); if (h->atl_pin) hipHostFree(h->atl_pin); fb(h->va_stage); fb(h->va_bitmaps); fb(h->va_dist); hipFree(h->va_mem); hipFree(h->va_cnt); if (h->va_pin) hipHostFree(h->va_pin); fb(h->ri_model); fb(h->ri_raw); fb(h->ri_poses); if (h->ri_poses_pin) hipHostFree(h->ri_poses_pin); fb(h->mo_dev); if (h->mo_pin) hipHostFree(h->mo_pin); fb(h->world_pts[0]); fb(h->world_pts[1]); fb(h->flink[0]); fb(h->flink[1]); fb(h->tl); fb(h->dir_keys); fb(h->dir_perm); hipFree(h->dir_hist);
-    for (SolveWork *w : {&h->ctg, &h->fr, &h->pf, &h->af, &h->afr}) { fb(w->work); if (w->pin) hipHostFree(w->pin); }   // the calls that wait: work buffer and pinned counters
+    fb(h->in_pts); fb(h->cl_g); fb(h->cl_stage); fb(h->rq_stage); fb(h->ctg_stage); fb(h->ctg_clr); fb(h->fp_tab); fb(h->ro_stage); fb(h->at_tab); fb(h->at_ground); fb(h->at_stage); fb(h->bd_tab); fb(h->bd_ground); fb(h->bd_stage); fb(h->al_grid); fb(h->al_stage); fb(h->fr_stage); fb(h->vp_bitmaps); fb(h->vp_stage); fb(h->pf_tab); fb(h->pf_stage); fb(h->atl_stage); fb(h->af_clr); fb(h->av_tab); fb(h->av_ground); fb(h->av_stage); fb(h->bv_ground); fb(h->bv_stage);hipFree(h->atl_mem); hipFree(h->atl_cnt); if (h->atl_pin) hipHostFree(h->atl_pin); fb(h->va_stage); fb(h->va_bitmaps); fb(h->va_dist); fb(h->va_chg); hipFree(h->va_mem); hipFree(h->va_cnt); if (h->va_pin) hipHostFree(h->va_pin); fb(h->ri_model); fb(h->ri_raw); fb(h->ri_poses); if (h->ri_poses_pin) hipHostFree(h->ri_poses_pin); fb(h->mo_dev); if (h->mo_pin) hipHostFree(h->mo_pin); fb(h->world_pts[0]); fb(h->world_pts[1]); fb(h->flink[0]); fb(h->flink[1]); fb(h->tl); fb(h->dir_keys); fb(h->dir_perm); hipFree(h->dir_hist);
+    for (SolveWork *w : {&h->ctg, &h->fr, &h->pf, &h->af, &h->afr, &h->vchg}) { fb(w->work); if (w->pin) hipHostFree(w->pin); }   // the calls that wait: work buffer and pinned counters
     hipFree(h->counters); if (h->counters_host) hipHostFree(h->counters_host);
     hipFree(h->descs_dev); if (h->descs_host) hipHostFree(h->descs_host);
     hipFree(h->blockcounts); hipFree(h->blockcounts2); hipFree(h->hmaps2);
@@ -626,7 +626,8 @@ VIS int gvom_get_tuning(gvom_t *h, const char *name, int *value)
     if (!strcmp(name, "voxel_atlas_levels")) { *value = h->va_A ? h->va_Z : 0; return GVOM_OK; }         // read-only: its levels Z
     if (!strcmp(name, "voxel_atlas_allocations")) { *value = h->va_allocs; return GVOM_OK; }             // read-only: device allocations the gvom_voxel_atlas_* calls have made
     if (!strcmp(name, "voxel_atlas_viewpoint_batch")) { *value = h->va_last_batch; return GVOM_OK; }     // read-only: poses per launch of the last gvom_voxel_atlas_score_viewpoints
-    if (!strcmp(name, "voxel_distance_field")) { *value = 1; return GVOM_OK; }                           // read-only: the library has gvom_voxel_atlas_distance_field and gvom_voxel_distance_sample
+    if (!strcmp(name, "voxel_changes")) { *value = 1; return GVOM_OK; }                                  // read-only: the library has gvom_voxel_atlas_changes
+    if (!strcmp(name, "voxel_distance_field")) { *value = 1; return GVOM_OK; }                          // read-only: the library has gvom_voxel_atlas_distance_field and gvom_voxel_distance_sample
     if (!strcmp(name, "voxel_distance_mb")) { *value = h->tune_vd_mb; return GVOM_OK; }
     if (!strcmp(name, "voxel_distance_halo_xy")) { *value = h->vd_halo[0]; return GVOM_OK; }             // read-only: Hxy of the last gvom_voxel_atlas_distance_field
     if (!strcmp(name, "voxel_distance_halo_z")) { *value = h->vd_halo[1]; return GVOM_OK; }              // read-only: its Hz

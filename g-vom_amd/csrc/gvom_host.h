@@ -20,6 +20,7 @@
 #include <immintrin.h>
 #include <algorithm>
 #include <atomic>
+#include <functional>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -443,6 +444,11 @@ struct gvom_handle {
     Buf va_dist;
     int tune_vd_mb = GVOM_VDIST_DEFAULT_MB;
     int vd_halo[2] = {0, 0};
+    // VOXEL ATLAS CHANGES (gvom_voxel_atlas_changes): vchg.work = gvom_frontiers' work buffer (fr_offsets) at the window's side; va_chg = 256
+    // bytes of uint64 counters {appeared, vanished, outside}, then the bit planes (gvom_vchange_planes_bytes), the columns' level pairs
+    // and the distance plane, each 256-byte aligned; both grow-only and counted in va_allocs
+    SolveWork vchg;
+    Buf va_chg;
     // ATTITUDE VOLUMES (gvom_attitude_volume): av_tab = what k_volume_attitude_table makes of the footprint table and the chassis --
     // (u - am, v) float64 pairs of every footprint cell, then at av_wcell_at bytes (a multiple of 256) per heading the wheels' cell offsets and the
     // footprint's box, [H][12] int32 --, rebuilt by the first call after a gvom_footprint_set / gvom_chassis_set (fp_gen / at_gen count those; av_fp_gen
@@ -614,9 +620,10 @@ int ctg_solve(gvom_handle *h, SolveWork &w, const GoalWorkPtrs &G, int n, const 
 // the part of gvom_frontiers that gvom_atlas_frontiers shares: everything around the marking kernel.  frontier_work: the work buffer
 // for n x n cells (fr_offsets) reserved in w, and its parts; the caller clears the first clear_bytes -- counters and flags -- on the
 // stream, waits for its set's releases and marks.  frontier_solve: the rows' initialisation, the rounds under gvom_frontiers' tuning,
-// the finish, the set's publication, info and w.last_*; errors are in fn's name.  It waits.
+// the finish, the set's publication, info and w.last_*; errors are in fn's name.  It waits.  `more` (gvom_voxel_atlas_changes' part 4;
+// empty for the frontier calls) is enqueued behind the finish and in front of the publication: what it writes is part of the product.
 struct FrWork { uint32_t *cnt, *fl, *bc, *L, *count; size_t clear_bytes; };
 int frontier_work(gvom_handle *h, SolveWork &w, int n, int &allocs, FrWork *W);
 int frontier_solve(gvom_handle *h, const char *fn, SolveWork &w, int n, const int32_t *D, const FrWork &W, int32_t min_cells,
-                   int32_t max_clusters, DevSet *set, int64_t *product_id, int64_t info[4]);
+                   int32_t max_clusters, DevSet *set, int64_t *product_id, int64_t info[4], const std::function<hipError_t()> &more = {});
 }  // namespace gvom_host

@@ -578,6 +578,23 @@ hipError_t gvom_launch_vatlas_raycast(hipStream_t s, const ScanParams &P, const 
 hipError_t gvom_launch_vatlas_viewpoints(hipStream_t s, const ScanParams &P, const ViewQuery &Q, const VAtlas &V, int batch, const int32_t *boxes,
                                          uint32_t *bitmaps, int32_t *rows);
 hipError_t gvom_launch_vatlas_viewpoint_best(hipStream_t s, const ScanParams &P, const ViewQuery &Q, const VAtlas &V, int32_t *rows, int32_t *best);
+// voxel atlas changes (gvom_voxel_changes.hip; include/gvom_hip.h "voxel atlas changes" defines the result).  B = the WINDOW as the box
+// kernels take a box (n, zs, r*, p*; the other fields are not read), F, fstate, ftags = the fused map as the merge takes it.
+// planes: gvom_vchange_planes_bytes(n, zs) of 16-byte words {appeared, vanished}, word ((y * zs + z) * nseg + q) = columns 64 q .. 64 q + 63
+// of window row y and level z, nseg = ceil(n / 64); cnt uint64 [3], CLEARED by the caller = {appeared, vanished, outside the extent}.
+// codes: out uint8 [n][n][zs] = 0 / 1 appeared / 2 vanished.  columns: cols uint16 [2][n][n] (appeared / vanished voxels per column,
+// [y][x] inside a plane), lohi uint32 [n][n] = lowest | highest << 16 of the levels whose code is in mask; L, count, flags, n_marked as
+// for gvom_launch_frontier_mark; D int32 [n][n] = squared cells to cell (n / 2, n / 2); rows4 int32 [cap][4] initialised.  clusters
+// (behind gvom_launch_frontier_finish): cmap = its cluster map, totals = its totals; rows4 = {appeared, vanished, lowest, highest level}
+// per kept rank below cap, zero beyond; counts[4 .. 7] = cnt[0 .. 2] (saturated to int32), seq.
+size_t gvom_vchange_planes_bytes(int n, int zs);
+hipError_t gvom_launch_vchange_planes(hipStream_t s, const VAtlas &V, const VAtlasBox &B, const OccParams &F, const int32_t *fstate,
+                                      const uint32_t *ftags, void *planes, unsigned long long *cnt);
+hipError_t gvom_launch_vchange_codes(hipStream_t s, int n, int zs, const void *planes, uint8_t *out);
+hipError_t gvom_launch_vchange_columns(hipStream_t s, int xy, int zs, int mask, int cap, const void *planes, uint16_t *cols, uint32_t *lohi,
+                                       uint32_t *L, uint32_t *count, uint32_t *flags, uint32_t *n_marked, int32_t *D, int32_t *rows4);
+hipError_t gvom_launch_vchange_clusters(hipStream_t s, int xy, int cap, int seq, const int32_t *cmap, const uint16_t *cols, const uint32_t *lohi,
+                                        const uint32_t *totals, const unsigned long long *cnt, int32_t *rows4, int32_t *counts);
 // voxel distance fields (gvom_voxel_distance.hip; include/gvom_hip.h "voxel distance field" defines the result).  B = the box as the box
 // kernels take it (n, zs, r*, p*, outside, seq).  The passes in y and z run on the box GROWN by the halo where a source can lie: hby rows
 // below the box, nyg rows in all (>= hby + n); hbz levels below, nzg in all.  kx = 64-bit words the x pass searches on either side, hxy =

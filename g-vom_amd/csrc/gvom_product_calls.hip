@@ -298,7 +298,7 @@ int frontier_work(gvom_handle *h, SolveWork &w, int n, int &allocs, FrWork *W)
 }
 
 int frontier_solve(gvom_handle *h, const char *fn, SolveWork &w, int n, const int32_t *D, const FrWork &W, int32_t min_cells,
-                   int32_t max_clusters, DevSet *set, int64_t *product_id, int64_t info[4])
+                   int32_t max_clusters, DevSet *set, int64_t *product_id, int64_t info[4], const std::function<hipError_t()> &more)
 {
     const int nt = gvom_frontier_tiles(n);
     uint32_t *const cnt = W.cnt;
@@ -317,6 +317,7 @@ int frontier_solve(gvom_handle *h, const char *fn, SolveWork &w, int n, const in
     if (!S.converged) return refuse(h, fn, "the labels did not settle", GVOM_ERR_HIP);                  // (the set keeps id -1: nobody gets it)
     HIPCHK(h, gvom_launch_frontier_finish(h->stream, n, min_cells, max_clusters, D, W.L, W.count, W.bc, cnt + FR_CNT_KEPT, cnt + FR_CNT_CELLS, rows,
                                           sums, cmap, counts));
+    if (more) HIPCHK(h, more());
     if ((rc = product_publish(h, set, product_id))) return rc;             // (`ready` goes in front of the counters' way back)
     HIPCHK(h, hipMemcpyAsync(w.pin, cnt, 256, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));

@@ -55,6 +55,11 @@
 //   body volume (46) cap x xy*xy uint8 (status), then cap x xy*xy uint8 (squeeze), then cap x xy*xy floats (clearance): volumes [h][y][x],
 //                    every plane laid out like a pose field's; then 8 int32 {states per status 0 .. 5, H, S}; cap = the headings H of the
 //                    call that wrote it.  Kind 45 is not assigned
+//   voxel changes (48)  the four parts of frontiers (16) with part 3 grown to 8 int32 {n_kept, marked columns, those in kept clusters, cap,
+//                    appeared voxels, vanished voxels, window voxels outside the extent, seq}; then cap x 4 int32 {appeared voxels, vanished
+//                    voxels, lowest level, highest level} per kept cluster; then xy*xy*zs bytes, out[x][y][z] like the voxel box: the change
+//                    codes 0 / 1 / 2; then 2 x xy*xy uint16 (appeared / vanished voxels per column): planes [k][y][x], each laid out like a
+//                    pose field's; cap = max_clusters of the call that wrote it.  Kind 47 is not assigned
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -109,6 +114,8 @@ inline size_t set_bytes(int kind, int xy, int zs, int64_t cap, int64_t cols = 0)
     case GVOM_PRODUCT_VOXEL_DISTANCE_SAMPLES: return align256((size_t)cap * 4) + 16;
     case GVOM_PRODUCT_BODY: return align256((size_t)cap * 16) + align256((size_t)cap * (size_t)cols * 4) + (size_t)cap * (size_t)cols * 2;
     case GVOM_PRODUCT_BODY_VOLUME: return 2 * align256((size_t)cap * n2) + align256((size_t)cap * n2 * 4) + 32;
+    case GVOM_PRODUCT_VOXEL_CHANGES:
+        return align256((size_t)cap * 32) + 2 * align256((size_t)cap * 16) + align256(n2 * 4) + 256 + align256(n2 * zs) + n2 * 4;
     }
     return 0;
 }
@@ -294,6 +301,28 @@ inline bool set_part(const SetShape *s, int part, SetPart *d)
         d->shape[0] = s->cap; d->shape[1] = d->shape[2] = xy;
         d->strides[0] = n2; d->strides[1] = 1; d->strides[2] = xy;
         if (part < 2) { d->code = kDLUInt; d->bits = 8; }
+        break;
+    }
+    case GVOM_PRODUCT_VOXEL_CHANGES: {                     // parts 0 .. 3 as frontiers (16), part 3 with 8 words
+        if (part < 0 || part > 6) return false;
+        char *const sums = s->mem + align256((size_t)s->cap * 32), *const cmap = sums + align256((size_t)s->cap * 16);
+        char *const counts = cmap + align256((size_t)n2 * 4), *const rows4 = counts + 256;
+        char *const codes = rows4 + align256((size_t)s->cap * 16), *const cols = codes + align256((size_t)n2 * s->zs);
+        if (part == 0) { rows(s->mem, s->cap, 8); d->code = kDLInt; }
+        else if (part == 1) { rows(sums, s->cap, 2); d->code = kDLInt; d->bits = 64; }
+        else if (part == 2) { d->ptr = cmap; d->shape[0] = d->shape[1] = xy; d->strides[0] = 1; d->strides[1] = xy; d->code = kDLInt; }   // [x, y] indexing, column-major, like a device map
+        else if (part == 3) { d->ptr = counts; d->ndim = 1; d->shape[0] = 8; d->strides[0] = 1; d->shape[1] = d->strides[1] = 1; d->code = kDLInt; }
+        else if (part == 4) { rows(rows4, s->cap, 4); d->code = kDLInt; }
+        else if (part == 5) {
+            d->ptr = codes; d->ndim = 3; d->code = kDLUInt; d->bits = 8;
+            d->shape[0] = d->shape[1] = xy; d->shape[2] = s->zs;
+            d->strides[0] = xy * s->zs; d->strides[1] = s->zs; d->strides[2] = 1;
+        }
+        else {                                             // [k, x, y] indexing: every plane column-major, like a pose field's
+            d->ptr = cols; d->ndim = 3; d->code = kDLUInt; d->bits = 16;
+            d->shape[0] = 2; d->shape[1] = d->shape[2] = xy;
+            d->strides[0] = n2; d->strides[1] = 1; d->strides[2] = xy;
+        }
         break;
     }
     default: return false;

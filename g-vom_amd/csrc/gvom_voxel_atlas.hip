@@ -31,20 +31,12 @@
 #include "gvom_ray.h"
 #include "gvom_raywalk.h"
 #include "gvom_classgrid.h"
+#include "gvom_vatlas_pairs.h"                               // the pair type and address, the fused-state read, the extent mask
 #include <algorithm>
 
 #define VA_BLOCK 256
 #define VA_WAVES (VA_BLOCK / WAVE)
 #define VA_MERGE_BLOCKS 2048                              // the most workgroups of k_vatlas_merge / k_vatlas_move: 8 per CU (every wave slot), each strides over its share
-
-typedef unsigned long long v2ull __attribute__((ext_vector_type(2)));      // one pair: .x observed, .y occupied
-
-__device__ __forceinline__ unsigned long long bits_below(uint32_t n) { return n >= 64u ? ~0ull : (1ull << n) - 1ull; }    // bits 0 .. n - 1
-
-__device__ __forceinline__ size_t va_pair(const VAtlas &V, uint32_t sx, uint32_t sy, uint32_t sz)
-{
-    return ((((size_t)sy << V.lgZ) | sz) << V.lgP) | (sx >> 6);
-}
 
 // ---- integrate -------------------------------------------------------------------------------------------------------------------------
 // A wave takes (window row y, window level z) = row r = yi * nz + zi at a time and walks its npx pair columns.  They are STORAGE columns --
@@ -80,11 +72,7 @@ __global__ __launch_bounds__(VA_BLOCK) void k_vatlas_merge(const VAtlas V, const
             const uint32_t mx = in ? wx + (uint32_t)F.om[0] : 0u;
             const uint32_t fx = min(mx, mx - uxy);
             int32_t s = -1;
-            if (in) {
-                const uint32_t tg = ftags[row * (uint32_t)F.nseg + (fx >> 6)];
-                const int32_t sv = fstate[row * uxy + fx];
-                s = tg == F.epoch ? sv : -1;                                               // a stale tile reads "never observed"
-            }
+            if (in) s = va_fused_state(F, fstate, ftags, row, fx);
             const unsigned long long m_in = lanes(in), m_obs = lanes(in && s != -1), m_occ = lanes(in && s >= 0);
             v2ull *const pair = (v2ull *)V.pairs + va_pair(V, sx, sy, sz);
             const v2ull old = *pair;                                                       // (wave-uniform address: every lane reads the pair)
@@ -180,10 +168,7 @@ __global__ __launch_bounds__(VA_BLOCK) void k_vatlas_box(const VAtlas V, const V
             const v2ull hi = ((const v2ull *)V.pairs)[va_pair(V, (sx + 64u) & (uA - 1u), sy, sz)];
             obs |= hi.x << (64u - sh); occ |= hi.y << (64u - sh);
         }
-        // box columns x0 + b inside the box and inside the extent: 0 <= rx + x0 + b < A
-        const int e0 = B.rx + (int)x0;                                                     // extent voxel of bit 0 (|rx| <= 2^30)
-        const int lo_b = e0 < 0 ? -e0 : 0, hi_b = min((int)(n - x0), (int)uA - e0);        // bits [lo_b, hi_b)
-        const unsigned long long valid = hi_b > lo_b ? bits_below((uint32_t)min(hi_b, 64)) & ~bits_below((uint32_t)min(lo_b, 64)) : 0ull;
+        const unsigned long long valid = va_columns_inside(B.rx, x0, n, uA);
         obs &= valid; occ &= valid;
     }
     const uint32_t c_occ = wave_sum((uint32_t)__builtin_popcountll(occ)), c_free = wave_sum((uint32_t)__builtin_popcountll(obs & ~occ));

@@ -1,5 +1,5 @@
 // gvom_voxel_atlas_calls.hip -- the voxel atlas's entry points (include/gvom_hip.h "voxel atlas"): gvom_voxel_atlas_configure, _integrate,
-// _clear, _counts, _box, _raycast, _score_viewpoints and _score_alignments.  The kernels are gvom_voxel_atlas.hip's; everything runs on the handle's stream --
+// _clear, _counts, _box, _changes, _raycast, _score_viewpoints and _score_alignments.  The kernels are gvom_voxel_atlas.hip's (gvom_voxel_changes.hip's for _changes, which waits like gvom_frontiers); everything runs on the handle's stream --
 // an integrate behind whatever produced the current fused map, a query behind the integrates before it -- and only gvom_voxel_atlas_counts
 // waits for it (the viewpoint call waits where it has to read poses or the sensor model back: the boxes of its bitmaps are proved here, on
 // the host).  The products go through the pool path of every product call (product_acquire / product_publish, gvom_sets.hip), host inputs
@@ -60,6 +60,15 @@ int64_t box_frame(const gvom_handle *h, const int64_t B[3], VAtlasBox &X)
     X.rx = r[0]; X.ry = r[1]; X.rz = r[2];
     X.px = (int)(B[0] & (h->va_A - 1)); X.py = (int)(B[1] & (h->va_A - 1)); X.pz = (int)(B[2] & (h->va_Z - 1));
     return (int64_t)n[0] * n[1] * n[2];
+}
+
+// the CURRENT fused map -- the map of the most recently begun combine -- as gvom_voxel_atlas_integrate and gvom_voxel_atlas_changes take
+// it: GVOM_NO_DATA before the first combine, refused where its window lies at or beyond 2^30 voxels
+int current_map(gvom_handle *h, const char *fn, const Fused **F)
+{
+    if (!h->has_combined) return GVOM_NO_DATA;
+    *F = &h->fused[h->cur];
+    return near_origin((*F)->origin) ? GVOM_OK : refuse(h, fn, "the window's origin lies at or beyond 2^30 voxels");
 }
 
 // follow mode: the extent goes to `to`; the voxels that entered it become NEVER -- the slab of columns over every row and level, the slab
@@ -249,9 +258,9 @@ VIS int gvom_voxel_atlas_integrate(gvom_t *h)
     const char *const fn = "gvom_voxel_atlas_integrate";
     int rc = need_atlas(h, fn);
     if (rc) return rc;
-    if (!h->has_combined) return GVOM_NO_DATA;
-    const Fused &F = h->fused[h->cur];
-    if (!near_origin(F.origin)) return refuse(h, fn, "the window's origin lies at or beyond 2^30 voxels");
+    const Fused *cur = nullptr;
+    if ((rc = current_map(h, fn, &cur))) return rc;
+    const Fused &F = *cur;
     int64_t to[3];
     for (int k = 0; k < 3; ++k) to[k] = F.origin[k] + window_side(h, k) / 2 - side(h, k) / 2;
     if (h->va_follow && !near_origin(to)) return refuse(h, fn, "the extent would lie at or beyond 2^30 voxels");
@@ -332,6 +341,64 @@ VIS int gvom_voxel_atlas_box(gvom_t *h, const int64_t origin[3], int64_t *produc
     for (int k = 0; k < 3; ++k) set->origin[k] = B[k];
     for (int k = 0; origin_out && k < 3; ++k) origin_out[k] = B[k];
     return product_publish(h, set, product_id);
+}
+
+// What the CURRENT fused map contradicts of what the atlas remembers (include/gvom_hip.h "voxel atlas changes"), read-only on both:
+// k_vchange_planes, _codes and _columns (gvom_voxel_changes.hip) on the handle's stream behind whatever produced that map and the
+// integrates before the call; the columns kernel leaves the labelling's work buffer as k_frontier_mark does, so everything behind it is
+// frontier_solve (gvom_product_calls.hip) on a work buffer of the handle's own (vchg.work), with k_vchange_clusters in front of the
+// publication.  Like gvom_frontiers this call WAITS.
+VIS int gvom_voxel_atlas_changes(gvom_t *h, int mask, int32_t min_cells, int32_t max_clusters, int64_t *product_id, int64_t origin_out[3],
+                                 int64_t info[4])
+{
+    if (!h || !product_id) return GVOM_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(h->mu);
+    *product_id = -1;
+    for (int k = 0; info && k < 4; ++k) info[k] = 0;
+    const char *const fn = "gvom_voxel_atlas_changes";
+    int rc = need_atlas(h, fn);
+    if (rc) return rc;
+    if (mask < 1 || mask > 3) return refuse(h, fn, "mask must be 1 (appeared), 2 (vanished) or 3 (both)");
+    if ((rc = check_clusters(h, fn, min_cells, max_clusters)) || (rc = check_side(h, fn))) return rc;
+    const Fused *cur = nullptr;
+    if ((rc = current_map(h, fn, &cur))) return rc;
+    const Fused &F = *cur;
+    const int xy = h->prm.xy_size, zs = h->prm.z_size;
+    const size_t n2 = (size_t)xy * xy;
+    HIPCHK(h, hipSetDevice(h->device));
+    DevSet *set = nullptr;
+    const size_t bytes = set_bytes(GVOM_PRODUCT_VOXEL_CHANGES, xy, zs, max_clusters);
+    if ((rc = product_acquire(h, GVOM_PRODUCT_VOXEL_CHANGES, bytes, bytes, fn, &h->va_allocs, &set))) return rc;
+    set->cap = max_clusters;
+    FrWork W;
+    if ((rc = frontier_work(h, h->vchg, xy, h->va_allocs, &W))) return rc;
+    const size_t planes_at = 256, lohi_at = planes_at + align256(gvom_vchange_planes_bytes(xy, zs)), d_at = lohi_at + align256(n2 * 4);
+    if ((rc = stage_buf(h, h->va_chg, d_at + n2 * 4, h->va_allocs))) return rc;            // (no kernel of an earlier call is left: every call waits)
+    char *const work = (char *)h->va_chg.p;
+    unsigned long long *const cnt = (unsigned long long *)work;
+    void *const planes = work + planes_at;
+    uint32_t *const lohi = (uint32_t *)(work + lohi_at);
+    int32_t *const D = (int32_t *)(work + d_at);
+    HIPCHK(h, join_second_stream(h));
+    HIPCHK(h, hipMemsetAsync(W.cnt, 0, W.clear_bytes, h->stream));          // the labelling's counters and both halves of the flags
+    HIPCHK(h, hipMemsetAsync(cnt, 0, 256, h->stream));
+    if ((rc = set_wait_releases(h, set))) return rc;
+    VAtlasBox X;
+    box_frame(h, F.origin, X);
+    OccParams P;
+    occ_params(h, F, P);
+    uint16_t *const cols = part_ptr<uint16_t>(set, 6);
+    int32_t *const rows4 = part_ptr<int32_t>(set, 4);
+    HIPCHK(h, gvom_launch_vchange_planes(h->stream, atlas_of(h), X, P, F.state, F.tags, planes, cnt));
+    HIPCHK(h, gvom_launch_vchange_codes(h->stream, xy, zs, planes, part_ptr<uint8_t>(set, 5)));
+    HIPCHK(h, gvom_launch_vchange_columns(h->stream, xy, zs, mask, max_clusters, planes, cols, lohi, W.L, W.count, W.fl, W.cnt + FR_CNT_CELLS, D, rows4));
+    const int seq = (int)std::min<int64_t>(h->va_seq, INT32_MAX);
+    for (int k = 0; k < 3; ++k) set->origin[k] = F.origin[k];
+    for (int k = 0; origin_out && k < 3; ++k) origin_out[k] = F.origin[k];
+    return frontier_solve(h, fn, h->vchg, xy, D, W, min_cells, max_clusters, set, product_id, info, [&]() {
+        return gvom_launch_vchange_clusters(h->stream, xy, max_clusters, seq, part_ptr<const int32_t>(set, 2), cols, lohi, W.cnt + FR_CNT_KEPT, cnt, rows4,
+                                            part_ptr<int32_t>(set, 3));
+    });
 }
 
 // gvom_raycast on the atlas: n segments walked by k_vatlas_raycast, read-only, behind the integrates before the call; the result is a

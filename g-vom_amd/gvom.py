@@ -197,6 +197,7 @@ ABI = [
     ("gvom_voxel_atlas_clear", _I, [_P]),
     ("gvom_voxel_atlas_counts", _I, [_P, ctypes.POINTER(_I64)]),
     ("gvom_voxel_atlas_box", _I, [_P, ctypes.POINTER(_I64), ctypes.POINTER(_I64), ctypes.POINTER(_I64)]),
+    ("gvom_voxel_atlas_changes", _I, [_P, _I, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(_I64), ctypes.POINTER(_I64), ctypes.POINTER(_I64)]),
     ("gvom_voxel_atlas_raycast", _I, [_P, _P, _I64, _P, _I64, _I, _I, ctypes.POINTER(_I64), ctypes.POINTER(_I64)]),
     ("gvom_voxel_atlas_score_viewpoints", _I, [_P, _P, _I64, _I, ctypes.c_double, ctypes.c_int32, ctypes.c_int32, _I, ctypes.POINTER(_I64),
                                                ctypes.POINTER(_I64)]),
@@ -639,7 +640,8 @@ PRODUCT_VOXEL_DISTANCE = 40               # GVOM_PRODUCT_VOXEL_DISTANCE: made by
 PRODUCT_VOXEL_DISTANCE_SAMPLES = 42       # GVOM_PRODUCT_VOXEL_DISTANCE_SAMPLES: made by gvom_voxel_distance_sample (kind 41 is not assigned)
 PRODUCT_BODY = 44                         # GVOM_PRODUCT_BODY: made by gvom_score_body (kind 43 is not assigned)
 PRODUCT_BODY_VOLUME = 46                  # GVOM_PRODUCT_BODY_VOLUME: made by gvom_body_volume (kind 45 is not assigned)
-_BODY_BLOCKS = (1, 2)                     # (BODY_COLLISION, BODY_LEFT_BOX): the statuses a pose field blocks by default -- an unknown clearance is not a free one
+PRODUCT_VOXEL_CHANGES = 48                # GVOM_PRODUCT_VOXEL_CHANGES: made by gvom_voxel_atlas_changes (kind 47 is not assigned)
+_BODY_BLOCKS = (1, 2)                    # (BODY_COLLISION, BODY_LEFT_BOX): the statuses a pose field blocks by default -- an unknown clearance is not a free one
 # element type of part k of a product, by kind (what set_part() of csrc/gvom_setlayout.h gives as DLPack code and bits)
 _PRODUCT_DTYPES = {PRODUCT_OCCUPANCY: (np.uint8,), PRODUCT_VOXEL_CLOUD: (np.float32, np.float32, np.int64),
                    PRODUCT_HEIGHT_CLOUD: (np.float32,), PRODUCT_INFERRED_HEIGHT_CLOUD: (np.float32,),
@@ -656,7 +658,8 @@ _PRODUCT_DTYPES = {PRODUCT_OCCUPANCY: (np.uint8,), PRODUCT_VOXEL_CLOUD: (np.floa
                    PRODUCT_VOXEL_ATLAS_VIEWPOINTS: (np.int32, np.int32), PRODUCT_VOXEL_ATLAS_ALIGNMENT: (np.int32, np.int32),
                    PRODUCT_VOXEL_DISTANCE: (np.float32, np.int32), PRODUCT_VOXEL_DISTANCE_SAMPLES: (np.float32, np.int32),
                    PRODUCT_BODY: (np.int32, np.float32, np.uint8),
-                   PRODUCT_BODY_VOLUME: (np.uint8, np.uint8, np.float32, np.int32)}
+                   PRODUCT_BODY_VOLUME: (np.uint8, np.uint8, np.float32, np.int32),
+                   PRODUCT_VOXEL_CHANGES: (np.int32, np.int64, np.int32, np.int32, np.int32, np.uint8, np.uint16)}
 CLEARANCE_FAR = 2147483647                # GVOM_CLEARANCE_FAR: squared_cells where no obstacle is in reach
 _CLEARANCE_NO_NEGATIVE = 1                # GVOM_CLEARANCE_NO_NEGATIVE
 
@@ -2267,6 +2270,59 @@ class DeviceVoxelBox(_OnePartDLPack, _ProductView):
         return self.classes.copy_to_host(), self.counts.copy_to_host()
 
 
+CHANGE_APPEARED, CHANGE_VANISHED = 1, 2                 # GVOM_CHANGE_*: the codes of a DeviceVoxelChanges
+
+
+def _change_mask(appeared, vanished):
+    mask = (1 if appeared else 0) | (2 if vanished else 0)
+    if mask == 0:
+        raise ValueError("changes() needs appeared, vanished or both")
+    return mask
+
+
+class DeviceVoxelChanges(_OnePartDLPack, _ProductView):
+    """The result of VoxelAtlas.changes(): what the current fused map contradicts of what the atlas remembers.  `.codes` uint8 [xy, xy, z]
+    in the occupancy grid's layout -- CHANGE_APPEARED where the window is occupied and the atlas remembers free, CHANGE_VANISHED where the
+    window is free and the atlas remembers occupied, 0 elsewhere --, `.column_counts` uint16 [2, xy, xy] (appeared / vanished voxels per
+    column, [k, x, y]-indexed), `.cluster_map` int32 [xy, xy] (the rank of the column's cluster, FRONTIER_NONE where the column is not
+    marked, FRONTIER_SMALL where its cluster is below min_cells), `.rows` int32 [cap, 8], `.sums` int64 [cap, 2] and `.voxels` int32
+    [cap, 4] per kept cluster (include/gvom_hip.h "voxel atlas changes": parts 0, 1 and 4) and `.counts` int32 [8] {kept clusters, marked
+    columns, marked columns in kept clusters, cap, appeared voxels, vanished voxels, window voxels outside the extent, seq}: seven
+    DeviceArrays of one product.  `.origin_voxels`: the window's corner in world voxels; `.rounds`, `.n_clusters`, `.marked_columns` and
+    `.dropped` describe the call.  A snapshot.  DLPack hands over the codes.  copy_to_host() returns (rows, sums, cluster_map, counts,
+    voxels, codes, column_counts)."""
+    _dlpack_part = "codes"
+
+    def __init__(self, hold, origin_voxels, info, xy_resolution, z_resolution):
+        _ProductView.__init__(self, hold)
+        self.origin_voxels = origin_voxels
+        self.rows, self.sums, self.cluster_map, self.counts, self.voxels, self.codes = (DeviceArray(hold, k) for k in range(6))
+        self.column_counts = _PoseVolume(hold, 6)            # planes laid out like a pose field's: [k, x, y]-indexed
+        self.rounds, self.n_clusters, self.marked_columns, self.dropped = int(info[0]), int(info[1]), int(info[2]), int(info[3])
+        self._res = (float(xy_resolution), float(z_resolution))
+
+    def copy_to_host(self):
+        return tuple(a.copy_to_host() for a in (self.rows, self.sums, self.cluster_map, self.counts, self.voxels, self.codes, self.column_counts))
+
+    def clusters(self):
+        """The kept clusters on the host, n = min(n_clusters, cap) of them in ascending label order: a dict of arrays -- "label" int64
+        [n], "columns" int64 [n], "appeared" and "vanished" int64 [n] (voxels), "box" int64 [n, 4] {min x, min y, max x, max y} in
+        window columns, "levels" int64 [n, 2] {lowest, highest} window level of a counted voxel, and in world metres "centroid"
+        float64 [n, 2], "nearest" float64 [n, 2] (the centre of the cluster's column nearest the vehicle), "nearest_distance" float64
+        [n] (between column centres) and "z_range" float64 [n, 2] (bottom of the lowest, top of the highest level)."""
+        n = min(self.n_clusters, self.rows.shape[0])
+        rows, sums, vox = self.rows.copy_to_host()[:n].astype(np.int64), self.sums.copy_to_host()[:n], self.voxels.copy_to_host()[:n].astype(np.int64)
+        xy = self.cluster_map.shape[0]
+        res, zres = self._res
+        W = np.array(self.origin_voxels, np.float64)
+        near = np.stack([rows[:, 6] % xy, rows[:, 6] // xy], axis=1).astype(np.float64)
+        centroid = sums.astype(np.float64) / np.maximum(rows[:, 1:2], 1)
+        return {"label": rows[:, 0], "columns": rows[:, 1], "appeared": vox[:, 0], "vanished": vox[:, 1], "box": rows[:, 2:6], "levels": vox[:, 2:4],
+                "centroid": (centroid + W[:2] + 0.5) * res, "nearest": (near + W[:2] + 0.5) * res,
+                "nearest_distance": np.sqrt(rows[:, 7].astype(np.float64)) * res,
+                "z_range": (vox[:, 2:4] + W[2] + np.array([0.0, 1.0])) * zres}
+
+
 class DeviceAtlasRays(_ProductView):
     """The result of VoxelAtlas.raycast() / raycast_device(): `.result` int32 [n, 3] -- per ray {status (RAY_*; RAY_LEFT_WINDOW: it left
     the extent), steps, unknown voxels passed} --, `.position` float32 [n, 3], where the ray stopped in world metres (NaN where it did
@@ -2474,6 +2530,19 @@ class VoxelAtlas(object):
         out = (_I64 * 3)()
         hold = g._make_product(lambda pid: g._lib.gvom_voxel_atlas_box(g._h, org, pid, out), PRODUCT_VOXEL_BOX, g._check_args)
         return None if hold is None else DeviceVoxelBox(hold, tuple(int(v) for v in out))
+
+    def changes(self, appeared=True, vanished=True, min_cells=2, max_clusters=1024):
+        """What the CURRENT fused map contradicts of what the atlas remembers, BEFORE integrate() merges it: a DeviceVoxelChanges -- the
+        voxels that are occupied now and remembered free (appeared) or free now and remembered occupied (vanished) as codes and per
+        column, and the 8-connected clusters of the columns that hold one of the selected kinds, of at least min_cells columns, at most
+        max_clusters of them summarised.  Read-only on the map and on the atlas; the intended loop is combine_maps_device(), changes(),
+        integrate().  None before the first combine.  Waits for the labelling, like DeviceCostField.frontiers()."""
+        g = self._owner
+        mask = _change_mask(appeared, vanished)
+        mc, cap = _frontier_limits(min_cells, max_clusters)
+        out, info = (_I64 * 3)(), (_I64 * 4)()
+        hold = g._make_product(lambda pid: g._lib.gvom_voxel_atlas_changes(g._h, mask, mc, cap, pid, out, info), PRODUCT_VOXEL_CHANGES, g._check_args)
+        return None if hold is None else DeviceVoxelChanges(hold, tuple(int(v) for v in out), info, g.xy_resolution, g.z_resolution)
 
     def distance_field(self, max_distance, origin_voxels=None, center=None, unknown_blocks=False):
         """The exact 3-D clearance of a window-sized part of the atlas, truncated at max_distance metres: a DeviceDistanceField whose

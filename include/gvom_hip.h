@@ -1447,6 +1447,57 @@ int gvom_pose_field_volumes(gvom_t *h, int64_t costfield_id, const int32_t *cost
                             int32_t squeeze_weight, const int32_t *goals /* [n_goals][3] */, int64_t n_goals, int32_t max_cost,
                             int32_t max_rounds, int64_t *product_id, int64_t info[4]);
 
+/* --- voxel atlas changes (an extension: what is different since I was last here -- the voxels of the current fused map that contradict
+ * what the voxel atlas remembers, as codes, per column, and clustered into objects that appeared or vanished) --------------------------------
+ * gvom_voxel_atlas_integrate counts how many voxels went free -> occupied and occupied -> free with every merge; it does not say where
+ * they are or which object they form.  gvom_voxel_atlas_changes answers that BEFORE the merge, read-only: it compares the CURRENT fused map
+ * -- selected exactly as gvom_voxel_atlas_integrate selects it -- with the atlas as it is at the moment of the call, with no move applied,
+ * and changes neither.  The intended loop is combine, changes, integrate.  An addition: GVOM_ABI_VERSION stays.  gvom_get_tuning
+ * "voxel_changes" (read-only): 1 -- how a caller probes a library for this entry point.  All arithmetic is integer -- population counts,
+ * sums, minima and maxima: the result is exact and does not depend on scheduling.
+ *
+ * DEFINITION.  W = the window origin of the current fused map, xy = xy_size, z = z_size; v = (x, y, l) a window voxel, c(v) the CLASS
+ * ("voxel atlas") of its fused state, a(v) the atlas's class of world voxel W + v (NEVER outside the extent).
+ * CODE       GVOM_CHANGE_APPEARED (1): W + v lies inside the extent, c == OCCUPIED and a == FREE.  GVOM_CHANGE_VANISHED (2): inside the
+ *            extent, c == FREE and a == OCCUPIED.  0 otherwise: first-seen, confirmed, uninformative and outside voxels are no changes.
+ * MASK       1, 2 or 3: the codes that mark a column (bit 0 appeared, bit 1 vanished).
+ * MARKED     column (x, y) is MARKED iff it holds at least one voxel whose code is in mask.
+ * CLUSTERS   the 8-connected components of the marked columns.  LABEL, KEPT (>= min_cells columns), RANK and cap (= max_clusters) are
+ *            word for word those of "frontier extraction", with "frontier cell" read as "marked column".
+ * DISTANCE   the plane that gvom_frontiers calls D is d2(x, y) = (x - cx)^2 + (y - cy)^2 with cx = cy = xy / 2 (integer division): a
+ *            cluster's "best cell" is its column nearest the vehicle, ties broken by the lowest index y * xy + x, and "best D" is that
+ *            squared distance in cells.
+ * The product, of kind GVOM_PRODUCT_VOXEL_CHANGES, is a SNAPSHOT in the product-set pool under its rule (at most GVOM_MAX_PRODUCT_SETS of
+ * the kind, sized by xy, z and max_clusters).  Its parts:
+ *   part 0  int32 [cap, 8]     per kept cluster of rank below cap {label, columns, min x, min y, max x, max y, nearest column, its d2}
+ *   part 1  int64 [cap, 2]     {sum x, sum y} over the cluster's columns
+ *   part 2  int32 [xy, xy]     the cluster map: rank, -1 unmarked, -2 below min_cells; [x, y]-indexed, strides (1, xy)
+ *   part 3  int32 [8]          {n_kept, marked columns, marked columns in kept clusters, cap, appeared voxels, vanished voxels, window
+ *                              voxels outside the extent, the atlas's seq}.  Words 4 and 5 count ALL coded voxels, whatever mask is
+ *   part 4  int32 [cap, 4]     per kept cluster of rank below cap {appeared voxels, vanished voxels, lowest window level, highest window
+ *                              level}: the voxel totals count both codes whatever mask is, the levels only voxels whose code is in mask.
+ *                              Zero rows beyond min(n_kept, cap), as in parts 0 and 1
+ *   part 5  uint8 [xy, xy, z]  the codes, in the occupancy grid's layout (the layout of a voxel box's class grid)
+ *   part 6  uint16 [2, xy, xy] appeared (plane 0) and vanished (plane 1) voxels per column: [k, x, y]-indexed, strides (xy*xy, 1, xy) --
+ *                              every plane has a pose field plane's layout
+ * Parts 0 to 2 and words 0 to 3 of part 3 are what the frontier kernels write, unchanged.
+ *
+ * gvom_voxel_atlas_changes(h, mask, min_cells, max_clusters, &product_id, origin_out, info): info is gvom_frontiers' info {rounds, kept
+ * clusters, marked columns, clusters below min_cells}; origin_out (may be NULL) receives W.  Like gvom_frontiers the call WAITS for the
+ * labelling.  GVOM_NO_DATA before the first combine.  An atlas that was never integrated is valid and yields no change (everything it
+ * holds is NEVER).  GVOM_ERR_INVALID: a sharded handle; no voxel atlas configured; mask outside 1 .. 3; min_cells < 1; max_clusters
+ * outside 1 .. GVOM_FRONTIER_MAX_CLUSTERS; W at or beyond 2^30 voxels; NULL product_id.  GVOM_ERR_CAPACITY: xy_size > 4096; every set of
+ * the kind exported.  The device allocations of the call (its product sets, the labelling's work buffer, the bit planes) are counted in
+ * "voxel_atlas_allocations" and do not grow in steady state.  gvom_device_product(GVOM_PRODUCT_VOXEL_CHANGES) is GVOM_ERR_INVALID (this
+ * call makes them).  Kind 47 is not assigned.
+ * NOT PROVIDED: 26-connected clusters in 3-D; a level band (changes between two heights only); a change query fused into the integrate;
+ * changes against a box other than the current window; sharded handles. */
+#define GVOM_CHANGE_APPEARED 1
+#define GVOM_CHANGE_VANISHED 2
+#define GVOM_PRODUCT_VOXEL_CHANGES 48   /* parts 0 .. 3 as kind 16 with part 3 int32 [8]; part 4 int32 [cap, 4]; part 5 uint8 [xy, xy, z]; part 6 uint16 [2, xy, xy]; kind 47 stays unassigned */
+int gvom_voxel_atlas_changes(gvom_t *h, int mask, int32_t min_cells, int32_t max_clusters, int64_t *product_id,
+                             int64_t origin_out[3] /* may be NULL */, int64_t info[4] /* may be NULL */);
+
 /* --- one map sharded over the GPUs of a node (one rank = one process = one GPU) -------------------
  * No counterpart in the reference (it has no multi-GPU path); semantics = SURVEY 8(e):
  * the rays are data-parallel, the per-voxel accumulators (hit / total: int32 sum, min-height: f32 min)
@@ -1706,6 +1757,7 @@ int gvom_host_timing(gvom_t *h, double us[8]);
  * "body_volume" / "body_volume_allocations" (read-only, gvom_get_tuning): see "body volumes" above.
  * "voxel_distance_field" / "voxel_distance_halo_xy" / "voxel_distance_halo_z" (read-only, gvom_get_tuning), "voxel_distance_mb": see
  * "voxel distance field" above.
+ * "voxel_changes" (read-only, gvom_get_tuning): see "voxel atlas changes" above.
  * (Test hooks are not part of this library: include/gvom_hip_test.h, lib/libgvom_hip_test.so.) */
 int gvom_set_tuning(gvom_t *h, const char *name, int value);
 /* The value the LAST scan ran with ("segs", "period", "ep_row", "prio", "interleave": what automatic resolved to).

@@ -626,4 +626,31 @@ struct FrWork { uint32_t *cnt, *fl, *bc, *L, *count; size_t clear_bytes; };
 int frontier_work(gvom_handle *h, SolveWork &w, int n, int &allocs, FrWork *W);
 int frontier_solve(gvom_handle *h, const char *fn, SolveWork &w, int n, const int32_t *D, const FrWork &W, int32_t min_cells,
                    int32_t max_clusters, DevSet *set, int64_t *product_id, int64_t info[4], const std::function<hipError_t()> &more = {});
+
+// THE WALK QUERIES -- rays, viewpoints, alignments -- against the fused window (gvom_product_calls.hip) and against the voxel atlas
+// (gvom_voxel_atlas_calls.hip): what the two members of a pair do alike.  A caller keeps its own product kind, stage buffer, alloc
+// counter, frame (raycast_params / walk_frame), launches and the one limit only it has, in the order they always had.
+//   rays         check_rays; rays_fill: everything of Q but lit and cap, which the frame gave, the join of the second stream, and host
+//                segments staged, up before it returns, with Q pointed at them
+//   viewpoints   check_views: the checks up to the beam limits, with the beam counts as it leaves them; `span` = side + levels of what
+//                is walked, `spans` its words in the refusal ("xy_size + z_size" / "cells + levels").  views_batch: bitmaps of `bits`
+//                bits in whole 256-byte lines, as many as "viewpoint_bitmap_mb" holds, at most K and the grid's limit.  views_fill:
+//                everything of Q but poses.  views_run: the rows cleared, per batch the bitmaps cleared and batch(nk) launched with
+//                Q.k0 set, then best() behind the last batch
+//   alignments   check_align: the checks and the class grid's size (*grid_bytes); align_fill: everything of P but its frame, the join
+//                of the second stream, and host transforms and cloud staged, up before it returns (*cdev, *tdev: where the kernels read)
+int check_rays(gvom_handle *h, const char *fn, const float *from, int64_t K, const float *to, int64_t n, int flags);
+int rays_fill(gvom_handle *h, Buf &stage, int &allocs, const float *from, int64_t K, const float *to, int64_t n, int on_device, int flags, RayQuery &Q);
+struct ViewBeams { int64_t nh, nw, nb; };
+int check_views(gvom_handle *h, const char *fn, const double *poses, int64_t K, double max_range, int32_t stride_h, int32_t stride_w, int flags,
+                int64_t span, const char *spans, ViewBeams *B);
+int64_t views_batch(const gvom_handle *h, int64_t bits, int64_t K, size_t *bm_words);
+void views_fill(const gvom_handle *h, const RayQuery &R, const ViewBeams &B, int64_t K, double max_range, int32_t stride_h, int32_t stride_w, int flags,
+                size_t bm_words, ViewQuery &Q);
+int views_run(gvom_handle *h, Buf &bitmaps, ViewQuery &Q, int64_t batch, int32_t *rows, const std::function<hipError_t(int)> &launch_batch,
+              const std::function<hipError_t()> &launch_best);
+int check_align(gvom_handle *h, const char *fn, const float *cloud, int64_t n, const double *transforms, int64_t K, int dilate, const int32_t weights[5],
+                size_t *grid_bytes);
+int align_fill(gvom_handle *h, Buf &stage, int &allocs, const float *cloud, int64_t n, const double *transforms, int64_t K, int on_device, int dilate,
+               const int32_t weights[5], AlignParams &P, const float **cdev, const double **tdev);
 }  // namespace gvom_host

@@ -3,7 +3,8 @@
 // gvom_score_attitude (with gvom_chassis_set), gvom_score_body (with gvom_body_set), gvom_score_alignments, gvom_frontiers, gvom_score_viewpoints, gvom_pose_field / gvom_pose_field_attitude / gvom_pose_field_volumes (with
 // gvom_primitives_set), gvom_attitude_volume and gvom_body_volume, and the frame builders they and the debug reads (gvom_debug.hip) give the kernels.  Every call takes its set
 // through product_acquire and hands it out through product_publish (gvom_sets.hip).  What several calls do alike stands once, in
-// front of the entry points, and serves the atlas calls (gvom_atlas_calls.hip) too: the argument checks (check_*, *_of), the staging
+// front of the entry points, and serves the atlas calls (gvom_atlas_calls.hip) and the voxel atlas's walk queries (gvom_voxel_atlas_calls.hip:
+// check_rays / rays_fill, check_views / views_* and check_align / align_fill) too: the argument checks (check_*, *_of), the staging
 // of host inputs (stage_host), the frames (metric_frame, rollout_frame), the vehicle on the ground of the four calls that stand it there
 // (check_standing, the Ground and the Field a call reads, the chassis as the kernels take it) and, for the calls that wait, the round driver (solve_rounds;
 // its arithmetic and the work buffers' layouts are gvom_solvework.h's), the work buffers and the epilogue (goal_solve_finish).  What
@@ -167,6 +168,116 @@ int check_clusters(gvom_handle *h, const char *fn, int32_t min_cells, int32_t ma
 {
     if (min_cells < 1) return refuse(h, fn, "min_cells must be at least 1");
     if (max_clusters < 1 || max_clusters > GVOM_FRONTIER_MAX_CLUSTERS) return refuse(h, fn, "max_clusters outside 1 .. 2^20");
+    return GVOM_OK;
+}
+
+// ---- the walk queries: what gvom_raycast / _score_viewpoints / _score_alignments and their atlas twins do alike (gvom_host.h) ---------------
+int check_rays(gvom_handle *h, const char *fn, const float *from, int64_t K, const float *to, int64_t n, int flags)
+{
+    if (!from || !to) return refuse(h, fn, "from and to must not be NULL");
+    if (n < 1) return refuse(h, fn, "n must be at least 1");
+    if (K != 1 && K != n) return refuse(h, fn, "K must be 1 or n");
+    if (flags & ~(GVOM_RAY_UNKNOWN_BLOCKS | GVOM_RAY_CHECK_TARGET)) return refuse(h, fn, "unknown flag bits");
+    if (n > GVOM_RAYCAST_MAX_RAYS) return refuse(h, fn, "more than 2^26 rays in one call", GVOM_ERR_CAPACITY);
+    return GVOM_OK;
+}
+
+int rays_fill(gvom_handle *h, Buf &stage, int &allocs, const float *from, int64_t K, const float *to, int64_t n, int on_device, int flags, RayQuery &Q)
+{
+    Q.from = from; Q.to = to; Q.n = (long)n;
+    Q.one_origin = K == 1 ? 1 : 0;
+    Q.unknown_blocks = (flags & GVOM_RAY_UNKNOWN_BLOCKS) ? 1 : 0;
+    Q.check_target = (flags & GVOM_RAY_CHECK_TARGET) ? 1 : 0;
+    HIPCHK(h, join_second_stream(h));
+    if (on_device) return GVOM_OK;
+    const HostPart parts[2] = {{from, (size_t)K * 12}, {to, (size_t)n * 12}};                // host segments: staged, and up before the call returns
+    const void *dev[2];
+    if (const int rc = stage_host(h, stage, allocs, parts, 2, true, dev)) return rc;
+    Q.from = (const float *)dev[0]; Q.to = (const float *)dev[1];
+    return GVOM_OK;
+}
+
+int check_views(gvom_handle *h, const char *fn, const double *poses, int64_t K, double max_range, int32_t stride_h, int32_t stride_w, int flags,
+                int64_t span, const char *spans, ViewBeams *B)
+{
+    if (!poses) return refuse(h, fn, "poses must not be NULL");
+    if (h->ri_H <= 0) return refuse(h, fn, "no sensor model (gvom_sensor_model_set)");
+    if (K < 1) return refuse(h, fn, "K must be at least 1");
+    if (stride_h < 1 || stride_w < 1) return refuse(h, fn, "the beam strides must be at least 1");
+    if (!std::isfinite(max_range) || !(max_range > 0.0)) return refuse(h, fn, "max_range must be finite and > 0");
+    if (flags & ~GVOM_RAY_UNKNOWN_BLOCKS) return refuse(h, fn, "unknown flag bits");
+    if (K > GVOM_VIEWPOINT_MAX_POSES) return refuse(h, fn, "more than 65536 viewpoints in one call", GVOM_ERR_CAPACITY);
+    B->nh = ((int64_t)h->ri_H + stride_h - 1) / stride_h; B->nw = ((int64_t)h->ri_W + stride_w - 1) / stride_w; B->nb = B->nh * B->nw;
+    if (B->nb > GVOM_VIEWPOINT_MAX_BEAMS) return refuse(h, fn, "more than 2^22 selected beams", GVOM_ERR_CAPACITY);
+    if (B->nb * (span + 1) >= ((int64_t)1 << 31)) return refuse(h, fn, std::string("beams x (") + spans + " + 1) reaches 2^31", GVOM_ERR_CAPACITY);
+    return GVOM_OK;
+}
+
+int64_t views_batch(const gvom_handle *h, int64_t bits, int64_t K, size_t *bm_words)
+{
+    *bm_words = (((size_t)bits + 31) / 32 + 63) & ~(size_t)63;                  // whole 256-byte lines
+    const int64_t batch = (int64_t)(((size_t)h->tune_vp_mb << 20) / (*bm_words * 4));
+    return std::max<int64_t>(1, std::min<int64_t>(batch, std::min<int64_t>(K, GVOM_VIEWPOINT_MAX_BATCH)));
+}
+
+void views_fill(const gvom_handle *h, const RayQuery &R, const ViewBeams &B, int64_t K, double max_range, int32_t stride_h, int32_t stride_w, int flags,
+                size_t bm_words, ViewQuery &Q)
+{
+    memset(&Q, 0, sizeof Q);
+    Q.dir = (const double *)h->ri_model.p; Q.off = Q.dir + (size_t)h->ri_H * h->ri_W * 3;
+    Q.max_range = max_range;
+    Q.W = h->ri_W; Q.stride_h = stride_h; Q.stride_w = stride_w;
+    Q.nh = (int)B.nh; Q.nw = (int)B.nw; Q.nwc = (int)((B.nw + 63) / 64); Q.nb = (int)B.nb; Q.K = (int)K;
+    Q.unknown_blocks = (flags & GVOM_RAY_UNKNOWN_BLOCKS) ? 1 : 0;
+    Q.lit = R.lit; Q.cap = R.cap; Q.bm_words = (uint32_t)bm_words;
+}
+
+int views_run(gvom_handle *h, Buf &bitmaps, ViewQuery &Q, int64_t batch, int32_t *rows, const std::function<hipError_t(int)> &launch_batch,
+              const std::function<hipError_t()> &launch_best)
+{
+    const int64_t K = Q.K;
+    HIPCHK(h, hipMemsetAsync(rows, 0, (size_t)K * 32, h->stream));
+    for (int64_t k0 = 0; k0 < K; k0 += batch) {
+        const int nk = (int)std::min<int64_t>(batch, K - k0);
+        Q.k0 = (int)k0;
+        HIPCHK(h, hipMemsetAsync(bitmaps.p, 0, (size_t)nk * Q.bm_words * 4, h->stream));
+        HIPCHK(h, launch_batch(nk));
+    }
+    Q.k0 = 0;
+    HIPCHK(h, launch_best());
+    return GVOM_OK;
+}
+
+int check_align(gvom_handle *h, const char *fn, const float *cloud, int64_t n, const double *transforms, int64_t K, int dilate, const int32_t weights[5],
+                size_t *grid_bytes)
+{
+    if (!cloud || !transforms || !weights) return refuse(h, fn, "cloud, transforms and weights must not be NULL");
+    if (n < 1) return refuse(h, fn, "n must be at least 1");
+    if (K < 1) return refuse(h, fn, "K must be at least 1");
+    if (dilate != 0 && dilate != 1) return refuse(h, fn, "dilate must be 0 or 1");
+    for (int c = 0; c < 5; ++c)
+        if (weights[c] < -GVOM_ALIGN_MAX_WEIGHT || weights[c] > GVOM_ALIGN_MAX_WEIGHT) return refuse(h, fn, "a weight outside -1024 .. 1024");
+    if (n > GVOM_ALIGN_MAX_POINTS) return refuse(h, fn, "more than 2^20 returns in one call", GVOM_ERR_CAPACITY);
+    if (K > GVOM_ALIGN_MAX_CANDIDATES) return refuse(h, fn, "more than 65536 candidates in one call", GVOM_ERR_CAPACITY);
+    if (n * K > GVOM_ALIGN_MAX_PAIRS) return refuse(h, fn, "more than 2^32 pairs in one call", GVOM_ERR_CAPACITY);
+    *grid_bytes = gvom_align_grid_bytes(h->prm.xy_size, h->prm.z_size);
+    if (*grid_bytes / 4 > 0xffffffffull) return refuse(h, fn, "the class grid of this map has 2^32 words or more", GVOM_ERR_CAPACITY);
+    return GVOM_OK;
+}
+
+int align_fill(gvom_handle *h, Buf &stage, int &allocs, const float *cloud, int64_t n, const double *transforms, int64_t K, int on_device, int dilate,
+               const int32_t weights[5], AlignParams &P, const float **cdev, const double **tdev)
+{
+    const int xy = h->prm.xy_size;
+    P.n = (long)n; P.K = (int)K; P.xy = xy; P.zs = h->prm.z_size; P.rw = (xy + 15) / 16; P.dilate = dilate;
+    for (int c = 0; c < 5; ++c) P.w[c] = weights[c];
+    *cdev = cloud; *tdev = transforms;
+    HIPCHK(h, join_second_stream(h));
+    if (on_device) return GVOM_OK;
+    const HostPart parts[2] = {{transforms, (size_t)K * 96}, {cloud, (size_t)n * 12}};      // host inputs: staged, and up before the call returns
+    const void *dev[2];
+    if (const int rc = stage_host(h, stage, allocs, parts, 2, true, dev)) return rc;
+    *tdev = (const double *)dev[0]; *cdev = (const float *)dev[1];
     return GVOM_OK;
 }
 
@@ -449,35 +560,22 @@ VIS int gvom_raycast(gvom_t *h, const float *from, int64_t K, const float *to, i
     if (!h || !product_id) return GVOM_ERR_INVALID;
     std::lock_guard<std::mutex> lk(h->mu);
     *product_id = -1;
-    if (h->sharded) return refuse(h, "gvom_raycast", "sharded handles are not supported");
-    if (!from || !to) return refuse(h, "gvom_raycast", "from and to must not be NULL");
-    if (n < 1) return refuse(h, "gvom_raycast", "n must be at least 1");
-    if (K != 1 && K != n) return refuse(h, "gvom_raycast", "K must be 1 or n");
-    if (flags & ~(GVOM_RAY_UNKNOWN_BLOCKS | GVOM_RAY_CHECK_TARGET)) return refuse(h, "gvom_raycast", "unknown flag bits");
-    if (n > GVOM_RAYCAST_MAX_RAYS) return refuse(h, "gvom_raycast", "more than 2^26 rays in one call", GVOM_ERR_CAPACITY);
+    const char *const fn = "gvom_raycast";
+    int rc;
+    if (h->sharded) return refuse(h, fn, "sharded handles are not supported");
+    if ((rc = check_rays(h, fn, from, K, to, n, flags))) return rc;
     if (!h->has_combined) return GVOM_NO_DATA;
     HIPCHK(h, hipSetDevice(h->device));
     DevSet *set = nullptr;
     const size_t bytes = set_bytes(GVOM_PRODUCT_RAYCAST, 0, 0, n);
-    int rc = product_acquire(h, GVOM_PRODUCT_RAYCAST, bytes, bytes, "gvom_raycast", &h->rq_allocs, &set);
-    if (rc) return rc;
+    if ((rc = product_acquire(h, GVOM_PRODUCT_RAYCAST, bytes, bytes, fn, &h->rq_allocs, &set))) return rc;
     set->cap = n;
     const Fused &F = h->fused[h->cur];
     ScanParams P;
     RayQuery Q;
     memset(&Q, 0, sizeof Q);
     raycast_params(h, F, P, Q);
-    Q.from = from; Q.to = to; Q.n = (long)n;
-    Q.one_origin = K == 1 ? 1 : 0;
-    Q.unknown_blocks = (flags & GVOM_RAY_UNKNOWN_BLOCKS) ? 1 : 0;
-    Q.check_target = (flags & GVOM_RAY_CHECK_TARGET) ? 1 : 0;
-    HIPCHK(h, join_second_stream(h));
-    if (!on_device) {                                                       // host segments: staged, and up before the call returns
-        const HostPart parts[2] = {{from, (size_t)K * 12}, {to, (size_t)n * 12}};
-        const void *dev[2];
-        if ((rc = stage_host(h, h->rq_stage, h->rq_allocs, parts, 2, true, dev))) return rc;
-        Q.from = (const float *)dev[0]; Q.to = (const float *)dev[1];
-    }
+    if ((rc = rays_fill(h, h->rq_stage, h->rq_allocs, from, K, to, n, on_device, flags, Q))) return rc;
     if ((rc = set_wait_releases(h, set))) return rc;
     HIPCHK(h, gvom_launch_raycast(h->stream, P, Q, F.state, F.tags, part_ptr<int32_t>(set, 0), part_ptr<float>(set, 1)));
     if ((rc = product_publish(h, set, product_id))) return rc;
@@ -801,25 +899,16 @@ VIS int gvom_score_alignments(gvom_t *h, const float *cloud, int64_t n, const do
     if (!h || !product_id) return GVOM_ERR_INVALID;
     std::lock_guard<std::mutex> lk(h->mu);
     *product_id = -1;
-    if (h->sharded) return refuse(h, "gvom_score_alignments", "sharded handles are not supported");
-    if (!cloud || !transforms || !weights) return refuse(h, "gvom_score_alignments", "cloud, transforms and weights must not be NULL");
-    if (n < 1) return refuse(h, "gvom_score_alignments", "n must be at least 1");
-    if (K < 1) return refuse(h, "gvom_score_alignments", "K must be at least 1");
-    if (dilate != 0 && dilate != 1) return refuse(h, "gvom_score_alignments", "dilate must be 0 or 1");
-    for (int c = 0; c < 5; ++c)
-        if (weights[c] < -GVOM_ALIGN_MAX_WEIGHT || weights[c] > GVOM_ALIGN_MAX_WEIGHT) return refuse(h, "gvom_score_alignments", "a weight outside -1024 .. 1024");
-    if (n > GVOM_ALIGN_MAX_POINTS) return refuse(h, "gvom_score_alignments", "more than 2^20 returns in one call", GVOM_ERR_CAPACITY);
-    if (K > GVOM_ALIGN_MAX_CANDIDATES) return refuse(h, "gvom_score_alignments", "more than 65536 candidates in one call", GVOM_ERR_CAPACITY);
-    if (n * K > GVOM_ALIGN_MAX_PAIRS) return refuse(h, "gvom_score_alignments", "more than 2^32 pairs in one call", GVOM_ERR_CAPACITY);
-    const int xy = h->prm.xy_size, zs = h->prm.z_size;
-    const size_t gb = gvom_align_grid_bytes(xy, zs);
-    if (gb / 4 > 0xffffffffull) return refuse(h, "gvom_score_alignments", "the class grid of this map has 2^32 words or more", GVOM_ERR_CAPACITY);
+    const char *const fn = "gvom_score_alignments";
+    int rc;
+    size_t gb;
+    if (h->sharded) return refuse(h, fn, "sharded handles are not supported");
+    if ((rc = check_align(h, fn, cloud, n, transforms, K, dilate, weights, &gb))) return rc;
     if (!h->has_combined) return GVOM_NO_DATA;
     HIPCHK(h, hipSetDevice(h->device));
     DevSet *set = nullptr;
     const size_t bytes = set_bytes(GVOM_PRODUCT_ALIGNMENT, 0, 0, K);
-    int rc = product_acquire(h, GVOM_PRODUCT_ALIGNMENT, bytes, bytes, "gvom_score_alignments", &h->al_allocs, &set);
-    if (rc) return rc;
+    if ((rc = product_acquire(h, GVOM_PRODUCT_ALIGNMENT, bytes, bytes, fn, &h->al_allocs, &set))) return rc;
     set->cap = K;
     if ((rc = stage_buf(h, h->al_grid, gb, h->al_allocs))) return rc;
     const Fused &F = h->fused[h->cur];
@@ -828,17 +917,9 @@ VIS int gvom_score_alignments(gvom_t *h, const float *cloud, int64_t n, const do
     AlignParams P;
     memset(&P, 0, sizeof P);
     metric_frame(h, F, P);
-    P.n = (long)n; P.K = (int)K; P.xy = xy; P.zs = zs; P.rw = (xy + 15) / 16; P.dilate = dilate;
-    for (int c = 0; c < 5; ++c) P.w[c] = weights[c];
-    const float *cdev = cloud;
-    const double *tdev = transforms;
-    HIPCHK(h, join_second_stream(h));
-    if (!on_device) {                                                       // host inputs: staged, and up before the call returns
-        const HostPart parts[2] = {{transforms, (size_t)K * 96}, {cloud, (size_t)n * 12}};
-        const void *dev[2];
-        if ((rc = stage_host(h, h->al_stage, h->al_allocs, parts, 2, true, dev))) return rc;
-        tdev = (const double *)dev[0]; cdev = (const float *)dev[1];
-    }
+    const float *cdev;
+    const double *tdev;
+    if ((rc = align_fill(h, h->al_stage, h->al_allocs, cloud, n, transforms, K, on_device, dilate, weights, P, &cdev, &tdev))) return rc;
     if ((rc = set_wait_releases(h, set))) return rc;
     HIPCHK(h, gvom_launch_align(h->stream, O, P, F.state, F.tags, cdev, tdev, (uint32_t *)h->al_grid.p, part_ptr<int32_t>(set, 0),
                                 part_ptr<int32_t>(set, 1)));
@@ -907,45 +988,31 @@ VIS int gvom_score_viewpoints(gvom_t *h, const double *poses, int64_t K, int on_
     if (!h || !product_id) return GVOM_ERR_INVALID;
     std::lock_guard<std::mutex> lk(h->mu);
     *product_id = -1;
-    if (h->sharded) return refuse(h, "gvom_score_viewpoints", "sharded handles are not supported");
-    if (!poses) return refuse(h, "gvom_score_viewpoints", "poses must not be NULL");
-    if (h->ri_H <= 0) return refuse(h, "gvom_score_viewpoints", "no sensor model (gvom_sensor_model_set)");
-    if (K < 1) return refuse(h, "gvom_score_viewpoints", "K must be at least 1");
-    if (stride_h < 1 || stride_w < 1) return refuse(h, "gvom_score_viewpoints", "the beam strides must be at least 1");
-    if (!std::isfinite(max_range) || !(max_range > 0.0)) return refuse(h, "gvom_score_viewpoints", "max_range must be finite and > 0");
-    if (flags & ~GVOM_RAY_UNKNOWN_BLOCKS) return refuse(h, "gvom_score_viewpoints", "unknown flag bits");
-    if (K > GVOM_VIEWPOINT_MAX_POSES) return refuse(h, "gvom_score_viewpoints", "more than 65536 viewpoints in one call", GVOM_ERR_CAPACITY);
+    const char *const fn = "gvom_score_viewpoints";
+    int rc;
+    ViewBeams B;
+    if (h->sharded) return refuse(h, fn, "sharded handles are not supported");
     const int xy = h->prm.xy_size, zs = h->prm.z_size;
-    const int64_t nh = ((int64_t)h->ri_H + stride_h - 1) / stride_h, nw = ((int64_t)h->ri_W + stride_w - 1) / stride_w, nb = nh * nw;
-    if (nb > GVOM_VIEWPOINT_MAX_BEAMS) return refuse(h, "gvom_score_viewpoints", "more than 2^22 selected beams", GVOM_ERR_CAPACITY);
-    if (nb * ((int64_t)xy + zs + 1) >= ((int64_t)1 << 31)) return refuse(h, "gvom_score_viewpoints", "beams x (xy_size + z_size + 1) reaches 2^31", GVOM_ERR_CAPACITY);
+    if ((rc = check_views(h, fn, poses, K, max_range, stride_h, stride_w, flags, (int64_t)xy + zs, "xy_size + z_size", &B))) return rc;
     const int64_t V = (int64_t)xy * xy * zs;
-    if (V >= ((int64_t)1 << 31)) return refuse(h, "gvom_score_viewpoints", "the window has 2^31 voxels or more", GVOM_ERR_CAPACITY);
+    if (V >= ((int64_t)1 << 31)) return refuse(h, fn, "the window has 2^31 voxels or more", GVOM_ERR_CAPACITY);
     if (!h->has_combined) return GVOM_NO_DATA;
     HIPCHK(h, hipSetDevice(h->device));
     DevSet *set = nullptr;
     const size_t bytes = set_bytes(GVOM_PRODUCT_VIEWPOINTS, 0, 0, K);
-    int rc = product_acquire(h, GVOM_PRODUCT_VIEWPOINTS, bytes, bytes, "gvom_score_viewpoints", &h->vp_allocs, &set);
-    if (rc) return rc;
+    if ((rc = product_acquire(h, GVOM_PRODUCT_VIEWPOINTS, bytes, bytes, fn, &h->vp_allocs, &set))) return rc;
     set->cap = K;
-    const size_t bm_words = (((size_t)V + 31) / 32 + 63) & ~(size_t)63, bm_bytes = bm_words * 4;       // whole 256-byte lines
-    int64_t batch = (int64_t)(((size_t)h->tune_vp_mb << 20) / bm_bytes);
-    batch = std::max<int64_t>(1, std::min<int64_t>(batch, std::min<int64_t>(K, GVOM_VIEWPOINT_MAX_BATCH)));
-    if ((rc = stage_buf(h, h->vp_bitmaps, (size_t)batch * bm_bytes, h->vp_allocs))) return rc;
+    size_t bm_words;
+    const int64_t batch = views_batch(h, V, K, &bm_words);
+    if ((rc = stage_buf(h, h->vp_bitmaps, (size_t)batch * bm_words * 4, h->vp_allocs))) return rc;
     const Fused &F = h->fused[h->cur];
     ScanParams P;
     RayQuery R;
     memset(&R, 0, sizeof R);
     raycast_params(h, F, P, R);
     ViewQuery Q;
-    memset(&Q, 0, sizeof Q);
+    views_fill(h, R, B, K, max_range, stride_h, stride_w, flags, bm_words, Q);
     Q.poses = poses;
-    Q.dir = (const double *)h->ri_model.p; Q.off = Q.dir + (size_t)h->ri_H * h->ri_W * 3;
-    Q.max_range = max_range;
-    Q.W = h->ri_W; Q.stride_h = stride_h; Q.stride_w = stride_w;
-    Q.nh = (int)nh; Q.nw = (int)nw; Q.nwc = (int)((nw + 63) / 64); Q.nb = (int)nb; Q.K = (int)K;
-    Q.unknown_blocks = (flags & GVOM_RAY_UNKNOWN_BLOCKS) ? 1 : 0;
-    Q.lit = R.lit; Q.cap = R.cap; Q.bm_words = (uint32_t)bm_words;
     HIPCHK(h, join_second_stream(h));
     if (!on_device) {                                                       // host poses: staged, and up before the call returns
         const HostPart part = {poses, (size_t)K * 96};
@@ -955,15 +1022,10 @@ VIS int gvom_score_viewpoints(gvom_t *h, const double *poses, int64_t K, int on_
     }
     if ((rc = set_wait_releases(h, set))) return rc;
     int32_t *rows = part_ptr<int32_t>(set, 0);
-    HIPCHK(h, hipMemsetAsync(rows, 0, (size_t)K * 32, h->stream));
-    for (int64_t k0 = 0; k0 < K; k0 += batch) {
-        const int nk = (int)std::min<int64_t>(batch, K - k0);
-        Q.k0 = (int)k0;
-        HIPCHK(h, hipMemsetAsync(h->vp_bitmaps.p, 0, (size_t)nk * bm_bytes, h->stream));
-        HIPCHK(h, gvom_launch_viewpoints(h->stream, P, Q, nk, F.state, F.tags, (uint32_t *)h->vp_bitmaps.p, rows));
-    }
-    Q.k0 = 0;
-    HIPCHK(h, gvom_launch_viewpoint_best(h->stream, P, Q, F.state, F.tags, rows, part_ptr<int32_t>(set, 1)));
+    rc = views_run(h, h->vp_bitmaps, Q, batch, rows,
+                   [&](int nk) { return gvom_launch_viewpoints(h->stream, P, Q, nk, F.state, F.tags, (uint32_t *)h->vp_bitmaps.p, rows); },
+                   [&]() { return gvom_launch_viewpoint_best(h->stream, P, Q, F.state, F.tags, rows, part_ptr<int32_t>(set, 1)); });
+    if (rc) return rc;
     h->vp_last_batch = (int)batch;
     if ((rc = product_publish(h, set, product_id))) return rc;
     for (int k = 0; origin_voxels && k < 3; ++k) origin_voxels[k] = (double)F.origin[k];

@@ -91,14 +91,11 @@ __global__ __launch_bounds__(RQ_BLOCK) void k_raycast(const ScanParams P, const 
     if (run) {                                            // S unstopped steps
         r_status = RQ_CLEAR; r_steps = (int32_t)S;
         if (Q.check_target) {                             // the end point's own voxel (gvom.py:1072-1080), literal form
-            const double fx = floor(div_by_res<float>(bx, P.xy_res, P.drcp[0], P.fastdiv & 1) - P.origin[0]);
-            const double fy = floor(div_by_res<float>(by, P.xy_res, P.drcp[0], P.fastdiv & 1) - P.origin[1]);
-            const double fz = floor(div_by_res<float>(bz, P.z_res, P.drcp[1], P.fastdiv & 2) - P.origin[2]);
-            const bool in = fx >= 0.0 && fx < (double)P.xy && fy >= 0.0 && fy < (double)P.xy && fz >= 0.0 && fz < (double)P.zs;
+            uint32_t wx, wy, wz;
+            const bool in = rq_point_voxel(P, bx, by, bz, wx, wy, wz);
             uint32_t L, T;
             int32_t vox;
-            rq_index<P2>(in, in ? (uint32_t)(int)fx : 0u, in ? (uint32_t)(int)fy : 0u, in ? (uint32_t)(int)fz : 0u, (uint32_t)P.xy,
-                         (uint32_t)P.zs, (uint32_t)P.nseg, (uint32_t)P.om[0], (uint32_t)P.om[1], (uint32_t)P.om[2], L, T, vox);
+            rq_index<P2>(in, wx, wy, wz, (uint32_t)P.xy, (uint32_t)P.zs, (uint32_t)P.nseg, (uint32_t)P.om[0], (uint32_t)P.om[1], (uint32_t)P.om[2], L, T, vox);
             const uint32_t tg = ftags[T];
             const int32_t sv = fstate[L];
             const int32_t s = tg == P.epoch ? sv : -1;

@@ -16,16 +16,6 @@
 #define VP_BLOCK 256
 #define VP_WAVES (VP_BLOCK / WAVE)
 
-// the pose of viewpoint k: rows 0..2 of the 4x4, wave-uniform; false where an entry is not finite
-__device__ __forceinline__ bool vp_pose(const double *__restrict__ poses, uint32_t k, double (&c)[12])
-{
-    const double *p = poses + (size_t)k * 12;
-    bool fin = true;
-#pragma unroll
-    for (int e = 0; e < 12; ++e) { c[e] = p[e]; fin = fin && fabs(c[e]) < INFINITY; }
-    return fin;
-}
-
 // A wave is 64 consecutive selected columns of one selected row of the model: its beams point almost the same way, share cache
 // lines of the map and words of the bitmap, and finish together.  The step body is k_raycast's: a round computes RQ_DEPTH positions,
 // issues their tile-tag and state loads together and examines them in step order.  Per wave: ballots and population counts of the
@@ -42,7 +32,7 @@ __global__ __launch_bounds__(VP_BLOCK) void k_viewpoints(const ScanParams P, con
     if (hi >= Q.nh) return;                               // (the whole wave: the last workgroup's spare waves)
     const uint32_t k = Q.k0 + blockIdx.y;                 // < K: the grid's y extent is the batch
     double c[12];
-    if (!vp_pose(Q.poses, k, c)) return;                  // an invalid pose: k_viewpoint_best writes its row
+    if (!rq_pose(Q.poses, k, c)) return;                  // an invalid pose: k_viewpoint_best writes its row
     const bool live = wi < Q.nw;
     // the beam's end point (include/gvom_hip.h "viewpoint scoring": k_unproject's arithmetic with r = max_range)
     double d[3] = {0.0, 0.0, 0.0}, o[3] = {0.0, 0.0, 0.0};
@@ -121,21 +111,7 @@ __global__ __launch_bounds__(VP_BLOCK) void k_viewpoints(const ScanParams P, con
         alive = lanes(run && j < S);
     }
     if (run) r_status = RQ_CLEAR;                         // S unstopped steps
-    const int32_t st = live ? r_status : -1;
-    const uint32_t n_occ = (uint32_t)__builtin_popcountll(lanes(st == RQ_OCCUPIED)), n_clr = (uint32_t)__builtin_popcountll(lanes(st == RQ_CLEAR));
-    const uint32_t n_left = (uint32_t)__builtin_popcountll(lanes(st == RQ_LEFT_WINDOW)), n_unk = (uint32_t)__builtin_popcountll(lanes(st == RQ_UNKNOWN));
-    const uint32_t n_inv = (uint32_t)__builtin_popcountll(lanes(st == RQ_INVALID));
-    const uint32_t visits = wave_sum((uint32_t)r_unknown), gain = wave_sum((uint32_t)r_first);
-    if (lane == 0u) {
-        int32_t *row = rows + (size_t)k * 8;
-        if (gain) atomicAdd(row + 1, (int32_t)gain);
-        if (visits) atomicAdd(row + 2, (int32_t)visits);
-        if (n_occ) atomicAdd(row + 3, (int32_t)n_occ);
-        if (n_clr) atomicAdd(row + 4, (int32_t)n_clr);
-        if (n_left) atomicAdd(row + 5, (int32_t)n_left);
-        if (n_unk) atomicAdd(row + 6, (int32_t)n_unk);
-        if (n_inv) atomicAdd(row + 7, (int32_t)n_inv);
-    }
+    rq_census(live ? r_status : -1, r_unknown, r_first, lane, rows + (size_t)k * 8);
 }
 
 // Column 0 of every row: the GVOM_RAY_* code of the viewpoint's own voxel floor((double)a / res - W) (the literal float64 lookup), the
@@ -146,25 +122,20 @@ __global__ __launch_bounds__(VP_BLOCK) void k_viewpoint_best(const ScanParams P,
                                                              const uint32_t *__restrict__ ftags, int32_t *__restrict__ rows,
                                                              int32_t *__restrict__ best)
 {
-    __shared__ unsigned long long s_key[VP_WAVES];
     unsigned long long key = 0ull;
     for (uint32_t k = threadIdx.x; k < (uint32_t)Q.K; k += VP_BLOCK) {
         double c[12];
         int32_t *row = rows + (size_t)k * 8;
-        if (!vp_pose(Q.poses, k, c)) {
+        if (!rq_pose(Q.poses, k, c)) {
             const v4i lo = {RQ_INVALID, 0, 0, 0}, hi = {0, 0, 0, Q.nb};
             *(v4i *)row = lo; *(v4i *)(row + 4) = hi;
             continue;
         }
-        const float ax = (float)c[3], ay = (float)c[7], az = (float)c[11];
-        const double fx = floor(div_by_res<float>(ax, P.xy_res, P.drcp[0], P.fastdiv & 1) - P.origin[0]);
-        const double fy = floor(div_by_res<float>(ay, P.xy_res, P.drcp[0], P.fastdiv & 1) - P.origin[1]);
-        const double fz = floor(div_by_res<float>(az, P.z_res, P.drcp[1], P.fastdiv & 2) - P.origin[2]);
-        const bool in = fx >= 0.0 && fx < (double)P.xy && fy >= 0.0 && fy < (double)P.xy && fz >= 0.0 && fz < (double)P.zs;
+        uint32_t wx, wy, wz;
+        const bool in = rq_point_voxel(P, (float)c[3], (float)c[7], (float)c[11], wx, wy, wz);
         uint32_t L, T;
         int32_t vox;
-        rq_index<P2>(in, in ? (uint32_t)(int)fx : 0u, in ? (uint32_t)(int)fy : 0u, in ? (uint32_t)(int)fz : 0u, (uint32_t)P.xy,
-                     (uint32_t)P.zs, (uint32_t)P.nseg, (uint32_t)P.om[0], (uint32_t)P.om[1], (uint32_t)P.om[2], L, T, vox);
+        rq_index<P2>(in, wx, wy, wz, (uint32_t)P.xy, (uint32_t)P.zs, (uint32_t)P.nseg, (uint32_t)P.om[0], (uint32_t)P.om[1], (uint32_t)P.om[2], L, T, vox);
         const uint32_t tg = ftags[T];
         const int32_t sv = fstate[L];
         const int32_t s = tg == P.epoch ? sv : -1;
@@ -175,19 +146,7 @@ __global__ __launch_bounds__(VP_BLOCK) void k_viewpoint_best(const ScanParams P,
             key = cand > key ? cand : key;
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned long long other = __shfl_xor(key, o);
-        key = other > key ? other : key;
-    }
-    if ((threadIdx.x & 63u) == 0u) s_key[threadIdx.x >> 6] = key;
-    __syncthreads();
-    if (threadIdx.x == 0u) {
-#pragma unroll
-        for (int w = 1; w < VP_WAVES; ++w) key = s_key[w] > key ? s_key[w] : key;
-        const v4i r = {key ? (int32_t)~(uint32_t)key : -1, key ? (int32_t)((uint32_t)(key >> 32) - 1u) : 0, Q.K, Q.nb};
-        *(v4i *)best = r;
-    }
+    rq_best_store<VP_BLOCK>(key, Q, best);
 }
 
 hipError_t gvom_launch_viewpoints(hipStream_t s, const ScanParams &P, const ViewQuery &Q, int batch, const int32_t *fstate, const uint32_t *ftags,

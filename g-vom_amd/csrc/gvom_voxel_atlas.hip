@@ -308,17 +308,6 @@ __device__ __forceinline__ void va_lookup_packed(const ScanParams &P, const VAtl
     }
 }
 
-// the extent voxel of a point given in metres, in the literal float64 form (gvom.py:1072-1080): a ray's end point, a pose's own voxel
-__device__ __forceinline__ bool va_point_voxel(const ScanParams &P, float x, float y, float z, uint32_t &wx, uint32_t &wy, uint32_t &wz)
-{
-    const double fx = floor(div_by_res<float>(x, P.xy_res, P.drcp[0], P.fastdiv & 1) - P.origin[0]);
-    const double fy = floor(div_by_res<float>(y, P.xy_res, P.drcp[0], P.fastdiv & 1) - P.origin[1]);
-    const double fz = floor(div_by_res<float>(z, P.z_res, P.drcp[1], P.fastdiv & 2) - P.origin[2]);
-    const bool in = fx >= 0.0 && fx < (double)P.xy && fy >= 0.0 && fy < (double)P.xy && fz >= 0.0 && fz < (double)P.zs;
-    wx = in ? (uint32_t)(int)fx : 0u; wy = in ? (uint32_t)(int)fy : 0u; wz = in ? (uint32_t)(int)fz : 0u;
-    return in;
-}
-
 __device__ __forceinline__ v2ull va_load(const VAtlas &V, const ScanParams &P, uint32_t wx, uint32_t wy, uint32_t wz, uint32_t &bit)
 {
     const uint32_t uA = (uint32_t)V.A, uZ = (uint32_t)V.Z;
@@ -409,7 +398,7 @@ __global__ __launch_bounds__(VA_BLOCK) void k_vatlas_raycast(const ScanParams P,
         r_status = RQ_CLEAR; r_steps = (int32_t)S;
         if (Q.check_target) {                             // the end point's own voxel (gvom.py:1072-1080), literal form
             uint32_t wx, wy, wz, bit;
-            const bool in = va_point_voxel(P, bx, by, bz, wx, wy, wz);
+            const bool in = rq_point_voxel(P, bx, by, bz, wx, wy, wz);
             const v2ull w = va_load(V, P, wx, wy, wz, bit);                                // (voxel 0 of the extent where outside: ignored)
             const bool occ = in && ((w.y >> bit) & 1ull) != 0ull;
             const bool unk = in && ((w.x >> bit) & 1ull) == 0ull;
@@ -436,16 +425,6 @@ __global__ __launch_bounds__(VA_BLOCK) void k_vatlas_raycast(const ScanParams P,
 }
 
 // ---- viewpoints ---------------------------------------------------------------------------------------------------------------------------
-// the pose of viewpoint k: rows 0..2 of the 4x4, wave-uniform; false where an entry is not finite (as gvom_viewpoint.hip's)
-__device__ __forceinline__ bool va_pose(const double *__restrict__ poses, uint32_t k, double (&c)[12])
-{
-    const double *p = poses + (size_t)k * 12;
-    bool fin = true;
-#pragma unroll
-    for (int e = 0; e < 12; ++e) { c[e] = p[e]; fin = fin && fabs(c[e]) < INFINITY; }
-    return fin;
-}
-
 // k_viewpoints' body (gvom_viewpoint.hip) with the atlas lookup.  boxes [K][8] int32 = {lx, ly, lz, dx, dy, dz, 0, 0}: the box of extent
 // voxels of pose k, inside the extent, dx * dy * dz <= 32 * Q.bm_words; bit ((wz - lz) * dy + (wy - ly)) * dx + (wx - lx) of the pose's
 // bitmap stands for extent voxel (wx, wy, wz).  The host proves that every voxel a beam of the pose examines lies in the box; a voxel
@@ -459,7 +438,7 @@ __global__ __launch_bounds__(VA_BLOCK) void k_vatlas_viewpoints(const ScanParams
     if (hi >= Q.nh) return;                               // (the whole wave: the last workgroup's spare waves)
     const uint32_t k = Q.k0 + blockIdx.y;                 // < K: the grid's y extent is the batch
     double c[12];
-    if (!va_pose(Q.poses, k, c)) return;                  // an invalid pose: k_vatlas_viewpoint_best writes its row
+    if (!rq_pose(Q.poses, k, c)) return;                  // an invalid pose: k_vatlas_viewpoint_best writes its row
     const bool live = wi < Q.nw;
     // the beam's end point (include/gvom_hip.h "viewpoint scoring": k_unproject's arithmetic with r = max_range)
     double d[3] = {0.0, 0.0, 0.0}, o[3] = {0.0, 0.0, 0.0};
@@ -543,21 +522,7 @@ __global__ __launch_bounds__(VA_BLOCK) void k_vatlas_viewpoints(const ScanParams
         alive = lanes(run && j < S);
     }
     if (run) r_status = RQ_CLEAR;                         // S unstopped steps
-    const int32_t st = live ? r_status : -1;
-    const uint32_t n_occ = (uint32_t)__builtin_popcountll(lanes(st == RQ_OCCUPIED)), n_clr = (uint32_t)__builtin_popcountll(lanes(st == RQ_CLEAR));
-    const uint32_t n_left = (uint32_t)__builtin_popcountll(lanes(st == RQ_LEFT_WINDOW)), n_unk = (uint32_t)__builtin_popcountll(lanes(st == RQ_UNKNOWN));
-    const uint32_t n_inv = (uint32_t)__builtin_popcountll(lanes(st == RQ_INVALID));
-    const uint32_t visits = wave_sum((uint32_t)r_unknown), gain = wave_sum((uint32_t)r_first);
-    if (lane == 0u) {
-        int32_t *row = rows + (size_t)k * 8;
-        if (gain) atomicAdd(row + 1, (int32_t)gain);
-        if (visits) atomicAdd(row + 2, (int32_t)visits);
-        if (n_occ) atomicAdd(row + 3, (int32_t)n_occ);
-        if (n_clr) atomicAdd(row + 4, (int32_t)n_clr);
-        if (n_left) atomicAdd(row + 5, (int32_t)n_left);
-        if (n_unk) atomicAdd(row + 6, (int32_t)n_unk);
-        if (n_inv) atomicAdd(row + 7, (int32_t)n_inv);
-    }
+    rq_census(live ? r_status : -1, r_unknown, r_first, lane, rows + (size_t)k * 8);
 }
 
 // k_viewpoint_best (gvom_viewpoint.hip) with the class of the pose's own voxel read from the atlas: column 0 of every row, the whole row
@@ -565,18 +530,17 @@ __global__ __launch_bounds__(VA_BLOCK) void k_vatlas_viewpoints(const ScanParams
 __global__ __launch_bounds__(VA_BLOCK) void k_vatlas_viewpoint_best(const ScanParams P, const ViewQuery Q, const VAtlas V, int32_t *__restrict__ rows,
                                                                     int32_t *__restrict__ best)
 {
-    __shared__ unsigned long long s_key[VA_WAVES];
     unsigned long long key = 0ull;
     for (uint32_t k = threadIdx.x; k < (uint32_t)Q.K; k += VA_BLOCK) {
         double c[12];
         int32_t *row = rows + (size_t)k * 8;
-        if (!va_pose(Q.poses, k, c)) {
+        if (!rq_pose(Q.poses, k, c)) {
             const v4i lo = {RQ_INVALID, 0, 0, 0}, hi = {0, 0, 0, Q.nb};
             *(v4i *)row = lo; *(v4i *)(row + 4) = hi;
             continue;
         }
         uint32_t wx, wy, wz, bit;
-        const bool in = va_point_voxel(P, (float)c[3], (float)c[7], (float)c[11], wx, wy, wz);
+        const bool in = rq_point_voxel(P, (float)c[3], (float)c[7], (float)c[11], wx, wy, wz);
         const v2ull w = va_load(V, P, wx, wy, wz, bit);
         const bool occ = ((w.y >> bit) & 1ull) != 0ull, obs = ((w.x >> bit) & 1ull) != 0ull;
         const int32_t status = !in ? RQ_LEFT_WINDOW : (occ ? RQ_OCCUPIED : (!obs ? RQ_UNKNOWN : RQ_CLEAR));
@@ -586,19 +550,7 @@ __global__ __launch_bounds__(VA_BLOCK) void k_vatlas_viewpoint_best(const ScanPa
             key = cand > key ? cand : key;
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned long long other = __shfl_xor(key, o);
-        key = other > key ? other : key;
-    }
-    if ((threadIdx.x & 63u) == 0u) s_key[threadIdx.x >> 6] = key;
-    __syncthreads();
-    if (threadIdx.x == 0u) {
-#pragma unroll
-        for (int w = 1; w < VA_WAVES; ++w) key = s_key[w] > key ? s_key[w] : key;
-        const v4i r = {key ? (int32_t)~(uint32_t)key : -1, key ? (int32_t)((uint32_t)(key >> 32) - 1u) : 0, Q.K, Q.nb};
-        *(v4i *)best = r;
-    }
+    rq_best_store<VA_BLOCK>(key, Q, best);
 }
 
 // ---- launchers ----------------------------------------------------------------------------------------------------------------------------

@@ -3,7 +3,9 @@
 // an integrate behind whatever produced the current fused map, a query behind the integrates before it -- and only gvom_voxel_atlas_counts
 // waits for it (the viewpoint call waits where it has to read poses or the sensor model back: the boxes of its bitmaps are proved here, on
 // the host).  The products go through the pool path of every product call (product_acquire / product_publish, gvom_sets.hip), host inputs
-// through stage_host, the checks through refuse (gvom_host.h).
+// through stage_host, the checks through refuse (gvom_host.h).  The three walk queries share their checks, the filling of their queries,
+// the staging and the viewpoint batch loop with gvom_raycast, gvom_score_viewpoints and gvom_score_alignments ("THE WALK QUERIES",
+// gvom_host.h); theirs alone are the frame (walk_frame), the boxes of the poses, the box origin and the launches.
 #include "gvom_host.h"
 
 namespace {
@@ -46,6 +48,17 @@ void clip(int r, int len, int size, int *lo, int *n)
     *n = b > a ? (int)(b - a) : 0;
 }
 
+// the window-sized box at world voxel B against the extent: per axis its relative origin and the part [lo, lo + n) inside the extent.
+// Returns how many of its voxels lie inside
+int64_t box_clip(const gvom_handle *h, const int64_t B[3], int r[3], int lo[3], int n[3])
+{
+    for (int k = 0; k < 3; ++k) {
+        r[k] = rel_of(h, B, k);
+        clip(r[k], window_side(h, k), side(h, k), &lo[k], &n[k]);
+    }
+    return (int64_t)n[0] * n[1] * n[2];
+}
+
 // the window-sized box at world voxel B as the box kernels take it: relative to the extent, with its storage phase.  Returns how many of
 // its voxels lie inside the extent
 int64_t box_frame(const gvom_handle *h, const int64_t B[3], VAtlasBox &X)
@@ -53,13 +66,30 @@ int64_t box_frame(const gvom_handle *h, const int64_t B[3], VAtlasBox &X)
     memset(&X, 0, sizeof X);
     X.n = h->prm.xy_size; X.zs = h->prm.z_size;
     int r[3], lo[3], n[3];
-    for (int k = 0; k < 3; ++k) {
-        r[k] = rel_of(h, B, k);
-        clip(r[k], window_side(h, k), side(h, k), &lo[k], &n[k]);
-    }
+    const int64_t inside = box_clip(h, B, r, lo, n);
     X.rx = r[0]; X.ry = r[1]; X.rz = r[2];
     X.px = (int)(B[0] & (h->va_A - 1)); X.py = (int)(B[1] & (h->va_A - 1)); X.pz = (int)(B[2] & (h->va_Z - 1));
-    return (int64_t)n[0] * n[1] * n[2];
+    return inside;
+}
+
+// THE BOX ORIGIN of the calls that take one: `origin`, or (NULL) the last integrated window; GVOM_NO_DATA before the first combine, and
+// for NULL before the first integrate
+int box_origin(const gvom_handle *h, const int64_t origin[3], int64_t B[3])
+{
+    if (!h->has_combined || (!origin && h->va_seq == 0)) return GVOM_NO_DATA;
+    for (int k = 0; k < 3; ++k) B[k] = origin ? origin[k] : h->va_last[k];
+    return GVOM_OK;
+}
+
+// the end of a call whose product lies at world voxel `at`: recorded in the set, handed to the caller, published.  The box calls hand
+// it out in front of the publication, the two extent calls (`after`) only behind a publication that succeeded: as each always did
+int publish_at(gvom_handle *h, DevSet *set, const int64_t at[3], int64_t out[3], int64_t *product_id, bool after = false)
+{
+    for (int k = 0; k < 3; ++k) set->origin[k] = at[k];
+    for (int k = 0; !after && out && k < 3; ++k) out[k] = at[k];
+    if (const int rc = product_publish(h, set, product_id)) return rc;
+    for (int k = 0; after && out && k < 3; ++k) out[k] = at[k];
+    return GVOM_OK;
 }
 
 // the CURRENT fused map -- the map of the most recently begun combine -- as gvom_voxel_atlas_integrate and gvom_voxel_atlas_changes take
@@ -273,11 +303,7 @@ VIS int gvom_voxel_atlas_integrate(gvom_t *h)
     VAtlasWindow D;
     memset(&D, 0, sizeof D);
     int r[3], lo[3], n[3];
-    for (int k = 0; k < 3; ++k) {
-        r[k] = rel_of(h, F.origin, k);
-        clip(r[k], window_side(h, k), side(h, k), &lo[k], &n[k]);
-    }
-    const int64_t inside = (int64_t)n[0] * n[1] * n[2];
+    const int64_t inside = box_clip(h, F.origin, r, lo, n);
     D.rx = r[0]; D.ry = r[1]; D.rz = r[2];
     D.pex = (int)(h->va_E[0] & (V.A - 1)); D.pey = (int)(h->va_E[1] & (V.A - 1)); D.pez = (int)(h->va_E[2] & (V.Z - 1));
     if (inside > 0) {
@@ -323,8 +349,8 @@ VIS int gvom_voxel_atlas_box(gvom_t *h, const int64_t origin[3], int64_t *produc
     const char *const fn = "gvom_voxel_atlas_box";
     int rc = need_atlas(h, fn);
     if (rc) return rc;
-    if (!h->has_combined || (!origin && h->va_seq == 0)) return GVOM_NO_DATA;     // (NULL: the last integrated window, and there is none yet)
-    const int64_t B[3] = {origin ? origin[0] : h->va_last[0], origin ? origin[1] : h->va_last[1], origin ? origin[2] : h->va_last[2]};
+    int64_t B[3];
+    if ((rc = box_origin(h, origin, B))) return rc;
     const int xy = h->prm.xy_size, zs = h->prm.z_size;
     HIPCHK(h, hipSetDevice(h->device));
     DevSet *set = nullptr;
@@ -338,9 +364,7 @@ VIS int gvom_voxel_atlas_box(gvom_t *h, const int64_t origin[3], int64_t *produc
     int32_t *counts = part_ptr<int32_t>(set, 1);
     HIPCHK(h, hipMemsetAsync(counts, 0, 16, h->stream));
     HIPCHK(h, gvom_launch_vatlas_box(h->stream, atlas_of(h), X, part_ptr<uint8_t>(set, 0), counts));
-    for (int k = 0; k < 3; ++k) set->origin[k] = B[k];
-    for (int k = 0; origin_out && k < 3; ++k) origin_out[k] = B[k];
-    return product_publish(h, set, product_id);
+    return publish_at(h, set, B, origin_out, product_id);
 }
 
 // What the CURRENT fused map contradicts of what the atlas remembers (include/gvom_hip.h "voxel atlas changes"), read-only on both:
@@ -412,11 +436,7 @@ VIS int gvom_voxel_atlas_raycast(gvom_t *h, const float *from, int64_t K, const 
     const char *const fn = "gvom_voxel_atlas_raycast";
     int rc = need_atlas(h, fn);
     if (rc) return rc;
-    if (!from || !to) return refuse(h, fn, "from and to must not be NULL");
-    if (n < 1) return refuse(h, fn, "n must be at least 1");
-    if (K != 1 && K != n) return refuse(h, fn, "K must be 1 or n");
-    if (flags & ~(GVOM_RAY_UNKNOWN_BLOCKS | GVOM_RAY_CHECK_TARGET)) return refuse(h, fn, "unknown flag bits");
-    if (n > GVOM_RAYCAST_MAX_RAYS) return refuse(h, fn, "more than 2^26 rays in one call", GVOM_ERR_CAPACITY);
+    if ((rc = check_rays(h, fn, from, K, to, n, flags))) return rc;
     if (!h->has_combined) return GVOM_NO_DATA;
     HIPCHK(h, hipSetDevice(h->device));
     DevSet *set = nullptr;
@@ -426,23 +446,10 @@ VIS int gvom_voxel_atlas_raycast(gvom_t *h, const float *from, int64_t K, const 
     ScanParams P;
     RayQuery Q;
     walk_frame(h, P, Q);
-    Q.from = from; Q.to = to; Q.n = (long)n;
-    Q.one_origin = K == 1 ? 1 : 0;
-    Q.unknown_blocks = (flags & GVOM_RAY_UNKNOWN_BLOCKS) ? 1 : 0;
-    Q.check_target = (flags & GVOM_RAY_CHECK_TARGET) ? 1 : 0;
-    HIPCHK(h, join_second_stream(h));
-    if (!on_device) {                                                       // host segments: staged, and up before the call returns
-        const HostPart parts[2] = {{from, (size_t)K * 12}, {to, (size_t)n * 12}};
-        const void *dev[2];
-        if ((rc = stage_host(h, h->va_stage, h->va_allocs, parts, 2, true, dev))) return rc;
-        Q.from = (const float *)dev[0]; Q.to = (const float *)dev[1];
-    }
+    if ((rc = rays_fill(h, h->va_stage, h->va_allocs, from, K, to, n, on_device, flags, Q))) return rc;
     if ((rc = set_wait_releases(h, set))) return rc;
     HIPCHK(h, gvom_launch_vatlas_raycast(h->stream, P, Q, atlas_of(h), part_ptr<int32_t>(set, 0), part_ptr<float>(set, 1), part_ptr<int32_t>(set, 2)));
-    for (int k = 0; k < 3; ++k) set->origin[k] = h->va_E[k];
-    if ((rc = product_publish(h, set, product_id))) return rc;
-    for (int k = 0; extent_voxels && k < 3; ++k) extent_voxels[k] = h->va_E[k];
-    return GVOM_OK;
+    return publish_at(h, set, h->va_E, extent_voxels, product_id, true);
 }
 
 // gvom_score_viewpoints on the atlas: the selected beams of the handle's sensor model cast from K poses by k_vatlas_viewpoints, a batch of
@@ -458,17 +465,8 @@ VIS int gvom_voxel_atlas_score_viewpoints(gvom_t *h, const double *poses, int64_
     const char *const fn = "gvom_voxel_atlas_score_viewpoints";
     int rc = need_atlas(h, fn);
     if (rc) return rc;
-    if (!poses) return refuse(h, fn, "poses must not be NULL");
-    if (h->ri_H <= 0) return refuse(h, fn, "no sensor model (gvom_sensor_model_set)");
-    if (K < 1) return refuse(h, fn, "K must be at least 1");
-    if (stride_h < 1 || stride_w < 1) return refuse(h, fn, "the beam strides must be at least 1");
-    if (!std::isfinite(max_range) || !(max_range > 0.0)) return refuse(h, fn, "max_range must be finite and > 0");
-    if (flags & ~GVOM_RAY_UNKNOWN_BLOCKS) return refuse(h, fn, "unknown flag bits");
-    if (K > GVOM_VIEWPOINT_MAX_POSES) return refuse(h, fn, "more than 65536 viewpoints in one call", GVOM_ERR_CAPACITY);
-    const int A = h->va_A, Z = h->va_Z;
-    const int64_t nh = ((int64_t)h->ri_H + stride_h - 1) / stride_h, nw = ((int64_t)h->ri_W + stride_w - 1) / stride_w, nb = nh * nw;
-    if (nb > GVOM_VIEWPOINT_MAX_BEAMS) return refuse(h, fn, "more than 2^22 selected beams", GVOM_ERR_CAPACITY);
-    if (nb * ((int64_t)A + Z + 1) >= ((int64_t)1 << 31)) return refuse(h, fn, "beams x (cells + levels + 1) reaches 2^31", GVOM_ERR_CAPACITY);
+    ViewBeams beams;
+    if ((rc = check_views(h, fn, poses, K, max_range, stride_h, stride_w, flags, (int64_t)h->va_A + h->va_Z, "cells + levels", &beams))) return rc;
     if (!h->has_combined) return GVOM_NO_DATA;
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, join_second_stream(h));
@@ -492,21 +490,14 @@ VIS int gvom_voxel_atlas_score_viewpoints(gvom_t *h, const double *poses, int64_
     const size_t bytes = set_bytes(GVOM_PRODUCT_VOXEL_ATLAS_VIEWPOINTS, 0, 0, K);
     if ((rc = product_acquire(h, GVOM_PRODUCT_VOXEL_ATLAS_VIEWPOINTS, bytes, bytes, fn, &h->va_allocs, &set))) return rc;
     set->cap = K;
-    const size_t bm_words = (((size_t)most + 31) / 32 + 63) & ~(size_t)63, bm_bytes = bm_words * 4;       // whole 256-byte lines
-    int64_t batch = (int64_t)(((size_t)h->tune_vp_mb << 20) / bm_bytes);
-    batch = std::max<int64_t>(1, std::min<int64_t>(batch, std::min<int64_t>(K, GVOM_VIEWPOINT_MAX_BATCH)));
-    if ((rc = stage_buf(h, h->va_bitmaps, (size_t)batch * bm_bytes, h->va_allocs))) return rc;
+    size_t bm_words;                                                        // every bitmap as large as the largest box of the call
+    const int64_t batch = views_batch(h, most, K, &bm_words);
+    if ((rc = stage_buf(h, h->va_bitmaps, (size_t)batch * bm_words * 4, h->va_allocs))) return rc;
     ScanParams P;
     RayQuery R;
     walk_frame(h, P, R);
     ViewQuery Q;
-    memset(&Q, 0, sizeof Q);
-    Q.dir = (const double *)h->ri_model.p; Q.off = Q.dir + (size_t)h->ri_H * h->ri_W * 3;
-    Q.max_range = max_range;
-    Q.W = h->ri_W; Q.stride_h = stride_h; Q.stride_w = stride_w;
-    Q.nh = (int)nh; Q.nw = (int)nw; Q.nwc = (int)((nw + 63) / 64); Q.nb = (int)nb; Q.K = (int)K;
-    Q.unknown_blocks = (flags & GVOM_RAY_UNKNOWN_BLOCKS) ? 1 : 0;
-    Q.lit = R.lit; Q.cap = R.cap; Q.bm_words = (uint32_t)bm_words;
+    views_fill(h, R, beams, K, max_range, stride_h, stride_w, flags, bm_words, Q);
     const HostPart parts[2] = {{on_device ? nullptr : poses, (size_t)K * 96}, {boxes.data(), (size_t)K * 32}};
     const void *dev[2];
     if ((rc = stage_host(h, h->va_stage, h->va_allocs, parts, 2, true, dev))) return rc;
@@ -515,20 +506,12 @@ VIS int gvom_voxel_atlas_score_viewpoints(gvom_t *h, const double *poses, int64_
     if ((rc = set_wait_releases(h, set))) return rc;
     const VAtlas V = atlas_of(h);
     int32_t *rows = part_ptr<int32_t>(set, 0);
-    HIPCHK(h, hipMemsetAsync(rows, 0, (size_t)K * 32, h->stream));
-    for (int64_t k0 = 0; k0 < K; k0 += batch) {
-        const int nk = (int)std::min<int64_t>(batch, K - k0);
-        Q.k0 = (int)k0;
-        HIPCHK(h, hipMemsetAsync(h->va_bitmaps.p, 0, (size_t)nk * bm_bytes, h->stream));
-        HIPCHK(h, gvom_launch_vatlas_viewpoints(h->stream, P, Q, V, nk, dboxes, (uint32_t *)h->va_bitmaps.p, rows));
-    }
-    Q.k0 = 0;
-    HIPCHK(h, gvom_launch_vatlas_viewpoint_best(h->stream, P, Q, V, rows, part_ptr<int32_t>(set, 1)));
+    rc = views_run(h, h->va_bitmaps, Q, batch, rows,
+                   [&](int nk) { return gvom_launch_vatlas_viewpoints(h->stream, P, Q, V, nk, dboxes, (uint32_t *)h->va_bitmaps.p, rows); },
+                   [&]() { return gvom_launch_vatlas_viewpoint_best(h->stream, P, Q, V, rows, part_ptr<int32_t>(set, 1)); });
+    if (rc) return rc;
     h->va_last_batch = (int)batch;
-    for (int k = 0; k < 3; ++k) set->origin[k] = h->va_E[k];
-    if ((rc = product_publish(h, set, product_id))) return rc;
-    for (int k = 0; extent_voxels && k < 3; ++k) extent_voxels[k] = h->va_E[k];
-    return GVOM_OK;
+    return publish_at(h, set, h->va_E, extent_voxels, product_id, true);
 }
 
 // gvom_score_alignments on the atlas: k_vatlas_align_field turns the box at B into the class grid -- in the handle's class-grid buffer,
@@ -544,20 +527,10 @@ VIS int gvom_voxel_atlas_score_alignments(gvom_t *h, const float *cloud, int64_t
     const char *const fn = "gvom_voxel_atlas_score_alignments";
     int rc = need_atlas(h, fn);
     if (rc) return rc;
-    if (!cloud || !transforms || !weights) return refuse(h, fn, "cloud, transforms and weights must not be NULL");
-    if (n < 1) return refuse(h, fn, "n must be at least 1");
-    if (K < 1) return refuse(h, fn, "K must be at least 1");
-    if (dilate != 0 && dilate != 1) return refuse(h, fn, "dilate must be 0 or 1");
-    for (int c = 0; c < 5; ++c)
-        if (weights[c] < -GVOM_ALIGN_MAX_WEIGHT || weights[c] > GVOM_ALIGN_MAX_WEIGHT) return refuse(h, fn, "a weight outside -1024 .. 1024");
-    if (n > GVOM_ALIGN_MAX_POINTS) return refuse(h, fn, "more than 2^20 returns in one call", GVOM_ERR_CAPACITY);
-    if (K > GVOM_ALIGN_MAX_CANDIDATES) return refuse(h, fn, "more than 65536 candidates in one call", GVOM_ERR_CAPACITY);
-    if (n * K > GVOM_ALIGN_MAX_PAIRS) return refuse(h, fn, "more than 2^32 pairs in one call", GVOM_ERR_CAPACITY);
-    const int xy = h->prm.xy_size, zs = h->prm.z_size;
-    const size_t gb = gvom_align_grid_bytes(xy, zs);
-    if (gb / 4 > 0xffffffffull) return refuse(h, fn, "the class grid of this map has 2^32 words or more", GVOM_ERR_CAPACITY);
-    if (!h->has_combined || (!origin && h->va_seq == 0)) return GVOM_NO_DATA;     // (NULL: the last integrated window, and there is none yet)
-    const int64_t B[3] = {origin ? origin[0] : h->va_last[0], origin ? origin[1] : h->va_last[1], origin ? origin[2] : h->va_last[2]};
+    size_t gb;
+    if ((rc = check_align(h, fn, cloud, n, transforms, K, dilate, weights, &gb))) return rc;
+    int64_t B[3];
+    if ((rc = box_origin(h, origin, B))) return rc;
     HIPCHK(h, hipSetDevice(h->device));
     DevSet *set = nullptr;
     const size_t bytes = set_bytes(GVOM_PRODUCT_VOXEL_ATLAS_ALIGNMENT, 0, 0, K);
@@ -568,26 +541,16 @@ VIS int gvom_voxel_atlas_score_alignments(gvom_t *h, const float *cloud, int64_t
     memset(&P, 0, sizeof P);
     metric_frame(h, h->fused[h->cur], P);
     for (int k = 0; k < 3; ++k) P.origin[k] = (double)B[k];
-    P.n = (long)n; P.K = (int)K; P.xy = xy; P.zs = zs; P.rw = (xy + 15) / 16; P.dilate = dilate;
-    for (int c = 0; c < 5; ++c) P.w[c] = weights[c];
-    const float *cdev = cloud;
-    const double *tdev = transforms;
-    HIPCHK(h, join_second_stream(h));
-    if (!on_device) {                                                       // host inputs: staged, and up before the call returns
-        const HostPart parts[2] = {{transforms, (size_t)K * 96}, {cloud, (size_t)n * 12}};
-        const void *dev[2];
-        if ((rc = stage_host(h, h->va_stage, h->va_allocs, parts, 2, true, dev))) return rc;
-        tdev = (const double *)dev[0]; cdev = (const float *)dev[1];
-    }
+    const float *cdev;
+    const double *tdev;
+    if ((rc = align_fill(h, h->va_stage, h->va_allocs, cloud, n, transforms, K, on_device, dilate, weights, P, &cdev, &tdev))) return rc;
     if ((rc = set_wait_releases(h, set))) return rc;
     VAtlasBox X;
     box_frame(h, B, X);
     uint32_t *const grid = (uint32_t *)h->al_grid.p;
     HIPCHK(h, gvom_launch_vatlas_align_field(h->stream, atlas_of(h), X, dilate, grid));
     HIPCHK(h, gvom_launch_align_grid(h->stream, P, cdev, tdev, grid, part_ptr<int32_t>(set, 0), part_ptr<int32_t>(set, 1)));
-    for (int k = 0; k < 3; ++k) set->origin[k] = B[k];
-    for (int k = 0; origin_out && k < 3; ++k) origin_out[k] = B[k];
-    return product_publish(h, set, product_id);
+    return publish_at(h, set, B, origin_out, product_id);
 }
 
 // The distance field of the box at B (include/gvom_hip.h "voxel distance field"): the three passes of gvom_voxel_distance.hip on the
@@ -605,8 +568,8 @@ VIS int gvom_voxel_atlas_distance_field(gvom_t *h, const int64_t origin[3], doub
     if (rc) return rc;
     if (!std::isfinite(max_distance) || !(max_distance > 0.0)) return refuse(h, fn, "max_distance must be finite and > 0");
     if (flags & ~GVOM_DISTANCE_UNKNOWN_BLOCKS) return refuse(h, fn, "unknown flag bits");
-    if (!h->has_combined || (!origin && h->va_seq == 0)) return GVOM_NO_DATA;     // (NULL: the last integrated window, and there is none yet)
-    const int64_t B[3] = {origin ? origin[0] : h->va_last[0], origin ? origin[1] : h->va_last[1], origin ? origin[2] : h->va_last[2]};
+    int64_t B[3];
+    if ((rc = box_origin(h, origin, B))) return rc;
     const int xy = h->prm.xy_size, zs = h->prm.z_size;
     VDistFrame F;
     memset(&F, 0, sizeof F);
@@ -643,9 +606,7 @@ VIS int gvom_voxel_atlas_distance_field(gvom_t *h, const int64_t origin[3], doub
     HIPCHK(h, hipMemsetAsync(counts, 0, 16, h->stream));
     HIPCHK(h, gvom_launch_vdist_field(h->stream, atlas_of(h), F, h->va_dist.p, part_ptr<float>(set, 0), counts));
     h->vd_halo[0] = (int)hxy; h->vd_halo[1] = (int)hz;
-    for (int k = 0; k < 3; ++k) set->origin[k] = B[k];
-    for (int k = 0; origin_out && k < 3; ++k) origin_out[k] = B[k];
-    return product_publish(h, set, product_id);
+    return publish_at(h, set, B, origin_out, product_id);
 }
 
 // The field of a live distance product gathered at n world points by k_vdist_sample, on the handle's stream: behind the passes that

@@ -1804,6 +1804,36 @@ def _align_options(dilate, weights):
     return int(dilate), (ctypes.c_int32 * 5)(*[int(v) for v in w])
 
 
+def _align_cloud(cloud):
+    """cloud float32 (n, 3) -> C-contiguous; other dtypes raise TypeError, nothing is cast"""
+    c = np.asarray(cloud)
+    if c.dtype != np.float32:
+        raise TypeError("cloud must be float32, got %s" % c.dtype)
+    if c.ndim != 2 or c.shape[1] != 3:
+        raise ValueError("cloud must have shape (n, 3), got %r" % (c.shape,))
+    return np.ascontiguousarray(c)
+
+
+def _ray_segments(origins, targets):
+    """targets (n, 3), origins (3,), (1, 3) or (n, 3), of any float type -> C-contiguous float32 (K, 3) and (n, 3), K = 1 or n"""
+    t = np.ascontiguousarray(np.asarray(targets), dtype=np.float32)
+    if t.ndim != 2 or t.shape[1] != 3 or t.shape[0] < 1:
+        raise ValueError("targets must have shape (n, 3) with n >= 1, got %r" % (t.shape,))
+    n = t.shape[0]
+    if n > RAYCAST_MAX_RAYS:
+        raise ValueError("at most 2**26 rays per call, got %d" % n)
+    o = np.ascontiguousarray(np.asarray(origins), dtype=np.float32)
+    if o.shape == (3,):
+        o = o.reshape(1, 3)
+    if o.shape not in ((1, 3), (n, 3)):
+        raise ValueError("origins must have shape (3,), (1, 3) or (%d, 3), got %r" % (n, o.shape))
+    return o, t
+
+
+def _ray_flags(unknown_blocks, check_target=False):
+    return (_RAY_UNKNOWN_BLOCKS if unknown_blocks else 0) | (_RAY_CHECK_TARGET if check_target else 0)
+
+
 def _align_transforms(transforms):
     """transforms float64 (K, 4, 4) or (K, 3, 4) -> C-contiguous float64 (K, 3, 4): rows 0..2"""
     a = np.asarray(transforms)
@@ -2591,12 +2621,7 @@ class VoxelAtlas(object):
         occupied voxel anywhere in the extent within one voxel on every axis), free, never observed (also: outside the extent);
         "outside" is outside the box.  Returns a DeviceAtlasAlignments; None before the first combine and, without an origin, before
         the first integrate."""
-        c = np.asarray(cloud)
-        if c.dtype != np.float32:
-            raise TypeError("cloud must be float32, got %s" % c.dtype)
-        if c.ndim != 2 or c.shape[1] != 3:
-            raise ValueError("cloud must have shape (n, 3), got %r" % (c.shape,))
-        c = np.ascontiguousarray(c)
+        c = _align_cloud(cloud)
         t = _align_transforms(transforms)
         return self._score_alignments(_ptr(c), c.shape[0], _ptr(t), t.shape[0], 0, dilate, weights, origin_voxels, center)
 
@@ -2609,7 +2634,7 @@ class VoxelAtlas(object):
     def _raycast(self, from_ptr, K, to_ptr, n, on_device, unknown_blocks, check_target):
         g = self._owner
         e = (_I64 * 3)()
-        flags = (_RAY_UNKNOWN_BLOCKS if unknown_blocks else 0) | (_RAY_CHECK_TARGET if check_target else 0)
+        flags = _ray_flags(unknown_blocks, check_target)
         hold = g._make_product(lambda pid: g._lib.gvom_voxel_atlas_raycast(g._h, from_ptr, int(K), to_ptr, int(n), int(on_device), flags, e, pid),
                                PRODUCT_VOXEL_ATLAS_RAYS, g._check_args)
         return None if hold is None else DeviceAtlasRays(hold, tuple(int(v) for v in e))
@@ -2618,18 +2643,8 @@ class VoxelAtlas(object):
         """Gvom.raycast() through the atlas: the same segments, flags and ray rule, with the extent in the window's place -- a ray
         stops at the first remembered occupied voxel, never-observed voxels count as unknown, RAY_LEFT_WINDOW means it left the
         extent.  Returns a DeviceAtlasRays; None before the first combine."""
-        t = np.ascontiguousarray(np.asarray(targets), dtype=np.float32)
-        if t.ndim != 2 or t.shape[1] != 3 or t.shape[0] < 1:
-            raise ValueError("targets must have shape (n, 3) with n >= 1, got %r" % (t.shape,))
-        n = t.shape[0]
-        if n > RAYCAST_MAX_RAYS:
-            raise ValueError("at most 2**26 rays per call, got %d" % n)
-        o = np.ascontiguousarray(np.asarray(origins), dtype=np.float32)
-        if o.shape == (3,):
-            o = o.reshape(1, 3)
-        if o.shape not in ((1, 3), (n, 3)):
-            raise ValueError("origins must have shape (3,), (1, 3) or (%d, 3), got %r" % (n, o.shape))
-        return self._raycast(_ptr(o), o.shape[0], _ptr(t), n, 0, unknown_blocks, check_target)
+        o, t = _ray_segments(origins, targets)
+        return self._raycast(_ptr(o), o.shape[0], _ptr(t), t.shape[0], 0, unknown_blocks, check_target)
 
     def raycast_device(self, from_ptr, K, to_ptr, n, unknown_blocks=False, check_target=False):
         """The same for segments in device memory, as Gvom.raycast_device().  Enqueues and returns: no host wait."""
@@ -2641,7 +2656,7 @@ class VoxelAtlas(object):
         g = self._owner
         K, r, sh, sw = _viewpoint_options(K, max_range, beam_stride)
         e = (_I64 * 3)()
-        flags = _RAY_UNKNOWN_BLOCKS if unknown_blocks else 0
+        flags = _ray_flags(unknown_blocks)
         hold = g._make_product(lambda pid: g._lib.gvom_voxel_atlas_score_viewpoints(g._h, poses_ptr, K, int(on_device), r, sh, sw, flags, e, pid),
                                PRODUCT_VOXEL_ATLAS_VIEWPOINTS, g._check_args)
         return None if hold is None else DeviceAtlasViewpoints(hold, tuple(int(v) for v in e), host_poses)
@@ -3285,7 +3300,7 @@ class Gvom(object):
     # ---- ray queries (an extension; include/gvom_hip.h "ray queries") ----
     def _raycast(self, from_ptr, K, to_ptr, n, on_device, unknown_blocks, check_target):
         org = (ctypes.c_double * 3)()
-        flags = (_RAY_UNKNOWN_BLOCKS if unknown_blocks else 0) | (_RAY_CHECK_TARGET if check_target else 0)
+        flags = _ray_flags(unknown_blocks, check_target)
         hold = self._make_product(lambda pid: self._lib.gvom_raycast(self._h, from_ptr, int(K), to_ptr, int(n), int(on_device), flags,
                                                                      org, pid), PRODUCT_RAYCAST, self._check_args)
         return None if hold is None else DeviceRays(hold, np.array(list(org), np.float64))
@@ -3299,18 +3314,8 @@ class Gvom(object):
         ROUNDED TO float32 (the library's input type; a float32 start and end are what makes the voxels walked exactly the ones
         a scan's ray marks).  None before the first combine.  A convenience route: the arrays are copied to the device; rays in
         a coherent order (neighbours pointing the same way) are faster."""
-        t = np.ascontiguousarray(np.asarray(targets), dtype=np.float32)
-        if t.ndim != 2 or t.shape[1] != 3 or t.shape[0] < 1:
-            raise ValueError("targets must have shape (n, 3) with n >= 1, got %r" % (t.shape,))
-        n = t.shape[0]
-        if n > RAYCAST_MAX_RAYS:
-            raise ValueError("at most 2**26 rays per call, got %d" % n)
-        o = np.ascontiguousarray(np.asarray(origins), dtype=np.float32)
-        if o.shape == (3,):
-            o = o.reshape(1, 3)
-        if o.shape not in ((1, 3), (n, 3)):
-            raise ValueError("origins must have shape (3,), (1, 3) or (%d, 3), got %r" % (n, o.shape))
-        return self._raycast(_ptr(o), o.shape[0], _ptr(t), n, 0, unknown_blocks, check_target)
+        o, t = _ray_segments(origins, targets)
+        return self._raycast(_ptr(o), o.shape[0], _ptr(t), t.shape[0], 0, unknown_blocks, check_target)
 
     def raycast_device(self, from_ptr, K, to_ptr, n, unknown_blocks=False, check_target=False):
         """The same for segments in device memory: raw device addresses of K x 3 and n x 3 float32 (C-contiguous; K is 1 or n;
@@ -3538,7 +3543,7 @@ class Gvom(object):
     def _score_viewpoints(self, poses_ptr, K, on_device, max_range, beam_stride, unknown_blocks, host_poses=None):
         K, r, sh, sw = _viewpoint_options(K, max_range, beam_stride)
         org = (ctypes.c_double * 3)()
-        flags = _RAY_UNKNOWN_BLOCKS if unknown_blocks else 0
+        flags = _ray_flags(unknown_blocks)
         hold = self._make_product(lambda pid: self._lib.gvom_score_viewpoints(self._h, poses_ptr, K, int(on_device), r, sh, sw, flags,
                                                                               org, pid), PRODUCT_VIEWPOINTS, self._check_args)
         return None if hold is None else DeviceViewpoints(hold, np.array(list(org), np.float64), host_poses)
@@ -3652,12 +3657,7 @@ class Gvom(object):
         cast; transforms: float64 (K, 4, 4) or (K, 3, 4) (pose_candidates builds a grid of them; arbitrary matrices are accepted).
         Read-only: the map does not change.  None before the first combine.  A convenience route: the arrays are copied to the
         device."""
-        c = np.asarray(cloud)
-        if c.dtype != np.float32:
-            raise TypeError("cloud must be float32, got %s" % c.dtype)
-        if c.ndim != 2 or c.shape[1] != 3:
-            raise ValueError("cloud must have shape (n, 3), got %r" % (c.shape,))
-        c = np.ascontiguousarray(c)
+        c = _align_cloud(cloud)
         t = _align_transforms(transforms)
         return self._score_alignments(_ptr(c), c.shape[0], _ptr(t), t.shape[0], 0, dilate, weights)
 

@@ -8,7 +8,13 @@ Every case is refused before any launch.  The handles are small: a 16-cell windo
 128-cell window for the atlas that would be smaller than its window.  Not replayed here: the refusals of windows above 4096 cells
 (test_maps_of_more_than_4096_cells_a_side_are_refused in test_costfield / test_rollouts / test_attitude / test_frontier / test_clearance,
 test_windows_beyond_the_limits_are_refused in test_posefield), and four capacity limits no small window reaches: gvom_score_alignments'
-class grid of 2^32 words, gvom_score_viewpoints' 2^22 beams, beams x (xy_size + z_size + 1) >= 2^31 and a window of 2^31 voxels."""
+class grid of 2^32 words, gvom_score_viewpoints' 2^22 beams, beams x (xy_size + z_size + 1) >= 2^31 and a window of 2^31 voxels.
+
+The voxel atlas's three walk queries (gvom_voxel_atlas_raycast, _score_viewpoints, _score_alignments) are replayed on an atlas of 64
+cells and 8 levels: the sharded handle, no atlas, every check arguments alone reach, and calls with several bad arguments for the
+order; recorded with the library of the commit before their checks moved into the helpers of their window twins.  Not reached by a
+small handle there: gvom_voxel_atlas_score_viewpoints' 2^22 beams, beams x (cells + levels + 1) >= 2^31 and the box of a pose of 2^31
+voxels (which also needs a combined map), and gvom_voxel_atlas_score_alignments' class grid of 2^32 words."""
 import ctypes
 import json
 import os
@@ -448,6 +454,58 @@ def replay(mod, settings):
     case("atlas_frontiers: min_cells, max_clusters", afr(min_cells=0, max_clusters=0))
     case("atlas_frontiers: max_clusters 0", afr(max_clusters=0))
     case("atlas_frontiers: max_clusters 2^20 + 1", afr(max_clusters=(1 << 20) + 1))
+
+    # ---- the voxel atlas's walk queries: gvom_voxel_atlas_raycast, _score_viewpoints, _score_alignments (recorded before they were folded
+    # onto the drivers of their window twins; an atlas of A cells and z_size levels, the smallest the library takes)
+    e3 = (I64 * 3)()
+    bare = mod.Gvom(0.5, 0.2, xy, zs, *rest, voxel_statistics=False)       # an atlas, no sensor model
+
+    def vrq(h=g, frm=poses, K=1, to=poses, n=1, flags=0):
+        return L.gvom_voxel_atlas_raycast(h._h, _p(frm), K, _p(to), n, 0, flags, e3, PID)
+
+    def vvp(h=g, p=one, K=1, max_range=5.0, sh=1, sw=1, flags=0):
+        return L.gvom_voxel_atlas_score_viewpoints(h._h, _p(p), K, 0, max_range, sh, sw, flags, e3, PID)
+
+    def val(h=g, c=poses, n=1, t=one, K=1, dilate=0, w=w5, o=None):
+        return L.gvom_voxel_atlas_score_alignments(h._h, _p(c), n, _p(t), K, 0, dilate, w, o, e3, PID)
+    case("voxel_atlas_raycast: sharded", vrq(s, frm=None), s)
+    case("voxel_atlas_score_viewpoints: sharded", vvp(s, p=None), s)
+    case("voxel_atlas_score_alignments: sharded", val(s, c=None), s)
+    case("voxel_atlas_raycast: no atlas, from", vrq(frm=None, n=0))
+    case("voxel_atlas_score_viewpoints: no atlas, poses", vvp(p=None, K=0))
+    case("voxel_atlas_score_alignments: no atlas, cloud", val(c=None, n=0))
+    for h in (g, bare):
+        assert L.gvom_voxel_atlas_configure(h._h, A, zs, 1, None) == 0, L.gvom_last_error(h._h)
+    case("voxel_atlas_raycast: from", vrq(frm=None, n=0))
+    case("voxel_atlas_raycast: to", vrq(to=None))
+    case("voxel_atlas_raycast: n, K", vrq(n=0, K=2))
+    case("voxel_atlas_raycast: n", vrq(n=-1, K=-1))
+    case("voxel_atlas_raycast: K, flags", vrq(K=2, n=3, flags=4))
+    case("voxel_atlas_raycast: K", vrq(K=0))
+    case("voxel_atlas_raycast: flags, capacity", vrq(flags=4, n=(1 << 26) + 1))
+    case("voxel_atlas_raycast: flags", vrq(flags=8))
+    case("voxel_atlas_raycast: capacity", vrq(n=(1 << 26) + 1))
+    case("voxel_atlas_raycast: capacity, K = n", vrq(n=(1 << 26) + 1, K=(1 << 26) + 1))
+    case("voxel_atlas_score_viewpoints: poses NULL", vvp(bare, p=None, K=0), bare)
+    case("voxel_atlas_score_viewpoints: no sensor model", vvp(bare, K=0), bare)
+    case("voxel_atlas_score_viewpoints: K, strides", vvp(K=0, sh=0))
+    case("voxel_atlas_score_viewpoints: stride_h, max_range", vvp(sh=0, max_range=nan))
+    case("voxel_atlas_score_viewpoints: stride_w", vvp(sw=0))
+    case("voxel_atlas_score_viewpoints: max_range NaN, flags", vvp(max_range=nan, flags=2))
+    case("voxel_atlas_score_viewpoints: max_range 0", vvp(max_range=0.0))
+    case("voxel_atlas_score_viewpoints: max_range inf", vvp(max_range=float("inf")))
+    case("voxel_atlas_score_viewpoints: flags, capacity", vvp(flags=2, K=65537))
+    case("voxel_atlas_score_viewpoints: capacity", vvp(K=65537))
+    case("voxel_atlas_score_alignments: cloud NULL", val(c=None, n=0))
+    case("voxel_atlas_score_alignments: transforms NULL", val(t=None))
+    case("voxel_atlas_score_alignments: weights NULL", val(w=None))
+    case("voxel_atlas_score_alignments: n, K", val(n=0, K=0))
+    case("voxel_atlas_score_alignments: K, dilate", val(K=0, dilate=2))
+    case("voxel_atlas_score_alignments: dilate, weight", val(dilate=2, w=(ctypes.c_int32 * 5)(1, 1, 1, 1, 1025)))
+    case("voxel_atlas_score_alignments: weight, n", val(w=(ctypes.c_int32 * 5)(-1025, 1, 1, 1, 1), n=(1 << 20) + 1))
+    case("voxel_atlas_score_alignments: n, K capacity", val(n=(1 << 20) + 1, K=65537))
+    case("voxel_atlas_score_alignments: K capacity", val(K=65537, o=_i64(FAR, 0, 0)))
+    case("voxel_atlas_score_alignments: pairs", val(n=1 << 20, K=65536))
     return out
 
 

@@ -5,13 +5,15 @@ tree's own -- alternated in fresh child processes, TURNS turns each, on one mach
   waiting calls  cost_to_go_of, frontiers_of and pose_field_of on 256-cell maps (seeded obstacles, host maps: staged), and the atlas's
                  cost_to_go and its field's frontiers on an extent of 1024 cells: end-to-end wall time per call, median of CALLS calls
                  behind WARM warm-up calls; the calls wait for the GPU themselves
-  overhead       raycast (n = 1) and score_rollouts_of (K = T = 1) on a 16-cell window: wall time per call averaged over MANY calls,
-                 behind a gvom sync -- a change in host overhead would show here
+  overhead       raycast (n = 1), the voxel atlas's raycast (n = 1; an atlas of 64 cells and 8 levels) and score_rollouts_of (K = T = 1)
+                 on a 16-cell window: wall time per call averaged over MANY calls, behind a gvom sync -- a change in host overhead
+                 would show here
   step           bench.py --config m256 and c4: ms per step
 
 Per measurement the median over each library's turns and the parent's own min .. max: the margin a difference is held against.
 
-    tools/product_calls_ab.py --parent PATH/libgvom_hip.so [--turns N] [out.json]      (default: 5 turns, profiles/product_calls_<lib sha8>.json)
+    tools/product_calls_ab.py --parent PATH/libgvom_hip.so [--turns N] [--sections waiting,overhead,m256,c4] [out.json]
+                                                                      (default: 5 turns, every section, profiles/product_calls_<lib sha8>.json)
 """
 import json
 import os
@@ -23,15 +25,24 @@ import benchkit as bk
 sys.path.insert(0, os.path.join(bk.ROOT, "tests"))
 TURNS, WARM, CALLS, MANY = 5, 3, 20, 2000
 REST = (1, 1.0, 0.5, 0.5, 0.3, 2.0, 4.0, 1.0, 1, 1)
+SECTIONS = ("waiting", "overhead", "m256", "c4")
 CHILD_TIMEOUT = 600                                                        # seconds, per child process and per bench.py run
 
 
-def child():
+def child(sections):
     import numpy as np
     import gvom
     import posefield_ref
     out = {}
     rng = np.random.default_rng(7)
+    if "waiting" in sections:
+        waiting_calls(np, gvom, posefield_ref, rng, out)
+    if "overhead" in sections:
+        overhead_calls(np, gvom, posefield_ref, rng, out)
+    return out
+
+
+def waiting_calls(np, gvom, posefield_ref, rng, out):
     xy = 256
     g = gvom.Gvom(0.4, 0.2, xy, 8, *REST, voxel_statistics=False)
     cost = np.where(rng.random((xy, xy)) < 0.2, 0, rng.integers(1, 40, (xy, xy))).astype(np.uint16)
@@ -69,7 +80,10 @@ def child():
     f.release()
     out["atlas_cost_to_go_A1024_ms"] = bk.timed_waiting(lambda: a.cost_to_go([(512, 512)], goals_in_cells=True).release(), WARM, CALLS)
     del a, ga
-    # host overhead: the smallest calls, many of them
+
+
+def overhead_calls(np, gvom, posefield_ref, rng, out):
+    """host overhead: the smallest calls, many of them"""
     s = 16
     gs = gvom.Gvom(0.4, 0.2, s, 8, *REST, voxel_statistics=False)
     pc = np.stack([rng.uniform(-2, 2, 500), rng.uniform(-2, 2, 500), rng.normal(-0.5, 0.2, 500)], axis=1).astype(np.float32)
@@ -89,8 +103,10 @@ def child():
         gs._lib.gvom_sync(gs._h)
         return (time.perf_counter() - t0) / MANY * 1e6
     out["raycast_n1_us"] = many(lambda: gs.raycast(o, t).release())
+    va = gs.create_voxel_atlas(64, 8)
+    va.integrate()
+    out["voxel_atlas_raycast_n1_us"] = many(lambda: va.raycast(o, t).release())
     out["score_rollouts_K1T1_us"] = many(lambda: gs.score_rollouts_of(small, pose).release())
-    return out
 
 
 def _bench(lib, config, steps, warmup):
@@ -100,18 +116,21 @@ def _bench(lib, config, steps, warmup):
 
 
 def main():
-    if bk.child(sys.argv[1:], {"calls": lambda a: child()}):
+    if bk.child(sys.argv[1:], {"calls": lambda a: child(a[0].split(","))}):
         return
     import gvom
-    args = bk.read_args(sys.argv[1:], has_resources=False, turns=TURNS)
+    args = bk.read_args(sys.argv[1:], has_resources=False, turns=TURNS, extra={"--sections": (list(SECTIONS), lambda s: [v for v in s.split(",") if v])})
+    sections = args["sections"]
     if not args["parent"]:
         raise SystemExit("--parent PATH/libgvom_hip.so: the library before")
     libs = {"parent": os.path.abspath(args["parent"]), "tree": os.path.abspath(gvom.library_path())}
 
     def one(name):
-        res = bk.spawn(__file__, "calls", (), CHILD_TIMEOUT, lib=libs[name])
-        res["bench_m256_ms_per_step"] = _bench(libs[name], "m256", 300, 60)
-        res["bench_c4_ms_per_step"] = _bench(libs[name], "c4", 40, 10)
+        res = bk.spawn(__file__, "calls", (",".join(sections),), CHILD_TIMEOUT, lib=libs[name])
+        if "m256" in sections:
+            res["bench_m256_ms_per_step"] = _bench(libs[name], "m256", 300, 60)
+        if "c4" in sections:
+            res["bench_c4_ms_per_step"] = _bench(libs[name], "c4", 40, 10)
         print(name, json.dumps(res), flush=True)
         return res
     turns = bk.alternate(args["turns"], {name: (lambda name=name: one(name)) for name in libs})      # parent, tree, parent, tree ...
@@ -125,7 +144,7 @@ def main():
         table[key] = {"parent_median": bk.median(p), "parent_min": min(p), "parent_max": max(p), "tree_median": bk.median(t), "tree_min": min(t),
                       "tree_max": max(t), "tree_median_inside_parent_spread": min(p) <= bk.median(t) <= max(p)}
     report = bk.Report("product_calls", args["path"], args["parent"], fresh=True)
-    report.out.update({"what": __doc__.split("\n\n")[0], "turns": args["turns"], "calls": CALLS, "many": MANY, "table": table, "runs": turns})
+    report.out.update({"what": __doc__.split("\n\n")[0], "turns": args["turns"], "sections": sections, "calls": CALLS, "many": MANY, "table": table, "runs": turns})
     report.save()
     for key, v in table.items():
         print(key, json.dumps(v))

@@ -8,13 +8,14 @@ every loop in a fresh child process, every child under a `timeout` of its own, a
   walk       after ONE integrate into a fixed extent around the window, where the answers are equal: gvom_raycast against
              gvom_voxel_atlas_raycast on the same 262,144 in-window segments (device route), gvom_score_viewpoints against
              gvom_voxel_atlas_score_viewpoints on the same 64 poses (a 32 x 1024 sensor) -- the whole calls by HIP events, and the
-             kernels alone from a rocprofv3 kernel trace of a second child
+             kernels alone from a rocprofv3 kernel trace of a second child; with --parent LIB both children on that library too,
+             alternating, --turns turns each: per call and per walk kernel this library's median against the parent's min .. max
   step       scan + combine_maps_device() per step: without an atlas call, with integrate(); and, with --parent LIB (the parent
              commit's libgvom_hip.so), the step without on that library, alternating, --turns runs each (default five)
   resources  tools/kernel_regs.py: the new kernels, and registers, scratch, LDS and code size of every kernel outside the new unit
              on the parent and on this library (--resources alone: no GPU needed)
 
-    tools/voxel_atlas_bench.py [--resources] [--parent LIB] [--configs m256,c4] [--turns N] [out.json]
+    tools/voxel_atlas_bench.py [--resources] [--parent LIB] [--configs m256,c4] [--sections events,walk,step] [--turns N] [out.json]
                                                                                 (default: profiles/voxel_atlas_<lib sha8>.json)
 """
 import json
@@ -31,6 +32,9 @@ N_RAYS = 1 << 18
 N_POSES = 64
 CHILD_TIMEOUT = 300                                       # seconds, per child process
 TURNS = 5
+SECTIONS = ("events", "walk", "step")
+WALK_CALLS = ("gvom_raycast (device route)", "gvom_voxel_atlas_raycast (device route)", "gvom_score_viewpoints (host poses)",
+              "gvom_voxel_atlas_score_viewpoints (host poses)")
 KERNELS = ("k_vatlas_merge", "k_vatlas_move", "k_vatlas_box", "k_vatlas_raycast", "k_vatlas_viewpoints", "k_vatlas_viewpoint_best",
            "k_raycast", "k_viewpoints", "k_viewpoint_best")
 
@@ -131,11 +135,28 @@ def child_step(name, steps, mode):
     return bk.step_loop(g, step, steps, warm=min(10, steps))
 
 
+def walk_against_parent(runs):
+    """{figure: this library's median over its turns against the parent's median, min and max}: the four calls (median_us of a turn's
+    HIP events) and the six walk kernels (avg_us of a turn's kernel trace)"""
+    def figures(rec):
+        out = {k: rec[k]["median_us"] for k in WALK_CALLS}
+        out.update({k: v["avg_us"] for k, v in rec["kernels"].items() if "raycast" in k or "viewpoint" in k})
+        return out
+    p, t = [figures(r) for r in runs["parent"]], [figures(r) for r in runs["this"]]
+    table = {}
+    for key in p[0]:
+        a, b = [x[key] for x in p], [x[key] for x in t]
+        table[key] = {"parent_median": bk.median(a), "parent_min": min(a), "parent_max": max(a), "this_median": bk.median(b), "this_min": min(b),
+                      "this_max": max(b), "this_median_inside_parents_own_spread": bool(min(a) <= bk.median(b) <= max(a))}
+    return table
+
+
 def main():
     if bk.child(sys.argv[1:], {"events": lambda a: child_events(a[0]), "walk": lambda a: child_walk(a[0]),
                                "step": lambda a: child_step(a[0], int(a[1]), int(a[2]))}):
         return
-    args = bk.read_args(sys.argv[1:], configs=CONFIGS, turns=TURNS)
+    args = bk.read_args(sys.argv[1:], configs=CONFIGS, turns=TURNS, extra={"--sections": (list(SECTIONS), lambda s: [v for v in s.split(",") if v])})
+    sections = args["sections"]
     parent = args["parent"]
     spawn = lambda mode, a, **kw: bk.spawn(__file__, mode, a, CHILD_TIMEOUT, **kw)
     report, configs = bk.product_report(
@@ -146,13 +167,26 @@ def main():
         return
     for name in args["configs"]:
         steps = CONFIGS[name]
-        res = {"events": spawn("events", (name,)), "walk": spawn("walk", (name,))}
-        configs[name] = res
-        report.save()
-        with tempfile.TemporaryDirectory() as d:                             # the kernels alone: a kernel trace of the same child
-            spawn("walk", (name,), profile_dir=d, stats=True)
-            res["kernels (rocprofv3 --kernel-trace --stats of the walk child)"] = bk.kernel_stats(d, KERNELS)
-        report.save()
+        res = configs.setdefault(name, {})
+        if "events" in sections:
+            res["events"] = spawn("events", (name,))
+            report.save()
+
+        def walk_once(lib):                                                      # the calls by events, then the kernels alone: a kernel trace of the same child
+            rec = spawn("walk", (name,), lib=lib)
+            with tempfile.TemporaryDirectory() as d:
+                spawn("walk", (name,), profile_dir=d, stats=True, lib=lib)
+                rec["kernels"] = bk.kernel_stats(d, KERNELS)
+            return rec
+        if "walk" in sections:
+            runs = bk.alternate(args["turns"] if parent else 1, {"parent": parent and (lambda: walk_once(parent)), "this": lambda: walk_once(None)})
+            res["walk"] = dict(runs["this"][-1])
+            res["kernels (rocprofv3 --kernel-trace --stats of the walk child)"] = res["walk"].pop("kernels")
+            if parent:
+                res["walk against the parent, %d alternating turns" % args["turns"]] = walk_against_parent(runs)
+            report.save()
+        if "step" not in sections:
+            continue
         runs = bk.alternate(args["turns"], {"parent_without": parent and (lambda: spawn("step", (name, steps, 0), lib=parent)),
                                             "without": lambda: spawn("step", (name, steps, 0)),
                                             "integrate": lambda: spawn("step", (name, steps, 1))})

@@ -25,6 +25,8 @@ first_seen = free_to_occupied = occupied_to_free = 0):
                        voxel_atlas_align_ref.score
 Before the first combine (the P0 hook of run_script) integrate() reports no data and seq stays 0.
 run_async_first_script is this file's own: there integrate() is the first call behind an asynchronous combine on the second stream.
+Q is made of hooks (before_bundle, before_merge, merges_at, after_merge) that do nothing here: tests/voxel_changes_cycle.py puts the
+atlas's change query in front of the bundle and of the merge, and merges only where its schedule says.
 
 Without a handle (g=None: the census) Q records in `trail`, per point, the referee's counts, and -- for every map a wrong answer would
 come from (Cycle.Q's `others`: the map before, and what a combine at that moment would give) -- the counts that merging THAT map would
@@ -186,9 +188,25 @@ class AtlasCycle(qc.Cycle):
             assert tuple(got) == va.COUNT_NAMES and got == want, "%s: counts %r, referee %r" % (what, got, want)
         return what, W, n, before
 
+    # the hooks of a subclass (tests/voxel_changes_cycle.py): calls in front of the parent's bundle, calls in front of the merge, points
+    # without a merge, and what follows a merge in place of the atlas's own product bundle
+    def before_bundle(self, label):
+        pass
+
+    def before_merge(self, label):
+        pass
+
+    def merges_at(self, label):
+        return True
+
     def Q(self, label):
+        self.before_bundle(label)
         qc.Cycle.Q(self, label)
-        what, W, n, before = self.merge(label)
+        self.before_merge(label)
+        if self.merges_at(label):
+            self.after_merge(label, *self.merge(label))
+
+    def after_merge(self, label, what, W, n, before):
         if self.g is None:
             self._census(label, before, n, W)
             return

@@ -530,13 +530,13 @@ static int scan_finish(gvom_handle *h, std::unique_lock<std::mutex> &lk, const v
 }
 
 // a pinned staging buffer of at least `bytes` (grown by half as much again; contents not kept)
-static int ensure_pinned(gvom_handle *h, void *&p, size_t &have, size_t bytes)
+static int ensure_pinned(gvom_handle *h, PinPtr<void> &b, size_t bytes)
 {
-    if (have >= bytes) return GVOM_OK;
-    if (p) HIPCHK(h, hipHostFree(p));
-    p = nullptr; have = 0;
-    HIPCHK(h, hipHostMalloc(&p, bytes + bytes / 2, hipHostMallocDefault));
-    have = bytes + bytes / 2;
+    if (b.bytes >= bytes) return GVOM_OK;
+    if (b.p) HIPCHK(h, hipHostFree(b.p));
+    b.p = nullptr; b.bytes = 0;
+    HIPCHK(h, hipHostMalloc(&b.p, bytes + bytes / 2, hipHostMallocDefault));
+    b.bytes = bytes + bytes / 2;
     return GVOM_OK;
 }
 
@@ -559,14 +559,14 @@ static int mo_table(gvom_handle *h, const double *origins, int32_t K, int64_t id
 {
     const gvom_params &p = h->prm;
     const size_t bytes = mo_index_offset(K) + (size_t)idx_n * 2;
-    int rc = ensure(h, h->mo_dev, bytes);
+    int rc = ensure(h, h->multi_origin.dev, bytes);
     if (rc) return rc;
-    if ((rc = ensure_pinned(h, h->mo_pin, h->mo_pin_bytes, bytes))) return rc;
+    if ((rc = ensure_pinned(h, h->multi_origin.pin, bytes))) return rc;
     double lo[3], size[3];
     scan_window_origin(h, lo);
     size[0] = size[1] = p.xy_size; size[2] = p.z_size;
     const double longest = (double)(p.xy_size > p.z_size ? p.xy_size : p.z_size);
-    float *tab = (float *)h->mo_pin;
+    float *tab = (float *)h->multi_origin.pin.p;
     double far_ = 0.0;
     for (int32_t k = 0; k < K; ++k) {
         double e = 0.0;
@@ -623,10 +623,10 @@ static int process_impl(gvom_handle *h, const void *xyz, bool on_device, int64_t
         const bool host_idx = mo->index && !on_device;
         if ((rc = mo_table(h, mo->origins, mo->K, host_idx ? n : 0, &mo_maxsteps))) return rc;
         const size_t ioff = mo_index_offset(mo->K);
-        if (host_idx) memcpy((char *)h->mo_pin + ioff, mo->index, (size_t)n * 2);
-        up[ups++] = {h->mo_dev.p, h->mo_pin, host_idx ? ioff + (size_t)n * 2 : (size_t)mo->K * 12};
-        RO.tab = (const float *)h->mo_dev.p; RO.K = (uint32_t)mo->K;
-        RO.idx = host_idx ? (const uint16_t *)((const char *)h->mo_dev.p + ioff) : mo->index;
+        if (host_idx) memcpy((char *)h->multi_origin.pin.p + ioff, mo->index, (size_t)n * 2);
+        up[ups++] = {h->multi_origin.dev.p, h->multi_origin.pin, host_idx ? ioff + (size_t)n * 2 : (size_t)mo->K * 12};
+        RO.tab = (const float *)h->multi_origin.dev.p; RO.K = (uint32_t)mo->K;
+        RO.idx = host_idx ? (const uint16_t *)((const char *)h->multi_origin.dev.p + ioff) : mo->index;
     }
     if (!on_device && n > 0) {
         if ((rc = ensure(h, h->in_pts, (size_t)n * row_stride_bytes))) return rc;
@@ -649,8 +649,8 @@ static int range_image_impl(gvom_handle *h, const void *raw, bool on_device, int
     std::lock_guard<std::mutex> scan_lk(h->scan_mu);
     std::unique_lock<std::mutex> lk(h->mu);
     if (h->sharded) { h->err = "range images are not supported on a sharded handle"; return GVOM_ERR_INVALID; }
-    if (h->ri_H <= 0) { h->err = "gvom_process_range_image: no sensor model (gvom_sensor_model_set)"; return GVOM_ERR_INVALID; }
-    const int64_t H = h->ri_H, W = h->ri_W, n = H * W;
+    if (h->range_image.H <= 0) { h->err = "gvom_process_range_image: no sensor model (gvom_sensor_model_set)"; return GVOM_ERR_INVALID; }
+    const int64_t H = h->range_image.H, W = h->range_image.W, n = H * W;
     if (row_stride_bytes < W * rsz || row_stride_bytes % rsz != 0) { h->err = "gvom_process_range_image: bad row stride"; return GVOM_ERR_INVALID; }
     // every pixel traced from its column's sensor position: O[w] = the translation of C[w] through the cloud's transform, in the
     // transform's own order of operations (load_return)
@@ -675,28 +675,28 @@ static int range_image_impl(gvom_handle *h, const void *raw, bool on_device, int
     int mo_maxsteps = 0;
     if (from_columns) {
         if ((rc = mo_table(h, col_org.data(), (int32_t)W, 0, &mo_maxsteps))) return rc;
-        up[ups++] = {h->mo_dev.p, h->mo_pin, (size_t)W * 12};
-        RO.tab = (const float *)h->mo_dev.p; RO.K = (uint32_t)W;      // index[i] = i % W: the pixel's column
+        up[ups++] = {h->multi_origin.dev.p, h->multi_origin.pin, (size_t)W * 12};
+        RO.tab = (const float *)h->multi_origin.dev.p; RO.K = (uint32_t)W;   // index[i] = i % W: the pixel's column
     }
-    if (col_poses) {                                       // (first: see ri_poses_pin)
+    if (col_poses) {                                       // (first: see RangeImageState::poses_pin)
         const size_t bytes = (size_t)W * 96;
-        if ((rc = ensure(h, h->ri_poses, bytes))) return rc;
-        if ((rc = ensure_pinned(h, h->ri_poses_pin, h->ri_poses_pin_bytes, bytes))) return rc;
-        memcpy(h->ri_poses_pin, col_poses, bytes);
-        up[ups++] = {h->ri_poses.p, h->ri_poses_pin, bytes};
+        if ((rc = ensure(h, h->range_image.poses, bytes))) return rc;
+        if ((rc = ensure_pinned(h, h->range_image.poses_pin, bytes))) return rc;
+        memcpy(h->range_image.poses_pin, col_poses, bytes);
+        up[ups++] = {h->range_image.poses.p, h->range_image.poses_pin, bytes};
     }
     if (!on_device) {
         const size_t bytes = (size_t)(H - 1) * row_stride_bytes + (size_t)(W * rsz);
-        if ((rc = ensure(h, h->ri_raw, bytes))) return rc;
-        up[ups++] = {h->ri_raw.p, raw, bytes};
+        if ((rc = ensure(h, h->range_image.raw, bytes))) return rc;
+        up[ups++] = {h->range_image.raw.p, raw, bytes};
     }
     if (ups && (rc = scan_upload(h, lk, up, ups))) return rc;
     UnprojectParams U;
-    U.raw = on_device ? raw : h->ri_raw.p; U.row_stride = row_stride_bytes;
-    U.dir = (const double *)h->ri_model.p; U.off = U.dir + (size_t)n * 3;
-    U.poses = col_poses ? (const double *)h->ri_poses.p : nullptr;
+    U.raw = on_device ? raw : h->range_image.raw.p; U.row_stride = row_stride_bytes;
+    U.dir = (const double *)h->range_image.model.p; U.off = U.dir + (size_t)n * 3;
+    U.poses = col_poses ? (const double *)h->range_image.poses.p : nullptr;
     U.out = h->in_pts.p;
-    U.scale = h->ri_scale; U.min_range = h->ri_min; U.max_range = h->ri_max;
+    U.scale = h->range_image.scale; U.min_range = h->range_image.min; U.max_range = h->range_image.max;
     U.W = (uint32_t)W; U.n = (uint32_t)n;
     HIPCHK(h, gvom_launch_unproject(h->stream, U, range_dtype, cloud_dtype));
     return scan_finish(h, lk, h->in_pts.p, n, 3, cloud_dtype, tf, false, from_columns ? &RO : nullptr, mo_maxsteps);
@@ -747,17 +747,17 @@ VIS int gvom_sensor_model_set(gvom_t *h, int32_t H, int32_t W, const double *dir
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     const size_t half = (size_t)H * W * 24;
-    h->ri_H = h->ri_W = 0;
-    int rc = ensure(h, h->ri_model, 2 * half);
+    h->range_image.H = h->range_image.W = 0;
+    int rc = ensure(h, h->range_image.model, 2 * half);
     if (rc) return rc;
-    char *m = (char *)h->ri_model.p;
+    char *m = (char *)h->range_image.model.p;
     HIPCHK(h, hipMemcpyAsync(m, dir, half, hipMemcpyHostToDevice, h->stream));
     if (off) HIPCHK(h, hipMemcpyAsync(m + half, off, half, hipMemcpyHostToDevice, h->stream));
     else HIPCHK(h, hipMemsetAsync(m + half, 0, half, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    h->ri_H = H; h->ri_W = W;
-    ++h->ri_gen;                                                            // (what the voxel atlas keeps of the model is stale from here on)
-    h->ri_scale = range_scale; h->ri_min = min_range; h->ri_max = max_range;
+    h->range_image.H = H; h->range_image.W = W;
+    ++h->range_image.gen;                                                   // (what the voxel atlas keeps of the model is stale from here on)
+    h->range_image.scale = range_scale; h->range_image.min = min_range; h->range_image.max = max_range;
     return GVOM_OK;
 }
 

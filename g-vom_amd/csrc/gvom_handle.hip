@@ -199,7 +199,7 @@ static int create_impl(const gvom_params *params, int device_id, int rank, int w
         CK(hipMalloc((void **)&h->fused[k].tags, h->ntiles * 4));
         CK(hipMemsetAsync(h->fused[k].tags, 0, h->ntiles * 4, h->stream));
     }
-    CK(hipMalloc((void **)&h->dir_hist, 3 * GVOM_DIRBINS * 4));
+    CK(hipMalloc((void **)&h->dir_hist.p, 3 * GVOM_DIRBINS * 4));
     CK(hipMemsetAsync(h->dir_hist, 0, 3 * GVOM_DIRBINS * 4, h->stream));
     CK(hipMalloc((void **)&h->counters, GVOM_CNT_WORDS * 4));
     CK(hipHostMalloc((void **)&h->counters_host, 64, hipHostMallocMapped | hipHostMallocCoherent));
@@ -448,8 +448,7 @@ VIS void gvom_destroy(gvom_t *h)
     if (h->x_host) hipHostFree(h->x_host);
     for (auto &s : h->slots) { hipFree(s.state); hipFree(s.code16); hipFree(s.tags); fb(s.crows); fb(s.metrics); fb(s.base); fb(s.rowvox); }
     for (auto &f : h->fused) { hipFree(f.state); hipFree(f.tags); fb(f.rows); fb(f.metrics); }
-    fb(h->in_pts); fb(h->cl_g); fb(h->cl_stage); fb(h->rq_stage); fb(h->ctg_stage); fb(h->ctg_clr); fb(h->fp_tab); fb(h->ro_stage); fb(h->at_tab); fb(h->at_ground); fb(h->at_stage); fb(h->bd_tab); fb(h->bd_ground); fb(h->bd_stage); fb(h->al_grid); fb(h->al_stage); fb(h->fr_stage); fb(h->vp_bitmaps); fb(h->vp_stage); fb(h->pf_tab); fb(h->pf_stage); fb(h->atl_stage); fb(h->af_clr); fb(h->av_tab); fb(h->av_ground); fb(h->av_stage); fb(h->bv_ground); fb(h->bv_stage);hipFree(h->atl_mem); hipFree(h->atl_cnt); if (h->atl_pin) hipHostFree(h->atl_pin); fb(h->va_stage); fb(h->va_bitmaps); fb(h->va_dist); fb(h->va_chg); hipFree(h->va_mem); hipFree(h->va_cnt); if (h->va_pin) hipHostFree(h->va_pin); fb(h->ri_model); fb(h->ri_raw); fb(h->ri_poses); if (h->ri_poses_pin) hipHostFree(h->ri_poses_pin); fb(h->mo_dev); if (h->mo_pin) hipHostFree(h->mo_pin); fb(h->world_pts[0]); fb(h->world_pts[1]); fb(h->flink[0]); fb(h->flink[1]); fb(h->tl); fb(h->dir_keys); fb(h->dir_perm); hipFree(h->dir_hist);
-    for (SolveWork *w : {&h->ctg, &h->fr, &h->pf, &h->af, &h->afr, &h->vchg}) { fb(w->work); if (w->pin) hipHostFree(w->pin); }   // the calls that wait: work buffer and pinned counters
+    // (the scan path's grow-only buffers and everything the calls keep -- the records of gvom_host.h -- own their memory: `delete h` below)
     hipFree(h->counters); if (h->counters_host) hipHostFree(h->counters_host);
     hipFree(h->descs_dev); if (h->descs_host) hipHostFree(h->descs_host);
     hipFree(h->blockcounts); hipFree(h->blockcounts2); hipFree(h->hmaps2);
@@ -518,6 +517,30 @@ VIS int gvom_host_timing(gvom_t *h, double us[8])
     return GVOM_OK;
 }
 
+// the clamps of gvom_set_tuning's product knobs: rounds per look at the counters ("<call>_batch"; 0: the default), sweeps a tile makes at
+// most per round ("<call>_inner"; 0: the default), and megabytes a call may use (< 0: its default)
+static int clamp_rounds(int v) { return v < 0 ? 0 : std::min(v, GVOM_CTG_MAX_BATCH); }
+static int clamp_sweeps(int v) { return v < 0 ? 0 : v; }
+static int clamp_mb(int v, int dflt, int cap) { return v < 0 ? dflt : std::min(v, cap); }
+// name == call + suffix
+static bool names(const char *name, const char *call, const char *suffix)
+{
+    const size_t n = strlen(call);
+    return !strncmp(name, call, n) && !strcmp(name + n, suffix);
+}
+// the calls that wait, by the word their tuning names begin with: "<call>_inner" / "<call>_batch" are set and read for the window's
+// three (the atlas forms run under those), "<call>_tiles" is read for all, "<call>_rounds" for those marked
+struct SolverNames { const char *call; SolveWork *w; bool tuned, rounds; };
+static const int N_SOLVERS = 5;
+static void solver_names(gvom_handle *h, SolverNames s[N_SOLVERS])
+{
+    s[0] = {"cost_to_go", &h->cost_to_go.solve, true, false};      // (inner 0: 256, batch 0: 8)
+    s[1] = {"frontier", &h->frontiers.solve, true, true};          // (inner 0: 256, batch 0: 8)
+    s[2] = {"pose_field", &h->pose_field.solve, true, true};       // (inner 0: 64, batch 0: 8)
+    s[3] = {"atlas_field", &h->atlas_field.solve, false, false};
+    s[4] = {"atlas_frontier", &h->atlas_frontiers.solve, false, true};
+}
+
 // Performance knobs that never change a result: "segs" = step segments per ray in k_trace, "period" =
 // committing steps between two flushes of a wave's line cache, "ep_row" = dispatch row of the endpoint
 // blocks, "prio" = steps of remaining walk per issue-priority level of a trace wave (0 / 0 / -2 / -1: automatic).
@@ -525,6 +548,12 @@ VIS int gvom_set_tuning(gvom_t *h, const char *name, int value)
 {
     if (!h || !name) return GVOM_ERR_INVALID;
     std::lock_guard<std::mutex> lk(h->mu);
+    SolverNames solvers[N_SOLVERS];
+    solver_names(h, solvers);
+    for (const SolverNames &s : solvers) {
+        if (s.tuned && names(name, s.call, "_inner")) { s.w->tune_inner = clamp_sweeps(value); return GVOM_OK; }
+        if (s.tuned && names(name, s.call, "_batch")) { s.w->tune_batch = clamp_rounds(value); return GVOM_OK; }
+    }
     if (!strcmp(name, "segs")) h->tune_segs = value;
     else if (!strcmp(name, "ep_row")) h->tune_ep_row = value;
     else if (!strcmp(name, "period")) h->tune_period = value;
@@ -537,14 +566,8 @@ VIS int gvom_set_tuning(gvom_t *h, const char *name, int value)
     else if (!strcmp(name, "fastdiv")) h->tune_fastdiv = value;
     else if (!strcmp(name, "eager")) { h->tune_eager = value; h->eager_waste = 0; }
     else if (!strcmp(name, "delta_out")) { if (value >= 0) h->tune_delta_out = value != 0; if (value <= 0) h->out_rec.clear(); }   // (-1: drop every record, keep the setting)   // 0: every run of the returned maps is stored, no record kept
-    else if (!strcmp(name, "cost_to_go_inner")) h->ctg.tune_inner = value < 0 ? 0 : value;     // sweeps a tile makes at most per round (0: 256)
-    else if (!strcmp(name, "cost_to_go_batch")) h->ctg.tune_batch = value < 0 ? 0 : (value > GVOM_CTG_MAX_BATCH ? GVOM_CTG_MAX_BATCH : value);   // rounds per look at the counters (0: 8)
-    else if (!strcmp(name, "frontier_inner")) h->fr.tune_inner = value < 0 ? 0 : value;        // sweeps a tile makes at most per round (0: 256)
-    else if (!strcmp(name, "frontier_batch")) h->fr.tune_batch = value < 0 ? 0 : (value > GVOM_CTG_MAX_BATCH ? GVOM_CTG_MAX_BATCH : value);   // rounds per look at the counters (0: 8)
-    else if (!strcmp(name, "pose_field_inner")) h->pf.tune_inner = value < 0 ? 0 : value;      // sweeps a tile makes at most per round (0: 64)
-    else if (!strcmp(name, "pose_field_batch")) h->pf.tune_batch = value < 0 ? 0 : (value > GVOM_CTG_MAX_BATCH ? GVOM_CTG_MAX_BATCH : value);   // rounds per look at the counters (0: 8)
-    else if (!strcmp(name, "viewpoint_bitmap_mb")) h->tune_vp_mb = value < 0 ? GVOM_VIEWPOINT_DEFAULT_MB : (value > GVOM_VIEWPOINT_MAX_MB ? GVOM_VIEWPOINT_MAX_MB : value);   // megabytes of bitmaps per launch (0: one viewpoint per launch; < 0: the default, 256)
-    else if (!strcmp(name, "voxel_distance_mb")) h->tune_vd_mb = value < 0 ? GVOM_VDIST_DEFAULT_MB : (value > GVOM_VDIST_MAX_MB ? GVOM_VDIST_MAX_MB : value);   // megabytes of halo-grown intermediates a distance field may use (< 0: the default, 256)
+    else if (!strcmp(name, "viewpoint_bitmap_mb")) h->viewpoints.mb = clamp_mb(value, GVOM_VIEWPOINT_DEFAULT_MB, GVOM_VIEWPOINT_MAX_MB);   // megabytes of bitmaps per launch (0: one viewpoint per launch; < 0: the default, 256)
+    else if (!strcmp(name, "voxel_distance_mb")) h->voxel_atlas.mb = clamp_mb(value, GVOM_VDIST_DEFAULT_MB, GVOM_VDIST_MAX_MB);   // megabytes of halo-grown intermediates a distance field may use (< 0: the default, 256)
     else if (!strcmp(name, "occupancy_clear")) h->tune_occ_clear = value;   // k_occupancy: 1 = clear the grid first, write live tile columns only
     else if (!strcmp(name, "exported")) h->exported = value != 0;       // (set by the peer transport, gvom_comm.hip)
 #ifdef GVOM_HOOKS
@@ -560,79 +583,66 @@ VIS int gvom_get_tuning(gvom_t *h, const char *name, int *value)
 {
     if (!h || !name || !value) return GVOM_ERR_INVALID;
     std::lock_guard<std::mutex> lk(h->mu);
-    static const char *const names[5] = {"segs", "period", "ep_row", "prio", "interleave"};
+    static const char *const knobs[5] = {"segs", "period", "ep_row", "prio", "interleave"};
     for (int k = 0; k < 5; ++k)
-        if (!strcmp(name, names[k])) { *value = h->last_knobs[k]; return GVOM_OK; }
+        if (!strcmp(name, knobs[k])) { *value = h->last_knobs[k]; return GVOM_OK; }     // (the last scan's, not the settings)
+    // read-only, "<call>_allocations": the device allocations the call's entry points have made on this handle (its record's count)
+    const struct { const char *call; const CallState &c; } calls[] = {
+        {"clearance", h->clearance}, {"raycast", h->raycast}, {"cost_to_go", h->cost_to_go}, {"rollout", h->rollouts}, {"attitude", h->attitude},
+        {"body", h->body}, {"alignment", h->alignment}, {"frontier", h->frontiers}, {"viewpoint", h->viewpoints}, {"pose_field", h->pose_field},
+        {"atlas", h->atlas}, {"atlas_field", h->atlas_field}, {"atlas_frontier", h->atlas_frontiers}, {"voxel_atlas", h->voxel_atlas},
+        {"attitude_volume", h->attitude_volume}, {"body_volume", h->body_volume}};
+    for (const auto &c : calls)
+        if (names(name, c.call, "_allocations")) { *value = c.c.allocs; return GVOM_OK; }
+    // the calls that wait: read-only "<call>_tiles" / "<call>_rounds" = tile relaxations / rounds of the last call, and the two knobs
+    SolverNames solvers[N_SOLVERS];
+    solver_names(h, solvers);
+    for (const SolverNames &s : solvers) {
+        if (names(name, s.call, "_tiles")) { *value = s.w->last_tiles; return GVOM_OK; }
+        if (s.rounds && names(name, s.call, "_rounds")) { *value = s.w->last_rounds; return GVOM_OK; }
+        if (s.tuned && names(name, s.call, "_inner")) { *value = s.w->tune_inner; return GVOM_OK; }
+        if (s.tuned && names(name, s.call, "_batch")) { *value = s.w->tune_batch; return GVOM_OK; }
+    }
     if (!strcmp(name, "dirsort")) { *value = h->last_dirsort; return GVOM_OK; }
     if (!strcmp(name, "eager_adopted")) { *value = h->eager_stat[0]; return GVOM_OK; }
     if (!strcmp(name, "eager_dropped")) { *value = h->eager_stat[1]; return GVOM_OK; }
-    if (!strcmp(name, "fuse_kernel")) { *value = h->last_fuse; return GVOM_OK; }
+    if (!strcmp(name, "fuse_kernel")) { *value = h->last_fuse; return GVOM_OK; }                         // read-only, GVOM_ROUTE_*
     if (!strcmp(name, "encfuse_width")) { *value = h->last_encfuse[0]; return GVOM_OK; }                // read-only: sx per column block of the last k_encfuse (32 / 16; 0: none yet)
     if (!strcmp(name, "encfuse_waves")) { *value = h->last_encfuse[1]; return GVOM_OK; }                // read-only: its waves per column block
-    if (!strcmp(name, "device_map_sets")) { *value = (int)h->dsets.size(); return GVOM_OK; }             // read-only: allocated device map sets                  // read-only, GVOM_ROUTE_*
-    if (!strcmp(name, "clearance_allocations")) { *value = h->cl_allocs; return GVOM_OK; }              // read-only: device allocations gvom_clearance has made
+    if (!strcmp(name, "device_map_sets")) { *value = (int)h->dsets.size(); return GVOM_OK; }             // read-only: allocated device map sets
     static const char *const cl_names[4] = {"clearance_lgw", "clearance_rows_per_tile", "clearance_lds_bytes", "clearance_chunks"};
     for (int k = 0; k < 4; ++k)                                                                          // read-only: the launch shape of the last gvom_clearance
-        if (!strcmp(name, cl_names[k])) { *value = h->cl_shape[k]; return GVOM_OK; }
+        if (!strcmp(name, cl_names[k])) { *value = h->clearance.shape[k]; return GVOM_OK; }
     if (!strcmp(name, "raycast")) { *value = 1; return GVOM_OK; }                                       // read-only: the library has gvom_raycast
-    if (!strcmp(name, "raycast_allocations")) { *value = h->rq_allocs; return GVOM_OK; }                // read-only: device allocations gvom_raycast has made
     if (!strcmp(name, "cost_to_go")) { *value = 1; return GVOM_OK; }                                    // read-only: the library has gvom_cost_to_go
-    if (!strcmp(name, "cost_to_go_allocations")) { *value = h->ctg_allocs; return GVOM_OK; }            // read-only: device allocations gvom_cost_to_go has made
-    if (!strcmp(name, "cost_to_go_tiles")) { *value = h->ctg.last_tiles; return GVOM_OK; }              // read-only: tile relaxations of the last gvom_cost_to_go
-    if (!strcmp(name, "cost_to_go_inner")) { *value = h->ctg.tune_inner; return GVOM_OK; }
-    if (!strcmp(name, "cost_to_go_batch")) { *value = h->ctg.tune_batch; return GVOM_OK; }
     if (!strcmp(name, "rollouts")) { *value = 1; return GVOM_OK; }                                      // read-only: the library has gvom_score_rollouts
-    if (!strcmp(name, "footprint")) { *value = h->fp_H > 0 ? 1 : 0; return GVOM_OK; }                   // read-only: a footprint table is set
-    if (!strcmp(name, "rollout_allocations")) { *value = h->ro_allocs; return GVOM_OK; }                // read-only: device allocations gvom_score_rollouts has made
+    if (!strcmp(name, "footprint")) { *value = h->footprint.H > 0 ? 1 : 0; return GVOM_OK; }            // read-only: a footprint table is set
     if (!strcmp(name, "alignments")) { *value = 1; return GVOM_OK; }                                    // read-only: the library has gvom_score_alignments
     if (!strcmp(name, "attitude")) { *value = 1; return GVOM_OK; }                                      // read-only: the library has gvom_score_attitude
-    if (!strcmp(name, "chassis")) { *value = h->at_H > 0 ? 1 : 0; return GVOM_OK; }                     // read-only: a chassis is set
-    if (!strcmp(name, "attitude_allocations")) { *value = h->at_allocs; return GVOM_OK; }               // read-only: device allocations gvom_score_attitude has made
+    if (!strcmp(name, "chassis")) { *value = h->chassis.H > 0 ? 1 : 0; return GVOM_OK; }                // read-only: a chassis is set
     if (!strcmp(name, "body")) { *value = 1; return GVOM_OK; }                                          // read-only: the library has gvom_body_set and gvom_score_body
-    if (!strcmp(name, "body_spheres")) { *value = h->bd_S; return GVOM_OK; }                            // read-only: the spheres of the body table (0: none set)
-    if (!strcmp(name, "body_allocations")) { *value = h->bd_allocs; return GVOM_OK; }                   // read-only: device allocations gvom_body_set and gvom_score_body have made
+    if (!strcmp(name, "body_spheres")) { *value = h->body.S; return GVOM_OK; }                          // read-only: the spheres of the body table (0: none set)
     if (!strcmp(name, "frontiers")) { *value = 1; return GVOM_OK; }                                     // read-only: the library has gvom_frontiers
-    if (!strcmp(name, "frontier_allocations")) { *value = h->fr_allocs; return GVOM_OK; }               // read-only: device allocations gvom_frontiers has made
-    if (!strcmp(name, "frontier_rounds")) { *value = h->fr.last_rounds; return GVOM_OK; }               // read-only: rounds of the last gvom_frontiers
-    if (!strcmp(name, "frontier_tiles")) { *value = h->fr.last_tiles; return GVOM_OK; }                 // read-only: tile relaxations of the last gvom_frontiers
-    if (!strcmp(name, "frontier_inner")) { *value = h->fr.tune_inner; return GVOM_OK; }
-    if (!strcmp(name, "frontier_batch")) { *value = h->fr.tune_batch; return GVOM_OK; }
     if (!strcmp(name, "viewpoints")) { *value = 1; return GVOM_OK; }                                    // read-only: the library has gvom_score_viewpoints
-    if (!strcmp(name, "viewpoint_allocations")) { *value = h->vp_allocs; return GVOM_OK; }              // read-only: device allocations gvom_score_viewpoints has made
-    if (!strcmp(name, "viewpoint_batch")) { *value = h->vp_last_batch; return GVOM_OK; }                // read-only: viewpoints per launch of the last gvom_score_viewpoints
-    if (!strcmp(name, "viewpoint_bitmap_mb")) { *value = h->tune_vp_mb; return GVOM_OK; }
+    if (!strcmp(name, "viewpoint_batch")) { *value = h->viewpoints.last_batch; return GVOM_OK; }        // read-only: viewpoints per launch of the last gvom_score_viewpoints
+    if (!strcmp(name, "viewpoint_bitmap_mb")) { *value = h->viewpoints.mb; return GVOM_OK; }
     if (!strcmp(name, "pose_field")) { *value = 1; return GVOM_OK; }                                    // read-only: the library has gvom_pose_field
-    if (!strcmp(name, "primitives")) { *value = h->pf_H > 0 ? 1 : 0; return GVOM_OK; }                  // read-only: a primitive table is set
-    if (!strcmp(name, "pose_field_allocations")) { *value = h->pf_allocs; return GVOM_OK; }             // read-only: device allocations gvom_primitives_set / gvom_pose_field have made
-    if (!strcmp(name, "pose_field_rounds")) { *value = h->pf.last_rounds; return GVOM_OK; }             // read-only: rounds of the last gvom_pose_field
-    if (!strcmp(name, "pose_field_tiles")) { *value = h->pf.last_tiles; return GVOM_OK; }               // read-only: tile relaxations of the last gvom_pose_field
-    if (!strcmp(name, "pose_field_inner")) { *value = h->pf.tune_inner; return GVOM_OK; }
-    if (!strcmp(name, "pose_field_batch")) { *value = h->pf.tune_batch; return GVOM_OK; }
-    if (!strcmp(name, "atlas")) { *value = h->atl_A; return GVOM_OK; }                                   // read-only: the side of the configured atlas in cells, 0 without one
+    if (!strcmp(name, "primitives")) { *value = h->pose_field.H > 0 ? 1 : 0; return GVOM_OK; }          // read-only: a primitive table is set
+    if (!strcmp(name, "atlas")) { *value = h->atlas.A; return GVOM_OK; }                                 // read-only: the side of the configured atlas in cells, 0 without one
     if (!strcmp(name, "atlas_cost_to_go")) { *value = 1; return GVOM_OK; }                              // read-only: the library has gvom_atlas_cost_to_go and gvom_atlas_field_window
-    if (!strcmp(name, "atlas_field_allocations")) { *value = h->af_allocs; return GVOM_OK; }            // read-only: device allocations those two have made
-    if (!strcmp(name, "atlas_field_tiles")) { *value = h->af.last_tiles; return GVOM_OK; }              // read-only: tile relaxations of the last gvom_atlas_cost_to_go
     if (!strcmp(name, "atlas_frontiers")) { *value = 1; return GVOM_OK; }                               // read-only: the library has gvom_atlas_frontiers
-    if (!strcmp(name, "atlas_frontier_allocations")) { *value = h->afr_allocs; return GVOM_OK; }        // read-only: device allocations gvom_atlas_frontiers has made
-    if (!strcmp(name, "atlas_frontier_rounds")) { *value = h->afr.last_rounds; return GVOM_OK; }        // read-only: rounds of the last gvom_atlas_frontiers
-    if (!strcmp(name, "atlas_frontier_tiles")) { *value = h->afr.last_tiles; return GVOM_OK; }          // read-only: tile relaxations of the last gvom_atlas_frontiers
     if (!strcmp(name, "attitude_volume")) { *value = 1; return GVOM_OK; }                               // read-only: the library has gvom_attitude_volume and gvom_pose_field_attitude
-    if (!strcmp(name, "attitude_volume_allocations")) { *value = h->av_allocs; return GVOM_OK; }        // read-only: device allocations gvom_attitude_volume has made
     if (!strcmp(name, "body_volume")) { *value = 1; return GVOM_OK; }                                   // read-only: the library has gvom_body_volume and gvom_pose_field_volumes
-    if (!strcmp(name, "body_volume_allocations")) { *value = h->bv_allocs; return GVOM_OK; }            // read-only: device allocations gvom_body_volume has made
-    if (!strcmp(name, "atlas_allocations")) { *value = h->atl_allocs; return GVOM_OK; }                  // read-only: device allocations the gvom_atlas_* calls have made
-    if (!strcmp(name, "voxel_atlas")) { *value = h->va_A; return GVOM_OK; }                              // read-only: the side A of the configured voxel atlas, 0 without one
+    if (!strcmp(name, "voxel_atlas")) { *value = h->voxel_atlas.A; return GVOM_OK; }                     // read-only: the side A of the configured voxel atlas, 0 without one
     if (!strcmp(name, "voxel_atlas_alignments")) { *value = 1; return GVOM_OK; }                         // read-only: the library has gvom_voxel_atlas_score_alignments
-    if (!strcmp(name, "voxel_atlas_levels")) { *value = h->va_A ? h->va_Z : 0; return GVOM_OK; }         // read-only: its levels Z
-    if (!strcmp(name, "voxel_atlas_allocations")) { *value = h->va_allocs; return GVOM_OK; }             // read-only: device allocations the gvom_voxel_atlas_* calls have made
-    if (!strcmp(name, "voxel_atlas_viewpoint_batch")) { *value = h->va_last_batch; return GVOM_OK; }     // read-only: poses per launch of the last gvom_voxel_atlas_score_viewpoints
+    if (!strcmp(name, "voxel_atlas_levels")) { *value = h->voxel_atlas.A ? h->voxel_atlas.Z : 0; return GVOM_OK; }   // read-only: its levels Z
+    if (!strcmp(name, "voxel_atlas_viewpoint_batch")) { *value = h->voxel_atlas.last_batch; return GVOM_OK; }   // read-only: poses per launch of the last gvom_voxel_atlas_score_viewpoints
     if (!strcmp(name, "voxel_changes")) { *value = 1; return GVOM_OK; }                                  // read-only: the library has gvom_voxel_atlas_changes
     if (!strcmp(name, "voxel_distance_field")) { *value = 1; return GVOM_OK; }                          // read-only: the library has gvom_voxel_atlas_distance_field and gvom_voxel_distance_sample
-    if (!strcmp(name, "voxel_distance_mb")) { *value = h->tune_vd_mb; return GVOM_OK; }
-    if (!strcmp(name, "voxel_distance_halo_xy")) { *value = h->vd_halo[0]; return GVOM_OK; }             // read-only: Hxy of the last gvom_voxel_atlas_distance_field
-    if (!strcmp(name, "voxel_distance_halo_z")) { *value = h->vd_halo[1]; return GVOM_OK; }              // read-only: its Hz
-    if (!strcmp(name, "alignment_allocations")) { *value = h->al_allocs; return GVOM_OK; }              // read-only: device allocations gvom_score_alignments has made
-    if (!strcmp(name, "alignment_grid_bytes")) { *value = (int)(h->al_grid.bytes > 0x7fffffffu ? 0x7fffffffu : h->al_grid.bytes); return GVOM_OK; }   // read-only: the class grid's allocation
+    if (!strcmp(name, "voxel_distance_mb")) { *value = h->voxel_atlas.mb; return GVOM_OK; }
+    if (!strcmp(name, "voxel_distance_halo_xy")) { *value = h->voxel_atlas.halo[0]; return GVOM_OK; }    // read-only: Hxy of the last gvom_voxel_atlas_distance_field
+    if (!strcmp(name, "voxel_distance_halo_z")) { *value = h->voxel_atlas.halo[1]; return GVOM_OK; }     // read-only: its Hz
+    if (!strcmp(name, "alignment_grid_bytes")) { *value = (int)(h->alignment.grid.bytes > 0x7fffffffu ? 0x7fffffffu : h->alignment.grid.bytes); return GVOM_OK; }   // read-only: the class grid's allocation
     if (!strcmp(name, "alignment_points_per_block")) { *value = GVOM_ALIGN_PTS_BLOCK; return GVOM_OK; }  // read-only: returns per k_align_score workgroup
     if (!strcmp(name, "alignment_candidate_group")) { *value = GVOM_ALIGN_CAND_GROUP; return GVOM_OK; }  // read-only: candidates per k_align_score workgroup
     if (!strcmp(name, "device_product_sets")) { *value = (int)h->psets.size(); return GVOM_OK; }        // read-only: allocated device product sets (every kind)
@@ -641,7 +651,7 @@ VIS int gvom_get_tuning(gvom_t *h, const char *name, int *value)
     if (!strcmp(name, "output_records")) { *value = h->out_rec.size(); return GVOM_OK; }                // read-only: output buffers with a content record
     if (!strcmp(name, "multi_origin")) { *value = 1; return GVOM_OK; }                                  // read-only: the library has the multi-origin entry points
     if (!strcmp(name, "multi_origin_ran")) { *value = h->last_multi_origin; return GVOM_OK; }           // read-only: the last scan ran the per-lane-origin trace
-    if (!strcmp(name, "range_image")) { *value = h->ri_H > 0 ? 1 : 0; return GVOM_OK; }                 // read-only: a sensor model is set
+    if (!strcmp(name, "range_image")) { *value = h->range_image.H > 0 ? 1 : 0; return GVOM_OK; }        // read-only: a sensor model is set
     if (!strcmp(name, "fastdiv")) { *value = h->tune_fastdiv == 0 ? 0 : h->fastdiv_ok; return GVOM_OK; }   // bit 0 / 1: xy / z resolution divided by reciprocal
     return GVOM_ERR_INVALID;
 }

@@ -34,6 +34,34 @@ struct Buf {                                   // grow-only device buffer
     uint64_t gen = 0;                          // changes with every (re-)allocation (process-wide unique: gvom_region_generation)
 };
 
+// WHAT OWNS ITS MEMORY.  OwnedBuf is a Buf whose end frees it: ensure, ensure_keep and stage_buf take it as the Buf it is, and a
+// member of this type needs no line in gvom_destroy -- `delete h` gives it back.  Owned<T, Free> is the same for a typed pointer that
+// is allocated once where it is used (hipMalloc / hipHostMalloc into .p): DevPtr frees with hipFree, PinPtr -- pinned host memory --
+// with hipHostFree; `bytes` is for the owner that grows one (ensure_pinned).  All move-only.  Who frees by hand all the same (a
+// reconfigured atlas, the statistics' buffers) frees .p and sets it to null, as before.  NOT owning, on purpose: Slot and Fused (in
+// vectors, freed selectively), the exported send regions (parked, not freed) and DevSet (may outlive the handle).
+struct OwnedBuf : Buf {
+    OwnedBuf() = default;
+    OwnedBuf(OwnedBuf &&o) noexcept : Buf(o) { o.p = nullptr; o.bytes = 0; }
+    OwnedBuf &operator=(OwnedBuf &&o) noexcept { std::swap<Buf>(*this, o); return *this; }
+    OwnedBuf(const OwnedBuf &) = delete;
+    OwnedBuf &operator=(const OwnedBuf &) = delete;
+    ~OwnedBuf() { if (p) (void)hipFree(p); }
+};
+template <class T, hipError_t (*Free)(void *)> struct Owned {
+    T *p = nullptr;
+    size_t bytes = 0;
+    Owned() = default;
+    Owned(Owned &&o) noexcept : p(o.p), bytes(o.bytes) { o.p = nullptr; o.bytes = 0; }
+    Owned &operator=(Owned &&o) noexcept { std::swap(p, o.p); std::swap(bytes, o.bytes); return *this; }
+    Owned(const Owned &) = delete;
+    Owned &operator=(const Owned &) = delete;
+    ~Owned() { if (p) (void)Free((void *)p); }
+    operator T *() const { return p; }
+};
+template <class T> using DevPtr = Owned<T, hipFree>;
+template <class T> using PinPtr = Owned<T, hipHostFree>;
+
 struct Slot {                                  // one scan in sparse form
     int32_t *state = nullptr;                  // [V] storage order
     uint16_t *code16 = nullptr;                // [V] 16-bit codes of the same voxels (xy % 4 == 0 grids), read by k_fuse4
@@ -105,11 +133,194 @@ extern std::mutex g_set_mu;                               // (gvom_sets.hip)
 // tile relaxations of the last call (gvom_get_tuning "<call>_rounds" / "<call>_tiles").  The atlas forms run under the tuning of the
 // window's calls: their own is never set
 struct SolveWork {
-    Buf work;
-    uint32_t *pin = nullptr;
+    OwnedBuf work;
+    PinPtr<uint32_t> pin;
     int tune_inner = 0, tune_batch = 0;
     int last_rounds = 0, last_tiles = 0;
 };
+
+// WHAT A CALL KEEPS ON THE HANDLE, one record per call (struct gvom_handle has them by the calls' names).  The shared core is
+// CallState: the staging copy of the caller's host inputs, and the count of every device allocation the call's entry points have
+// made on this handle -- its buffers here and its product sets (gvom_get_tuning "<call>_allocations").  stage_buf, stage_host,
+// product_acquire and the fills of the walk queries take the record; a second buffer of the same record is passed beside it.  A
+// record adds only what its call really has: GroundCall the ground map of the map-set route (ground_reserve), SolveCall the work of a
+// call that waits (solve_work_reserve, frontier_work).  Every buffer is grow-only, allocated by the first call that needs it, and
+// owned: nothing here is freed by name.
+struct CallState {
+    OwnedBuf stage;
+    int allocs = 0;
+};
+struct GroundCall : CallState { OwnedBuf ground; };
+struct SolveCall : CallState { SolveWork solve; };
+
+// RANGE IMAGES (gvom_sensor_model_set / gvom_process_range_image): the sensor model in device memory -- [n][3] directions, then
+// [n][3] offsets, n = H * W -- and the staging buffers of host images and column poses.  k_unproject (gvom_ingest.hip)
+// turns an image into the cloud in in_pts, which the scan then reads like an uploaded host cloud
+struct RangeImageState {
+    OwnedBuf model, raw, poses;
+    // column poses go through a pinned staging copy: a second PAGEABLE upload per scan is a second staged, blocking copy of the
+    // runtime (m256, 196 KB of poses: +27 us per step); copied here by the calling thread and sent from pinned memory, the
+    // transfer is in flight while the image's own upload runs.  Free again once the scan's k_trace has completed, as in_pts is
+    PinPtr<void> poses_pin;
+    int32_t H = 0, W = 0;                               // 0: no model set
+    double scale = 0.0, min = 0.0, max = 0.0;
+    uint64_t gen = 0;                                   // counts the gvom_sensor_model_set calls (VoxelAtlasState::model_gen)
+};
+// MULTI-ORIGIN scans (gvom_process_pointcloud_origins / gvom_process_range_image_origins): the K x 3 float32 table of ray
+// origins in voxels, followed (host index) by the uint16 index of every return: ONE region in device memory, one pinned
+// staging copy the calling thread fills (as RangeImageState::poses_pin), one upload per scan, re-used across scans
+struct MultiOriginState {
+    OwnedBuf dev;
+    PinPtr<void> pin;
+};
+// CLEARANCE (gvom_clearance): g = the row pass's uint16 distances, stage = the staging copy of a caller's host maps, each allocated
+// by the first call that needs it; allocs counts every device allocation the entry point has made on this handle
+// (these two and its product sets: gvom_get_tuning "clearance_allocations")
+struct ClearanceCall : CallState {
+    OwnedBuf g;
+    int shape[4] = {0, 0, 0, 0};                        // the launch shape of the last gvom_clearance (gvom_get_tuning "clearance_lgw" ...), from gvom_launch_clearance
+};
+// RAY QUERIES (gvom_raycast): stage = the staging copy of a caller's host segments ([K][3] origins, then [n][3] end points), grown by
+// the first call that needs more; allocs counts every device allocation the entry point has made on this handle (this
+// buffer and its product sets: gvom_get_tuning "raycast_allocations")
+struct RaycastCall : CallState {};
+// COST-TO-GO FIELDS (gvom_cost_to_go): solve.work = goal_work() with goals of 2 int32; stage = the staging copy of a caller's
+// host cost map; clr = what gvom_launch_clearance needs for the inflation of the map-set route (its row scratch, a distance
+// map nobody reads, d2).  Each is allocated by the first call that needs it; allocs counts those and the entry point's product
+// sets (gvom_get_tuning "cost_to_go_allocations")
+struct CostToGoCall : SolveCall { OwnedBuf clr; };
+// ROLLOUT SCORING (gvom_footprint_set / gvom_score_rollouts): FootprintTable::tab = the footprint table in device memory -- start[H + 1]
+// int32, then at offs_at bytes (a multiple of 256) the offsets, 4 bytes each (dx low, dy high) --, total = its offsets and gen the
+// gvom_footprint_set calls so far; RolloutCall::stage = the staging
+// copy of a caller's host maps and poses; its allocs counts the device allocations gvom_score_rollouts has made on this handle
+// (stage and its product sets: gvom_get_tuning "rollout_allocations"; the table is in nobody's count)
+struct FootprintTable {
+    OwnedBuf tab;
+    size_t offs_at = 0;
+    int H = 0;                                          // 0: no footprint set
+    int total = 0;
+    uint64_t gen = 0;
+};
+struct RolloutCall : CallState {};
+// TERRAIN ATTITUDE SCORING (gvom_chassis_set / gvom_score_attitude): ChassisTable::tab = the chassis table in device memory -- the wheel
+// offsets [H][4][2] float64, then at cs_at bytes (a multiple of 256) cos_sin [H][2] float64 --, c the chassis itself and gen the
+// gvom_chassis_set calls so far; AttitudeCall::ground = the ground map
+// k_attitude_ground writes on the map-set route, stage = the staging copy of a caller's host ground map and poses; allocs
+// counts the device allocations gvom_score_attitude has made on this handle (ground, stage and its product sets:
+// gvom_get_tuning "attitude_allocations"; the table is in nobody's count)
+struct ChassisTable {
+    OwnedBuf tab;
+    size_t cs_at = 0;
+    int H = 0;                                          // 0: no chassis set
+    gvom_chassis_t c = {};
+    uint64_t gen = 0;
+};
+struct AttitudeCall : GroundCall {};
+// BODY CLEARANCE SCORING (gvom_body_set / gvom_score_body): tab = the sphere table in device memory, [256][4] float32 of which S
+// are set (0: no body), ground = the ground map k_attitude_ground writes on the map-set route, stage = the staging copy of a
+// caller's host field, ground map and poses; allocs counts the device allocations the two entry points have made on this handle
+// (the three and the product sets: gvom_get_tuning "body_allocations")
+struct BodyCall : GroundCall {
+    OwnedBuf tab;
+    int S = 0;
+};
+// SCAN ALIGNMENT SCORING (gvom_score_alignments): grid = the class grid k_align_field rebuilds in every call (2 bits per voxel,
+// gvom_align_grid_bytes: gvom_get_tuning "alignment_grid_bytes" reads what is allocated), stage = the staging copy of a caller's
+// host cloud and transforms; allocs counts the device allocations the entry point has made on this handle (the two and its product sets)
+struct AlignmentCall : CallState { OwnedBuf grid; };
+// FRONTIER EXTRACTION (gvom_frontiers): solve.work = fr_offsets() at the window's side; stage = the staging copy of a caller's host
+// maps.  Each is allocated by the first call that needs it; allocs counts those and the entry point's product sets
+// (gvom_get_tuning "frontier_allocations")
+struct FrontierCall : SolveCall {};
+// VIEWPOINT SCORING (gvom_score_viewpoints): bitmaps = one bitmap of the window's voxels per viewpoint of a batch, cleared on the
+// stream before every batch; at most mb megabytes ("viewpoint_bitmap_mb"; a bitmap that alone is larger makes batches of
+// one).  stage = the staging copy of a caller's host poses.  Each is allocated by the first call that needs it; allocs counts
+// those and the entry point's product sets (gvom_get_tuning "viewpoint_allocations"); last_batch: viewpoints per launch of the
+// last call ("viewpoint_batch", read-only)
+struct ViewpointCall : CallState {
+    OwnedBuf bitmaps;
+    int mb = GVOM_VIEWPOINT_DEFAULT_MB;
+    int last_batch = 0;
+};
+// POSE FIELDS (gvom_primitives_set / gvom_pose_field): tab = the primitive table in device memory -- start[H + 1] int32, then at
+// prims_at bytes (a multiple of 256) the primitives, 8 bytes each (int16 dx, dy, h_to, w) --, H its headings (0: none set) and
+// R its largest |dx|, |dy|: the halo of a tile.  solve.work = goal_work() with goals of 3 int32 and, as its tail,
+// the uint16 cost map converted from a caller's int32 one; stage = the staging copy of a caller's host cost map.  Each is allocated
+// by the first call that needs it; allocs counts those and the entry point's product sets (gvom_get_tuning "pose_field_allocations")
+struct PoseFieldCall : SolveCall {
+    OwnedBuf tab;
+    size_t prims_at = 0;
+    int H = 0, R = 0;
+};
+// MAP ATLAS (gvom_atlas_*): mem = the ten planes of A x A cells (gvom_internal.h "map atlas"; A == 0: none
+// configured), cnt = 256 bytes of int32 counters in device memory and pin their pinned copy for gvom_atlas_counts,
+// stage = the staging copy of a caller's nine host maps.  E = the extent's origin in world cells, seq = integrates so far,
+// last = the origin of the last integrated set (the default of a recall; z is what a recall reports).  allocs counts the
+// device allocations the entry points have made on this handle (gvom_get_tuning "atlas_allocations")
+struct AtlasState : CallState {
+    DevPtr<char> mem;
+    DevPtr<int32_t> cnt;
+    PinPtr<int32_t> pin;
+    int A = 0, follow = 1;
+    int64_t E[2] = {0, 0}, last[3] = {0, 0, 0};
+    int32_t seq = 0;
+};
+// ATLAS FIELDS (gvom_atlas_cost_to_go / gvom_atlas_field_window): the solver's buffers at the atlas's side A, apart from the
+// window-sized ones of gvom_cost_to_go -- solve.work = goal_work() at that side (the goals relative to the extent); clr = the
+// inflation's row distances (A*A uint16), a distance map nobody reads and d2 (A*A x 4 bytes each), allocated by the first call that
+// inflates.  allocs counts those and the two entry points' product sets (gvom_get_tuning "atlas_field_allocations").  No host
+// inputs: stage stays empty
+struct AtlasFieldCall : SolveCall { OwnedBuf clr; };
+// ATLAS FRONTIERS (gvom_atlas_frontiers): solve.work = gvom_frontiers' work buffer (fr_offsets) at the side of the FIELD the call was
+// given, 8 bytes per cell plus flags and counters -- apart from the window-sized one of FrontierCall, which an atlas call never touches.
+// allocs counts it and the entry point's product sets (gvom_get_tuning "atlas_frontier_allocations").  No host inputs: stage stays empty
+struct AtlasFrontierCall : SolveCall {};
+// VOXEL ATLAS (gvom_voxel_atlas_*): mem = the pairs of A x A x Z voxels (gvom_voxel_atlas.hip has the layout; A == 0: none
+// configured), cnt = 256 bytes of uint64 counters in device memory (gvom_internal.h VA_CNT_*) and pin their pinned copy for
+// gvom_voxel_atlas_counts; E = the extent's origin in world voxels, seq = integrates so far, last = the window origin of the last
+// integrate (the default of a box), outside / moved = counts [5] and [6] of the last integrate, which the host computes.  stage =
+// the staging copy of a caller's host segments or poses, with the viewpoints' boxes behind them; bitmaps = the viewpoints' bitmaps
+// under "viewpoint_bitmap_mb".  dmax / omax = the sensor model's largest finite |direction| and |offset| per axis, read back by the
+// first viewpoint call after a gvom_sensor_model_set (RangeImageState::gen counts those; model_gen says which model the two were made of).
+// allocs counts the device allocations the entry points have made on this handle (gvom_get_tuning "voxel_atlas_allocations"): ONE
+// counter and one stage buffer for the three walk queries, the distance field and the change query
+struct VoxelAtlasState : SolveCall {
+    DevPtr<unsigned long long> mem, cnt;
+    PinPtr<unsigned long long> pin;
+    OwnedBuf bitmaps;
+    int A = 0, Z = 0, follow = 1;
+    int64_t E[3] = {0, 0, 0}, last[3] = {0, 0, 0};
+    int64_t seq = 0, outside = 0, moved = 0;
+    double dmax[3] = {0, 0, 0}, omax[3] = {0, 0, 0};
+    uint64_t model_gen = 0;
+    int last_batch = 0;                                 // poses per launch of the last gvom_voxel_atlas_score_viewpoints ("voxel_atlas_viewpoint_batch", read-only)
+    // VOXEL DISTANCE FIELDS (gvom_voxel_atlas_distance_field): dist = the halo-grown intermediates of the x and y passes (gvom_internal.h
+    // VDistFrame), grow-only, counted in allocs, at most mb megabytes ("voxel_distance_mb"); halo = {Hxy, Hz} of the last
+    // call ("voxel_distance_halo_xy" / "_z", read-only)
+    OwnedBuf dist;
+    int mb = GVOM_VDIST_DEFAULT_MB;
+    int halo[2] = {0, 0};
+    // VOXEL ATLAS CHANGES (gvom_voxel_atlas_changes): solve.work = gvom_frontiers' work buffer (fr_offsets) at the window's side; chg = 256
+    // bytes of uint64 counters {appeared, vanished, outside}, then the bit planes (gvom_vchange_planes_bytes), the columns' level pairs
+    // and the distance plane, each 256-byte aligned; both grow-only and counted in allocs
+    OwnedBuf chg;
+};
+// ATTITUDE VOLUMES (gvom_attitude_volume): tab = what k_volume_attitude_table makes of the footprint table and the chassis --
+// (u - am, v) float64 pairs of every footprint cell, then at wcell_at bytes (a multiple of 256) per heading the wheels' cell offsets and the
+// footprint's box, [H][12] int32 --, rebuilt by the first call after a gvom_footprint_set / gvom_chassis_set (FootprintTable::gen / ChassisTable::gen count those; fp_gen
+// / at_gen say which pair the table was made of; FootprintTable::total = the offsets of the footprint table).  ground = the ground map of
+// the map-set route, stage = the staging copy of a caller's host ground map.  allocs counts the device allocations the entry
+// point has made on this handle (the three and its product sets: gvom_get_tuning "attitude_volume_allocations")
+struct AttitudeVolumeCall : GroundCall {
+    OwnedBuf tab;
+    size_t wcell_at = 0;
+    uint64_t fp_gen = 0, at_gen = 0;
+};
+// BODY VOLUMES (gvom_body_volume): the wheel offsets come from AttitudeVolumeCall::tab (rebuilt by the same rule, allocated once for both entry
+// points and counted in ITS allocs); ground = the ground map of the map-set route, stage = the staging copy of a caller's host
+// field and ground map.  allocs counts the device allocations the entry point has made on this handle (the two and its product
+// sets: gvom_get_tuning "body_volume_allocations")
+struct BodyVolumeCall : GroundCall {};
 }  // namespace gvom_host
 
 using namespace gvom_host;
@@ -165,7 +376,7 @@ struct gvom_handle {
     std::vector<int> ring;                              // ring position -> slots index
     int staging = 0;
     int buffer_index = 0, last_buffer_index = 0;
-    Buf in_pts, world_pts[2];                           // world_pts: the returns as k_trace stored them for k_stats, alternating per scan
+    OwnedBuf in_pts, world_pts[2];                      // world_pts: the returns as k_trace stored them for k_stats, alternating per scan
     uint32_t *counters = nullptr;                       // device: [0] scan rows, [2..3] fuse rows (u64)
     uint32_t *counters_host = nullptr;                  // pinned, device-mapped: kernels publish counts here
     uint32_t *counters_host_dev = nullptr;              // device view of counters_host
@@ -199,15 +410,15 @@ struct gvom_handle {
     // ... with per-voxel statistics: the speculative fusion's statistics half (k_fuse_stats on the statistics stream, behind the
     // scan's own k_stats / k_stats_gather) is enqueued with the scan too; what it needs of eager_launch's frame is kept here
     bool spec_has_metrics = false;                      // the speculative fused map will carry merged statistics
-    Buf flink[2];                                       // per fused buffer: link[fused row] = row in the previous map (k_encfuse -> k_fuse_stats)
+    OwnedBuf flink[2];                                  // per fused buffer: link[fused row] = row in the previous map (k_encfuse -> k_fuse_stats)
     bool fs_reads[2] = {false, false};                  // the pending k_fuse_stats reads fused[i]'s states / tile tags
     FuseParams spec_FP;
     FuseDescs spec_KD;
     // DIRECTIONAL ORDER of unordered clouds (k_dirbin_*, ScanParams::perm): "dirsort" 1 always, -1 never, 0 automatic -- when the
     // layout probe found no spatial order in the previous cloud of this length (BASELINE c1's 50,000 random points: k_trace 65 -> 16 us)
     int tune_dirsort = 0;
-    Buf dir_keys, dir_perm;                             // uint16 key / uint32 position -> return, per return
-    uint32_t *dir_hist = nullptr;                       // [3][GVOM_DIRBINS]: two histograms (alternating, zero between uses) + the bins' cursors
+    OwnedBuf dir_keys, dir_perm;                        // uint16 key / uint32 position -> return, per return
+    DevPtr<uint32_t> dir_hist;                          // [3][GVOM_DIRBINS]: two histograms (alternating, zero between uses) + the bins' cursors
     uint32_t dir_flip = 0;
     int last_dirsort = 0;                               // gvom_get_tuning "dirsort": the last scan ran in directional order
     int tune_encfuse = 0;                               // gvom_set_tuning "encfuse": A/B of k_encfuse's shape (low 4 bits: waves per block, bit 4: blocks in dispatch order, bit 5: the 16-sx form)
@@ -280,7 +491,7 @@ struct gvom_handle {
     int in_off[3] = {0, 1, 2};                          // element offsets of x, y, z in the cloud being scanned
     bool in_f32 = false;                                // float32 records widened to a float64 computation (PointCloud2 ingest)
 
-    Buf tl;                                             // diagnostic build: k_trace's timeline of the last scan (GVOM_TRACE_TIMELINE)
+    OwnedBuf tl;                                        // diagnostic build: k_trace's timeline of the last scan (GVOM_TRACE_TIMELINE)
     int tl_grid[2] = {0, 0};
     double host_ns[8] = {0, 0, 0, 0, 0, 0, 0, 0};       // host-side phase timing (GVOM_HOST_TIMING)
     long host_calls = 0;
@@ -306,166 +517,28 @@ struct gvom_handle {
     int tune_occ_clear = 0;                             // gvom_set_tuning "occupancy_clear": 1 = clear the grid, write live tile columns only (A/B)
     bool count_pending = false;                         // the last combine was a device combine: its fused cell count is read
     hipEvent_t ev_dcount = nullptr;                     //   from the host-mapped counter once this event (behind its k_map2d) has completed
-    // RANGE IMAGES (gvom_sensor_model_set / gvom_process_range_image): the sensor model in device memory -- [n][3] directions, then
-    // [n][3] offsets, n = ri_H * ri_W -- and the staging buffers of host images and column poses.  k_unproject (gvom_ingest.hip)
-    // turns an image into the cloud in in_pts, which the scan then reads like an uploaded host cloud
-    Buf ri_model, ri_raw, ri_poses;
-    // column poses go through a pinned staging copy: a second PAGEABLE upload per scan is a second staged, blocking copy of the
-    // runtime (m256, 196 KB of poses: +27 us per step); copied here by the calling thread and sent from pinned memory, the
-    // transfer is in flight while the image's own upload runs.  Free again once the scan's k_trace has completed, as in_pts is
-    void *ri_poses_pin = nullptr;
-    size_t ri_poses_pin_bytes = 0;
-    int32_t ri_H = 0, ri_W = 0;                         // 0: no model set
-    // MULTI-ORIGIN scans (gvom_process_pointcloud_origins / gvom_process_range_image_origins): the K x 3 float32 table of ray
-    // origins in voxels, followed (host index) by the uint16 index of every return: ONE region in device memory, one pinned
-    // staging copy the calling thread fills (as ri_poses_pin), one upload per scan, re-used across scans
-    Buf mo_dev;
-    void *mo_pin = nullptr;
-    size_t mo_pin_bytes = 0;
+    // WHAT THE CALLS KEEP, one record each (declared above, each with what it holds): the two ingest routes, then the product calls
+    RangeImageState range_image;
+    MultiOriginState multi_origin;
     int last_multi_origin = 0;                          // the last scan ran the per-lane-origin trace (gvom_get_tuning "multi_origin_ran")
-    double ri_scale = 0.0, ri_min = 0.0, ri_max = 0.0;
-    // CLEARANCE (gvom_clearance): the row pass's uint16 distances and the staging copy of a caller's host maps, each allocated
-    // by the first call that needs it; cl_allocs counts every device allocation the entry point has made on this handle
-    // (these two and its product sets: gvom_get_tuning "clearance_allocations")
-    Buf cl_g, cl_stage;
-    int cl_allocs = 0;
-    int cl_shape[4] = {0, 0, 0, 0};                     // the launch shape of the last gvom_clearance (gvom_get_tuning "clearance_lgw" ...), from gvom_launch_clearance
-    // RAY QUERIES (gvom_raycast): the staging copy of a caller's host segments ([K][3] origins, then [n][3] end points), grown by
-    // the first call that needs more; rq_allocs counts every device allocation the entry point has made on this handle (this
-    // buffer and its product sets: gvom_get_tuning "raycast_allocations")
-    Buf rq_stage;
-    int rq_allocs = 0;
-    // COST-TO-GO FIELDS (gvom_cost_to_go): ctg.work = goal_work() with goals of 2 int32; ctg_stage = the staging copy of a caller's
-    // host cost map; ctg_clr = what gvom_launch_clearance needs for the inflation of the map-set route (its row scratch, a distance
-    // map nobody reads, d2).  Each is allocated by the first call that needs it; ctg_allocs counts those and the entry point's product
-    // sets (gvom_get_tuning "cost_to_go_allocations")
-    SolveWork ctg;
-    Buf ctg_stage, ctg_clr;
-    int ctg_allocs = 0;
-    // ROLLOUT SCORING (gvom_footprint_set / gvom_score_rollouts): fp_tab = the footprint table in device memory -- start[H + 1]
-    // int32, then at fp_offs_at bytes (a multiple of 256) the offsets, 4 bytes each (dx low, dy high) -- and ro_stage = the staging
-    // copy of a caller's host maps and poses; ro_allocs counts the device allocations gvom_score_rollouts has made on this handle
-    // (ro_stage and its product sets: gvom_get_tuning "rollout_allocations")
-    Buf fp_tab, ro_stage;
-    size_t fp_offs_at = 0;
-    int fp_H = 0;                                       // 0: no footprint set
-    int ro_allocs = 0;
-    // TERRAIN ATTITUDE SCORING (gvom_chassis_set / gvom_score_attitude): at_tab = the chassis table in device memory -- the wheel
-    // offsets [H][4][2] float64, then at at_cs_at bytes (a multiple of 256) cos_sin [H][2] float64 --, at_ground = the ground map
-    // k_attitude_ground writes on the map-set route, at_stage = the staging copy of a caller's host ground map and poses; at_allocs
-    // counts the device allocations gvom_score_attitude has made on this handle (at_ground, at_stage and its product sets:
-    // gvom_get_tuning "attitude_allocations")
-    Buf at_tab, at_ground, at_stage;
-    size_t at_cs_at = 0;
-    int at_H = 0;                                       // 0: no chassis set
-    gvom_chassis_t at_chassis = {};
-    int at_allocs = 0;
-    // BODY CLEARANCE SCORING (gvom_body_set / gvom_score_body): bd_tab = the sphere table in device memory, [256][4] float32 of which bd_S
-    // are set (0: no body), bd_ground = the ground map k_attitude_ground writes on the map-set route, bd_stage = the staging copy of a
-    // caller's host field, ground map and poses; bd_allocs counts the device allocations the two entry points have made on this handle
-    // (the three and the product sets: gvom_get_tuning "body_allocations")
-    Buf bd_tab, bd_ground, bd_stage;
-    int bd_S = 0;
-    int bd_allocs = 0;
-    // SCAN ALIGNMENT SCORING (gvom_score_alignments): al_grid = the class grid k_align_field rebuilds in every call (2 bits per voxel,
-    // gvom_align_grid_bytes: gvom_get_tuning "alignment_grid_bytes" reads what is allocated), al_stage = the staging copy of a caller's
-    // host cloud and transforms; al_allocs counts the device allocations the entry point has made on this handle (the two and its product sets)
-    Buf al_grid, al_stage;
-    int al_allocs = 0;
-    // FRONTIER EXTRACTION (gvom_frontiers): fr.work = fr_offsets() at the window's side; fr_stage = the staging copy of a caller's host
-    // maps.  Each is allocated by the first call that needs it; fr_allocs counts those and the entry point's product sets
-    // (gvom_get_tuning "frontier_allocations")
-    SolveWork fr;
-    Buf fr_stage;
-    int fr_allocs = 0;
-    // VIEWPOINT SCORING (gvom_score_viewpoints): vp_bitmaps = one bitmap of the window's voxels per viewpoint of a batch, cleared on the
-    // stream before every batch; at most tune_vp_mb megabytes ("viewpoint_bitmap_mb"; a bitmap that alone is larger makes batches of
-    // one).  vp_stage = the staging copy of a caller's host poses.  Each is allocated by the first call that needs it; vp_allocs counts
-    // those and the entry point's product sets (gvom_get_tuning "viewpoint_allocations"); vp_last_batch: viewpoints per launch of the
-    // last call ("viewpoint_batch", read-only)
-    Buf vp_bitmaps, vp_stage;
-    int vp_allocs = 0;
-    int tune_vp_mb = GVOM_VIEWPOINT_DEFAULT_MB;
-    int vp_last_batch = 0;
-    // POSE FIELDS (gvom_primitives_set / gvom_pose_field): pf_tab = the primitive table in device memory -- start[H + 1] int32, then at
-    // pf_prims_at bytes (a multiple of 256) the primitives, 8 bytes each (int16 dx, dy, h_to, w) --, pf_H its headings (0: none set) and
-    // pf_R its largest |dx|, |dy|: the halo of a tile.  pf.work = goal_work() with goals of 3 int32 and, as its tail,
-    // the uint16 cost map converted from a caller's int32 one; pf_stage = the staging copy of a caller's host cost map.  Each is allocated
-    // by the first call that needs it; pf_allocs counts those and the entry point's product sets (gvom_get_tuning "pose_field_allocations")
-    SolveWork pf;
-    Buf pf_tab, pf_stage;
-    size_t pf_prims_at = 0;
-    int pf_H = 0, pf_R = 0;
-    int pf_allocs = 0;
-    // MAP ATLAS (gvom_atlas_*): atl_mem = the ten planes of atl_A x atl_A cells (gvom_internal.h "map atlas"; atl_A == 0: none
-    // configured), atl_cnt = 256 bytes of int32 counters in device memory and atl_pin their pinned copy for gvom_atlas_counts,
-    // atl_stage = the staging copy of a caller's nine host maps.  atl_E = the extent's origin in world cells, atl_seq = integrates so far,
-    // atl_last = the origin of the last integrated set (the default of a recall; z is what a recall reports).  atl_allocs counts the
-    // device allocations the entry points have made on this handle (gvom_get_tuning "atlas_allocations")
-    char *atl_mem = nullptr;
-    int32_t *atl_cnt = nullptr, *atl_pin = nullptr;
-    Buf atl_stage;
-    int atl_A = 0, atl_follow = 1;
-    int64_t atl_E[2] = {0, 0}, atl_last[3] = {0, 0, 0};
-    int32_t atl_seq = 0;
-    int atl_allocs = 0;
-    // ATLAS FIELDS (gvom_atlas_cost_to_go / gvom_atlas_field_window): the solver's buffers at the atlas's side A, apart from the
-    // window-sized ones of gvom_cost_to_go -- af.work = goal_work() at that side (the goals relative to the extent); af_clr = the
-    // inflation's row distances (A*A uint16), a distance map nobody reads and d2 (A*A x 4 bytes each), allocated by the first call that
-    // inflates.  af_allocs counts those and the two entry points' product sets (gvom_get_tuning "atlas_field_allocations")
-    SolveWork af;
-    Buf af_clr;
-    int af_allocs = 0;
-    // ATLAS FRONTIERS (gvom_atlas_frontiers): afr.work = gvom_frontiers' work buffer (fr_offsets) at the side of the FIELD the call was
-    // given, 8 bytes per cell plus flags and counters -- apart from the window-sized fr.work, which an atlas call never touches.
-    // afr_allocs counts it and the entry point's product sets (gvom_get_tuning "atlas_frontier_allocations")
-    SolveWork afr;
-    int afr_allocs = 0;
-    // VOXEL ATLAS (gvom_voxel_atlas_*): va_mem = the pairs of va_A x va_A x va_Z voxels (gvom_voxel_atlas.hip has the layout; va_A == 0: none
-    // configured), va_cnt = 256 bytes of uint64 counters in device memory (gvom_internal.h VA_CNT_*) and va_pin their pinned copy for
-    // gvom_voxel_atlas_counts; va_E = the extent's origin in world voxels, va_seq = integrates so far, va_last = the window origin of the last
-    // integrate (the default of a box), va_outside / va_moved = counts [5] and [6] of the last integrate, which the host computes.  va_stage =
-    // the staging copy of a caller's host segments or poses, with the viewpoints' boxes behind them; va_bitmaps = the viewpoints' bitmaps
-    // under "viewpoint_bitmap_mb".  va_dmax / va_omax = the sensor model's largest finite |direction| and |offset| per axis, read back by the
-    // first viewpoint call after a gvom_sensor_model_set (ri_gen counts those; va_model_gen says which model the two were made of).
-    // va_allocs counts the device allocations the entry points have made on this handle (gvom_get_tuning "voxel_atlas_allocations")
-    unsigned long long *va_mem = nullptr, *va_cnt = nullptr, *va_pin = nullptr;
-    Buf va_stage, va_bitmaps;
-    int va_A = 0, va_Z = 0, va_follow = 1;
-    int64_t va_E[3] = {0, 0, 0}, va_last[3] = {0, 0, 0};
-    int64_t va_seq = 0, va_outside = 0, va_moved = 0;
-    double va_dmax[3] = {0, 0, 0}, va_omax[3] = {0, 0, 0};
-    uint64_t ri_gen = 0, va_model_gen = 0;
-    int va_allocs = 0;
-    int va_last_batch = 0;                              // poses per launch of the last gvom_voxel_atlas_score_viewpoints ("voxel_atlas_viewpoint_batch", read-only)
-    // VOXEL DISTANCE FIELDS (gvom_voxel_atlas_distance_field): va_dist = the halo-grown intermediates of the x and y passes (gvom_internal.h
-    // VDistFrame), grow-only, counted in va_allocs, at most tune_vd_mb megabytes ("voxel_distance_mb"); vd_halo = {Hxy, Hz} of the last
-    // call ("voxel_distance_halo_xy" / "_z", read-only)
-    Buf va_dist;
-    int tune_vd_mb = GVOM_VDIST_DEFAULT_MB;
-    int vd_halo[2] = {0, 0};
-    // VOXEL ATLAS CHANGES (gvom_voxel_atlas_changes): vchg.work = gvom_frontiers' work buffer (fr_offsets) at the window's side; va_chg = 256
-    // bytes of uint64 counters {appeared, vanished, outside}, then the bit planes (gvom_vchange_planes_bytes), the columns' level pairs
-    // and the distance plane, each 256-byte aligned; both grow-only and counted in va_allocs
-    SolveWork vchg;
-    Buf va_chg;
-    // ATTITUDE VOLUMES (gvom_attitude_volume): av_tab = what k_volume_attitude_table makes of the footprint table and the chassis --
-    // (u - am, v) float64 pairs of every footprint cell, then at av_wcell_at bytes (a multiple of 256) per heading the wheels' cell offsets and the
-    // footprint's box, [H][12] int32 --, rebuilt by the first call after a gvom_footprint_set / gvom_chassis_set (fp_gen / at_gen count those; av_fp_gen
-    // / av_at_gen say which pair the table was made of; fp_total = the offsets of the footprint table).  av_ground = the ground map of
-    // the map-set route, av_stage = the staging copy of a caller's host ground map.  av_allocs counts the device allocations the entry
-    // point has made on this handle (the three and its product sets: gvom_get_tuning "attitude_volume_allocations")
-    Buf av_tab, av_ground, av_stage;
-    size_t av_wcell_at = 0;
-    uint64_t fp_gen = 0, at_gen = 0, av_fp_gen = 0, av_at_gen = 0;
-    int fp_total = 0;
-    int av_allocs = 0;
-    // BODY VOLUMES (gvom_body_volume): the wheel offsets come from av_tab (rebuilt by the same rule, allocated once for both entry
-    // points and counted in av_allocs); bv_ground = the ground map of the map-set route, bv_stage = the staging copy of a caller's host
-    // field and ground map.  bv_allocs counts the device allocations the entry point has made on this handle (the two and its product
-    // sets: gvom_get_tuning "body_volume_allocations")
-    Buf bv_ground, bv_stage;
-    int bv_allocs = 0;
+    ClearanceCall clearance;
+    RaycastCall raycast;
+    CostToGoCall cost_to_go;
+    FootprintTable footprint;
+    RolloutCall rollouts;
+    ChassisTable chassis;
+    AttitudeCall attitude;
+    BodyCall body;
+    AlignmentCall alignment;
+    FrontierCall frontiers;
+    ViewpointCall viewpoints;
+    PoseFieldCall pose_field;
+    AtlasState atlas;
+    AtlasFieldCall atlas_field;
+    AtlasFrontierCall atlas_frontiers;
+    VoxelAtlasState voxel_atlas;
+    AttitudeVolumeCall attitude_volume;
+    BodyVolumeCall body_volume;
 };
 
 namespace gvom_host {
@@ -536,7 +609,7 @@ int settle_count(gvom_handle *h);
 void set_free(DevSet *s);
 DevSet *find_set(const std::vector<DevSet *> &sets, int64_t set_id);
 int set_wait_releases(gvom_handle *h, DevSet *set);
-int product_acquire(gvom_handle *h, int kind, size_t need_bytes, size_t new_bytes, const char *fn, int *allocs, DevSet **set);
+int product_acquire(gvom_handle *h, int kind, size_t need_bytes, size_t new_bytes, const char *fn, CallState *call, DevSet **set);   // (call: whose allocs a new set counts in; null: nobody's)
 int product_publish(gvom_handle *h, DevSet *set, int64_t *product_id);
 int map_set_acquire(gvom_handle *h, const char *fn, DevSet **set);
 // gvom_product_calls.hip
@@ -563,20 +636,21 @@ template <class P> inline void metric_frame(const gvom_handle *h, const Fused &F
     for (int k = 0; k < 3; ++k) p.origin[k] = (double)F.origin[k];
 }
 
-// grows a buffer of the handle to at least `bytes`; an allocation counts in `allocs`
-inline int stage_buf(gvom_handle *h, Buf &b, size_t bytes, int &allocs)
+// grows buffer `b` of the call's record to at least `bytes`; an allocation counts in the record.  Without `b`: the record's stage buffer
+inline int stage_buf(gvom_handle *h, CallState &call, Buf &b, size_t bytes)
 {
     if (b.bytes >= bytes) return GVOM_OK;
     const int rc = ensure(h, b, bytes);
-    allocs += rc ? 0 : 1;
+    call.allocs += rc ? 0 : 1;
     return rc;
 }
+inline int stage_buf(gvom_handle *h, CallState &call, size_t bytes) { return stage_buf(h, call, call.stage, bytes); }
 
-// HOST INPUTS: the present ones of `n` parts (src null: absent) copied into `b`, grown as stage_buf does, each but the last listed
+// HOST INPUTS: the present ones of `n` parts (src null: absent) copied into the call's stage buffer, grown as stage_buf does, each but the last listed
 // padded to 256 bytes; dev[i] = where part i went (null: absent).  sync: the call returns with the copies done (the caller's arrays
 // are free again); otherwise they are in flight on the handle's stream, as a call that waits anyway leaves them
 struct HostPart { const void *src; size_t bytes; };
-int stage_host(gvom_handle *h, Buf &b, int &allocs, const HostPart *parts, int n, bool sync, const void **dev);
+int stage_host(gvom_handle *h, CallState &call, const HostPart *parts, int n, bool sync, const void **dev);
 
 // THE ARGUMENT CHECKS.  refuse: h->err = fn + ": " + what, and the code.  The others are what more than one entry point checks: each
 // refuses in fn's name and returns the code, or GVOM_OK.  A caller keeps the order its checks always had: these fold only runs of
@@ -600,7 +674,7 @@ int ctg_cost_params(gvom_handle *h, const char *fn, const gvom_ctg_params *param
 struct SolveRounds { bool converged = false; int64_t rounds = 0, tiles = 0; };
 template <class Enqueue> int solve_rounds(gvom_handle *h, uint32_t *cnt, uint32_t *fl, uint32_t *pin, int ntiles, int batch, int64_t limit,
                                           Enqueue enqueue, SolveRounds *out);
-int solve_work_reserve(gvom_handle *h, SolveWork &w, size_t bytes, int &allocs);     // a work buffer of at least `bytes`, and the pinned counters
+int solve_work_reserve(gvom_handle *h, SolveCall &call, size_t bytes);     // a work buffer of at least `bytes` in call.solve, and the pinned counters
 // the goal solvers (gvom_cost_to_go, gvom_atlas_cost_to_go, gvom_pose_field): the parts of their work buffer, the goals sent up and
 // the counters cleared on the stream, and -- behind the solve -- the epilogue: the set published, the counters fetched, a solve that
 // did not settle under max_rounds == 0 retracted in fn's name, info and w.last_* filled
@@ -618,18 +692,18 @@ int goal_solve_finish(gvom_handle *h, const char *fn, SolveWork &w, DevSet *set,
 int ctg_solve(gvom_handle *h, SolveWork &w, const GoalWorkPtrs &G, int n, const int32_t *cost32, uint16_t *c16, int32_t *D, uint8_t *dir,
               int n_goals, int32_t max_cost, int32_t max_rounds, SolveRounds *out);
 // the part of gvom_frontiers that gvom_atlas_frontiers shares: everything around the marking kernel.  frontier_work: the work buffer
-// for n x n cells (fr_offsets) reserved in w, and its parts; the caller clears the first clear_bytes -- counters and flags -- on the
+// for n x n cells (fr_offsets) reserved in call.solve, and its parts; the caller clears the first clear_bytes -- counters and flags -- on the
 // stream, waits for its set's releases and marks.  frontier_solve: the rows' initialisation, the rounds under gvom_frontiers' tuning,
 // the finish, the set's publication, info and w.last_*; errors are in fn's name.  It waits.  `more` (gvom_voxel_atlas_changes' part 4;
 // empty for the frontier calls) is enqueued behind the finish and in front of the publication: what it writes is part of the product.
 struct FrWork { uint32_t *cnt, *fl, *bc, *L, *count; size_t clear_bytes; };
-int frontier_work(gvom_handle *h, SolveWork &w, int n, int &allocs, FrWork *W);
+int frontier_work(gvom_handle *h, SolveCall &call, int n, FrWork *W);
 int frontier_solve(gvom_handle *h, const char *fn, SolveWork &w, int n, const int32_t *D, const FrWork &W, int32_t min_cells,
                    int32_t max_clusters, DevSet *set, int64_t *product_id, int64_t info[4], const std::function<hipError_t()> &more = {});
 
 // THE WALK QUERIES -- rays, viewpoints, alignments -- against the fused window (gvom_product_calls.hip) and against the voxel atlas
-// (gvom_voxel_atlas_calls.hip): what the two members of a pair do alike.  A caller keeps its own product kind, stage buffer, alloc
-// counter, frame (raycast_params / walk_frame), launches and the one limit only it has, in the order they always had.
+// (gvom_voxel_atlas_calls.hip): what the two members of a pair do alike.  A caller keeps its own product kind, record (stage buffer
+// and alloc counter), frame (raycast_params / walk_frame), launches and the one limit only it has, in the order they always had.
 //   rays         check_rays; rays_fill: everything of Q but lit and cap, which the frame gave, the join of the second stream, and host
 //                segments staged, up before it returns, with Q pointed at them
 //   viewpoints   check_views: the checks up to the beam limits, with the beam counts as it leaves them; `span` = side + levels of what
@@ -640,7 +714,7 @@ int frontier_solve(gvom_handle *h, const char *fn, SolveWork &w, int n, const in
 //   alignments   check_align: the checks and the class grid's size (*grid_bytes); align_fill: everything of P but its frame, the join
 //                of the second stream, and host transforms and cloud staged, up before it returns (*cdev, *tdev: where the kernels read)
 int check_rays(gvom_handle *h, const char *fn, const float *from, int64_t K, const float *to, int64_t n, int flags);
-int rays_fill(gvom_handle *h, Buf &stage, int &allocs, const float *from, int64_t K, const float *to, int64_t n, int on_device, int flags, RayQuery &Q);
+int rays_fill(gvom_handle *h, CallState &call, const float *from, int64_t K, const float *to, int64_t n, int on_device, int flags, RayQuery &Q);
 struct ViewBeams { int64_t nh, nw, nb; };
 int check_views(gvom_handle *h, const char *fn, const double *poses, int64_t K, double max_range, int32_t stride_h, int32_t stride_w, int flags,
                 int64_t span, const char *spans, ViewBeams *B);
@@ -651,6 +725,6 @@ int views_run(gvom_handle *h, Buf &bitmaps, ViewQuery &Q, int64_t batch, int32_t
               const std::function<hipError_t()> &launch_best);
 int check_align(gvom_handle *h, const char *fn, const float *cloud, int64_t n, const double *transforms, int64_t K, int dilate, const int32_t weights[5],
                 size_t *grid_bytes);
-int align_fill(gvom_handle *h, Buf &stage, int &allocs, const float *cloud, int64_t n, const double *transforms, int64_t K, int on_device, int dilate,
+int align_fill(gvom_handle *h, CallState &call, const float *cloud, int64_t n, const double *transforms, int64_t K, int on_device, int dilate,
                const int32_t weights[5], AlignParams &P, const float **cdev, const double **tdev);
 }  // namespace gvom_host

@@ -58,8 +58,8 @@ hipError_t launch_height_cloud(gvom_handle *h, const Fused &F, float *out7, floa
 static void rollout_frame(const gvom_handle *h, int64_t K, int64_t T, const int64_t origin_cells[2], RolloutParams &R)
 {
     memset(&R, 0, sizeof R);
-    R.xy = h->prm.xy_size; R.H = h->fp_H; R.T = (int)T; R.K = K;
-    R.s = (float)((double)h->fp_H / 6.283185307179586476925286766559);
+    R.xy = h->prm.xy_size; R.H = h->footprint.H; R.T = (int)T; R.K = K;
+    R.s = (float)((double)h->footprint.H / 6.283185307179586476925286766559);
     R.ox = origin_cells[0]; R.oy = origin_cells[1];
     R.res = h->prm.xy_resolution;
 }
@@ -78,23 +78,23 @@ static int product_of_kind(gvom_handle *h, const char *fn, int64_t id, int kind,
 static int check_standing(gvom_handle *h, const char *fn, bool volume)
 {
     if (h->sharded) return refuse(h, fn, "sharded handles are not supported");
-    if (h->fp_H < 1) return refuse(h, fn, "no footprint table is set (gvom_footprint_set)");
-    if (h->at_H < 1) return refuse(h, fn, "no chassis is set (gvom_chassis_set)");
-    if (volume && h->fp_H > GVOM_POSE_MAX_HEADINGS) return refuse(h, fn, "footprint tables of more than 64 headings are not supported", GVOM_ERR_CAPACITY);
-    if (h->at_H != h->fp_H) return refuse(h, fn, "the chassis was set for another number of headings than the footprint table has");
+    if (h->footprint.H < 1) return refuse(h, fn, "no footprint table is set (gvom_footprint_set)");
+    if (h->chassis.H < 1) return refuse(h, fn, "no chassis is set (gvom_chassis_set)");
+    if (volume && h->footprint.H > GVOM_POSE_MAX_HEADINGS) return refuse(h, fn, "footprint tables of more than 64 headings are not supported", GVOM_ERR_CAPACITY);
+    if (h->chassis.H != h->footprint.H) return refuse(h, fn, "the chassis was set for another number of headings than the footprint table has");
     return GVOM_OK;
 }
 static int check_states(gvom_handle *h, const char *fn, int64_t H, int64_t xy) { return H * xy * xy > GVOM_POSE_MAX_STATES ? refuse(h, fn, "more than 2^28 states (headings x xy_size^2)", GVOM_ERR_CAPACITY) : GVOM_OK; }
 
 // THE GROUND a call reads: the caller's map (a staged host map takes dev over), or a map set's, which k_attitude_ground writes into the
-// call's own grow-only buffer.  ground_reserve, in front of the call's uploads: room for it, counted in the call's allocs;
+// call's own grow-only buffer.  ground_reserve, in front of the call's uploads: room for it in the call's record, counted there;
 // ground_write, behind the call's set_wait_releases: the pass itself, on the handle's stream
 struct Ground { DevSet *m = nullptr; double *own = nullptr; const double *dev = nullptr; };
-static int ground_reserve(gvom_handle *h, Ground &g, Buf &buf, int &allocs, const double *ground)
+static int ground_reserve(gvom_handle *h, Ground &g, GroundCall &call, const double *ground)
 {
     const size_t xy = (size_t)h->prm.xy_size;
-    if (const int rc = g.m ? stage_buf(h, buf, xy * xy * 8, allocs) : GVOM_OK) return rc;
-    g.own = g.m ? (double *)buf.p : nullptr;
+    if (const int rc = g.m ? stage_buf(h, call, call.ground, xy * xy * 8) : GVOM_OK) return rc;
+    g.own = g.m ? (double *)call.ground.p : nullptr;
     g.dev = g.m ? g.own : ground;
     return GVOM_OK;
 }
@@ -122,7 +122,7 @@ static int field_of(gvom_handle *h, const char *fn, int64_t id, const int64_t or
 // the chassis as AttitudeParams, AttitudeVolumeParams and BodyParams take it: the lengths (axle_mid where the params have one), the limits
 static void chassis_lengths(const gvom_handle *h, double &wheelbase, double &track, double *axle_mid)
 {
-    const gvom_chassis_t &c = h->at_chassis;
+    const gvom_chassis_t &c = h->chassis.c;
     wheelbase = c.front_axle - c.rear_axle; track = c.track;
     if (axle_mid) *axle_mid = 0.5 * (c.front_axle + c.rear_axle);
 }
@@ -134,7 +134,7 @@ static void body_params(const gvom_handle *h, const Field &F, float min_margin, 
     chassis_lengths(h, P.wheelbase, P.track, &P.axle_mid);
     P.z_res = h->prm.z_resolution;
     P.bx = F.B[0]; P.by = F.B[1]; P.bz = F.B[2];
-    P.n = F.n; P.zs = F.zs; P.S = h->bd_S; P.min_margin = min_margin;
+    P.n = F.n; P.zs = F.zs; P.S = h->body.S; P.min_margin = min_margin;
 }
 
 int check_one_source(gvom_handle *h, const char *fn, bool id, bool also, bool missing, const char *by_id, const char *both, const char *other)
@@ -182,7 +182,7 @@ int check_rays(gvom_handle *h, const char *fn, const float *from, int64_t K, con
     return GVOM_OK;
 }
 
-int rays_fill(gvom_handle *h, Buf &stage, int &allocs, const float *from, int64_t K, const float *to, int64_t n, int on_device, int flags, RayQuery &Q)
+int rays_fill(gvom_handle *h, CallState &call, const float *from, int64_t K, const float *to, int64_t n, int on_device, int flags, RayQuery &Q)
 {
     Q.from = from; Q.to = to; Q.n = (long)n;
     Q.one_origin = K == 1 ? 1 : 0;
@@ -192,7 +192,7 @@ int rays_fill(gvom_handle *h, Buf &stage, int &allocs, const float *from, int64_
     if (on_device) return GVOM_OK;
     const HostPart parts[2] = {{from, (size_t)K * 12}, {to, (size_t)n * 12}};                // host segments: staged, and up before the call returns
     const void *dev[2];
-    if (const int rc = stage_host(h, stage, allocs, parts, 2, true, dev)) return rc;
+    if (const int rc = stage_host(h, call, parts, 2, true, dev)) return rc;
     Q.from = (const float *)dev[0]; Q.to = (const float *)dev[1];
     return GVOM_OK;
 }
@@ -201,13 +201,13 @@ int check_views(gvom_handle *h, const char *fn, const double *poses, int64_t K, 
                 int64_t span, const char *spans, ViewBeams *B)
 {
     if (!poses) return refuse(h, fn, "poses must not be NULL");
-    if (h->ri_H <= 0) return refuse(h, fn, "no sensor model (gvom_sensor_model_set)");
+    if (h->range_image.H <= 0) return refuse(h, fn, "no sensor model (gvom_sensor_model_set)");
     if (K < 1) return refuse(h, fn, "K must be at least 1");
     if (stride_h < 1 || stride_w < 1) return refuse(h, fn, "the beam strides must be at least 1");
     if (!std::isfinite(max_range) || !(max_range > 0.0)) return refuse(h, fn, "max_range must be finite and > 0");
     if (flags & ~GVOM_RAY_UNKNOWN_BLOCKS) return refuse(h, fn, "unknown flag bits");
     if (K > GVOM_VIEWPOINT_MAX_POSES) return refuse(h, fn, "more than 65536 viewpoints in one call", GVOM_ERR_CAPACITY);
-    B->nh = ((int64_t)h->ri_H + stride_h - 1) / stride_h; B->nw = ((int64_t)h->ri_W + stride_w - 1) / stride_w; B->nb = B->nh * B->nw;
+    B->nh = ((int64_t)h->range_image.H + stride_h - 1) / stride_h; B->nw = ((int64_t)h->range_image.W + stride_w - 1) / stride_w; B->nb = B->nh * B->nw;
     if (B->nb > GVOM_VIEWPOINT_MAX_BEAMS) return refuse(h, fn, "more than 2^22 selected beams", GVOM_ERR_CAPACITY);
     if (B->nb * (span + 1) >= ((int64_t)1 << 31)) return refuse(h, fn, std::string("beams x (") + spans + " + 1) reaches 2^31", GVOM_ERR_CAPACITY);
     return GVOM_OK;
@@ -216,7 +216,7 @@ int check_views(gvom_handle *h, const char *fn, const double *poses, int64_t K, 
 int64_t views_batch(const gvom_handle *h, int64_t bits, int64_t K, size_t *bm_words)
 {
     *bm_words = (((size_t)bits + 31) / 32 + 63) & ~(size_t)63;                  // whole 256-byte lines
-    const int64_t batch = (int64_t)(((size_t)h->tune_vp_mb << 20) / (*bm_words * 4));
+    const int64_t batch = (int64_t)(((size_t)h->viewpoints.mb << 20) / (*bm_words * 4));
     return std::max<int64_t>(1, std::min<int64_t>(batch, std::min<int64_t>(K, GVOM_VIEWPOINT_MAX_BATCH)));
 }
 
@@ -224,9 +224,9 @@ void views_fill(const gvom_handle *h, const RayQuery &R, const ViewBeams &B, int
                 size_t bm_words, ViewQuery &Q)
 {
     memset(&Q, 0, sizeof Q);
-    Q.dir = (const double *)h->ri_model.p; Q.off = Q.dir + (size_t)h->ri_H * h->ri_W * 3;
+    Q.dir = (const double *)h->range_image.model.p; Q.off = Q.dir + (size_t)h->range_image.H * h->range_image.W * 3;
     Q.max_range = max_range;
-    Q.W = h->ri_W; Q.stride_h = stride_h; Q.stride_w = stride_w;
+    Q.W = h->range_image.W; Q.stride_h = stride_h; Q.stride_w = stride_w;
     Q.nh = (int)B.nh; Q.nw = (int)B.nw; Q.nwc = (int)((B.nw + 63) / 64); Q.nb = (int)B.nb; Q.K = (int)K;
     Q.unknown_blocks = (flags & GVOM_RAY_UNKNOWN_BLOCKS) ? 1 : 0;
     Q.lit = R.lit; Q.cap = R.cap; Q.bm_words = (uint32_t)bm_words;
@@ -265,7 +265,7 @@ int check_align(gvom_handle *h, const char *fn, const float *cloud, int64_t n, c
     return GVOM_OK;
 }
 
-int align_fill(gvom_handle *h, Buf &stage, int &allocs, const float *cloud, int64_t n, const double *transforms, int64_t K, int on_device, int dilate,
+int align_fill(gvom_handle *h, CallState &call, const float *cloud, int64_t n, const double *transforms, int64_t K, int on_device, int dilate,
                const int32_t weights[5], AlignParams &P, const float **cdev, const double **tdev)
 {
     const int xy = h->prm.xy_size;
@@ -276,7 +276,7 @@ int align_fill(gvom_handle *h, Buf &stage, int &allocs, const float *cloud, int6
     if (on_device) return GVOM_OK;
     const HostPart parts[2] = {{transforms, (size_t)K * 96}, {cloud, (size_t)n * 12}};      // host inputs: staged, and up before the call returns
     const void *dev[2];
-    if (const int rc = stage_host(h, stage, allocs, parts, 2, true, dev)) return rc;
+    if (const int rc = stage_host(h, call, parts, 2, true, dev)) return rc;
     *tdev = (const double *)dev[0]; *cdev = (const float *)dev[1];
     return GVOM_OK;
 }
@@ -299,14 +299,15 @@ int map_set_of(gvom_handle *h, int64_t id, DevSet **m)
 }
 
 // ---- host inputs (gvom_host.h) -----------------------------------------------------------------------------------------------------------
-int stage_host(gvom_handle *h, Buf &b, int &allocs, const HostPart *parts, int n, bool sync, const void **dev)
+int stage_host(gvom_handle *h, CallState &call, const HostPart *parts, int n, bool sync, const void **dev)
 {
     size_t at[4], need = 0;
     for (int i = 0; i < n; ++i) {
         at[i] = need;
         if (parts[i].src) need += i + 1 < n ? align256(parts[i].bytes) : parts[i].bytes;
     }
-    if (const int rc = stage_buf(h, b, need, allocs)) return rc;
+    if (const int rc = stage_buf(h, call, need)) return rc;
+    const Buf &b = call.stage;
     for (int i = 0; i < n; ++i) {
         dev[i] = parts[i].src ? (char *)b.p + at[i] : nullptr;
         if (parts[i].src) HIPCHK(h, hipMemcpyAsync((char *)b.p + at[i], parts[i].src, parts[i].bytes, hipMemcpyHostToDevice, h->stream));
@@ -353,10 +354,11 @@ template <class Enqueue> int solve_rounds(gvom_handle *h, uint32_t *cnt, uint32_
     return GVOM_OK;
 }
 
-int solve_work_reserve(gvom_handle *h, SolveWork &w, size_t bytes, int &allocs)
+int solve_work_reserve(gvom_handle *h, SolveCall &call, size_t bytes)
 {
-    if (const int rc = stage_buf(h, w.work, bytes, allocs)) return rc;
-    if (!w.pin) HIPCHK(h, hipHostMalloc((void **)&w.pin, 256, hipHostMallocDefault));
+    SolveWork &w = call.solve;
+    if (const int rc = stage_buf(h, call, w.work, bytes)) return rc;
+    if (!w.pin) HIPCHK(h, hipHostMalloc((void **)&w.pin.p, 256, hipHostMallocDefault));
     return GVOM_OK;
 }
 
@@ -386,8 +388,8 @@ int ctg_solve(gvom_handle *h, SolveWork &w, const GoalWorkPtrs &G, int n, const 
     const int nt = gvom_ctg_tiles(n);
     HIPCHK(h, gvom_launch_ctg_seed(h->stream, n, cost32, c16, D, G.fl, G.goals, n_goals, G.cnt + CTG_CNT_SEEDED));
     const int32_t cap = max_cost == 0 ? GVOM_CTG_MAX_COST : max_cost;
-    const int inner = h->ctg.tune_inner > 0 ? h->ctg.tune_inner : 256;
-    const int batch = h->ctg.tune_batch > 0 ? h->ctg.tune_batch : 8;
+    const int inner = h->cost_to_go.solve.tune_inner > 0 ? h->cost_to_go.solve.tune_inner : 256;
+    const int batch = h->cost_to_go.solve.tune_batch > 0 ? h->cost_to_go.solve.tune_batch : 8;
     // by induction over the tile crossings of a shortest path the solve ends after at most (crossings + 1) rounds of tiles that
     // reach their fixed point; the limit below is beyond anything n <= 4096 can need and only keeps the loop finite
     const int64_t limit = max_rounds > 0 ? (int64_t)max_rounds : (int64_t)1 << 22;
@@ -399,11 +401,11 @@ int ctg_solve(gvom_handle *h, SolveWork &w, const GoalWorkPtrs &G, int n, const 
     return GVOM_OK;
 }
 
-int frontier_work(gvom_handle *h, SolveWork &w, int n, int &allocs, FrWork *W)
+int frontier_work(gvom_handle *h, SolveCall &call, int n, FrWork *W)
 {
     const FrOffsets o = fr_offsets(n, gvom_frontier_tiles(n), gvom_frontier_blocks(n));
-    if (const int rc = solve_work_reserve(h, w, o.end, allocs)) return rc;
-    char *p = (char *)w.work.p;
+    if (const int rc = solve_work_reserve(h, call, o.end)) return rc;
+    char *p = (char *)call.solve.work.p;
     *W = FrWork{(uint32_t *)p, (uint32_t *)(p + o.flags), (uint32_t *)(p + o.bc), (uint32_t *)(p + o.L), (uint32_t *)(p + o.count), o.bc};
     return GVOM_OK;
 }
@@ -416,8 +418,8 @@ int frontier_solve(gvom_handle *h, const char *fn, SolveWork &w, int n, const in
     int32_t *rows = part_ptr<int32_t>(set, 0), *cmap = part_ptr<int32_t>(set, 2), *counts = part_ptr<int32_t>(set, 3);
     int64_t *sums = part_ptr<int64_t>(set, 1);
     HIPCHK(h, gvom_launch_frontier_rows(h->stream, 0, max_clusters, rows, sums, cnt + FR_CNT_KEPT, cnt + FR_CNT_CELLS, counts));
-    const int inner = h->fr.tune_inner > 0 ? h->fr.tune_inner : 256;
-    const int batch = h->fr.tune_batch > 0 ? h->fr.tune_batch : 8;
+    const int inner = h->frontiers.solve.tune_inner > 0 ? h->frontiers.solve.tune_inner : 256;
+    const int batch = h->frontiers.solve.tune_batch > 0 ? h->frontiers.solve.tune_batch : 8;
     // labels only go down and there are n * n of them: a round that lowers none flags no tile, so fewer than n * n + 1 rounds lower
     // one.  The limit cannot be reached and only keeps the loop finite
     SolveRounds S;
@@ -531,13 +533,13 @@ VIS int gvom_clearance(gvom_t *h, int64_t map_set_id, const int32_t *positive, c
     HIPCHK(h, hipSetDevice(h->device));
     DevSet *set = nullptr;
     const size_t bytes = set_bytes(GVOM_PRODUCT_CLEARANCE, xy, 0, 0);
-    rc = product_acquire(h, GVOM_PRODUCT_CLEARANCE, bytes, bytes, fn, &h->cl_allocs, &set);
+    rc = product_acquire(h, GVOM_PRODUCT_CLEARANCE, bytes, bytes, fn, &h->clearance, &set);
     if (rc) return rc;
-    if ((rc = stage_buf(h, h->cl_g, gvom_clearance_scratch_bytes(xy), h->cl_allocs))) return rc;
+    if ((rc = stage_buf(h, h->clearance, h->clearance.g, gvom_clearance_scratch_bytes(xy)))) return rc;
     HIPCHK(h, join_second_stream(h));
     if (map_set_id < 0 && !on_device) {                                     // host maps: staged, and up before the call returns
-        if ((rc = stage_buf(h, h->cl_stage, 2 * n2 * 4, h->cl_allocs))) return rc;
-        int32_t *st = (int32_t *)h->cl_stage.p;
+        if ((rc = stage_buf(h, h->clearance, 2 * n2 * 4))) return rc;
+        int32_t *st = (int32_t *)h->clearance.stage.p;
         HIPCHK(h, hipMemcpyAsync(st, positive, n2 * 4, hipMemcpyHostToDevice, h->stream));
         if (negative) HIPCHK(h, hipMemcpyAsync(st + n2, negative, n2 * 4, hipMemcpyHostToDevice, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -546,7 +548,7 @@ VIS int gvom_clearance(gvom_t *h, int64_t map_set_id, const int32_t *positive, c
     if (flags & GVOM_CLEARANCE_NO_NEGATIVE) neg = nullptr;
     if ((rc = set_wait_releases(h, set))) return rc;
     HIPCHK(h, gvom_launch_clearance(h->stream, xy, h->prm.xy_resolution, pos, neg, density_threshold, max_cells2,
-                                    (uint16_t *)h->cl_g.p, part_ptr<float>(set, 0), part_ptr<int32_t>(set, 1), h->cl_shape));
+                                    (uint16_t *)h->clearance.g.p, part_ptr<float>(set, 0), part_ptr<int32_t>(set, 1), h->clearance.shape));
     return product_publish(h, set, product_id);
 }
 
@@ -568,14 +570,14 @@ VIS int gvom_raycast(gvom_t *h, const float *from, int64_t K, const float *to, i
     HIPCHK(h, hipSetDevice(h->device));
     DevSet *set = nullptr;
     const size_t bytes = set_bytes(GVOM_PRODUCT_RAYCAST, 0, 0, n);
-    if ((rc = product_acquire(h, GVOM_PRODUCT_RAYCAST, bytes, bytes, fn, &h->rq_allocs, &set))) return rc;
+    if ((rc = product_acquire(h, GVOM_PRODUCT_RAYCAST, bytes, bytes, fn, &h->raycast, &set))) return rc;
     set->cap = n;
     const Fused &F = h->fused[h->cur];
     ScanParams P;
     RayQuery Q;
     memset(&Q, 0, sizeof Q);
     raycast_params(h, F, P, Q);
-    if ((rc = rays_fill(h, h->rq_stage, h->rq_allocs, from, K, to, n, on_device, flags, Q))) return rc;
+    if ((rc = rays_fill(h, h->raycast, from, K, to, n, on_device, flags, Q))) return rc;
     if ((rc = set_wait_releases(h, set))) return rc;
     HIPCHK(h, gvom_launch_raycast(h->stream, P, Q, F.state, F.tags, part_ptr<int32_t>(set, 0), part_ptr<float>(set, 1)));
     if ((rc = product_publish(h, set, product_id))) return rc;
@@ -617,19 +619,19 @@ VIS int gvom_cost_to_go(gvom_t *h, int64_t map_set_id, const gvom_ctg_params *pa
     HIPCHK(h, hipSetDevice(h->device));
     DevSet *set = nullptr;
     const size_t bytes = set_bytes(GVOM_PRODUCT_COSTFIELD, xy, 0, 0);
-    if ((rc = product_acquire(h, GVOM_PRODUCT_COSTFIELD, bytes, bytes, fn, &h->ctg_allocs, &set))) return rc;
+    if ((rc = product_acquire(h, GVOM_PRODUCT_COSTFIELD, bytes, bytes, fn, &h->cost_to_go, &set))) return rc;
     const int nt = gvom_ctg_tiles(xy);
     const GoalWork lay = goal_work(nt * nt, 8, 0);
-    if ((rc = solve_work_reserve(h, h->ctg, lay.end, h->ctg_allocs))) return rc;
-    const GoalWorkPtrs G = goal_work_ptrs(h->ctg, lay);
+    if ((rc = solve_work_reserve(h, h->cost_to_go, lay.end))) return rc;
+    const GoalWorkPtrs G = goal_work_ptrs(h->cost_to_go.solve, lay);
     HIPCHK(h, join_second_stream(h));
     const void *cost32 = map_set_id < 0 ? cost : nullptr;
     if (map_set_id < 0 && !on_device) {                                     // a host cost map: staged
         const HostPart part = {cost, n2 * 4};
-        if ((rc = stage_host(h, h->ctg_stage, h->ctg_allocs, &part, 1, false, &cost32))) return rc;
+        if ((rc = stage_host(h, h->cost_to_go, &part, 1, false, &cost32))) return rc;
     }
     const size_t clr_g = align256(gvom_clearance_scratch_bytes(xy)), clr_map = align256(n2 * 4);
-    if (m && C.inflation_cells2 > 0 && (rc = stage_buf(h, h->ctg_clr, clr_g + 2 * clr_map, h->ctg_allocs))) return rc;
+    if (m && C.inflation_cells2 > 0 && (rc = stage_buf(h, h->cost_to_go, h->cost_to_go.clr, clr_g + 2 * clr_map))) return rc;
     if ((rc = goal_work_start(h, G, goals, (size_t)n_goals * 8)) || (rc = set_wait_releases(h, set))) return rc;
     int32_t *D = part_ptr<int32_t>(set, 0);
     uint16_t *c16 = part_ptr<uint16_t>(set, 2);
@@ -637,7 +639,7 @@ VIS int gvom_cost_to_go(gvom_t *h, int64_t map_set_id, const gvom_ctg_params *pa
         const int32_t *mp = part_ptr<const int32_t>(m, 0), *mn = part_ptr<const int32_t>(m, 1);
         const int32_t *cd2 = nullptr;
         if (C.inflation_cells2 > 0) {
-            char *q = (char *)h->ctg_clr.p;
+            char *q = (char *)h->cost_to_go.clr.p;
             HIPCHK(h, gvom_launch_clearance(h->stream, xy, h->prm.xy_resolution, mp, C.use_negative ? mn : nullptr, C.density_threshold,
                                             C.inflation_cells2, (uint16_t *)q, (float *)(q + clr_g), (int32_t *)(q + clr_g + clr_map)));
             cd2 = (const int32_t *)(q + clr_g + clr_map);
@@ -645,8 +647,8 @@ VIS int gvom_cost_to_go(gvom_t *h, int64_t map_set_id, const gvom_ctg_params *pa
         HIPCHK(h, gvom_launch_travcost(h->stream, xy, mp, mn, part_ptr<const int32_t>(m, 2), part_ptr<const double>(m, 3), cd2, C, c16));
     }
     SolveRounds S;
-    if ((rc = ctg_solve(h, h->ctg, G, xy, (const int32_t *)cost32, c16, D, part_ptr<uint8_t>(set, 1), (int)n_goals, max_cost, max_rounds, &S))) return rc;
-    return goal_solve_finish(h, fn, h->ctg, set, product_id, S, max_rounds, info);
+    if ((rc = ctg_solve(h, h->cost_to_go.solve, G, xy, (const int32_t *)cost32, c16, D, part_ptr<uint8_t>(set, 1), (int)n_goals, max_cost, max_rounds, &S))) return rc;
+    return goal_solve_finish(h, fn, h->cost_to_go.solve, set, product_id, S, max_rounds, info);
 }
 // ---- rollout scoring (gvom_footprint_set, gvom_score_rollouts) -------------------------------------------------------------------
 // K trajectories of T poses each, scored by k_rollouts (gvom_rollouts.hip) against a uint16 cost map with the footprint table of the
@@ -666,16 +668,16 @@ VIS int gvom_footprint_set(gvom_t *h, int32_t n_headings, const int32_t *start, 
     }
     HIPCHK(h, hipSetDevice(h->device));
     const size_t sb = (size_t)(n_headings + 1) * 4, offs_at = align256(sb), ob = (size_t)start[n_headings] * 4;
-    h->fp_H = 0;                                                            // (no table while this one is on its way)
-    if (h->fp_tab.bytes < offs_at + ob) HIPCHK(h, hipStreamSynchronize(h->stream));   // the kernels that read the table it outgrows
-    const int rc = ensure(h, h->fp_tab, offs_at + ob);
+    h->footprint.H = 0;                                                     // (no table while this one is on its way)
+    if (h->footprint.tab.bytes < offs_at + ob) HIPCHK(h, hipStreamSynchronize(h->stream));   // the kernels that read the table it outgrows
+    const int rc = ensure(h, h->footprint.tab, offs_at + ob);
     if (rc) return rc;
     // on the handle's stream: behind whatever still reads the previous table
-    HIPCHK(h, hipMemcpyAsync(h->fp_tab.p, start, sb, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync((char *)h->fp_tab.p + offs_at, offsets, ob, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->footprint.tab.p, start, sb, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync((char *)h->footprint.tab.p + offs_at, offsets, ob, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    h->fp_offs_at = offs_at; h->fp_H = n_headings;
-    h->fp_total = start[n_headings]; ++h->fp_gen;                           // (gvom_attitude_volume rebuilds its table)
+    h->footprint.offs_at = offs_at; h->footprint.H = n_headings;
+    h->footprint.total = start[n_headings]; ++h->footprint.gen;             // (gvom_attitude_volume rebuilds its table)
     return GVOM_OK;
 }
 
@@ -688,7 +690,7 @@ VIS int gvom_score_rollouts(gvom_t *h, int64_t costfield_id, const uint16_t *cel
     const char *const fn = "gvom_score_rollouts";
     int rc;
     if (h->sharded) return refuse(h, fn, "sharded handles are not supported");
-    if (h->fp_H < 1) return refuse(h, "gvom_score_rollouts", "no footprint table is set (gvom_footprint_set)");
+    if (h->footprint.H < 1) return refuse(h, "gvom_score_rollouts", "no footprint table is set (gvom_footprint_set)");
     if (!poses || !origin_cells) return refuse(h, "gvom_score_rollouts", "poses and origin_cells must not be NULL");
     if ((rc = check_one_source(h, fn, costfield_id >= 0, cell_cost || cost_to_go, !cell_cost, "a cost field id", "map pointers", "a cell-cost map")) ||
         (rc = check_rollout_shape(h, fn, K, T, origin_cells)) || (rc = check_side(h, fn))) return rc;
@@ -704,7 +706,7 @@ VIS int gvom_score_rollouts(gvom_t *h, int64_t costfield_id, const uint16_t *cel
     HIPCHK(h, hipSetDevice(h->device));
     DevSet *set = nullptr;
     const size_t bytes = set_bytes(GVOM_PRODUCT_ROLLOUTS, 0, 0, K, T);
-    rc = product_acquire(h, GVOM_PRODUCT_ROLLOUTS, bytes, bytes, fn, &h->ro_allocs, &set);
+    rc = product_acquire(h, GVOM_PRODUCT_ROLLOUTS, bytes, bytes, fn, &h->rollouts, &set);
     if (rc) return rc;
     set->cap = K; set->cols = T;
     const float *pdev = poses;
@@ -712,7 +714,7 @@ VIS int gvom_score_rollouts(gvom_t *h, int64_t costfield_id, const uint16_t *cel
     if (!on_device) {                                                       // host poses (and maps): staged, and up before the call returns
         const HostPart parts[3] = {{cell_cost, n2 * 2}, {cost_to_go, n2 * 4}, {poses, (size_t)K * T * 12}};
         const void *dev[3];
-        if ((rc = stage_host(h, h->ro_stage, h->ro_allocs, parts, 3, true, dev))) return rc;
+        if ((rc = stage_host(h, h->rollouts, parts, 3, true, dev))) return rc;
         if (dev[0]) c16 = (const uint16_t *)dev[0];
         if (dev[1]) D = (const int32_t *)dev[1];
         pdev = (const float *)dev[2];
@@ -720,7 +722,7 @@ VIS int gvom_score_rollouts(gvom_t *h, int64_t costfield_id, const uint16_t *cel
     if ((rc = set_wait_releases(h, set))) return rc;
     RolloutParams P;
     rollout_frame(h, K, T, origin_cells, P);
-    HIPCHK(h, gvom_launch_rollouts(h->stream, P, pdev, (const int32_t *)h->fp_tab.p, (const uint32_t *)((char *)h->fp_tab.p + h->fp_offs_at),
+    HIPCHK(h, gvom_launch_rollouts(h->stream, P, pdev, (const int32_t *)h->footprint.tab.p, (const uint32_t *)((char *)h->footprint.tab.p + h->footprint.offs_at),
                                    c16, D, part_ptr<int32_t>(set, 0), part_ptr<uint16_t>(set, 1)));
     return product_publish(h, set, product_id);
 }
@@ -755,15 +757,15 @@ VIS int gvom_chassis_set(gvom_t *h, const gvom_chassis_t *c, int32_t n_headings,
         tab[cs_at / 8 + 2 * k] = co; tab[cs_at / 8 + 2 * k + 1] = si;
     }
     HIPCHK(h, hipSetDevice(h->device));
-    h->at_H = 0;                                                            // (no chassis while this one is on its way)
-    if (h->at_tab.bytes < cs_at + cb) HIPCHK(h, hipStreamSynchronize(h->stream));   // the kernels that read the table it outgrows
-    const int rc = ensure(h, h->at_tab, cs_at + cb);
+    h->chassis.H = 0;                                                       // (no chassis while this one is on its way)
+    if (h->chassis.tab.bytes < cs_at + cb) HIPCHK(h, hipStreamSynchronize(h->stream));   // the kernels that read the table it outgrows
+    const int rc = ensure(h, h->chassis.tab, cs_at + cb);
     if (rc) return rc;
     // on the handle's stream: behind whatever still reads the previous table
-    HIPCHK(h, hipMemcpyAsync(h->at_tab.p, tab.data(), cs_at + cb, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->chassis.tab.p, tab.data(), cs_at + cb, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    h->at_cs_at = cs_at; h->at_H = n_headings; h->at_chassis = *c;
-    ++h->at_gen;                                                            // (gvom_attitude_volume rebuilds its table)
+    h->chassis.cs_at = cs_at; h->chassis.H = n_headings; h->chassis.c = *c;
+    ++h->chassis.gen;                                                       // (gvom_attitude_volume rebuilds its table)
     return GVOM_OK;
 }
 
@@ -787,15 +789,15 @@ VIS int gvom_score_attitude(gvom_t *h, int64_t map_set_id, const double *ground,
     HIPCHK(h, hipSetDevice(h->device));
     DevSet *set = nullptr;
     const size_t bytes = set_bytes(GVOM_PRODUCT_ATTITUDE, 0, 0, K, T);
-    if ((rc = product_acquire(h, GVOM_PRODUCT_ATTITUDE, bytes, bytes, fn, &h->at_allocs, &set))) return rc;
+    if ((rc = product_acquire(h, GVOM_PRODUCT_ATTITUDE, bytes, bytes, fn, &h->attitude, &set))) return rc;
     set->cap = K; set->cols = T;
-    if ((rc = ground_reserve(h, g, h->at_ground, h->at_allocs, ground))) return rc;
+    if ((rc = ground_reserve(h, g, h->attitude, ground))) return rc;
     const float *pdev = poses;
     HIPCHK(h, join_second_stream(h));
     if (!on_device) {                                                       // host poses (and ground): staged, and up before the call returns
         const HostPart parts[2] = {{ground, n2 * 8}, {poses, (size_t)K * T * 12}};
         const void *dev[2];
-        if ((rc = stage_host(h, h->at_stage, h->at_allocs, parts, 2, true, dev))) return rc;
+        if ((rc = stage_host(h, h->attitude, parts, 2, true, dev))) return rc;
         if (dev[0]) g.dev = (const double *)dev[0];
         pdev = (const float *)dev[1];
     }
@@ -804,9 +806,9 @@ VIS int gvom_score_attitude(gvom_t *h, int64_t map_set_id, const double *ground,
     memset(&P, 0, sizeof P);
     rollout_frame(h, K, T, origin_cells, P.R);
     chassis_lengths(h, P.wheelbase, P.track, &P.axle_mid);
-    chassis_limits(h->at_chassis, P);
-    HIPCHK(h, gvom_launch_attitude(h->stream, P, pdev, (const int32_t *)h->fp_tab.p, (const uint32_t *)((char *)h->fp_tab.p + h->fp_offs_at),
-                                   (const double *)h->at_tab.p, (const double *)((char *)h->at_tab.p + h->at_cs_at), g.dev,
+    chassis_limits(h->chassis.c, P);
+    HIPCHK(h, gvom_launch_attitude(h->stream, P, pdev, (const int32_t *)h->footprint.tab.p, (const uint32_t *)((char *)h->footprint.tab.p + h->footprint.offs_at),
+                                   (const double *)h->chassis.tab.p, (const double *)((char *)h->chassis.tab.p + h->chassis.cs_at), g.dev,
                                    part_ptr<int32_t>(set, 0), part_ptr<float>(set, 1), part_ptr<uint8_t>(set, 2)));
     return product_publish(h, set, product_id);
 }
@@ -828,13 +830,13 @@ VIS int gvom_body_set(gvom_t *h, const float *spheres, int32_t S)
     for (int k = 0; k < S; ++k)
         if (spheres[4 * k + 3] < 0.0f) return refuse(h, fn, "a radius is negative");
     HIPCHK(h, hipSetDevice(h->device));
-    h->bd_S = 0;                                                            // (no body while this one is on its way)
-    const int rc = stage_buf(h, h->bd_tab, (size_t)GVOM_BODY_MAX_SPHERES * 16, h->bd_allocs);     // (allocated once: it holds every S)
+    h->body.S = 0;                                                          // (no body while this one is on its way)
+    const int rc = stage_buf(h, h->body, h->body.tab, (size_t)GVOM_BODY_MAX_SPHERES * 16);        // (allocated once: it holds every S)
     if (rc) return rc;
     // on the handle's stream: behind whatever still reads the previous table
-    HIPCHK(h, hipMemcpyAsync(h->bd_tab.p, spheres, (size_t)S * 16, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->body.tab.p, spheres, (size_t)S * 16, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    h->bd_S = S;
+    h->body.S = S;
     return GVOM_OK;
 }
 
@@ -848,7 +850,7 @@ VIS int gvom_score_body(gvom_t *h, int64_t field_product_id, const float *field,
     const char *const fn = "gvom_score_body";
     int rc;
     if ((rc = check_standing(h, fn, false))) return rc;
-    if (h->bd_S < 1) return refuse(h, fn, "no body is set (gvom_body_set)");
+    if (h->body.S < 1) return refuse(h, fn, "no body is set (gvom_body_set)");
     if (!poses || !origin_cells) return refuse(h, fn, "poses and origin_cells must not be NULL");
     if (flags & ~GVOM_ATTITUDE_INFERRED_GROUND) return refuse(h, fn, "unknown flag bits");
     if (!std::isfinite(min_margin)) return refuse(h, fn, "min_margin must be finite");
@@ -864,16 +866,16 @@ VIS int gvom_score_body(gvom_t *h, int64_t field_product_id, const float *field,
     HIPCHK(h, hipSetDevice(h->device));
     DevSet *set = nullptr;
     const size_t bytes = set_bytes(GVOM_PRODUCT_BODY, 0, 0, K, T);
-    if ((rc = product_acquire(h, GVOM_PRODUCT_BODY, bytes, bytes, fn, &h->bd_allocs, &set))) return rc;
+    if ((rc = product_acquire(h, GVOM_PRODUCT_BODY, bytes, bytes, fn, &h->body, &set))) return rc;
     set->cap = K; set->cols = T;
-    if ((rc = ground_reserve(h, g, h->bd_ground, h->bd_allocs, ground))) return rc;
+    if ((rc = ground_reserve(h, g, h->body, ground))) return rc;
     const float *pdev = poses;
     const float *fdev = F.f ? part_ptr<const float>(F.f, 0) : field;
     HIPCHK(h, join_second_stream(h));
     if (!on_device) {                                                       // host poses (field and ground): staged, and up before the call returns
         const HostPart parts[3] = {{field, n2 * (size_t)F.zs * 4}, {ground, n2 * 8}, {poses, (size_t)K * T * 12}};
         const void *dev[3];
-        if ((rc = stage_host(h, h->bd_stage, h->bd_allocs, parts, 3, true, dev))) return rc;
+        if ((rc = stage_host(h, h->body, parts, 3, true, dev))) return rc;
         if (dev[0]) fdev = (const float *)dev[0];
         if (dev[1]) g.dev = (const double *)dev[1];
         pdev = (const float *)dev[2];
@@ -883,8 +885,8 @@ VIS int gvom_score_body(gvom_t *h, int64_t field_product_id, const float *field,
     memset(&P, 0, sizeof P);
     rollout_frame(h, K, T, origin_cells, P.R);
     body_params(h, F, min_margin, P);
-    HIPCHK(h, gvom_launch_body(h->stream, P, pdev, (const double *)h->at_tab.p, (const double *)((char *)h->at_tab.p + h->at_cs_at), g.dev,
-                               (const float *)h->bd_tab.p, fdev, part_ptr<int32_t>(set, 0), part_ptr<float>(set, 1), part_ptr<uint8_t>(set, 2)));
+    HIPCHK(h, gvom_launch_body(h->stream, P, pdev, (const double *)h->chassis.tab.p, (const double *)((char *)h->chassis.tab.p + h->chassis.cs_at), g.dev,
+                               (const float *)h->body.tab.p, fdev, part_ptr<int32_t>(set, 0), part_ptr<float>(set, 1), part_ptr<uint8_t>(set, 2)));
     return product_publish(h, set, product_id);
 }
 
@@ -908,9 +910,9 @@ VIS int gvom_score_alignments(gvom_t *h, const float *cloud, int64_t n, const do
     HIPCHK(h, hipSetDevice(h->device));
     DevSet *set = nullptr;
     const size_t bytes = set_bytes(GVOM_PRODUCT_ALIGNMENT, 0, 0, K);
-    if ((rc = product_acquire(h, GVOM_PRODUCT_ALIGNMENT, bytes, bytes, fn, &h->al_allocs, &set))) return rc;
+    if ((rc = product_acquire(h, GVOM_PRODUCT_ALIGNMENT, bytes, bytes, fn, &h->alignment, &set))) return rc;
     set->cap = K;
-    if ((rc = stage_buf(h, h->al_grid, gb, h->al_allocs))) return rc;
+    if ((rc = stage_buf(h, h->alignment, h->alignment.grid, gb))) return rc;
     const Fused &F = h->fused[h->cur];
     OccParams O;
     occ_params(h, F, O);
@@ -919,9 +921,9 @@ VIS int gvom_score_alignments(gvom_t *h, const float *cloud, int64_t n, const do
     metric_frame(h, F, P);
     const float *cdev;
     const double *tdev;
-    if ((rc = align_fill(h, h->al_stage, h->al_allocs, cloud, n, transforms, K, on_device, dilate, weights, P, &cdev, &tdev))) return rc;
+    if ((rc = align_fill(h, h->alignment, cloud, n, transforms, K, on_device, dilate, weights, P, &cdev, &tdev))) return rc;
     if ((rc = set_wait_releases(h, set))) return rc;
-    HIPCHK(h, gvom_launch_align(h->stream, O, P, F.state, F.tags, cdev, tdev, (uint32_t *)h->al_grid.p, part_ptr<int32_t>(set, 0),
+    HIPCHK(h, gvom_launch_align(h->stream, O, P, F.state, F.tags, cdev, tdev, (uint32_t *)h->alignment.grid.p, part_ptr<int32_t>(set, 0),
                                 part_ptr<int32_t>(set, 1)));
     return product_publish(h, set, product_id);
 }
@@ -959,21 +961,21 @@ VIS int gvom_frontiers(gvom_t *h, int64_t costfield_id, int64_t map_set_id, cons
     HIPCHK(h, hipSetDevice(h->device));
     DevSet *set = nullptr;
     const size_t bytes = set_bytes(GVOM_PRODUCT_FRONTIERS, xy, 0, max_clusters);
-    if ((rc = product_acquire(h, GVOM_PRODUCT_FRONTIERS, bytes, bytes, fn, &h->fr_allocs, &set))) return rc;
+    if ((rc = product_acquire(h, GVOM_PRODUCT_FRONTIERS, bytes, bytes, fn, &h->frontiers, &set))) return rc;
     set->cap = max_clusters;
     FrWork W;
-    if ((rc = frontier_work(h, h->fr, xy, h->fr_allocs, &W))) return rc;
+    if ((rc = frontier_work(h, h->frontiers, xy, &W))) return rc;
     HIPCHK(h, join_second_stream(h));
     if (!ids && !on_device) {                                               // host maps: staged
         const HostPart parts[3] = {{cell_cost, n2 * 2}, {visibility, n2 * 4}, {cost_to_go, n2 * 4}};
         const void *dev[3];
-        if ((rc = stage_host(h, h->fr_stage, h->fr_allocs, parts, 3, false, dev))) return rc;
+        if ((rc = stage_host(h, h->frontiers, parts, 3, false, dev))) return rc;
         c16 = (const uint16_t *)dev[0]; vis = (const int32_t *)dev[1]; D = (const int32_t *)dev[2];
     }
     HIPCHK(h, hipMemsetAsync(W.cnt, 0, W.clear_bytes, h->stream));          // the counters and both halves of the flags
     if ((rc = set_wait_releases(h, set))) return rc;
     HIPCHK(h, gvom_launch_frontier_mark(h->stream, xy, c16, vis, D, W.L, W.count, W.fl, W.cnt + FR_CNT_CELLS));
-    return frontier_solve(h, fn, h->fr, xy, D, W, min_cells, max_clusters, set, product_id, info);
+    return frontier_solve(h, fn, h->frontiers.solve, xy, D, W, min_cells, max_clusters, set, product_id, info);
 }
 
 // ---- viewpoint scoring (gvom_score_viewpoints) -------------------------------------------------------------------------------------
@@ -1000,11 +1002,11 @@ VIS int gvom_score_viewpoints(gvom_t *h, const double *poses, int64_t K, int on_
     HIPCHK(h, hipSetDevice(h->device));
     DevSet *set = nullptr;
     const size_t bytes = set_bytes(GVOM_PRODUCT_VIEWPOINTS, 0, 0, K);
-    if ((rc = product_acquire(h, GVOM_PRODUCT_VIEWPOINTS, bytes, bytes, fn, &h->vp_allocs, &set))) return rc;
+    if ((rc = product_acquire(h, GVOM_PRODUCT_VIEWPOINTS, bytes, bytes, fn, &h->viewpoints, &set))) return rc;
     set->cap = K;
     size_t bm_words;
     const int64_t batch = views_batch(h, V, K, &bm_words);
-    if ((rc = stage_buf(h, h->vp_bitmaps, (size_t)batch * bm_words * 4, h->vp_allocs))) return rc;
+    if ((rc = stage_buf(h, h->viewpoints, h->viewpoints.bitmaps, (size_t)batch * bm_words * 4))) return rc;
     const Fused &F = h->fused[h->cur];
     ScanParams P;
     RayQuery R;
@@ -1017,16 +1019,16 @@ VIS int gvom_score_viewpoints(gvom_t *h, const double *poses, int64_t K, int on_
     if (!on_device) {                                                       // host poses: staged, and up before the call returns
         const HostPart part = {poses, (size_t)K * 96};
         const void *dev;
-        if ((rc = stage_host(h, h->vp_stage, h->vp_allocs, &part, 1, true, &dev))) return rc;
+        if ((rc = stage_host(h, h->viewpoints, &part, 1, true, &dev))) return rc;
         Q.poses = (const double *)dev;
     }
     if ((rc = set_wait_releases(h, set))) return rc;
     int32_t *rows = part_ptr<int32_t>(set, 0);
-    rc = views_run(h, h->vp_bitmaps, Q, batch, rows,
-                   [&](int nk) { return gvom_launch_viewpoints(h->stream, P, Q, nk, F.state, F.tags, (uint32_t *)h->vp_bitmaps.p, rows); },
+    rc = views_run(h, h->viewpoints.bitmaps, Q, batch, rows,
+                   [&](int nk) { return gvom_launch_viewpoints(h->stream, P, Q, nk, F.state, F.tags, (uint32_t *)h->viewpoints.bitmaps.p, rows); },
                    [&]() { return gvom_launch_viewpoint_best(h->stream, P, Q, F.state, F.tags, rows, part_ptr<int32_t>(set, 1)); });
     if (rc) return rc;
-    h->vp_last_batch = (int)batch;
+    h->viewpoints.last_batch = (int)batch;
     if ((rc = product_publish(h, set, product_id))) return rc;
     for (int k = 0; origin_voxels && k < 3; ++k) origin_voxels[k] = (double)F.origin[k];
     return GVOM_OK;
@@ -1058,13 +1060,13 @@ VIS int gvom_primitives_set(gvom_t *h, int32_t n_headings, const int32_t *start,
     }
     HIPCHK(h, hipSetDevice(h->device));
     const size_t sb = (size_t)(n_headings + 1) * 4, prims_at = align256(sb), pb = (size_t)start[n_headings] * 8;
-    h->pf_H = 0;                                                            // (no table while this one is on its way)
-    const int rc = stage_buf(h, h->pf_tab, prims_at + (size_t)GVOM_POSE_MAX_HEADINGS * GVOM_POSE_MAX_PRIMS * 8, h->pf_allocs);   // (the largest table: never grows again)
+    h->pose_field.H = 0;                                                    // (no table while this one is on its way)
+    const int rc = stage_buf(h, h->pose_field, h->pose_field.tab, prims_at + (size_t)GVOM_POSE_MAX_HEADINGS * GVOM_POSE_MAX_PRIMS * 8);   // (the largest table: never grows again)
     if (rc) return rc;
-    HIPCHK(h, hipMemcpyAsync(h->pf_tab.p, start, sb, hipMemcpyHostToDevice, h->stream));
-    if (pb) HIPCHK(h, hipMemcpyAsync((char *)h->pf_tab.p + prims_at, prims, pb, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->pose_field.tab.p, start, sb, hipMemcpyHostToDevice, h->stream));
+    if (pb) HIPCHK(h, hipMemcpyAsync((char *)h->pose_field.tab.p + prims_at, prims, pb, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    h->pf_prims_at = prims_at; h->pf_H = n_headings; h->pf_R = R;
+    h->pose_field.prims_at = prims_at; h->pose_field.H = n_headings; h->pose_field.R = R;
     return GVOM_OK;
 }
 
@@ -1085,13 +1087,13 @@ static int pose_field_call(gvom_t *h, const char *fn, int64_t costfield_id, cons
     for (int k = 0; info && k < 4; ++k) info[k] = 0;
     int rc;
     if (h->sharded) return refuse(h, fn, "sharded handles are not supported");
-    if (h->fp_H < 1) return refuse(h, fn, "no footprint table is set (gvom_footprint_set)");
-    if (h->pf_H < 1) return refuse(h, fn, "no primitive table is set (gvom_primitives_set)");
-    if (h->fp_H > GVOM_POSE_MAX_HEADINGS) return refuse(h, fn, "footprint tables of more than 64 headings are not supported", GVOM_ERR_CAPACITY);
-    if (h->pf_H != h->fp_H) return refuse(h, fn, "the primitives were set for another number of headings than the footprint table has");
+    if (h->footprint.H < 1) return refuse(h, fn, "no footprint table is set (gvom_footprint_set)");
+    if (h->pose_field.H < 1) return refuse(h, fn, "no primitive table is set (gvom_primitives_set)");
+    if (h->footprint.H > GVOM_POSE_MAX_HEADINGS) return refuse(h, fn, "footprint tables of more than 64 headings are not supported", GVOM_ERR_CAPACITY);
+    if (h->pose_field.H != h->footprint.H) return refuse(h, fn, "the primitives were set for another number of headings than the footprint table has");
     if ((rc = check_one_source(h, fn, costfield_id >= 0, cost, !cost, "a cost field id", "a cost map", "a cost map"))) return rc;
     if ((rc = check_goals(h, fn, goals, n_goals, max_cost, max_rounds)) || (rc = check_side(h, fn))) return rc;
-    const int xy = h->prm.xy_size, H = h->pf_H, R = h->pf_R;
+    const int xy = h->prm.xy_size, H = h->pose_field.H, R = h->pose_field.R;
     const size_t n2 = (size_t)xy * xy;
     if ((rc = check_states(h, fn, H, xy))) return rc;
     for (int64_t k = 0; k < n_goals; ++k) {
@@ -1115,45 +1117,45 @@ static int pose_field_call(gvom_t *h, const char *fn, int64_t costfield_id, cons
     HIPCHK(h, hipSetDevice(h->device));
     DevSet *set = nullptr;
     const size_t bytes = set_bytes(GVOM_PRODUCT_POSEFIELD, xy, 0, H);
-    if ((rc = product_acquire(h, GVOM_PRODUCT_POSEFIELD, bytes, bytes, fn, &h->pf_allocs, &set))) return rc;
+    if ((rc = product_acquire(h, GVOM_PRODUCT_POSEFIELD, bytes, bytes, fn, &h->pose_field, &set))) return rc;
     set->cap = H;
     const int nt = gvom_pose_tiles(xy);
     const GoalWork lay = goal_work(nt * nt, 12, n2 * 2);                     // (the tail: the uint16 cost map converted from cost32)
-    if ((rc = solve_work_reserve(h, h->pf, lay.end, h->pf_allocs))) return rc;
-    const GoalWorkPtrs G = goal_work_ptrs(h->pf, lay);
+    if ((rc = solve_work_reserve(h, h->pose_field, lay.end))) return rc;
+    const GoalWorkPtrs G = goal_work_ptrs(h->pose_field.solve, lay);
     uint16_t *c16w = (uint16_t *)G.tail;
     HIPCHK(h, join_second_stream(h));
     const void *cost32 = f ? nullptr : cost;
     if (!f && !on_device) {                                                 // a host cost map: staged
         const HostPart part = {cost, n2 * 4};
-        if ((rc = stage_host(h, h->pf_stage, h->pf_allocs, &part, 1, false, &cost32))) return rc;
+        if ((rc = stage_host(h, h->pose_field, &part, 1, false, &cost32))) return rc;
     }
     const uint16_t *c16 = f ? part_ptr<const uint16_t>(f, 2) : c16w;
     if ((rc = goal_work_start(h, G, goals, (size_t)n_goals * 12)) || (rc = set_wait_releases(h, set))) return rc;
     int32_t *D = part_ptr<int32_t>(set, 0);
     uint16_t *C = part_ptr<uint16_t>(set, 2);
-    const int32_t *pstart = (const int32_t *)h->pf_tab.p;
-    const int16_t *prims = (const int16_t *)((char *)h->pf_tab.p + h->pf_prims_at);
+    const int32_t *pstart = (const int32_t *)h->pose_field.tab.p;
+    const int16_t *prims = (const int16_t *)((char *)h->pose_field.tab.p + h->pose_field.prims_at);
     HIPCHK(h, gvom_launch_pose_seed(h->stream, 0, xy, H, R, (const int32_t *)cost32, c16w, C, D, G.fl, G.goals, (int)n_goals, G.cnt + CTG_CNT_SEEDED));
-    HIPCHK(h, gvom_launch_cspace(h->stream, xy, H, c16, (const int32_t *)h->fp_tab.p, (const uint32_t *)((char *)h->fp_tab.p + h->fp_offs_at), C));
+    HIPCHK(h, gvom_launch_cspace(h->stream, xy, H, c16, (const int32_t *)h->footprint.tab.p, (const uint32_t *)((char *)h->footprint.tab.p + h->footprint.offs_at), C));
     for (int i = 0; i < 2; ++i)
         if (vol[i]) HIPCHK(h, gvom_launch_cspace_attitude(h->stream, xy, H, part_ptr<const uint8_t>(vol[i], 0), part_ptr<const uint8_t>(vol[i], 1),
                                                           volumes[i].mask, (uint32_t)volumes[i].weight, C));
     HIPCHK(h, gvom_launch_pose_seed(h->stream, 1, xy, H, R, (const int32_t *)cost32, c16w, C, D, G.fl, G.goals, (int)n_goals, G.cnt + CTG_CNT_SEEDED));
     const int32_t cap = max_cost == 0 ? GVOM_CTG_MAX_COST : max_cost;
-    const int inner = h->pf.tune_inner > 0 ? h->pf.tune_inner : 64;
-    const int batch = h->pf.tune_batch > 0 ? h->pf.tune_batch : 8;
+    const int inner = h->pose_field.solve.tune_inner > 0 ? h->pose_field.solve.tune_inner : 64;
+    const int batch = h->pose_field.solve.tune_batch > 0 ? h->pose_field.solve.tune_batch : 8;
     // a state's final value is in memory at the latest one round after the round in which its successor's was, so
     // the solve ends after at most (primitives on a cheapest drive + 1) rounds of tiles that reach their fixed point; the limit below
     // is beyond that for 2^28 states and only keeps the loop finite
     const int64_t limit = max_rounds > 0 ? (int64_t)max_rounds : (int64_t)1 << 29;
     SolveRounds S;
-    rc = solve_rounds(h, G.cnt, G.fl, h->pf.pin, nt * nt, batch, limit, [&](int64_t, uint32_t *fin, uint32_t *fout, uint32_t *any, uint32_t *ran) {
+    rc = solve_rounds(h, G.cnt, G.fl, h->pose_field.solve.pin, nt * nt, batch, limit, [&](int64_t, uint32_t *fin, uint32_t *fout, uint32_t *any, uint32_t *ran) {
         return gvom_launch_pose_relax(h->stream, xy, H, R, C, D, pstart, prims, fin, fout, any, ran, cap, inner);
     }, &S);
     if (rc) return rc;
     HIPCHK(h, gvom_launch_pose_actions(h->stream, xy, H, C, D, pstart, prims, part_ptr<uint8_t>(set, 1), G.cnt + CTG_CNT_REACHED));
-    return goal_solve_finish(h, fn, h->pf, set, product_id, S, max_rounds, info);
+    return goal_solve_finish(h, fn, h->pose_field.solve, set, product_id, S, max_rounds, info);
 }
 
 VIS int gvom_pose_field(gvom_t *h, int64_t costfield_id, const int32_t *cost, int on_device, const int32_t *goals, int64_t n_goals,
@@ -1189,28 +1191,28 @@ VIS int gvom_pose_field_volumes(gvom_t *h, int64_t costfield_id, const int32_t *
     return pose_field_call(h, fn, costfield_id, cost, on_device, v, goals, n_goals, max_cost, max_rounds, product_id, info);
 }
 
-// the table of "attitude volumes" (av_tab: (u - am, v) of every footprint cell and per heading the wheels' cell offsets and the footprint's
+// the table of "attitude volumes" (attitude_volume.tab: (u - am, v) of every footprint cell and per heading the wheels' cell offsets and the footprint's
 // box), shared by gvom_attitude_volume and gvom_body_volume: the first call of either after a gvom_footprint_set / gvom_chassis_set
 // rebuilds it.  reserve: room for it, in front of the call's uploads; rebuild: k_volume_attitude_table on the handle's stream, behind
 // whatever still reads the previous table
-static bool volume_table_stale(const gvom_t *h) { return h->av_fp_gen != h->fp_gen || h->av_at_gen != h->at_gen; }
+static bool volume_table_stale(const gvom_t *h) { return h->attitude_volume.fp_gen != h->footprint.gen || h->attitude_volume.at_gen != h->chassis.gen; }
 static int volume_table_reserve(gvom_t *h, int H)
 {
     if (!volume_table_stale(h)) return GVOM_OK;
-    const size_t tab_bytes = align256((size_t)h->fp_total * 16) + (size_t)H * 48;
-    if (h->av_tab.bytes < tab_bytes) HIPCHK(h, hipStreamSynchronize(h->stream));   // the kernels that read the table it outgrows
-    return stage_buf(h, h->av_tab, tab_bytes, h->av_allocs);
+    const size_t tab_bytes = align256((size_t)h->footprint.total * 16) + (size_t)H * 48;
+    if (h->attitude_volume.tab.bytes < tab_bytes) HIPCHK(h, hipStreamSynchronize(h->stream));   // the kernels that read the table it outgrows
+    return stage_buf(h, h->attitude_volume, h->attitude_volume.tab, tab_bytes);
 }
 static int volume_table_rebuild(gvom_t *h, int H)
 {
     if (!volume_table_stale(h)) return GVOM_OK;
-    const gvom_chassis_t &c = h->at_chassis;
-    const size_t wcell_at = align256((size_t)h->fp_total * 16);
-    HIPCHK(h, gvom_launch_attitude_volume_table(h->stream, H, h->fp_total, h->prm.xy_resolution, 0.5 * (c.front_axle + c.rear_axle),
-                                                (const int32_t *)h->fp_tab.p, (const uint32_t *)((char *)h->fp_tab.p + h->fp_offs_at),
-                                                (const double *)h->at_tab.p, (const double *)((char *)h->at_tab.p + h->at_cs_at),
-                                                (double *)h->av_tab.p, (int32_t *)((char *)h->av_tab.p + wcell_at)));
-    h->av_wcell_at = wcell_at; h->av_fp_gen = h->fp_gen; h->av_at_gen = h->at_gen;
+    const gvom_chassis_t &c = h->chassis.c;
+    const size_t wcell_at = align256((size_t)h->footprint.total * 16);
+    HIPCHK(h, gvom_launch_attitude_volume_table(h->stream, H, h->footprint.total, h->prm.xy_resolution, 0.5 * (c.front_axle + c.rear_axle),
+                                                (const int32_t *)h->footprint.tab.p, (const uint32_t *)((char *)h->footprint.tab.p + h->footprint.offs_at),
+                                                (const double *)h->chassis.tab.p, (const double *)((char *)h->chassis.tab.p + h->chassis.cs_at),
+                                                (double *)h->attitude_volume.tab.p, (int32_t *)((char *)h->attitude_volume.tab.p + wcell_at)));
+    h->attitude_volume.wcell_at = wcell_at; h->attitude_volume.fp_gen = h->footprint.gen; h->attitude_volume.at_gen = h->chassis.gen;
     return GVOM_OK;
 }
 
@@ -1230,7 +1232,7 @@ VIS int gvom_attitude_volume(gvom_t *h, int64_t map_set_id, const double *ground
     if ((rc = check_standing(h, fn, true))) return rc;
     if (flags & ~GVOM_ATTITUDE_INFERRED_GROUND) return refuse(h, fn, "unknown flag bits");
     if ((rc = check_one_source(h, fn, map_set_id >= 0, ground, !ground, "a map set id", "a ground map", "a ground map")) || (rc = check_side(h, fn))) return rc;
-    const int xy = h->prm.xy_size, H = h->fp_H;
+    const int xy = h->prm.xy_size, H = h->footprint.H;
     const size_t n2 = (size_t)xy * xy;
     if ((rc = check_states(h, fn, H, xy))) return rc;
     Ground g;
@@ -1238,14 +1240,14 @@ VIS int gvom_attitude_volume(gvom_t *h, int64_t map_set_id, const double *ground
     HIPCHK(h, hipSetDevice(h->device));
     DevSet *set = nullptr;
     const size_t bytes = set_bytes(GVOM_PRODUCT_ATTITUDE_VOLUME, xy, 0, H);
-    if ((rc = product_acquire(h, GVOM_PRODUCT_ATTITUDE_VOLUME, bytes, bytes, fn, &h->av_allocs, &set))) return rc;
+    if ((rc = product_acquire(h, GVOM_PRODUCT_ATTITUDE_VOLUME, bytes, bytes, fn, &h->attitude_volume, &set))) return rc;
     set->cap = H;
-    if ((rc = volume_table_reserve(h, H)) || (rc = ground_reserve(h, g, h->av_ground, h->av_allocs, ground))) return rc;
+    if ((rc = volume_table_reserve(h, H)) || (rc = ground_reserve(h, g, h->attitude_volume, ground))) return rc;
     HIPCHK(h, join_second_stream(h));
     if (!g.m && !on_device) {                                               // a host ground map: staged, and up before the call returns
         const HostPart part = {ground, n2 * 8};
         const void *dev;
-        if ((rc = stage_host(h, h->av_stage, h->av_allocs, &part, 1, true, &dev))) return rc;
+        if ((rc = stage_host(h, h->attitude_volume, &part, 1, true, &dev))) return rc;
         g.dev = (const double *)dev;
     }
     if ((rc = volume_table_rebuild(h, H)) || (rc = set_wait_releases(h, set)) || (rc = ground_write(h, g, flags))) return rc;
@@ -1253,11 +1255,11 @@ VIS int gvom_attitude_volume(gvom_t *h, int64_t map_set_id, const double *ground
     memset(&P, 0, sizeof P);
     P.xy = xy; P.H = H;
     chassis_lengths(h, P.wheelbase, P.track, nullptr);
-    chassis_limits(h->at_chassis, P);
+    chassis_limits(h->chassis.c, P);
     int32_t *counts = part_ptr<int32_t>(set, 2);
     HIPCHK(h, hipMemsetAsync(counts, 0, 32, h->stream));
-    HIPCHK(h, gvom_launch_attitude_volume(h->stream, P, (const int32_t *)h->fp_tab.p, (const uint32_t *)((char *)h->fp_tab.p + h->fp_offs_at), (const double *)h->av_tab.p,
-                                          (const int32_t *)((char *)h->av_tab.p + h->av_wcell_at), g.dev, part_ptr<uint8_t>(set, 0), part_ptr<uint8_t>(set, 1), counts));
+    HIPCHK(h, gvom_launch_attitude_volume(h->stream, P, (const int32_t *)h->footprint.tab.p, (const uint32_t *)((char *)h->footprint.tab.p + h->footprint.offs_at), (const double *)h->attitude_volume.tab.p,
+                                          (const int32_t *)((char *)h->attitude_volume.tab.p + h->attitude_volume.wcell_at), g.dev, part_ptr<uint8_t>(set, 0), part_ptr<uint8_t>(set, 1), counts));
     return product_publish(h, set, product_id);
 }
 
@@ -1276,7 +1278,7 @@ VIS int gvom_body_volume(gvom_t *h, int64_t field_product_id, const float *field
     const char *const fn = "gvom_body_volume";
     int rc;
     if ((rc = check_standing(h, fn, true))) return rc;
-    if (h->bd_S < 1) return refuse(h, fn, "no body is set (gvom_body_set)");
+    if (h->body.S < 1) return refuse(h, fn, "no body is set (gvom_body_set)");
     if (!origin_cells) return refuse(h, fn, "origin_cells must not be NULL");
     if (flags & ~GVOM_ATTITUDE_INFERRED_GROUND) return refuse(h, fn, "unknown flag bits");
     if (!std::isfinite(min_margin)) return refuse(h, fn, "min_margin must be finite");
@@ -1288,7 +1290,7 @@ VIS int gvom_body_volume(gvom_t *h, int64_t field_product_id, const float *field
     for (int k = 0; k < 2; ++k)
         if (origin_cells[k] < -((int64_t)1 << 40) || origin_cells[k] > ((int64_t)1 << 40)) return refuse(h, fn, "an origin beyond 2^40 cells");
     if ((rc = check_side(h, fn))) return rc;
-    const int xy = h->prm.xy_size, H = h->fp_H;
+    const int xy = h->prm.xy_size, H = h->footprint.H;
     const size_t n2 = (size_t)xy * xy;
     if ((rc = check_states(h, fn, H, xy))) return rc;
     Ground g;
@@ -1297,15 +1299,15 @@ VIS int gvom_body_volume(gvom_t *h, int64_t field_product_id, const float *field
     HIPCHK(h, hipSetDevice(h->device));
     DevSet *set = nullptr;
     const size_t bytes = set_bytes(GVOM_PRODUCT_BODY_VOLUME, xy, 0, H);
-    if ((rc = product_acquire(h, GVOM_PRODUCT_BODY_VOLUME, bytes, bytes, fn, &h->bv_allocs, &set))) return rc;
+    if ((rc = product_acquire(h, GVOM_PRODUCT_BODY_VOLUME, bytes, bytes, fn, &h->body_volume, &set))) return rc;
     set->cap = H;
-    if ((rc = volume_table_reserve(h, H)) || (rc = ground_reserve(h, g, h->bv_ground, h->bv_allocs, ground))) return rc;
+    if ((rc = volume_table_reserve(h, H)) || (rc = ground_reserve(h, g, h->body_volume, ground))) return rc;
     const float *fdev = F.f ? part_ptr<const float>(F.f, 0) : field;
     HIPCHK(h, join_second_stream(h));
     if (!on_device && (field || ground)) {                                  // a host field and / or ground map: staged, and up before the call returns
         const HostPart parts[2] = {{field, n2 * (size_t)F.zs * 4}, {ground, n2 * 8}};
         const void *dev[2];
-        if ((rc = stage_host(h, h->bv_stage, h->bv_allocs, parts, 2, true, dev))) return rc;
+        if ((rc = stage_host(h, h->body_volume, parts, 2, true, dev))) return rc;
         if (dev[0]) fdev = (const float *)dev[0];
         if (dev[1]) g.dev = (const double *)dev[1];
     }
@@ -1316,8 +1318,8 @@ VIS int gvom_body_volume(gvom_t *h, int64_t field_product_id, const float *field
     body_params(h, F, min_margin, P);
     int32_t *counts = part_ptr<int32_t>(set, 3);
     HIPCHK(h, hipMemsetAsync(counts, 0, 32, h->stream));
-    HIPCHK(h, gvom_launch_body_volume(h->stream, P, soft_margin, (const int32_t *)((char *)h->av_tab.p + h->av_wcell_at),
-                                      (const double *)((char *)h->at_tab.p + h->at_cs_at), g.dev, (const float *)h->bd_tab.p, fdev,
+    HIPCHK(h, gvom_launch_body_volume(h->stream, P, soft_margin, (const int32_t *)((char *)h->attitude_volume.tab.p + h->attitude_volume.wcell_at),
+                                      (const double *)((char *)h->chassis.tab.p + h->chassis.cs_at), g.dev, (const float *)h->body.tab.p, fdev,
                                       part_ptr<uint8_t>(set, 0), part_ptr<uint8_t>(set, 1), part_ptr<float>(set, 2), counts));
     return product_publish(h, set, product_id);
 }

@@ -138,9 +138,9 @@ int set_wait_releases(gvom_handle *h, DevSet *set)
 }
 
 // the pool path of every product call: a free set of `kind` that holds need_bytes (free sets of the kind that are too small are given
-// up), or a new one of new_bytes counted in *allocs (null: not counted); GVOM_ERR_CAPACITY, in fn's name, with GVOM_MAX_PRODUCT_SETS held
+// up), or a new one of new_bytes counted in the call's record (null: not counted); GVOM_ERR_CAPACITY, in fn's name, with GVOM_MAX_PRODUCT_SETS held
 // (GVOM_MAX_DEVICE_SETS of the stamps of recalled map sets)
-int product_acquire(gvom_handle *h, int kind, size_t need_bytes, size_t new_bytes, const char *fn, int *allocs, DevSet **set)
+int product_acquire(gvom_handle *h, int kind, size_t need_bytes, size_t new_bytes, const char *fn, CallState *call, DevSet **set)
 {
     if ((*set = set_recycle(h->psets, kind, need_bytes))) return GVOM_OK;
     int n = 0;
@@ -151,7 +151,7 @@ int product_acquire(gvom_handle *h, int kind, size_t need_bytes, size_t new_byte
         return GVOM_ERR_CAPACITY;
     }
     const int rc = set_new(h, h->psets, kind, new_bytes, set);
-    if (!rc && allocs) ++*allocs;
+    if (!rc && call) ++call->allocs;
     return rc;
 }
 

@@ -14,7 +14,7 @@ const int64_t VA_FAR = (int64_t)1 << 30;                   // E and W stay below
 int need_atlas(gvom_handle *h, const char *fn)
 {
     if (h->sharded) return refuse(h, fn, "sharded handles are not supported");
-    return h->va_A ? GVOM_OK : refuse(h, fn, "no voxel atlas is configured (gvom_voxel_atlas_configure)");
+    return h->voxel_atlas.A ? GVOM_OK : refuse(h, fn, "no voxel atlas is configured (gvom_voxel_atlas_configure)");
 }
 
 int lg2(int v) { int k = 0; while ((1 << k) < v) ++k; return k; }
@@ -22,19 +22,19 @@ int lg2(int v) { int k = 0; while ((1 << k) < v) ++k; return k; }
 VAtlas atlas_of(const gvom_handle *h)
 {
     VAtlas V;
-    V.pairs = h->va_mem; V.A = h->va_A; V.Z = h->va_Z;
-    V.lgZ = lg2(h->va_Z); V.lgP = lg2(h->va_A / 64);
+    V.pairs = h->voxel_atlas.mem; V.A = h->voxel_atlas.A; V.Z = h->voxel_atlas.Z;
+    V.lgZ = lg2(h->voxel_atlas.Z); V.lgP = lg2(h->voxel_atlas.A / 64);
     return V;
 }
 
-int side(const gvom_handle *h, int k) { return k < 2 ? h->va_A : h->va_Z; }
+int side(const gvom_handle *h, int k) { return k < 2 ? h->voxel_atlas.A : h->voxel_atlas.Z; }
 int window_side(const gvom_handle *h, int k) { return k < 2 ? h->prm.xy_size : h->prm.z_size; }
 bool near_origin(const int64_t o[3]) { return o[0] > -VA_FAR && o[0] < VA_FAR && o[1] > -VA_FAR && o[1] < VA_FAR && o[2] > -VA_FAR && o[2] < VA_FAR; }
 
 // box origin - extent origin on axis k, clamped to +-2^30 (|E| < 2^30: the comparisons cannot overflow)
 int rel_of(const gvom_handle *h, const int64_t B[3], int k)
 {
-    const int64_t e = h->va_E[k];
+    const int64_t e = h->voxel_atlas.E[k];
     if (B[k] >= e + VA_FAR) return (int)VA_FAR;
     if (B[k] <= e - VA_FAR) return -(int)VA_FAR;
     return (int)(B[k] - e);
@@ -68,7 +68,7 @@ int64_t box_frame(const gvom_handle *h, const int64_t B[3], VAtlasBox &X)
     int r[3], lo[3], n[3];
     const int64_t inside = box_clip(h, B, r, lo, n);
     X.rx = r[0]; X.ry = r[1]; X.rz = r[2];
-    X.px = (int)(B[0] & (h->va_A - 1)); X.py = (int)(B[1] & (h->va_A - 1)); X.pz = (int)(B[2] & (h->va_Z - 1));
+    X.px = (int)(B[0] & (h->voxel_atlas.A - 1)); X.py = (int)(B[1] & (h->voxel_atlas.A - 1)); X.pz = (int)(B[2] & (h->voxel_atlas.Z - 1));
     return inside;
 }
 
@@ -76,8 +76,8 @@ int64_t box_frame(const gvom_handle *h, const int64_t B[3], VAtlasBox &X)
 // for NULL before the first integrate
 int box_origin(const gvom_handle *h, const int64_t origin[3], int64_t B[3])
 {
-    if (!h->has_combined || (!origin && h->va_seq == 0)) return GVOM_NO_DATA;
-    for (int k = 0; k < 3; ++k) B[k] = origin ? origin[k] : h->va_last[k];
+    if (!h->has_combined || (!origin && h->voxel_atlas.seq == 0)) return GVOM_NO_DATA;
+    for (int k = 0; k < 3; ++k) B[k] = origin ? origin[k] : h->voxel_atlas.last[k];
     return GVOM_OK;
 }
 
@@ -111,19 +111,19 @@ int move_extent(gvom_handle *h, const int64_t to[3])
     int w[3], s[3];                                                          // per axis: how many storage coordinates entered, from where on
     bool all = false;
     for (int k = 0; k < 3; ++k) {
-        const int64_t d = to[k] - h->va_E[k], ad = d < 0 ? -d : d;
+        const int64_t d = to[k] - h->voxel_atlas.E[k], ad = d < 0 ? -d : d;
         const int size = side(h, k);
         all = all || ad >= size;
         w[k] = (int)std::min<int64_t>(ad, size);
         s[k] = (int)((d > 0 ? to[k] + size - w[k] : to[k]) & (size - 1));
     }
     const int64_t total = (int64_t)A * A * Z;
-    h->va_moved = all ? total : total - (int64_t)(A - w[0]) * (A - w[1]) * (Z - w[2]);
+    h->voxel_atlas.moved = all ? total : total - (int64_t)(A - w[0]) * (A - w[1]) * (Z - w[2]);
     auto slab = [&](int ys, int ny, int zs, int nz, int xs, int wx) {
         VAtlasSlab S;
         S.ys = ys; S.ny = ny; S.zs = zs; S.nz = nz; S.xs = xs; S.wx = wx;
         S.npairs = (uint64_t)ny * (uint64_t)nz * (uint64_t)(A / 64);
-        return gvom_launch_vatlas_move(h->stream, V, S, h->va_cnt);
+        return gvom_launch_vatlas_move(h->stream, V, S, h->voxel_atlas.cnt);
     };
     if (all) HIPCHK(h, slab(0, A, 0, Z, 0, A));
     else {
@@ -132,7 +132,7 @@ int move_extent(gvom_handle *h, const int64_t to[3])
         HIPCHK(h, slab(s[1], w[1], 0, Z, ox, A - w[0]));
         HIPCHK(h, slab(oy, A - w[1], s[2], w[2], ox, A - w[0]));
     }
-    for (int k = 0; k < 3; ++k) h->va_E[k] = to[k];
+    for (int k = 0; k < 3; ++k) h->voxel_atlas.E[k] = to[k];
     return GVOM_OK;
 }
 
@@ -141,41 +141,41 @@ void walk_frame(const gvom_handle *h, ScanParams &P, RayQuery &Q)
 {
     memset(&P, 0, sizeof P);
     memset(&Q, 0, sizeof Q);
-    P.xy = h->va_A; P.zs = h->va_Z;
+    P.xy = h->voxel_atlas.A; P.zs = h->voxel_atlas.Z;
     P.xy_res = h->prm.xy_resolution; P.z_res = h->prm.z_resolution;
     P.drcp[0] = 1.0 / h->prm.xy_resolution; P.drcp[1] = 1.0 / h->prm.z_resolution;
     P.fastdiv = h->tune_fastdiv == 0 ? 0 : h->fastdiv_ok;
     P.f32_sqrt = h->f32_sqrt ? 1 : 0;
     bool far = false;
     for (int k = 0; k < 3; ++k) {
-        P.origin[k] = (double)h->va_E[k];
-        P.om[k] = (int)(h->va_E[k] & (side(h, k) - 1));
-        far = far || h->va_E[k] <= -((int64_t)1 << 24) || h->va_E[k] >= ((int64_t)1 << 24);
+        P.origin[k] = (double)h->voxel_atlas.E[k];
+        P.om[k] = (int)(h->voxel_atlas.E[k] & (side(h, k) - 1));
+        far = far || h->voxel_atlas.E[k] <= -((int64_t)1 << 24) || h->voxel_atlas.E[k] >= ((int64_t)1 << 24);
     }
     Q.lit = far ? 1 : 0;                                                    // (Z <= A: the integer extent test holds for every near origin)
-    Q.cap = (uint32_t)h->va_A + (uint32_t)h->va_Z;
+    Q.cap = (uint32_t)h->voxel_atlas.A + (uint32_t)h->voxel_atlas.Z;
 }
 
 // the sensor model's largest finite |direction| and |offset| per axis, read back once per gvom_sensor_model_set (which drains the stream
 // and leaves the model complete in device memory).  A pixel with a non-finite entry casts no beam: it bounds nothing.
 int model_bounds(gvom_handle *h)
 {
-    if (h->va_model_gen == h->ri_gen) return GVOM_OK;
-    const size_t n = (size_t)h->ri_H * h->ri_W;
+    if (h->voxel_atlas.model_gen == h->range_image.gen) return GVOM_OK;
+    const size_t n = (size_t)h->range_image.H * h->range_image.W;
     std::vector<double> m(n * 6);
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    HIPCHK(h, hipMemcpy(m.data(), h->ri_model.p, n * 48, hipMemcpyDeviceToHost));
-    for (int e = 0; e < 3; ++e) h->va_dmax[e] = h->va_omax[e] = 0.0;
+    HIPCHK(h, hipMemcpy(m.data(), h->range_image.model.p, n * 48, hipMemcpyDeviceToHost));
+    for (int e = 0; e < 3; ++e) h->voxel_atlas.dmax[e] = h->voxel_atlas.omax[e] = 0.0;
     const double *d = m.data(), *o = d + n * 3;
     for (size_t i = 0; i < n; ++i) {
         bool fin = true;
         for (int e = 0; e < 3; ++e) fin = fin && std::isfinite(d[3 * i + e]) && std::isfinite(o[3 * i + e]);
         for (int e = 0; fin && e < 3; ++e) {
-            h->va_dmax[e] = std::max(h->va_dmax[e], fabs(d[3 * i + e]));
-            h->va_omax[e] = std::max(h->va_omax[e], fabs(o[3 * i + e]));
+            h->voxel_atlas.dmax[e] = std::max(h->voxel_atlas.dmax[e], fabs(d[3 * i + e]));
+            h->voxel_atlas.omax[e] = std::max(h->voxel_atlas.omax[e], fabs(o[3 * i + e]));
         }
     }
-    h->va_model_gen = h->ri_gen;
+    h->voxel_atlas.model_gen = h->range_image.gen;
     return GVOM_OK;
 }
 
@@ -192,15 +192,15 @@ int64_t pose_box(const gvom_handle *h, const double *c, double max_range, int32_
     for (int e = 0; e < 8; ++e) box[e] = e >= 3 && e < 6 ? 1 : 0;
     for (int e = 0; e < 12; ++e)
         if (!std::isfinite(c[e])) return 1;                                  // an invalid pose casts no beam
-    const double cap = (double)h->va_A + h->va_Z + 1.0;
+    const double cap = (double)h->voxel_atlas.A + h->voxel_atlas.Z + 1.0;
     int64_t bits = 1;
     for (int e = 0; e < 3; ++e) {
         double R = 0.0;
-        for (int j = 0; j < 3; ++j) R += fabs(c[4 * e + j]) * (max_range * h->va_dmax[j] + h->va_omax[j]);
+        for (int j = 0; j < 3; ++j) R += fabs(c[4 * e + j]) * (max_range * h->voxel_atlas.dmax[j] + h->voxel_atlas.omax[j]);
         R = R * (1.0 + 1e-9) + 1e-300;                                       // (the sum's own rounding)
         const double res = e < 2 ? h->prm.xy_resolution : h->prm.z_resolution, t = c[4 * e + 3];
         const int size = side(h, e);
-        const double E = (double)h->va_E[e];
+        const double E = (double)h->voxel_atlas.E[e];
         const double lo_w = (t - R) / res, hi_w = (t + R) / res;
         const double mag = std::max(std::max(fabs(lo_w), fabs(hi_w)), fabs(E) + size);
         const double m = 3.0 + (cap + 4.0) * mag * 0x1p-23;
@@ -245,23 +245,23 @@ VIS int gvom_voxel_atlas_configure(gvom_t *h, int32_t cells, int32_t levels, int
         if (fixed_origin && !near_origin(fixed_origin)) return refuse(h, fn, "an origin at or beyond 2^30 voxels");
     }
     HIPCHK(h, hipSetDevice(h->device));
-    if (cells != h->va_A || (cells && levels != h->va_Z)) {                 // another size, or none: the kernels that use the old one first
+    if (cells != h->voxel_atlas.A || (cells && levels != h->voxel_atlas.Z)) {   // another size, or none: the kernels that use the old one first
         HIPCHK(h, hipStreamSynchronize(h->stream));
-        if (h->va_mem) HIPCHK(h, hipFree(h->va_mem));
-        h->va_mem = nullptr; h->va_A = h->va_Z = 0;
+        if (h->voxel_atlas.mem) HIPCHK(h, hipFree(h->voxel_atlas.mem.p));
+        h->voxel_atlas.mem.p = nullptr; h->voxel_atlas.A = h->voxel_atlas.Z = 0;
         if (cells == 0) return GVOM_OK;
-        HIPCHK(h, hipMalloc((void **)&h->va_mem, gvom_vatlas_bytes(cells, levels)));
-        ++h->va_allocs;
+        HIPCHK(h, hipMalloc((void **)&h->voxel_atlas.mem.p, gvom_vatlas_bytes(cells, levels)));
+        ++h->voxel_atlas.allocs;
     }
     if (cells == 0) return GVOM_OK;
-    if (!h->va_cnt) { HIPCHK(h, hipMalloc((void **)&h->va_cnt, 256)); ++h->va_allocs; }
-    if (!h->va_pin) HIPCHK(h, hipHostMalloc((void **)&h->va_pin, 256, hipHostMallocDefault));
-    h->va_A = cells; h->va_Z = levels; h->va_follow = mode == GVOM_ATLAS_FOLLOW ? 1 : 0;
-    for (int k = 0; k < 3; ++k) { h->va_E[k] = fixed_origin ? fixed_origin[k] : 0; h->va_last[k] = 0; }
-    h->va_seq = h->va_outside = h->va_moved = 0;
+    if (!h->voxel_atlas.cnt) { HIPCHK(h, hipMalloc((void **)&h->voxel_atlas.cnt.p, 256)); ++h->voxel_atlas.allocs; }
+    if (!h->voxel_atlas.pin) HIPCHK(h, hipHostMalloc((void **)&h->voxel_atlas.pin.p, 256, hipHostMallocDefault));
+    h->voxel_atlas.A = cells; h->voxel_atlas.Z = levels; h->voxel_atlas.follow = mode == GVOM_ATLAS_FOLLOW ? 1 : 0;
+    for (int k = 0; k < 3; ++k) { h->voxel_atlas.E[k] = fixed_origin ? fixed_origin[k] : 0; h->voxel_atlas.last[k] = 0; }
+    h->voxel_atlas.seq = h->voxel_atlas.outside = h->voxel_atlas.moved = 0;
     HIPCHK(h, join_second_stream(h));
-    HIPCHK(h, hipMemsetAsync(h->va_cnt, 0, 256, h->stream));
-    HIPCHK(h, hipMemsetAsync(h->va_mem, 0, gvom_vatlas_bytes(cells, levels), h->stream));
+    HIPCHK(h, hipMemsetAsync(h->voxel_atlas.cnt, 0, 256, h->stream));
+    HIPCHK(h, hipMemsetAsync(h->voxel_atlas.mem, 0, gvom_vatlas_bytes(cells, levels), h->stream));
     return GVOM_OK;
 }
 
@@ -273,9 +273,9 @@ VIS int gvom_voxel_atlas_clear(gvom_t *h)
     if (rc) return rc;
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, join_second_stream(h));
-    HIPCHK(h, hipMemsetAsync(h->va_cnt, 0, 256, h->stream));
-    HIPCHK(h, hipMemsetAsync(h->va_mem, 0, gvom_vatlas_bytes(h->va_A, h->va_Z), h->stream));
-    h->va_outside = h->va_moved = 0;
+    HIPCHK(h, hipMemsetAsync(h->voxel_atlas.cnt, 0, 256, h->stream));
+    HIPCHK(h, hipMemsetAsync(h->voxel_atlas.mem, 0, gvom_vatlas_bytes(h->voxel_atlas.A, h->voxel_atlas.Z), h->stream));
+    h->voxel_atlas.outside = h->voxel_atlas.moved = 0;
     return GVOM_OK;
 }
 
@@ -293,19 +293,19 @@ VIS int gvom_voxel_atlas_integrate(gvom_t *h)
     const Fused &F = *cur;
     int64_t to[3];
     for (int k = 0; k < 3; ++k) to[k] = F.origin[k] + window_side(h, k) / 2 - side(h, k) / 2;
-    if (h->va_follow && !near_origin(to)) return refuse(h, fn, "the extent would lie at or beyond 2^30 voxels");
+    if (h->voxel_atlas.follow && !near_origin(to)) return refuse(h, fn, "the extent would lie at or beyond 2^30 voxels");
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, join_second_stream(h));
-    HIPCHK(h, hipMemsetAsync(h->va_cnt, 0, 64, h->stream));                 // the counters of the last integrate and its move
-    h->va_moved = 0;
-    if (h->va_follow && (rc = move_extent(h, to))) return rc;
+    HIPCHK(h, hipMemsetAsync(h->voxel_atlas.cnt, 0, 64, h->stream));        // the counters of the last integrate and its move
+    h->voxel_atlas.moved = 0;
+    if (h->voxel_atlas.follow && (rc = move_extent(h, to))) return rc;
     const VAtlas V = atlas_of(h);
     VAtlasWindow D;
     memset(&D, 0, sizeof D);
     int r[3], lo[3], n[3];
     const int64_t inside = box_clip(h, F.origin, r, lo, n);
     D.rx = r[0]; D.ry = r[1]; D.rz = r[2];
-    D.pex = (int)(h->va_E[0] & (V.A - 1)); D.pey = (int)(h->va_E[1] & (V.A - 1)); D.pez = (int)(h->va_E[2] & (V.Z - 1));
+    D.pex = (int)(h->voxel_atlas.E[0] & (V.A - 1)); D.pey = (int)(h->voxel_atlas.E[1] & (V.A - 1)); D.pez = (int)(h->voxel_atlas.E[2] & (V.Z - 1));
     if (inside > 0) {
         D.y0 = lo[1]; D.ny = n[1]; D.z0 = lo[2]; D.nz = n[2];
         const int s0 = (r[0] + lo[0] + D.pex) & (V.A - 1);                  // storage column of the first window column inside the extent
@@ -317,10 +317,10 @@ VIS int gvom_voxel_atlas_integrate(gvom_t *h)
     }
     OccParams P;
     occ_params(h, F, P);
-    ++h->va_seq;
-    for (int k = 0; k < 3; ++k) h->va_last[k] = F.origin[k];
-    h->va_outside = (int64_t)h->prm.xy_size * h->prm.xy_size * h->prm.z_size - inside;
-    HIPCHK(h, gvom_launch_vatlas_merge(h->stream, V, D, P, F.state, F.tags, h->va_cnt));
+    ++h->voxel_atlas.seq;
+    for (int k = 0; k < 3; ++k) h->voxel_atlas.last[k] = F.origin[k];
+    h->voxel_atlas.outside = (int64_t)h->prm.xy_size * h->prm.xy_size * h->prm.z_size - inside;
+    HIPCHK(h, gvom_launch_vatlas_merge(h->stream, V, D, P, F.state, F.tags, h->voxel_atlas.cnt));
     return GVOM_OK;
 }
 
@@ -331,12 +331,12 @@ VIS int gvom_voxel_atlas_counts(gvom_t *h, int64_t out[11])
     const int rc = need_atlas(h, "gvom_voxel_atlas_counts");
     if (rc) return rc;
     HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, hipMemcpyAsync(h->va_pin, h->va_cnt, 128, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->voxel_atlas.pin, h->voxel_atlas.cnt, 128, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    for (int k = 0; k < 5; ++k) out[k] = (int64_t)h->va_pin[k];
-    out[5] = h->va_outside; out[6] = h->va_moved;
-    out[7] = (int64_t)h->va_pin[VA_CNT_MOVED_OBS]; out[8] = (int64_t)h->va_pin[VA_CNT_OBSERVED]; out[9] = (int64_t)h->va_pin[VA_CNT_OCCUPIED];
-    out[10] = h->va_seq;
+    for (int k = 0; k < 5; ++k) out[k] = (int64_t)h->voxel_atlas.pin[k];
+    out[5] = h->voxel_atlas.outside; out[6] = h->voxel_atlas.moved;
+    out[7] = (int64_t)h->voxel_atlas.pin[VA_CNT_MOVED_OBS]; out[8] = (int64_t)h->voxel_atlas.pin[VA_CNT_OBSERVED]; out[9] = (int64_t)h->voxel_atlas.pin[VA_CNT_OCCUPIED];
+    out[10] = h->voxel_atlas.seq;
     return GVOM_OK;
 }
 
@@ -355,12 +355,12 @@ VIS int gvom_voxel_atlas_box(gvom_t *h, const int64_t origin[3], int64_t *produc
     HIPCHK(h, hipSetDevice(h->device));
     DevSet *set = nullptr;
     const size_t bytes = set_bytes(GVOM_PRODUCT_VOXEL_BOX, xy, zs, 0);
-    if ((rc = product_acquire(h, GVOM_PRODUCT_VOXEL_BOX, bytes, bytes, fn, &h->va_allocs, &set))) return rc;
+    if ((rc = product_acquire(h, GVOM_PRODUCT_VOXEL_BOX, bytes, bytes, fn, &h->voxel_atlas, &set))) return rc;
     HIPCHK(h, join_second_stream(h));
     if ((rc = set_wait_releases(h, set))) return rc;
     VAtlasBox X;
     X.outside = (int)((int64_t)xy * xy * zs - box_frame(h, B, X));
-    X.seq = (int)std::min<int64_t>(h->va_seq, INT32_MAX);
+    X.seq = (int)std::min<int64_t>(h->voxel_atlas.seq, INT32_MAX);
     int32_t *counts = part_ptr<int32_t>(set, 1);
     HIPCHK(h, hipMemsetAsync(counts, 0, 16, h->stream));
     HIPCHK(h, gvom_launch_vatlas_box(h->stream, atlas_of(h), X, part_ptr<uint8_t>(set, 0), counts));
@@ -370,7 +370,7 @@ VIS int gvom_voxel_atlas_box(gvom_t *h, const int64_t origin[3], int64_t *produc
 // What the CURRENT fused map contradicts of what the atlas remembers (include/gvom_hip.h "voxel atlas changes"), read-only on both:
 // k_vchange_planes, _codes and _columns (gvom_voxel_changes.hip) on the handle's stream behind whatever produced that map and the
 // integrates before the call; the columns kernel leaves the labelling's work buffer as k_frontier_mark does, so everything behind it is
-// frontier_solve (gvom_product_calls.hip) on a work buffer of the handle's own (vchg.work), with k_vchange_clusters in front of the
+// frontier_solve (gvom_product_calls.hip) on a work buffer of the handle's own (voxel_atlas.solve.work), with k_vchange_clusters in front of the
 // publication.  Like gvom_frontiers this call WAITS.
 VIS int gvom_voxel_atlas_changes(gvom_t *h, int mask, int32_t min_cells, int32_t max_clusters, int64_t *product_id, int64_t origin_out[3],
                                  int64_t info[4])
@@ -392,13 +392,13 @@ VIS int gvom_voxel_atlas_changes(gvom_t *h, int mask, int32_t min_cells, int32_t
     HIPCHK(h, hipSetDevice(h->device));
     DevSet *set = nullptr;
     const size_t bytes = set_bytes(GVOM_PRODUCT_VOXEL_CHANGES, xy, zs, max_clusters);
-    if ((rc = product_acquire(h, GVOM_PRODUCT_VOXEL_CHANGES, bytes, bytes, fn, &h->va_allocs, &set))) return rc;
+    if ((rc = product_acquire(h, GVOM_PRODUCT_VOXEL_CHANGES, bytes, bytes, fn, &h->voxel_atlas, &set))) return rc;
     set->cap = max_clusters;
     FrWork W;
-    if ((rc = frontier_work(h, h->vchg, xy, h->va_allocs, &W))) return rc;
+    if ((rc = frontier_work(h, h->voxel_atlas, xy, &W))) return rc;
     const size_t planes_at = 256, lohi_at = planes_at + align256(gvom_vchange_planes_bytes(xy, zs)), d_at = lohi_at + align256(n2 * 4);
-    if ((rc = stage_buf(h, h->va_chg, d_at + n2 * 4, h->va_allocs))) return rc;            // (no kernel of an earlier call is left: every call waits)
-    char *const work = (char *)h->va_chg.p;
+    if ((rc = stage_buf(h, h->voxel_atlas, h->voxel_atlas.chg, d_at + n2 * 4))) return rc;   // (no kernel of an earlier call is left: every call waits)
+    char *const work = (char *)h->voxel_atlas.chg.p;
     unsigned long long *const cnt = (unsigned long long *)work;
     void *const planes = work + planes_at;
     uint32_t *const lohi = (uint32_t *)(work + lohi_at);
@@ -416,10 +416,10 @@ VIS int gvom_voxel_atlas_changes(gvom_t *h, int mask, int32_t min_cells, int32_t
     HIPCHK(h, gvom_launch_vchange_planes(h->stream, atlas_of(h), X, P, F.state, F.tags, planes, cnt));
     HIPCHK(h, gvom_launch_vchange_codes(h->stream, xy, zs, planes, part_ptr<uint8_t>(set, 5)));
     HIPCHK(h, gvom_launch_vchange_columns(h->stream, xy, zs, mask, max_clusters, planes, cols, lohi, W.L, W.count, W.fl, W.cnt + FR_CNT_CELLS, D, rows4));
-    const int seq = (int)std::min<int64_t>(h->va_seq, INT32_MAX);
+    const int seq = (int)std::min<int64_t>(h->voxel_atlas.seq, INT32_MAX);
     for (int k = 0; k < 3; ++k) set->origin[k] = F.origin[k];
     for (int k = 0; origin_out && k < 3; ++k) origin_out[k] = F.origin[k];
-    return frontier_solve(h, fn, h->vchg, xy, D, W, min_cells, max_clusters, set, product_id, info, [&]() {
+    return frontier_solve(h, fn, h->voxel_atlas.solve, xy, D, W, min_cells, max_clusters, set, product_id, info, [&]() {
         return gvom_launch_vchange_clusters(h->stream, xy, max_clusters, seq, part_ptr<const int32_t>(set, 2), cols, lohi, W.cnt + FR_CNT_KEPT, cnt, rows4,
                                             part_ptr<int32_t>(set, 3));
     });
@@ -441,15 +441,15 @@ VIS int gvom_voxel_atlas_raycast(gvom_t *h, const float *from, int64_t K, const 
     HIPCHK(h, hipSetDevice(h->device));
     DevSet *set = nullptr;
     const size_t bytes = set_bytes(GVOM_PRODUCT_VOXEL_ATLAS_RAYS, 0, 0, n);
-    if ((rc = product_acquire(h, GVOM_PRODUCT_VOXEL_ATLAS_RAYS, bytes, bytes, fn, &h->va_allocs, &set))) return rc;
+    if ((rc = product_acquire(h, GVOM_PRODUCT_VOXEL_ATLAS_RAYS, bytes, bytes, fn, &h->voxel_atlas, &set))) return rc;
     set->cap = n;
     ScanParams P;
     RayQuery Q;
     walk_frame(h, P, Q);
-    if ((rc = rays_fill(h, h->va_stage, h->va_allocs, from, K, to, n, on_device, flags, Q))) return rc;
+    if ((rc = rays_fill(h, h->voxel_atlas, from, K, to, n, on_device, flags, Q))) return rc;
     if ((rc = set_wait_releases(h, set))) return rc;
     HIPCHK(h, gvom_launch_vatlas_raycast(h->stream, P, Q, atlas_of(h), part_ptr<int32_t>(set, 0), part_ptr<float>(set, 1), part_ptr<int32_t>(set, 2)));
-    return publish_at(h, set, h->va_E, extent_voxels, product_id, true);
+    return publish_at(h, set, h->voxel_atlas.E, extent_voxels, product_id, true);
 }
 
 // gvom_score_viewpoints on the atlas: the selected beams of the handle's sensor model cast from K poses by k_vatlas_viewpoints, a batch of
@@ -466,7 +466,7 @@ VIS int gvom_voxel_atlas_score_viewpoints(gvom_t *h, const double *poses, int64_
     int rc = need_atlas(h, fn);
     if (rc) return rc;
     ViewBeams beams;
-    if ((rc = check_views(h, fn, poses, K, max_range, stride_h, stride_w, flags, (int64_t)h->va_A + h->va_Z, "cells + levels", &beams))) return rc;
+    if ((rc = check_views(h, fn, poses, K, max_range, stride_h, stride_w, flags, (int64_t)h->voxel_atlas.A + h->voxel_atlas.Z, "cells + levels", &beams))) return rc;
     if (!h->has_combined) return GVOM_NO_DATA;
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, join_second_stream(h));
@@ -488,11 +488,11 @@ VIS int gvom_voxel_atlas_score_viewpoints(gvom_t *h, const double *poses, int64_
     }
     DevSet *set = nullptr;
     const size_t bytes = set_bytes(GVOM_PRODUCT_VOXEL_ATLAS_VIEWPOINTS, 0, 0, K);
-    if ((rc = product_acquire(h, GVOM_PRODUCT_VOXEL_ATLAS_VIEWPOINTS, bytes, bytes, fn, &h->va_allocs, &set))) return rc;
+    if ((rc = product_acquire(h, GVOM_PRODUCT_VOXEL_ATLAS_VIEWPOINTS, bytes, bytes, fn, &h->voxel_atlas, &set))) return rc;
     set->cap = K;
     size_t bm_words;                                                        // every bitmap as large as the largest box of the call
     const int64_t batch = views_batch(h, most, K, &bm_words);
-    if ((rc = stage_buf(h, h->va_bitmaps, (size_t)batch * bm_words * 4, h->va_allocs))) return rc;
+    if ((rc = stage_buf(h, h->voxel_atlas, h->voxel_atlas.bitmaps, (size_t)batch * bm_words * 4))) return rc;
     ScanParams P;
     RayQuery R;
     walk_frame(h, P, R);
@@ -500,18 +500,18 @@ VIS int gvom_voxel_atlas_score_viewpoints(gvom_t *h, const double *poses, int64_
     views_fill(h, R, beams, K, max_range, stride_h, stride_w, flags, bm_words, Q);
     const HostPart parts[2] = {{on_device ? nullptr : poses, (size_t)K * 96}, {boxes.data(), (size_t)K * 32}};
     const void *dev[2];
-    if ((rc = stage_host(h, h->va_stage, h->va_allocs, parts, 2, true, dev))) return rc;
+    if ((rc = stage_host(h, h->voxel_atlas, parts, 2, true, dev))) return rc;
     Q.poses = on_device ? poses : (const double *)dev[0];
     const int32_t *dboxes = (const int32_t *)dev[1];
     if ((rc = set_wait_releases(h, set))) return rc;
     const VAtlas V = atlas_of(h);
     int32_t *rows = part_ptr<int32_t>(set, 0);
-    rc = views_run(h, h->va_bitmaps, Q, batch, rows,
-                   [&](int nk) { return gvom_launch_vatlas_viewpoints(h->stream, P, Q, V, nk, dboxes, (uint32_t *)h->va_bitmaps.p, rows); },
+    rc = views_run(h, h->voxel_atlas.bitmaps, Q, batch, rows,
+                   [&](int nk) { return gvom_launch_vatlas_viewpoints(h->stream, P, Q, V, nk, dboxes, (uint32_t *)h->voxel_atlas.bitmaps.p, rows); },
                    [&]() { return gvom_launch_vatlas_viewpoint_best(h->stream, P, Q, V, rows, part_ptr<int32_t>(set, 1)); });
     if (rc) return rc;
-    h->va_last_batch = (int)batch;
-    return publish_at(h, set, h->va_E, extent_voxels, product_id, true);
+    h->voxel_atlas.last_batch = (int)batch;
+    return publish_at(h, set, h->voxel_atlas.E, extent_voxels, product_id, true);
 }
 
 // gvom_score_alignments on the atlas: k_vatlas_align_field turns the box at B into the class grid -- in the handle's class-grid buffer,
@@ -534,20 +534,20 @@ VIS int gvom_voxel_atlas_score_alignments(gvom_t *h, const float *cloud, int64_t
     HIPCHK(h, hipSetDevice(h->device));
     DevSet *set = nullptr;
     const size_t bytes = set_bytes(GVOM_PRODUCT_VOXEL_ATLAS_ALIGNMENT, 0, 0, K);
-    if ((rc = product_acquire(h, GVOM_PRODUCT_VOXEL_ATLAS_ALIGNMENT, bytes, bytes, fn, &h->va_allocs, &set))) return rc;
+    if ((rc = product_acquire(h, GVOM_PRODUCT_VOXEL_ATLAS_ALIGNMENT, bytes, bytes, fn, &h->voxel_atlas, &set))) return rc;
     set->cap = K;
-    if ((rc = stage_buf(h, h->al_grid, gb, h->al_allocs))) return rc;
+    if ((rc = stage_buf(h, h->alignment, h->alignment.grid, gb))) return rc;
     AlignParams P;
     memset(&P, 0, sizeof P);
     metric_frame(h, h->fused[h->cur], P);
     for (int k = 0; k < 3; ++k) P.origin[k] = (double)B[k];
     const float *cdev;
     const double *tdev;
-    if ((rc = align_fill(h, h->va_stage, h->va_allocs, cloud, n, transforms, K, on_device, dilate, weights, P, &cdev, &tdev))) return rc;
+    if ((rc = align_fill(h, h->voxel_atlas, cloud, n, transforms, K, on_device, dilate, weights, P, &cdev, &tdev))) return rc;
     if ((rc = set_wait_releases(h, set))) return rc;
     VAtlasBox X;
     box_frame(h, B, X);
-    uint32_t *const grid = (uint32_t *)h->al_grid.p;
+    uint32_t *const grid = (uint32_t *)h->alignment.grid.p;
     HIPCHK(h, gvom_launch_vatlas_align_field(h->stream, atlas_of(h), X, dilate, grid));
     HIPCHK(h, gvom_launch_align_grid(h->stream, P, cdev, tdev, grid, part_ptr<int32_t>(set, 0), part_ptr<int32_t>(set, 1)));
     return publish_at(h, set, B, origin_out, product_id);
@@ -579,7 +579,7 @@ VIS int gvom_voxel_atlas_distance_field(gvom_t *h, const int64_t origin[3], doub
     const int64_t hxy = distance_halo(F.a, F.cap2), hz = distance_halo(F.b, F.cap2);
     if (hxy > GVOM_VDIST_MAX_HALO || hz > GVOM_VDIST_MAX_HALO) return refuse(h, fn, "max_distance reaches further than 32767 voxels", GVOM_ERR_CAPACITY);
     F.B.outside = (int)((int64_t)xy * xy * zs - box_frame(h, B, F.B));
-    F.B.seq = (int)std::min<int64_t>(h->va_seq, INT32_MAX);
+    F.B.seq = (int)std::min<int64_t>(h->voxel_atlas.seq, INT32_MAX);
     F.unknown = (flags & GVOM_DISTANCE_UNKNOWN_BLOCKS) ? 1 : 0;
     F.hxy = (int)hxy; F.kx = (int)((hxy + 63) / 64) + 1; F.nw = (xy + 63) / 64;
     // rows of the extent (and the one beyond it) below and above the box, as far as the halo reaches: (r + f) below, (size + f) - (r + n) above
@@ -589,23 +589,23 @@ VIS int gvom_voxel_atlas_distance_field(gvom_t *h, const int64_t origin[3], doub
         const int64_t hi = e0 < n + halo ? std::max<int64_t>(0, std::min<int64_t>(halo, e1 - n)) : 0;
         *below = (int)lo; *all = (int)(lo + n + hi);
     };
-    grown(F.B.ry, xy, h->va_A, hxy, &F.hby, &F.nyg);
-    grown(F.B.rz, zs, h->va_Z, hz, &F.hbz, &F.nzg);
+    grown(F.B.ry, xy, h->voxel_atlas.A, hxy, &F.hby, &F.nyg);
+    grown(F.B.rz, zs, h->voxel_atlas.Z, hz, &F.hbz, &F.nzg);
     const size_t rows_bytes = align256(gvom_vdist_rows_bytes(F)), work_bytes = rows_bytes + gvom_vdist_cols_bytes(F);
-    if (work_bytes > ((size_t)h->tune_vd_mb << 20))
+    if (work_bytes > ((size_t)h->voxel_atlas.mb << 20))
         return refuse(h, fn, "the working buffers of this cap need " + std::to_string((work_bytes >> 20) + 1) + " MB, more than \"voxel_distance_mb\" allows", GVOM_ERR_CAPACITY);
     HIPCHK(h, hipSetDevice(h->device));
     DevSet *set = nullptr;
     const size_t bytes = set_bytes(GVOM_PRODUCT_VOXEL_DISTANCE, xy, zs, 0);
-    if ((rc = product_acquire(h, GVOM_PRODUCT_VOXEL_DISTANCE, bytes, bytes, fn, &h->va_allocs, &set))) return rc;
+    if ((rc = product_acquire(h, GVOM_PRODUCT_VOXEL_DISTANCE, bytes, bytes, fn, &h->voxel_atlas, &set))) return rc;
     HIPCHK(h, join_second_stream(h));
-    if (h->va_dist.bytes < work_bytes) HIPCHK(h, hipStreamSynchronize(h->stream));         // the passes that still run on the buffer it outgrows
-    if ((rc = stage_buf(h, h->va_dist, work_bytes, h->va_allocs))) return rc;
+    if (h->voxel_atlas.dist.bytes < work_bytes) HIPCHK(h, hipStreamSynchronize(h->stream));   // the passes that still run on the buffer it outgrows
+    if ((rc = stage_buf(h, h->voxel_atlas, h->voxel_atlas.dist, work_bytes))) return rc;
     if ((rc = set_wait_releases(h, set))) return rc;
     int32_t *counts = part_ptr<int32_t>(set, 1);
     HIPCHK(h, hipMemsetAsync(counts, 0, 16, h->stream));
-    HIPCHK(h, gvom_launch_vdist_field(h->stream, atlas_of(h), F, h->va_dist.p, part_ptr<float>(set, 0), counts));
-    h->vd_halo[0] = (int)hxy; h->vd_halo[1] = (int)hz;
+    HIPCHK(h, gvom_launch_vdist_field(h->stream, atlas_of(h), F, h->voxel_atlas.dist.p, part_ptr<float>(set, 0), counts));
+    h->voxel_atlas.halo[0] = (int)hxy; h->voxel_atlas.halo[1] = (int)hz;
     return publish_at(h, set, B, origin_out, product_id);
 }
 
@@ -627,14 +627,14 @@ VIS int gvom_voxel_distance_sample(gvom_t *h, int64_t field_product_id, const fl
     HIPCHK(h, hipSetDevice(h->device));
     DevSet *set = nullptr;
     const size_t bytes = set_bytes(GVOM_PRODUCT_VOXEL_DISTANCE_SAMPLES, 0, 0, n);
-    if ((rc = product_acquire(h, GVOM_PRODUCT_VOXEL_DISTANCE_SAMPLES, bytes, bytes, fn, &h->va_allocs, &set))) return rc;
+    if ((rc = product_acquire(h, GVOM_PRODUCT_VOXEL_DISTANCE_SAMPLES, bytes, bytes, fn, &h->voxel_atlas, &set))) return rc;
     set->cap = n;
     const float *pdev = points;
     HIPCHK(h, join_second_stream(h));
     if (!on_device) {                                                       // host points: staged, and up before the call returns
         const HostPart parts[1] = {{points, (size_t)n * 12}};
         const void *dev[1];
-        if ((rc = stage_host(h, h->va_stage, h->va_allocs, parts, 1, true, dev))) return rc;
+        if ((rc = stage_host(h, h->voxel_atlas, parts, 1, true, dev))) return rc;
         pdev = (const float *)dev[0];
     }
     if ((rc = set_wait_releases(h, set))) return rc;
